@@ -3,7 +3,13 @@
 dense block.  One "step" = one complete node solve (cold start -> optimal to gaptol = feastol = 1e-5) of the planted
 instance of BASELINE.md section 3, with A already resident in HBM (generated on the device).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 500] [--m 1000] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 500] [--m 1000] [--dump-outputs DIR] [--full [--no-cpu] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps and prints the line: its headline fields and the roofline of the timed
+assemblies.  Everything that takes runs of its own - the measured clock and matrix peak, the phase anatomy, the CPU
+baseline, the other sizes, densities and start modes, the boundary and B&B legs - runs only with --full.
+--dump-outputs DIR writes what the last timed solve returned (y, X, Z and the status / objective / residual scalars) as
+DIR/<name>.npy in float64, so that two builds can be compared output for output; inputs depend on the arguments only.
 
 N > 1: one process per GPU.  When the driver has already started the ranks (torch.distributed.run: RANK / LOCAL_RANK /
 WORLD_SIZE in the environment) this process is one of them and checks that --gpus equals WORLD_SIZE.  Started plainly as
@@ -188,10 +194,14 @@ def parse_args(argv=None):
     ap.add_argument("--n", type=int, default=500)
     ap.add_argument("--m", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=20240)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: measured clock / peak, phases, CPU baseline, other sizes and legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed solve as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--density", type=float, default=0.1,
                     help="density of the matrices in the `density` sub-object (SURVEY.md 8(d): 0.1); the headline run is dense")
-    ap.add_argument("--no-extras", action="store_true", help="skip the t1 / sdpi_boundary / warm_start / phases sub-objects")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the t1 / sdpi_boundary / warm_start / phases sub-objects")
     ap.add_argument("--shard-matrices", choices=["auto", "on", "off"], default="auto",
                     help="N > 1: constraint matrices sharded by variable (auto: when the replicated matrices would not fit)")
     ap.add_argument("--schur-form", choices=["auto", "cols", "rows", "vars"], default="auto",
@@ -315,6 +325,27 @@ def dry_run_rank(args):
                           "local_rank": int(os.environ.get("LOCAL_RANK", "-1")), "master_addr": os.environ.get("MASTER_ADDR")}))
     dist.destroy_process_group()
     return 0
+
+
+# ---- outputs of the timed path (--dump-outputs) --------------------------------------------------------------------------
+
+DUMP_MAX_ENTRIES = 1 << 21        # per array: 16 MB of float64; X, Z and y stay below 64 MB together at every size
+
+
+def dump_outputs(dirname, solver, info):
+    """What a caller of the timed solve receives, as float64 .npy files: y (m), X and Z of the block (n x n, row-major) and the
+    scalars of the info record that do not depend on timing.  An array of more than DUMP_MAX_ENTRIES entries is replaced by the
+    entries at a fixed, seeded sample of its flat indices (sorted; the same for every run with the same shape), named <name>_sample."""
+    os.makedirs(dirname, exist_ok=True)
+    scalars = ("status", "iterations", "pobj", "dobj", "pinf", "dinf", "dabs", "gap", "mu", "tau", "kappa")
+    arrays = {"y": solver.y(), "X": solver.X(0), "Z": solver.Z(0),
+              "info": np.array([float(getattr(info, k)) for k in scalars])}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ENTRIES:
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, size=DUMP_MAX_ENTRIES, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ---- sub-benchmarks of the one JSON line ---------------------------------------------------------------------------------
@@ -706,6 +737,9 @@ def main():
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
+        return 2
     if not in_launcher and args.gpus > 1:
         return launch_ranks(args, argv)            # parent: no GPU call has been made in this process
     rank = int(os.environ.get("RANK", "0"))
@@ -794,14 +828,16 @@ def main():
         elapsed = float(t.item())
 
     last = infos[-1]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, last)
     ok = all(i.status == 0 for i in infos) and abs(last.dobj - opt) <= 1e-5 * (1 + abs(opt))
     iters = sum(i.iterations for i in infos)
     sharded = bool(lib.hipsdp_matrices_sharded(solver.h))
     # measured beside the vendor figure: the shader frequency during the assemblies of one more (untimed) solve -
     # one-thread kernels read the clock counters right before and after every assembly - and the matrix peak of THIS device under a
-    # 20 ms register-only MFMA loop, with the frequency the firmware grants under that load
+    # 20 ms register-only MFMA loop, with the frequency the firmware grants under that load (--full only)
     measured = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             ghz = C.c_double(0.0)
             lib.hipsdp_set_clock_sampling(solver.h, 1)
@@ -882,12 +918,12 @@ def main():
         out["collectives"] = {"unit": "ms per solve on rank 0 (device time between HIP events around each RCCL call)",
                               **{names[p]: {"ms_per_solve": 1e3 * sec[p] / args.steps, "calls_per_solve": calls[p] / args.steps,
                                             "MB_per_solve": byt[p] / args.steps / 1e6} for p in range(4)}}
-    if rank == 0 and world == 1 and not args.no_extras and ok:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and ok:
         try:
             out["phases"] = phase_anatomy(hb, solver)
         except Exception as e:                                   # the headline number stands on its own
             out["phases"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_extras and ok:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and ok:
         # the same solves with the first assembly through the general products: at the cold start X = Z = xi I the Schur complement is
         # the Gram matrix of the constraint matrices themselves (M_ij = <A_i, A_j>), so the headline run does not multiply by
         # sqrt(xi) I and I / sqrt(xi) in its first iteration (csrc/schur.hip: hs_schur_W_identity); this is what that is worth
@@ -913,11 +949,11 @@ def main():
             out["cold_start_first_assembly"] = {"error": repr(e)}
         finally:
             os.environ.pop("HIPSDP_NO_IDENTITY_START", None)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(solver, b, n, m, int(round(iters / max(1, len(infos)))))
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not args.no_extras and ok and (n, m) == (500, 1000):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and ok and (n, m) == (500, 1000):
         for key, fn in (("warm_start", lambda: bench_warm_start(solver, n, m, b, barrier, last.iterations)),
                         ("sdpi_boundary", lambda: bench_sdpi_boundary(hb, solver, n, m, b, opt))):
             try:
@@ -929,12 +965,12 @@ def main():
     solver.close()
     if comm is not None:
         lib.hipsdp_comm_destroy(comm)
-    if rank == 0 and world == 1 and not args.no_extras and ok and (n, m) == (500, 1000):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and ok and (n, m) == (500, 1000):
         try:
             out["t1"] = bench_t1(hb, args.seed, barrier, cpu=not args.no_cpu)
         except Exception as e:
             out["t1"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_extras and ok and (n, m) == (500, 1000):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and ok and (n, m) == (500, 1000):
         try:
             out["density"] = bench_density(hb, n, m, args.seed, args.density, barrier)
         except Exception as e:

@@ -2,20 +2,22 @@
 (-DHIPSDP_WITH_SCIP) every SCIPlapack* eigen call with n <= 128, every matrix-vector product and every matrix-matrix product below
 1e8 flops goes to the host's DSYEVR / DGEMV / DGEMM - SCIP-SDP always links LAPACK, and a device round trip cannot win at the sizes
 cons_sdp.c calls these with (profiles/r04_d_lapack_small_sizes.txt).  Here that build is compiled against the
-REFERENCE's lapack_interface.h (with the test-only SCIP type stand-ins of tests/scip_stubs/), linked with scipy's bundled OpenBLAS
+REFERENCE's declarations of lapack_interface.h (tests/golden/sdpi_signatures.json, written into an sdpi/lapack_interface.h that
+includes what the reference header includes: the test-only SCIP type stand-ins of tests/scip_stubs/), linked with scipy's bundled OpenBLAS
 (symbols scipy_dsyevr_ ... through the same F77_FUNC hook SCIP-SDP's configf77.h provides; LP64) and a stub libhipsdp whose device
 entry points fail, and the DSYEVR-semantics the callers rely on are executed through the seven symbols: i-th eigenvalue 1-based
 (lapack_interface.c:178-288), eigenvectors as ROWS, the negative range with its tolerance (:398-503), the full decomposition
 (:507-603), DGEMV (:607-650), DGEMM with the four transpose combinations and the vector of unittests/src/checklapack.c:80-119."""
 import ctypes as C
 import glob
+import json
 import os
 import subprocess
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
+SIGNATURES = os.path.join(ROOT, "tests", "golden", "sdpi_signatures.json")
 
 
 def _openblas():
@@ -29,8 +31,11 @@ def _openblas():
 
 @pytest.fixture(scope="module")
 def hostlib(tmp_path_factory):
-    if not os.path.exists(os.path.join(REF, "sdpi", "lapack_interface.h")):
-        pytest.skip("reference tree not present")
+    ref = tmp_path_factory.mktemp("refheader")
+    os.makedirs(str(ref / "sdpi"))
+    with open(str(ref / "sdpi" / "lapack_interface.h"), "w") as f:
+        f.write('#include "scip/def.h"\n#include "blockmemshell/memory.h"\n#include "scip/type_retcode.h"\n%s\n'
+                % "\n".join(json.load(open(SIGNATURES))["sdpi/lapack_interface.h"]))
     blas = _openblas()
     if blas is None:
         pytest.skip("no OpenBLAS with scipy_-prefixed LAPACK symbols in this image")
@@ -40,7 +45,7 @@ def hostlib(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("hostlapack") / "liblapack_host_branch.so")
     cmd = ["gcc", "-std=c99", "-O1", "-shared", "-fPIC", "-Wall", "-Werror=implicit-function-declaration", "-DHIPSDP_WITH_SCIP",
            "-DF77_FUNC(name,NAME)=scipy_ ## name ## _", "-DHIPSDP_LAPACK_INT=int",
-           "-I" + os.path.join(ROOT, "tests", "scip_stubs"), "-I" + REF, "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(ROOT, "tests", "scip_stubs"), "-I" + str(ref), "-I" + os.path.join(ROOT, "include"),
            os.path.join(ROOT, "scip-sdp_amd", "src", "sdpi", "lapack_interface_hip.c"),
            os.path.join(ROOT, "tests", "scip_stubs", "hipsdp_stub.c"), blas, "-Wl,-rpath," + os.path.dirname(blas), "-Wl,-Bsymbolic", "-lm", "-o", out]   # (-Bsymbolic: calls between the seven symbols stay inside this library even when libhipsdp_sdpi.so is loaded globally by another test)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -5,7 +5,7 @@ tag=${1:-x}
 out=$GRAFT_REPO_ROOT/gpurun_out/round_$tag
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python3 bench.py --steps 5 --warmup 1 > $out/bench_c2.json 2> $out/bench_c2.err
+python3 bench.py --full --steps 5 --warmup 1 > $out/bench_c2.json 2> $out/bench_c2.err
 cut -c1-300 $out/bench_c2.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -o c2 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu > $out/bench_c2_prof.json 2> $out/bench_c2_prof.err

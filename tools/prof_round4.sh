@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/round_$tag
 mkdir -p $out
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $out/bench_c2.json 2> $out/bench_c2.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_c2.json 2> $out/bench_c2.err
 cut -c1-260 $out/bench_c2.json
 python3 tests/devtools/solve1_waves.py > $out/solve1_wave_profile.txt 2> $out/solve1_wave_profile.err
 tail -3 $out/solve1_wave_profile.txt

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/round_$tag
 mkdir -p $out
 cd $R
-python3 bench.py > $out/bench_c2.json 2> $out/bench_c2.err
+python3 bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err
 cut -c1-200 $out/bench_c2.json; echo "bench done"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -o c2 -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-extras > $out/bench_c2_prof.json 2> $out/bench_c2_prof.err
