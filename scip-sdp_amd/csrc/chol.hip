@@ -941,8 +941,7 @@ int hs_potrf_psd(hipStream_t s, int n, double* A, double* dinv, int* flag, const
    const pd_ext* extp = ((diag0 != NULL && regmask != NULL) || ext.set_flag) ? &ext : NULL;
    const long long lda = n;
    const int nblk = (n + NB - 1) / NB;
-   static int v1 = getenv("HIPSDP_POTRF_V1") != NULL ? atoi(getenv("HIPSDP_POTRF_V1")) : 0;
-   if ( nblk > 1 && !v1 && !g_potrf_force_v1 )
+   if ( nblk > 1 && !g_potrf_force_v1 )
    {
       /* one launch per block column (k_potrf_step) */
       pd_ext est = {NULL, NULL, 0.0, NULL, NULL, NULL, 0, rule, (diag0 != NULL) ? regmask : NULL, 0, 0, NULL};
@@ -1032,23 +1031,6 @@ int hs_trtri(hipStream_t s, int n, const double* L, const double* dinv, double* 
    const int nblk = (n + NB - 1) / NB;
    hipLaunchKernelGGL(k_copy_diag_blocks, dim3(4 * nblk), dim3(256), 0, s, n, dinv, Linv);
    HS_LAUNCH_CHECK();
-   static const bool rowwise = getenv("HIPSDP_TRTRI_V1") != NULL;
-   if ( rowwise )
-   {
-      for (int b = 1; b < nblk; ++b)
-      {
-         const int i0 = b * NB;
-         const int nb = (n - i0) < NB ? (n - i0) : NB;
-         const double* db = dinv + (long long) b * NB * NB;
-         /* tmp[nb x i0] = L[i0:i0+nb, 0:i0] * Linv[0:i0, 0:i0] */
-         hs_gemm_args g1 = {nb, i0, i0, HS_KC, HS_MC, L + (long long) i0 * ld, ld, 0, Linv, ld, 0, tmp, (long long) i0, 0, 1.0, 0.0, 1, 0, 1, NULL};
-         HS_CALL( hs_dgemm(s, &g1) );
-         /* Linv[i0:i0+nb, 0:i0] = - inv(L_bb) * tmp */
-         hs_gemm_args g2 = {nb, i0, nb, HS_KC, HS_MC, db, NB, 0, tmp, (long long) i0, 0, Linv + (long long) i0 * ld, ld, 0, -1.0, 0.0, 1, 0, 1, NULL};
-         HS_CALL( hs_dgemm(s, &g2) );
-      }
-      return HS_OK;
-   }
    for (long long bs = NB; bs < n; bs *= 2)
    {
       const long long span = 2 * bs;

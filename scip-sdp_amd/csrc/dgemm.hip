@@ -411,9 +411,10 @@ double hs_mfma_flops_total(void) { return g_mfma_flops; }
 void hs_mfma_flops_add(double flops) { g_mfma_flops += flops; }
 
 /* see hs_common.h.  BT: tile edge; kstage: K granularity of the kernel's main loop (a tile's K range is walked in whole stages);
- * kchunk: slice length of a split-K product; slabskip: the persistent kernel's interleaved-slab instance (dgemm2.hip, IL = 1)
- * issues only the 16 x 16 x 4 products whose operand slabs are not identically zero - the loop below repeats its predicate. */
-double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kchunk, int slabskip)
+ * kchunk: slice length of a split-K product; persistent: the product ran on the persistent kernels of dgemm2.hip - the
+ * paired-band kernel, or else the interleaved-slab instances (IL = 1, 2) that issue only the 16 x 16 x 4 products whose operand
+ * slabs are not identically zero (the loop below repeats their predicate). */
+double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kchunk, int persistent)
 {
    const long long tm = (a->M + BT - 1) / BT, tn = (a->N + BT - 1) / BT;
    const int nsl = a->splitk > 1 ? a->splitk : 1;
@@ -436,7 +437,7 @@ double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kch
          if ( kend <= ks0 )
             continue;
          const int stages = (kend - ks0 + kstage - 1) / kstage;
-         if ( slabskip == 2 && BT == 128 && kstage == 8 && hs_dgemm2_tri5_eligible(a) )
+         if ( persistent && BT == 128 && kstage == 8 && hs_dgemm2_tri5_eligible(a) )
          {
             /* paired-band kernel (hs_dgemm5_kernel): the band of 16 stages as 8 double stages of 36 matrix instructions per
              * wavefront, whatever part of it lies inside the K range; full stages outside it */
@@ -444,7 +445,7 @@ double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kch
             f += 2048.0 * 4.0 * (8.0 * 36.0 + 32.0 * (double) nfull);
             continue;
          }
-         if ( !(slabskip && BT == 128 && kstage == 8 && (triA || triB)) )
+         if ( !(persistent && BT == 128 && kstage == 8 && (triA || triB)) )
          {
             f += per_k * (double) stages * kstage;
             continue;
@@ -608,7 +609,7 @@ int hs_dgemm(hipStream_t stream, const hs_gemm_args* a)
          hs_mfma_flops_add(hs_gemm_executed_flops(a, 128, HS_BK, kchunk, 0));
       }
       else
-         hs_mfma_flops_add(hs_gemm_executed_flops(a, 128, 8, kchunk, hs_dgemm2_slabskip()));
+         hs_mfma_flops_add(hs_gemm_executed_flops(a, 128, 8, kchunk, 1));
    }
    else
    {

@@ -44,7 +44,7 @@ typedef const __attribute__((address_space(1))) void* hs_gbl_ptr;
 #define G2_SLOT (2 * G2_OPSZ)
 #define G2_GPS  4                           /* LDS-DMA instructions per wave per stage: 2 per operand */
 #ifndef G2_ABL
-#define G2_ABL  0                           /* developer ablations (tests/devtools/gemm2_abl.sh), wrong results: 1 no C stores, 2 no DMA,
+#define G2_ABL  0                           /* developer ablations (make EXTRA=-DG2_ABL=k), wrong results: 1 no C stores, 2 no DMA,
                                              * 4 no matrix instructions, 8 no drain of the DMA counter in front of the stores */
 #endif
 
@@ -1306,7 +1306,7 @@ extern "C" __attribute__((visibility("default"))) int hs_dgemm5_prof_read(unsign
 #endif
 
 /* 1: launched, 0: not eligible (caller uses dgemm.hip), < 0: error code negated */
-static int g2_disabled = -1;
+static int g2_disabled = 0;
 static int g2_taken = 0;
 
 /* test hook: on = 0 forces dgemm.hip for every product, on = 1 restores the default; returns how many products the
@@ -1315,24 +1315,6 @@ int hs_dgemm2_enable(int on)
 {
    g2_disabled = on ? 0 : 1;
    return __atomic_load_n(&g2_taken, __ATOMIC_RELAXED);
-}
-
-/* 1: products with a triangular operand skip the zero slabs inside the diagonal band (instance IL = 1); 0 (HIPSDP_GEMM2_SKIP=0):
- * they run the straight-line instance over the same K ranges - more matrix instructions, no branches between them */
-int hs_dgemm2_slabskip(void)
-{
-   static int skip = -1;
-   if ( skip < 0 )
-   {
-      const char* env = getenv("HIPSDP_GEMM2_SKIP");
-      skip = (env != NULL && env[0] == '0') ? 0 : 1;
-      /* round 5: products with ONE triangular operand and no K slices take the paired-band kernel (hs_dgemm5_kernel) unless
-       * HIPSDP_GEMM_TRI=1 (the skipping instances of round 3) or HIPSDP_GEMM2_SKIP=0 (no skipping at all) says otherwise */
-      const char* tri = getenv("HIPSDP_GEMM_TRI");
-      if ( skip == 1 && !(tri != NULL && tri[0] == '1') )
-         skip = 2;
-   }
-   return skip;
 }
 
 /* 16 counters per (device, stream): launches on one stream are ordered, so they can share them (cleared before each launch);
@@ -1360,38 +1342,14 @@ static unsigned int* g5_counters(hipStream_t stream)
 int hs_dgemm2_tri5_eligible(const hs_gemm_args* a)
 {
    const bool triA = (a->flags & HS_GEMM_A_LOWTRI) != 0, triB = (a->flags & HS_GEMM_B_LOWTRI) != 0;
-   return hs_dgemm2_slabskip() == 2 && triA != triB && a->splitk <= 1 && !(a->flags & (HS_GEMM_LOWER | HS_GEMM_UPPER | HS_GEMM_A_UPTRI))
+   return triA != triB && a->splitk <= 1 && !(a->flags & (HS_GEMM_LOWER | HS_GEMM_UPPER | HS_GEMM_A_UPTRI))
       && !(triB && a->layB != HS_MC);
 }
 
 int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
 {
-   if ( g2_disabled < 0 )
-   {
-      const char* env = getenv("HIPSDP_GEMM_V1");
-      g2_disabled = (env != NULL && env[0] == '1') ? 1 : 0;
-   }
    if ( g2_disabled )
       return 0;
-   {
-      /* diagnostic: HIPSDP_GEMM_V1_MASK routes classes of products to the tile kernel (1: B triangular, 2: A triangular, 4: lower
-       * tiles / Gram, 8: all others, 16: batched, 32: split-K) */
-      static int mask = -1;
-      if ( mask < 0 )
-         mask = getenv("HIPSDP_GEMM_V1_MASK") != NULL ? atoi(getenv("HIPSDP_GEMM_V1_MASK")) : 0;
-      if ( mask != 0 )
-      {
-         int cls = 0;
-         if ( a->flags & HS_GEMM_B_LOWTRI ) cls |= 1;
-         if ( a->flags & HS_GEMM_A_LOWTRI ) cls |= 2;
-         if ( a->flags & HS_GEMM_LOWER ) cls |= 4;
-         if ( cls == 0 ) cls = 8;
-         if ( a->batch > 1 ) cls |= 16;
-         if ( a->splitk > 1 ) cls |= 32;
-         if ( cls & mask )
-            return 0;
-      }
-   }
    if ( a->layA != HS_KC || (a->flags & (HS_GEMM_UPPER)) )
       return 0;
    if ( (a->lda & 1) || (a->ldb & 1) || (a->strideA & 1) || (a->strideB & 1) || (a->K & 1) || a->K < 16 )
@@ -1444,15 +1402,10 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
       unsigned int* ctr = g5_counters(stream);
       if ( ctr == NULL || hipMemsetAsync(ctr, 0, 64, stream) != hipSuccess )
          return -HS_ERR_HIP;
-      /* list order and store policy (HIPSDP_GEMM_ORDER=0: the natural order, entries taken one by one, plain stores - round 5's
-       * first form): entries in sets of the small operand's panels, taken two at a time, result tiles stored non-temporally.  The
-       * same products per tile either way: only which workgroup computes a tile, and when, changes */
+      /* list order and store policy: entries in sets of the small operand's panels, taken two at a time, result tiles stored
+       * non-temporally (kernel arguments rather than template constants: folded in, they cost the kernel up to 16 VGPRs) */
       hs_gemm_args a5 = *a;
-      {
-         static const int order = getenv("HIPSDP_GEMM_ORDER") != NULL ? atoi(getenv("HIPSDP_GEMM_ORDER")) : 1;
-         if ( order )
-            a5.flags |= G5_F_NT | G5_F_SETS | G5_F_PAIRS;
-      }
+      a5.flags |= G5_F_NT | G5_F_SETS | G5_F_PAIRS;
       switch ( inst5 )
       {
       case 0: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 1>), dim3(grid), dim3(256), smem5, stream, a5, ntile, total, ctr); break;
@@ -1464,7 +1417,7 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
       (void) __atomic_add_fetch(&g2_taken, 1, __ATOMIC_RELAXED);
       return 1;
    }
-   const int il = (hs_dgemm2_slabskip() && triA != triB) ? (triB ? 1 : 2) : 0;
+   const int il = triA != triB ? (triB ? 1 : 2) : 0;
    static hs_attr_mask attr_done[6];
    const int inst = (a->layB == HS_KC ? 0 : 3) + il;
    const void* fn = NULL;

@@ -180,23 +180,11 @@ static int g3_launch(hipStream_t stream, const hs_gemm_args* a)
    return 1;
 }
 
-static int g3_disabled = -1;
-
-int hs_dgemm3_enabled(void)
-{
-   if ( g3_disabled < 0 )
-   {
-      const char* env = getenv("HIPSDP_GEMM_SMALL");
-      g3_disabled = (env != NULL && env[0] == '0') ? 1 : 0;
-   }
-   return g3_disabled ? 0 : 1;
-}
-
 /* 1: launched; 0: not this kernel's shape (the caller goes on with the tile kernels); < 0: error code negated.
  * Takes products without split-K whose 64 x 64 tiling would occupy less than about two thirds of the chip. */
 int hs_dgemm3_try(hipStream_t stream, const hs_gemm_args* a)
 {
-   if ( !hs_dgemm3_enabled() || a->splitk > 1 || a->K < 16 || a->M < 2 || a->N < 2 )
+   if ( a->splitk > 1 || a->K < 16 || a->M < 2 || a->N < 2 )
       return 0;
    if ( a->flags & (HS_GEMM_XCD | HS_GEMM_REMAP | HS_GEMM_TILE64) )
       return 0;

@@ -911,17 +911,10 @@ int hs_steplen_small_multi(hipStream_t s, const hs_step_jobs* P, int maxsteps)
       HS_LAUNCH_CHECK();
       return HS_OK;
    }
-   {
-      /* 17 .. 64 rows: the exact eigenvalue is the faster kernel (HIPSDP_STEP_LANCZOS=1: the Lanczos estimate of round 2) */
-      static int lanczos = -1;
-      if ( lanczos < 0 )
-      {
-         const char* env = getenv("HIPSDP_STEP_LANCZOS");
-         lanczos = (env != NULL && env[0] == '1') ? 1 : 0;
-      }
-      if ( !lanczos && nmax <= 48 )          /* (at 64 rows the 24 Lanczos steps are as fast: measured 9.0 against 9.2 ms per iteration) */
-         return hs_lmin_exact_multi(s, P);
-   }
+   /* 17 .. 48 rows: the exact eigenvalue is the faster kernel (at 64 rows the 24 Lanczos steps are as fast: measured 9.0 against
+    * 9.2 ms per iteration) */
+   if ( nmax <= 48 )
+      return hs_lmin_exact_multi(s, P);
    int k = maxsteps < nmax ? maxsteps : nmax;
    if ( k > LS_MAXK ) k = LS_MAXK;
    static hs_attr_mask attr_done;
@@ -946,7 +939,6 @@ static void lanczos_job_init(lanczos_job* J, int n, int maxsteps, const double* 
 }
 
 /* smallest eigenvalue of one or two symmetric n x n matrices (W1 may be NULL); res = {theta, residual bound, steps} */
-static int lz_no_persist = -1;
 
 int hs_lanczos_lmin2(hipStream_t s, int n, const double* W0, const double* W1, int maxsteps, double* res0, double* res1,
    double* ws0, double* ws1, int* rot, unsigned long long* dsync, int nwipe)
@@ -981,13 +973,8 @@ int hs_lanczos_lmin2(hipStream_t s, int n, const double* W0, const double* W1, i
       jobs.job[1] = jobs.job[0];
    int G = (n + 15) / 16;          /* >= 16 rows per workgroup: one per wavefront */
    if ( G > 128 ) G = 128;
-   if ( lz_no_persist < 0 )
-   {
-      const char* env = getenv("HIPSDP_LANCZOS_LAUNCHES");
-      lz_no_persist = (env != NULL && env[0] == '1') ? 1 : 0;
-   }
    const size_t lds_persist = (size_t) (k + 2) * (size_t) n * sizeof(double);
-   if ( rot != NULL && dsync != NULL && !lz_no_persist && k >= 3 && k <= 250 && lds_persist <= 120 * 1024 && nwipe <= LZ_STRIDE )
+   if ( rot != NULL && dsync != NULL && k >= 3 && k <= 250 && lds_persist <= 120 * 1024 && nwipe <= LZ_STRIDE )
    {
       /* one launch (see k_lanczos_persist); rot[0 / 1]: which of the three exchange vectors of a matrix is the clean one */
       jobs.job[0].sync = dsync;
@@ -1061,128 +1048,6 @@ __device__ __forceinline__ void jac_pair(int np, int r, int k, int* p, int* q)
    }
    *p = a < b ? a : b;
    *q = a < b ? b : a;
-}
-
-/* rotation angles for all pairs of a round; rot[k] = {c, s}; indices >= n (padding player) give the identity */
-__global__ void k_jacobi_angles(int n, int np, int r, const double* __restrict__ A, double* __restrict__ rot)
-{
-   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-   if ( k >= np / 2 )
-      return;
-   int p, q;
-   jac_pair(np, r, k, &p, &q);
-   double c = 1.0, s = 0.0;
-   if ( q < n )
-   {
-      const double apq = A[(long long) p * n + q];
-      const double app = A[(long long) p * n + p];
-      const double aqq = A[(long long) q * n + q];
-      if ( fabs(apq) > 1e-300 && fabs(apq) > 1e-19 * (fabs(app) + fabs(aqq)) )
-      {
-         const double th = (aqq - app) / (2.0 * apq);
-         const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-         c = 1.0 / sqrt(t * t + 1.0);
-         s = t * c;
-      }
-   }
-   rot[2 * k] = c;
-   rot[2 * k + 1] = s;
-}
-
-/* two-sided update A <- J^T A J and Vt <- J^T Vt: thread (k1, k2) owns the 2 x 2 intersection of pairs k1 (rows) and k2
- * (columns); threads with k2 >= half own the rows of Vt instead */
-__global__ void k_jacobi_apply(int n, int np, int r, double* __restrict__ A, double* __restrict__ Vt,
-   const double* __restrict__ rot)
-{
-   const int half = np / 2;
-   const long long tot = (long long) half * half;
-   for (long long t = (long long) blockIdx.x * blockDim.x + threadIdx.x; t < 2 * tot; t += (long long) gridDim.x * blockDim.x)
-   {
-      if ( t < tot )
-      {
-         const int k1 = (int) (t / half), k2 = (int) (t % half);
-         int p, q, u, v;
-         jac_pair(np, r, k1, &p, &q);
-         jac_pair(np, r, k2, &u, &v);
-         if ( q >= n && v >= n )
-            continue;
-         const double c1 = rot[2 * k1], s1 = rot[2 * k1 + 1];
-         const double c2 = rot[2 * k2], s2 = rot[2 * k2 + 1];
-         const bool hq = q < n, hv = v < n;
-         double apu = A[(long long) p * n + u];
-         double apv = hv ? A[(long long) p * n + v] : 0.0;
-         double aqu = hq ? A[(long long) q * n + u] : 0.0;
-         double aqv = (hq && hv) ? A[(long long) q * n + v] : 0.0;
-         /* rows: [p; q] <- [[c1, -s1], [s1, c1]] [p; q] */
-         const double bpu = c1 * apu - s1 * aqu, bqu = s1 * apu + c1 * aqu;
-         const double bpv = c1 * apv - s1 * aqv, bqv = s1 * apv + c1 * aqv;
-         /* columns: [u, v] <- [u, v] [[c2, s2], [-s2, c2]] */
-         apu = c2 * bpu - s2 * bpv; apv = s2 * bpu + c2 * bpv;
-         aqu = c2 * bqu - s2 * bqv; aqv = s2 * bqu + c2 * bqv;
-         A[(long long) p * n + u] = apu;
-         if ( hv ) A[(long long) p * n + v] = apv;
-         if ( hq ) A[(long long) q * n + u] = aqu;
-         if ( hq && hv ) A[(long long) q * n + v] = aqv;
-      }
-      else
-      {
-         /* Vt rows p, q; column pairs taken as consecutive columns */
-         const long long tt = t - tot;
-         const int k1 = (int) (tt / half), cc = (int) (tt % half);
-         int p, q;
-         jac_pair(np, r, k1, &p, &q);
-         if ( q >= n )
-            continue;
-         const double c1 = rot[2 * k1], s1 = rot[2 * k1 + 1];
-         for (int col = 2 * cc; col < 2 * cc + 2 && col < n; ++col)
-         {
-            const double vp = Vt[(long long) p * n + col], vq = Vt[(long long) q * n + col];
-            Vt[(long long) p * n + col] = c1 * vp - s1 * vq;
-            Vt[(long long) q * n + col] = s1 * vp + c1 * vq;
-         }
-      }
-   }
-}
-
-/* off-diagonal square sum and diagonal square sum -> out[0], out[1] (single workgroup) */
-__global__ void __launch_bounds__(1024) k_jacobi_offnorm(int n, const double* __restrict__ A, double* __restrict__ out)
-{
-   __shared__ double sh[16];
-   double off = 0.0, dg = 0.0;
-   const long long tot = (long long) n * n;
-   for (long long e = threadIdx.x; e < tot; e += blockDim.x)
-   {
-      const int r = (int) (e / n), c = (int) (e % n);
-      const double v = A[e];
-      if ( r == c ) dg += v * v; else off += v * v;
-   }
-   off = bsum1024(off, sh);
-   dg = bsum1024(dg, sh);
-   if ( threadIdx.x == 0 )
-   {
-      out[0] = off;
-      out[1] = dg;
-   }
-}
-
-/* ascending sort of the diagonal and matching row permutation of Vt into V (rank sort, one workgroup) */
-__global__ void __launch_bounds__(1024) k_jacobi_sort(int n, const double* __restrict__ A, const double* __restrict__ Vt,
-   double* __restrict__ lam, double* __restrict__ V)
-{
-   for (int i = threadIdx.x; i < n; i += blockDim.x)
-   {
-      const double di = A[(long long) i * n + i];
-      int rank = 0;
-      for (int j = 0; j < n; ++j)
-      {
-         const double dj = A[(long long) j * n + j];
-         if ( dj < di || (dj == di && j < i) )
-            ++rank;
-      }
-      lam[rank] = di;
-      for (int c = 0; c < n; ++c)
-         V[(long long) rank * n + c] = Vt[(long long) i * n + c];
-   }
 }
 
 /* n <= 64: the whole decomposition in ONE launch of one workgroup, matrix and eigenvector matrix in LDS, parallel-order
@@ -1610,8 +1475,8 @@ __global__ void __launch_bounds__(64) k_lmin_tiny_multi(hs_step_jobs P)
  * them up, every pair (P, Q) is one independent 64 x 64 symmetric subproblem [[A_PP, A_PQ], [A_QP, A_QQ]] that ONE workgroup
  * (nearly) diagonalises in LDS by a few sweeps of the same parallel-order two-sided Jacobi as k_jacobi_small, leaving its
  * accumulated rotation J_k; then  A <- J^T A J,  Vt <- J^T Vt  with J = diag(J_k) are three 64-deep products per pair and
- * 64-column chunk (rows of A, rows of Vt, columns of A).  A sweep over all block pairs is nb - 1 rounds of 3 launches instead of
- * the n - 1 rounds of 2 launches of the element-wise form, and the O(n^3) part runs as dense 64 x 64 x 64 products from LDS.
+ * 64-column chunk (rows of A, rows of Vt, columns of A).  A sweep over all block pairs is nb - 1 rounds of 3 launches (an
+ * element-wise Jacobi needs n - 1 rounds of 2), and the O(n^3) part runs as dense 64 x 64 x 64 products from LDS.
  * Rows / columns beyond n are zero padding: a rotation with a zero off-diagonal entry is never formed, so the padded
  * coordinates stay unit vectors and are dropped by the final sort. */
 #define BJ_B 32
@@ -1967,118 +1832,73 @@ int hs_syev_jacobi(hipStream_t s, int n, double* A, double* lam, double* V, int*
       HS_LAUNCH_CHECK();
       return HS_OK;
    }
-   if ( getenv("HIPSDP_JACOBI_ELEMENTWISE") == NULL )
+   const int N = bj_padded(n), nbp = N / BJ_B;
+   double* Ap = ws;
+   double* Vtp = Ap + (long long) N * N;
+   double* J = Vtp + (long long) N * N;
+   double* part = J + (long long) (nbp / 2) * BJ_M * BJ_M;
+   double* Ap2 = part + 2 * BJ_OFFBLOCKS + 32;                     /* second pair of arrays: target of the permutations below */
+   double* Vtp2 = Ap2 + (long long) N * N;
+   int* perm = reinterpret_cast<int*>(Vtp2 + (long long) N * N);
+   long long pg = ((long long) N * N + 255) / 256; if ( pg > 4096 ) pg = 4096;
+   hipLaunchKernelGGL(k_bjac_pad, dim3((unsigned) pg), dim3(256), 0, s, n, N, A, Ap, Vtp);
+   HS_LAUNCH_CHECK();
+   /* the update of a sweep leaves rounding noise of about N eps relative to the diagonal: below that nothing more is gained */
+   double tol = 0.25 * (double) N * 2.2e-16; tol = tol * tol;
+   if ( tol < 1e-30 ) tol = 1e-30;
+   double prev = 1e300;
+   int sweeps_b = 0;
+   int nperm = 0, lastperm = -3;
+   double* const h = bj_readback_buffer();
+   if ( h == NULL )
+      return HS_ERR_HIP;
+   for (sweeps_b = 0; sweeps_b < 40; ++sweeps_b)
    {
-      const int N = bj_padded(n), nbp = N / BJ_B;
-      double* Ap = ws;
-      double* Vtp = Ap + (long long) N * N;
-      double* J = Vtp + (long long) N * N;
-      double* part = J + (long long) (nbp / 2) * BJ_M * BJ_M;
-      double* Ap2 = part + 2 * BJ_OFFBLOCKS + 32;                     /* second pair of arrays: target of the permutations below */
-      double* Vtp2 = Ap2 + (long long) N * N;
-      int* perm = reinterpret_cast<int*>(Vtp2 + (long long) N * N);
-      long long pg = ((long long) N * N + 255) / 256; if ( pg > 4096 ) pg = 4096;
-      hipLaunchKernelGGL(k_bjac_pad, dim3((unsigned) pg), dim3(256), 0, s, n, N, A, Ap, Vtp);
+      hipLaunchKernelGGL(k_bjac_offnorm, dim3(BJ_OFFBLOCKS), dim3(256), 0, s, N, Ap, part);
       HS_LAUNCH_CHECK();
-      /* the update of a sweep leaves rounding noise of about N eps relative to the diagonal: below that nothing more is gained */
-      double tol = 0.25 * (double) N * 2.2e-16; tol = tol * tol;
-      if ( tol < 1e-30 ) tol = 1e-30;
-      double prev = 1e300;
-      int sweeps_b = 0;
-      int nperm = 0, lastperm = -3;
-      const bool bjsort = !(getenv("HIPSDP_BJ_SORT") != NULL && getenv("HIPSDP_BJ_SORT")[0] == '0');
-      int inner0 = 1, inner = 1;               /* inner sweeps of a subproblem: first outer sweep (dense subproblems), later ones */
-      if ( getenv("HIPSDP_BJ_INNER") != NULL )
-         (void) sscanf(getenv("HIPSDP_BJ_INNER"), "%d,%d", &inner0, &inner);
-      double* const h = bj_readback_buffer();
-      if ( h == NULL )
-         return HS_ERR_HIP;
-      for (sweeps_b = 0; sweeps_b < 40; ++sweeps_b)
+      HS_HIP( hipMemcpyAsync(h, part, 2 * BJ_OFFBLOCKS * sizeof(double), hipMemcpyDeviceToHost, s) );
+      HS_HIP( hipStreamSynchronize(s) );
+      double off = 0.0, dg = 0.0;
+      for (int b = 0; b < BJ_OFFBLOCKS; ++b) { off += h[2 * b]; dg += h[2 * b + 1]; }
+      if ( getenv("HIPSDP_JACOBI_VERBOSE") != NULL )
+         fprintf(stderr, "block jacobi n=%d sweep %d: off^2 / diag^2 = %.3e (tol %.1e)\n", n, sweeps_b, off / dg, tol);
+      if ( !(off > tol * dg) || !(off > 0.0) )
+         break;
+      if ( off <= 1e-24 * dg && off > 0.25 * prev )
+         break;                                      /* at the noise floor: no longer shrinking */
+      const double prev0 = prev;
+      prev = off;
+      /* Multiple eigenvalues (the n - rank equal ones of a low-rank matrix - what the PSD projection of a warm start meets): the
+       * cyclic method converges quadratically only when the diagonal entries that belong to one eigenvalue sit next to each other;
+       * scattered among the others they made the tail linear (off^2 / diag^2 from 1e-17 down by 0.6 per sweep: 25 sweeps at
+       * n = 200, the limit of 40 at n = 500 with 1e-11 still off the diagonal).  So when the diagonal entries are close to the
+       * eigenvalues and a sweep has NOT brought the quadratic drop (a matrix with separated eigenvalues never comes here), the
+       * coordinates are sorted by their diagonal entries, and once more three sweeps later if it is still slow:
+       * A <- P A P^T, Vt <- P Vt.  What remains behind that is the second convergence phase every Jacobi method has on such a
+       * matrix - the perturbation inside the eigenspace is a dense matrix of its own - at 0.1 per sweep instead of 0.6. */
+      if ( nperm < 2 && off <= 1e-8 * dg && off > 1e-2 * prev0 && sweeps_b >= lastperm + 3 )
       {
-         hipLaunchKernelGGL(k_bjac_offnorm, dim3(BJ_OFFBLOCKS), dim3(256), 0, s, N, Ap, part);
+         lastperm = sweeps_b;
+         hipLaunchKernelGGL(k_bjac_rank, dim3(n), dim3(256), 0, s, n, N, Ap, perm);
+         hipLaunchKernelGGL(k_bjac_permute, dim3((unsigned) pg), dim3(256), 0, s, n, N, perm, Ap, Vtp, Ap2, Vtp2);
          HS_LAUNCH_CHECK();
-         HS_HIP( hipMemcpyAsync(h, part, 2 * BJ_OFFBLOCKS * sizeof(double), hipMemcpyDeviceToHost, s) );
-         HS_HIP( hipStreamSynchronize(s) );
-         double off = 0.0, dg = 0.0;
-         for (int b = 0; b < BJ_OFFBLOCKS; ++b) { off += h[2 * b]; dg += h[2 * b + 1]; }
-         if ( getenv("HIPSDP_JACOBI_VERBOSE") != NULL )
-            fprintf(stderr, "block jacobi n=%d sweep %d: off^2 / diag^2 = %.3e (tol %.1e)\n", n, sweeps_b, off / dg, tol);
-         if ( !(off > tol * dg) || !(off > 0.0) )
-            break;
-         if ( off <= 1e-24 * dg && off > 0.25 * prev )
-            break;                                      /* at the noise floor: no longer shrinking */
-         const double prev0 = prev;
-         prev = off;
-         /* Multiple eigenvalues (the n - rank equal ones of a low-rank matrix - what the PSD projection of a warm start meets): the
-          * cyclic method converges quadratically only when the diagonal entries that belong to one eigenvalue sit next to each other;
-          * scattered among the others they made the tail linear (off^2 / diag^2 from 1e-17 down by 0.6 per sweep: 25 sweeps at
-          * n = 200, the limit of 40 at n = 500 with 1e-11 still off the diagonal).  So when the diagonal entries are close to the
-          * eigenvalues and a sweep has NOT brought the quadratic drop (a matrix with separated eigenvalues never comes here), the
-          * coordinates are sorted by their diagonal entries, and once more three sweeps later if it is still slow:
-          * A <- P A P^T, Vt <- P Vt.  What remains behind that is the second convergence phase every Jacobi method has on such a
-          * matrix - the perturbation inside the eigenspace is a dense matrix of its own - at 0.1 per sweep instead of 0.6. */
-         if ( bjsort && nperm < 2 && off <= 1e-8 * dg && off > 1e-2 * prev0 && sweeps_b >= lastperm + 3 )
-         {
-            lastperm = sweeps_b;
-            hipLaunchKernelGGL(k_bjac_rank, dim3(n), dim3(256), 0, s, n, N, Ap, perm);
-            hipLaunchKernelGGL(k_bjac_permute, dim3((unsigned) pg), dim3(256), 0, s, n, N, perm, Ap, Vtp, Ap2, Vtp2);
-            HS_LAUNCH_CHECK();
-            double* t = Ap; Ap = Ap2; Ap2 = t;
-            t = Vtp; Vtp = Vtp2; Vtp2 = t;
-            ++nperm;
-         }
-         for (int r = -1; r < nbp - 1; ++r)
-         {
-            /* r = -1: the pairs inside the blocks (pairing of round 0); r >= 0: the cross pairs of the block pairs of round r */
-            const int rr = r < 0 ? 0 : r;
-            hipLaunchKernelGGL(k_bjac_sub, dim3(nbp / 2), dim3(BJ_T), 0, s, N, nbp, rr, Ap, J, sweeps_b == 0 ? inner0 : inner, r < 0 ? 0 : 1);
-            hipLaunchKernelGGL(k_bjac_apply, dim3(nbp / 2, N / BJ_M, 2), dim3(256), 0, s, N, nbp, rr, 0, Ap, Vtp, J);
-            hipLaunchKernelGGL(k_bjac_apply, dim3(nbp / 2, N / BJ_M, 1), dim3(256), 0, s, N, nbp, rr, 1, Ap, Vtp, J);
-         }
-         HS_LAUNCH_CHECK();
+         double* t = Ap; Ap = Ap2; Ap2 = t;
+         t = Vtp; Vtp = Vtp2; Vtp2 = t;
+         ++nperm;
       }
-      hipLaunchKernelGGL(k_bjac_sort, dim3(n), dim3(256), 0, s, n, N, Ap, Vtp, lam, V);
+      for (int r = -1; r < nbp - 1; ++r)
+      {
+         /* r = -1: the pairs inside the blocks (pairing of round 0); r >= 0: the cross pairs of the block pairs of round r */
+         const int rr = r < 0 ? 0 : r;
+         hipLaunchKernelGGL(k_bjac_sub, dim3(nbp / 2), dim3(BJ_T), 0, s, N, nbp, rr, Ap, J, 1, r < 0 ? 0 : 1);
+         hipLaunchKernelGGL(k_bjac_apply, dim3(nbp / 2, N / BJ_M, 2), dim3(256), 0, s, N, nbp, rr, 0, Ap, Vtp, J);
+         hipLaunchKernelGGL(k_bjac_apply, dim3(nbp / 2, N / BJ_M, 1), dim3(256), 0, s, N, nbp, rr, 1, Ap, Vtp, J);
+      }
       HS_LAUNCH_CHECK();
-      if ( info != NULL )
-         HS_HIP( hipMemsetAsync(info, 0, sizeof(int), s) );
-      return HS_OK;
    }
-   double* Vt = ws;                              /* n x n */
-   double* rot = Vt + (long long) n * n;         /* 2 * ceil(n/2) */
-   double* nrm = rot + 2LL * ((n + 1) / 2) + 2;  /* 2 */
-   HS_CALL( hs_symmetrize(s, A, n) );
-   HS_CALL( hs_set_identity(s, Vt, n, 1.0) );
-   const int np = (n + 1) & ~1;
-   const int half = np / 2;
-   int sweeps = 0;
-   if ( n > 1 )
-   {
-      const long long work = 2LL * half * half;
-      int grid = (int) ((work + 255) / 256);
-      if ( grid > 4096 ) grid = 4096;
-      double* const h = bj_readback_buffer();
-      if ( h == NULL )
-         return HS_ERR_HIP;
-      for (sweeps = 0; sweeps < 30; ++sweeps)
-      {
-         hipLaunchKernelGGL(k_jacobi_offnorm, dim3(1), dim3(1024), 0, s, n, A, nrm);
-         HS_LAUNCH_CHECK();
-         HS_HIP( hipMemcpyAsync(h, nrm, 2 * sizeof(double), hipMemcpyDeviceToHost, s) );
-         HS_HIP( hipStreamSynchronize(s) );
-         if ( !(h[0] > 1e-30 * h[1]) || !(h[0] > 0.0) )
-            break;
-         for (int r = 0; r < np - 1; ++r)
-         {
-            hipLaunchKernelGGL(k_jacobi_angles, dim3((half + 255) / 256), dim3(256), 0, s, n, np, r, A, rot);
-            hipLaunchKernelGGL(k_jacobi_apply, dim3(grid), dim3(256), 0, s, n, np, r, A, Vt, rot);
-         }
-         HS_LAUNCH_CHECK();
-      }
-   }
-   hipLaunchKernelGGL(k_jacobi_sort, dim3(1), dim3(1024), 0, s, n, A, Vt, lam, V);
+   hipLaunchKernelGGL(k_bjac_sort, dim3(n), dim3(256), 0, s, n, N, Ap, Vtp, lam, V);
    HS_LAUNCH_CHECK();
    if ( info != NULL )
       HS_HIP( hipMemsetAsync(info, 0, sizeof(int), s) );
-   (void) sweeps;
    return HS_OK;
 }

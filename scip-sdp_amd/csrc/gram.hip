@@ -386,16 +386,6 @@ __global__ void hs_gram_reduce_kernel(int M, int no, int nd, const double* __res
    }
 }
 
-static int gr_mode = -1;
-
-/* test hook: 0 off, 1 on (default unless HIPSDP_GRAM=0); returns the previous mode */
-int hs_gram_enable(int on)
-{
-   const int prev = gr_mode;
-   gr_mode = on ? 1 : 0;
-   return prev;
-}
-
 namespace {
 
 /* how the product is cut into items and who computes them, decided on the host once per shape */
@@ -412,16 +402,7 @@ struct GramPlan
 
 /* cost of a diagonal stage relative to an off-diagonal one: 18 of 32 matrix instructions, one of two operand images; measured 0.71
  * (the barrier, the waits and 11 fragment reads per K step do not shrink with the matrix instructions) */
-double gr_diag_cost(void)
-{
-   static double c = -1.0;
-   if ( c < 0.0 )
-   {
-      const char* env = getenv("HIPSDP_GRAM_DIAGCOST");
-      c = env != NULL && atof(env) > 0.0 ? atof(env) : 0.72;
-   }
-   return c;
-}
+#define GR_DIAG_COST 0.72
 
 /* Every tile in equal K slices, so for the off-diagonal tiles and sd <= so for the diagonal ones (their stages are cheaper).  The
  * items sorted by their start in K are dealt to the XCDs in runs of equal cost, so that the workgroups of an XCD read the same rows
@@ -430,7 +411,7 @@ double gr_diag_cost(void)
 bool gr_make_plan(GramPlan& P, int tm, long long K, int so, int sd)
 {
    const int noff = tm * (tm - 1) / 2;
-   const double cd = gr_diag_cost();
+   const double cd = GR_DIAG_COST;
    if ( so < 1 || sd < 1 )
       return false;
    long long lo = (K + so - 1) / so, ld = (K + sd - 1) / sd;
@@ -535,31 +516,24 @@ GramPlan* gr_plan(int M, long long K, int nslab)
          *best = cand;
       }
    };
-   const char* force = getenv("HIPSDP_GRAM_PLAN");            /* "so sd": developer override */
-   int a = 0, b = 0;
-   if ( force != NULL && sscanf(force, "%d %d", &a, &b) == 2 )
-      consider(gr_make_plan(cand, tm, K, a, b), 0.0);
-   else
+   /* Candidates: ONE item per workgroup (at most 512 items).  With several items per workgroup the lists of an XCD's workgroups
+    * drift apart in K and the rows of W are no longer shared through its L2: measured at m = 2000 (136 tiles, 8 items per
+    * workgroup, balanced to 3 % below the K-sliced tile kernel's estimate) 68.6 against 66.3 ms - the tile kernel's rounds of
+    * equal items stay in step by construction, and the diagonal tiles are only 6 % of that product.  The plan is taken when its
+    * estimate beats the tile kernel's (whole rounds of 512 equal items) by 3 %.  Every partial tile is stored by its workgroup
+    * and read again by the summation kernel: priced at 0.24 K positions of one tile. */
+   const int noff = ntile - tm;
+   for (int so = 1; so <= nslab && (long long) noff * so + tm <= 512; ++so)
+      for (int sd = (so + 1) / 2; sd <= so && (long long) noff * so + (long long) tm * sd <= 512; ++sd)
+         consider(gr_make_plan(cand, tm, K, so, sd), 0.24 * ((double) so * noff + (double) sd * tm) / (double) K);
+   if ( best != NULL )
    {
-      /* Candidates: ONE item per workgroup (at most 512 items).  With several items per workgroup the lists of an XCD's workgroups
-       * drift apart in K and the rows of W are no longer shared through its L2: measured at m = 2000 (136 tiles, 8 items per
-       * workgroup, balanced to 3 % below the K-sliced tile kernel's estimate) 68.6 against 66.3 ms - the tile kernel's rounds of
-       * equal items stay in step by construction, and the diagonal tiles are only 6 % of that product.  The plan is taken when its
-       * estimate beats the tile kernel's (whole rounds of 512 equal items) by 3 %.  Every partial tile is stored by its workgroup
-       * and read again by the summation kernel: priced at 0.24 K positions of one tile. */
-      const int noff = ntile - tm;
-      for (int so = 1; so <= nslab && (long long) noff * so + tm <= 512; ++so)
-         for (int sd = (so + 1) / 2; sd <= so && (long long) noff * so + (long long) tm * sd <= 512; ++sd)
-            consider(gr_make_plan(cand, tm, K, so, sd), 0.24 * ((double) so * noff + (double) sd * tm) / (double) K);
-      if ( best != NULL )
+      const int sold = hs_dgemm_pick_xcd_slices(ntile, K);
+      const double oldspan = (double) (((long long) ntile * sold + 511) / 512) / (double) sold;
+      if ( best->span * 1.03 > oldspan || best->items.size() < 256 )
       {
-         const int sold = hs_dgemm_pick_xcd_slices(ntile, K);
-         const double oldspan = (double) (((long long) ntile * sold + 511) / 512) / (double) sold;
-         if ( best->span * 1.03 > oldspan || best->items.size() < 256 )
-         {
-            delete best;
-            best = NULL;
-         }
+         delete best;
+         best = NULL;
       }
    }
    if ( best != NULL )
@@ -591,12 +565,7 @@ GramPlan* gr_plan(int M, long long K, int nslab)
 int hs_gram_try(hipStream_t stream, int M, long long K, const double* W, long long ldw, double* C, long long ldc, double alpha, double beta,
    double* ws, int nslab, double* executed)
 {
-   if ( gr_mode < 0 )
-   {
-      const char* env = getenv("HIPSDP_GRAM");
-      gr_mode = (env != NULL && env[0] == '0') ? 0 : 1;
-   }
-   if ( !gr_mode || ws == NULL || nslab < 2 || M < 256 || K < 16384 )
+   if ( ws == NULL || nslab < 2 || M < 256 || K < 16384 )
       return 0;
    if ( (ldw & 1) || (K & 1) || (((uintptr_t) W) & 15) || K > 2000000000LL )
       return 0;

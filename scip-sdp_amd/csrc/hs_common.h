@@ -102,13 +102,11 @@ int hs_dgemm2_enable(int on);
  * workgroup built on the host (no atomics).  1: done, 0: not eligible (the caller takes hs_dgemm with HS_GEMM_LOWER), < 0: error code negated */
 int hs_gram_try(hipStream_t stream, int M, long long K, const double* W, long long ldw, double* C, long long ldc, double alpha, double beta,
    double* ws, int nslab, double* executed);
-int hs_gram_enable(int on);
 int hs_gram_plan_info(int M, long long K, int nslab, int* no, int* nd, int* nitems, double* span);
 
 /* latency-oriented 32 x 32 kernel with the K split inside the workgroup (dgemm3.hip) for products of few tiles: 1 launched,
  * 0 not eligible, < 0 error (negated code); hs_dgemm tries it first for products without split-K */
 int hs_dgemm3_try(hipStream_t stream, const hs_gemm_args* args);
-int hs_dgemm3_enabled(void);
 
 /* FP64 matrix-core flops the GEMM launches of the calling host thread have EXECUTED so far (what the MFMA pipes are issued, as
  * opposed to the algorithmic count 2 M N K): whole tiles (edge tiles are computed padded), over the K range each tile walks
@@ -116,9 +114,8 @@ int hs_dgemm3_enabled(void);
  * skips inside the diagonal band.  The engine reads the difference around a Schur assembly (hipsdp_info.schur_flops_executed). */
 double hs_mfma_flops_total(void);
 void   hs_mfma_flops_add(double flops);
-int hs_dgemm2_slabskip(void);            /* 0: no skipping of zero slabs, 1: skipping instances of round 3, 2: paired-band kernel (default) */
 int hs_dgemm2_tri5_eligible(const hs_gemm_args* a);
-double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kchunk, int slabskip);
+double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kchunk, int persistent);
 
 /* choose a split-K factor for a [M x N x K] product so that at least ~2 waves of workgroups exist */
 int hs_dgemm_pick_splitk(int M, int N, int K, int lowerOnly);

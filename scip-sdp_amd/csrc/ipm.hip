@@ -126,21 +126,18 @@ struct hipsdp_solver
    bool pre_valid;
    double pre_scale;       /* 1 / tau at the capture */
    int* regmask;           /* forced pivots of the last factorization of M (semidefinite pivot rule) */
-   double *sc, *red_ws, *gemv_ws, *lan_ws, *lan_ws2, *gws1, *gws2;
+   double *sc, *red_ws, *gemv_ws, *lan_ws, *lan_ws2;
    double* gemvt_ws;                   /* row-chunk partial sums of the passes A^T over blocks with few entries (hs_gemv_t_ws) */
    long long gemvt_ws_len;
    double* hsc;            /* pinned, device-visible host mirror of sc followed by the flags and a sequence number: the last kernel
                             * before a read-back stores the scalars there itself and the host waits for the number */
    double* hsc_dev;        /* device view of hsc */
-   bool use_publish;       /* HIPSDP_READBACK=copy selects hipMemcpyAsync + hipStreamSynchronize instead */
    unsigned long long pub_seq;
    long long hsc_cap;      /* doubles; kept across re-shapes (pinned allocations are slow) */
    int* trsv_ws;           /* block flags of the multi-workgroup triangular solves */
    int trsv_epoch;
-   bool refine_solves;           /* the triangular solves with M correct themselves once with the factor (hs_trsv mode bit 4) */
    int lan_rot[2];                     /* which exchange vector of the one-launch Lanczos runs is the clean one (eig.hip) */
    unsigned long long* lan_sync;       /* device: error word + exchange vectors per matrix of a pair */
-   long long gws_len;
    long long gemv_ws_len;
    int* flags;       /* device ints: 0 chol Z, 1 chol X, 2 chol M */
    hs_schur_ws sws;
@@ -474,7 +471,7 @@ static void free_problem(hipsdp_solver* s)
    s->blk.clear();
    double* ptrs[] = {s->b, s->Dext, s->y, s->x, s->z, s->yt, s->dyt, s->wt, s->AX, s->AH, s->tmpe, s->rp, s->rd, s->tmpq, s->hl,
       s->beta, s->elp, s->dxa, s->dza, s->dx, s->dz, s->xs, s->zs, s->ys, s->rhs2, s->cvec, s->u2, s->dy, s->dya, s->Mx, s->Lm,
-      s->dinvm, s->Slp, s->sc, s->red_ws, s->gemv_ws, s->lan_ws, s->lan_ws2, s->gws1, s->gws2};
+      s->dinvm, s->Slp, s->sc, s->red_ws, s->gemv_ws, s->lan_ws, s->lan_ws2};
    for (double* p : ptrs) dfree(p);
    hs_schur_ws_free(&s->sws);
    dfree(s->Mgather);
@@ -496,7 +493,7 @@ static void free_problem(hipsdp_solver* s)
    s->pre_valid = false;
    s->b = s->Dext = s->y = s->x = s->z = s->yt = s->dyt = s->wt = s->AX = s->AH = s->tmpe = s->rp = s->rd = s->tmpq = s->hl = NULL;
    s->beta = s->elp = s->dxa = s->dza = s->dx = s->dz = s->xs = s->zs = s->ys = s->u1 = s->rhs2 = s->cvec = s->u2 = s->dy = s->dya = NULL;
-   s->Mx = s->Lm = s->dinvm = s->Slp = s->sc = s->red_ws = s->gemv_ws = s->lan_ws = s->lan_ws2 = s->gws1 = s->gws2 = NULL;
+   s->Mx = s->Lm = s->dinvm = s->Slp = s->sc = s->red_ws = s->gemv_ws = s->lan_ws = s->lan_ws2 = NULL;
    s->flags = NULL;
    s->shaped = false;
    s->solved = false;
@@ -534,10 +531,6 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->hsc = NULL;
    s->hsc_dev = NULL;
    s->pub_seq = 0;
-   {
-      const char* rb = getenv("HIPSDP_READBACK");
-      s->use_publish = !(rb != NULL && rb[0] == 'c');
-   }
    s->hsc_cap = 0;
    s->clk_on = false; s->clk_buf = NULL; s->clk_n = 0; s->clk_ghz = 0.0; s->clk_stream = NULL;
    s->s1_ws = NULL; s->s1_ws_len = 0; s->s1_host = NULL; s->s1_host_dev = NULL; s->s1_seq = 0; s->s1_last = 0; s->s1_sol_host = false; s->zero_b = false; s->zero_D = false;
@@ -560,7 +553,7 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->stage_cap = 0;
    s->b = s->Dext = s->y = s->x = s->z = s->yt = s->dyt = s->wt = s->AX = s->AH = s->tmpe = s->rp = s->rd = s->tmpq = s->hl = NULL;
    s->beta = s->elp = s->dxa = s->dza = s->dx = s->dz = s->xs = s->zs = s->ys = s->u1 = s->rhs2 = s->cvec = s->u2 = s->dy = s->dya = NULL;
-   s->Mx = s->Lm = s->dinvm = s->Slp = s->sc = s->red_ws = s->gemv_ws = s->lan_ws = s->lan_ws2 = s->gws1 = s->gws2 = NULL;
+   s->Mx = s->Lm = s->dinvm = s->Slp = s->sc = s->red_ws = s->gemv_ws = s->lan_ws = s->lan_ws2 = NULL;
    s->gemvt_ws = NULL;
    s->gemvt_ws_len = 0;
    hipsdp_default_params(&s->par);
@@ -826,7 +819,7 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
       R.pkv = NULL;
       /* the packed copy halves the HBM traffic of the passes; small blocks are launch bound and their passes take one
        * launch less on the full storage */
-      if ( getenv("HIPSDP_NOPACK") == NULL && B.n > 64 && !R.sparse )
+      if ( B.n > 64 && !R.sparse )
       {
          if ( hipMalloc((void**) &R.Apkown, (size_t) ((arowsA > 0 ? arowsA : 1) * R.Lp) * sizeof(double)) != hipSuccess )
          {
@@ -894,10 +887,6 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
          HS_HIP( hipMalloc((void**) &s->lan_sync, (size_t) hs_lanczos_sync_words() * sizeof(unsigned long long)) );
       HS_CALL( hs_lanczos_sync_reset(s->stream, s->lan_sync, s->lan_rot) );
    }
-   s->gws_len = 8LL * nmax * nmax;
-   if ( s->gws_len > 8LL * 1024 * 1024 ) s->gws_len = 8LL * 1024 * 1024;
-   HS_CALL( dalloc(&s->gws1, s->gws_len) );
-   HS_CALL( dalloc(&s->gws2, s->gws_len) );
    HS_CALL( dalloc(&s->trsv_ws, hs_trsv_sync_ws(mA)) );
    if ( m > 2 * 64 )
       HS_CALL( hs_trsv_sync_init(s->stream, m, s->trsv_ws, &s->trsv_epoch) );
@@ -1690,32 +1679,18 @@ __global__ void k_cert(long long n2, double tau, const double* __restrict__ Rd, 
 static inline dim3 g1d(long long n) { long long g = (n + 255) / 256; if ( g < 1 ) g = 1; if ( g > 4096 ) g = 4096; return dim3((unsigned) g); }
 
 /* ---- GEMM convenience ------------------------------------------------------------------------------------------ */
-/* n x n x n products of the predictor-corrector chain: at n = 500 they are 64 tiles on 256 CUs, so K is cut into slices
- * (slabs in ws, summed in slice order) to occupy the chip; ws = NULL: no split */
-static int gemm_on(hipStream_t st, double* ws, long long wslen, int layA, int layB, int M, int N, int K, double alpha,
-   const double* A, long long lda, const double* B, long long ldb, double beta, double* C, long long ldc, int flags = 0)
+static int gemm_on(hipStream_t st, int layA, int layB, int M, int N, int K, double alpha, const double* A, long long lda,
+   const double* B, long long ldb, double beta, double* C, long long ldc, int flags = 0)
 {
    (void) hs_red_batch_flush();          /* inside a held region: behind the records */
-   int sk = 1;
-   const long long tiles = (long long) ((M + 63) / 64) * ((N + 63) / 64);
-   /* few tiles: the 32 x 32 kernel with the K split inside the workgroup takes the product (no slabs, no second launch);
-    * HIPSDP_GEMM_SMALL=0 restores the split-K slabs of the 64 x 64 tile kernel */
-   if ( !hs_dgemm3_enabled() && ws != NULL && tiles <= 160 && tiles >= 4 && K >= 192 )
-   {
-      sk = (int) ((384 + tiles - 1) / tiles);
-      if ( sk > K / 64 ) sk = K / 64;
-      if ( sk > 8 ) sk = 8;
-      while ( sk > 1 && (long long) sk * M * N > wslen ) --sk;
-      if ( sk < 2 ) sk = 1;
-   }
-   hs_gemm_args g = {M, N, K, layA, layB, A, lda, 0, B, ldb, 0, C, ldc, 0, alpha, beta, 1, flags, sk, sk > 1 ? ws : NULL};
+   hs_gemm_args g = {M, N, K, layA, layB, A, lda, 0, B, ldb, 0, C, ldc, 0, alpha, beta, 1, flags, 1, NULL};
    return hs_dgemm(st, &g);
 }
 
 static int gemm(hipsdp_solver* s, int layA, int layB, int M, int N, int K, double alpha, const double* A, long long lda,
    const double* B, long long ldb, double beta, double* C, long long ldc, int flags = 0)
 {
-   return gemm_on(s->stream, s->gws1, s->gws_len, layA, layB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, flags);
+   return gemm_on(s->stream, layA, layB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, flags);
 }
 
 /* fork: stream2 starts after everything queued on stream so far; join: stream continues after stream2 has drained */
@@ -1920,7 +1895,7 @@ static int publish_and_wait(hipsdp_solver* s, int off, int n, const std::functio
 
 static int read_scalars(hipsdp_solver* s, HostScalars& h, int* flags3, const std::function<int()>* between = NULL)
 {
-   if ( s->comm != NULL || !s->use_publish )
+   if ( s->comm != NULL )
       HS_CALL( hs_red_batch_end_all() );  /* recorded operations must run before the scalars are read */
    h.v.resize(s->nsc);
    if ( s->comm != NULL )
@@ -1929,7 +1904,7 @@ static int read_scalars(hipsdp_solver* s, HostScalars& h, int* flags3, const std
       /* the flags live right behind the scalars: one broadcast covers both */
       HS_CALL( hs_bcast_doubles(s->comm, s->sc, s->nsc + (flags3 != NULL ? 2 : 0), s->stream) );
    }
-   if ( s->comm == NULL && s->use_publish )
+   if ( s->comm == NULL )
    {
       /* the batch kernel (or a one-block kernel when the batch is empty) stores the scalars to the host mirror itself */
       HS_CALL( publish_and_wait(s, 0, s->nsc + 4, between) );
@@ -2220,13 +2195,12 @@ static int apply_A(hipsdp_solver* s, double* const* Vk, const double* vlp, doubl
    return HS_OK;
 }
 
-/* the engine's two queues trade places for a while: everything enqueued through s->stream (and its GEMM workspace) goes to the
- * second queue */
+/* the engine's two queues trade places for a while: everything enqueued through s->stream goes to the second queue */
 struct QueueSwap
 {
    hipsdp_solver* s;
-   explicit QueueSwap(hipsdp_solver* s_) : s(s_) { std::swap(s->stream, s->stream2); std::swap(s->gws1, s->gws2); }
-   ~QueueSwap() { std::swap(s->stream, s->stream2); std::swap(s->gws1, s->gws2); }
+   explicit QueueSwap(hipsdp_solver* s_) : s(s_) { std::swap(s->stream, s->stream2); }
+   ~QueueSwap() { std::swap(s->stream, s->stream2); }
 };
 
 /* one Newton direction; results in (dy, dyt, SC_DTAU, SC_DKAPPA), B.dX, B.dZ, s->dx, s->dz.
@@ -2236,11 +2210,10 @@ struct QueueSwap
 /* split: 0 = dZ by one pass with the coefficients [-dtau; dy]; 1 = dZ = P1 - dtau P2 + eta Rd with P1 = A^T([0; u1]) computed here
  * by one pass and P2 = A^T([1; u2]) from the three-vector sweep of this iteration; 2 = P1 has been computed by that sweep as well
  * (the predictor: its u1 was solved together with the right-hand sides of the tau elimination) */
-/* mode of the triangular solves with the factor of M: forward + backward, corrected where that is free or asked for */
-static inline int solve_mode(const hipsdp_solver* s)
-{
-   return 3 | (s->refine_solves ? 4 : 0);
-}
+/* mode of the triangular solves with the factor of M: forward + backward (3), corrected (4).  They go block by block as
+ * x = inv(L_bb) r, whose residual grows with cond(L_bb) and ends up as primal infeasibility of the step; each of them is corrected
+ * once with the factor itself (about 0.3 % of a solve at n = 500, m = 1000). */
+static const int SOLVE_MODE = 3 | 4;
 
 static int direction(hipsdp_solver* s, double sigma, double eta, double mu, double rg, bool useE, double etk, int part = 0,
    bool u1_solved = false, int split = 0)
@@ -2288,7 +2261,7 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
    if ( m > 0 && !fuse_solve && !u1_solved )
    {
       HS_CALL( hs_red_batch_flush() );
-      HS_CALL( hs_trsv_sync(s->stream, m, s->Lm, s->dinvm, 1, s->u1, m, solve_mode(s), s->trsv_ws, &s->trsv_epoch) );
+      HS_CALL( hs_trsv_sync(s->stream, m, s->Lm, s->dinvm, 1, s->u1, m, SOLVE_MODE, s->trsv_ws, &s->trsv_epoch) );
    }
    /* BH = sum <B_k, H_k> + beta^T hl ; wrp ; bu1 */
    hs_red_batch_begin(s->stream);
@@ -2377,10 +2350,10 @@ static int steplen_enqueue(hipsdp_solver* s)
       const int n = B.n;
       if ( n <= 64 )
          continue;                   /* products and eigenvalues of small blocks share one launch below */
-      HS_CALL( gemm_on(st, s->gws1, s->gws_len, HS_KC, HS_MC, n, n, n, 1.0, B.LxInv, n, B.dX, n, 0.0, B.T1, n) );
-      HS_CALL( gemm_on(st, s->gws1, s->gws_len, HS_KC, HS_KC, n, n, n, 1.0, B.T1, n, B.LxInv, n, 0.0, B.W, n) );
-      HS_CALL( gemm_on(st2, s->gws2, s->gws_len, HS_KC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.dZ, n, 0.0, B.T2, n) );
-      HS_CALL( gemm_on(st2, s->gws2, s->gws_len, HS_KC, HS_KC, n, n, n, 1.0, B.T2, n, B.LzInv, n, 0.0, B.W2, n) );
+      HS_CALL( gemm_on(st, HS_KC, HS_MC, n, n, n, 1.0, B.LxInv, n, B.dX, n, 0.0, B.T1, n) );
+      HS_CALL( gemm_on(st, HS_KC, HS_KC, n, n, n, 1.0, B.T1, n, B.LxInv, n, 0.0, B.W, n) );
+      HS_CALL( gemm_on(st2, HS_KC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.dZ, n, 0.0, B.T2, n) );
+      HS_CALL( gemm_on(st2, HS_KC, HS_KC, n, n, n, 1.0, B.T2, n, B.LzInv, n, 0.0, B.W2, n) );
    }
    HS_CALL( join2(s) );
    /* the X-side and the Z-side eigenvalue of a block run in the same launch */
@@ -2631,7 +2604,7 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
    s->s1_sol_host = false;
    /* (read at every solve: tests and tools switch the path between two solves of one process) */
    int on = 1, prof = 0;
-   double maxwork = 3e6;
+   const double maxwork = 3e6;
    /* largest block the kernel is offered (HIPSDP_SOLVE1_MAXN): whatever fits its LDS - one block of 36 rows, two of 30, eight of 12.
     * Measured with sparse variable matrices, dense constant matrices and LP rows of density 0.3 (tests/devtools/solve1_sizes.py) it
     * is ahead of the general path at every such size: 16 rows 0.124 against 0.281 ms per iteration, 24: 0.233 / 0.360, 32: 0.360 /
@@ -2648,16 +2621,12 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
          maxm = atoi(getenv("HIPSDP_SOLVE1_MAXM"));
       const char* env = getenv("HIPSDP_SOLVE1");
       on = (env != NULL && env[0] == '0') ? 0 : 1;
-      if ( getenv("HIPSDP_SOLVE1_MAXWORK") != NULL )
-         maxwork = atof(getenv("HIPSDP_SOLVE1_MAXWORK"));
       prof = getenv("HIPSDP_SOLVE1_PROF") != NULL ? atoi(getenv("HIPSDP_SOLVE1_PROF")) : 0;
       if ( getenv("HIPSDP_SOLVE1_MAXN") != NULL )
          maxn = atoi(getenv("HIPSDP_SOLVE1_MAXN"));
    }
    const hipsdp_params& par = s->par;
    if ( !on || s->comm != NULL || s->shardA || s->schur_mode_forced || par.verbose || s->pc.on )
-      return HS_OK;
-   if ( getenv("HIPSDP_REFINE_SOLVES") != NULL && getenv("HIPSDP_REFINE_SOLVES")[0] == '0' )
       return HS_OK;
    const int K = (int) s->blk.size();
    int ns[HS_S1_MAXBLK];
@@ -2847,15 +2816,11 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
    else
       hipsdp_default_params(&s->par);
    {
-      const char* env = getenv("HIPSDP_LANCZOS");
-      if ( env != NULL && atoi(env) > 0 )
-         s->par.lanczos_steps = atoi(env);
       if ( s->par.lanczos_steps <= 0 )
       {
          /* default: 24 steps; 16 once every block has more than 64 rows - there each step is a launch of its own and the estimate
           * (used with its residual bound subtracted, the Cholesky of the new iterate being the exact test) costs 4 % of an iteration
-          * at n = 500 and 20 % at n = 200; measured on the bench instances: same iteration counts from 12 steps on
-          * (tools/lanczos_steps.sh) */
+          * at n = 500 and 20 % at n = 200; measured on the bench instances: same iteration counts from 12 steps on */
          int nmin = 1 << 30;
          for (auto& B : s->blk) if ( B.n < nmin ) nmin = B.n;
          s->par.lanczos_steps = (!s->blk.empty() && nmin > 64) ? 16 : 24;
@@ -2914,7 +2879,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
    {
       int nmaxb = 0;
       for (auto& B : s->blk) if ( B.n > nmaxb ) nmaxb = B.n;
-      s->use2 = (nmaxb >= 128) && getenv("HIPSDP_ONEQUEUE") == NULL;
+      s->use2 = nmaxb >= 128;
    }
 
    long long N = q;
@@ -3025,14 +2990,13 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
     * (dy~, dZ) the new residual is (1 - alpha eta) Rd whatever the quality of dy (forced pivots included), and likewise for the
     * LP rows.  The general path (blocks above 64 rows: each pass over A is HBM bound, 1 GB at n = 500 / m = 1000) therefore
     * scales the residual it has instead of sweeping A again; it is recomputed from scratch at the first iteration and whenever
-    * the certificate residuals are needed (tau -> 0 divides the rounding the recurrence carries).  HIPSDP_RD_RECOMPUTE=1: always. */
-   static const bool rd_recompute = getenv("HIPSDP_RD_RECOMPUTE") != NULL && atoi(getenv("HIPSDP_RD_RECOMPUTE")) != 0;
+    * the certificate residuals are needed (tau -> 0 divides the rounding the recurrence carries). */
    bool rd_have = false;             /* Rd / rd hold the residual of SOME iterate: the current one once rd_pending is worked off */
    bool rd_pending = false;
    double rd_scale = 1.0;
    auto enqueue_residuals = [&]() -> int
    {
-      const bool recur = rd_have && !want_cert && !rd_recompute;
+      const bool recur = rd_have && !want_cert;
       HS_CALL( hs_make_ext(st, m, -s->tau, 1.0, s->y, s->yt) );
       HS_LAUNCH_CHECK();
       hs_red_batch_begin(st);         /* the reductions of this phase run in one launch, right before the scalars are read */
@@ -3117,12 +3081,11 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
     * result itself and the flags need no clearing */
    const int setf = (small_all && s->blk.size() == 1) ? 1 : 0;
 
-   /* Overlap on the second queue (blocks of at least 128 rows, HIPSDP_ONEQUEUE / HIPSDP_NO_OVERLAP switch it off):
+   /* Overlap on the second queue (blocks of at least 128 rows):
     *  - the Z chain of the factorization phase (inverse factor, Z^-1) needs nothing from the residual pass, so it is started at
     *    the top of the iteration and runs beside the residual kernels and the host's read-back of the termination scalars;
     *  - the predictor's right-hand side (H_k, A(H), h) needs nothing from the Schur matrix, so it runs beside the latency-bound
     *    factorization of M (one communicator serves one queue: not with several ranks). */
-   static const bool no_overlap = getenv("HIPSDP_NO_OVERLAP") != NULL;
    bool zchain_queued = false;
    auto enqueue_z_chains = [&]() -> int
    {
@@ -3139,7 +3102,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
             HS_CALL( hs_potrf(st2, n, B.Lz, B.dinvz, s->flags + 0, NULL) );
          }
          HS_CALL( hs_trtri(st2, n, B.Lz, B.dinvz, B.LzInv, B.T2) );
-         HS_CALL( gemm_on(st2, s->gws2, s->gws_len, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
+         HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
          HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
       }
       return HS_OK;
@@ -3180,8 +3143,8 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
     * stood between the termination decision and the assembly (profiles/r06_*_iter_sequence.txt). */
    auto defer_possible = [&]() -> bool
    {
-      if ( !(s->use2 && !no_overlap && s->comm == NULL && !s->shardA && !s->schur_mode_cols && !s->schur_mode_rows
-            && !s->schur_mode_U && !s->schur_mode_forced && K > 0 && getenv("HIPSDP_NO_DEFER_JOIN") == NULL) )
+      if ( !(s->use2 && s->comm == NULL && !s->shardA && !s->schur_mode_cols && !s->schur_mode_rows
+            && !s->schur_mode_U && !s->schur_mode_forced && K > 0) )
          return false;
       for (auto& B : s->blk)
          if ( B.n <= 64 || B.sparse )
@@ -3207,7 +3170,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
       if ( !residuals_ready )
       {
          phase_mark(s, PH_RESID);
-         if ( s->use2 && !no_overlap && !zchain_queued && K > 0 )
+         if ( s->use2 && !zchain_queued && K > 0 )
          {
             HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
             HS_CALL( fork2(s) );
@@ -3237,18 +3200,6 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
       dinf = sqrt(rd2) / tau / (1.0 + normC);
       dabs = rdmax / tau;
       gap = fabs(dobj - pobj) / tau;
-      /* The triangular solves with the factor of M go block by block as x = inv(L_bb) r, whose residual grows with cond(L_bb)
-       * and ends up as primal infeasibility of the step; each of them is corrected once with the factor itself (hs_trsv mode
-       * bit 4; about 0.3 % of a solve at n = 500, m = 1000).  HIPSDP_REFINE_SOLVES=0 switches the correction off. */
-      {
-         static int forced = -2;
-         if ( forced == -2 )
-         {
-            const char* env = getenv("HIPSDP_REFINE_SOLVES");
-            forced = (env == NULL) ? -1 : (env[0] == '0' ? 0 : 1);
-         }
-         s->refine_solves = (forced != 0);
-      }
       if ( par.verbose )
          printf("hipsdp it %3d mu %.3e pinf %.3e dinf %.3e gap %.3e pobj %.8e dobj %.8e tau %.3e kap %.3e\n", it, mu, pinf, dinf,
             gap, pobj / tau, dobj / tau, tau, kappa);
@@ -3394,7 +3345,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
             }
             if ( n > 32 )
             {
-               HS_CALL( gemm_on(st2, s->gws2, s->gws_len, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
+               HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
                HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
             }
             continue;
@@ -3408,7 +3359,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
             HS_CALL( hs_potrf(st2, n, B.Lz, B.dinvz, s->flags + 0, NULL) );
          }
          HS_CALL( hs_trtri(st2, n, B.Lz, B.dinvz, B.LzInv, B.T2) );
-         HS_CALL( gemm_on(st2, s->gws2, s->gws_len, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
+         HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
          HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
          }
          /* X chain on the first (already queued behind the read-back when the Z chain was started at the top of the iteration) */
@@ -3603,7 +3554,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
       hs_comm_phase(2);
       phase_mark(s, PH_MSOLVE);
       bool predH_queued = false, predH_joined = false, split_dz = false;
-      if ( s->use2 && !no_overlap && s->comm == NULL && !small_problem(s) && m > 0 )
+      if ( s->use2 && s->comm == NULL && !small_problem(s) && m > 0 )
       {
          HS_CALL( fork2(s) );
          {
@@ -3638,10 +3589,10 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
                 * solve with three right-hand sides instead of a pair and, later, a single one */
                HS_CALL( join2(s) );
                predH_joined = true;
-               HS_CALL( hs_trsv_sync(st, m, s->Lm, s->dinvm, 3, s->rhs2, m, solve_mode(s), s->trsv_ws, &s->trsv_epoch) );
+               HS_CALL( hs_trsv_sync(st, m, s->Lm, s->dinvm, 3, s->rhs2, m, SOLVE_MODE, s->trsv_ws, &s->trsv_epoch) );
             }
             else
-               HS_CALL( hs_trsv_sync(st, m, s->Lm, s->dinvm, 2, s->rhs2, m, solve_mode(s), s->trsv_ws, &s->trsv_epoch) );
+               HS_CALL( hs_trsv_sync(st, m, s->Lm, s->dinvm, 2, s->rhs2, m, SOLVE_MODE, s->trsv_ws, &s->trsv_epoch) );
          }
       }
       if ( m == 0 || m > 64 )
@@ -3657,7 +3608,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
        * P1 = A^T([0; u1]) come out of ONE sweep over A (three coefficient vectors), the corrector needs one more sweep for its P1:
        * two sweeps per iteration where B, the predictor's dZ and the corrector's dZ took three - and the dependent chain
        * B pass -> dtau -> dZ pass loses a link.  Single GPU, packed copy present, predictor solved early (else the old form). */
-      bool split_ok = predH_joined && s->comm == NULL && getenv("HIPSDP_NO_SPLIT_DZ") == NULL;
+      bool split_ok = predH_joined && s->comm == NULL;
       for (auto& B : s->blk)
          if ( B.Apk == NULL )
             split_ok = false;
@@ -3912,7 +3863,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
                s->tau = tau0 + alpha * dt;
                s->kappa = kappa0 + alpha * dk;
                factors_valid = true;                    /* (what the chains below test: the check has produced the factors) */
-               if ( s->use2 && !no_overlap && !zchain_queued )
+               if ( s->use2 && !zchain_queued )
                {
                   HS_CALL( fork2(s) );
                   HS_CALL( enqueue_z_chains() );
@@ -3946,7 +3897,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
             }
             if ( s->comm != NULL )
                HS_CALL( hs_bcast_ints(s->comm, s->flags, 3, st) );
-            if ( s->comm == NULL && s->use_publish )
+            if ( s->comm == NULL )
                HS_CALL( publish_and_wait(s, s->nsc, 2) );
             else
             {
@@ -4014,7 +3965,7 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
 
    phase_mark(s, -1);
    /* a break above may leave the Z chain of the abandoned iteration running on the second queue (it is started at the top of an
-    * iteration, before the termination decision): it writes B.Lz / B.LzInv / B.Zinv / B.T2 / gws2, so the solve is over - and
+    * iteration, before the termination decision): it writes B.Lz / B.LzInv / B.Zinv / B.T2, so the solve is over - and
     * its buffers may be re-shaped, freed or read - only when that queue has drained as well */
    if ( zchain_queued )
       HS_CALL( join2(s) );

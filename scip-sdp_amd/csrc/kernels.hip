@@ -1421,18 +1421,6 @@ static int rb_record(hipStream_t s, int kind, long long n, const double* a, cons
 /* a record of the round-3 kinds: NULL when no batch is open on this stream (the caller launches; pending records are flushed first) */
 static rb_desc* rb_record_ext(hipStream_t s, int kind, size_t smem)
 {
-   {
-      /* developer switch HIPSDP_BATCH_SKIP: bit (kind - 110) set = that kind is never recorded */
-      static int skip = -1;
-      if ( skip < 0 )
-         skip = getenv("HIPSDP_BATCH_SKIP") != NULL ? atoi(getenv("HIPSDP_BATCH_SKIP")) : 0;
-      if ( kind >= 110 && ((skip >> (kind - 110)) & 1) )
-      {
-         if ( g_rb.open && g_rb.hold > 0 )
-            (void) rb_flush();
-         return NULL;
-      }
-   }
    /* only inside a held region: a batch opened by begin alone keeps its round-2 meaning (reductions whose inputs nobody touches
     * before the read-back; the launches between them are not recorded and run first) */
    if ( !g_rb.open || g_rb.hold == 0 )

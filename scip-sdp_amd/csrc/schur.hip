@@ -134,11 +134,7 @@ static int schur_gram(hipStream_t s, int m1, long long K, const double* V, long 
 }
 
 /* smallest m1 for which the Gram product runs in XCD-walked K slices (below: plain split-K over the lower tiles) */
-static int hs_syrk_min_m1(void)
-{
-   const char* e = getenv("HIPSDP_SYRK_MINM");
-   return e != NULL && atoi(e) > 0 ? atoi(e) : 256;
-}
+#define SYRK_MIN_M1 256
 
 /* Slab count and flags of the tile-kernel form of Mx += V V^T (K contiguous): XCD-walked K slices when `xcd` and at least two m1 x m1
  * slabs fit the workspace, plain split-K otherwise, and ONE pass straight into Mx (no slabs, ws unused) when not even two fit - a
@@ -180,7 +176,7 @@ int hs_schur_W_identity_range(hipStream_t s, int m1, int n, const double* A, lon
          return HS_OK;
    }
    int flags, sk;
-   schur_syrk_shape(w, m1, K, m1 >= hs_syrk_min_m1() && K >= 16384 && (K >= 50000 || m1 >= 900), &flags, &sk);
+   schur_syrk_shape(w, m1, K, m1 >= SYRK_MIN_M1 && K >= 16384 && (K >= 50000 || m1 >= 900), &flags, &sk);
    hs_gemm_args g3 = {m1, m1, (int) K, HS_KC, HS_KC, A + k0, n2, 0, A + k0, n2, 0, Mx, m1, 0, 1.0, 1.0, 1, flags, sk, sk > 1 ? w->K : NULL};
    return hs_dgemm(s, &g3);
 }
@@ -219,20 +215,16 @@ int hs_schur_W(hipStream_t s, int m1, int n, const double* A, const double* R, c
    }
    int flags = HS_GEMM_LOWER;
    int sk;
-   /* measured (tools/syrk_threshold.sh): the XCD-walked slices win by 8-10 % for n >= 256 at every m1 >= 256, and for n = 128 from
+   /* measured: the XCD-walked slices win by 8-10 % for n >= 256 at every m1 >= 256, and for n = 128 from
     * m1 = 1000 on; below that plain split-K over the lower tiles is 5-40 % faster */
-   if ( m1 >= hs_syrk_min_m1() && n2 >= 16384 && (n2 >= 50000 || m1 >= 900) )
+   if ( m1 >= SYRK_MIN_M1 && n2 >= 16384 && (n2 >= 50000 || m1 >= 900) )
    {
       const long long tm = (m1 + 127) / 128;
       const long long ntri = tm * (tm + 1) / 2;
       sk = hs_dgemm_pick_xcd_slices(ntri, n2);
-      if ( getenv("HIPSDP_SYRK_SLICES") != NULL && atoi(getenv("HIPSDP_SYRK_SLICES")) >= 2 )
-         sk = atoi(getenv("HIPSDP_SYRK_SLICES"));
       while ( sk > 2 && (long long) sk * m1 * m1 > w->kws_len ) --sk;
-      if ( getenv("HIPSDP_SYRK_NOXCD") == NULL )
-         flags |= HS_GEMM_XCD;
-      if ( getenv("HIPSDP_SYRK_FAST") == NULL )
-         flags |= HS_GEMM_NOFAST;          /* measured on this shape: the checked loads are 5 % faster (tools/gemm_syrk.cpp) */
+      flags |= HS_GEMM_XCD;
+      flags |= HS_GEMM_NOFAST;             /* measured on this shape: the checked loads are 5 % faster (tools/gemm_syrk.cpp) */
    }
    else
    {
@@ -260,7 +252,7 @@ int hs_schur_Wcols(hipStream_t s, int m1, int n, const double* A, const double* 
    if ( c0 < 0 || c0 + cw > n || rows > 2000000000LL || nk > 2000000000LL || (long long) m1 * nk > w->chunk_cols * w->n2 )
       return HS_ERR_ARG;
    /* a slice of at most 64 columns (8 ranks at n = 500: 62) fills half a 128-wide tile: 64 x 64 tiles for the two n^3 products */
-   const int narrow = (cw <= 64 && getenv("HIPSDP_NO_TILE64") == NULL) ? HS_GEMM_TILE64 : 0;
+   const int narrow = cw <= 64 ? HS_GEMM_TILE64 : 0;
    hs_gemm_args g1 = {(int) rows, cw, n - c0, HS_KC, HS_MC, A + c0, n, 0, R + (long long) c0 * n + c0, n, 0, w->T, cw, 0, 1.0, 0.0, 1,
       HS_GEMM_B_LOWTRI | narrow, 1, NULL};
    HS_CALL( hs_dgemm(s, &g1) );
@@ -700,13 +692,8 @@ int hs_schur_small(hipStream_t s, int m1, int nblk, const int* n, const double* 
       /* the one-launch form does the m1^2 / 2 inner products <A_i, U_j> with scalar arithmetic out of L2: it wins while the launch
        * count decides (few variables) and loses by 20x at m = 1000 (n = 48: 4.4 ms against 0.2 ms of the GEMM path).  The bound is
        * on the multiply-adds of those products; measured crossover of the whole iteration (tools/grid_sweep.sh, round 3): n = 16
-       * between m = 100 and 200, n = 32 between 50 and 100, n = 48 at about 20, i.e. 1 - 5e6 (HIPSDP_SCHUR_SMALL_MAXWORK) */
-      static double maxwork = -1.0;
-      if ( maxwork < 0.0 )
-      {
-         const char* env = getenv("HIPSDP_SCHUR_SMALL_MAXWORK");
-         maxwork = env != NULL ? atof(env) : 1.5e6;
-      }
+       * between m = 100 and 200, n = 32 between 50 and 100, n = 48 at about 20, i.e. 1 - 5e6: the bound is 1.5e6 */
+      const double maxwork = 1.5e6;
       double work = 0.0;
       for (int k = 0; k < nblk; ++k)
          work += 0.5 * (double) m1 * m1 * (double) n[k] * n[k];

@@ -38,19 +38,8 @@ int hs_solve1_class(const hs_solve1_args* a)
    int nmax = 0;
    for (int k = 0; k < a->nblk; ++k)
       if ( a->n[k] > nmax ) nmax = a->n[k];
-   /* HIPSDP_SOLVE1_CLASS=64: everything through the general instance (developer switch: the instances must agree bit for bit) */
-   static int force = -1;
-   if ( force < 0 )
-   {
-      const char* env = getenv("HIPSDP_SOLVE1_CLASS");
-      force = env != NULL ? atoi(env) : 0;
-   }
    if ( a->m > 64 )
       return 1064;
-   if ( force == 64 )
-      return 64;
-   if ( force == 16 && nmax <= 16 )
-      return 16;
    return nmax <= 10 ? 10 : (nmax <= 16 ? 16 : 64);
 }
 

@@ -635,7 +635,7 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
 {
    clock_t tfp0, tfp1, tup1;                 /* processor time of this thread's marshalling work (printed with SDPINFO) */
    unsigned long long fp;
-   SCIP_Bool usemaster = (getenv("HIPSDP_NOMASTER") == NULL);
+   SCIP_Bool usemaster = TRUE;
    const SCIP_Bool usecache = (getenv("HIPSDP_NOCACHE") == NULL);
    CooBuf coo = {NULL, NULL, NULL, NULL};
    int* slots = NULL;
@@ -1349,8 +1349,6 @@ SCIP_RETCODE SCIPsdpiSolverLoadAndSolveWithPenalty(
          level = 1;
       else
          level = 0;
-      if ( getenv("HIPSDP_NOLADDER") != NULL && ! s->penalty )
-         level = 0;
       for (;;)
       {
          retcode = solveAndCheckTolerances(s, level, timelimit, usedsdpitime, &remaining);
@@ -1358,8 +1356,7 @@ SCIP_RETCODE SCIPsdpiSolverLoadAndSolveWithPenalty(
             return retcode;
          if ( ! s->penalty )
             s->usedsetting = (level == 0) ? SCIP_SDPSOLVERSETTING_FAST : (level == 1 ? SCIP_SDPSOLVERSETTING_MEDIUM : SCIP_SDPSOLVERSETTING_STABLE);
-         if ( s->penalty || level >= 2 || statusKnown(s->info.status) || s->info.status == HIPSDP_STATUS_TIMELIM
-            || getenv("HIPSDP_NOLADDER") != NULL )
+         if ( s->penalty || level >= 2 || statusKnown(s->info.status) || s->info.status == HIPSDP_STATUS_TIMELIM )
             break;
          {
             SCIP_Bool expired = FALSE;

@@ -1,6 +1,5 @@
 """developer script: the block-Jacobi decomposition (n > 128) on low-rank and full-rank matrices - time per call and residuals.  Device
-timings first, host reference decompositions afterwards (idle BLAS threads keep spinning and slow the launching thread down).
-HIPSDP_BJ_SORT=0: without the sorting of the coordinates by their diagonal entries."""
+timings first, host reference decompositions afterwards (idle BLAS threads keep spinning and slow the launching thread down)."""
 import sys, os, time, importlib.util
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,6 +1,5 @@
 """developer script: full decomposition of low-rank matrices (a large cluster of zero eigenvalues: what the PSD projection of the
-warm-start producer meets), wall time per call.  usage: python tests/devtools/syev_lowrank_time.py   (HIPSDP_SYEV_MID_FROM=65 for
-the round-3 kernel below 65 rows, HIPSDP_SYEV_JACOBI=1 for the block Jacobi)"""
+warm-start producer meets), wall time per call.  usage: python tests/devtools/syev_lowrank_time.py"""
 import sys, os, time, importlib.util
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,5 @@
-"""developer script: wall time of the full decomposition (hipsdp_syev) at 64 ... 128 rows, one launch against the block Jacobi
-(HIPSDP_SYEV_JACOBI is read once per process: run twice to compare).  usage: python tests/devtools/syev_mid_time.py"""
+"""developer script: wall time of the full decomposition (hipsdp_syev) at 32 ... 128 rows (one launch; compare two builds with
+HIPSDP_LIB).  usage: python tests/devtools/syev_mid_time.py [n,n,...]"""
 import sys, os, time, importlib.util
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
