@@ -168,6 +168,19 @@ HIPSDP_API long long hipsdp_solve1_fallbacks_warm(void);   /* ... of these: warm
 HIPSDP_API int hipsdp_solve1_debug_counts(unsigned int* counts2);
 HIPSDP_API int  hipsdp_solve1_trace(hipsdp_solver* solver, double* out64, int maxrows, double* hist);
 
+/* Solve count independent problems, each already shaped and loaded on its own solver (same device, no communicator).
+ * Every eligible problem runs in the one-launch kernel, all of them together: ONE launch of one workgroup per problem for each
+ * size class present.  Problems the kernel declines or gives up on, and problems the one-launch path is not offered, are solved
+ * afterwards by the general path exactly as hipsdp_solve would solve them.  params: count entries, or NULL for defaults.
+ * For every i, solvers[i] and infos[i] end as hipsdp_solve(solvers[i], &params[i], &infos[i]) leaves them (solve_seconds aside).
+ * HIPSDP_ERR_ARG, and nothing launched: count < 0, a NULL or unshaped solver, the same solver twice, solvers on different devices,
+ * a solver with a communicator.  count == 0 does nothing.
+ * rcs (optional): per-solver return code.  Returns HIPSDP_OK when every rcs[i] is HIPSDP_OK, else the first failing code.
+ * Two host threads may call it at the same time on disjoint sets of solvers. */
+HIPSDP_API int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const hipsdp_params* params,
+                                 hipsdp_info* infos, int* rcs);
+HIPSDP_API int hipsdp_solve_many_stats(long long* launches, long long* problems);  /* process totals of the one-launch part */
+
 /* solution readback (host arrays).  For STATUS_OPTIMAL the iterate scaled by 1 / tau; for the infeasibility statuses
  * the normalised ray. */
 HIPSDP_API int  hipsdp_get_y(hipsdp_solver* solver, double* y);

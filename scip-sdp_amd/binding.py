@@ -280,6 +280,45 @@ class Solver:
 
 # ---- unit-level host-buffer kernels ---------------------------------------------------------------------------------
 
+def _params(kw):
+    p = Params()
+    lib().hipsdp_default_params(C.byref(p))
+    for k, v in (kw or {}).items():
+        setattr(p, k, v)
+    return p
+
+
+def solve_many(solvers, params=None):
+    """hipsdp_solve_many: every Solver of the list (loaded, one device, each at most once) solved in one call - the one-launch
+    kernel once per size class for all of them, the general path one after another for the rest.  params: None (defaults), one dict
+    for all, or a list of dicts, one per solver (Solver.solve's keywords).  Returns the list of Info; raises RuntimeError with the
+    per-solver return codes when any of them failed."""
+    n = len(solvers)
+    if isinstance(params, (list, tuple)):
+        if len(params) != n:
+            raise ValueError("solve_many: %d params for %d solvers" % (len(params), n))
+        plist = [_params(kw) for kw in params]
+    else:
+        plist = [_params(params)] * n
+    hs = (C.c_void_p * max(n, 1))(*[s.h for s in solvers])
+    ps = (Params * max(n, 1))(*plist)
+    infos = (Info * max(n, 1))()
+    rcs = (C.c_int * max(n, 1))()
+    rc = lib().hipsdp_solve_many(n, hs, ps, infos, rcs)
+    if rc != 0:
+        raise RuntimeError("hipsdp_solve_many failed: rc=%d, per solver %s (%s)" %
+                           (rc, list(rcs)[:n], lib().hipsdp_last_error().decode()))
+    return [infos[i] for i in range(n)]
+
+
+def solve_many_stats():
+    """(launches, problems): process totals of hipsdp_solve_many's one-launch part"""
+    launches = C.c_longlong(0)
+    problems = C.c_longlong(0)
+    _chk(lib().hipsdp_solve_many_stats(C.byref(launches), C.byref(problems)), "hipsdp_solve_many_stats")
+    return launches.value, problems.value
+
+
 def dgemm(A, B, layA=0, layB=1, alpha=1.0, beta=0.0, Cin=None, lower_only=False, splitk=0, device=0):
     """row-major C = alpha op(A) op(B) + beta C.  layA = 0: A is [M, K]; 1: A is [K, M].  layB = 0: B is [N, K]; 1: [K, N]."""
     A = _f64(A)

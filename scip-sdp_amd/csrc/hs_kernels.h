@@ -542,11 +542,23 @@ struct hs_solve1_args
    double* hist;                           /* optional: 16 doubles per iteration (tests, tools) */
    unsigned long long seq; unsigned long long* flag;   /* when flag != NULL: *flag = seq once out[] is complete */
 };
+/* the parameter of the one-launch kernel (csrc/solve1_body.h): the arguments by value, or in the instances of hipsdp_solve_many
+ * (S1_MANY, csrc/solve1_*_many.hip) an array of them in device memory, one per workgroup, bound by reference - read where they are
+ * used, like kernel arguments, with no copy of the struct into registers.  (Defined here rather than in solve1_body.h: the kernel
+ * reports the line of a numerical failure in its results, so the lines of that file stay where they are.) */
+#ifdef S1_MANY
+#define S1_PARAMS const hs_solve1_args* __restrict__ PA
+#define S1_BIND_P const hs_solve1_args& P = PA[blockIdx.x];
+#else
+#define S1_PARAMS const hs_solve1_args P
+#define S1_BIND_P
+#endif
 int hs_small_solve_by_substitution(void);
 int hs_solve1_fits(int m, int q, int nblk, const int* n);
 long long hs_solve1_ws_doubles(int m, int q, int nblk, const int* n);
 int hs_solve1_launch(hipStream_t st, const hs_solve1_args* a);
 int hs_solve1_class(const hs_solve1_args* a);
+int hs_solve1_launch_many(hipStream_t st, int cls, const hs_solve1_args* dev_args, int count);
 int hs_solve1_debug_counts(unsigned int* out2);
 
 #endif

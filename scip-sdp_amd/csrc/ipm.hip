@@ -19,6 +19,7 @@
 #include <utility>
 #include <functional>
 #include <chrono>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2505,20 +2506,9 @@ static int sync_outcome(hipsdp_solver* s, int rc, hipsdp_info* info)
    return HIPSDP_OK;
 }
 
-extern "C" int hipsdp_solve(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
+/* the end of every solve (hipsdp_solve, hipsdp_solve_many) */
+static int solve_end(hipsdp_solver* s, int rc)
 {
-   if ( s == NULL || !s->shaped || info == NULL )
-      return HIPSDP_ERR_ARG;
-   HS_HIP( hipSetDevice(s->device) );
-   HS_CALL( flush_zeros(s) );
-   if ( s->comm != NULL )
-      HS_CALL( flush_cmds(s) );                   /* (one rank alone: the one-launch solve runs the waiting commands itself) */
-   const bool alone = replicate_small(s);
-   int rc;
-   {
-      CommOff off(s, alone);
-      rc = solve_impl(s, params, info);
-   }
    /* no recorded operation and no held region outlives the call: a normal return has launched everything (the final read-back
     * ends the regions), an error return may have left records behind, which are dropped */
    if ( rc == HIPSDP_OK )
@@ -2536,6 +2526,24 @@ extern "C" int hipsdp_solve(hipsdp_solver* s, const hipsdp_params* params, hipsd
       (void) hipStreamSynchronize(s->stream);
       phase_finish(s);
    }
+   return rc;
+}
+
+extern "C" int hipsdp_solve(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
+{
+   if ( s == NULL || !s->shaped || info == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( flush_zeros(s) );
+   if ( s->comm != NULL )
+      HS_CALL( flush_cmds(s) );                   /* (one rank alone: the one-launch solve runs the waiting commands itself) */
+   const bool alone = replicate_small(s);
+   int rc;
+   {
+      CommOff off(s, alone);
+      rc = solve_impl(s, params, info);
+   }
+   rc = solve_end(s, rc);
    if ( alone )
       rc = sync_outcome(s, rc, info);
    return rc;
@@ -2597,9 +2605,21 @@ extern "C" int hipsdp_get_assembly_clock(hipsdp_solver* s, double* ghz)
 static long long g_solve1_solves = 0;      /* solves of this process that ran in the one launch (bench.py reports the share) */
 static long long g_solve1_fallbacks = 0;   /* ... that the kernel gave up on numerically and the general path solved again */
 static long long g_solve1_fallbacks_warm = 0;   /* ... of these: warm-started solves (retried from the caller's start) */
-static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
+static long long g_many_launches = 0;      /* hipsdp_solve_many: launches of the one-launch kernel (one per size class and call) */
+static long long g_many_problems = 0;      /* ... and the problems whose results the kernel delivered there */
+/* the three stages of a one-launch solve: prepare (eligibility, workspace, the kernel's arguments, the node's commands taken over),
+ * wait (the sequence word), finish (the result block into the solver and info).  hipsdp_solve runs them back to back (solve1_try),
+ * hipsdp_solve_many prepares many solvers, launches them together and finishes each. */
+struct S1Prep
 {
-   *done = false;
+   hs_solve1_args a;
+   int prof, nofb;
+   std::chrono::steady_clock::time_point t_begin;
+};
+/* *offered = false: not this path's problem (shape, options) - nothing has been touched */
+static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
+{
+   *offered = false;
    s->s1_last = 0;
    s->s1_sol_host = false;
    /* (read at every solve: tests and tools switch the path between two solves of one process) */
@@ -2672,8 +2692,8 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
          if ( B.Xpre == NULL )
             HS_CALL( dalloc(&B.Xpre, (long long) B.n * B.n) );
    }
-   const auto t_begin = std::chrono::steady_clock::now();
-   hs_solve1_args a;
+   pp->t_begin = std::chrono::steady_clock::now();
+   hs_solve1_args& a = pp->a;
    memset(&a, 0, sizeof(a));
    a.m = s->m; a.q = s->q; a.nblk = K;
    for (int k = 0; k < K; ++k)
@@ -2690,8 +2710,10 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
       a.pivot_rule = env != NULL ? atoi(env) : 3;
    }
    a.prof_on = prof;
+   pp->prof = prof;
    const int nofb = (getenv("HIPSDP_SOLVE1_NO_FALLBACK") != NULL && getenv("HIPSDP_SOLVE1_NO_FALLBACK")[0] == '1') ? 1 : 0;    /* (read at every solve, like the other switches of this path) */
    a.keep_on_fail = nofb ? 0 : 1;
+   pp->nofb = nofb;
    a.gws = s->s1_ws; a.gws_len = s->s1_ws_len;
    a.out = s->s1_host_dev;
    a.hist = (getenv("HIPSDP_SOLVE1_HIST") != NULL && getenv("HIPSDP_SOLVE1_HIST")[0] != '0') ? s->s1_host_dev + HS_S1_OUT_DOUBLES + 8 : NULL;
@@ -2706,18 +2728,24 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
       a.cmd_bytes = (long long) ((used + 15) & ~(size_t) 15);         /* (the arena's size is a multiple of 16) */
    }
    s->ncmd = 0;
-   HS_CALL( hs_solve1_launch(st, &a) );
+   *offered = true;
+   return HS_OK;
+}
+
+/* spin on the sequence word of the launch on st */
+static int solve1_wait(hipsdp_solver* s, unsigned long long seq, hipStream_t st)
+{
    {
       volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s->s1_host + HS_S1_OUT_DOUBLES);
       long long spins = 0;
-      while ( *flag != a.seq )
+      while ( *flag != seq )
       {
          if ( (++spins & 0x3FFF) == 0 )
          {
             const hipError_t e = hipStreamQuery(st);
             if ( e == hipSuccess )
             {
-               if ( *flag == a.seq )
+               if ( *flag == seq )
                   break;
                set_err("the one-launch solve finished without publishing its results");
                return HS_ERR_HIP;
@@ -2731,6 +2759,17 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
       }
       __atomic_thread_fence(__ATOMIC_ACQUIRE);
    }
+   return HS_OK;
+}
+
+/* *done = true: the solve ran there; false: the kernel declined (too much work for one compute unit) or gave up numerically, and the
+ * general path takes the problem from the same start */
+static int solve1_finish(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, bool* done)
+{
+   *done = false;
+   const hipsdp_params& par = s->par;
+   hipStream_t st = s->stream;
+   const int prof = pp->prof, nofb = pp->nofb;
    const double* o = s->s1_host;
    const int status = (int) o[0];
    if ( status == -2 )
@@ -2779,7 +2818,7 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
    info->schur_calls = info->iterations;
    for (auto& B : s->blk)
       info->schur_flops += (double) info->iterations * (4.0 * (s->m + 1) * (double) B.n * B.n * B.n + (double) (s->m + 1) * (s->m + 1) * (double) B.n * B.n);
-   info->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+   info->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - pp->t_begin).count();
    if ( prof )
    {
       static const char* const names[12] = {"lists", "start", "residuals", "inverse factors + LP part", "Zinv", "Schur", "chol M + X Rd",
@@ -2800,7 +2839,22 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
    return HS_OK;
 }
 
-static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
+static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
+{
+   *done = false;
+   S1Prep pp;
+   bool offered = false;
+   HS_CALL( solve1_prepare(s, &pp, &offered) );
+   if ( !offered )
+      return HS_OK;
+   HS_CALL( hs_solve1_launch(s->stream, &pp.a) );
+   HS_CALL( solve1_wait(s, pp.a.seq, s->stream) );
+   return solve1_finish(s, &pp, info, done);
+}
+
+/* a solve in two parts: solve_begin checks the solver and normalises the parameters (once per solve), solve_run solves - with the
+ * one-launch kernel first when try1 (hipsdp_solve), or on the general path alone (hipsdp_solve_many, which has run the kernel) */
+static int solve_begin(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
 {
    g_err[0] = 0;
    if ( s == NULL || !s->shaped || info == NULL )
@@ -2842,6 +2896,24 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
       if ( s->par.lanczos_steps < 4 ) s->par.lanczos_steps = 4;
       if ( s->par.lanczos_steps > 250 ) s->par.lanczos_steps = 250;
    }
+   return HIPSDP_OK;
+}
+
+/* the state every solve starts from (before the one-launch kernel is offered the problem) */
+static void solve_reset(hipsdp_solver* s, hipsdp_info* info)
+{
+   hs_comm_phase(2);
+   for (int p = 0; p < PH_COUNT; ++p) s->pc.ms[p] = 0.0;
+   memset(info, 0, sizeof(*info));
+   info->status = HIPSDP_STATUS_UNSOLVED;
+   hs_red_batch_reset();
+   s->pre_valid = false;
+   s->clk_n = 0;
+   s->clk_ghz = 0.0;
+}
+
+static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
+{
    const hipsdp_params& par = s->par;
    /* the retry ladder of the backend (sdpisolver_sdpa.cpp:1415-1449: fast / default / stable parameter sets): more conservative
     * settings take shorter steps, keep the iterates more central and wait longer before they call a stall (oracle/ipm_ref.py:
@@ -2852,18 +2924,12 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
    const int nobest_lim = settings == 0 ? 6 : (settings == 1 ? 10 : 15);
    const double sigma_floor = settings == 0 ? 1e-8 : (settings == 1 ? 1e-4 : 1e-2);
    const int maxiter = par.maxiter;
-   hs_comm_phase(2);
-   for (int p = 0; p < PH_COUNT; ++p) s->pc.ms[p] = 0.0;
    const int m = s->m, m1 = s->m + 1, q = s->q;
    const int K = (int) s->blk.size();
    hipStream_t st = s->stream;
    const auto t_begin = std::chrono::steady_clock::now();
-   memset(info, 0, sizeof(*info));
-   info->status = HIPSDP_STATUS_UNSOLVED;
-   hs_red_batch_reset();
-   s->pre_valid = false;
-   s->clk_n = 0;
-   s->clk_ghz = 0.0;
+   solve_reset(s, info);
+   if ( try1 )
    {
       bool done1 = false;
       HS_CALL( solve1_try(s, info, &done1) );
@@ -4005,6 +4071,274 @@ static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info
    info->settings_used = settings;
    info->schur_seconds = schur_ms * 1e-3;
    info->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+   return HIPSDP_OK;
+}
+
+static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
+{
+   HS_CALL( solve_begin(s, params, info) );
+   return solve_run(s, info, true);
+}
+
+/* ---- many problems at once: one launch of the one-launch kernel per size class, one workgroup per problem -------------------- */
+
+/* per host thread and grow-only (two threads may call hipsdp_solve_many at the same time): the kernels' arguments staged in pinned
+ * memory and their copy in device memory (read throughout the solve: never left in coherent host memory), and the events that order
+ * the launches against the solvers' queues.  A call has waited for every launch it made before it returns, so the next call may
+ * write them again. */
+struct ManyStage
+{
+   int device = -1;
+   size_t cap = 0;                         /* hs_solve1_args in h and d */
+   hs_solve1_args* h = NULL;
+   hs_solve1_args* d = NULL;
+   std::vector<hipEvent_t> ev;
+   void release_args()
+   {
+      if ( h != NULL ) (void) hipHostFree(h);
+      if ( d != NULL ) (void) hipFree(d);
+      h = NULL; d = NULL; cap = 0;
+   }
+   void release()
+   {
+      release_args();
+      for (hipEvent_t e : ev) (void) hipEventDestroy(e);
+      ev.clear();
+      device = -1;
+   }
+   ~ManyStage() { release(); }
+};
+static thread_local ManyStage g_many;
+
+static int many_stage(int device, size_t nargs, size_t nev)
+{
+   ManyStage& g = g_many;
+   if ( g.device != device )
+   {
+      g.release();
+      g.device = device;
+   }
+   if ( g.cap < nargs )
+   {
+      g.release_args();
+      const size_t cap = nargs + nargs / 2 + 16;
+      HS_HIP( hipHostMalloc((void**) &g.h, cap * sizeof(hs_solve1_args), hipHostMallocDefault) );
+      HS_HIP( hipMalloc((void**) &g.d, cap * sizeof(hs_solve1_args)) );
+      g.cap = cap;
+   }
+   while ( g.ev.size() < nev )
+   {
+      hipEvent_t e = NULL;
+      HS_HIP( hipEventCreateWithFlags(&e, hipEventDisableTiming) );
+      g.ev.push_back(e);
+   }
+   return HIPSDP_OK;
+}
+
+static bool many_hip_ok(hipError_t e, const char* what, int line)
+{
+   if ( e == hipSuccess )
+      return true;
+   hs_record_hip_error(e, what, __FILE__, line);
+   return false;
+}
+
+extern "C" int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const hipsdp_params* params, hipsdp_info* infos, int* rcs)
+{
+   g_err[0] = 0;
+   if ( count < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( count == 0 )
+      return HIPSDP_OK;
+   if ( solvers == NULL || infos == NULL )
+      return HIPSDP_ERR_ARG;
+   for (int i = 0; i < count; ++i)
+   {
+      const hipsdp_solver* s = solvers[i];
+      if ( s == NULL || !s->shaped )
+      {
+         set_err("hipsdp_solve_many: a solver is NULL or has no shape");
+         return HIPSDP_ERR_ARG;
+      }
+      if ( s->comm != NULL || s->device != solvers[0]->device )
+      {
+         set_err("hipsdp_solve_many: the solvers must be on one device and have no communicator");
+         return HIPSDP_ERR_ARG;
+      }
+   }
+   {
+      std::vector<const hipsdp_solver*> u(solvers, solvers + count);
+      std::sort(u.begin(), u.end());
+      if ( std::adjacent_find(u.begin(), u.end()) != u.end() )
+      {
+         set_err("hipsdp_solve_many: the same solver twice");
+         return HIPSDP_ERR_ARG;
+      }
+   }
+   const int dev = solvers[0]->device;
+   HS_HIP( hipSetDevice(dev) );
+   HS_CALL( many_stage(dev, (size_t) count, (size_t) count + 4) );
+
+   /* 1. what hipsdp_solve does before the kernel, for each solver, and the kernel's arguments */
+   static const int classes[4] = {10, 16, 64, 1064};
+   struct Item { int rc; bool offered, launched, done; int cls; S1Prep pp; };
+   std::vector<Item> it((size_t) count);
+   std::vector<int> members[4];
+   for (int i = 0; i < count; ++i)
+   {
+      hipsdp_solver* s = solvers[i];
+      Item& I = it[i];
+      I.offered = I.launched = I.done = false;
+      I.cls = -1;
+      int rc = flush_zeros(s);
+      if ( rc == HIPSDP_OK )
+         rc = solve_begin(s, params != NULL ? &params[i] : NULL, &infos[i]);
+      if ( rc == HIPSDP_OK )
+      {
+         solve_reset(s, &infos[i]);
+         rc = solve1_prepare(s, &I.pp, &I.offered);
+      }
+      I.rc = rc;
+      if ( rc == HIPSDP_OK && I.offered )
+      {
+         const int c = hs_solve1_class(&I.pp.a);
+         I.cls = c == 10 ? 0 : (c == 16 ? 1 : (c == 64 ? 2 : 3));
+         members[I.cls].push_back(i);
+      }
+   }
+
+   /* 2. one launch per class, on the queue of its first solver, behind everything queued on every member's queue (the staged
+    * setters); every member's queue then waits for the launch, so X and Z are complete once that queue has drained, as after
+    * hipsdp_solve */
+   ManyStage& g = g_many;
+   hipStream_t lst[4] = {NULL, NULL, NULL, NULL};
+   size_t off = 0, nev = 0;
+   for (int c = 0; c < 4; ++c)
+   {
+      const std::vector<int>& mem = members[c];
+      const int n = (int) mem.size();
+      if ( n == 0 )
+         continue;
+      hipStream_t L = solvers[mem[0]]->stream;
+      for (int j = 0; j < n; ++j)
+         memcpy(&g.h[off + j], &it[mem[j]].pp.a, sizeof(hs_solve1_args));
+      bool ok = true;
+      for (int j = 1; j < n && ok; ++j)
+      {
+         hipEvent_t e = g.ev[nev++];
+         ok = many_hip_ok(hipEventRecord(e, solvers[mem[j]]->stream), "hipEventRecord(member queue)", __LINE__) &&
+              many_hip_ok(hipStreamWaitEvent(L, e, 0), "hipStreamWaitEvent(launch queue)", __LINE__);
+      }
+      ok = ok && many_hip_ok(hipMemcpyAsync(g.d + off, g.h + off, (size_t) n * sizeof(hs_solve1_args), hipMemcpyHostToDevice, L),
+                             "hipMemcpyAsync(solve-many arguments)", __LINE__);
+      ok = ok && hs_solve1_launch_many(L, classes[c], g.d + off, n) == HS_OK;
+      if ( ok )
+      {
+         hipEvent_t e = g.ev[nev++];
+         ok = many_hip_ok(hipEventRecord(e, L), "hipEventRecord(launch queue)", __LINE__);
+         for (int j = 1; j < n && ok; ++j)
+            ok = many_hip_ok(hipStreamWaitEvent(solvers[mem[j]]->stream, e, 0), "hipStreamWaitEvent(member queue)", __LINE__);
+      }
+      if ( ok )
+      {
+         lst[c] = L;
+         (void) __sync_add_and_fetch(&g_many_launches, 1);
+      }
+      for (int j = 0; j < n; ++j)
+      {
+         it[mem[j]].launched = ok;
+         if ( !ok )
+            it[mem[j]].rc = HIPSDP_ERR_HIP;
+      }
+      off += (size_t) n;
+   }
+
+   /* 3. the sequence words of all launched problems, polled together; a launch queue that has finished while a member's word is
+    * missing: that launch failed (asked at the cadence of hipsdp_solve's wait, counted in words read) */
+   {
+      std::vector<char> pend((size_t) count, 0);
+      int left = 0;
+      for (int i = 0; i < count; ++i)
+         if ( it[i].launched ) { pend[i] = 1; ++left; }
+      auto published = [&](int i) -> bool {
+         const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(solvers[i]->s1_host + HS_S1_OUT_DOUBLES);
+         return *flag == it[i].pp.a.seq;
+      };
+      long long spins = 0;
+      while ( left > 0 )
+      {
+         for (int i = 0; i < count; ++i)
+            if ( pend[i] && published(i) ) { pend[i] = 0; --left; }
+         spins += left + 1;
+         if ( left == 0 || spins < 0x4000 )
+            continue;
+         spins = 0;
+         for (int c = 0; c < 4; ++c)
+         {
+            if ( lst[c] == NULL )
+               continue;
+            bool any = false;
+            for (int i : members[c]) any = any || pend[i];
+            if ( !any )
+               continue;
+            const hipError_t e = hipStreamQuery(lst[c]);
+            if ( e == hipErrorNotReady )
+               continue;
+            if ( e != hipSuccess )
+               hs_record_hip_error(e, "hipStreamQuery(one-launch solve of many)", __FILE__, __LINE__);
+            for (int i : members[c])
+               if ( pend[i] )
+               {
+                  pend[i] = 0; --left;
+                  if ( e == hipSuccess && published(i) )
+                     continue;
+                  if ( e == hipSuccess )
+                     set_err("the one-launch solve finished without publishing its results");
+                  it[i].rc = HIPSDP_ERR_HIP;
+               }
+         }
+      }
+      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+   }
+
+   /* 4. the results, then the general path for the problems the kernel declined or gave up on (from the same start) and the ones
+    * never offered, one after another as hipsdp_solve would solve them */
+   for (int i = 0; i < count; ++i)
+   {
+      Item& I = it[i];
+      hipsdp_solver* s = solvers[i];
+      if ( I.rc == HIPSDP_OK && I.launched )
+      {
+         I.rc = solve1_finish(s, &I.pp, &infos[i], &I.done);
+         if ( I.rc == HIPSDP_OK && I.done )
+         {
+            s->stage_off = 0;                                   /* (the kernel ran the commands and read their data at its start) */
+            (void) __sync_add_and_fetch(&g_many_problems, 1);
+         }
+      }
+      if ( I.rc != HIPSDP_OK || I.done )
+         I.rc = solve_end(s, I.rc);
+   }
+   int rc_all = HIPSDP_OK;
+   for (int i = 0; i < count; ++i)
+   {
+      Item& I = it[i];
+      if ( I.rc == HIPSDP_OK && !I.done )
+         I.rc = solve_end(solvers[i], solve_run(solvers[i], &infos[i], false));
+      if ( rcs != NULL )
+         rcs[i] = I.rc;
+      if ( rc_all == HIPSDP_OK )
+         rc_all = I.rc;
+   }
+   return rc_all;
+}
+
+extern "C" int hipsdp_solve_many_stats(long long* launches, long long* problems)
+{
+   if ( launches != NULL )
+      *launches = __sync_add_and_fetch(&g_many_launches, 0);
+   if ( problems != NULL )
+      *problems = __sync_add_and_fetch(&g_many_problems, 0);
    return HIPSDP_OK;
 }
 

@@ -1880,8 +1880,8 @@ template<bool AL, class T> __device__ __forceinline__ typename S1Ptr<AL, T>::typ
 #define S1_SETUP_STAMP(i) do { if ( P.prof_on == 2 && P.hist != NULL && tid == 0 ) P.hist[2048 + 480 + (i)] = (double) (clock64() - t_start); } while (0)
 #define S1_STAMP(id) do { if ( P.prof_on && tid == 0 ) { const long long t_ = clock64(); sh.prof[id] += (double) (t_ - sh.t_last); sh.t_last = t_; } } while (0)
 
-__global__ void __launch_bounds__(S1_NT) S1_KERNEL(const hs_solve1_args P)
-{
+__global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
+{  S1_BIND_P
    extern __shared__ __attribute__((aligned(16))) double sm[];
    __shared__ S1Sh sh;
    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -4031,6 +4031,19 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(const hs_solve1_args P)
 
 static hs_attr_mask s1_attr_done;
 
+#ifdef S1_MANY
+/* count problems of this class in one launch: dev_args holds count hs_solve1_args in device memory, one workgroup each (the whole LDS
+ * of a compute unit: at most one per CU runs at a time, the rest wait in the dispatcher) */
+int S1_LAUNCH_MANY(hipStream_t st, const hs_solve1_args* dev_args, int count)
+{
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&S1_KERNEL), S1_DYN_LDS, &s1_attr_done) );
+   hipLaunchKernelGGL(S1_KERNEL, dim3(count), dim3(S1_NT), S1_DYN_LDS, st, dev_args);
+   if ( hipGetLastError() != hipSuccess )
+      return HS_ERR_HIP;
+   return HS_OK;
+}
+#define S1_DBG_NAME S1_LAUNCH_MANY
+#else
 int S1_LAUNCH(hipStream_t st, const hs_solve1_args* a)
 {
    HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&S1_KERNEL), S1_DYN_LDS, &s1_attr_done) );
@@ -4039,12 +4052,14 @@ int S1_LAUNCH(hipStream_t st, const hs_solve1_args* a)
       return HS_ERR_HIP;
    return HS_OK;
 }
+#define S1_DBG_NAME S1_LAUNCH
+#endif
 
 
 #define S1_CAT2(a, b) a##b
 #define S1_CAT(a, b) S1_CAT2(a, b)
 /* debug counters of this instance (all zero in a release build) */
-int S1_CAT(S1_LAUNCH, _dbg)(unsigned int* out4)
+int S1_CAT(S1_DBG_NAME, _dbg)(unsigned int* out4)
 {
 #ifdef S1_DEBUG
    return hipMemcpyFromSymbol(out4, HIP_SYMBOL(s1_dbg), 4 * sizeof(unsigned int)) == hipSuccess ? 1 : -1;
