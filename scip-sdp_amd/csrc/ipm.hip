@@ -110,6 +110,7 @@ struct hipsdp_solver
    hipStream_t stream2;          /* second queue: the Z-side chains run beside the X-side ones (both are latency bound) */
    hipEvent_t evFork, evJoin;
    bool use2;                    /* false for tiny blocks: they are launch bound and the cross-queue events only add latency */
+   bool busy2;                   /* stream2 has work that stream has not joined (fork2 / join2) */
    int m, q;
    int sparse_policy;            /* 0: blocks are never kept as nonzeros, 1: when the caller's count makes it cheaper, 2: whenever a count is given */
    std::vector<Block> blk;
@@ -1699,6 +1700,7 @@ static int fork2(hipsdp_solver* s)
 {
    if ( !s->use2 )
       return HS_OK;
+   s->busy2 = true;
    HS_HIP( hipEventRecord(s->evFork, s->stream) );
    HS_HIP( hipStreamWaitEvent(s->stream2, s->evFork, 0) );
    return HS_OK;
@@ -1708,6 +1710,7 @@ static int join2(hipsdp_solver* s)
 {
    if ( !s->use2 )
       return HS_OK;
+   s->busy2 = false;
    HS_HIP( hipEventRecord(s->evJoin, s->stream2) );
    HS_HIP( hipStreamWaitEvent(s->stream, s->evJoin, 0) );
    return HS_OK;
@@ -2448,7 +2451,8 @@ struct CommOff        /* the communicator is out of sight while a replicated (sm
    ~CommOff() { if ( on ) s->comm = saved; }
 };
 
-static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info);
+static int solve_begin(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info);
+static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1);
 
 static int sync_outcome(hipsdp_solver* s, int rc, hipsdp_info* info)
 {
@@ -2520,12 +2524,6 @@ static int solve_end(hipsdp_solver* s, int rc)
       (void) hipStreamSynchronize(s->stream);
       (void) hipStreamSynchronize(s->stream2);
    }
-   if ( s->pc.open >= 0 )          /* an error return inside the iteration: close the roctx range, drop the marks */
-   {
-      phase_mark(s, -1);
-      (void) hipStreamSynchronize(s->stream);
-      phase_finish(s);
-   }
    return rc;
 }
 
@@ -2541,7 +2539,9 @@ extern "C" int hipsdp_solve(hipsdp_solver* s, const hipsdp_params* params, hipsd
    int rc;
    {
       CommOff off(s, alone);
-      rc = solve_impl(s, params, info);
+      rc = solve_begin(s, params, info);
+      if ( rc == HIPSDP_OK )
+         rc = solve_run(s, info, true);
    }
    rc = solve_end(s, rc);
    if ( alone )
@@ -2912,9 +2912,29 @@ static void solve_reset(hipsdp_solver* s, hipsdp_info* info)
    s->clk_ghz = 0.0;
 }
 
-static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
+/* hs_schur_ws.after_g1 of the W form (argument: the solver): R = Lx itself is the operand of the first product and G = LzInv of the
+ * second only, so the inverse factor of X follows the first product into the second queue, and ev_g2 makes the second product wait */
+static int after_g1_x_inverse(void* arg)
 {
+   hipsdp_solver* s = static_cast<hipsdp_solver*>(arg);
+   HS_CALL( fork2(s) );              /* (behind hs_zero_upper of Lx and the first product) */
+   for (auto& B : s->blk)
+      HS_CALL( hs_trtri(s->stream2, B.n, B.Lx, B.dinvx, B.LxInv, B.T1) );
+   HS_HIP( hipEventRecord(s->evJoin, s->stream2) );
+   s->sws.ev_g2 = (void*) s->evJoin;
+   return HS_OK;
+}
+
+/* one solve on the general path: its constants, the bookkeeping of the iterate and one member function per phase of an iteration.
+ * It lives on solve_run's stack, and every way out of it goes through close(). */
+struct GeneralSolve
+{
+   hipsdp_solver* const s;
+   hipsdp_info* const info;
+   const std::chrono::steady_clock::time_point t_begin;
    const hipsdp_params& par = s->par;
+   const hipStream_t st = s->stream;
+   const int m = s->m, m1 = s->m + 1, q = s->q, K = (int) s->blk.size();
    /* the retry ladder of the backend (sdpisolver_sdpa.cpp:1415-1449: fast / default / stable parameter sets): more conservative
     * settings take shorter steps, keep the iterates more central and wait longer before they call a stall (oracle/ipm_ref.py:
     * Params.settings, same numbers) */
@@ -2923,135 +2943,25 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
    const int stall_lim = settings == 0 ? 3 : (settings == 1 ? 5 : 8);
    const int nobest_lim = settings == 0 ? 6 : (settings == 1 ? 10 : 15);
    const double sigma_floor = settings == 0 ? 1e-8 : (settings == 1 ? 1e-4 : 1e-2);
-   const int maxiter = par.maxiter;
-   const int m = s->m, m1 = s->m + 1, q = s->q;
-   const int K = (int) s->blk.size();
-   hipStream_t st = s->stream;
-   const auto t_begin = std::chrono::steady_clock::now();
-   solve_reset(s, info);
-   if ( try1 )
-   {
-      bool done1 = false;
-      HS_CALL( solve1_try(s, info, &done1) );
-      if ( done1 )
-      {
-         s->stage_off = 0;                                      /* (the kernel ran the commands and read their data at its start) */
-         return HIPSDP_OK;
-      }
-   }
-   HS_CALL( stage_sync(s) );                                  /* the general path uses both queues */
-   HS_CALL( ensure_schur_ws(s) );
-   HS_CALL( ensure_packed(s) );
-   {
-      int nmaxb = 0;
-      for (auto& B : s->blk) if ( B.n > nmaxb ) nmaxb = B.n;
-      s->use2 = nmaxb >= 128;
-   }
-
-   long long N = q;
-   for (auto& B : s->blk) N += B.n;
-   const double N1 = (double) (N + 1);
-
-   /* norms of b and of the constant part (host needs them once) */
-   HS_CALL( hs_dot(st, m, s->b, s->b, s->sc + 0, 0, s->red_ws) );
-   HS_CALL( hs_fill(st, s->sc + 1, 1, 0.0) );
-   for (auto& B : s->blk)
-      HS_CALL( hs_dot(st, (long long) B.n * B.n, B.A0, B.A0, s->sc + 1, 1, s->red_ws) );
-   if ( q > 0 )
-   {
-      /* column 0 of Dext: strided -> gather through gemv with unit vector would be overkill; copy it */
-      HS_HIP( hipMemcpy2DAsync(s->tmpq, sizeof(double), s->Dext, (size_t) m1 * sizeof(double), sizeof(double), (size_t) q, hipMemcpyDeviceToDevice, st) );
-      HS_CALL( hs_dot(st, q, s->tmpq, s->tmpq, s->sc + 1, 1, s->red_ws) );
-   }
-   /* (into the pinned mirror of the scalars: a copy into a stack variable is staged by the runtime and blocks) */
-   HS_HIP( hipMemcpyAsync(s->hsc, s->sc, 2 * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   const double normb = sqrt(s->hsc[0]);
-   const double normC = sqrt(s->hsc[1]);
-
-   /* ---- starting point */
-   /* cold start: X = Z = xi I in every block until the first step - the first Schur complement is then the Gram matrix of the
-    * constraint matrices themselves, M_ij = tr(A_i (xi I) A_j (I / xi)) = <A_i, A_j>, and the two n^3 products of the assembly
-    * (which would multiply by sqrt(xi) I and I / sqrt(xi)) are not needed for it (round 5; single rank, dense blocks, W form) */
-   bool identity_start = false;
-   bool start_factors = false;
-   for (auto& B : s->blk)
-      B.derived_valid = false;
-   if ( s->have_start )
-   {
-      /* a caller-supplied point (warm start, sdpisolver.h:160-173) is used when it is strictly interior: X_k, Z_k positive
-       * definite (checked by the factorizations the first iteration needs anyway) and x, z > 0; kappa = its mean
-       * complementarity (tau = 1).  Otherwise the solve falls back to the cold start below. */
-      HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
-      HS_CALL( hs_fill(st, s->sc + SC_XZ, 1, 0.0) );
-      for (auto& B : s->blk)
-      {
-         const long long n2 = (long long) B.n * B.n;
-         HS_CALL( hs_symmetrize(st, B.X, B.n) );
-         HS_CALL( hs_symmetrize(st, B.Z, B.n) );
-         HS_CALL( hs_copy(st, B.Lz, B.Z, n2) );
-         HS_CALL( hs_potrf(st, B.n, B.Lz, B.dinvz, s->flags + 0, NULL) );
-         HS_CALL( hs_copy(st, B.Lx, B.X, n2) );
-         HS_CALL( hs_potrf(st, B.n, B.Lx, B.dinvx, s->flags + 1, NULL) );
-         HS_CALL( hs_dot(st, n2, B.X, B.Z, s->sc + SC_XZ, 1, s->red_ws) );
-      }
-      if ( q > 0 )
-      {
-         hipLaunchKernelGGL(k_flag_nonpositive, g1d(q), dim3(256), 0, st, q, s->x, s->z, s->flags + 3);
-         HS_LAUNCH_CHECK();
-         HS_CALL( hs_dot(st, q, s->x, s->z, s->sc + SC_XZ, 1, s->red_ws) );
-      }
-      int f4[4];
-      double xz = 0.0;
-      HS_HIP( hipMemcpyAsync(s->hsc + 4, s->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, st) );
-      HS_HIP( hipMemcpyAsync(s->hsc + 8, s->sc + SC_XZ, sizeof(double), hipMemcpyDeviceToHost, st) );
-      HS_HIP( hipStreamSynchronize(st) );
-      memcpy(f4, s->hsc + 4, sizeof(f4));
-      xz = s->hsc[8];
-      const double mu0 = xz / (double) (N > 0 ? N : 1);
-      if ( f4[0] == 0 && f4[1] == 0 && f4[3] == 0 && std::isfinite(mu0) && mu0 > 0.0 )
-      {
-         s->tau = 1.0;
-         s->kappa = mu0;
-         start_factors = true;
-      }
-      else
-         s->have_start = false;
-   }
-   if ( !s->have_start )
-   {
-      const double xi = fmax(1.0, sqrt(fmax(fmax(normb, normC), 1.0)));
-      HS_CALL( hs_fill(st, s->y, m, 0.0) );
-      for (auto& B : s->blk)
-      {
-         HS_CALL( hs_set_identity(st, B.X, B.n, xi) );
-         HS_CALL( hs_set_identity(st, B.Z, B.n, xi) );
-      }
-      HS_CALL( hs_fill(st, s->x, q, xi) );
-      HS_CALL( hs_fill(st, s->z, q, xi) );
-      s->tau = 1.0;
-      s->kappa = xi * xi;
-      identity_start = true;
-   }
-   info->warm_started = s->have_start ? 1 : 0;
-   s->have_start = false;
    /* HIPSDP_NO_IDENTITY_START=1: the first assembly of a cold solve through the general products as well (A/B runs, tests) */
-   if ( getenv("HIPSDP_NO_IDENTITY_START") != NULL && getenv("HIPSDP_NO_IDENTITY_START")[0] == '1' )
-      identity_start = false;
+   const bool no_identity_start = getenv("HIPSDP_NO_IDENTITY_START") != NULL && getenv("HIPSDP_NO_IDENTITY_START")[0] == '1';
+   const bool optimistic = (s->comm == NULL) && getenv("HIPSDP_NO_OPTIMISTIC") == NULL;
+   /* (test hook, tests/test_gpu_ipm.py: HIPSDP_TEST_OVERSTEP=<factor> lengthens the step of iteration 2 beyond the boundary of the
+    * cone, so that the rarely taken road - failed check, step halved, optimistic part taken back - is driven) */
+   const char* const overstep = getenv("HIPSDP_TEST_OVERSTEP");
 
-   int status = HIPSDP_STATUS_ITERLIM;
-   int it = 0, certwait = 0, nstall = 0;
-   double lastmu = 1e300, alpha_last = 1.0, bestmerit = 1e300;
-   int sincebest = 0;
-   double mu = 0, pinf = 0, dinf = 0, dabs = 0, gap = 0, pobj = 0, dobj = 0;
-   HostScalars hs;
-   int hflags[3] = {0, 0, 0};
+   double N1 = 0.0, normb = 0.0, normC = 0.0;
+   bool small_all = false;            /* one rank, every block of at most 64 rows */
+   int setf = 0;
+   bool defer_ok = false;             /* the W form may await the second queue between its products (after_g1_x_inverse) */
+   hipStream_t st2 = NULL;            /* the second queue, or the first when the blocks are too small for two */
+
+   int it = 0, status = HIPSDP_STATUS_ITERLIM;
+   bool stop = false;
+   bool identity_start = false;
+   bool factors_valid = false;        /* the Cholesky factors of X and Z are those of the current iterate */
+   bool residuals_ready = false;      /* the residual pass of the current iterate has been read back */
    bool want_cert = false;
-   bool factors_valid = start_factors;      /* the factors of an accepted warm start are those of the first iteration */
-   double schur_ms = 0.0;
-
-   /* ---- residuals of the current iterate: enqueued at the top of an iteration, or (small problems) already at the end of
-    * the previous one together with the step's Cholesky check, so that one read-back serves both */
    /* The dual residual obeys an exact recurrence: dZ is DEFINED as A^T(dy~) + eta Rd, so after the update (y~, Z) += alpha
     * (dy~, dZ) the new residual is (1 - alpha eta) Rd whatever the quality of dy (forced pivots included), and likewise for the
     * LP rows.  The general path (blocks above 64 rows: each pass over A is HBM bound, 1 GB at n = 500 / m = 1000) therefore
@@ -3060,7 +2970,232 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
    bool rd_have = false;             /* Rd / rd hold the residual of SOME iterate: the current one once rd_pending is worked off */
    bool rd_pending = false;
    double rd_scale = 1.0;
-   auto enqueue_residuals = [&]() -> int
+   bool zchain_queued = false, xchain_queued = false;      /* the chains of this iterate's factorization phase are queued */
+
+   int certwait = 0, nstall = 0, sincebest = 0;
+   double lastmu = 1e300, alpha_last = 1.0, bestmerit = 1e300;
+
+   /* the last host scalars and what the phases of an iteration hand on */
+   HostScalars hs;
+   int hflags[3] = {0, 0, 0};
+   double mu = 0, pinf = 0, dinf = 0, dabs = 0, gap = 0, pobj = 0, dobj = 0, rg = 0;
+   double schur_ms = 0.0;
+   bool defer_join = false, gram_only_used = false, schur_small = false;
+   bool predH_queued = false, predH_joined = false, split_dz = false;
+   double dta = 0, dka = 0, sigma = 0, eta = 0, amax = 0, alpha = 0, dt = 0, dk = 0;
+   double tau0 = 0, kappa0 = 0, applied = 0;
+
+   int halt(int why) { status = why; stop = true; return HS_OK; }
+
+   /* L = chol(M) on the queue qf, the failure flag in flags[f] */
+   int factor(hipStream_t qf, int n, double* L, double* dinv, const double* M, int f)
+   {
+      HS_CALL( hs_copy(qf, L, M, (long long) n * n) );
+      return hs_potrf(qf, n, L, dinv, s->flags + f, NULL);
+   }
+
+   /* the Z chain of the factorization phase for one block: factor (unless the step's Cholesky check has), inverse factor, Z^-1 */
+   int z_chain(Block& B, hipStream_t qz)
+   {
+      const int n = B.n;
+      if ( !factors_valid )
+         HS_CALL( factor(qz, n, B.Lz, B.dinvz, B.Z, 0) );
+      HS_CALL( hs_trtri(qz, n, B.Lz, B.dinvz, B.LzInv, B.T2) );
+      HS_CALL( gemm_on(qz, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
+      return hs_mirror_lower(qz, B.Zinv, n, n);
+   }
+
+   /* the X chain for one block: factor (likewise), zero upper triangle, inverse factor (unless after_g1_x_inverse launches it) */
+   int x_chain(Block& B, bool inverse)
+   {
+      const int n = B.n;
+      if ( !factors_valid )
+         HS_CALL( factor(st, n, B.Lx, B.dinvx, B.X, 1) );
+      HS_CALL( hs_zero_upper(st, B.Lx, n) );
+      return inverse ? hs_trtri(st, n, B.Lx, B.dinvx, B.LxInv, B.T1) : HS_OK;
+   }
+
+   /* the Z chains need nothing from the residual pass: on the second queue, they run beside it and beside the host's read-back */
+   int queue_z_chains()
+   {
+      HS_CALL( fork2(s) );
+      for (auto& B : s->blk)
+         if ( B.n > 64 )
+            HS_CALL( z_chain(B, st2) );
+      zchain_queued = true;
+      return HS_OK;
+   }
+
+   /* Reads the scalars back.  With the Z chains under way, the X chains do not depend on the scalars either: they are queued behind
+    * the kernel that publishes them and run while the host waits, decides and launches (a solve that ends here has run them in vain:
+    * 0.1 ms at n = 500).
+    * INVARIANT: the X chain is speculative - when the solve ends at this read-back, B.Lx, B.dinvx, B.LxInv, B.T1 and flags[1] already
+    * hold the factors of the FINAL X.  Lx, LxInv, dinvx and T1 are therefore UNDEFINED after solve_run returns (nothing reads them:
+    * every getter works from X, Z, y; the next solve refactors).  The chain's time is charged to PH_RESID, not PH_FACTOR, in the
+    * phase anatomy (bench.py says so next to those two figures). */
+   int read_back(int* flags3)
+   {
+      const std::function<int()> x_chains = [this]() -> int
+      {
+         for (auto& B : s->blk)
+            if ( B.n > 64 )
+               HS_CALL( x_chain(B, true) );
+         xchain_queued = true;
+         return HS_OK;
+      };
+      const bool with_x = zchain_queued && !xchain_queued && s->comm == NULL && !(factors_valid && defer_ok);
+      return read_scalars(s, hs, flags3, with_x ? &x_chains : NULL);
+   }
+
+   /* blocks of at most 64 rows keep the trial iterate of a step in Xs / Zs: swapped in, and back on a failed check */
+   void swap_trial()
+   {
+      for (auto& B : s->blk)
+         if ( B.n <= 64 )
+         {
+            std::swap(B.X, B.Xs);
+            std::swap(B.Z, B.Zs);
+         }
+   }
+
+   int apply_step()
+   {
+      HS_CALL( hs_axpy3(st, alpha - applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
+      applied = alpha;
+      s->tau = tau0 + alpha * dt;
+      s->kappa = kappa0 + alpha * dk;
+      return HS_OK;
+   }
+
+   /* no step length keeps X and Z positive definite: the step is taken back (the part applied when undo) and the solve stops */
+   int give_up(bool undo)
+   {
+      if ( par.verbose )
+         printf("hipsdp: no step length down to %g keeps X and Z positive definite\n", alpha);
+      if ( undo )
+      {
+         HS_CALL( hs_axpy3(st, -applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
+         s->tau = tau0;
+         s->kappa = kappa0;
+      }
+      for (auto& B : s->blk)
+      {
+         B.derived_valid = false;
+         if ( B.n <= 64 )
+            continue;         /* X, Z were never overwritten */
+         HS_CALL( hs_copy(st, B.X, B.Xs, (long long) B.n * B.n) );
+         HS_CALL( hs_copy(st, B.Z, B.Zs, (long long) B.n * B.n) );
+      }
+      return halt(HIPSDP_STATUS_NUMERIC);
+   }
+
+   /* ---- norms of b and of the constant part, the constants of the solve, the starting point */
+   int start()
+   {
+      HS_CALL( stage_sync(s) );                                  /* the general path uses both queues */
+      HS_CALL( ensure_schur_ws(s) );
+      HS_CALL( ensure_packed(s) );
+      int nmaxb = 0;
+      long long N = q;
+      small_all = (s->comm == NULL);
+      for (auto& B : s->blk)
+      {
+         nmaxb = std::max(nmaxb, B.n);
+         N += B.n;
+         small_all = small_all && B.n <= 64;
+      }
+      s->use2 = nmaxb >= 128;
+      st2 = s->use2 ? s->stream2 : st;
+      N1 = (double) (N + 1);
+      /* one block of at most 64 rows: every Cholesky flag has exactly one writing launch between two reads, which then stores its
+       * result itself and the flags need no clearing */
+      setf = (small_all && K == 1) ? 1 : 0;
+      defer_ok = s->use2 && s->comm == NULL && !s->shardA && !s->schur_mode_cols && !s->schur_mode_rows && !s->schur_mode_U
+         && !s->schur_mode_forced && K > 0;
+      for (auto& B : s->blk)
+         defer_ok = defer_ok && B.n > 64 && !B.sparse;
+
+      HS_CALL( hs_dot(st, m, s->b, s->b, s->sc + 0, 0, s->red_ws) );
+      HS_CALL( hs_fill(st, s->sc + 1, 1, 0.0) );
+      for (auto& B : s->blk)
+         HS_CALL( hs_dot(st, (long long) B.n * B.n, B.A0, B.A0, s->sc + 1, 1, s->red_ws) );
+      if ( q > 0 )
+      {
+         /* column 0 of Dext: strided -> gather through gemv with unit vector would be overkill; copy it */
+         HS_HIP( hipMemcpy2DAsync(s->tmpq, sizeof(double), s->Dext, (size_t) m1 * sizeof(double), sizeof(double), (size_t) q, hipMemcpyDeviceToDevice, st) );
+         HS_CALL( hs_dot(st, q, s->tmpq, s->tmpq, s->sc + 1, 1, s->red_ws) );
+      }
+      /* (into the pinned mirror of the scalars: a copy into a stack variable is staged by the runtime and blocks) */
+      HS_HIP( hipMemcpyAsync(s->hsc, s->sc, 2 * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      normb = sqrt(s->hsc[0]);
+      normC = sqrt(s->hsc[1]);
+
+      /* cold start: X = Z = xi I in every block until the first step - the first Schur complement is then the Gram matrix of the
+       * constraint matrices themselves, M_ij = tr(A_i (xi I) A_j (I / xi)) = <A_i, A_j>, and the two n^3 products of the assembly
+       * (which would multiply by sqrt(xi) I and I / sqrt(xi)) are not needed for it (single rank, dense blocks, W form) */
+      for (auto& B : s->blk)
+         B.derived_valid = false;
+      if ( s->have_start )
+      {
+         /* a caller-supplied point (warm start, sdpisolver.h:160-173) is used when it is strictly interior: X_k, Z_k positive
+          * definite (checked by the factorizations the first iteration needs anyway) and x, z > 0; kappa = its mean
+          * complementarity (tau = 1).  Otherwise the solve falls back to the cold start below. */
+         HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
+         HS_CALL( hs_fill(st, s->sc + SC_XZ, 1, 0.0) );
+         for (auto& B : s->blk)
+         {
+            const long long n2 = (long long) B.n * B.n;
+            HS_CALL( hs_symmetrize(st, B.X, B.n) );
+            HS_CALL( hs_symmetrize(st, B.Z, B.n) );
+            HS_CALL( factor(st, B.n, B.Lz, B.dinvz, B.Z, 0) );
+            HS_CALL( factor(st, B.n, B.Lx, B.dinvx, B.X, 1) );
+            HS_CALL( hs_dot(st, n2, B.X, B.Z, s->sc + SC_XZ, 1, s->red_ws) );
+         }
+         if ( q > 0 )
+         {
+            hipLaunchKernelGGL(k_flag_nonpositive, g1d(q), dim3(256), 0, st, q, s->x, s->z, s->flags + 3);
+            HS_LAUNCH_CHECK();
+            HS_CALL( hs_dot(st, q, s->x, s->z, s->sc + SC_XZ, 1, s->red_ws) );
+         }
+         int f4[4];
+         HS_HIP( hipMemcpyAsync(s->hsc + 4, s->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, st) );
+         HS_HIP( hipMemcpyAsync(s->hsc + 8, s->sc + SC_XZ, sizeof(double), hipMemcpyDeviceToHost, st) );
+         HS_HIP( hipStreamSynchronize(st) );
+         memcpy(f4, s->hsc + 4, sizeof(f4));
+         const double mu0 = s->hsc[8] / (double) (N > 0 ? N : 1);
+         if ( f4[0] == 0 && f4[1] == 0 && f4[3] == 0 && std::isfinite(mu0) && mu0 > 0.0 )
+         {
+            s->tau = 1.0;
+            s->kappa = mu0;
+            factors_valid = true;      /* the factors of an accepted warm start are those of the first iteration */
+         }
+         else
+            s->have_start = false;
+      }
+      if ( !s->have_start )
+      {
+         const double xi = fmax(1.0, sqrt(fmax(fmax(normb, normC), 1.0)));
+         HS_CALL( hs_fill(st, s->y, m, 0.0) );
+         for (auto& B : s->blk)
+         {
+            HS_CALL( hs_set_identity(st, B.X, B.n, xi) );
+            HS_CALL( hs_set_identity(st, B.Z, B.n, xi) );
+         }
+         HS_CALL( hs_fill(st, s->x, q, xi) );
+         HS_CALL( hs_fill(st, s->z, q, xi) );
+         s->tau = 1.0;
+         s->kappa = xi * xi;
+         identity_start = !no_identity_start;
+      }
+      info->warm_started = s->have_start ? 1 : 0;
+      s->have_start = false;
+      return HS_OK;
+   }
+
+   /* ---- residuals of the current iterate: enqueued at the top of an iteration, or already at the end of the previous one
+    * together with the step's Cholesky check, so that one read-back serves both */
+   int enqueue_residuals()
    {
       const bool recur = rd_have && !want_cert;
       HS_CALL( hs_make_ext(st, m, -s->tau, 1.0, s->y, s->yt) );
@@ -3118,140 +3253,44 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
       }
       else
          HS_CALL( hs_fill_scalar(st, s->sc + SC_RDLPMAX, 0.0) );
+      const int fusedA = apply_A_small(s, Xs.data(), s->x, s->AX, 2, s->tau, s->b, s->rp);
+      if ( fusedA < 0 )
+         return -fusedA;
+      if ( fusedA == 0 )
+         HS_CALL( apply_A(s, Xs.data(), s->x, s->AX) );
+      HS_CALL( hs_copy_scalar(st, s->sc + SC_AX0, s->AX) );
+      if ( fusedA == 0 )
       {
-         const int fusedA = apply_A_small(s, Xs.data(), s->x, s->AX, 2, s->tau, s->b, s->rp);
-         if ( fusedA < 0 )
-            return -fusedA;
-         if ( fusedA == 0 )
-            HS_CALL( apply_A(s, Xs.data(), s->x, s->AX) );
-         HS_CALL( hs_copy_scalar(st, s->sc + SC_AX0, s->AX) );
-         if ( fusedA == 0 )
-         {
-            HS_CALL( hs_red_batch_flush() );
-            hipLaunchKernelGGL(k_rp, g1d(m > 0 ? m : 1), dim3(256), 0, st, m, s->tau, s->b, s->AX, s->rp);
-            HS_LAUNCH_CHECK();
-         }
+         HS_CALL( hs_red_batch_flush() );
+         hipLaunchKernelGGL(k_rp, g1d(m > 0 ? m : 1), dim3(256), 0, st, m, s->tau, s->b, s->AX, s->rp);
+         HS_LAUNCH_CHECK();
       }
       HS_CALL( hs_dot(st, m, s->rp, s->rp, s->sc + SC_RP2, 0, s->red_ws) );
       HS_CALL( hs_dot(st, m, s->AX + 1, s->AX + 1, s->sc + SC_HP2, 0, s->red_ws) );
       HS_CALL( hs_dot(st, m, s->b, s->y, s->sc + SC_DOBJ, 0, s->red_ws) );
       rd_pending = false;
       return HS_OK;
-   };
-   bool residuals_ready = false;
-   bool small_all = (s->comm == NULL);
-   for (auto& B : s->blk)
-      if ( B.n > 64 )
-         small_all = false;
-   /* one block of at most 64 rows: every Cholesky flag has exactly one writing launch between two reads, which then stores its
-    * result itself and the flags need no clearing */
-   const int setf = (small_all && s->blk.size() == 1) ? 1 : 0;
+   }
 
-   /* Overlap on the second queue (blocks of at least 128 rows):
-    *  - the Z chain of the factorization phase (inverse factor, Z^-1) needs nothing from the residual pass, so it is started at
-    *    the top of the iteration and runs beside the residual kernels and the host's read-back of the termination scalars;
-    *  - the predictor's right-hand side (H_k, A(H), h) needs nothing from the Schur matrix, so it runs beside the latency-bound
-    *    factorization of M (one communicator serves one queue: not with several ranks). */
-   bool zchain_queued = false;
-   auto enqueue_z_chains = [&]() -> int
+   int residual_pass()
    {
-      hipStream_t st2 = s->stream2;
-      for (auto& B : s->blk)
+      phase_mark(s, PH_RESID);
+      if ( s->use2 && !zchain_queued && K > 0 )
       {
-         const int n = B.n;
-         const long long n2 = (long long) n * n;
-         if ( n <= 64 )
-            continue;
-         if ( !factors_valid )
-         {
-            HS_CALL( hs_copy(st2, B.Lz, B.Z, n2) );
-            HS_CALL( hs_potrf(st2, n, B.Lz, B.dinvz, s->flags + 0, NULL) );
-         }
-         HS_CALL( hs_trtri(st2, n, B.Lz, B.dinvz, B.LzInv, B.T2) );
-         HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
-         HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
+         HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
+         HS_CALL( queue_z_chains() );
       }
-      return HS_OK;
-   };
+      HS_CALL( enqueue_residuals() );
+      return read_back(NULL);
+   }
 
-   /* round 5: the X chain of the factorization phase (triangular inverse of the factor of X) does not depend on the termination
-    * scalars either: it is queued behind the kernel that publishes them and runs while the host waits, decides and launches (a
-    * solve that ends here has run it in vain: 0.1 ms at n = 500).
-    * INVARIANT: the chain is speculative - when the solve ends at this read-back, B.Lx, B.dinvx, B.LxInv, B.T1 and
-    * flags[1] already hold the factors of the FINAL X.  Lx, LxInv, dinvx and T1 are therefore UNDEFINED after solve_impl returns
-    * (nothing reads them: every getter works from X, Z, y; the next solve refactors).  The chain's time is charged to PH_RESID, not
-    * PH_FACTOR, in the phase anatomy (bench.py says so next to those two figures). */
-   bool xchain_queued = false;
-   const std::function<int()> enqueue_x_chains = [&]() -> int
+   /* ---- termination (mirrors oracle/ipm_ref.py) */
+   int terminate()
    {
-      if ( xchain_queued )
-         return HS_OK;
-      for (auto& B : s->blk)
-      {
-         const int n = B.n;
-         if ( n <= 64 )
-            continue;
-         if ( !factors_valid )
-         {
-            HS_CALL( hs_copy(st, B.Lx, B.X, (long long) n * n) );
-            HS_CALL( hs_potrf(st, n, B.Lx, B.dinvx, s->flags + 1, NULL) );
-         }
-         HS_CALL( hs_zero_upper(st, B.Lx, n) );
-         HS_CALL( hs_trtri(st, n, B.Lx, B.dinvx, B.LxInv, B.T1) );
-      }
-      xchain_queued = true;
-      return HS_OK;
-   };
-   /* round 6: every block above 64 rows, one rank, the W formulation (W_j = G A_j R): the inverse factor of X is not an operand of the
-    * assembly (R = Lx itself) and G = LzInv is the operand of its SECOND product only.  The chains of the second queue are then
-    * awaited between the first and the second product (hs_schur_ws.ev_g2), and the inverse factor of X is put into the second queue
-    * when the first product has been launched (hs_schur_ws.after_g1) - 75 us of device time and as much of the host's launching that
-    * stood between the termination decision and the assembly (profiles/r06_*_iter_sequence.txt). */
-   auto defer_possible = [&]() -> bool
-   {
-      if ( !(s->use2 && s->comm == NULL && !s->shardA && !s->schur_mode_cols && !s->schur_mode_rows
-            && !s->schur_mode_U && !s->schur_mode_forced && K > 0) )
-         return false;
-      for (auto& B : s->blk)
-         if ( B.n <= 64 || B.sparse )
-            return false;
-      return true;
-   };
-   struct AfterG1 { hipsdp_solver* s; };
-   AfterG1 after_g1_arg = {s};
-   auto after_g1_fn = [](void* p) -> int
-   {
-      hipsdp_solver* s = static_cast<AfterG1*>(p)->s;
-      HS_HIP( hipEventRecord(s->evFork, s->stream) );              /* (behind hs_zero_upper of Lx and the first product) */
-      HS_HIP( hipStreamWaitEvent(s->stream2, s->evFork, 0) );
-      for (auto& B : s->blk)
-         HS_CALL( hs_trtri(s->stream2, B.n, B.Lx, B.dinvx, B.LxInv, B.T1) );
-      HS_HIP( hipEventRecord(s->evJoin, s->stream2) );
-      s->sws.ev_g2 = (void*) s->evJoin;
-      return HS_OK;
-   };
-
-   for (it = 0; it <= maxiter; ++it)
-   {
-      if ( !residuals_ready )
-      {
-         phase_mark(s, PH_RESID);
-         if ( s->use2 && !zchain_queued && K > 0 )
-         {
-            HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
-            HS_CALL( fork2(s) );
-            HS_CALL( enqueue_z_chains() );
-            zchain_queued = true;
-         }
-         HS_CALL( enqueue_residuals() );
-         HS_CALL( read_scalars(s, hs, NULL, (zchain_queued && s->comm == NULL && !(factors_valid && defer_possible())) ? &enqueue_x_chains : NULL) );
-      }
-      residuals_ready = false;
-
       const double tau = s->tau, kappa = s->kappa;
       pobj = hs.v[SC_AX0];
       dobj = hs.v[SC_DOBJ];
-      const double rg = pobj - dobj - kappa;
+      rg = pobj - dobj - kappa;
       mu = (hs.v[SC_XZ] + tau * kappa) / N1;
       double rd2 = hs.v[SC_RD2];
       double rdmax = hs.v[SC_RDLPMAX];
@@ -3269,14 +3308,12 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
       if ( par.verbose )
          printf("hipsdp it %3d mu %.3e pinf %.3e dinf %.3e gap %.3e pobj %.8e dobj %.8e tau %.3e kap %.3e\n", it, mu, pinf, dinf,
             gap, pobj / tau, dobj / tau, tau, kappa);
-
       if ( !std::isfinite(mu) || !std::isfinite(pinf) || !std::isfinite(dinf) )
       {
-         status = HIPSDP_STATUS_NUMERIC;
-         break;
+         return halt(HIPSDP_STATUS_NUMERIC);
       }
-      /* ---- preoptimal iterate (warm-start point for the children of a node: relax_sdp.c "warmstartpreoptsol"): the first
-       * interior iterate that is feasible to tolerance with a relative gap below preoptgap, as DSDP's monitor captures it
+      /* preoptimal iterate (warm-start point for the children of a node: relax_sdp.c "warmstartpreoptsol"): the first interior
+       * iterate that is feasible to tolerance with a relative gap below preoptgap, as DSDP's monitor captures it
        * (sdpisolver_dsdp.c:323-358) */
       if ( par.preoptgap > 0.0 && !s->pre_valid && pinf <= par.feastol && dabs <= par.feastol
          && gap / (1.0 + 0.5 * fabs(pobj / tau) + 0.5 * fabs(dobj / tau)) < par.preoptgap )
@@ -3297,18 +3334,15 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          s->pre_scale = 1.0 / tau;
          s->pre_valid = true;
       }
-      /* ---- termination (mirrors oracle/ipm_ref.py) */
       /* objective limit: with X feasible to tolerance, pobj is a lower bound of the minimisation problem
        * (SCIP_SDPPAR_OBJLIMIT, type_sdpi.h:53); tested first so that a node whose optimum lies above the limit reports it */
       if ( par.objlimit < 1e20 && pinf <= par.feastol && pobj / tau > par.objlimit + par.gaptol )
       {
-         status = HIPSDP_STATUS_OBJLIM;
-         break;
+         return halt(HIPSDP_STATUS_OBJLIM);
       }
       if ( pinf <= par.feastol && pabsok && dabs <= par.feastol && gap <= par.gaptol )
       {
-         status = HIPSDP_STATUS_OPTIMAL;
-         break;
+         return halt(HIPSDP_STATUS_OPTIMAL);
       }
       const bool certzone = (tau < 1e-2 * fmin(1.0, kappa)) || (mu / (tau * tau) > 1e10);
       if ( certzone && want_cert )
@@ -3322,8 +3356,7 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          const bool ok_dinf = cand_dinf && hp <= par.infeastol * pobj;
          if ( (ok_dunb || ok_dinf) && (ok_dunb || !cand_dunb || certwait >= 5) && (ok_dinf || !cand_dinf || certwait >= 5) )
          {
-            status = (ok_dunb && ok_dinf) ? HIPSDP_STATUS_PDINF : (ok_dunb ? HIPSDP_STATUS_DUNB : HIPSDP_STATUS_DINF);
-            break;
+            return halt((ok_dunb && ok_dinf) ? HIPSDP_STATUS_PDINF : (ok_dunb ? HIPSDP_STATUS_DUNB : HIPSDP_STATUS_DINF));
          }
          if ( ok_dunb || ok_dinf )
             ++certwait;
@@ -3332,18 +3365,17 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
       {
          /* the certificate residual was not computed in this pass: redo the (cheap) residual pass with it */
          want_cert = true;
-         --it;
-         continue;
+         HS_CALL( residual_pass() );
+         return terminate();
       }
       want_cert = certzone;
-      if ( it == maxiter )
-         break;
+      if ( it == par.maxiter )
+         return halt(status);
       if ( mu > 0.9 * lastmu && alpha_last < 1e-2 )
       {
          if ( ++nstall >= stall_lim )
          {
-            status = HIPSDP_STATUS_NUMERIC;
-            break;
+            return halt(HIPSDP_STATUS_NUMERIC);
          }
       }
       else
@@ -3362,8 +3394,7 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          }
          else if ( ++sincebest >= nobest_lim )
          {
-            status = HIPSDP_STATUS_NUMERIC;
-            break;
+            return halt(HIPSDP_STATUS_NUMERIC);
          }
       }
       if ( par.timelimit > 0.0 )
@@ -3380,14 +3411,17 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          }
          if ( over )
          {
-            status = HIPSDP_STATUS_TIMELIM;
-            break;
+            return halt(HIPSDP_STATUS_TIMELIM);
          }
       }
+      return HS_OK;
+   }
 
-      /* ---- factorizations (the factors of an accepted step are re-used: they were computed by its Cholesky check) */
+   /* ---- factorizations (the factors of an accepted step are re-used: they were computed by its Cholesky check) */
+   int factorize()
+   {
       phase_mark(s, PH_FACTOR);
-      const bool defer_join = defer_possible() && !(identity_start && it == 0) && !xchain_queued;
+      defer_join = defer_ok && !(identity_start && it == 0) && !xchain_queued;
       if ( !zchain_queued )
       {
          if ( !(setf && m <= 64) )
@@ -3397,64 +3431,41 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
       for (auto& B : s->blk)
       {
          const int n = B.n;
-         const long long n2 = (long long) n * n;
-         hipStream_t st2 = s->use2 ? s->stream2 : s->stream;
-         if ( n <= 64 )
+         if ( n > 64 )
          {
-            /* single-block factors: one launch per matrix yields L (zero upper), inv(L) as n x n and, for n <= 32, the inverse
-             * of Z; after an accepted step they already exist (the step's Cholesky check produced them) */
-            if ( !(factors_valid && B.derived_valid) )
-            {
-               HS_CALL( hs_potrf_small_ext(st2, n, B.Lz, B.dinvz, s->flags + 0, B.Z, NULL, 0.0, NULL, B.LzInv, n <= 32 ? B.Zinv : NULL, setf) );
-               HS_CALL( hs_potrf_small_ext(st, n, B.Lx, B.dinvx, s->flags + 1, B.X, NULL, 0.0, NULL, B.LxInv, NULL, setf) );
-               B.derived_valid = true;
-            }
-            if ( n > 32 )
-            {
-               HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
-               HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
-            }
+            if ( !zchain_queued )
+               HS_CALL( z_chain(B, st2) );
+            if ( !xchain_queued )
+               HS_CALL( x_chain(B, !defer_join) );
             continue;
          }
-         /* Z chain on the second queue (already under way when it was started at the top of the iteration) */
-         if ( !zchain_queued )
+         /* single-block factors: one launch per matrix yields L (zero upper), inv(L) as n x n and, for n <= 32, the inverse of Z;
+          * after an accepted step they already exist (the step's Cholesky check produced them) */
+         if ( !(factors_valid && B.derived_valid) )
          {
-         if ( !factors_valid )
-         {
-            HS_CALL( hs_copy(st2, B.Lz, B.Z, n2) );
-            HS_CALL( hs_potrf(st2, n, B.Lz, B.dinvz, s->flags + 0, NULL) );
+            HS_CALL( hs_potrf_small_ext(st2, n, B.Lz, B.dinvz, s->flags + 0, B.Z, NULL, 0.0, NULL, B.LzInv, n <= 32 ? B.Zinv : NULL, setf) );
+            HS_CALL( hs_potrf_small_ext(st, n, B.Lx, B.dinvx, s->flags + 1, B.X, NULL, 0.0, NULL, B.LxInv, NULL, setf) );
+            B.derived_valid = true;
          }
-         HS_CALL( hs_trtri(st2, n, B.Lz, B.dinvz, B.LzInv, B.T2) );
-         HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
-         HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
-         }
-         /* X chain on the first (already queued behind the read-back when the Z chain was started at the top of the iteration) */
-         if ( !xchain_queued )
+         if ( n > 32 )
          {
-         if ( !factors_valid )
-         {
-            HS_CALL( hs_copy(st, B.Lx, B.X, n2) );
-            HS_CALL( hs_potrf(st, n, B.Lx, B.dinvx, s->flags + 1, NULL) );
-         }
-         HS_CALL( hs_zero_upper(st, B.Lx, n) );
-         if ( !defer_join )
-            HS_CALL( hs_trtri(st, n, B.Lx, B.dinvx, B.LxInv, B.T1) );
+            HS_CALL( gemm_on(st2, HS_MC, HS_MC, n, n, n, 1.0, B.LzInv, n, B.LzInv, n, 0.0, B.Zinv, n, HS_GEMM_LOWER) );
+            HS_CALL( hs_mirror_lower(st2, B.Zinv, n, n) );
          }
       }
-      if ( defer_join )
-      {
-         /* (the inverse factor of X follows the first product into the second queue; the event is recorded behind it) */
-         s->sws.after_g1 = after_g1_fn;
-         s->sws.after_g1_arg = &after_g1_arg;
-      }
-      else
-         HS_CALL( join2(s) );
-      zchain_queued = false;
-      xchain_queued = false;
+      zchain_queued = xchain_queued = false;
+      if ( !defer_join )
+         return join2(s);
+      s->sws.after_g1 = after_g1_x_inverse;
+      s->sws.after_g1_arg = s;
+      return HS_OK;
+   }
 
-      /* ---- Schur complement (extended by the constant matrix as "variable 0") */
+   /* ---- Schur complement (extended by the constant matrix as "variable 0") */
+   int assemble()
+   {
       phase_mark(s, PH_SCHUR);
-      bool gram_only_used = false;
+      gram_only_used = false;
       hs_comm_phase(0);
       const bool clk_this = s->clk_on && s->clk_buf != NULL && s->clk_stream != NULL && s->clk_n < CLK_MAX_ASSEMBLIES;
       HS_HIP( hipEventRecord(s->ev0, st) );
@@ -3468,30 +3479,48 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          HS_LAUNCH_CHECK();
       }
       const double mfma_flops_before = hs_mfma_flops_total();
-      bool schur_small = false;
+      schur_small = false;
       if ( s->comm == NULL && !s->shardA && !s->schur_mode_rows && !s->schur_mode_forced && K > 0 )
       {
          /* B&B-sized problems: one launch for the whole extended Schur matrix and the copies the factorization needs */
          std::vector<int> bn;
          std::vector<const double*> bA, bX, bZ;
+         bool anysp = false;
          for (auto& B : s->blk)
          {
             bn.push_back(B.n); bA.push_back(B.A); bX.push_back(B.X); bZ.push_back(B.Zinv);
+            anysp = anysp || B.sparse;
          }
-         bool anysp = false;
-         for (auto& B : s->blk) anysp = anysp || B.sparse;
          const int rs = anysp ? 0 : hs_schur_small(st, m1, K, bn.data(), bA.data(), bX.data(), bZ.data(), q, s->Dext, s->x, s->z, s->Mx,
             m > 0 ? s->Lm : NULL, s->dya);
          if ( rs < 0 )
             return -rs;
          schur_small = (rs == 1);
       }
-      if ( schur_small )
+      if ( !schur_small )
+         HS_CALL( assemble_forms() );
+      if ( defer_join )
       {
-         /* nothing else to assemble */
+         /* (the first queue has waited for the event inside hs_schur_W; once more for whoever follows, and the hooks are taken out) */
+         s->sws.ev_g2 = NULL;
+         s->sws.after_g1 = NULL;
+         HS_CALL( join2(s) );
       }
-      else
+      HS_HIP( hipEventRecord(s->ev1, st) );
+      if ( clk_this )
       {
+         hipLaunchKernelGGL(k_clock_stop, dim3(1), dim3(1), 0, st, s->clk_buf + 4 * s->clk_n);
+         HS_LAUNCH_CHECK();
+         ++s->clk_n;
+      }
+      info->schur_flops_executed += hs_mfma_flops_total() - mfma_flops_before;
+      hs_comm_phase(2);
+      return HS_OK;
+   }
+
+   /* the assembly in the form the solver's mode selects, then the sparse blocks and the LP term */
+   int assemble_forms()
+   {
       HS_CALL( hs_fill(st, s->Mx, (long long) m1 * m1, 0.0) );
       if ( s->shardA )
       {
@@ -3600,28 +3629,18 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          HS_CALL( hs_lp_scale_rows(st, q, m1, s->x, s->z, s->Dext, s->Slp) );
          HS_CALL( gemm(s, HS_MC, HS_MC, m1, m1, q, 1.0, s->Dext, m1, s->Slp, m1, 1.0, s->Mx, m1, HS_GEMM_LOWER) );
       }
-      HS_CALL( hs_mirror_lower(st, s->Mx, m1, m1) );
-      }
-      if ( defer_join )
-      {
-         /* (the first queue has waited for the event inside hs_schur_W; once more for whoever follows, and the hooks are taken out) */
-         s->sws.ev_g2 = NULL;
-         s->sws.after_g1 = NULL;
-         HS_CALL( join2(s) );
-      }
-      HS_HIP( hipEventRecord(s->ev1, st) );
-      if ( clk_this )
-      {
-         hipLaunchKernelGGL(k_clock_stop, dim3(1), dim3(1), 0, st, s->clk_buf + 4 * s->clk_n);
-         HS_LAUNCH_CHECK();
-         ++s->clk_n;
-      }
-      info->schur_flops_executed += hs_mfma_flops_total() - mfma_flops_before;
-      hs_comm_phase(2);
+      return hs_mirror_lower(st, s->Mx, m1, m1);
+   }
+
+   /* ---- solves with M, then B_k = A_0 - sum w_i A_i ; beta = c - D w ; S0 ; b^T M^-1 b */
+   int solve_m()
+   {
       phase_mark(s, PH_MSOLVE);
-      bool predH_queued = false, predH_joined = false, split_dz = false;
+      predH_queued = predH_joined = split_dz = false;
       if ( s->use2 && s->comm == NULL && !small_problem(s) && m > 0 )
       {
+         /* the predictor's right-hand side (H_k, A(H), h) needs nothing from the Schur matrix: it runs on the second queue beside the
+          * latency-bound factorization of M (one communicator serves one queue: not with several ranks) */
          HS_CALL( fork2(s) );
          {
             QueueSwap sw(s);
@@ -3666,7 +3685,6 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          hipLaunchKernelGGL(k_after_solve2, g1d(m1), dim3(256), 0, st, m, s->rhs2, s->u2, s->wt);
          HS_LAUNCH_CHECK();
       }
-      /* B_k = A_0 - sum w_i A_i ; beta = c - D w ; S0 ; b^T M^-1 b */
       hs_red_batch_begin(st);
       HS_CALL( hs_fill_scalar(st, s->sc + SC_S0, 0.0) );
       /* dZ = A^T([-dtau; u1 - u2 dtau]) + eta Rd is linear in dtau: A^T([0; u1]) - dtau A^T([1; u2]) + eta Rd.  u2 belongs to the
@@ -3674,23 +3692,22 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
        * P1 = A^T([0; u1]) come out of ONE sweep over A (three coefficient vectors), the corrector needs one more sweep for its P1:
        * two sweeps per iteration where B, the predictor's dZ and the corrector's dZ took three - and the dependent chain
        * B pass -> dtau -> dZ pass loses a link.  Single GPU, packed copy present, predictor solved early (else the old form). */
-      bool split_ok = predH_joined && s->comm == NULL;
+      split_dz = predH_joined && s->comm == NULL;
       for (auto& B : s->blk)
          if ( B.Apk == NULL )
-            split_ok = false;
-      if ( split_ok )
+            split_dz = false;
+      if ( split_dz )
       {
          HS_CALL( hs_make_ext(st, m, 1.0, 1.0, s->u2, s->cvec) );
          HS_CALL( hs_make_ext(st, m, 0.0, 1.0, s->u1, s->cvec + m1) );
          HS_LAUNCH_CHECK();
       }
-      split_dz = split_ok;
       for (auto& B : s->blk)
       {
          const int n = B.n;
          const long long n2 = (long long) n * n;
          bool swept = false;
-         if ( split_ok )
+         if ( split_dz )
          {
             if ( B.P2 == NULL )
             {
@@ -3726,76 +3743,78 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          HS_CALL( hs_lp_s0(st, q, s->x, s->z, s->beta, s->sc + SC_S0, 1, s->red_ws) );
       }
       HS_CALL( hs_dot(st, m, s->b, s->rhs2 + m, s->sc + SC_BUB, 0, s->red_ws) );
-      HS_CALL( hs_red_batch_end() );
+      return hs_red_batch_end();
+   }
 
-      /* ---- predictor */
+   /* ---- predictor: its direction, step length and the centering it leaves to the corrector */
+   int predictor()
+   {
       phase_mark(s, PH_PRED);
       if ( predH_queued && !predH_joined )
          HS_CALL( join2(s) );
       HS_CALL( direction(s, 0.0, 1.0, mu, rg, false, 0.0, predH_queued ? 2 : 0, predH_joined, split_dz ? 2 : 0) );
       HS_CALL( steplen_enqueue(s) );
       HS_CALL( read_scalars(s, hs, hflags) );
-      {
-         float ms = 0.f;
-         if ( hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess )
-            schur_ms += ms;
-         info->schur_calls++;
-         /* (the assembly at the cold start is the Gram product alone: the count of SURVEY.md 8(d) without its n^3 part) */
-         const bool gram_only = gram_only_used;
-         for (auto& B : s->blk)
-            info->schur_flops += (gram_only && !B.sparse ? 0.0 : 4.0 * m1 * (double) B.n * B.n * B.n) + (double) m1 * m1 * (double) B.n * B.n;
-      }
+      float ms = 0.f;
+      if ( hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess )
+         schur_ms += ms;
+      info->schur_calls++;
+      /* (the assembly at the cold start is the Gram product alone: the count of SURVEY.md 8(d) without its n^3 part) */
+      for (auto& B : s->blk)
+         info->schur_flops += (gram_only_used && !B.sparse ? 0.0 : 4.0 * m1 * (double) B.n * B.n * B.n) + (double) m1 * m1 * (double) B.n * B.n;
       if ( hflags[0] != 0 || hflags[1] != 0 || hflags[2] != 0 )
       {
          if ( par.verbose )
             printf("hipsdp: Cholesky failure flags Z=%d X=%d M=%d\n", hflags[0], hflags[1], hflags[2]);
-         status = HIPSDP_STATUS_NUMERIC;
-         break;
+         return halt(HIPSDP_STATUS_NUMERIC);
       }
       const double aa = fmin(1.0, steplen_host(s, hs));
-      const double dta = hs.v[SC_DTAU], dka = hs.v[SC_DKAPPA];
+      dta = hs.v[SC_DTAU];
+      dka = hs.v[SC_DKAPPA];
       if ( !std::isfinite(aa) || !std::isfinite(dta) )
       {
          if ( par.verbose )
             printf("hipsdp: predictor not finite (alpha %g dtau %g)\n", aa, dta);
-         status = HIPSDP_STATUS_NUMERIC;
-         break;
+         return halt(HIPSDP_STATUS_NUMERIC);
       }
-      double sigma = (1.0 - aa) * (1.0 - aa) * (1.0 - aa);
+      sigma = (1.0 - aa) * (1.0 - aa) * (1.0 - aa);
       sigma = fmin(1.0, fmax(sigma_floor, sigma));
-      const double eta = 1.0 - sigma;
+      eta = 1.0 - sigma;
+      return HS_OK;
+   }
+
+   /* ---- corrector, with the second-order terms of the predictor */
+   int corrector()
+   {
       phase_mark(s, PH_CORR);
-      /* second-order terms from the predictor */
       for (auto& B : s->blk)
-      {
-         const int n = B.n;
-         const long long n2 = (long long) n * n;
-         HS_CALL( gemm(s, HS_KC, HS_MC, n, n, n, 1.0, B.dX, n, B.dZ, n, 0.0, B.E, n) );
-      }
+         HS_CALL( gemm(s, HS_KC, HS_MC, B.n, B.n, B.n, 1.0, B.dX, B.n, B.dZ, B.n, 0.0, B.E, B.n) );
       {
          /* (B&B-sized: the LP term and the whole corrector direction are one launch) */
          BatchRegion region(s, batch_regions(s));
          if ( q > 0 )
             HS_CALL( hs_vec_mul(st, q, s->dx, s->dz, s->elp) );
-
-         /* ---- corrector */
          HS_CALL( direction(s, sigma, eta, mu, rg, true, dta * dka, 0, false, split_dz ? 1 : 0) );
          HS_CALL( region.close() );
       }
       HS_CALL( steplen_enqueue(s) );
       HS_CALL( read_scalars(s, hs, NULL) );
-      const double amax = steplen_host(s, hs);
-      double alpha = fmin(1.0, gamma_eff * amax);
-      const double dt = hs.v[SC_DTAU], dk = hs.v[SC_DKAPPA];
+      amax = steplen_host(s, hs);
+      alpha = fmin(1.0, gamma_eff * amax);
+      dt = hs.v[SC_DTAU];
+      dk = hs.v[SC_DKAPPA];
       if ( !std::isfinite(alpha) || !std::isfinite(dt) || !std::isfinite(dk) )
       {
          if ( par.verbose )
             printf("hipsdp: corrector not finite (alpha %g dtau %g dkappa %g)\n", alpha, dt, dk);
-         status = HIPSDP_STATUS_NUMERIC;
-         break;
+         return halt(HIPSDP_STATUS_NUMERIC);
       }
+      return HS_OK;
+   }
 
-      /* ---- update, with a Cholesky check of the new X and Z (the Lanczos bound is an estimate) */
+   /* ---- update, with a Cholesky check of the new X and Z (the Lanczos bound is an estimate) */
+   int update()
+   {
       phase_mark(s, PH_UPDATE);
       for (auto& B : s->blk)
       {
@@ -3805,279 +3824,256 @@ static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
          HS_CALL( hs_copy(st, B.Xs, B.X, n2) );
          HS_CALL( hs_copy(st, B.Zs, B.Z, n2) );
       }
-      if ( small_all && K > 0 )
+      tau0 = s->tau;
+      kappa0 = s->kappa;
+      applied = 0.0;
+      return (small_all && K > 0) ? step_small() : step_general();
+   }
+
+   /* small problems: the whole step is applied optimistically and the residual phase of the next iteration is enqueued behind the
+    * Cholesky check, so that ONE read-back returns the flags and the new residuals; a failed check takes the step back (pointer
+    * swaps, a correcting axpy) and halves it */
+   int step_small()
+   {
+      for (int attempt = 0; attempt < 8; ++attempt)
       {
-         /* small problems: the whole step is applied optimistically and the residual phase of the next iteration is enqueued
-          * behind the Cholesky check, so that ONE read-back returns the flags and the new residuals; a failed check takes the
-          * step back (pointer swaps, a correcting axpy) and halves it */
-         const double tau0 = s->tau, kappa0 = s->kappa;
-         double applied = 0.0;
-         bool accepted = false;
-         for (int attempt = 0; attempt < 8; ++attempt)
-         {
-            if ( !setf )
-               HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
-            for (auto& B : s->blk)
-            {
-               const int n = B.n;
-               {
-                  /* the Cholesky checks of the trial X and Z: one launch of two workgroups */
-                  double* L2[2] = {B.Lx, B.Lz};
-                  double* di2[2] = {B.dinvx, B.dinvz};
-                  int* fl2[2] = {s->flags + 1, s->flags + 0};
-                  const double* ba2[2] = {B.X, B.Z};
-                  const double* dr2[2] = {B.dX, B.dZ};
-                  double* mo2[2] = {B.Xs, B.Zs};
-                  double* li2[2] = {B.LxInv, B.LzInv};
-                  double* gr2[2] = {NULL, n <= 32 ? B.Zinv : NULL};
-                  HS_CALL( hs_potrf_small_ext_pair(st, n, L2, di2, fl2, ba2, dr2, alpha, mo2, li2, gr2, setf) );
-               }
-               std::swap(B.X, B.Xs);
-               std::swap(B.Z, B.Zs);
-            }
-            if ( batch_regions(s) )
-               hs_red_batch_hold(st);           /* (the read-back below ends the region) */
-            HS_CALL( hs_axpy3(st, alpha - applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
-            applied = alpha;
-            s->tau = tau0 + alpha * dt;
-            s->kappa = kappa0 + alpha * dk;
-            HS_CALL( enqueue_residuals() );
-            HS_CALL( read_scalars(s, hs, hflags) );
-            if ( hflags[0] == 0 && hflags[1] == 0 )
-            {
-               accepted = true;
-               break;
-            }
-            for (auto& B : s->blk)
-            {
-               std::swap(B.X, B.Xs);
-               std::swap(B.Z, B.Zs);
-            }
-            alpha *= 0.5;
-            info->chol_fail++;
-         }
-         if ( !accepted )
-         {
-            if ( par.verbose )
-               printf("hipsdp: no step length down to %g keeps X and Z positive definite\n", alpha);
-            HS_CALL( hs_axpy3(st, -applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
-            s->tau = tau0;
-            s->kappa = kappa0;
-            for (auto& B : s->blk)
-               B.derived_valid = false;
-            status = HIPSDP_STATUS_NUMERIC;
-            break;
-         }
-         for (auto& B : s->blk)
-            B.derived_valid = true;
-         factors_valid = true;
-         residuals_ready = true;
-         alpha_last = alpha;
-      }
-      else
-      {
-         /* Round 6: one rank - the rest of the step (y, x, z, tau, kappa) is applied optimistically behind the Cholesky check of the
-          * new X and Z, and the residual pass of the NEXT iterate (the sweep A(X), the scaled dual residual, the reductions) and the
-          * chains of its factorization phase are queued behind that: ONE read-back returns the check's flags and the termination
-          * scalars of the next iteration, where there were two with an idle device between them (profiles/r06_a_iter_sequence.txt:
-          * 50 us waiting for the flags, then 200 us of small kernels arriving one launch at a time).  A failed check - rare: the
-          * step lengths are Lanczos estimates with a safety factor - halves the step as before; the optimistic part is taken back by
-          * a correcting axpy and the dual residual is recomputed from scratch at the next pass (its recurrence was applied in place). */
-         const bool optimistic = (s->comm == NULL) && getenv("HIPSDP_NO_OPTIMISTIC") == NULL;
-         /* (test hook, tests/test_gpu_ipm.py: HIPSDP_TEST_OVERSTEP=<factor> lengthens the step of iteration 2 beyond the boundary of the
-          * cone, so that the rarely taken road - failed check, step halved, optimistic part taken back - is driven) */
-         if ( it == 2 && getenv("HIPSDP_TEST_OVERSTEP") != NULL )
-            alpha = amax * atof(getenv("HIPSDP_TEST_OVERSTEP"));
-         const double tau0 = s->tau, kappa0 = s->kappa;
-         double applied = 0.0;
-         for (int attempt = 0; attempt < 8; ++attempt)
-         {
+         if ( !setf )
             HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
-            HS_CALL( fork2(s) );
+         for (auto& B : s->blk)
+         {
+            /* the Cholesky checks of the trial X and Z: one launch of two workgroups */
+            double* L2[2] = {B.Lx, B.Lz};
+            double* di2[2] = {B.dinvx, B.dinvz};
+            int* fl2[2] = {s->flags + 1, s->flags + 0};
+            const double* ba2[2] = {B.X, B.Z};
+            const double* dr2[2] = {B.dX, B.dZ};
+            double* mo2[2] = {B.Xs, B.Zs};
+            double* li2[2] = {B.LxInv, B.LzInv};
+            double* gr2[2] = {NULL, B.n <= 32 ? B.Zinv : NULL};
+            HS_CALL( hs_potrf_small_ext_pair(st, B.n, L2, di2, fl2, ba2, dr2, alpha, mo2, li2, gr2, setf) );
+         }
+         swap_trial();
+         if ( batch_regions(s) )
+            hs_red_batch_hold(st);           /* (the read-back below ends the region) */
+         HS_CALL( apply_step() );
+         HS_CALL( enqueue_residuals() );
+         HS_CALL( read_scalars(s, hs, hflags) );
+         if ( hflags[0] == 0 && hflags[1] == 0 )
+         {
             for (auto& B : s->blk)
+               B.derived_valid = true;
+            factors_valid = true;
+            residuals_ready = true;
+            alpha_last = alpha;
+            return HS_OK;
+         }
+         swap_trial();
+         alpha *= 0.5;
+         info->chol_fail++;
+      }
+      return give_up(true);
+   }
+
+   /* One rank: the rest of the step (y, x, z, tau, kappa) is applied optimistically behind the Cholesky check of the new X and Z, and
+    * the residual pass of the NEXT iterate (the sweep A(X), the scaled dual residual, the reductions) and the chains of its
+    * factorization phase are queued behind that: ONE read-back returns the check's flags and the termination scalars of the next
+    * iteration, where there were two with an idle device between them (profiles/r06_a_iter_sequence.txt: 50 us waiting for the flags,
+    * then 200 us of small kernels arriving one launch at a time).  A failed check - rare: the step lengths are Lanczos estimates with
+    * a safety factor - halves the step; the optimistic part is taken back by a correcting axpy and the dual residual is recomputed
+    * from scratch at the next pass (its recurrence was applied in place). */
+   int step_general()
+   {
+      if ( it == 2 && overstep != NULL )
+         alpha = amax * atof(overstep);
+      for (int attempt = 0; attempt < 8; ++attempt)
+      {
+         HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
+         HS_CALL( fork2(s) );
+         for (auto& B : s->blk)
+         {
+            const int n = B.n;
+            const long long n2 = (long long) n * n;
+            if ( n <= 64 )
             {
-               const int n = B.n;
-               const long long n2 = (long long) n * n;
-               hipStream_t st2 = s->use2 ? s->stream2 : s->stream;
-               if ( n <= 64 )
-               {
-                  HS_CALL( hs_potrf_small_ext(st, n, B.Lx, B.dinvx, s->flags + 1, B.X, B.dX, alpha, B.Xs, B.LxInv, NULL, setf) );
-                  HS_CALL( hs_potrf_small_ext(st2, n, B.Lz, B.dinvz, s->flags + 0, B.Z, B.dZ, alpha, B.Zs, B.LzInv, n <= 32 ? B.Zinv : NULL, setf) );
-                  continue;
-               }
-               HS_CALL( hs_scale_add(st, n2, alpha, B.dX, 1.0, B.Xs, B.X) );
-               HS_CALL( hs_copy(st, B.Lx, B.X, n2) );
-               HS_CALL( hs_potrf(st, n, B.Lx, B.dinvx, s->flags + 1, NULL) );
-               HS_CALL( hs_scale_add(st2, n2, alpha, B.dZ, 1.0, B.Zs, B.Z) );
-               HS_CALL( hs_copy(st2, B.Lz, B.Z, n2) );
-               HS_CALL( hs_potrf(st2, n, B.Lz, B.dinvz, s->flags + 0, NULL) );
-            }
-            HS_CALL( join2(s) );
-            if ( K == 0 )
-               break;
-            if ( optimistic )
-            {
-               /* (blocks of at most 64 rows: their trial iterate sits in Xs / Zs - swapped in now, back on a failure) */
-               for (auto& B : s->blk)
-                  if ( B.n <= 64 )
-                  {
-                     std::swap(B.X, B.Xs);
-                     std::swap(B.Z, B.Zs);
-                  }
-               HS_CALL( hs_axpy3(st, alpha - applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
-               applied = alpha;
-               s->tau = tau0 + alpha * dt;
-               s->kappa = kappa0 + alpha * dk;
-               factors_valid = true;                    /* (what the chains below test: the check has produced the factors) */
-               if ( s->use2 && !zchain_queued )
-               {
-                  HS_CALL( fork2(s) );
-                  HS_CALL( enqueue_z_chains() );
-                  zchain_queued = true;
-               }
-               if ( attempt == 0 )
-               {
-                  rd_have = !small_problem(s);
-                  rd_pending = rd_have;
-                  rd_scale = 1.0 - alpha * eta;
-               }
-               HS_CALL( enqueue_residuals() );
-               HS_CALL( read_scalars(s, hs, hflags, (zchain_queued && s->comm == NULL && !defer_possible()) ? &enqueue_x_chains : NULL) );
-               if ( hflags[0] == 0 && hflags[1] == 0 )
-                  break;
-               /* the step was too long: everything queued behind the check ran on an iterate that is given up */
-               for (auto& B : s->blk)
-                  if ( B.n <= 64 )
-                  {
-                     std::swap(B.X, B.Xs);
-                     std::swap(B.Z, B.Zs);
-                  }
-               factors_valid = false;
-               zchain_queued = false;
-               xchain_queued = false;
-               rd_have = false;
-               rd_pending = false;
-               alpha *= 0.5;
-               info->chol_fail++;
+               HS_CALL( hs_potrf_small_ext(st, n, B.Lx, B.dinvx, s->flags + 1, B.X, B.dX, alpha, B.Xs, B.LxInv, NULL, setf) );
+               HS_CALL( hs_potrf_small_ext(st2, n, B.Lz, B.dinvz, s->flags + 0, B.Z, B.dZ, alpha, B.Zs, B.LzInv, n <= 32 ? B.Zinv : NULL, setf) );
                continue;
             }
-            if ( s->comm != NULL )
-               HS_CALL( hs_bcast_ints(s->comm, s->flags, 3, st) );
+            HS_CALL( hs_scale_add(st, n2, alpha, B.dX, 1.0, B.Xs, B.X) );
+            HS_CALL( factor(st, n, B.Lx, B.dinvx, B.X, 1) );
+            HS_CALL( hs_scale_add(st2, n2, alpha, B.dZ, 1.0, B.Zs, B.Z) );
+            HS_CALL( factor(st2, n, B.Lz, B.dinvz, B.Z, 0) );
+         }
+         HS_CALL( join2(s) );
+         if ( K == 0 )
+            break;
+         if ( optimistic )
+         {
+            swap_trial();
+            HS_CALL( apply_step() );
+            factors_valid = true;                    /* (what the chains below test: the check has produced the factors) */
+            if ( s->use2 && !zchain_queued )
+               HS_CALL( queue_z_chains() );
+            if ( attempt == 0 )
+            {
+               rd_have = !small_problem(s);
+               rd_pending = rd_have;
+               rd_scale = 1.0 - alpha * eta;
+            }
+            HS_CALL( enqueue_residuals() );
+            HS_CALL( read_back(hflags) );
+            if ( hflags[0] == 0 && hflags[1] == 0 )
+               break;
+            /* the step was too long: everything queued behind the check ran on an iterate that is given up (the Z chains may still
+             * be running: s->busy2 stays set) */
+            swap_trial();
+            factors_valid = zchain_queued = xchain_queued = false;
+            rd_have = rd_pending = false;
+         }
+         else
+         {
             if ( s->comm == NULL )
                HS_CALL( publish_and_wait(s, s->nsc, 2) );
             else
             {
+               HS_CALL( hs_bcast_ints(s->comm, s->flags, 3, st) );
                HS_HIP( hipMemcpyAsync(s->hsc + s->nsc, s->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, st) );
                HS_HIP( hipStreamSynchronize(st) );
             }
             memcpy(hflags, s->hsc + s->nsc, 3 * sizeof(int));
             if ( hflags[0] == 0 && hflags[1] == 0 )
                break;
-            alpha *= 0.5;
-            info->chol_fail++;
          }
-         if ( K > 0 && (hflags[0] != 0 || hflags[1] != 0) )
-         {
-            if ( par.verbose )
-               printf("hipsdp: no step length down to %g keeps X and Z positive definite\n", alpha);
-            if ( optimistic && applied != 0.0 )
-            {
-               HS_CALL( hs_axpy3(st, -applied, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
-               s->tau = tau0;
-               s->kappa = kappa0;
-            }
-            for (auto& B : s->blk)
-            {
-               const long long n2 = (long long) B.n * B.n;
-               B.derived_valid = false;
-               if ( B.n <= 64 )
-                  continue;         /* X, Z were never overwritten */
-               HS_CALL( hs_copy(st, B.X, B.Xs, n2) );
-               HS_CALL( hs_copy(st, B.Z, B.Zs, n2) );
-            }
-            status = HIPSDP_STATUS_NUMERIC;
-            break;
-         }
-         for (auto& B : s->blk)
-         {
-            if ( B.n <= 64 )
-            {
-               /* accept the trial iterate: its factors, inverse factors (and inverse) are those of the fused factorization */
-               if ( !optimistic )
-               {
-                  std::swap(B.X, B.Xs);
-                  std::swap(B.Z, B.Zs);
-               }
-               B.derived_valid = true;
-            }
-         }
-         factors_valid = (K > 0);
-         alpha_last = alpha;
-         if ( optimistic && K > 0 )
-            residuals_ready = true;                /* (applied, queued and read above) */
-         else
-         {
-            HS_CALL( hs_axpy3(st, alpha, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
-            s->tau += alpha * dt;
-            s->kappa += alpha * dk;
-            /* the residual the next iteration starts from: (1 - alpha eta) times the one this iteration used (general path only:
-             * the single-launch kernels of small problems recompute it inside the fused launches) */
-            rd_have = !small_problem(s);
-            rd_pending = rd_have;
-            rd_scale = 1.0 - alpha * eta;
-         }
+         alpha *= 0.5;
+         info->chol_fail++;
       }
-   }
-
-   phase_mark(s, -1);
-   /* a break above may leave the Z chain of the abandoned iteration running on the second queue (it is started at the top of an
-    * iteration, before the termination decision): it writes B.Lz / B.LzInv / B.Zinv / B.T2, so the solve is over - and
-    * its buffers may be re-shaped, freed or read - only when that queue has drained as well */
-   if ( zchain_queued )
-      HS_CALL( join2(s) );
-   HS_HIP( hipStreamSynchronize(st) );
-   if ( s->clk_on && s->clk_n > 0 )
-   {
-      if ( s->clk_stream != NULL )
-         HS_HIP( hipStreamSynchronize(s->clk_stream) );
-      std::vector<unsigned long long> h((size_t) 4 * s->clk_n);
-      HS_HIP( hipMemcpy(h.data(), s->clk_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) );
-      double dc = 0.0, dw = 0.0;
-      for (int a = 0; a < s->clk_n; ++a)
+      if ( K > 0 && (hflags[0] != 0 || hflags[1] != 0) )
+         return give_up(optimistic && applied != 0.0);
+      /* accept the trial iterate: its factors, inverse factors (and inverse) are those of the fused factorization */
+      if ( !optimistic )
+         swap_trial();
+      for (auto& B : s->blk)
+         if ( B.n <= 64 )
+            B.derived_valid = true;
+      factors_valid = (K > 0);
+      alpha_last = alpha;
+      if ( optimistic && K > 0 )
       {
-         dc += (double) h[4 * a + 2];
-         dw += (double) h[4 * a + 3];
+         residuals_ready = true;                /* (applied, queued and read above) */
+         return HS_OK;
       }
-      s->clk_ghz = dw > 0.0 ? dc / (dw * 10.0) : 0.0;
+      HS_CALL( hs_axpy3(st, alpha, m, s->dy, s->y, q, s->dx, s->x, q, s->dz, s->z) );
+      s->tau += alpha * dt;
+      s->kappa += alpha * dk;
+      /* the residual the next iteration starts from: (1 - alpha eta) times the one this iteration used (general path only: the
+       * single-launch kernels of small problems recompute it inside the fused launches) */
+      rd_have = !small_problem(s);
+      rd_pending = rd_have;
+      rd_scale = 1.0 - alpha * eta;
+      return HS_OK;
    }
-   phase_finish(s);
-   s->last_status = status;
-   s->solved = true;
-   if ( status == HIPSDP_STATUS_DINF || status == HIPSDP_STATUS_DUNB || status == HIPSDP_STATUS_PDINF )
-      s->sol_scale = 1.0 / fmax(fmax(fabs(dobj), fabs(pobj)), 1e-300);
-   else
-      s->sol_scale = 1.0 / s->tau;
-   info->status = status;
-   info->iterations = it;
-   info->pobj = pobj * s->sol_scale;
-   info->dobj = dobj * s->sol_scale;
-   info->pinf = pinf;
-   info->dinf = dinf;
-   info->dabs = dabs;
-   info->gap = gap;
-   info->mu = mu;
-   info->tau = s->tau;
-   info->kappa = s->kappa;
-   info->settings_used = settings;
-   info->schur_seconds = schur_ms * 1e-3;
-   info->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-   return HIPSDP_OK;
-}
 
-static int solve_impl(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info)
+   int run()
+   {
+      HS_CALL( start() );
+      for (it = 0; it <= par.maxiter; ++it)
+      {
+         if ( !residuals_ready )
+            HS_CALL( residual_pass() );
+         residuals_ready = false;
+         HS_CALL( terminate() );
+         if ( stop )
+            break;
+         HS_CALL( factorize() );
+         HS_CALL( assemble() );
+         HS_CALL( solve_m() );
+         HS_CALL( predictor() );
+         if ( !stop )
+            HS_CALL( corrector() );
+         if ( !stop )
+            HS_CALL( update() );
+         if ( stop )
+            break;
+      }
+      return HS_OK;
+   }
+
+   int finish()
+   {
+      HS_HIP( hipStreamSynchronize(st) );
+      if ( s->clk_on && s->clk_n > 0 )
+      {
+         if ( s->clk_stream != NULL )
+            HS_HIP( hipStreamSynchronize(s->clk_stream) );
+         std::vector<unsigned long long> h((size_t) 4 * s->clk_n);
+         HS_HIP( hipMemcpy(h.data(), s->clk_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) );
+         double dc = 0.0, dw = 0.0;
+         for (int a = 0; a < s->clk_n; ++a)
+         {
+            dc += (double) h[4 * a + 2];
+            dw += (double) h[4 * a + 3];
+         }
+         s->clk_ghz = dw > 0.0 ? dc / (dw * 10.0) : 0.0;
+      }
+      phase_finish(s);
+      s->last_status = status;
+      s->solved = true;
+      if ( status == HIPSDP_STATUS_DINF || status == HIPSDP_STATUS_DUNB || status == HIPSDP_STATUS_PDINF )
+         s->sol_scale = 1.0 / fmax(fmax(fabs(dobj), fabs(pobj)), 1e-300);
+      else
+         s->sol_scale = 1.0 / s->tau;
+      info->status = status;
+      info->iterations = it;
+      info->pobj = pobj * s->sol_scale;
+      info->dobj = dobj * s->sol_scale;
+      info->pinf = pinf;
+      info->dinf = dinf;
+      info->dabs = dabs;
+      info->gap = gap;
+      info->mu = mu;
+      info->tau = s->tau;
+      info->kappa = s->kappa;
+      info->settings_used = settings;
+      info->schur_seconds = schur_ms * 1e-3;
+      info->solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+      return HIPSDP_OK;
+   }
+
+   /* The one way out of run(), whatever it returned.  A stop may leave the Z chains of the abandoned iterate running on the second
+    * queue (they are started before the termination decision, and behind a step's Cholesky check): they write B.Lz / B.LzInv /
+    * B.Zinv / B.T2, so the solve is over - and its buffers may be re-shaped, freed or read - only when that queue has drained as well.
+    * The hooks of the assembly point into this solve. */
+   int close(int rc)
+   {
+      phase_mark(s, -1);
+      const int rj = s->busy2 ? join2(s) : HS_OK;
+      s->sws.ev_g2 = NULL;
+      s->sws.after_g1 = NULL;
+      s->sws.after_g1_arg = NULL;
+      if ( rc == HIPSDP_OK && rj == HIPSDP_OK )
+         return finish();
+      (void) hipStreamSynchronize(st);         /* (the roctx range closed, the marks dropped) */
+      phase_finish(s);
+      return rc != HIPSDP_OK ? rc : rj;
+   }
+};
+
+static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1)
 {
-   HS_CALL( solve_begin(s, params, info) );
-   return solve_run(s, info, true);
+   const auto t_begin = std::chrono::steady_clock::now();
+   solve_reset(s, info);
+   if ( try1 )
+   {
+      bool done1 = false;
+      HS_CALL( solve1_try(s, info, &done1) );
+      if ( done1 )
+      {
+         s->stage_off = 0;                                      /* (the kernel ran the commands and read their data at its start) */
+         return HIPSDP_OK;
+      }
+   }
+   GeneralSolve g{s, info, t_begin};
+   return g.close(g.run());
 }
 
 /* ---- many problems at once: one launch of the one-launch kernel per size class, one workgroup per problem -------------------- */

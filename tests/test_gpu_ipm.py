@@ -20,7 +20,7 @@ def gpu_solve(hb, core, **kw):
     s = hb.Solver(0)
     s.load_core(core)
     info = s.solve(**kw)
-    out = dict(info=info, y=s.y(), X=[s.X(k) for k in range(len(core.blocks))], lp=s.lp())
+    out = dict(info=info, y=s.y(), X=[s.X(k) for k in range(len(core.blocks))], Z=[s.Z(k) for k in range(len(core.blocks))], lp=s.lp())
     s.close()
     return out
 
@@ -453,13 +453,7 @@ def test_solves_with_m_by_substitution_in_the_oracles_order(gpu, n, m, monkeypat
     assert not np.array_equal(sub["y"], dflt["y"])                    # (another algorithm: other last bits)
 
 
-@pytest.mark.parametrize("sizes", [(100,), (70, 20)])
-def test_failed_cholesky_check_takes_the_optimistic_step_back(gpu, sizes, monkeypatch):
-    """Round 6: on the general path the rest of the step and the residual pass of the next iterate are queued behind the Cholesky check
-    of the new X and Z, one read-back for both (csrc/ipm.hip, "optimistic").  A step beyond the boundary of the cone - forced here in
-    iteration 2 (HIPSDP_TEST_OVERSTEP) - fails the check: the step is halved, the optimistic part taken back, the dual residual
-    recomputed.  Same optimum, same iteration count and the same number of failed checks as the form that reads the flags first
-    (HIPSDP_NO_OPTIMISTIC=1); blocks of at most 64 rows keep their trial iterate in a second buffer that is swapped in and back."""
+def overstep_core(sizes):
     rng = np.random.default_rng(23)
     m = 40
     blocks = []
@@ -470,7 +464,18 @@ def test_failed_cholesky_check_takes_the_optimistic_step_back(gpu, sizes, monkey
         blocks.append(A)
     D = np.concatenate([np.eye(m), -np.eye(m)])
     c = np.concatenate([-2.0 * np.ones(m), -2.0 * np.ones(m)])
-    core = ipm_ref.CoreProblem(rng.standard_normal(m), blocks, D, c)
+    return ipm_ref.CoreProblem(rng.standard_normal(m), blocks, D, c)
+
+
+@pytest.mark.parametrize("sizes", [(100,), (70, 20), (130,)])
+def test_failed_cholesky_check_takes_the_optimistic_step_back(gpu, sizes, monkeypatch):
+    """On the general path the rest of the step and the residual pass of the next iterate are queued behind the Cholesky check of
+    the new X and Z, one read-back for both (csrc/ipm.hip, "optimistic").  A step beyond the boundary of the cone - forced here in
+    iteration 2 (HIPSDP_TEST_OVERSTEP) - fails the check: the step is halved, the optimistic part taken back, the dual residual
+    recomputed.  Same optimum, same iteration count and the same number of failed checks as the form that reads the flags first
+    (HIPSDP_NO_OPTIMISTIC=1); blocks of at most 64 rows keep their trial iterate in a second buffer that is swapped in and back, and
+    a block of 130 rows puts the Z chains of the abandoned iterate on the second queue."""
+    core = overstep_core(sizes)
     monkeypatch.setenv("HIPSDP_SOLVE1", "0")
     plain = gpu_solve(gpu, core, gaptol=1e-6, feastol=1e-6)
     assert plain["info"].status == 0 and plain["info"].chol_fail == 0
@@ -485,6 +490,34 @@ def test_failed_cholesky_check_takes_the_optimistic_step_back(gpu, sizes, monkey
     assert np.max(np.abs(opt["y"] - old["y"])) <= 1e-7
     ok, det = checker.certificate(core, opt["y"], opt["X"], opt["lp"][0], TOL, TOL)
     assert ok, det
+
+
+def test_every_halving_failed_returns_the_iterate_the_step_started_from(gpu, monkeypatch):
+    """A step so far beyond the boundary of the cone that all 8 halvings fail the Cholesky check, on a block of 130 rows (the second
+    queue in use): the solve stops with NUMERIC at iteration 2 and returns the iterate the step started from - X and Z bit for bit
+    what maxiter = 2 returns, y up to the rounding of the correcting axpy - with the second queue drained, so that the next solve on
+    the same handle gives the bits of a fresh solver."""
+    core = overstep_core((130,))
+    kw = dict(gaptol=1e-6, feastol=1e-6)
+    monkeypatch.setenv("HIPSDP_SOLVE1", "0")
+    start = gpu_solve(gpu, core, maxiter=2, **kw)
+    assert start["info"].iterations == 2
+    s = gpu.Solver(0)
+    s.load_core(core)
+    monkeypatch.setenv("HIPSDP_TEST_OVERSTEP", "1000")
+    info = s.solve(**kw)
+    assert info.status == 5 and info.iterations == 2 and info.chol_fail == 8
+    assert np.array_equal(s.X(0), start["X"][0])
+    assert np.array_equal(s.Z(0), start["Z"][0])
+    y = s.y()
+    assert np.max(np.abs(y - start["y"])) <= 1e-12 * np.max(np.abs(start["y"]))
+    monkeypatch.delenv("HIPSDP_TEST_OVERSTEP")
+    again = s.solve(**kw)
+    y2, X2 = s.y(), s.X(0)
+    s.close()
+    fresh = gpu_solve(gpu, core, **kw)
+    assert again.status == fresh["info"].status == 0 and again.iterations == fresh["info"].iterations
+    assert np.array_equal(y2, fresh["y"]) and np.array_equal(X2, fresh["X"][0])
 
 
 @pytest.mark.parametrize("mode", ["K3", "R", "U"])
