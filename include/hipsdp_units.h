@@ -58,6 +58,10 @@ HIPSDP_API int  hipsdp_trtri(int device, int n, const double* A, double* Linv); 
 HIPSDP_API int  hipsdp_lambda_min(int device, int n, const double* W, int steps, double* theta, double* resid);
 /* lambda_min(L D L^T), n <= 64, L lower triangular, D symmetric: the small-block step-length kernels; theta[2], resid[2] */
 HIPSDP_API int  hipsdp_lambda_min_scaled(int device, int n, const double* L, const double* D, int steps, double* theta, double* resid);
+/* host only: whether the one-launch kernel admits a shape (m variables, q LP rows, nblk blocks of ns[k] rows: its LDS layout fits),
+ * and the size class that would serve it (10 / 16 / 64: largest block, 1064: m > 64; -1: no such shape) */
+HIPSDP_API int  hipsdp_solve1_fits(int m, int q, int nblk, const int* ns);
+HIPSDP_API int  hipsdp_solve1_class(int m, int nblk, const int* ns);
 
 #ifdef __cplusplus
 }

@@ -319,6 +319,18 @@ def solve_many_stats():
     return launches.value, problems.value
 
 
+def solve1_fits(m, q, ns):
+    """the one-launch kernel's admission rule (hs_solve1_fits: its LDS layout fits) for m variables, q LP rows, blocks of ns rows"""
+    a = (C.c_int * max(len(ns), 1))(*[int(n) for n in ns])
+    return bool(ulib().hipsdp_solve1_fits(int(m), int(q), len(ns), a))
+
+
+def solve1_class(m, ns):
+    """the size class of the kernel instance that would serve the shape: 10, 16, 64, or 1064 (m > 64)"""
+    a = (C.c_int * max(len(ns), 1))(*[int(n) for n in ns])
+    return ulib().hipsdp_solve1_class(int(m), len(ns), a)
+
+
 def dgemm(A, B, layA=0, layB=1, alpha=1.0, beta=0.0, Cin=None, lower_only=False, splitk=0, device=0):
     """row-major C = alpha op(A) op(B) + beta C.  layA = 0: A is [M, K]; 1: A is [K, M].  layB = 0: B is [N, K]; 1: [K, N]."""
     A = _f64(A)

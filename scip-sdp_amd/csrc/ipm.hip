@@ -2625,7 +2625,8 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
    /* (read at every solve: tests and tools switch the path between two solves of one process) */
    int on = 1, prof = 0;
    const double maxwork = 3e6;
-   /* largest block the kernel is offered (HIPSDP_SOLVE1_MAXN): whatever fits its LDS - one block of 36 rows, two of 30, eight of 12.
+   /* largest block the kernel is offered (HIPSDP_SOLVE1_MAXN): whatever fits its LDS (hs_solve1_fits) - with no LP rows one block
+    * of 49 rows at m = 1, 41 at m = 64, 37 at m = 108; two of 34 / 29 / 25; eight of 16 / 13 / 12 (hipsdp_solve1_fits, units library).
     * Measured with sparse variable matrices, dense constant matrices and LP rows of density 0.3 (tests/devtools/solve1_sizes.py) it
     * is ahead of the general path at every such size: 16 rows 0.124 against 0.281 ms per iteration, 24: 0.233 / 0.360, 32: 0.360 /
     * 0.422, two of 30: 0.449 / 0.572.  [Mid-round it lost at 32 rows, 0.62 against 0.43 - a dense constant matrix went through

@@ -4014,7 +4014,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          out[18 + i] = sh.prof[i];
       out[40] = (double) sh.fl[2]; out[41] = (double) sh.fl[3];
       out[42] = (double) (((size_t) (void*) sh.blk[0].vval) >> 32);
-      out[44] = (double) numwhere;
+      out[44] = (double) numwhere; out[45] = (double) sh.fl[30];      /* (45: 1 = every list in LDS, 0 = some in the global workspace) */
       out[0] = (double) status;
       __threadfence_system();
       if ( P.flag != NULL )

@@ -819,3 +819,24 @@ extern "C" int hipsdp_mfma_peak(int device, double ms, double* tflops, double* g
    if ( ghz != NULL ) *ghz = bestghz;
    return HIPSDP_OK;
 }
+
+/* the one-launch kernel's admission rule (csrc/solve1_body.h: hs_solve1_fits) and size class (csrc/solve1.hip: hs_solve1_class) for a
+ * shape: the tests pick "the largest block that fits" and one row more from the rule itself */
+extern "C" int hipsdp_solve1_fits(int m, int q, int nblk, const int* ns)
+{
+   if ( ns == NULL || nblk < 1 || nblk > HS_S1_MAXBLK )
+      return 0;
+   return hs_solve1_fits(m, q, nblk, ns);
+}
+
+extern "C" int hipsdp_solve1_class(int m, int nblk, const int* ns)
+{
+   if ( ns == NULL || nblk < 1 || nblk > HS_S1_MAXBLK )
+      return -1;
+   hs_solve1_args a;
+   memset(&a, 0, sizeof(a));
+   a.m = m; a.nblk = nblk;
+   for (int k = 0; k < nblk; ++k)
+      a.n[k] = ns[k];
+   return hs_solve1_class(&a);
+}
