@@ -31,6 +31,10 @@ HIPSDP_API int  hipsdp_gram_selfcheck(int device, int M, long long K, int reps, 
  * TWO runs of the default dispatch (must be 0) */
 HIPSDP_API int  hipsdp_dgemm_selfcheck3(int device, int M, int N, int K, int layB, int batch, int splitk, int flags, double alpha, double beta,
    int reps, int* used, long long* ndiff, double* maxdiff, long long* nrepro, double* ms_tile, double* ms_fast);
+/* first assembly of a cold solve: Mx += <A_i, A_j> on the lower tiles, from the packed lower triangles (full_storage = 0) or from the
+ * full rows (1); *flops: FP64 matrix-core flops executed by the call */
+HIPSDP_API int  hipsdp_schur_identity_unit(int device, int m1, int n, const double* A, double ws_gbytes, int full_storage, double* Mx,
+   double* flops);
 /* Schur block Mx[(m1) x (m1)] = tr(A_i X A_j Zinv) for i, j = 0..m1-1 */
 HIPSDP_API int  hipsdp_schur_dense(int device, int m1, int n, const double* A, const double* X, const double* Zinv, double* Mx,
    double ws_gbytes);

@@ -419,6 +419,18 @@ def gram_selfcheck(M, K, reps=0, device=0):
     return used.value, md.value, nr.value, t0.value, t1.value
 
 
+def schur_identity_unit(A, Mx=None, ws_gbytes=0.0, full_storage=False, device=0):
+    """first assembly of a cold solve on its own: Mx (zeros when None) += <A_i, A_j> on the lower tiles, from the packed lower triangles
+    (csrc/schur.hip: hs_schur_W_identity_packed) or, full_storage=True, from the full rows -> (Mx, executed matrix-core flops)"""
+    A = _f64(A)
+    m1, n = A.shape[0], A.shape[1]
+    Mx = np.zeros((m1, m1)) if Mx is None else _f64(Mx).copy()
+    fl = C.c_double(0.0)
+    _chk(ulib().hipsdp_schur_identity_unit(device, m1, n, _dp(A), C.c_double(ws_gbytes), int(full_storage), _dp(Mx), C.byref(fl)),
+         "hipsdp_schur_identity_unit")
+    return Mx, fl.value
+
+
 def potrf(A, device=0):
     L = _f64(A).copy()
     fail = C.c_int(0)

@@ -85,6 +85,10 @@ int hs_lp_s0(hipStream_t s, int q, const double* x, const double* z, const doubl
 
 /* packed lower copies for the bandwidth-bound passes (half the bytes of the full storage) */
 int hs_pack_rows(hipStream_t s, int m1, int n, long long Lp, const double* A, double* Apk);
+/* D[i][r] = A_i[r][r] (r < n; 0 for n <= r < ldd) gathered from the packed rows */
+int hs_packed_diag(hipStream_t s, int m1, int n, int ldd, long long Lp, const double* Apk, double* D);
+/* C[r][c] -= S[r][c] for c <= r (both n x n, leading dimension n) */
+int hs_sub_lower(hipStream_t s, int n, const double* S, double* C);
 int hs_pack_weighted(hipStream_t s, int n, const double* V, double* pk);
 int hs_unpack_sym(hipStream_t s, int n, const double* pk, double sa, const double* add, double* out);
 int hs_zero_upper(hipStream_t s, double* A, int n);                                         /* A[i][j] = 0 for i < j */
@@ -122,6 +126,12 @@ int  hs_schur_U(hipStream_t s, int m1, int n, const double* A, const double* X, 
 int  hs_schur_W(hipStream_t s, int m1, int n, const double* A, const double* R, const double* G, double* Mx, hs_schur_ws* w);
 int  hs_schur_W_identity(hipStream_t s, int m1, int n, const double* A, double* Mx, hs_schur_ws* w);
 int  hs_schur_W_identity_range(hipStream_t s, int m1, int n, const double* A, long long k0, long long k1, double* Mx, hs_schur_ws* w);
+/* the same Gram matrix from the packed lower triangles Apk[m1][Lp] (hs_pack_rows): Mx += 2 P P^T - D D^T, D[i][r] = A_i[r][r] gathered
+ * into w->T; hs_schur_identity_packed_fits: 1 when w->T holds D.  Both identity forms write the lower triangle of Mx exactly when the
+ * Gram kernel takes the product, and the lower TILES (every 64- or 128-wide tile that touches the lower triangle: a diagonal tile whole)
+ * when the tile kernels do; nothing above the diagonal tiles is ever written, and the caller mirrors the lower triangle afterwards */
+int  hs_schur_W_identity_packed(hipStream_t s, int m1, int n, const double* Apk, long long Lp, double* Mx, hs_schur_ws* w);
+int  hs_schur_identity_packed_fits(const hs_schur_ws* w, int m1, int n);
 
 int  hs_schur_Urows(hipStream_t s, int m1, int n, const double* A, const double* X, const double* Zinv, double* Mx,
    hs_schur_ws* w, int r_begin, int r_end);

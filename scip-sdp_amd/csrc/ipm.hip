@@ -21,6 +21,7 @@
 #include <chrono>
 #include <algorithm>
 #include <cmath>
+#include <cassert>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -3602,7 +3603,16 @@ struct GeneralSolve
                continue;
             if ( identity_start && it == 0 )
             {
-               HS_CALL( hs_schur_W_identity(st, m1, B.n, B.A, s->Mx, &s->sws) );
+               /* one device: the Gram matrix from the packed lower triangles, half the K of the full rows.  The solve packed them ahead
+                * of its first residual sweep (ensure_packed): a packed copy that exists is valid here.  The full storage serves when there
+                * is no packed copy (n <= 64, or no memory for it) or when a chunked workspace is too small for the m1 x n diagonals the
+                * packed form gathers into it (m1 above about 128 n).  The sharded branches above stay on the full storage: a rank's packed
+                * copy covers its own rows only. */
+               assert(B.Apk == NULL || B.apk_valid);
+               if ( B.Apk != NULL && hs_schur_identity_packed_fits(&s->sws, m1, B.n) )
+                  HS_CALL( hs_schur_W_identity_packed(st, m1, B.n, B.Apk, B.Lp, s->Mx, &s->sws) );
+               else
+                  HS_CALL( hs_schur_W_identity(st, m1, B.n, B.A, s->Mx, &s->sws) );
                gram_only_used = true;
             }
             else if ( s->schur_mode_U )

@@ -115,6 +115,31 @@ __global__ void k_pack_rows(int m1, int n, long long Lp, const double* __restric
    }
 }
 
+/* D[i][r] = A_i[r][r] out of the packed rows (entry (r, r) at t = r (r + 3) / 2); rows of D have ldd >= n entries, those behind n are
+ * set to zero */
+__global__ void k_packed_diag(int m1, int n, int ldd, long long Lp, const double* __restrict__ Apk, double* __restrict__ D)
+{
+   const long long total = (long long) m1 * ldd;
+   for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long) gridDim.x * blockDim.x)
+   {
+      const long long i = e / ldd;
+      const int r = (int) (e - i * ldd);
+      D[e] = r < n ? Apk[i * Lp + (long long) r * (r + 3) / 2] : 0.0;
+   }
+}
+
+/* C[r][c] -= S[r][c] on the lower triangle (c <= r) of two n x n matrices */
+__global__ void k_sub_lower(int n, const double* __restrict__ S, double* __restrict__ C)
+{
+   const long long total = (long long) n * n;
+   for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long) gridDim.x * blockDim.x)
+   {
+      const int r = (int) (e / n), c = (int) (e - (long long) r * n);
+      if ( c <= r )
+         C[e] -= S[e];
+   }
+}
+
 /* pk[t] = w * V[r][c] with w = 1 on the diagonal, 2 off it: <A_i, V> = sum_t Apk[i][t] pk[t] for symmetric V */
 __global__ void k_pack_weighted(int n, const double* __restrict__ V, double* __restrict__ pk)
 {
@@ -329,6 +354,24 @@ int hs_pack_rows(hipStream_t s, int m1, int n, long long Lp, const double* A, do
    (void) hs_red_batch_flush();          /* inside a held region: behind the records */
    HS_HIP( hipMemsetAsync(Apk, 0, (size_t) m1 * (size_t) Lp * sizeof(double), s) );
    hipLaunchKernelGGL(k_pack_rows, dim3(grid_for((long long) m1 * n * n, 256, 65536)), dim3(256), 0, s, m1, n, Lp, A, Apk);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+int hs_packed_diag(hipStream_t s, int m1, int n, int ldd, long long Lp, const double* Apk, double* D)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   if ( ldd < n )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_packed_diag, dim3(grid_for((long long) m1 * ldd, 256, 2048)), dim3(256), 0, s, m1, n, ldd, Lp, Apk, D);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+int hs_sub_lower(hipStream_t s, int n, const double* S, double* C)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   hipLaunchKernelGGL(k_sub_lower, dim3(grid_for((long long) n * n, 256, 2048)), dim3(256), 0, s, n, S, C);
    HS_LAUNCH_CHECK();
    return HS_OK;
 }

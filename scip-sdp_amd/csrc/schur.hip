@@ -115,14 +115,14 @@ int hs_schur_U(hipStream_t s, int m1, int n, const double* A, const double* X, c
    return HS_OK;
 }
 
-/* Mx += V V^T (lower triangle) through the Gram kernel (gram.hip) when it takes the shape: *done = 1 */
-static int schur_gram(hipStream_t s, int m1, long long K, const double* V, long long ldv, double* Mx, hs_schur_ws* w, int* done)
+/* Mx += alpha V V^T (lower triangle) through the Gram kernel (gram.hip) when it takes the shape: *done = 1 */
+static int schur_gram(hipStream_t s, int m1, long long K, const double* V, long long ldv, double* Mx, hs_schur_ws* w, int* done, double alpha = 1.0)
 {
    *done = 0;
    long long nslab = w->kws_len / ((long long) m1 * m1);
    if ( nslab > 64 ) nslab = 64;
    double executed = 0.0;
-   const int r = hs_gram_try(s, m1, K, V, ldv, Mx, m1, 1.0, 1.0, w->K, (int) nslab, &executed);
+   const int r = hs_gram_try(s, m1, K, V, ldv, Mx, m1, alpha, 1.0, w->K, (int) nslab, &executed);
    if ( r < 0 )
       return -r;
    if ( r == 1 )
@@ -184,6 +184,44 @@ int hs_schur_W_identity_range(hipStream_t s, int m1, int n, const double* A, lon
 int hs_schur_W_identity(hipStream_t s, int m1, int n, const double* A, double* Mx, hs_schur_ws* w)
 {
    return hs_schur_W_identity_range(s, m1, n, A, 0, (long long) n * n, Mx, w);
+}
+
+/* The cold-start Gram matrix from the packed lower triangles (rows P_i of Lp entries, (r, c), r >= c, at r (r + 1) / 2 + c, zero padded):
+ * every A_i is symmetric, so with D[i][r] = A_i[r][r]
+ *      <A_i, A_j> = 2 sum_{r >= c} A_i[r][c] A_j[r][c] - sum_r A_i[r][r] A_j[r][r],      Mx += 2 P P^T - D D^T   (lower tiles)
+ * The big product has K = Lp, half of n^2: half the matrix instructions and half the bytes of hs_schur_W_identity; D D^T has K = n.
+ * Entry by entry |D D^T| <= |P| |P|^T, so nothing cancels: the error bound is that of the direct sum.  Same ladder as the full-storage
+ * form: the Gram kernel when it takes the shape, else the tile kernels in the slabs schur_syrk_shape allows.  D (m1 rows of n entries,
+ * padded to an even length) is gathered into w->T, which is idle at the cold start - the n^3 products do not run.
+ * What is written: as in the full-storage form, the Gram kernel's summation writes the lower triangle exactly and the tile kernels
+ * write every tile that touches it (a diagonal tile whole).  The correction keeps to that: D D^T goes into the first slab of w->K (free
+ * once the big product is summed) and its lower triangle is subtracted entry by entry; only a workspace without room for one slab
+ * sends it through the tile kernel straight into Mx - a workspace that small has sent the big product there as well. */
+int hs_schur_identity_packed_fits(const hs_schur_ws* w, int m1, int n)
+{
+   return w->T != NULL && (long long) m1 * ((n + 1) & ~1) <= w->chunk_cols * w->n2;
+}
+
+int hs_schur_W_identity_packed(hipStream_t s, int m1, int n, const double* Apk, long long Lp, double* Mx, hs_schur_ws* w)
+{
+   const int ldd = (n + 1) & ~1;
+   if ( n < 1 || Lp < (long long) n * (n + 1) / 2 || (Lp & 1) || Lp > 2000000000LL || !hs_schur_identity_packed_fits(w, m1, n) )
+      return HS_ERR_ARG;
+   int done = 0;
+   HS_CALL( schur_gram(s, m1, Lp, Apk, Lp, Mx, w, &done, 2.0) );
+   if ( !done )
+   {
+      int flags, sk;
+      schur_syrk_shape(w, m1, Lp, m1 >= SYRK_MIN_M1 && Lp >= 16384 && (Lp >= 50000 || m1 >= 900), &flags, &sk);
+      hs_gemm_args g3 = {m1, m1, (int) Lp, HS_KC, HS_KC, Apk, Lp, 0, Apk, Lp, 0, Mx, m1, 0, 2.0, 1.0, 1, flags, sk, sk > 1 ? w->K : NULL};
+      HS_CALL( hs_dgemm(s, &g3) );
+   }
+   HS_CALL( hs_packed_diag(s, m1, n, ldd, Lp, Apk, w->T) );
+   const bool slab = w->K != NULL && (long long) m1 * m1 <= w->kws_len;
+   hs_gemm_args gd = {m1, m1, n, HS_KC, HS_KC, w->T, ldd, 0, w->T, ldd, 0, slab ? w->K : Mx, m1, 0, slab ? 1.0 : -1.0, slab ? 0.0 : 1.0, 1,
+      HS_GEMM_LOWER, 1, NULL};
+   HS_CALL( hs_dgemm(s, &gd) );
+   return slab ? hs_sub_lower(s, m1, w->K, Mx) : HS_OK;
 }
 
 int hs_schur_W(hipStream_t s, int m1, int n, const double* A, const double* R, const double* G, double* Mx, hs_schur_ws* w)

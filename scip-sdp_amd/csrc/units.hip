@@ -365,6 +365,47 @@ extern "C" int hipsdp_gram_plan_info(int device, int M, long long K, int nslab, 
    return hs_gram_plan_info(M, K, nslab, no, nd, nitems, span) ? HIPSDP_OK : HIPSDP_ERR_ARG;
 }
 
+/* The cold start's first assembly on its own: Mx (m1 x m1, as the caller filled it) += the Gram matrix <A_i, A_j> of the host matrices
+ * A[m1][n][n] on the lower tiles.  full_storage = 0: hs_pack_rows + hs_schur_W_identity_packed (2 P P^T - D D^T over the packed lower
+ * triangles), 1: hs_schur_W_identity over the full rows.  ws_gbytes > 0: the Schur workspace under that budget (chunked when the
+ * T, W pair does not fit), as the engine sizes it.  *flops: FP64 matrix-core flops the call executed. */
+extern "C" int hipsdp_schur_identity_unit(int device, int m1, int n, const double* A, double ws_gbytes, int full_storage, double* Mx,
+   double* flops)
+{
+   HS_CALL( pick_device(device) );
+   if ( m1 <= 0 || n <= 0 || A == NULL || Mx == NULL )
+      return HIPSDP_ERR_ARG;
+   const long long n2 = (long long) n * n;
+   const long long Lp = (((long long) n * (n + 1) / 2) + 1) & ~1LL;
+   DevBuf dA, dP, dM;
+   HS_CALL( dA.alloc(m1 * n2) ); HS_CALL( dM.alloc((long long) m1 * m1) );
+   HS_CALL( dA.up(A, m1 * n2) ); HS_CALL( dM.up(Mx, (long long) m1 * m1) );
+   if ( !full_storage )
+      HS_CALL( dP.alloc(m1 * Lp) );
+   hs_schur_ws w;
+   int rc = hs_schur_ws_alloc(&w, m1, n2, ws_gbytes > 0.0 ? ws_gbytes : 40.0);
+   if ( rc != HS_OK )
+   {
+      hs_schur_ws_free(&w);              /* (what a failed allocation left behind) */
+      return rc;
+   }
+   const double before = hs_mfma_flops_total();
+   if ( full_storage )
+      rc = hs_schur_W_identity(0, m1, n, dA.p, dM.p, &w);
+   else
+   {
+      rc = hs_pack_rows(0, m1, n, Lp, dA.p, dP.p);
+      if ( rc == HS_OK ) rc = hs_schur_W_identity_packed(0, m1, n, dP.p, Lp, dM.p, &w);
+   }
+   if ( flops != NULL )
+      *flops = hs_mfma_flops_total() - before;
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   hs_schur_ws_free(&w);
+   HS_CALL( rc );
+   HS_CALL( dM.down(Mx, (long long) m1 * m1) );
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_schur_dense(int device, int m1, int n, const double* A, const double* X, const double* Zinv, double* Mx,
    double ws_gbytes)
 {
