@@ -219,6 +219,20 @@ HIPSDP_API const char* hipsdp_phase_name(int phase);
  * is violated at y by -eigvals[c].  y: m host values (engine variables); coefs: maxcuts x m; vecs: maxcuts x n or NULL. */
 HIPSDP_API int  hipsdp_eigencuts(hipsdp_solver* solver, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
                       double* coefs, double* lhs, double* vecs);
+/* The separation round of cons_sdp.c (separateSol over all constraints) and the eigenvalue part of CONSCHECK in one call:
+ * for EVERY block b, lmin[b] = smallest eigenvalue of Z_b(y), and the cuts hipsdp_eigencuts(solver, b, y, tol, maxcuts, ...)
+ * would return.  Slot (b, c) of eigvals / lhs is entry b * maxcuts + c, of coefs row b * maxcuts + c (m values); the vectors
+ * of block b start at vecs + maxcuts * (n_0 + ... + n_{b-1}), row c has n_b values.  Slots c >= ncuts[b] are not written.
+ * maxcuts == 0: only ncuts (all 0) and lmin - a pure feasibility check; then eigvals, coefs, lhs may be NULL.
+ * lmin and vecs may be NULL.
+ * Blocks of at most 128 rows of a solver without communicator and without sharded matrices are BATCHED: whatever their number
+ * and the number of cuts, the call issues one upload of y, one launch that forms all Z_b(y), at most three launches for the
+ * decompositions, one for the selection and all coefficients, and one read-back (csrc/eigcuts.hip).  Every other block is served
+ * inside the same call the way hipsdp_eigencuts serves it.  Two host threads may call it at the same time on different solvers. */
+HIPSDP_API int hipsdp_eigencuts_all(hipsdp_solver* solver, const double* y, double tol, int maxcuts, int* ncuts, double* lmin,
+                                    double* eigvals, double* coefs, double* lhs, double* vecs);
+/* process totals: calls, kernel launches those calls issued for batched blocks, device->host synchronisations they waited on */
+HIPSDP_API int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks);
 
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves

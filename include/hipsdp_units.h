@@ -66,6 +66,10 @@ HIPSDP_API int  hipsdp_lambda_min_scaled(int device, int n, const double* L, con
  * and the size class that would serve it (10 / 16 / 64: largest block, 1064: m > 64; -1: no such shape) */
 HIPSDP_API int  hipsdp_solve1_fits(int m, int q, int nblk, const int* ns);
 HIPSDP_API int  hipsdp_solve1_class(int m, int nblk, const int* ns);
+/* the batched full decomposition behind hipsdp_eigencuts_all on `count` host matrices, one behind the other in A: matrix j has
+ * ns[j] <= 128 rows; lam: ns[j] eigenvalues each (ascending), V: ns[j] x ns[j] each (row k = k-th eigenvector) - for every matrix
+ * the bits of hipsdp_syev_small; *launches: kernel launches issued (at most 3, whatever count is) */
+HIPSDP_API int  hipsdp_syev_many_unit(int device, int count, const int* ns, const double* A, double* lam, double* V, int* launches);
 
 #ifdef __cplusplus
 }

@@ -278,6 +278,45 @@ class Solver:
              "hipsdp_eigencuts")
         return ev[:k.value], co[:k.value, :m], lh[:k.value], ve[:k.value]
 
+    def eigencuts_all(self, y, tol, maxcuts):
+        """the separation round of all blocks in one call (hipsdp_eigencuts_all): per block a tuple (lmin, eigvals[k], coefs[k, m],
+        lhs[k], vecs[k, n]) with lmin the smallest eigenvalue of Z_b(y); cut c of a block: coefs[c] @ y >= lhs[c]"""
+        y = _f64(y)
+        m, nb, mc = len(y), len(self.ns), max(1, maxcuts)
+        k = np.zeros(max(1, nb), dtype=np.int32)
+        lmin = np.zeros(max(1, nb))
+        ev = np.zeros((max(1, nb), mc))
+        co = np.zeros((max(1, nb), mc, max(1, m)))
+        lh = np.zeros((max(1, nb), mc))
+        ve = np.zeros(max(1, maxcuts * sum(self.ns)))
+        if m > 0 and maxcuts > 0:
+            co = np.zeros((max(1, nb), maxcuts, m))
+        _chk(lib().hipsdp_eigencuts_all(self.h, _dp(y), C.c_double(tol), maxcuts, _ip(k), _dp(lmin), _dp(ev), _dp(co), _dp(lh), _dp(ve)),
+             "hipsdp_eigencuts_all")
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            kb = int(k[b])
+            if maxcuts > 0:
+                evb, lhb = ev.reshape(-1)[b * maxcuts:b * maxcuts + kb], lh.reshape(-1)[b * maxcuts:b * maxcuts + kb]
+                cob = co.reshape(-1)[b * maxcuts * m:(b * maxcuts + kb) * m].reshape(kb, m)
+            else:
+                evb, lhb, cob = np.zeros(0), np.zeros(0), np.zeros((0, m))
+            out.append((float(lmin[b]), evb.copy(), cob.copy(), lhb.copy(), ve[off:off + kb * n].reshape(kb, n).copy()))
+            off += maxcuts * n
+        return out
+
+    @staticmethod
+    def eigencuts_all_stats():
+        """process totals (calls, launches, read-backs): the module's eigencuts_all_stats()"""
+        return eigencuts_all_stats()
+
+def eigencuts_all_stats():
+    """process totals of hipsdp_eigencuts_all: (calls, kernel launches issued for batched blocks, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_eigencuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_stats")
+    return calls.value, launches.value, readbacks.value
+
+
 # ---- unit-level host-buffer kernels ---------------------------------------------------------------------------------
 
 def _params(kw):

@@ -1286,7 +1286,9 @@ __device__ __forceinline__ void em_backtransform(int n, int ld, const double* Z,
    }
 }
 
-__global__ void __launch_bounds__(EM_NT) k_syev_mid(int n, const double* __restrict__ in, double* __restrict__ out, double* __restrict__ scratch,
+/* the body of k_syev_mid (one problem per launch) and of k_syev_mid_many (a job per workgroup): the LDS layout depends on n alone, not
+ * on what the launch asked for, so a job of the many-form computes the bits of the single launch */
+__device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in, double* __restrict__ out, double* __restrict__ scratch,
    unsigned long long seq, unsigned long long* __restrict__ flag)
 {
    extern __shared__ __attribute__((aligned(16))) double em_a[];
@@ -1515,6 +1517,28 @@ __global__ void __launch_bounds__(EM_NT) k_syev_mid(int n, const double* __restr
    __syncthreads();
    if ( tid == 0 )
       __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_syev_mid(int n, const double* __restrict__ in, double* __restrict__ out, double* __restrict__ scratch,
+   unsigned long long seq, unsigned long long* __restrict__ flag)
+{
+   d_syev_mid(n, in, out, scratch, seq, flag);
+}
+
+/* many-forms of the two full decompositions: workgroup j serves jobs[j] (a uniform bind, then the same body).  The slab ws of a job is
+ * laid out as hs_syev_small_dev lays out its scratch: output (eigenvalues, eigenvectors with pitch n, flag word) first, the device
+ * scratch of k_syev_mid behind it. */
+__global__ void __launch_bounds__(EM_NT) k_syev_mid_many(const hs_eig_job* __restrict__ jobs)
+{
+   const hs_eig_job job = jobs[blockIdx.x];
+   d_syev_mid(job.n, job.in, job.ws, job.ws + EM_ALL_OUT, 1ULL, reinterpret_cast<unsigned long long*>(job.ws + EM_ALL_FLAG));
+}
+
+__global__ void __launch_bounds__(256) k_syevi_small_many(const hs_eig_job* __restrict__ jobs)
+{
+   const hs_eig_job job = jobs[blockIdx.x];
+   d_syevi_small<true>(job.n, 0, 1, job.in, job.ws, 1ULL,
+      reinterpret_cast<unsigned long long*>(job.ws + EI_N + (long long) EI_N * EI_N + 4));
 }
 
 /* dynamic LDS of k_syev_mid: the matrix / the eigenvectors of T, and up to 64 rows the two factor arrays of the inverse iteration */
@@ -1754,6 +1778,50 @@ int hs_syev_small_dev(hipStream_t st, int n, const double* A, double* lam, doubl
    HS_HIP( hipGetLastError() );
    HS_HIP( hipMemcpyAsync(lam, scratch, (size_t) n * sizeof(double), hipMemcpyDeviceToDevice, st) );
    HS_HIP( hipMemcpyAsync(V, scratch + EI_N, (size_t) n * n * sizeof(double), hipMemcpyDeviceToDevice, st) );
+   return HS_OK;
+}
+
+/* Full decompositions of many matrices of at most 128 rows in a constant number of launches: jobs[count] in device memory (hjobs:
+ * the same table on the host), sorted by the caller into the three classes [0, c0) below EM_MID_FROM rows (k_syevi_small_many),
+ * [c0, c1) up to 64 rows and [c1, count) above (k_syev_mid_many; the dynamic LDS of a launch is the largest em_all_lds(n) among
+ * its jobs, and the request changes shape at 64 rows).  A class without jobs is not launched.  For the same matrix a job gets the
+ * bits of hs_syev_small_dev: eigenvalues at ws[0 .. n), row k of the eigenvectors at ws + hs_syev_many_vecpos(n) + k n. */
+long long hs_syev_many_vecpos(int n) { return n < EM_MID_FROM ? EI_N : EM_N; }
+int hs_syev_many_class(int n) { return n < EM_MID_FROM ? 0 : (n <= 64 ? 1 : 2); }
+
+int hs_syev_small_many(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* jobs, int* launches)
+{
+   int c0 = 0, c1 = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( hjobs[j].n < 1 || hjobs[j].n > EM_N || (j > 0 && hs_syev_many_class(hjobs[j].n) < hs_syev_many_class(hjobs[j - 1].n)) )
+         return HS_ERR_ARG;
+      if ( hs_syev_many_class(hjobs[j].n) < 1 ) ++c0;
+      if ( hs_syev_many_class(hjobs[j].n) < 2 ) ++c1;
+   }
+   if ( c0 > 0 )
+   {
+      static hs_attr_mask attr_small;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_syevi_small_many), EI_ALL_LDS, &attr_small) );
+      hipLaunchKernelGGL(k_syevi_small_many, dim3(c0), dim3(256), EI_ALL_LDS, st, jobs);
+      HS_HIP( hipGetLastError() );
+      if ( launches != NULL ) ++*launches;
+   }
+   static hs_attr_mask attr_mid;
+   if ( c1 > c0 || count > c1 )
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_syev_mid_many), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
+   for (int cls = 1; cls <= 2; ++cls)
+   {
+      const int j0 = cls == 1 ? c0 : c1, j1 = cls == 1 ? c1 : count;
+      if ( j1 <= j0 )
+         continue;
+      size_t lds = 0;
+      for (int j = j0; j < j1; ++j)
+         lds = em_all_lds(hjobs[j].n) > lds ? em_all_lds(hjobs[j].n) : lds;
+      hipLaunchKernelGGL(k_syev_mid_many, dim3(j1 - j0), dim3(EM_NT), lds, st, jobs + j0);
+      HS_HIP( hipGetLastError() );
+      if ( launches != NULL ) ++*launches;
+   }
    return HS_OK;
 }
 

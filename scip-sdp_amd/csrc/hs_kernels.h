@@ -244,6 +244,33 @@ int hs_lanczos_sync_reset(hipStream_t s, unsigned long long* dsync, int* rot);
 /* eigi.hip: n <= 128, all eigenpairs in one launch on device buffers (same results as hipsdp_syev_small) */
 long long hs_syev_small_scratch(int n);
 int hs_syev_small_dev(hipStream_t st, int n, const double* A, double* lam, double* V, double* scratch);
+/* the same decompositions for many matrices in at most three launches (see eigi.hip); ws: hs_syev_small_scratch(n) doubles per job */
+struct hs_eig_job { int n; int pad; const double* in; double* ws; };
+long long hs_syev_many_vecpos(int n);
+int hs_syev_many_class(int n);
+int hs_syev_small_many(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* jobs, int* launches);
+
+/* ---- eigcuts.hip: the separation round of all blocks (hipsdp_eigencuts_all) ------------------------------------------------- */
+#define HS_EC_DENSE  0     /* A: (m + 1) rows of n^2 */
+#define HS_EC_PACKED 1     /* A: (m + 1) rows of Lp, entry (r, c), c <= r, at r (r + 1) / 2 + c */
+#define HS_EC_SPARSE 2     /* A0 dense n x n; the variables' lower-triangular nonzeros by variable and by position (hs_sp_view) */
+struct hs_sp_view { long long nnz, npos; const int *voff, *vrow, *vcol; const double* vval; const int *poff, *prow, *pcol, *pvar; const double* pval; };
+void hs_sp_get_view(const hs_sparse* sp, hs_sp_view* v);
+struct hs_ec_job
+{
+   int n, form, blk, pad;        /* blk: the block's index in the result arrays */
+   long long ld;                 /* n^2 or Lp */
+   const double* A;              /* dense / packed rows (row 0 = constant matrix); sparse: the dense constant matrix */
+   hs_sp_view sp;
+   double* Z;                    /* n x n: Z(y) */
+   double* ws;                   /* the slab of the block's decomposition (hs_eig_job.ws) */
+   long long vpos;               /* eigenvectors of the decomposition: row k at ws + vpos + k n (hs_syev_many_vecpos) */
+   long long vecoff;             /* where the block's vectors start in the result: maxcuts * (rows of the blocks before it) */
+};
+/* the result block of a call for nb blocks, doubles: ncuts[nb] | lmin[nb] | eigvals[nb maxcuts] | lhs[nb maxcuts] |
+ * coefs[nb maxcuts m] | vecs[maxcuts sum n] */
+int hs_ec_form_z(hipStream_t st, int count, int nmax, int m, const hs_ec_job* jobs, const double* y);
+int hs_ec_cuts(hipStream_t st, int count, int nmax, int m, int nb, int maxcuts, double tol, const hs_ec_job* jobs, double* res);
 
 /* Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix A (destroyed): eigenvalues ascending in lam[n],
  * eigenvectors as rows of V (row k = k-th eigenvector).  info (device int) = sweeps used or -1. */

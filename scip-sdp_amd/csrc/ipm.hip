@@ -16,6 +16,7 @@
 #include "../../include/hipsdp.h"
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include <vector>
+#include <atomic>
 #include <utility>
 #include <functional>
 #include <chrono>
@@ -194,6 +195,13 @@ struct hipsdp_solver
    int s1_last;            /* 1: the last solve ran in the single launch */
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
+   /* hipsdp_eigencuts_all (csrc/eigcuts.hip), all grow-only and kept until hipsdp_free: device workspace (y, result block, Z and
+    * decomposition slab per batched block), its pinned host mirror (y, result block), the job tables on the device and the host
+    * copies they were uploaded from (a call uploads them again only when they differ) */
+   double* ec_dev; long long ec_dev_len;
+   double* ec_pin; long long ec_pin_len;
+   char* ec_tab; long long ec_tab_len;
+   std::vector<hs_ec_job> ec_jobs; std::vector<hs_eig_job> ec_ejobs;
 };
 
 void hs_comm_phase(int phase);      /* multi.hip: the phase the next collectives are booked under */
@@ -538,6 +546,7 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->clk_on = false; s->clk_buf = NULL; s->clk_n = 0; s->clk_ghz = 0.0; s->clk_stream = NULL;
    s->s1_ws = NULL; s->s1_ws_len = 0; s->s1_host = NULL; s->s1_host_dev = NULL; s->s1_seq = 0; s->s1_last = 0; s->s1_sol_host = false; s->zero_b = false; s->zero_D = false;
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0; s->stage_off = 0; s->stage_pending = false; s->ncmd = 0; s->cmd_ev = NULL; s->cmd_inflight = false; s->m_alloc = 0; s->q_alloc = 0;
+   s->ec_dev = NULL; s->ec_dev_len = 0; s->ec_pin = NULL; s->ec_pin_len = 0; s->ec_tab = NULL; s->ec_tab_len = 0;
    s->trsv_ws = NULL;
    s->pre_y = s->pre_x = NULL;
    s->pre_valid = false;
@@ -605,6 +614,10 @@ extern "C" void hipsdp_free(hipsdp_solver** ps)
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0;
    if ( s->s1_ws != NULL ) (void) hipFree(s->s1_ws);
    s->s1_ws = NULL;
+   if ( s->ec_dev != NULL ) (void) hipFree(s->ec_dev);
+   if ( s->ec_tab != NULL ) (void) hipFree(s->ec_tab);
+   if ( s->ec_pin != NULL ) (void) hipHostFree(s->ec_pin);
+   s->ec_dev = NULL; s->ec_tab = NULL; s->ec_pin = NULL;
    if ( s->clk_buf != NULL ) (void) hipFree(s->clk_buf);
    s->clk_buf = NULL;
    if ( s->clk_stream != NULL ) (void) hipStreamDestroy(s->clk_stream);
@@ -4601,6 +4614,9 @@ __global__ void k_outer_row(int n, const double* __restrict__ V, int row, double
  * Z(y) (one pass over A), its eigen-decomposition (one launch up to 128 rows, block Jacobi above) and the coefficients <A_i, v v^T> (one pass over A per cut) are
  * formed on the device.  The most negative eigenvalues come first; at most maxcuts cuts.
  * eigvals[maxcuts], coefs[maxcuts x m], lhs[maxcuts], vecs[maxcuts x n] (may be NULL) are host arrays. */
+static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
+   double* coefs, double* lhs, double* vecs, double* lam0);
+
 extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
    double* coefs, double* lhs, double* vecs)
 {
@@ -4611,6 +4627,13 @@ extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, do
       return HIPSDP_OK;
    if ( eigvals == NULL || coefs == NULL || lhs == NULL )
       return HIPSDP_ERR_ARG;
+   return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, NULL);
+}
+
+/* one block, arguments checked by the caller (maxcuts may be 0: only the decomposition); lam0 (may be NULL): its first eigenvalue */
+static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
+   double* coefs, double* lhs, double* vecs, double* lam0)
+{
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    CommOff off(s, replicate_small(s));
@@ -4662,6 +4685,181 @@ extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, do
    dfree(lam); dfree(V); dfree(ws); dfree(out);
    HS_CALL( rc );
    *ncuts = k;
+   if ( lam0 != NULL )
+      *lam0 = hlam[0];
+   return HIPSDP_OK;
+}
+
+/* ---- all blocks in one call (kernels: csrc/eigcuts.hip, many-forms of the decompositions: csrc/eigi.hip) ---------------------- */
+static std::atomic<long long> g_ec_calls(0), g_ec_launches(0), g_ec_readbacks(0);
+
+extern "C" int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   if ( calls != NULL ) *calls = g_ec_calls.load();
+   if ( launches != NULL ) *launches = g_ec_launches.load();
+   if ( readbacks != NULL ) *readbacks = g_ec_readbacks.load();
+   return HIPSDP_OK;
+}
+
+/* a block whose round runs in the shared launches: the whole matrices are on this device and k_syev_mid holds the block */
+static bool ec_batched(const hipsdp_solver* s, const Block& B)
+{
+   return s->comm == NULL && !s->shardA && B.n <= 128 && (B.sparse ? (B.sp != NULL && B.A0 != NULL) : B.A != NULL);
+}
+
+extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
+   double* coefs, double* lhs, double* vecs)
+{
+   if ( s == NULL || !s->shaped || y == NULL || ncuts == NULL || maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   const int nb = (int) s->blk.size(), m = s->m;
+   for (int b = 0; b < nb; ++b)
+      ncuts[b] = 0;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
+   hipStream_t st = s->stream;
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+      vecoff[b + 1] = vecoff[b] + (long long) maxcuts * s->blk[b].n;
+   /* the batched blocks, in the order of the decomposition's classes */
+   std::vector<int> ids;
+   for (int cls = 0; cls < 3; ++cls)
+      for (int b = 0; b < nb; ++b)
+         if ( ec_batched(s, s->blk[b]) && hs_syev_many_class(s->blk[b].n) == cls )
+            ids.push_back(b);
+   const int nj = (int) ids.size();
+   if ( nj > 0 )
+   {
+      const long long ylen = (m + 2) & ~1LL;
+      const long long reslen = 2LL * nb + 2LL * nb * maxcuts + (long long) nb * maxcuts * m + vecoff[nb];
+      long long need = ylen + reslen;
+      int nmax = 0;
+      for (int b : ids)
+      {
+         const int n = s->blk[b].n;
+         need += (((long long) n * n + 1) & ~1LL) + hs_syev_small_scratch(n);
+         nmax = n > nmax ? n : nmax;
+      }
+      if ( need > s->ec_dev_len )
+      {
+         if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
+         s->ec_dev = NULL; s->ec_dev_len = 0;
+         HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
+         s->ec_dev_len = need;
+      }
+      if ( ylen + reslen > s->ec_pin_len )
+      {
+         if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
+         s->ec_pin = NULL; s->ec_pin_len = 0;
+         HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) (ylen + reslen) * sizeof(double), hipHostMallocDefault) );
+         s->ec_pin_len = ylen + reslen;
+      }
+      const size_t tabbytes = (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job));
+      if ( (long long) tabbytes > s->ec_tab_len )
+      {
+         if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
+         s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
+         HS_HIP( hipMalloc((void**) &s->ec_tab, tabbytes) );
+         s->ec_tab_len = (long long) tabbytes;
+      }
+      /* the job tables: what the shape, the storage forms and the workspace make of them; uploaded when that differs from what the
+       * device holds (first use, a new shape, a grown workspace) */
+      double* dy = s->ec_dev;
+      double* dres = dy + ylen;
+      double* cur = dres + reslen;
+      std::vector<hs_ec_job> jobs((size_t) nj);
+      std::vector<hs_eig_job> ejobs((size_t) nj);
+      for (int j = 0; j < nj; ++j)
+      {
+         const Block& B = s->blk[ids[j]];
+         hs_ec_job& J = jobs[j];
+         memset(&J, 0, sizeof(J));
+         memset(&ejobs[j], 0, sizeof(hs_eig_job));
+         J.n = B.n; J.blk = ids[j];
+         J.ld = (long long) B.n * B.n;
+         if ( B.sparse )
+         {
+            J.form = HS_EC_SPARSE; J.A = B.A0;
+            hs_sp_get_view(B.sp, &J.sp);
+         }
+         else if ( B.Apk != NULL && B.apk_valid )
+         {
+            J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
+         }
+         else
+         {
+            J.form = HS_EC_DENSE; J.A = B.A;
+         }
+         J.Z = cur; cur += ((long long) B.n * B.n + 1) & ~1LL;
+         J.ws = cur; cur += hs_syev_small_scratch(B.n);
+         J.vpos = hs_syev_many_vecpos(B.n);
+         J.vecoff = vecoff[ids[j]];
+         ejobs[j].n = B.n; ejobs[j].in = J.Z; ejobs[j].ws = J.ws;
+      }
+      hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
+      hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
+      if ( s->ec_jobs.size() != jobs.size() || memcmp(s->ec_jobs.data(), jobs.data(), jobs.size() * sizeof(hs_ec_job)) != 0 )
+      {
+         HS_HIP( hipMemcpy(djobs, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+         HS_HIP( hipMemcpy(dejobs, ejobs.data(), ejobs.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
+         s->ec_jobs = jobs; s->ec_ejobs = ejobs;
+      }
+      int launches = 0;
+      if ( m > 0 )
+      {
+         memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
+         HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
+      }
+      HS_CALL( hs_ec_form_z(st, nj, nmax, m, djobs, dy) );
+      ++launches;
+      HS_CALL( hs_syev_small_many(st, nj, s->ec_ejobs.data(), dejobs, &launches) );
+      HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, djobs, dres) );
+      ++launches;
+      double* hres = s->ec_pin + ylen;
+      HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      g_ec_launches += launches;
+      g_ec_readbacks += 1;
+      const double* h_eig = hres + 2LL * nb;
+      const double* h_lhs = h_eig + (long long) nb * maxcuts;
+      const double* h_coef = h_lhs + (long long) nb * maxcuts;
+      const double* h_vec = h_coef + (long long) nb * maxcuts * m;
+      for (int b : ids)
+      {
+         const int k = (int) hres[b];
+         if ( k < 0 || k > maxcuts || k > s->blk[b].n )
+            return HIPSDP_ERR_NUMERIC;
+         ncuts[b] = k;
+         if ( lmin != NULL )
+            lmin[b] = hres[nb + b];
+         const size_t slot = (size_t) b * maxcuts;
+         if ( k > 0 )
+         {
+            memcpy(eigvals + slot, h_eig + slot, (size_t) k * sizeof(double));
+            memcpy(lhs + slot, h_lhs + slot, (size_t) k * sizeof(double));
+            if ( m > 0 )
+               memcpy(coefs + slot * m, h_coef + slot * m, (size_t) k * m * sizeof(double));
+            if ( vecs != NULL )
+               memcpy(vecs + vecoff[b], h_vec + vecoff[b], (size_t) k * s->blk[b].n * sizeof(double));
+         }
+      }
+   }
+   /* every other block: the per-block path, inside the same call */
+   for (int b = 0; b < nb; ++b)
+   {
+      if ( std::find(ids.begin(), ids.end(), b) != ids.end() )
+         continue;
+      const size_t slot = (size_t) b * maxcuts;
+      double l0 = 0.0;
+      HS_CALL( eigencuts_one(s, b, y, tol, maxcuts, &ncuts[b], maxcuts > 0 ? eigvals + slot : NULL, maxcuts > 0 ? coefs + slot * m : NULL,
+            maxcuts > 0 ? lhs + slot : NULL, vecs != NULL ? vecs + vecoff[b] : NULL, &l0) );
+      if ( lmin != NULL )
+         lmin[b] = l0;
+   }
+   ++g_ec_calls;
    return HIPSDP_OK;
 }
 

@@ -70,6 +70,13 @@ template<typename T> int sp_upload(T** d, const std::vector<T>& h)
 
 }
 
+void hs_sp_get_view(const hs_sparse* sp, hs_sp_view* v)
+{
+   v->nnz = sp->nnz; v->npos = sp->npos;
+   v->voff = sp->voff; v->vrow = sp->vrow; v->vcol = sp->vcol; v->vval = sp->vval;
+   v->poff = sp->poff; v->prow = sp->prow; v->pcol = sp->pcol; v->pvar = sp->pvar; v->pval = sp->pval;
+}
+
 void hs_sp_free(hs_sparse* sp)
 {
    if ( sp == NULL )

@@ -881,3 +881,59 @@ extern "C" int hipsdp_solve1_class(int m, int nblk, const int* ns)
       a.n[k] = ns[k];
    return hs_solve1_class(&a);
 }
+
+/* the batched full decomposition of hipsdp_eigencuts_all (csrc/eigi.hip: hs_syev_small_many) on `count` host matrices: matrix j has
+ * ns[j] <= 128 rows and follows matrix j - 1 in A; lam receives the eigenvalues (ns[j] each, ascending), V the eigenvectors
+ * (ns[j] x ns[j] each, row k = k-th eigenvector); *launches = kernel launches issued (at most 3 whatever count is) */
+extern "C" int hipsdp_syev_many_unit(int device, int count, const int* ns, const double* A, double* lam, double* V, int* launches)
+{
+   HS_CALL( pick_device(device) );
+   if ( count < 1 || ns == NULL || A == NULL || lam == NULL || V == NULL )
+      return HIPSDP_ERR_ARG;
+   long long tot = 0, wslen = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( ns[j] < 1 || ns[j] > 128 )
+         return HIPSDP_ERR_ARG;
+      tot += (long long) ns[j] * ns[j];
+      wslen += hs_syev_small_scratch(ns[j]);
+   }
+   DevBuf din, dws, dtab;
+   HS_CALL( din.alloc(tot) ); HS_CALL( dws.alloc(wslen) );
+   HS_CALL( din.up(A, tot) );
+   /* jobs in the order of the size classes; where[j]: the job of matrix j */
+   std::vector<hs_eig_job> jobs;
+   std::vector<int> where((size_t) count, -1);
+   std::vector<long long> aoff((size_t) count + 1, 0), woff((size_t) count + 1, 0);
+   for (int j = 0; j < count; ++j)
+   {
+      aoff[j + 1] = aoff[j] + (long long) ns[j] * ns[j];
+      woff[j + 1] = woff[j] + hs_syev_small_scratch(ns[j]);
+   }
+   for (int cls = 0; cls < 3; ++cls)
+      for (int j = 0; j < count; ++j)
+         if ( hs_syev_many_class(ns[j]) == cls )
+         {
+            hs_eig_job J;
+            memset(&J, 0, sizeof(J));
+            J.n = ns[j]; J.in = din.p + aoff[j]; J.ws = dws.p + woff[j];
+            where[j] = (int) jobs.size();
+            jobs.push_back(J);
+         }
+   HS_CALL( dtab.alloc((long long) ((jobs.size() * sizeof(hs_eig_job) + 7) / 8)) );
+   HS_HIP( hipMemcpy(dtab.p, jobs.data(), jobs.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
+   int nl = 0;
+   HS_CALL( hs_syev_small_many(0, count, jobs.data(), reinterpret_cast<const hs_eig_job*>(dtab.p), &nl) );
+   HS_HIP( hipDeviceSynchronize() );
+   long long lo = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      const int n = ns[j];
+      HS_HIP( hipMemcpy(lam + lo, dws.p + woff[j], (size_t) n * sizeof(double), hipMemcpyDeviceToHost) );
+      HS_HIP( hipMemcpy(V + aoff[j], dws.p + woff[j] + hs_syev_many_vecpos(n), (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost) );
+      lo += n;
+   }
+   if ( launches != NULL )
+      *launches = nl;
+   return HIPSDP_OK;
+}
