@@ -309,6 +309,21 @@ HIPSDP_API int  hipsdp_syevi_small(int device, int n, const double* A, int i, do
 /* all eigenpairs, n <= 128, the same way (what DSYEVR RANGE = 'A' computes, lapack_interface.c:507-603): eigenvalues by multisection,
  * eigenvectors by inverse iteration with re-orthogonalisation inside clusters, one launch; hipsdp_syev takes this path for n <= 128 */
 HIPSDP_API int  hipsdp_syev_small(int device, int n, const double* A, double* lam, double* V);
+/* Selected eigenpairs of a symmetric matrix of up to 512 rows without a full decomposition (above 128 rows: Householder
+ * tridiagonalisation over several workgroups, Sturm multisection for the wanted eigenvalues, inverse iteration and back-transformation
+ * of the wanted vectors only - csrc/syevx.hip; up to 128 rows the one-launch kernels above serve the call).  The triangle of A that
+ * hipsdp_syevi_small reads is read.  Sign of a vector and basis inside a multiple eigenvalue are free; the returned vectors are
+ * orthonormal among themselves.  HIPSDP_ERR_ARG, nothing launched: n < 1, n > HIPSDP_SYEVX_MAXN, il < 1, iu > n, il > iu, more than
+ * HIPSDP_SYEVX_MAXK pairs, maxk outside 0 .. HIPSDP_SYEVX_MAXK, A, lam or count NULL.  Same input, same bits. */
+#define HIPSDP_SYEVX_MAXN 512
+#define HIPSDP_SYEVX_MAXK 32
+/* eigenpairs il..iu (1-based, ascending) of the symmetric n x n host matrix A: DSYEVR RANGE='I'.  lam: iu-il+1 values;
+ * V: (iu-il+1) x n, one unit eigenvector per row, or NULL (values only, no vector work is done). */
+HIPSDP_API int hipsdp_syevx(int device, int n, const double* A, int il, int iu, double* lam, double* V);
+/* eigenpairs with eigenvalue <= bound, ascending, at most maxk of them: *count = how many were returned,
+ * *nbelow (may be NULL) = how many eigenvalues are <= bound altogether (DSYEVR RANGE='V' with a cap). V may be NULL. */
+HIPSDP_API int hipsdp_syevx_below(int device, int n, const double* A, double bound, int maxk, int* count, int* nbelow,
+                                  double* lam, double* V);
 /* PSD projection chain of the warm-start producer (relax_sdp.c:2715-2766 for Z, :3405-3445 for X), fused on the device: sparse
  * lower/upper triangle (row, col, val; both triangles are filled) -> eigen-decomposition -> eigenvalues below minev (by more
  * than epsilon, SCIPisLT) raised to minev -> recombination -> entries with row <= col and |value| > epsilon in row-major order.

@@ -70,6 +70,9 @@ HIPSDP_API int  hipsdp_solve1_class(int m, int nblk, const int* ns);
  * ns[j] <= 128 rows; lam: ns[j] eigenvalues each (ascending), V: ns[j] x ns[j] each (row k = k-th eigenvector) - for every matrix
  * the bits of hipsdp_syev_small; *launches: kernel launches issued (at most 3, whatever count is) */
 HIPSDP_API int  hipsdp_syev_many_unit(int device, int count, const int* ns, const double* A, double* lam, double* V, int* launches);
+/* the first stage of hipsdp_syevx alone, 2 <= n <= 512: the tridiagonal matrix Q^T A Q (d[n], e[n - 1] in e[0 .. n - 2], e[n - 1] = 0)
+ * and Q = H_0 H_1 ... H_{n-2}, H_j = I - tau[j] v_j v_j^T, row j of Vrefl (n x n) = v_j (zeros up to entry j, entry j + 1 one) */
+HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau);
 
 #ifdef __cplusplus
 }

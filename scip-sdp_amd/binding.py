@@ -520,6 +520,42 @@ def syev(A, device=0):
     return lam, V
 
 
+def syevx(A, il, iu, vectors=True, device=0):
+    """eigenpairs il..iu (1-based, ascending) of the symmetric matrix A, n <= 512, at most 32 of them: lam, V (row k = k-th returned
+    unit eigenvector; None with vectors=False: no vector work is done)"""
+    A = _f64(A)
+    n = A.shape[0]
+    k = max(0, iu - il + 1)
+    lam = np.zeros(k)
+    V = np.zeros((k, n)) if vectors else None
+    _chk(lib().hipsdp_syevx(device, n, _dp(A), int(il), int(iu), _dp(lam), _dp(V) if vectors else None), "hipsdp_syevx")
+    return lam, V
+
+
+def syevx_below(A, bound, maxk, vectors=True, device=0):
+    """eigenpairs with eigenvalue <= bound, ascending, at most maxk <= 32 of them: lam, V (as syevx), nbelow = eigenvalues <= bound
+    altogether"""
+    A = _f64(A)
+    n = A.shape[0]
+    lam = np.zeros(max(1, maxk))
+    V = np.zeros((max(1, maxk), n)) if vectors else None
+    cnt, nbelow = C.c_int(-1), C.c_int(-1)
+    _chk(lib().hipsdp_syevx_below(device, n, _dp(A), C.c_double(bound), int(maxk), C.byref(cnt), C.byref(nbelow), _dp(lam),
+                                  _dp(V) if vectors else None), "hipsdp_syevx_below")
+    return lam[:cnt.value].copy(), (V[:cnt.value].copy() if vectors else None), nbelow.value
+
+
+def tridiag_unit(A, device=0):
+    """stage 1 of syevx alone (libhipsdp_units.so): d, e (n - 1), Vrefl (row j = reflector j), tau"""
+    A = _f64(A)
+    n = A.shape[0]
+    d, e, tau, Vr = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((n, n))
+    rc = ulib().hipsdp_tridiag_unit(device, n, _dp(A), _dp(d), _dp(e), _dp(Vr), _dp(tau))
+    if rc != 0:
+        raise RuntimeError("hipsdp_tridiag_unit failed: rc=%d (%s)" % (rc, ulib().hipsdp_last_error().decode()))
+    return d, e[:n - 1].copy(), Vr, tau
+
+
 def gemv_n(A, V, device=0):
     A = _f64(A)
     V = _f64(V).reshape(-1, A.shape[1])

@@ -1,6 +1,6 @@
 /* host_entries.hip - the host-buffer entry points the SCIPlapack* surface is built on (src/sdpi/lapack_interface_hip.c; reference
  * src/sdpi/lapack_interface.c:398-706: DSYEVR / DGEMV / DGEMM on host arrays, called from cons_sdp.c and relax_sdp.c between node
- * solves) and that the parity tests call directly: hipsdp_dgemm, hipsdp_gemv_n / _t, hipsdp_syev.
+ * solves) and that the parity tests call directly: hipsdp_dgemm, hipsdp_gemv_n / _t, hipsdp_syev, hipsdp_syevx / _below.
  *
  * Product path, not scaffolding: every calling host thread owns a context per device - a non-blocking stream, a pinned,
  * device-mapped staging buffer and a pool of device memory, both grow-only - so that a call in steady state does NO hipMalloc /
@@ -12,6 +12,7 @@
 #include "../../include/hipsdp.h"
 #include <cstring>
 #include <cstdlib>
+#include <vector>
 
 namespace {
 
@@ -201,4 +202,88 @@ extern "C" int hipsdp_syev(int device, int n, const double* A, double* lam, doub
    if ( V != NULL )
       memcpy(V, c->hpin + n2 + nl, (size_t) n * n * sizeof(double));
    return HIPSDP_OK;
+}
+
+/* ---- selected eigenpairs up to 512 rows (DSYEVR RANGE = 'I' / 'V'): one interface for every size.  Up to 128 rows the one-launch
+ * kernels of eigi.hip serve the call (one pair: k_syevi_small / k_syevi_mid; several: the full small decomposition, then the
+ * selection); above, syevx.hip on this thread's context: one upload, one read-back, one synchronisation. */
+namespace {
+
+int syevx_small(int device, int n, const double* A, bool below, int il, int iu, double bound, int maxk, int* count, int* nbelow,
+   double* lam, double* V)
+{
+   if ( !below && il == iu )
+      return hipsdp_syevi_small(device, n, A, il, lam, V);
+   /* (host memory of the thread, grow-only like the device pool) */
+   thread_local std::vector<double> full;
+   if ( full.size() < (size_t) n * n + n )
+      full.resize((size_t) n * n + n);
+   double* fl = full.data(); double* fv = fl + n;
+   HS_CALL( hipsdp_syev_small(device, n, A, fl, V != NULL ? fv : NULL) );
+   int first = il - 1, k = iu - il + 1;
+   if ( below )
+   {
+      int nb = 0;
+      while ( nb < n && fl[nb] <= bound )
+         ++nb;
+      first = 0;
+      k = nb < maxk ? nb : maxk;
+      *count = k;
+      if ( nbelow != NULL )
+         *nbelow = nb;
+   }
+   memcpy(lam, fl + first, (size_t) k * sizeof(double));
+   if ( V != NULL )
+      memcpy(V, fv + (size_t) first * n, (size_t) k * n * sizeof(double));
+   return HIPSDP_OK;
+}
+
+int syevx_large(int device, int n, const double* A, int mode, int il, int iu, double bound, int maxk, int* count, int* nbelow,
+   double* lam, double* V)
+{
+   const long long n2 = even((long long) n * n), no = even(HS_SYEVX_OUT(n)), nws = even((long long) hs_syevx_ws(n));
+   if ( V == NULL )
+      mode |= HS_SYEVX_NOVEC;
+   he_ctx* c = NULL;
+   HS_CALL( he_context(device, n2 + no, n2 + no + nws, &c) );
+   memcpy(c->hpin, A, (size_t) n * n * sizeof(double));
+   double* dA = c->dpool; double* dO = c->dpool + n2; double* dW = c->dpool + n2 + no;
+   HS_HIP( hipMemcpyAsync(dA, c->hpin, (size_t) n * n * sizeof(double), hipMemcpyHostToDevice, c->stream) );
+   HS_CALL( hs_syevx_dev(c->stream, n, dA, mode, il, iu, bound, maxk, dO, dW) );
+   const int kmax = (mode & HS_SYEVX_BELOW) ? maxk : iu - il + 1;
+   const long long back = (V != NULL) ? HS_SYEVX_OUT_VEC + (long long) kmax * n : HS_SYEVX_OUT_VEC;
+   HS_HIP( hipMemcpyAsync(c->hpin + n2, dO, (size_t) back * sizeof(double), hipMemcpyDeviceToHost, c->stream) );
+   HS_HIP( hipStreamSynchronize(c->stream) );
+   const double* o = c->hpin + n2;
+   const int k = (int) o[0];
+   if ( k < 0 || k > kmax )
+      return HIPSDP_ERR_HIP;
+   if ( count != NULL )
+      *count = k;
+   if ( nbelow != NULL )
+      *nbelow = (int) o[1];
+   memcpy(lam, o + HS_SYEVX_OUT_LAM, (size_t) k * sizeof(double));
+   if ( V != NULL )
+      memcpy(V, o + HS_SYEVX_OUT_VEC, (size_t) k * n * sizeof(double));
+   return HIPSDP_OK;
+}
+
+}
+
+extern "C" int hipsdp_syevx(int device, int n, const double* A, int il, int iu, double* lam, double* V)
+{
+   if ( n < 1 || n > HIPSDP_SYEVX_MAXN || il < 1 || iu > n || il > iu || iu - il + 1 > HIPSDP_SYEVX_MAXK || A == NULL || lam == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( n <= 128 )
+      return syevx_small(device, n, A, false, il, iu, 0.0, 0, NULL, NULL, lam, V);
+   return syevx_large(device, n, A, HS_SYEVX_INDEX, il, iu, 0.0, 0, NULL, NULL, lam, V);
+}
+
+extern "C" int hipsdp_syevx_below(int device, int n, const double* A, double bound, int maxk, int* count, int* nbelow, double* lam, double* V)
+{
+   if ( n < 1 || n > HIPSDP_SYEVX_MAXN || maxk < 0 || maxk > HIPSDP_SYEVX_MAXK || A == NULL || lam == NULL || count == NULL || bound != bound )
+      return HIPSDP_ERR_ARG;
+   if ( n <= 128 )
+      return syevx_small(device, n, A, true, 0, 0, bound, maxk, count, nbelow, lam, maxk > 0 ? V : NULL);
+   return syevx_large(device, n, A, HS_SYEVX_BELOW, 0, 0, bound, maxk, count, nbelow, lam, maxk > 0 ? V : NULL);
 }

@@ -277,6 +277,27 @@ int hs_ec_cuts(hipStream_t st, int count, int nmax, int m, int nb, int maxcuts, 
 int hs_syev_jacobi(hipStream_t s, int n, double* A, double* lam, double* V, int* info, double* ws);
 long long hs_syev_ws(int n);
 
+/* ---- syevx.hip: selected eigenpairs of a matrix of 2 .. 512 rows without a full decomposition ------------------------------
+ * dA: n x n in device memory, the triangle at memory positions [j n + i], i >= j, is read and nothing of it is changed.
+ * mode: HS_SYEVX_INDEX (eigenpairs il .. iu, 1-based, at most HS_SYEVX_MAXK of them) or HS_SYEVX_BELOW (those with eigenvalue
+ * <= bound, at most maxk <= HS_SYEVX_MAXK), | HS_SYEVX_NOVEC: eigenvalues only, the two vector kernels are not launched.
+ * dOut, HS_SYEVX_OUT(n) doubles: [0] pairs returned, [1] eigenvalues <= bound altogether (-1 for an index range),
+ * [HS_SYEVX_OUT_LAM + k] k-th returned eigenvalue (ascending), [HS_SYEVX_OUT_VEC + k n + i] component i of its unit vector.
+ * ws: hs_syevx_ws(n) doubles.  Everything in stream order on st: n + 1 launches for the values, two more for the vectors. */
+#define HS_SYEVX_MAXN 512
+#define HS_SYEVX_MAXK 32
+#define HS_SYEVX_INDEX 0
+#define HS_SYEVX_BELOW 1
+#define HS_SYEVX_NOVEC 2
+#define HS_SYEVX_OUT_LAM 8
+#define HS_SYEVX_OUT_VEC 40
+#define HS_SYEVX_OUT(n) (HS_SYEVX_OUT_VEC + (long long) HS_SYEVX_MAXK * (n))
+int hs_syevx_dev(hipStream_t st, int n, const double* dA, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws);
+size_t hs_syevx_ws(int n);
+/* its first stage alone (the unit entry): d, e, tau (n each) and the reflectors (row j = v_j, entry j + 1 one, zeros before) in ws */
+int hs_syevx_tridiag_dev(hipStream_t st, int n, const double* dA, double* ws);
+void hs_syevx_tridiag_view(int n, double* ws, double** d, double** e, double** R, double** tau);
+
 /* ---- solve1.hip: a whole node solve of a B&B-sized problem in one launch of one workgroup ------------------------------- */
 #define HS_S1_MAXBLK 8
 /* termination status written to out[0]: the HIPSDP_STATUS_* values of include/hipsdp.h, or -2: declined (too much work for one

@@ -937,3 +937,23 @@ extern "C" int hipsdp_syev_many_unit(int device, int count, const int* ns, const
       *launches = nl;
    return HIPSDP_OK;
 }
+
+extern "C" int hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau)
+{
+   HS_CALL( pick_device(device) );
+   if ( n < 2 || n > HS_SYEVX_MAXN || A == NULL || d == NULL || e == NULL || Vrefl == NULL || tau == NULL )
+      return HIPSDP_ERR_ARG;
+   DevBuf din, dws;
+   HS_CALL( din.alloc((long long) n * n) ); HS_CALL( dws.alloc((long long) hs_syevx_ws(n)) );
+   HS_CALL( din.up(A, (long long) n * n) );
+   HS_CALL( hs_syevx_tridiag_dev(0, n, din.p, dws.p) );
+   HS_HIP( hipDeviceSynchronize() );
+   double* pd; double* pe; double* pr; double* pt;
+   hs_syevx_tridiag_view(n, dws.p, &pd, &pe, &pr, &pt);
+   HS_HIP( hipMemcpy(d, pd, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) );
+   HS_HIP( hipMemcpy(e, pe, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) );
+   HS_HIP( hipMemcpy(tau, pt, (size_t) (n - 1) * sizeof(double), hipMemcpyDeviceToHost) );
+   tau[n - 1] = 0.0;
+   HS_HIP( hipMemcpy(Vrefl, pr, (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost) );
+   return HIPSDP_OK;
+}
