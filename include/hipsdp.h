@@ -324,6 +324,14 @@ HIPSDP_API int hipsdp_syevx(int device, int n, const double* A, int il, int iu, 
  * *nbelow (may be NULL) = how many eigenvalues are <= bound altogether (DSYEVR RANGE='V' with a cap). V may be NULL. */
 HIPSDP_API int hipsdp_syevx_below(int device, int n, const double* A, double bound, int maxk, int* count, int* nbelow,
                                   double* lam, double* V);
+/* all eigenpairs, ascending, eigenvectors as rows of V (what DSYEVR RANGE = 'A' computes); n <= HIPSDP_SYEVX_MAXN.  Above 128 rows:
+ * the tridiagonalisation of hipsdp_syevx, all eigenvalues by multisection over several workgroups, the eigenvectors of the
+ * tridiagonal matrix by inverse iteration with re-orthogonalisation inside clusters (per block where the matrix splits), the
+ * back-transformation of all n vectors - csrc/syevr.hip; up to 128 rows hipsdp_syev_small.  Conventions of hipsdp_syevx: the same
+ * triangle is read, signs and the basis of a multiple eigenvalue are free, the n vectors are orthonormal, same input, same bits.
+ * V may be NULL: values only, no vector work is launched.  HIPSDP_ERR_ARG, nothing launched: n < 1, n > HIPSDP_SYEVX_MAXN, A or
+ * lam NULL.  hipsdp_syev is not routed here. */
+HIPSDP_API int hipsdp_syevr(int device, int n, const double* A, double* lam, double* V);
 /* PSD projection chain of the warm-start producer (relax_sdp.c:2715-2766 for Z, :3405-3445 for X), fused on the device: sparse
  * lower/upper triangle (row, col, val; both triangles are filled) -> eigen-decomposition -> eigenvalues below minev (by more
  * than epsilon, SCIPisLT) raised to minev -> recombination -> entries with row <= col and |value| > epsilon in row-major order.

@@ -73,6 +73,9 @@ HIPSDP_API int  hipsdp_syev_many_unit(int device, int count, const int* ns, cons
 /* the first stage of hipsdp_syevx alone, 2 <= n <= 512: the tridiagonal matrix Q^T A Q (d[n], e[n - 1] in e[0 .. n - 2], e[n - 1] = 0)
  * and Q = H_0 H_1 ... H_{n-2}, H_j = I - tau[j] v_j v_j^T, row j of Vrefl (n x n) = v_j (zeros up to entry j, entry j + 1 one) */
 HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau);
+/* stages 2 and 3 of the full decomposition above 128 rows (csrc/syevr.hip) alone on a caller's symmetric tridiagonal matrix, 2 <= n <= 512,
+ * diagonal d[n], off-diagonal e[n - 1]: all eigenvalues (ascending) and the unit eigenvectors of T as the rows of Z (n x n) */
+HIPSDP_API int  hipsdp_tvec_unit(int device, int n, const double* d, const double* e, double* lam, double* Z);
 
 #ifdef __cplusplus
 }

@@ -545,6 +545,31 @@ def syevx_below(A, bound, maxk, vectors=True, device=0):
     return lam[:cnt.value].copy(), (V[:cnt.value].copy() if vectors else None), nbelow.value
 
 
+def syevr(A, vectors=True, device=0):
+    """all eigenpairs of the symmetric matrix A, n <= 512, through the tridiagonal form: lam (ascending), V (row k = k-th unit
+    eigenvector; None with vectors=False: no vector work is done)"""
+    A = _f64(A)
+    n = A.shape[0]
+    lam = np.zeros(n)
+    V = np.zeros((n, n)) if vectors else None
+    _chk(lib().hipsdp_syevr(device, n, _dp(A), _dp(lam), _dp(V) if vectors else None), "hipsdp_syevr")
+    return lam, V
+
+
+def tvec_unit(d, e, device=0):
+    """stages 2 and 3 of syevr alone (libhipsdp_units.so) on the tridiagonal matrix (d, e): lam (ascending), Z (row k = k-th unit
+    eigenvector of T)"""
+    d = _f64(d)
+    e = _f64(e)
+    n = d.shape[0]
+    assert e.shape[0] == n - 1
+    lam, Z = np.zeros(n), np.zeros((n, n))
+    rc = ulib().hipsdp_tvec_unit(device, n, _dp(d), _dp(e), _dp(lam), _dp(Z))
+    if rc != 0:
+        raise RuntimeError("hipsdp_tvec_unit failed: rc=%d (%s)" % (rc, ulib().hipsdp_last_error().decode()))
+    return lam, Z
+
+
 def tridiag_unit(A, device=0):
     """stage 1 of syevx alone (libhipsdp_units.so): d, e (n - 1), Vrefl (row j = reflector j), tau"""
     A = _f64(A)

@@ -1,6 +1,6 @@
 /* host_entries.hip - the host-buffer entry points the SCIPlapack* surface is built on (src/sdpi/lapack_interface_hip.c; reference
  * src/sdpi/lapack_interface.c:398-706: DSYEVR / DGEMV / DGEMM on host arrays, called from cons_sdp.c and relax_sdp.c between node
- * solves) and that the parity tests call directly: hipsdp_dgemm, hipsdp_gemv_n / _t, hipsdp_syev, hipsdp_syevx / _below.
+ * solves) and that the parity tests call directly: hipsdp_dgemm, hipsdp_gemv_n / _t, hipsdp_syev, hipsdp_syevx / _below, hipsdp_syevr.
  *
  * Product path, not scaffolding: every calling host thread owns a context per device - a non-blocking stream, a pinned,
  * device-mapped staging buffer and a pool of device memory, both grow-only - so that a call in steady state does NO hipMalloc /
@@ -286,4 +286,29 @@ extern "C" int hipsdp_syevx_below(int device, int n, const double* A, double bou
    if ( n <= 128 )
       return syevx_small(device, n, A, true, 0, 0, bound, maxk, count, nbelow, lam, maxk > 0 ? V : NULL);
    return syevx_large(device, n, A, HS_SYEVX_BELOW, 0, 0, bound, maxk, count, nbelow, lam, maxk > 0 ? V : NULL);
+}
+
+/* ---- all eigenpairs up to 512 rows through the tridiagonal form (DSYEVR RANGE = 'A'): up to 128 rows the one-launch decomposition
+ * of eigi.hip, above syevr.hip on this thread's context: one upload, one read-back, one synchronisation.  hipsdp_syev is NOT routed
+ * here (the timing table decides that). */
+extern "C" int hipsdp_syevr(int device, int n, const double* A, double* lam, double* V)
+{
+   if ( n < 1 || n > HIPSDP_SYEVX_MAXN || A == NULL || lam == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( n <= 128 )
+      return hipsdp_syev_small(device, n, A, lam, V);
+   const long long n2 = even((long long) n * n), no = even(HS_SYEVR_OUT(n)), nws = even((long long) hs_syevr_ws(n));
+   he_ctx* c = NULL;
+   HS_CALL( he_context(device, n2 + no, n2 + no + nws, &c) );
+   memcpy(c->hpin, A, (size_t) n * n * sizeof(double));
+   double* dA = c->dpool; double* dO = c->dpool + n2; double* dW = c->dpool + n2 + no;
+   HS_HIP( hipMemcpyAsync(dA, c->hpin, (size_t) n * n * sizeof(double), hipMemcpyHostToDevice, c->stream) );
+   HS_CALL( hs_syevr_dev(c->stream, n, dA, V != NULL ? 1 : 0, dO, dW) );
+   const long long back = (V != NULL) ? HS_SYEVR_OUT(n) : n;
+   HS_HIP( hipMemcpyAsync(c->hpin + n2, dO, (size_t) back * sizeof(double), hipMemcpyDeviceToHost, c->stream) );
+   HS_HIP( hipStreamSynchronize(c->stream) );
+   memcpy(lam, c->hpin + n2, (size_t) n * sizeof(double));
+   if ( V != NULL )
+      memcpy(V, c->hpin + n2 + HS_SYEVR_OUT_VEC(n), (size_t) n * n * sizeof(double));
+   return HIPSDP_OK;
 }

@@ -298,6 +298,19 @@ size_t hs_syevx_ws(int n);
 int hs_syevx_tridiag_dev(hipStream_t st, int n, const double* dA, double* ws);
 void hs_syevx_tridiag_view(int n, double* ws, double** d, double** e, double** R, double** tau);
 
+/* ---- syevr.hip: ALL eigenpairs of a matrix of 2 .. 512 rows through the tridiagonal form (stage 1 is hs_syevx_tridiag_dev) --------
+ * dA as for hs_syevx_dev.  dOut, HS_SYEVR_OUT(n) doubles: [k] k-th eigenvalue (ascending), [HS_SYEVR_OUT_VEC(n) + k n + i] component
+ * i of its unit vector (vectors != 0; otherwise no vector kernel is launched).  ws: hs_syevr_ws(n) doubles, its head is the
+ * workspace of syevx.hip.  Everything in stream order on st: n + 2 launches for the values, 4 + 6 ceil(n / 32) more for the vectors. */
+#define HS_SYEVR_OUT_VEC(n) (((long long) (n) + 1) & ~1LL)
+#define HS_SYEVR_OUT(n) (HS_SYEVR_OUT_VEC(n) + (long long) (n) * (n))
+int hs_syevr_dev(hipStream_t st, int n, const double* dA, int vectors, double* dOut, double* ws);
+size_t hs_syevr_ws(int n);
+/* its stages 2 and 3 alone (the unit entry) on the d, e that lie in ws (hs_syevx_tridiag_view; e[n - 1] = 0): eigenvalues to
+ * dOut[0 .. n - 1], the eigenvectors of the tridiagonal matrix as the rows of the n x n array hs_syevr_tvec_view returns */
+int hs_syevr_tvec_dev(hipStream_t st, int n, int vectors, double* dOut, double* ws);
+double* hs_syevr_tvec_view(int n, double* ws);
+
 /* ---- solve1.hip: a whole node solve of a B&B-sized problem in one launch of one workgroup ------------------------------- */
 #define HS_S1_MAXBLK 8
 /* termination status written to out[0]: the HIPSDP_STATUS_* values of include/hipsdp.h, or -2: declined (too much work for one

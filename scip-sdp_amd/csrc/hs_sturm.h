@@ -57,4 +57,53 @@ __device__ __forceinline__ int ei_sturm_count(const double* ds, const double* es
    return cnt;
 }
 
+/* The same count for the leading `rows` rows alone (a block of a matrix that splits, syevr.hip): the steps of ei_sturm_count, those
+ * of the last block of four that lie behind row `rows` are computed and not counted.  ds, es as above; they are read up to three
+ * rows behind the block (the next block of the matrix or the padding). */
+__device__ __forceinline__ int ei_sturm_count_rows(const double* ds, const double* es, int rows, double x)
+{
+   const int nb = (rows - 1 + 3) >> 2;
+   double pp_ = 1.0, pc = ds[0] - x;
+   if ( pc == 0.0 ) pc = -1e-290;
+   bool posc = pc > 0.0;
+   int cnt = posc ? 0 : 1;
+   double dn[4], en[4];
+#pragma unroll
+   for (int u = 0; u < 4; ++u)
+   {
+      dn[u] = ds[1 + u];
+      en[u] = es[u];
+   }
+   for (int b = 0; b < nb; ++b)
+   {
+      double dc[4], ec[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+      {
+         dc[u] = dn[u];
+         ec[u] = en[u];
+      }
+      const int nx = (b + 1 < nb) ? 5 + 4 * b : 1;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+      {
+         dn[u] = ds[nx + u];
+         en[u] = es[nx - 1 + u];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+      {
+         double pn = fma(dc[u] - x, pc, -ec[u] * pp_);
+         if ( pn == 0.0 ) pn = -copysign(1e-290, pc);
+         const bool posn = pn > 0.0;
+         cnt += (posn != posc && 1 + 4 * b + u < rows) ? 1 : 0;
+         pp_ = pc; pc = pn; posc = posn;
+      }
+      const int ex = -max(__builtin_amdgcn_frexp_exp(pc), __builtin_amdgcn_frexp_exp(pp_));
+      pc = ldexp(pc, ex);
+      pp_ = ldexp(pp_, ex);
+   }
+   return cnt;
+}
+
 #endif

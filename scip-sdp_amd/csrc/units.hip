@@ -957,3 +957,22 @@ extern "C" int hipsdp_tridiag_unit(int device, int n, const double* A, double* d
    HS_HIP( hipMemcpy(Vrefl, pr, (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost) );
    return HIPSDP_OK;
 }
+
+extern "C" int hipsdp_tvec_unit(int device, int n, const double* d, const double* e, double* lam, double* Z)
+{
+   HS_CALL( pick_device(device) );
+   if ( n < 2 || n > HS_SYEVX_MAXN || d == NULL || e == NULL || lam == NULL || Z == NULL )
+      return HIPSDP_ERR_ARG;
+   DevBuf dws, dout;
+   HS_CALL( dws.alloc((long long) hs_syevr_ws(n)) ); HS_CALL( dout.alloc(HS_SYEVR_OUT(n)) );
+   double* pd; double* pe; double* pr; double* pt;
+   hs_syevx_tridiag_view(n, dws.p, &pd, &pe, &pr, &pt);
+   HS_HIP( hipMemset(pe, 0, (size_t) n * sizeof(double)) );
+   HS_HIP( hipMemcpy(pd, d, (size_t) n * sizeof(double), hipMemcpyHostToDevice) );
+   HS_HIP( hipMemcpy(pe, e, (size_t) (n - 1) * sizeof(double), hipMemcpyHostToDevice) );
+   HS_CALL( hs_syevr_tvec_dev(0, n, 1, dout.p, dws.p) );
+   HS_HIP( hipDeviceSynchronize() );
+   HS_HIP( hipMemcpy(lam, dout.p, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) );
+   HS_HIP( hipMemcpy(Z, hs_syevr_tvec_view(n, dws.p), (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost) );
+   return HIPSDP_OK;
+}

@@ -1,0 +1,235 @@
+"""GPU: all eigenpairs above 128 rows through the tridiagonal form (hipsdp_syevr, csrc/syevr.hip) and its stages 2 + 3 alone on a
+caller's tridiagonal matrix (hipsdp_tvec_unit).
+
+Reference: numpy.linalg.eigvalsh, scale = max(1, max|ev|).  Tolerances: those of check_pairs in test_gpu_syevx.py, applied to all n
+pairs at once - |lam - ev| <= 1e-12 scale and ascending, | ||v|| - 1 | <= 1e-12, residual <= 1e-9 scale, |V V^T - I| <= 1e-11 over the
+whole n x n product.  numpy.linalg.eigh itself meets them on every matrix below.
+
+Dense sizes: 129 (first size of the multi-launch path: four panels and one vector), 130, 193, 257, 512 (the cap); 5 and 128 are
+served by the one-launch decomposition behind the same interface, bit for bit.  Tridiagonal sizes: the panel edges 31, 32, 33, 65, 129,
+the smallest (2) and the cap."""
+import ctypes as C
+import threading
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+LARGE = [129, 130, 193, 257, 512]
+TSIZES = [2, 31, 32, 33, 65, 129, 512]
+_CACHE = {}
+_TCACHE = {}
+
+
+def spectra(n):
+    """the seven spectra of test_gpu_syevx.py and, above 50 rows, two decoupled blocks that share an eigenvalue and a cluster of 40
+    eigenvalues 1e-10 apart - with their eigenvalues (computed once, shared, read-only)"""
+    if n not in _CACHE:
+        rng = np.random.default_rng(300 + n)
+        Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        cases = {"low_rank_shifted": (lambda B: B @ B.T - 0.01 * np.eye(n))(rng.standard_normal((n, n // 10))),
+                 "rank_one": (lambda b: np.outer(b, b))(rng.standard_normal(n)),
+                 "two_clusters": (Q * np.where(np.arange(n) < n // 2, -1.0, 2.0)) @ Q.T,
+                 "identity": 3.5 * np.eye(n),
+                 "random": (lambda G: G + G.T)(rng.standard_normal((n, n))),
+                 "close_pairs": (Q * np.repeat(np.arange(1, n // 2 + 2, dtype=float), 2)[:n] * (1 + 1e-9 * np.arange(n))) @ Q.T,
+                 "graded": (Q * 10.0 ** np.linspace(-6, 6, n)) @ Q.T}
+        if n > 50:
+            # (the dense sizes) two decoupled random blocks of 50 and n - 50 rows; the second one is built around an eigenvalue of the first
+            G1 = rng.standard_normal((50, 50))
+            B1 = 0.5 * (G1 + G1.T)
+            mu = np.linalg.eigvalsh(B1)[20]
+            Q2, _ = np.linalg.qr(rng.standard_normal((n - 50, n - 50)))
+            ev2 = 3.0 * rng.standard_normal(n - 50)
+            ev2[0] = mu
+            B2 = (Q2 * ev2) @ Q2.T
+            BD = np.zeros((n, n))
+            BD[:50, :50] = B1
+            BD[50:, 50:] = 0.5 * (B2 + B2.T)
+            cases["block_diagonal"] = BD
+            tc = 3.0 * rng.standard_normal(n)
+            tc[:40] = 1.0 + 1e-10 * np.arange(40)
+            cases["tight_cluster"] = (Q * tc) @ Q.T
+        out = {}
+        for name, W in cases.items():
+            W = np.ascontiguousarray(0.5 * (W + W.T))
+            ev = np.linalg.eigvalsh(W)
+            W.setflags(write=False); ev.setflags(write=False)
+            out[name] = (W, ev, max(1.0, np.abs(ev).max()))
+        _CACHE[n] = out
+    return _CACHE[n]
+
+
+def tridiagonals(n):
+    """name -> (d, e, eigenvalues of T, scale); n >= 2"""
+    if n not in _TCACHE:
+        i = np.arange(n, dtype=float)
+        m1 = n // 2
+        m2 = n - m1
+        glued_d = np.concatenate([np.abs(np.arange(m1) - m1 // 2), np.abs(np.arange(m2) - m2 // 2)]).astype(float)
+        glued_e = np.ones(n - 1)
+        glued_e[m1 - 1] = 1e-14
+        cut = np.full(n - 1, 0.5)
+        cut[6::7] = 0.0
+        gd = 10.0 ** np.linspace(-6, 6, n)
+        cases = {"toeplitz_121": (np.full(n, 2.0), np.ones(n - 1)),
+                 "wilkinson": (np.abs(i - n // 2), np.ones(n - 1)),
+                 "wilkinson_glued": (glued_d, glued_e),
+                 "diagonal_repeated": (np.mod(i, 5.0) - 1.0, np.zeros(n - 1)),
+                 "ones_cut_every_7th": (np.ones(n), cut),
+                 "graded": (gd, 1e-3 * np.sqrt(gd[:-1] * gd[1:]))}
+        out = {}
+        for name, (d, e) in cases.items():
+            T = np.diag(d) + np.diag(e, 1) + np.diag(e, -1)
+            ev = np.linalg.eigvalsh(T)
+            for a in (d, e, T, ev):
+                a.setflags(write=False)
+            out[name] = (d, e, T, ev, max(1.0, np.abs(ev).max()))
+        _TCACHE[n] = out
+    return _TCACHE[n]
+
+
+def check_all_pairs(name, W, ev, scale, lam, V):
+    """the four checks of check_pairs (test_gpu_syevx.py) on all n pairs; every figure is printed before it is asserted"""
+    n = W.shape[0]
+    err = np.abs(lam - ev).max()
+    nrm = np.abs(np.linalg.norm(V, axis=1) - 1.0).max()
+    res = np.linalg.norm(W @ V.T - V.T * lam, axis=0).max()
+    orth = np.abs(V @ V.T - np.eye(n)).max()
+    print("%s n=%d: |lam - ev| %.2e (scale %.2e), |norm - 1| %.2e, residual %.2e, |VV^T - I| %.2e" % (name, n, err, scale, nrm, res, orth))
+    bad = []
+    if not err <= 1e-12 * scale:
+        bad.append(("eigenvalues", err))
+    if not np.all(np.diff(lam) >= 0.0):
+        bad.append(("not ascending", float(np.diff(lam).min())))
+    if not nrm <= 1e-12:
+        bad.append(("norm", nrm))
+    if not res <= 1e-9 * scale:
+        bad.append(("residual", res))
+    if not orth <= 1e-11:
+        bad.append(("orthogonality", orth))
+    return [(name, n) + b for b in bad]
+
+
+@pytest.mark.parametrize("n", LARGE)
+def test_dense_route(gpu, n):
+    bad = []
+    for name, (W, ev, scale) in spectra(n).items():
+        lam, V = gpu.syevr(W)
+        bad += check_all_pairs(name, W, ev, scale, lam, V)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("n", [5, 128])
+def test_small_sizes_are_the_one_launch_decomposition(gpu, n):
+    lib = gpu.lib()
+    pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    for name in ("random", "low_rank_shifted", "graded"):
+        W = np.ascontiguousarray(spectra(n)[name][0])
+        lam, V = gpu.syevr(W)
+        lam0, V0 = np.zeros(n), np.zeros((n, n))
+        assert lib.hipsdp_syev_small(0, n, pd(W), pd(lam0), pd(V0)) == 0
+        assert lam.tobytes() == lam0.tobytes() and V.tobytes() == V0.tobytes(), name
+        lamv, Vv = gpu.syevr(W, vectors=False)
+        assert lib.hipsdp_syev_small(0, n, pd(W), pd(lam0), None) == 0
+        assert Vv is None and lamv.tobytes() == lam0.tobytes(), name
+
+
+@pytest.mark.parametrize("n", TSIZES)
+def test_tridiagonal_stages_alone(gpu, n):
+    bad = []
+    for name, (d, e, T, ev, scale) in tridiagonals(n).items():
+        lam, Z = gpu.tvec_unit(d, e)
+        bad += check_all_pairs(name, T, ev, scale, lam, Z)
+        if name == "toeplitz_121":
+            exact = 2.0 - 2.0 * np.cos(np.arange(1, n + 1) * np.pi / (n + 1))
+            err = np.abs(lam - exact).max()
+            print("%s n=%d: against 2 - 2 cos(k pi / (n + 1)) %.2e" % (name, n, err))
+            if not err <= 1e-12 * scale:
+                bad.append((name, n, "analytic", err))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("n", [129, 512])
+def test_values_only_second_call_and_triangle(gpu, n):
+    """vectors=False returns None and the same eigenvalue bits; a second call returns the same bits; the triangle DSYEVR('L') reads
+    from a column-major array (memory [j n + i], i >= j) is the one that is read"""
+    rng = np.random.default_rng(n)
+    for name in ("random", "low_rank_shifted", "graded"):
+        W = spectra(n)[name][0]
+        lam, V = gpu.syevr(W)
+        lam0, V0 = gpu.syevr(W, vectors=False)
+        assert V0 is None and lam0.tobytes() == lam.tobytes(), name
+        lam2, V2 = gpu.syevr(W)
+        assert lam2.tobytes() == lam.tobytes() and V2.tobytes() == V.tobytes(), name
+        B = np.triu(W) + np.tril(rng.standard_normal((n, n)), -1)
+        lamb, Vb = gpu.syevr(B)
+        assert lamb.tobytes() == lam.tobytes() and Vb.tobytes() == V.tobytes(), name
+
+
+def test_agrees_with_selected_pairs(gpu):
+    n = 257
+    for name in ("random", "graded"):
+        W, ev, scale = spectra(n)[name]
+        lam, _ = gpu.syevr(W, vectors=False)
+        for il, iu in ((1, 1), (1, 32), (n // 2, n // 2 + 7), (n - 4, n)):
+            lx, _ = gpu.syevx(W, il, iu, vectors=False)
+            err = np.abs(lam[il - 1:iu] - lx).max()
+            print("%s %d..%d: |syevr - syevx| %.2e (scale %.2e)" % (name, il, iu, err, scale))
+            assert err <= 1e-12 * scale, (name, il, iu, err)
+
+
+def test_arguments(gpu):
+    lib = gpu.lib()
+    n = 130
+    A = np.ascontiguousarray(spectra(n)["random"][0])
+    big = np.ascontiguousarray(spectra(512)["random"][0])
+    pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    lam, V = np.zeros(513), np.zeros((513, 513))
+    bad = 3                                                  # HIPSDP_ERR_ARG
+    assert lib.hipsdp_syevr(0, 0, pd(A), pd(lam), pd(V)) == bad
+    assert lib.hipsdp_syevr(0, -1, pd(A), pd(lam), pd(V)) == bad
+    assert lib.hipsdp_syevr(0, 513, pd(V), pd(lam), None) == bad
+    assert lib.hipsdp_syevr(0, n, None, pd(lam), pd(V)) == bad
+    assert lib.hipsdp_syevr(0, n, pd(A), None, pd(V)) == bad
+    # the cap itself is served, with and without vectors
+    ev, scale = spectra(512)["random"][1:]
+    assert lib.hipsdp_syevr(0, 512, pd(big), pd(lam), None) == 0
+    assert np.abs(lam[:512] - ev).max() <= 1e-12 * scale
+    lam2 = np.zeros(512)
+    assert lib.hipsdp_syevr(0, 512, pd(big), pd(lam2), pd(V)) == 0
+    assert lam2.tobytes() == lam[:512].tobytes()
+
+
+def test_no_allocation_on_a_repeated_call(gpu):
+    lib = gpu.lib()
+    W = spectra(257)["random"][0]
+    gpu.syevr(W)                                             # warm-up: the context grows here
+    f0, f1, tot = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    assert lib.hipsdp_mem_info(0, C.byref(f0), C.byref(tot)) == 0
+    for _ in range(5):
+        gpu.syevr(W)
+    assert lib.hipsdp_mem_info(0, C.byref(f1), C.byref(tot)) == 0
+    assert f0.value == f1.value, (f0.value, f1.value)
+
+
+def test_two_host_threads(gpu):
+    """each host thread has its own context (stream, staging, pool): two threads, four calls each on different matrices, reproduce
+    the single-thread bits"""
+    names = [("random", "graded", "close_pairs", "tight_cluster"), ("low_rank_shifted", "two_clusters", "block_diagonal", "rank_one")]
+    mats = [[spectra(193)[nm][0] for nm in row] for row in names]
+    ref = [[gpu.syevr(W) for W in row] for row in mats]
+    bad = []
+
+    def work(t):
+        for i, W in enumerate(mats[t]):
+            lam, V = gpu.syevr(W)
+            if lam.tobytes() != ref[t][i][0].tobytes() or V.tobytes() != ref[t][i][1].tobytes():
+                bad.append((t, i))
+
+    th = [threading.Thread(target=work, args=(t,)) for t in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not bad, bad
