@@ -47,7 +47,7 @@ def binding():
 
 
 def matrices(n):
-    """the matrices of spectra(n) in tests/test_gpu_syevr.py (same generator, same order of draws)"""
+    """the matrices of spectra(n) in tests/harness/eig_cases.py (same generator, same order of draws)"""
     rng = np.random.default_rng(300 + n)
     Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
     out = {"low_rank_shifted": (lambda B: B @ B.T - 0.01 * np.eye(n))(rng.standard_normal((n, n // 10)))}

@@ -1,7 +1,8 @@
 """GPU: all eigenpairs above 128 rows through the tridiagonal form (hipsdp_syevr, csrc/syevr.hip) and its stages 2 + 3 alone on a
 caller's tridiagonal matrix (hipsdp_tvec_unit).
 
-Reference: numpy.linalg.eigvalsh, scale = max(1, max|ev|).  Tolerances: those of check_pairs in test_gpu_syevx.py, applied to all n
+Reference: numpy.linalg.eigvalsh, scale = max(1, max|ev|).  Matrices and checks: tests/harness/eig_cases.py, shared with
+test_gpu_syevx.py; the tolerances of check_pairs applied to all n
 pairs at once - |lam - ev| <= 1e-12 scale and ascending, | ||v|| - 1 | <= 1e-12, residual <= 1e-9 scale, |V V^T - I| <= 1e-11 over the
 whole n x n product.  numpy.linalg.eigh itself meets them on every matrix below.
 
@@ -12,52 +13,19 @@ import ctypes as C
 import threading
 import numpy as np
 import pytest
+import eig_cases
+from eig_cases import check_all_pairs
 
 pytestmark = pytest.mark.gpu
 
 LARGE = [129, 130, 193, 257, 512]
 TSIZES = [2, 31, 32, 33, 65, 129, 512]
-_CACHE = {}
 _TCACHE = {}
 
 
 def spectra(n):
-    """the seven spectra of test_gpu_syevx.py and, above 50 rows, two decoupled blocks that share an eigenvalue and a cluster of 40
-    eigenvalues 1e-10 apart - with their eigenvalues (computed once, shared, read-only)"""
-    if n not in _CACHE:
-        rng = np.random.default_rng(300 + n)
-        Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-        cases = {"low_rank_shifted": (lambda B: B @ B.T - 0.01 * np.eye(n))(rng.standard_normal((n, n // 10))),
-                 "rank_one": (lambda b: np.outer(b, b))(rng.standard_normal(n)),
-                 "two_clusters": (Q * np.where(np.arange(n) < n // 2, -1.0, 2.0)) @ Q.T,
-                 "identity": 3.5 * np.eye(n),
-                 "random": (lambda G: G + G.T)(rng.standard_normal((n, n))),
-                 "close_pairs": (Q * np.repeat(np.arange(1, n // 2 + 2, dtype=float), 2)[:n] * (1 + 1e-9 * np.arange(n))) @ Q.T,
-                 "graded": (Q * 10.0 ** np.linspace(-6, 6, n)) @ Q.T}
-        if n > 50:
-            # (the dense sizes) two decoupled random blocks of 50 and n - 50 rows; the second one is built around an eigenvalue of the first
-            G1 = rng.standard_normal((50, 50))
-            B1 = 0.5 * (G1 + G1.T)
-            mu = np.linalg.eigvalsh(B1)[20]
-            Q2, _ = np.linalg.qr(rng.standard_normal((n - 50, n - 50)))
-            ev2 = 3.0 * rng.standard_normal(n - 50)
-            ev2[0] = mu
-            B2 = (Q2 * ev2) @ Q2.T
-            BD = np.zeros((n, n))
-            BD[:50, :50] = B1
-            BD[50:, 50:] = 0.5 * (B2 + B2.T)
-            cases["block_diagonal"] = BD
-            tc = 3.0 * rng.standard_normal(n)
-            tc[:40] = 1.0 + 1e-10 * np.arange(40)
-            cases["tight_cluster"] = (Q * tc) @ Q.T
-        out = {}
-        for name, W in cases.items():
-            W = np.ascontiguousarray(0.5 * (W + W.T))
-            ev = np.linalg.eigvalsh(W)
-            W.setflags(write=False); ev.setflags(write=False)
-            out[name] = (W, ev, max(1.0, np.abs(ev).max()))
-        _CACHE[n] = out
-    return _CACHE[n]
+    """the seven spectra of tests/harness/eig_cases.py and, above 50 rows, its two decoupled ones"""
+    return eig_cases.spectra(n, decoupled=True)
 
 
 def tridiagonals(n):
@@ -87,28 +55,6 @@ def tridiagonals(n):
             out[name] = (d, e, T, ev, max(1.0, np.abs(ev).max()))
         _TCACHE[n] = out
     return _TCACHE[n]
-
-
-def check_all_pairs(name, W, ev, scale, lam, V):
-    """the four checks of check_pairs (test_gpu_syevx.py) on all n pairs; every figure is printed before it is asserted"""
-    n = W.shape[0]
-    err = np.abs(lam - ev).max()
-    nrm = np.abs(np.linalg.norm(V, axis=1) - 1.0).max()
-    res = np.linalg.norm(W @ V.T - V.T * lam, axis=0).max()
-    orth = np.abs(V @ V.T - np.eye(n)).max()
-    print("%s n=%d: |lam - ev| %.2e (scale %.2e), |norm - 1| %.2e, residual %.2e, |VV^T - I| %.2e" % (name, n, err, scale, nrm, res, orth))
-    bad = []
-    if not err <= 1e-12 * scale:
-        bad.append(("eigenvalues", err))
-    if not np.all(np.diff(lam) >= 0.0):
-        bad.append(("not ascending", float(np.diff(lam).min())))
-    if not nrm <= 1e-12:
-        bad.append(("norm", nrm))
-    if not res <= 1e-9 * scale:
-        bad.append(("residual", res))
-    if not orth <= 1e-11:
-        bad.append(("orthogonality", orth))
-    return [(name, n) + b for b in bad]
 
 
 @pytest.mark.parametrize("n", LARGE)

@@ -1,60 +1,18 @@
 """GPU: selected eigenpairs without a full decomposition (hipsdp_syevx / hipsdp_syevx_below, csrc/syevx.hip).
 
 Sizes: 129 (first size of the multi-launch path), 130 (even), 193 (not divisible by the rows per workgroup), 257 (one past a power of
-two), 512 (the cap); 5, 64, 128 are served by the one-launch kernels behind the same interface.  Reference: numpy.linalg.eigvalsh,
-scale = max(1, max|ev|); tolerances are those of test_gpu_units.py for the one-launch kernels."""
+two), 512 (the cap); 5, 64, 128 are served by the one-launch kernels behind the same interface.  Matrices (the seven spectra),
+reference and tolerances: tests/harness/eig_cases.py, shared with test_gpu_syevr.py."""
 import ctypes as C
 import threading
 import numpy as np
 import pytest
+from eig_cases import spectra, check_pairs
 
 pytestmark = pytest.mark.gpu
 
 LARGE = [129, 130, 193, 257, 512]
 SMALL = [5, 64, 128]
-_CACHE = {}
-
-
-def spectra(n):
-    """the spectra of test_block_jacobi_on_clustered_spectra plus graded / close_pairs of test_mid_full_decomposition_in_one_launch, with
-    their eigenvalues (computed once, shared, read-only)"""
-    if n not in _CACHE:
-        rng = np.random.default_rng(300 + n)
-        Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-        cases = {"low_rank_shifted": (lambda B: B @ B.T - 0.01 * np.eye(n))(rng.standard_normal((n, n // 10))),
-                 "rank_one": (lambda b: np.outer(b, b))(rng.standard_normal(n)),
-                 "two_clusters": (Q * np.where(np.arange(n) < n // 2, -1.0, 2.0)) @ Q.T,
-                 "identity": 3.5 * np.eye(n),
-                 "random": (lambda G: G + G.T)(rng.standard_normal((n, n))),
-                 "close_pairs": (Q * np.repeat(np.arange(1, n // 2 + 2, dtype=float), 2)[:n] * (1 + 1e-9 * np.arange(n))) @ Q.T,
-                 "graded": (Q * 10.0 ** np.linspace(-6, 6, n)) @ Q.T}
-        out = {}
-        for name, W in cases.items():
-            W = np.ascontiguousarray(0.5 * (W + W.T))
-            ev = np.linalg.eigvalsh(W)
-            W.setflags(write=False); ev.setflags(write=False)
-            out[name] = (W, ev, max(1.0, np.abs(ev).max()))
-        _CACHE[n] = out
-    return _CACHE[n]
-
-
-def check_pairs(name, W, ev, scale, first, lam, V):
-    """accuracy of returned pairs first .. first + len(lam) - 1 (1-based)"""
-    k = len(lam)
-    n = W.shape[0]
-    err = np.abs(lam - ev[first - 1:first - 1 + k]).max()
-    print("%s n=%d pairs %d..%d: |lam - ev| %.2e (scale %.2e)" % (name, n, first, first + k - 1, err, scale), end="")
-    assert err <= 1e-12 * scale, (name, first, err)
-    assert np.all(np.diff(lam) >= 0.0), (name, first)
-    if V is not None:
-        nrm = np.abs(np.linalg.norm(V, axis=1) - 1.0).max()
-        res = np.linalg.norm(W @ V.T - V.T * lam, axis=0).max()
-        orth = np.abs(V @ V.T - np.eye(k)).max()
-        print(", |norm - 1| %.2e, residual %.2e, |VV^T - I| %.2e" % (nrm, res, orth), end="")
-        assert nrm <= 1e-12, (name, first, nrm)
-        assert res <= 1e-9 * scale, (name, first, res)
-        assert orth <= 1e-11, (name, first, orth)
-    print()
 
 
 @pytest.mark.parametrize("n", [129, 193, 512])
