@@ -82,7 +82,9 @@ typedef struct hipsdp_info
    double solve_seconds;    /* wall time of hipsdp_solve */
    double schur_seconds;    /* device time spent in the Schur assembly (sum of HIP event intervals) */
    double schur_flops;      /* algorithmic flops of the assemblies: (4 m1 n^3 + m1^2 n^2) per block and iteration */
-   int    schur_calls;
+   int    schur_calls;      /* assemblies, one per iteration.  A first assembly taken from the cold-start store (hipsdp_gram_cache_stats)
+                             * counts as a call - its copy's time is in schur_seconds - and adds nothing to schur_flops or
+                             * schur_flops_executed: no matrix-core flops ran for it */
    int    chol_fail;        /* number of step halvings forced by a failed Cholesky */
    int    warm_started;     /* 1: the point given with hipsdp_set_start was interior and has been used */
    int    settings_used;    /* the hipsdp_params.settings this solve ran with */
@@ -141,7 +143,8 @@ HIPSDP_API int  hipsdp_master_gather(hipsdp_solver* solver, int engine_block, in
 HIPSDP_API int  hipsdp_set_block_dense(hipsdp_solver* solver, int block, const double* A);
 /* LP rows: Dext[q x (m+1)] host, row-major, column 0 = c (constant), columns 1..m = D */
 HIPSDP_API int  hipsdp_set_lp(hipsdp_solver* solver, const double* Dext);
-/* device-resident access for generators / benchmarks: pointer to A_k on the device */
+/* device-resident access for generators / benchmarks: pointer to A_k on the device.  The engine cannot see what is written through
+ * it: the first assembly of such a block is computed in every cold solve (no cold-start store) for as long as the allocation lives */
 HIPSDP_API int  hipsdp_block_device_ptr(hipsdp_solver* solver, int block, double** dptr);
 
 /* optional warm start (host arrays; X, Z: nblocks dense n_k x n_k matrices; x, z: q) */
@@ -149,6 +152,14 @@ HIPSDP_API int  hipsdp_set_start(hipsdp_solver* solver, const double* y, const d
    const double* x, const double* z);
 
 HIPSDP_API int  hipsdp_solve(hipsdp_solver* solver, const hipsdp_params* params, hipsdp_info* info);
+/* Cold-start store.  A cold solve starts from X = Z = xi I, where the first Schur matrix is the Gram matrix <A_i, A_j> of the
+ * constraint matrices: a function of the matrices alone, whatever b, the LP rows, the tolerances and the settings are.  On one
+ * device, on the general path, with every block dense, the solver keeps that matrix (8 (m + 33) (m + 1) bytes) and a later cold solve
+ * of the SAME matrices copies it instead of computing it - bit for bit what it would have computed.  Every call that writes, gathers,
+ * generates, clears or re-shapes the matrices of a block makes the next cold solve compute (and store) it again.  Not used: warm
+ * starts, the one-launch path, blocks kept as nonzeros, several ranks, sharded matrices.  hits / misses (either may be NULL): cold
+ * solves of this solver so far that took the matrix from the store / that computed and stored it. */
+HIPSDP_API int  hipsdp_gram_cache_stats(hipsdp_solver* solver, long long* hits, long long* misses);
 
 /* B&B-sized problems (no communicator, every block <= 64 rows, m <= 108 (HIPSDP_SOLVE1_MAXM; 128 fit), q <= 4096, the fixed part of the state fits the 160 KiB of
  * LDS of one compute unit - hs_solve1_fits: with no LP rows one block of 49 rows at m = 1, 37 at m = 108, two of 34 / 25, eight of 16 / 12 -, and one Schur assembly

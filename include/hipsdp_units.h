@@ -66,6 +66,13 @@ HIPSDP_API int  hipsdp_lambda_min_scaled(int device, int n, const double* L, con
  * and the size class that would serve it (10 / 16 / 64: largest block, 1064: m > 64; -1: no such shape) */
 HIPSDP_API int  hipsdp_solve1_fits(int m, int q, int nblk, const int* ns);
 HIPSDP_API int  hipsdp_solve1_class(int m, int nblk, const int* ns);
+/* host only: the bookkeeping of the cold-start store (csrc/hs_gram_cache.h).  hipsdp_gram_gen_next: the next generation number of
+ * *counter.  hipsdp_gram_key_match_unit: 1 when a Gram matrix stored under key a (m variables, nblk blocks of n[k] rows with form[k]
+ * - 1 full rows, 2 packed - and generation gen[k], workspace ws = {kws_len, chunk_cols, full}) serves a cold solve with key b; 0 when
+ * it does not, or when either key is none the store would take */
+HIPSDP_API unsigned long long hipsdp_gram_gen_next(unsigned long long* counter);
+HIPSDP_API int  hipsdp_gram_key_match_unit(int m_a, int nblk_a, const int* n_a, const int* form_a, const unsigned long long* gen_a,
+   const long long* ws_a, int m_b, int nblk_b, const int* n_b, const int* form_b, const unsigned long long* gen_b, const long long* ws_b);
 /* the batched full decomposition behind hipsdp_eigencuts_all on `count` host matrices, one behind the other in A: matrix j has
  * ns[j] <= 128 rows; lam: ns[j] eigenvalues each (ascending), V: ns[j] x ns[j] each (row k = k-th eigenvector) - for every matrix
  * the bits of hipsdp_syev_small; *launches: kernel launches issued (at most 3, whatever count is) */

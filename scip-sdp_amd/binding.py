@@ -212,6 +212,13 @@ class Solver:
         """1: the last solve ran in the one-launch kernel of csrc/solve1.hip, 0: the general path"""
         return lib().hipsdp_solve_path(self.h)
 
+    def gram_cache_stats(self):
+        """(hits, misses) of this solver's cold-start store: cold solves that copied the first Schur matrix / computed and stored it"""
+        hits = C.c_longlong(0)
+        misses = C.c_longlong(0)
+        _chk(lib().hipsdp_gram_cache_stats(self.h, C.byref(hits), C.byref(misses)), "hipsdp_gram_cache_stats")
+        return hits.value, misses.value
+
     def solve1_trace(self, rows=0):
         out = np.zeros(64)
         hist = np.zeros((max(rows, 1), 16))

@@ -13,6 +13,7 @@
  * The host thread only reads back a few dozen scalars three times per iteration and decides sigma / alpha / termination.
  */
 #include "hs_kernels.h"
+#include "hs_gram_cache.h"
 #include "../../include/hipsdp.h"
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include <vector>
@@ -75,6 +76,8 @@ struct Block
    double *pkv;      /* 2 Lp: packed vector in / out */
    long long Lp;
    bool apk_valid;
+   unsigned long long A_gen;   /* generation of the matrices (hs_gram_cache.h): a new number from every writer of A / A0 (a_written) */
+   bool a_escaped;       /* the caller holds a device pointer to A (hipsdp_block_device_ptr) and may write at any time: never cached */
    bool derived_valid;   /* n <= 64: LxInv, LzInv (and Zinv for n <= 32) belong to the current X, Z (written by the fused factorization) */
    /* SPARSE mode (csrc/sparse.hip): the matrices of the variables are kept as the caller's nonzeros - A is NULL, A0 a dense n x n
     * array of its own; the triplets are collected on the host (sph) and built into the device structure sp before they are used */
@@ -202,7 +205,22 @@ struct hipsdp_solver
    double* ec_pin; long long ec_pin_len;
    char* ec_tab; long long ec_tab_len;
    std::vector<hs_ec_job> ec_jobs; std::vector<hs_eig_job> ec_ejobs;
+   /* the first assembly of a cold solve, kept across solves of the same matrices (hs_gram_cache.h; GeneralSolve::assemble_forms):
+    * gc_M holds (m1 + 32) m1 doubles as the identity assemblies left them in Mx, gc_key says of what.  Allocated at the first cold
+    * solve that qualifies (gc_nomem: that failed for this shape, not tried again), freed with the problem. */
+   unsigned long long a_gen_next;
+   double* gc_M; long long gc_len; bool gc_nomem;
+   hs_gram_key gc_key;
+   long long gc_hits, gc_misses;
 };
+
+/* EVERY writer of a dense block's constraint matrices (rows of A, the constant matrix A0 included) ends here: the packed copy is
+ * stale and the matrices are a new generation - a cached Gram matrix of the old one no longer matches */
+static void a_written(hipsdp_solver* s, Block& B)
+{
+   B.apk_valid = false;
+   B.A_gen = hs_gen_next(&s->a_gen_next);
+}
 
 void hs_comm_phase(int phase);      /* multi.hip: the phase the next collectives are booked under */
 
@@ -485,6 +503,9 @@ static void free_problem(hipsdp_solver* s)
       s->dinvm, s->Slp, s->sc, s->red_ws, s->gemv_ws, s->lan_ws, s->lan_ws2};
    for (double* p : ptrs) dfree(p);
    hs_schur_ws_free(&s->sws);
+   if ( s->gc_M != NULL ) (void) hipFree(s->gc_M);
+   s->gc_M = NULL; s->gc_len = 0; s->gc_nomem = false;
+   hs_gram_key_clear(&s->gc_key);
    dfree(s->Mgather);
    s->Mgather = NULL;
    dfree(s->passg);
@@ -548,6 +569,8 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0; s->stage_off = 0; s->stage_pending = false; s->ncmd = 0; s->cmd_ev = NULL; s->cmd_inflight = false; s->m_alloc = 0; s->q_alloc = 0;
    s->ec_dev = NULL; s->ec_dev_len = 0; s->ec_pin = NULL; s->ec_pin_len = 0; s->ec_tab = NULL; s->ec_tab_len = 0;
    s->trsv_ws = NULL;
+   s->a_gen_next = 0; s->gc_M = NULL; s->gc_len = 0; s->gc_nomem = false; s->gc_hits = s->gc_misses = 0;
+   hs_gram_key_clear(&s->gc_key);
    s->pre_y = s->pre_x = NULL;
    s->pre_valid = false;
    s->pre_scale = 1.0;
@@ -749,7 +772,7 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
             }
             else
                HS_CALL( stage_zero(s, B.Aown, m1s * B.n * B.n) );
-            B.apk_valid = false;
+            a_written(s, B);
             B.derived_valid = false;
          }
          /* (b and Dext are cleared when they are next used - unless set_obj / set_lp, which replace them whole, come first) */
@@ -830,7 +853,7 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
       HS_CALL( dalloc(&R.dinvz, nd) );
       HS_CALL( dalloc(&R.dinvx, nd) );
       R.Lp = (((long long) B.n * (B.n + 1) / 2) + 1) & ~1LL;
-      R.apk_valid = false;
+      a_written(s, R);            /* (a fresh allocation, cleared above) */
       R.Apk = NULL;
       R.pkv = NULL;
       /* the packed copy halves the HBM traffic of the passes; small blocks are launch bound and their passes take one
@@ -1026,6 +1049,7 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
          memcpy(hi + 2 * nnz, col, (size_t) nnz * sizeof(int));
          const double* dval = (const double*) dvp;
          const int* di = (const int*) ((const char*) dvp + (size_t) nnz * sizeof(double));
+         a_written(s, B);
          NodeCmd* q = cmd_new(s);
          if ( q != NULL )
          {
@@ -1040,12 +1064,12 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
             HS_LAUNCH_CHECK();
             s->stage_pending = true;
          }
-         B.apk_valid = false;
          s->solved = false;
          return HIPSDP_OK;
       }
    }
    int *dv, *dr, *dc; double* dval;
+   a_written(s, B);         /* (before the first call that can fail: entries in range are written even when one is not) */
    HS_CALL( flush_cmds(s) );
    HS_CALL( dalloc(&dv, nnz) ); HS_CALL( dalloc(&dr, nnz) ); HS_CALL( dalloc(&dc, nnz) ); HS_CALL( dalloc(&dval, nnz) );
    HS_HIP( hipMemcpyAsync(dv, var, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
@@ -1061,7 +1085,6 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
    HS_HIP( hipMemcpyAsync(&herr, s->flags + 6, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
    HS_HIP( hipStreamSynchronize(s->stream) );
    dfree(dv); dfree(dr); dfree(dc); dfree(dval);
-   B.apk_valid = false;
    s->solved = false;
    if ( herr != 0 )
    {
@@ -1300,6 +1323,7 @@ extern "C" int hipsdp_master_gather(hipsdp_solver* s, int engine_block, int mast
       if ( kept[r] < 0 || kept[r] >= N )
          return HIPSDP_ERR_ARG;
    Block& B = s->blk[engine_block];
+   a_written(s, B);
    long long g = ((long long) nactive * nkept * nkept + 255) / 256; if ( g > 65536 ) g = 65536;
    {
       /* the two index lists through the arena: the kernel reads them there, nothing is copied and nothing waited for */
@@ -1338,7 +1362,6 @@ extern "C" int hipsdp_master_gather(hipsdp_solver* s, int engine_block, int mast
          dfree(dact); dfree(dkept);
       }
    }
-   B.apk_valid = false;
    s->solved = false;
    return HIPSDP_OK;
 }
@@ -1356,11 +1379,11 @@ extern "C" int hipsdp_set_block_dense(hipsdp_solver* s, int block, const double*
       return HIPSDP_ERR_ARG;
    }
    const size_t n2b = (size_t) B.n * B.n * sizeof(double);
+   a_written(s, B);
    if ( s->a_r1 > s->a_r0 )
       HS_HIP( hipMemcpy(B.Aown, A + (size_t) s->a_r0 * B.n * B.n, (size_t) (s->a_r1 - s->a_r0) * n2b, hipMemcpyHostToDevice) );
    if ( B.A0sep != NULL )
       HS_HIP( hipMemcpy(B.A0sep, A, n2b, hipMemcpyHostToDevice) );
-   B.apk_valid = false;
    s->solved = false;
    return HIPSDP_OK;
 }
@@ -1392,6 +1415,7 @@ extern "C" int hipsdp_gen_planted(hipsdp_solver* s, int n, int m, long long seed
    const long long n2 = (long long) n * n;
    const int m1 = m + 1;
    hipStream_t st = s->stream;
+   a_written(s, B);         /* (first: a failure below leaves the matrices half written) */
    HS_CALL( hs_gen_dense(st, n, s->a_r0 > 1 ? s->a_r0 : 1, s->a_r1, seed, B.A) );
    /* A_0 = sum_i ystar_i A_i - Zstar : coefficient vector [0, ystar] over all m + 1 rows (row 0 is overwritten) */
    HS_HIP( hipMemcpyAsync(B.Z, Zstar, (size_t) n2 * sizeof(double), hipMemcpyHostToDevice, st) );
@@ -1403,7 +1427,7 @@ extern "C" int hipsdp_gen_planted(hipsdp_solver* s, int n, int m, long long seed
    {
       /* every rank generated the matrices it holds; the two sums over all variables go through the sharded passes (row 0 is
        * zero and has coefficient 0 in the first, and its entry of the second is not used) */
-      B.apk_valid = false;
+      a_written(s, B);
       HS_CALL( ensure_packed(s) );
       HS_CALL( pass_AT(s, B, s->yt, -1.0, B.Z, B.T1) );
       HS_CALL( hs_symmetrize(st, B.T1, n) );
@@ -1422,7 +1446,7 @@ extern "C" int hipsdp_gen_planted(hipsdp_solver* s, int n, int m, long long seed
    HS_CALL( hs_copy(st, s->b, s->AX + 1, m) );
    HS_HIP( hipMemcpyAsync(b_out, s->b, (size_t) m * sizeof(double), hipMemcpyDeviceToHost, st) );
    HS_HIP( hipStreamSynchronize(st) );
-   B.apk_valid = false;
+   a_written(s, B);
    s->solved = false;
    return HIPSDP_OK;
 }
@@ -1474,6 +1498,10 @@ extern "C" int hipsdp_block_device_ptr(hipsdp_solver* s, int block, double** dpt
    if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() )
       return HIPSDP_ERR_ARG;
    HS_CALL( stage_sync(s) );
+   /* whoever holds the pointer may write through it whenever it likes, unseen: the block counts as written now and its first
+    * assembly is not cached for as long as this allocation lives (a hipsdp_set_shape of the same shape keeps it) */
+   a_written(s, s->blk[block]);
+   s->blk[block].a_escaped = true;
    *dptr = s->blk[block].Aown;
    return HIPSDP_OK;
 }
@@ -1951,6 +1979,7 @@ static int ensure_packed(hipsdp_solver* s)
       {
          if ( s->a_r1 > s->a_r0 )
             HS_CALL( hs_pack_rows(s->stream, s->a_r1 - s->a_r0, B.n, B.Lp, B.Aown, B.Apkown) );
+         a_written(s, B);       /* (the packed copy is an operand of the cached assembly too: rebuilt counts as written) */
          B.apk_valid = true;
       }
    }
@@ -2996,6 +3025,7 @@ struct GeneralSolve
    double mu = 0, pinf = 0, dinf = 0, dabs = 0, gap = 0, pobj = 0, dobj = 0, rg = 0;
    double schur_ms = 0.0;
    bool defer_join = false, gram_only_used = false, schur_small = false;
+   bool gram_cached = false;          /* this assembly came out of the store: no matrix-core flops were executed for it */
    bool predH_queued = false, predH_joined = false, split_dz = false;
    double dta = 0, dka = 0, sigma = 0, eta = 0, amax = 0, alpha = 0, dt = 0, dk = 0;
    double tau0 = 0, kappa0 = 0, applied = 0;
@@ -3480,7 +3510,7 @@ struct GeneralSolve
    int assemble()
    {
       phase_mark(s, PH_SCHUR);
-      gram_only_used = false;
+      gram_only_used = gram_cached = false;
       hs_comm_phase(0);
       const bool clk_this = s->clk_on && s->clk_buf != NULL && s->clk_stream != NULL && s->clk_n < CLK_MAX_ASSEMBLIES;
       HS_HIP( hipEventRecord(s->ev0, st) );
@@ -3533,11 +3563,76 @@ struct GeneralSolve
       return HS_OK;
    }
 
+   /* which identity form a dense block takes on one device (see assemble_forms) */
+   bool identity_packed(const Block& B) const
+   {
+      return B.Apk != NULL && hs_schur_identity_packed_fits(&s->sws, m1, B.n);
+   }
+
+   /* Cold start on one device, general path, every block dense: the first assembly is a function of the constraint matrices alone and
+    * is kept across solves (hs_gram_cache.h).  Fills the key of what this assembly would compute and makes sure the store exists;
+    * false: this assembly is not cached (computed as ever, the store left alone) - warm start or HIPSDP_NO_IDENTITY_START, a later
+    * iteration, several ranks or any sharded / forced / U form, a block kept as nonzeros, a block whose device pointer the caller
+    * holds, or no memory for the store. */
+   bool gram_cache_key(hs_gram_key* key)
+   {
+      if ( !(identity_start && it == 0) || s->comm != NULL || s->shardA || s->schur_mode_cols || s->schur_mode_rows || K < 1
+         || K > HS_GRAM_MAXBLK )
+         return false;
+      int bn[HS_GRAM_MAXBLK], form[HS_GRAM_MAXBLK];
+      unsigned long long gen[HS_GRAM_MAXBLK];
+      for (int k = 0; k < K; ++k)
+      {
+         const Block& B = s->blk[k];
+         if ( B.sparse || B.a_escaped )
+            return false;
+         bn[k] = B.n;
+         form[k] = identity_packed(B) ? HS_GRAM_FORM_PACKED : HS_GRAM_FORM_FULL;
+         gen[k] = B.A_gen;
+      }
+      if ( !hs_gram_key_make(key, m, K, bn, form, gen, s->sws.kws_len, s->sws.chunk_cols, s->sws.full) )
+         return false;
+      const long long len = (long long) (m1 + 32) * m1;
+      if ( s->gc_M != NULL && s->gc_len != len )
+      {
+         /* (a shape of the same blocks with another m inside the same allocations: nothing is queued on the store - the copy into it
+          * and every copy out of it ran in solves that have ended) */
+         (void) hipFree(s->gc_M);
+         s->gc_M = NULL;
+         s->gc_nomem = false;
+         hs_gram_key_clear(&s->gc_key);
+      }
+      if ( s->gc_M == NULL && !s->gc_nomem )
+      {
+         if ( hipMalloc((void**) &s->gc_M, (size_t) len * sizeof(double)) != hipSuccess )
+         {
+            (void) hipGetLastError();        /* no room: no cache, not an error */
+            s->gc_M = NULL;
+            s->gc_nomem = true;
+         }
+         s->gc_len = len;
+         hs_gram_key_clear(&s->gc_key);
+      }
+      return s->gc_M != NULL;
+   }
+
    /* the assembly in the form the solver's mode selects, then the sparse blocks and the LP term */
    int assemble_forms()
    {
-      HS_CALL( hs_fill(st, s->Mx, (long long) m1 * m1, 0.0) );
-      if ( s->shardA )
+      hs_gram_key gkey;
+      const bool gram_keyed = gram_cache_key(&gkey);
+      gram_cached = gram_keyed && hs_gram_key_match(&s->gc_key, &gkey);
+      if ( !gram_cached )
+         HS_CALL( hs_fill(st, s->Mx, (long long) m1 * m1, 0.0) );
+      if ( gram_cached )
+      {
+         /* the same matrices as at the cold solve that stored it: the Gram matrix of all blocks as that solve's identity assemblies
+          * left it in Mx (padding rows included) - no clear, no Gram launch, no summation, no D D^T */
+         HS_CALL( hs_copy(st, s->Mx, s->gc_M, s->gc_len) );
+         ++s->gc_hits;
+         gram_only_used = true;
+      }
+      else if ( s->shardA )
       {
          /* matrices sharded by variable: W_j where A_j lives, all-to-all of the row ranges, partial Gram matrices summed */
          for (auto& B : s->blk)
@@ -3622,7 +3717,7 @@ struct GeneralSolve
                 * packed form gathers into it (m1 above about 128 n).  The sharded branches above stay on the full storage: a rank's packed
                 * copy covers its own rows only. */
                assert(B.Apk == NULL || B.apk_valid);
-               if ( B.Apk != NULL && hs_schur_identity_packed_fits(&s->sws, m1, B.n) )
+               if ( identity_packed(B) )
                   HS_CALL( hs_schur_W_identity_packed(st, m1, B.n, B.Apk, B.Lp, s->Mx, &s->sws) );
                else
                   HS_CALL( hs_schur_W_identity(st, m1, B.n, B.A, s->Mx, &s->sws) );
@@ -3632,6 +3727,13 @@ struct GeneralSolve
                HS_CALL( hs_schur_U(st, m1, B.n, B.A, B.X, B.Zinv, s->Mx, &s->sws, 0, m1) );
             else
                HS_CALL( hs_schur_W(st, m1, B.n, B.A, B.Lx, B.LzInv, s->Mx, &s->sws) );
+         }
+         if ( gram_keyed )
+         {
+            /* a cold solve of matrices the store does not hold: kept for the next one (before the LP term, which depends on x / z) */
+            ++s->gc_misses;
+            HS_CALL( hs_copy(st, s->gc_M, s->Mx, s->gc_len) );
+            s->gc_key = gkey;
          }
       }
       /* blocks in sparse mode (csrc/sparse.hip), on every rank alike, behind the exchange of the sharded forms: column 0 from
@@ -3784,8 +3886,10 @@ struct GeneralSolve
          schur_ms += ms;
       info->schur_calls++;
       /* (the assembly at the cold start is the Gram product alone: the count of SURVEY.md 8(d) without its n^3 part) */
+      /* (... and one that came out of the store is a call, hipsdp.h, but no flops: every block of it is dense) */
       for (auto& B : s->blk)
-         info->schur_flops += (gram_only_used && !B.sparse ? 0.0 : 4.0 * m1 * (double) B.n * B.n * B.n) + (double) m1 * m1 * (double) B.n * B.n;
+         if ( !gram_cached )
+            info->schur_flops += (gram_only_used && !B.sparse ? 0.0 : 4.0 * m1 * (double) B.n * B.n * B.n) + (double) m1 * m1 * (double) B.n * B.n;
       if ( hflags[0] != 0 || hflags[1] != 0 || hflags[2] != 0 )
       {
          if ( par.verbose )
@@ -4351,6 +4455,15 @@ extern "C" int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const
          rc_all = I.rc;
    }
    return rc_all;
+}
+
+extern "C" int hipsdp_gram_cache_stats(hipsdp_solver* s, long long* hits, long long* misses)
+{
+   if ( s == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( hits != NULL ) *hits = s->gc_hits;
+   if ( misses != NULL ) *misses = s->gc_misses;
+   return HIPSDP_OK;
 }
 
 extern "C" int hipsdp_solve_many_stats(long long* launches, long long* problems)

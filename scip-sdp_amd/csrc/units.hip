@@ -3,6 +3,7 @@
  * per-call allocations - fine for tests, not for the product: what lapack_interface_hip.c calls (hipsdp_dgemm, hipsdp_gemv_*,
  * hipsdp_syev) lives in host_entries.hip.  Nothing here has a CPU code path. */
 #include "hs_kernels.h"
+#include "hs_gram_cache.h"
 #include "../../include/hipsdp.h"
 #include "../../include/hipsdp_units.h"
 #include <vector>
@@ -868,6 +869,22 @@ extern "C" int hipsdp_solve1_fits(int m, int q, int nblk, const int* ns)
    if ( ns == NULL || nblk < 1 || nblk > HS_S1_MAXBLK )
       return 0;
    return hs_solve1_fits(m, q, nblk, ns);
+}
+
+extern "C" unsigned long long hipsdp_gram_gen_next(unsigned long long* counter)
+{
+   return counter != NULL ? hs_gen_next(counter) : 0;
+}
+
+extern "C" int hipsdp_gram_key_match_unit(int m_a, int nblk_a, const int* n_a, const int* form_a, const unsigned long long* gen_a,
+   const long long* ws_a, int m_b, int nblk_b, const int* n_b, const int* form_b, const unsigned long long* gen_b, const long long* ws_b)
+{
+   hs_gram_key a, b;
+   if ( n_a == NULL || form_a == NULL || gen_a == NULL || ws_a == NULL || n_b == NULL || form_b == NULL || gen_b == NULL || ws_b == NULL )
+      return 0;
+   (void) hs_gram_key_make(&a, m_a, nblk_a, n_a, form_a, gen_a, ws_a[0], ws_a[1], (int) ws_a[2]);
+   (void) hs_gram_key_make(&b, m_b, nblk_b, n_b, form_b, gen_b, ws_b[0], ws_b[1], (int) ws_b[2]);
+   return hs_gram_key_match(&a, &b);
 }
 
 extern "C" int hipsdp_solve1_class(int m, int nblk, const int* ns)
