@@ -9,10 +9,10 @@
  *     matrix products only (no divisions on the critical path).
  */
 #include "hs_kernels.h"
+#include "hs_wave.h"
 #include <cstdlib>
 
 #define NB 64
-#define HS_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if ( e_ != hipSuccess ) { hs_record_hip_error(e_, "kernel launch", __FILE__, __LINE__); return HS_ERR_HIP; } } while (0)
 
 #ifdef PD_TIMING
 /* development build only (tests/devtools/potrf_phase_time.py): 100 MHz time stamps of the second step workgroup of the launch
@@ -70,14 +70,6 @@ __device__ __forceinline__ void pd_wave_sync()
    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
    __builtin_amdgcn_wave_barrier();
    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-/* the value lane src holds, as a wavefront-uniform (scalar) operand */
-__device__ __forceinline__ double pd_lane(double v, int src)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-   return __hiloint2double(hi, lo);
 }
 
 struct __attribute__((aligned(16))) dpair { double x, y; };
@@ -141,7 +133,7 @@ __device__ __forceinline__ bool pd_panel(double (&r)[16], const double (&thr)[16
    bool special = false;
    fbits = 0u;
    double cprev[16], tprev = 0.0;
-   double d = pd_lane(r[0], c0);
+   double d = hs_lane(r[0], c0);
 #pragma unroll
    for (int k = 0; k < 16; ++k)
    {
@@ -151,11 +143,11 @@ __device__ __forceinline__ bool pd_panel(double (&r)[16], const double (&thr)[16
       double sa = 0.0, sb = 0.0, sa2 = 0.0;
       if ( k + 1 < 16 )
       {
-         sa = pd_lane(a, gk + 1);
-         sb = pd_lane(r[k + 1], gk + 1);
+         sa = hs_lane(a, gk + 1);
+         sb = hs_lane(r[k + 1], gk + 1);
       }
       if ( k + 2 < 16 )
-         sa2 = pd_lane(a, gk + 2);
+         sa2 = hs_lane(a, gk + 2);
       double rc0 = __builtin_amdgcn_rcp(d);
       double y0 = __builtin_amdgcn_rsq(d);
       double cj[16];

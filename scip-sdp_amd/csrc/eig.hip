@@ -11,9 +11,8 @@
  *      with RANGE = 'I', 'V', 'A'); ordering and eigenvectors-as-rows follow lapack_interface.c:507-603.
  */
 #include "hs_kernels.h"
+#include "hs_wave.h"
 #include <math.h>
-
-#define HS_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if ( e_ != hipSuccess ) { hs_record_hip_error(e_, "kernel launch", __FILE__, __LINE__); return HS_ERR_HIP; } } while (0)
 
 __global__ void k_lmin_tiny(int n, const double* __restrict__ A0, const double* __restrict__ A1, double* __restrict__ res0,
    double* __restrict__ res1, const double* __restrict__ L0, const double* __restrict__ L1);
@@ -23,18 +22,10 @@ __global__ void k_lmin_tiny_multi(hs_step_jobs P);
 /* Lanczos                                                                                                            */
 /* ---------------------------------------------------------------------------------------------------------------- */
 
-__device__ __forceinline__ double wsum(double v)
-{
-#pragma unroll
-   for (int off = 32; off > 0; off >>= 1)
-      v += __shfl_down(v, off, 64);
-   return v;
-}
-
 /* block-wide sum over 1024 threads, result broadcast to all */
 __device__ __forceinline__ double bsum1024(double v, double* sh)
 {
-   v = wsum(v);
+   v = hs_wave_sum_down(v);
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
    __syncthreads();
    if ( lane == 0 )
@@ -90,7 +81,7 @@ __global__ void __launch_bounds__(1024) k_lanczos_step(int n, int j, double* __r
          double s = 0.0;
          for (int e = lane; e < n; e += 64)
             s += q[e] * vbuf[e];
-         s = wsum(s);
+         s = hs_wave_sum_down(s);
          if ( lane == 0 )
             coef[i] = s;
       }
@@ -134,15 +125,6 @@ __global__ void __launch_bounds__(1024) k_lanczos_step(int n, int j, double* __r
 /* Smallest eigenvalue of the k x k tridiagonal (alpha, beta) by 64-way multisection on the Sturm count, its eigenvector
  * by inverse iteration; res = {theta, |beta_{k-1} s_{k-1}|, k}.  One wavefront. */
 struct tridiag_smem { double d[260], e[260], sv[260], wk[4][260]; };
-
-/* reciprocal by v_rcp_f64 and one Newton step (full precision for finite, normal t): a third of the latency of a division,
- * which is what the sequential recurrences below are made of */
-__device__ __forceinline__ double rcp_newton(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   return r;
-}
 
 /* executed by ONE wavefront (all 64 lanes); other wavefronts of the workgroup must not call it */
 /* (ovr_idx, ovr_alpha, ovr_beta): entry ovr_idx of alpha / beta is taken from the arguments instead of memory (the
@@ -190,7 +172,7 @@ __device__ void tridiag_min_wave(int kmax, const double* __restrict__ alpha, con
       if ( t < 0.0 ) ++cnt;
       for (int i = 1; i < k; ++i)
       {
-         t = d[i] - x - wk[3][i - 1] * rcp_newton(t);
+         t = d[i] - x - wk[3][i - 1] * hs_rcp1(t);
          if ( fabs(t) < pivmin ) t = -pivmin;
          if ( !(fabs(t) < 1e290) ) t = (t < 0.0) ? -1e290 : 1e290;
          if ( t < 0.0 ) ++cnt;
@@ -229,7 +211,7 @@ __device__ void tridiag_min_wave(int kmax, const double* __restrict__ alpha, con
             if ( fabs(dd) >= fabs(dl) )
             {
                if ( fabs(dd) < tiny ) dd = tiny;
-               const double rinv = rcp_newton(dd);
+               const double rinv = hs_rcp1(dd);
                const double mlt = dl * rinv;
                wk[0][i] = rinv; wk[1][i] = du; wk[2][i] = 0.0; wk[3][i] = mlt; d[i] = 0.0;
                dd = dn - mlt * du;
@@ -237,7 +219,7 @@ __device__ void tridiag_min_wave(int kmax, const double* __restrict__ alpha, con
             }
             else
             {
-               const double rinv = rcp_newton(dl);
+               const double rinv = hs_rcp1(dl);
                const double mlt = dd * rinv;
                wk[0][i] = rinv; wk[1][i] = dn; wk[2][i] = un; wk[3][i] = mlt; d[i] = 1.0;
                dd = du - mlt * dn;
@@ -245,7 +227,7 @@ __device__ void tridiag_min_wave(int kmax, const double* __restrict__ alpha, con
             }
          }
          if ( fabs(dd) < tiny ) dd = tiny;
-         wk[0][k - 1] = rcp_newton(dd); wk[1][k - 1] = 0.0; wk[2][k - 1] = 0.0;
+         wk[0][k - 1] = hs_rcp1(dd); wk[1][k - 1] = 0.0; wk[2][k - 1] = 0.0;
          const double s0 = 1.0 / sqrt((double) k);
          for (int i = 0; i < k; ++i)
             sv[i] = s0;
@@ -375,7 +357,7 @@ __global__ void __launch_bounds__(1024) k_lanczos_fused(int n, int j, int k, lan
             double sacc = 0.0;
             for (int e = lane; e < n; e += 64)
                sacc += q[e] * vs[e];
-            sacc = wsum(sacc);
+            sacc = hs_wave_sum_down(sacc);
             if ( lane == 0 )
                coef[i] = sacc;
          }
@@ -435,7 +417,7 @@ __global__ void __launch_bounds__(1024) k_lanczos_fused(int n, int j, int k, lan
          double sacc = 0.0;
          for (int e = lane; e < n; e += 64)
             sacc += wr[e] * vs[e];
-         sacc = wsum(sacc);
+         sacc = hs_wave_sum_down(sacc);
          if ( lane == 0 )
             vout[r] = sacc;
       }
@@ -579,7 +561,7 @@ __global__ void __launch_bounds__(1024) k_lanczos_persist(int n, int k, lanczos_
                double sacc = 0.0;
                for (int e = lane; e < n; e += 64)
                   sacc += q[e] * vs[e];
-               sacc = wsum(sacc);
+               sacc = hs_wave_sum_down(sacc);
                if ( lane == 0 )
                   coef[i] = sacc;
             }
@@ -630,7 +612,7 @@ __global__ void __launch_bounds__(1024) k_lanczos_persist(int n, int k, lanczos_
             double sacc = 0.0;
             for (int e = lane; e < n; e += 64)
                sacc += wr[e] * vs[e];
-            sacc = wsum(sacc);
+            sacc = hs_wave_sum_down(sacc);
             if ( lane == 0 )
                __hip_atomic_store(&vout[r], sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
          }
@@ -697,6 +679,8 @@ static int hs_lanczos_lmin_unfused(hipStream_t s, int n, const double* W, int ma
  * so the dependent chains are n / 4 long.  Same algorithm and start vector as k_lanczos_fused; replaces 4 GEMM launches +
  * k + 1 launches per pair of estimates. */
 #define LS_MAXK 32
+/* sum over a quad of lanes, valid in every lane: hs_xsum<4> written out - as the unrolled loop the compiler orders the instructions
+ * of d_lanczos_small differently */
 __device__ __forceinline__ double quad_sum(double x)
 {
    x += __shfl_xor(x, 1, 64);
@@ -734,7 +718,7 @@ __device__ __forceinline__ void d_lanczos_small(int n, int k, const double* __re
       v[tid] = q0;
       sacc = q0 * q0;
    }
-   sacc = wsum(sacc);
+   sacc = hs_wave_sum_down(sacc);
    if ( lane == 0 ) shr[wave] = sacc;
    __syncthreads();
    {
@@ -831,7 +815,7 @@ __device__ __forceinline__ void d_lanczos_small(int n, int k, const double* __re
             }
             if ( pass == 1 )
             {
-               const double sq = wsum(vn * vn);
+               const double sq = hs_wave_sum_down(vn * vn);
                if ( lane == 0 ) shr[wave] = sq;
             }
          }
@@ -1191,18 +1175,6 @@ __global__ void __launch_bounds__(256) k_jacobi_small(int n, const double* __res
       *info = sweeps;
 }
 
-/* rsqrt with two Newton steps (v_rsq_f64 is a low-precision seed) */
-__device__ __forceinline__ double rsqrt_nr(double x)
-{
-   double y = __builtin_amdgcn_rsq(x);
-   double h = 0.5 * y, g = x * y;
-   double r = fma(-h, g, 0.5);
-   g = fma(g, r, g); h = fma(h, r, h);
-   r = fma(-h, g, 0.5);
-   h = fma(h, r, h);
-   return 2.0 * h;
-}
-
 #ifdef EIG_TIMING
 __device__ long long lm_tbuf[8];
 #define LM_T(i) do { if ( threadIdx.x == 0 && blockIdx.x == 0 ) lm_tbuf[i] = wall_clock64(); } while (0)
@@ -1213,49 +1185,6 @@ extern "C" int hipsdp_debug_lm_timing(long long* out)
 #else
 #define LM_T(i) do { } while (0)
 #endif
-
-/* lane exchange inside a row of 16 lanes on the data-parallel-primitive path (no LDS crossbar round trip as with __shfl) */
-template<int CTRL>
-__device__ __forceinline__ double lm_dpp(double v)
-{
-   int lo = __double2loint(v), hi = __double2hiint(v);
-   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lm_lane(double v, int l)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-   return __hiloint2double(hi, lo);
-}
-/* sums inside the rows of 16 lanes (every lane of a row gets its row's sum) */
-__device__ __forceinline__ double lm_rowsum(double v)
-{
-   v += lm_dpp<0xB1>(v);              /* quad_perm [1, 0, 3, 2] */
-   v += lm_dpp<0x4E>(v);              /* quad_perm [2, 3, 0, 1] */
-   v += lm_dpp<0x141>(v);             /* row_half_mirror */
-   v += lm_dpp<0x140>(v);             /* row_mirror */
-   return v;
-}
-__device__ __forceinline__ double lm_wsum(double v)
-{
-   v = lm_rowsum(v);
-   return ((lm_lane(v, 0) + lm_lane(v, 16)) + lm_lane(v, 32)) + lm_lane(v, 48);
-}
-/* reciprocal to full precision: v_rcp_f64 and two Newton steps */
-__device__ __forceinline__ double lm_rcp(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   r = fma(fma(-t, r, 1.0), r, r);
-   return r;
-}
-__device__ __forceinline__ double lm_quad(double x)
-{
-   x += lm_dpp<0xB1>(x);
-   x += lm_dpp<0x4E>(x);
-   return x;
-}
 
 /* smallest eigenvalue of the symmetric n x n matrix in a[][] (n <= 16; destroyed), one wavefront of 64 lanes: Householder
  * tridiagonalisation in LDS (the DSYTD2 recurrence, lane = (row, quarter of the columns)), then Sturm-count multisection on the
@@ -1269,15 +1198,15 @@ __device__ double lmin_sym16(double (*a)[17], int n, double* vv, double* ww, dou
    {
       const int len = n - k - 1;                       /* length of x = a[k + 1 .., k] */
       const double xi = (lane < len) ? a[k + 1 + lane][k] : 0.0;
-      const double x0 = lm_lane(xi, 0);
-      const double s2 = lm_lane(lm_rowsum((lane >= 1) ? xi * xi : 0.0), 0);      /* x sits in the first row of lanes */
+      const double x0 = hs_lane(xi, 0);
+      const double s2 = hs_lane(hs_row_sum_dpp((lane >= 1) ? xi * xi : 0.0), 0);      /* x sits in the first row of lanes */
       double beta = x0, scale = 0.0, t = 0.0;
       if ( s2 > 0.0 )
       {
          const double h2 = x0 * x0 + s2;
-         beta = -copysign(h2 * rsqrt_nr(h2), x0);
-         t = (beta - x0) * lm_rcp(beta);
-         scale = lm_rcp(x0 - beta);
+         beta = -copysign(h2 * hs_rsqrt2(h2), x0);
+         t = (beta - x0) * hs_rcp2(beta);
+         scale = hs_rcp2(x0 - beta);
       }
       if ( lane < len )
          vv[lane] = (lane == 0) ? 1.0 : xi * scale;
@@ -1294,9 +1223,9 @@ __device__ double lmin_sym16(double (*a)[17], int n, double* vv, double* ww, dou
          if ( r < len )
             for (int c = q; c < len; c += 4)
                acc += a[k + 1 + r][k + 1 + c] * vv[c];
-         acc = lm_quad(acc);
+         acc = hs_quad_sum_dpp(acc);
          const double pr = t * acc;
-         const double pv = lm_wsum((q == 0 && r < len) ? pr * vv[r] : 0.0);
+         const double pv = hs_wave_sum_dpp((q == 0 && r < len) ? pr * vv[r] : 0.0);
          const double wr = (r < len) ? pr - 0.5 * t * pv * vv[r] : 0.0;
          if ( q == 0 && r < len )
             ww[r] = wr;
@@ -1330,10 +1259,10 @@ __device__ double lmin_sym16(double (*a)[17], int n, double* vv, double* ww, dou
       for (int i = 0; i < 16; ++i)
          mine = (lane == i) ? er[i] : mine;
       (void) ev;
-      const double sq = (mine > 0.0) ? mine * rsqrt_nr(mine) : 0.0;
+      const double sq = (mine > 0.0) ? mine * hs_rsqrt2(mine) : 0.0;
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-         sr[i] = lm_lane(sq, i);
+         sr[i] = hs_lane(sq, i);
    }
    double lo = 1e300, hi = -1e300;
 #pragma unroll
@@ -1364,7 +1293,7 @@ __device__ double lmin_sym16(double (*a)[17], int n, double* vv, double* ww, dou
       {
          if ( i < n )
          {
-            t = dr[i] - x - er[i - 1] * rcp_newton(t);
+            t = dr[i] - x - er[i - 1] * hs_rcp1(t);
             if ( fabs(t) < pivmin ) t = -pivmin;
             if ( !(fabs(t) < 1e290) ) t = (t < 0.0) ? -1e290 : 1e290;
             if ( t < 0.0 ) ++cnt;
@@ -1485,27 +1414,6 @@ __global__ void __launch_bounds__(64) k_lmin_tiny_multi(hs_step_jobs P)
 #define BJ_T 1024           /* threads of the subproblem workgroup */
 #endif
 
-/* reciprocal square root: v_rsq_f64 seed + two coupled Newton steps (no division, no sqrt expansion) */
-__device__ __forceinline__ double bj_rsqrt(double x)
-{
-   double y = __builtin_amdgcn_rsq(x);
-   double h = 0.5 * y, g = x * y;
-   double r = fma(-h, g, 0.5);
-   g = fma(g, r, g); h = fma(h, r, h);
-   r = fma(-h, g, 0.5);
-   h = fma(h, r, h);
-   return 2.0 * h;
-}
-
-/* reciprocal: v_rcp_f64 seed + two Newton steps */
-__device__ __forceinline__ double bj_rcp(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   r = fma(fma(-t, r, 1.0), r, r);
-   return r;
-}
-
 __global__ void k_bjac_pad(int n, int N, const double* __restrict__ A, double* __restrict__ Ap, double* __restrict__ Vtp)
 {
    for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < (long long) N * N; e += (long long) gridDim.x * blockDim.x)
@@ -1591,12 +1499,12 @@ __global__ void __launch_bounds__(BJ_T) k_bjac_sub(int N, int nbp, int r, const 
 #ifdef BJ_DIV
                const double sc = 1.0 / fmax(fabs(d), fabs(b));
 #else
-               const double sc = bj_rcp(fmax(fabs(d), fabs(b)));      /* (only scales d and b against overflow: no division expansion) */
+               const double sc = hs_rcp2(fmax(fabs(d), fabs(b)));      /* (only scales d and b against overflow: no division expansion) */
 #endif
                d *= sc; b *= sc;
-               const double ir = bj_rsqrt(d * d + b * b);
+               const double ir = hs_rsqrt2(d * d + b * b);
                const double c2 = 0.5 + 0.5 * fabs(d) * ir;
-               const double ic = bj_rsqrt(c2);
+               const double ic = hs_rsqrt2(c2);
                c = c2 * ic;
                s = (d >= 0.0 ? 0.5 : -0.5) * b * ir * ic;
             }

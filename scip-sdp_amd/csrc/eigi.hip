@@ -19,83 +19,12 @@
 #include <cstring>
 #include <cmath>
 #include "hs_sturm.h"
+#include "hs_wave.h"
 
 #define EI_N  64
 #define EI_LD 65
 
 namespace {
-
-/* lane exchange inside a row of 16 lanes on the data-parallel-primitive path (no LDS crossbar round trip as with ds_bpermute):
- * CTRL = quad_perm / row_half_mirror / row_mirror pattern */
-template<int CTRL>
-__device__ __forceinline__ double ei_dpp(double v)
-{
-   int lo = __double2loint(v), hi = __double2hiint(v);
-   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-   return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double ei_lane(double v, int l)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-   return __hiloint2double(hi, lo);
-}
-
-/* sum over the 64 lanes, result in every lane: four butterfly steps inside the rows of 16 (lane ^ 1, lane ^ 2, mirror of 8,
- * mirror of 16), then the four row sums are read as scalars and added in a fixed order */
-__device__ __forceinline__ double ei_wsum(double v)
-{
-   v += ei_dpp<0xB1>(v);              /* quad_perm [1, 0, 3, 2] */
-   v += ei_dpp<0x4E>(v);              /* quad_perm [2, 3, 0, 1] */
-   v += ei_dpp<0x141>(v);             /* row_half_mirror */
-   v += ei_dpp<0x140>(v);             /* row_mirror */
-   return ((ei_lane(v, 0) + ei_lane(v, 16)) + ei_lane(v, 32)) + ei_lane(v, 48);
-}
-
-/* sum over the 16 lanes of a row, result in every lane of the row */
-__device__ __forceinline__ double ei_sum16(double v)
-{
-   v += ei_dpp<0xB1>(v);
-   v += ei_dpp<0x4E>(v);
-   v += ei_dpp<0x141>(v);
-   v += ei_dpp<0x140>(v);
-   return v;
-}
-
-__device__ __forceinline__ double ei_quad(double x)
-{
-   x += ei_dpp<0xB1>(x);
-   x += ei_dpp<0x4E>(x);
-   return x;
-}
-
-/* reciprocal and reciprocal square root to full precision (v_rcp_f64 / v_rsq_f64 and two Newton steps): the scalars of a
- * reflector without the division and square-root expansions */
-__device__ __forceinline__ double ei_rcp2(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   r = fma(fma(-t, r, 1.0), r, r);
-   return r;
-}
-__device__ __forceinline__ double ei_rsqrt(double x)
-{
-   double y = __builtin_amdgcn_rsq(x);
-   double h = 0.5 * y, g = x * y;
-   double r = fma(-h, g, 0.5);
-   g = fma(g, r, g); h = fma(h, r, h);
-   r = fma(-h, g, 0.5);
-   h = fma(h, r, h);
-   return 2.0 * h;
-}
-
-__device__ __forceinline__ double ei_rcp(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   return r;
-}
 
 /* in: n x n symmetric, in mapped host memory, the triangle at memory positions [j n + i], i >= j, is read; out[0] = eigenvalue, out[1 .. n] = eigenvector,
  * then the sequence number is stored to *flag (system scope) */
@@ -167,16 +96,16 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
       double t;
       {
          const double xi = (lane < len) ? xc[k + 1 + lane] : 0.0;
-         const double x0 = ei_lane(xi, 0);
-         const double s2 = ei_wsum(lane >= 1 ? xi * xi : 0.0);
+         const double x0 = hs_lane(xi, 0);
+         const double s2 = hs_wave_sum_dpp(lane >= 1 ? xi * xi : 0.0);
          double beta = x0, scale = 0.0;
          t = 0.0;
          if ( s2 > 0.0 )
          {
             const double h2 = x0 * x0 + s2;
-            beta = -copysign(h2 * ei_rsqrt(h2), x0);
-            t = (beta - x0) * ei_rcp2(beta);
-            scale = ei_rcp2(x0 - beta);
+            beta = -copysign(h2 * hs_rsqrt2(h2), x0);
+            t = (beta - x0) * hs_rcp2(beta);
+            scale = hs_rcp2(x0 - beta);
          }
          if ( lane < len )
             vv[k + 1 + lane] = (lane == 0) ? 1.0 : xi * scale;
@@ -202,13 +131,13 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
 #pragma unroll
          for (int j = 0; j < 16; ++j)
             acc += ar[j] * vq[j];
-         acc = ei_quad(acc);
+         acc = hs_quad_sum_dpp(acc);
          if ( q == 0 )
             pp[r] = (r > k) ? t * acc : 0.0;
          __syncthreads();
          {
             const double pl = lane < len ? pp[k + 1 + lane] : 0.0, vl = lane < len ? vv[k + 1 + lane] : 0.0;
-            const double pv = ei_wsum(pl * vl);
+            const double pv = hs_wave_sum_dpp(pl * vl);
             const double al = -0.5 * t * pv;
             if ( lane < len )
                ww[k + 1 + lane] = pl + al * vl;
@@ -281,7 +210,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                if ( t < 0.0 ) ++cnt;
                for (int i = 1; i < n; ++i)
                {
-                  t = d[i] - x - e2[i - 1] * ei_rcp(t);
+                  t = d[i] - x - e2[i - 1] * hs_rcp1(t);
                   if ( fabs(t) < pivmin ) t = -pivmin;
                   if ( !(fabs(t) < 1e290) ) t = (t < 0.0) ? -1e290 : 1e290;
                   if ( t < 0.0 ) ++cnt;
@@ -290,8 +219,8 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
             /* number of the four shifts with fewer than k + 1 eigenvalues below them = index of the subinterval that holds
              * eigenvalue k (the counts are monotone in the shift) */
             int below = (cnt < k + 1) ? 1 : 0;
-            below += __builtin_amdgcn_update_dpp(0, below, 0xB1, 0xf, 0xf, true);
-            below += __builtin_amdgcn_update_dpp(0, below, 0x4E, 0xf, 0xf, true);
+            below += hs_dpp<0xB1>(below);
+            below += hs_dpp<0x4E>(below);
             const double nlo = lo + w * (double) below;
             const double nhi = (below < 4) ? lo + w * (double) (below + 1) : hi;
             lo = nlo; hi = nhi;
@@ -347,7 +276,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                   if ( fabs(dd) >= fabs(dl) || fabs(dl) < tiny )
                   {
                      if ( fabs(dd) < tiny ) dd = tiny;
-                     const double rinv = ei_rcp2(dd);
+                     const double rinv = hs_rcp2(dd);
                      const double mlt = dl * rinv;
                      f0[i * EI_N + k] = rinv; f1[i * EI_N + k] = du;
                      Z[i * EI_N + k] = cur;
@@ -357,7 +286,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                   }
                   else
                   {
-                     const double rinv = ei_rcp2(dl);
+                     const double rinv = hs_rcp2(dl);
                      const double mlt = dd * rinv;
                      f0[i * EI_N + k] = rinv; f1[i * EI_N + k] = dn;
                      swapped |= 1ULL << i;
@@ -368,7 +297,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                   }
                }
                if ( fabs(dd) < tiny ) dd = tiny;
-               double x1 = cur * ei_rcp2(dd), x2 = 0.0;
+               double x1 = cur * hs_rcp2(dd), x2 = 0.0;
                double nrm = x1 * x1;
                Z[(n - 1) * EI_N + k] = x1;
                for (int i = n - 2; i >= 0; --i)
@@ -387,7 +316,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                      x1 *= sc1; x2 *= sc1; nrm *= sc1 * sc1;
                   }
                }
-               double rn = ei_rsqrt(fmax(nrm, 1e-300));
+               double rn = hs_rsqrt2(fmax(nrm, 1e-300));
                if ( !(nrm > 0.0) || !(nrm < 1e300) )
                {
                   for (int i = 0; i < n; ++i)
@@ -419,10 +348,10 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                         for (int p = k0; p < k; ++p)
                         {
                            const double u = (lane < n) ? Z[lane * EI_N + p] : 0.0;
-                           v -= ei_wsum(u * v) * u;
+                           v -= hs_wave_sum_dpp(u * v) * u;
                         }
-                     const double nr = ei_wsum(v * v);
-                     v *= ei_rsqrt(fmax(nr, 1e-300));
+                     const double nr = hs_wave_sum_dpp(v * v);
+                     v *= hs_rsqrt2(fmax(nr, 1e-300));
                      if ( lane < n )
                         Z[lane * EI_N + k] = v;
                      __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -445,12 +374,12 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
                continue;
             const bool in = lane > kk && lane < n;
             const double vk = in ? ((lane == kk + 1) ? 1.0 : a[lane][kk]) : 0.0;
-            const double dot = ei_wsum(vk * zi);
+            const double dot = hs_wave_sum_dpp(vk * zi);
             zi -= t * dot * vk;
          }
-         const double nrm = ei_wsum(zi * zi);
+         const double nrm = hs_wave_sum_dpp(zi * zi);
          if ( lane < n )
-            out[EI_N + (long long) k * n + lane] = nrm > 0.0 ? zi * ei_rsqrt(nrm) : zi;
+            out[EI_N + (long long) k * n + lane] = nrm > 0.0 ? zi * hs_rsqrt2(nrm) : zi;
       }
       __threadfence_system();
       __syncthreads();
@@ -609,10 +538,10 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
             continue;
          const bool in = lane > k && lane < n;
          const double vk = in ? ((lane == k + 1) ? 1.0 : a[lane][k]) : 0.0;
-         const double dot = ei_wsum(vk * zi);
+         const double dot = hs_wave_sum_dpp(vk * zi);
          zi -= t * dot * vk;
       }
-      const double nrm = sqrt(ei_wsum(zi * zi));
+      const double nrm = sqrt(hs_wave_sum_dpp(zi * zi));
       if ( lane < n )
          out[1 + lane] = nrm > 0.0 ? zi / nrm : zi;
    }
@@ -719,16 +648,16 @@ __device__ __forceinline__ void em_tridiag_t(int n, const double* __restrict__ i
       {
          const double xa = (lane < len) ? em_a[(k + 1 + lane) * ld + k] : 0.0;
          const double xb = (lane + 64 < len) ? em_a[(k + 65 + lane) * ld + k] : 0.0;
-         const double x0 = ei_lane(xa, 0);
-         const double s2 = ei_wsum((lane >= 1 ? xa * xa : 0.0) + xb * xb);
+         const double x0 = hs_lane(xa, 0);
+         const double s2 = hs_wave_sum_dpp((lane >= 1 ? xa * xa : 0.0) + xb * xb);
          double beta = x0, scale = 0.0;
          t = 0.0;
          if ( s2 > 0.0 )
          {
             const double h2 = x0 * x0 + s2;
-            beta = -copysign(h2 * ei_rsqrt(h2), x0);
-            t = (beta - x0) * ei_rcp2(beta);
-            scale = ei_rcp2(x0 - beta);
+            beta = -copysign(h2 * hs_rsqrt2(h2), x0);
+            t = (beta - x0) * hs_rcp2(beta);
+            scale = hs_rcp2(x0 - beta);
          }
          if ( lane < len )
             vv[k + 1 + lane] = (lane == 0) ? 1.0 : xa * scale;
@@ -768,9 +697,9 @@ __device__ __forceinline__ void em_tridiag_t(int n, const double* __restrict__ i
                acc = (a0 + a1) + (a2 + a3);
             }
             if ( EM_TPR == 4 )
-               acc = ei_quad(acc);                      /* the parts of a row are neighbours */
+               acc = hs_quad_sum_dpp(acc);                      /* the parts of a row are neighbours */
             else
-               acc += ei_dpp<0xB1>(acc);
+               acc += hs_dpp<0xB1>(acc);
             if ( part == 0 && row < n )
                pp[row] = t * acc;
          }
@@ -778,7 +707,7 @@ __device__ __forceinline__ void em_tridiag_t(int n, const double* __restrict__ i
          {
             const double pa = (lane < len) ? pp[k + 1 + lane] : 0.0, pb = (lane + 64 < len) ? pp[k + 65 + lane] : 0.0;
             const double va = (lane < len) ? vv[k + 1 + lane] : 0.0, vb = (lane + 64 < len) ? vv[k + 65 + lane] : 0.0;
-            const double pv = ei_wsum(pa * va + pb * vb);
+            const double pv = hs_wave_sum_dpp(pa * va + pb * vb);
             const double al = -0.5 * t * pv;
             if ( lane < len )
                ww[k + 1 + lane] = pa + al * va;
@@ -965,11 +894,11 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
          const int ia = lane, ib = lane + 64;
          const double va = (ia > k && ia < n) ? ((ia == k + 1) ? 1.0 : em_a[ia * ld + k]) : 0.0;
          const double vb = (ib > k && ib < n) ? ((ib == k + 1) ? 1.0 : em_a[ib * ld + k]) : 0.0;
-         const double dot = ei_wsum(va * za + vb * zb);
+         const double dot = hs_wave_sum_dpp(va * za + vb * zb);
          za -= t * dot * va;
          zb -= t * dot * vb;
       }
-      const double nrm = sqrt(ei_wsum(za * za + zb * zb));
+      const double nrm = sqrt(hs_wave_sum_dpp(za * za + zb * zb));
       if ( lane < n )
          out[1 + lane] = nrm > 0.0 ? za / nrm : za;
       if ( lane + 64 < n )
@@ -1051,7 +980,7 @@ __device__ __forceinline__ void em_clusters(int n, int ld, int iter, double orto
                         u[j] = (i < n && p < k) ? Z[i * ld + (p < k ? p : k0)] : 0.0;
                         dt = fma(u[j], v[j], dt);
                      }
-                     dt = ei_sum16(dt);
+                     dt = hs_row_sum_dpp(dt);
 #pragma unroll
                      for (int j = 0; j < NJ; ++j)
                         corr[j] = fma(dt, u[j], corr[j]);
@@ -1080,8 +1009,8 @@ __device__ __forceinline__ void em_clusters(int n, int ld, int iter, double orto
 #pragma unroll
                for (int j = 0; j < NJ; ++j)
                   nr = fma(v[j], v[j], nr);
-               nr = ei_sum16(nr);
-               const double rs = ei_rsqrt(fmax(nr, 1e-300));
+               nr = hs_row_sum_dpp(nr);
+               const double rs = hs_rsqrt2(fmax(nr, 1e-300));
                if ( wave == 0 && row == 0 )
                {
 #pragma unroll
@@ -1124,7 +1053,7 @@ __device__ __forceinline__ void em_clusters(int n, int ld, int iter, double orto
                         u[j] = (i < n && p < k) ? Z[i * ld + (p < k ? p : k0)] : 0.0;
                         dt = fma(u[j], v[j], dt);
                      }
-                     dt = ei_sum16(dt);
+                     dt = hs_row_sum_dpp(dt);
 #pragma unroll
                      for (int j = 0; j < NJ; ++j)
                         corr[j] = fma(dt, u[j], corr[j]);
@@ -1143,8 +1072,8 @@ __device__ __forceinline__ void em_clusters(int n, int ld, int iter, double orto
 #pragma unroll
                for (int j = 0; j < NJ; ++j)
                   nr = fma(v[j], v[j], nr);
-               nr = ei_sum16(nr);
-               const double rs = ei_rsqrt(fmax(nr, 1e-300));
+               nr = hs_row_sum_dpp(nr);
+               const double rs = hs_rsqrt2(fmax(nr, 1e-300));
                if ( row == 0 )
                {
 #pragma unroll
@@ -1213,7 +1142,7 @@ __device__ __forceinline__ void em_backtransform(int n, int ld, const double* Z,
                   vr[j] = (i > kk && i < n) ? ((i == kk + 1) ? 1.0 : rv) : 0.0;
                   dot = fma(vr[j], z[j], dot);
                }
-               dot = t * ei_sum16(dot);
+               dot = t * hs_row_sum_dpp(dot);
 #pragma unroll
                for (int j = 0; j < NJ; ++j)
                   z[j] = fma(-dot, vr[j], z[j]);
@@ -1223,8 +1152,8 @@ __device__ __forceinline__ void em_backtransform(int n, int ld, const double* Z,
 #pragma unroll
          for (int j = 0; j < NJ; ++j)
             nrm = fma(z[j], z[j], nrm);
-         nrm = ei_sum16(nrm);
-         const double rs = nrm > 0.0 ? ei_rsqrt(nrm) : 1.0;
+         nrm = hs_row_sum_dpp(nrm);
+         const double rs = nrm > 0.0 ? hs_rsqrt2(nrm) : 1.0;
 #pragma unroll
          for (int j = 0; j < NJ; ++j)
          {
@@ -1313,12 +1242,12 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
          const int cnt = (k < n) ? ei_sturm_count(ds, es, nb, x) : 0;
          /* number of the S shifts with fewer than k + 1 eigenvalues below them = index of the subinterval that holds eigenvalue k */
          int below = (cnt < k + 1) ? 1 : 0;
-         below += __builtin_amdgcn_update_dpp(0, below, 0xB1, 0xf, 0xf, true);
-         below += __builtin_amdgcn_update_dpp(0, below, 0x4E, 0xf, 0xf, true);
+         below += hs_dpp<0xB1>(below);
+         below += hs_dpp<0x4E>(below);
          if ( lgS >= 3 )
-            below += __builtin_amdgcn_update_dpp(0, below, 0x141, 0xf, 0xf, true);
+            below += hs_dpp<0x141>(below);
          if ( lgS >= 4 )
-            below += __builtin_amdgcn_update_dpp(0, below, 0x140, 0xf, 0xf, true);
+            below += hs_dpp<0x140>(below);
          const double nlo = lo + w * (double) below;
          const double nhi = (below < S) ? lo + w * (double) (below + 1) : hi;
          lo = nlo; hi = nhi;
@@ -1368,7 +1297,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
                if ( fabs(dd) >= fabs(dl) || fabs(dl) < tiny )
                {
                   if ( fabs(dd) < tiny ) dd = tiny;
-                  const double rinv = ei_rcp2(dd);
+                  const double rinv = hs_rcp2(dd);
                   const double mlt = dl * rinv;
                   G0[i * gs + k] = rinv; G1[i * gs + k] = du;
                   Z[i * ld + k] = cur;
@@ -1378,7 +1307,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
                }
                else
                {
-                  const double rinv = ei_rcp2(dl);
+                  const double rinv = hs_rcp2(dl);
                   const double mlt = dd * rinv;
                   G0[i * gs + k] = rinv; G1[i * gs + k] = dn;
                   if ( i < 64 ) swlo |= 1ULL << i; else swhi |= 1ULL << (i - 64);
@@ -1389,7 +1318,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
                }
             }
             if ( fabs(dd) < tiny ) dd = tiny;
-            double x1 = cur * ei_rcp2(dd), x2 = 0.0;
+            double x1 = cur * hs_rcp2(dd), x2 = 0.0;
             double nrm = x1 * x1;
             Z[(n - 1) * ld + k] = x1;
             /* backward sweep, the factors of eight rows on their way while the recurrence runs */
@@ -1425,7 +1354,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
                   }
                }
             }
-            double rn = ei_rsqrt(fmax(nrm, 1e-300));
+            double rn = hs_rsqrt2(fmax(nrm, 1e-300));
             if ( !(nrm > 0.0) || !(nrm < 1e300) )
             {
                for (int i = 0; i < n; ++i)

@@ -34,6 +34,16 @@
          return hs_r_;                                                                     \
    } while (0)
 
+/* behind a kernel launch: a launch that failed is recorded and ends the calling function */
+#define HS_LAUNCH_CHECK()                                                                  \
+   do {                                                                                    \
+      hipError_t e_ = hipGetLastError();                                                   \
+      if ( e_ != hipSuccess ) {                                                            \
+         hs_record_hip_error(e_, "kernel launch", __FILE__, __LINE__);                     \
+         return HS_ERR_HIP;                                                                \
+      }                                                                                    \
+   } while (0)
+
 void hs_record_hip_error(hipError_t e, const char* what, const char* file, int line);
 const char* hs_last_error(void);
 

@@ -442,18 +442,14 @@ __device__ __forceinline__ void hs_run_node_cmds(const NodeCmd* __restrict__ cmd
 #endif
 
 #ifdef __HIPCC__
+#include "hs_wave.h"
+
 /* ---- one wavefront: x = (L L^T)^-1 r for a single-block factor (m <= 64) in the ORACLE's order (oracle/ipm_ref.py: msolve) - forward
  * substitution, one correction with the factor itself, backward substitution, one correction - where the default multiplies by an
  * explicitly inverted factor (with the same corrections).  An option (HIPSDP_SMALL_SOLVE=subst, kernels.hip:
  * hs_small_solve_by_substitution), built in round 6 to test whether the inverted blocks are why the general path parts from the oracle
  * on singular Schur complements; they are not.
  * sL: LDS image of L, row i at sL + 65 i (entries j <= i valid, the diagonal included); lane = row; r, result: this lane's entry. */
-__device__ __forceinline__ double hs_wl_bcast(double v, int src)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-   return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double hs_wl_fwd(const double* sL, int m, int lane, double di, double x)
 {
    const bool live = lane < m;
@@ -461,7 +457,7 @@ __device__ __forceinline__ double hs_wl_fwd(const double* sL, int m, int lane, d
    double a = live ? x : 0.0;
    for (int k = 0; k < m; ++k)
    {
-      const double y = hs_wl_bcast(a * di, k);
+      const double y = hs_lane(a * di, k);
       const double c = row[k];
       if ( live && lane > k )
          a = fma(-c, y, a);
@@ -475,7 +471,7 @@ __device__ __forceinline__ double hs_wl_bwd(const double* sL, int m, int lane, d
    double a = live ? x : 0.0;
    for (int k = m - 1; k >= 0; --k)
    {
-      const double y = hs_wl_bcast(a * di, k);
+      const double y = hs_lane(a * di, k);
       const double c = sL[k * 65 + col];
       if ( live && lane < k )
          a = fma(-c, y, a);
@@ -490,7 +486,7 @@ __device__ __forceinline__ double hs_wl_mulL(const double* sL, int m, int lane, 
    double acc = 0.0;
    for (int j = 0; j < m; ++j)
    {
-      const double wj = hs_wl_bcast(w, j);
+      const double wj = hs_lane(w, j);
       const double c = row[j];
       if ( live && j <= lane )
          acc = fma(c, wj, acc);
@@ -504,7 +500,7 @@ __device__ __forceinline__ double hs_wl_mulLt(const double* sL, int m, int lane,
    double acc = 0.0;
    for (int j = 0; j < m; ++j)
    {
-      const double vj = hs_wl_bcast(v, j);
+      const double vj = hs_lane(v, j);
       const double c = sL[j * 65 + col];
       if ( live && j >= lane )
          acc = fma(c, vj, acc);
@@ -521,7 +517,7 @@ __device__ __forceinline__ void hs_wl2_fwd(const double* sL, int m, int lane, co
    const double* row1 = sL + (l1 ? r1 : 0) * P;
    for (int k = 0; k < m; ++k)
    {
-      const double y = (k < 64) ? hs_wl_bcast(a[0] * di[0], k) : hs_wl_bcast(a[1] * di[1], k - 64);
+      const double y = (k < 64) ? hs_lane(a[0] * di[0], k) : hs_lane(a[1] * di[1], k - 64);
       const double c0 = row0[k], c1 = row1[k];
       if ( r0 > k ) a[0] = fma(-c0, y, a[0]);
       if ( l1 && r1 > k ) a[1] = fma(-c1, y, a[1]);
@@ -536,7 +532,7 @@ __device__ __forceinline__ void hs_wl2_bwd(const double* sL, int m, int lane, co
    const int c1col = l1 ? r1 : 0;
    for (int k = m - 1; k >= 0; --k)
    {
-      const double y = (k < 64) ? hs_wl_bcast(a[0] * di[0], k) : hs_wl_bcast(a[1] * di[1], k - 64);
+      const double y = (k < 64) ? hs_lane(a[0] * di[0], k) : hs_lane(a[1] * di[1], k - 64);
       const double c0 = sL[k * P + r0], c1 = sL[k * P + c1col];
       if ( r0 < k ) a[0] = fma(-c0, y, a[0]);
       if ( l1 && r1 < k ) a[1] = fma(-c1, y, a[1]);
@@ -552,7 +548,7 @@ __device__ __forceinline__ void hs_wl2_mul(const double* sL, int m, int lane, co
    double s0 = 0.0, s1 = 0.0;
    for (int j = 0; j < m; ++j)
    {
-      const double wj = (j < 64) ? hs_wl_bcast(w[0], j) : hs_wl_bcast(w[1], j - 64);
+      const double wj = (j < 64) ? hs_lane(w[0], j) : hs_lane(w[1], j - 64);
       const double c0 = TRANS ? sL[j * P + r0] : sL[r0 * P + j];
       const double c1 = TRANS ? sL[j * P + q1] : sL[q1 * P + j];
       if ( TRANS ? j >= r0 : j <= r0 ) s0 = fma(c0, wj, s0);

@@ -28,8 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define HS_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if ( e_ != hipSuccess ) { hs_record_hip_error(e_, "kernel launch", __FILE__, __LINE__); return HS_ERR_HIP; } } while (0)
-
 /* ---- device scalar slots -------------------------------------------------------------------------------------- */
 enum
 {

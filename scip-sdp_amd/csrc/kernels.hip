@@ -41,8 +41,6 @@ static inline int hs_launch_ok(void)
    return hipGetLastError() == hipSuccess ? HS_OK : HS_ERR_HIP;
 }
 
-#define HS_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if ( e_ != hipSuccess ) { hs_record_hip_error(e_, "kernel launch", __FILE__, __LINE__); return HS_ERR_HIP; } } while (0)
-
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* element-wise                                                                                                       */
 /* ---------------------------------------------------------------------------------------------------------------- */
@@ -1648,8 +1646,7 @@ __global__ void __launch_bounds__(256) k_lp_rows_small(int q, int m1, const doub
    double t = 0.0;
    for (int i = lane; i < m1; i += 64)
       t += d[i] * v[i];
-   for (int off = 32; off > 0; off >>= 1)
-      t += __shfl_down(t, off, 64);
+   t = hs_wave_sum_down(t);
    if ( lane == 0 )
    {
       if ( mode == 0 )

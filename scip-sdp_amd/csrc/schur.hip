@@ -684,9 +684,7 @@ __global__ void __launch_bounds__(256) k_schur_small(int m1, int nmax, ss_args B
             const int r = e / n, c = e - r * n;
             acc += Ai[e] * su[r * ldm + c];
          }
-#pragma unroll
-         for (int off = 32; off > 0; off >>= 1)
-            acc += __shfl_down(acc, off, 64);
+         acc = hs_wave_sum_down(acc);
          if ( lane == 0 )
             colv[i] += acc;
       }

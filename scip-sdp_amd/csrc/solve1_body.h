@@ -28,6 +28,7 @@
  *     in the scratch region), M_ij = <A_i, U_j> over the nonzeros of A_i.
  */
 #include "hs_kernels.h"
+#include "hs_wave.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -179,20 +180,6 @@ namespace {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-template<int CTRL>
-__device__ __forceinline__ double s1_dpp(double v)
-{
-   int lo = __double2loint(v), hi = __double2hiint(v);
-   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double s1_lane(double v, int l)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-   return __hiloint2double(hi, lo);
-}
-/* e / n for 0 <= e < 2^20, 1 <= n <= 64 without the integer-division expansion: float reciprocal, one correction step */
 /* a value every lane computed identically, moved to scalar registers (the kernel keeps dozens of such loop-carried values; as vector
  * registers they take two each for the whole solve, as scalars they are spilled 64 to a vector register) */
 #ifdef S1_DEBUG
@@ -214,6 +201,7 @@ __device__ __forceinline__ double s1_uni(double v)
 #endif
 }
 
+/* e / n for 0 <= e < 2^20, 1 <= n <= 64 without the integer-division expansion: float reciprocal, one correction step */
 __device__ __forceinline__ int s1_div(int e, int n)
 {
    int r = (int) ((float) e * __builtin_amdgcn_rcpf((float) n));
@@ -222,35 +210,21 @@ __device__ __forceinline__ int s1_div(int e, int n)
    else if ( c < 0 ) --r;
    return r;
 }
-/* sum within the rows of 16 lanes (every lane of a row gets its row's sum) */
-__device__ __forceinline__ double s1_sum16(double v)
-{
-   v += s1_dpp<0xB1>(v);              /* quad_perm [1, 0, 3, 2] */
-   v += s1_dpp<0x4E>(v);              /* quad_perm [2, 3, 0, 1] */
-   v += s1_dpp<0x141>(v);             /* row_half_mirror */
-   v += s1_dpp<0x140>(v);             /* row_mirror */
-   return v;
-}
-__device__ __forceinline__ double s1_wsum(double v)
-{
-   v = s1_sum16(v);
-   return ((s1_lane(v, 0) + s1_lane(v, 16)) + s1_lane(v, 32)) + s1_lane(v, 48);
-}
 __device__ __forceinline__ double s1_wmax(double v)
 {
-   v = fmax(v, s1_dpp<0xB1>(v));
-   v = fmax(v, s1_dpp<0x4E>(v));
-   v = fmax(v, s1_dpp<0x141>(v));
-   v = fmax(v, s1_dpp<0x140>(v));
-   return fmax(fmax(s1_lane(v, 0), s1_lane(v, 16)), fmax(s1_lane(v, 32), s1_lane(v, 48)));
+   v = fmax(v, hs_dpp<0xB1>(v));
+   v = fmax(v, hs_dpp<0x4E>(v));
+   v = fmax(v, hs_dpp<0x141>(v));
+   v = fmax(v, hs_dpp<0x140>(v));
+   return fmax(fmax(hs_lane(v, 0), hs_lane(v, 16)), fmax(hs_lane(v, 32), hs_lane(v, 48)));
 }
 __device__ __forceinline__ double s1_wmin(double v)
 {
-   v = fmin(v, s1_dpp<0xB1>(v));
-   v = fmin(v, s1_dpp<0x4E>(v));
-   v = fmin(v, s1_dpp<0x141>(v));
-   v = fmin(v, s1_dpp<0x140>(v));
-   return fmin(fmin(s1_lane(v, 0), s1_lane(v, 16)), fmin(s1_lane(v, 32), s1_lane(v, 48)));
+   v = fmin(v, hs_dpp<0xB1>(v));
+   v = fmin(v, hs_dpp<0x4E>(v));
+   v = fmin(v, hs_dpp<0x141>(v));
+   v = fmin(v, hs_dpp<0x140>(v));
+   return fmin(fmin(hs_lane(v, 0), hs_lane(v, 16)), fmin(hs_lane(v, 32), hs_lane(v, 48)));
 }
 
 struct S1Blk
@@ -318,7 +292,7 @@ __device__ __forceinline__ int s1_chol(double* L, int n, int p, int lane, bool p
          }
          v = rl[k] - ((s0 + s1) + (s2 + s3));
       }
-      double d = s1_lane(v, k);
+      double d = hs_lane(v, k);
       bool zero = false;
       if ( psd )
       {
@@ -342,8 +316,8 @@ __device__ __forceinline__ int s1_chol(double* L, int n, int p, int lane, bool p
    return 0;
 }
 
-/* reciprocal square root and reciprocal to full precision: v_rsq_f64 / v_rcp_f64 and two Newton steps (a few instructions instead
- * of the division and square-root expansions - the single-wavefront recurrences are bound by their instruction count) */
+/* reciprocal square root to full precision: v_rsq_f64 and two Newton steps in the residual form r += (r / 2) (1 - x r^2) - not the
+ * coupled form of hs_rsqrt2, the two round differently (a few instructions instead of the square-root expansion) */
 __device__ __forceinline__ double s1_rsqrt(double x)
 {
    double r = __builtin_amdgcn_rsq(x);
@@ -351,13 +325,6 @@ __device__ __forceinline__ double s1_rsqrt(double x)
    r = fma(0.5 * r, e, r);
    e = fma(-x * r, r, 1.0);
    r = fma(0.5 * r, e, r);
-   return r;
-}
-__device__ __forceinline__ double s1_rcp(double t)
-{
-   double r = __builtin_amdgcn_rcp(t);
-   r = fma(fma(-t, r, 1.0), r, r);
-   r = fma(fma(-t, r, 1.0), r, r);
    return r;
 }
 
@@ -446,13 +413,13 @@ __device__ __forceinline__ int s1_cholp(double* A, int n, int p, int lane, bool 
          const int k = k0 + u;
          if ( k < n )
          {
-            double d = s1_lane(a[u], k);
+            double d = hs_lane(a[u], k);
             bool zero = false;
             if ( psd )
             {
-               if ( !(d > s1_lane(thr, k)) )
+               if ( !(d > hs_lane(thr, k)) )
                {
-                  const double mkk = s1_lane(dg0, k);
+                  const double mkk = hs_lane(dg0, k);
                   zero = (rule == 1) || (rule == 2 && !(d > 0.0)) || (rule == 3 && !(d > 1.78e-15 * (double) (k + 1) * mkk));
                   d = (mkk > 1e-280) ? regtol * mkk : 1.0;
                   nforced += zero ? 65536 : 1;
@@ -470,7 +437,7 @@ __device__ __forceinline__ int s1_cholp(double* A, int n, int p, int lane, bool 
              * when its pivot comes they were a chain of up to seven dependent ones in front of every pivot) */
 #pragma unroll
             for (int v = u + 1; v < 8; ++v)
-               a[v] = fma(-lu, s1_lane(lu, (k0 + v) & 63), a[v]);
+               a[v] = fma(-lu, hs_lane(lu, (k0 + v) & 63), a[v]);
          }
       }
 #pragma unroll
@@ -519,8 +486,8 @@ __device__ __forceinline__ void s1_llt_solve(const double* L, int m, int p, int 
          for (int u = 0; u < 8; ++u)
          {
             const double t0 = a0 * dinv, t1 = a1 * dinv;
-            const double y0 = s1_lane(t0, k0 + u);
-            const double y1 = TWO ? s1_lane(t1, k0 + u) : 0.0;
+            const double y0 = hs_lane(t0, k0 + u);
+            const double y1 = TWO ? hs_lane(t1, k0 + u) : 0.0;
             a0 = fma(-c[u], y0, a0);
             if ( TWO )
                a1 = fma(-c[u], y1, a1);
@@ -555,8 +522,8 @@ __device__ __forceinline__ void s1_llt_solve(const double* L, int m, int p, int 
          for (int u = 7; u >= 0; --u)
          {
             const double t0 = a0 * dinv, t1 = a1 * dinv;
-            const double y0 = s1_lane(t0, (k0 + u) & 63);
-            const double y1 = TWO ? s1_lane(t1, (k0 + u) & 63) : 0.0;
+            const double y0 = hs_lane(t0, (k0 + u) & 63);
+            const double y1 = TWO ? hs_lane(t1, (k0 + u) & 63) : 0.0;
             a0 = fma(-c[u], y0, a0);
             if ( TWO )
                a1 = fma(-c[u], y1, a1);
@@ -607,11 +574,11 @@ __device__ __forceinline__ void s1_cholp2_cols(s1_ldsd* A, int n, int k0, int la
       if ( k < n )
       {
          const int kl = HI ? k - 64 : k;
-         double d = s1_lane(HI ? b[u] : a[u], kl);
+         double d = hs_lane(HI ? b[u] : a[u], kl);
          bool zero = false;
-         if ( !(d > s1_lane(thr, kl)) )
+         if ( !(d > hs_lane(thr, kl)) )
          {
-            const double mkk = s1_lane(dgx, kl);
+            const double mkk = hs_lane(dgx, kl);
             zero = (rule == 1) || (rule == 2 && !(d > 0.0)) || (rule == 3 && !(d > 1.78e-15 * (double) (k + 1) * mkk));
             d = (mkk > 1e-280) ? regtol * mkk : 1.0;
             nforced += zero ? 65536 : 1;
@@ -625,7 +592,7 @@ __device__ __forceinline__ void s1_cholp2_cols(s1_ldsd* A, int n, int k0, int la
 #pragma unroll
          for (int v = u + 1; v < 8; ++v)
          {
-            const double piv = s1_lane(HI ? lub : lua, HI ? k0 + v - 64 : k0 + v);
+            const double piv = hs_lane(HI ? lub : lua, HI ? k0 + v - 64 : k0 + v);
             if ( !HI )
                a[v] = fma(-lua, piv, a[v]);
             b[v] = fma(-lub, piv, b[v]);
@@ -713,9 +680,9 @@ __device__ __attribute__((noinline)) int s1_cholp2(double* Ag, int n_, int wave_
    }
    if ( wave == 0 )
    {
-      dinv_out[lane] = s1_rcp(diag0);
+      dinv_out[lane] = hs_rcp2(diag0);
       if ( has1 )
-         dinv_out[lane + 64] = s1_rcp(diag1);
+         dinv_out[lane + 64] = hs_rcp2(diag1);
    }
    __syncthreads();
    return nforced;
@@ -734,8 +701,8 @@ __device__ __forceinline__ void s1_llt_steps2(const double* c, const double* ch,
       const int u = DOWN ? uu : 7 - uu;
       const int kl = HI ? k0 + u - 64 : k0 + u;
       const double t0 = HI ? a0h * di1 : a0 * di0, t1 = HI ? a1h * di1 : a1 * di0;
-      const double y0 = s1_lane(t0, kl);
-      const double y1 = TWO ? s1_lane(t1, kl) : 0.0;
+      const double y0 = hs_lane(t0, kl);
+      const double y1 = TWO ? hs_lane(t1, kl) : 0.0;
       a0 = fma(-c[u], y0, a0); a0h = fma(-ch[u], y0, a0h);
       if ( TWO )
       {
@@ -849,7 +816,7 @@ __device__ __forceinline__ void s1_trinv(const double* L, double* Li, int n, int
             }
          }
       }
-      const double rd = s1_rcp(ri[i]);
+      const double rd = hs_rcp2(ri[i]);
       const double val = (lane == i) ? rd : -((s0 + s1) + (s2 + s3)) * rd;
       __builtin_amdgcn_wave_barrier();
       if ( lane <= i )
@@ -983,7 +950,7 @@ __device__ __forceinline__ double s1u_lmin(const double* W, int n, int p, int la
             const double rh = s1_rsqrt(h2);
             const double beta = -copysign(h2 * rh, x0);
             const double t = (x0 - beta) * copysign(rh, x0);
-            const double scale = s1_rcp(x0 - beta);
+            const double scale = hs_rcp2(x0 - beta);
             double v[NP], w[NP];
             v[k + 1] = 1.0;
 #pragma unroll
@@ -1049,7 +1016,7 @@ __device__ __forceinline__ double s1u_lmin(const double* W, int n, int p, int la
       res = 0.0;
    else
    {
-      const double sinv = s1_rcp(nrm);
+      const double sinv = hs_rcp2(nrm);
       double dsv[NP], e2v[NP];
 #pragma unroll
       for (int i = 0; i < NP; ++i)
@@ -1140,15 +1107,6 @@ __device__ __forceinline__ double s1u_lmin_n(const double* W, int n, int p, int 
 #endif
 }
 
-template<int CTRL>
-__device__ __forceinline__ double s1_dppz(double v)
-{
-   int lo = __double2loint(v), hi = __double2hiint(v);
-   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-   return __hiloint2double(hi, lo);
-}
-
 /* ---- one wavefront: min(lambda_min, 0) of the symmetric tridiagonal matrix with diagonal d_i and off-diagonal e_i (coupling i and
  * i + 1) held by lane i, n <= 64: Sturm multisection, 64 shifts per round, to a relative accuracy of 1e-10 (from below); NaN when
  * an entry is not finite.  The sequence runs in product form out of REGISTERS: d_i and e_i^2 reach all lanes by v_readlane (an LDS
@@ -1168,13 +1126,13 @@ __device__ __forceinline__ double s1_sturm_min(double dl, double el, int n, int 
    const double glo = s1_wmin((lane < n) ? dl - rad : 1e300);
    if ( !(glo < 0.0) || !(nrm > 0.0) )
       return 0.0;
-   const double sinv = s1_rcp(nrm);
+   const double sinv = hs_rcp2(nrm);
    const double ds = dl * sinv;
    const double e2 = (el * sinv) * (el * sinv);
    if ( tprof != NULL && lane == 0 )
       tprof[1] -= (double) clock64();
    double lo = glo * sinv * (1.0 + 1e-12) - 1e-300, hi = 0.0;
-   const double d0 = s1_lane(ds, 0);
+   const double d0 = hs_lane(ds, 0);
    /* SMALL (n <= 16): every lane holds the whole matrix in VECTOR registers (written to LDS once, read back by all lanes), padded to
     * 16 rows with rows that cannot change a sign (diagonal 4 > |x| + 1, no coupling): the 15 steps are straight-line code, three
     * arithmetic instructions and a compare each.  [Broadcast by v_readlane made the entries wavefront-uniform SCALAR values: the
@@ -1233,7 +1191,7 @@ __device__ __forceinline__ double s1_sturm_min(double dl, double el, int n, int 
       else
       for (int i = 1; i < n; ++i)
       {
-         const double di = s1_lane(ds, i), ei = s1_lane(e2, i - 1);
+         const double di = hs_lane(ds, i), ei = hs_lane(e2, i - 1);
          const double pn = fma(di - x, pc, -ei * pp);
          const bool posn = pn > 0.0;
          below = below || (posn != posc);
@@ -1303,10 +1261,10 @@ __device__ __forceinline__ double s1_lmin16(const double* W, int n, int p, int l
          const double theirs = __shfl_xor(mine, 16, 64);
          const double ek = (half == (k & 1)) ? mine : theirs;
          const double xa = (row > k) ? ek : 0.0;
-         const double x0 = s1_lane(xa, k + 1);
+         const double x0 = hs_lane(xa, k + 1);
          /* (the sums over rows exactly as the one-lane-per-row form wrote them - the lanes from 16 on sum garbage of their own that
           * nobody reads: the compiler fuses the first addition of the second sum with its product, a select in between would stop it) */
-         const double s2 = s1_lane(s1_sum16(lane > k + 1 ? xa * xa : 0.0), 0);
+         const double s2 = hs_lane(hs_row_sum_dpp(lane > k + 1 ? xa * xa : 0.0), 0);
          if ( lane == k )
             dreg = ek;
          if ( s2 != s2 )
@@ -1322,7 +1280,7 @@ __device__ __forceinline__ double s1_lmin16(const double* W, int n, int p, int l
             const double rh = s1_rsqrt(h2);
             const double beta = -copysign(h2 * rh, x0);
             const double t = (x0 - beta) * copysign(rh, x0);
-            const double scale = s1_rcp(x0 - beta);
+            const double scale = hs_rcp2(x0 - beta);
             /* the reflector is zero in the rows up to k, so the sums and the update run over all columns without guards */
             const double vl = (row == k + 1) ? 1.0 : ((row > k + 1) ? xa * scale : 0.0);
             if ( lane == k )
@@ -1340,7 +1298,7 @@ __device__ __forceinline__ double s1_lmin16(const double* W, int n, int p, int l
                acc = fma(ah[i], vh[i], acc);
             const double oth = __shfl_xor(acc, 16, 64);
             const double pl = (row > k) ? t * (half == 0 ? acc + oth : oth + acc) : 0.0;
-            const double pv = s1_lane(s1_sum16(pl * vl), 0);
+            const double pv = hs_lane(hs_row_sum_dpp(pl * vl), 0);
             const double wl = fma(-0.5 * t * pv, vl, pl);
             if ( lane < 16 )
                bc[16 + lane] = wl;
@@ -1366,7 +1324,7 @@ __device__ __forceinline__ double s1_lmin16(const double* W, int n, int p, int l
       dreg = own;
    if ( n >= 2 )
    {
-      const double elast = s1_lane(left, n - 1);
+      const double elast = hs_lane(left, n - 1);
       if ( lane == n - 2 )
          ereg = elast;
    }
@@ -1395,8 +1353,8 @@ __device__ __forceinline__ double s1_lmin(double* W, int n, int p, int lane, dou
    for (int k = 0; k + 2 < n; ++k)
    {
       const double xa = (lane > k && lane < n) ? W[lane * p + k] : 0.0;
-      const double x0 = s1_lane(xa, k + 1);
-      const double s2 = small ? s1_lane(s1_sum16(lane > k + 1 ? xa * xa : 0.0), 0) : s1_wsum(lane > k + 1 ? xa * xa : 0.0);
+      const double x0 = hs_lane(xa, k + 1);
+      const double s2 = small ? hs_lane(hs_row_sum_dpp(lane > k + 1 ? xa * xa : 0.0), 0) : hs_wave_sum_dpp(lane > k + 1 ? xa * xa : 0.0);
       if ( lane == 0 )
          dd[k] = W[k * p + k];
       if ( !(s2 > 1e-290) )
@@ -1411,7 +1369,7 @@ __device__ __forceinline__ double s1_lmin(double* W, int n, int p, int lane, dou
       const double rh = s1_rsqrt(h2);
       const double beta = -copysign(h2 * rh, x0);
       const double t = (x0 - beta) * copysign(rh, x0);          /* (beta - x0) / beta with 1 / beta = -sign(x0) / sqrt(h2) */
-      const double scale = s1_rcp(x0 - beta);
+      const double scale = hs_rcp2(x0 - beta);
       const double vl = (lane == k + 1) ? 1.0 : xa * scale;          /* lanes > k */
       if ( lane > k && lane < n )
          vv[lane] = vl;
@@ -1463,7 +1421,7 @@ __device__ __forceinline__ double s1_lmin(double* W, int n, int p, int lane, dou
          pl = t * ((a0 + a1) + (a2 + a3));
       }
       const double pvl = (lane > k && lane < n) ? pl * vl : 0.0;
-      const double pv = small ? s1_lane(s1_sum16(pvl), 0) : s1_wsum(pvl);
+      const double pv = small ? hs_lane(hs_row_sum_dpp(pvl), 0) : hs_wave_sum_dpp(pvl);
       const double al = -0.5 * t * pv;
       const double wl = pl + al * vl;
       if ( lane > k && lane < n )
@@ -1524,7 +1482,7 @@ __device__ __forceinline__ double s1_lmin(double* W, int n, int p, int lane, dou
  * twice, on one wavefront with the others idle; with two lanes per row every lane forms half of its row's entry of A v and applies half
  * of its row's part of the rank-2 update.  THE SAME BITS as s1_lmin: the entry of A v is ((a0 + a1) + (a2 + a3)) of four chains over the
  * columns k + 1 + j + 4 i - the first half owns chains 0 and 1, the second 2 and 3, the two partial sums meet through one lane
- * exchange -; the sums over rows (s1_wsum) see the same values in the same lanes, zeros in the lanes from 32 on as before. */
+ * exchange -; the sums over rows (hs_wave_sum_dpp) see the same values in the same lanes, zeros in the lanes from 32 on as before. */
 __device__ __forceinline__ double s1_lmin2(double* W, int n, int p, int lane, double* scr, double* tprof)
 {
    double* dd = scr;
@@ -1536,8 +1494,8 @@ __device__ __forceinline__ double s1_lmin2(double* W, int n, int p, int lane, do
    {
       const bool act = row > k && row < n;
       const double xa = act ? W[row * p + k] : 0.0;
-      const double x0 = s1_lane(xa, k + 1);
-      const double s2 = s1_wsum((half == 0 && lane > k + 1) ? xa * xa : 0.0);
+      const double x0 = hs_lane(xa, k + 1);
+      const double s2 = hs_wave_sum_dpp((half == 0 && lane > k + 1) ? xa * xa : 0.0);
       if ( lane == 0 )
          dd[k] = W[k * p + k];
       if ( !(s2 > 1e-290) )
@@ -1552,7 +1510,7 @@ __device__ __forceinline__ double s1_lmin2(double* W, int n, int p, int lane, do
       const double rh = s1_rsqrt(h2);
       const double beta = -copysign(h2 * rh, x0);
       const double t = (x0 - beta) * copysign(rh, x0);          /* (beta - x0) / beta with 1 / beta = -sign(x0) / sqrt(h2) */
-      const double scale = s1_rcp(x0 - beta);
+      const double scale = hs_rcp2(x0 - beta);
       const double vl = (row == k + 1) ? 1.0 : xa * scale;           /* rows > k */
       if ( act && half == 0 )
          vv[row] = vl;
@@ -1599,7 +1557,7 @@ __device__ __forceinline__ double s1_lmin2(double* W, int n, int p, int lane, do
       const double other = __shfl_xor(part, 32, 64);
       const double pl = act ? t * (half == 0 ? part + other : other + part) : 0.0;
       const double pvl = (half == 0 && act) ? pl * vl : 0.0;
-      const double pv = s1_wsum(pvl);
+      const double pv = hs_wave_sum_dpp(pvl);
       const double al = -0.5 * t * pv;
       const double wl = pl + al * vl;
       if ( act && half == 0 )
@@ -2401,7 +2359,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          if ( t < sh.roff[r + 1] && sh.rcol[t] == 0 )
             c2 += sh.rval[t] * sh.rval[t];
       }
-      c2 = s1_wsum(c2);
+      c2 = hs_wave_sum_dpp(c2);
       if ( lane == 0 )
          sh.red[wave][RS_NC2] = c2;
       if ( wave == 0 )
@@ -2409,7 +2367,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          double bsq = 0.0;
          for (int i = lane; i < m; i += 64)
             bsq = fma(VEC(V_b)[i], VEC(V_b)[i], bsq);
-         const double nb2 = s1_wsum(bsq);
+         const double nb2 = hs_wave_sum_dpp(bsq);
          if ( lane == 0 )
             sh.sc[SC_NORMB] = sqrt(nb2);
       }
@@ -2494,7 +2452,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          const double cv0 = LP(sh.cval)[t];
          s00 = fma(cv0 * sx[LP(sh.crow)[t]], cv0, s00);
       }
-      s00 = s1_wsum(s00);
+      s00 = hs_wave_sum_dpp(s00);
       if ( lane == 0 )
          Mx[0] = s00;
    };
@@ -2594,7 +2552,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          if ( !(xv > 0.0) || !(zv > 0.0) )
             bad = 1.0;
       }
-      xz = s1_wsum(xz);
+      xz = hs_wave_sum_dpp(xz);
       bad = s1_wmax(bad);
       if ( lane == 0 )
       {
@@ -2734,7 +2692,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             for (int t = LP(sh.coff)[i] + l16; t < t1; t += 16)
                s = fma(LP(sh.cval)[t], xv[LP(sh.crow)[t]], s);
          }
-         s = s1_sum16(s);
+         s = hs_row_sum_dpp(s);
          if ( l16 == 0 )
          {
             outv[i] = s;
@@ -2838,14 +2796,14 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          bu1 = fma(VEC(V_b)[i], VEC(V_u1)[i], bu1);
          wrp = fma(VEC(V_w)[i], VEC(V_rp)[i], wrp);
       }
-      bu1 = s1_wsum(bu1);
-      wrp = s1_wsum(wrp);
+      bu1 = hs_wave_sum_dpp(bu1);
+      wrp = hs_wave_sum_dpp(wrp);
       const double S0 = red_sum(RS_S0);
       const double BH = red_sum(RS_BH);
-      const double it_ = s1_rcp(tau);
+      const double it_ = hs_rcp2(tau);
       const double den = S0 + kappa * it_ + sh.sc[SC_BUB];
       const double num = -eta * rg + (sigmu - tau * kappa - etk) * it_ - BH - eta * wrp + bu1;
-      const double dtau = num * s1_rcp(den);
+      const double dtau = num * hs_rcp2(den);
       const double dkappa = (sigmu - tau * kappa - etk - kappa * dtau) * it_;
       for (int i = lane; i < m; i += 64)
       {
@@ -2876,7 +2834,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
       }
       for (int r = tro(320); r < q; r += S1_NT)
          s = fma(QV(Q_beta)[r], QV(Q_hl)[r], s);
-      s = s1_wsum(s);
+      s = hs_wave_sum_dpp(s);
       if ( lane == 0 )
          sh.red[wave][RS_BH] = s;
    };
@@ -2930,8 +2888,8 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          for (int r = tro(256); r < q; r += S1_NT)
          {
             const double dxv = QV(Q_dx)[r], dzv = QV(Q_dz)[r];
-            if ( dxv < 0.0 ) rx = fmin(rx, -QV(Q_x)[r] * s1_rcp(dxv));
-            if ( dzv < 0.0 ) rz = fmin(rz, -QV(Q_z)[r] * s1_rcp(dzv));
+            if ( dxv < 0.0 ) rx = fmin(rx, -QV(Q_x)[r] * hs_rcp2(dxv));
+            if ( dzv < 0.0 ) rz = fmin(rz, -QV(Q_z)[r] * hs_rcp2(dzv));
          }
          rx = s1_wmin(rx); rz = s1_wmin(rz);
          if ( lane == 0 )
@@ -2982,7 +2940,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
          if ( lm != lm )
             a = nan("");
          else if ( lm < 0.0 )
-            a = fmin(a, -s1_rcp(lm));
+            a = fmin(a, -hs_rcp2(lm));
       }
       double rx = 1e300, rz = 1e300;
       for (int w = 0; w < S1_NW; ++w)
@@ -2992,8 +2950,8 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
       }
       a = fmin(a, fmin(rx, rz));
       const double tau = sh.sc[SC_TAU], kappa = sh.sc[SC_KAPPA], dtau = sh.sc[SC_DTAU], dkappa = sh.sc[SC_DKAPPA];
-      if ( dtau < 0.0 ) a = fmin(a, -tau * s1_rcp(dtau));
-      if ( dkappa < 0.0 ) a = fmin(a, -kappa * s1_rcp(dkappa));
+      if ( dtau < 0.0 ) a = fmin(a, -tau * hs_rcp2(dtau));
+      if ( dkappa < 0.0 ) a = fmin(a, -kappa * hs_rcp2(dkappa));
       return a;
    };
 
@@ -3022,7 +2980,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
                r2 = fma(wgt * v, v, r2);
                xz = fma(wgt * sm[B.oX + r * p + c], zv, xz);
             });
-            r2 = s1_wsum(r2);
+            r2 = hs_wave_sum_dpp(r2);
             if ( lane == 0 )
                sh.red[wave][RS_BLK0 + k] = r2;
          }
@@ -3036,7 +2994,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             rmax = fmax(rmax, fabs(v));
             xz = fma(QV(Q_x)[r], zv, xz);
          }
-         xz = s1_wsum(xz); r2lp = s1_wsum(r2lp); rmax = s1_wmax(rmax);
+         xz = hs_wave_sum_dpp(xz); r2lp = hs_wave_sum_dpp(r2lp); rmax = s1_wmax(rmax);
          if ( lane == 0 )
          {
             sh.red[wave][RS_XZ] = xz;
@@ -3059,7 +3017,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
                   dob = fma(bv, VEC(V_y)[i - 1], dob);
                }
             });
-            rp2 = s1_wsum(rp2); hp2 = s1_wsum(hp2); dob = s1_wsum(dob);
+            rp2 = hs_wave_sum_dpp(rp2); hp2 = hs_wave_sum_dpp(hp2); dob = hs_wave_sum_dpp(dob);
             if ( lane == 0 )
             {
                sh.red[wave][RS_RP2] = rp2; sh.red[wave][RS_HP2] = hp2; sh.red[wave][RS_DOB] = dob;
@@ -3072,7 +3030,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
       pobj = s1_uni(VEC(V_AX)[0]);
       dobj = s1_uni(red_sum(RS_DOB));
       const double rg = pobj - dobj - kappa;
-      const double itau = s1_rcp(tau);
+      const double itau = hs_rcp2(tau);
       mu = s1_uni((red_sum(RS_XZ) + tau * kappa) * iN1);
       double rd2 = red_sum(RS_RD2LP);
       double rdmax = 0.0;
@@ -3159,7 +3117,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             const double v = fma(tau, c0, QV(Q_rd)[r]);
             h2 = fma(v, v, h2);
          }
-         h2 = s1_wsum(h2);
+         h2 = hs_wave_sum_dpp(h2);
          if ( lane == 0 )
             sh.red[wave][RS_HD2] = h2;
          S1_BAR();
@@ -3346,7 +3304,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
                         const int pp = (int) (pq >> 16), qq = (int) (pq & 0xffffu);
                         s0 = fma(LP(B.vval)[t], U[qq * p + pp], s0);
                      }
-                     s0 = s1_sum16(s0);
+                     s0 = hs_row_sum_dpp(s0);
                      if ( l16 == 0 )
                         Mx[(i >= j) ? MROW(i) + j : MROW(j) + i] += s0;
                   }
@@ -3537,7 +3495,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
                S1_BAR();
             if ( lane == 0 )
                sh.fl[6] = nforced;
-            mdinv = s1_rcp(mdiag);
+            mdinv = hs_rcp2(mdiag);
             if ( lane < m )
                VEC(V_dg)[lane] = mdinv;
             if ( P.prof_on && lane == 0 ) { const long long tq1 = clock64(); sh.prof[20] += (double) (tq1 - tq0); tq0 = tq1; }
@@ -3585,7 +3543,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             double bubp = 0.0;
             for (int i = lane; i < m; i += 64)
                bubp = fma(VEC(V_b)[i], VEC(V_ub)[i], bubp);
-            const double bub = s1_wsum(bubp);
+            const double bub = hs_wave_sum_dpp(bubp);
             if ( lane == 0 )
                sh.sc[SC_BUB] = bub;
          }
@@ -3645,7 +3603,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             {
                const double dg0 = (lane < m) ? Lm[lane * pm + lane] : 1.0;
                (void) s1_cholp(Lm, m, pm, lane, true, dg0, P.pivot_rule, false, mdiag, nforced, zsrc);
-               mdinv = s1_rcp(mdiag);
+               mdinv = hs_rcp2(mdiag);
                if ( lane < m )
                   VEC(V_dg)[lane] = mdinv;
             }
@@ -3671,7 +3629,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             double bubp = 0.0;
             for (int i = lane; i < m; i += 64)
                bubp = fma(VEC(V_b)[i], VEC(V_ub)[i], bubp);
-            const double bub = s1_wsum(bubp);
+            const double bub = hs_wave_sum_dpp(bubp);
             if ( lane == 0 )
                sh.sc[SC_BUB] = bub;
          }
@@ -3749,7 +3707,7 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
             const double be = QV(Q_beta)[r];
             s = fma(QV(Q_sx)[r] * be, be, s);
          }
-         s = s1_wsum(s);
+         s = hs_wave_sum_dpp(s);
          if ( lane == 0 )
             sh.red[wave][RS_S0] = s;
       }
@@ -3889,11 +3847,11 @@ __global__ void __launch_bounds__(S1_NT) S1_KERNEL(S1_PARAMS)
                e2p = fma(e, e, e2p);
                dy2p = fma(VEC(V_dy)[i], VEC(V_dy)[i], dy2p);
             }
-            const double e2 = s1_wsum(e2p);
-            const double dy2 = s1_wsum(dy2p);
+            const double e2 = hs_wave_sum_dpp(e2p);
+            const double dy2 = hs_wave_sum_dpp(dy2p);
             /* (the residual of the solve itself cannot be formed any more: the factor has overwritten M) */
             const double rs = 0.0;
-            const double h2 = s1_wsum(rs * rs);
+            const double h2 = hs_wave_sum_dpp(rs * rs);
             if ( lane == 0 && it < P.hist_len )
             {
                double* hh = P.hist + 16 * it;

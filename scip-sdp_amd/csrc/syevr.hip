@@ -31,6 +31,7 @@
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_sturm.h"
+#include "hs_wave.h"
 #include <cmath>
 
 #define SR_N   HS_SYEVX_MAXN
@@ -40,28 +41,6 @@
 #define SR_BC  8                    /* reflectors staged in LDS at a time */
 
 namespace {
-
-__device__ __forceinline__ double sr_wsum(double v)
-{
-#pragma unroll
-   for (int m = 1; m < 64; m <<= 1)
-      v += __shfl_xor(v, m, 64);
-   return v;
-}
-
-/* sum over the workgroup in a fixed order, the same bits in every thread; one barrier, red not to be reused before the next one */
-__device__ __forceinline__ double sr_bsum(double v, double* red)
-{
-   v = sr_wsum(v);
-   if ( (threadIdx.x & 63) == 0 )
-      red[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double s = red[0];
-#pragma unroll
-   for (int w = 1; w < SR_T / 64; ++w)
-      s += red[w];
-   return s;
-}
 
 /* the part of the workspace behind that of syevx.hip */
 struct sr_ws
@@ -417,7 +396,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_ortho_prev(int n, int p, const i
             const double* __restrict__ zq = Zg + (size_t) (c + q) * n + r0;
             for (int i = lane; i < rows; i += 64)
                acc = fma(zq[i], zs[i], acc);
-            acc = sr_wsum(acc);
+            acc = hs_xsum<64>(acc);
          }
          if ( lane == 0 )
             coef[q] = acc;
@@ -487,7 +466,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel(int n, int p, const 
             {
                for (int i = lane; i < n; i += 64)
                   acc = fma(Z[q * ld + i], Z[t * ld + i], acc);
-               acc = sr_wsum(acc);
+               acc = hs_xsum<64>(acc);
             }
             if ( lane == 0 )
                coef[q] = acc;
@@ -504,7 +483,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel(int n, int p, const 
          __syncthreads();
       }
       const double v = (tid < n) ? Z[t * ld + tid] : 0.0;
-      const double nr = sr_bsum(v * v, red[t & 1]);
+      const double nr = hs_block_sum<SR_T / 64>(v * v, red[t & 1]);
       if ( tid < n )
          Z[t * ld + tid] = v / sqrt(fmax(nr, 1e-300));
       __syncthreads();
@@ -562,7 +541,7 @@ __global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* 
 #pragma unroll
             for (int m = 0; m < SR_N / 64; ++m)
                dot = fma(vs[u][lane + 64 * m], z[m], dot);
-            dot = ts[j] * sr_wsum(dot);
+            dot = ts[j] * hs_xsum<64>(dot);
 #pragma unroll
             for (int m = 0; m < SR_N / 64; ++m)
                z[m] = fma(-dot, vs[u][lane + 64 * m], z[m]);
@@ -580,7 +559,7 @@ __global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* 
 #pragma unroll
    for (int m = 0; m < SR_N / 64; ++m)
       nr = fma(z[m], z[m], nr);
-   nr = sr_wsum(nr);
+   nr = hs_xsum<64>(nr);
    const double rn = nr > 0.0 ? 1.0 / sqrt(nr) : 1.0;
 #pragma unroll
    for (int m = 0; m < SR_N / 64; ++m)

@@ -29,6 +29,7 @@
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_sturm.h"
+#include "hs_wave.h"
 #include <cmath>
 
 #define SX_N   HS_SYEVX_MAXN
@@ -37,31 +38,6 @@
 #define SX_VT  512                  /* threads of the eigenvalue and the eigenvector kernel */
 
 namespace {
-
-/* sum over the 64 lanes, the same bits in every lane */
-__device__ __forceinline__ double sx_wsum(double v)
-{
-#pragma unroll
-   for (int m = 1; m < 64; m <<= 1)
-      v += __shfl_xor(v, m, 64);
-   return v;
-}
-
-/* sum over the workgroup in a fixed order (wavefront sums through red[], NW of them), the same bits in every thread; contains
- * one barrier - red must not be reused before the next one */
-template<int NW>
-__device__ __forceinline__ double sx_bsum(double v, double* red)
-{
-   v = sx_wsum(v);
-   if ( (threadIdx.x & 63) == 0 )
-      red[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double s = red[0];
-#pragma unroll
-   for (int w = 1; w < NW; ++w)
-      s += red[w];
-   return s;
-}
 
 /* a b + c d with both products rounded: symmetric under (a, b) <-> (d, c), so the update keeps A[i][c] == A[c][i] to the bit */
 __device__ __forceinline__ double sx_sym2(double a, double b, double c, double d)
@@ -127,7 +103,7 @@ __global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __res
          wp[c] = p;
          part = fma(p, v, part);
       }
-      const double al = -0.5 * tprev * sx_bsum<SX_CT / 64>(part, red[0]);
+      const double al = -0.5 * tprev * hs_block_sum<SX_CT / 64>(part, red[0]);
       for (int c = j + tid; c < n; c += SX_CT)
          wp[c] = fma(al, vp[c], wp[c]);                   /* (each thread its own entries) */
       __syncthreads();
@@ -146,7 +122,7 @@ __global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __res
    double s2p = 0.0;
    for (int c = j + 2 + tid; c < n; c += SX_CT)
       s2p = fma(xs[c], xs[c], s2p);
-   const double s2 = sx_bsum<SX_CT / 64>(s2p, red[1]);
+   const double s2 = hs_block_sum<SX_CT / 64>(s2p, red[1]);
    const double x0 = xs[j + 1], dj = xs[j];
    double beta = x0, t = 0.0, scale = 0.0;
    if ( s2 > 0.0 )
@@ -211,7 +187,7 @@ __global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __res
             if ( c < n )
                acc = fma(a[m], xs[c], acc);
          }
-         acc = sx_wsum(acc);
+         acc = hs_xsum<64>(acc);
          if ( lane == 0 )
             pcur[i] = t * acc;
       }
@@ -472,7 +448,7 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __res
                double acc = 0.0;
                for (int i = lane; i < n; i += 64)
                   acc = fma(Z[p * ld + i], Z[k * ld + i], acc);
-               acc = sx_wsum(acc);
+               acc = hs_xsum<64>(acc);
                if ( lane == 0 )
                   coef[p] = acc;
             }
@@ -487,7 +463,7 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __res
             __syncthreads();
          }
          const double v = (tid < n) ? Z[k * ld + tid] : 0.0;
-         const double nr = sx_bsum<SX_VT / 64>(v * v, red[k & 1]);
+         const double nr = hs_block_sum<SX_VT / 64>(v * v, red[k & 1]);
          if ( tid < n )
             Z[k * ld + tid] = v / sqrt(fmax(nr, 1e-300));
          __syncthreads();
@@ -539,7 +515,7 @@ __global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restri
 #pragma unroll
             for (int m = 0; m < SX_N / 64; ++m)
                dot = fma(vb[u][m], z[m], dot);
-            dot = t * sx_wsum(dot);
+            dot = t * hs_xsum<64>(dot);
 #pragma unroll
             for (int m = 0; m < SX_N / 64; ++m)
                z[m] = fma(-dot, vb[u][m], z[m]);
@@ -554,7 +530,7 @@ __global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restri
 #pragma unroll
    for (int m = 0; m < SX_N / 64; ++m)
       nr = fma(z[m], z[m], nr);
-   nr = sx_wsum(nr);
+   nr = hs_xsum<64>(nr);
    const double rn = nr > 0.0 ? 1.0 / sqrt(nr) : 1.0;
 #pragma unroll
    for (int m = 0; m < SX_N / 64; ++m)
