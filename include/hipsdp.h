@@ -204,7 +204,11 @@ HIPSDP_API int  hipsdp_get_preoptimal(hipsdp_solver* solver, int* available, dou
 HIPSDP_API int  hipsdp_get_preoptimal_X(hipsdp_solver* solver, int block, double* X);
 
 /* smallest eigenvalue of  sum_i A_i^k y_i - A_0^k  for every block, on the device (backs the feasibility check of
- * sdpsolchecker.c:201-257 inside the backend); y: m host values; lmin: nblocks host values */
+ * sdpsolchecker.c:201-257 inside the backend); y: m host values; lmin: nblocks host values.  Per block: up to 200 rows the
+ * Lanczos value minus its residual norm, a lower estimate and no decomposition; 201 .. HIPSDP_SYEVX_MAXN (512) rows the first eigenvalue
+ * as hipsdp_syevx computes it, relative to the norm of Z(y) in the scale range stated there; above that a lower bound
+ * estimate - 1e-9 (1 + |estimate|) certified by a Cholesky factorization, whose margin is absolute, or the computed eigenvalue
+ * where the factorization fails */
 HIPSDP_API int  hipsdp_check_y(hipsdp_solver* solver, const double* y, double* lmin, double* lpviol);
 /* the same against a known tolerance: blocks above 64 rows are certified by one Cholesky factorization of Z(y) + 0.999 tol I
  * (lmin = -0.999 tol on success: a rigorous lower bound that passes "lmin >= -tol"); the exact eigenvalue is computed only when
@@ -325,7 +329,16 @@ HIPSDP_API int  hipsdp_syev_small(int device, int n, const double* A, double* la
  * of the wanted vectors only - csrc/syevx.hip; up to 128 rows the one-launch kernels above serve the call).  The triangle of A that
  * hipsdp_syevi_small reads is read.  Sign of a vector and basis inside a multiple eigenvalue are free; the returned vectors are
  * orthonormal among themselves.  HIPSDP_ERR_ARG, nothing launched: n < 1, n > HIPSDP_SYEVX_MAXN, il < 1, iu > n, il > iu, more than
- * HIPSDP_SYEVX_MAXK pairs, maxk outside 0 .. HIPSDP_SYEVX_MAXK, A, lam or count NULL.  Same input, same bits. */
+ * HIPSDP_SYEVX_MAXK pairs, maxk outside 0 .. HIPSDP_SYEVX_MAXK, A, lam or count NULL.  Same input, same bits.
+ * An eigenvalue is the midpoint of its own bisection interval, and the copies of a multiple eigenvalue are made ascending by a running
+ * maximum over the returned range: the last bit of lam for one index may differ between calls with another il, and from hipsdp_syevr
+ * and hipsdp_syev_small on the same matrix.
+ * SCALE RANGE of all eigen entries (hipsdp_syev, hipsdp_syev_small, hipsdp_syevi_small, hipsdp_syevx, hipsdp_syevx_below, hipsdp_syevr,
+ * the decompositions behind hipsdp_eigencuts_all): a finite symmetric matrix that is 2^-100 .. 2^100 times a matrix with entries of
+ * order 1 .. n - squares of entries and sums of n of them stay far from overflow and underflow there.  Inside the range the accuracy
+ * is relative to the norm of the matrix (eigenvalues to 1e-12 of the largest one in absolute value, residuals to 1e-9 of it, vectors
+ * orthonormal to 1e-11, whatever the scale), and the zero matrix returns eigenvalues below 1e-200 in absolute value with
+ * orthonormal vectors.  Larger or smaller scales, NaN, Inf and non-symmetric input are outside the contract.  hipsdp_check_y: see there. */
 #define HIPSDP_SYEVX_MAXN 512
 #define HIPSDP_SYEVX_MAXK 32
 /* eigenpairs il..iu (1-based, ascending) of the symmetric n x n host matrix A: DSYEVR RANGE='I'.  lam: iu-il+1 values;

@@ -231,6 +231,17 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
             zz[k] = 0.5 * (lo + hi);                   /* eigenvalue k */
       }
       __syncthreads();
+      /* every index is searched in an interval of its own: the midpoints of a multiple eigenvalue may differ in the last place, in
+       * either order.  Ascending as promised: the running maximum (changes nothing where the values ascend already) */
+      {
+         double zmax = (tid < n) ? zz[tid] : 0.0;
+         for (int j = 0; j < tid && tid < n; ++j)
+            zmax = fmax(zmax, zz[j]);
+         __syncthreads();
+         if ( tid < n )
+            zz[tid] = zmax;
+      }
+      __syncthreads();
       if ( tid < n )
          out[tid] = zz[tid];
       /* ---- eigenvectors: three rounds of { one step of inverse iteration for every vector (thread k owns vector k),
@@ -1257,6 +1268,16 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
       }
       if ( k < n && sh == 0 )
          zz[k] = 0.5 * (lo + hi) * tnorm;
+   }
+   __syncthreads();
+   /* (the running maximum, as in k_syevi_small: the midpoints of a multiple eigenvalue may differ in the last place in either order) */
+   {
+      double zmax = (tid < n) ? zz[tid] : 0.0;
+      for (int j = 0; j < tid && tid < n; ++j)
+         zmax = fmax(zmax, zz[j]);
+      __syncthreads();
+      if ( tid < n )
+         zz[tid] = zmax;
    }
    __syncthreads();
    EM_STAMP(1);

@@ -4666,9 +4666,11 @@ static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* l
    /* The reference accepts a solution on an EXACT eigenvalue (sdpsolchecker.c:201-257).  A Ritz value is an upper bound of
     * lambda_min and "theta - resid" only says that SOME eigenvalue lies that close to theta; once the Krylov space cannot span
     * the matrix (n above the 250 steps) an unconverged smaller eigenvalue would go unnoticed - and at an optimum Z(y) has a
-    * cluster at 0, the slow case.  So the bound is certified: a Cholesky factorization of W - sigma I with sigma just below the
-    * estimate succeeds only if lambda_min > sigma (then sigma is returned, a rigorous lower bound); if it fails the exact
-    * Jacobi eigenvalue is computed. */
+    * cluster at 0, the slow case.  So above 200 rows the Lanczos estimate is not returned.  Without a tolerance and up to
+    * HS_SYEVX_MAXN rows the first eigenvalue is computed (tridiagonal path, values only).  Otherwise the bound is certified: a
+    * Cholesky factorization of W - sigma I succeeds only if lambda_min > sigma (then sigma is returned, a rigorous lower bound) -
+    * sigma = -0.999 tol against a tolerance, estimate - 1e-9 (1 + |theta|) without one, a margin that is absolute and so not
+    * relative to the norm of Z(y); if it fails the eigenvalue is computed. */
    for (size_t b = 0; b < s->blk.size(); ++b)
    {
       Block& B = s->blk[b];
@@ -4677,6 +4679,23 @@ static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* l
       if ( n <= 200 && !bytol )
          continue;
       const long long n2 = (long long) n * n;
+      if ( !bytol && n <= HS_SYEVX_MAXN )
+      {
+         /* tridiagonalisation and Sturm multisection for the first eigenvalue alone (syevx.hip): accurate to rounding relative to
+          * the norm of Z(y) at every scale, and cheaper than the factorization */
+         double *out = NULL, *ws = NULL;
+         double l0 = 0.0;
+         int rc = dalloc(&out, HS_SYEVX_OUT_VEC);
+         if ( rc == HS_OK ) rc = dalloc(&ws, (long long) hs_syevx_ws(n));
+         if ( rc == HS_OK ) rc = hs_syevx_dev(st, n, B.W, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, out, ws);
+         if ( rc == HS_OK && (hipMemcpyAsync(&l0, out + HS_SYEVX_OUT_LAM, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
+               || hipStreamSynchronize(st) != hipSuccess) )
+            rc = HS_ERR_HIP;
+         dfree(out); dfree(ws);
+         HS_CALL( rc );
+         lmin[b] = l0;
+         continue;
+      }
       const double theta = h.v[SC_BLK(b, 1)];
       const double sigma = bytol ? -0.999 * tol : lmin[b] - 1e-9 * (1.0 + fabs(theta));
       int fl = 0;

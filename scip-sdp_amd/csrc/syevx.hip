@@ -303,8 +303,19 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il
       if ( __syncthreads_and((!act || hi - lo <= 4.5e-16 * fmax(fmax(fabs(lo), fabs(hi)), 0.25)) ? 1 : 0) )
          break;
    }
+   /* every index is searched in an interval of its own: the midpoints of a multiple eigenvalue may differ in the last place, in either
+    * order.  Ascending as promised: the running maximum (changes nothing where the values ascend already; ds is free by now) */
+   __syncthreads();
    if ( act && sh == 0 )
-      out[HS_SYEVX_OUT_LAM + kk] = 0.5 * (lo + hi) * tnorm;
+      ds[kk] = 0.5 * (lo + hi) * tnorm;
+   __syncthreads();
+   if ( tid < cnt )
+   {
+      double lmax = ds[tid];
+      for (int j = 0; j < tid; ++j)
+         lmax = fmax(lmax, ds[j]);
+      out[HS_SYEVX_OUT_LAM + tid] = lmax;
+   }
 }
 
 /* ---- stage 3: eigenvectors of T for the returned eigenvalues, Zt[k][i].  Dynamic LDS: Z[SX_K][n | 1]. */

@@ -578,7 +578,7 @@ def test_full_size_c4_properties(gpu):
     """BASELINE configs[3] (n = 2000, m = 4000) on ONE device: 128 GB of constraint matrices generated in HBM + their 64 GB packed
     copy; the W formulation runs in column slices because T and W (2 x 128 GB) do not fit beside them.  About 20 s per solve, so
     one solve only; size-independent properties: planted optimum on both sides, the y-side acceptance test with its rigorous
-    certificate (hipsdp_check_y: Cholesky of Z(y) - sigma I, exact eigenvalue when that fails), X psd, primal residual."""
+    certificate (hipsdp_check_y above 512 rows: Cholesky of Z(y) - sigma I, exact eigenvalue when that fails), X psd, primal residual."""
     n, m = 2000, 4000
     Q, _ = np.linalg.qr(instances.counter_normal(20240 + 1000003, np.arange(n * n, dtype=np.uint64)).reshape(n, n))
     r = n // 4

@@ -14,47 +14,17 @@ import threading
 import numpy as np
 import pytest
 import eig_cases
-from eig_cases import check_all_pairs
+from eig_cases import check_all_pairs, tridiagonals
 
 pytestmark = pytest.mark.gpu
 
 LARGE = [129, 130, 193, 257, 512]
 TSIZES = [2, 31, 32, 33, 65, 129, 512]
-_TCACHE = {}
 
 
 def spectra(n):
     """the seven spectra of tests/harness/eig_cases.py and, above 50 rows, its two decoupled ones"""
     return eig_cases.spectra(n, decoupled=True)
-
-
-def tridiagonals(n):
-    """name -> (d, e, eigenvalues of T, scale); n >= 2"""
-    if n not in _TCACHE:
-        i = np.arange(n, dtype=float)
-        m1 = n // 2
-        m2 = n - m1
-        glued_d = np.concatenate([np.abs(np.arange(m1) - m1 // 2), np.abs(np.arange(m2) - m2 // 2)]).astype(float)
-        glued_e = np.ones(n - 1)
-        glued_e[m1 - 1] = 1e-14
-        cut = np.full(n - 1, 0.5)
-        cut[6::7] = 0.0
-        gd = 10.0 ** np.linspace(-6, 6, n)
-        cases = {"toeplitz_121": (np.full(n, 2.0), np.ones(n - 1)),
-                 "wilkinson": (np.abs(i - n // 2), np.ones(n - 1)),
-                 "wilkinson_glued": (glued_d, glued_e),
-                 "diagonal_repeated": (np.mod(i, 5.0) - 1.0, np.zeros(n - 1)),
-                 "ones_cut_every_7th": (np.ones(n), cut),
-                 "graded": (gd, 1e-3 * np.sqrt(gd[:-1] * gd[1:]))}
-        out = {}
-        for name, (d, e) in cases.items():
-            T = np.diag(d) + np.diag(e, 1) + np.diag(e, -1)
-            ev = np.linalg.eigvalsh(T)
-            for a in (d, e, T, ev):
-                a.setflags(write=False)
-            out[name] = (d, e, T, ev, max(1.0, np.abs(ev).max()))
-        _TCACHE[n] = out
-    return _TCACHE[n]
 
 
 @pytest.mark.parametrize("n", LARGE)
