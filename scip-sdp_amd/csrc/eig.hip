@@ -11,7 +11,7 @@
  *      with RANGE = 'I', 'V', 'A'); ordering and eigenvectors-as-rows follow lapack_interface.c:507-603.
  */
 #include "hs_kernels.h"
-#include "hs_wave.h"
+#include "hs_tridiag.h"
 #include <math.h>
 
 __global__ void k_lmin_tiny(int n, const double* __restrict__ A0, const double* __restrict__ A1, double* __restrict__ res0,
@@ -158,9 +158,9 @@ __device__ void tridiag_min_wave(int kmax, const double* __restrict__ alpha, con
       lo = fmin(lo, d[i] - r);
       hi = fmax(hi, d[i] + r);
    }
-   const double span0 = fmax(hi - lo, 1e-300);
-   lo -= 1e-12 * span0 + 1e-300;
-   hi += 1e-12 * span0 + 1e-300;
+   const hs_td_bracket g = hs_td_widen(lo, hi);
+   const double span0 = g.span0;
+   lo = g.lo; hi = g.hi;
    const double pivmin = 1e-290;
    for (int round = 0; round < 14; ++round)
    {
@@ -1275,9 +1275,9 @@ __device__ double lmin_sym16(double (*a)[17], int n, double* vv, double* ww, dou
          hi = fmax(hi, dr[i] + rad);
       }
    }
-   const double span0 = fmax(hi - lo, 1e-300);
-   lo -= 1e-12 * span0 + 1e-300;
-   hi += 1e-12 * span0 + 1e-300;
+   const hs_td_bracket g = hs_td_widen(lo, hi);
+   const double span0 = g.span0;
+   lo = g.lo; hi = g.hi;
    const double pivmin = 1e-290;
    LM_T(3);
    /* every round narrows the interval 65-fold: 10 rounds take it below the rounding level of its ends */

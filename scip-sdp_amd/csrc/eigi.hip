@@ -18,8 +18,7 @@
 #include "../../include/hipsdp.h"
 #include <cstring>
 #include <cmath>
-#include "hs_sturm.h"
-#include "hs_wave.h"
+#include "hs_tridiag.h"
 
 #define EI_N  64
 #define EI_LD 65
@@ -183,17 +182,9 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
          e2[tid] = e[tid] * e[tid];
       __syncthreads();
       /* ---- all eigenvalues: thread (k = tid >> 2, s = tid & 3) */
-      double glo = 1e300, ghi = -1e300, tnorm = 0.0;
-      for (int i = 0; i < n; ++i)
-      {
-         const double rad = (i > 0 ? fabs(e[i - 1]) : 0.0) + (i + 1 < n ? fabs(e[i]) : 0.0);
-         glo = fmin(glo, d[i] - rad);
-         ghi = fmax(ghi, d[i] + rad);
-         tnorm = fmax(tnorm, fabs(d[i]) + rad);
-      }
-      const double span0 = fmax(ghi - glo, 1e-300);
-      glo -= 1e-12 * span0 + 1e-300;
-      ghi += 1e-12 * span0 + 1e-300;
+      const hs_td_gersh g = hs_td_gershgorin(n, d, e);
+      double glo = g.lo, ghi = g.hi, tnorm = g.tnorm;
+      const double span0 = g.span0;
       const double pivmin = 1e-290;
       {
          const int k = tid >> 2, sh = tid & 3;
@@ -256,9 +247,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
          for (int idx = tid; idx < n * n; idx += 256)
          {
             const int i = idx / n, k = idx - i * n;
-            unsigned h = (unsigned) (i * 2654435761u) ^ (unsigned) ((k + 1) * 40503u);
-            h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-            Z[i * EI_N + k] = 0.5 + (double) (h & 0xFFFF) * (1.0 / 65536.0);
+            Z[i * EI_N + k] = hs_td_start(i, k);
          }
       }
       else if ( tid == 0 )
@@ -403,17 +392,9 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
 
    /* ---- wavefront 0: i-th eigenvalue of T by Sturm multisection, 64 shifts per round, counts in product form on the matrix scaled
     * to norm 1 (ei_sturm_count) */
-   double lo = 1e300, hi = -1e300, tnorm = 0.0;
-   for (int i = 0; i < n; ++i)
-   {
-      const double rad = (i > 0 ? fabs(e[i - 1]) : 0.0) + (i + 1 < n ? fabs(e[i]) : 0.0);
-      lo = fmin(lo, d[i] - rad);
-      hi = fmax(hi, d[i] + rad);
-      tnorm = fmax(tnorm, fabs(d[i]) + rad);
-   }
-   const double span0 = fmax(hi - lo, 1e-300);
-   lo -= 1e-12 * span0 + 1e-300;
-   hi += 1e-12 * span0 + 1e-300;
+   const hs_td_gersh g = hs_td_gershgorin(n, d, e);
+   double lo = g.lo, hi = g.hi, tnorm = g.tnorm;
+   const double span0 = g.span0;
    tnorm = fmax(tnorm, 1e-300);
    const double sinv = 1.0 / tnorm;
    double* ds = pp;                                    /* (free since the reduction) */
@@ -425,11 +406,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
    }
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
-   if ( lane < 8 )
-   {
-      ds[n + lane] = 4.0;
-      es[n - 1 + lane] = 0.0;
-   }
+   hs_td_pad(ds, es, n, lane);
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
    lo *= sinv; hi *= sinv;
@@ -771,17 +748,9 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
       return;
 
    /* ---- wavefront 0: i-th eigenvalue of T by Sturm multisection (64 shifts per round, counts in product form: ei_sturm_count) */
-   double lo = 1e300, hi = -1e300, tnorm = 0.0;
-   for (int i = 0; i < n; ++i)
-   {
-      const double rad = (i > 0 ? fabs(e[i - 1]) : 0.0) + (i + 1 < n ? fabs(e[i]) : 0.0);
-      lo = fmin(lo, d[i] - rad);
-      hi = fmax(hi, d[i] + rad);
-      tnorm = fmax(tnorm, fabs(d[i]) + rad);
-   }
-   const double span0 = fmax(hi - lo, 1e-300);
-   lo -= 1e-12 * span0 + 1e-300;
-   hi += 1e-12 * span0 + 1e-300;
+   const hs_td_gersh g = hs_td_gershgorin(n, d, e);
+   double lo = g.lo, hi = g.hi, tnorm = g.tnorm;
+   const double span0 = g.span0;
    tnorm = fmax(tnorm, 1e-300);
    const double sinv = 1.0 / tnorm;
    double* ds = vv;                                    /* (free since the reduction) */
@@ -793,11 +762,7 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
    }
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
-   if ( lane < 8 )
-   {
-      ds[n + lane] = 4.0;
-      es[n - 1 + lane] = 0.0;
-   }
+   hs_td_pad(ds, es, n, lane);
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
    lo *= sinv; hi *= sinv;
@@ -812,7 +777,7 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
       const double nlo = lo + w * (double) first;
       const double nhi = (first < 64) ? lo + w * (double) (first + 1) : hi;
       lo = nlo; hi = nhi;
-      if ( hi - lo <= 4.5e-16 * fmax(fmax(fabs(lo), fabs(hi)), 0.25) )
+      if ( hs_td_converged(lo, hi) )
          break;
    }
    lo *= tnorm; hi *= tnorm;
@@ -1207,7 +1172,8 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
    __syncthreads();
    double* Z = em_a;                                        /* [i][k], pitch ld */
 
-   /* ---- all eigenvalues: thread (k = tid >> 2 (+ 64 in the second pass), s = tid & 3) */
+   /* ---- all eigenvalues: thread (k = tid >> 2 (+ 64 in the second pass), s = tid & 3).  The loop of hs_td_gershgorin and, below, the
+    * stores of hs_td_pad stay written out in this kernel: with the helpers it measured slower at 128 rows than the spread of two runs */
    double glo = 1e300, ghi = -1e300, tnorm = 0.0;
    for (int i = 0; i < n; ++i)
    {
@@ -1216,9 +1182,9 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
       ghi = fmax(ghi, d[i] + rad);
       tnorm = fmax(tnorm, fabs(d[i]) + rad);
    }
-   const double span0 = fmax(ghi - glo, 1e-300);
-   glo -= 1e-12 * span0 + 1e-300;
-   ghi += 1e-12 * span0 + 1e-300;
+   const hs_td_bracket br = hs_td_widen(glo, ghi);
+   const double span0 = br.span0;
+   glo = br.lo; ghi = br.hi;
    /* Sturm counts in product form on the matrix scaled to norm 1 (p_0 = 1, p_1 = d_0 - x, p_{i+1} = (d_i - x) p_i - e_{i-1}^2 p_{i-1};
     * a sign change = an eigenvalue below x, a zero takes the sign opposite to its predecessor; rescaled every fourth step): two
     * dependent operations per step where the quotient form of the small kernel has a division - 260 cycles per step, 640 us for the
@@ -1234,7 +1200,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
    __syncthreads();
    if ( tid < 8 )
    {
-      ds[n + tid] = 4.0;                                    /* rows behind the matrix: no coupling, no sign change (|x| <= 1) */
+      ds[n + tid] = 4.0;                                    /* (the rows hs_td_pad writes) */
       es[n - 1 + tid] = 0.0;
    }
    __syncthreads();
@@ -1263,7 +1229,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
          const double nhi = (below < S) ? lo + w * (double) (below + 1) : hi;
          lo = nlo; hi = nhi;
          /* (to two ulps of the eigenvalue - an interval cannot get shorter than one -, but not below half an ulp of the norm) */
-         if ( __all(k >= n || hi - lo <= 4.5e-16 * fmax(fmax(fabs(lo), fabs(hi)), 0.25)) )
+         if ( __all(k >= n || hs_td_converged(lo, hi)) )
             break;
       }
       if ( k < n && sh == 0 )
@@ -1293,9 +1259,7 @@ __device__ __forceinline__ void d_syev_mid(int n, const double* __restrict__ in,
    for (int idx = tid; idx < n * n; idx += EM_NT)
    {
       const int i = idx / n, k = idx - i * n;
-      unsigned h = (unsigned) (i * 2654435761u) ^ (unsigned) ((k + 1) * 40503u);
-      h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-      Z[i * ld + k] = 0.5 + (double) (h & 0xFFFF) * (1.0 / 65536.0);
+      Z[i * ld + k] = hs_td_start(i, k);
    }
    __syncthreads();
    for (int iter = 0; iter < 3; ++iter)

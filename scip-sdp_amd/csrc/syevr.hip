@@ -7,7 +7,7 @@
  *        k_syevr_values, ceil(n / 32) workgroups: every workgroup finds the places where T splits (SPLIT TABLE: row i belongs to
  *          the block [bs, be) of rows between two negligible off-diagonal entries) and computes the eigenvalues of 32 SLOTS: slot p
  *          is eigenvalue p - bs + 1 of the block that holds row p, found by Sturm multisection ON THAT BLOCK (ei_sturm_count_rows,
- *          16 shifts per slot and round, interval and stopping rule of k_syevx_values).  An eigenvalue therefore belongs to its
+ *          16 shifts per slot and round: hs_td_multisect of hs_tridiag.h, as k_syevx_values).  An eigenvalue therefore belongs to its
  *          block by construction, also when several blocks have it in common; a block of one row returns its diagonal entry.
  *        k_syevr_order, one workgroup: rank of every slot among all n (ties in the order of the slots) -> the ascending eigenvalues,
  *          and per eigenvalue its block and its CLUSTER: the run of eigenvalues OF THE SAME BLOCK each closer than 1e-3 ||T|| to
@@ -15,8 +15,8 @@
  *      Both tables stay in the workspace; nothing is read back.
  *   3. The eigenvectors of T, three rounds of
  *        k_syevr_step, ceil(n / 32) workgroups of 32 vectors: one step of inverse iteration per vector on the vector's block of T,
- *          one thread per elimination chain (partial pivoting, factors in device memory as [row][vector]) - the chain of
- *          k_syevx_tvec restated with a vector offset and a row range;
+ *          one thread per elimination chain (partial pivoting, factors in device memory as [row][vector]): hs_td_invit of
+ *          hs_tridiag.h, the chain of k_syevx_tvec on a range of rows;
  *        then per panel p of 32 consecutive eigenvalue indices, in the order of the panels,
  *        k_syevr_ortho_prev (A(p)), one workgroup per vector: classical Gram-Schmidt, twice, against the members of the vector's
  *          cluster in the panels before p - those are final for this round;
@@ -30,12 +30,11 @@
  * Launches: n for stage 1, 2 for stage 2, 3 + 6 ceil(n / 32) for stage 3, 1 for stage 4. */
 #include "hs_common.h"
 #include "hs_kernels.h"
-#include "hs_sturm.h"
-#include "hs_wave.h"
+#include "hs_tridiag.h"
 #include <cmath>
 
 #define SR_N   HS_SYEVX_MAXN
-#define SR_P   32                   /* vectors of a panel, slots of a workgroup of the eigenvalue kernel */
+#define SR_P   HS_SYEVX_MAXK        /* vectors of a panel, slots of a workgroup of the eigenvalue kernel */
 #define SR_T   512                  /* threads of the kernels of stages 2 and 3 */
 #define SR_BW  8                    /* wavefronts (= vectors) of a workgroup of the back-transformation */
 #define SR_BC  8                    /* reflectors staged in LDS at a time */
@@ -75,7 +74,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
 {
    __shared__ double ds[SR_N + 8], es[SR_N + 8], red[3][SR_T / 64];
    __shared__ int spl[SR_N], cntb[2][SR_P];
-   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int tid = threadIdx.x;
    double lo = 1e300, hi = -1e300, tn = 0.0, dt = 0.0, et = 0.0;
    if ( tid < n )
    {
@@ -86,31 +85,10 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
       hi = dt + rad;
       tn = fabs(dt) + rad;
    }
-#pragma unroll
-   for (int m = 1; m < 64; m <<= 1)
-   {
-      lo = fmin(lo, __shfl_xor(lo, m, 64));
-      hi = fmax(hi, __shfl_xor(hi, m, 64));
-      tn = fmax(tn, __shfl_xor(tn, m, 64));
-   }
-   if ( lane == 0 )
-   {
-      red[0][wave] = lo; red[1][wave] = hi; red[2][wave] = tn;
-   }
    if ( tid < 2 * SR_P )
       cntb[tid / SR_P][tid % SR_P] = 0;
-   __syncthreads();
-   double glo = red[0][0], ghi = red[1][0], tnorm = red[2][0];
-#pragma unroll
-   for (int w = 1; w < SR_T / 64; ++w)
-   {
-      glo = fmin(glo, red[0][w]); ghi = fmax(ghi, red[1][w]); tnorm = fmax(tnorm, red[2][w]);
-   }
-   const double span0 = fmax(ghi - glo, 1e-300);
-   glo -= 1e-12 * span0 + 1e-300;
-   ghi += 1e-12 * span0 + 1e-300;
-   tnorm = fmax(tnorm, 1e-300);
-   const double sinv = 1.0 / tnorm;
+   const hs_td_gersh g = hs_td_bounds<SR_T>(lo, hi, tn, red);
+   const double glo = g.lo, ghi = g.hi, span0 = g.span0, tnorm = g.tnorm, sinv = 1.0 / tnorm;
    /* T splits behind row j where |e_j| <= eps (|d_j| + |d_{j+1}|) (DSTEIN's test) or |e_j| <= 4 eps ||T|| (the absolute test of the
     * QR routines: the eigenvalues are asked for to a multiple of eps ||T||, and only this one separates the rows that the reduction
     * of a low-rank matrix leaves coupled by its rounding errors).  The scaled matrix has e_j = 0 there. */
@@ -123,11 +101,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
       ds[tid] = dt * sinv;
       es[tid] = s ? 0.0 : (et * sinv) * (et * sinv);
    }
-   if ( tid < 8 )
-   {
-      ds[n + tid] = 4.0;
-      es[n + tid] = 0.0;
-   }
+   hs_td_pad(ds, es, n, tid);
    __syncthreads();
    /* thread = (slot kk of this workgroup, one of 16 shifts) */
    const int S = SR_T / SR_P;
@@ -146,29 +120,11 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
    }
    const int rows = be - bs, ith = slot - bs + 1;
    const bool act = slot < n && rows > 1;
-   const double rS1 = 1.0 / (double) (S + 1);
-   lo = glo * sinv; hi = ghi * sinv;
-   for (int round = 0; round < 48; ++round)
-   {
-      const double w = (hi - lo) * rS1;
-      const double x = lo + w * (double) (sh + 1);
-      const int c = act ? ei_sturm_count_rows(ds + bs, es + bs, rows, x) : n;
-      if ( tid < SR_P )
-         cntb[(round + 1) & 1][tid] = 0;
-      /* (integer counts: the order of the additions does not matter) */
-      if ( act && c < ith )
-         atomicAdd(&cntb[round & 1][kk], 1);
-      __syncthreads();
-      const int b = act ? cntb[round & 1][kk] : 0;
-      const double nlo = lo + w * (double) b;
-      const double nhi = (b < S) ? lo + w * (double) (b + 1) : hi;
-      lo = nlo; hi = nhi;
-      if ( __syncthreads_and((!act || hi - lo <= 4.5e-16 * fmax(fmax(fabs(lo), fabs(hi)), 0.25)) ? 1 : 0) )
-         break;
-   }
+   const hs_td_interval iv = hs_td_multisect(S, kk, sh, act, ith, n, glo * sinv, ghi * sinv, cntb,
+      [=](double x) { return ei_sturm_count_rows(ds + bs, es + bs, rows, x); });
    if ( slot < n && sh == 0 )
    {
-      lamU[slot] = act ? 0.5 * (lo + hi) * tnorm : d[slot];
+      lamU[slot] = act ? 0.5 * (iv.lo + iv.hi) * tnorm : d[slot];
       bsU[slot] = bs;
       beU[slot] = be;
    }
@@ -263,11 +219,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_step(int n, int iter, const doub
       else if ( iter > 0 )
          z = Zg[(size_t) k * n + i];
       else
-      {
-         unsigned h = (unsigned) (i * 2654435761u) ^ (unsigned) ((k + 1) * 40503u);
-         h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-         z = 0.5 + (double) (h & 0xFFFF) * (1.0 / 65536.0);
-      }
+         z = hs_td_start(i, k);
       Z[t * ld + i] = z;
    }
    __syncthreads();
@@ -275,86 +227,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_step(int n, int iter, const doub
    if ( lane < SR_P / 8 && (lane << 3 | wave) < cnt && bhi[lane << 3 | wave] - blo[lane << 3 | wave] > 1 )
    {
       const int t = lane << 3 | wave;
-      const int r0 = blo[t], r1 = bhi[t];
-      double* z = Z + t * ld;
-      const double theta = th[t];
-      const double tiny = 1e-14 * fmax(span0, fmax(fabs(theta), 1e-300));
-      double dd = d[r0] - theta, du = e[r0];
-      double cur = z[r0];
-      for (int i = r0; i < r1 - 1; ++i)
-      {
-         const double dl = e[i];
-         const double dn = d[i + 1] - theta;
-         const double un = (i + 2 < r1) ? e[i + 1] : 0.0;
-         const double nxt = z[i + 1];
-         if ( fabs(dd) >= fabs(dl) || fabs(dl) < tiny )
-         {
-            if ( fabs(dd) < tiny ) dd = tiny;
-            const double rinv = 1.0 / dd;
-            const double mlt = dl * rinv;
-            G0[i * SR_P + t] = rinv; G1[i * SR_P + t] = du; G2[i * SR_P + t] = 0.0;
-            z[i] = cur;
-            cur = nxt - mlt * cur;
-            dd = dn - mlt * du;
-            du = un;
-         }
-         else
-         {
-            const double rinv = 1.0 / dl;
-            const double mlt = dd * rinv;
-            G0[i * SR_P + t] = rinv; G1[i * SR_P + t] = dn; G2[i * SR_P + t] = un;
-            z[i] = nxt;
-            cur = cur - mlt * nxt;
-            dd = du - mlt * dn;
-            du = -mlt * un;
-         }
-      }
-      if ( fabs(dd) < tiny ) dd = tiny;
-      double x1 = cur / dd, x2 = 0.0;
-      double nrm = x1 * x1;
-      z[r1 - 1] = x1;
-      /* backward sweep, the factors of eight rows on their way while the recurrence runs */
-      for (int i0 = r1 - 2; i0 >= r0; i0 -= 8)
-      {
-         double g0[8], g1[8], g2[8];
-#pragma unroll
-         for (int u = 0; u < 8; ++u)
-         {
-            const int i = (i0 - u >= r0) ? i0 - u : r0;
-            g0[u] = G0[i * SR_P + t];
-            g1[u] = G1[i * SR_P + t];
-            g2[u] = G2[i * SR_P + t];
-         }
-#pragma unroll
-         for (int u = 0; u < 8; ++u)
-         {
-            const int i = i0 - u;
-            if ( i >= r0 )
-            {
-               const double xi = (z[i] - g1[u] * x1 - g2[u] * x2) * g0[u];
-               z[i] = xi;
-               nrm += xi * xi;
-               x2 = x1; x1 = xi;
-               if ( !(nrm < 1e280) )
-               {
-                  const double sc1 = 1e-140;
-                  for (int q = i; q < r1; ++q)
-                     z[q] *= sc1;
-                  x1 *= sc1; x2 *= sc1; nrm *= sc1 * sc1;
-               }
-            }
-         }
-      }
-      double rn = 1.0 / sqrt(fmax(nrm, 1e-300));
-      if ( !(nrm > 0.0) || !(nrm < 1e300) )
-      {
-         const int one = r0 + (k0 + t) % (r1 - r0);
-         for (int i = r0; i < r1; ++i)
-            z[i] = (i == one) ? 1.0 : 0.0;
-         rn = 1.0;
-      }
-      for (int i = r0; i < r1; ++i)
-         z[i] *= rn;
+      hs_td_invit<SR_P, true>(Z + t * ld, d, e, blo[t], bhi[t], th[t], span0, G0, G1, G2, t, k0 + t);
    }
    __syncthreads();
    for (int idx = tid; idx < cnt * n; idx += SR_T)
@@ -555,16 +428,7 @@ __global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* 
    }
    if ( !have )
       return;
-   double nr = 0.0;
-#pragma unroll
-   for (int m = 0; m < SR_N / 64; ++m)
-      nr = fma(z[m], z[m], nr);
-   nr = hs_xsum<64>(nr);
-   const double rn = nr > 0.0 ? 1.0 / sqrt(nr) : 1.0;
-#pragma unroll
-   for (int m = 0; m < SR_N / 64; ++m)
-      if ( lane + 64 * m < n )
-         out[(size_t) k * n + lane + 64 * m] = z[m] * rn;
+   hs_td_store_unit(z, n, lane, out + (size_t) k * n);
 }
 
 }

@@ -18,18 +18,17 @@
  *      is therefore NOT updated in place by its owner (nobody needs it again: its content lives on as d_j, e_j and v_j in the
  *      reflector array); every other entry is read and written by its owner alone; p alternates between two buffers.
  *   2. The wanted eigenvalues by Sturm multisection on (d, e) in LDS (k_syevx_values): one workgroup, every thread counts at its own
- *      shift (ei_sturm_count), 512 / k shifts per wanted index and round, all intervals shrink together; stopping rule of
- *      k_syevi_mid.  For a bound: the count at the bound first, then the indices 1 .. min(count, maxk).
+ *      shift (ei_sturm_count), 512 / k shifts per wanted index and round, all intervals shrink together (hs_td_multisect,
+ *      hs_tridiag.h).  For a bound: the count at the bound first, then the indices 1 .. min(count, maxk).
  *   3. Their eigenvectors of the tridiagonal matrix by inverse iteration (k_syevx_tvec): one workgroup, one thread per vector for
- *      the elimination (spread over the wavefronts), three rounds of { one step, Gram-Schmidt twice inside the clusters of
- *      eigenvalues closer than 1e-3 ||T|| } as in k_syev_mid; only the RETURNED vectors are made orthonormal, so an index inside a
+ *      the elimination (spread over the wavefronts), three rounds of { one step (hs_td_invit, hs_tridiag.h), Gram-Schmidt twice
+ *      inside the clusters of eigenvalues closer than 1e-3 ||T|| }; only the RETURNED vectors are made orthonormal, so an index inside a
  *      cluster of hundreds of equal eigenvalues (low-rank matrices) costs what the k <= 32 wanted vectors cost.
  *   4. Back-transformation through the reflectors (k_syevx_back): one wavefront per vector, the reflectors read four ahead.
  * Every reduction runs in a fixed order (no floating-point atomics): the same input gives the same bits. */
 #include "hs_common.h"
 #include "hs_kernels.h"
-#include "hs_sturm.h"
-#include "hs_wave.h"
+#include "hs_tridiag.h"
 #include <cmath>
 
 #define SX_N   HS_SYEVX_MAXN
@@ -203,7 +202,7 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il
 {
    __shared__ double ds[SX_N + 8], es[SX_N + 8], red[3][SX_VT / 64];
    __shared__ int cntb[2][SX_K], sh_cnt, sh_nbelow;
-   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int tid = threadIdx.x;
    double lo = 1e300, hi = -1e300, tn = 0.0;
    if ( tid < n )
    {
@@ -212,42 +211,17 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il
       hi = d[tid] + rad;
       tn = fabs(d[tid]) + rad;
    }
-#pragma unroll
-   for (int m = 1; m < 64; m <<= 1)
-   {
-      lo = fmin(lo, __shfl_xor(lo, m, 64));
-      hi = fmax(hi, __shfl_xor(hi, m, 64));
-      tn = fmax(tn, __shfl_xor(tn, m, 64));
-   }
-   if ( lane == 0 )
-   {
-      red[0][wave] = lo; red[1][wave] = hi; red[2][wave] = tn;
-   }
    if ( tid < 2 * SX_K )
       cntb[tid / SX_K][tid % SX_K] = 0;
-   __syncthreads();
-   double glo = red[0][0], ghi = red[1][0], tnorm = red[2][0];
-#pragma unroll
-   for (int w = 1; w < SX_VT / 64; ++w)
-   {
-      glo = fmin(glo, red[0][w]); ghi = fmax(ghi, red[1][w]); tnorm = fmax(tnorm, red[2][w]);
-   }
-   const double span0 = fmax(ghi - glo, 1e-300);
-   glo -= 1e-12 * span0 + 1e-300;
-   ghi += 1e-12 * span0 + 1e-300;
-   tnorm = fmax(tnorm, 1e-300);
-   const double sinv = 1.0 / tnorm;
-   /* the matrix scaled to norm <= 1 for the counts in product form, padded as ei_sturm_count asks */
+   const hs_td_gersh g = hs_td_bounds<SX_VT>(lo, hi, tn, red);
+   const double glo = g.lo, ghi = g.hi, span0 = g.span0, tnorm = g.tnorm, sinv = 1.0 / tnorm;
+   /* the matrix scaled to norm <= 1 for the counts in product form */
    if ( tid < n )
    {
       ds[tid] = d[tid] * sinv;
       es[tid] = (tid + 1 < n) ? (e[tid] * sinv) * (e[tid] * sinv) : 0.0;
    }
-   if ( tid < 8 )
-   {
-      ds[n + tid] = 4.0;
-      es[n + tid] = 0.0;
-   }
+   hs_td_pad(ds, es, n, tid);
    __syncthreads();
    const int nb = (n - 1 + 3) >> 2;
    if ( tid == 0 )
@@ -282,32 +256,13 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il
    const int kk = tid >> lgS, sh = tid & (S - 1);
    const bool act = kk < cnt;
    const int ith = k0 + kk;
-   const double rS1 = 1.0 / (double) (S + 1);
-   lo = glo * sinv; hi = ghi * sinv;
-   for (int round = 0; round < 48; ++round)
-   {
-      const double w = (hi - lo) * rS1;
-      const double x = lo + w * (double) (sh + 1);
-      const int c = act ? ei_sturm_count(ds, es, nb, x) : n;
-      if ( tid < SX_K )
-         cntb[(round + 1) & 1][tid] = 0;
-      /* (integer counts: the order of the additions does not matter) */
-      if ( act && c < ith )
-         atomicAdd(&cntb[round & 1][kk], 1);
-      __syncthreads();
-      const int b = act ? cntb[round & 1][kk] : 0;         /* index of the subinterval that holds eigenvalue ith */
-      const double nlo = lo + w * (double) b;
-      const double nhi = (b < S) ? lo + w * (double) (b + 1) : hi;
-      lo = nlo; hi = nhi;
-      /* (to two ulps of the eigenvalue, but not below half an ulp of the norm: the rule of k_syevi_mid) */
-      if ( __syncthreads_and((!act || hi - lo <= 4.5e-16 * fmax(fmax(fabs(lo), fabs(hi)), 0.25)) ? 1 : 0) )
-         break;
-   }
+   const hs_td_interval iv = hs_td_multisect(S, kk, sh, act, ith, n, glo * sinv, ghi * sinv, cntb,
+      [=](double x) { return ei_sturm_count(ds, es, nb, x); });
    /* every index is searched in an interval of its own: the midpoints of a multiple eigenvalue may differ in the last place, in either
     * order.  Ascending as promised: the running maximum (changes nothing where the values ascend already; ds is free by now) */
    __syncthreads();
    if ( act && sh == 0 )
-      ds[kk] = 0.5 * (lo + hi) * tnorm;
+      ds[kk] = 0.5 * (iv.lo + iv.hi) * tnorm;
    __syncthreads();
    if ( tid < cnt )
    {
@@ -351,97 +306,18 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __res
    for (int idx = tid; idx < cnt * n; idx += SX_VT)
    {
       const int k = idx / n, i = idx - k * n;
-      unsigned h = (unsigned) (i * 2654435761u) ^ (unsigned) ((k + 1) * 40503u);
-      h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-      Z[k * ld + i] = 0.5 + (double) (h & 0xFFFF) * (1.0 / 65536.0);
+      Z[k * ld + i] = hs_td_start(i, k);
    }
    __syncthreads();
 
    for (int iter = 0; iter < 3; ++iter)
    {
-      /* one step of inverse iteration per vector: Gaussian elimination of T - theta I with partial pivoting, thread (wavefront k mod 8,
-       * lane k / 8) owns vector k - the 32 serial chains spread over the wavefronts; factors in device memory as [row][vector] */
+      /* one step of inverse iteration per vector (hs_td_invit): thread (wavefront k mod 8, lane k / 8) owns vector k - the 32 serial
+       * chains spread over the wavefronts; factors in device memory as [row][vector] */
       if ( lane < SX_K / 8 && (lane << 3 | wave) < cnt )
       {
          const int k = lane << 3 | wave;
-         double* z = Z + k * ld;
-         const double theta = th[k];
-         const double tiny = 1e-14 * fmax(span0, fmax(fabs(theta), 1e-300));
-         double dd = d[0] - theta, du = e[0];
-         double cur = z[0];
-         for (int i = 0; i < n - 1; ++i)
-         {
-            const double dl = e[i];
-            const double dn = d[i + 1] - theta;
-            const double un = (i + 2 < n) ? e[i + 1] : 0.0;
-            const double nxt = z[i + 1];
-            if ( fabs(dd) >= fabs(dl) || fabs(dl) < tiny )
-            {
-               if ( fabs(dd) < tiny ) dd = tiny;
-               const double rinv = 1.0 / dd;
-               const double mlt = dl * rinv;
-               G0[i * SX_K + k] = rinv; G1[i * SX_K + k] = du; G2[i * SX_K + k] = 0.0;
-               z[i] = cur;
-               cur = nxt - mlt * cur;
-               dd = dn - mlt * du;
-               du = un;
-            }
-            else
-            {
-               const double rinv = 1.0 / dl;
-               const double mlt = dd * rinv;
-               G0[i * SX_K + k] = rinv; G1[i * SX_K + k] = dn; G2[i * SX_K + k] = un;
-               z[i] = nxt;
-               cur = cur - mlt * nxt;
-               dd = du - mlt * dn;
-               du = -mlt * un;
-            }
-         }
-         if ( fabs(dd) < tiny ) dd = tiny;
-         double x1 = cur / dd, x2 = 0.0;
-         double nrm = x1 * x1;
-         z[n - 1] = x1;
-         /* backward sweep, the factors of eight rows on their way while the recurrence runs */
-         for (int i0 = n - 2; i0 >= 0; i0 -= 8)
-         {
-            double g0[8], g1[8], g2[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-            {
-               const int i = (i0 - u >= 0) ? i0 - u : 0;
-               g0[u] = G0[i * SX_K + k];
-               g1[u] = G1[i * SX_K + k];
-               g2[u] = G2[i * SX_K + k];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-            {
-               const int i = i0 - u;
-               if ( i >= 0 )
-               {
-                  const double xi = (z[i] - g1[u] * x1 - g2[u] * x2) * g0[u];
-                  z[i] = xi;
-                  nrm += xi * xi;
-                  x2 = x1; x1 = xi;
-                  if ( !(nrm < 1e280) )
-                  {
-                     const double sc1 = 1e-140;
-                     for (int q = i; q < n; ++q)
-                        z[q] *= sc1;
-                     x1 *= sc1; x2 *= sc1; nrm *= sc1 * sc1;
-                  }
-               }
-            }
-         }
-         double rn = 1.0 / sqrt(fmax(nrm, 1e-300));
-         if ( !(nrm > 0.0) || !(nrm < 1e300) )
-         {
-            for (int i = 0; i < n; ++i)
-               z[i] = (i == k) ? 1.0 : 0.0;
-            rn = 1.0;
-         }
-         for (int i = 0; i < n; ++i)
-            z[i] *= rn;
+         hs_td_invit<SX_K, false>(Z + k * ld, d, e, 0, n, th[k], span0, G0, G1, G2, k, k);
       }
       __syncthreads();
 
@@ -537,16 +413,7 @@ __global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restri
          }
       }
    }
-   double nr = 0.0;
-#pragma unroll
-   for (int m = 0; m < SX_N / 64; ++m)
-      nr = fma(z[m], z[m], nr);
-   nr = hs_xsum<64>(nr);
-   const double rn = nr > 0.0 ? 1.0 / sqrt(nr) : 1.0;
-#pragma unroll
-   for (int m = 0; m < SX_N / 64; ++m)
-      if ( lane + 64 * m < n )
-         out[HS_SYEVX_OUT_VEC + (size_t) k * n + lane + 64 * m] = z[m] * rn;
+   hs_td_store_unit(z, n, lane, out + HS_SYEVX_OUT_VEC + (size_t) k * n);
 }
 
 }
