@@ -364,6 +364,36 @@ HIPSDP_API int hipsdp_syevr(int device, int n, const double* A, double* lam, dou
  * cap = length of the output arrays; *nnz_out = entries produced (when it exceeds cap: HIPSDP_ERR_ARG, nothing is written). */
 HIPSDP_API int  hipsdp_psd_project(int device, int n, int nnz, const int* row, const int* col, const double* val, double minev, double epsilon,
    int mode, int cap, int* nnz_out, int* rowout, int* colout, double* valout);
+/* The projections of ALL blocks of a node - or of many nodes - in one call: the warm-start producer projects Z and X of every block
+ * (relax_sdp.c:2680-2774 and :3405-3445 loop over the blocks), 2 B projections for B blocks.  Job j is exactly
+ * hipsdp_psd_project(device, n, nnz, row, col, val, minev, epsilon, mode, cap, &nnz_out, rowout, colout, valout): mode 0 the literal
+ * chain, mode 1 the spectral form, entries with row <= col and |value| > epsilon in row-major order, an eigenvalue lam is raised
+ * when lam - minev < -epsilon.  A job that does not fit its cap gets the needed length in nnz_out and nothing written; the other jobs
+ * are written normally and the call returns HIPSDP_ERR_ARG.
+ * Jobs of at most 128 rows are BATCHED: whatever their number, the call issues one upload (job table and all triplets through the
+ * calling thread's pinned staging), one launch that expands all matrices, at most three for the decompositions, one that recombines
+ * and counts, one that writes the packed result, and one device->host synchronisation (csrc/psd_many.hip).  A job above 128 rows
+ * takes, inside the same call, the chain of hipsdp_psd_project and returns its bits.  A batched job returns the same bits whatever
+ * count is, whatever the other jobs are and wherever it stands in the array (its values agree with hipsdp_psd_project's to rounding:
+ * the recombination sums in index order by fma instead of through the GEMM).
+ * HIPSDP_ERR_ARG, checked on the host before anything is launched: count < 0 or count > HIPSDP_PSD_MANY_MAXJOBS, jobs NULL with
+ * count > 0, device < 0, a mode other than 0 / 1, and per job n < 1, nnz < 0, cap < 0, a triplet index outside the matrix, a NULL
+ * array where the length (nnz, cap) is positive.  count == 0: HIPSDP_OK, nothing launched.
+ * Outside the contract, as for hipsdp_psd_project: a position that appears twice in a job's triplets.
+ * Two host threads may call it at the same time (contexts are thread-local). */
+#define HIPSDP_PSD_MANY_MAXJOBS 1024
+typedef struct hipsdp_psd_job {
+   int n, nnz;                       /* in: order of the matrix; triplets (both triangles are filled, as hipsdp_psd_project) */
+   const int *row, *col; const double* val;
+   double minev;                     /* in: per job (the reference uses warmstartmevdual for Z, warmstartmevprimal for X) */
+   int cap;                          /* in: length of rowout / colout / valout */
+   int nnz_out;                      /* out: entries the projection has (the needed length when it exceeds cap) */
+   int *rowout, *colout; double* valout;
+} hipsdp_psd_job;
+HIPSDP_API int hipsdp_psd_project_many(int device, int count, hipsdp_psd_job* jobs, double epsilon, int mode);
+/* process totals: calls with count > 0 that passed the argument checks, kernel launches they issued for batched jobs, device->host
+ * synchronisations they waited on (one for all batched jobs of a call, one more per job above 128 rows); any pointer may be NULL */
+HIPSDP_API int hipsdp_psd_project_many_stats(long long* calls, long long* launches, long long* readbacks);
 HIPSDP_API int  hipsdp_gemv_n(int device, int R, long long E, const double* A, int nv, const double* V, double* out);
 HIPSDP_API int  hipsdp_gemv_t(int device, int R, long long E, const double* A, const double* coef, double* out);
 

@@ -618,3 +618,39 @@ def psd_project(n, row, col, val, minev, epsilon=1e-9, mode=0, device=0):
     _chk(lib().hipsdp_psd_project(device, n, len(val), _ip(row), _ip(col), _dp(val), C.c_double(minev), C.c_double(epsilon), mode,
                                   cap, C.byref(k), _ip(ro), _ip(co), _dp(vo)), "hipsdp_psd_project")
     return ro[:k.value], co[:k.value], vo[:k.value]
+
+
+class PsdJob(C.Structure):
+    """hipsdp_psd_job of include/hipsdp.h, field for field"""
+    _fields_ = [("n", C.c_int), ("nnz", C.c_int), ("row", C.POINTER(C.c_int)), ("col", C.POINTER(C.c_int)),
+                ("val", C.POINTER(C.c_double)), ("minev", C.c_double), ("cap", C.c_int), ("nnz_out", C.c_int),
+                ("rowout", C.POINTER(C.c_int)), ("colout", C.POINTER(C.c_int)), ("valout", C.POINTER(C.c_double))]
+
+
+def psd_project_many(jobs, epsilon=1e-9, mode=0, device=0):
+    """hipsdp_psd_project_many: jobs is a list of (n, row, col, val, minev); returns the list of (row, col, val) psd_project returns
+    for each of them, from one call (cap = n (n + 1) / 2 per job)"""
+    count = len(jobs)
+    tab = (PsdJob * max(count, 1))()
+    keep = []
+    for j, (n, row, col, val, minev) in enumerate(jobs):
+        row = np.ascontiguousarray(row, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = _f64(val)
+        cap = n * (n + 1) // 2
+        ro = np.zeros(cap, dtype=np.int32)
+        co = np.zeros(cap, dtype=np.int32)
+        vo = np.zeros(cap)
+        keep.append((row, col, val, ro, co, vo))
+        tab[j].n, tab[j].nnz, tab[j].minev, tab[j].cap = n, len(val), minev, cap
+        tab[j].row, tab[j].col, tab[j].val = _ip(row), _ip(col), _dp(val)
+        tab[j].rowout, tab[j].colout, tab[j].valout = _ip(ro), _ip(co), _dp(vo)
+    _chk(lib().hipsdp_psd_project_many(device, count, tab, C.c_double(epsilon), mode), "hipsdp_psd_project_many")
+    return [(k[3][:tab[j].nnz_out], k[4][:tab[j].nnz_out], k[5][:tab[j].nnz_out]) for j, k in enumerate(keep)]
+
+
+def psd_project_many_stats():
+    """process totals of hipsdp_psd_project_many: (calls, kernel launches issued for batched jobs, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_psd_project_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_psd_project_many_stats")
+    return calls.value, launches.value, readbacks.value

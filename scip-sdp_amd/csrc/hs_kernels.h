@@ -250,6 +250,10 @@ long long hs_syev_many_vecpos(int n);
 int hs_syev_many_class(int n);
 int hs_syev_small_many(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* jobs, int* launches);
 
+/* psd.hip: the PSD projection chain of one matrix on host buffers (arguments and results of hipsdp_psd_project, which is this) */
+int hs_psd_project_one(int device, int n, int nnz, const int* row, const int* col, const double* val, double minev,
+   double epsilon, int mode, int cap, int* nnz_out, int* rowout, int* colout, double* valout);
+
 /* ---- eigcuts.hip: the separation round of all blocks (hipsdp_eigencuts_all) ------------------------------------------------- */
 #define HS_EC_DENSE  0     /* A: (m + 1) rows of n^2 */
 #define HS_EC_PACKED 1     /* A: (m + 1) rows of Lp, entry (r, c), c <= r, at r (r + 1) / 2 + c */

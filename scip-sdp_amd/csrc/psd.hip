@@ -205,7 +205,8 @@ template<class T> struct PoolBuf
 
 }
 
-extern "C" int hipsdp_psd_project(int device, int n, int nnz, const int* row, const int* col, const double* val, double minev,
+/* one projection, the body of hipsdp_psd_project; hipsdp_psd_project_many (psd_many.hip) sends its jobs above 128 rows here */
+int hs_psd_project_one(int device, int n, int nnz, const int* row, const int* col, const double* val, double minev,
    double epsilon, int mode, int cap, int* nnz_out, int* rowout, int* colout, double* valout)
 {
    int nd = 0;
@@ -321,4 +322,10 @@ extern "C" int hipsdp_psd_project(int device, int n, int nnz, const int* row, co
       HS_CALL( d2h_through_staging(device, st, valout, oval.p, (size_t) total * sizeof(double)) );
    }
    return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_psd_project(int device, int n, int nnz, const int* row, const int* col, const double* val, double minev,
+   double epsilon, int mode, int cap, int* nnz_out, int* rowout, int* colout, double* valout)
+{
+   return hs_psd_project_one(device, n, nnz, row, col, val, minev, epsilon, mode, cap, nnz_out, rowout, colout, valout);
 }
