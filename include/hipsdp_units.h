@@ -58,6 +58,20 @@ HIPSDP_API int  hipsdp_potrf(int device, int n, double* A, int* fail);          
  * semidefinite pivot rule with diag0 = diag(A), forced pivots in regmask[n]; dinv[ceil(n / 64) * 4096] (any output may be NULL) */
 HIPSDP_API int  hipsdp_potrf_ex(int device, int n, double* A, int psd, int v1, double* dinv, int* regmask, int* fail);
 HIPSDP_API int  hipsdp_potrs(int device, int n, const double* A, int nrhs, double* rhs);     /* factor + solve, rhs[k * n + i] */
+/* one factorization of A (psd = 0: hs_potrf; 1: hs_potrf_psd with diag0 = diag(A) and a mask, as hipsdp_potrf_ex), then ncalls solves one
+ * behind the other on ONE hs_trsv_sync workspace with one epoch counter, as the engine issues them: call c has nrhs[c] in 1..4 right-hand
+ * sides and mode[c] in {3, 5, 6, 7} (1 forward + 2 backward + 4 corrected) and runs in place on slab c of rhs (row k of the slab at
+ * rhs[(4 c + k) n]).  Anything else: HIPSDP_ERR_ARG before the first launch.  regmask[n] (may be NULL): the zeroed columns (psd = 1);
+ * *fail: the factorization flag.  HIPSDP_ERR_NUMERIC when a solve set the error word of the workspace */
+HIPSDP_API int  hipsdp_potrs_seq(int device, int n, const double* A, int psd, int ncalls, const int* nrhs, const int* mode, double* rhs,
+   int* regmask, int* fail);
+/* the fused single-block factorization of base + alpha dir (dir may be NULL), 1 <= n <= 64: pair = 0 one problem through
+ * hs_potrf_small_ext, pair = 1 two problems of n rows, one behind the other in every array, through hs_potrf_small_ext_pair.  L (upper
+ * triangle zeroed), Mout, Linv, Gram: n x n each, dinv: 4096 each, flag: one word each, cleared before the launch (set_flag as in
+ * hs_potrf_psd); Mout, Linv may be NULL; Gram (the inverse of the matrix) only with want_gram = 1, which n > 32 answers with
+ * HIPSDP_ERR_ARG as the engine function does */
+HIPSDP_API int  hipsdp_potrf_small_unit(int device, int n, int pair, const double* base, const double* dir, double alpha, int set_flag,
+   int want_gram, double* L, double* dinv, double* Mout, double* Linv, double* Gram, int* flag);
 HIPSDP_API int  hipsdp_trtri(int device, int n, const double* A, double* Linv);              /* A spd -> inverse of its Cholesky factor */
 HIPSDP_API int  hipsdp_lambda_min(int device, int n, const double* W, int steps, double* theta, double* resid);
 /* lambda_min(L D L^T), n <= 64, L lower triangular, D symmetric: the small-block step-length kernels; theta[2], resid[2] */

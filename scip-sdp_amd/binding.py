@@ -503,6 +503,46 @@ def potrs(A, rhs, device=0):
     return r2.reshape(r.shape)
 
 
+def potrs_seq(A, calls, psd=False, device=0):
+    """one factorization, then the solves of `calls` = [(mode, rhs[k, n]), ...] one behind the other on ONE hs_trsv_sync workspace
+    -> (list of solved rhs, zeroed-column mask, fail)"""
+    A = _f64(A)
+    n = A.shape[0]
+    nc = len(calls)
+    slab = np.zeros((max(nc, 1), 4, n))
+    nrhs = np.zeros(max(nc, 1), dtype=np.int32)
+    mode = np.zeros(max(nc, 1), dtype=np.int32)
+    for c, (md, r) in enumerate(calls):
+        r = _f64(r).reshape(-1, n)
+        nrhs[c], mode[c] = r.shape[0], md
+        slab[c, :min(r.shape[0], 4)] = r[:4]
+    mask = np.zeros(n, dtype=np.int32)
+    fail = C.c_int(0)
+    _chk(ulib().hipsdp_potrs_seq(device, n, _dp(A), int(psd), nc, _ip(nrhs), _ip(mode), _dp(slab), _ip(mask), C.byref(fail)),
+         "hipsdp_potrs_seq")
+    return [slab[c, :nrhs[c]].copy() for c in range(nc)], mask, fail.value
+
+
+def potrf_small_unit(base, dir=None, alpha=0.0, pair=False, set_flag=False, want_gram=False, device=0):
+    """fused single-block factorization of base + alpha dir; pair: base (and dir) hold two problems [2, n, n]
+    -> dict(L, dinv, Mout, Linv, Gram or None, flag) with a leading axis of 2 when pair"""
+    base = _f64(base)
+    n = base.shape[-1]
+    npb = 2 if pair else 1
+    assert base.size == npb * n * n
+    d = None if dir is None else _f64(dir)
+    assert d is None or d.size == base.size
+    shp = (2, n, n) if pair else (n, n)
+    out = {"L": np.zeros(shp), "dinv": np.zeros((2, 64, 64) if pair else (64, 64)), "Mout": np.zeros(shp), "Linv": np.zeros(shp),
+           "Gram": np.zeros(shp) if want_gram else None}
+    flag = np.zeros(2, dtype=np.int32)
+    _chk(ulib().hipsdp_potrf_small_unit(device, n, int(pair), _dp(base), None if d is None else _dp(d), C.c_double(alpha), int(set_flag),
+                                        int(want_gram), _dp(out["L"]), _dp(out["dinv"]), _dp(out["Mout"]), _dp(out["Linv"]),
+                                        None if not want_gram else _dp(out["Gram"]), _ip(flag)), "hipsdp_potrf_small_unit")
+    out["flag"] = flag.copy() if pair else int(flag[0])
+    return out
+
+
 def trtri(A, device=0):
     A = _f64(A)
     Li = np.zeros_like(A)

@@ -655,6 +655,109 @@ extern "C" int hipsdp_potrs(int device, int n, const double* A, int nrhs, double
    return hflag == 0 ? HIPSDP_OK : HIPSDP_ERR_NUMERIC;
 }
 
+/* test entry: ONE factorization (psd = 0: hs_potrf; 1: hs_potrf_psd with diag0 = the matrix diagonal and a mask, as hipsdp_potrf_ex
+ * sets it up), ONE workspace of hs_trsv_sync with one epoch counter, then ncalls solves one behind the other on that workspace, as
+ * the engine issues them through a whole interior-point solve: call c takes nrhs[c] right-hand sides in mode[c], in place on slab c
+ * of rhs (4 rows of n doubles per slab) */
+extern "C" int hipsdp_potrs_seq(int device, int n, const double* A, int psd, int ncalls, const int* nrhs, const int* mode, double* rhs,
+   int* regmask, int* fail)
+{
+   if ( n <= 0 || A == NULL || ncalls < 0 || (psd != 0 && psd != 1) || (ncalls > 0 && (nrhs == NULL || mode == NULL || rhs == NULL)) )
+      return HIPSDP_ERR_ARG;
+   for (int c = 0; c < ncalls; ++c)
+      if ( nrhs[c] < 1 || nrhs[c] > 4 || (mode[c] != 3 && mode[c] != 5 && mode[c] != 6 && mode[c] != 7) )
+         return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   const long long nr = (long long) ncalls * 4 * n;
+   DevBuf dA, dD, dG, dR;
+   int* dint = NULL;
+   int* dsync = NULL;
+   HS_CALL( dA.alloc(n2) ); HS_CALL( dD.alloc(hs_potrf_dinv_len(n)) ); HS_CALL( dG.alloc(n) ); HS_CALL( dR.alloc(nr) );
+   HS_CALL( dA.up(A, n2) ); HS_CALL( dR.up(rhs, nr) );
+   std::vector<double> dg(n);
+   for (int i = 0; i < n; ++i) dg[i] = A[(long long) i * n + i];
+   HS_CALL( dG.up(dg.data(), n) );
+   std::vector<int> hint(n + 1, 0);
+   int gaveup = 0;                   /* the error word of the workspace: a block of a solve left without its predecessors' entries */
+   int epoch = 0;
+   int rc = HS_OK;
+   /* from here on every path goes through the two hipFree below */
+   if ( hipMalloc((void**) &dint, (size_t) (n + 1) * sizeof(int)) != hipSuccess
+         || hipMalloc((void**) &dsync, (size_t) hs_trsv_sync_ws(n) * sizeof(int)) != hipSuccess
+         || hipMemset(dint, 0, (size_t) (n + 1) * sizeof(int)) != hipSuccess )
+      rc = HS_ERR_HIP;
+   if ( rc == HS_OK ) rc = hs_trsv_sync_init(0, n, dsync, &epoch);
+   if ( rc == HS_OK ) rc = hs_potrf_psd(0, n, dA.p, dD.p, dint, psd ? dG.p : NULL, psd ? dint + 1 : NULL, 0);
+   for (int c = 0; c < ncalls && rc == HS_OK; ++c)
+      rc = hs_trsv_sync(0, n, dA.p, dD.p, nrhs[c], dR.p + (long long) c * 4 * n, n, mode[c], dsync, &epoch);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   if ( rc == HS_OK && hipMemcpy(hint.data(), dint, (size_t) (n + 1) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ) rc = HS_ERR_HIP;
+   if ( rc == HS_OK && hipMemcpy(&gaveup, dsync, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ) rc = HS_ERR_HIP;
+   if ( rc == HS_OK ) rc = dR.down(rhs, nr);
+   (void) hipFree(dsync);
+   (void) hipFree(dint);
+   HS_CALL( rc );
+   if ( fail != NULL ) *fail = hint[0];
+   if ( regmask != NULL )
+      for (int i = 0; i < n; ++i) regmask[i] = psd ? hint[1 + i] : 0;
+   return gaveup == 0 ? HIPSDP_OK : HIPSDP_ERR_NUMERIC;
+}
+
+/* test entry: the fused single-block factorization of base + alpha * dir (n <= 64) with all its outputs, through hs_potrf_small_ext
+ * (pair = 0) or - two problems of n rows laid one behind the other in every array - through hs_potrf_small_ext_pair (pair = 1).  L, Mout,
+ * Linv, Gram: n x n per problem, dinv: 4096 per problem, flag: one word per problem, cleared before the launch; dir, Mout, Linv and Gram
+ * may be NULL, Gram is written only when want_gram = 1 (n <= 32) */
+extern "C" int hipsdp_potrf_small_unit(int device, int n, int pair, const double* base, const double* dir, double alpha, int set_flag,
+   int want_gram, double* L, double* dinv, double* Mout, double* Linv, double* Gram, int* flag)
+{
+   if ( n < 1 || n > 64 || (pair != 0 && pair != 1) || base == NULL || L == NULL || dinv == NULL || flag == NULL
+         || (set_flag != 0 && set_flag != 1) || (want_gram != 0 && want_gram != 1) || (want_gram && (n > 32 || Gram == NULL)) )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const int np = pair ? 2 : 1;
+   const long long n2 = (long long) n * n;
+   DevBuf dB, dR, dL, dD, dM, dI, dG;
+   int* dflag = NULL;
+   HS_CALL( dB.alloc(np * n2) ); HS_CALL( dR.alloc(np * n2) ); HS_CALL( dL.alloc(np * n2) ); HS_CALL( dD.alloc(np * 4096) );
+   HS_CALL( dM.alloc(np * n2) ); HS_CALL( dI.alloc(np * n2) ); HS_CALL( dG.alloc(np * n2) );
+   HS_HIP( hipMalloc((void**) &dflag, 2 * sizeof(int)) );
+   HS_HIP( hipMemset(dflag, 0, 2 * sizeof(int)) );
+   /* every output starts as NaN: what the kernel does not write shows */
+   HS_HIP( hipMemset(dL.p, 0xFF, (size_t) (np * n2) * sizeof(double)) ); HS_HIP( hipMemset(dD.p, 0xFF, (size_t) (np * 4096) * sizeof(double)) );
+   HS_HIP( hipMemset(dM.p, 0xFF, (size_t) (np * n2) * sizeof(double)) ); HS_HIP( hipMemset(dI.p, 0xFF, (size_t) (np * n2) * sizeof(double)) );
+   HS_HIP( hipMemset(dG.p, 0xFF, (size_t) (np * n2) * sizeof(double)) );
+   HS_CALL( dB.up(base, np * n2) );
+   if ( dir != NULL ) HS_CALL( dR.up(dir, np * n2) );
+   int rc;
+   if ( !pair )
+      rc = hs_potrf_small_ext(0, n, dL.p, dD.p, dflag, dB.p, dir != NULL ? dR.p : NULL, alpha, Mout != NULL ? dM.p : NULL,
+         Linv != NULL ? dI.p : NULL, want_gram ? dG.p : NULL, set_flag);
+   else
+   {
+      double* pL[2] = {dL.p, dL.p + n2};
+      double* pD[2] = {dD.p, dD.p + 4096};
+      int* pF[2] = {dflag, dflag + 1};
+      const double* pB[2] = {dB.p, dB.p + n2};
+      const double* pR[2] = {dir != NULL ? dR.p : NULL, dir != NULL ? dR.p + n2 : NULL};
+      double* pM[2] = {Mout != NULL ? dM.p : NULL, Mout != NULL ? dM.p + n2 : NULL};
+      double* pI[2] = {Linv != NULL ? dI.p : NULL, Linv != NULL ? dI.p + n2 : NULL};
+      double* pG[2] = {want_gram ? dG.p : NULL, want_gram ? dG.p + n2 : NULL};
+      rc = hs_potrf_small_ext_pair(0, n, pL, pD, pF, pB, pR, alpha, pM, pI, pG, set_flag);
+   }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   int hflag[2] = {0, 0};
+   if ( rc == HS_OK && hipMemcpy(hflag, dflag, 2 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ) rc = HS_ERR_HIP;
+   (void) hipFree(dflag);
+   HS_CALL( rc );
+   HS_CALL( dL.down(L, np * n2) ); HS_CALL( dD.down(dinv, np * 4096) );
+   if ( Mout != NULL ) HS_CALL( dM.down(Mout, np * n2) );
+   if ( Linv != NULL ) HS_CALL( dI.down(Linv, np * n2) );
+   if ( want_gram ) HS_CALL( dG.down(Gram, np * n2) );
+   for (int k = 0; k < np; ++k) flag[k] = hflag[k];
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_trtri(int device, int n, const double* A, double* Linv)
 {
    HS_CALL( pick_device(device) );
