@@ -72,6 +72,35 @@ HIPSDP_API int  hipsdp_potrs_seq(int device, int n, const double* A, int psd, in
  * HIPSDP_ERR_ARG as the engine function does */
 HIPSDP_API int  hipsdp_potrf_small_unit(int device, int n, int pair, const double* base, const double* dir, double alpha, int set_flag,
    int want_gram, double* L, double* dinv, double* Mout, double* Linv, double* Gram, int* flag);
+/* strict-mode factorization of two matrices of n rows, one behind the other in A: pair = 1 through hs_potrf_pair (n > 64: one launch per
+ * block column for both), 0 through two calls of hs_potrf.  dinv: hipsdp_potrf_dinv_len(n) doubles per matrix (inverses of the diagonal
+ * blocks, then the staging blocks of the block-column kernel; zero where nothing is written), fail[2]: the flag of each matrix */
+HIPSDP_API long long hipsdp_potrf_dinv_len(int n);
+HIPSDP_API int  hipsdp_potrf_pair_unit(int device, int n, int pair, double* A, double* dinv, int* fail);
+/* the trial iterates X + alpha dX, Z + alpha dZ of a step with the saved iterate and the copies the Cholesky check factors: io = X, Z, dX,
+ * dZ, Xs, Zs, Lx, Lz (n x n each, all read, all but dX and dZ come back); fused = 1: hs_trial_pair, 0: the hs_copy / hs_scale_add /
+ * hs_copy launches it replaces; first = 1: first attempt (base X, Z, saved on the way), 0: halved step (base Xs, Zs) */
+HIPSDP_API int  hipsdp_trial_pair_unit(int device, int n, int fused, int first, double alpha, double* io);
+/* The merged launches between two Schur assemblies on the general path, each against the launches it replaces (fused = 1 / 0); outputs
+ * that a form does not write come back as NaN.  Lp = n (n + 1) / 2 rounded up to even, the packed lower triangle.
+ * after_solve2: rhs2[2 m], u1[m] -> u2[m], wt[m + 1], e2[m + 1] = [1; u2], e1[m + 1] = [0; u1] (k_after_solve2 + hs_make_ext twice).
+ * unpack3: pk[3][Lp] -> out[3][n][n] (hs_unpack_sym three times).  dz: pk[Lp], P2, Rd, dtau, eta -> dZ = (unpack(pk) - dtau P2) + eta Rd
+ * (hs_unpack_sym + k_dz_combine).  dirmat: H = s1 Zinv - X - sym(GZ) and its packed, weighted copy pk[Lp] (hs_dirmat + hs_pack_weighted).
+ * dir: the scalars of a direction and its closing kernel through the engine's own function, one block of n rows, m variables: B, H [n][n];
+ * rhs2, rp, b, u1, u2 [m]; par = eta, rg, sigmu, tau, kappa, etk; sc[hipsdp_tail_sc_len()] read and written; dy[m], dyt[m + 1].
+ * dots: out[0] = <a0, a1> + <a0, a2>, out[1] = <a2, a2> over n^2 entries and out[2] = <v0, v1> over m inside one batch of deferred
+ * reductions (hs_dot against hs_dot_deferred); a[3][n^2], v[2][m], out[3] */
+HIPSDP_API int  hipsdp_tail_after_solve2_unit(int device, int m, int fused, const double* rhs2, const double* u1, double* u2, double* wt,
+   double* e2, double* e1);
+HIPSDP_API int  hipsdp_tail_unpack3_unit(int device, int n, int fused, const double* pk, double* out);
+HIPSDP_API int  hipsdp_tail_dz_unit(int device, int n, int fused, const double* pk, const double* P2, const double* Rd, double dtau, double eta,
+   double* dZ);
+HIPSDP_API int  hipsdp_tail_dirmat_unit(int device, int n, int fused, double s1, const double* Zinv, const double* X, const double* GZ, double* H,
+   double* pk);
+HIPSDP_API int  hipsdp_tail_sc_len(void);
+HIPSDP_API int  hipsdp_tail_dir_unit(int device, int m, int n, int fused, const double* B, const double* H, const double* rhs2, const double* rp,
+   const double* b, const double* u1, const double* u2, const double* par, double* sc, double* dy, double* dyt);
+HIPSDP_API int  hipsdp_tail_dots_unit(int device, int m, int n, int fused, const double* a, const double* v, double* out);
 HIPSDP_API int  hipsdp_trtri(int device, int n, const double* A, double* Linv);              /* A spd -> inverse of its Cholesky factor */
 HIPSDP_API int  hipsdp_lambda_min(int device, int n, const double* W, int steps, double* theta, double* resid);
 /* lambda_min(L D L^T), n <= 64, L lower triangular, D symmetric: the small-block step-length kernels; theta[2], resid[2] */

@@ -543,6 +543,100 @@ def potrf_small_unit(base, dir=None, alpha=0.0, pair=False, set_flag=False, want
     return out
 
 
+def potrf_pair_unit(A2, pair=True, device=0):
+    """strict-mode blocked Cholesky of two matrices A2[2, n, n], through hs_potrf_pair or (pair=False) two hs_potrf calls
+    -> (L[2, n, n] with the upper part as stored, dinv[2, len] with the staging blocks, fail[2])"""
+    L = _f64(A2).copy()
+    n = L.shape[-1]
+    assert L.shape == (2, n, n)
+    ulib().hipsdp_potrf_dinv_len.restype = C.c_longlong
+    nd = int(ulib().hipsdp_potrf_dinv_len(n))
+    dinv = np.zeros((2, nd))
+    fail = np.zeros(2, dtype=np.int32)
+    _chk(ulib().hipsdp_potrf_pair_unit(device, n, int(pair), _dp(L), _dp(dinv), _ip(fail)), "hipsdp_potrf_pair_unit")
+    return L, dinv, fail
+
+
+def trial_pair_unit(arrays, alpha, fused=True, first=True, device=0):
+    """arrays[8, n, n] = X, Z, dX, dZ, Xs, Zs, Lx, Lz -> the same eight after the trial iterates of a step were formed by hs_trial_pair
+    (fused) or by the copy / scale_add / copy launches it replaces"""
+    io = _f64(arrays).copy()
+    n = io.shape[-1]
+    assert io.shape == (8, n, n)
+    _chk(ulib().hipsdp_trial_pair_unit(device, n, int(fused), int(first), C.c_double(alpha), _dp(io)), "hipsdp_trial_pair_unit")
+    return io
+
+
+def _packed_len(n):
+    t = n * (n + 1) // 2
+    return t + (t & 1)
+
+
+def tail_after_solve2_unit(rhs2, u1, fused, device=0):
+    """-> (u2, wt, e2, e1) of k_after_solve2 + hs_make_ext twice, or of the one launch that replaces them"""
+    rhs2, u1 = _f64(rhs2), _f64(u1)
+    m = u1.size
+    assert rhs2.size == 2 * m
+    u2, wt, e2, e1 = np.zeros(m), np.zeros(m + 1), np.zeros(m + 1), np.zeros(m + 1)
+    _chk(ulib().hipsdp_tail_after_solve2_unit(device, m, int(fused), _dp(rhs2), _dp(u1), _dp(u2), _dp(wt), _dp(e2), _dp(e1)),
+         "hipsdp_tail_after_solve2_unit")
+    return u2, wt, e2, e1
+
+
+def tail_unpack3_unit(pk, n, fused, device=0):
+    pk = _f64(pk)
+    assert pk.shape == (3, _packed_len(n))
+    out = np.zeros((3, n, n))
+    _chk(ulib().hipsdp_tail_unpack3_unit(device, n, int(fused), _dp(pk), _dp(out)), "hipsdp_tail_unpack3_unit")
+    return out
+
+
+def tail_dz_unit(pk, P2, Rd, dtau, eta, fused, device=0):
+    pk, P2, Rd = _f64(pk), _f64(P2), _f64(Rd)
+    n = P2.shape[0]
+    assert pk.size == _packed_len(n) and P2.shape == Rd.shape == (n, n)
+    dZ = np.zeros((n, n))
+    _chk(ulib().hipsdp_tail_dz_unit(device, n, int(fused), _dp(pk), _dp(P2), _dp(Rd), C.c_double(dtau), C.c_double(eta), _dp(dZ)),
+         "hipsdp_tail_dz_unit")
+    return dZ
+
+
+def tail_dirmat_unit(s1, Zinv, X, GZ, fused, device=0):
+    Zinv, X, GZ = _f64(Zinv), _f64(X), _f64(GZ)
+    n = X.shape[0]
+    H, pk = np.zeros((n, n)), np.zeros(_packed_len(n))
+    _chk(ulib().hipsdp_tail_dirmat_unit(device, n, int(fused), C.c_double(s1), _dp(Zinv), _dp(X), _dp(GZ), _dp(H), _dp(pk)),
+         "hipsdp_tail_dirmat_unit")
+    return H, pk
+
+
+def tail_dir_unit(B, H, rhs2, rp, b, u1, u2, par, sc, fused, device=0):
+    """the scalars of a direction and its closing kernel -> (scalar block, dy, dyt)"""
+    B, H = _f64(B), _f64(H)
+    vs = [_f64(v) for v in (rhs2, rp, b, u1, u2)]
+    m, n = vs[0].size, B.shape[0]
+    par = _f64(par)
+    sc = _f64(sc).copy()
+    assert par.size == 6 and sc.size == ulib().hipsdp_tail_sc_len() and all(v.size == m for v in vs) and B.shape == H.shape == (n, n)
+    dy, dyt = np.zeros(m), np.zeros(m + 1)
+    _chk(ulib().hipsdp_tail_dir_unit(device, m, n, int(fused), _dp(B), _dp(H), _dp(vs[0]), _dp(vs[1]), _dp(vs[2]), _dp(vs[3]), _dp(vs[4]),
+                                     _dp(par), _dp(sc), _dp(dy), _dp(dyt)), "hipsdp_tail_dir_unit")
+    return sc, dy, dyt
+
+
+def tail_sc_len():
+    return int(ulib().hipsdp_tail_sc_len())
+
+
+def tail_dots_unit(a, v, fused, device=0):
+    a, v = _f64(a), _f64(v)
+    n = int(round(np.sqrt(a.shape[1])))
+    assert a.shape == (3, n * n) and v.shape[0] == 2
+    out = np.zeros(3)
+    _chk(ulib().hipsdp_tail_dots_unit(device, v.shape[1], n, int(fused), _dp(a), _dp(v), _dp(out)), "hipsdp_tail_dots_unit")
+    return out
+
+
 def trtri(A, device=0):
     A = _f64(A)
     Li = np.zeros_like(A)

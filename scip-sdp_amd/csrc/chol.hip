@@ -642,8 +642,8 @@ __device__ __forceinline__ void ps_mma(const double (*Ta)[PD_LD], const double (
 }
 
 template<int NBK>
-__global__ void __launch_bounds__(256) k_potrf_step(double* __restrict__ A, long long lda, int n, int kb, int nblk,
-   double* __restrict__ dinv, int* __restrict__ flag, const double* __restrict__ diag0, double regtol, pd_ext ext)
+__device__ __forceinline__ void ps_step_body(double* __restrict__ A, long long lda, int n, int kb, int nblk,
+   double* __restrict__ dinv, int* __restrict__ flag, const double* __restrict__ diag0, double regtol, const pd_ext& ext)
 {
    extern __shared__ __attribute__((aligned(16))) double pd_smem[];
    double* lstage = dinv + (long long) nblk * NB * NB;                                              /* staged L_kk blocks */
@@ -814,6 +814,38 @@ __global__ void __launch_bounds__(256) k_potrf_step(double* __restrict__ A, long
 }
 
 template<int NBK>
+__global__ void __launch_bounds__(256) k_potrf_step(double* __restrict__ A, long long lda, int n, int kb, int nblk,
+   double* __restrict__ dinv, int* __restrict__ flag, const double* __restrict__ diag0, double regtol, pd_ext ext)
+{
+   ps_step_body<NBK>(A, lda, n, kb, nblk, dinv, flag, diag0, regtol, ext);
+}
+
+/* the same block column of two matrices of the same order in one launch (blockIdx.y selects the job; plain mode only): the Cholesky
+ * check of the trial iterates X + alpha dX and Z + alpha dZ of a block above 64 rows was two chains of launches on two queues, the
+ * second one starting a fork, a scale_add and a copy late.  Same device code per matrix as k_potrf_step: identical bits
+ * (tests/test_gpu_potrf_pair.py) */
+struct ps_job { double* A; double* dinv; int* flag; };
+template<int NBK>
+__global__ void __launch_bounds__(256) k_potrf_step_pair(ps_job J0, ps_job J1, long long lda, int n, int kb, int nblk, pd_ext ext)
+{
+   const ps_job J = blockIdx.y ? J1 : J0;
+   ps_step_body<NBK>(J.A, lda, n, kb, nblk, J.dinv, J.flag, NULL, 1e-13, ext);
+}
+
+template<int NBK>
+static int launch_potrf_step_pair(hipStream_t s, const ps_job* J, long long lda, int n, int kb, int nblk, const pd_ext& ext)
+{
+   static hs_attr_mask attr_done;
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_potrf_step_pair<NBK>), PD_SMEM_BYTES, &attr_done) );
+   const int nS = nblk - kb;
+   const int t = nblk - kb - 1;
+   const int nT = kb > 0 ? t * (t + 1) / 2 : 0;
+   hipLaunchKernelGGL((k_potrf_step_pair<NBK>), dim3(nS + nT, 2), dim3(256), PD_SMEM_BYTES, s, J[0], J[1], lda, n, kb, nblk, ext);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+template<int NBK>
 static int launch_potrf_step(hipStream_t s, double* A, long long lda, int n, int kb, int nblk, double* dinv, int* flag,
    const double* diag0, const pd_ext& ext)
 {
@@ -919,6 +951,37 @@ long long hs_potrf_dinv_len(int n)
 int hs_potrf(hipStream_t s, int n, double* A, double* dinv, int* flag, const double* diag0)
 {
    return hs_potrf_psd(s, n, A, dinv, flag, diag0, NULL, 0);
+}
+
+/* hs_potrf(s, n, A, dinv, flag, NULL) for two matrices of the same order, one launch per block column for both (n > 64; up to 64
+ * rows hs_potrf_small_ext_pair is the pair form).  The flags stay apart: each receives the first failing pivot of its own matrix */
+int hs_potrf_pair(hipStream_t s, int n, const hs_potrf_job* jobs)
+{
+   if ( n <= 0 )
+      return HS_OK;
+   if ( jobs == NULL || jobs[0].A == NULL || jobs[1].A == NULL || jobs[0].A == jobs[1].A || jobs[0].dinv == jobs[1].dinv )
+      return HS_ERR_ARG;
+   const int nblk = (n + NB - 1) / NB;
+   if ( nblk <= 1 || g_potrf_force_v1 )
+   {
+      HS_CALL( hs_potrf(s, n, jobs[0].A, jobs[0].dinv, jobs[0].flag, NULL) );
+      return hs_potrf(s, n, jobs[1].A, jobs[1].dinv, jobs[1].flag, NULL);
+   }
+   const ps_job J[2] = {{jobs[0].A, jobs[0].dinv, jobs[0].flag}, {jobs[1].A, jobs[1].dinv, jobs[1].flag}};
+   /* (the pivot rule - HIPSDP_PIVOT_RULE in hs_potrf_psd - is consulted in semidefinite mode only, diag0 != NULL: in strict mode the
+    * value in est is never read, so the bits do not depend on the switch) */
+   const pd_ext est = {NULL, NULL, 0.0, NULL, NULL, NULL, 0, 3, NULL, 0, 0, NULL};
+   for (int b = 0; b < nblk; ++b)
+   {
+      const int nb = (n - b * NB) < NB ? (n - b * NB) : NB;
+      if ( nb <= 16 )
+         HS_CALL( launch_potrf_step_pair<16>(s, J, n, n, b, nblk, est) );
+      else if ( nb <= 32 )
+         HS_CALL( launch_potrf_step_pair<32>(s, J, n, n, b, nblk, est) );
+      else
+         HS_CALL( launch_potrf_step_pair<64>(s, J, n, n, b, nblk, est) );
+   }
+   return HS_OK;
 }
 
 /* diag0 != NULL: semidefinite mode; regmask (n ints, device; required when n > 64 in that mode) receives the forced pivots */

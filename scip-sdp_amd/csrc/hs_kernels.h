@@ -12,6 +12,11 @@ int hs_set_identity(hipStream_t s, double* A, int n, double v);
 int hs_copy(hipStream_t s, double* dst, const double* src, long long n);
 int hs_axpy(hipStream_t s, long long n, double a, const double* x, double* y);              /* y += a x */
 int hs_scale_add(hipStream_t s, long long n, double a, const double* x, double b, const double* y, double* out); /* out = a x + b y (y may be NULL) */
+/* the trial iterates of a step for X and Z in one launch: V <- alpha dV + 1.0 base, the value also into L (the matrix the Cholesky check
+ * factors in place); first = 1: base is V itself, saved to Vs on the way; 0 (halved step): base is the saved Vs.  Element for element
+ * what hs_copy(Vs, V), hs_scale_add(alpha, dV, 1.0, Vs, V), hs_copy(L, V) leave behind */
+struct hs_trial_job { double* V; const double* dV; double* Vs; double* L; };
+int hs_trial_pair(hipStream_t s, long long n, double alpha, int first, const hs_trial_job* jobs);
 int hs_mirror_lower(hipStream_t s, double* A, int n, long long lda);                        /* A[i][j] = A[j][i] for i < j */
 int hs_symmetrize(hipStream_t s, double* A, int n);
 int hs_transpose(hipStream_t s, int n, const double* src, double* dst);                     /* dst[i][j] = src[j][i], n x n, dst != src */                                         /* A = (A + A^T) / 2 */
@@ -63,6 +68,12 @@ int hs_apply_A_small(hipStream_t s, int m1, const hs_as_args* B, int q, const do
 int hs_axpy3(hipStream_t s, double a, long long n1, const double* x1, double* y1, long long n2, const double* x2, double* y2,
    long long n3, const double* x3, double* y3);
 int hs_dot(hipStream_t s, long long n, const double* a, const double* b, double* out, int accumulate, double* ws);
+/* hs_dot of a long vector inside a batch (begin without a held region): first stage launched at once, second stage a record of the batch;
+ * slot 0 .. 3 selects 256 doubles of ws (>= 1024) for the partial sums; anything else falls back to hs_dot.  See kernels.hip */
+#define HS_DOT_SLOT_DOUBLES 256        /* partial sums of one dot: the first stage never has more workgroups */
+#define HS_DOT_SLOTS 4                /* deferred dots of one batch */
+#define HS_RED_WS_DOUBLES (HS_DOT_SLOTS * HS_DOT_SLOT_DOUBLES)      /* what the engine allocates for ws */
+int hs_dot_deferred(hipStream_t s, long long n, const double* a, const double* b, double* out, int accumulate, double* ws, int slot);
 /* out[slot] = max(out[slot] if accumulate, max_e |a[e]|) */
 int hs_absmax(hipStream_t s, long long n, const double* a, double* out, int accumulate, double* ws);
 /* out[slot] = min(out[slot] if accumulate, min over e with d[e] < 0 of -x[e] / d[e]); +1e300 when no such e */
@@ -75,6 +86,8 @@ int hs_ratio_min(hipStream_t s, long long n, const double* x, const double* d, d
 int hs_dir_block_small(hipStream_t s, int n, double c, const double* X, const double* R, const double* E, const double* Zinv,
    double s1, double* out);
 int hs_dirmat(hipStream_t s, int n, double s1, const double* Zinv, const double* X, const double* GZ, double* H);
+/* hs_dirmat that also stores hs_pack_weighted(H) to pk (same values, one launch) */
+int hs_dirmat_pack(hipStream_t s, int n, double s1, const double* Zinv, const double* X, const double* GZ, double* H, double* pk);
 
 /* LP block element-wise pieces (length q) */
 int hs_lp_dir(hipStream_t s, int q, double sigmu, double eta, const double* x, const double* z, const double* rd_or_dz,
@@ -91,6 +104,11 @@ int hs_packed_diag(hipStream_t s, int m1, int n, int ldd, long long Lp, const do
 int hs_sub_lower(hipStream_t s, int n, const double* S, double* C);
 int hs_pack_weighted(hipStream_t s, int n, const double* V, double* pk);
 int hs_unpack_sym(hipStream_t s, int n, const double* pk, double sa, const double* add, double* out);
+/* cnt <= 3 calls hs_unpack_sym(n, pk[k], 0.0, NULL, out[k]) in one launch */
+int hs_unpack_sym3(hipStream_t s, int n, int cnt, const double* const* pk, double* const* out);
+/* hs_unpack_sym(n, pk, 0.0, NULL, dZ) and dZ = (dZ - sc[idtau] P2) + eta Rd (the engine's k_dz_combine) in one launch */
+int hs_unpack_dz_combine(hipStream_t s, int n, const double* pk, const double* P2, const double* sc, int idtau, double eta, const double* Rd,
+   double* dZ);
 int hs_zero_upper(hipStream_t s, double* A, int n);                                         /* A[i][j] = 0 for i < j */
 
 /* ---- schur.hip ------------------------------------------------------------------------------------------------ */
@@ -176,6 +194,16 @@ int  hs_sp_apply_AT(hipStream_t s, const hs_sparse* sp, const double* coef, doub
 int  hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx);   /* lower triangle, i, j >= 1 */
 int  hs_sp_expand(hipStream_t s, const hs_sparse* sp, double* A);
 
+/* ---- ipm.hip: pieces of an iteration's tail that have a unit entry (tests/test_gpu_tail_fusions.py) ------------------ */
+struct hs_dir_tail_args { int m, q, K; const int* n; const double* const* B; const double* const* H; const double* beta; const double* hl;
+   const double* rhs2; const double* rp; const double* b; double* u1; const double* u2; double* dy; double* dyt; double* sc; double* red_ws;
+   const double* dinvm; const double* Lm; double eta, rg, sigmu, tau, kappa, etk; };
+int hs_ipm_dir_tail(hipStream_t st, const hs_dir_tail_args* a, int tail, int fuse_solve);
+int hs_ipm_after_solve2(hipStream_t st, int m, const double* rhs2, double* u2, double* wt, const double* u1, double* e2, double* e1, int fused);
+int hs_ipm_dz_combine(hipStream_t st, long long n2, double* dZ, const double* P2, const double* sc, double eta, const double* Rd);
+int hs_ipm_sc_dtau(void);             /* index of dtau in the scalar block */
+int hs_ipm_sc_len(int nblocks);       /* doubles of the scalar block */
+
 /* ---- chol.hip ------------------------------------------------------------------------------------------------- */
 /* In-place blocked Cholesky of the lower triangle of the row-major n x n matrix A (lda = n): A = L L^T, L stored in the
  * lower triangle (upper triangle is left untouched).  dinv receives the inverses of the 64 x 64 diagonal blocks of L
@@ -187,6 +215,10 @@ long long hs_potrf_dinv_len(int n);         /* doubles dinv must hold (inverses 
 /* set_flag: the (single-launch, n <= 64) factorization stores its result into *flag instead of recording a failure into a
  * cleared flag - for callers where it is the only writer of that flag between two reads */
 int hs_potrf_psd(hipStream_t s, int n, double* A, double* dinv, int* flag, const double* diag0, int* regmask, int set_flag);
+/* hs_potrf in strict mode for two matrices of the same order (n > 64: one launch per block column serves both; the bits of either are
+ * those of hs_potrf alone).  A job: the matrix, its dinv (hs_potrf_dinv_len(n) doubles) and its own failure flag */
+struct hs_potrf_job { double* A; double* dinv; int* flag; };
+int hs_potrf_pair(hipStream_t s, int n, const hs_potrf_job* jobs);
 /* Linv = L^-1 (lower triangular, full n x n storage, upper triangle zero); needs dinv from hs_potrf */
 int hs_trtri(hipStream_t s, int n, const double* L, const double* dinv, double* Linv, double* tmp);
 /* solves L y = r (nrhs <= 4 right-hand sides, rhs[k * ldr + i]) then optionally L^T x = y, in place.  mode 1: forward only,

@@ -902,7 +902,7 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
       HS_HIP( hipHostGetDevicePointer((void**) &s->hsc_dev, s->hsc, 0) );
       memset(s->hsc, 0, (size_t) s->hsc_cap * sizeof(double));
    }
-   HS_CALL( dalloc(&s->red_ws, 1024) );
+   HS_CALL( dalloc(&s->red_ws, HS_RED_WS_DOUBLES) );
    s->gemv_ws_len = 8192 + 4LL * 1024 * 4;
    HS_CALL( dalloc(&s->gemv_ws, s->gemv_ws_len) );
    {
@@ -1399,7 +1399,7 @@ extern "C" int hipsdp_set_lp(hipsdp_solver* s, const double* Dext)
 
 int hs_gen_dense(hipStream_t s, int n, int i0, int i1, long long seed, double* A);
 static int ensure_packed(hipsdp_solver* s);
-static int pass_A(hipsdp_solver* s, Block& B, const double* V, double* out);
+static int pass_A(hipsdp_solver* s, Block& B, const double* V, double* out, bool packed = false);
 static int pass_AT(hipsdp_solver* s, Block& B, const double* coef, double sa, const double* add, double* out);
 
 extern "C" int hipsdp_gen_planted(hipsdp_solver* s, int n, int m, long long seed, const double* Xstar, const double* Zstar,
@@ -1569,6 +1569,28 @@ __global__ void k_after_solve2(int m, const double* __restrict__ rhs2, double* _
    }
 }
 
+/* k_after_solve2 and, in the same thread, the two coefficient vectors of the three-vector sweep that hs_make_ext formed behind it:
+ * e2 = [s20; s21 u2] from the u2 just stored, e1 = [s10; s11 u1] (u1: the predictor's right-hand side, solved with g and b) */
+__global__ void k_after_solve2_ext(int m, const double* __restrict__ rhs2, double* __restrict__ u2, double* __restrict__ wt,
+   double s20, double s21, double* __restrict__ e2, double s10, double s11, const double* __restrict__ u1, double* __restrict__ e1)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if ( i == 0 )
+   {
+      wt[0] = 1.0;
+      e2[0] = s20;
+      e1[0] = s10;
+   }
+   if ( i < m )
+   {
+      const double v = rhs2[m + i] - rhs2[i];
+      u2[i] = v;
+      wt[1 + i] = -rhs2[i];
+      e2[1 + i] = s21 * v;
+      e1[1 + i] = s11 * u1[i];
+   }
+}
+
 /* m <= 64 (single-block factor, dinv = inv(L) as 64 x 64, L = the factor as m x m): rhs2 = [g ; b] with g = Mx[0, 1:], both
  * solves M x = r as x = inv(L)^T (inv(L) r) with each triangular solve corrected once by the factor itself (see RB_SOLVE in
  * kernels.hip: the residual of these solves is primal infeasibility of the step), then u2 = ub - w and wt = [1, -w]: k_rhs2 + the
@@ -1719,6 +1741,79 @@ __global__ void k_cert(long long n2, double tau, const double* __restrict__ Rd, 
 }
 
 static inline dim3 g1d(long long n) { long long g = (n + 255) / 256; if ( g < 1 ) g = 1; if ( g > 4096 ) g = 4096; return dim3((unsigned) g); }
+
+/* The scalars of a direction and its closing kernel: BH = sum <B_k, H_k> + beta^T hl, w^T rp, b^T u1, then dtau, dkappa, dy, dyt.
+ * fuse_solve: the solve with the single-block factor of M is the first record.  tail (general path, see general_tail): the first stage
+ * of every <B_k, H_k> is a launch, everything else - the fill, the second stages, the dots over m, the closing kernel as a record
+ * with a loop over m - is the batch's one launch; the partial sums are combined in the order of the separate launches */
+int hs_ipm_dir_tail(hipStream_t st, const hs_dir_tail_args* a, int tail, int fuse_solve)
+{
+   const int m = a->m;
+   hs_red_batch_begin(st);
+   if ( fuse_solve )
+      (void) hs_red_batch_solve(st, m, a->dinvm, a->Lm, 1, a->u1, m);
+   HS_CALL( hs_fill_scalar(st, a->sc + SC_BH, 0.0) );
+   for (int k = 0; k < a->K; ++k)
+   {
+      const long long n2 = (long long) a->n[k] * a->n[k];
+      if ( tail )
+         HS_CALL( hs_dot_deferred(st, n2, a->B[k], a->H[k], a->sc + SC_BH, 1, a->red_ws, k) );
+      else
+         HS_CALL( hs_dot(st, n2, a->B[k], a->H[k], a->sc + SC_BH, 1, a->red_ws) );
+   }
+   if ( a->q > 0 )
+      HS_CALL( hs_dot(st, a->q, a->beta, a->hl, a->sc + SC_BH, 1, a->red_ws) );
+   HS_CALL( hs_dot(st, m, a->rhs2, a->rp, a->sc + SC_WRP, 0, a->red_ws) );       /* w = rhs2[0:m] */
+   HS_CALL( hs_dot(st, m, a->b, a->u1, a->sc + SC_BU1, 0, a->red_ws) );
+   bool finished = false;
+   if ( fuse_solve || tail )
+   {
+      hs_rb_finish F = {m, a->eta, a->rg, a->sigmu, a->tau, a->kappa, a->etk, a->u1, a->u2, a->dy, a->dyt, a->sc,
+         SC_S0, SC_BUB, SC_BH, SC_WRP, SC_BU1, SC_DTAU, SC_DKAPPA, SC_DEN};
+      finished = hs_red_batch_finish(st, &F, sizeof(F)) == 1;
+   }
+   HS_CALL( hs_red_batch_end() );
+   if ( !finished )
+   {
+      HS_CALL( hs_red_batch_flush() );
+      hipLaunchKernelGGL(k_finish_dir, g1d(m > 0 ? m : 1), dim3(256), 0, st, m, a->eta, a->rg, a->sigmu, a->tau, a->kappa, a->etk,
+         a->u1, a->u2, a->dy, a->dyt, a->sc);
+      HS_LAUNCH_CHECK();
+   }
+   return HS_OK;
+}
+
+/* after the two (three) solves with M: u2 and wt; fused: with the coefficient vectors e2 = [1; u2], e1 = [0; u1] of the three-vector
+ * sweep from the same launch (hs_make_ext twice behind it otherwise; e2 == NULL: neither) */
+int hs_ipm_after_solve2(hipStream_t st, int m, const double* rhs2, double* u2, double* wt, const double* u1, double* e2, double* e1, int fused)
+{
+   if ( fused && e2 != NULL )
+   {
+      hipLaunchKernelGGL(k_after_solve2_ext, g1d(m + 1), dim3(256), 0, st, m, rhs2, u2, wt, 1.0, 1.0, e2, 0.0, 1.0, u1, e1);
+      HS_LAUNCH_CHECK();
+      return HS_OK;
+   }
+   hipLaunchKernelGGL(k_after_solve2, g1d(m + 1), dim3(256), 0, st, m, rhs2, u2, wt);
+   HS_LAUNCH_CHECK();
+   if ( e2 != NULL )
+   {
+      HS_CALL( hs_make_ext(st, m, 1.0, 1.0, u2, e2) );
+      HS_CALL( hs_make_ext(st, m, 0.0, 1.0, u1, e1) );
+   }
+   return HS_OK;
+}
+
+/* dZ = (dZ - dtau P2) + eta Rd with dtau out of the scalar block */
+int hs_ipm_dz_combine(hipStream_t st, long long n2, double* dZ, const double* P2, const double* sc, double eta, const double* Rd)
+{
+   HS_CALL( hs_red_batch_flush() );
+   hipLaunchKernelGGL(k_dz_combine, g1d(n2), dim3(256), 0, st, n2, dZ, P2, sc, eta, Rd);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+int hs_ipm_sc_dtau(void) { return SC_DTAU; }
+int hs_ipm_sc_len(int nblocks) { return SC_FIXED_END + 8 * (nblocks > 0 ? nblocks : 1) + 8; }
 
 /* ---- GEMM convenience ------------------------------------------------------------------------------------------ */
 static int gemm_on(hipStream_t st, int layA, int layB, int M, int N, int K, double alpha, const double* A, long long lda,
@@ -2065,8 +2160,8 @@ __global__ void k_add_col0(int m1, const double* __restrict__ v, double* __restr
       Mx[(long long) i * m1] += v[i];
 }
 
-/* out[m + 1] = <A_i, V>, V symmetric */
-static int pass_A(hipsdp_solver* s, Block& B, const double* V, double* out)
+/* out[m + 1] = <A_i, V>, V symmetric; packed: B.pkv already holds the packed, weighted copy of V (hs_dirmat_pack) */
+static int pass_A(hipsdp_solver* s, Block& B, const double* V, double* out, bool packed)
 {
    const int m1 = s->m + 1;
    if ( B.sparse )
@@ -2105,7 +2200,8 @@ static int pass_A(hipsdp_solver* s, Block& B, const double* V, double* out)
    }
    if ( B.Apk != NULL )
    {
-      HS_CALL( hs_pack_weighted(s->stream, B.n, V, B.pkv) );
+      if ( !packed )
+         HS_CALL( hs_pack_weighted(s->stream, B.n, V, B.pkv) );
       const double* v = B.pkv;
       return hs_gemv_n(s->stream, m1, B.Lp, B.Apk, B.Lp, 1, &v, out, m1, s->gemv_ws, s->gemv_ws_len);
    }
@@ -2191,6 +2287,25 @@ struct BatchRegion
    ~BatchRegion() { if ( on ) (void) hs_red_batch_release(); }
 };
 
+/* The general path proper - one rank, more than 64 variables, every block above 64 rows, no batch regions: between two Schur assemblies
+ * it is a chain of launches of a few microseconds each, so neighbouring launches are merged where the arithmetic per element and
+ * the order of every sum stay what they were; every other path keeps its launches */
+static bool general_tail(const hipsdp_solver* s)
+{
+   if ( s->comm != NULL || s->m <= 64 || s->blk.empty() || batch_regions(s) )
+      return false;
+   for (auto& B : s->blk)
+      if ( B.n <= 64 )
+         return false;
+   return true;
+}
+
+/* ... and a block whose sweeps run over the packed rows on this rank alone gets the packed copy of H from the kernel that forms H */
+static bool pack_with_dirmat(const hipsdp_solver* s, const Block& B)
+{
+   return general_tail(s) && B.Apk != NULL && !B.sparse;
+}
+
 /* returns 1 when the fused launch was used */
 static int apply_A_small(hipsdp_solver* s, double* const* Vk, const double* vlp, double* out, int epi, double scal,
    const double* vin, double* vout)
@@ -2219,7 +2334,7 @@ static int apply_A_small(hipsdp_solver* s, double* const* Vk, const double* vlp,
 }
 
 /* A(V) over all blocks + LP: out[m + 1] = sum_k A_k vec(V_k) + Dext^T vlp */
-static int apply_A(hipsdp_solver* s, double* const* Vk, const double* vlp, double* out)
+static int apply_A(hipsdp_solver* s, double* const* Vk, const double* vlp, double* out, bool packed = false)
 {
    const int m1 = s->m + 1;
    bool first = true;
@@ -2228,7 +2343,7 @@ static int apply_A(hipsdp_solver* s, double* const* Vk, const double* vlp, doubl
       Block& B = s->blk[k];
       const double* v = Vk[k];
       double* dst = first ? out : s->tmpe;
-      HS_CALL( pass_A(s, B, v, dst) );
+      HS_CALL( pass_A(s, B, v, dst, packed && pack_with_dirmat(s, B)) );
       if ( !first )
          HS_CALL( hs_axpy(s->stream, m1, 1.0, s->tmpe, out) );
       first = false;
@@ -2282,7 +2397,10 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
             HS_CALL( hs_copy(s->stream, B.G, B.E, n2) );
          HS_CALL( gemm(s, HS_KC, HS_MC, n, n, n, eta, B.X, n, B.Rd, n, useE ? 1.0 : 0.0, B.G, n) );
          HS_CALL( gemm(s, HS_KC, HS_MC, n, n, n, 1.0, B.G, n, B.Zinv, n, 0.0, B.GZ, n) );
-         HS_CALL( hs_dirmat(s->stream, n, sigmu, B.Zinv, B.X, B.GZ, B.H) );
+         if ( pack_with_dirmat(s, B) )
+            HS_CALL( hs_dirmat_pack(s->stream, n, sigmu, B.Zinv, B.X, B.GZ, B.H, B.pkv) );    /* (pass_A below: packed) */
+         else
+            HS_CALL( hs_dirmat(s->stream, n, sigmu, B.Zinv, B.X, B.GZ, B.H) );
       }
       Hs.push_back(B.H);
    }
@@ -2292,7 +2410,7 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
    if ( fusedA < 0 )
       return -fusedA;
    if ( fusedA == 0 )
-      HS_CALL( apply_A(s, Hs.data(), s->hl, s->AH) );
+      HS_CALL( apply_A(s, Hs.data(), s->hl, s->AH, true) );
    if ( fusedA == 0 && m > 0 )
    {
       HS_CALL( hs_red_batch_flush() );
@@ -2308,31 +2426,17 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
       HS_CALL( hs_red_batch_flush() );
       HS_CALL( hs_trsv_sync(s->stream, m, s->Lm, s->dinvm, 1, s->u1, m, SOLVE_MODE, s->trsv_ws, &s->trsv_epoch) );
    }
-   /* BH = sum <B_k, H_k> + beta^T hl ; wrp ; bu1 */
-   hs_red_batch_begin(s->stream);
-   if ( fuse_solve )
-      (void) hs_red_batch_solve(s->stream, m, s->dinvm, s->Lm, 1, s->u1, m);
-   HS_CALL( hs_fill_scalar(s->stream, s->sc + SC_BH, 0.0) );
-   for (auto& B : s->blk)
-      HS_CALL( hs_dot(s->stream, (long long) B.n * B.n, B.B, B.H, s->sc + SC_BH, 1, s->red_ws) );
-   if ( q > 0 )
-      HS_CALL( hs_dot(s->stream, q, s->beta, s->hl, s->sc + SC_BH, 1, s->red_ws) );
-   HS_CALL( hs_dot(s->stream, m, s->rhs2, s->rp, s->sc + SC_WRP, 0, s->red_ws) );       /* w = rhs2[0:m] */
-   HS_CALL( hs_dot(s->stream, m, s->b, s->u1, s->sc + SC_BU1, 0, s->red_ws) );
-   bool finished = false;
-   if ( fuse_solve )
+   /* BH = sum <B_k, H_k> + beta^T hl ; wrp ; bu1 ; dtau, dkappa, dy */
    {
-      hs_rb_finish F = {m, eta, rg, sigmu, s->tau, s->kappa, etk, s->u1, s->u2, s->dy, s->dyt, s->sc,
-         SC_S0, SC_BUB, SC_BH, SC_WRP, SC_BU1, SC_DTAU, SC_DKAPPA, SC_DEN};
-      finished = hs_red_batch_finish(s->stream, &F, sizeof(F)) == 1;
-   }
-   HS_CALL( hs_red_batch_end() );
-   if ( !finished )
-   {
-      HS_CALL( hs_red_batch_flush() );
-      hipLaunchKernelGGL(k_finish_dir, g1d(m > 0 ? m : 1), dim3(256), 0, s->stream, m, eta, rg, sigmu, s->tau, s->kappa, etk,
-         s->u1, s->u2, s->dy, s->dyt, s->sc);
-      HS_LAUNCH_CHECK();
+      std::vector<int> bn;
+      std::vector<const double*> bB, bH;
+      for (auto& B : s->blk)
+      {
+         bn.push_back(B.n); bB.push_back(B.B); bH.push_back(B.H);
+      }
+      const hs_dir_tail_args ta = {m, q, (int) s->blk.size(), bn.data(), bB.data(), bH.data(), s->beta, s->hl, s->rhs2, s->rp, s->b, s->u1, s->u2,
+         s->dy, s->dyt, s->sc, s->red_ws, s->dinvm, s->Lm, eta, rg, sigmu, s->tau, s->kappa, etk};
+      HS_CALL( hs_ipm_dir_tail(s->stream, &ta, general_tail(s) ? 1 : 0, fuse_solve ? 1 : 0) );
    }
    for (auto& B : s->blk)
    {
@@ -2342,6 +2446,7 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
          HS_CALL( pass_AT(s, B, s->dyt, eta, B.Rd, B.dZ) );
       else
       {
+         bool combined = false;
          if ( split == 1 )
          {
             if ( &B == &s->blk[0] )
@@ -2349,11 +2454,18 @@ static int direction(hipsdp_solver* s, double sigma, double eta, double mu, doub
                HS_CALL( hs_make_ext(s->stream, m, 0.0, 1.0, s->u1, s->cvec + m1) );
                HS_LAUNCH_CHECK();
             }
-            HS_CALL( pass_AT(s, B, s->cvec + m1, 0.0, NULL, B.dZ) );
+            if ( pack_with_dirmat(s, B) )
+            {
+               /* pass_AT over the packed rows, its hs_unpack_sym and k_dz_combine in one launch behind the sweep */
+               HS_CALL( hs_gemv_t_ws(s->stream, m1, B.Lp, B.Apk, B.Lp, s->cvec + m1, 0.0, NULL, B.pkv + B.Lp, s->gemvt_ws, s->gemvt_ws_len) );
+               HS_CALL( hs_unpack_dz_combine(s->stream, n, B.pkv + B.Lp, B.P2, s->sc, SC_DTAU, eta, B.Rd, B.dZ) );
+               combined = true;
+            }
+            else
+               HS_CALL( pass_AT(s, B, s->cvec + m1, 0.0, NULL, B.dZ) );
          }
-         HS_CALL( hs_red_batch_flush() );
-         hipLaunchKernelGGL(k_dz_combine, g1d(n2), dim3(256), 0, s->stream, n2, B.dZ, B.P2, s->sc, eta, B.Rd);
-         HS_LAUNCH_CHECK();
+         if ( !combined )
+            HS_CALL( hs_ipm_dz_combine(s->stream, n2, B.dZ, B.P2, s->sc, eta, B.Rd) );
       }
       if ( n <= HS_SMALL_N )
          HS_CALL( hs_dir_block_small(s->stream, n, 1.0, B.X, B.dZ, useE ? B.E : NULL, B.Zinv, sigmu, B.dX) );
@@ -3241,6 +3353,7 @@ struct GeneralSolve
    int enqueue_residuals()
    {
       const bool recur = rd_have && !want_cert;
+      const bool tail = general_tail(s);
       HS_CALL( hs_make_ext(st, m, -s->tau, 1.0, s->y, s->yt) );
       HS_LAUNCH_CHECK();
       hs_red_batch_begin(st);         /* the reductions of this phase run in one launch, right before the scalars are read */
@@ -3256,8 +3369,17 @@ struct GeneralSolve
             HS_CALL( pass_AT(s, B, s->yt, -1.0, B.Z, B.Rd) );
          else if ( rd_pending )
             HS_CALL( hs_scale_add(st, n2, rd_scale, B.Rd, 0.0, NULL, B.Rd) );
-         HS_CALL( hs_dot(st, n2, B.Rd, B.Rd, s->sc + SC_BLK(k, 0), 0, s->red_ws) );
-         HS_CALL( hs_dot(st, n2, B.X, B.Z, s->sc + SC_XZ, 1, s->red_ws) );
+         if ( tail && !want_cert )
+         {
+            /* (first stages now, second stages with the records: the read-back's launch) */
+            HS_CALL( hs_dot_deferred(st, n2, B.Rd, B.Rd, s->sc + SC_BLK(k, 0), 0, s->red_ws, 2 * k) );
+            HS_CALL( hs_dot_deferred(st, n2, B.X, B.Z, s->sc + SC_XZ, 1, s->red_ws, 2 * k + 1) );
+         }
+         else
+         {
+            HS_CALL( hs_dot(st, n2, B.Rd, B.Rd, s->sc + SC_BLK(k, 0), 0, s->red_ws) );
+            HS_CALL( hs_dot(st, n2, B.X, B.Z, s->sc + SC_XZ, 1, s->red_ws) );
+         }
          if ( want_cert )
          {
             HS_CALL( hs_red_batch_flush() );
@@ -3804,11 +3926,14 @@ struct GeneralSolve
                HS_CALL( hs_trsv_sync(st, m, s->Lm, s->dinvm, 2, s->rhs2, m, SOLVE_MODE, s->trsv_ws, &s->trsv_epoch) );
          }
       }
+      split_dz = predH_joined && s->comm == NULL;
+      for (auto& B : s->blk)
+         if ( B.Apk == NULL )
+            split_dz = false;
+      const bool tail = general_tail(s);
+      /* (with the three-vector sweep ahead, the coefficient vectors [1; u2] and [0; u1] come out of the same launch) */
       if ( m == 0 || m > 64 )
-      {
-         hipLaunchKernelGGL(k_after_solve2, g1d(m1), dim3(256), 0, st, m, s->rhs2, s->u2, s->wt);
-         HS_LAUNCH_CHECK();
-      }
+         HS_CALL( hs_ipm_after_solve2(st, m, s->rhs2, s->u2, s->wt, s->u1, (split_dz && tail) ? s->cvec : NULL, s->cvec + m1, 1) );
       hs_red_batch_begin(st);
       HS_CALL( hs_fill_scalar(st, s->sc + SC_S0, 0.0) );
       /* dZ = A^T([-dtau; u1 - u2 dtau]) + eta Rd is linear in dtau: A^T([0; u1]) - dtau A^T([1; u2]) + eta Rd.  u2 belongs to the
@@ -3816,16 +3941,13 @@ struct GeneralSolve
        * P1 = A^T([0; u1]) come out of ONE sweep over A (three coefficient vectors), the corrector needs one more sweep for its P1:
        * two sweeps per iteration where B, the predictor's dZ and the corrector's dZ took three - and the dependent chain
        * B pass -> dtau -> dZ pass loses a link.  Single GPU, packed copy present, predictor solved early (else the old form). */
-      split_dz = predH_joined && s->comm == NULL;
-      for (auto& B : s->blk)
-         if ( B.Apk == NULL )
-            split_dz = false;
-      if ( split_dz )
+      if ( split_dz && !tail )
       {
          HS_CALL( hs_make_ext(st, m, 1.0, 1.0, s->u2, s->cvec) );
          HS_CALL( hs_make_ext(st, m, 0.0, 1.0, s->u1, s->cvec + m1) );
          HS_LAUNCH_CHECK();
       }
+      int slot = 0;
       for (auto& B : s->blk)
       {
          const int n = B.n;
@@ -3843,9 +3965,18 @@ struct GeneralSolve
                return -r3;
             if ( r3 == 1 )
             {
-               HS_CALL( hs_unpack_sym(st, n, B.pk3, 0.0, NULL, B.B) );
-               HS_CALL( hs_unpack_sym(st, n, B.pk3 + B.Lp, 0.0, NULL, B.P2) );
-               HS_CALL( hs_unpack_sym(st, n, B.pk3 + 2 * B.Lp, 0.0, NULL, B.dZ) );
+               if ( tail )
+               {
+                  const double* pk[3] = {B.pk3, B.pk3 + B.Lp, B.pk3 + 2 * B.Lp};
+                  double* un[3] = {B.B, B.P2, B.dZ};
+                  HS_CALL( hs_unpack_sym3(st, n, 3, pk, un) );
+               }
+               else
+               {
+                  HS_CALL( hs_unpack_sym(st, n, B.pk3, 0.0, NULL, B.B) );
+                  HS_CALL( hs_unpack_sym(st, n, B.pk3 + B.Lp, 0.0, NULL, B.P2) );
+                  HS_CALL( hs_unpack_sym(st, n, B.pk3 + 2 * B.Lp, 0.0, NULL, B.dZ) );
+               }
                swept = true;
             }
             else
@@ -3858,7 +3989,10 @@ struct GeneralSolve
             HS_CALL( pass_AT(s, B, s->wt, 0.0, NULL, B.B) );
          HS_CALL( gemm(s, HS_KC, HS_MC, n, n, n, 1.0, B.X, n, B.B, n, 0.0, B.T1, n) );
          HS_CALL( gemm(s, HS_KC, HS_MC, n, n, n, 1.0, B.T1, n, B.Zinv, n, 0.0, B.W, n) );
-         HS_CALL( hs_dot(st, n2, B.B, B.W, s->sc + SC_S0, 1, s->red_ws) );
+         if ( tail )
+            HS_CALL( hs_dot_deferred(st, n2, B.B, B.W, s->sc + SC_S0, 1, s->red_ws, slot++) );
+         else
+            HS_CALL( hs_dot(st, n2, B.B, B.W, s->sc + SC_S0, 1, s->red_ws) );
       }
       if ( q > 0 )
       {
@@ -3942,14 +4076,8 @@ struct GeneralSolve
    int update()
    {
       phase_mark(s, PH_UPDATE);
-      for (auto& B : s->blk)
-      {
-         const long long n2 = (long long) B.n * B.n;
-         if ( B.n <= 64 )
-            continue;            /* single-block factorization: the trial iterate is written to Xs / Zs and swapped in */
-         HS_CALL( hs_copy(st, B.Xs, B.X, n2) );
-         HS_CALL( hs_copy(st, B.Zs, B.Z, n2) );
-      }
+      /* (blocks of at most 64 rows: the trial iterate is written to Xs / Zs and swapped in; above that the first attempt of
+       * step_general saves X and Z to Xs / Zs in the launch that forms the trial iterate) */
       tau0 = s->tau;
       kappa0 = s->kappa;
       applied = 0.0;
@@ -4014,23 +4142,40 @@ struct GeneralSolve
       for (int attempt = 0; attempt < 8; ++attempt)
       {
          HS_HIP( hipMemsetAsync(s->flags, 0, 8 * sizeof(int), st) );
-         HS_CALL( fork2(s) );
+         /* Blocks above 64 rows: the trial iterates of X and Z and their Cholesky checks are ONE chain on the first queue - one launch
+          * for X + alpha dX, Z + alpha dZ, the saved iterate and the copies to factor, then one launch per block column for both
+          * matrices (seven launches and a fork in front of two chains before: profiles/r06_c_iter_sequence.txt, 1994 -> 2319 us).
+          * The chain writes Z, Lz and dinvz on the first queue, so whatever the second queue still has in flight is awaited first:
+          * nothing on a first attempt (solve_m or predictor joined it); after a failed check the Z chains of the iterate that was
+          * given up, which read Lz and dinvz - they were ordered before the next factorization of Z by sharing its queue */
+         bool large = false, small = false;
+         for (auto& B : s->blk)
+            (B.n > 64 ? large : small) = true;
+         if ( large && s->busy2 )
+            HS_CALL( join2(s) );
          for (auto& B : s->blk)
          {
-            const int n = B.n;
-            const long long n2 = (long long) n * n;
-            if ( n <= 64 )
+            if ( B.n <= 64 )
+               continue;
+            const hs_trial_job tj[2] = {{B.X, B.dX, B.Xs, B.Lx}, {B.Z, B.dZ, B.Zs, B.Lz}};
+            HS_CALL( hs_trial_pair(st, (long long) B.n * B.n, alpha, attempt == 0 ? 1 : 0, tj) );
+            const hs_potrf_job pj[2] = {{B.Lx, B.dinvx, s->flags + 1}, {B.Lz, B.dinvz, s->flags + 0}};
+            HS_CALL( hs_potrf_pair(st, B.n, pj) );
+         }
+         if ( small )
+         {
+            /* the single-launch checks of X and Z of the small blocks of a mixed problem side by side on the two queues */
+            HS_CALL( fork2(s) );
+            for (auto& B : s->blk)
             {
+               const int n = B.n;
+               if ( n > 64 )
+                  continue;
                HS_CALL( hs_potrf_small_ext(st, n, B.Lx, B.dinvx, s->flags + 1, B.X, B.dX, alpha, B.Xs, B.LxInv, NULL, setf) );
                HS_CALL( hs_potrf_small_ext(st2, n, B.Lz, B.dinvz, s->flags + 0, B.Z, B.dZ, alpha, B.Zs, B.LzInv, n <= 32 ? B.Zinv : NULL, setf) );
-               continue;
             }
-            HS_CALL( hs_scale_add(st, n2, alpha, B.dX, 1.0, B.Xs, B.X) );
-            HS_CALL( factor(st, n, B.Lx, B.dinvx, B.X, 1) );
-            HS_CALL( hs_scale_add(st2, n2, alpha, B.dZ, 1.0, B.Zs, B.Z) );
-            HS_CALL( factor(st2, n, B.Lz, B.dinvz, B.Z, 0) );
+            HS_CALL( join2(s) );
          }
-         HS_CALL( join2(s) );
          if ( K == 0 )
             break;
          if ( optimistic )

@@ -165,6 +165,56 @@ __global__ void k_unpack_sym(int n, const double* __restrict__ pk, double sa, co
    }
 }
 
+/* up to three k_unpack_sym of the same order in one launch (blockIdx.y selects; add == NULL in all of them): the three results of the
+ * three-vector sweep over the packed rows */
+struct unpack3_args { const double* pk[3]; double* out[3]; };
+__global__ void k_unpack_sym3(int n, unpack3_args U)
+{
+   const double* __restrict__ pk = U.pk[blockIdx.y];
+   double* __restrict__ out = U.out[blockIdx.y];
+   const long long total = (long long) n * n;
+   for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long) gridDim.x * blockDim.x)
+   {
+      const int r0 = (int) (e / n), c0 = (int) (e - (long long) (e / n) * n);
+      const int r = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
+      out[e] = pk[(long long) r * (r + 1) / 2 + c];
+   }
+}
+
+/* k_unpack_sym (add == NULL) into dZ followed by ipm.hip's k_dz_combine on it, element for element: dZ = (P1 - dtau P2) + eta Rd with
+ * P1 out of the packed vector and dtau = sc[idtau] */
+__global__ void k_unpack_dz_combine(int n, const double* __restrict__ pk, const double* __restrict__ P2, const double* __restrict__ sc, int idtau,
+   double eta, const double* __restrict__ Rd, double* __restrict__ dZ)
+{
+   const double dtau = sc[idtau];
+   const long long total = (long long) n * n;
+   for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long) gridDim.x * blockDim.x)
+   {
+      const int r0 = (int) (e / n), c0 = (int) (e - (long long) (e / n) * n);
+      const int r = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
+      const double p1 = pk[(long long) r * (r + 1) / 2 + c];
+      dZ[e] = (p1 - dtau * P2[e]) + eta * Rd[e];
+   }
+}
+
+/* k_dirmat that also leaves the packed, weighted copy of its result (k_pack_weighted of H): the element (r, c), c <= r, is stored to
+ * both places by the thread that formed it */
+__global__ void k_dirmat_pack(int n, double s1, const double* __restrict__ Zinv, const double* __restrict__ X,
+   const double* __restrict__ GZ, double* __restrict__ H, double* __restrict__ pk)
+{
+   const long long total = (long long) n * n;
+   for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long) gridDim.x * blockDim.x)
+   {
+      const int r = (int) (i / n);
+      const int c = (int) (i - (long long) r * n);
+      const double g = 0.5 * (GZ[i] + GZ[(long long) c * n + r]);
+      const double h = s1 * Zinv[i] - X[i] - g;
+      H[i] = h;
+      if ( c <= r )
+         pk[(long long) r * (r + 1) / 2 + c] = (r == c ? 1.0 : 2.0) * h;
+   }
+}
+
 __global__ void k_zero_upper(double* A, int n)
 {
    const long long total = (long long) n * n;
@@ -323,6 +373,33 @@ int hs_scale_add(hipStream_t s, long long n, double a, const double* x, double b
    return HS_OK;
 }
 
+/* blockIdx.y = 0: X, 1: Z.  The value is formed by the statements of k_scale_add (b arrives as an argument there and here, so the
+ * compiler contracts both alike); on the first attempt V is read and written by the same thread at the same index */
+__global__ void k_trial_pair(long long n, double a, double b, int first, hs_trial_job J0, hs_trial_job J1)
+{
+   const hs_trial_job J = blockIdx.y ? J1 : J0;
+   const double* base = first ? J.V : J.Vs;
+   for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x)
+   {
+      const double y = base[i];
+      double v = a * J.dV[i];
+      v += b * y;
+      if ( first )
+         J.Vs[i] = y;
+      J.V[i] = v;
+      J.L[i] = v;
+   }
+}
+
+int hs_trial_pair(hipStream_t s, long long n, double alpha, int first, const hs_trial_job* jobs)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   if ( n <= 0 ) return HS_OK;
+   hipLaunchKernelGGL(k_trial_pair, dim3(grid_for(n, 256, 2048), 2), dim3(256), 0, s, n, alpha, 1.0, first, jobs[0], jobs[1]);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
 int hs_axpy(hipStream_t s, long long n, double a, const double* x, double* y)
 {
    (void) hs_red_batch_flush();          /* inside a held region: behind the records */
@@ -386,6 +463,30 @@ int hs_unpack_sym(hipStream_t s, int n, const double* pk, double sa, const doubl
 {
    (void) hs_red_batch_flush();          /* inside a held region: behind the records */
    hipLaunchKernelGGL(k_unpack_sym, dim3(grid_for((long long) n * n, 256, 2048)), dim3(256), 0, s, n, pk, sa, add, out);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+int hs_unpack_sym3(hipStream_t s, int n, int cnt, const double* const* pk, double* const* out)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   if ( cnt < 1 || cnt > 3 )
+      return HS_ERR_ARG;
+   unpack3_args U = {{NULL, NULL, NULL}, {NULL, NULL, NULL}};
+   for (int k = 0; k < cnt; ++k)
+   {
+      U.pk[k] = pk[k]; U.out[k] = out[k];
+   }
+   hipLaunchKernelGGL(k_unpack_sym3, dim3(grid_for((long long) n * n, 256, 2048), cnt), dim3(256), 0, s, n, U);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+int hs_unpack_dz_combine(hipStream_t s, int n, const double* pk, const double* P2, const double* sc, int idtau, double eta, const double* Rd,
+   double* dZ)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   hipLaunchKernelGGL(k_unpack_dz_combine, dim3(grid_for((long long) n * n, 256, 2048)), dim3(256), 0, s, n, pk, P2, sc, idtau, eta, Rd, dZ);
    HS_LAUNCH_CHECK();
    return HS_OK;
 }
@@ -576,6 +677,14 @@ int hs_dirmat(hipStream_t s, int n, double s1, const double* Zinv, const double*
    return HS_OK;
 }
 
+int hs_dirmat_pack(hipStream_t s, int n, double s1, const double* Zinv, const double* X, const double* GZ, double* H, double* pk)
+{
+   (void) hs_red_batch_flush();          /* inside a held region: behind the records */
+   hipLaunchKernelGGL(k_dirmat_pack, dim3(grid_for((long long) n * n, 256, 2048)), dim3(256), 0, s, n, s1, Zinv, X, GZ, H, pk);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
 int hs_lp_dir(hipStream_t s, int q, double sigmu, double eta, const double* x, const double* z, const double* r,
    const double* elp, double* out)
 {
@@ -723,6 +832,8 @@ __global__ void __launch_bounds__(256) k_reduce_stage2(int nparts, const double*
 #define RB_COPY1 101
 #define RB_SOLVE 102      /* out[0:n] <- inv(L)^T inv(L) out[0:n] with a = inv(L) as 64 x 64, b = L as n x n (single-block factor, n <= 64); accumulate = number of right-hand sides, v = stride in doubles */
 #define RB_FINISH 103     /* the direction's closing element-wise kernel (k_finish_dir of ipm.hip) with its parameters in fin */
+#define RB_STAGE2 105     /* (105 & 31 = 9: a slot of the developer timing table that no other kind maps to) k_reduce_stage2<RED_DOT> of a dot whose first stage was launched on its own (hs_dot_deferred): p[0] = the partial
+                           * sums, i[0] = their number, p[3] = out */
 /* Round 3: the B&B-sized regime is bound by its launches (example_TT: 37 per iteration, 26 of them a few microseconds of work), so
  * the small single-workgroup kernels of an iteration can be recorded as well.  Every one of them does the arithmetic of its own
  * launch in the same order (element-wise kernels: any thread mapping gives the same bits; row sums of the passes: one thread /
@@ -869,6 +980,19 @@ __global__ void __launch_bounds__(256) k_red_batch(rb_args A)
       case RED_LPS0:     rb_run<RED_LPS0>(D, sh); break;
       case RB_FILL:      if ( threadIdx.x == 0 ) *(double*) D.p[3] = D.d[0]; break;
       case RB_COPY1:     if ( threadIdx.x == 0 ) *(double*) D.p[3] = *(const double*) D.p[0]; break;
+      case RB_STAGE2:
+      {
+         /* the statements of k_reduce_stage2 (256 threads there as here): the partial sums are combined in its order */
+         const double* part = (const double*) D.p[0];
+         double* out = (double*) D.p[3];
+         double v = OpSum::id();
+         for (int i = threadIdx.x; i < D.i[0]; i += 256)
+            v = OpSum::f(v, part[i]);
+         v = block_reduce_256<OpSum>(v, sh);
+         if ( threadIdx.x == 0 )
+            *out = D.accumulate ? OpSum::f(*out, v) : v;
+         break;
+      }
       case RB_DIRBLK:
          d_dir_block_small(D.i[0], D.d[0], (const double*) D.p[0], (const double*) D.p[1], (const double*) D.p[2], (const double*) D.p[3],
             D.d[1], (double*) D.p[4], rb_dyn);
@@ -1781,6 +1905,32 @@ static int reduce_launch(hipStream_t s, long long n, const double* a, const doub
 int hs_dot(hipStream_t s, long long n, const double* a, const double* b, double* out, int accumulate, double* ws)
 {
    return reduce_launch<RED_DOT>(s, n, a, b, NULL, out, accumulate, ws);
+}
+
+/* hs_dot of a long vector inside a batch opened by hs_red_batch_begin alone (no held region): the first stage is launched at once,
+ * in front of the records - it reads a and b and writes its partial sums, so no record of the batch may write a or b or read the
+ * partial sums: the engine's batches of this kind hold scalar fills and reductions only - and the second stage becomes a record:
+ * the batch's one launch then combines the partial sums in the order of k_reduce_stage2, behind the records before it (the fill of
+ * a slot that several dots accumulate into) and in front of those behind it (the direction's closing record reads the result).
+ * Two launches where a flush of the records so far, the two stages and a later batch launch were four.  slot: which 256 doubles of
+ * ws (at least 1024) hold the partial sums until the batch is launched - distinct for the deferred dots of one batch.  Anything else
+ * (no such batch, short vector, slot out of range) is hs_dot. */
+int hs_dot_deferred(hipStream_t s, long long n, const double* a, const double* b, double* out, int accumulate, double* ws, int slot)
+{
+   const int g = n > 0 ? grid_for(n, 2048, 256) : 0;
+   /* (a call that falls back after deferred ones is safe: hs_dot launches the records - the pending second stages - before its own first
+    * stage writes ws from offset 0) */
+   if ( !g_rb.open || g_rb.hold > 0 || s != g_rb.s || n <= RB_MAXN || g <= 1 || g > HS_DOT_SLOT_DOUBLES || slot < 0 || slot >= HS_DOT_SLOTS )
+      return hs_dot(s, n, a, b, out, accumulate, ws);
+   double* part = ws + HS_DOT_SLOT_DOUBLES * slot;
+   hipLaunchKernelGGL((k_reduce_stage1<RED_DOT>), dim3(g), dim3(256), 0, s, n, a, b, (const double*) NULL, part, out, accumulate, 0);
+   HS_LAUNCH_CHECK();
+   if ( g_rb.args.cnt == RB_MAX )
+      HS_CALL( rb_flush() );
+   rb_desc& D = g_rb.args.d[g_rb.args.cnt++];
+   memset(&D, 0, sizeof(D));
+   D.kind = RB_STAGE2; D.accumulate = accumulate; D.i[0] = g; D.p[0] = part; D.p[3] = out;
+   return HS_OK;
 }
 
 int hs_absmax(hipStream_t s, long long n, const double* a, double* out, int accumulate, double* ws)

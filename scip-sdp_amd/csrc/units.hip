@@ -758,6 +758,249 @@ extern "C" int hipsdp_potrf_small_unit(int device, int n, int pair, const double
    return HIPSDP_OK;
 }
 
+/* test entry: strict-mode factorization of two matrices of n rows (one behind the other in A), pair = 1 through hs_potrf_pair, 0 through
+ * two calls of hs_potrf.  dinv: hs_potrf_dinv_len(n) doubles per matrix - the staging blocks included - zero where nothing is written;
+ * fail[2]: each matrix's own flag */
+extern "C" long long hipsdp_potrf_dinv_len(int n) { return hs_potrf_dinv_len(n); }
+extern "C" int hipsdp_potrf_pair_unit(int device, int n, int pair, double* A, double* dinv, int* fail)
+{
+   if ( n < 1 || (pair != 0 && pair != 1) || A == NULL || dinv == NULL || fail == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   const long long nd = hs_potrf_dinv_len(n);
+   DevBuf dA, dD;
+   int* dflag = NULL;
+   HS_CALL( dA.alloc(2 * n2) ); HS_CALL( dD.alloc(2 * nd) );
+   HS_HIP( hipMalloc((void**) &dflag, 2 * sizeof(int)) );
+   HS_HIP( hipMemset(dflag, 0, 2 * sizeof(int)) );
+   HS_HIP( hipMemset(dD.p, 0, (size_t) (2 * nd) * sizeof(double)) );
+   HS_CALL( dA.up(A, 2 * n2) );
+   const hs_potrf_job jobs[2] = {{dA.p, dD.p, dflag}, {dA.p + n2, dD.p + nd, dflag + 1}};
+   int rc;
+   if ( pair )
+      rc = hs_potrf_pair(0, n, jobs);
+   else
+   {
+      rc = hs_potrf(0, n, jobs[0].A, jobs[0].dinv, jobs[0].flag, NULL);
+      if ( rc == HS_OK ) rc = hs_potrf(0, n, jobs[1].A, jobs[1].dinv, jobs[1].flag, NULL);
+   }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   int hflag[2] = {0, 0};
+   if ( rc == HS_OK && hipMemcpy(hflag, dflag, 2 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ) rc = HS_ERR_HIP;
+   (void) hipFree(dflag);
+   HS_CALL( rc );
+   HS_CALL( dA.down(A, 2 * n2) ); HS_CALL( dD.down(dinv, 2 * nd) );
+   fail[0] = hflag[0]; fail[1] = hflag[1];
+   return HIPSDP_OK;
+}
+
+/* test entry: the trial iterates of a step.  io holds eight arrays of n x n, one behind the other: X, Z, dX, dZ, Xs, Zs, Lx, Lz (all of
+ * them inputs, so that what a form leaves untouched shows; X, Z, Xs, Zs, Lx, Lz come back).  fused = 1: hs_trial_pair; 0: the launches
+ * it replaces - first: hs_copy(Vs, V); then hs_scale_add(alpha, dV, 1.0, Vs, V) and hs_copy(L, V) - for X, then for Z */
+extern "C" int hipsdp_trial_pair_unit(int device, int n, int fused, int first, double alpha, double* io)
+{
+   if ( n < 1 || (fused != 0 && fused != 1) || (first != 0 && first != 1) || io == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   DevBuf d;
+   HS_CALL( d.alloc(8 * n2) );
+   HS_CALL( d.up(io, 8 * n2) );
+   double* X = d.p; double* Z = d.p + n2; double* dX = d.p + 2 * n2; double* dZ = d.p + 3 * n2;
+   double* Xs = d.p + 4 * n2; double* Zs = d.p + 5 * n2; double* Lx = d.p + 6 * n2; double* Lz = d.p + 7 * n2;
+   const hs_trial_job tj[2] = {{X, dX, Xs, Lx}, {Z, dZ, Zs, Lz}};
+   int rc = HS_OK;
+   if ( fused )
+      rc = hs_trial_pair(0, n2, alpha, first, tj);
+   else
+      for (int k = 0; k < 2 && rc == HS_OK; ++k)
+      {
+         if ( first ) rc = hs_copy(0, tj[k].Vs, tj[k].V, n2);
+         if ( rc == HS_OK ) rc = hs_scale_add(0, n2, alpha, tj[k].dV, 1.0, tj[k].Vs, tj[k].V);
+         if ( rc == HS_OK ) rc = hs_copy(0, tj[k].L, tj[k].V, n2);
+      }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   HS_CALL( d.down(io, 8 * n2) );
+   return HIPSDP_OK;
+}
+
+/* ---- test entries of the merged launches between two Schur assemblies (general path): fused = 1 the merged launch, 0 the launches it
+ * replaces.  Outputs start as NaN on the device, so that what a form does not write shows */
+namespace {
+int nan_fill(DevBuf& d, long long n) { HS_HIP( hipMemset(d.p, 0xFF, (size_t) (n > 0 ? n : 1) * sizeof(double)) ); return HS_OK; }
+long long packed_len(int n) { const long long t = (long long) n * (n + 1) / 2; return t + (t & 1); }
+}
+
+/* k_after_solve2 + hs_make_ext twice: rhs2[2 m], u1[m] -> u2[m], wt[m + 1], e2[m + 1] = [1; u2], e1[m + 1] = [0; u1] */
+extern "C" int hipsdp_tail_after_solve2_unit(int device, int m, int fused, const double* rhs2, const double* u1, double* u2, double* wt,
+   double* e2, double* e1)
+{
+   if ( m < 1 || (fused != 0 && fused != 1) || rhs2 == NULL || u1 == NULL || u2 == NULL || wt == NULL || e2 == NULL || e1 == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   DevBuf dR, dU1, dU2, dW, dE2, dE1;
+   HS_CALL( dR.alloc(2 * m) ); HS_CALL( dU1.alloc(m) ); HS_CALL( dU2.alloc(m) ); HS_CALL( dW.alloc(m + 1) ); HS_CALL( dE2.alloc(m + 1) );
+   HS_CALL( dE1.alloc(m + 1) );
+   HS_CALL( nan_fill(dU2, m) ); HS_CALL( nan_fill(dW, m + 1) ); HS_CALL( nan_fill(dE2, m + 1) ); HS_CALL( nan_fill(dE1, m + 1) );
+   HS_CALL( dR.up(rhs2, 2 * m) ); HS_CALL( dU1.up(u1, m) );
+   int rc = hs_ipm_after_solve2(0, m, dR.p, dU2.p, dW.p, dU1.p, dE2.p, dE1.p, fused);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   HS_CALL( dU2.down(u2, m) ); HS_CALL( dW.down(wt, m + 1) ); HS_CALL( dE2.down(e2, m + 1) ); HS_CALL( dE1.down(e1, m + 1) );
+   return HIPSDP_OK;
+}
+
+/* three hs_unpack_sym: pk[3][Lp] (Lp = n (n + 1) / 2 rounded up to even) -> out[3][n][n] */
+extern "C" int hipsdp_tail_unpack3_unit(int device, int n, int fused, const double* pk, double* out)
+{
+   if ( n < 1 || (fused != 0 && fused != 1) || pk == NULL || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n, Lp = packed_len(n);
+   DevBuf dP, dO;
+   HS_CALL( dP.alloc(3 * Lp) ); HS_CALL( dO.alloc(3 * n2) ); HS_CALL( nan_fill(dO, 3 * n2) );
+   HS_CALL( dP.up(pk, 3 * Lp) );
+   int rc = HS_OK;
+   if ( fused )
+   {
+      const double* p3[3] = {dP.p, dP.p + Lp, dP.p + 2 * Lp};
+      double* o3[3] = {dO.p, dO.p + n2, dO.p + 2 * n2};
+      rc = hs_unpack_sym3(0, n, 3, p3, o3);
+   }
+   else
+      for (int k = 0; k < 3 && rc == HS_OK; ++k)
+         rc = hs_unpack_sym(0, n, dP.p + k * Lp, 0.0, NULL, dO.p + k * n2);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   return dO.down(out, 3 * n2);
+}
+
+/* hs_unpack_sym into dZ + the engine's k_dz_combine: pk[Lp], P2[n][n], Rd[n][n], dtau, eta -> dZ[n][n] */
+extern "C" int hipsdp_tail_dz_unit(int device, int n, int fused, const double* pk, const double* P2, const double* Rd, double dtau, double eta,
+   double* dZ)
+{
+   if ( n < 1 || (fused != 0 && fused != 1) || pk == NULL || P2 == NULL || Rd == NULL || dZ == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n, Lp = packed_len(n);
+   const int nsc = hs_ipm_sc_len(1);
+   DevBuf dP, dP2, dR, dZd, dS;
+   HS_CALL( dP.alloc(Lp) ); HS_CALL( dP2.alloc(n2) ); HS_CALL( dR.alloc(n2) ); HS_CALL( dZd.alloc(n2) ); HS_CALL( dS.alloc(nsc) );
+   HS_CALL( nan_fill(dZd, n2) );
+   std::vector<double> sc((size_t) nsc, 0.0);
+   sc[hs_ipm_sc_dtau()] = dtau;
+   HS_CALL( dS.up(sc.data(), nsc) ); HS_CALL( dP.up(pk, Lp) ); HS_CALL( dP2.up(P2, n2) ); HS_CALL( dR.up(Rd, n2) );
+   int rc;
+   if ( fused )
+      rc = hs_unpack_dz_combine(0, n, dP.p, dP2.p, dS.p, hs_ipm_sc_dtau(), eta, dR.p, dZd.p);
+   else
+   {
+      rc = hs_unpack_sym(0, n, dP.p, 0.0, NULL, dZd.p);
+      if ( rc == HS_OK ) rc = hs_ipm_dz_combine(0, n2, dZd.p, dP2.p, dS.p, eta, dR.p);
+   }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   return dZd.down(dZ, n2);
+}
+
+/* hs_dirmat + hs_pack_weighted of its result: Zinv, X, GZ [n][n], s1 -> H[n][n], pk[Lp] (the padding entry, if any, is not written) */
+extern "C" int hipsdp_tail_dirmat_unit(int device, int n, int fused, double s1, const double* Zinv, const double* X, const double* GZ, double* H,
+   double* pk)
+{
+   if ( n < 1 || (fused != 0 && fused != 1) || Zinv == NULL || X == NULL || GZ == NULL || H == NULL || pk == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n, Lp = packed_len(n);
+   DevBuf dZ, dX, dG, dH, dP;
+   HS_CALL( dZ.alloc(n2) ); HS_CALL( dX.alloc(n2) ); HS_CALL( dG.alloc(n2) ); HS_CALL( dH.alloc(n2) ); HS_CALL( dP.alloc(Lp) );
+   HS_CALL( nan_fill(dH, n2) ); HS_CALL( nan_fill(dP, Lp) );
+   HS_CALL( dZ.up(Zinv, n2) ); HS_CALL( dX.up(X, n2) ); HS_CALL( dG.up(GZ, n2) );
+   int rc;
+   if ( fused )
+      rc = hs_dirmat_pack(0, n, s1, dZ.p, dX.p, dG.p, dH.p, dP.p);
+   else
+   {
+      rc = hs_dirmat(0, n, s1, dZ.p, dX.p, dG.p, dH.p);
+      if ( rc == HS_OK ) rc = hs_pack_weighted(0, n, dH.p, dP.p);
+   }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   HS_CALL( dH.down(H, n2) );
+   return dP.down(pk, Lp);
+}
+
+/* the scalars of a direction and its closing kernel for one block of n rows and m variables (hs_ipm_dir_tail, the engine's own function):
+ * fused = 0: fill, the two stages of <B, H>, the dots over m, k_finish_dir as launches of their own; 1: first stage + one batch launch.
+ * B, H [n][n]; rhs2, rp, b, u1, u2 [m]; par = eta, rg, sigmu, tau, kappa, etk; sc: the scalar block (hipsdp_tail_sc_len() doubles,
+ * read and written); dy[m], dyt[m + 1] */
+extern "C" int hipsdp_tail_sc_len(void) { return hs_ipm_sc_len(1); }
+extern "C" int hipsdp_tail_dir_unit(int device, int m, int n, int fused, const double* B, const double* H, const double* rhs2, const double* rp,
+   const double* b, const double* u1, const double* u2, const double* par, double* sc, double* dy, double* dyt)
+{
+   if ( m < 1 || n < 1 || (fused != 0 && fused != 1) || B == NULL || H == NULL || rhs2 == NULL || rp == NULL || b == NULL || u1 == NULL
+         || u2 == NULL || par == NULL || sc == NULL || dy == NULL || dyt == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   const int nsc = hs_ipm_sc_len(1);
+   DevBuf dB, dH, dR, dRp, db, dU1, dU2, dS, dY, dYt, dW;
+   HS_CALL( dB.alloc(n2) ); HS_CALL( dH.alloc(n2) ); HS_CALL( dR.alloc(m) ); HS_CALL( dRp.alloc(m) ); HS_CALL( db.alloc(m) );
+   HS_CALL( dU1.alloc(m) ); HS_CALL( dU2.alloc(m) ); HS_CALL( dS.alloc(nsc) ); HS_CALL( dY.alloc(m) ); HS_CALL( dYt.alloc(m + 1) );
+   HS_CALL( dW.alloc(HS_RED_WS_DOUBLES) );
+   HS_CALL( nan_fill(dY, m) ); HS_CALL( nan_fill(dYt, m + 1) ); HS_CALL( nan_fill(dW, HS_RED_WS_DOUBLES) );
+   HS_CALL( dB.up(B, n2) ); HS_CALL( dH.up(H, n2) ); HS_CALL( dR.up(rhs2, m) ); HS_CALL( dRp.up(rp, m) ); HS_CALL( db.up(b, m) );
+   HS_CALL( dU1.up(u1, m) ); HS_CALL( dU2.up(u2, m) ); HS_CALL( dS.up(sc, nsc) );
+   const double* pB = dB.p; const double* pH = dH.p;
+   const hs_dir_tail_args ta = {m, 0, 1, &n, &pB, &pH, NULL, NULL, dR.p, dRp.p, db.p, dU1.p, dU2.p, dY.p, dYt.p, dS.p, dW.p, NULL, NULL,
+      par[0], par[1], par[2], par[3], par[4], par[5]};
+   hs_red_batch_reset();
+   int rc = hs_ipm_dir_tail(0, &ta, fused, 0);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   hs_red_batch_reset();
+   HS_CALL( rc );
+   HS_CALL( dS.down(sc, nsc) ); HS_CALL( dY.down(dy, m) );
+   return dYt.down(dyt, m + 1);
+}
+
+/* the reductions of the solves with M and of the residual pass: inside one batch  out[0] = 0;  out[0] += <a0, a1>;  out[1] = <a2, a2>;
+ * out[0] += <a0, a2>  (vectors of n^2 entries; several sums into one slot, slots of their own for the partial sums)  and
+ * out[2] = <v0, v1> (m entries); fused = 0: hs_dot, 1: hs_dot_deferred.  a[3][n^2], v[2][m], out[3] */
+extern "C" int hipsdp_tail_dots_unit(int device, int m, int n, int fused, const double* a, const double* v, double* out)
+{
+   if ( m < 1 || n < 1 || (fused != 0 && fused != 1) || a == NULL || v == NULL || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   DevBuf dA, dV, dO, dW;
+   HS_CALL( dA.alloc(3 * n2) ); HS_CALL( dV.alloc(2 * m) ); HS_CALL( dO.alloc(3) ); HS_CALL( dW.alloc(HS_RED_WS_DOUBLES) );
+   HS_CALL( nan_fill(dO, 3) ); HS_CALL( nan_fill(dW, HS_RED_WS_DOUBLES) );
+   HS_CALL( dA.up(a, 3 * n2) ); HS_CALL( dV.up(v, 2 * m) );
+   const double* a0 = dA.p; const double* a1 = dA.p + n2; const double* a2 = dA.p + 2 * n2;
+   hs_red_batch_reset();
+   hs_red_batch_begin(0);
+   int rc = hs_fill_scalar(0, dO.p, 0.0);
+   if ( fused )
+   {
+      if ( rc == HS_OK ) rc = hs_dot_deferred(0, n2, a0, a1, dO.p, 1, dW.p, 0);
+      if ( rc == HS_OK ) rc = hs_dot_deferred(0, n2, a2, a2, dO.p + 1, 0, dW.p, 1);
+      if ( rc == HS_OK ) rc = hs_dot_deferred(0, n2, a0, a2, dO.p, 1, dW.p, 2);
+   }
+   else
+   {
+      if ( rc == HS_OK ) rc = hs_dot(0, n2, a0, a1, dO.p, 1, dW.p);
+      if ( rc == HS_OK ) rc = hs_dot(0, n2, a2, a2, dO.p + 1, 0, dW.p);
+      if ( rc == HS_OK ) rc = hs_dot(0, n2, a0, a2, dO.p, 1, dW.p);
+   }
+   if ( rc == HS_OK ) rc = hs_dot(0, m, dV.p, dV.p + m, dO.p + 2, 0, dW.p);
+   if ( rc == HS_OK ) rc = hs_red_batch_end();
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   hs_red_batch_reset();
+   HS_CALL( rc );
+   return dO.down(out, 3);
+}
+
 extern "C" int hipsdp_trtri(int device, int n, const double* A, double* Linv)
 {
    HS_CALL( pick_device(device) );
