@@ -109,7 +109,8 @@ HIPSDP_API int  hipsdp_set_shape(hipsdp_solver* solver, int m, int nblocks, cons
  * against 4 (m + 1) n^3 + (m + 1)^2 n^2; never for n <= 64) is kept SPARSE: no (m + 1) x n^2 array is allocated, the matrices of the
  * variables stay the triplets of hipsdp_add_entries (what the reference backends hand DSDP / SDPA:
  * sdpisolver_dsdp.c:1126-1195, sdpisolver_sdpa.cpp:1223-1267), the constant matrix a dense n x n array.  Such a block takes
- * hipsdp_add_entries only (not hipsdp_set_block_dense / hipsdp_master_gather / hipsdp_gen_planted). */
+ * hipsdp_add_entries, or hipsdp_master_gather from a master block kept as triplets (hipsdp_master_define2), not
+ * hipsdp_set_block_dense / hipsdp_master_gather from a dense master block / hipsdp_gen_planted. */
 HIPSDP_API int  hipsdp_set_shape2(hipsdp_solver* solver, int m, int nblocks, const int* blocksizes, int q, const long long* nnz);
 HIPSDP_API int  hipsdp_block_is_sparse(hipsdp_solver* solver, int block);
 /* 0: never keep a block as nonzeros, 1 (default; environment HIPSDP_SPARSE): by the cost rule above, 2: whenever a count is given */
@@ -139,6 +140,27 @@ HIPSDP_API int  hipsdp_master_add_vars(hipsdp_solver* solver, int block, int nsl
    const int* const* col, const double* const* val);
 HIPSDP_API int  hipsdp_master_gather(hipsdp_solver* solver, int engine_block, int master_block, int nactive, const int* slots,
    int nkept, const int* kept);
+/* hipsdp_master_define with a storage per block: nnz == NULL or nnz[b] < 0 gives the dense slots x N x N array above, nnz[b] >= 0
+ * (the number of triplets to come; a hint) a master block KEPT AS TRIPLETS - nothing of size N^2 per slot is allocated.  Its entries
+ * (hipsdp_master_add_entries / _add_vars) are collected and checked on the host; the larger index is the row and a later entry at
+ * the same (slot, row, col) replaces an earlier one.  The first hipsdp_master_gather after the entries changed sorts and uploads
+ * them once (HIPSDP_ERR_ARG when the mirrored entries do not fit int offsets).  From such a block hipsdp_master_gather
+ *  - into an engine block kept as nonzeros builds the node's whole device structure on the device, in a number of launches that
+ *    does not depend on the sizes, with one read-back of the four counts, bit for bit what hipsdp_add_entries of the node's triplets
+ *    (active variables a + 1, rows renumbered through kept, entries on removed rows dropped) builds on the host.  The slots of
+ *    the active variables must be distinct.  Until the next hipsdp_set_shape* such a block takes hipsdp_add_entries for the constant
+ *    matrix only (var >= 1: HIPSDP_ERR_ARG), and it is valid until the master copy is defined again or the same master block is
+ *    gathered into another engine block;
+ *  - into a dense engine block zeroes and scatters the rows of the active variables in one launch: the bits of the dense master.
+ * A DENSE master block into an engine block kept as nonzeros stays an error. */
+HIPSDP_API int  hipsdp_master_define2(hipsdp_solver* solver, int nvars, int nblocks, const int* blocksizes, const int* nblockvars,
+   const long long* nnz);
+HIPSDP_API int  hipsdp_master_block_is_sparse(hipsdp_solver* solver, int master_block);
+/* totals of this solver (any pointer may be NULL): structures of blocks kept as nonzeros built on the device by hipsdp_master_gather /
+ * built on the host from the triplets of hipsdp_add_entries; kernel launches and device -> host synchronisations the gathers from
+ * triplet master blocks issued */
+HIPSDP_API int  hipsdp_master_gather_stats(hipsdp_solver* solver, long long* device_builds, long long* host_builds, long long* launches,
+   long long* readbacks);
 /* dense upload of a whole block: A[(m+1) * n * n] host, row-major */
 HIPSDP_API int  hipsdp_set_block_dense(hipsdp_solver* solver, int block, const double* A);
 /* LP rows: Dext[q x (m+1)] host, row-major, column 0 = c (constant), columns 1..m = D */

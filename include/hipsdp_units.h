@@ -126,6 +126,12 @@ HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* 
 /* stages 2 and 3 of the full decomposition above 128 rows (csrc/syevr.hip) alone on a caller's symmetric tridiagonal matrix, 2 <= n <= 512,
  * diagonal d[n], off-diagonal e[n - 1]: all eigenvalues (ascending) and the unit eigenvectors of T as the rows of Z (n x n) */
 HIPSDP_API int  hipsdp_tvec_unit(int device, int n, const double* d, const double* e, double* lam, double* Z);
+/* the device structure of engine block `block` of a solver CREATED FROM THIS LIBRARY (it contains the engine), a block kept as
+ * nonzeros - built first if triplets are waiting: counts[6] = n, m, nnz, npos, nfull, nslots, then every array that is not NULL:
+ * voff[m + 1], vrow / vcol / vval[nnz]; poff[npos + 1], prow / pcol[npos], pvar / pval[nnz]; foff[m + 1], frow / fcol / fval[nfull];
+ * soff[m + 1], srow[nslots], sent[nslots + 1].  A first call with the arrays NULL gives the counts to size them by. */
+HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long long* counts, int* voff, int* vrow, int* vcol, double* vval,
+   int* poff, int* prow, int* pcol, int* pvar, double* pval, int* foff, int* frow, int* fcol, double* fval, int* soff, int* srow, int* sent);
 
 #ifdef __cplusplus
 }

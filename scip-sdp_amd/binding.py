@@ -85,16 +85,19 @@ def device_count():
 class Solver:
     """thin RAII wrapper of hipsdp_solver"""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, units=False):
+        """units: the solver lives in libhipsdp_units.so's copy of the engine (what the unit entries that take a solver need:
+        sparse_dump)"""
+        self._l = ulib if units else lib
         self.h = C.c_void_p()
-        _chk(lib().hipsdp_create(C.byref(self.h), device), "hipsdp_create")
+        _chk(self._l().hipsdp_create(C.byref(self.h), device), "hipsdp_create")
         self.m = 0
         self.ns = []
         self.q = 0
 
     def close(self):
         if self.h:
-            lib().hipsdp_free(C.byref(self.h))
+            self._l().hipsdp_free(C.byref(self.h))
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -108,18 +111,18 @@ class Solver:
         pair formula the cheaper Schur assembly is kept as nonzeros)"""
         bs = np.asarray(blocksizes, dtype=np.int32)
         if nnz is None:
-            _chk(lib().hipsdp_set_shape(self.h, m, len(bs), _ip(bs), q), "hipsdp_set_shape")
+            _chk(self._l().hipsdp_set_shape(self.h, m, len(bs), _ip(bs), q), "hipsdp_set_shape")
         else:
             cnt = np.ascontiguousarray(nnz, dtype=np.int64)
             assert len(cnt) == len(bs)
-            _chk(lib().hipsdp_set_shape2(self.h, m, len(bs), _ip(bs), q, cnt.ctypes.data_as(C.POINTER(C.c_longlong))), "hipsdp_set_shape2")
+            _chk(self._l().hipsdp_set_shape2(self.h, m, len(bs), _ip(bs), q, cnt.ctypes.data_as(C.POINTER(C.c_longlong))), "hipsdp_set_shape2")
         self.m, self.ns, self.q = m, [int(v) for v in bs], q
 
     def sparse_policy(self, mode):
-        _chk(lib().hipsdp_sparse_policy(self.h, mode), "hipsdp_sparse_policy")
+        _chk(self._l().hipsdp_sparse_policy(self.h, mode), "hipsdp_sparse_policy")
 
     def is_sparse(self, k):
-        return bool(lib().hipsdp_block_is_sparse(self.h, k))
+        return bool(self._l().hipsdp_block_is_sparse(self.h, k))
 
     def load_sparse(self, m, n, b, coo, A0):
         """one block given as triplets of the variables' matrices (var 1 .. m, row >= col) and a dense constant matrix"""
@@ -135,48 +138,118 @@ class Solver:
 
     def set_obj(self, b):
         b = _f64(b)
-        _chk(lib().hipsdp_set_obj(self.h, _dp(b)), "hipsdp_set_obj")
+        _chk(self._l().hipsdp_set_obj(self.h, _dp(b)), "hipsdp_set_obj")
+
+    # ---- master copy (hipsdp_master_*): matrices of all variables in original indices, gathered per node on the device ----
+
+    def master_define(self, nvars, blocksizes, nblockvars=None, nnz=None):
+        """nnz: None - every block a dense slots x N x N array (hipsdp_master_define); a list - block b is kept as triplets where
+        nnz[b] >= 0 (hipsdp_master_define2)"""
+        bs = np.ascontiguousarray(blocksizes, dtype=np.int32)
+        bv = None if nblockvars is None else np.ascontiguousarray(nblockvars, dtype=np.int32)
+        if nnz is None:
+            _chk(self._l().hipsdp_master_define(self.h, nvars, len(bs), _ip(bs), None if bv is None else _ip(bv)), "hipsdp_master_define")
+        else:
+            cnt = np.ascontiguousarray(nnz, dtype=np.int64)
+            assert len(cnt) == len(bs)
+            _chk(self._l().hipsdp_master_define2(self.h, nvars, len(bs), _ip(bs), None if bv is None else _ip(bv),
+                                                 cnt.ctypes.data_as(C.POINTER(C.c_longlong))), "hipsdp_master_define2")
+
+    def master_block_is_sparse(self, b):
+        return bool(self._l().hipsdp_master_block_is_sparse(self.h, b))
+
+    def master_add_entries(self, b, slot, row, col, val):
+        slot = np.ascontiguousarray(slot, dtype=np.int32)
+        row = np.ascontiguousarray(row, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = _f64(val)
+        return self._l().hipsdp_master_add_entries(self.h, b, C.c_longlong(len(val)), _ip(slot), _ip(row), _ip(col), _dp(val))
+
+    def master_add_vars(self, b, rows, cols, vals):
+        """per-slot arrays: slot k has rows[k], cols[k], vals[k]"""
+        rs = [np.ascontiguousarray(r, dtype=np.int32) for r in rows]
+        cs = [np.ascontiguousarray(c, dtype=np.int32) for c in cols]
+        vs = [_f64(v) for v in vals]
+        k = len(vs)
+        nnz = np.array([len(v) for v in vs], dtype=np.int32)
+        PR = (C.POINTER(C.c_int) * max(k, 1))(*[_ip(r) for r in rs])
+        PC = (C.POINTER(C.c_int) * max(k, 1))(*[_ip(c) for c in cs])
+        PV = (C.POINTER(C.c_double) * max(k, 1))(*[_dp(v) for v in vs])
+        return self._l().hipsdp_master_add_vars(self.h, b, k, _ip(nnz), PR, PC, PV)
+
+    def master_gather(self, engine_block, master_block, slots, kept):
+        """return code of hipsdp_master_gather (0: done): slots[a] = slot of the a-th active variable or -1, kept = original rows"""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        kept = np.ascontiguousarray(kept, dtype=np.int32)
+        return self._l().hipsdp_master_gather(self.h, engine_block, master_block, len(slots), _ip(slots), len(kept), _ip(kept))
+
+    def master_gather_stats(self):
+        """(device_builds, host_builds, launches, readbacks) of this solver"""
+        v = [C.c_longlong(0) for _ in range(4)]
+        _chk(self._l().hipsdp_master_gather_stats(self.h, *[C.byref(x) for x in v]), "hipsdp_master_gather_stats")
+        return tuple(x.value for x in v)
+
+    def last_error(self):
+        return self._l().hipsdp_last_error().decode()
+
+    def sparse_dump(self, k):
+        """the device structure of block k, a block kept as nonzeros (hipsdp_sparse_dump_unit; the solver must have been created with
+        units=True): dict of the counts n, m, nnz, npos, nfull, nslots and the seventeen arrays"""
+        assert self._l is ulib
+        cnt = np.zeros(6, dtype=np.int64)
+        pc = cnt.ctypes.data_as(C.POINTER(C.c_longlong))
+        _chk(ulib().hipsdp_sparse_dump_unit(self.h, k, pc, *([None] * 16)), "hipsdp_sparse_dump_unit")
+        n, m, nnz, npos, nfull, nslots = [int(x) for x in cnt]
+        shape = [("voff", m + 1, 'i'), ("vrow", nnz, 'i'), ("vcol", nnz, 'i'), ("vval", nnz, 'd'), ("poff", npos + 1, 'i'), ("prow", npos, 'i'),
+                 ("pcol", npos, 'i'), ("pvar", nnz, 'i'), ("pval", nnz, 'd'), ("foff", m + 1, 'i'), ("frow", nfull, 'i'), ("fcol", nfull, 'i'),
+                 ("fval", nfull, 'd'), ("soff", m + 1, 'i'), ("srow", nslots, 'i'), ("sent", nslots + 1, 'i')]
+        arrs = [np.full(max(ln, 1), -7, dtype=np.int32 if t == 'i' else np.float64) for _, ln, t in shape]
+        _chk(ulib().hipsdp_sparse_dump_unit(self.h, k, pc, *[_ip(a) if a.dtype == np.int32 else _dp(a) for a in arrs]), "hipsdp_sparse_dump_unit")
+        out = dict(n=n, m=m, nnz=nnz, npos=npos, nfull=nfull, nslots=nslots)
+        for (name, ln, _), a in zip(shape, arrs):
+            out[name] = a[:ln].copy()
+        return out
 
     def set_block_dense(self, k, A):
         A = _f64(A)
         assert A.size == (self.m + 1) * self.ns[k] ** 2
-        _chk(lib().hipsdp_set_block_dense(self.h, k, _dp(A)), "hipsdp_set_block_dense")
+        _chk(self._l().hipsdp_set_block_dense(self.h, k, _dp(A)), "hipsdp_set_block_dense")
 
     def add_entries(self, k, var, row, col, val):
         var = np.ascontiguousarray(var, dtype=np.int32)
         row = np.ascontiguousarray(row, dtype=np.int32)
         col = np.ascontiguousarray(col, dtype=np.int32)
         val = _f64(val)
-        _chk(lib().hipsdp_add_entries(self.h, k, C.c_longlong(len(val)), _ip(var), _ip(row), _ip(col), _dp(val)),
+        _chk(self._l().hipsdp_add_entries(self.h, k, C.c_longlong(len(val)), _ip(var), _ip(row), _ip(col), _dp(val)),
              "hipsdp_add_entries")
 
     def set_lp(self, Dext):
         Dext = _f64(Dext)
-        _chk(lib().hipsdp_set_lp(self.h, _dp(Dext)), "hipsdp_set_lp")
+        _chk(self._l().hipsdp_set_lp(self.h, _dp(Dext)), "hipsdp_set_lp")
 
     def block_device_ptr(self, k):
         p = C.POINTER(C.c_double)()
-        _chk(lib().hipsdp_block_device_ptr(self.h, k, C.byref(p)), "hipsdp_block_device_ptr")
+        _chk(self._l().hipsdp_block_device_ptr(self.h, k, C.byref(p)), "hipsdp_block_device_ptr")
         return C.cast(p, C.c_void_p).value
 
     def gen_planted(self, n, m, seed, Xstar, Zstar, ystar):
         """device-side synthetic instance (see hipsdp_gen_planted); returns b"""
         Xstar, Zstar, ystar = _f64(Xstar), _f64(Zstar), _f64(ystar)
         b = np.zeros(m)
-        _chk(lib().hipsdp_gen_planted(self.h, n, m, C.c_longlong(seed), _dp(Xstar), _dp(Zstar), _dp(ystar), _dp(b)),
+        _chk(self._l().hipsdp_gen_planted(self.h, n, m, C.c_longlong(seed), _dp(Xstar), _dp(Zstar), _dp(ystar), _dp(b)),
              "hipsdp_gen_planted")
         return b
 
     def gen_planted_density(self, n, m, seed, density, Xstar, Zstar, ystar):
         Xstar, Zstar, ystar = _f64(Xstar), _f64(Zstar), _f64(ystar)
         b = np.zeros(m)
-        _chk(lib().hipsdp_gen_planted_density(self.h, n, m, C.c_longlong(seed), C.c_double(density), _dp(Xstar), _dp(Zstar), _dp(ystar),
+        _chk(self._l().hipsdp_gen_planted_density(self.h, n, m, C.c_longlong(seed), C.c_double(density), _dp(Xstar), _dp(Zstar), _dp(ystar),
                                               _dp(b)), "hipsdp_gen_planted_density")
         return b
 
     def get_block_dense(self, k):
         A = np.zeros((self.m + 1, self.ns[k], self.ns[k]))
-        _chk(lib().hipsdp_get_block_dense(self.h, k, _dp(A)), "hipsdp_get_block_dense")
+        _chk(self._l().hipsdp_get_block_dense(self.h, k, _dp(A)), "hipsdp_get_block_dense")
         return A
 
     def load_core(self, prob):
@@ -197,53 +270,53 @@ class Solver:
         PZ = (C.POINTER(C.c_double) * max(len(Zs), 1))(*[_dp(M) for M in Zs])
         xx = _f64(x if x is not None else np.zeros(max(self.q, 1)))
         zz = _f64(z if z is not None else np.zeros(max(self.q, 1)))
-        _chk(lib().hipsdp_set_start(self.h, _dp(y), PX, PZ, _dp(xx), _dp(zz)), "hipsdp_set_start")
+        _chk(self._l().hipsdp_set_start(self.h, _dp(y), PX, PZ, _dp(xx), _dp(zz)), "hipsdp_set_start")
 
     def solve(self, **kw):
         p = Params()
-        lib().hipsdp_default_params(C.byref(p))
+        self._l().hipsdp_default_params(C.byref(p))
         for k, v in kw.items():
             setattr(p, k, v)
         info = Info()
-        _chk(lib().hipsdp_solve(self.h, C.byref(p), C.byref(info)), "hipsdp_solve")
+        _chk(self._l().hipsdp_solve(self.h, C.byref(p), C.byref(info)), "hipsdp_solve")
         return info
 
     def solve_path(self):
         """1: the last solve ran in the one-launch kernel of csrc/solve1.hip, 0: the general path"""
-        return lib().hipsdp_solve_path(self.h)
+        return self._l().hipsdp_solve_path(self.h)
 
     def gram_cache_stats(self):
         """(hits, misses) of this solver's cold-start store: cold solves that copied the first Schur matrix / computed and stored it"""
         hits = C.c_longlong(0)
         misses = C.c_longlong(0)
-        _chk(lib().hipsdp_gram_cache_stats(self.h, C.byref(hits), C.byref(misses)), "hipsdp_gram_cache_stats")
+        _chk(self._l().hipsdp_gram_cache_stats(self.h, C.byref(hits), C.byref(misses)), "hipsdp_gram_cache_stats")
         return hits.value, misses.value
 
     def solve1_trace(self, rows=0):
         out = np.zeros(64)
         hist = np.zeros((max(rows, 1), 16))
-        _chk(lib().hipsdp_solve1_trace(self.h, _dp(out), rows, _dp(hist) if rows else None), "hipsdp_solve1_trace")
+        _chk(self._l().hipsdp_solve1_trace(self.h, _dp(out), rows, _dp(hist) if rows else None), "hipsdp_solve1_trace")
         return out, hist[:rows]
 
     def y(self):
         out = np.zeros(self.m)
-        _chk(lib().hipsdp_get_y(self.h, _dp(out)), "hipsdp_get_y")
+        _chk(self._l().hipsdp_get_y(self.h, _dp(out)), "hipsdp_get_y")
         return out
 
     def X(self, k):
         out = np.zeros((self.ns[k], self.ns[k]))
-        _chk(lib().hipsdp_get_X(self.h, k, _dp(out)), "hipsdp_get_X")
+        _chk(self._l().hipsdp_get_X(self.h, k, _dp(out)), "hipsdp_get_X")
         return out
 
     def Z(self, k):
         out = np.zeros((self.ns[k], self.ns[k]))
-        _chk(lib().hipsdp_get_Z(self.h, k, _dp(out)), "hipsdp_get_Z")
+        _chk(self._l().hipsdp_get_Z(self.h, k, _dp(out)), "hipsdp_get_Z")
         return out
 
     def lp(self):
         x = np.zeros(self.q)
         z = np.zeros(self.q)
-        _chk(lib().hipsdp_get_lp(self.h, _dp(x), _dp(z)), "hipsdp_get_lp")
+        _chk(self._l().hipsdp_get_lp(self.h, _dp(x), _dp(z)), "hipsdp_get_lp")
         return x, z
 
     def preoptimal(self):
@@ -251,13 +324,13 @@ class Solver:
         avail = C.c_int(0)
         y = np.zeros(max(1, self.m))
         x = np.zeros(max(1, self.q))
-        _chk(lib().hipsdp_get_preoptimal(self.h, C.byref(avail), _dp(y), _dp(x)), "hipsdp_get_preoptimal")
+        _chk(self._l().hipsdp_get_preoptimal(self.h, C.byref(avail), _dp(y), _dp(x)), "hipsdp_get_preoptimal")
         if not avail.value:
             return None
         Xs = []
         for k, n in enumerate(self.ns):
             X = np.zeros((n, n))
-            _chk(lib().hipsdp_get_preoptimal_X(self.h, k, _dp(X)), "hipsdp_get_preoptimal_X")
+            _chk(self._l().hipsdp_get_preoptimal_X(self.h, k, _dp(X)), "hipsdp_get_preoptimal_X")
             Xs.append(X)
         return y[:self.m], Xs, x[:self.q]
 
@@ -267,9 +340,9 @@ class Solver:
         lmin = np.zeros(max(1, len(self.ns)))
         viol = C.c_double(0.0)
         if tol > 0.0:
-            _chk(lib().hipsdp_check_y_tol(self.h, _dp(y), C.c_double(tol), _dp(lmin), C.byref(viol)), "hipsdp_check_y_tol")
+            _chk(self._l().hipsdp_check_y_tol(self.h, _dp(y), C.c_double(tol), _dp(lmin), C.byref(viol)), "hipsdp_check_y_tol")
         else:
-            _chk(lib().hipsdp_check_y(self.h, _dp(y), _dp(lmin), C.byref(viol)), "hipsdp_check_y")
+            _chk(self._l().hipsdp_check_y(self.h, _dp(y), _dp(lmin), C.byref(viol)), "hipsdp_check_y")
         return lmin[:len(self.ns)], viol.value
 
     def eigencuts(self, block, y, tol, maxcuts):
@@ -281,7 +354,7 @@ class Solver:
         co = np.zeros((max(1, maxcuts), max(1, m)))
         lh = np.zeros(max(1, maxcuts))
         ve = np.zeros((max(1, maxcuts), n))
-        _chk(lib().hipsdp_eigencuts(self.h, block, _dp(y), C.c_double(tol), maxcuts, C.byref(k), _dp(ev), _dp(co), _dp(lh), _dp(ve)),
+        _chk(self._l().hipsdp_eigencuts(self.h, block, _dp(y), C.c_double(tol), maxcuts, C.byref(k), _dp(ev), _dp(co), _dp(lh), _dp(ve)),
              "hipsdp_eigencuts")
         return ev[:k.value], co[:k.value, :m], lh[:k.value], ve[:k.value]
 
@@ -298,7 +371,7 @@ class Solver:
         ve = np.zeros(max(1, maxcuts * sum(self.ns)))
         if m > 0 and maxcuts > 0:
             co = np.zeros((max(1, nb), maxcuts, m))
-        _chk(lib().hipsdp_eigencuts_all(self.h, _dp(y), C.c_double(tol), maxcuts, _ip(k), _dp(lmin), _dp(ev), _dp(co), _dp(lh), _dp(ve)),
+        _chk(self._l().hipsdp_eigencuts_all(self.h, _dp(y), C.c_double(tol), maxcuts, _ip(k), _dp(lmin), _dp(ev), _dp(co), _dp(lh), _dp(ve)),
              "hipsdp_eigencuts_all")
         out, off = [], 0
         for b, n in enumerate(self.ns):

@@ -184,7 +184,36 @@ int  hs_allgather_inplace(void* comm, double* buf, long long count_per_rank, int
 int  hs_allgather(void* comm, const double* send, double* recv, long long count_per_rank, hipStream_t stream);
 
 /* ---- sparse.hip: constraint matrices kept as nonzeros (see there) ----------------------------------------------------- */
-struct hs_sparse;
+struct hs_sparse
+{
+   int        n, m;
+   long long  nnz;
+   /* by variable: entries of variable v (1 .. m) are [voff[v - 1], voff[v]) */
+   int*       voff;
+   int*       vrow;
+   int*       vcol;
+   double*    vval;
+   /* by position: position k (a lower-triangular (row, col) that occurs) has the entries [poff[k], poff[k + 1]) */
+   long long  npos;
+   int*       poff;
+   int*       prow;
+   int*       pcol;
+   int*       pvar;        /* variable (1-based) of an entry */
+   double*    pval;
+   /* FULL symmetric entries by variable, row-major (the two-stage Schur assembly): entries of variable v are [foff[v - 1], foff[v]),
+    * entry e = (frow[e], fcol[e], fval[e]); the non-empty rows of variable v are the slots [soff[v - 1], soff[v]): slot s is row
+    * srow[s] with the entries [sent[s], sent[s + 1]); Tc: nslots x n doubles of workspace, Tc[s][c] = (A_v Zinv)[srow[s]][c] */
+   long long  nfull, nslots;
+   int*       foff;
+   int*       frow;
+   int*       fcol;
+   double*    fval;
+   int*       soff;
+   int*       srow;
+   int*       sent;
+   double*    Tc;
+   int        borrowed;    /* 1: every array above belongs to the gather workspace of a triplet master block (sp_master.hip): not freed here */
+};
 int  hs_sp_prefers_sparse(int n, int m, long long nnz);
 int  hs_sp_build(hs_sparse** out, int n, int m, long long nnz, const int* var, const int* row, const int* col, const double* val);
 void hs_sp_free(hs_sparse* sp);
@@ -193,6 +222,25 @@ int  hs_sp_apply_A(hipStream_t s, const hs_sparse* sp, const double* V, double* 
 int  hs_sp_apply_AT(hipStream_t s, const hs_sparse* sp, const double* coef, double* out);        /* out += sum_{v >= 1} coef[v] A_v */
 int  hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx);   /* lower triangle, i, j >= 1 */
 int  hs_sp_expand(hipStream_t s, const hs_sparse* sp, double* A);
+
+/* ---- sp_master.hip: master copy of a block kept as triplets in ORIGINAL indices, and the gather of a node from it ------- */
+struct hs_spm;
+int  hs_spm_create(hs_spm** out, int N, int S);
+void hs_spm_free(hs_spm* M);
+int  hs_spm_size(const hs_spm* M);
+int  hs_spm_slots(const hs_spm* M);
+/* collects entries on the host (indices checked: HS_ERR_ARG and nothing taken); slot == NULL: all entries belong to `oneslot` */
+int  hs_spm_add(hs_spm* M, long long nnz, const int* slot, int oneslot, const int* row, const int* col, const double* val);
+/* the complete structure of the node (n kept rows, m variables of which the first nactive are act[a] = slot or -1) in the block's
+ * workspace: *out is a borrowed hs_sparse (hs_sp_free releases only the handle).  launches / readbacks are added to. */
+int  hs_spm_gather_sparse(hipStream_t s, hs_spm* M, int n, int m, int nactive, const int* act, const int* kept, hs_sparse** out,
+   long long* launches, long long* readbacks);
+/* A[(a + 1) n^2 ..] = the matrix of slot dact[a] restricted to the kept rows (dinv[N]: new index of an original row, -1 removed),
+ * zeros elsewhere; dact, dinv are device-visible: one launch */
+int  hs_spm_gather_dense(hipStream_t s, hs_spm* M, int n, int nactive, const int* dact, const int* dinv, double* A, long long* launches);
+/* ipm.hip: the device structure of a sparse block of a solver, built if need be (csrc/units.hip: hipsdp_sparse_dump_unit) */
+struct hipsdp_solver;
+int  hs_solver_sparse_block(struct hipsdp_solver* s, int block, const hs_sparse** sp);
 
 /* ---- ipm.hip: pieces of an iteration's tail that have a unit entry (tests/test_gpu_tail_fusions.py) ------------------ */
 struct hs_dir_tail_args { int m, q, K; const int* n; const double* const* B; const double* const* H; const double* beta; const double* hl;

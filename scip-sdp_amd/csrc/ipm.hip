@@ -14,6 +14,7 @@
  */
 #include "hs_kernels.h"
 #include "hs_gram_cache.h"
+#include "hs_sp_master.h"
 #include "../../include/hipsdp.h"
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include <vector>
@@ -83,6 +84,10 @@ struct Block
    bool sp_dirty;
    hs_sparse* sp;
    struct SpHost* sph;
+   /* sp was built on the device by hipsdp_master_gather from the triplet master block sp_master and lives in that block's workspace:
+    * there are no host triplets behind it (hipsdp_add_entries takes the constant matrix only until the next set_shape) */
+   bool sp_gathered;
+   int sp_master;
 };
 
 struct SpHost
@@ -161,7 +166,9 @@ struct hipsdp_solver
    int master_nvars;
    std::vector<int> master_sizes;
    std::vector<int> master_slots;         /* per master block: number of variable slots */
-   std::vector<double*> master_A;
+   std::vector<double*> master_A;         /* NULL for a block kept as triplets ... */
+   std::vector<hs_spm*> master_sp;        /* ... which lives here (csrc/sp_master.hip); NULL for a dense block */
+   long long mg_device_builds, mg_host_builds, mg_launches, mg_readbacks;      /* hipsdp_master_gather_stats */
    /* multi GPU */
    void* comm; int rank, nranks;
    double* passg;          /* gather buffer of the row-sharded passes: nranks * ceil(m1 / nranks) doubles */
@@ -552,6 +559,7 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->passg = NULL;
    s->shard_passes = getenv("HIPSDP_SHARD_PASSES") != NULL ? atoi(getenv("HIPSDP_SHARD_PASSES")) : -1;
    s->master_nvars = 0;
+   s->mg_device_builds = s->mg_host_builds = s->mg_launches = s->mg_readbacks = 0;
    s->Mgather = NULL;
    s->schur_mode_rows = false;
    s->schur_mode_cols = false; s->schur_sim_shards = 0;
@@ -609,7 +617,17 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
 
 static void master_free(hipsdp_solver* s)
 {
-   for (double* p : s->master_A) dfree(p);
+   /* a block gathered from a triplet master block points into that block's workspace: it goes with it (ensure_sparse then refuses
+    * the block until it is loaded again) */
+   for (auto& B : s->blk)
+      if ( B.sparse && B.sp_gathered && B.sp != NULL )
+      {
+         hs_sp_free(B.sp);
+         B.sp = NULL;
+      }
+   for (double* p : s->master_A) if ( p != NULL ) dfree(p);
+   for (hs_spm* M : s->master_sp) hs_spm_free(M);
+   s->master_sp.clear();
    s->master_A.clear();
    s->master_sizes.clear();
    s->master_slots.clear();
@@ -767,6 +785,7 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
                free_sparse(B);
                B.sph = new SpHost();
                B.sp_dirty = true;
+               B.sp_gathered = false;
             }
             else
                HS_CALL( stage_zero(s, B.Aown, m1s * B.n * B.n) );
@@ -987,6 +1006,14 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
    {
       /* variables: collected on the host (built into the device structure before the next use); constant matrix: dense scatter */
       std::vector<int> cv, cr, cc; std::vector<double> cx;
+      if ( B.sp_gathered )
+         for (long long e = 0; e < nnz; ++e)
+            if ( var[e] >= 1 )
+            {
+               set_err("hipsdp_add_entries: the matrices of this block were gathered from the master copy; only the constant matrix "
+                  "(var 0) can be set until the next hipsdp_set_shape");
+               return HIPSDP_ERR_ARG;
+            }
       for (long long e = 0; e < nnz; ++e)
       {
          if ( var[e] < 0 || var[e] > s->m || row[e] < 0 || row[e] >= B.n || col[e] < 0 || col[e] >= B.n )
@@ -1003,7 +1030,8 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
             B.sph->var.push_back(var[e]); B.sph->row.push_back(row[e]); B.sph->col.push_back(col[e]); B.sph->val.push_back(val[e]);
          }
       }
-      B.sp_dirty = true;
+      if ( !B.sp_gathered )
+         B.sp_dirty = true;
       s->solved = false;
       if ( cv.empty() )
          return HIPSDP_OK;
@@ -1097,6 +1125,31 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
  * sdprow/sdpcol/sdpval arrays do not change between the nodes of a branch-and-bound run). */
 extern "C" int hipsdp_master_define(hipsdp_solver* s, int nvars, int nblocks, const int* blocksizes, const int* nblockvars)
 {
+   return hipsdp_master_define2(s, nvars, nblocks, blocksizes, nblockvars, NULL);
+}
+
+extern "C" int hipsdp_master_block_is_sparse(hipsdp_solver* s, int master_block)
+{
+   if ( s == NULL || master_block < 0 || master_block >= (int) s->master_sp.size() )
+      return 0;
+   return s->master_sp[master_block] != NULL ? 1 : 0;
+}
+
+extern "C" int hipsdp_master_gather_stats(hipsdp_solver* s, long long* device_builds, long long* host_builds, long long* launches,
+   long long* readbacks)
+{
+   if ( s == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( device_builds != NULL ) *device_builds = s->mg_device_builds;
+   if ( host_builds != NULL ) *host_builds = s->mg_host_builds;
+   if ( launches != NULL ) *launches = s->mg_launches;
+   if ( readbacks != NULL ) *readbacks = s->mg_readbacks;
+   return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_master_define2(hipsdp_solver* s, int nvars, int nblocks, const int* blocksizes, const int* nblockvars,
+   const long long* nnz)
+{
    if ( s == NULL || nvars < 0 || nblocks < 0 )
       return HIPSDP_ERR_ARG;
    HS_HIP( hipSetDevice(s->device) );
@@ -1113,6 +1166,17 @@ extern "C" int hipsdp_master_define(hipsdp_solver* s, int nvars, int nblocks, co
       const int slots = nblockvars != NULL ? nblockvars[b] : nvars;
       if ( slots < 0 || slots > nvars )
          return HIPSDP_ERR_ARG;
+      if ( nnz != NULL && nnz[b] >= 0 )
+      {
+         /* kept as triplets: collected on the host, sorted and uploaded by the first gather (csrc/sp_master.hip) */
+         hs_spm* M = NULL;
+         HS_CALL( hs_spm_create(&M, blocksizes[b], slots) );
+         s->master_A.push_back(NULL);
+         s->master_sp.push_back(M);
+         s->master_sizes.push_back(blocksizes[b]);
+         s->master_slots.push_back(slots);
+         continue;
+      }
       const long long cnt = (long long) slots * blocksizes[b] * blocksizes[b];
       const int rc = dalloc(&p, cnt);
       if ( rc != HS_OK )
@@ -1122,6 +1186,7 @@ extern "C" int hipsdp_master_define(hipsdp_solver* s, int nvars, int nblocks, co
       }
       HS_HIP( hipMemsetAsync(p, 0, (size_t) (cnt > 0 ? cnt : 1) * sizeof(double), s->stream) );
       s->master_A.push_back(p);
+      s->master_sp.push_back(NULL);
       s->master_sizes.push_back(blocksizes[b]);
       s->master_slots.push_back(slots);
    }
@@ -1136,6 +1201,15 @@ extern "C" int hipsdp_master_add_entries(hipsdp_solver* s, int block, long long 
       return HIPSDP_ERR_ARG;
    if ( nnz == 0 )
       return HIPSDP_OK;
+   if ( s->master_sp[block] != NULL )
+   {
+      if ( hs_spm_add(s->master_sp[block], nnz, var, 0, row, col, val) != HS_OK )
+      {
+         set_err("hipsdp_master_add_entries: index out of range");
+         return HIPSDP_ERR_ARG;
+      }
+      return HIPSDP_OK;
+   }
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    const int n = s->master_sizes[block];
@@ -1211,6 +1285,16 @@ extern "C" int hipsdp_master_add_vars(hipsdp_solver* s, int block, int nslots, c
    }
    if ( total == 0 )
       return HIPSDP_OK;
+   if ( s->master_sp[block] != NULL )
+   {
+      for (int k = 0; k < nslots; ++k)
+         if ( nnz[k] > 0 && hs_spm_add(s->master_sp[block], nnz[k], NULL, k, row[k], col[k], val[k]) != HS_OK )
+         {
+            set_err("hipsdp_master_add_vars: index out of range");
+            return HIPSDP_ERR_ARG;
+         }
+      return HIPSDP_OK;
+   }
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    HS_CALL( stage_ensure(s, total) );
@@ -1299,17 +1383,97 @@ __global__ void k_master_gather(int nactive, int nk, int N, const int* __restric
    }
 }
 
+/* from a master block kept as triplets (csrc/sp_master.hip): into a block kept as nonzeros the node's whole structure is built on the
+ * device, in the master block's workspace; into a dense block the rows of the active variables are cleared and scattered */
+static int master_gather_triplets(hipsdp_solver* s, int engine_block, int master_block, int nactive, const int* activevars, int nkept,
+   const int* kept)
+{
+   hs_spm* M = s->master_sp[master_block];
+   Block& B = s->blk[engine_block];
+   const int N = hs_spm_size(M), S = hs_spm_slots(M);
+   HS_HIP( hipSetDevice(s->device) );
+   if ( B.sparse )
+   {
+      /* the workspace holds one node: whoever held it before (this block's last load, another block) loses it */
+      for (auto& O : s->blk)
+         if ( O.sparse && O.sp_gathered && O.sp_master == master_block && O.sp != NULL )
+         {
+            HS_HIP( hipStreamSynchronize(s->stream) );
+            hs_sp_free(O.sp);
+            O.sp = NULL;
+         }
+      if ( B.sp != NULL )
+         hs_sp_free(B.sp);
+      B.sp = NULL;
+      if ( B.sph != NULL && !B.sph->var.empty() )
+      {
+         set_err("hipsdp_master_gather: the block already has entries of hipsdp_add_entries for its variables");
+         return HIPSDP_ERR_ARG;
+      }
+      const int rc = hs_spm_gather_sparse(s->stream, M, B.n, s->m, nactive, activevars, kept, &B.sp, &s->mg_launches, &s->mg_readbacks);
+      if ( rc != HS_OK )
+      {
+         if ( rc == HS_ERR_ARG )
+            set_err("hipsdp_master_gather: slot or row out of range, a slot named twice, rows not increasing, or too many entries");
+         return rc;
+      }
+      B.sp_gathered = true;
+      B.sp_master = master_block;
+      B.sp_dirty = false;
+      ++s->mg_device_builds;
+      s->solved = false;
+      return HIPSDP_OK;
+   }
+   /* dense engine block: slots and the inverse of kept through the arena, one launch */
+   std::vector<int> inv((size_t) N), svar((size_t) (S > 0 ? S : 1));
+   int ordered = 1;
+   if ( hs_spm_node_maps(N, S, nactive, activevars, nkept, kept, inv.data(), svar.data(), &ordered) != HIPSDP_OK )
+   {
+      set_err("hipsdp_master_gather: slot or row out of range, a slot named twice or rows not increasing");
+      return HIPSDP_ERR_ARG;
+   }
+   if ( nactive == 0 )
+      return HIPSDP_OK;
+   a_written(s, B);
+   HS_CALL( flush_cmds(s) );                 /* (the clears of set_shape come first) */
+   void* dv = NULL;
+   int* hidx = (int*) stage_take(s, (size_t) (nactive + N) * sizeof(int), &dv);
+   if ( hidx != NULL )
+   {
+      memcpy(hidx, activevars, (size_t) nactive * sizeof(int));
+      memcpy(hidx + nactive, inv.data(), (size_t) N * sizeof(int));
+      const int* didx = (const int*) dv;
+      HS_CALL( hs_spm_gather_dense(s->stream, M, nkept, nactive, didx, didx + nactive, B.A, &s->mg_launches) );
+      s->stage_pending = true;
+   }
+   else
+   {
+      int *dact, *dinv;
+      HS_CALL( dalloc(&dact, nactive) ); HS_CALL( dalloc(&dinv, N) );
+      HS_HIP( hipMemcpyAsync(dact, activevars, (size_t) nactive * sizeof(int), hipMemcpyHostToDevice, s->stream) );
+      HS_HIP( hipMemcpyAsync(dinv, inv.data(), (size_t) N * sizeof(int), hipMemcpyHostToDevice, s->stream) );
+      HS_CALL( hs_spm_gather_dense(s->stream, M, nkept, nactive, dact, dinv, B.A, &s->mg_launches) );
+      HS_HIP( hipStreamSynchronize(s->stream) );
+      ++s->mg_readbacks;
+      dfree(dact); dfree(dinv);
+   }
+   s->solved = false;
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_master_gather(hipsdp_solver* s, int engine_block, int master_block, int nactive, const int* activevars,
    int nkept, const int* kept)
 {
    if ( s == NULL || !s->shaped || engine_block < 0 || engine_block >= (int) s->blk.size() || master_block < 0
       || master_block >= (int) s->master_A.size() || nactive < 0 || nactive > s->m || nkept != s->blk[engine_block].n )
       return HIPSDP_ERR_ARG;
-   if ( s->shardA || s->blk[engine_block].sparse )
+   if ( s->shardA || (s->blk[engine_block].sparse && s->master_sp[master_block] == NULL) )
    {
       set_err("hipsdp_master_gather: not available with matrices sharded by variable or kept as nonzeros");
       return HIPSDP_ERR_ARG;
    }
+   if ( s->master_sp[master_block] != NULL )
+      return master_gather_triplets(s, engine_block, master_block, nactive, activevars, nkept, kept);
    if ( nactive == 0 )
       return HIPSDP_OK;
    HS_HIP( hipSetDevice(s->device) );
@@ -1473,6 +1637,31 @@ extern "C" int hipsdp_get_block_dense(hipsdp_solver* s, int block, double* A)
       const size_t n2 = (size_t) B.n * B.n;
       memset(A, 0, (size_t) (s->m + 1) * n2 * sizeof(double));
       HS_HIP( hipMemcpy(A, B.A0, n2 * sizeof(double), hipMemcpyDeviceToHost) );
+      if ( B.sp_gathered )
+      {
+         /* no host triplets: the by-variable list of the device structure */
+         if ( B.sp == NULL )
+            return HIPSDP_ERR_ARG;
+         HS_HIP( hipStreamSynchronize(s->stream) );
+         const size_t nz = (size_t) B.sp->nnz;
+         std::vector<int> voff((size_t) s->m + 1), vrow(nz + 1), vcol(nz + 1);
+         std::vector<double> vval(nz + 1);
+         HS_HIP( hipMemcpy(voff.data(), B.sp->voff, voff.size() * sizeof(int), hipMemcpyDeviceToHost) );
+         if ( nz > 0 )
+         {
+            HS_HIP( hipMemcpy(vrow.data(), B.sp->vrow, nz * sizeof(int), hipMemcpyDeviceToHost) );
+            HS_HIP( hipMemcpy(vcol.data(), B.sp->vcol, nz * sizeof(int), hipMemcpyDeviceToHost) );
+            HS_HIP( hipMemcpy(vval.data(), B.sp->vval, nz * sizeof(double), hipMemcpyDeviceToHost) );
+         }
+         for (int v = 1; v <= s->m; ++v)
+            for (int e = voff[(size_t) v - 1]; e < voff[(size_t) v]; ++e)
+            {
+               double* a = A + (size_t) v * n2;
+               a[(size_t) vrow[e] * B.n + vcol[e]] = vval[e];
+               a[(size_t) vcol[e] * B.n + vrow[e]] = vval[e];
+            }
+         return HIPSDP_OK;
+      }
       const SpHost& h = *B.sph;
       for (size_t e = 0; e < h.var.size(); ++e)
       {
@@ -2112,13 +2301,33 @@ static int ensure_sparse(hipsdp_solver* s)
    for (auto& B : s->blk)
       if ( B.sparse && (B.sp_dirty || B.sp == NULL) )
       {
+         if ( B.sp_gathered )
+         {
+            set_err("a block gathered from the master copy lost its structure (the master copy was defined again, or its master block "
+               "gathered into another block): load the block again");
+            return HS_ERR_ARG;
+         }
          if ( B.sp != NULL ) hs_sp_free(B.sp);
          B.sp = NULL;
          HS_HIP( hipStreamSynchronize(s->stream) );
          const SpHost& h = *B.sph;
          HS_CALL( hs_sp_build(&B.sp, B.n, s->m, (long long) h.var.size(), h.var.data(), h.row.data(), h.col.data(), h.val.data()) );
          B.sp_dirty = false;
+         ++s->mg_host_builds;
       }
+   return HS_OK;
+}
+
+int hs_solver_sparse_block(hipsdp_solver* s, int block, const hs_sparse** sp)
+{
+   *sp = NULL;
+   if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || !s->blk[block].sparse )
+      return HS_ERR_ARG;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_sparse(s) );
+   HS_HIP( hipStreamSynchronize(s->stream) );
+   *sp = s->blk[block].sp;
    return HS_OK;
 }
 

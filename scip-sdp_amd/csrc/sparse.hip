@@ -26,36 +26,6 @@
 #include <vector>
 #include <numeric>
 
-struct hs_sparse
-{
-   int        n, m;
-   long long  nnz;
-   /* by variable: entries of variable v (1 .. m) are [voff[v - 1], voff[v]) */
-   int*       voff;
-   int*       vrow;
-   int*       vcol;
-   double*    vval;
-   /* by position: position k (a lower-triangular (row, col) that occurs) has the entries [poff[k], poff[k + 1]) */
-   long long  npos;
-   int*       poff;
-   int*       prow;
-   int*       pcol;
-   int*       pvar;        /* variable (1-based) of an entry */
-   double*    pval;
-   /* FULL symmetric entries by variable, row-major (the two-stage Schur assembly): entries of variable v are [foff[v - 1], foff[v]),
-    * entry e = (frow[e], fcol[e], fval[e]); the non-empty rows of variable v are the slots [soff[v - 1], soff[v]): slot s is row
-    * srow[s] with the entries [sent[s], sent[s + 1]); Tc: nslots x n doubles of workspace, Tc[s][c] = (A_v Zinv)[srow[s]][c] */
-   long long  nfull, nslots;
-   int*       foff;
-   int*       frow;
-   int*       fcol;
-   double*    fval;
-   int*       soff;
-   int*       srow;
-   int*       sent;
-   double*    Tc;
-};
-
 namespace {
 
 template<typename T> int sp_upload(T** d, const std::vector<T>& h)
@@ -81,6 +51,11 @@ void hs_sp_free(hs_sparse* sp)
 {
    if ( sp == NULL )
       return;
+   if ( sp->borrowed )
+   {
+      delete sp;                 /* the arrays are the workspace of a master block (sp_master.hip) */
+      return;
+   }
    hs_pool_free(sp->voff); hs_pool_free(sp->vrow); hs_pool_free(sp->vcol); hs_pool_free(sp->vval);
    hs_pool_free(sp->poff); hs_pool_free(sp->prow); hs_pool_free(sp->pcol); hs_pool_free(sp->pvar); hs_pool_free(sp->pval);
    hs_pool_free(sp->foff); hs_pool_free(sp->frow); hs_pool_free(sp->fcol); hs_pool_free(sp->fval);

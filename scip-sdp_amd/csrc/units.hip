@@ -1339,3 +1339,28 @@ extern "C" int hipsdp_tvec_unit(int device, int n, const double* d, const double
    HS_HIP( hipMemcpy(Z, hs_syevr_tvec_view(n, dws.p), (size_t) n * n * sizeof(double), hipMemcpyDeviceToHost) );
    return HIPSDP_OK;
 }
+
+/* the device structure of a block kept as nonzeros, copied to the host as it stands (tests/test_gpu_sparse_master.py compares the
+ * structure hipsdp_master_gather builds on the device with the one hs_sp_build makes from the node's triplets) */
+extern "C" int hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long long* counts, int* voff, int* vrow, int* vcol, double* vval,
+   int* poff, int* prow, int* pcol, int* pvar, double* pval, int* foff, int* frow, int* fcol, double* fval, int* soff, int* srow, int* sent)
+{
+   const hs_sparse* sp = NULL;
+   if ( solver == NULL || counts == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( hs_solver_sparse_block(solver, block, &sp) );
+   if ( sp == NULL )
+      return HIPSDP_ERR_ARG;
+   counts[0] = sp->n; counts[1] = sp->m; counts[2] = sp->nnz; counts[3] = sp->npos; counts[4] = sp->nfull; counts[5] = sp->nslots;
+   const size_t m1 = (size_t) sp->m + 1, nz = (size_t) sp->nnz, np = (size_t) sp->npos, nf = (size_t) sp->nfull, ns = (size_t) sp->nslots;
+   struct { void* dst; const void* src; size_t bytes; } cp[] = {
+      {voff, sp->voff, m1 * sizeof(int)}, {vrow, sp->vrow, nz * sizeof(int)}, {vcol, sp->vcol, nz * sizeof(int)}, {vval, sp->vval, nz * sizeof(double)},
+      {poff, sp->poff, (np + 1) * sizeof(int)}, {prow, sp->prow, np * sizeof(int)}, {pcol, sp->pcol, np * sizeof(int)},
+      {pvar, sp->pvar, nz * sizeof(int)}, {pval, sp->pval, nz * sizeof(double)},
+      {foff, sp->foff, m1 * sizeof(int)}, {frow, sp->frow, nf * sizeof(int)}, {fcol, sp->fcol, nf * sizeof(int)}, {fval, sp->fval, nf * sizeof(double)},
+      {soff, sp->soff, m1 * sizeof(int)}, {srow, sp->srow, ns * sizeof(int)}, {sent, sp->sent, (ns + 1) * sizeof(int)}};
+   for (auto& c : cp)
+      if ( c.dst != NULL && c.bytes > 0 )
+         HS_HIP( hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost) );
+   return HIPSDP_OK;
+}

@@ -627,7 +627,14 @@ static void cooFree(CooBuf* c)
 }
 
 /* fills the engine's compact blocks: non-constant part through the device-resident master copy (or directly when that does not
- * fit), then the constant matrix of the node and the identity of the penalty variable */
+ * fit), then the constant matrix of the node and the identity of the penalty variable.
+ *
+ * The master copy is a decision per block.  When it is (re)defined, a block whose engine block is kept as nonzeros at this node is
+ * declared as triplets (hipsdp_master_define2 with its number of nonzeros), every other one as a dense array.  At a node a triplet
+ * master block is gathered into whatever the engine block is; a dense master block whose engine block is kept as nonzeros at this
+ * node is loaded directly (that block only).  With the penalty formulation a block kept as nonzeros is loaded directly as well: the
+ * identity of the penalty variable is a variable matrix, which a gathered block does not take (the rare retry).  HIPSDP_NOCACHE=1
+ * defines the master copy anew at every node; blocks kept as nonzeros then take the direct load, which costs less than sorting. */
 static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, const int* sdpblocksizes, const int* sdpnblockvars,
    const int* sdpconstnblocknonz, int* const* sdpconstrow, int* const* sdpconstcol, SCIP_Real* const* sdpconstval, int sdpnnonz,
    int* const* sdpnblockvarnonz, int* const* sdpvar, int** const* sdprow, int** const* sdpcol, SCIP_Real** const* sdpval,
@@ -639,15 +646,12 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
    const SCIP_Bool usecache = (getenv("HIPSDP_NOCACHE") == NULL);
    CooBuf coo = {NULL, NULL, NULL, NULL};
    int* slots = NULL;
+   long long* masternnz = NULL;
    SCIP_RETCODE retcode = SCIP_OKAY;
    int b;
    int k;
    int t;
 
-   /* blocks the engine keeps as nonzeros are loaded directly (a few triplets per matrix: nothing a dense master copy would save) */
-   for (b = 0; b < nsdpblocks; ++b)
-      if ( s->blockmap[b] >= 0 && hipsdp_block_is_sparse(s->engine, s->blockmap[b]) )
-         usemaster = FALSE;
    tfp0 = clock();
    fp = sdpFingerprint(nvars, nsdpblocks, sdpblocksizes, sdpnblockvars, sdpnnonz, sdpnblockvarnonz, sdpvar, sdprow, sdpcol, sdpval);
    tfp1 = clock();
@@ -658,12 +662,29 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
    {
       int rc;
       s->mastervalid = FALSE;
-      rc = hipsdp_master_define(s->engine, nvars, nsdpblocks, sdpblocksizes, sdpnblockvars);
+      masternnz = (long long*) malloc((size_t) (nsdpblocks > 0 ? nsdpblocks : 1) * sizeof(long long));
+      if ( masternnz == NULL )
+         return SCIP_NOMEMORY;
+      for (b = 0; b < nsdpblocks; ++b)
+      {
+         masternnz[b] = -1;
+         if ( s->blockmap[b] >= 0 && hipsdp_block_is_sparse(s->engine, s->blockmap[b]) )
+         {
+            masternnz[b] = 0;
+            for (k = 0; k < sdpnblockvars[b]; ++k)
+               masternnz[b] += sdpnblockvarnonz[b][k];
+         }
+      }
+      rc = hipsdp_master_define2(s->engine, nvars, nsdpblocks, sdpblocksizes, sdpnblockvars, masternnz);
       /* slot = position of the variable in the block's list; the engine streams the caller's per-variable arrays through pinned
-       * staging chunks (no concatenated host copy: 1.25e8 triplets at n = 500, m = 1000) */
+       * staging chunks (no concatenated host copy: 1.25e8 triplets at n = 500, m = 1000), or collects them on the host for a block
+       * kept as triplets (not when the copy is not kept across nodes: that block is loaded directly below) */
       for (b = 0; b < nsdpblocks && rc == HIPSDP_OK; ++b)
-         rc = hipsdp_master_add_vars(s->engine, b, sdpnblockvars[b], sdpnblockvarnonz[b], (const int* const*) sdprow[b],
-            (const int* const*) sdpcol[b], (const double* const*) sdpval[b]);
+         if ( usecache || masternnz[b] < 0 )
+            rc = hipsdp_master_add_vars(s->engine, b, sdpnblockvars[b], sdpnblockvarnonz[b], (const int* const*) sdprow[b],
+               (const int* const*) sdpcol[b], (const double* const*) sdpval[b]);
+      free(masternnz);
+      masternnz = NULL;
       if ( rc == HIPSDP_ERR_NOMEM )
       {
          /* the master copy does not fit beside the engine's storage: drop it and load this node's blocks directly */
@@ -709,10 +730,15 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
       long long cnt = 0;
       long long pos = 0;
       int rc;
+      SCIP_Bool direct;
       const int eb = s->blockmap[b];
       if ( eb < 0 )
          continue;
-      if ( usemaster )
+      direct = ! usemaster;
+      if ( usemaster && hipsdp_block_is_sparse(s->engine, eb)
+         && (s->penalty || ! usecache || ! hipsdp_master_block_is_sparse(s->engine, b)) )
+         direct = TRUE;
+      if ( ! direct )
       {
          /* slot of every active variable in this block (-1: it does not appear) */
          for (k = 0; k < s->nactivevars; ++k)
@@ -747,7 +773,7 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
          retcode = SCIP_NOMEMORY;
          break;
       }
-      if ( ! usemaster )
+      if ( direct )
       {
          for (k = 0; k < sdpnblockvars[b]; ++k)
          {
@@ -802,6 +828,17 @@ static SCIP_RETCODE loadBlocks(SCIP_SDPISOLVER* s, int nvars, int nsdpblocks, co
    free(slots);
    return retcode;
 }
+
+#ifndef HIPSDP_WITH_SCIP
+/* hipsdp_master_gather_stats of the engine behind a solver (tests: which path loaded the blocks kept as nonzeros); 0 on success */
+int hipsdp_compat_gather_stats(SCIP_SDPISOLVER* s, long long* device_builds, long long* host_builds, long long* launches,
+   long long* readbacks)
+{
+   if ( s == NULL || s->engine == NULL )
+      return 1;
+   return hipsdp_master_gather_stats(s->engine, device_builds, host_builds, launches, readbacks) == HIPSDP_OK ? 0 : 1;
+}
+#endif
 
 /* pull y and the LP multipliers of the last engine solve to the host */
 static SCIP_RETCODE fetchVectors(SCIP_SDPISOLVER* s)
