@@ -271,6 +271,38 @@ HIPSDP_API int hipsdp_eigencuts_all(hipsdp_solver* solver, const double* y, doub
 /* process totals: calls, kernel launches those calls issued for batched blocks, device->host synchronisations they waited on */
 HIPSDP_API int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* Sparse eigenvector cuts of all blocks in one call: the separation mode `multiplesparsecuts` of cons_sdp.c (:1340-1607,
+ * addMultipleSparseCuts, after Algorithm 1 of Dey et al., "Cutting plane generation through sparse principal component analysis")
+ * in its default configuration (recomputesparseev, recomputeinitial and exacttrans FALSE).  Per block b with lmin[b] < -tol:
+ *     Z = Z_b(y), (lam, V) its decomposition, v0 = V[0], maxeig = lam[n - 1]
+ *     (x, theta) = TPower(maxeig I - Z, v0), scalar = maxeig - theta
+ *     while scalar < -feastol and ncuts < maxcuts:  cut (scalar, x);  Z -= scalar x x^T;  maxeig -= scalar;  TPower again from v0
+ * TPower (the truncated power method, cons_sdp.c:1140-1234) keeps the sizes[b] entries of largest absolute value of every iterate -
+ * of two equal absolute values the one with the smaller index - and stops when its Rayleigh quotient grew by <= convtol.
+ * The cut of slot (b, c), laid out as in hipsdp_eigencuts_all: sum_i coefs[i] y_i >= lhs with coefs[i] = x^T A_i x, lhs = x^T A_0 x,
+ * violated at y by -eigvals; row c of the block's vectors is x, dense, with exact zeros outside its support of sizes[b] entries.
+ * Slots c >= ncuts[b] are not written.  iters[b]: TPower iterations of the block, summed; flags[b] bit 0: a TPower run stopped at
+ * maxit (its iterate was used as it stood), bit 1: a truncated iterate had norm 0 (the block's loop ended there).  lmin, vecs,
+ * iters and flags may be NULL.
+ * ncuts[b] = 0: lmin[b] >= -tol, or sizes[b] > n_b (as :1403-1407), or maxcuts == 0 (a pure feasibility check; then eigvals, coefs
+ * and lhs may be NULL).  ncuts[b] = -1: the block is NOT served - more than 128 rows, or a solver with a communicator or with
+ * sharded matrices; nothing else is written for it and hipsdp_eigencuts separates it.  The call still serves the other blocks.
+ * Whatever the number of blocks, cuts and iterations: one upload of y and sizes, 4 to 6 launches (Z_b(y), at most three for the
+ * decompositions, TPower, coefficients; 3 to 5 with maxcuts == 0) and one read-back (csrc/sparsecuts.hip).  Same input, same bits,
+ * whatever other blocks the solver has.  Two host threads may call it at the same time on different solvers. */
+#define HIPSDP_SPARSECUTS_MAXIT 10000
+typedef struct hipsdp_sparsecut_opts {
+   double tol;      /* a block takes part when lambda_min(Z_b(y)) < -tol            (cons_sdp.c:1690) */
+   double feastol;  /* cuts are produced while the sparse eigenvalue is < -feastol   (SCIPisFeasNegative, :1450/:1458) */
+   double convtol;  /* TPower stops when its Rayleigh quotient grew by <= convtol; <= 0: 1e-6 (:1441) */
+   int    maxcuts;  /* per block, >= 0 (maxnsparsecuts; the output arrays are sized by it) */
+   int    maxit;    /* cap on the iterations of ONE TPower run; <= 0: HIPSDP_SPARSECUTS_MAXIT */
+} hipsdp_sparsecut_opts;
+HIPSDP_API int hipsdp_sparsecuts_all(hipsdp_solver* solver, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
+/* process totals: calls, kernel launches those calls issued, device->host synchronisations they waited on */
+HIPSDP_API int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves
  * them alone with the single-rank kernels and rank 0's outcome (status, iterate, preoptimal iterate) is broadcast once per solve. */

@@ -120,6 +120,13 @@ HIPSDP_API int  hipsdp_gram_key_match_unit(int m_a, int nblk_a, const int* n_a, 
  * ns[j] <= 128 rows; lam: ns[j] eigenvalues each (ascending), V: ns[j] x ns[j] each (row k = k-th eigenvector) - for every matrix
  * the bits of hipsdp_syev_small; *launches: kernel launches issued (at most 3, whatever count is) */
 HIPSDP_API int  hipsdp_syev_many_unit(int device, int count, const int* ns, const double* A, double* lam, double* V, int* launches);
+/* k_sc_tpower (csrc/sparsecuts.hip) alone on `count` host matrices, one behind the other in Z: matrix j has ns[j] <= 128 rows, the
+ * start vector v0 (ns[j] values each, one behind the other), the largest eigenvalue maxeig[j] and the target sparsity sizes[j].
+ * Every matrix takes part (opts->tol is not used: there is no decomposition to take lmin from); feastol, convtol, maxcuts >= 1 and
+ * maxit as in hipsdp_sparsecuts_all.  ncuts[count], eigvals[count * maxcuts], vecs (maxcuts x ns[j] each, one behind the other),
+ * iters[count], flags[count] as that call returns them; slots c >= ncuts[j] are not written. */
+HIPSDP_API int  hipsdp_sparsecuts_unit(int device, int count, const int* ns, const double* Z, const double* v0, const double* maxeig,
+   const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags);
 /* the first stage of hipsdp_syevx alone, 2 <= n <= 512: the tridiagonal matrix Q^T A Q (d[n], e[n - 1] in e[0 .. n - 2], e[n - 1] = 0)
  * and Q = H_0 H_1 ... H_{n-2}, H_j = I - tau[j] v_j v_j^T, row j of Vrefl (n x n) = v_j (zeros up to entry j, entry j + 1 one) */
 HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau);

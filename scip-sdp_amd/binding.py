@@ -390,6 +390,78 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's eigencuts_all_stats()"""
         return eigencuts_all_stats()
 
+    def sparsecuts_all(self, y, sizes, tol, feastol, maxcuts, convtol=0, maxit=0):
+        """sparse eigenvector cuts of all blocks in one call (hipsdp_sparsecuts_all; sizes[b]: target sparsity of block b): per block
+        a tuple (ncuts, lmin, eigvals[k], coefs[k, m], lhs[k], vecs[k, n], iters, flags); ncuts = -1: the block is not served (then
+        lmin is nan and the rest empty / 0); cut c of a block: coefs[c] @ y >= lhs[c], violated at y by -eigvals[c]"""
+        y = _f64(y)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        m, nb, mc = len(y), len(self.ns), max(1, maxcuts)
+        assert len(sizes) == nb
+        opts = SparsecutOpts(tol, feastol, convtol, maxcuts, maxit)
+        k = np.zeros(max(1, nb), dtype=np.int32)
+        it = np.zeros(max(1, nb), dtype=np.int32)
+        fl = np.zeros(max(1, nb), dtype=np.int32)
+        lmin = np.full(max(1, nb), np.nan)
+        ev = np.zeros(max(1, nb) * mc)
+        co = np.zeros(max(1, nb) * mc * max(1, m))
+        lh = np.zeros(max(1, nb) * mc)
+        ve = np.zeros(max(1, maxcuts * sum(self.ns)))
+        _chk(self._l().hipsdp_sparsecuts_all(self.h, _dp(y), _ip(sizes), C.byref(opts), _ip(k), _dp(lmin), _dp(ev), _dp(co), _dp(lh),
+                                             _dp(ve), _ip(it), _ip(fl)), "hipsdp_sparsecuts_all")
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            kb = max(0, int(k[b]))
+            s0 = b * maxcuts
+            out.append((int(k[b]), float(lmin[b]), ev[s0:s0 + kb].copy(), co[s0 * m:(s0 + kb) * m].reshape(kb, m).copy(),
+                        lh[s0:s0 + kb].copy(), ve[off:off + kb * n].reshape(kb, n).copy(), int(it[b]), int(fl[b])))
+            off += maxcuts * n
+        return out
+
+    @staticmethod
+    def sparsecuts_all_stats():
+        """process totals (calls, launches, read-backs): the module's sparsecuts_all_stats()"""
+        return sparsecuts_all_stats()
+
+
+class SparsecutOpts(C.Structure):
+    """hipsdp_sparsecut_opts"""
+    _fields_ = [("tol", C.c_double), ("feastol", C.c_double), ("convtol", C.c_double), ("maxcuts", C.c_int), ("maxit", C.c_int)]
+
+
+def sparsecuts_all_stats():
+    """process totals of hipsdp_sparsecuts_all: (calls, kernel launches issued, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_sparsecuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_all_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def sparsecuts_unit(ns, Zs, v0s, maxeig, sizes, feastol, maxcuts, convtol=0, maxit=0, device=0):
+    """k_sc_tpower alone on host matrices (hipsdp_sparsecuts_unit of the units library): per matrix (ncuts, eigvals[k], vecs[k, n],
+    iters, flags)"""
+    ns = [int(n) for n in ns]
+    cnt = len(ns)
+    cns = np.asarray(ns, dtype=np.int32)
+    Z = _f64(np.concatenate([np.asarray(z, dtype=np.float64).reshape(-1) for z in Zs]))
+    v0 = _f64(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in v0s]))
+    me = _f64(maxeig)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    opts = SparsecutOpts(0.0, feastol, convtol, maxcuts, maxit)
+    k, it, fl = (np.zeros(cnt, dtype=np.int32) for _ in range(3))
+    ev = np.zeros(cnt * maxcuts)
+    ve = np.zeros(maxcuts * sum(ns))
+    rc = ulib().hipsdp_sparsecuts_unit(device, cnt, _ip(cns), _dp(Z), _dp(v0), _dp(me), _ip(sizes), C.byref(opts), _ip(k), _dp(ev), _dp(ve),
+                                       _ip(it), _ip(fl))
+    if rc != 0:
+        raise RuntimeError("hipsdp_sparsecuts_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    out, off = [], 0
+    for j, n in enumerate(ns):
+        kj = int(k[j])
+        out.append((kj, ev[j * maxcuts:j * maxcuts + kj].copy(), ve[off:off + kj * n].reshape(kj, n).copy(), int(it[j]), int(fl[j])))
+        off += maxcuts * n
+    return out
+
+
 def eigencuts_all_stats():
     """process totals of hipsdp_eigencuts_all: (calls, kernel launches issued for batched blocks, device->host synchronisations)"""
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)

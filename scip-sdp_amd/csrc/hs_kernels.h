@@ -356,6 +356,17 @@ struct hs_ec_job
 int hs_ec_form_z(hipStream_t st, int count, int nmax, int m, const hs_ec_job* jobs, const double* y);
 int hs_ec_cuts(hipStream_t st, int count, int nmax, int m, int nb, int maxcuts, double tol, const hs_ec_job* jobs, double* res);
 
+/* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
+#define HS_SC_MAXN 128
+struct hs_sc_par { double tol, feastol, convtol; int maxcuts, maxit; };      /* convtol > 0, maxit >= 1: the defaults are the caller's */
+/* where the kernels put their results, all indexed by the block's index (hs_ec_job.blk) or its slots blk * maxcuts + c; sup: smax
+ * ints per slot, the ascending support of the cut (k_sc_tpower writes it, k_sc_coefs reads it) */
+struct hs_sc_out { int *ncuts, *iters, *flags; double *lmin, *eig, *lhs, *coef, *vec; int* sup; int smax, pad; };
+/* one workgroup per job: Z from job.Z, eigenvalues ascending at job.ws (lmin first, maxeig last), v0 at job.ws + job.vpos;
+ * sizes[job.blk]: the target sparsity */
+int hs_sc_tpower(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const int* sizes, const hs_sc_par* par, const hs_sc_out* out);
+int hs_sc_coefs(hipStream_t st, int count, int m, int maxcuts, const hs_ec_job* jobs, const int* sizes, const hs_sc_out* out);
+
 /* Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix A (destroyed): eigenvalues ascending in lam[n],
  * eigenvectors as rows of V (row k = k-th eigenvector).  info (device int) = sweeps used or -1. */
 int hs_syev_jacobi(hipStream_t s, int n, double* A, double* lam, double* V, int* info, double* ws);

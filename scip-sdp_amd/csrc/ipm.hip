@@ -203,9 +203,10 @@ struct hipsdp_solver
    int s1_last;            /* 1: the last solve ran in the single launch */
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
-   /* hipsdp_eigencuts_all (csrc/eigcuts.hip), all grow-only and kept until hipsdp_free: device workspace (y, result block, Z and
-    * decomposition slab per batched block), its pinned host mirror (y, result block), the job tables on the device and the host
-    * copies they were uploaded from (a call uploads them again only when they differ) */
+   /* hipsdp_eigencuts_all (csrc/eigcuts.hip) and hipsdp_sparsecuts_all (csrc/sparsecuts.hip), all grow-only and kept until
+    * hipsdp_free: device workspace (y, result block, Z and decomposition slab per batched block), its pinned host mirror (y, result
+    * block), the job tables on the device and the host copies they were uploaded from (a call uploads them again only when they
+    * differ) */
    double* ec_dev; long long ec_dev_len;
    double* ec_pin; long long ec_pin_len;
    char* ec_tab; long long ec_tab_len;
@@ -5191,6 +5192,86 @@ static bool ec_batched(const hipsdp_solver* s, const Block& B)
    return s->comm == NULL && !s->shardA && B.n <= 128 && (B.sparse ? (B.sp != NULL && B.A0 != NULL) : B.A != NULL);
 }
 
+/* The workspace and the job tables of a round over the batched blocks `ids` (ordered by decomposition class): ec_dev holds `front`
+ * doubles for the caller (y, its result block) and behind them Z and the decomposition slab of every block, ec_pin `pin` doubles,
+ * ec_tab the hs_ec_job of the blocks and behind them their hs_eig_job.  All three only grow; the tables are uploaded when they differ
+ * from what the device holds (first use, a new shape, another storage form, a workspace laid out differently). */
+static int ec_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long front, long long pin,
+   int* nmax_out)
+{
+   const int nj = (int) ids.size();
+   long long need = front;
+   int nmax = 0;
+   for (int b : ids)
+   {
+      const int n = s->blk[b].n;
+      need += (((long long) n * n + 1) & ~1LL) + hs_syev_small_scratch(n);
+      nmax = n > nmax ? n : nmax;
+   }
+   if ( need > s->ec_dev_len )
+   {
+      if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
+      s->ec_dev = NULL; s->ec_dev_len = 0;
+      HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
+      s->ec_dev_len = need;
+   }
+   if ( pin > s->ec_pin_len )
+   {
+      if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
+      s->ec_pin = NULL; s->ec_pin_len = 0;
+      HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) pin * sizeof(double), hipHostMallocDefault) );
+      s->ec_pin_len = pin;
+   }
+   const size_t tabbytes = (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job));
+   if ( (long long) tabbytes > s->ec_tab_len )
+   {
+      if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
+      s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
+      HS_HIP( hipMalloc((void**) &s->ec_tab, tabbytes) );
+      s->ec_tab_len = (long long) tabbytes;
+   }
+   double* cur = s->ec_dev + front;
+   std::vector<hs_ec_job> jobs((size_t) nj);
+   std::vector<hs_eig_job> ejobs((size_t) nj);
+   for (int j = 0; j < nj; ++j)
+   {
+      const Block& B = s->blk[ids[j]];
+      hs_ec_job& J = jobs[j];
+      memset(&J, 0, sizeof(J));
+      memset(&ejobs[j], 0, sizeof(hs_eig_job));
+      J.n = B.n; J.blk = ids[j];
+      J.ld = (long long) B.n * B.n;
+      if ( B.sparse )
+      {
+         J.form = HS_EC_SPARSE; J.A = B.A0;
+         hs_sp_get_view(B.sp, &J.sp);
+      }
+      else if ( B.Apk != NULL && B.apk_valid )
+      {
+         J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
+      }
+      else
+      {
+         J.form = HS_EC_DENSE; J.A = B.A;
+      }
+      J.Z = cur; cur += ((long long) B.n * B.n + 1) & ~1LL;
+      J.ws = cur; cur += hs_syev_small_scratch(B.n);
+      J.vpos = hs_syev_many_vecpos(B.n);
+      J.vecoff = vecoff[ids[j]];
+      ejobs[j].n = B.n; ejobs[j].in = J.Z; ejobs[j].ws = J.ws;
+   }
+   hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
+   hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
+   if ( s->ec_jobs.size() != jobs.size() || memcmp(s->ec_jobs.data(), jobs.data(), jobs.size() * sizeof(hs_ec_job)) != 0 )
+   {
+      HS_HIP( hipMemcpy(djobs, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+      HS_HIP( hipMemcpy(dejobs, ejobs.data(), ejobs.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
+      s->ec_jobs = jobs; s->ec_ejobs = ejobs;
+   }
+   *nmax_out = nmax;
+   return HS_OK;
+}
+
 extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
    double* coefs, double* lhs, double* vecs)
 {
@@ -5219,78 +5300,12 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
    {
       const long long ylen = (m + 2) & ~1LL;
       const long long reslen = 2LL * nb + 2LL * nb * maxcuts + (long long) nb * maxcuts * m + vecoff[nb];
-      long long need = ylen + reslen;
       int nmax = 0;
-      for (int b : ids)
-      {
-         const int n = s->blk[b].n;
-         need += (((long long) n * n + 1) & ~1LL) + hs_syev_small_scratch(n);
-         nmax = n > nmax ? n : nmax;
-      }
-      if ( need > s->ec_dev_len )
-      {
-         if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
-         s->ec_dev = NULL; s->ec_dev_len = 0;
-         HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
-         s->ec_dev_len = need;
-      }
-      if ( ylen + reslen > s->ec_pin_len )
-      {
-         if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
-         s->ec_pin = NULL; s->ec_pin_len = 0;
-         HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) (ylen + reslen) * sizeof(double), hipHostMallocDefault) );
-         s->ec_pin_len = ylen + reslen;
-      }
-      const size_t tabbytes = (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job));
-      if ( (long long) tabbytes > s->ec_tab_len )
-      {
-         if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
-         s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
-         HS_HIP( hipMalloc((void**) &s->ec_tab, tabbytes) );
-         s->ec_tab_len = (long long) tabbytes;
-      }
-      /* the job tables: what the shape, the storage forms and the workspace make of them; uploaded when that differs from what the
-       * device holds (first use, a new shape, a grown workspace) */
+      HS_CALL( ec_prepare(s, ids, vecoff, ylen + reslen, ylen + reslen, &nmax) );
       double* dy = s->ec_dev;
       double* dres = dy + ylen;
-      double* cur = dres + reslen;
-      std::vector<hs_ec_job> jobs((size_t) nj);
-      std::vector<hs_eig_job> ejobs((size_t) nj);
-      for (int j = 0; j < nj; ++j)
-      {
-         const Block& B = s->blk[ids[j]];
-         hs_ec_job& J = jobs[j];
-         memset(&J, 0, sizeof(J));
-         memset(&ejobs[j], 0, sizeof(hs_eig_job));
-         J.n = B.n; J.blk = ids[j];
-         J.ld = (long long) B.n * B.n;
-         if ( B.sparse )
-         {
-            J.form = HS_EC_SPARSE; J.A = B.A0;
-            hs_sp_get_view(B.sp, &J.sp);
-         }
-         else if ( B.Apk != NULL && B.apk_valid )
-         {
-            J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
-         }
-         else
-         {
-            J.form = HS_EC_DENSE; J.A = B.A;
-         }
-         J.Z = cur; cur += ((long long) B.n * B.n + 1) & ~1LL;
-         J.ws = cur; cur += hs_syev_small_scratch(B.n);
-         J.vpos = hs_syev_many_vecpos(B.n);
-         J.vecoff = vecoff[ids[j]];
-         ejobs[j].n = B.n; ejobs[j].in = J.Z; ejobs[j].ws = J.ws;
-      }
       hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
       hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
-      if ( s->ec_jobs.size() != jobs.size() || memcmp(s->ec_jobs.data(), jobs.data(), jobs.size() * sizeof(hs_ec_job)) != 0 )
-      {
-         HS_HIP( hipMemcpy(djobs, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
-         HS_HIP( hipMemcpy(dejobs, ejobs.data(), ejobs.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
-         s->ec_jobs = jobs; s->ec_ejobs = ejobs;
-      }
       int launches = 0;
       if ( m > 0 )
       {
@@ -5344,6 +5359,134 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
          lmin[b] = l0;
    }
    ++g_ec_calls;
+   return HIPSDP_OK;
+}
+
+/* ---- sparse eigenvector cuts of all blocks in one call (kernels: csrc/sparsecuts.hip) ------------------------------------------- */
+static std::atomic<long long> g_sc_calls(0), g_sc_launches(0), g_sc_readbacks(0);
+
+extern "C" int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   if ( calls != NULL ) *calls = g_sc_calls.load();
+   if ( launches != NULL ) *launches = g_sc_launches.load();
+   if ( readbacks != NULL ) *readbacks = g_sc_readbacks.load();
+   return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( s == NULL || !s->shaped || y == NULL || sizes == NULL || opts == NULL || ncuts == NULL || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   const int maxcuts = opts->maxcuts;
+   if ( maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   const int nb = (int) s->blk.size(), m = s->m;
+   for (int b = 0; b < nb; ++b)
+      if ( sizes[b] < 1 )
+         return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      ncuts[b] = -1;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
+   hipStream_t st = s->stream;
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+      vecoff[b + 1] = vecoff[b] + (long long) maxcuts * s->blk[b].n;
+   /* the served blocks, in the order of the decomposition's classes */
+   std::vector<int> ids;
+   for (int cls = 0; cls < 3; ++cls)
+      for (int b = 0; b < nb; ++b)
+         if ( ec_batched(s, s->blk[b]) && hs_syev_many_class(s->blk[b].n) == cls )
+            ids.push_back(b);
+   const int nj = (int) ids.size();
+   if ( nj > 0 )
+   {
+      /* the largest support a served block can have: the pitch of the support lists */
+      int smax = 1;
+      for (int b : ids)
+         if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
+            smax = sizes[b];
+      /* uploaded: y | sizes (int);  read back: lmin | eigvals | lhs | coefs | vecs | ncuts, iters, flags (int);  device only: supports (int) */
+      const long long ylen = (m + 2) & ~1LL, szlen = ((long long) nb + 1) / 2;
+      const long long slots = (long long) nb * maxcuts;
+      const long long reslen = nb + 2 * slots + slots * m + vecoff[nb] + (3LL * nb + 1) / 2;
+      const long long suplen = (slots * smax + 1) / 2;
+      int nmax = 0;
+      HS_CALL( ec_prepare(s, ids, vecoff, ylen + szlen + reslen + suplen, ylen + szlen + reslen, &nmax) );
+      double* dy = s->ec_dev;
+      int* dsizes = reinterpret_cast<int*>(dy + ylen);
+      double* dres = dy + ylen + szlen;
+      hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
+      hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
+      hs_sc_out out;
+      memset(&out, 0, sizeof(out));
+      out.lmin = dres;
+      out.eig = out.lmin + nb;
+      out.lhs = out.eig + slots;
+      out.coef = out.lhs + slots;
+      out.vec = out.coef + slots * m;
+      out.ncuts = reinterpret_cast<int*>(out.vec + vecoff[nb]);
+      out.iters = out.ncuts + nb;
+      out.flags = out.iters + nb;
+      out.sup = reinterpret_cast<int*>(dres + reslen);
+      out.smax = smax;
+      hs_sc_par par;
+      par.tol = opts->tol; par.feastol = opts->feastol;
+      par.convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+      par.maxcuts = maxcuts;
+      par.maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+      int launches = 0;
+      if ( m > 0 )
+         memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
+      memcpy(s->ec_pin + ylen, sizes, (size_t) nb * sizeof(int));
+      HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) (ylen + szlen) * sizeof(double), hipMemcpyHostToDevice, st) );
+      HS_CALL( hs_ec_form_z(st, nj, nmax, m, djobs, dy) );
+      ++launches;
+      HS_CALL( hs_syev_small_many(st, nj, s->ec_ejobs.data(), dejobs, &launches) );
+      HS_CALL( hs_sc_tpower(st, nj, nmax, djobs, dsizes, &par, &out) );
+      ++launches;
+      if ( maxcuts > 0 )
+      {
+         HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, djobs, dsizes, &out) );
+         ++launches;
+      }
+      double* hres = s->ec_pin + ylen + szlen;
+      HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      g_sc_launches += launches;
+      g_sc_readbacks += 1;
+      const double* h_eig = hres + nb;
+      const double* h_lhs = h_eig + slots;
+      const double* h_coef = h_lhs + slots;
+      const double* h_vec = h_coef + slots * m;
+      const int* h_ncuts = reinterpret_cast<const int*>(h_vec + vecoff[nb]);
+      for (int b : ids)
+      {
+         const int k = h_ncuts[b];
+         if ( k < 0 || k > maxcuts )
+            return HIPSDP_ERR_NUMERIC;
+         ncuts[b] = k;
+         if ( lmin != NULL )
+            lmin[b] = hres[b];
+         if ( iters != NULL )
+            iters[b] = h_ncuts[nb + b];
+         if ( flags != NULL )
+            flags[b] = h_ncuts[2 * nb + b];
+         const size_t slot = (size_t) b * maxcuts;
+         if ( k > 0 )
+         {
+            memcpy(eigvals + slot, h_eig + slot, (size_t) k * sizeof(double));
+            memcpy(lhs + slot, h_lhs + slot, (size_t) k * sizeof(double));
+            if ( m > 0 )
+               memcpy(coefs + slot * m, h_coef + slot * m, (size_t) k * m * sizeof(double));
+            if ( vecs != NULL )
+               memcpy(vecs + vecoff[b], h_vec + vecoff[b], (size_t) k * s->blk[b].n * sizeof(double));
+         }
+      }
+   }
+   ++g_sc_calls;
    return HIPSDP_OK;
 }
 

@@ -1301,6 +1301,81 @@ extern "C" int hipsdp_syev_many_unit(int device, int count, const int* ns, const
    return HIPSDP_OK;
 }
 
+/* k_sc_tpower alone (csrc/sparsecuts.hip) on `count` host matrices with given start vectors and largest eigenvalues: the slab of a
+ * job holds maxeig in all ns[j] eigenvalue slots and v0 behind them, and the launch gets tol = -infinity, so every matrix takes part */
+extern "C" int hipsdp_sparsecuts_unit(int device, int count, const int* ns, const double* Z, const double* v0, const double* maxeig,
+   const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags)
+{
+   HS_CALL( pick_device(device) );
+   if ( count < 1 || ns == NULL || Z == NULL || v0 == NULL || maxeig == NULL || sizes == NULL || opts == NULL || opts->maxcuts < 1
+      || ncuts == NULL || eigvals == NULL || vecs == NULL || iters == NULL || flags == NULL )
+      return HIPSDP_ERR_ARG;
+   const int maxcuts = opts->maxcuts;
+   std::vector<long long> zoff((size_t) count + 1, 0), woff((size_t) count + 1, 0), vecoff((size_t) count + 1, 0);
+   int nmax = 0, smax = 1;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( ns[j] < 1 || ns[j] > HS_SC_MAXN || sizes[j] < 1 )
+         return HIPSDP_ERR_ARG;
+      zoff[j + 1] = zoff[j] + (long long) ns[j] * ns[j];
+      woff[j + 1] = woff[j] + 2LL * ns[j];
+      vecoff[j + 1] = vecoff[j] + (long long) maxcuts * ns[j];
+      nmax = ns[j] > nmax ? ns[j] : nmax;
+      if ( sizes[j] <= ns[j] && sizes[j] > smax )
+         smax = sizes[j];
+   }
+   std::vector<double> slab((size_t) woff[count]);
+   for (int j = 0; j < count; ++j)
+      for (int i = 0; i < ns[j]; ++i)
+      {
+         slab[(size_t) woff[j] + i] = maxeig[j];
+         slab[(size_t) woff[j] + ns[j] + i] = v0[woff[j] / 2 + i];
+      }
+   /* results: lmin | eigvals | vecs | ncuts, iters, flags (int) | supports (int) | sizes (int) */
+   const long long slots = (long long) count * maxcuts;
+   const long long ipos = count + slots + vecoff[count], spos = ipos + (3LL * count + 1) / 2, zpos = spos + (slots * smax + 1) / 2;
+   const long long reslen = zpos + ((long long) count + 1) / 2;
+   DevBuf dz, dws, dres, dtab;
+   HS_CALL( dz.alloc(zoff[count]) ); HS_CALL( dws.alloc(woff[count]) ); HS_CALL( dres.alloc(reslen) );
+   HS_CALL( dz.up(Z, zoff[count]) ); HS_CALL( dws.up(slab.data(), woff[count]) );
+   HS_HIP( hipMemcpy(dres.p + zpos, sizes, (size_t) count * sizeof(int), hipMemcpyHostToDevice) );
+   std::vector<hs_ec_job> jobs((size_t) count);
+   for (int j = 0; j < count; ++j)
+   {
+      hs_ec_job& J = jobs[j];
+      memset(&J, 0, sizeof(J));
+      J.n = ns[j]; J.blk = j; J.form = HS_EC_DENSE; J.ld = (long long) ns[j] * ns[j];
+      J.Z = dz.p + zoff[j]; J.ws = dws.p + woff[j]; J.vpos = ns[j]; J.vecoff = vecoff[j];
+   }
+   HS_CALL( dtab.alloc((long long) ((jobs.size() * sizeof(hs_ec_job) + 7) / 8)) );
+   HS_HIP( hipMemcpy(dtab.p, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+   hs_sc_out out;
+   memset(&out, 0, sizeof(out));
+   out.lmin = dres.p; out.eig = dres.p + count; out.vec = out.eig + slots;
+   out.ncuts = reinterpret_cast<int*>(dres.p + ipos); out.iters = out.ncuts + count; out.flags = out.iters + count;
+   out.sup = reinterpret_cast<int*>(dres.p + spos); out.smax = smax;
+   hs_sc_par par;
+   par.tol = -HUGE_VAL; par.feastol = opts->feastol;
+   par.convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+   par.maxcuts = maxcuts;
+   par.maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+   HS_CALL( hs_sc_tpower(0, count, nmax, reinterpret_cast<const hs_ec_job*>(dtab.p), reinterpret_cast<const int*>(dres.p + zpos), &par, &out) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> h((size_t) spos);
+   HS_CALL( dres.down(h.data(), spos) );
+   const int* hi = reinterpret_cast<const int*>(h.data() + ipos);
+   for (int j = 0; j < count; ++j)
+   {
+      const int k = hi[j];
+      if ( k < 0 || k > maxcuts )
+         return HIPSDP_ERR_NUMERIC;
+      ncuts[j] = k; iters[j] = hi[count + j]; flags[j] = hi[2 * count + j];
+      memcpy(eigvals + (size_t) j * maxcuts, h.data() + count + (size_t) j * maxcuts, (size_t) k * sizeof(double));
+      memcpy(vecs + vecoff[j], h.data() + count + slots + vecoff[j], (size_t) k * ns[j] * sizeof(double));
+   }
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau)
 {
    HS_CALL( pick_device(device) );
