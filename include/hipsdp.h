@@ -286,7 +286,8 @@ HIPSDP_API int hipsdp_eigencuts_all_stats(long long* calls, long long* launches,
  * iters and flags may be NULL.
  * ncuts[b] = 0: lmin[b] >= -tol, or sizes[b] > n_b (as :1403-1407), or maxcuts == 0 (a pure feasibility check; then eigvals, coefs
  * and lhs may be NULL).  ncuts[b] = -1: the block is NOT served - more than 128 rows, or a solver with a communicator or with
- * sharded matrices; nothing else is written for it and hipsdp_eigencuts separates it.  The call still serves the other blocks.
+ * sharded matrices; nothing else is written for it.  hipsdp_sparsecuts (below) gives the sparse cuts of such a block of up to 512
+ * rows, hipsdp_eigencuts dense eigenvector cuts of any block.  The call still serves the other blocks.
  * Whatever the number of blocks, cuts and iterations: one upload of y and sizes, 4 to 6 launches (Z_b(y), at most three for the
  * decompositions, TPower, coefficients; 3 to 5 with maxcuts == 0) and one read-back (csrc/sparsecuts.hip).  Same input, same bits,
  * whatever other blocks the solver has.  Two host threads may call it at the same time on different solvers. */
@@ -302,6 +303,28 @@ HIPSDP_API int hipsdp_sparsecuts_all(hipsdp_solver* solver, const double* y, con
    int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
 /* process totals: calls, kernel launches those calls issued, device->host synchronisations they waited on */
 HIPSDP_API int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks);
+
+/* The same for ONE block of up to HIPSDP_SPARSECUTS_MAXN rows: the per-block partner of hipsdp_sparsecuts_all, as hipsdp_eigencuts is
+ * of hipsdp_eigencuts_all.  Algorithm, options, tie rule, flags and the meaning of every output are those of hipsdp_sparsecuts_all
+ * restricted to block `block` with target sparsity `size`: eigvals[maxcuts], lhs[maxcuts], coefs[maxcuts x m], vecs[maxcuts x n]
+ * (dense rows, exact zeros off the support), *ncuts, *lmin, *iters, *flags; slots c >= *ncuts are not written; lmin, vecs, iters and
+ * flags may be NULL, with maxcuts == 0 also eigvals, coefs and lhs.
+ * A block of at most 128 rows runs through the launches of hipsdp_sparsecuts_all with that block as the only job and returns the
+ * bits that call returns for it.  A block of 129 .. 512 rows (csrc/sparsecuts_large.hip): Z(y) in one launch, ONE
+ * tridiagonalisation (n launches), from it (lmin, v0) in three launches and maxeig in one, the whole TPower loop in one launch of a
+ * single workgroup, the coefficients in one - n + 7 launches, one upload of y, one read-back and one synchronisation whatever the
+ * number of cuts and iterations; with maxcuts == 0 only lmin is computed: n + 2 launches.  lmin and maxeig have the accuracy of
+ * hipsdp_syevx.  Same input, same bits.
+ * *ncuts = -1 with HIPSDP_OK and nothing else written: a block of more than 512 rows, or a solver with a communicator or with
+ * sharded matrices.  HIPSDP_ERR_ARG, nothing launched: solver NULL or without a shape, block out of range, y, opts or ncuts NULL,
+ * size < 1, maxcuts < 0, maxcuts > 0 with eigvals, coefs or lhs NULL.  Two host threads may call it at the same time on different
+ * solvers. */
+#define HIPSDP_SPARSECUTS_MAXN 512      /* = the largest matrix of hipsdp_syevx */
+HIPSDP_API int hipsdp_sparsecuts(hipsdp_solver* solver, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
+/* process totals of hipsdp_sparsecuts alone: calls that served their block, kernel launches they issued, device->host
+ * synchronisations they waited on (the totals of hipsdp_sparsecuts_all_stats do not move) */
+HIPSDP_API int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks);
 
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves

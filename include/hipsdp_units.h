@@ -127,6 +127,11 @@ HIPSDP_API int  hipsdp_syev_many_unit(int device, int count, const int* ns, cons
  * iters[count], flags[count] as that call returns them; slots c >= ncuts[j] are not written. */
 HIPSDP_API int  hipsdp_sparsecuts_unit(int device, int count, const int* ns, const double* Z, const double* v0, const double* maxeig,
    const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags);
+/* k_sc_tpower_large (csrc/sparsecuts_large.hip) alone on ONE host matrix Z of 129 <= n <= 512 rows with the start vector v0[n], the
+ * largest eigenvalue maxeig and the target sparsity size >= 1; opts as above (tol is not used, maxcuts >= 1).  *ncuts, eigvals[maxcuts],
+ * vecs[maxcuts x n], *iters, *flags as hipsdp_sparsecuts returns them; slots c >= *ncuts are not written. */
+HIPSDP_API int  hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, const double* v0, double maxeig, int size,
+   const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags);
 /* the first stage of hipsdp_syevx alone, 2 <= n <= 512: the tridiagonal matrix Q^T A Q (d[n], e[n - 1] in e[0 .. n - 2], e[n - 1] = 0)
  * and Q = H_0 H_1 ... H_{n-2}, H_j = I - tau[j] v_j v_j^T, row j of Vrefl (n x n) = v_j (zeros up to entry j, entry j + 1 one) */
 HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau);

@@ -423,6 +423,29 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's sparsecuts_all_stats()"""
         return sparsecuts_all_stats()
 
+    def sparsecuts(self, block, y, size, tol, feastol, maxcuts, convtol=0.0, maxit=0):
+        """sparse eigenvector cuts of ONE block of up to 512 rows (hipsdp_sparsecuts; size: its target sparsity): the tuple one block
+        of sparsecuts_all has, (ncuts, lmin, eigvals[k], coefs[k, m], lhs[k], vecs[k, n], iters, flags); ncuts = -1: the block is
+        not served (more than 512 rows, a communicator or sharded matrices; then lmin is nan and the rest empty / 0)"""
+        y = _f64(y)
+        m, n, mc = len(y), self.ns[block], max(1, maxcuts)
+        opts = SparsecutOpts(tol, feastol, convtol, maxcuts, maxit)
+        k, it, fl = C.c_int(0), C.c_int(0), C.c_int(0)
+        lmin = C.c_double(np.nan)
+        ev, lh = np.zeros(mc), np.zeros(mc)
+        co = np.zeros(mc * max(1, m))
+        ve = np.zeros(mc * n)
+        _chk(self._l().hipsdp_sparsecuts(self.h, int(block), _dp(y), int(size), C.byref(opts), C.byref(k), C.byref(lmin), _dp(ev), _dp(co),
+                                         _dp(lh), _dp(ve), C.byref(it), C.byref(fl)), "hipsdp_sparsecuts")
+        kb = max(0, k.value)
+        return (k.value, lmin.value, ev[:kb].copy(), co[:kb * m].reshape(kb, m).copy(), lh[:kb].copy(), ve[:kb * n].reshape(kb, n).copy(),
+                it.value, fl.value)
+
+    @staticmethod
+    def sparsecuts_stats():
+        """process totals (calls, launches, read-backs): the module's sparsecuts_stats()"""
+        return sparsecuts_stats()
+
 
 class SparsecutOpts(C.Structure):
     """hipsdp_sparsecut_opts"""
@@ -434,6 +457,32 @@ def sparsecuts_all_stats():
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_sparsecuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_all_stats")
     return calls.value, launches.value, readbacks.value
+
+
+def sparsecuts_stats():
+    """process totals of hipsdp_sparsecuts: (calls, kernel launches issued, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_sparsecuts_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def sparsecuts_large_unit(n, Z, v0, maxeig, size, feastol, maxcuts, convtol=0, maxit=0, device=0):
+    """k_sc_tpower_large alone on one host matrix of 129 .. 512 rows (hipsdp_sparsecuts_large_unit of the units library): (ncuts,
+    eigvals[k], vecs[k, n], iters, flags)"""
+    n = int(n)
+    Z = _f64(np.asarray(Z, dtype=np.float64).reshape(-1))
+    v0 = _f64(np.asarray(v0, dtype=np.float64).reshape(-1))
+    assert len(Z) == n * n and len(v0) == n
+    opts = SparsecutOpts(0.0, feastol, convtol, maxcuts, maxit)
+    k, it, fl = C.c_int(0), C.c_int(0), C.c_int(0)
+    ev = np.zeros(max(1, maxcuts))
+    ve = np.zeros(max(1, maxcuts) * n)
+    rc = ulib().hipsdp_sparsecuts_large_unit(device, n, _dp(Z), _dp(v0), C.c_double(maxeig), int(size), C.byref(opts), C.byref(k), _dp(ev),
+                                             _dp(ve), C.byref(it), C.byref(fl))
+    if rc != 0:
+        raise RuntimeError("hipsdp_sparsecuts_large_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    kk = k.value
+    return kk, ev[:kk].copy(), ve[:kk * n].reshape(kk, n).copy(), it.value, fl.value
 
 
 def sparsecuts_unit(ns, Zs, v0s, maxeig, sizes, feastol, maxcuts, convtol=0, maxit=0, device=0):

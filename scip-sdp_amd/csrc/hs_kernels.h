@@ -367,6 +367,15 @@ struct hs_sc_out { int *ncuts, *iters, *flags; double *lmin, *eig, *lhs, *coef, 
 int hs_sc_tpower(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const int* sizes, const hs_sc_par* par, const hs_sc_out* out);
 int hs_sc_coefs(hipStream_t st, int count, int m, int maxcuts, const hs_ec_job* jobs, const int* sizes, const hs_sc_out* out);
 
+/* ---- sparsecuts_large.hip: the same for ONE block of 129 .. 512 rows (hipsdp_sparsecuts) ---------------------------------------- */
+#define HS_SCL_MAXN 512
+/* one workgroup: Z (n x n), lmin[0], maxeig[0] and the start vector v0[n] in device memory, MT: n^2 doubles that only this launch
+ * touches; the results go to index 0 of out (slots 0 .. maxcuts - 1, vectors from out.vec, supports with pitch out.smax) */
+int hs_scl_tpower(hipStream_t st, int n, int size, const double* Z, const double* lmin, const double* maxeig, const double* v0, double* MT,
+   const hs_sc_par* par, const hs_sc_out* out);
+/* grid (m + 1): x_c^T A_i x_c of every cut of job[0] (its blk and vecoff are 0) in any of the three storage forms */
+int hs_scl_coefs(hipStream_t st, int m, int maxcuts, int size, const hs_ec_job* job, const hs_sc_out* out);
+
 /* Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix A (destroyed): eigenvalues ascending in lam[n],
  * eigenvectors as rows of V (row k = k-th eigenvector).  info (device int) = sweeps used or -1. */
 int hs_syev_jacobi(hipStream_t s, int n, double* A, double* lam, double* V, int* info, double* ws);
@@ -392,6 +401,9 @@ size_t hs_syevx_ws(int n);
 /* its first stage alone (the unit entry): d, e, tau (n each) and the reflectors (row j = v_j, entry j + 1 one, zeros before) in ws */
 int hs_syevx_tridiag_dev(hipStream_t st, int n, const double* dA, double* ws);
 void hs_syevx_tridiag_view(int n, double* ws, double** d, double** e, double** R, double** tau);
+/* its stages 2 to 4 alone on the form hs_syevx_tridiag_dev left in ws: the arguments of hs_syevx_dev without the matrix, one launch
+ * for the values and two more for the vectors.  Several requests may follow one tridiagonalisation, each with a dOut of its own. */
+int hs_syevx_select_dev(hipStream_t st, int n, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws);
 
 /* ---- syevr.hip: ALL eigenpairs of a matrix of 2 .. 512 rows through the tridiagonal form (stage 1 is hs_syevx_tridiag_dev) --------
  * dA as for hs_syevx_dev.  dOut, HS_SYEVR_OUT(n) doubles: [k] k-th eigenvalue (ascending), [HS_SYEVR_OUT_VEC(n) + k n + i] component

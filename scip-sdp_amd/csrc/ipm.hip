@@ -5490,6 +5490,280 @@ extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const in
    return HIPSDP_OK;
 }
 
+/* ---- sparse eigenvector cuts of ONE block of up to 512 rows (kernels: csrc/sparsecuts.hip, csrc/sparsecuts_large.hip) ---------- */
+static std::atomic<long long> g_sc1_calls(0), g_sc1_launches(0), g_sc1_readbacks(0);
+
+extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   if ( calls != NULL ) *calls = g_sc1_calls.load();
+   if ( launches != NULL ) *launches = g_sc1_launches.load();
+   if ( readbacks != NULL ) *readbacks = g_sc1_readbacks.load();
+   return HIPSDP_OK;
+}
+
+static void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
+{
+   par->tol = opts->tol; par->feastol = opts->feastol;
+   par->convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+   par->maxcuts = opts->maxcuts;
+   par->maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+}
+
+/* a block of at most 128 rows: the launches of hipsdp_sparsecuts_all with this block as the only job.  The result block keeps that
+ * call's layout (indexed by the block's number), so the kernels and what they compute are the same to the bit. */
+static int sparsecuts_small(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, n = s->blk[block].n;
+   hipStream_t st = s->stream;
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   for (int b = block + 1; b <= nb; ++b)
+      vecoff[b] = (long long) maxcuts * n;                 /* only this block has vectors */
+   const std::vector<int> ids(1, block);
+   const int smax = size <= n ? size : 1;
+   const long long ylen = (m + 2) & ~1LL, szlen = ((long long) nb + 1) / 2;
+   const long long slots = (long long) nb * maxcuts;
+   const long long reslen = nb + 2 * slots + slots * m + vecoff[nb] + (3LL * nb + 1) / 2;
+   const long long suplen = (slots * smax + 1) / 2;
+   int nmax = 0;
+   HS_CALL( ec_prepare(s, ids, vecoff, ylen + szlen + reslen + suplen, ylen + szlen + reslen, &nmax) );
+   double* dy = s->ec_dev;
+   int* dsizes = reinterpret_cast<int*>(dy + ylen);
+   double* dres = dy + ylen + szlen;
+   hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
+   hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + sizeof(hs_ec_job));
+   hs_sc_out out;
+   memset(&out, 0, sizeof(out));
+   out.lmin = dres;
+   out.eig = out.lmin + nb;
+   out.lhs = out.eig + slots;
+   out.coef = out.lhs + slots;
+   out.vec = out.coef + slots * m;
+   out.ncuts = reinterpret_cast<int*>(out.vec + vecoff[nb]);
+   out.iters = out.ncuts + nb;
+   out.flags = out.iters + nb;
+   out.sup = reinterpret_cast<int*>(dres + reslen);
+   out.smax = smax;
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   int launches = 0;
+   if ( m > 0 )
+      memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
+   int* hsizes = reinterpret_cast<int*>(s->ec_pin + ylen);
+   for (int b = 0; b < nb; ++b)
+      hsizes[b] = b == block ? size : 1;
+   HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) (ylen + szlen) * sizeof(double), hipMemcpyHostToDevice, st) );
+   HS_CALL( hs_ec_form_z(st, 1, nmax, m, djobs, dy) );
+   ++launches;
+   HS_CALL( hs_syev_small_many(st, 1, s->ec_ejobs.data(), dejobs, &launches) );
+   HS_CALL( hs_sc_tpower(st, 1, nmax, djobs, dsizes, &par, &out) );
+   ++launches;
+   if ( maxcuts > 0 )
+   {
+      HS_CALL( hs_sc_coefs(st, 1, m, maxcuts, djobs, dsizes, &out) );
+      ++launches;
+   }
+   double* hres = s->ec_pin + ylen + szlen;
+   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_sc1_launches += launches;
+   g_sc1_readbacks += 1;
+   const double* h_eig = hres + nb;
+   const double* h_lhs = h_eig + slots;
+   const double* h_coef = h_lhs + slots;
+   const double* h_vec = h_coef + slots * m;
+   const int* h_ncuts = reinterpret_cast<const int*>(h_vec + vecoff[nb]);
+   const int k = h_ncuts[block];
+   if ( k < 0 || k > maxcuts )
+      return HIPSDP_ERR_NUMERIC;
+   *ncuts = k;
+   if ( lmin != NULL ) *lmin = hres[block];
+   if ( iters != NULL ) *iters = h_ncuts[nb + block];
+   if ( flags != NULL ) *flags = h_ncuts[2 * nb + block];
+   const size_t slot = (size_t) block * maxcuts;
+   if ( k > 0 )
+   {
+      memcpy(eigvals, h_eig + slot, (size_t) k * sizeof(double));
+      memcpy(lhs, h_lhs + slot, (size_t) k * sizeof(double));
+      if ( m > 0 )
+         memcpy(coefs, h_coef + slot * m, (size_t) k * m * sizeof(double));
+      if ( vecs != NULL )
+         memcpy(vecs, h_vec + vecoff[block], (size_t) k * n * sizeof(double));
+   }
+   return HIPSDP_OK;
+}
+
+/* a block of 129 .. 512 rows: Z(y), ONE tridiagonalisation, (lmin, v0) and maxeig from it, TPower in one workgroup, coefficients -
+ * n + 7 launches (n + 2 with maxcuts == 0) and one read-back.  The workspaces are those of the calls above: they only grow. */
+static int sparsecuts_large(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   const Block& B = s->blk[block];
+   const int m = s->m, maxcuts = opts->maxcuts, n = B.n;
+   hipStream_t st = s->stream;
+   const int smax = size <= n ? size : 1;
+   /* uploaded: y;  read back: lmin | eigvals | lhs | coefs | vecs | ncuts, iters, flags (int);  device only: supports (int), Z, the
+    * workspace of the tridiagonal form, the two requests' results, MT */
+   const long long ylen = (m + 2) & ~1LL, slots = maxcuts;
+   const long long reslen = (1 + 2 * slots + slots * m + slots * n + 2 + 1) & ~1LL;
+   const long long suplen = (slots * smax + 1) / 2;
+   const long long n2 = ((long long) n * n + 1) & ~1LL, wslen = ((long long) hs_syevx_ws(n) + 1) & ~1LL;
+   const long long o1len = (HS_SYEVX_OUT(n) + 1) & ~1LL, o2len = HS_SYEVX_OUT_VEC;
+   const long long need = ylen + reslen + suplen + n2 + wslen + o1len + o2len + n2;
+   const long long pin = ylen + (reslen > o2len ? reslen : o2len);
+   if ( need > s->ec_dev_len )
+   {
+      if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
+      s->ec_dev = NULL; s->ec_dev_len = 0;
+      HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
+      s->ec_dev_len = need;
+   }
+   if ( pin > s->ec_pin_len )
+   {
+      if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
+      s->ec_pin = NULL; s->ec_pin_len = 0;
+      HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) pin * sizeof(double), hipHostMallocDefault) );
+      s->ec_pin_len = pin;
+   }
+   if ( (long long) sizeof(hs_ec_job) > s->ec_tab_len )
+   {
+      if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
+      s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
+      HS_HIP( hipMalloc((void**) &s->ec_tab, sizeof(hs_ec_job)) );
+      s->ec_tab_len = (long long) sizeof(hs_ec_job);
+   }
+   double* dy = s->ec_dev;
+   double* dres = dy + ylen;
+   double* dZ = dres + reslen + suplen;
+   double* dws = dZ + n2;
+   double* o1 = dws + wslen;
+   double* o2 = o1 + o1len;
+   double* dMT = o2 + o2len;
+   hs_ec_job J;
+   memset(&J, 0, sizeof(J));
+   J.n = n; J.blk = 0;
+   J.ld = (long long) n * n;
+   if ( B.sparse )
+   {
+      J.form = HS_EC_SPARSE; J.A = B.A0;
+      hs_sp_get_view(B.sp, &J.sp);
+   }
+   else if ( B.Apk != NULL && B.apk_valid )
+   {
+      J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
+   }
+   else
+   {
+      J.form = HS_EC_DENSE; J.A = B.A;
+   }
+   J.Z = dZ; J.ws = dws;
+   hs_ec_job* djob = reinterpret_cast<hs_ec_job*>(s->ec_tab);
+   if ( s->ec_jobs.size() != 1 || memcmp(s->ec_jobs.data(), &J, sizeof(hs_ec_job)) != 0 )
+   {
+      HS_HIP( hipMemcpy(djob, &J, sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+      s->ec_jobs.assign(1, J); s->ec_ejobs.clear();
+   }
+   hs_sc_out out;
+   memset(&out, 0, sizeof(out));
+   out.lmin = dres;
+   out.eig = out.lmin + 1;
+   out.lhs = out.eig + slots;
+   out.coef = out.lhs + slots;
+   out.vec = out.coef + slots * m;
+   out.ncuts = reinterpret_cast<int*>(out.vec + slots * n);
+   out.iters = out.ncuts + 1;
+   out.flags = out.iters + 1;
+   out.sup = reinterpret_cast<int*>(dres + reslen);
+   out.smax = smax;
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   int launches = 0;
+   if ( m > 0 )
+   {
+      memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
+      HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
+   }
+   HS_CALL( hs_ec_form_z(st, 1, n, m, djob, dy) );
+   ++launches;
+   HS_CALL( hs_syevx_tridiag_dev(st, n, dZ, dws) );
+   launches += n;
+   double* hres = s->ec_pin + ylen;
+   if ( maxcuts == 0 )
+   {
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, o1, dws) );
+      ++launches;
+      HS_HIP( hipMemcpyAsync(hres, o1, (size_t) o2len * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      g_sc1_launches += launches;
+      g_sc1_readbacks += 1;
+      *ncuts = 0;
+      if ( lmin != NULL ) *lmin = hres[HS_SYEVX_OUT_LAM];
+      if ( iters != NULL ) *iters = 0;
+      if ( flags != NULL ) *flags = 0;
+      return HIPSDP_OK;
+   }
+   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
+   launches += 3;
+   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
+   ++launches;
+   HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, dMT, &par, &out) );
+   ++launches;
+   HS_CALL( hs_scl_coefs(st, m, maxcuts, size, djob, &out) );
+   ++launches;
+   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_sc1_launches += launches;
+   g_sc1_readbacks += 1;
+   const double* h_eig = hres + 1;
+   const double* h_lhs = h_eig + slots;
+   const double* h_coef = h_lhs + slots;
+   const double* h_vec = h_coef + slots * m;
+   const int* h_int = reinterpret_cast<const int*>(h_vec + slots * n);
+   const int k = h_int[0];
+   if ( k < 0 || k > maxcuts )
+      return HIPSDP_ERR_NUMERIC;
+   *ncuts = k;
+   if ( lmin != NULL ) *lmin = hres[0];
+   if ( iters != NULL ) *iters = h_int[1];
+   if ( flags != NULL ) *flags = h_int[2];
+   if ( k > 0 )
+   {
+      memcpy(eigvals, h_eig, (size_t) k * sizeof(double));
+      memcpy(lhs, h_lhs, (size_t) k * sizeof(double));
+      if ( m > 0 )
+         memcpy(coefs, h_coef, (size_t) k * m * sizeof(double));
+      if ( vecs != NULL )
+         memcpy(vecs, h_vec, (size_t) k * n * sizeof(double));
+   }
+   return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || y == NULL || opts == NULL || ncuts == NULL || size < 1
+      || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( opts->maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   const int n = s->blk[block].n;
+   *ncuts = -1;
+   if ( s->comm != NULL || s->shardA || n > HIPSDP_SPARSECUTS_MAXN )
+      return HIPSDP_OK;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
+   const Block& B = s->blk[block];
+   if ( B.sparse ? (B.sp == NULL || B.A0 == NULL) : B.A == NULL )
+      return HIPSDP_OK;
+   if ( n <= HS_SC_MAXN )
+      HS_CALL( sparsecuts_small(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
+   else
+      HS_CALL( sparsecuts_large(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
+   ++g_sc1_calls;
+   return HIPSDP_OK;
+}
+
 /* host-only: the column ranges of the sharded W formulation, bounds[0 .. nranks] (rank g owns [bounds[g], bounds[g + 1])) */
 extern "C" int hipsdp_shard_columns(int m1, int n, int nranks, int* bounds)
 {

@@ -445,15 +445,16 @@ void hs_syevx_tridiag_view(int n, double* ws, double** d, double** e, double** R
    *d = w.d; *e = w.e; *R = w.R; *tau = w.tau;
 }
 
-int hs_syevx_dev(hipStream_t st, int n, const double* dA, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws)
+/* stages 2 to 4 alone on the tridiagonal form that lies in ws (hs_syevx_tridiag_dev): one launch for the values, two more for the
+ * vectors.  May be called several times on one form, each time with a dOut of its own. */
+int hs_syevx_select_dev(hipStream_t st, int n, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws)
 {
    const int below = (mode & HS_SYEVX_BELOW) ? 1 : 0;
-   if ( n < 2 || n > SX_N || dA == NULL || dOut == NULL || ws == NULL )
+   if ( n < 2 || n > SX_N || dOut == NULL || ws == NULL )
       return HS_ERR_ARG;
    if ( below ? (maxk < 0 || maxk > SX_K) : (il < 1 || iu > n || il > iu || iu - il + 1 > SX_K) )
       return HS_ERR_ARG;
    const sx_ws w = sx_layout(n, ws);
-   HS_CALL( hs_syevx_tridiag_dev(st, n, dA, ws) );
    hipLaunchKernelGGL(k_syevx_values, dim3(1), dim3(SX_VT), 0, st, n, below, il, iu, bound, maxk, w.d, w.e, dOut);
    const int kmax = below ? maxk : iu - il + 1;
    if ( !(mode & HS_SYEVX_NOVEC) && kmax > 0 )
@@ -465,4 +466,15 @@ int hs_syevx_dev(hipStream_t st, int n, const double* dA, int mode, int il, int 
    }
    HS_HIP( hipGetLastError() );
    return HS_OK;
+}
+
+int hs_syevx_dev(hipStream_t st, int n, const double* dA, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws)
+{
+   const int below = (mode & HS_SYEVX_BELOW) ? 1 : 0;
+   if ( n < 2 || n > SX_N || dA == NULL || dOut == NULL || ws == NULL )
+      return HS_ERR_ARG;
+   if ( below ? (maxk < 0 || maxk > SX_K) : (il < 1 || iu > n || il > iu || iu - il + 1 > SX_K) )
+      return HS_ERR_ARG;
+   HS_CALL( hs_syevx_tridiag_dev(st, n, dA, ws) );
+   return hs_syevx_select_dev(st, n, mode, il, iu, bound, maxk, dOut, ws);
 }

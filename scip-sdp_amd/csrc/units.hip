@@ -1376,6 +1376,50 @@ extern "C" int hipsdp_sparsecuts_unit(int device, int count, const int* ns, cons
    return HIPSDP_OK;
 }
 
+/* k_sc_tpower_large alone (csrc/sparsecuts_large.hip) on one host matrix: lmin is given as -1 with tol = -infinity, so the matrix
+ * takes part */
+extern "C" int hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, const double* v0, double maxeig, int size,
+   const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags)
+{
+   HS_CALL( pick_device(device) );
+   if ( n <= HS_SC_MAXN || n > HS_SCL_MAXN || Z == NULL || v0 == NULL || size < 1 || opts == NULL || opts->maxcuts < 1 || ncuts == NULL
+      || eigvals == NULL || vecs == NULL || iters == NULL || flags == NULL )
+      return HIPSDP_ERR_ARG;
+   const int maxcuts = opts->maxcuts, smax = size <= n ? size : 1;
+   const long long n2 = (long long) n * n, slots = maxcuts;
+   /* input: lmin, maxeig | v0;  results: lmin | eigvals | vecs | ncuts, iters, flags (int) | supports (int) */
+   const long long inlen = 2 + (((long long) n + 1) & ~1LL);
+   const long long ipos = 1 + slots + slots * n, spos = ipos + 2, reslen = spos + (slots * smax + 1) / 2;
+   std::vector<double> hin((size_t) inlen, 0.0);
+   hin[0] = -1.0; hin[1] = maxeig;
+   memcpy(hin.data() + 2, v0, (size_t) n * sizeof(double));
+   DevBuf dz, dmt, din, dres;
+   HS_CALL( dz.alloc(n2) ); HS_CALL( dmt.alloc(n2) ); HS_CALL( din.alloc(inlen) ); HS_CALL( dres.alloc(reslen) );
+   HS_CALL( dz.up(Z, n2) ); HS_CALL( din.up(hin.data(), inlen) );
+   hs_sc_out out;
+   memset(&out, 0, sizeof(out));
+   out.lmin = dres.p; out.eig = dres.p + 1; out.vec = out.eig + slots;
+   out.ncuts = reinterpret_cast<int*>(dres.p + ipos); out.iters = out.ncuts + 1; out.flags = out.iters + 1;
+   out.sup = reinterpret_cast<int*>(dres.p + spos); out.smax = smax;
+   hs_sc_par par;
+   par.tol = -HUGE_VAL; par.feastol = opts->feastol;
+   par.convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+   par.maxcuts = maxcuts;
+   par.maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+   HS_CALL( hs_scl_tpower(0, n, size, dz.p, din.p, din.p + 1, din.p + 2, dmt.p, &par, &out) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> h((size_t) spos);
+   HS_CALL( dres.down(h.data(), spos) );
+   const int* hi = reinterpret_cast<const int*>(h.data() + ipos);
+   const int k = hi[0];
+   if ( k < 0 || k > maxcuts )
+      return HIPSDP_ERR_NUMERIC;
+   *ncuts = k; *iters = hi[1]; *flags = hi[2];
+   memcpy(eigvals, h.data() + 1, (size_t) k * sizeof(double));
+   memcpy(vecs, h.data() + 1 + slots, (size_t) k * n * sizeof(double));
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau)
 {
    HS_CALL( pick_device(device) );
