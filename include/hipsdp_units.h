@@ -40,6 +40,22 @@ HIPSDP_API int  hipsdp_schur_dense(int device, int m1, int n, const double* A, c
    double ws_gbytes);
 /* the same matrix through the W formulation (W_j = G A_j R, Mx = W W^T); takes X and Z, factors them on the device */
 HIPSDP_API int  hipsdp_schur_w(int device, int m1, int n, const double* A, const double* X, const double* Z, double* Mx);
+/* one dense block through ONE form of the assembly from the caller's operands, all parts of a sharded form added up on this device:
+ * form 0 hs_schur_W            P = R, Q = G  (lower triangular, upper triangle zero: X = R R^T, Z^-1 = G^T G; nothing is factored here)
+ *      1 hs_schur_Wcols        P = R, Q = G; the `parts` slices of hs_shard_cols one behind the other into the same Mx
+ *      2 hs_schur_Urows        P = X, Q = Zinv; the 2 * parts chunks of hs_shard_rows, then hs_mirror_upper
+ *      3 hs_schur_U            P = X, Q = Zinv; ws_gbytes > 0 chunks it as hipsdp_schur_dense does
+ *      4 hs_schur_Wvar         P = R, Q = G; null communicator of ONE rank, column slices of `parts` columns
+ * Mx: m1 x m1, both triangles.  used[3] (may be NULL): products of this call taken by the persistent kernels of dgemm2.hip, of these
+ * by the paired-band kernel, and Gram products taken by gram.hip.  parts: 1 .. 64 (forms 1, 2), >= 1 (form 4), ignored otherwise;
+ * anything else HIPSDP_ERR_ARG before the first launch */
+HIPSDP_API int  hipsdp_schur_form_unit(int device, int form, int parts, int m1, int n, const double* A, const double* P, const double* Q,
+   double ws_gbytes, double* Mx, int* used);
+/* hs_schur_small alone: nblk <= 8 blocks of ns[k] <= 48 rows (A[k]: m1 matrices of ns[k] x ns[k]), q LP rows (Dext[q][m1], x[q], z[q];
+ * q = 0: NULL).  *taken = its return value (0: shape not admitted, nothing written: Mx, Lm, diagM come back as they were passed in);
+ * Mx m1 x m1, Lm (m1-1) x (m1-1), diagM[m1-1] */
+HIPSDP_API int  hipsdp_schur_small_unit(int device, int m1, int nblk, const int* ns, const double* const* A, const double* const* X,
+   const double* const* Zinv, int q, const double* Dext, const double* x, const double* z, double* Mx, double* Lm, double* diagM, int* taken);
 /* milliseconds one rank of an nranks-way sharded assembly spends on its share of the Schur matrix (by_columns: column slices
  * of the W formulation, else row chunks of the U formulation); synthetic operands made in HBM */
 HIPSDP_API int  hipsdp_schur_shard_time(int device, int m1, int n, int nranks, int rank, int by_columns, int reps, double ws_gbytes, double* ms);

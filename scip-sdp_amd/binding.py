@@ -617,6 +617,53 @@ def schur_w(A, X, Z, device=0):
     return Mx
 
 
+def schur_form_unit(form, A, P, Q, parts=1, ws_gbytes=0.0, device=0):
+    """one dense block through ONE form of the assembly from the caller's operands (0 hs_schur_W, 1 hs_schur_Wcols in `parts` slices,
+    2 hs_schur_Urows in 2 * parts chunks, 3 hs_schur_U, 4 hs_schur_Wvar in slices of `parts` columns; W forms: P = R, Q = G, U forms:
+    P = X, Q = Zinv) -> (Mx with both triangles, (products of the persistent kernels, of these the paired-band kernel's, Gram kernel's))"""
+    A = _f64(A)
+    m1, n = A.shape[0], A.shape[1]
+    P = _f64(P); Q = _f64(Q)
+    assert A.shape == (m1, n, n) and P.shape == (n, n) and Q.shape == (n, n)
+    Mx = np.zeros((m1, m1))
+    used = (C.c_int * 3)(0, 0, 0)
+    _chk(ulib().hipsdp_schur_form_unit(device, form, parts, m1, n, _dp(A), _dp(P), _dp(Q), C.c_double(ws_gbytes), _dp(Mx), used),
+         "hipsdp_schur_form_unit")
+    return Mx, tuple(used)
+
+
+def schur_small_unit(As, Xs, Zinvs, Dext=None, x=None, z=None, fill=0.0, device=0):
+    """hs_schur_small alone: block k has the matrices As[k] (m1 x n_k x n_k), Xs[k], Zinvs[k]; LP rows Dext (q x m1), x, z or None
+    -> (taken, Mx, Lm, diagM); the outputs start as `fill`, which is what comes back where the kernel wrote nothing"""
+    As = [_f64(a) for a in As]; Xs = [_f64(a) for a in Xs]; Zinvs = [_f64(a) for a in Zinvs]
+    nblk, m1 = len(As), As[0].shape[0]
+    ns = np.array([a.shape[1] for a in As], dtype=np.int32)
+    for k in range(nblk):
+        assert As[k].shape == (m1, ns[k], ns[k]) and Xs[k].shape == (ns[k], ns[k]) and Zinvs[k].shape == (ns[k], ns[k])
+    q = 0 if Dext is None else int(np.shape(Dext)[0])
+    if q > 0:
+        Dext = _f64(Dext); x = _f64(x); z = _f64(z)
+        assert Dext.shape == (q, m1) and x.shape == (q,) and z.shape == (q,)
+    arr = C.POINTER(C.c_double) * nblk
+    pA, pX, pZ = arr(*[_dp(a) for a in As]), arr(*[_dp(a) for a in Xs]), arr(*[_dp(a) for a in Zinvs])
+    m = m1 - 1
+    Mx = np.full((m1, m1), fill)
+    Lm = np.full(max(m * m, 1), fill)
+    dg = np.full(max(m, 1), fill)
+    taken = C.c_int(-1)
+    _chk(ulib().hipsdp_schur_small_unit(device, m1, nblk, _ip(ns), pA, pX, pZ, q, _dp(Dext) if q else None, _dp(x) if q else None,
+                                        _dp(z) if q else None, _dp(Mx), _dp(Lm), _dp(dg), C.byref(taken)), "hipsdp_schur_small_unit")
+    return taken.value, Mx, Lm[:m * m].reshape(m, m), dg[:m]
+
+
+def gram_plan_info(M, K, nslab=64, device=0):
+    """the plan csrc/gram.hip chooses for the Gram product of a shape -> (no, nd, items, span), or None when it takes none"""
+    no, nd, ni = C.c_int(0), C.c_int(0), C.c_int(0)
+    sp = C.c_double(0.0)
+    rc = ulib().hipsdp_gram_plan_info(device, M, C.c_longlong(K), nslab, C.byref(no), C.byref(nd), C.byref(ni), C.byref(sp))
+    return (no.value, nd.value, ni.value, sp.value) if rc == 0 else None
+
+
 def dgemm_selfcheck(M, N, K, layB=1, batch=1, splitk=1, flags=0, beta=0.0, device=0):
     """both GEMM kernels on the same device-generated operands -> (used_v2, number of elements of C differing in any bit)"""
     used = C.c_int(0)

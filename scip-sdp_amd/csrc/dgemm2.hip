@@ -1308,6 +1308,7 @@ extern "C" __attribute__((visibility("default"))) int hs_dgemm5_prof_read(unsign
 /* 1: launched, 0: not eligible (caller uses dgemm.hip), < 0: error code negated */
 static int g2_disabled = 0;
 static int g2_taken = 0;
+static int g5_taken = 0;
 
 /* test hook: on = 0 forces dgemm.hip for every product, on = 1 restores the default; returns how many products the
  * persistent kernel has taken so far */
@@ -1315,6 +1316,12 @@ int hs_dgemm2_enable(int on)
 {
    g2_disabled = on ? 0 : 1;
    return __atomic_load_n(&g2_taken, __ATOMIC_RELAXED);
+}
+
+/* test hook: how many of those products went to the paired-band kernel */
+int hs_dgemm2_paired_taken(void)
+{
+   return __atomic_load_n(&g5_taken, __ATOMIC_RELAXED);
 }
 
 /* 16 counters per (device, stream): launches on one stream are ordered, so they can share them (cleared before each launch);
@@ -1415,6 +1422,7 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
       if ( hipGetLastError() != hipSuccess )
          return -HS_ERR_HIP;
       (void) __atomic_add_fetch(&g2_taken, 1, __ATOMIC_RELAXED);
+      (void) __atomic_add_fetch(&g5_taken, 1, __ATOMIC_RELAXED);
       return 1;
    }
    const int il = triA != triB ? (triB ? 1 : 2) : 0;

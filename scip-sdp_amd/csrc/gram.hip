@@ -559,6 +559,14 @@ GramPlan* gr_plan(int M, long long K, int nslab)
 
 }
 
+static int gr_taken = 0;
+
+/* test hook: how many products the Gram kernel has taken so far */
+int hs_gram_taken(void)
+{
+   return __atomic_load_n(&gr_taken, __ATOMIC_RELAXED);
+}
+
 /* C (M x M, lower triangle) = alpha W W^T + beta C with W [M][K] (K contiguous, leading dimension ldw), through `nslab` slabs of
  * M x M doubles at ws.  1: done, 0: not eligible (the caller takes hs_dgemm), < 0: error code negated.  *executed: the FP64
  * matrix-core flops the launch executes. */
@@ -591,6 +599,7 @@ int hs_gram_try(hipStream_t stream, int M, long long K, const double* W, long lo
    }
    if ( executed != NULL )
       *executed = P->executed;
+   (void) __atomic_add_fetch(&gr_taken, 1, __ATOMIC_RELAXED);
    return 1;
 }
 

@@ -106,6 +106,8 @@ int hs_dgemm(hipStream_t stream, const hs_gemm_args* args);
 /* persistent LDS-DMA variant for the 128-tile shapes (dgemm2.hip): 1 launched, 0 not eligible, < 0 error (negated code) */
 int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* args, int kchunk);
 int hs_dgemm2_enable(int on);
+int hs_dgemm2_paired_taken(void);
+int hs_gram_taken(void);
 
 /* the Gram product of the Schur assembly (gram.hip): C (M x M, lower triangle) = alpha W W^T + beta C with W [M][K] K contiguous,
  * through nslab >= 8 slabs of M x M doubles at ws; diagonal tiles at 9 / 16 of the matrix instructions, a static list of items per

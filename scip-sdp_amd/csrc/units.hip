@@ -567,6 +567,140 @@ extern "C" int hipsdp_schur_w(int device, int m1, int n, const double* A, const 
    return HIPSDP_OK;
 }
 
+/* One dense block through ONE form of the assembly, from the caller's operands (nothing is factored here), every part of a sharded
+ * form added up on this device in rank order.  The workspace of each form is sized as the engine sizes it: forms 0, 2, 3 for the
+ * whole block (3: under ws_gbytes with the small chunks of hipsdp_schur_dense), 1 for its widest slice, 4 by hs_schur_ws_alloc_var.
+ * used[3]: products the persistent kernels took during the call, of these the paired-band kernel's, and the Gram kernel's. */
+extern "C" int hipsdp_schur_form_unit(int device, int form, int parts, int m1, int n, const double* A, const double* P, const double* Q,
+   double ws_gbytes, double* Mx, int* used)
+{
+   HS_CALL( pick_device(device) );
+   if ( form < 0 || form > 4 || m1 < 1 || n < 1 || A == NULL || P == NULL || Q == NULL || Mx == NULL || !(ws_gbytes == ws_gbytes) )
+      return HIPSDP_ERR_ARG;
+   if ( ((form == 1 || form == 2) && (parts < 1 || parts > 64)) || (form == 4 && parts < 1) )
+      return HIPSDP_ERR_ARG;
+   const long long n2 = (long long) n * n;
+   if ( n2 > 2000000000LL || (long long) m1 * n > 2000000000LL || (long long) m1 * m1 > 2000000000LL )
+      return HIPSDP_ERR_ARG;
+   DevBuf dA, dP, dQ, dM;
+   HS_CALL( dA.alloc(m1 * n2) ); HS_CALL( dP.alloc(n2) ); HS_CALL( dQ.alloc(n2) ); HS_CALL( dM.alloc((long long) m1 * m1) );
+   HS_CALL( dA.up(A, m1 * n2) ); HS_CALL( dP.up(P, n2) ); HS_CALL( dQ.up(Q, n2) );
+   hs_schur_ws w;
+   void* comm = NULL;
+   int rc = HS_OK;
+   if ( form == 1 )
+   {
+      long long widest = 1;
+      for (int g = 0; g < parts; ++g)
+      {
+         int c0, cw;
+         hs_shard_cols(m1, n, parts, g, &c0, &cw);
+         if ( (long long) n * cw > widest ) widest = (long long) n * cw;
+      }
+      rc = hs_schur_ws_alloc(&w, m1, widest, 40.0);
+   }
+   else if ( form == 4 )
+   {
+      if ( parts > n ) parts = n;
+      rc = hipsdp_comm_create_null(0, 1, &comm);
+      if ( rc != HS_OK )
+         return rc;
+      rc = hs_schur_ws_alloc_var(&w, m1, 1, n, parts);
+   }
+   else
+   {
+      rc = hs_schur_ws_alloc(&w, m1, n2, form == 3 && ws_gbytes > 0.0 ? ws_gbytes : 40.0);
+      if ( rc == HS_OK && form == 3 && ws_gbytes > 0.0 && w.chunk_cols > 1 )
+      {
+         long long cols = (long long) (ws_gbytes * 1e9 / (16.0 * (double) n2));
+         if ( cols < 1 ) cols = 1;
+         if ( cols < w.chunk_cols ) w.chunk_cols = cols;
+      }
+   }
+   const int t2 = hs_dgemm2_enable(1), t5 = hs_dgemm2_paired_taken(), tg = hs_gram_taken();
+   if ( rc == HS_OK ) rc = hs_fill(0, dM.p, (long long) m1 * m1, 0.0);
+   switch ( form )
+   {
+   case 0:
+      if ( rc == HS_OK ) rc = hs_schur_W(0, m1, n, dA.p, dP.p, dQ.p, dM.p, &w);
+      break;
+   case 1:
+      for (int g = 0; g < parts && rc == HS_OK; ++g)
+      {
+         int c0, cw;
+         hs_shard_cols(m1, n, parts, g, &c0, &cw);
+         rc = hs_schur_Wcols(0, m1, n, dA.p, dP.p, dQ.p, dM.p, &w, c0, cw);
+      }
+      break;
+   case 2:
+      for (int g = 0; g < parts && rc == HS_OK; ++g)
+      {
+         int c, b1, b2;
+         hs_shard_rows(m1, parts, g, &c, &b1, &b2);
+         rc = hs_schur_Urows(0, m1, n, dA.p, dP.p, dQ.p, dM.p, &w, b1, b1 + c);
+         if ( rc == HS_OK ) rc = hs_schur_Urows(0, m1, n, dA.p, dP.p, dQ.p, dM.p, &w, b2, b2 + c);
+      }
+      break;
+   case 3:
+      if ( rc == HS_OK ) rc = hs_schur_U(0, m1, n, dA.p, dP.p, dQ.p, dM.p, &w, 0, m1);
+      break;
+   default:
+      if ( rc == HS_OK ) rc = hs_schur_Wvar_all(0, NULL, comm, 0, 1, m1, n, dA.p, dP.p, dQ.p, dM.p, &w, parts, 0);
+      break;
+   }
+   if ( rc == HS_OK ) rc = form == 2 ? hs_mirror_upper(0, dM.p, m1, m1) : hs_mirror_lower(0, dM.p, m1, m1);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   if ( used != NULL )
+   {
+      used[0] = hs_dgemm2_enable(1) - t2;
+      used[1] = hs_dgemm2_paired_taken() - t5;
+      used[2] = hs_gram_taken() - tg;
+   }
+   hs_schur_ws_free(&w);
+   if ( comm != NULL )
+      hipsdp_comm_destroy(comm);
+   HS_CALL( rc );
+   HS_CALL( dM.down(Mx, (long long) m1 * m1) );
+   return HIPSDP_OK;
+}
+
+/* hs_schur_small alone on host operands: block k has ns[k] rows and m1 matrices A[k][m1][ns[k]^2]; outputs are copied back only when
+ * the kernel took the shape (*taken = 1), so a refused shape leaves the caller's arrays as they were */
+extern "C" int hipsdp_schur_small_unit(int device, int m1, int nblk, const int* ns, const double* const* A, const double* const* X,
+   const double* const* Zinv, int q, const double* Dext, const double* x, const double* z, double* Mx, double* Lm, double* diagM, int* taken)
+{
+   HS_CALL( pick_device(device) );
+   if ( m1 < 1 || m1 > 32768 || nblk < 1 || nblk > 64 || ns == NULL || A == NULL || X == NULL || Zinv == NULL || q < 0 || Mx == NULL
+      || Lm == NULL || diagM == NULL || taken == NULL || (q > 0 && (Dext == NULL || x == NULL || z == NULL)) )
+      return HIPSDP_ERR_ARG;
+   for (int k = 0; k < nblk; ++k)
+      if ( ns[k] < 1 || ns[k] > 4096 || A[k] == NULL || X[k] == NULL || Zinv[k] == NULL )
+         return HIPSDP_ERR_ARG;
+   const int m = m1 - 1;
+   std::vector<DevBuf> dA(nblk), dX(nblk), dZ(nblk);
+   std::vector<const double*> pA(nblk), pX(nblk), pZ(nblk);
+   for (int k = 0; k < nblk; ++k)
+   {
+      const long long n2 = (long long) ns[k] * ns[k];
+      HS_CALL( dA[k].alloc(m1 * n2) ); HS_CALL( dX[k].alloc(n2) ); HS_CALL( dZ[k].alloc(n2) );
+      HS_CALL( dA[k].up(A[k], m1 * n2) ); HS_CALL( dX[k].up(X[k], n2) ); HS_CALL( dZ[k].up(Zinv[k], n2) );
+      pA[k] = dA[k].p; pX[k] = dX[k].p; pZ[k] = dZ[k].p;
+   }
+   DevBuf dD, dx, dz, dM, dL, dg;
+   HS_CALL( dD.alloc((long long) q * m1) ); HS_CALL( dx.alloc(q) ); HS_CALL( dz.alloc(q) );
+   HS_CALL( dM.alloc((long long) m1 * m1) ); HS_CALL( dL.alloc((long long) m * m) ); HS_CALL( dg.alloc(m) );
+   HS_CALL( dD.up(Dext, (long long) q * m1) ); HS_CALL( dx.up(x, q) ); HS_CALL( dz.up(z, q) );
+   HS_CALL( dM.up(Mx, (long long) m1 * m1) ); HS_CALL( dL.up(Lm, (long long) m * m) ); HS_CALL( dg.up(diagM, m) );
+   const int r = hs_schur_small(0, m1, nblk, ns, pA.data(), pX.data(), pZ.data(), q, q > 0 ? dD.p : NULL, q > 0 ? dx.p : NULL,
+      q > 0 ? dz.p : NULL, dM.p, dL.p, dg.p);
+   if ( r < 0 )
+      return -r;
+   HS_HIP( hipDeviceSynchronize() );
+   *taken = r;
+   HS_CALL( dM.down(Mx, (long long) m1 * m1) ); HS_CALL( dL.down(Lm, (long long) m * m) ); HS_CALL( dg.down(diagM, m) );
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_potrf(int device, int n, double* A, int* fail)
 {
    HS_CALL( pick_device(device) );
