@@ -1,0 +1,55 @@
+/* hs_cut_plan.cpp - see hs_cut_plan.h */
+#include "hs_cut_plan.h"
+
+static long long even(long long len) { return (len + 1) & ~1LL; }
+
+/* lmin .. vec from offset `at` on; returns the offset behind the vectors */
+static long long res_arrays(long long at, int nb, int m, int maxcuts, long long vec_len, hs_cut_res* r)
+{
+   const long long slots = (long long) nb * maxcuts;
+   r->nb = nb; r->smax = 0;
+   r->ints = r->sup = -1;
+   r->lmin = at; r->eig = r->lmin + nb; r->lhs = r->eig + slots; r->coef = r->lhs + slots; r->vec = r->coef + slots * m;
+   return r->vec + vec_len;
+}
+
+void hs_ec_layout_make(int nb, int m, int maxcuts, long long vec_len, long long slab_len, hs_ec_layout* L)
+{
+   L->y = 0;
+   L->ncuts = (m + 2) & ~1LL;
+   L->slabs = res_arrays(L->ncuts + nb, nb, m, maxcuts, vec_len, &L->r);
+   L->len.res_off = L->ncuts; L->len.res_len = L->slabs - L->ncuts;
+   L->len.upload_len = m; L->len.pin_len = L->slabs; L->len.dev_len = L->slabs + slab_len;
+}
+
+void hs_sc_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, hs_sc_layout* L)
+{
+   L->y = 0;
+   L->sizes = (m + 2) & ~1LL;
+   L->len.res_off = L->sizes + ((long long) nb + 1) / 2;
+   L->r.ints = res_arrays(L->len.res_off, nb, m, maxcuts, vec_len, &L->r);
+   L->r.smax = smax;
+   L->r.sup = L->r.ints + (3LL * nb + 1) / 2;
+   L->slabs = L->r.sup + ((long long) nb * maxcuts * smax + 1) / 2;
+   L->len.res_len = L->r.sup - L->len.res_off;
+   L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->slabs + slab_len;
+}
+
+void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, long long out_len, long long out_vec, hs_scl_layout* L)
+{
+   const long long ylen = (m + 2) & ~1LL;
+   L->y = 0;
+   L->len.res_off = ylen;
+   L->r.ints = res_arrays(ylen, 1, m, maxcuts, (long long) maxcuts * n, &L->r);
+   L->r.smax = smax;
+   L->len.res_len = even(L->r.ints + 2 - ylen);          /* three ints, and an even length */
+   L->r.sup = ylen + L->len.res_len;
+   L->Z = L->r.sup + even(((long long) maxcuts * smax + 1) / 2);
+   L->ws = L->Z + hs_cut_mat_len(n);
+   L->o1 = L->ws + even(ws_len);
+   L->o2 = L->o1 + even(out_len);
+   L->MT = L->o2 + out_vec;
+   L->len.upload_len = m;
+   L->len.pin_len = ylen + (L->len.res_len > out_vec ? L->len.res_len : out_vec);      /* maxcuts = 0 reads the head of o1 back */
+   L->len.dev_len = L->MT + hs_cut_mat_len(n);
+}

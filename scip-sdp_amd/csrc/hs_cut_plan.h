@@ -1,0 +1,59 @@
+/* hs_cut_plan.h - where everything lies in the workspace of the cut calls of csrc/ipm.hip (hipsdp_eigencuts_all, hipsdp_sparsecuts_all,
+ * hipsdp_sparsecuts): one layout per call form, written down once.  All offsets and lengths count doubles from the start of the device
+ * workspace; the pinned host buffer mirrors its head (upload and read-back lie at the same offsets), so ONE view function gives the
+ * pointers the launches take (applied to the device buffer) and the pointers the copy-out reads (applied to the pinned one).
+ * Host only: nothing here includes or calls HIP, so the file compiles with the host compiler alone (tests/harness/cut_plan_check.cpp
+ * runs it under the sanitizers). */
+#ifndef HS_CUT_PLAN_H
+#define HS_CUT_PLAN_H
+
+#include <string.h>
+
+/* where the kernels of sparsecuts.hip / sparsecuts_large.hip put their results, all indexed by the block's index (hs_ec_job.blk) or its
+ * slots blk * maxcuts + c; sup: smax ints per slot, the ascending support of the cut (k_sc_tpower writes it, k_sc_coefs reads it) */
+struct hs_sc_out { int *ncuts, *iters, *flags; double *lmin, *eig, *lhs, *coef, *vec; int* sup; int smax, pad; };
+
+/* the result arrays of a call over nb blocks with slots = nb maxcuts, in this order:
+ *    lmin[nb] | eig[slots] | lhs[slots] | coef[slots m] | vec[vec_len] | ints: ncuts[nb], iters[nb], flags[nb] | sup[slots smax] (int)
+ * ints and sup are -1 in the form that has none (eigencuts-all: its counts are doubles in front of lmin) */
+struct hs_cut_res { long long lmin, eig, lhs, coef, vec, ints, sup; int nb, smax; };
+
+/* res_off, res_len: the one read-back (to the same offset of the pinned buffer); upload_len: doubles uploaded from offset 0 */
+struct hs_cut_lens { long long res_off, res_len, upload_len, pin_len, dev_len; };
+
+/* hipsdp_eigencuts_all:  y | ncuts[nb] (as doubles) | res | slabs (Z and decomposition workspace of every batched block) */
+struct hs_ec_layout { long long y, ncuts; hs_cut_res r; long long slabs; hs_cut_lens len; };
+/* hipsdp_sparsecuts_all, and hipsdp_sparsecuts up to 128 rows:  y | sizes[nb] (int) | res | sup | slabs */
+struct hs_sc_layout { long long y, sizes; hs_cut_res r; long long slabs; hs_cut_lens len; };
+/* hipsdp_sparsecuts above 128 rows (nb = 1):  y | res | sup | Z | workspace of the tridiagonal form | the two selection outputs | MT;
+ * Z and MT start at even offsets */
+struct hs_scl_layout { long long y; hs_cut_res r; long long Z, ws, o1, o2, MT; hs_cut_lens len; };
+
+/* an n x n matrix in the workspace: n^2 doubles rounded up to an even count */
+static inline long long hs_cut_mat_len(int n) { return ((long long) n * n + 1) & ~1LL; }
+
+/* vec_len: doubles of all vectors (maxcuts * rows of the blocks that return vectors); slab_len: sum of hs_cut_mat_len(n) +
+ * hs_syev_small_scratch(n) over the batched blocks */
+void hs_ec_layout_make(int nb, int m, int maxcuts, long long vec_len, long long slab_len, hs_ec_layout* L);
+void hs_sc_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, hs_sc_layout* L);
+/* ws_len = hs_syevx_ws(n), out_len = HS_SYEVX_OUT(n), out_vec = HS_SYEVX_OUT_VEC (csrc/syevx.hip), passed in as numbers */
+void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, long long out_len, long long out_vec, hs_scl_layout* L);
+
+/* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
+static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
+{
+   hs_sc_out o;
+   memset(&o, 0, sizeof(o));
+   o.lmin = base + r.lmin; o.eig = base + r.eig; o.lhs = base + r.lhs; o.coef = base + r.coef; o.vec = base + r.vec;
+   if ( r.ints >= 0 )
+   {
+      o.ncuts = reinterpret_cast<int*>(base + r.ints);
+      o.iters = o.ncuts + r.nb;
+      o.flags = o.iters + r.nb;
+      o.sup = reinterpret_cast<int*>(base + r.sup);
+   }
+   o.smax = r.smax;
+   return o;
+}
+
+#endif

@@ -5,6 +5,7 @@
 #define HS_KERNELS_H
 
 #include "hs_common.h"
+#include "hs_cut_plan.h"
 
 /* ---- kernels.hip ---------------------------------------------------------------------------------------------- */
 int hs_fill(hipStream_t s, double* p, long long n, double v);
@@ -352,16 +353,14 @@ struct hs_ec_job
    long long vecoff;             /* where the block's vectors start in the result: maxcuts * (rows of the blocks before it) */
 };
 /* the result block of a call for nb blocks, doubles: ncuts[nb] | lmin[nb] | eigvals[nb maxcuts] | lhs[nb maxcuts] |
- * coefs[nb maxcuts m] | vecs[maxcuts sum n] */
+ * coefs[nb maxcuts m] | vecs[maxcuts sum n] (written down once for the host side: hs_ec_layout in hs_cut_plan.h) */
 int hs_ec_form_z(hipStream_t st, int count, int nmax, int m, const hs_ec_job* jobs, const double* y);
 int hs_ec_cuts(hipStream_t st, int count, int nmax, int m, int nb, int maxcuts, double tol, const hs_ec_job* jobs, double* res);
 
 /* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
 #define HS_SC_MAXN 128
 struct hs_sc_par { double tol, feastol, convtol; int maxcuts, maxit; };      /* convtol > 0, maxit >= 1: the defaults are the caller's */
-/* where the kernels put their results, all indexed by the block's index (hs_ec_job.blk) or its slots blk * maxcuts + c; sup: smax
- * ints per slot, the ascending support of the cut (k_sc_tpower writes it, k_sc_coefs reads it) */
-struct hs_sc_out { int *ncuts, *iters, *flags; double *lmin, *eig, *lhs, *coef, *vec; int* sup; int smax, pad; };
+/* hs_sc_out, where the kernels put their results: hs_cut_plan.h, with the layouts of the workspace it points into */
 /* one workgroup per job: Z from job.Z, eigenvalues ascending at job.ws (lmin first, maxeig last), v0 at job.ws + job.vpos;
  * sizes[job.blk]: the target sparsity */
 int hs_sc_tpower(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const int* sizes, const hs_sc_par* par, const hs_sc_out* out);

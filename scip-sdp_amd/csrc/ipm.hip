@@ -111,6 +111,58 @@ struct PhaseClock
    double ms[PH_COUNT];
 };
 
+/* The workspace of the cut calls (hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts; layouts: hs_cut_plan.h), grow-only and
+ * kept until hipsdp_free: the device buffer, its pinned host mirror (upload and read-back), the job tables on the device (the hs_ec_job
+ * of a round and behind them their hs_eig_job) and the host copies they were uploaded from. */
+struct CutWs
+{
+   double* dev = NULL; long long dev_len = 0;
+   double* pin = NULL; long long pin_len = 0;
+   char* tab = NULL; long long tab_len = 0;
+   std::vector<hs_ec_job> jobs; std::vector<hs_eig_job> ejobs;
+
+   /* *p (len units of `unit` bytes) holds at least `need` units afterwards; nothing is kept across a reallocation */
+   static int regrow(void** p, long long* len, long long need, size_t unit, bool pinned)
+   {
+      if ( need <= *len )
+         return HS_OK;
+      if ( *p != NULL ) HS_HIP( pinned ? hipHostFree(*p) : hipFree(*p) );
+      *p = NULL; *len = 0;
+      HS_HIP( pinned ? hipHostMalloc(p, (size_t) need * unit, hipHostMallocDefault) : hipMalloc(p, (size_t) need * unit) );
+      *len = need;
+      return HS_OK;
+   }
+   /* lengths in doubles, the tables in bytes; a reallocated table forgets what it held */
+   int grow(long long dev_need, long long pin_need, size_t tab_bytes)
+   {
+      HS_CALL( regrow((void**) &dev, &dev_len, dev_need, sizeof(double), false) );
+      HS_CALL( regrow((void**) &pin, &pin_len, pin_need, sizeof(double), true) );
+      if ( (long long) tab_bytes > tab_len ) { jobs.clear(); ejobs.clear(); }
+      return regrow((void**) &tab, &tab_len, (long long) tab_bytes, 1, false);
+   }
+   /* the tables of a round (je may be empty), uploaded when they differ from what the device holds: first use, a new shape, another
+    * storage form, a workspace laid out differently */
+   int upload(const std::vector<hs_ec_job>& j, const std::vector<hs_eig_job>& je)
+   {
+      if ( jobs.size() == j.size() && memcmp(jobs.data(), j.data(), j.size() * sizeof(hs_ec_job)) == 0 )
+         return HS_OK;
+      HS_HIP( hipMemcpy(tab, j.data(), j.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+      if ( !je.empty() )
+         HS_HIP( hipMemcpy(tab + j.size() * sizeof(hs_ec_job), je.data(), je.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
+      jobs = j; ejobs = je;
+      return HS_OK;
+   }
+   const hs_ec_job* djobs() const { return reinterpret_cast<const hs_ec_job*>(tab); }
+   const hs_eig_job* dejobs() const { return reinterpret_cast<const hs_eig_job*>(tab + jobs.size() * sizeof(hs_ec_job)); }
+   void release()
+   {
+      if ( dev != NULL ) (void) hipFree(dev);
+      if ( tab != NULL ) (void) hipFree(tab);
+      if ( pin != NULL ) (void) hipHostFree(pin);
+      dev = NULL; tab = NULL; pin = NULL;
+   }
+};
+
 struct hipsdp_solver
 {
    int device;
@@ -203,14 +255,7 @@ struct hipsdp_solver
    int s1_last;            /* 1: the last solve ran in the single launch */
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
-   /* hipsdp_eigencuts_all (csrc/eigcuts.hip) and hipsdp_sparsecuts_all (csrc/sparsecuts.hip), all grow-only and kept until
-    * hipsdp_free: device workspace (y, result block, Z and decomposition slab per batched block), its pinned host mirror (y, result
-    * block), the job tables on the device and the host copies they were uploaded from (a call uploads them again only when they
-    * differ) */
-   double* ec_dev; long long ec_dev_len;
-   double* ec_pin; long long ec_pin_len;
-   char* ec_tab; long long ec_tab_len;
-   std::vector<hs_ec_job> ec_jobs; std::vector<hs_eig_job> ec_ejobs;
+   CutWs cw;               /* hipsdp_eigencuts_all (csrc/eigcuts.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts (csrc/sparsecuts*.hip) */
    /* the first assembly of a cold solve, kept across solves of the same matrices (hs_gram_cache.h; GeneralSolve::assemble_forms):
     * gc_M holds (m1 + 32) m1 doubles as the identity assemblies left them in Mx, gc_key says of what.  Allocated at the first cold
     * solve that qualifies (gc_nomem: that failed for this shape, not tried again), freed with the problem. */
@@ -574,7 +619,6 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->clk_on = false; s->clk_buf = NULL; s->clk_n = 0; s->clk_ghz = 0.0; s->clk_stream = NULL;
    s->s1_ws = NULL; s->s1_ws_len = 0; s->s1_host = NULL; s->s1_host_dev = NULL; s->s1_seq = 0; s->s1_last = 0; s->s1_sol_host = false; s->zero_b = false; s->zero_D = false;
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0; s->stage_off = 0; s->stage_pending = false; s->ncmd = 0; s->cmd_ev = NULL; s->cmd_inflight = false; s->m_alloc = 0; s->q_alloc = 0;
-   s->ec_dev = NULL; s->ec_dev_len = 0; s->ec_pin = NULL; s->ec_pin_len = 0; s->ec_tab = NULL; s->ec_tab_len = 0;
    s->trsv_ws = NULL;
    s->a_gen_next = 0; s->gc_M = NULL; s->gc_len = 0; s->gc_nomem = false; s->gc_hits = s->gc_misses = 0;
    hs_gram_key_clear(&s->gc_key);
@@ -654,10 +698,7 @@ extern "C" void hipsdp_free(hipsdp_solver** ps)
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0;
    if ( s->s1_ws != NULL ) (void) hipFree(s->s1_ws);
    s->s1_ws = NULL;
-   if ( s->ec_dev != NULL ) (void) hipFree(s->ec_dev);
-   if ( s->ec_tab != NULL ) (void) hipFree(s->ec_tab);
-   if ( s->ec_pin != NULL ) (void) hipHostFree(s->ec_pin);
-   s->ec_dev = NULL; s->ec_tab = NULL; s->ec_pin = NULL;
+   s->cw.release();
    if ( s->clk_buf != NULL ) (void) hipFree(s->clk_buf);
    s->clk_buf = NULL;
    if ( s->clk_stream != NULL ) (void) hipStreamDestroy(s->clk_stream);
@@ -4960,6 +5001,41 @@ extern "C" int hipsdp_sync_flag(hipsdp_solver* s, int* flag)
    return rc;
 }
 
+/* a point y of the host for the passes over A: y in s->ys, (-1, y) in s->dyt, the packed triangles and the device form of the blocks
+ * kept as nonzeros up to date */
+static int point_to_device(hipsdp_solver* s, const double* y)
+{
+   if ( s->m > 0 )
+      HS_HIP( hipMemcpyAsync(s->ys, y, (size_t) s->m * sizeof(double), hipMemcpyHostToDevice, s->stream) );
+   HS_CALL( hs_make_ext(s->stream, s->m, -1.0, 1.0, s->ys, s->dyt) );
+   HS_LAUNCH_CHECK();
+   HS_CALL( ensure_packed(s) );
+   return HS_OK;
+}
+
+/* The full decomposition of B.W (up to 128 rows: tridiagonal reduction, multisection, inverse iteration in one launch, eigi.hip; block
+ * Jacobi above): its first nlam eigenvalues (ascending) to hlam, one read-back.  Vout (may be NULL): the eigenvectors, rows of an
+ * n x n device array that the caller releases with dfree. */
+static int decompose_W(hipsdp_solver* s, Block& B, int nlam, double* hlam, double** Vout)
+{
+   const int n = B.n;
+   hipStream_t st = s->stream;
+   double *lam = NULL, *V = NULL, *ws = NULL;
+   int rc = dalloc(&lam, n);
+   if ( rc == HS_OK ) rc = dalloc(&V, (long long) n * n);
+   if ( rc == HS_OK ) rc = dalloc(&ws, n <= 128 ? hs_syev_small_scratch(n) : hs_syev_ws(n));
+   if ( rc == HS_OK ) rc = n <= 128 ? hs_syev_small_dev(st, n, B.W, lam, V, ws) : hs_syev_jacobi(st, n, B.W, lam, V, NULL, ws);
+   if ( rc == HS_OK && (hipMemcpyAsync(hlam, lam, (size_t) nlam * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
+         || hipStreamSynchronize(st) != hipSuccess) )
+      rc = HS_ERR_HIP;
+   dfree(lam); dfree(ws);
+   if ( rc == HS_OK && Vout != NULL )
+      *Vout = V;
+   else
+      dfree(V);
+   return rc;
+}
+
 static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* lmin, double* lpviol);
 
 extern "C" int hipsdp_check_y(hipsdp_solver* s, const double* y, double* lmin, double* lpviol)
@@ -4983,13 +5059,9 @@ static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* l
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    CommOff off(s, replicate_small(s));
-   const int m = s->m, m1 = m + 1, q = s->q;
+   const int m1 = s->m + 1, q = s->q;
    hipStream_t st = s->stream;
-   if ( m > 0 )
-      HS_HIP( hipMemcpyAsync(s->ys, y, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_make_ext(st, m, -1.0, 1.0, s->ys, s->dyt) );
-   HS_LAUNCH_CHECK();
-   HS_CALL( ensure_packed(s) );
+   HS_CALL( point_to_device(s, y) );
    int k = 0;
    for (auto& B : s->blk)
    {
@@ -5066,18 +5138,8 @@ static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* l
          lmin[b] = sigma;
          continue;
       }
-      double *lam = NULL, *V = NULL, *ws = NULL;
       double l0 = 0.0;
-      int rc = dalloc(&lam, n);
-      if ( rc == HS_OK ) rc = dalloc(&V, n2);
-      /* (up to 128 rows: tridiagonal reduction, multisection, inverse iteration in one launch, eigi.hip; block Jacobi above) */
-      if ( rc == HS_OK ) rc = dalloc(&ws, n <= 128 ? hs_syev_small_scratch(n) : hs_syev_ws(n));
-      if ( rc == HS_OK ) rc = n <= 128 ? hs_syev_small_dev(st, n, B.W, lam, V, ws) : hs_syev_jacobi(st, n, B.W, lam, V, NULL, ws);
-      if ( rc == HS_OK && (hipMemcpyAsync(&l0, lam, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
-            || hipStreamSynchronize(st) != hipSuccess) )
-         rc = HS_ERR_HIP;
-      dfree(lam); dfree(V); dfree(ws);
-      HS_CALL( rc );
+      HS_CALL( decompose_W(s, B, 1, &l0, NULL) );
       lmin[b] = l0;
    }
    if ( lpviol != NULL )
@@ -5098,24 +5160,8 @@ __global__ void k_outer_row(int n, const double* __restrict__ V, int row, double
  *    sum_i (v^T A_i v) y_i >= v^T A_0 v.
  * Z(y) (one pass over A), its eigen-decomposition (one launch up to 128 rows, block Jacobi above) and the coefficients <A_i, v v^T> (one pass over A per cut) are
  * formed on the device.  The most negative eigenvalues come first; at most maxcuts cuts.
- * eigvals[maxcuts], coefs[maxcuts x m], lhs[maxcuts], vecs[maxcuts x n] (may be NULL) are host arrays. */
-static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
-   double* coefs, double* lhs, double* vecs, double* lam0);
-
-extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
-   double* coefs, double* lhs, double* vecs)
-{
-   if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || y == NULL || maxcuts < 0 || ncuts == NULL )
-      return HIPSDP_ERR_ARG;
-   *ncuts = 0;
-   if ( maxcuts == 0 )
-      return HIPSDP_OK;
-   if ( eigvals == NULL || coefs == NULL || lhs == NULL )
-      return HIPSDP_ERR_ARG;
-   return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, NULL);
-}
-
-/* one block, arguments checked by the caller (maxcuts may be 0: only the decomposition); lam0 (may be NULL): its first eigenvalue */
+ * eigvals[maxcuts], coefs[maxcuts x m], lhs[maxcuts], vecs[maxcuts x n] (may be NULL) are host arrays.
+ * Arguments checked by the caller (maxcuts may be 0: only the decomposition); lam0 (may be NULL): the block's first eigenvalue */
 static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
    double* coefs, double* lhs, double* vecs, double* lam0)
 {
@@ -5127,22 +5173,12 @@ static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double to
    const int n = B.n;
    const long long n2 = (long long) n * n;
    hipStream_t st = s->stream;
-   if ( m > 0 )
-      HS_HIP( hipMemcpyAsync(s->ys, y, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_make_ext(st, m, -1.0, 1.0, s->ys, s->dyt) );
-   HS_LAUNCH_CHECK();
-   HS_CALL( ensure_packed(s) );
+   HS_CALL( point_to_device(s, y) );
    HS_CALL( pass_AT(s, B, s->dyt, 0.0, NULL, B.W) );
-   double *lam = NULL, *V = NULL, *ws = NULL, *out = NULL;
+   double *V = NULL, *out = NULL;
    std::vector<double> hlam(n), hout;
-   int rc = dalloc(&lam, n);
-   if ( rc == HS_OK ) rc = dalloc(&V, n2);
-   if ( rc == HS_OK ) rc = dalloc(&ws, n <= 128 ? hs_syev_small_scratch(n) : hs_syev_ws(n));
-   if ( rc == HS_OK ) rc = dalloc(&out, m1);
-   if ( rc == HS_OK ) rc = n <= 128 ? hs_syev_small_dev(st, n, B.W, lam, V, ws) : hs_syev_jacobi(st, n, B.W, lam, V, NULL, ws);
-   if ( rc == HS_OK && (hipMemcpyAsync(hlam.data(), lam, (size_t) n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
-         || hipStreamSynchronize(st) != hipSuccess) )
-      rc = HS_ERR_HIP;
+   int rc = dalloc(&out, m1);
+   if ( rc == HS_OK ) rc = decompose_W(s, B, n, hlam.data(), &V);
    int k = 0;
    if ( rc == HS_OK )
    {
@@ -5167,7 +5203,7 @@ static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double to
       if ( vecs != NULL && hipMemcpy(vecs + (size_t) c * n, V + (size_t) c * n, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess )
          rc = HS_ERR_HIP;
    }
-   dfree(lam); dfree(V); dfree(ws); dfree(out);
+   dfree(V); dfree(out);
    HS_CALL( rc );
    *ncuts = k;
    if ( lam0 != NULL )
@@ -5175,15 +5211,47 @@ static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double to
    return HIPSDP_OK;
 }
 
+extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
+   double* coefs, double* lhs, double* vecs)
+{
+   if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || y == NULL || maxcuts < 0 || ncuts == NULL )
+      return HIPSDP_ERR_ARG;
+   *ncuts = 0;
+   if ( maxcuts == 0 )
+      return HIPSDP_OK;
+   if ( eigvals == NULL || coefs == NULL || lhs == NULL )
+      return HIPSDP_ERR_ARG;
+   return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, NULL);
+}
+
 /* ---- all blocks in one call (kernels: csrc/eigcuts.hip, many-forms of the decompositions: csrc/eigi.hip) ---------------------- */
-static std::atomic<long long> g_ec_calls(0), g_ec_launches(0), g_ec_readbacks(0);
+/* calls served, and their launches and read-backs: hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts */
+struct CutStats
+{
+   std::atomic<long long> calls{0}, launches{0}, readbacks{0};
+   int get(long long* c, long long* l, long long* r) const
+   {
+      if ( c != NULL ) *c = calls.load();
+      if ( l != NULL ) *l = launches.load();
+      if ( r != NULL ) *r = readbacks.load();
+      return HIPSDP_OK;
+   }
+};
+static CutStats g_ec, g_sc, g_sc1;
 
 extern "C" int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks)
 {
-   if ( calls != NULL ) *calls = g_ec_calls.load();
-   if ( launches != NULL ) *launches = g_ec_launches.load();
-   if ( readbacks != NULL ) *readbacks = g_ec_readbacks.load();
-   return HIPSDP_OK;
+   return g_ec.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_sc.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_sc1.get(calls, launches, readbacks);
 }
 
 /* a block whose round runs in the shared launches: the whole matrices are on this device and k_syev_mid holds the block */
@@ -5192,84 +5260,99 @@ static bool ec_batched(const hipsdp_solver* s, const Block& B)
    return s->comm == NULL && !s->shardA && B.n <= 128 && (B.sparse ? (B.sp != NULL && B.A0 != NULL) : B.A != NULL);
 }
 
-/* The workspace and the job tables of a round over the batched blocks `ids` (ordered by decomposition class): ec_dev holds `front`
- * doubles for the caller (y, its result block) and behind them Z and the decomposition slab of every block, ec_pin `pin` doubles,
- * ec_tab the hs_ec_job of the blocks and behind them their hs_eig_job.  All three only grow; the tables are uploaded when they differ
- * from what the device holds (first use, a new shape, another storage form, a workspace laid out differently). */
-static int ec_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long front, long long pin,
-   int* nmax_out)
+/* the batched blocks, in the order of the decomposition's classes */
+static std::vector<int> ec_batched_ids(const hipsdp_solver* s)
+{
+   std::vector<int> ids;
+   for (int cls = 0; cls < 3; ++cls)
+      for (size_t b = 0; b < s->blk.size(); ++b)
+         if ( ec_batched(s, s->blk[b]) && hs_syev_many_class(s->blk[b].n) == cls )
+            ids.push_back((int) b);
+   return ids;
+}
+
+/* where the vectors of block b start in the result, [nb]: their total length - maxcuts vectors per block, or of block `only` alone */
+static std::vector<long long> cut_vecoff(const hipsdp_solver* s, int maxcuts, int only)
+{
+   const size_t nb = s->blk.size();
+   std::vector<long long> vecoff(nb + 1, 0);
+   for (size_t b = 0; b < nb; ++b)
+      vecoff[b + 1] = vecoff[b] + (only < 0 || (int) b == only ? (long long) maxcuts * s->blk[b].n : 0);
+   return vecoff;
+}
+
+/* Z and the decomposition workspace of every block of a round */
+static long long ec_slab_len(const hipsdp_solver* s, const std::vector<int>& ids)
+{
+   long long len = 0;
+   for (int b : ids)
+      len += hs_cut_mat_len(s->blk[b].n) + hs_syev_small_scratch(s->blk[b].n);
+   return len;
+}
+
+/* the storage form the kernels read the block's matrices in (J zeroed by the caller) */
+static void ec_job_form(const Block& B, hs_ec_job* J)
+{
+   J->n = B.n;
+   J->ld = (long long) B.n * B.n;
+   if ( B.sparse )
+   {
+      J->form = HS_EC_SPARSE; J->A = B.A0;
+      hs_sp_get_view(B.sp, &J->sp);
+   }
+   else if ( B.Apk != NULL && B.apk_valid )
+   {
+      J->form = HS_EC_PACKED; J->A = B.Apk; J->ld = B.Lp;
+   }
+   else
+   {
+      J->form = HS_EC_DENSE; J->A = B.A;
+   }
+}
+
+/* The workspace (lengths of the call's layout, its slabs from offset `slabs` on) and the job tables of a round over the batched blocks
+ * `ids` (ordered by decomposition class); nmax_out: their largest n */
+static int ec_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long slabs,
+   const hs_cut_lens& len, int* nmax_out)
 {
    const int nj = (int) ids.size();
-   long long need = front;
-   int nmax = 0;
-   for (int b : ids)
-   {
-      const int n = s->blk[b].n;
-      need += (((long long) n * n + 1) & ~1LL) + hs_syev_small_scratch(n);
-      nmax = n > nmax ? n : nmax;
-   }
-   if ( need > s->ec_dev_len )
-   {
-      if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
-      s->ec_dev = NULL; s->ec_dev_len = 0;
-      HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
-      s->ec_dev_len = need;
-   }
-   if ( pin > s->ec_pin_len )
-   {
-      if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
-      s->ec_pin = NULL; s->ec_pin_len = 0;
-      HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) pin * sizeof(double), hipHostMallocDefault) );
-      s->ec_pin_len = pin;
-   }
-   const size_t tabbytes = (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job));
-   if ( (long long) tabbytes > s->ec_tab_len )
-   {
-      if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
-      s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
-      HS_HIP( hipMalloc((void**) &s->ec_tab, tabbytes) );
-      s->ec_tab_len = (long long) tabbytes;
-   }
-   double* cur = s->ec_dev + front;
+   HS_CALL( s->cw.grow(len.dev_len, len.pin_len, (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job))) );
+   double* cur = s->cw.dev + slabs;
    std::vector<hs_ec_job> jobs((size_t) nj);
    std::vector<hs_eig_job> ejobs((size_t) nj);
+   int nmax = 0;
    for (int j = 0; j < nj; ++j)
    {
       const Block& B = s->blk[ids[j]];
       hs_ec_job& J = jobs[j];
       memset(&J, 0, sizeof(J));
       memset(&ejobs[j], 0, sizeof(hs_eig_job));
-      J.n = B.n; J.blk = ids[j];
-      J.ld = (long long) B.n * B.n;
-      if ( B.sparse )
-      {
-         J.form = HS_EC_SPARSE; J.A = B.A0;
-         hs_sp_get_view(B.sp, &J.sp);
-      }
-      else if ( B.Apk != NULL && B.apk_valid )
-      {
-         J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
-      }
-      else
-      {
-         J.form = HS_EC_DENSE; J.A = B.A;
-      }
-      J.Z = cur; cur += ((long long) B.n * B.n + 1) & ~1LL;
+      ec_job_form(B, &J);
+      J.blk = ids[j];
+      J.Z = cur; cur += hs_cut_mat_len(B.n);
       J.ws = cur; cur += hs_syev_small_scratch(B.n);
       J.vpos = hs_syev_many_vecpos(B.n);
       J.vecoff = vecoff[ids[j]];
       ejobs[j].n = B.n; ejobs[j].in = J.Z; ejobs[j].ws = J.ws;
+      nmax = B.n > nmax ? B.n : nmax;
    }
-   hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
-   hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
-   if ( s->ec_jobs.size() != jobs.size() || memcmp(s->ec_jobs.data(), jobs.data(), jobs.size() * sizeof(hs_ec_job)) != 0 )
-   {
-      HS_HIP( hipMemcpy(djobs, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
-      HS_HIP( hipMemcpy(dejobs, ejobs.data(), ejobs.size() * sizeof(hs_eig_job), hipMemcpyHostToDevice) );
-      s->ec_jobs = jobs; s->ec_ejobs = ejobs;
-   }
+   HS_CALL( s->cw.upload(jobs, ejobs) );
    *nmax_out = nmax;
    return HS_OK;
+}
+
+/* the k cuts of one block of n rows - first slot `slot`, vectors from `voff` on - from a host view to the caller's arrays (vecs may be NULL) */
+static void cut_copy_out(const hs_sc_out& h, size_t slot, long long voff, int k, int m, int n, double* eigvals, double* lhs, double* coefs,
+   double* vecs)
+{
+   if ( k <= 0 )
+      return;
+   memcpy(eigvals, h.eig + slot, (size_t) k * sizeof(double));
+   memcpy(lhs, h.lhs + slot, (size_t) k * sizeof(double));
+   if ( m > 0 )
+      memcpy(coefs, h.coef + slot * m, (size_t) k * m * sizeof(double));
+   if ( vecs != NULL )
+      memcpy(vecs, h.vec + voff, (size_t) k * n * sizeof(double));
 }
 
 extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
@@ -5286,70 +5369,52 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
    HS_CALL( stage_sync(s) );
    HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
    hipStream_t st = s->stream;
-   std::vector<long long> vecoff((size_t) nb + 1, 0);
-   for (int b = 0; b < nb; ++b)
-      vecoff[b + 1] = vecoff[b] + (long long) maxcuts * s->blk[b].n;
-   /* the batched blocks, in the order of the decomposition's classes */
-   std::vector<int> ids;
-   for (int cls = 0; cls < 3; ++cls)
-      for (int b = 0; b < nb; ++b)
-         if ( ec_batched(s, s->blk[b]) && hs_syev_many_class(s->blk[b].n) == cls )
-            ids.push_back(b);
+   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, -1);
+   const std::vector<int> ids = ec_batched_ids(s);
    const int nj = (int) ids.size();
+   std::vector<char> served((size_t) nb, 0);
    if ( nj > 0 )
    {
-      const long long ylen = (m + 2) & ~1LL;
-      const long long reslen = 2LL * nb + 2LL * nb * maxcuts + (long long) nb * maxcuts * m + vecoff[nb];
+      hs_ec_layout L;
+      hs_ec_layout_make(nb, m, maxcuts, vecoff[nb], ec_slab_len(s, ids), &L);
       int nmax = 0;
-      HS_CALL( ec_prepare(s, ids, vecoff, ylen + reslen, ylen + reslen, &nmax) );
-      double* dy = s->ec_dev;
-      double* dres = dy + ylen;
-      hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
-      hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
+      HS_CALL( ec_prepare(s, ids, vecoff, L.slabs, L.len, &nmax) );
+      CutWs& cw = s->cw;
+      double* dy = cw.dev + L.y;
       int launches = 0;
       if ( m > 0 )
       {
-         memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
-         HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
+         memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
+         HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
       }
-      HS_CALL( hs_ec_form_z(st, nj, nmax, m, djobs, dy) );
+      HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
       ++launches;
-      HS_CALL( hs_syev_small_many(st, nj, s->ec_ejobs.data(), dejobs, &launches) );
-      HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, djobs, dres) );
+      HS_CALL( hs_syev_small_many(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
+      HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, cw.djobs(), cw.dev + L.len.res_off) );
       ++launches;
-      double* hres = s->ec_pin + ylen;
-      HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
+            st) );
       HS_HIP( hipStreamSynchronize(st) );
-      g_ec_launches += launches;
-      g_ec_readbacks += 1;
-      const double* h_eig = hres + 2LL * nb;
-      const double* h_lhs = h_eig + (long long) nb * maxcuts;
-      const double* h_coef = h_lhs + (long long) nb * maxcuts;
-      const double* h_vec = h_coef + (long long) nb * maxcuts * m;
+      g_ec.launches += launches;
+      g_ec.readbacks += 1;
+      const hs_sc_out h = hs_cut_view(L.r, cw.pin);
       for (int b : ids)
       {
-         const int k = (int) hres[b];
+         const int k = (int) cw.pin[L.ncuts + b];
          if ( k < 0 || k > maxcuts || k > s->blk[b].n )
             return HIPSDP_ERR_NUMERIC;
          ncuts[b] = k;
-         if ( lmin != NULL )
-            lmin[b] = hres[nb + b];
+         served[b] = 1;
+         if ( lmin != NULL ) lmin[b] = h.lmin[b];
          const size_t slot = (size_t) b * maxcuts;
-         if ( k > 0 )
-         {
-            memcpy(eigvals + slot, h_eig + slot, (size_t) k * sizeof(double));
-            memcpy(lhs + slot, h_lhs + slot, (size_t) k * sizeof(double));
-            if ( m > 0 )
-               memcpy(coefs + slot * m, h_coef + slot * m, (size_t) k * m * sizeof(double));
-            if ( vecs != NULL )
-               memcpy(vecs + vecoff[b], h_vec + vecoff[b], (size_t) k * s->blk[b].n * sizeof(double));
-         }
+         cut_copy_out(h, slot, vecoff[b], k, m, s->blk[b].n, eigvals + slot, lhs + slot, coefs + slot * m,
+            vecs != NULL ? vecs + vecoff[b] : NULL);
       }
    }
    /* every other block: the per-block path, inside the same call */
    for (int b = 0; b < nb; ++b)
    {
-      if ( std::find(ids.begin(), ids.end(), b) != ids.end() )
+      if ( served[b] )
          continue;
       const size_t slot = (size_t) b * maxcuts;
       double l0 = 0.0;
@@ -5358,19 +5423,64 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
       if ( lmin != NULL )
          lmin[b] = l0;
    }
-   ++g_ec_calls;
+   ++g_ec.calls;
    return HIPSDP_OK;
 }
 
 /* ---- sparse eigenvector cuts of all blocks in one call (kernels: csrc/sparsecuts.hip) ------------------------------------------- */
-static std::atomic<long long> g_sc_calls(0), g_sc_launches(0), g_sc_readbacks(0);
-
-extern "C" int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+static void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
 {
-   if ( calls != NULL ) *calls = g_sc_calls.load();
-   if ( launches != NULL ) *launches = g_sc_launches.load();
-   if ( readbacks != NULL ) *readbacks = g_sc_readbacks.load();
-   return HIPSDP_OK;
+   par->tol = opts->tol; par->feastol = opts->feastol;
+   par->convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+   par->maxcuts = opts->maxcuts;
+   par->maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+}
+
+/* The round of the served blocks `ids` (ordered by decomposition class; sizes[nb]: the target sparsity of every block of the solver):
+ * Z(y), the decompositions, TPower and, with maxcuts > 0, the coefficients, then ONE read-back.  The result block is indexed by the
+ * block's number whatever `ids` holds, so a round over one block computes that block's bits of the round over all.  h: the view of the
+ * read-back in the pinned buffer. */
+static int sc_round(hipsdp_solver* s, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   const std::vector<long long>& vecoff, CutStats* stats, hs_sc_out* h)
+{
+   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, nj = (int) ids.size();
+   hipStream_t st = s->stream;
+   /* the largest support a served block can have: the pitch of the support lists */
+   int smax = 1;
+   for (int b : ids)
+      if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
+         smax = sizes[b];
+   hs_sc_layout L;
+   hs_sc_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), &L);
+   int nmax = 0;
+   HS_CALL( ec_prepare(s, ids, vecoff, L.slabs, L.len, &nmax) );
+   CutWs& cw = s->cw;
+   double* dy = cw.dev + L.y;
+   const int* dsizes = reinterpret_cast<const int*>(cw.dev + L.sizes);
+   const hs_sc_out out = hs_cut_view(L.r, cw.dev);
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   int launches = 0;
+   if ( m > 0 )
+      memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
+   memcpy(cw.pin + L.sizes, sizes, (size_t) nb * sizeof(int));
+   HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
+   ++launches;
+   HS_CALL( hs_syev_small_many(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
+   HS_CALL( hs_sc_tpower(st, nj, nmax, cw.djobs(), dsizes, &par, &out) );
+   ++launches;
+   if ( maxcuts > 0 )
+   {
+      HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, cw.djobs(), dsizes, &out) );
+      ++launches;
+   }
+   HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   stats->launches += launches;
+   stats->readbacks += 1;
+   *h = hs_cut_view(L.r, cw.pin);
+   return HS_OK;
 }
 
 extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
@@ -5390,206 +5500,49 @@ extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const in
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
-   hipStream_t st = s->stream;
-   std::vector<long long> vecoff((size_t) nb + 1, 0);
-   for (int b = 0; b < nb; ++b)
-      vecoff[b + 1] = vecoff[b] + (long long) maxcuts * s->blk[b].n;
-   /* the served blocks, in the order of the decomposition's classes */
-   std::vector<int> ids;
-   for (int cls = 0; cls < 3; ++cls)
-      for (int b = 0; b < nb; ++b)
-         if ( ec_batched(s, s->blk[b]) && hs_syev_many_class(s->blk[b].n) == cls )
-            ids.push_back(b);
-   const int nj = (int) ids.size();
-   if ( nj > 0 )
+   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, -1);
+   const std::vector<int> ids = ec_batched_ids(s);
+   if ( !ids.empty() )
    {
-      /* the largest support a served block can have: the pitch of the support lists */
-      int smax = 1;
-      for (int b : ids)
-         if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
-            smax = sizes[b];
-      /* uploaded: y | sizes (int);  read back: lmin | eigvals | lhs | coefs | vecs | ncuts, iters, flags (int);  device only: supports (int) */
-      const long long ylen = (m + 2) & ~1LL, szlen = ((long long) nb + 1) / 2;
-      const long long slots = (long long) nb * maxcuts;
-      const long long reslen = nb + 2 * slots + slots * m + vecoff[nb] + (3LL * nb + 1) / 2;
-      const long long suplen = (slots * smax + 1) / 2;
-      int nmax = 0;
-      HS_CALL( ec_prepare(s, ids, vecoff, ylen + szlen + reslen + suplen, ylen + szlen + reslen, &nmax) );
-      double* dy = s->ec_dev;
-      int* dsizes = reinterpret_cast<int*>(dy + ylen);
-      double* dres = dy + ylen + szlen;
-      hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
-      hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + (size_t) nj * sizeof(hs_ec_job));
-      hs_sc_out out;
-      memset(&out, 0, sizeof(out));
-      out.lmin = dres;
-      out.eig = out.lmin + nb;
-      out.lhs = out.eig + slots;
-      out.coef = out.lhs + slots;
-      out.vec = out.coef + slots * m;
-      out.ncuts = reinterpret_cast<int*>(out.vec + vecoff[nb]);
-      out.iters = out.ncuts + nb;
-      out.flags = out.iters + nb;
-      out.sup = reinterpret_cast<int*>(dres + reslen);
-      out.smax = smax;
-      hs_sc_par par;
-      par.tol = opts->tol; par.feastol = opts->feastol;
-      par.convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
-      par.maxcuts = maxcuts;
-      par.maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
-      int launches = 0;
-      if ( m > 0 )
-         memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
-      memcpy(s->ec_pin + ylen, sizes, (size_t) nb * sizeof(int));
-      HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) (ylen + szlen) * sizeof(double), hipMemcpyHostToDevice, st) );
-      HS_CALL( hs_ec_form_z(st, nj, nmax, m, djobs, dy) );
-      ++launches;
-      HS_CALL( hs_syev_small_many(st, nj, s->ec_ejobs.data(), dejobs, &launches) );
-      HS_CALL( hs_sc_tpower(st, nj, nmax, djobs, dsizes, &par, &out) );
-      ++launches;
-      if ( maxcuts > 0 )
-      {
-         HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, djobs, dsizes, &out) );
-         ++launches;
-      }
-      double* hres = s->ec_pin + ylen + szlen;
-      HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
-      HS_HIP( hipStreamSynchronize(st) );
-      g_sc_launches += launches;
-      g_sc_readbacks += 1;
-      const double* h_eig = hres + nb;
-      const double* h_lhs = h_eig + slots;
-      const double* h_coef = h_lhs + slots;
-      const double* h_vec = h_coef + slots * m;
-      const int* h_ncuts = reinterpret_cast<const int*>(h_vec + vecoff[nb]);
+      hs_sc_out h;
+      HS_CALL( sc_round(s, ids, y, sizes, opts, vecoff, &g_sc, &h) );
       for (int b : ids)
       {
-         const int k = h_ncuts[b];
+         const int k = h.ncuts[b];
          if ( k < 0 || k > maxcuts )
             return HIPSDP_ERR_NUMERIC;
          ncuts[b] = k;
-         if ( lmin != NULL )
-            lmin[b] = hres[b];
-         if ( iters != NULL )
-            iters[b] = h_ncuts[nb + b];
-         if ( flags != NULL )
-            flags[b] = h_ncuts[2 * nb + b];
+         if ( lmin != NULL ) lmin[b] = h.lmin[b];
+         if ( iters != NULL ) iters[b] = h.iters[b];
+         if ( flags != NULL ) flags[b] = h.flags[b];
          const size_t slot = (size_t) b * maxcuts;
-         if ( k > 0 )
-         {
-            memcpy(eigvals + slot, h_eig + slot, (size_t) k * sizeof(double));
-            memcpy(lhs + slot, h_lhs + slot, (size_t) k * sizeof(double));
-            if ( m > 0 )
-               memcpy(coefs + slot * m, h_coef + slot * m, (size_t) k * m * sizeof(double));
-            if ( vecs != NULL )
-               memcpy(vecs + vecoff[b], h_vec + vecoff[b], (size_t) k * s->blk[b].n * sizeof(double));
-         }
+         cut_copy_out(h, slot, vecoff[b], k, m, s->blk[b].n, eigvals + slot, lhs + slot, coefs + slot * m,
+            vecs != NULL ? vecs + vecoff[b] : NULL);
       }
    }
-   ++g_sc_calls;
+   ++g_sc.calls;
    return HIPSDP_OK;
 }
 
 /* ---- sparse eigenvector cuts of ONE block of up to 512 rows (kernels: csrc/sparsecuts.hip, csrc/sparsecuts_large.hip) ---------- */
-static std::atomic<long long> g_sc1_calls(0), g_sc1_launches(0), g_sc1_readbacks(0);
-
-extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks)
-{
-   if ( calls != NULL ) *calls = g_sc1_calls.load();
-   if ( launches != NULL ) *launches = g_sc1_launches.load();
-   if ( readbacks != NULL ) *readbacks = g_sc1_readbacks.load();
-   return HIPSDP_OK;
-}
-
-static void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
-{
-   par->tol = opts->tol; par->feastol = opts->feastol;
-   par->convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
-   par->maxcuts = opts->maxcuts;
-   par->maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
-}
-
-/* a block of at most 128 rows: the launches of hipsdp_sparsecuts_all with this block as the only job.  The result block keeps that
- * call's layout (indexed by the block's number), so the kernels and what they compute are the same to the bit. */
+/* a block of at most 128 rows: the round of hipsdp_sparsecuts_all with this block as the only job, the same bits */
 static int sparsecuts_small(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
    double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
 {
-   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, n = s->blk[block].n;
-   hipStream_t st = s->stream;
-   std::vector<long long> vecoff((size_t) nb + 1, 0);
-   for (int b = block + 1; b <= nb; ++b)
-      vecoff[b] = (long long) maxcuts * n;                 /* only this block has vectors */
-   const std::vector<int> ids(1, block);
-   const int smax = size <= n ? size : 1;
-   const long long ylen = (m + 2) & ~1LL, szlen = ((long long) nb + 1) / 2;
-   const long long slots = (long long) nb * maxcuts;
-   const long long reslen = nb + 2 * slots + slots * m + vecoff[nb] + (3LL * nb + 1) / 2;
-   const long long suplen = (slots * smax + 1) / 2;
-   int nmax = 0;
-   HS_CALL( ec_prepare(s, ids, vecoff, ylen + szlen + reslen + suplen, ylen + szlen + reslen, &nmax) );
-   double* dy = s->ec_dev;
-   int* dsizes = reinterpret_cast<int*>(dy + ylen);
-   double* dres = dy + ylen + szlen;
-   hs_ec_job* djobs = reinterpret_cast<hs_ec_job*>(s->ec_tab);
-   hs_eig_job* dejobs = reinterpret_cast<hs_eig_job*>(s->ec_tab + sizeof(hs_ec_job));
-   hs_sc_out out;
-   memset(&out, 0, sizeof(out));
-   out.lmin = dres;
-   out.eig = out.lmin + nb;
-   out.lhs = out.eig + slots;
-   out.coef = out.lhs + slots;
-   out.vec = out.coef + slots * m;
-   out.ncuts = reinterpret_cast<int*>(out.vec + vecoff[nb]);
-   out.iters = out.ncuts + nb;
-   out.flags = out.iters + nb;
-   out.sup = reinterpret_cast<int*>(dres + reslen);
-   out.smax = smax;
-   hs_sc_par par;
-   sc_par_from_opts(opts, &par);
-   int launches = 0;
-   if ( m > 0 )
-      memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
-   int* hsizes = reinterpret_cast<int*>(s->ec_pin + ylen);
-   for (int b = 0; b < nb; ++b)
-      hsizes[b] = b == block ? size : 1;
-   HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) (ylen + szlen) * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_ec_form_z(st, 1, nmax, m, djobs, dy) );
-   ++launches;
-   HS_CALL( hs_syev_small_many(st, 1, s->ec_ejobs.data(), dejobs, &launches) );
-   HS_CALL( hs_sc_tpower(st, 1, nmax, djobs, dsizes, &par, &out) );
-   ++launches;
-   if ( maxcuts > 0 )
-   {
-      HS_CALL( hs_sc_coefs(st, 1, m, maxcuts, djobs, dsizes, &out) );
-      ++launches;
-   }
-   double* hres = s->ec_pin + ylen + szlen;
-   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_sc1_launches += launches;
-   g_sc1_readbacks += 1;
-   const double* h_eig = hres + nb;
-   const double* h_lhs = h_eig + slots;
-   const double* h_coef = h_lhs + slots;
-   const double* h_vec = h_coef + slots * m;
-   const int* h_ncuts = reinterpret_cast<const int*>(h_vec + vecoff[nb]);
-   const int k = h_ncuts[block];
+   const int maxcuts = opts->maxcuts;
+   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, block);      /* only this block has vectors */
+   std::vector<int> sizes(s->blk.size(), 1);
+   sizes[block] = size;
+   hs_sc_out h;
+   HS_CALL( sc_round(s, std::vector<int>(1, block), y, sizes.data(), opts, vecoff, &g_sc1, &h) );
+   const int k = h.ncuts[block];
    if ( k < 0 || k > maxcuts )
       return HIPSDP_ERR_NUMERIC;
    *ncuts = k;
-   if ( lmin != NULL ) *lmin = hres[block];
-   if ( iters != NULL ) *iters = h_ncuts[nb + block];
-   if ( flags != NULL ) *flags = h_ncuts[2 * nb + block];
-   const size_t slot = (size_t) block * maxcuts;
-   if ( k > 0 )
-   {
-      memcpy(eigvals, h_eig + slot, (size_t) k * sizeof(double));
-      memcpy(lhs, h_lhs + slot, (size_t) k * sizeof(double));
-      if ( m > 0 )
-         memcpy(coefs, h_coef + slot * m, (size_t) k * m * sizeof(double));
-      if ( vecs != NULL )
-         memcpy(vecs, h_vec + vecoff[block], (size_t) k * n * sizeof(double));
-   }
+   if ( lmin != NULL ) *lmin = h.lmin[block];
+   if ( iters != NULL ) *iters = h.iters[block];
+   if ( flags != NULL ) *flags = h.flags[block];
+   cut_copy_out(h, (size_t) block * maxcuts, vecoff[block], k, s->m, s->blk[block].n, eigvals, lhs, coefs, vecs);
    return HIPSDP_OK;
 }
 
@@ -5601,140 +5554,69 @@ static int sparsecuts_large(hipsdp_solver* s, int block, const double* y, int si
    const Block& B = s->blk[block];
    const int m = s->m, maxcuts = opts->maxcuts, n = B.n;
    hipStream_t st = s->stream;
-   const int smax = size <= n ? size : 1;
-   /* uploaded: y;  read back: lmin | eigvals | lhs | coefs | vecs | ncuts, iters, flags (int);  device only: supports (int), Z, the
-    * workspace of the tridiagonal form, the two requests' results, MT */
-   const long long ylen = (m + 2) & ~1LL, slots = maxcuts;
-   const long long reslen = (1 + 2 * slots + slots * m + slots * n + 2 + 1) & ~1LL;
-   const long long suplen = (slots * smax + 1) / 2;
-   const long long n2 = ((long long) n * n + 1) & ~1LL, wslen = ((long long) hs_syevx_ws(n) + 1) & ~1LL;
-   const long long o1len = (HS_SYEVX_OUT(n) + 1) & ~1LL, o2len = HS_SYEVX_OUT_VEC;
-   const long long need = ylen + reslen + suplen + n2 + wslen + o1len + o2len + n2;
-   const long long pin = ylen + (reslen > o2len ? reslen : o2len);
-   if ( need > s->ec_dev_len )
-   {
-      if ( s->ec_dev != NULL ) HS_HIP( hipFree(s->ec_dev) );
-      s->ec_dev = NULL; s->ec_dev_len = 0;
-      HS_HIP( hipMalloc((void**) &s->ec_dev, (size_t) need * sizeof(double)) );
-      s->ec_dev_len = need;
-   }
-   if ( pin > s->ec_pin_len )
-   {
-      if ( s->ec_pin != NULL ) HS_HIP( hipHostFree(s->ec_pin) );
-      s->ec_pin = NULL; s->ec_pin_len = 0;
-      HS_HIP( hipHostMalloc((void**) &s->ec_pin, (size_t) pin * sizeof(double), hipHostMallocDefault) );
-      s->ec_pin_len = pin;
-   }
-   if ( (long long) sizeof(hs_ec_job) > s->ec_tab_len )
-   {
-      if ( s->ec_tab != NULL ) HS_HIP( hipFree(s->ec_tab) );
-      s->ec_tab = NULL; s->ec_tab_len = 0; s->ec_jobs.clear(); s->ec_ejobs.clear();
-      HS_HIP( hipMalloc((void**) &s->ec_tab, sizeof(hs_ec_job)) );
-      s->ec_tab_len = (long long) sizeof(hs_ec_job);
-   }
-   double* dy = s->ec_dev;
-   double* dres = dy + ylen;
-   double* dZ = dres + reslen + suplen;
-   double* dws = dZ + n2;
-   double* o1 = dws + wslen;
-   double* o2 = o1 + o1len;
-   double* dMT = o2 + o2len;
-   hs_ec_job J;
+   hs_scl_layout L;
+   hs_scl_layout_make(n, m, maxcuts, size <= n ? size : 1, (long long) hs_syevx_ws(n), HS_SYEVX_OUT(n), HS_SYEVX_OUT_VEC, &L);
+   CutWs& cw = s->cw;
+   HS_CALL( cw.grow(L.len.dev_len, L.len.pin_len, sizeof(hs_ec_job)) );
+   double *dy = cw.dev + L.y, *dZ = cw.dev + L.Z, *dws = cw.dev + L.ws, *o1 = cw.dev + L.o1, *o2 = cw.dev + L.o2;
+   std::vector<hs_ec_job> job(1);
+   hs_ec_job& J = job[0];
    memset(&J, 0, sizeof(J));
-   J.n = n; J.blk = 0;
-   J.ld = (long long) n * n;
-   if ( B.sparse )
-   {
-      J.form = HS_EC_SPARSE; J.A = B.A0;
-      hs_sp_get_view(B.sp, &J.sp);
-   }
-   else if ( B.Apk != NULL && B.apk_valid )
-   {
-      J.form = HS_EC_PACKED; J.A = B.Apk; J.ld = B.Lp;
-   }
-   else
-   {
-      J.form = HS_EC_DENSE; J.A = B.A;
-   }
+   ec_job_form(B, &J);
    J.Z = dZ; J.ws = dws;
-   hs_ec_job* djob = reinterpret_cast<hs_ec_job*>(s->ec_tab);
-   if ( s->ec_jobs.size() != 1 || memcmp(s->ec_jobs.data(), &J, sizeof(hs_ec_job)) != 0 )
-   {
-      HS_HIP( hipMemcpy(djob, &J, sizeof(hs_ec_job), hipMemcpyHostToDevice) );
-      s->ec_jobs.assign(1, J); s->ec_ejobs.clear();
-   }
-   hs_sc_out out;
-   memset(&out, 0, sizeof(out));
-   out.lmin = dres;
-   out.eig = out.lmin + 1;
-   out.lhs = out.eig + slots;
-   out.coef = out.lhs + slots;
-   out.vec = out.coef + slots * m;
-   out.ncuts = reinterpret_cast<int*>(out.vec + slots * n);
-   out.iters = out.ncuts + 1;
-   out.flags = out.iters + 1;
-   out.sup = reinterpret_cast<int*>(dres + reslen);
-   out.smax = smax;
+   HS_CALL( cw.upload(job, std::vector<hs_eig_job>()) );
+   const hs_sc_out out = hs_cut_view(L.r, cw.dev);
    hs_sc_par par;
    sc_par_from_opts(opts, &par);
    int launches = 0;
    if ( m > 0 )
    {
-      memcpy(s->ec_pin, y, (size_t) m * sizeof(double));
-      HS_HIP( hipMemcpyAsync(dy, s->ec_pin, (size_t) m * sizeof(double), hipMemcpyHostToDevice, st) );
+      memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
+      HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
    }
-   HS_CALL( hs_ec_form_z(st, 1, n, m, djob, dy) );
+   HS_CALL( hs_ec_form_z(st, 1, n, m, cw.djobs(), dy) );
    ++launches;
    HS_CALL( hs_syevx_tridiag_dev(st, n, dZ, dws) );
    launches += n;
-   double* hres = s->ec_pin + ylen;
+   /* the one read-back: the result block, or with maxcuts = 0 the head of the first request's output (its eigenvalue) */
+   double* hres = cw.pin + L.len.res_off;
+   const double* dres = cw.dev + L.len.res_off;
+   long long reslen = L.len.res_len;
    if ( maxcuts == 0 )
    {
       HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, o1, dws) );
       ++launches;
-      HS_HIP( hipMemcpyAsync(hres, o1, (size_t) o2len * sizeof(double), hipMemcpyDeviceToHost, st) );
-      HS_HIP( hipStreamSynchronize(st) );
-      g_sc1_launches += launches;
-      g_sc1_readbacks += 1;
+      dres = o1; reslen = HS_SYEVX_OUT_VEC;
+   }
+   else
+   {
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
+      HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, cw.dev + L.MT, &par, &out) );
+      HS_CALL( hs_scl_coefs(st, m, maxcuts, size, cw.djobs(), &out) );
+      launches += 3 + 1 + 1 + 1;
+   }
+   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_sc1.launches += launches;
+   g_sc1.readbacks += 1;
+   if ( maxcuts == 0 )
+   {
       *ncuts = 0;
       if ( lmin != NULL ) *lmin = hres[HS_SYEVX_OUT_LAM];
       if ( iters != NULL ) *iters = 0;
       if ( flags != NULL ) *flags = 0;
       return HIPSDP_OK;
    }
-   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
-   launches += 3;
-   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
-   ++launches;
-   HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, dMT, &par, &out) );
-   ++launches;
-   HS_CALL( hs_scl_coefs(st, m, maxcuts, size, djob, &out) );
-   ++launches;
-   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_sc1_launches += launches;
-   g_sc1_readbacks += 1;
-   const double* h_eig = hres + 1;
-   const double* h_lhs = h_eig + slots;
-   const double* h_coef = h_lhs + slots;
-   const double* h_vec = h_coef + slots * m;
-   const int* h_int = reinterpret_cast<const int*>(h_vec + slots * n);
-   const int k = h_int[0];
+   const hs_sc_out h = hs_cut_view(L.r, cw.pin);
+   const int k = h.ncuts[0];
    if ( k < 0 || k > maxcuts )
       return HIPSDP_ERR_NUMERIC;
    *ncuts = k;
-   if ( lmin != NULL ) *lmin = hres[0];
-   if ( iters != NULL ) *iters = h_int[1];
-   if ( flags != NULL ) *flags = h_int[2];
-   if ( k > 0 )
-   {
-      memcpy(eigvals, h_eig, (size_t) k * sizeof(double));
-      memcpy(lhs, h_lhs, (size_t) k * sizeof(double));
-      if ( m > 0 )
-         memcpy(coefs, h_coef, (size_t) k * m * sizeof(double));
-      if ( vecs != NULL )
-         memcpy(vecs, h_vec, (size_t) k * n * sizeof(double));
-   }
+   if ( lmin != NULL ) *lmin = h.lmin[0];
+   if ( iters != NULL ) *iters = h.iters[0];
+   if ( flags != NULL ) *flags = h.flags[0];
+   cut_copy_out(h, 0, 0, k, m, n, eigvals, lhs, coefs, vecs);
    return HIPSDP_OK;
 }
 
@@ -5760,7 +5642,7 @@ extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, i
       HS_CALL( sparsecuts_small(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
    else
       HS_CALL( sparsecuts_large(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
-   ++g_sc1_calls;
+   ++g_sc1.calls;
    return HIPSDP_OK;
 }
 

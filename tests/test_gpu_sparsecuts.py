@@ -3,7 +3,8 @@ up to 512 rows - against the numpy restatement tests/harness/sparsecuts_ref.py o
 sparsecuts_large_cases.py, for the properties that need no oracle, in the storage forms of a block, for blocks of at most 128 rows
 against hipsdp_sparsecuts_all, and for what makes it one call: n + 7 launches and one read-back whatever the cuts and iterations.
 k_sc_tpower_large alone (hipsdp_sparsecuts_large_unit) runs on the matrices of the table and on hand-made ones: exact ties, the
-iteration cap, a zero iterate, the extreme sizes.
+iteration cap, a zero iterate, the extreme sizes.  A last test alternates all cut calls on ONE solver - they share a grow-only workspace
+and the cached job tables - and compares every call with the same call on a fresh solver, bit for bit.
 
 The truncated power method takes data-dependent decisions; counts, supports and iteration numbers are compared only after the
 restatement has shown that none of its decisions was close (sparsecuts_large_cases.reference asserts: selection gap >= 1e-9
@@ -441,3 +442,70 @@ def test_an_oversized_target_and_a_quiet_block_give_no_cut_and_the_right_lmin(gp
     s.close()
     assert (nc, iters, flags) == (0, 0, 0)
     assert abs(lmin - rq[1]) <= 1e-9 * max(1.0, abs(rq[1]))
+
+
+# ---- 8. one workspace and one set of job tables behind all cut calls ----------------------------------------------------------------
+
+def _mixed_solver(gpu, blocks, b):
+    """blocks 0 and 2 dense, block 1 handed over as lower-triangular triplets with a count and kept as nonzeros"""
+    m = len(b)
+    s = gpu.Solver(0)
+    s.sparse_policy(2)
+    il = np.tril_indices(blocks[1].shape[1])
+    var = np.repeat(np.arange(m + 1, dtype=np.int32), len(il[0]))
+    row = np.tile(il[0].astype(np.int32), m + 1)
+    col = np.tile(il[1].astype(np.int32), m + 1)
+    val = np.concatenate([blocks[1][i][il] for i in range(m + 1)])
+    keep = val != 0.0
+    s.set_shape(m, [A.shape[1] for A in blocks], 0, nnz=[-1, int(keep.sum()), -1])
+    s.set_obj(b)
+    s.set_block_dense(0, blocks[0])
+    s.add_entries(1, var[keep], row[keep], col[keep], val[keep])
+    s.set_block_dense(2, blocks[2])
+    assert [s.is_sparse(k) for k in range(3)] == [False, True, False]
+    return s
+
+
+def _bits(x):
+    """a result of any of the cut calls (nested tuples and lists of numbers and arrays) as bytes: equal bytes, equal bits (nan included)"""
+    if isinstance(x, (list, tuple)):
+        return b"(" + b"|".join(_bits(v) for v in x) + b")"
+    a = np.asarray(x)
+    return str((a.dtype, a.shape)).encode() + a.tobytes()
+
+
+def test_call_forms_sharing_one_workspace_reproduce_a_fresh_solver(gpu):
+    """Blocks of 5, 40 (kept as nonzeros) and 130 rows, m = 6.  The cut calls of one solver share a grow-only workspace and the job
+    tables cached on the device; every call form lays the workspace out differently and needs other tables.  A sequence that makes the
+    workspace grow between calls and the cached tables go stale across call forms must return, call by call, the bits of the same
+    call made first on a freshly created solver with the same data."""
+    m, ns = 6, (5, 40, 130)
+    blocks, ys, b = [], None, np.zeros(m)
+    for k, n in enumerate(ns):
+        _, A, ysk, Xs, Zs = instances.planted_dense(n, m, seed=41900 + 1000 * k)
+        ys = ysk if k == 0 else ys
+        blocks.append(L.rebuilt(A, ys, Zs))
+        b += blocks[-1][1:].reshape(m, -1) @ Xs.reshape(-1)
+    y = ys + 2.0 * np.random.default_rng(419).standard_normal(m)
+    sizes = [3, 8, 10]
+    steps = [("eigencuts_all, 2 cuts", lambda s: s.eigencuts_all(y, TOL, 2)),
+             ("sparsecuts, 130 rows", lambda s: s.sparsecuts(2, y, 10, TOL, FEASTOL, MAXCUTS)),
+             ("sparsecuts_all", lambda s: s.sparsecuts_all(y, sizes, TOL, FEASTOL, MAXCUTS)),
+             ("sparsecuts, 5 rows", lambda s: s.sparsecuts(0, y, 3, TOL, FEASTOL, MAXCUTS)),
+             ("eigencuts_all, 5 cuts", lambda s: s.eigencuts_all(y, TOL, MAXCUTS)),
+             ("sparsecuts, 130 rows, no cuts", lambda s: s.sparsecuts(2, y, 10, TOL, FEASTOL, 0)),
+             ("sparsecuts_all again", lambda s: s.sparsecuts_all(y, sizes, TOL, FEASTOL, MAXCUTS))]
+    shared = _mixed_solver(gpu, blocks, b)
+    got, want = [], []
+    for what, call in steps:
+        fresh = _mixed_solver(gpu, blocks, b)
+        want.append(call(fresh))
+        fresh.close()
+        got.append(call(shared))
+    shared.close()
+    for (what, call), g, w in zip(steps, got, want):
+        assert _bits(g) == _bits(w), what
+    # the sequence computed something in every form: cuts from the dense rounds, from the sparse round and from the large block
+    assert sum(len(r[1]) for r in want[4]) >= 3 and want[1][0] >= 1 and sum(max(0, r[0]) for r in want[2]) >= 1
+    assert want[2][2][0] == -1 and want[5][0] == 0 and want[5][1] == want[1][1]
+    assert _bits(want[6]) == _bits(want[2])
