@@ -273,7 +273,8 @@ HIPSDP_API int hipsdp_eigencuts_all_stats(long long* calls, long long* launches,
 
 /* Sparse eigenvector cuts of all blocks in one call: the separation mode `multiplesparsecuts` of cons_sdp.c (:1340-1607,
  * addMultipleSparseCuts, after Algorithm 1 of Dey et al., "Cutting plane generation through sparse principal component analysis")
- * in its default configuration (recomputesparseev, recomputeinitial and exacttrans FALSE).  Per block b with lmin[b] < -tol:
+ * in its default configuration (recomputesparseev, recomputeinitial and exacttrans FALSE; with one of them set:
+ * hipsdp_sparsecuts_all_ex below).  Per block b with lmin[b] < -tol:
  *     Z = Z_b(y), (lam, V) its decomposition, v0 = V[0], maxeig = lam[n - 1]
  *     (x, theta) = TPower(maxeig I - Z, v0), scalar = maxeig - theta
  *     while scalar < -feastol and ncuts < maxcuts:  cut (scalar, x);  Z -= scalar x x^T;  maxeig -= scalar;  TPower again from v0
@@ -325,6 +326,44 @@ HIPSDP_API int hipsdp_sparsecuts(hipsdp_solver* solver, int block, const double*
 /* process totals of hipsdp_sparsecuts alone: calls that served their block, kernel launches they issued, device->host
  * synchronisations they waited on (the totals of hipsdp_sparsecuts_all_stats do not move) */
 HIPSDP_API int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks);
+
+/* The two calls above with the reference's three switches on the loop of addMultipleSparseCuts (cons_sdp.c:156-158), as a bit mask.
+ * With x, S and theta the vector, support and value of a TPower run on maxeig I - Z and scalar = maxeig - theta, a cut is produced
+ * while scalar < -feastol and ncuts < maxcuts, and
+ *   HIPSDP_SC_RECOMPUTE_SPARSEEV (recomputesparseev, :1460-1514): (lambda, w) is the smallest eigenpair of the principal submatrix
+ *       Z_S of the current (deflated) Z, w normalised.  lambda >= -tol ENDS the block's loop with no cut from this run (:1487) and
+ *       sets flags bit 2; otherwise the cut vector is w lifted with zeros outside S, and the cut and the deflation use lambda.
+ *   (always) Z -= value x x^T, with value = lambda or scalar and x the cut vector.
+ *   HIPSDP_SC_RECOMPUTE_INITIAL (recomputeinitial, :1532-1550): the next TPower run starts from the eigenvector of the smallest
+ *       eigenvalue of the DEFLATED Z instead of v0.
+ *   HIPSDP_SC_EXACTTRANS (exacttrans, :1552-1568): maxeig becomes the largest eigenvalue of the deflated Z instead of maxeig - value.
+ * As in the default loop one more TPower run follows the last cut, and its iterations are counted.
+ * Arguments, layouts, NULL rules, flags and the meaning of ncuts = 0 / -1 are those of hipsdp_sparsecuts_all and hipsdp_sparsecuts.
+ * eigvals[c] is the value the cut and the deflation used (lambda with HIPSDP_SC_RECOMPUTE_SPARSEEV, else scalar), the vector row is the
+ * cut vector with exact zeros off its support.  The per-block call returns the bits the all-blocks call returns for that block; a
+ * block's bits do not depend on the other blocks of the solver; same input, same bits.  Two host threads may call them at the same
+ * time on different solvers.
+ * variant == 0: the call IS hipsdp_sparsecuts_all / hipsdp_sparsecuts - the same launches, the same bits, booked under their stats;
+ * the totals of hipsdp_sparsecuts_ex_stats do not move.  A bit above HIPSDP_SC_EXACTTRANS set: HIPSDP_ERR_ARG, nothing launched.
+ * variant != 0 serves blocks of AT MOST 128 ROWS of a solver without communicator and without sharded matrices, in all three storage
+ * forms of a block.  A block of more than 128 rows gets ncuts = -1 and nothing else written, from BOTH calls: for 129 .. 512 rows
+ * this is a limit of the present implementation (every cut would need a tridiagonalisation of its own) - keep the host loop for such a
+ * block, or call with variant 0.
+ * The loop runs as maxcuts + 1 rounds on the device (csrc/sparsecuts_rounds.hip): the state of a block stays in the workspace, the
+ * decompositions stand between the TPower launches, and nothing is read back in between.  With s = 1 for
+ * HIPSDP_SC_RECOMPUTE_SPARSEEV (else 0) and d = 1 for HIPSDP_SC_RECOMPUTE_INITIAL or HIPSDP_SC_EXACTTRANS (else 0) a call issues
+ * 5 + maxcuts (1 + 4 s + 3 d) launches and one more for the coefficients when maxcuts > 0 - at most 5 + (maxcuts + 1) (2 + 3 s + 3 d),
+ * a function of (variant, maxcuts) alone: a class of the batched decompositions that has no job gets an empty launch -, one upload
+ * of y and sizes, and one read-back, whatever the number of blocks, cuts and iterations. */
+#define HIPSDP_SC_RECOMPUTE_SPARSEEV 1
+#define HIPSDP_SC_RECOMPUTE_INITIAL  2
+#define HIPSDP_SC_EXACTTRANS         4
+HIPSDP_API int hipsdp_sparsecuts_all_ex(hipsdp_solver* solver, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
+HIPSDP_API int hipsdp_sparsecuts_ex(hipsdp_solver* solver, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
+/* process totals of the two calls with variant != 0: calls, kernel launches they issued, device->host synchronisations they waited on */
+HIPSDP_API int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks);
 
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves

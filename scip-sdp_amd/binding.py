@@ -446,6 +446,56 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's sparsecuts_stats()"""
         return sparsecuts_stats()
 
+    def sparsecuts_all_ex(self, y, sizes, tol, feastol, maxcuts, variant, convtol=0, maxit=0):
+        """sparsecuts_all with the reference's switches as a bit mask (hipsdp_sparsecuts_all_ex; variant: SC_RECOMPUTE_SPARSEEV |
+        SC_RECOMPUTE_INITIAL | SC_EXACTTRANS, 0: the call is sparsecuts_all): the same list of tuples; with a switch set a block of
+        more than 128 rows is not served (ncuts = -1), and flags bit 2 says that the loop ended at lambda >= -tol"""
+        y = _f64(y)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        m, nb, mc = len(y), len(self.ns), max(1, maxcuts)
+        assert len(sizes) == nb
+        opts = SparsecutOpts(tol, feastol, convtol, maxcuts, maxit)
+        k = np.zeros(max(1, nb), dtype=np.int32)
+        it = np.zeros(max(1, nb), dtype=np.int32)
+        fl = np.zeros(max(1, nb), dtype=np.int32)
+        lmin = np.full(max(1, nb), np.nan)
+        ev = np.zeros(max(1, nb) * mc)
+        co = np.zeros(max(1, nb) * mc * max(1, m))
+        lh = np.zeros(max(1, nb) * mc)
+        ve = np.zeros(max(1, maxcuts * sum(self.ns)))
+        _chk(self._l().hipsdp_sparsecuts_all_ex(self.h, _dp(y), _ip(sizes), C.byref(opts), C.c_uint(variant), _ip(k), _dp(lmin), _dp(ev),
+                                                _dp(co), _dp(lh), _dp(ve), _ip(it), _ip(fl)), "hipsdp_sparsecuts_all_ex")
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            kb = max(0, int(k[b]))
+            s0 = b * maxcuts
+            out.append((int(k[b]), float(lmin[b]), ev[s0:s0 + kb].copy(), co[s0 * m:(s0 + kb) * m].reshape(kb, m).copy(),
+                        lh[s0:s0 + kb].copy(), ve[off:off + kb * n].reshape(kb, n).copy(), int(it[b]), int(fl[b])))
+            off += maxcuts * n
+        return out
+
+    def sparsecuts_ex(self, block, y, size, tol, feastol, maxcuts, variant, convtol=0.0, maxit=0):
+        """sparsecuts with the reference's switches as a bit mask (hipsdp_sparsecuts_ex): the tuple one block of sparsecuts_all_ex has"""
+        y = _f64(y)
+        m, n, mc = len(y), self.ns[block], max(1, maxcuts)
+        opts = SparsecutOpts(tol, feastol, convtol, maxcuts, maxit)
+        k, it, fl = C.c_int(0), C.c_int(0), C.c_int(0)
+        lmin = C.c_double(np.nan)
+        ev, lh = np.zeros(mc), np.zeros(mc)
+        co = np.zeros(mc * max(1, m))
+        ve = np.zeros(mc * n)
+        _chk(self._l().hipsdp_sparsecuts_ex(self.h, int(block), _dp(y), int(size), C.byref(opts), C.c_uint(variant), C.byref(k),
+                                            C.byref(lmin), _dp(ev), _dp(co), _dp(lh), _dp(ve), C.byref(it), C.byref(fl)),
+             "hipsdp_sparsecuts_ex")
+        kb = max(0, k.value)
+        return (k.value, lmin.value, ev[:kb].copy(), co[:kb * m].reshape(kb, m).copy(), lh[:kb].copy(), ve[:kb * n].reshape(kb, n).copy(),
+                it.value, fl.value)
+
+    @staticmethod
+    def sparsecuts_ex_stats():
+        """process totals (calls, launches, read-backs): the module's sparsecuts_ex_stats()"""
+        return sparsecuts_ex_stats()
+
 
 class SparsecutOpts(C.Structure):
     """hipsdp_sparsecut_opts"""
@@ -463,6 +513,17 @@ def sparsecuts_stats():
     """process totals of hipsdp_sparsecuts: (calls, kernel launches issued, device->host synchronisations)"""
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_sparsecuts_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+SC_RECOMPUTE_SPARSEEV, SC_RECOMPUTE_INITIAL, SC_EXACTTRANS = 1, 2, 4      # HIPSDP_SC_*
+
+
+def sparsecuts_ex_stats():
+    """process totals of hipsdp_sparsecuts_all_ex / hipsdp_sparsecuts_ex with a switch set: (calls, kernel launches issued,
+    device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_sparsecuts_ex_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_ex_stats")
     return calls.value, launches.value, readbacks.value
 
 

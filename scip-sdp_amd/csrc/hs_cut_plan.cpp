@@ -35,6 +35,14 @@ void hs_sc_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, 
    L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->slabs + slab_len;
 }
 
+void hs_scr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, long long state_len, hs_scr_layout* L)
+{
+   hs_sc_layout_make(nb, m, maxcuts, smax, vec_len, slab_len, &L->sc);
+   L->state = even(L->sc.len.dev_len);
+   L->len = L->sc.len;
+   L->len.dev_len = L->state + state_len;
+}
+
 void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, long long out_len, long long out_vec, hs_scl_layout* L)
 {
    const long long ylen = (m + 2) & ~1LL;

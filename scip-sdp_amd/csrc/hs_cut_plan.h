@@ -29,13 +29,38 @@ struct hs_sc_layout { long long y, sizes; hs_cut_res r; long long slabs; hs_cut_
  * Z and MT start at even offsets */
 struct hs_scl_layout { long long y; hs_cut_res r; long long Z, ws, o1, o2, MT; hs_cut_lens len; };
 
+/* hipsdp_sparsecuts_all_ex / hipsdp_sparsecuts_ex with a switch set (csrc/sparsecuts_rounds.hip): the layout of hs_sc_layout, and
+ * behind its slabs, from `state` on, per served block (hs_scr_block): its hs_scr_state | the start vector of round 0 | Z_S | the
+ * slab of the decomposition of Z_S */
+struct hs_scr_layout { hs_sc_layout sc; long long state; hs_cut_lens len; };
+
+/* what a block's loop keeps in the workspace between the launches of two rounds, besides the deflated Z (in place in its slab) */
+struct hs_scr_state { double maxeig; int nc, iters, flags, done; };
+#define HS_SCR_STATE_LEN 4             /* doubles set aside for it */
+
 /* an n x n matrix in the workspace: n^2 doubles rounded up to an even count */
 static inline long long hs_cut_mat_len(int n) { return ((long long) n * n + 1) & ~1LL; }
+
+/* what a served block of n rows has behind `state` (ns: rows of its Z_S, scratch: hs_syev_small_scratch(ns)), as offsets from the
+ * block's start, every one even: st | v0[n] | ZS[ns^2] | wsS[scratch]; len: where the next block starts */
+struct hs_scr_block { long long st, v0, ZS, wsS, len; };
+static inline hs_scr_block hs_scr_block_make(int n, int ns, long long scratch)
+{
+   hs_scr_block B;
+   B.st = 0;
+   B.v0 = HS_SCR_STATE_LEN;
+   B.ZS = B.v0 + (((long long) n + 1) & ~1LL);
+   B.wsS = B.ZS + hs_cut_mat_len(ns);
+   B.len = B.wsS + ((scratch + 1) & ~1LL);
+   return B;
+}
 
 /* vec_len: doubles of all vectors (maxcuts * rows of the blocks that return vectors); slab_len: sum of hs_cut_mat_len(n) +
  * hs_syev_small_scratch(n) over the batched blocks */
 void hs_ec_layout_make(int nb, int m, int maxcuts, long long vec_len, long long slab_len, hs_ec_layout* L);
 void hs_sc_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, hs_sc_layout* L);
+/* state_len: sum of hs_scr_block_make(..).len over the served blocks; upload and read-back are those of hs_sc_layout */
+void hs_scr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, long long state_len, hs_scr_layout* L);
 /* ws_len = hs_syevx_ws(n), out_len = HS_SYEVX_OUT(n), out_vec = HS_SYEVX_OUT_VEC (csrc/syevx.hip), passed in as numbers */
 void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, long long out_len, long long out_vec, hs_scl_layout* L);
 

@@ -366,6 +366,24 @@ struct hs_sc_par { double tol, feastol, convtol; int maxcuts, maxit; };      /* 
 int hs_sc_tpower(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const int* sizes, const hs_sc_par* par, const hs_sc_out* out);
 int hs_sc_coefs(hipStream_t st, int count, int m, int maxcuts, const hs_ec_job* jobs, const int* sizes, const hs_sc_out* out);
 
+/* ---- sparsecuts_rounds.hip: the same loop as a sequence of rounds, for the switches recomputesparseev, recomputeinitial, exacttrans --- */
+#define HS_SCR_SPARSEEV   1u     /* = HIPSDP_SC_RECOMPUTE_SPARSEEV */
+#define HS_SCR_INITIAL    2u     /* = HIPSDP_SC_RECOMPUTE_INITIAL */
+#define HS_SCR_EXACTTRANS 4u     /* = HIPSDP_SC_EXACTTRANS */
+/* what a block has besides its hs_ec_job (same index in the table): its state between the launches (hs_scr_state, hs_cut_plan.h), the
+ * start vector of round 0 (n doubles), and the job of its principal submatrix - Z_S (sizes[blk]^2 doubles, row-major), the slab of
+ * that decomposition and where its eigenvectors start in it */
+struct hs_scr_job { hs_scr_state* st; double* v0; double* ZS; double* wsS; long long vposS; };
+/* round `round` (0: the state is set up from the decomposition in job.ws) of every job: one TPower run and its decision; without
+ * HS_SCR_SPARSEEV also the cut, with it the support and Z_S for hs_scr_cut behind the decomposition of the Z_S */
+int hs_scr_tpower(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const hs_scr_job* xjobs, const int* sizes, const hs_sc_par* par,
+   unsigned variant, int round, const hs_sc_out* out);
+int hs_scr_cut(hipStream_t st, int count, const hs_ec_job* jobs, const hs_scr_job* xjobs, const int* sizes, const hs_sc_par* par,
+   const hs_sc_out* out);
+/* `launches` empty launches: in place of the classes of a decomposition that have no job, the sequence of a call being a function of
+ * (variant, maxcuts) alone */
+int hs_scr_pad(hipStream_t st, int launches);
+
 /* ---- sparsecuts_large.hip: the same for ONE block of 129 .. 512 rows (hipsdp_sparsecuts) ---------------------------------------- */
 #define HS_SCL_MAXN 512
 /* one workgroup: Z (n x n), lmin[0], maxeig[0] and the start vector v0[n] in device memory, MT: n^2 doubles that only this launch

@@ -154,12 +154,32 @@ struct CutWs
    }
    const hs_ec_job* djobs() const { return reinterpret_cast<const hs_ec_job*>(tab); }
    const hs_eig_job* dejobs() const { return reinterpret_cast<const hs_eig_job*>(tab + jobs.size() * sizeof(hs_ec_job)); }
+   /* the two further tables of the rounds of csrc/sparsecuts_rounds.hip, in a buffer of their own under the same rules: the hs_scr_job of
+    * the blocks (in the order of `jobs`) and behind them the hs_eig_job of their Z_S (ordered by decomposition class) */
+   char* rtab = NULL; long long rtab_len = 0;
+   std::vector<hs_scr_job> xjobs; std::vector<hs_eig_job> sjobs;
+   int upload_rounds(const std::vector<hs_scr_job>& x, const std::vector<hs_eig_job>& sj)
+   {
+      const size_t xb = x.size() * sizeof(hs_scr_job), sb = sj.size() * sizeof(hs_eig_job);
+      if ( (long long) (xb + sb) > rtab_len ) { xjobs.clear(); sjobs.clear(); }
+      HS_CALL( regrow((void**) &rtab, &rtab_len, (long long) (xb + sb), 1, false) );
+      if ( xjobs.size() == x.size() && sjobs.size() == sj.size() && memcmp(xjobs.data(), x.data(), xb) == 0
+         && memcmp(sjobs.data(), sj.data(), sb) == 0 )
+         return HS_OK;
+      HS_HIP( hipMemcpy(rtab, x.data(), xb, hipMemcpyHostToDevice) );
+      HS_HIP( hipMemcpy(rtab + xb, sj.data(), sb, hipMemcpyHostToDevice) );
+      xjobs = x; sjobs = sj;
+      return HS_OK;
+   }
+   const hs_scr_job* dxjobs() const { return reinterpret_cast<const hs_scr_job*>(rtab); }
+   const hs_eig_job* dsjobs() const { return reinterpret_cast<const hs_eig_job*>(rtab + xjobs.size() * sizeof(hs_scr_job)); }
    void release()
    {
       if ( dev != NULL ) (void) hipFree(dev);
       if ( tab != NULL ) (void) hipFree(tab);
+      if ( rtab != NULL ) (void) hipFree(rtab);
       if ( pin != NULL ) (void) hipHostFree(pin);
-      dev = NULL; tab = NULL; pin = NULL;
+      dev = NULL; tab = NULL; rtab = NULL; pin = NULL;
    }
 };
 
@@ -5483,8 +5503,122 @@ static int sc_round(hipsdp_solver* s, const std::vector<int>& ids, const double*
    return HS_OK;
 }
 
-extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+/* ---- the same loop with the reference's switches recomputesparseev, recomputeinitial, exacttrans (kernels: csrc/sparsecuts_rounds.hip) - */
+static CutStats g_scx;
+
+extern "C" int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_scx.get(calls, launches, readbacks);
+}
+
+/* hs_syev_small_many as THREE launches whatever classes the jobs fall into: a class without jobs gets an empty launch */
+static int scx_syev(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* djobs, int* launches)
+{
+   int mine = 0;
+   HS_CALL( hs_syev_small_many(st, count, hjobs, djobs, &mine) );
+   HS_CALL( hs_scr_pad(st, 3 - mine) );
+   *launches += 3;
+   return HS_OK;
+}
+
+/* sc_round with a switch set (variant: HS_SCR_* bits, != 0): Z(y) and its decompositions as there, then maxcuts + 1 rounds - a TPower run
+ * of every block; with HS_SCR_SPARSEEV the decompositions of the Z_S and the cut behind them, without it the cut inside the TPower
+ * launch; with HS_SCR_INITIAL or HS_SCR_EXACTTRANS the decompositions of the deflated Z - and the coefficients, all enqueued on the
+ * solver's stream and followed by ONE read-back.  The last round cannot produce a cut (a block that is still running has maxcuts of
+ * them), so it is its TPower launch alone.  With s = 1 for HS_SCR_SPARSEEV and d = 1 for one of the other two, a call takes
+ * 4 + maxcuts (1 + 4 s + 3 d) + 1 launches and one more for the coefficients when maxcuts > 0, whatever the blocks are. */
+static int scx_rounds(hipsdp_solver* s, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, const std::vector<long long>& vecoff, hs_sc_out* h)
+{
+   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, nj = (int) ids.size();
+   hipStream_t st = s->stream;
+   int smax = 1;
+   for (int b : ids)
+      if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
+         smax = sizes[b];
+   /* rows of the blocks' Z_S; a block whose size exceeds its rows gets no cut, its job is a matrix of one row */
+   std::vector<int> ns((size_t) nj);
+   long long state_len = 0;
+   for (int j = 0; j < nj; ++j)
+   {
+      const int n = s->blk[ids[j]].n;
+      ns[j] = sizes[ids[j]] <= n ? sizes[ids[j]] : 1;
+      state_len += hs_scr_block_make(n, ns[j], hs_syev_small_scratch(ns[j])).len;
+   }
+   hs_scr_layout L;
+   hs_scr_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), state_len, &L);
+   int nmax = 0;
+   HS_CALL( ec_prepare(s, ids, vecoff, L.sc.slabs, L.len, &nmax) );
+   CutWs& cw = s->cw;
+   std::vector<hs_scr_job> xj((size_t) nj);
+   std::vector<hs_eig_job> sj;
+   double* cur = cw.dev + L.state;
+   for (int j = 0; j < nj; ++j)
+   {
+      hs_scr_job& X = xj[j];
+      memset(&X, 0, sizeof(X));
+      const hs_scr_block B = hs_scr_block_make(s->blk[ids[j]].n, ns[j], hs_syev_small_scratch(ns[j]));
+      X.st = reinterpret_cast<hs_scr_state*>(cur + B.st);
+      X.v0 = cur + B.v0;
+      X.ZS = cur + B.ZS;
+      X.wsS = cur + B.wsS;
+      X.vposS = hs_syev_many_vecpos(ns[j]);
+      cur += B.len;
+   }
+   for (int cls = 0; cls < 3; ++cls)
+      for (int j = 0; j < nj; ++j)
+         if ( hs_syev_many_class(ns[j]) == cls )
+         {
+            hs_eig_job E;
+            memset(&E, 0, sizeof(E));
+            E.n = ns[j]; E.in = xj[j].ZS; E.ws = xj[j].wsS;
+            sj.push_back(E);
+         }
+   HS_CALL( cw.upload_rounds(xj, sj) );
+   double* dy = cw.dev + L.sc.y;
+   const int* dsizes = reinterpret_cast<const int*>(cw.dev + L.sc.sizes);
+   const hs_sc_out out = hs_cut_view(L.sc.r, cw.dev);
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   int launches = 0;
+   if ( m > 0 )
+      memcpy(cw.pin + L.sc.y, y, (size_t) m * sizeof(double));
+   memcpy(cw.pin + L.sc.sizes, sizes, (size_t) nb * sizeof(int));
+   HS_HIP( hipMemcpyAsync(dy, cw.pin + L.sc.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
+   ++launches;
+   HS_CALL( scx_syev(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
+   for (int round = 0; round <= maxcuts; ++round)
+   {
+      HS_CALL( hs_scr_tpower(st, nj, nmax, cw.djobs(), cw.dxjobs(), dsizes, &par, variant, round, &out) );
+      ++launches;
+      if ( round == maxcuts )
+         break;
+      if ( variant & HS_SCR_SPARSEEV )
+      {
+         HS_CALL( scx_syev(st, nj, cw.sjobs.data(), cw.dsjobs(), &launches) );
+         HS_CALL( hs_scr_cut(st, nj, cw.djobs(), cw.dxjobs(), dsizes, &par, &out) );
+         ++launches;
+      }
+      if ( variant & (HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
+         HS_CALL( scx_syev(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
+   }
+   if ( maxcuts > 0 )
+   {
+      HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, cw.djobs(), dsizes, &out) );
+      ++launches;
+   }
+   HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_scx.launches += launches;
+   g_scx.readbacks += 1;
+   *h = hs_cut_view(L.sc.r, cw.pin);
+   return HS_OK;
+}
+
+/* hipsdp_sparsecuts_all (variant = 0: sc_round, booked under g_sc) and hipsdp_sparsecuts_all_ex with a switch set */
+static int sparsecuts_all_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
 {
    if ( s == NULL || !s->shaped || y == NULL || sizes == NULL || opts == NULL || ncuts == NULL || opts->maxcuts < 0 )
       return HIPSDP_ERR_ARG;
@@ -5505,7 +5639,10 @@ extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const in
    if ( !ids.empty() )
    {
       hs_sc_out h;
-      HS_CALL( sc_round(s, ids, y, sizes, opts, vecoff, &g_sc, &h) );
+      if ( variant == 0 )
+         HS_CALL( sc_round(s, ids, y, sizes, opts, vecoff, &g_sc, &h) );
+      else
+         HS_CALL( scx_rounds(s, ids, y, sizes, opts, variant, vecoff, &h) );
       for (int b : ids)
       {
          const int k = h.ncuts[b];
@@ -5520,21 +5657,38 @@ extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const in
             vecs != NULL ? vecs + vecoff[b] : NULL);
       }
    }
-   ++g_sc.calls;
+   ++(variant == 0 ? g_sc : g_scx).calls;
    return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   return sparsecuts_all_impl(s, y, sizes, opts, 0, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
+}
+
+extern "C" int hipsdp_sparsecuts_all_ex(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( variant > (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
+      return HIPSDP_ERR_ARG;
+   return sparsecuts_all_impl(s, y, sizes, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
 }
 
 /* ---- sparse eigenvector cuts of ONE block of up to 512 rows (kernels: csrc/sparsecuts.hip, csrc/sparsecuts_large.hip) ---------- */
 /* a block of at most 128 rows: the round of hipsdp_sparsecuts_all with this block as the only job, the same bits */
-static int sparsecuts_small(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+static int sparsecuts_small(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
 {
    const int maxcuts = opts->maxcuts;
    const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, block);      /* only this block has vectors */
    std::vector<int> sizes(s->blk.size(), 1);
    sizes[block] = size;
    hs_sc_out h;
-   HS_CALL( sc_round(s, std::vector<int>(1, block), y, sizes.data(), opts, vecoff, &g_sc1, &h) );
+   if ( variant == 0 )
+      HS_CALL( sc_round(s, std::vector<int>(1, block), y, sizes.data(), opts, vecoff, &g_sc1, &h) );
+   else
+      HS_CALL( scx_rounds(s, std::vector<int>(1, block), y, sizes.data(), opts, variant, vecoff, &h) );
    const int k = h.ncuts[block];
    if ( k < 0 || k > maxcuts )
       return HIPSDP_ERR_NUMERIC;
@@ -5620,8 +5774,9 @@ static int sparsecuts_large(hipsdp_solver* s, int block, const double* y, int si
    return HIPSDP_OK;
 }
 
-extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+/* hipsdp_sparsecuts (variant = 0, booked under g_sc1) and hipsdp_sparsecuts_ex with a switch set: blocks of at most 128 rows */
+static int sparsecuts_impl(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
 {
    if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || y == NULL || opts == NULL || ncuts == NULL || size < 1
       || opts->maxcuts < 0 )
@@ -5630,7 +5785,7 @@ extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, i
       return HIPSDP_ERR_ARG;
    const int n = s->blk[block].n;
    *ncuts = -1;
-   if ( s->comm != NULL || s->shardA || n > HIPSDP_SPARSECUTS_MAXN )
+   if ( s->comm != NULL || s->shardA || n > (variant == 0 ? HIPSDP_SPARSECUTS_MAXN : HS_SC_MAXN) )
       return HIPSDP_OK;
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
@@ -5639,11 +5794,25 @@ extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, i
    if ( B.sparse ? (B.sp == NULL || B.A0 == NULL) : B.A == NULL )
       return HIPSDP_OK;
    if ( n <= HS_SC_MAXN )
-      HS_CALL( sparsecuts_small(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
+      HS_CALL( sparsecuts_small(s, block, y, size, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
    else
       HS_CALL( sparsecuts_large(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
-   ++g_sc1.calls;
+   ++(variant == 0 ? g_sc1 : g_scx).calls;
    return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   return sparsecuts_impl(s, block, y, size, opts, 0, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
+}
+
+extern "C" int hipsdp_sparsecuts_ex(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( variant > (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
+      return HIPSDP_ERR_ARG;
+   return sparsecuts_impl(s, block, y, size, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
 }
 
 /* host-only: the column ranges of the sharded W formulation, bounds[0 .. nranks] (rank g owns [bounds[g], bounds[g + 1])) */

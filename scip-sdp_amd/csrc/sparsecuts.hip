@@ -13,7 +13,8 @@
  *
  * M = maxeig I - Z is EXPLICIT in LDS, as in the reference (m_ii = maxeig - z_ii, m_ij = -z_ij), so that a product has the summands
  * of the reference's; the diagonal of Z is kept beside it, and a cut (Z -= scalar x x^T, maxeig -= scalar) adds scalar x_r x_c to the
- * size^2 entries of M on the support and forms M's diagonal again.  One product per iteration: the M x behind the Rayleigh quotient
+ * size^2 entries of M on the support and forms M's diagonal again.  A single TPower run is sc_tpower_run of hs_sc_tpower.h, shared
+ * with the rounds of sparsecuts_rounds.hip.  One product per iteration: the M x behind the Rayleigh quotient
  * of an iteration is the w of the next one (the reference forms it twice).  A product walks the support of x in ascending index
  * order - the skipped summands are exact zeros.  The truncation keeps entry i when fewer than `size` entries j have |w_j| > |w_i|, or
  * |w_j| == |w_i| and j < i: of two equal absolute values the smaller index stays.  All sums over the threads run in a fixed order
@@ -22,8 +23,8 @@
  * condition is false for a NaN, and every loop is bounded by maxit or maxcuts. */
 #include "hs_kernels.h"
 #include "hs_wave.h"
+#include "hs_sc_tpower.h"
 
-#define SC_NT 128          /* k_sc_tpower: one thread per row, HS_SC_MAXN rows at most */
 #define SC_CT 256          /* k_sc_coefs */
 
 /* dynamic LDS of k_sc_tpower for a block of n rows: M | diagonal of Z | x on its support | |w| | v0 | red[2] | support (int) | kept
@@ -33,37 +34,12 @@ static size_t sc_lds(int n)
    return ((size_t) n * (n | 1) + 4 * (size_t) n + 2) * sizeof(double) + ((size_t) n + 2) * sizeof(int);
 }
 
-/* Sum over the workgroup, the same bits in every thread: hs_wave_sum_dpp per wavefront, then the wavefronts in index order.  ONE
- * barrier, behind the stores to red - red must not be written again before the next barrier of the caller. */
-__device__ __forceinline__ double sc_block_sum(double v, double* red)
-{
-   v = hs_wave_sum_dpp(v);
-   if ( (threadIdx.x & 63) == 0 )
-      red[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double s = red[0];
-#pragma unroll
-   for (int w = 1; w < SC_NT / 64; ++w)
-      s += red[w];
-   return s;
-}
-
-/* (M x)_i over the support of x in ascending index order: sup[p] the indices, xc[p] the values */
-__device__ __forceinline__ double sc_row_product(const double* mrow, const double* xc, const int* sup, int ns)
-{
-   double acc = 0.0;
-#pragma unroll 4
-   for (int p = 0; p < ns; ++p)
-      acc += mrow[sup[p]] * xc[p];
-   return acc;
-}
-
 __global__ void __launch_bounds__(SC_NT) k_sc_tpower(const hs_ec_job* __restrict__ jobs, const int* __restrict__ sizes, hs_sc_par par,
    hs_sc_out out)
 {
    extern __shared__ __attribute__((aligned(16))) double sc_mem[];
    const hs_ec_job job = jobs[blockIdx.x];
-   const int n = job.n, pitch = n | 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int n = job.n, pitch = n | 1, tid = threadIdx.x;
    const int size = sizes[job.blk];
    const double* __restrict__ lam = job.ws;
    const double lmin = lam[0];
@@ -102,57 +78,11 @@ __global__ void __launch_bounds__(SC_NT) k_sc_tpower(const hs_ec_job* __restrict
    for (;;)
    {
       /* ---- one TPower run from v0 on M (as in the reference, one more follows the last cut) ---- */
-      __syncthreads();           /* M (first run: loaded, later: after the cut) and the last reads of x and the support */
-      double x = 0.0, u = 0.0;
-      if ( row )
-      {
-         x = v0s[tid];
-#pragma unroll 4
-         for (int j = 0; j < n; ++j)
-            u += mrow[j] * v0s[j];
-      }
-      double newv = -1.0, oldv = -2.0;
-      int it = 0;
-      bool dead = false;
-      while ( newv - oldv > par.convtol && it < par.maxit )
-      {
-         oldv = newv;
-         const double w = u, awi = fabs(w);
-         if ( row )
-            aw[tid] = awi;
-         __syncthreads();
-         int above = 0;
-#pragma unroll 4
-         for (int j = 0; j < n; ++j)
-         {
-            const double a = aw[j];
-            above += (int) (a > awi) | ((int) (a == awi) & (int) (j < tid));
-         }
-         const bool kept = row && above < size;
-         const unsigned long long mask = __ballot(kept);
-         const int before = __popcll(mask & ((1ull << lane) - 1ull));
-         if ( lane == 0 )
-            wkept[wave] = __popcll(mask);
-         const double nrm = sqrt(sc_block_sum(kept ? w * w : 0.0, red));
-         if ( nrm == 0.0 )
-         {
-            dead = true;
-            break;
-         }
-         const int pos = (wave == 0 ? 0 : wkept[0]) + before;
-         x = kept ? w / nrm : 0.0;
-         if ( kept )
-         {
-            sup[pos] = tid;
-            xc[pos] = x;
-         }
-         __syncthreads();
-         u = row ? sc_row_product(mrow, xc, sup, size) : 0.0;
-         newv = sc_block_sum(x * u, red);
-         ++it;
-      }
+      const sc_run run = sc_tpower_run(n, size, row, mrow, v0s, aw, xc, sup, wkept, red, par.convtol, par.maxit);
+      const double x = run.x, newv = run.newv, oldv = run.oldv;
+      const int it = run.it;
       iters += it;
-      if ( dead )
+      if ( run.dead )
       {
          flags |= 2;
          break;
