@@ -365,6 +365,54 @@ HIPSDP_API int hipsdp_sparsecuts_ex(hipsdp_solver* solver, int block, const doub
 /* process totals of the two calls with variant != 0: calls, kernel launches they issued, device->host synchronisations they waited on */
 HIPSDP_API int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* All one-variable SDPs of a block in one call: the bound-tightening loops of cons_sdp.c - tightenBounds (:1968-2201) and
+ * tightenMatrices (:1856-1961) solve one SDP PER VARIABLE of a block, each the semismooth Newton method of
+ * SCIPsolveOneVarSDPDense (solveonevarsdp.c:370-533) on  mu A_i - C_i,  C_i = A_0 - sum_{k != i} ub_k A_k.  With
+ * Z(u) = sum_k u_k A_k - A_0 that matrix is
+ *     M_i(mu) = Z_block(u) + (mu - u_i) A_i        (tightenBounds: u = ub; tightenMatrices: u = 0),
+ * and the loop over i never changes u: the jobs of a block are independent.  Job j, i = vars[j], with f(mu) the smallest
+ * eigenvalue of M_i(mu) and g(mu) = v^T A_i v at its unit eigenvector v (a supergradient of the concave f):
+ *   HIPSDP_ONEVAR_NEWTON, the order of evaluations and the comparisons of solveonevarsdp.c:434-525 with obj = 1:
+ *     at ub:  f < -feastol and g > 0   -> INFEASIBLE, optval = ub
+ *     at lb:  f >= -feastol            -> LB, optval = lb, grad = 0;      g <= 0 -> INFEASIBLE, optval = lb
+ *     loop:   mu <- mu - (feastol / 2 + f) / g;  mu > ub -> INFEASIBLE, optval = mu;  evaluate at mu;  while f < -feastol and g > 0
+ *     then:   f < -feastol -> INFEASIBLE, else INNER, optval = mu
+ *   HIPSDP_ONEVAR_TWOPOINT, the binary-variable branch of tightenBounds (:2102-2153), eigenvalues only:
+ *     f(lb) >= -feastol -> LB;  else f(ub) < -feastol -> INFEASIBLE, optval = ub;  else UBONLY, optval = ub
+ * u: m host values (engine variables, as y of hipsdp_eigencuts); vars: count engine variable indices (0-based), NULL: all m
+ * variables in index order (count must be m); kind: one HIPSDP_ONEVAR_* kind per job, NULL: all NEWTON; lb, ub: per job.
+ * Per job: status, optval, lmin (the last eigenvalue computed), grad (the last supergradient; 0 for LB and for TWOPOINT), evals
+ * (eigenvalue evaluations); lmin, grad and evals may be NULL.  DECLINED (an infinite bound, solveonevarsdp.c:407-411) computes
+ * nothing: optval = lmin = grad = 0, evals = 0.  GAVEUP (opts->maxevals evaluations done and one more needed, or a non-finite
+ * eigenvalue or supergradient): optval is the last point evaluated.
+ * Whatever the number of jobs and evaluations: ONE upload (u, the job table, bounds and kinds in one buffer), TWO launches (Z(u),
+ * then one workgroup per job that runs the whole loop of its job: csrc/eigi.hip, k_onevar_small up to 64 rows, k_onevar_mid up to
+ * 128) and ONE read-back.  Same input, same bits; the bits of a job do not depend on the other jobs of the call.  Two host
+ * threads may call it at the same time on different solvers.
+ * Every status[j] = -1 with HIPSDP_OK and nothing else written: a block of more than HIPSDP_ONEVAR_MAXN rows, or a solver with a
+ * communicator or with sharded matrices.  HIPSDP_ERR_ARG, checked before the device is looked at, nothing launched: solver NULL or
+ * without a shape, block out of range, u, lb, ub, opts, status or optval NULL, count < 0, a variable index outside [0, m), a kind
+ * other than the two, feastol < 0, vars == NULL with count != m.  count == 0: HIPSDP_OK, nothing launched. */
+#define HIPSDP_ONEVAR_MAXN      128
+/* kind of a job */
+#define HIPSDP_ONEVAR_NEWTON    0   /* SCIPsolveOneVarSDPDense with obj = 1 (solveonevarsdp.c:370-533) */
+#define HIPSDP_ONEVAR_TWOPOINT  1   /* the binary-variable branch of tightenBounds (cons_sdp.c:2102-2153): two eigenvalues, no vectors */
+/* status of a job */
+#define HIPSDP_ONEVAR_LB          0   /* M(lb) is psd to feastol: optval = lb, nothing to tighten */
+#define HIPSDP_ONEVAR_INNER       1   /* NEWTON: optval = the last iterate mu in (lb, ub] */
+#define HIPSDP_ONEVAR_INFEASIBLE  2   /* optval = the point where it was detected (ub, lb or the last mu, as the reference) */
+#define HIPSDP_ONEVAR_UBONLY      3   /* TWOPOINT: M(lb) is not psd, M(ub) is: optval = ub */
+#define HIPSDP_ONEVAR_DECLINED    4   /* lb <= -infinity or ub >= infinity (solveonevarsdp.c:407-411): nothing computed */
+#define HIPSDP_ONEVAR_GAVEUP      5   /* maxevals reached, or a non-finite eigenvalue / supergradient: optval = last mu */
+typedef struct hipsdp_onevar_opts { double feastol; double infinity; int maxevals; /* <= 0: 100 */ } hipsdp_onevar_opts;
+
+HIPSDP_API int hipsdp_onevar_bounds(hipsdp_solver* solver, int block, const double* u, int count, const int* vars, const int* kind,
+   const double* lb, const double* ub, const hipsdp_onevar_opts* opts,
+   int* status, double* optval, double* lmin, double* grad, int* evals);
+/* process totals: calls that served their block, kernel launches they issued, device->host synchronisations they waited on (NULL
+ * pointers are accepted; works without a device) */
+HIPSDP_API int hipsdp_onevar_bounds_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves
  * them alone with the single-rank kernels and rank 0's outcome (status, iterate, preoptimal iterate) is broadcast once per solve. */

@@ -160,6 +160,12 @@ HIPSDP_API int  hipsdp_tvec_unit(int device, int n, const double* d, const doubl
  * soff[m + 1], srow[nslots], sent[nslots + 1].  A first call with the arrays NULL gives the counts to size them by. */
 HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long long* counts, int* voff, int* vrow, int* vcol, double* vval,
    int* poff, int* prow, int* pcol, int* pvar, double* pval, int* foff, int* frow, int* fcol, double* fval, int* soff, int* srow, int* sent);
+/* the Newton kernel of hipsdp_onevar_bounds (csrc/eigi.hip: k_onevar_small for n <= 64, k_onevar_mid for n <= 128) alone on host
+ * matrices: Z (n x n) and, for job j < count, the dense A + j n^2 (n x n), the shift shift[j] (= u_i), kind[j] (NULL: all NEWTON),
+ * lb[j], ub[j]: M_j(mu) = Z + (mu - shift[j]) A_j.  infinity is 1e20, maxevals <= 0 means 100.  status, optval, lmin, grad, evals as
+ * hipsdp_onevar_bounds returns them (lmin, grad, evals may be NULL). */
+HIPSDP_API int  hipsdp_onevar_unit(int device, int n, int count, const double* Z, const double* A, const double* shift, const int* kind,
+   const double* lb, const double* ub, double feastol, int maxevals, int* status, double* optval, double* lmin, double* grad, int* evals);
 
 #ifdef __cplusplus
 }

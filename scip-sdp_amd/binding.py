@@ -496,6 +496,67 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's sparsecuts_ex_stats()"""
         return sparsecuts_ex_stats()
 
+    def onevar_bounds(self, block, u, lb, ub, feastol, vars=None, kind=None, infinity=1e20, maxevals=0):
+        """all one-variable SDPs of a block in one call (hipsdp_onevar_bounds): job j works on Z_block(u) + (mu - u_i) A_i with
+        i = vars[j] (None: all variables in index order), kind[j] ONEVAR_NEWTON (None: all) or ONEVAR_TWOPOINT, bounds lb[j], ub[j].
+        Returns the arrays (status, optval, lmin, grad, evals); every status -1: the block is not served"""
+        u, lb, ub = _f64(u), _f64(lb), _f64(ub)
+        count = len(lb)
+        assert len(ub) == count
+        cv = None if vars is None else np.ascontiguousarray(vars, dtype=np.int32)
+        ck = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32)
+        assert cv is None or len(cv) == count
+        assert ck is None or len(ck) == count
+        opts = OnevarOpts(feastol, infinity, maxevals)
+        status = np.full(max(1, count), -1, dtype=np.int32)
+        evals = np.zeros(max(1, count), dtype=np.int32)
+        optval, lmin, grad = (np.full(max(1, count), np.nan) for _ in range(3))
+        _chk(self._l().hipsdp_onevar_bounds(self.h, int(block), _dp(u), count, None if cv is None else _ip(cv),
+                                            None if ck is None else _ip(ck), _dp(lb), _dp(ub), C.byref(opts), _ip(status), _dp(optval),
+                                            _dp(lmin), _dp(grad), _ip(evals)), "hipsdp_onevar_bounds")
+        return status[:count], optval[:count], lmin[:count], grad[:count], evals[:count]
+
+    @staticmethod
+    def onevar_bounds_stats():
+        """process totals (calls, launches, read-backs): the module's onevar_bounds_stats()"""
+        return onevar_bounds_stats()
+
+
+class OnevarOpts(C.Structure):
+    """hipsdp_onevar_opts"""
+    _fields_ = [("feastol", C.c_double), ("infinity", C.c_double), ("maxevals", C.c_int)]
+
+
+ONEVAR_NEWTON, ONEVAR_TWOPOINT = 0, 1                                                                          # HIPSDP_ONEVAR_* kinds
+ONEVAR_LB, ONEVAR_INNER, ONEVAR_INFEASIBLE, ONEVAR_UBONLY, ONEVAR_DECLINED, ONEVAR_GAVEUP = 0, 1, 2, 3, 4, 5    # ... and statuses
+
+
+def onevar_bounds_stats():
+    """process totals of hipsdp_onevar_bounds: (calls that served their block, kernel launches issued, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_onevar_bounds_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_onevar_bounds_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def onevar_unit(n, Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, device=0):
+    """the Newton kernel of hipsdp_onevar_bounds alone on host matrices (hipsdp_onevar_unit of the units library): Z (n x n), A
+    (count dense n x n), shift[j] = u_i; returns the arrays (status, optval, lmin, grad, evals)"""
+    n = int(n)
+    Z = _f64(np.asarray(Z, dtype=np.float64).reshape(-1))
+    A = _f64(np.asarray(A, dtype=np.float64).reshape(-1))
+    shift, lb, ub = _f64(np.atleast_1d(shift)), _f64(np.atleast_1d(lb)), _f64(np.atleast_1d(ub))
+    count = len(lb)
+    assert len(Z) == n * n and len(A) == count * n * n and len(ub) == count and len(shift) == count
+    ck = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32)
+    status = np.full(count, -1, dtype=np.int32)
+    evals = np.zeros(count, dtype=np.int32)
+    optval, lmin, grad = (np.full(count, np.nan) for _ in range(3))
+    rc = ulib().hipsdp_onevar_unit(device, n, count, _dp(Z), _dp(A), _dp(shift), None if ck is None else _ip(ck), _dp(lb), _dp(ub),
+                                   C.c_double(feastol), int(maxevals), _ip(status), _dp(optval), _dp(lmin), _dp(grad), _ip(evals))
+    if rc != 0:
+        raise RuntimeError("hipsdp_onevar_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    return status, optval, lmin, grad, evals
+
 
 class SparsecutOpts(C.Structure):
     """hipsdp_sparsecut_opts"""

@@ -735,7 +735,9 @@ __device__ __forceinline__ void em_tridiag(int n, const double* __restrict__ in,
       em_tridiag_t<2>(n, in, em_a, vv, pp, ww, tau, d, e);
 }
 
-__global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec, const double* __restrict__ in, double* __restrict__ out,
+/* the body (flag == NULL: no sequence number, no system-scope fence - the caller is another kernel of the engine, k_onevar_mid below;
+ * the wavefronts other than 0 come back right after the reduction, the caller's barrier waits for wavefront 0) */
+__device__ __forceinline__ void d_syevi_mid(int n, int ith, int wantvec, const double* __restrict__ in, double* __restrict__ out,
    unsigned long long seq, unsigned long long* __restrict__ flag)
 {
    extern __shared__ __attribute__((aligned(16))) double em_a[];
@@ -880,10 +882,279 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
       if ( lane + 64 < n )
          out[65 + lane] = nrm > 0.0 ? zb / nrm : zb;
    }
+   if ( flag == NULL )
+      return;
    __threadfence_system();
    __builtin_amdgcn_wave_barrier();
    if ( lane == 0 )
       __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec, const double* __restrict__ in, double* __restrict__ out,
+   unsigned long long seq, unsigned long long* __restrict__ flag)
+{
+   d_syevi_mid(n, ith, wantvec, in, out, seq, flag);
+}
+
+/* ---- all one-variable SDPs of a block (hipsdp_onevar_bounds): the whole semismooth Newton method of a job in ONE workgroup -------
+ * Reference: SCIPsolveOneVarSDPDense (solveonevarsdp.c:370-533) as tightenBounds (cons_sdp.c:1968-2201) and tightenMatrices
+ * (:1856-1961) call it once per variable of a block, 2 to about 13 smallest eigenpairs of  mu A_i - C_i  each.  Here job j of the
+ * launch is a workgroup that works on  M(mu) = Z(u) + (mu - u_i) A_i  (the same matrix: C_i = A_0 - sum_{k != i} u_k A_k):
+ *   - n <= 64 (k_onevar_small, 256 threads): Z(u) and the dense A_i staged ONCE into LDS from whichever storage form the block has,
+ *     M(mu) formed in LDS per evaluation, the eigenpair by d_syevi_small<false> at full accuracy, g = v^T A_i v by a workgroup
+ *     reduction in a fixed order.  LDS: 3 n^2 doubles dynamic (96 KB at n = 64) + 38 KB of the eigenpair body + 1 KB here, of 160 KB.
+ *   - 64 < n <= 128 (k_onevar_mid, 512 threads): the reduction alone needs the matrix in LDS (n (n | 1) doubles, 129 KB at n = 128,
+ *     + 12 KB of the body + 1.2 KB here), so Z(u) stays where k_ec_form_z put it, the dense A_i and M(mu) live in a 2 n^2 slab of
+ *     the job in the workspace (L2-resident: 256 KB per job), and d_syevi_mid reads M(mu) from there.
+ * The Newton scalars are kept by thread 0 and broadcast through LDS.  Every loop is bounded: maxevals evaluations per job; a
+ * non-finite eigenvalue or supergradient ends the job (GAVEUP).  A TWOPOINT job asks for no eigenvector.  n = 1 is a scalar.
+ * Nothing here depends on the other jobs of the launch, and every sum runs in a fixed order: same input, same bits. */
+#define OV_ST_LB 0
+#define OV_ST_INNER 1
+#define OV_ST_INFEASIBLE 2
+#define OV_ST_UBONLY 3
+#define OV_ST_DECLINED 4
+#define OV_ST_GAVEUP 5
+/* where the loop of a job stands: the point it evaluates next */
+#define OV_AT_UB 0            /* NEWTON: upper bound first */
+#define OV_AT_LB 1
+#define OV_AT_MU 2
+#define OV_TP_LB 3            /* TWOPOINT */
+#define OV_TP_UB 4
+#define OV_DONE 5
+struct ov_state { double mu, ub, lb, shift, f, g, optval; int at, evals, status, wantvec; };
+
+/* the dense A_i (n x n, no pitch) of job j into dst (LDS or device memory); contains barriers */
+__device__ __forceinline__ void ov_stage_a(const hs_ov_par& P, int j, int var, double* dst)
+{
+   const int n = P.n, tid = threadIdx.x, nt = (int) blockDim.x;
+   if ( P.blk == NULL )
+   {
+      const double* __restrict__ a = P.A + (long long) j * n * n;
+      for (int e = tid; e < n * n; e += nt)
+         dst[e] = a[e];
+   }
+   else if ( P.blk->form == HS_EC_SPARSE )
+   {
+      const hs_sp_view sp = P.blk->sp;
+      for (int e = tid; e < n * n; e += nt)
+         dst[e] = 0.0;
+      __syncthreads();
+      /* the variable's lower-triangular nonzeros, every position once */
+      for (int e = sp.voff[var] + tid; e < sp.voff[var + 1]; e += nt)
+      {
+         const int r = sp.vrow[e], c = sp.vcol[e];
+         const double v = sp.vval[e];
+         if ( r >= 0 && r < n && c >= 0 && c < n )
+         {
+            dst[r * n + c] = v;
+            dst[c * n + r] = v;
+         }
+      }
+   }
+   else
+   {
+      const bool packed = P.blk->form == HS_EC_PACKED;
+      const double* __restrict__ a = P.blk->A + (long long) (var + 1) * P.blk->ld;
+      for (int e = tid; e < n * n; e += nt)
+      {
+         const int r0 = e / n, c0 = e - r0 * n;
+         const int r = r0 > c0 ? r0 : c0, c = r0 > c0 ? c0 : r0;
+         dst[e] = a[packed ? (long long) r * (r + 1) / 2 + c : (long long) e];
+      }
+   }
+   __syncthreads();
+}
+
+/* thread 0, before the first evaluation */
+__device__ __forceinline__ void ov_begin(const hs_ov_par& P, int j, ov_state* S)
+{
+   const double* __restrict__ t = P.tab + (long long) j * HS_OV_TAB;
+   const int kind = (int) t[1];
+   S->lb = t[2]; S->ub = t[3]; S->shift = t[4];
+   S->f = 0.0; S->g = 0.0; S->optval = 0.0; S->evals = 0; S->status = OV_ST_DECLINED;
+   S->wantvec = kind == 0 ? 1 : 0;
+   if ( S->lb <= -P.infinity || S->ub >= P.infinity )
+   {
+      S->at = OV_DONE;
+      S->mu = 0.0;
+      return;
+   }
+   S->at = kind == 0 ? OV_AT_UB : OV_TP_LB;
+   S->mu = kind == 0 ? S->ub : S->lb;
+}
+
+/* thread 0, after the evaluation at S->mu gave (f, g): the comparisons of solveonevarsdp.c:434-525 in their order, or those of
+ * cons_sdp.c:2119 / :2143; sets the next point or the result */
+__device__ __forceinline__ void ov_decide(const hs_ov_par& P, ov_state* S, double f, double g)
+{
+   const double feastol = P.feastol, here = S->mu;
+   const int at = S->at;
+   ++S->evals;
+   S->f = f;
+   S->g = S->wantvec ? g : 0.0;
+   int next = OV_DONE;
+   if ( !isfinite(f) || (S->wantvec && !isfinite(g)) )
+   {
+      S->status = OV_ST_GAVEUP; S->optval = here;
+   }
+   else if ( at == OV_TP_LB )
+   {
+      if ( f >= -feastol ) { S->status = OV_ST_LB; S->optval = S->lb; }
+      else { next = OV_TP_UB; S->mu = S->ub; }
+   }
+   else if ( at == OV_TP_UB )
+   {
+      S->status = f < -feastol ? OV_ST_INFEASIBLE : OV_ST_UBONLY; S->optval = S->ub;
+   }
+   else if ( at == OV_AT_UB )
+   {
+      if ( f < -feastol && g > 0.0 ) { S->status = OV_ST_INFEASIBLE; S->optval = S->ub; }
+      else { next = OV_AT_LB; S->mu = S->lb; }
+   }
+   else
+   {
+      if ( at == OV_AT_LB && f >= -feastol ) { S->status = OV_ST_LB; S->optval = S->lb; S->g = 0.0; }
+      else if ( at == OV_AT_LB && g <= 0.0 ) { S->status = OV_ST_INFEASIBLE; S->optval = S->lb; }
+      else if ( f < -feastol && g > 0.0 )
+      {
+         const double mu = S->mu - (feastol / 2.0 + f) / g;
+         if ( mu > S->ub ) { S->status = OV_ST_INFEASIBLE; S->optval = mu; }
+         else { next = OV_AT_MU; S->mu = mu; }
+      }
+      else { S->status = f < -feastol ? OV_ST_INFEASIBLE : OV_ST_INNER; S->optval = S->mu; }
+   }
+   if ( next != OV_DONE && S->evals >= P.maxevals )
+   {
+      /* (S->mu is the next point already: the last point EVALUATED is reported) */
+      S->status = OV_ST_GAVEUP; S->optval = here;
+      next = OV_DONE;
+   }
+   S->at = next;
+}
+
+__device__ __forceinline__ void ov_store(const hs_ov_par& P, int j, const ov_state* S)
+{
+   double* __restrict__ r = P.res + (long long) j * HS_OV_RES;
+   r[0] = (double) S->status; r[1] = S->optval; r[2] = S->f; r[3] = S->g; r[4] = (double) S->evals; r[5] = 0.0;
+}
+
+__global__ void __launch_bounds__(256) k_onevar_small(hs_ov_par P)
+{
+   extern __shared__ __attribute__((aligned(16))) double ov_dyn[];
+   __shared__ ov_state S;
+   __shared__ double eo[EI_N + 2], part[4];
+   const int j = blockIdx.x, n = P.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   double* sz = ov_dyn;                 /* Z(u) */
+   double* sa = sz + n * n;             /* A_i */
+   double* sm = sa + n * n;             /* M(mu) */
+   if ( tid == 0 )
+      ov_begin(P, j, &S);
+   __syncthreads();
+   if ( S.at == OV_DONE )               /* (declined: the same in every thread) */
+   {
+      if ( tid == 0 )
+         ov_store(P, j, &S);
+      return;
+   }
+   {
+      const double* __restrict__ Z = P.blk != NULL ? P.blk->Z : P.Z;
+      for (int e = tid; e < n * n; e += 256)
+         sz[e] = Z[e];
+   }
+   ov_stage_a(P, j, (int) P.tab[(long long) j * HS_OV_TAB], sa);
+   /* at most maxevals rounds: ov_decide ends the job at that count */
+   for (int round = 0; round < P.maxevals; ++round)
+   {
+      const double s = S.mu - S.shift;
+      const int wantvec = S.wantvec;
+      for (int e = tid; e < n * n; e += 256)
+         sm[e] = sz[e] + s * sa[e];
+      __syncthreads();
+      if ( n == 1 )
+      {
+         if ( tid == 0 ) { eo[0] = sm[0]; eo[1] = 1.0; }
+      }
+      else
+         d_syevi_small<false>(n, 1, wantvec, sm, eo, 0ULL, NULL);
+      __syncthreads();
+      double g = 0.0;
+      if ( wantvec )
+      {
+         for (int e = tid; e < n * n; e += 256)
+         {
+            const int r = e / n, c = e - r * n;
+            g += sa[e] * eo[1 + r] * eo[1 + c];
+         }
+         g = hs_wave_sum_dpp(g);
+         if ( lane == 0 )
+            part[wave] = g;
+         __syncthreads();
+      }
+      if ( tid == 0 )
+         ov_decide(P, &S, eo[0], wantvec ? ((part[0] + part[1]) + part[2]) + part[3] : 0.0);
+      __syncthreads();
+      if ( S.at == OV_DONE )
+         break;
+   }
+   if ( tid == 0 )
+      ov_store(P, j, &S);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_onevar_mid(hs_ov_par P)
+{
+   __shared__ ov_state S;
+   __shared__ double eo[EM_N + 2], part[EM_NT / 64];
+   const int j = blockIdx.x, n = P.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   double* ga = P.slab + 2LL * j * n * n;       /* A_i */
+   double* gm = ga + (long long) n * n;         /* M(mu) */
+   if ( tid == 0 )
+      ov_begin(P, j, &S);
+   __syncthreads();
+   if ( S.at == OV_DONE )
+   {
+      if ( tid == 0 )
+         ov_store(P, j, &S);
+      return;
+   }
+   const double* __restrict__ Z = P.blk != NULL ? P.blk->Z : P.Z;
+   ov_stage_a(P, j, (int) P.tab[(long long) j * HS_OV_TAB], ga);
+   for (int round = 0; round < P.maxevals; ++round)
+   {
+      const double s = S.mu - S.shift;
+      const int wantvec = S.wantvec;
+      for (int e = tid; e < n * n; e += EM_NT)
+         gm[e] = Z[e] + s * ga[e];
+      __syncthreads();                          /* (the slab is read by this workgroup alone: its own stores are visible behind the barrier) */
+      d_syevi_mid(n, 1, wantvec, gm, eo, 0ULL, NULL);
+      __syncthreads();
+      double g = 0.0;
+      if ( wantvec )
+      {
+         for (int e = tid; e < n * n; e += EM_NT)
+         {
+            const int r = e / n, c = e - r * n;
+            g += ga[e] * eo[1 + r] * eo[1 + c];
+         }
+         g = hs_wave_sum_dpp(g);
+         if ( lane == 0 )
+            part[wave] = g;
+         __syncthreads();
+      }
+      if ( tid == 0 )
+      {
+         double gs = 0.0;
+         if ( wantvec )
+            for (int w = 0; w < EM_NT / 64; ++w)
+               gs += part[w];
+         ov_decide(P, &S, eo[0], gs);
+      }
+      __syncthreads();
+      if ( S.at == OV_DONE )
+         break;
+   }
+   if ( tid == 0 )
+      ov_store(P, j, &S);
 }
 
 
@@ -1705,6 +1976,32 @@ int hs_lmin_exact_multi(hipStream_t st, const hs_step_jobs* P)
    HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_lmin_exact_multi), 3 * EI_N * EI_LD * (int) sizeof(double), &attr_done) );
    const size_t smem = (size_t) 3 * nmax * (nmax | 1) * sizeof(double);
    hipLaunchKernelGGL(k_lmin_exact_multi, dim3(2, P->nblk), dim3(256), smem, st, *P);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* the one-variable SDPs of a block, one workgroup per job (k_onevar_small / k_onevar_mid); slab: hs_onevar_slab(n, count) doubles */
+long long hs_onevar_slab(int n, int count) { return n > EI_N ? 2LL * n * n * count : 0; }
+
+int hs_onevar_newton(hipStream_t st, const hs_ov_par* P)
+{
+   if ( P->count <= 0 )
+      return HS_OK;
+   if ( P->n < 1 || P->n > EM_N || P->maxevals < 1 || P->tab == NULL || P->res == NULL || (P->blk == NULL && (P->Z == NULL || P->A == NULL))
+      || (P->n > EI_N && P->slab == NULL) )
+      return HS_ERR_ARG;
+   if ( P->n <= EI_N )
+   {
+      static hs_attr_mask attr_small;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_small), 3 * EI_N * EI_N * (int) sizeof(double), &attr_small) );
+      hipLaunchKernelGGL(k_onevar_small, dim3(P->count), dim3(256), (size_t) 3 * P->n * P->n * sizeof(double), st, *P);
+   }
+   else
+   {
+      static hs_attr_mask attr_mid;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
+      hipLaunchKernelGGL(k_onevar_mid, dim3(P->count), dim3(EM_NT), (size_t) P->n * (P->n | 1) * sizeof(double), st, *P);
+   }
    HS_HIP( hipGetLastError() );
    return HS_OK;
 }

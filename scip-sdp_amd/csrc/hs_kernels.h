@@ -357,6 +357,34 @@ struct hs_ec_job
 int hs_ec_form_z(hipStream_t st, int count, int nmax, int m, const hs_ec_job* jobs, const double* y);
 int hs_ec_cuts(hipStream_t st, int count, int nmax, int m, int nb, int maxcuts, double tol, const hs_ec_job* jobs, double* res);
 
+/* ---- eigi.hip: the one-variable SDPs of a block, one workgroup per job (hipsdp_onevar_bounds; host side: onevar.hip) ----------- */
+#define HS_OV_MAXN 128
+#define HS_OV_TAB 5        /* doubles of a job in the table: variable (0-based engine index), kind, lb, ub, shift u_i */
+#define HS_OV_RES 6        /* doubles of a job in the result: status, optval, lmin, grad, evals, 0 */
+/* blk != NULL: an entry of a job table in device memory - Z(u) at blk->Z, A_i from the block's storage form; blk == NULL: Z and the
+ * dense A + j n^2 of job j are given.  slab: 2 n^2 doubles per job when n > 64 (the dense A_i and M(mu)), else not used. */
+struct hs_ov_par
+{
+   int n, count, maxevals, pad;
+   double feastol, infinity;
+   const hs_ec_job* blk;
+   const double* Z; const double* A;
+   const double* tab;            /* [count][HS_OV_TAB] */
+   double* slab;
+   double* res;                  /* [count][HS_OV_RES] */
+};
+long long hs_onevar_slab(int n, int count);
+int hs_onevar_newton(hipStream_t st, const hs_ov_par* P);
+/* ipm.hip, for onevar.hip: what the call needs of a solver.  hs_solver_dims: 0 when s is NULL or has no shape, else 1 with the number
+ * of variables and blocks; hs_solver_block_n: rows of a block.  hs_solver_cut_job: *served = 0 (nothing else done) for a solver with a
+ * communicator or sharded matrices or a block without matrices on this device; else the device is set, staged entries are flushed,
+ * the workspace of the cut calls holds dev_len / pin_len doubles, and its job table is the block's hs_ec_job with Z at dev + zoff. */
+struct hipsdp_solver;
+struct hs_solver_cut_ws { hipStream_t stream; double* dev; double* pin; const hs_ec_job* djob; };
+int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks);
+int hs_solver_block_n(const hipsdp_solver* s, int block);
+int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, hs_solver_cut_ws* w, int* served);
+
 /* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
 #define HS_SC_MAXN 128
 struct hs_sc_par { double tol, feastol, convtol; int maxcuts, maxit; };      /* convtol > 0, maxit >= 1: the defaults are the caller's */

@@ -5815,6 +5815,44 @@ extern "C" int hipsdp_sparsecuts_ex(hipsdp_solver* s, int block, const double* y
    return sparsecuts_impl(s, block, y, size, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
 }
 
+/* ---- what hipsdp_onevar_bounds (csrc/onevar.hip) needs of a solver: its shape, and the block as the only job of the cut workspace -- */
+int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks)
+{
+   if ( s == NULL || !s->shaped )
+      return 0;
+   *m = s->m;
+   *nblocks = (int) s->blk.size();
+   return 1;
+}
+
+int hs_solver_block_n(const hipsdp_solver* s, int block)
+{
+   return s->blk[block].n;
+}
+
+int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, hs_solver_cut_ws* w, int* served)
+{
+   *served = 0;
+   if ( s->comm != NULL || s->shardA )
+      return HS_OK;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
+   const Block& B = s->blk[block];
+   if ( B.sparse ? (B.sp == NULL || B.A0 == NULL) : B.A == NULL )
+      return HS_OK;
+   CutWs& cw = s->cw;
+   HS_CALL( cw.grow(dev_len, pin_len, sizeof(hs_ec_job)) );
+   std::vector<hs_ec_job> job(1);
+   memset(&job[0], 0, sizeof(hs_ec_job));
+   ec_job_form(B, &job[0]);
+   job[0].Z = cw.dev + zoff;
+   HS_CALL( cw.upload(job, std::vector<hs_eig_job>()) );
+   w->stream = s->stream; w->dev = cw.dev; w->pin = cw.pin; w->djob = cw.djobs();
+   *served = 1;
+   return HS_OK;
+}
+
 /* host-only: the column ranges of the sharded W formulation, bounds[0 .. nranks] (rank g owns [bounds[g], bounds[g + 1])) */
 extern "C" int hipsdp_shard_columns(int m1, int n, int nranks, int* bounds)
 {

@@ -1510,6 +1510,53 @@ extern "C" int hipsdp_sparsecuts_unit(int device, int count, const int* ns, cons
    return HIPSDP_OK;
 }
 
+/* the Newton kernel of hipsdp_onevar_bounds alone (csrc/eigi.hip: k_onevar_small / k_onevar_mid) on host matrices: Z and one dense
+ * A per job */
+extern "C" int hipsdp_onevar_unit(int device, int n, int count, const double* Z, const double* A, const double* shift, const int* kind,
+   const double* lb, const double* ub, double feastol, int maxevals, int* status, double* optval, double* lmin, double* grad, int* evals)
+{
+   HS_CALL( pick_device(device) );
+   if ( n < 1 || n > HS_OV_MAXN || count < 1 || Z == NULL || A == NULL || shift == NULL || lb == NULL || ub == NULL || !(feastol >= 0.0)
+      || status == NULL || optval == NULL )
+      return HIPSDP_ERR_ARG;
+   const long long n2 = (long long) n * n;
+   std::vector<double> tab((size_t) count * HS_OV_TAB);
+   for (int j = 0; j < count; ++j)
+   {
+      if ( kind != NULL && kind[j] != HIPSDP_ONEVAR_NEWTON && kind[j] != HIPSDP_ONEVAR_TWOPOINT )
+         return HIPSDP_ERR_ARG;
+      double* t = tab.data() + (size_t) j * HS_OV_TAB;
+      t[0] = (double) j; t[1] = (double) (kind != NULL ? kind[j] : HIPSDP_ONEVAR_NEWTON); t[2] = lb[j]; t[3] = ub[j]; t[4] = shift[j];
+   }
+   DevBuf dz, da, dtab, dres, dslab;
+   HS_CALL( dz.alloc(n2) ); HS_CALL( da.alloc(n2 * count) ); HS_CALL( dtab.alloc((long long) tab.size()) );
+   HS_CALL( dres.alloc((long long) count * HS_OV_RES) );
+   if ( hs_onevar_slab(n, count) > 0 )
+      HS_CALL( dslab.alloc(hs_onevar_slab(n, count)) );
+   HS_CALL( dz.up(Z, n2) ); HS_CALL( da.up(A, n2 * count) ); HS_CALL( dtab.up(tab.data(), (long long) tab.size()) );
+   hs_ov_par P;
+   memset(&P, 0, sizeof(P));
+   P.n = n; P.count = count; P.maxevals = maxevals > 0 ? maxevals : 100;
+   P.feastol = feastol; P.infinity = 1e20;
+   P.Z = dz.p; P.A = da.p; P.tab = dtab.p; P.slab = dslab.p; P.res = dres.p;
+   HS_CALL( hs_onevar_newton(0, &P) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> h((size_t) count * HS_OV_RES);
+   HS_CALL( dres.down(h.data(), (long long) h.size()) );
+   for (int j = 0; j < count; ++j)
+   {
+      const double* r = h.data() + (size_t) j * HS_OV_RES;
+      if ( !(r[0] >= 0.0 && r[0] <= (double) HIPSDP_ONEVAR_GAVEUP) )
+         return HIPSDP_ERR_NUMERIC;
+      status[j] = (int) r[0];
+      optval[j] = r[1];
+      if ( lmin != NULL ) lmin[j] = r[2];
+      if ( grad != NULL ) grad[j] = r[3];
+      if ( evals != NULL ) evals[j] = (int) r[4];
+   }
+   return HIPSDP_OK;
+}
+
 /* k_sc_tpower_large alone (csrc/sparsecuts_large.hip) on one host matrix: lmin is given as -1 with tol = -infinity, so the matrix
  * takes part */
 extern "C" int hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, const double* v0, double maxeig, int size,
