@@ -1,0 +1,509 @@
+/* cut_calls.hip - the host side of the cut calls that serve many blocks, or one large block, in a fixed number of launches:
+ * hipsdp_eigencuts_all (kernels: eigcuts.hip, many-forms of the decompositions: eigi.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts
+ * (sparsecuts.hip, sparsecuts_large.hip) and their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip).
+ *
+ * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
+ * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
+ * copy-out of every block to the caller's arrays.  The solver itself is seen through the hs_solver_* functions of hs_kernels.h alone:
+ * they enter a call, grow the workspace and keep its job tables on the device (ipm.hip). */
+#include "hs_common.h"
+#include "hs_kernels.h"
+#include "hs_cut_plan.h"
+#include "hs_cut_stats.h"
+#include "../../include/hipsdp.h"
+#include <vector>
+#include <cstring>
+
+namespace {
+
+/* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, and the two _ex calls with a switch set */
+CutStats g_ec, g_sc, g_sc1, g_scx;
+
+/* the caller's arrays of a call, or of one block of it (all but ncuts may be NULL) */
+struct CutDst
+{
+   int* ncuts; double *lmin, *eigvals, *coefs, *lhs, *vecs; int *iters, *flags;
+   /* those of block b of a call over all blocks, its vectors from voff on */
+   CutDst block(int b, int maxcuts, int m, long long voff) const
+   {
+      const size_t slot = (size_t) b * maxcuts;
+      return CutDst{ncuts + b, lmin != NULL ? lmin + b : NULL, eigvals + slot, coefs + slot * m, lhs + slot, vecs != NULL ? vecs + voff : NULL,
+         iters != NULL ? iters + b : NULL, flags != NULL ? flags + b : NULL};
+   }
+};
+
+bool variant_ok(unsigned variant)
+{
+   return variant <= (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS);
+}
+
+/* where the vectors of block b start in the result, [nb]: their total length - maxcuts vectors per block, or of block `only` alone */
+std::vector<long long> cut_vecoff(const hipsdp_solver* s, int nb, int maxcuts, int only)
+{
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+      vecoff[b + 1] = vecoff[b] + (only < 0 || b == only ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
+   return vecoff;
+}
+
+/* Z and the decomposition workspace of every block of a round */
+long long ec_slab_len(const hipsdp_solver* s, const std::vector<int>& ids)
+{
+   long long len = 0;
+   for (int b : ids)
+      len += hs_cut_mat_len(hs_solver_block_n(s, b)) + hs_syev_small_scratch(hs_solver_block_n(s, b));
+   return len;
+}
+
+/* the k cuts of one block of n rows - first slot `slot`, vectors from `voff` on - from a host view to the caller's arrays (vecs may be NULL) */
+void cut_copy_out(const hs_sc_out& h, size_t slot, long long voff, int k, int m, int n, double* eigvals, double* lhs, double* coefs,
+   double* vecs)
+{
+   if ( k <= 0 )
+      return;
+   memcpy(eigvals, h.eig + slot, (size_t) k * sizeof(double));
+   memcpy(lhs, h.lhs + slot, (size_t) k * sizeof(double));
+   if ( m > 0 )
+      memcpy(coefs, h.coef + slot * m, (size_t) k * m * sizeof(double));
+   if ( vecs != NULL )
+      memcpy(vecs, h.vec + voff, (size_t) k * n * sizeof(double));
+}
+
+/* block b (n rows, k cuts, vectors from voff on) of a read-back view to the caller's arrays of that block */
+int cut_block_out(const hs_sc_out& h, int b, int k, int maxcuts, long long voff, int m, int n, const CutDst& d)
+{
+   if ( k < 0 || k > maxcuts )
+      return HIPSDP_ERR_NUMERIC;
+   *d.ncuts = k;
+   if ( d.lmin != NULL ) *d.lmin = h.lmin[b];
+   if ( d.iters != NULL ) *d.iters = h.iters[b];
+   if ( d.flags != NULL ) *d.flags = h.flags[b];
+   cut_copy_out(h, (size_t) b * maxcuts, voff, k, m, n, d.eigvals, d.lhs, d.coefs, d.vecs);
+   return HIPSDP_OK;
+}
+
+void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
+{
+   par->tol = opts->tol; par->feastol = opts->feastol;
+   par->convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
+   par->maxcuts = opts->maxcuts;
+   par->maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
+}
+
+/* hs_syev_small_many as THREE launches whatever classes the jobs fall into: a class without jobs gets an empty launch */
+int scx_syev(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* djobs, int* launches)
+{
+   int mine = 0;
+   HS_CALL( hs_syev_small_many(st, count, hjobs, djobs, &mine) );
+   HS_CALL( hs_scr_pad(st, 3 - mine) );
+   *launches += 3;
+   return HS_OK;
+}
+
+/* the tables of the rounds over the blocks `ids`, whose Z_S have ns[j] rows and whose states start at `cur` in the workspace */
+int scx_tables(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<int>& ns, double* cur, hs_solver_cut_ws* w)
+{
+   const int nj = (int) ids.size();
+   std::vector<hs_scr_job> xj((size_t) nj);
+   std::vector<hs_eig_job> sj;
+   for (int j = 0; j < nj; ++j)
+   {
+      hs_scr_job& X = xj[j];
+      memset(&X, 0, sizeof(X));
+      const hs_scr_block B = hs_scr_block_make(hs_solver_block_n(s, ids[j]), ns[j], hs_syev_small_scratch(ns[j]));
+      X.st = reinterpret_cast<hs_scr_state*>(cur + B.st);
+      X.v0 = cur + B.v0;
+      X.ZS = cur + B.ZS;
+      X.wsS = cur + B.wsS;
+      X.vposS = hs_syev_many_vecpos(ns[j]);
+      cur += B.len;
+   }
+   for (int cls = 0; cls < 3; ++cls)
+      for (int j = 0; j < nj; ++j)
+         if ( hs_syev_many_class(ns[j]) == cls )
+         {
+            hs_eig_job E;
+            memset(&E, 0, sizeof(E));
+            E.n = ns[j]; E.in = xj[j].ZS; E.ws = xj[j].wsS;
+            sj.push_back(E);
+         }
+   return hs_solver_cut_rounds(s, xj, sj, w);
+}
+
+/* a round of sc_round between its two ends: the workspace, what the launches take, the launches so far */
+struct ScRun
+{
+   hs_solver_cut_ws w;
+   hs_cut_res r;                 /* the result arrays: on w.dev what the launches write (out), on w.pin what the copy-out reads */
+   hs_cut_lens len;
+   hs_sc_out out;
+   hs_sc_par par;
+   const int* dsizes;
+   int nj, nmax, m, maxcuts, launches;
+};
+
+/* The head of a round over the served blocks `ids` (ordered by decomposition class; sizes[nb]: the target sparsity of every block of the
+ * solver): the layout - with `rounds` that of the refinement rounds, whose two further tables are uploaded as well -, the job tables,
+ * y | sizes  in the pinned mirror, the ONE upload, Z(y). */
+int sc_begin(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   const std::vector<long long>& vecoff, bool rounds, ScRun* R)
+{
+   const int maxcuts = opts->maxcuts, nj = (int) ids.size();
+   /* the largest support a served block can have: the pitch of the support lists */
+   int smax = 1;
+   for (int b : ids)
+      if ( sizes[b] <= hs_solver_block_n(s, b) && sizes[b] > smax )
+         smax = sizes[b];
+   hs_scr_layout L;
+   std::vector<int> ns;
+   if ( !rounds )
+   {
+      hs_sc_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), &L.sc);
+      L.len = L.sc.len;
+   }
+   else
+   {
+      /* rows of the blocks' Z_S; a block whose size exceeds its rows gets no cut, its job is a matrix of one row */
+      ns.resize((size_t) nj);
+      long long state_len = 0;
+      for (int j = 0; j < nj; ++j)
+      {
+         const int n = hs_solver_block_n(s, ids[j]);
+         ns[j] = sizes[ids[j]] <= n ? sizes[ids[j]] : 1;
+         state_len += hs_scr_block_make(n, ns[j], hs_syev_small_scratch(ns[j])).len;
+      }
+      hs_scr_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), state_len, &L);
+   }
+   HS_CALL( hs_solver_cut_prepare(s, ids, vecoff, L.sc.slabs, L.len, &R->nmax, &R->w) );
+   if ( rounds )
+      HS_CALL( scx_tables(s, ids, ns, R->w.dev + L.state, &R->w) );
+   const hs_solver_cut_ws& w = R->w;
+   R->r = L.sc.r; R->len = L.len;
+   R->out = hs_cut_view(L.sc.r, w.dev);
+   sc_par_from_opts(opts, &R->par);
+   R->dsizes = reinterpret_cast<const int*>(w.dev + L.sc.sizes);
+   R->nj = nj; R->m = m; R->maxcuts = maxcuts;
+   if ( m > 0 )
+      memcpy(w.pin + L.sc.y, y, (size_t) m * sizeof(double));
+   memcpy(w.pin + L.sc.sizes, sizes, (size_t) nb * sizeof(int));
+   HS_HIP( hipMemcpyAsync(w.dev + L.sc.y, w.pin + L.sc.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, w.stream) );
+   HS_CALL( hs_ec_form_z(w.stream, nj, R->nmax, m, w.djobs, w.dev + L.sc.y) );
+   R->launches = 1;
+   return HS_OK;
+}
+
+/* the tail of a round: with maxcuts > 0 the coefficients, then the ONE read-back; h: its view in the pinned mirror */
+int sc_finish(ScRun& R, CutStats* stats, hs_sc_out* h)
+{
+   const hs_solver_cut_ws& w = R.w;
+   if ( R.maxcuts > 0 )
+   {
+      HS_CALL( hs_sc_coefs(w.stream, R.nj, R.m, R.maxcuts, w.djobs, R.dsizes, &R.out) );
+      ++R.launches;
+   }
+   HS_HIP( hipMemcpyAsync(w.pin + R.len.res_off, w.dev + R.len.res_off, (size_t) R.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
+         w.stream) );
+   HS_HIP( hipStreamSynchronize(w.stream) );
+   stats->launches += R.launches;
+   stats->readbacks += 1;
+   *h = hs_cut_view(R.r, w.pin);
+   return HS_OK;
+}
+
+/* The launches of a round with a switch set (variant: HS_SCR_* bits, != 0) between sc_begin and sc_finish: the decompositions of Z(y),
+ * then maxcuts + 1 rounds - a TPower run of every block; with HS_SCR_SPARSEEV the decompositions of the Z_S and the cut behind them,
+ * without it the cut inside the TPower launch; with HS_SCR_INITIAL or HS_SCR_EXACTTRANS the decompositions of the deflated Z.  The
+ * last round cannot produce a cut (a block that is still running has maxcuts of them), so it is its TPower launch alone.  With s = 1
+ * for HS_SCR_SPARSEEV and d = 1 for one of the other two, a call takes 4 + maxcuts (1 + 4 s + 3 d) + 1 launches and one more for the
+ * coefficients when maxcuts > 0, whatever the blocks are. */
+int scx_rounds(ScRun& R, unsigned variant)
+{
+   const hs_solver_cut_ws& w = R.w;
+   hipStream_t st = w.stream;
+   HS_CALL( scx_syev(st, R.nj, w.ejobs, w.dejobs, &R.launches) );
+   for (int round = 0; round <= R.maxcuts; ++round)
+   {
+      HS_CALL( hs_scr_tpower(st, R.nj, R.nmax, w.djobs, w.dxjobs, R.dsizes, &R.par, variant, round, &R.out) );
+      ++R.launches;
+      if ( round == R.maxcuts )
+         break;
+      if ( variant & HS_SCR_SPARSEEV )
+      {
+         HS_CALL( scx_syev(st, R.nj, w.sjobs, w.dsjobs, &R.launches) );
+         HS_CALL( hs_scr_cut(st, R.nj, w.djobs, w.dxjobs, R.dsizes, &R.par, &R.out) );
+         ++R.launches;
+      }
+      if ( variant & (HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
+         HS_CALL( scx_syev(st, R.nj, w.ejobs, w.dejobs, &R.launches) );
+   }
+   return HS_OK;
+}
+
+/* The round of the served blocks `ids`: Z(y), the decompositions, TPower - with a switch set the rounds of scx_rounds in their place,
+ * booked under g_scx instead of stats0 - and, with maxcuts > 0, the coefficients, all enqueued on the solver's stream and followed by
+ * ONE read-back.  The result block is indexed by the block's number whatever `ids` holds, so a round over one block computes that
+ * block's bits of the round over all. */
+int sc_round(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, const std::vector<long long>& vecoff, CutStats* stats0, hs_sc_out* h)
+{
+   ScRun R;
+   HS_CALL( sc_begin(s, m, nb, ids, y, sizes, opts, vecoff, variant != 0, &R) );
+   if ( variant != 0 )
+      HS_CALL( scx_rounds(R, variant) );
+   else
+   {
+      HS_CALL( hs_syev_small_many(R.w.stream, R.nj, R.w.ejobs, R.w.dejobs, &R.launches) );
+      HS_CALL( hs_sc_tpower(R.w.stream, R.nj, R.nmax, R.w.djobs, R.dsizes, &R.par, &R.out) );
+      ++R.launches;
+   }
+   return sc_finish(R, variant == 0 ? stats0 : &g_scx, h);
+}
+
+/* hipsdp_sparsecuts_all (variant = 0) and hipsdp_sparsecuts_all_ex with a switch set */
+int sparsecuts_all_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   const CutDst& d)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || sizes == NULL || opts == NULL || d.ncuts == NULL || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   const int maxcuts = opts->maxcuts;
+   if ( maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      if ( sizes[b] < 1 )
+         return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      d.ncuts[b] = -1;
+   std::vector<int> ids;
+   HS_CALL( hs_solver_cut_enter(s, -1, &ids) );
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, -1);
+   if ( !ids.empty() )
+   {
+      hs_sc_out h;
+      HS_CALL( sc_round(s, m, nb, ids, y, sizes, opts, variant, vecoff, &g_sc, &h) );
+      for (int b : ids)
+         HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, vecoff[b])) );
+   }
+   ++(variant == 0 ? g_sc : g_scx).calls;
+   return HIPSDP_OK;
+}
+
+/* a block of at most 128 rows: the round of hipsdp_sparsecuts_all with this block as the only job, the same bits */
+int sparsecuts_small(hipsdp_solver* s, int m, int nb, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   const CutDst& d, int* served)
+{
+   std::vector<int> ids;
+   HS_CALL( hs_solver_cut_enter(s, block, &ids) );
+   *served = !ids.empty();
+   if ( !*served )
+      return HIPSDP_OK;
+   const int maxcuts = opts->maxcuts;
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, block);      /* only this block has vectors */
+   std::vector<int> sizes((size_t) nb, 1);
+   sizes[block] = size;
+   hs_sc_out h;
+   HS_CALL( sc_round(s, m, nb, ids, y, sizes.data(), opts, variant, vecoff, &g_sc1, &h) );
+   return cut_block_out(h, block, h.ncuts[block], maxcuts, vecoff[block], m, hs_solver_block_n(s, block), d);
+}
+
+/* a block of 129 .. 512 rows: Z(y), ONE tridiagonalisation, (lmin, v0) and maxeig from it, TPower in one workgroup, coefficients -
+ * n + 7 launches (n + 2 with maxcuts == 0) and one read-back.  The workspace is that of the calls above: it only grows. */
+int sparsecuts_large(hipsdp_solver* s, int m, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, const CutDst& d,
+   int* served)
+{
+   const int maxcuts = opts->maxcuts, n = hs_solver_block_n(s, block);
+   hs_scl_layout L;
+   hs_scl_layout_make(n, m, maxcuts, size <= n ? size : 1, (long long) hs_syevx_ws(n), HS_SYEVX_OUT(n), HS_SYEVX_OUT_VEC, &L);
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_job(s, block, L.len.dev_len, L.len.pin_len, L.Z, L.ws, &w, served) );
+   if ( !*served )
+      return HIPSDP_OK;
+   hipStream_t st = w.stream;
+   double *dy = w.dev + L.y, *dZ = w.dev + L.Z, *dws = w.dev + L.ws, *o1 = w.dev + L.o1, *o2 = w.dev + L.o2;
+   const hs_sc_out out = hs_cut_view(L.r, w.dev);
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   int launches = 0;
+   if ( m > 0 )
+   {
+      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+      HS_HIP( hipMemcpyAsync(dy, w.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   }
+   HS_CALL( hs_ec_form_z(st, 1, n, m, w.djobs, dy) );
+   ++launches;
+   HS_CALL( hs_syevx_tridiag_dev(st, n, dZ, dws) );
+   launches += n;
+   /* the one read-back: the result block, or with maxcuts = 0 the head of the first request's output (its eigenvalue) */
+   double* hres = w.pin + L.len.res_off;
+   const double* dres = w.dev + L.len.res_off;
+   long long reslen = L.len.res_len;
+   if ( maxcuts == 0 )
+   {
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, o1, dws) );
+      ++launches;
+      dres = o1; reslen = HS_SYEVX_OUT_VEC;
+   }
+   else
+   {
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
+      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
+      HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, w.dev + L.MT, &par, &out) );
+      HS_CALL( hs_scl_coefs(st, m, maxcuts, size, w.djobs, &out) );
+      launches += 3 + 1 + 1 + 1;
+   }
+   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_sc1.launches += launches;
+   g_sc1.readbacks += 1;
+   if ( maxcuts == 0 )
+   {
+      *d.ncuts = 0;
+      if ( d.lmin != NULL ) *d.lmin = hres[HS_SYEVX_OUT_LAM];
+      if ( d.iters != NULL ) *d.iters = 0;
+      if ( d.flags != NULL ) *d.flags = 0;
+      return HIPSDP_OK;
+   }
+   const hs_sc_out h = hs_cut_view(L.r, w.pin);
+   return cut_block_out(h, 0, h.ncuts[0], maxcuts, 0, m, n, d);
+}
+
+/* hipsdp_sparsecuts (variant = 0, booked under g_sc1) and hipsdp_sparsecuts_ex with a switch set: blocks of at most 128 rows */
+int sparsecuts_impl(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant, const CutDst& d)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || block < 0 || block >= nb || y == NULL || opts == NULL || d.ncuts == NULL || size < 1
+      || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( opts->maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   const int n = hs_solver_block_n(s, block);
+   *d.ncuts = -1;
+   if ( n > (variant == 0 ? HIPSDP_SPARSECUTS_MAXN : HS_SC_MAXN) )
+      return HIPSDP_OK;
+   /* not served (nothing else done): a solver with a communicator or sharded matrices, a block without matrices on this device */
+   int served = 0;
+   if ( n <= HS_SC_MAXN )
+      HS_CALL( sparsecuts_small(s, m, nb, block, y, size, opts, variant, d, &served) );
+   else
+      HS_CALL( sparsecuts_large(s, m, block, y, size, opts, d, &served) );
+   if ( served )
+      ++(variant == 0 ? g_sc1 : g_scx).calls;
+   return HIPSDP_OK;
+}
+
+}
+
+extern "C" int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_ec.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_sc.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_sc1.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_scx.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
+   double* coefs, double* lhs, double* vecs)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || ncuts == NULL || maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      ncuts[b] = 0;
+   std::vector<int> ids;
+   HS_CALL( hs_solver_cut_enter(s, -1, &ids) );
+   const CutDst dst = {ncuts, lmin, eigvals, coefs, lhs, vecs, NULL, NULL};
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, -1);
+   const int nj = (int) ids.size();
+   std::vector<char> served((size_t) nb, 0);
+   if ( nj > 0 )
+   {
+      hs_ec_layout L;
+      hs_ec_layout_make(nb, m, maxcuts, vecoff[nb], ec_slab_len(s, ids), &L);
+      int nmax = 0;
+      hs_solver_cut_ws w;
+      HS_CALL( hs_solver_cut_prepare(s, ids, vecoff, L.slabs, L.len, &nmax, &w) );
+      hipStream_t st = w.stream;
+      double* dy = w.dev + L.y;
+      int launches = 0;
+      if ( m > 0 )
+      {
+         memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+         HS_HIP( hipMemcpyAsync(dy, w.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+      }
+      HS_CALL( hs_ec_form_z(st, nj, nmax, m, w.djobs, dy) );
+      ++launches;
+      HS_CALL( hs_syev_small_many(st, nj, w.ejobs, w.dejobs, &launches) );
+      HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, w.djobs, w.dev + L.len.res_off) );
+      ++launches;
+      HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
+            st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      g_ec.launches += launches;
+      g_ec.readbacks += 1;
+      const hs_sc_out h = hs_cut_view(L.r, w.pin);
+      for (int b : ids)
+      {
+         const int k = (int) w.pin[L.ncuts + b], n = hs_solver_block_n(s, b);
+         if ( k > n )
+            return HIPSDP_ERR_NUMERIC;
+         HS_CALL( cut_block_out(h, b, k, maxcuts, vecoff[b], m, n, dst.block(b, maxcuts, m, vecoff[b])) );
+         served[b] = 1;
+      }
+   }
+   /* every other block: the per-block path, inside the same call */
+   for (int b = 0; b < nb; ++b)
+   {
+      if ( served[b] )
+         continue;
+      const CutDst d = dst.block(b, maxcuts, m, vecoff[b]);
+      double l0 = 0.0;
+      HS_CALL( hs_solver_eigencuts_block(s, b, y, tol, maxcuts, d.ncuts, maxcuts > 0 ? d.eigvals : NULL, maxcuts > 0 ? d.coefs : NULL,
+            maxcuts > 0 ? d.lhs : NULL, d.vecs, &l0) );
+      if ( d.lmin != NULL )
+         *d.lmin = l0;
+   }
+   ++g_ec.calls;
+   return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   return sparsecuts_all_impl(s, y, sizes, opts, 0, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}
+
+extern "C" int hipsdp_sparsecuts_all_ex(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( !variant_ok(variant) )
+      return HIPSDP_ERR_ARG;
+   return sparsecuts_all_impl(s, y, sizes, opts, variant, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}
+
+extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
+   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   return sparsecuts_impl(s, block, y, size, opts, 0, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}
+
+extern "C" int hipsdp_sparsecuts_ex(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( !variant_ok(variant) )
+      return HIPSDP_ERR_ARG;
+   return sparsecuts_impl(s, block, y, size, opts, variant, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}

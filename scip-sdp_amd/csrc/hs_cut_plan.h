@@ -1,4 +1,4 @@
-/* hs_cut_plan.h - where everything lies in the workspace of the cut calls of csrc/ipm.hip (hipsdp_eigencuts_all, hipsdp_sparsecuts_all,
+/* hs_cut_plan.h - where everything lies in the workspace of the cut calls of csrc/cut_calls.hip (hipsdp_eigencuts_all, hipsdp_sparsecuts_all,
  * hipsdp_sparsecuts): one layout per call form, written down once.  All offsets and lengths count doubles from the start of the device
  * workspace; the pinned host buffer mirrors its head (upload and read-back lie at the same offsets), so ONE view function gives the
  * pointers the launches take (applied to the device buffer) and the pointers the copy-out reads (applied to the pinned one).

@@ -6,6 +6,7 @@
 
 #include "hs_common.h"
 #include "hs_cut_plan.h"
+#include <vector>
 
 /* ---- kernels.hip ---------------------------------------------------------------------------------------------- */
 int hs_fill(hipStream_t s, double* p, long long n, double v);
@@ -375,15 +376,6 @@ struct hs_ov_par
 };
 long long hs_onevar_slab(int n, int count);
 int hs_onevar_newton(hipStream_t st, const hs_ov_par* P);
-/* ipm.hip, for onevar.hip: what the call needs of a solver.  hs_solver_dims: 0 when s is NULL or has no shape, else 1 with the number
- * of variables and blocks; hs_solver_block_n: rows of a block.  hs_solver_cut_job: *served = 0 (nothing else done) for a solver with a
- * communicator or sharded matrices or a block without matrices on this device; else the device is set, staged entries are flushed,
- * the workspace of the cut calls holds dev_len / pin_len doubles, and its job table is the block's hs_ec_job with Z at dev + zoff. */
-struct hipsdp_solver;
-struct hs_solver_cut_ws { hipStream_t stream; double* dev; double* pin; const hs_ec_job* djob; };
-int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks);
-int hs_solver_block_n(const hipsdp_solver* s, int block);
-int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, hs_solver_cut_ws* w, int* served);
 
 /* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
 #define HS_SC_MAXN 128
@@ -420,6 +412,39 @@ int hs_scl_tpower(hipStream_t st, int n, int size, const double* Z, const double
    const hs_sc_par* par, const hs_sc_out* out);
 /* grid (m + 1): x_c^T A_i x_c of every cut of job[0] (its blk and vecoff are 0) in any of the three storage forms */
 int hs_scl_coefs(hipStream_t st, int m, int maxcuts, int size, const hs_ec_job* job, const hs_sc_out* out);
+
+/* ---- ipm.hip: what the cut calls (cut_calls.hip) and hipsdp_onevar_bounds (onevar.hip) need of a solver, whose definition they do not see --
+ * hs_solver_dims: 0 when s is NULL or has no shape, else 1 with the number of variables and blocks; hs_solver_block_n: rows of a block.
+ * hs_solver_cut_enter: the device is set, staged entries are flushed, the packed triangles and the device form of blocks kept as
+ *    nonzeros are up to date; ids: the blocks whose round runs in the shared launches (the whole matrices on this device, at most 128
+ *    rows), ordered by decomposition class - none for a solver with a communicator or sharded matrices.  only >= 0: that block alone,
+ *    if it is one of them, and such a solver is not touched at all.
+ * hs_solver_cut_prepare: the workspace of the cut calls holds len.dev_len / len.pin_len doubles, and the job tables of a round over ids
+ *    (vecoff[block]: where a block's vectors start in the result; Z and decomposition slab of every job from dev + slabs on) are on
+ *    the device, uploaded only when they differ from what it holds; nmax: the largest block of the round.
+ * hs_solver_cut_rounds: the same for the two further tables of sparsecuts_rounds.hip (fills dxjobs, dsjobs, sjobs of w alone).
+ * hs_solver_cut_job: *served = 0 (nothing else done) for a solver with a communicator or sharded matrices or a block without matrices
+ *    on this device; else as hs_solver_cut_enter, the workspace holds dev_len / pin_len doubles, and its job table is the block's
+ *    hs_ec_job with Z at dev + zoff and ws at dev + wsoff (wsoff < 0: none).
+ * hs_solver_eigencuts_block: hipsdp_eigencuts behind its argument checks (maxcuts may be 0), lam0: the block's first eigenvalue. */
+struct hipsdp_solver;
+struct hs_solver_cut_ws
+{
+   hipStream_t stream; double* dev; double* pin;
+   const hs_ec_job* djobs; const hs_eig_job* dejobs;        /* the tables on the device */
+   const hs_eig_job* ejobs;                                 /* the host copy hs_syev_small_many wants, valid until the next prepare */
+   const hs_scr_job* dxjobs; const hs_eig_job* dsjobs; const hs_eig_job* sjobs;      /* the same of the rounds */
+};
+int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks);
+int hs_solver_block_n(const hipsdp_solver* s, int block);
+int hs_solver_cut_enter(hipsdp_solver* s, int only, std::vector<int>* ids);
+int hs_solver_cut_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long slabs,
+   const hs_cut_lens& len, int* nmax, hs_solver_cut_ws* w);
+int hs_solver_cut_rounds(hipsdp_solver* s, const std::vector<hs_scr_job>& xjobs, const std::vector<hs_eig_job>& sjobs, hs_solver_cut_ws* w);
+int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, long long wsoff, hs_solver_cut_ws* w,
+   int* served);
+int hs_solver_eigencuts_block(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
+   double* coefs, double* lhs, double* vecs, double* lam0);
 
 /* Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix A (destroyed): eigenvalues ascending in lam[n],
  * eigenvectors as rows of V (row k = k-th eigenvector).  info (device int) = sweeps used or -1. */

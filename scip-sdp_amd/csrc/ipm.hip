@@ -111,7 +111,7 @@ struct PhaseClock
    double ms[PH_COUNT];
 };
 
-/* The workspace of the cut calls (hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts; layouts: hs_cut_plan.h), grow-only and
+/* The workspace of the cut calls (csrc/cut_calls.hip, csrc/onevar.hip; layouts: hs_cut_plan.h), grow-only and
  * kept until hipsdp_free: the device buffer, its pinned host mirror (upload and read-back), the job tables on the device (the hs_ec_job
  * of a round and behind them their hs_eig_job) and the host copies they were uploaded from. */
 struct CutWs
@@ -173,6 +173,13 @@ struct CutWs
    }
    const hs_scr_job* dxjobs() const { return reinterpret_cast<const hs_scr_job*>(rtab); }
    const hs_eig_job* dsjobs() const { return reinterpret_cast<const hs_eig_job*>(rtab + xjobs.size() * sizeof(hs_scr_job)); }
+   /* what a cut call works with (hs_kernels.h): the buffers and the tables of `upload`, those of the rounds unset */
+   void view(hipStream_t st, hs_solver_cut_ws* w) const
+   {
+      memset(w, 0, sizeof(*w));
+      w->stream = st; w->dev = dev; w->pin = pin;
+      w->djobs = djobs(); w->dejobs = dejobs(); w->ejobs = ejobs.data();
+   }
    void release()
    {
       if ( dev != NULL ) (void) hipFree(dev);
@@ -275,7 +282,7 @@ struct hipsdp_solver
    int s1_last;            /* 1: the last solve ran in the single launch */
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
-   CutWs cw;               /* hipsdp_eigencuts_all (csrc/eigcuts.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts (csrc/sparsecuts*.hip) */
+   CutWs cw;               /* the calls of csrc/cut_calls.hip and csrc/onevar.hip, through hs_solver_cut_* below */
    /* the first assembly of a cold solve, kept across solves of the same matrices (hs_gram_cache.h; GeneralSolve::assemble_forms):
     * gc_M holds (m1 + 32) m1 doubles as the identity assemblies left them in Mx, gc_key says of what.  Allocated at the first cold
     * solve that qualifies (gc_nomem: that failed for this shape, not tried again), freed with the problem. */
@@ -5244,40 +5251,32 @@ extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, do
    return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, NULL);
 }
 
-/* ---- all blocks in one call (kernels: csrc/eigcuts.hip, many-forms of the decompositions: csrc/eigi.hip) ---------------------- */
-/* calls served, and their launches and read-backs: hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts */
-struct CutStats
+/* ---- what the cut calls of many blocks (csrc/cut_calls.hip) and hipsdp_onevar_bounds (csrc/onevar.hip) need of a solver: its shape, the
+ * blocks their shared launches serve, the cut workspace with its job tables, the per-block path (declared in hs_kernels.h) ------------ */
+int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks)
 {
-   std::atomic<long long> calls{0}, launches{0}, readbacks{0};
-   int get(long long* c, long long* l, long long* r) const
-   {
-      if ( c != NULL ) *c = calls.load();
-      if ( l != NULL ) *l = launches.load();
-      if ( r != NULL ) *r = readbacks.load();
-      return HIPSDP_OK;
-   }
-};
-static CutStats g_ec, g_sc, g_sc1;
-
-extern "C" int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks)
-{
-   return g_ec.get(calls, launches, readbacks);
+   if ( s == NULL || !s->shaped )
+      return 0;
+   *m = s->m;
+   *nblocks = (int) s->blk.size();
+   return 1;
 }
 
-extern "C" int hipsdp_sparsecuts_all_stats(long long* calls, long long* launches, long long* readbacks)
+int hs_solver_block_n(const hipsdp_solver* s, int block)
 {
-   return g_sc.get(calls, launches, readbacks);
+   return s->blk[block].n;
 }
 
-extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, long long* readbacks)
+/* the whole matrices of the block are on this device */
+static bool ec_has_matrices(const Block& B)
 {
-   return g_sc1.get(calls, launches, readbacks);
+   return B.sparse ? (B.sp != NULL && B.A0 != NULL) : B.A != NULL;
 }
 
 /* a block whose round runs in the shared launches: the whole matrices are on this device and k_syev_mid holds the block */
 static bool ec_batched(const hipsdp_solver* s, const Block& B)
 {
-   return s->comm == NULL && !s->shardA && B.n <= 128 && (B.sparse ? (B.sp != NULL && B.A0 != NULL) : B.A != NULL);
+   return s->comm == NULL && !s->shardA && B.n <= 128 && ec_has_matrices(B);
 }
 
 /* the batched blocks, in the order of the decomposition's classes */
@@ -5291,23 +5290,19 @@ static std::vector<int> ec_batched_ids(const hipsdp_solver* s)
    return ids;
 }
 
-/* where the vectors of block b start in the result, [nb]: their total length - maxcuts vectors per block, or of block `only` alone */
-static std::vector<long long> cut_vecoff(const hipsdp_solver* s, int maxcuts, int only)
+int hs_solver_cut_enter(hipsdp_solver* s, int only, std::vector<int>* ids)
 {
-   const size_t nb = s->blk.size();
-   std::vector<long long> vecoff(nb + 1, 0);
-   for (size_t b = 0; b < nb; ++b)
-      vecoff[b + 1] = vecoff[b] + (only < 0 || (int) b == only ? (long long) maxcuts * s->blk[b].n : 0);
-   return vecoff;
-}
-
-/* Z and the decomposition workspace of every block of a round */
-static long long ec_slab_len(const hipsdp_solver* s, const std::vector<int>& ids)
-{
-   long long len = 0;
-   for (int b : ids)
-      len += hs_cut_mat_len(s->blk[b].n) + hs_syev_small_scratch(s->blk[b].n);
-   return len;
+   ids->clear();
+   if ( only >= 0 && (s->comm != NULL || s->shardA) )
+      return HS_OK;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
+   if ( only < 0 )
+      *ids = ec_batched_ids(s);
+   else if ( ec_batched(s, s->blk[only]) )
+      ids->assign(1, only);
+   return HS_OK;
 }
 
 /* the storage form the kernels read the block's matrices in (J zeroed by the caller) */
@@ -5332,8 +5327,8 @@ static void ec_job_form(const Block& B, hs_ec_job* J)
 
 /* The workspace (lengths of the call's layout, its slabs from offset `slabs` on) and the job tables of a round over the batched blocks
  * `ids` (ordered by decomposition class); nmax_out: their largest n */
-static int ec_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long slabs,
-   const hs_cut_lens& len, int* nmax_out)
+int hs_solver_cut_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long slabs,
+   const hs_cut_lens& len, int* nmax_out, hs_solver_cut_ws* w)
 {
    const int nj = (int) ids.size();
    HS_CALL( s->cw.grow(len.dev_len, len.pin_len, (size_t) nj * (sizeof(hs_ec_job) + sizeof(hs_eig_job))) );
@@ -5358,479 +5353,19 @@ static int ec_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::
    }
    HS_CALL( s->cw.upload(jobs, ejobs) );
    *nmax_out = nmax;
+   s->cw.view(s->stream, w);
    return HS_OK;
 }
 
-/* the k cuts of one block of n rows - first slot `slot`, vectors from `voff` on - from a host view to the caller's arrays (vecs may be NULL) */
-static void cut_copy_out(const hs_sc_out& h, size_t slot, long long voff, int k, int m, int n, double* eigvals, double* lhs, double* coefs,
-   double* vecs)
+int hs_solver_cut_rounds(hipsdp_solver* s, const std::vector<hs_scr_job>& xjobs, const std::vector<hs_eig_job>& sjobs, hs_solver_cut_ws* w)
 {
-   if ( k <= 0 )
-      return;
-   memcpy(eigvals, h.eig + slot, (size_t) k * sizeof(double));
-   memcpy(lhs, h.lhs + slot, (size_t) k * sizeof(double));
-   if ( m > 0 )
-      memcpy(coefs, h.coef + slot * m, (size_t) k * m * sizeof(double));
-   if ( vecs != NULL )
-      memcpy(vecs, h.vec + voff, (size_t) k * n * sizeof(double));
-}
-
-extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
-   double* coefs, double* lhs, double* vecs)
-{
-   if ( s == NULL || !s->shaped || y == NULL || ncuts == NULL || maxcuts < 0 )
-      return HIPSDP_ERR_ARG;
-   if ( maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
-      return HIPSDP_ERR_ARG;
-   const int nb = (int) s->blk.size(), m = s->m;
-   for (int b = 0; b < nb; ++b)
-      ncuts[b] = 0;
-   HS_HIP( hipSetDevice(s->device) );
-   HS_CALL( stage_sync(s) );
-   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
-   hipStream_t st = s->stream;
-   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, -1);
-   const std::vector<int> ids = ec_batched_ids(s);
-   const int nj = (int) ids.size();
-   std::vector<char> served((size_t) nb, 0);
-   if ( nj > 0 )
-   {
-      hs_ec_layout L;
-      hs_ec_layout_make(nb, m, maxcuts, vecoff[nb], ec_slab_len(s, ids), &L);
-      int nmax = 0;
-      HS_CALL( ec_prepare(s, ids, vecoff, L.slabs, L.len, &nmax) );
-      CutWs& cw = s->cw;
-      double* dy = cw.dev + L.y;
-      int launches = 0;
-      if ( m > 0 )
-      {
-         memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
-         HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
-      }
-      HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
-      ++launches;
-      HS_CALL( hs_syev_small_many(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
-      HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, cw.djobs(), cw.dev + L.len.res_off) );
-      ++launches;
-      HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
-            st) );
-      HS_HIP( hipStreamSynchronize(st) );
-      g_ec.launches += launches;
-      g_ec.readbacks += 1;
-      const hs_sc_out h = hs_cut_view(L.r, cw.pin);
-      for (int b : ids)
-      {
-         const int k = (int) cw.pin[L.ncuts + b];
-         if ( k < 0 || k > maxcuts || k > s->blk[b].n )
-            return HIPSDP_ERR_NUMERIC;
-         ncuts[b] = k;
-         served[b] = 1;
-         if ( lmin != NULL ) lmin[b] = h.lmin[b];
-         const size_t slot = (size_t) b * maxcuts;
-         cut_copy_out(h, slot, vecoff[b], k, m, s->blk[b].n, eigvals + slot, lhs + slot, coefs + slot * m,
-            vecs != NULL ? vecs + vecoff[b] : NULL);
-      }
-   }
-   /* every other block: the per-block path, inside the same call */
-   for (int b = 0; b < nb; ++b)
-   {
-      if ( served[b] )
-         continue;
-      const size_t slot = (size_t) b * maxcuts;
-      double l0 = 0.0;
-      HS_CALL( eigencuts_one(s, b, y, tol, maxcuts, &ncuts[b], maxcuts > 0 ? eigvals + slot : NULL, maxcuts > 0 ? coefs + slot * m : NULL,
-            maxcuts > 0 ? lhs + slot : NULL, vecs != NULL ? vecs + vecoff[b] : NULL, &l0) );
-      if ( lmin != NULL )
-         lmin[b] = l0;
-   }
-   ++g_ec.calls;
-   return HIPSDP_OK;
-}
-
-/* ---- sparse eigenvector cuts of all blocks in one call (kernels: csrc/sparsecuts.hip) ------------------------------------------- */
-static void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
-{
-   par->tol = opts->tol; par->feastol = opts->feastol;
-   par->convtol = opts->convtol > 0.0 ? opts->convtol : 1e-6;
-   par->maxcuts = opts->maxcuts;
-   par->maxit = opts->maxit > 0 ? opts->maxit : HIPSDP_SPARSECUTS_MAXIT;
-}
-
-/* The round of the served blocks `ids` (ordered by decomposition class; sizes[nb]: the target sparsity of every block of the solver):
- * Z(y), the decompositions, TPower and, with maxcuts > 0, the coefficients, then ONE read-back.  The result block is indexed by the
- * block's number whatever `ids` holds, so a round over one block computes that block's bits of the round over all.  h: the view of the
- * read-back in the pinned buffer. */
-static int sc_round(hipsdp_solver* s, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
-   const std::vector<long long>& vecoff, CutStats* stats, hs_sc_out* h)
-{
-   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, nj = (int) ids.size();
-   hipStream_t st = s->stream;
-   /* the largest support a served block can have: the pitch of the support lists */
-   int smax = 1;
-   for (int b : ids)
-      if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
-         smax = sizes[b];
-   hs_sc_layout L;
-   hs_sc_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), &L);
-   int nmax = 0;
-   HS_CALL( ec_prepare(s, ids, vecoff, L.slabs, L.len, &nmax) );
-   CutWs& cw = s->cw;
-   double* dy = cw.dev + L.y;
-   const int* dsizes = reinterpret_cast<const int*>(cw.dev + L.sizes);
-   const hs_sc_out out = hs_cut_view(L.r, cw.dev);
-   hs_sc_par par;
-   sc_par_from_opts(opts, &par);
-   int launches = 0;
-   if ( m > 0 )
-      memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
-   memcpy(cw.pin + L.sizes, sizes, (size_t) nb * sizeof(int));
-   HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
-   ++launches;
-   HS_CALL( hs_syev_small_many(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
-   HS_CALL( hs_sc_tpower(st, nj, nmax, cw.djobs(), dsizes, &par, &out) );
-   ++launches;
-   if ( maxcuts > 0 )
-   {
-      HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, cw.djobs(), dsizes, &out) );
-      ++launches;
-   }
-   HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   stats->launches += launches;
-   stats->readbacks += 1;
-   *h = hs_cut_view(L.r, cw.pin);
+   HS_CALL( s->cw.upload_rounds(xjobs, sjobs) );
+   w->dxjobs = s->cw.dxjobs(); w->dsjobs = s->cw.dsjobs(); w->sjobs = s->cw.sjobs.data();
    return HS_OK;
 }
 
-/* ---- the same loop with the reference's switches recomputesparseev, recomputeinitial, exacttrans (kernels: csrc/sparsecuts_rounds.hip) - */
-static CutStats g_scx;
-
-extern "C" int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks)
-{
-   return g_scx.get(calls, launches, readbacks);
-}
-
-/* hs_syev_small_many as THREE launches whatever classes the jobs fall into: a class without jobs gets an empty launch */
-static int scx_syev(hipStream_t st, int count, const hs_eig_job* hjobs, const hs_eig_job* djobs, int* launches)
-{
-   int mine = 0;
-   HS_CALL( hs_syev_small_many(st, count, hjobs, djobs, &mine) );
-   HS_CALL( hs_scr_pad(st, 3 - mine) );
-   *launches += 3;
-   return HS_OK;
-}
-
-/* sc_round with a switch set (variant: HS_SCR_* bits, != 0): Z(y) and its decompositions as there, then maxcuts + 1 rounds - a TPower run
- * of every block; with HS_SCR_SPARSEEV the decompositions of the Z_S and the cut behind them, without it the cut inside the TPower
- * launch; with HS_SCR_INITIAL or HS_SCR_EXACTTRANS the decompositions of the deflated Z - and the coefficients, all enqueued on the
- * solver's stream and followed by ONE read-back.  The last round cannot produce a cut (a block that is still running has maxcuts of
- * them), so it is its TPower launch alone.  With s = 1 for HS_SCR_SPARSEEV and d = 1 for one of the other two, a call takes
- * 4 + maxcuts (1 + 4 s + 3 d) + 1 launches and one more for the coefficients when maxcuts > 0, whatever the blocks are. */
-static int scx_rounds(hipsdp_solver* s, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
-   unsigned variant, const std::vector<long long>& vecoff, hs_sc_out* h)
-{
-   const int nb = (int) s->blk.size(), m = s->m, maxcuts = opts->maxcuts, nj = (int) ids.size();
-   hipStream_t st = s->stream;
-   int smax = 1;
-   for (int b : ids)
-      if ( sizes[b] <= s->blk[b].n && sizes[b] > smax )
-         smax = sizes[b];
-   /* rows of the blocks' Z_S; a block whose size exceeds its rows gets no cut, its job is a matrix of one row */
-   std::vector<int> ns((size_t) nj);
-   long long state_len = 0;
-   for (int j = 0; j < nj; ++j)
-   {
-      const int n = s->blk[ids[j]].n;
-      ns[j] = sizes[ids[j]] <= n ? sizes[ids[j]] : 1;
-      state_len += hs_scr_block_make(n, ns[j], hs_syev_small_scratch(ns[j])).len;
-   }
-   hs_scr_layout L;
-   hs_scr_layout_make(nb, m, maxcuts, smax, vecoff[nb], ec_slab_len(s, ids), state_len, &L);
-   int nmax = 0;
-   HS_CALL( ec_prepare(s, ids, vecoff, L.sc.slabs, L.len, &nmax) );
-   CutWs& cw = s->cw;
-   std::vector<hs_scr_job> xj((size_t) nj);
-   std::vector<hs_eig_job> sj;
-   double* cur = cw.dev + L.state;
-   for (int j = 0; j < nj; ++j)
-   {
-      hs_scr_job& X = xj[j];
-      memset(&X, 0, sizeof(X));
-      const hs_scr_block B = hs_scr_block_make(s->blk[ids[j]].n, ns[j], hs_syev_small_scratch(ns[j]));
-      X.st = reinterpret_cast<hs_scr_state*>(cur + B.st);
-      X.v0 = cur + B.v0;
-      X.ZS = cur + B.ZS;
-      X.wsS = cur + B.wsS;
-      X.vposS = hs_syev_many_vecpos(ns[j]);
-      cur += B.len;
-   }
-   for (int cls = 0; cls < 3; ++cls)
-      for (int j = 0; j < nj; ++j)
-         if ( hs_syev_many_class(ns[j]) == cls )
-         {
-            hs_eig_job E;
-            memset(&E, 0, sizeof(E));
-            E.n = ns[j]; E.in = xj[j].ZS; E.ws = xj[j].wsS;
-            sj.push_back(E);
-         }
-   HS_CALL( cw.upload_rounds(xj, sj) );
-   double* dy = cw.dev + L.sc.y;
-   const int* dsizes = reinterpret_cast<const int*>(cw.dev + L.sc.sizes);
-   const hs_sc_out out = hs_cut_view(L.sc.r, cw.dev);
-   hs_sc_par par;
-   sc_par_from_opts(opts, &par);
-   int launches = 0;
-   if ( m > 0 )
-      memcpy(cw.pin + L.sc.y, y, (size_t) m * sizeof(double));
-   memcpy(cw.pin + L.sc.sizes, sizes, (size_t) nb * sizeof(int));
-   HS_HIP( hipMemcpyAsync(dy, cw.pin + L.sc.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_ec_form_z(st, nj, nmax, m, cw.djobs(), dy) );
-   ++launches;
-   HS_CALL( scx_syev(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
-   for (int round = 0; round <= maxcuts; ++round)
-   {
-      HS_CALL( hs_scr_tpower(st, nj, nmax, cw.djobs(), cw.dxjobs(), dsizes, &par, variant, round, &out) );
-      ++launches;
-      if ( round == maxcuts )
-         break;
-      if ( variant & HS_SCR_SPARSEEV )
-      {
-         HS_CALL( scx_syev(st, nj, cw.sjobs.data(), cw.dsjobs(), &launches) );
-         HS_CALL( hs_scr_cut(st, nj, cw.djobs(), cw.dxjobs(), dsizes, &par, &out) );
-         ++launches;
-      }
-      if ( variant & (HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
-         HS_CALL( scx_syev(st, nj, cw.ejobs.data(), cw.dejobs(), &launches) );
-   }
-   if ( maxcuts > 0 )
-   {
-      HS_CALL( hs_sc_coefs(st, nj, m, maxcuts, cw.djobs(), dsizes, &out) );
-      ++launches;
-   }
-   HS_HIP( hipMemcpyAsync(cw.pin + L.len.res_off, cw.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_scx.launches += launches;
-   g_scx.readbacks += 1;
-   *h = hs_cut_view(L.sc.r, cw.pin);
-   return HS_OK;
-}
-
-/* hipsdp_sparsecuts_all (variant = 0: sc_round, booked under g_sc) and hipsdp_sparsecuts_all_ex with a switch set */
-static int sparsecuts_all_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
-   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   if ( s == NULL || !s->shaped || y == NULL || sizes == NULL || opts == NULL || ncuts == NULL || opts->maxcuts < 0 )
-      return HIPSDP_ERR_ARG;
-   const int maxcuts = opts->maxcuts;
-   if ( maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
-      return HIPSDP_ERR_ARG;
-   const int nb = (int) s->blk.size(), m = s->m;
-   for (int b = 0; b < nb; ++b)
-      if ( sizes[b] < 1 )
-         return HIPSDP_ERR_ARG;
-   for (int b = 0; b < nb; ++b)
-      ncuts[b] = -1;
-   HS_HIP( hipSetDevice(s->device) );
-   HS_CALL( stage_sync(s) );
-   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
-   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, -1);
-   const std::vector<int> ids = ec_batched_ids(s);
-   if ( !ids.empty() )
-   {
-      hs_sc_out h;
-      if ( variant == 0 )
-         HS_CALL( sc_round(s, ids, y, sizes, opts, vecoff, &g_sc, &h) );
-      else
-         HS_CALL( scx_rounds(s, ids, y, sizes, opts, variant, vecoff, &h) );
-      for (int b : ids)
-      {
-         const int k = h.ncuts[b];
-         if ( k < 0 || k > maxcuts )
-            return HIPSDP_ERR_NUMERIC;
-         ncuts[b] = k;
-         if ( lmin != NULL ) lmin[b] = h.lmin[b];
-         if ( iters != NULL ) iters[b] = h.iters[b];
-         if ( flags != NULL ) flags[b] = h.flags[b];
-         const size_t slot = (size_t) b * maxcuts;
-         cut_copy_out(h, slot, vecoff[b], k, m, s->blk[b].n, eigvals + slot, lhs + slot, coefs + slot * m,
-            vecs != NULL ? vecs + vecoff[b] : NULL);
-      }
-   }
-   ++(variant == 0 ? g_sc : g_scx).calls;
-   return HIPSDP_OK;
-}
-
-extern "C" int hipsdp_sparsecuts_all(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   return sparsecuts_all_impl(s, y, sizes, opts, 0, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
-}
-
-extern "C" int hipsdp_sparsecuts_all_ex(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
-   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   if ( variant > (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
-      return HIPSDP_ERR_ARG;
-   return sparsecuts_all_impl(s, y, sizes, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
-}
-
-/* ---- sparse eigenvector cuts of ONE block of up to 512 rows (kernels: csrc/sparsecuts.hip, csrc/sparsecuts_large.hip) ---------- */
-/* a block of at most 128 rows: the round of hipsdp_sparsecuts_all with this block as the only job, the same bits */
-static int sparsecuts_small(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
-   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   const int maxcuts = opts->maxcuts;
-   const std::vector<long long> vecoff = cut_vecoff(s, maxcuts, block);      /* only this block has vectors */
-   std::vector<int> sizes(s->blk.size(), 1);
-   sizes[block] = size;
-   hs_sc_out h;
-   if ( variant == 0 )
-      HS_CALL( sc_round(s, std::vector<int>(1, block), y, sizes.data(), opts, vecoff, &g_sc1, &h) );
-   else
-      HS_CALL( scx_rounds(s, std::vector<int>(1, block), y, sizes.data(), opts, variant, vecoff, &h) );
-   const int k = h.ncuts[block];
-   if ( k < 0 || k > maxcuts )
-      return HIPSDP_ERR_NUMERIC;
-   *ncuts = k;
-   if ( lmin != NULL ) *lmin = h.lmin[block];
-   if ( iters != NULL ) *iters = h.iters[block];
-   if ( flags != NULL ) *flags = h.flags[block];
-   cut_copy_out(h, (size_t) block * maxcuts, vecoff[block], k, s->m, s->blk[block].n, eigvals, lhs, coefs, vecs);
-   return HIPSDP_OK;
-}
-
-/* a block of 129 .. 512 rows: Z(y), ONE tridiagonalisation, (lmin, v0) and maxeig from it, TPower in one workgroup, coefficients -
- * n + 7 launches (n + 2 with maxcuts == 0) and one read-back.  The workspaces are those of the calls above: they only grow. */
-static int sparsecuts_large(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   const Block& B = s->blk[block];
-   const int m = s->m, maxcuts = opts->maxcuts, n = B.n;
-   hipStream_t st = s->stream;
-   hs_scl_layout L;
-   hs_scl_layout_make(n, m, maxcuts, size <= n ? size : 1, (long long) hs_syevx_ws(n), HS_SYEVX_OUT(n), HS_SYEVX_OUT_VEC, &L);
-   CutWs& cw = s->cw;
-   HS_CALL( cw.grow(L.len.dev_len, L.len.pin_len, sizeof(hs_ec_job)) );
-   double *dy = cw.dev + L.y, *dZ = cw.dev + L.Z, *dws = cw.dev + L.ws, *o1 = cw.dev + L.o1, *o2 = cw.dev + L.o2;
-   std::vector<hs_ec_job> job(1);
-   hs_ec_job& J = job[0];
-   memset(&J, 0, sizeof(J));
-   ec_job_form(B, &J);
-   J.Z = dZ; J.ws = dws;
-   HS_CALL( cw.upload(job, std::vector<hs_eig_job>()) );
-   const hs_sc_out out = hs_cut_view(L.r, cw.dev);
-   hs_sc_par par;
-   sc_par_from_opts(opts, &par);
-   int launches = 0;
-   if ( m > 0 )
-   {
-      memcpy(cw.pin + L.y, y, (size_t) m * sizeof(double));
-      HS_HIP( hipMemcpyAsync(dy, cw.pin + L.y, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
-   }
-   HS_CALL( hs_ec_form_z(st, 1, n, m, cw.djobs(), dy) );
-   ++launches;
-   HS_CALL( hs_syevx_tridiag_dev(st, n, dZ, dws) );
-   launches += n;
-   /* the one read-back: the result block, or with maxcuts = 0 the head of the first request's output (its eigenvalue) */
-   double* hres = cw.pin + L.len.res_off;
-   const double* dres = cw.dev + L.len.res_off;
-   long long reslen = L.len.res_len;
-   if ( maxcuts == 0 )
-   {
-      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, o1, dws) );
-      ++launches;
-      dres = o1; reslen = HS_SYEVX_OUT_VEC;
-   }
-   else
-   {
-      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
-      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
-      HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, cw.dev + L.MT, &par, &out) );
-      HS_CALL( hs_scl_coefs(st, m, maxcuts, size, cw.djobs(), &out) );
-      launches += 3 + 1 + 1 + 1;
-   }
-   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_sc1.launches += launches;
-   g_sc1.readbacks += 1;
-   if ( maxcuts == 0 )
-   {
-      *ncuts = 0;
-      if ( lmin != NULL ) *lmin = hres[HS_SYEVX_OUT_LAM];
-      if ( iters != NULL ) *iters = 0;
-      if ( flags != NULL ) *flags = 0;
-      return HIPSDP_OK;
-   }
-   const hs_sc_out h = hs_cut_view(L.r, cw.pin);
-   const int k = h.ncuts[0];
-   if ( k < 0 || k > maxcuts )
-      return HIPSDP_ERR_NUMERIC;
-   *ncuts = k;
-   if ( lmin != NULL ) *lmin = h.lmin[0];
-   if ( iters != NULL ) *iters = h.iters[0];
-   if ( flags != NULL ) *flags = h.flags[0];
-   cut_copy_out(h, 0, 0, k, m, n, eigvals, lhs, coefs, vecs);
-   return HIPSDP_OK;
-}
-
-/* hipsdp_sparsecuts (variant = 0, booked under g_sc1) and hipsdp_sparsecuts_ex with a switch set: blocks of at most 128 rows */
-static int sparsecuts_impl(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
-   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   if ( s == NULL || !s->shaped || block < 0 || block >= (int) s->blk.size() || y == NULL || opts == NULL || ncuts == NULL || size < 1
-      || opts->maxcuts < 0 )
-      return HIPSDP_ERR_ARG;
-   if ( opts->maxcuts > 0 && (eigvals == NULL || coefs == NULL || lhs == NULL) )
-      return HIPSDP_ERR_ARG;
-   const int n = s->blk[block].n;
-   *ncuts = -1;
-   if ( s->comm != NULL || s->shardA || n > (variant == 0 ? HIPSDP_SPARSECUTS_MAXN : HS_SC_MAXN) )
-      return HIPSDP_OK;
-   HS_HIP( hipSetDevice(s->device) );
-   HS_CALL( stage_sync(s) );
-   HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
-   const Block& B = s->blk[block];
-   if ( B.sparse ? (B.sp == NULL || B.A0 == NULL) : B.A == NULL )
-      return HIPSDP_OK;
-   if ( n <= HS_SC_MAXN )
-      HS_CALL( sparsecuts_small(s, block, y, size, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
-   else
-      HS_CALL( sparsecuts_large(s, block, y, size, opts, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags) );
-   ++(variant == 0 ? g_sc1 : g_scx).calls;
-   return HIPSDP_OK;
-}
-
-extern "C" int hipsdp_sparsecuts(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, int* ncuts,
-   double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   return sparsecuts_impl(s, block, y, size, opts, 0, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
-}
-
-extern "C" int hipsdp_sparsecuts_ex(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant,
-   int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
-{
-   if ( variant > (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS) )
-      return HIPSDP_ERR_ARG;
-   return sparsecuts_impl(s, block, y, size, opts, variant, ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags);
-}
-
-/* ---- what hipsdp_onevar_bounds (csrc/onevar.hip) needs of a solver: its shape, and the block as the only job of the cut workspace -- */
-int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks)
-{
-   if ( s == NULL || !s->shaped )
-      return 0;
-   *m = s->m;
-   *nblocks = (int) s->blk.size();
-   return 1;
-}
-
-int hs_solver_block_n(const hipsdp_solver* s, int block)
-{
-   return s->blk[block].n;
-}
-
-int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, hs_solver_cut_ws* w, int* served)
+int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, long long wsoff, hs_solver_cut_ws* w,
+   int* served)
 {
    *served = 0;
    if ( s->comm != NULL || s->shardA )
@@ -5839,7 +5374,7 @@ int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long 
    HS_CALL( stage_sync(s) );
    HS_CALL( ensure_packed(s) );          /* (also builds the device form of blocks kept as nonzeros) */
    const Block& B = s->blk[block];
-   if ( B.sparse ? (B.sp == NULL || B.A0 == NULL) : B.A == NULL )
+   if ( !ec_has_matrices(B) )
       return HS_OK;
    CutWs& cw = s->cw;
    HS_CALL( cw.grow(dev_len, pin_len, sizeof(hs_ec_job)) );
@@ -5847,10 +5382,18 @@ int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long 
    memset(&job[0], 0, sizeof(hs_ec_job));
    ec_job_form(B, &job[0]);
    job[0].Z = cw.dev + zoff;
+   if ( wsoff >= 0 )
+      job[0].ws = cw.dev + wsoff;
    HS_CALL( cw.upload(job, std::vector<hs_eig_job>()) );
-   w->stream = s->stream; w->dev = cw.dev; w->pin = cw.pin; w->djob = cw.djobs();
+   cw.view(s->stream, w);
    *served = 1;
    return HS_OK;
+}
+
+int hs_solver_eigencuts_block(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
+   double* coefs, double* lhs, double* vecs, double* lam0)
+{
+   return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, lam0);
 }
 
 /* host-only: the column ranges of the sharded W formulation, bounds[0 .. nranks] (rank g owns [bounds[g], bounds[g + 1])) */

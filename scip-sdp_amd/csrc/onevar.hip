@@ -9,26 +9,22 @@
  * The call: argument checks (before the device is looked at), one buffer  u[m] | job table [count][HS_OV_TAB]  through the pinned
  * mirror of the cut workspace and ONE upload, TWO launches, ONE read-back of [count][HS_OV_RES].  Workspace (doubles, device):
  *     u[m] | table | result | Z (n^2) | slabs (hs_onevar_slab: 2 n^2 per job above 64 rows)
- * the pinned mirror holds the first three. */
+ * the pinned mirror holds the first three.
+ *
+ * The solver is seen through hs_solver_dims, hs_solver_block_n and hs_solver_cut_job (hs_kernels.h) alone: the last one hands out the
+ * cut workspace with the block as its only job, no decomposition slab (wsoff = -1).  The counters are a CutStats, as those of the cut
+ * calls (cut_calls.hip). */
 #include "hs_common.h"
 #include "hs_kernels.h"
+#include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
-#include <atomic>
 #include <cstring>
 
-namespace {
-
-struct OvStats { std::atomic<long long> calls{0}, launches{0}, readbacks{0}; };
-OvStats g_ov;
-
-}
+static CutStats g_ov;
 
 extern "C" int hipsdp_onevar_bounds_stats(long long* calls, long long* launches, long long* readbacks)
 {
-   if ( calls != NULL ) *calls = g_ov.calls.load();
-   if ( launches != NULL ) *launches = g_ov.launches.load();
-   if ( readbacks != NULL ) *readbacks = g_ov.readbacks.load();
-   return HIPSDP_OK;
+   return g_ov.get(calls, launches, readbacks);
 }
 
 extern "C" int hipsdp_onevar_bounds(hipsdp_solver* s, int block, const double* u, int count, const int* vars, const int* kind,
@@ -57,7 +53,7 @@ extern "C" int hipsdp_onevar_bounds(hipsdp_solver* s, int block, const double* u
    const long long slab = zoff + (long long) n * n;
    hs_solver_cut_ws w;
    int served = 0;
-   HS_CALL( hs_solver_cut_job(s, block, slab + hs_onevar_slab(n, count), zoff, zoff, &w, &served) );
+   HS_CALL( hs_solver_cut_job(s, block, slab + hs_onevar_slab(n, count), zoff, zoff, -1, &w, &served) );
    if ( !served )
       return HIPSDP_OK;
    if ( m > 0 )
@@ -72,12 +68,12 @@ extern "C" int hipsdp_onevar_bounds(hipsdp_solver* s, int block, const double* u
    }
    hipStream_t st = w.stream;
    HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) res * sizeof(double), hipMemcpyHostToDevice, st) );
-   HS_CALL( hs_ec_form_z(st, 1, n, m, w.djob, w.dev) );
+   HS_CALL( hs_ec_form_z(st, 1, n, m, w.djobs, w.dev) );
    hs_ov_par P;
    memset(&P, 0, sizeof(P));
    P.n = n; P.count = count; P.maxevals = opts->maxevals > 0 ? opts->maxevals : 100;
    P.feastol = opts->feastol; P.infinity = opts->infinity;
-   P.blk = w.djob; P.tab = w.dev + tab; P.slab = w.dev + slab; P.res = w.dev + res;
+   P.blk = w.djobs; P.tab = w.dev + tab; P.slab = w.dev + slab; P.res = w.dev + res;
    HS_CALL( hs_onevar_newton(st, &P) );
    HS_HIP( hipMemcpyAsync(w.pin + res, w.dev + res, (size_t) count * HS_OV_RES * sizeof(double), hipMemcpyDeviceToHost, st) );
    HS_HIP( hipStreamSynchronize(st) );

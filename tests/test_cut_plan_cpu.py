@@ -34,6 +34,6 @@ def test_the_layouts_are_host_only_and_built_into_the_library():
     assert "hip_runtime" not in _read("scip-sdp_amd", "csrc", "hs_cut_plan.cpp")
     hdr = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h")
     assert "hip_runtime" not in hdr and "hs_kernels.h" not in hdr and "hs_common.h" not in hdr
-    src = _read("scip-sdp_amd", "csrc", "ipm.hip")
+    src = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
     for name in ("hs_ec_layout_make", "hs_sc_layout_make", "hs_scl_layout_make", "hs_cut_view"):
         assert name in src, name

@@ -115,7 +115,7 @@ def test_the_layout_of_the_rounds_runs_clean_under_the_sanitizers(tmp_path):
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0 and "cut plan rounds check: ok" in r.stdout, r.stdout[-4000:]
     assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
-    assert "hs_scr_layout_make" in _read("scip-sdp_amd", "csrc", "ipm.hip") and "hs_scr_block_make" in _read("scip-sdp_amd", "csrc", "ipm.hip")
+    assert "hs_scr_layout_make" in _read("scip-sdp_amd", "csrc", "cut_calls.hip") and "hs_scr_block_make" in _read("scip-sdp_amd", "csrc", "cut_calls.hip")
 
 
 def test_libraries_export_the_calls_and_check_their_arguments(hb):
