@@ -214,6 +214,28 @@ HIPSDP_API int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const
                                  hipsdp_info* infos, int* rcs);
 HIPSDP_API int hipsdp_solve_many_stats(long long* launches, long long* problems);  /* process totals of the one-launch part */
 
+/* Solve ONE loaded problem under count objectives: job j is the solver's problem with b = row j of B (count x m, host, row-major),
+ * everything else shared - what optimisation-based bound tightening asks for (min / max y_v over one node relaxation).  Every job
+ * starts from the solver's start point when one is set (hipsdp_set_start), cold otherwise.  An eligible problem runs in the one-launch
+ * kernel, one workgroup per job on the solver's matrices: the node's pending setters in at most one launch, one fan-out launch per
+ * chunk that writes every job's objective (and start point) into a lane of its own, one solve launch per chunk of at most 512 jobs
+ * (fewer when 512 lanes would take more than 256 MiB of device memory; HIPSDP_OBJECTIVES_CHUNK in the environment sets another
+ * number).  The lanes belong to the solver and only grow.  Jobs the kernel declines or gives up on are solved afterwards by the
+ * general path, in job order, from the same start; a problem the one-launch path is not offered is solved count times on the general path.
+ * infos[j] (solve_seconds and schur_seconds aside) and row j of Y (count x m, may be NULL) are bit for bit what hipsdp_set_obj(B + j m),
+ * hipsdp_solve, hipsdp_get_y give on a solver loaded the same way (and given the same start point before every solve).
+ * params: ONE set for all jobs, or NULL for defaults.  params->preoptgap > 0 is refused: the preoptimal iterate is kept per solver,
+ * not per job.  Afterwards the solver has its own objective back, its start point is consumed and it holds no solution.
+ * HIPSDP_ERR_ARG, with nothing launched and nothing changed: a NULL or unshaped solver, count < 0, B or infos NULL with count > 0, a
+ * solver with a communicator or sharded matrices, preoptgap > 0.  count == 0 does nothing.
+ * rcs (optional): per-job return code.  Returns HIPSDP_OK when every rcs[j] is HIPSDP_OK, else the first failing code.
+ * Two host threads may call it at the same time on different solvers. */
+HIPSDP_API int hipsdp_solve_objectives(hipsdp_solver* solver, int count, const double* B, const hipsdp_params* params,
+                                       hipsdp_info* infos, double* Y, int* rcs);
+/* process totals: calls that passed the argument checks with count > 0, launches of the fan-out and of the one-launch kernel, jobs
+ * whose result that kernel delivered; any pointer may be NULL */
+HIPSDP_API int hipsdp_solve_objectives_stats(long long* calls, long long* launches, long long* problems);
+
 /* solution readback (host arrays).  For STATUS_OPTIMAL the iterate scaled by 1 / tau; for the infeasibility statuses
  * the normalised ray. */
 HIPSDP_API int  hipsdp_get_y(hipsdp_solver* solver, double* y);

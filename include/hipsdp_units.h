@@ -166,6 +166,16 @@ HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long l
  * hipsdp_onevar_bounds returns them (lmin, grad, evals may be NULL). */
 HIPSDP_API int  hipsdp_onevar_unit(int device, int n, int count, const double* Z, const double* A, const double* shift, const int* kind,
    const double* lb, const double* ub, double feastol, int maxevals, int* status, double* optval, double* lmin, double* grad, int* evals);
+/* the fan-out kernel of hipsdp_solve_objectives (hs_objs_fanout, csrc/kernels.hip) alone: count jobs of a problem with m variables, q LP
+ * rows and nblk blocks of ns[k] rows.  B: count x m objectives, b_own[m]: the solver's own; have_start = 1: the start point y[m], x[q],
+ * z[q] and XZ = X_0, Z_0, X_1, Z_1, ... one behind the other (have_start = 0: not read, only the objectives are fanned out).
+ * lanes: (count + 1) lanes of *lane_len doubles, lane 0 the home lane (b_own and the start), lane 1 + j job j; every double of it is set
+ * to `guard` before the launch, and every array of a lane (offs[4 + 2 nblk]: b, y, x, z, X_0, Z_0, ...) is followed by `gap` (even, >= 0)
+ * doubles that nothing may write.  A call with lanes = NULL returns *lane_len and offs alone; *launches (may be NULL): kernel
+ * launches issued (1 whatever count is) */
+HIPSDP_API int  hipsdp_objs_fanout_unit(int device, int count, int m, int q, int nblk, const int* ns, const double* B, const double* b_own,
+   int have_start, const double* y, const double* x, const double* z, const double* XZ, int gap, double guard, long long* lane_len,
+   long long* offs, double* lanes, int* launches);
 
 #ifdef __cplusplus
 }

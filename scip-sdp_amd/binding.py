@@ -281,6 +281,24 @@ class Solver:
         _chk(self._l().hipsdp_solve(self.h, C.byref(p), C.byref(info)), "hipsdp_solve")
         return info
 
+    def solve_objectives(self, B, **kw):
+        """hipsdp_solve_objectives: the loaded problem under every row of B (count x m) as objective, in one call; the keywords are
+        Solver.solve's, one set for all jobs.  Returns (list of Info, Y) with Y[j] = y of job j; raises RuntimeError with the per-job
+        return codes when the call failed."""
+        B = _f64(B)
+        if B.ndim != 2 or B.shape[1] != self.m:
+            raise ValueError("solve_objectives: B must be count x %d" % self.m)
+        n = B.shape[0]
+        p = _params(kw)
+        infos = (Info * max(n, 1))()
+        rcs = (C.c_int * max(n, 1))()
+        Y = np.zeros((n, self.m))
+        rc = self._l().hipsdp_solve_objectives(self.h, n, _dp(B), C.byref(p), infos, _dp(Y), rcs)
+        if rc != 0:
+            raise RuntimeError("hipsdp_solve_objectives failed: rc=%d, per job %s (%s)" %
+                               (rc, list(rcs)[:n], self._l().hipsdp_last_error().decode()))
+        return [infos[i] for i in range(n)], Y
+
     def solve_path(self):
         """1: the last solve ran in the one-launch kernel of csrc/solve1.hip, 0: the general path"""
         return self._l().hipsdp_solve_path(self.h)
@@ -679,6 +697,46 @@ def solve_many_stats():
     problems = C.c_longlong(0)
     _chk(lib().hipsdp_solve_many_stats(C.byref(launches), C.byref(problems)), "hipsdp_solve_many_stats")
     return launches.value, problems.value
+
+
+def solve_objectives_stats():
+    """(calls, launches, problems): process totals of hipsdp_solve_objectives - calls, launches of its fan-out and of the one-launch
+    kernel, jobs whose results that kernel delivered"""
+    v = [C.c_longlong(0) for _ in range(3)]
+    _chk(lib().hipsdp_solve_objectives_stats(*[C.byref(x) for x in v]), "hipsdp_solve_objectives_stats")
+    return tuple(x.value for x in v)
+
+
+def objs_fanout_unit(B, b_own, ns, q=0, start=None, gap=2, guard=-7.25):
+    """hipsdp_objs_fanout_unit (libhipsdp_units.so): the fan-out kernel of hipsdp_solve_objectives alone.  B: count x m, b_own: m,
+    start: None or (y, x, z, [X_k], [Z_k]).  Returns (lanes [(count + 1) x lane_len], offs, launches): lane 0 is the home lane, every
+    array of a lane is followed by gap guard words."""
+    B = _f64(B)
+    count, m = B.shape
+    b_own = _f64(b_own)
+    nsa = (C.c_int * max(len(ns), 1))(*[int(n) for n in ns])
+    offs = np.zeros(4 + 2 * len(ns), dtype=np.int64)
+    po = offs.ctypes.data_as(C.POINTER(C.c_longlong))
+    ln = C.c_longlong(0)
+    launches = C.c_int(0)
+    if start is not None:
+        y, x, z, X, Z = start
+        y, x, z = _f64(y), _f64(x if q else np.zeros(1)), _f64(z if q else np.zeros(1))
+        XZ = _f64(np.concatenate([np.concatenate([_f64(X[k]).ravel(), _f64(Z[k]).ravel()]) for k in range(len(ns))]))
+        ptrs = (_dp(y), _dp(x), _dp(z), _dp(XZ))
+    else:
+        ptrs = (None, None, None, None)
+    hs = 1 if start is not None else 0
+    rc = ulib().hipsdp_objs_fanout_unit(0, count, m, q, len(ns), nsa, _dp(B), _dp(b_own), hs, *ptrs, gap, C.c_double(guard), C.byref(ln),
+                                        po, None, None)
+    if rc != 0:
+        raise RuntimeError("hipsdp_objs_fanout_unit failed: rc=%d" % rc)
+    lanes = np.zeros((count + 1, ln.value))
+    rc = ulib().hipsdp_objs_fanout_unit(0, count, m, q, len(ns), nsa, _dp(B), _dp(b_own), hs, *ptrs, gap, C.c_double(guard), C.byref(ln),
+                                        po, _dp(lanes), C.byref(launches))
+    if rc != 0:
+        raise RuntimeError("hipsdp_objs_fanout_unit failed: rc=%d (%s)" % (rc, ulib().hipsdp_last_error().decode()))
+    return lanes, offs.copy(), launches.value
 
 
 def solve1_fits(m, q, ns):

@@ -805,4 +805,18 @@ int hs_solve1_class(const hs_solve1_args* a);
 int hs_solve1_launch_many(hipStream_t st, int cls, const hs_solve1_args* dev_args, int count);
 int hs_solve1_debug_counts(unsigned int* out2);
 
+/* ---- the lanes of hipsdp_solve_objectives (csrc/ipm.hip): one loaded problem, one lane per objective.  A lane holds, in device memory
+ * and in this order, b[m], y[m], x[q], z[q] and X_k, Z_k (n_k x n_k) of every block; every array starts at an even offset (16 bytes)
+ * and is followed by `gap` doubles (even; 0 in the engine, guard words in the unit test).  hs_objs_lane_layout writes the 4 + 2 nblk
+ * offsets and returns the length of a lane (even). */
+#define HS_FAN_MAXSEG (4 + 2 * HS_S1_MAXBLK)
+long long hs_objs_lane_layout(int m, int q, int nblk, const int* n, int gap, long long* off);
+/* the fan-out (csrc/kernels.hip): segment i of lane j is len doubles at lanes + j lane_stride + dst, copied from src0 for lane 0 (the
+ * home lane: the solver's own objective and start point, kept for the jobs the general path solves later) and from src + (j - 1) stride
+ * for the lanes of the jobs (stride 0: the same start point for all).  Every address is a multiple of 16 bytes.  ONE launch over
+ * (lane, segment), 16-byte loads and stores, one 8-byte copy more where len is odd; it copies and does nothing else. */
+struct hs_fan_seg { const double* src0; const double* src; long long stride, dst, len; };
+struct hs_fan_plan { int nseg; hs_fan_seg seg[HS_FAN_MAXSEG]; };
+int hs_objs_fanout(hipStream_t st, const hs_fan_plan* plan, double* lanes, long long lane_stride, int nlanes);
+
 #endif

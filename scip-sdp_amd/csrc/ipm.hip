@@ -280,6 +280,12 @@ struct hipsdp_solver
    bool cmd_inflight;      /* slots must not be written again before it has (cmd_new waits for the event) */
    unsigned long long s1_seq;
    int s1_last;            /* 1: the last solve ran in the single launch */
+   /* the lanes of hipsdp_solve_objectives (objs_lanes): device part and pinned, device-visible part, grow-only; every call lays
+    * them out for its shape and count.  They go with the problem's buffers: hipsdp_free, or a hipsdp_set_shape that does not keep
+    * the allocations of the shape before.  ln_seq: their sequence numbers */
+   double* ln_dev; long long ln_dev_len;
+   double* ln_host; double* ln_host_dev; long long ln_host_len;
+   unsigned long long ln_seq;
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
    CutWs cw;               /* the calls of csrc/cut_calls.hip and csrc/onevar.hip, through hs_solver_cut_* below */
@@ -584,6 +590,10 @@ static void free_problem(hipsdp_solver* s)
    if ( s->gc_M != NULL ) (void) hipFree(s->gc_M);
    s->gc_M = NULL; s->gc_len = 0; s->gc_nomem = false;
    hs_gram_key_clear(&s->gc_key);
+   /* (the lanes of hipsdp_solve_objectives go with the problem they were laid out for) */
+   if ( s->ln_dev != NULL ) (void) hipFree(s->ln_dev);
+   if ( s->ln_host != NULL ) (void) hipHostFree(s->ln_host);
+   s->ln_dev = NULL; s->ln_host = NULL; s->ln_host_dev = NULL; s->ln_dev_len = 0; s->ln_host_len = 0;
    dfree(s->Mgather);
    s->Mgather = NULL;
    dfree(s->passg);
@@ -646,6 +656,7 @@ extern "C" int hipsdp_create(hipsdp_solver** out, int device)
    s->clk_on = false; s->clk_buf = NULL; s->clk_n = 0; s->clk_ghz = 0.0; s->clk_stream = NULL;
    s->s1_ws = NULL; s->s1_ws_len = 0; s->s1_host = NULL; s->s1_host_dev = NULL; s->s1_seq = 0; s->s1_last = 0; s->s1_sol_host = false; s->zero_b = false; s->zero_D = false;
    s->arena_h = NULL; s->arena_d = NULL; s->arena_cap = 0; s->stage_off = 0; s->stage_pending = false; s->ncmd = 0; s->cmd_ev = NULL; s->cmd_inflight = false; s->m_alloc = 0; s->q_alloc = 0;
+   s->ln_dev = NULL; s->ln_dev_len = 0; s->ln_host = NULL; s->ln_host_dev = NULL; s->ln_host_len = 0; s->ln_seq = 0;
    s->trsv_ws = NULL;
    s->a_gen_next = 0; s->gc_M = NULL; s->gc_len = 0; s->gc_nomem = false; s->gc_hits = s->gc_misses = 0;
    hs_gram_key_clear(&s->gc_key);
@@ -3041,21 +3052,74 @@ static long long g_many_problems = 0;      /* ... and the problems whose results
 /* the three stages of a one-launch solve: prepare (eligibility, workspace, the kernel's arguments, the node's commands taken over),
  * wait (the sequence word), finish (the result block into the solver and info).  hipsdp_solve runs them back to back (solve1_try),
  * hipsdp_solve_many prepares many solvers, launches them together and finishes each. */
+/* A LANE is what one workgroup of the kernel works on beside the matrices A[k] and Dext, which it only reads: the objective, the
+ * iterate, the workspace, and in pinned host memory the result block, the sequence word behind it (at HS_S1_OUT_DOUBLES), optionally
+ * the history (behind the word's 8 doubles) and y, x, z once more.  The solver's own storage is the lane of hipsdp_solve and
+ * hipsdp_solve_many (solve1_own_lane); hipsdp_solve_objectives gives one solver many (objs_lanes) that share its matrices. */
+struct S1Lane
+{
+   double *b, *y, *x, *z;
+   double *X[HS_S1_MAXBLK], *Z[HS_S1_MAXBLK];
+   double* gws; long long gws_len;
+   double* host; double* host_dev;          /* the pinned part as the host and as the device see it */
+   bool hist;                               /* it has room for the history */
+   long long hy, hx, hz;                    /* offsets of y, x, z in the pinned part */
+   unsigned long long* seq;                 /* the counter its sequence numbers are drawn from */
+};
 struct S1Prep
 {
    hs_solve1_args a;
    int prof, nofb;
    std::chrono::steady_clock::time_point t_begin;
+   const double* host;                      /* the pinned part of the lane the launch reports to */
+   long long hy;
 };
-/* *offered = false: not this path's problem (shape, options) - nothing has been touched */
-static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
+/* what a finished lane says about the solution it holds (solve1_result) */
+struct S1Sol
 {
-   *offered = false;
-   s->s1_last = 0;
-   s->s1_sol_host = false;
+   int status;
+   double tau, kappa, sol_scale, pre_scale;
+   bool pre_valid;
+};
+static void solve1_own_lane(hipsdp_solver* s, S1Lane* L)
+{
+   memset(L, 0, sizeof(*L));
+   const int K = (int) s->blk.size();
+   for (int k = 0; k < K && k < HS_S1_MAXBLK; ++k)
+   {
+      L->X[k] = s->blk[k].X; L->Z[k] = s->blk[k].Z;
+   }
+   L->b = s->b; L->y = s->y; L->x = s->x; L->z = s->z;
+   L->gws = s->s1_ws; L->gws_len = s->s1_ws_len;
+   L->host = s->s1_host; L->host_dev = s->s1_host_dev;
+   L->hist = true;
+   L->hy = S1_SOL_OFF; L->hx = L->hy + 128; L->hz = L->hx + 4096;
+   L->seq = &s->s1_seq;
+}
+/* the lane's part of the kernel's arguments, with the next sequence number of the lane's counter */
+static void solve1_bind(S1Prep* pp, const S1Lane& L, int K)
+{
+   hs_solve1_args& a = pp->a;
+   for (int k = 0; k < K; ++k)
+   {
+      a.X[k] = L.X[k]; a.Z[k] = L.Z[k];
+   }
+   a.b = L.b; a.y = L.y; a.x = L.x; a.z = L.z;
+   a.gws = L.gws; a.gws_len = L.gws_len;
+   a.out = L.host_dev;
+   a.hist = (L.hist && getenv("HIPSDP_SOLVE1_HIST") != NULL && getenv("HIPSDP_SOLVE1_HIST")[0] != '0') ? L.host_dev + HS_S1_OUT_DOUBLES + 8 : NULL;
+   a.hist_len = S1_HIST_MAX;
+   a.hy = L.host_dev + L.hy; a.hx = L.host_dev + L.hx; a.hz = L.host_dev + L.hz;
+   a.seq = ++*L.seq;
+   a.flag = reinterpret_cast<unsigned long long*>(L.host_dev + HS_S1_OUT_DOUBLES);
+   pp->host = L.host;
+   pp->hy = L.hy;
+}
+/* whether the one-launch path is offered the solver's problem under s->par and the environment; ns: the block sizes when it is */
+static bool solve1_eligible(hipsdp_solver* s, int* ns, int* prof_out)
+{
    /* (read at every solve: tests and tools switch the path between two solves of one process) */
    int on = 1, prof = 0;
-   const double maxwork = 3e6;
    /* largest block the kernel is offered (HIPSDP_SOLVE1_MAXN): whatever fits its LDS (hs_solve1_fits) - with no LP rows one block
     * of 49 rows at m = 1, 41 at m = 64, 37 at m = 108; two of 34 / 29 / 25; eight of 16 / 13 / 12 (hipsdp_solve1_fits, units library).
     * Measured with sparse variable matrices, dense constant matrices and LP rows of density 0.3 (tests/devtools/solve1_sizes.py) it
@@ -3078,23 +3142,38 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
          maxn = atoi(getenv("HIPSDP_SOLVE1_MAXN"));
    }
    const hipsdp_params& par = s->par;
+   *prof_out = prof;
    if ( !on || s->comm != NULL || s->shardA || s->schur_mode_forced || par.verbose || s->pc.on )
-      return HS_OK;
+      return false;
    const int K = (int) s->blk.size();
-   int ns[HS_S1_MAXBLK];
    if ( K < 1 || K > HS_S1_MAXBLK || s->m > maxm )
-      return HS_OK;
+      return false;
    for (int k = 0; k < K; ++k)
    {
       if ( s->blk[k].sparse || s->blk[k].A == NULL || s->blk[k].n > maxn )
-         return HS_OK;
+         return false;
       ns[k] = s->blk[k].n;
    }
-   if ( !hs_solve1_fits(s->m, s->q, K, ns) )
+   return hs_solve1_fits(s->m, s->q, K, ns) != 0;
+}
+/* *offered = false: not this path's problem (shape, options) - nothing has been touched.  lane = NULL: the solver's own lane, its
+ * workspace and pinned part allocated here, and the node's waiting setters taken over by the launch; a lane of
+ * hipsdp_solve_objectives: the setters have been flushed and the launch runs none */
+static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered, const S1Lane* lane = NULL)
+{
+   *offered = false;
+   s->s1_last = 0;
+   s->s1_sol_host = false;
+   const double maxwork = 3e6;
+   int ns[HS_S1_MAXBLK];
+   int prof = 0;
+   if ( !solve1_eligible(s, ns, &prof) )
       return HS_OK;
+   const hipsdp_params& par = s->par;
+   const int K = (int) s->blk.size();
    hipStream_t st = s->stream;
    const long long want = hs_solve1_ws_doubles(s->m, s->q, K, ns);
-   if ( s->s1_ws_len < want )
+   if ( lane == NULL && s->s1_ws_len < want )
    {
       if ( s->s1_ws != NULL )
       {
@@ -3106,7 +3185,7 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
       HS_HIP( hipMalloc((void**) &s->s1_ws, (size_t) len * sizeof(double)) );
       s->s1_ws_len = len;
    }
-   if ( s->s1_host == NULL )
+   if ( lane == NULL && s->s1_host == NULL )
    {
       HS_HIP( hipHostMalloc((void**) &s->s1_host, (size_t) S1_HOST_DOUBLES * sizeof(double),
             hipHostMallocMapped | hipHostMallocCoherent) );
@@ -3131,9 +3210,9 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
    for (int k = 0; k < K; ++k)
    {
       Block& B = s->blk[k];
-      a.n[k] = B.n; a.A[k] = B.A; a.X[k] = B.X; a.Z[k] = B.Z; a.Xpre[k] = B.Xpre;
+      a.n[k] = B.n; a.A[k] = B.A; a.Xpre[k] = B.Xpre;
    }
-   a.b = s->b; a.Dext = s->Dext; a.y = s->y; a.x = s->x; a.z = s->z; a.pre_y = s->pre_y; a.pre_x = s->pre_x;
+   a.Dext = s->Dext; a.pre_y = s->pre_y; a.pre_x = s->pre_x;
    a.gaptol = par.gaptol; a.feastol = par.feastol; a.infeastol = par.infeastol; a.objlimit = par.objlimit; a.timelimit = par.timelimit;
    a.gamma = par.gamma; a.pabstol = par.pabstol; a.preoptgap = par.preoptgap; a.elapsed0 = 0.0; a.maxwork = maxwork;
    a.maxiter = par.maxiter; a.settings = par.settings; a.have_start = s->have_start ? 1 : 0;
@@ -3146,13 +3225,14 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
    const int nofb = (getenv("HIPSDP_SOLVE1_NO_FALLBACK") != NULL && getenv("HIPSDP_SOLVE1_NO_FALLBACK")[0] == '1') ? 1 : 0;    /* (read at every solve, like the other switches of this path) */
    a.keep_on_fail = nofb ? 0 : 1;
    pp->nofb = nofb;
-   a.gws = s->s1_ws; a.gws_len = s->s1_ws_len;
-   a.out = s->s1_host_dev;
-   a.hist = (getenv("HIPSDP_SOLVE1_HIST") != NULL && getenv("HIPSDP_SOLVE1_HIST")[0] != '0') ? s->s1_host_dev + HS_S1_OUT_DOUBLES + 8 : NULL;
-   a.hist_len = S1_HIST_MAX;
-   a.hy = s->s1_host_dev + S1_SOL_OFF; a.hx = a.hy + 128; a.hz = a.hx + 4096;
-   a.seq = ++s->s1_seq;
-   a.flag = reinterpret_cast<unsigned long long*>(s->s1_host_dev + HS_S1_OUT_DOUBLES);
+   if ( lane != NULL )
+      solve1_bind(pp, *lane, K);
+   else
+   {
+      S1Lane own;
+      solve1_own_lane(s, &own);
+      solve1_bind(pp, own, K);
+   }
    a.cmds = s->arena_d; a.ncmd = s->ncmd;         /* the node's setters: run by the same launch */
    if ( s->ncmd > 0 )
    {
@@ -3164,11 +3244,11 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered)
    return HS_OK;
 }
 
-/* spin on the sequence word of the launch on st */
-static int solve1_wait(hipsdp_solver* s, unsigned long long seq, hipStream_t st)
+/* spin on the sequence word of the launch on st (host: the pinned part of its lane) */
+static int solve1_wait(const double* host, unsigned long long seq, hipStream_t st)
 {
    {
-      volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s->s1_host + HS_S1_OUT_DOUBLES);
+      const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(host + HS_S1_OUT_DOUBLES);
       long long spins = 0;
       while ( *flag != seq )
       {
@@ -3196,13 +3276,15 @@ static int solve1_wait(hipsdp_solver* s, unsigned long long seq, hipStream_t st)
 
 /* *done = true: the solve ran there; false: the kernel declined (too much work for one compute unit) or gave up numerically, and the
  * general path takes the problem from the same start */
-static int solve1_finish(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, bool* done)
+/* the lane's part of it: the result block of the lane pp was bound to into info and sol; the solver is read (parameters, shape), the
+ * process counters move, nothing of the solver's solution state is written */
+static int solve1_result(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, S1Sol* sol, bool* done)
 {
    *done = false;
    const hipsdp_params& par = s->par;
    hipStream_t st = s->stream;
    const int prof = pp->prof, nofb = pp->nofb;
-   const double* o = s->s1_host;
+   const double* o = pp->host;
    const int status = (int) o[0];
    if ( status == -2 )
       return HS_OK;                              /* declined: the general path takes the problem */
@@ -3222,28 +3304,23 @@ static int solve1_finish(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, 
    }
    /* the result block, y, x and z are in pinned memory, published before the sequence word; X and Z in device memory are complete
     * when the kernel has retired - whoever reads them waits for the queue first (stage_sync), this call does not */
-   s->stage_pending = true;
    memset(info, 0, sizeof(*info));
-   s->tau = o[9];
-   s->kappa = o[10];
+   sol->status = status;
+   sol->tau = o[9];
+   sol->kappa = o[10];
    const double pobj = o[2], dobj = o[3];
    if ( status == HIPSDP_STATUS_DINF || status == HIPSDP_STATUS_DUNB || status == HIPSDP_STATUS_PDINF )
-      s->sol_scale = 1.0 / fmax(fmax(fabs(dobj), fabs(pobj)), 1e-300);
+      sol->sol_scale = 1.0 / fmax(fmax(fabs(dobj), fabs(pobj)), 1e-300);
    else
-      s->sol_scale = 1.0 / s->tau;
-   s->last_status = status;
-   s->solved = true;
-   s->have_start = false;
-   s->pre_valid = o[13] != 0.0;
-   s->pre_scale = o[14];
-   for (auto& B : s->blk)
-      B.derived_valid = false;
+      sol->sol_scale = 1.0 / sol->tau;
+   sol->pre_valid = o[13] != 0.0;
+   sol->pre_scale = o[14];
    info->status = status;
    info->iterations = (int) o[1];
-   info->pobj = pobj * s->sol_scale;
-   info->dobj = dobj * s->sol_scale;
+   info->pobj = pobj * sol->sol_scale;
+   info->dobj = dobj * sol->sol_scale;
    info->pinf = o[4]; info->dinf = o[5]; info->dabs = o[6]; info->gap = o[7]; info->mu = o[8];
-   info->tau = s->tau; info->kappa = s->kappa;
+   info->tau = sol->tau; info->kappa = sol->kappa;
    info->chol_fail = (int) o[11];
    info->warm_started = (int) o[12];
    info->settings_used = par.settings;
@@ -3264,10 +3341,30 @@ static int solve1_finish(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, 
          fprintf(stderr, " %.0f", o[18 + i]);
       fprintf(stderr, " | nnz A %d, LP %d\n", (int) o[40], (int) o[41]);
    }
-   s->s1_last = 1;
-   s->s1_sol_host = true;
    (void) __sync_add_and_fetch(&g_solve1_solves, 1);
    *done = true;
+   return HS_OK;
+}
+/* the solver's own lane: the solution it holds becomes the solver's */
+static int solve1_finish(hipsdp_solver* s, const S1Prep* pp, hipsdp_info* info, bool* done)
+{
+   S1Sol sol;
+   HS_CALL( solve1_result(s, pp, info, &sol, done) );
+   if ( !*done )
+      return HS_OK;
+   s->stage_pending = true;
+   s->tau = sol.tau;
+   s->kappa = sol.kappa;
+   s->sol_scale = sol.sol_scale;
+   s->last_status = sol.status;
+   s->solved = true;
+   s->have_start = false;
+   s->pre_valid = sol.pre_valid;
+   s->pre_scale = sol.pre_scale;
+   for (auto& B : s->blk)
+      B.derived_valid = false;
+   s->s1_last = 1;
+   s->s1_sol_host = true;
    return HS_OK;
 }
 
@@ -3280,7 +3377,7 @@ static int solve1_try(hipsdp_solver* s, hipsdp_info* info, bool* done)
    if ( !offered )
       return HS_OK;
    HS_CALL( hs_solve1_launch(s->stream, &pp.a) );
-   HS_CALL( solve1_wait(s, pp.a.seq, s->stream) );
+   HS_CALL( solve1_wait(pp.host, pp.a.seq, s->stream) );
    return solve1_finish(s, &pp, info, done);
 }
 
@@ -4806,7 +4903,7 @@ extern "C" int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const
       for (int i = 0; i < count; ++i)
          if ( it[i].launched ) { pend[i] = 1; ++left; }
       auto published = [&](int i) -> bool {
-         const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(solvers[i]->s1_host + HS_S1_OUT_DOUBLES);
+         const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(it[i].pp.host + HS_S1_OUT_DOUBLES);
          return *flag == it[i].pp.a.seq;
       };
       long long spins = 0;
@@ -4876,6 +4973,420 @@ extern "C" int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const
          rc_all = I.rc;
    }
    return rc_all;
+}
+
+/* ---- one problem, many objectives: one workgroup per objective on the matrices of ONE solver -------------------------------- */
+
+static long long g_objs_calls = 0;         /* hipsdp_solve_objectives: calls that passed the argument checks with count > 0 */
+static long long g_objs_launches = 0;      /* ... launches of the fan-out and of the one-launch kernel */
+static long long g_objs_problems = 0;      /* ... jobs whose results the kernel delivered */
+#define OBJS_CHUNK_MAX 512                 /* most lanes of a solver, and jobs of one launch */
+#define OBJS_LANE_BYTES (256LL << 20)      /* ... fewer when that many would take more device memory than this */
+
+/* the lanes of a call: lane 0 is the home lane (the solver's own objective and start point, saved by the fan-out: what the jobs
+ * that the general path solves later start from, and what the solver gets back), lanes 1 .. nlanes the jobs of a chunk.  Device
+ * part: nlanes + 1 lanes of `stride` doubles (the arrays of hs_objs_lane_layout, then the kernel's workspace), then nlanes rows of
+ * mp doubles for the objectives when the staging arena cannot take them.  Pinned part: nlanes times hstride doubles (result block,
+ * sequence word, y, x, z). */
+struct ObjsLanes
+{
+   int nlanes;
+   long long off[HS_FAN_MAXSEG];
+   long long iter_len, stride, ws_len, mp, qp, hstride;
+   double* dev; double* Bdev; double* host; double* host_dev;
+};
+/* with_ws = false: the home lane alone and no workspace (a problem the one-launch path is not offered; any number of blocks) */
+static int objs_lanes(hipsdp_solver* s, int nlanes, bool with_ws, std::vector<long long>& off, ObjsLanes* L)
+{
+   const int K = (int) s->blk.size();
+   std::vector<int> ns((size_t) K + 1);
+   for (int k = 0; k < K; ++k) ns[k] = s->blk[k].n;
+   off.assign((size_t) 4 + 2 * K, 0);
+   memset(L, 0, sizeof(*L));
+   L->nlanes = nlanes;
+   L->iter_len = hs_objs_lane_layout(s->m, s->q, K, ns.data(), 0, off.data());
+   L->mp = (s->m + 1) & ~1LL; L->qp = (s->q + 1) & ~1LL;
+   long long dev_need = L->iter_len, host_need = 0;
+   if ( with_ws )
+   {
+      for (int i = 0; i < 4 + 2 * K; ++i) L->off[i] = off[i];
+      L->ws_len = (hs_solve1_ws_doubles(s->m, s->q, K, ns.data()) + 1) & ~1LL;
+      L->stride = L->iter_len + L->ws_len;
+      L->hstride = HS_S1_OUT_DOUBLES + 8 + L->mp + 2 * L->qp;
+      dev_need = (long long) (nlanes + 1) * L->stride + (long long) nlanes * L->mp;
+      host_need = (long long) nlanes * L->hstride;
+   }
+   if ( s->ln_dev_len < dev_need )
+   {
+      if ( s->ln_dev != NULL )
+      {
+         HS_HIP( hipStreamSynchronize(s->stream) );
+         (void) hipFree(s->ln_dev);
+         s->ln_dev = NULL; s->ln_dev_len = 0;
+      }
+      HS_HIP( hipMalloc((void**) &s->ln_dev, (size_t) dev_need * sizeof(double)) );
+      s->ln_dev_len = dev_need;
+   }
+   if ( s->ln_host_len < host_need )
+   {
+      if ( s->ln_host != NULL )
+      {
+         HS_HIP( hipStreamSynchronize(s->stream) );
+         (void) hipHostFree(s->ln_host);
+         s->ln_host = NULL; s->ln_host_dev = NULL; s->ln_host_len = 0;
+      }
+      HS_HIP( hipHostMalloc((void**) &s->ln_host, (size_t) host_need * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) );
+      HS_HIP( hipHostGetDevicePointer((void**) &s->ln_host_dev, s->ln_host, 0) );
+      s->ln_host_len = host_need;
+   }
+   L->dev = s->ln_dev; L->Bdev = s->ln_dev + (long long) (nlanes + 1) * L->stride;
+   L->host = s->ln_host; L->host_dev = s->ln_host_dev;
+   return HIPSDP_OK;
+}
+/* lane 1 + j of a chunk as the kernel's stages see it */
+static void objs_lane(const hipsdp_solver* s, const ObjsLanes& L, int j, S1Lane* o)
+{
+   memset(o, 0, sizeof(*o));
+   double* base = L.dev + (long long) (j + 1) * L.stride;
+   const int K = (int) s->blk.size();
+   o->b = base + L.off[0]; o->y = base + L.off[1]; o->x = base + L.off[2]; o->z = base + L.off[3];
+   for (int k = 0; k < K; ++k)
+   {
+      o->X[k] = base + L.off[4 + 2 * k]; o->Z[k] = base + L.off[5 + 2 * k];
+   }
+   o->gws = base + L.iter_len; o->gws_len = L.ws_len;
+   o->host = L.host + (long long) j * L.hstride; o->host_dev = L.host_dev + (long long) j * L.hstride;
+   o->hist = false;
+   o->hy = HS_S1_OUT_DOUBLES + 8; o->hx = o->hy + L.mp; o->hz = o->hx + L.qp;
+   o->seq = const_cast<unsigned long long*>(&s->ln_seq);
+}
+/* the solver's objective and, when it has one, its start point to (save) or from the home lane at `home`, on the solver's queue */
+static int objs_home_copy(hipsdp_solver* s, double* home, const std::vector<long long>& off, bool warm, bool save, bool obj)
+{
+   hipStream_t st = s->stream;
+   auto cp = [&](double* own, long long o, long long len) -> int {
+      if ( len > 0 )
+         HS_HIP( hipMemcpyAsync(save ? home + o : own, save ? own : home + o, (size_t) len * sizeof(double), hipMemcpyDeviceToDevice, st) );
+      return HIPSDP_OK;
+   };
+   if ( obj )
+      HS_CALL( cp(s->b, off[0], s->m) );
+   if ( warm )
+   {
+      HS_CALL( cp(s->y, off[1], s->m) );
+      HS_CALL( cp(s->x, off[2], s->q) );
+      HS_CALL( cp(s->z, off[3], s->q) );
+      for (size_t k = 0; k < s->blk.size(); ++k)
+      {
+         const long long n2 = (long long) s->blk[k].n * s->blk[k].n;
+         HS_CALL( cp(s->blk[k].X, off[4 + 2 * k], n2) );
+         HS_CALL( cp(s->blk[k].Z, off[5 + 2 * k], n2) );
+      }
+   }
+   s->stage_pending = true;
+   return HIPSDP_OK;
+}
+/* one job on the general path, on the solver's own storage, as hipsdp_set_start, hipsdp_set_obj, hipsdp_solve, hipsdp_get_y run it */
+static int objs_general_job(hipsdp_solver* s, const hipsdp_params* params, const double* bj, double* home, const std::vector<long long>& off,
+   bool warm, hipsdp_info* info, double* yrow)
+{
+   HS_CALL( objs_home_copy(s, home, off, warm, false, false) );
+   s->have_start = warm;
+   if ( s->m > 0 )
+      HS_CALL( stage_upload(s, s->b, bj, (size_t) s->m * sizeof(double)) );
+   s->solved = false;
+   int rc = solve_begin(s, params, info);
+   if ( rc == HIPSDP_OK )
+      rc = solve_run(s, info, false);
+   rc = solve_end(s, rc);
+   if ( rc == HIPSDP_OK && yrow != NULL )
+      rc = hipsdp_get_y(s, yrow);
+   return rc;
+}
+
+extern "C" int hipsdp_solve_objectives(hipsdp_solver* s, int count, const double* B, const hipsdp_params* params, hipsdp_info* infos,
+   double* Y, int* rcs)
+{
+   g_err[0] = 0;
+   if ( s == NULL || !s->shaped || count < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( count == 0 )
+      return HIPSDP_OK;
+   if ( B == NULL || infos == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( s->comm != NULL || s->shardA )
+   {
+      set_err("hipsdp_solve_objectives: the solver must have no communicator and no sharded matrices");
+      return HIPSDP_ERR_ARG;
+   }
+   if ( params != NULL && params->preoptgap > 0.0 )
+   {
+      set_err("hipsdp_solve_objectives: preoptgap > 0 - the preoptimal iterate is kept per solver, not per job");
+      return HIPSDP_ERR_ARG;
+   }
+   HS_HIP( hipSetDevice(s->device) );
+   (void) __sync_add_and_fetch(&g_objs_calls, 1);
+   const int m = s->m, K = (int) s->blk.size();
+   const bool warm = s->have_start;
+   hipStream_t st = s->stream;
+   std::vector<int> rc((size_t) count, HIPSDP_OK);
+   auto leave = [&](int rc_call) -> int {
+      int rc_all = rc_call;
+      for (int j = 0; j < count; ++j)
+      {
+         if ( rc_call != HIPSDP_OK ) rc[j] = rc_call;
+         if ( rcs != NULL ) rcs[j] = rc[j];
+         if ( rc_all == HIPSDP_OK ) rc_all = rc[j];
+      }
+      return rc_all;
+   };
+
+   /* 1. the node's waiting setters write the shared matrices: ONE launch for them, before any lane runs (the lanes run none) */
+   int r = flush_zeros(s);
+   if ( r == HIPSDP_OK ) r = flush_cmds(s);
+   if ( r == HIPSDP_OK ) r = solve_begin(s, params, &infos[0]);
+   if ( r != HIPSDP_OK )
+      return leave(solve_end(s, r));
+   for (int j = 0; j < count; ++j)
+      solve_reset(s, &infos[j]);
+   s->solved = false;
+   s->s1_last = 0;
+   s->s1_sol_host = false;
+   int ns[HS_S1_MAXBLK], prof = 0;
+   const bool offered = solve1_eligible(s, ns, &prof);
+   std::vector<long long> off;
+   ObjsLanes L;
+   std::vector<int> later;                      /* jobs for the general path, in job order */
+
+   if ( !offered )
+   {
+      /* not the one-launch path's problem: the call is the loop */
+      r = objs_lanes(s, 0, false, off, &L);
+      if ( r == HIPSDP_OK ) r = objs_home_copy(s, L.dev, off, warm, true, true);
+      if ( r != HIPSDP_OK )
+         return leave(solve_end(s, r));
+      for (int j = 0; j < count; ++j)
+         later.push_back(j);
+   }
+   else
+   {
+      /* 2. the lanes: as many as a chunk has jobs */
+      int chunk = OBJS_CHUNK_MAX;
+      {
+         const long long per = (hs_objs_lane_layout(m, s->q, K, ns, 0, L.off) + hs_solve1_ws_doubles(m, s->q, K, ns) + 2) * (long long) sizeof(double);
+         if ( (long long) chunk * per > OBJS_LANE_BYTES )
+            chunk = (int) (OBJS_LANE_BYTES / per);
+         const char* env = getenv("HIPSDP_OBJECTIVES_CHUNK");          /* (read at every call, like the switches of the one-launch path) */
+         if ( env != NULL && atoi(env) > 0 )
+            chunk = atoi(env);
+         if ( chunk < 1 ) chunk = 1;
+         if ( chunk > count ) chunk = count;
+      }
+      r = objs_lanes(s, chunk, true, off, &L);
+      if ( r == HIPSDP_OK ) r = many_stage(s->device, (size_t) chunk, 0);
+      if ( r != HIPSDP_OK )
+         return leave(solve_end(s, r));
+      ManyStage& g = g_many;
+      std::vector<S1Prep> pp((size_t) chunk);
+      int cls = 0;
+      bool all_published = true;
+      for (int c0 = 0; c0 < count; c0 += chunk)
+      {
+         const int n = count - c0 < chunk ? count - c0 : chunk;
+         /* 3. the objectives of the chunk, rows of mp doubles: ONE upload through the staging arena (read there by the fan-out), or,
+          * when it has no room, a copy into device memory behind the lanes */
+         const size_t so = s->stage_off;
+         const double* Bsrc = NULL;
+         if ( m > 0 )
+         {
+            void* dv = NULL;
+            double* h = static_cast<double*>(stage_take(s, (size_t) n * L.mp * sizeof(double), &dv));
+            std::vector<double> tmp;
+            if ( h == NULL )
+            {
+               tmp.assign((size_t) n * L.mp, 0.0);
+               h = tmp.data();
+            }
+            for (int j = 0; j < n; ++j)
+            {
+               memcpy(h + (size_t) j * L.mp, B + (size_t) (c0 + j) * m, (size_t) m * sizeof(double));
+               if ( L.mp > m ) h[(size_t) j * L.mp + m] = 0.0;
+            }
+            if ( dv != NULL )
+               Bsrc = static_cast<const double*>(dv);
+            else
+            {
+               r = hipStreamSynchronize(st) == hipSuccess
+                  && hipMemcpy(L.Bdev, h, (size_t) n * L.mp * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? HIPSDP_OK : HIPSDP_ERR_HIP;
+               Bsrc = L.Bdev;
+            }
+         }
+         /* 4. the fan-out: every job's objective, and the start point when there is one, into its lane; the solver's own into lane 0 */
+         hs_fan_plan plan;
+         memset(&plan, 0, sizeof(plan));
+         {
+            auto seg = [&](const double* own, const double* src, long long stride, long long dst, long long len) {
+               if ( len <= 0 ) return;
+               hs_fan_seg& S = plan.seg[plan.nseg++];
+               S.src0 = own; S.src = src; S.stride = stride; S.dst = dst; S.len = len;
+            };
+            seg(s->b, Bsrc, L.mp, L.off[0], m);
+            if ( warm )
+            {
+               seg(s->y, s->y, 0, L.off[1], m);
+               seg(s->x, s->x, 0, L.off[2], s->q);
+               seg(s->z, s->z, 0, L.off[3], s->q);
+               for (int k = 0; k < K; ++k)
+               {
+                  const long long n2 = (long long) ns[k] * ns[k];
+                  seg(s->blk[k].X, s->blk[k].X, 0, L.off[4 + 2 * k], n2);
+                  seg(s->blk[k].Z, s->blk[k].Z, 0, L.off[5 + 2 * k], n2);
+               }
+            }
+         }
+         if ( r == HIPSDP_OK && plan.nseg > 0 )
+         {
+            r = hs_objs_fanout(st, &plan, L.dev, L.stride, n + 1);
+            if ( r == HIPSDP_OK )
+               (void) __sync_add_and_fetch(&g_objs_launches, 1);
+         }
+         /* 5. the kernel's arguments, one record per lane, and ONE launch of n workgroups on the solver's queue */
+         bool launched = false;
+         if ( r == HIPSDP_OK )
+         {
+            for (int j = 0; j < n && r == HIPSDP_OK; ++j)
+            {
+               S1Lane lane;
+               objs_lane(s, L, j, &lane);
+               *reinterpret_cast<volatile unsigned long long*>(lane.host + HS_S1_OUT_DOUBLES) = 0ULL;
+               bool off1 = false;
+               r = solve1_prepare(s, &pp[j], &off1, &lane);
+               if ( r == HIPSDP_OK && !off1 )
+                  r = HIPSDP_ERR_ARG;
+               if ( r == HIPSDP_OK )
+                  memcpy(&g.h[j], &pp[j].a, sizeof(hs_solve1_args));
+            }
+            if ( r == HIPSDP_OK && c0 == 0 )
+               cls = hs_solve1_class(&pp[0].a);
+            __atomic_thread_fence(__ATOMIC_RELEASE);
+            if ( r == HIPSDP_OK )
+               r = many_hip_ok(hipMemcpyAsync(g.d, g.h, (size_t) n * sizeof(hs_solve1_args), hipMemcpyHostToDevice, st),
+                     "hipMemcpyAsync(solve-objectives arguments)", __LINE__) ? HIPSDP_OK : HIPSDP_ERR_HIP;
+            if ( r == HIPSDP_OK )
+               r = hs_solve1_launch_many(st, cls, g.d, n) == HS_OK ? HIPSDP_OK : HIPSDP_ERR_HIP;
+            if ( r == HIPSDP_OK )
+            {
+               launched = true;
+               s->stage_pending = true;
+               (void) __sync_add_and_fetch(&g_objs_launches, 1);
+            }
+         }
+         if ( !launched )
+         {
+            /* nothing of this chunk runs: whatever was queued drains, the jobs from here on report the error */
+            (void) hipStreamSynchronize(st);
+            for (int j = c0; j < count; ++j) rc[j] = r != HIPSDP_OK ? r : HIPSDP_ERR_HIP;
+            all_published = false;
+            break;
+         }
+         /* 6. the sequence words of the chunk, polled together (hipsdp_solve_many's loop on one queue) */
+         std::vector<char> pend((size_t) n, 1);
+         {
+            int left = n;
+            auto published = [&](int j) -> bool {
+               const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(pp[j].host + HS_S1_OUT_DOUBLES);
+               return *flag == pp[j].a.seq;
+            };
+            long long spins = 0;
+            while ( left > 0 )
+            {
+               for (int j = 0; j < n; ++j)
+                  if ( pend[j] && published(j) ) { pend[j] = 0; --left; }
+               spins += left + 1;
+               if ( left == 0 || spins < 0x4000 )
+                  continue;
+               spins = 0;
+               const hipError_t e = hipStreamQuery(st);
+               if ( e == hipErrorNotReady )
+                  continue;
+               if ( e != hipSuccess )
+                  hs_record_hip_error(e, "hipStreamQuery(one-launch solve of many objectives)", __FILE__, __LINE__);
+               for (int j = 0; j < n; ++j)
+                  if ( pend[j] )
+                  {
+                     --left;
+                     if ( e == hipSuccess && published(j) ) { pend[j] = 0; continue; }
+                     if ( e == hipSuccess )
+                        set_err("the one-launch solve finished without publishing its results");
+                     rc[c0 + j] = HIPSDP_ERR_HIP;
+                  }
+            }
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+         }
+         /* 7. every job's results out of its lane's pinned part: no copy from the device */
+         bool chunk_ok = true;
+         for (int j = 0; j < n; ++j)
+         {
+            const int J = c0 + j;
+            if ( pend[j] ) { chunk_ok = false; continue; }
+            S1Sol sol;
+            bool done = false;
+            rc[J] = solve1_result(s, &pp[j], &infos[J], &sol, &done);
+            if ( rc[J] != HIPSDP_OK )
+               continue;
+            if ( !done )
+            {
+               later.push_back(J);
+               continue;
+            }
+            (void) __sync_add_and_fetch(&g_objs_problems, 1);
+            if ( Y != NULL )
+            {
+               const double* hy = pp[j].host + pp[j].hy;
+               for (int i = 0; i < m; ++i)
+                  Y[(size_t) J * m + i] = hy[i] * sol.sol_scale;
+            }
+         }
+         if ( !chunk_ok )
+         {
+            (void) hipStreamSynchronize(st);
+            for (int j = c0 + n; j < count; ++j) rc[j] = HIPSDP_ERR_HIP;
+            all_published = false;
+            break;
+         }
+         /* (the fan-out has read the objectives: the next chunk's take their place in the arena) */
+         s->stage_off = so;
+      }
+      if ( all_published )
+         s->stage_off = 0;                 /* (everything queued before the launches has run: the setters' data has been read) */
+      if ( !all_published )
+         later.clear();
+   }
+
+   /* 8. the jobs of the general path, one after another on the solver's own storage, each from the start the call was given; then the
+    * solver's own objective back.  The start point is consumed and the solver holds no solution. */
+   double* home = L.dev;
+   for (int J : later)
+      rc[J] = objs_general_job(s, params, B + (size_t) J * m, home, off, warm, &infos[J], Y != NULL ? Y + (size_t) J * m : NULL);
+   r = HIPSDP_OK;
+   if ( !later.empty() )
+      r = objs_home_copy(s, home, off, false, false, true);
+   s->have_start = false;
+   s->solved = false;
+   s->s1_last = 0;
+   s->s1_sol_host = false;
+   return leave(solve_end(s, r));
+}
+
+extern "C" int hipsdp_solve_objectives_stats(long long* calls, long long* launches, long long* problems)
+{
+   if ( calls != NULL )
+      *calls = __sync_add_and_fetch(&g_objs_calls, 0);
+   if ( launches != NULL )
+      *launches = __sync_add_and_fetch(&g_objs_launches, 0);
+   if ( problems != NULL )
+      *problems = __sync_add_and_fetch(&g_objs_problems, 0);
+   return HIPSDP_OK;
 }
 
 extern "C" int hipsdp_gram_cache_stats(hipsdp_solver* s, long long* hits, long long* misses)

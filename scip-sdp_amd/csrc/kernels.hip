@@ -318,6 +318,56 @@ __global__ void k_copy(long long n, const double* __restrict__ src, double* __re
       dst[i] = src[i];
 }
 
+/* ---- the lanes of hipsdp_solve_objectives (hs_kernels.h) */
+long long hs_objs_lane_layout(int m, int q, int nblk, const int* n, int gap, long long* off)
+{
+   long long t = 0;
+   int i = 0;
+   auto put = [&](long long len) { off[i++] = t; t += ((len + 1) & ~1LL) + gap; };
+   put(m); put(m); put(q); put(q);
+   for (int k = 0; k < nblk; ++k)
+   {
+      put((long long) n[k] * n[k]);
+      put((long long) n[k] * n[k]);
+   }
+   return t;
+}
+
+/* blockIdx.y: the segment, blockIdx.x (and on from there in steps of the grid): the lane; a copy in 16-byte pieces */
+__global__ void __launch_bounds__(256) k_objs_fanout(const hs_fan_plan P, double* __restrict__ lanes, long long lane_stride, int nlanes)
+{
+   typedef double fan_v2 __attribute__((ext_vector_type(2)));
+   const hs_fan_seg& S = P.seg[blockIdx.y];
+   const long long nv = S.len >> 1;
+   for (long long j = blockIdx.x; j < nlanes; j += gridDim.x)
+   {
+      const double* __restrict__ src = (j == 0) ? S.src0 : S.src + (j - 1) * S.stride;
+      double* __restrict__ dst = lanes + j * lane_stride + S.dst;
+      for (long long e = threadIdx.x; e < nv; e += 256)
+         reinterpret_cast<fan_v2*>(dst)[e] = reinterpret_cast<const fan_v2*>(src)[e];
+      if ( (S.len & 1) && threadIdx.x == 0 )
+         dst[S.len - 1] = src[S.len - 1];
+   }
+}
+
+int hs_objs_fanout(hipStream_t st, const hs_fan_plan* plan, double* lanes, long long lane_stride, int nlanes)
+{
+   if ( plan->nseg <= 0 || nlanes <= 0 )
+      return HS_OK;
+   if ( plan->nseg > HS_FAN_MAXSEG || (lane_stride & 1) || (reinterpret_cast<size_t>(lanes) & 15) )
+      return HS_ERR_ARG;
+   for (int i = 0; i < plan->nseg; ++i)
+   {
+      const hs_fan_seg& S = plan->seg[i];
+      if ( S.len <= 0 || (S.dst & 1) || (S.stride & 1) || (reinterpret_cast<size_t>(S.src0) & 15) || (reinterpret_cast<size_t>(S.src) & 15) )
+         return HS_ERR_ARG;
+   }
+   const int gx = nlanes < (1 << 20) ? nlanes : (1 << 20);
+   hipLaunchKernelGGL(k_objs_fanout, dim3(gx, plan->nseg), dim3(256), 0, st, *plan, lanes, lane_stride, nlanes);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
 int hs_copy(hipStream_t s, double* dst, const double* src, long long n)
 {
    (void) hs_red_batch_flush();          /* inside a held region: behind the records */

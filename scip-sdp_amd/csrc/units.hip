@@ -1664,3 +1664,81 @@ extern "C" int hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long lo
          HS_HIP( hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost) );
    return HIPSDP_OK;
 }
+
+/* the fan-out of hipsdp_solve_objectives alone (hs_objs_fanout, csrc/kernels.hip): the sources in device memory as the engine holds them
+ * (the objectives in rows of m rounded up to even), the lanes filled with the guard word, one launch, the lanes back */
+extern "C" int hipsdp_objs_fanout_unit(int device, int count, int m, int q, int nblk, const int* ns, const double* B, const double* b_own,
+   int have_start, const double* y, const double* x, const double* z, const double* XZ, int gap, double guard, long long* lane_len,
+   long long* offs, double* lanes, int* launches)
+{
+   if ( count < 1 || m < 0 || q < 0 || nblk < 0 || nblk > HS_S1_MAXBLK || (nblk > 0 && ns == NULL) || gap < 0 || (gap & 1) || lane_len == NULL
+      || offs == NULL || (have_start != 0 && have_start != 1) )
+      return HIPSDP_ERR_ARG;
+   for (int k = 0; k < nblk; ++k)
+      if ( ns[k] < 1 )
+         return HIPSDP_ERR_ARG;
+   const long long len = hs_objs_lane_layout(m, q, nblk, ns, gap, offs);
+   *lane_len = len;
+   if ( launches != NULL ) *launches = 0;
+   if ( lanes == NULL )
+      return HIPSDP_OK;
+   if ( (m > 0 && (B == NULL || b_own == NULL)) || (have_start && ((m > 0 && y == NULL) || (q > 0 && (x == NULL || z == NULL)) || (nblk > 0 && XZ == NULL))) )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long mp = (m + 1) & ~1LL, qp = (q + 1) & ~1LL;
+   /* the sources, each at an even offset: B (count rows of mp), b_own, y, x, z, X_0, Z_0, ... */
+   std::vector<long long> so;
+   long long tot = 0;
+   auto put = [&](long long n) { so.push_back(tot); tot += (n + 1) & ~1LL; };
+   put((long long) count * mp); put(m); put(m); put(q); put(q);
+   for (int k = 0; k < nblk; ++k) { put((long long) ns[k] * ns[k]); put((long long) ns[k] * ns[k]); }
+   std::vector<double> hs((size_t) tot + 2, 0.0);
+   for (int j = 0; j < count; ++j)
+      for (int i = 0; i < m; ++i)
+         hs[(size_t) (so[0] + j * mp + i)] = B[(size_t) j * m + i];
+   for (int i = 0; i < m; ++i) hs[(size_t) (so[1] + i)] = b_own[i];
+   if ( have_start )
+   {
+      for (int i = 0; i < m; ++i) hs[(size_t) (so[2] + i)] = y[i];
+      for (int i = 0; i < q; ++i) { hs[(size_t) (so[3] + i)] = x[i]; hs[(size_t) (so[4] + i)] = z[i]; }
+      const double* p = XZ;
+      for (int k = 0; k < 2 * nblk; ++k)
+      {
+         const long long n2 = (long long) ns[k / 2] * ns[k / 2];
+         for (long long e = 0; e < n2; ++e) hs[(size_t) (so[5 + k] + e)] = p[e];
+         p += n2;
+      }
+   }
+   (void) qp;
+   const long long nl = (long long) count + 1;
+   DevBuf dS, dL;
+   HS_CALL( dS.alloc(tot + 2) ); HS_CALL( dL.alloc(nl * len) );
+   HS_CALL( dS.up(hs.data(), tot) );
+   {
+      std::vector<double> fill((size_t) (nl * len), guard);
+      HS_CALL( dL.up(fill.data(), nl * len) );
+   }
+   hs_fan_plan plan;
+   memset(&plan, 0, sizeof(plan));
+   auto seg = [&](const double* own, const double* src, long long stride, long long dst, long long n) {
+      if ( n <= 0 ) return;
+      hs_fan_seg& S = plan.seg[plan.nseg++];
+      S.src0 = own; S.src = src; S.stride = stride; S.dst = dst; S.len = n;
+   };
+   seg(dS.p + so[1], dS.p + so[0], mp, offs[0], m);
+   if ( have_start )
+   {
+      seg(dS.p + so[2], dS.p + so[2], 0, offs[1], m);
+      seg(dS.p + so[3], dS.p + so[3], 0, offs[2], q);
+      seg(dS.p + so[4], dS.p + so[4], 0, offs[3], q);
+      for (int k = 0; k < 2 * nblk; ++k)
+         seg(dS.p + so[5 + k], dS.p + so[5 + k], 0, offs[4 + k], (long long) ns[k / 2] * ns[k / 2]);
+   }
+   if ( plan.nseg > 0 )
+   {
+      HS_CALL( hs_objs_fanout(0, &plan, dL.p, len, (int) nl) );
+      if ( launches != NULL ) *launches = 1;
+   }
+   HS_HIP( hipDeviceSynchronize() );
+   return dL.down(lanes, nl * len);
+}
