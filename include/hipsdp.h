@@ -435,6 +435,43 @@ HIPSDP_API int hipsdp_onevar_bounds(hipsdp_solver* solver, int block, const doub
  * pointers are accepted; works without a device) */
 HIPSDP_API int hipsdp_onevar_bounds_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* The same one-variable SDPs for ALL blocks of the solver in one call: a round of tightenBounds / tightenMatrices runs over all
+ * constraints (for (c = 0; c < nconss; ++c)), and a call per block leaves most of the device idle and waits for the host once per
+ * block.  Job j is the pair (blocks[j], vars[j]) with kind[j] and the bounds lb[j], ub[j]; u: the m engine variables, ONE vector for
+ * the call (u = ub: tightenBounds, u = 0: tightenMatrices).  blocks == NULL AND vars == NULL: every (block, variable) pair in
+ * block-major order (job b m + i is variable i of block b), count must be nblocks * m; exactly one of the two NULL is an error.
+ * kind == NULL: all NEWTON.
+ *   HIPSDP_ONEVAR_NEWTON, HIPSDP_ONEVAR_TWOPOINT: as hipsdp_onevar_bounds documents them, DECLINED and GAVEUP included, on
+ *     M(mu) = Z_b(u) + (mu - u_i) A_i^b, and with the BITS hipsdp_onevar_bounds(solver, block, u, 1, &var, &kind, &lb, &ub, opts, ..)
+ *     returns for the job on the same solver.
+ *   HIPSDP_ONEVAR_EXTREMES (this call alone): lmin = lambda_min(A_i^b), optval = lambda_max(A_i^b), grad = 0, evals = 2, status
+ *     HIPSDP_ONEVAR_DONE - what the lock computation asks of every A_i (cons_sdp.c:4007/:4020, :4096/:4104, :6787/:6809).  It reads
+ *     neither u nor the job's bounds, so it is never DECLINED; GAVEUP if an eigenvalue is not finite.  With opts->maxevals == 1
+ *     lambda_min ALONE is computed: evals = 1, optval = lmin, status DONE - the precondition allmatricespsd of both loops
+ *     (computeAllmatricespsd, cons_sdp.c:1832-1842), one job per (block, variable).  A block of one row is a scalar.
+ * A job gets status[j] = -1 and nothing else written when its block has more than HIPSDP_ONEVAR_MAXN rows or no matrices on this
+ * device; the OTHER jobs of the call are still served.  A solver with a communicator or with sharded matrices: every status -1,
+ * nothing launched.
+ * Whatever the number of blocks, jobs and evaluations: ONE upload (u, the job table, bounds and kinds in one buffer), ONE launch of
+ * the Z(u) kernel over the blocks with a served NEWTON or TWOPOINT job (none: left out), ONE launch per size class with a served job
+ * (up to 64 rows: a workgroup per job; 65 to 128 rows: at most a workgroup per compute unit, each running its jobs one after the
+ * other in its own slab, so the workspace is bounded by the grid - 64 MB on 256 compute units - not by the job count), ONE
+ * read-back.  The bits of a job depend neither on the other jobs of the call nor on their order; same input, same bits.  Two host
+ * threads may call it at the same time on different solvers.
+ * HIPSDP_ERR_ARG, checked before the device is looked at, nothing launched: solver NULL or without a shape, u, lb, ub, opts, status or
+ * optval NULL, count < 0, a block index outside [0, nblocks), a variable index outside [0, m), a kind outside {0, 1, 2}, feastol < 0,
+ * one of blocks / vars NULL without the other, both NULL with count != nblocks * m.  count == 0: HIPSDP_OK, nothing launched.
+ * lmin, grad and evals may be NULL. */
+#define HIPSDP_ONEVAR_EXTREMES  2   /* kind, accepted by hipsdp_onevar_bounds_all ONLY: lambda_min and lambda_max of A_i alone */
+#define HIPSDP_ONEVAR_DONE      6   /* status of an EXTREMES job */
+HIPSDP_API int hipsdp_onevar_bounds_all(hipsdp_solver* solver, const double* u, int count,
+   const int* blocks, const int* vars, const int* kind, const double* lb, const double* ub,
+   const hipsdp_onevar_opts* opts,
+   int* status, double* optval, double* lmin, double* grad, int* evals);
+/* process totals: calls that served at least one job, kernel launches they issued, device->host synchronisations they waited on
+ * (NULL pointers are accepted; works without a device).  The totals of hipsdp_onevar_bounds_stats do not move, and the reverse. */
+HIPSDP_API int hipsdp_onevar_bounds_all_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves
  * them alone with the single-rank kernels and rank 0's outcome (status, iterate, preoptimal iterate) is broadcast once per solve. */

@@ -166,6 +166,13 @@ HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long l
  * hipsdp_onevar_bounds returns them (lmin, grad, evals may be NULL). */
 HIPSDP_API int  hipsdp_onevar_unit(int device, int n, int count, const double* Z, const double* A, const double* shift, const int* kind,
    const double* lb, const double* ub, double feastol, int maxevals, int* status, double* optval, double* lmin, double* grad, int* evals);
+/* the launches of hipsdp_onevar_bounds_all (csrc/eigi.hip: k_onevar_all_small, k_onevar_all_mid) alone on host matrices given PER JOB:
+ * job j < count has n[j] rows (1 .. 128), Z + zoff[j] (n[j]^2 doubles) and the dense A + zoff[j] (the same offsets: zoff[j] = sum of
+ * n[k]^2, k < j), shift[j], kind[j] (NULL: all NEWTON; EXTREMES allowed), lb[j], ub[j].  mid_cap >= 1: the cap on the grid of the
+ * 65-128 launch (the product call passes the device's compute units), so that a handful of jobs stride.  infinity is 1e20. */
+HIPSDP_API int  hipsdp_onevar_all_unit(int device, int count, const int* n, const double* Z, const double* A, const double* shift,
+   const int* kind, const double* lb, const double* ub, double feastol, int maxevals, int mid_cap,
+   int* status, double* optval, double* lmin, double* grad, int* evals);
 /* the fan-out kernel of hipsdp_solve_objectives (hs_objs_fanout, csrc/kernels.hip) alone: count jobs of a problem with m variables, q LP
  * rows and nblk blocks of ns[k] rows.  B: count x m objectives, b_own[m]: the solver's own; have_start = 1: the start point y[m], x[q],
  * z[q] and XZ = X_0, Z_0, X_1, Z_1, ... one behind the other (have_start = 0: not read, only the objectives are fanned out).

@@ -922,21 +922,29 @@ __global__ void __launch_bounds__(EM_NT) k_syevi_mid(int n, int ith, int wantvec
 #define OV_TP_LB 3            /* TWOPOINT */
 #define OV_TP_UB 4
 #define OV_DONE 5
+#define OV_EX 6               /* EXTREMES (k_onevar_all_* alone): the extreme eigenvalues of A_i, no point at all */
+#define OV_ST_DONE 6
 struct ov_state { double mu, ub, lb, shift, f, g, optval; int at, evals, status, wantvec; };
+/* what the loop of a job takes from its launch, and the job itself: its block (blk != NULL: an entry of a job table in device memory,
+ * Z(u) at blk->Z = Z, A_i from the block's storage form; blk == NULL: Z and the dense A are given), its row of the table and its row
+ * of the result.  k_onevar_small / k_onevar_mid fill it from the ONE block of their launch, k_onevar_all_small / k_onevar_all_mid per
+ * job: the bodies below are the same code for both, so the bits of a job cannot depend on the call that carries it. */
+struct ov_ctl { int maxevals; double feastol, infinity; };
+struct ov_job { int n; const hs_ec_job* blk; const double* Z; const double* A; const double* tab; double* res; };
 
-/* the dense A_i (n x n, no pitch) of job j into dst (LDS or device memory); contains barriers */
-__device__ __forceinline__ void ov_stage_a(const hs_ov_par& P, int j, int var, double* dst)
+/* the dense A_i (n x n, no pitch) of the job into dst (LDS or device memory); contains barriers */
+__device__ __forceinline__ void ov_stage_a(const ov_job& J, int var, double* dst)
 {
-   const int n = P.n, tid = threadIdx.x, nt = (int) blockDim.x;
-   if ( P.blk == NULL )
+   const int n = J.n, tid = threadIdx.x, nt = (int) blockDim.x;
+   if ( J.blk == NULL )
    {
-      const double* __restrict__ a = P.A + (long long) j * n * n;
+      const double* __restrict__ a = J.A;
       for (int e = tid; e < n * n; e += nt)
          dst[e] = a[e];
    }
-   else if ( P.blk->form == HS_EC_SPARSE )
+   else if ( J.blk->form == HS_EC_SPARSE )
    {
-      const hs_sp_view sp = P.blk->sp;
+      const hs_sp_view sp = J.blk->sp;
       for (int e = tid; e < n * n; e += nt)
          dst[e] = 0.0;
       __syncthreads();
@@ -954,8 +962,8 @@ __device__ __forceinline__ void ov_stage_a(const hs_ov_par& P, int j, int var, d
    }
    else
    {
-      const bool packed = P.blk->form == HS_EC_PACKED;
-      const double* __restrict__ a = P.blk->A + (long long) (var + 1) * P.blk->ld;
+      const bool packed = J.blk->form == HS_EC_PACKED;
+      const double* __restrict__ a = J.blk->A + (long long) (var + 1) * J.blk->ld;
       for (int e = tid; e < n * n; e += nt)
       {
          const int r0 = e / n, c0 = e - r0 * n;
@@ -967,13 +975,19 @@ __device__ __forceinline__ void ov_stage_a(const hs_ov_par& P, int j, int var, d
 }
 
 /* thread 0, before the first evaluation */
-__device__ __forceinline__ void ov_begin(const hs_ov_par& P, int j, ov_state* S)
+__device__ __forceinline__ void ov_begin(const ov_ctl& P, const ov_job& J, ov_state* S)
 {
-   const double* __restrict__ t = P.tab + (long long) j * HS_OV_TAB;
+   const double* __restrict__ t = J.tab;
    const int kind = (int) t[1];
    S->lb = t[2]; S->ub = t[3]; S->shift = t[4];
    S->f = 0.0; S->g = 0.0; S->optval = 0.0; S->evals = 0; S->status = OV_ST_DECLINED;
    S->wantvec = kind == 0 ? 1 : 0;
+   if ( kind == 2 )                     /* EXTREMES reads neither u nor the bounds: never declined */
+   {
+      S->at = OV_EX;
+      S->mu = 0.0;
+      return;
+   }
    if ( S->lb <= -P.infinity || S->ub >= P.infinity )
    {
       S->at = OV_DONE;
@@ -986,7 +1000,7 @@ __device__ __forceinline__ void ov_begin(const hs_ov_par& P, int j, ov_state* S)
 
 /* thread 0, after the evaluation at S->mu gave (f, g): the comparisons of solveonevarsdp.c:434-525 in their order, or those of
  * cons_sdp.c:2119 / :2143; sets the next point or the result */
-__device__ __forceinline__ void ov_decide(const hs_ov_par& P, ov_state* S, double f, double g)
+__device__ __forceinline__ void ov_decide(const ov_ctl& P, ov_state* S, double f, double g)
 {
    const double feastol = P.feastol, here = S->mu;
    const int at = S->at;
@@ -1033,36 +1047,75 @@ __device__ __forceinline__ void ov_decide(const hs_ov_par& P, ov_state* S, doubl
    S->at = next;
 }
 
-__device__ __forceinline__ void ov_store(const hs_ov_par& P, int j, const ov_state* S)
+/* thread 0 of an EXTREMES job, after eigenvalue number S->evals + 1 of its (at most two): lambda_min first, lambda_max second; with
+ * maxevals == 1 lambda_min alone (optval = lmin: what computeAllmatricespsd asks) */
+__device__ __forceinline__ void ov_extreme(const ov_ctl& P, ov_state* S, double ev)
 {
-   double* __restrict__ r = P.res + (long long) j * HS_OV_RES;
+   if ( S->evals == 0 )
+      S->f = ev;
+   S->optval = ev;
+   ++S->evals;
+   S->g = 0.0;
+   S->status = isfinite(S->f) && isfinite(ev) ? OV_ST_DONE : OV_ST_GAVEUP;
+   if ( S->evals >= 2 || S->evals >= P.maxevals || S->status == OV_ST_GAVEUP )
+      S->at = OV_DONE;
+}
+
+__device__ __forceinline__ void ov_store(const ov_job& J, const ov_state* S)
+{
+   double* __restrict__ r = J.res;
    r[0] = (double) S->status; r[1] = S->optval; r[2] = S->f; r[3] = S->g; r[4] = (double) S->evals; r[5] = 0.0;
 }
 
-__global__ void __launch_bounds__(256) k_onevar_small(hs_ov_par P)
+/* a job of at most 64 rows, the whole workgroup (256 threads); ov_dyn: 3 n^2 doubles of LDS laid out with the JOB's n.  EX: the launch
+ * may carry EXTREMES jobs (k_onevar_small is compiled without that branch, as it was) */
+template<bool EX>
+__device__ __forceinline__ void ov_run_small(const ov_ctl& P, const ov_job& J, double* ov_dyn)
 {
-   extern __shared__ __attribute__((aligned(16))) double ov_dyn[];
    __shared__ ov_state S;
    __shared__ double eo[EI_N + 2], part[4];
-   const int j = blockIdx.x, n = P.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int n = J.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    double* sz = ov_dyn;                 /* Z(u) */
    double* sa = sz + n * n;             /* A_i */
    double* sm = sa + n * n;             /* M(mu) */
    if ( tid == 0 )
-      ov_begin(P, j, &S);
+      ov_begin(P, J, &S);
    __syncthreads();
    if ( S.at == OV_DONE )               /* (declined: the same in every thread) */
    {
       if ( tid == 0 )
-         ov_store(P, j, &S);
+         ov_store(J, &S);
+      return;
+   }
+   if ( EX && S.at == OV_EX )
+   {
+      /* the eigenpair body leaves its input as it is: A_i is staged once */
+      ov_stage_a(J, (int) J.tab[0], sa);
+      for (int round = 0; round < 2; ++round)
+      {
+         if ( n == 1 )
+         {
+            if ( tid == 0 ) eo[0] = sa[0];
+         }
+         else
+            d_syevi_small<false>(n, round == 0 ? 1 : n, 0, sa, eo, 0ULL, NULL);
+         __syncthreads();
+         if ( tid == 0 )
+            ov_extreme(P, &S, eo[0]);
+         __syncthreads();
+         if ( S.at == OV_DONE )
+            break;
+      }
+      if ( tid == 0 )
+         ov_store(J, &S);
       return;
    }
    {
-      const double* __restrict__ Z = P.blk != NULL ? P.blk->Z : P.Z;
+      const double* __restrict__ Z = J.Z;
       for (int e = tid; e < n * n; e += 256)
          sz[e] = Z[e];
    }
-   ov_stage_a(P, j, (int) P.tab[(long long) j * HS_OV_TAB], sa);
+   ov_stage_a(J, (int) J.tab[0], sa);
    /* at most maxevals rounds: ov_decide ends the job at that count */
    for (int round = 0; round < P.maxevals; ++round)
    {
@@ -1098,27 +1151,47 @@ __global__ void __launch_bounds__(256) k_onevar_small(hs_ov_par P)
          break;
    }
    if ( tid == 0 )
-      ov_store(P, j, &S);
+      ov_store(J, &S);
 }
 
-__global__ void __launch_bounds__(EM_NT) k_onevar_mid(hs_ov_par P)
+/* a job of 65 to 128 rows, the whole workgroup (EM_NT threads); slab: 2 n^2 doubles of device memory that this workgroup alone
+ * touches while the job runs (the dense A_i and M(mu), laid out with the JOB's n) */
+template<bool EX>
+__device__ __forceinline__ void ov_run_mid(const ov_ctl& P, const ov_job& J, double* slab)
 {
    __shared__ ov_state S;
    __shared__ double eo[EM_N + 2], part[EM_NT / 64];
-   const int j = blockIdx.x, n = P.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   double* ga = P.slab + 2LL * j * n * n;       /* A_i */
+   const int n = J.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   double* ga = slab;                           /* A_i */
    double* gm = ga + (long long) n * n;         /* M(mu) */
    if ( tid == 0 )
-      ov_begin(P, j, &S);
+      ov_begin(P, J, &S);
    __syncthreads();
    if ( S.at == OV_DONE )
    {
       if ( tid == 0 )
-         ov_store(P, j, &S);
+         ov_store(J, &S);
       return;
    }
-   const double* __restrict__ Z = P.blk != NULL ? P.blk->Z : P.Z;
-   ov_stage_a(P, j, (int) P.tab[(long long) j * HS_OV_TAB], ga);
+   const double* __restrict__ Z = J.Z;
+   ov_stage_a(J, (int) J.tab[0], ga);
+   if ( EX && S.at == OV_EX )
+   {
+      /* (d_syevi_mid reads its input into LDS and leaves it as it is) */
+      for (int round = 0; round < 2; ++round)
+      {
+         d_syevi_mid(n, round == 0 ? 1 : n, 0, ga, eo, 0ULL, NULL);
+         __syncthreads();
+         if ( tid == 0 )
+            ov_extreme(P, &S, eo[0]);
+         __syncthreads();
+         if ( S.at == OV_DONE )
+            break;
+      }
+      if ( tid == 0 )
+         ov_store(J, &S);
+      return;
+   }
    for (int round = 0; round < P.maxevals; ++round)
    {
       const double s = S.mu - S.shift;
@@ -1154,7 +1227,73 @@ __global__ void __launch_bounds__(EM_NT) k_onevar_mid(hs_ov_par P)
          break;
    }
    if ( tid == 0 )
-      ov_store(P, j, &S);
+      ov_store(J, &S);
+}
+
+__device__ __forceinline__ ov_ctl ov_ctl_of(int maxevals, double feastol, double infinity)
+{
+   ov_ctl C;
+   C.maxevals = maxevals; C.feastol = feastol; C.infinity = infinity;
+   return C;
+}
+
+/* job j of a launch over ONE block */
+__device__ __forceinline__ ov_job ov_job_of(const hs_ov_par& P, int j)
+{
+   ov_job J;
+   J.n = P.n; J.blk = P.blk;
+   J.Z = P.blk != NULL ? P.blk->Z : P.Z;
+   J.A = P.blk != NULL ? NULL : P.A + (long long) j * P.n * P.n;
+   J.tab = P.tab + (long long) j * HS_OV_TAB;
+   J.res = P.res + (long long) j * HS_OV_RES;
+   return J;
+}
+
+/* row `row` of the table of a launch over MANY blocks (hipsdp_onevar_bounds_all): its block from the job table, its result at its slot */
+__device__ __forceinline__ ov_job ov_job_of(const hs_ova_par& P, int row)
+{
+   const double* __restrict__ t = P.tab + (long long) row * HS_OVA_TAB;
+   const hs_ec_job* blk = P.jobs + (int) t[5];
+   ov_job J;
+   J.n = blk->n; J.blk = blk; J.Z = blk->Z; J.A = NULL;
+   J.tab = t;
+   J.res = P.res + (long long) t[6] * HS_OV_RES;
+   return J;
+}
+
+__global__ void __launch_bounds__(256) k_onevar_small(hs_ov_par P)
+{
+   extern __shared__ __attribute__((aligned(16))) double ov_dyn[];
+   ov_run_small<false>(ov_ctl_of(P.maxevals, P.feastol, P.infinity), ov_job_of(P, (int) blockIdx.x), ov_dyn);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_onevar_mid(hs_ov_par P)
+{
+   const int j = blockIdx.x;
+   ov_run_mid<false>(ov_ctl_of(P.maxevals, P.feastol, P.infinity), ov_job_of(P, j), P.slab + 2LL * j * P.n * P.n);
+}
+
+/* ---- the same jobs over ALL blocks of a solver (hipsdp_onevar_bounds_all): n and the block come from the job's row of the table.
+ *   - k_onevar_all_small: one workgroup per row, dynamic LDS 3 nmax^2 doubles for the largest block of the launch, a job's three
+ *     matrices laid out with ITS n (ov_run_small), so its sums run in the order of k_onevar_small.
+ *   - k_onevar_all_mid: at most one workgroup per compute unit; workgroup w runs the rows w, w + grid, w + 2 grid, ... one after the
+ *     other in ITS slab of 2 nmax^2 doubles - the slab of a launch is bounded by the grid, not by the number of jobs.  The barrier
+ *     behind a job stands between its last read of the slab (and of the job's state in LDS) and the staging of the next one. */
+__global__ void __launch_bounds__(256) k_onevar_all_small(hs_ova_par P)
+{
+   extern __shared__ __attribute__((aligned(16))) double ov_dyn[];
+   ov_run_small<true>(ov_ctl_of(P.maxevals, P.feastol, P.infinity), ov_job_of(P, (int) blockIdx.x), ov_dyn);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_onevar_all_mid(hs_ova_par P)
+{
+   double* slab = P.slab + 2LL * blockIdx.x * P.nmax * P.nmax;
+   const ov_ctl C = ov_ctl_of(P.maxevals, P.feastol, P.infinity);
+   for (int row = blockIdx.x; row < P.count; row += (int) gridDim.x)
+   {
+      ov_run_mid<true>(C, ov_job_of(P, row), slab);
+      __syncthreads();
+   }
 }
 
 
@@ -2001,6 +2140,34 @@ int hs_onevar_newton(hipStream_t st, const hs_ov_par* P)
       static hs_attr_mask attr_mid;
       HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
       hipLaunchKernelGGL(k_onevar_mid, dim3(P->count), dim3(EM_NT), (size_t) P->n * (P->n | 1) * sizeof(double), st, *P);
+   }
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* a launch of hipsdp_onevar_bounds_all: cls 0 - the rows are jobs of at most 64 rows, one workgroup each; cls 1 - 65 to 128 rows,
+ * P->grid workgroups that stride over the rows, slab: P->grid x 2 nmax^2 doubles */
+int hs_onevar_all(hipStream_t st, int cls, const hs_ova_par* P)
+{
+   if ( P->count <= 0 )
+      return HS_OK;
+   if ( P->maxevals < 1 || P->jobs == NULL || P->tab == NULL || P->res == NULL || P->nmax < 1 )
+      return HS_ERR_ARG;
+   if ( cls == 0 )
+   {
+      if ( P->nmax > EI_N )
+         return HS_ERR_ARG;
+      static hs_attr_mask attr_small;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_all_small), 3 * EI_N * EI_N * (int) sizeof(double), &attr_small) );
+      hipLaunchKernelGGL(k_onevar_all_small, dim3(P->count), dim3(256), (size_t) 3 * P->nmax * P->nmax * sizeof(double), st, *P);
+   }
+   else
+   {
+      if ( P->nmax <= EI_N || P->nmax > EM_N || P->slab == NULL || P->grid < 1 || P->grid > P->count )
+         return HS_ERR_ARG;
+      static hs_attr_mask attr_mid;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_all_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
+      hipLaunchKernelGGL(k_onevar_all_mid, dim3(P->grid), dim3(EM_NT), (size_t) P->nmax * (P->nmax | 1) * sizeof(double), st, *P);
    }
    HS_HIP( hipGetLastError() );
    return HS_OK;

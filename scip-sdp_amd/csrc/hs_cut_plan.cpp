@@ -61,3 +61,15 @@ void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, l
    L->len.pin_len = ylen + (L->len.res_len > out_vec ? L->len.res_len : out_vec);      /* maxcuts = 0 reads the head of o1 back */
    L->len.dev_len = L->MT + hs_cut_mat_len(n);
 }
+
+void hs_ova_layout_make(int m, int count, int tabw, int resw, long long z_len, int mid_grid, int mid_nmax, hs_ova_layout* L)
+{
+   L->u = 0;
+   L->tab = even(m);
+   L->res = L->tab + (long long) count * tabw;
+   L->Z = even(L->res + (long long) count * resw);
+   L->slabs = L->Z + even(z_len);
+   L->len.res_off = L->res; L->len.res_len = (long long) count * resw;
+   L->len.upload_len = L->res; L->len.pin_len = L->res + L->len.res_len;
+   L->len.dev_len = L->slabs + 2LL * mid_grid * mid_nmax * mid_nmax;
+}

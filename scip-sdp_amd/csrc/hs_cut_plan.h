@@ -34,6 +34,11 @@ struct hs_scl_layout { long long y; hs_cut_res r; long long Z, ws, o1, o2, MT; h
  * slab of the decomposition of Z_S */
 struct hs_scr_layout { hs_sc_layout sc; long long state; hs_cut_lens len; };
 
+/* hipsdp_onevar_bounds_all (csrc/onevar.hip):  u[m] | table [count][tabw] | result [count][resw] | Z of every block with jobs | slabs of
+ * the 65-128 class (mid_grid workgroups x 2 mid_nmax^2: bounded by the launch grid, whatever the job count).  table, Z and slabs start
+ * at even offsets; the pinned mirror holds u, table and result */
+struct hs_ova_layout { long long u, tab, res, Z, slabs; hs_cut_lens len; };
+
 /* what a block's loop keeps in the workspace between the launches of two rounds, besides the deflated Z (in place in its slab) */
 struct hs_scr_state { double maxeig; int nc, iters, flags, done; };
 #define HS_SCR_STATE_LEN 4             /* doubles set aside for it */
@@ -63,6 +68,9 @@ void hs_sc_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, 
 void hs_scr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, long long slab_len, long long state_len, hs_scr_layout* L);
 /* ws_len = hs_syevx_ws(n), out_len = HS_SYEVX_OUT(n), out_vec = HS_SYEVX_OUT_VEC (csrc/syevx.hip), passed in as numbers */
 void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, long long out_len, long long out_vec, hs_scl_layout* L);
+
+/* z_len: sum of hs_cut_mat_len(n) over the blocks with jobs; mid_grid = 0: no job of the 65-128 class */
+void hs_ova_layout_make(int m, int count, int tabw, int resw, long long z_len, int mid_grid, int mid_nmax, hs_ova_layout* L);
 
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)

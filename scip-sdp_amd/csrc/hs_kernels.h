@@ -376,6 +376,22 @@ struct hs_ov_par
 };
 long long hs_onevar_slab(int n, int count);
 int hs_onevar_newton(hipStream_t st, const hs_ov_par* P);
+/* ... and of ALL blocks of a solver in one call (hipsdp_onevar_bounds_all): a row of the table carries the job's block and its slot */
+#define HS_OVA_TAB 8       /* doubles of a row: the five of HS_OV_TAB, the index of the block's entry in `jobs`, the job's slot in the result, 0 */
+#define HS_OV_KIND_EXTREMES 2    /* = HIPSDP_ONEVAR_EXTREMES, in these launches alone: lambda_min and lambda_max of A_i, no Z */
+/* one launch of one size class (hs_onevar_all): count rows in workgroup order; jobs: the hs_ec_job table of the blocks (Z(u) at Z, no
+ * decomposition slab); nmax: the largest block among the rows; res: job of slot k at res + k HS_OV_RES.  Class 1 (65 to 128 rows): grid
+ * workgroups, workgroup w runs the rows w, w + grid, ... in its own slab + w 2 nmax^2. */
+struct hs_ova_par
+{
+   int count, grid, maxevals, nmax;
+   double feastol, infinity;
+   const hs_ec_job* jobs;
+   const double* tab;            /* [count][HS_OVA_TAB] */
+   double* slab;
+   double* res;
+};
+int hs_onevar_all(hipStream_t st, int cls, const hs_ova_par* P);
 
 /* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
 #define HS_SC_MAXN 128
@@ -426,6 +442,9 @@ int hs_scl_coefs(hipStream_t st, int m, int maxcuts, int size, const hs_ec_job* 
  * hs_solver_cut_job: *served = 0 (nothing else done) for a solver with a communicator or sharded matrices or a block without matrices
  *    on this device; else as hs_solver_cut_enter, the workspace holds dev_len / pin_len doubles, and its job table is the block's
  *    hs_ec_job with Z at dev + zoff and ws at dev + wsoff (wsoff < 0: none).
+ * hs_solver_cut_blocks: behind hs_solver_cut_enter(s, -1, ..), for a subset `ids` of the blocks it gave, in any order: the workspace
+ *    holds dev_len / pin_len doubles, and its job table is their hs_ec_job in that order, Z of ids[j] at dev + zoff[j], no
+ *    decomposition slab (hipsdp_onevar_bounds_all); uploaded only when it differs from what the device holds, as every table.
  * hs_solver_eigencuts_block: hipsdp_eigencuts behind its argument checks (maxcuts may be 0), lam0: the block's first eigenvalue. */
 struct hipsdp_solver;
 struct hs_solver_cut_ws
@@ -443,6 +462,8 @@ int hs_solver_cut_prepare(hipsdp_solver* s, const std::vector<int>& ids, const s
 int hs_solver_cut_rounds(hipsdp_solver* s, const std::vector<hs_scr_job>& xjobs, const std::vector<hs_eig_job>& sjobs, hs_solver_cut_ws* w);
 int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long pin_len, long long zoff, long long wsoff, hs_solver_cut_ws* w,
    int* served);
+int hs_solver_cut_blocks(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& zoff, long long dev_len,
+   long long pin_len, hs_solver_cut_ws* w);
 int hs_solver_eigencuts_block(hipsdp_solver* s, int block, const double* y, double tol, int maxcuts, int* ncuts, double* eigvals,
    double* coefs, double* lhs, double* vecs, double* lam0);
 

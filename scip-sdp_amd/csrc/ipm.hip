@@ -5762,7 +5762,7 @@ extern "C" int hipsdp_eigencuts(hipsdp_solver* s, int block, const double* y, do
    return eigencuts_one(s, block, y, tol, maxcuts, ncuts, eigvals, coefs, lhs, vecs, NULL);
 }
 
-/* ---- what the cut calls of many blocks (csrc/cut_calls.hip) and hipsdp_onevar_bounds (csrc/onevar.hip) need of a solver: its shape, the
+/* ---- what the cut calls of many blocks (csrc/cut_calls.hip) and hipsdp_onevar_bounds[_all] (csrc/onevar.hip) need of a solver: its shape, the
  * blocks their shared launches serve, the cut workspace with its job tables, the per-block path (declared in hs_kernels.h) ------------ */
 int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks)
 {
@@ -5898,6 +5898,25 @@ int hs_solver_cut_job(hipsdp_solver* s, int block, long long dev_len, long long 
    HS_CALL( cw.upload(job, std::vector<hs_eig_job>()) );
    cw.view(s->stream, w);
    *served = 1;
+   return HS_OK;
+}
+
+int hs_solver_cut_blocks(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& zoff, long long dev_len,
+   long long pin_len, hs_solver_cut_ws* w)
+{
+   const int nj = (int) ids.size();
+   CutWs& cw = s->cw;
+   HS_CALL( cw.grow(dev_len, pin_len, (size_t) nj * sizeof(hs_ec_job)) );
+   std::vector<hs_ec_job> jobs((size_t) nj);
+   for (int j = 0; j < nj; ++j)
+   {
+      memset(&jobs[j], 0, sizeof(hs_ec_job));
+      ec_job_form(s->blk[ids[j]], &jobs[j]);
+      jobs[j].blk = ids[j];
+      jobs[j].Z = cw.dev + zoff[j];
+   }
+   HS_CALL( cw.upload(jobs, std::vector<hs_eig_job>()) );
+   cw.view(s->stream, w);
    return HS_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "../../include/hipsdp.h"
 #include "../../include/hipsdp_units.h"
 #include <vector>
+#include <algorithm>
 #include <cstring>
 #include <cstdlib>
 
@@ -1547,6 +1548,92 @@ extern "C" int hipsdp_onevar_unit(int device, int n, int count, const double* Z,
    {
       const double* r = h.data() + (size_t) j * HS_OV_RES;
       if ( !(r[0] >= 0.0 && r[0] <= (double) HIPSDP_ONEVAR_GAVEUP) )
+         return HIPSDP_ERR_NUMERIC;
+      status[j] = (int) r[0];
+      optval[j] = r[1];
+      if ( lmin != NULL ) lmin[j] = r[2];
+      if ( grad != NULL ) grad[j] = r[3];
+      if ( evals != NULL ) evals[j] = (int) r[4];
+   }
+   return HIPSDP_OK;
+}
+
+/* the launches of hipsdp_onevar_bounds_all alone (csrc/eigi.hip: k_onevar_all_small / k_onevar_all_mid) on host matrices per job: every
+ * job is a block of its own in the table of hs_ec_job - dense rows, row 0 (the constant matrix, never read here) and row 1 = A_j,
+ * the job's variable index 0 - so the kernels take the path they take in the product call */
+extern "C" int hipsdp_onevar_all_unit(int device, int count, const int* n, const double* Z, const double* A, const double* shift,
+   const int* kind, const double* lb, const double* ub, double feastol, int maxevals, int mid_cap,
+   int* status, double* optval, double* lmin, double* grad, int* evals)
+{
+   HS_CALL( pick_device(device) );
+   if ( count < 1 || n == NULL || Z == NULL || A == NULL || shift == NULL || lb == NULL || ub == NULL || !(feastol >= 0.0) || mid_cap < 1
+      || status == NULL || optval == NULL )
+      return HIPSDP_ERR_ARG;
+   std::vector<long long> off((size_t) count + 1, 0);
+   std::vector<int> small, mid;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( n[j] < 1 || n[j] > HS_OV_MAXN )
+         return HIPSDP_ERR_ARG;
+      if ( kind != NULL && (kind[j] < 0 || kind[j] > HS_OV_KIND_EXTREMES) )
+         return HIPSDP_ERR_ARG;
+      off[j + 1] = off[j] + (long long) n[j] * n[j];
+      (n[j] <= 64 ? small : mid).push_back(j);
+   }
+   std::stable_sort(mid.begin(), mid.end(), [&](int a, int c) { return n[a] > n[c]; });
+   const long long tot = off[count];
+   DevBuf dz, da, dtab, dres, dslab, djobs;
+   HS_CALL( dz.alloc(tot) ); HS_CALL( da.alloc(2 * tot) ); HS_CALL( dtab.alloc((long long) count * HS_OVA_TAB) );
+   HS_CALL( dres.alloc((long long) count * HS_OV_RES) );
+   HS_CALL( djobs.alloc((long long) ((size_t) count * sizeof(hs_ec_job) + sizeof(double) - 1) / (long long) sizeof(double)) );
+   /* the two rows of job j at da + 2 off[j] */
+   std::vector<double> ha((size_t) (2 * tot), 0.0), tab((size_t) count * HS_OVA_TAB, 0.0);
+   std::vector<hs_ec_job> jobs((size_t) count);
+   for (int j = 0; j < count; ++j)
+   {
+      const long long n2 = (long long) n[j] * n[j];
+      memcpy(ha.data() + 2 * off[j] + n2, A + off[j], (size_t) n2 * sizeof(double));
+      memset(&jobs[j], 0, sizeof(hs_ec_job));
+      jobs[j].n = n[j]; jobs[j].form = HS_EC_DENSE; jobs[j].blk = j; jobs[j].ld = n2;
+      jobs[j].A = da.p + 2 * off[j];
+      jobs[j].Z = dz.p + off[j];
+   }
+   int nsmall = 0, row = 0;
+   for (int cls = 0; cls < 2; ++cls)
+   {
+      const std::vector<int>& list = cls == 0 ? small : mid;
+      for (size_t k = 0; k < list.size(); ++k, ++row)
+      {
+         const int j = list[k];
+         double* t = tab.data() + (size_t) row * HS_OVA_TAB;
+         t[0] = 0.0; t[1] = (double) (kind != NULL ? kind[j] : HIPSDP_ONEVAR_NEWTON); t[2] = lb[j]; t[3] = ub[j]; t[4] = shift[j];
+         t[5] = (double) j; t[6] = (double) j;
+         if ( cls == 0 )
+            nsmall = n[j] > nsmall ? n[j] : nsmall;
+      }
+   }
+   const int nmid = mid.empty() ? 0 : n[mid[0]];
+   const int grid = (int) mid.size() < mid_cap ? (int) mid.size() : mid_cap;
+   if ( grid > 0 )
+      HS_CALL( dslab.alloc(2LL * grid * nmid * nmid) );
+   HS_CALL( dz.up(Z, tot) ); HS_CALL( da.up(ha.data(), 2 * tot) ); HS_CALL( dtab.up(tab.data(), (long long) tab.size()) );
+   HS_HIP( hipMemcpy(djobs.p, jobs.data(), (size_t) count * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+   hs_ova_par P;
+   memset(&P, 0, sizeof(P));
+   P.maxevals = maxevals > 0 ? maxevals : 100;
+   P.feastol = feastol; P.infinity = 1e20;
+   P.jobs = reinterpret_cast<const hs_ec_job*>(djobs.p); P.res = dres.p;
+   P.count = (int) small.size(); P.grid = P.count; P.nmax = nsmall; P.tab = dtab.p;
+   HS_CALL( hs_onevar_all(0, 0, &P) );
+   P.count = (int) mid.size(); P.grid = grid; P.nmax = nmid; P.tab = dtab.p + (long long) small.size() * HS_OVA_TAB; P.slab = dslab.p;
+   HS_CALL( hs_onevar_all(0, 1, &P) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> h((size_t) count * HS_OV_RES);
+   HS_CALL( dres.down(h.data(), (long long) h.size()) );
+   for (int j = 0; j < count; ++j)
+   {
+      const double* r = h.data() + (size_t) j * HS_OV_RES;
+      if ( !(r[0] >= 0.0 && r[0] <= (double) HIPSDP_ONEVAR_DONE) )
          return HIPSDP_ERR_NUMERIC;
       status[j] = (int) r[0];
       optval[j] = r[1];
