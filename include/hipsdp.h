@@ -472,6 +472,40 @@ HIPSDP_API int hipsdp_onevar_bounds_all(hipsdp_solver* solver, const double* u, 
  * (NULL pointers are accepted; works without a device).  The totals of hipsdp_onevar_bounds_stats do not move, and the reverse. */
 HIPSDP_API int hipsdp_onevar_bounds_all_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* The same one-variable SDPs for the blocks of 129 .. HIPSDP_ONEVAR_LARGE_MAXN rows, the ones hipsdp_onevar_bounds_all turns away: call
+ * hipsdp_onevar_bounds_all first, then this with the jobs that came back -1.  Arguments, job list (the implicit block-major list
+ * included), NULL rules, kinds (NEWTON, TWOPOINT, EXTREMES; EXTREMES with opts->maxevals == 1: lambda_min alone), argument errors
+ * (checked before the device is looked at, nothing launched) and the meaning of every output are those of hipsdp_onevar_bounds_all;
+ * every comparison and the order of evaluations are those hipsdp_onevar_bounds documents.  DECLINED is decided before anything is read.
+ * A job on a block of at most HIPSDP_ONEVAR_MAXN rows (they belong to hipsdp_onevar_bounds_all), of more than
+ * HIPSDP_ONEVAR_LARGE_MAXN rows or without matrices on this device gets status[j] = -1 and nothing else written; the other jobs are
+ * still served.  A solver with a communicator or sharded matrices: every status -1, nothing launched.  count == 0 or no served job:
+ * HIPSDP_OK, nothing launched.
+ * Above 128 rows an eigenpair is the tridiagonal path of hipsdp_syevx - one launch per column -, so the loop of a job cannot stay in one
+ * launch; the JOBS go into the launches instead.  The call runs as rounds: round r is evaluation r of every job still active, all its
+ * launches batched over the jobs (form M_j straight into the job's workspace, nmax - 1 column launches, values, vector, back-
+ * transformation, decide, count), then ONE int is read back, the number of jobs that go on.  Eigenvalues and vectors have the accuracy stated
+ * for hipsdp_syevx in its scale range, relative to ||M(mu)||: the eigenvalue to 1e-12 of the largest one in absolute value, the residual
+ * of the unit vector to 1e-9 of it (EXTREMES: relative to ||A_i||).
+ * Launches and read-backs of a call whose jobs fit one chunk, with nmax the largest served block, R the most tridiagonalisations a
+ * served job needed (its evals for NEWTON and TWOPOINT, 1 for EXTREMES) and z = 1 if a served job that is not declined is NEWTON or
+ * TWOPOINT (Z(u) is formed), else 0:
+ *     launches = z + R (nmax + 5)   (<= 1 + R (nmax + 6)),      read-backs = R + 1   (R when R = maxevals)
+ * - functions of (nmax, R, z) alone, whatever the number of jobs and blocks; a call whose jobs are all declined launches nothing.  A job
+ * needs about 4.7 MB of the solver's grow-only cut workspace at 512 rows, so the jobs, ordered by descending n, run in chunks of at
+ * most 512 MiB of it (HIPSDP_ONEVAR_LARGE_CHUNK in the environment: jobs per chunk instead), one after the other on the solver's
+ * stream; each chunk has the launches and read-backs above for ITS nmax, R and z.
+ * Same input, same bits; the bits of a job depend neither on the other jobs, nor on their order, nor on the number of workgroups a job
+ * gets, nor on the chunking; no floating-point atomics.  Two host threads may call it at the same time on different solvers. */
+#define HIPSDP_ONEVAR_LARGE_MAXN 512     /* = HIPSDP_SYEVX_MAXN */
+HIPSDP_API int hipsdp_onevar_bounds_large(hipsdp_solver* solver, const double* u, int count,
+   const int* blocks, const int* vars, const int* kind, const double* lb, const double* ub,
+   const hipsdp_onevar_opts* opts,
+   int* status, double* optval, double* lmin, double* grad, int* evals);
+/* process totals: calls that served at least one job, kernel launches they issued, device->host synchronisations they waited on
+ * (NULL pointers are accepted; works without a device).  The totals of the two other one-variable calls do not move, and the reverse. */
+HIPSDP_API int hipsdp_onevar_bounds_large_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* multi-GPU: Schur rows are sharded over the ranks of an RCCL communicator (one process per GPU); comm comes from hipsdp_comm_create[_host] */
 /* Small problems (one assembly below HIPSDP_SHARD_MIN_FLOPS, default 2e10 algorithmic flops) are not sharded: every rank solves
  * them alone with the single-rank kernels and rank 0's outcome (status, iterate, preoptimal iterate) is broadcast once per solve. */

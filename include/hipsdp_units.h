@@ -173,6 +173,14 @@ HIPSDP_API int  hipsdp_onevar_unit(int device, int n, int count, const double* Z
 HIPSDP_API int  hipsdp_onevar_all_unit(int device, int count, const int* n, const double* Z, const double* A, const double* shift,
    const int* kind, const double* lb, const double* ub, double feastol, int maxevals, int mid_cap,
    int* status, double* optval, double* lmin, double* grad, int* evals);
+/* the rounds of hipsdp_onevar_bounds_large (csrc/onevar_large.hip: hs_onevar_large_chunk) alone on host matrices given PER JOB, as
+ * hipsdp_onevar_all_unit takes them, with n[j] = 2 .. 512 and mixed sizes in one call: the batched kernels at small sizes.  Every job
+ * is a block of its own with dense rows and its Z given, so no Z(u) launch is issued.  wg_cap: the cap on the workgroups per job of
+ * the column launches (<= 0: the product call's default for the number of jobs); chunk: jobs per chunk at most (<= 0: all in one).
+ * rounds (may be NULL): the sum of the rounds of the chunks.  infinity is 1e20. */
+HIPSDP_API int  hipsdp_onevar_large_unit(int device, int count, const int* n, const double* Z, const double* A, const double* shift,
+   const int* kind, const double* lb, const double* ub, double feastol, int maxevals, int wg_cap, int chunk,
+   int* status, double* optval, double* lmin, double* grad, int* evals, int* rounds);
 /* the fan-out kernel of hipsdp_solve_objectives (hs_objs_fanout, csrc/kernels.hip) alone: count jobs of a problem with m variables, q LP
  * rows and nblk blocks of ns[k] rows.  B: count x m objectives, b_own[m]: the solver's own; have_start = 1: the start point y[m], x[q],
  * z[q] and XZ = X_0, Z_0, X_1, Z_1, ... one behind the other (have_start = 0: not read, only the objectives are fanned out).

@@ -565,6 +565,30 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's onevar_bounds_all_stats()"""
         return onevar_bounds_all_stats()
 
+    def onevar_bounds_large(self, u, lb, ub, feastol, blocks=None, vars=None, kind=None, infinity=1e20, maxevals=0):
+        """the one-variable SDPs of the blocks of 129 .. 512 rows (hipsdp_onevar_bounds_large): arguments and results of
+        onevar_bounds_all; status -1 and NaN: the job's block is not served here (at most 128 rows: onevar_bounds_all serves it)"""
+        u, lb, ub = _f64(u), _f64(lb), _f64(ub)
+        count = len(lb)
+        assert len(ub) == count
+        cb = None if blocks is None else np.ascontiguousarray(blocks, dtype=np.int32)
+        cv = None if vars is None else np.ascontiguousarray(vars, dtype=np.int32)
+        ck = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32)
+        assert all(c is None or len(c) == count for c in (cb, cv, ck))
+        opts = OnevarOpts(feastol, infinity, maxevals)
+        status = np.full(max(1, count), -1, dtype=np.int32)
+        evals = np.zeros(max(1, count), dtype=np.int32)
+        optval, lmin, grad = (np.full(max(1, count), np.nan) for _ in range(3))
+        _chk(self._l().hipsdp_onevar_bounds_large(self.h, _dp(u), count, None if cb is None else _ip(cb), None if cv is None else _ip(cv),
+                                                  None if ck is None else _ip(ck), _dp(lb), _dp(ub), C.byref(opts), _ip(status),
+                                                  _dp(optval), _dp(lmin), _dp(grad), _ip(evals)), "hipsdp_onevar_bounds_large")
+        return status[:count], optval[:count], lmin[:count], grad[:count], evals[:count]
+
+    @staticmethod
+    def onevar_bounds_large_stats():
+        """process totals (calls, launches, read-backs): the module's onevar_bounds_large_stats()"""
+        return onevar_bounds_large_stats()
+
 
 class OnevarOpts(C.Structure):
     """hipsdp_onevar_opts"""
@@ -613,6 +637,41 @@ def onevar_all_unit(Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, mid_cap
     if rc != 0:
         raise RuntimeError("hipsdp_onevar_all_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
     return status, optval, lmin, grad, evals
+
+
+def onevar_bounds_large_stats():
+    """process totals of hipsdp_onevar_bounds_large: (calls that served a job, kernel launches issued, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_onevar_bounds_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_onevar_bounds_large_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def onevar_large_unit(Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, wg_cap=0, chunk=0, device=0, with_rounds=False):
+    """the rounds of hipsdp_onevar_bounds_large alone on host matrices per job (hipsdp_onevar_large_unit of the units library): Z[j] and
+    A[j] are n_j x n_j, 2 <= n_j <= 512, shift[j] = u_i; wg_cap: workgroups per job of a column launch at most (0: the product call's
+    choice); chunk: jobs per chunk at most (0: one chunk); returns the arrays (status, optval, lmin, grad, evals), with_rounds: and the
+    number of rounds"""
+    Z = [np.asarray(z, dtype=np.float64) for z in Z]
+    A = [np.asarray(a, dtype=np.float64) for a in A]
+    count = len(Z)
+    ns = np.ascontiguousarray([z.shape[0] for z in Z], dtype=np.int32)
+    assert len(A) == count and all(Z[j].shape == A[j].shape == (ns[j], ns[j]) for j in range(count))
+    zf = _f64(np.concatenate([z.reshape(-1) for z in Z]))
+    af = _f64(np.concatenate([a.reshape(-1) for a in A]))
+    shift, lb, ub = _f64(np.atleast_1d(shift)), _f64(np.atleast_1d(lb)), _f64(np.atleast_1d(ub))
+    assert len(lb) == count and len(ub) == count and len(shift) == count
+    ck = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32)
+    status = np.full(count, -1, dtype=np.int32)
+    evals = np.zeros(count, dtype=np.int32)
+    optval, lmin, grad = (np.full(count, np.nan) for _ in range(3))
+    rounds = C.c_int(0)
+    rc = ulib().hipsdp_onevar_large_unit(device, count, _ip(ns), _dp(zf), _dp(af), _dp(shift), None if ck is None else _ip(ck), _dp(lb),
+                                         _dp(ub), C.c_double(feastol), int(maxevals), int(wg_cap), int(chunk), _ip(status), _dp(optval),
+                                         _dp(lmin), _dp(grad), _ip(evals), C.byref(rounds))
+    if rc != 0:
+        raise RuntimeError("hipsdp_onevar_large_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    res = (status, optval, lmin, grad, evals)
+    return res + (rounds.value,) if with_rounds else res
 
 
 def onevar_unit(n, Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, device=0):

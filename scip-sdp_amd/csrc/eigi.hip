@@ -1296,6 +1296,178 @@ __global__ void __launch_bounds__(EM_NT) k_onevar_all_mid(hs_ova_par P)
    }
 }
 
+/* ---- the same jobs on blocks of up to 512 rows (hipsdp_onevar_bounds_large): the loop of a job does not fit into one launch - its
+ * eigenpair is the tridiagonal path of syevx.hip, one launch per column -, so the call runs as ROUNDS: round r is evaluation r of
+ * every job that is still active, and the two kernels here stand around the batched launches of syevx.hip (hs_syevx_many_*):
+ *   k_onevar_large_form    grid (workgroups per job, jobs): M(mu) straight into the job's tridiagonalisation workspace, from the
+ *                          block's storage form; a workgroup owns a range of rows, every entry is written by one thread from the
+ *                          lower-triangular entry of Z and A_i (symmetric to the bit, whatever the grid);
+ *   k_onevar_large_decide  one workgroup per job: g = v^T A_i v in a fixed order, then thread 0 with ov_decide / ov_extreme.
+ * The state of a job (ov_state) lives in device memory between the rounds; ov_begin runs in round 0, in both kernels (the form kernel
+ * needs the first point, the decide kernel keeps the state).  act[job]: the flags of hs_sxm_job's launches, 0 once the job is done.
+ * The jobs that go on are counted by a launch of one workgroup behind the decide launch (k_onevar_large_count): no atomic at all. */
+static_assert(sizeof(ov_state) <= HS_OVL_STATE * sizeof(double), "HS_OVL_STATE");
+
+__device__ __forceinline__ ov_job ov_job_of(const hs_ovl_par& P, int row)
+{
+   const double* __restrict__ t = P.tab + (long long) row * HS_OVA_TAB;
+   const hs_ec_job* blk = P.blocks + (int) t[5];
+   ov_job J;
+   J.n = blk->n; J.blk = blk; J.Z = blk->Z; J.A = NULL;
+   J.tab = t;
+   J.res = P.res + (long long) t[6] * HS_OV_RES;
+   return J;
+}
+
+/* thread 0: where the job stands at the start of round P.round */
+__device__ __forceinline__ void ovl_load(const hs_ovl_par& P, const ov_job& J, int job, ov_state* S)
+{
+   if ( P.round == 0 )
+      ov_begin(ov_ctl_of(P.maxevals, P.feastol, P.infinity), J, S);
+   else
+      *S = *reinterpret_cast<const ov_state*>(P.state + (long long) job * HS_OVL_STATE);
+}
+
+/* entry (r, c), r >= c, of the dense or packed A_i */
+__device__ __forceinline__ double ovl_entry(const double* __restrict__ a, bool packed, int n, int r, int c)
+{
+   return a[packed ? (long long) r * (r + 1) / 2 + c : (long long) r * n + c];
+}
+
+__global__ void __launch_bounds__(256) k_onevar_large_form(hs_ovl_par P)
+{
+   __shared__ ov_state S;
+   const int job = blockIdx.y, tid = threadIdx.x;
+   if ( P.act[job] == 0 )
+      return;
+   const ov_job J = ov_job_of(P, job);
+   if ( tid == 0 )
+      ovl_load(P, J, job, &S);
+   __syncthreads();
+   if ( S.at == OV_DONE )
+      return;
+   const bool ex = S.at == OV_EX;
+   const double s = ex ? 1.0 : S.mu - S.shift;
+   const int n = J.n, var = (int) J.tab[0];
+   const int per = (n + (int) gridDim.x - 1) / (int) gridDim.x;
+   const int r0 = (int) blockIdx.x * per, r1 = min(n, r0 + per);
+   if ( r0 >= r1 )
+      return;
+   const double* __restrict__ Z = J.Z;
+   double* __restrict__ M = P.jobs[job].A;
+   double* __restrict__ R = P.jobs[job].R;
+   const bool sparse = J.blk->form == HS_EC_SPARSE, packed = J.blk->form == HS_EC_PACKED;
+   const double* __restrict__ a = sparse ? NULL : J.blk->A + (long long) (var + 1) * J.blk->ld;
+   for (int e = r0 * n + tid; e < r1 * n; e += 256)
+   {
+      const int i = e / n, k = e - i * n;
+      const int r = i > k ? i : k, c = i > k ? k : i;
+      const double z = ex ? 0.0 : Z[(long long) r * n + c];
+      M[e] = sparse ? z : fma(s, ovl_entry(a, packed, n, r, c), z);
+      R[e] = 0.0;
+   }
+   if ( !sparse )
+      return;
+   __syncthreads();
+   /* the variable's nonzeros, every position once: both mirror images, each by the workgroup that owns its row */
+   const hs_sp_view sp = J.blk->sp;
+   for (int e = sp.voff[var] + tid; e < sp.voff[var + 1]; e += 256)
+   {
+      const int i = sp.vrow[e], k = sp.vcol[e];
+      const int r = i > k ? i : k, c = i > k ? k : i;
+      if ( c < 0 || r >= n )
+         continue;
+      const double v = fma(s, sp.vval[e], ex ? 0.0 : Z[(long long) r * n + c]);
+      if ( r >= r0 && r < r1 )
+         M[(long long) r * n + c] = v;
+      if ( c != r && c >= r0 && c < r1 )
+         M[(long long) c * n + r] = v;
+   }
+}
+
+__global__ void __launch_bounds__(256) k_onevar_large_decide(hs_ovl_par P)
+{
+   __shared__ ov_state S;
+   __shared__ double part[4];
+   const int job = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   if ( P.act[job] == 0 )
+      return;
+   const ov_job J = ov_job_of(P, job);
+   const ov_ctl C = ov_ctl_of(P.maxevals, P.feastol, P.infinity);
+   if ( tid == 0 )
+      ovl_load(P, J, job, &S);
+   __syncthreads();
+   const hs_sxm_job X = P.jobs[job];
+   const int n = J.n, var = (int) J.tab[0];
+   const int wantvec = S.at != OV_DONE && S.at != OV_EX && S.wantvec;
+   if ( wantvec )
+   {
+      const double* __restrict__ v = X.out + HS_SYEVX_OUT_VEC;
+      double g = 0.0;
+      if ( J.blk->form == HS_EC_SPARSE )
+      {
+         const hs_sp_view sp = J.blk->sp;
+         for (int e = sp.voff[var] + tid; e < sp.voff[var + 1]; e += 256)
+         {
+            const int r = sp.vrow[e], c = sp.vcol[e];
+            if ( r >= 0 && r < n && c >= 0 && c < n )
+               g += (r == c ? 1.0 : 2.0) * sp.vval[e] * v[r] * v[c];
+         }
+      }
+      else
+      {
+         const bool packed = J.blk->form == HS_EC_PACKED;
+         const double* __restrict__ a = J.blk->A + (long long) (var + 1) * J.blk->ld;
+         for (int e = tid; e < n * n; e += 256)
+         {
+            const int i = e / n, k = e - i * n;
+            g += ovl_entry(a, packed, n, i > k ? i : k, i > k ? k : i) * v[i] * v[k];
+         }
+      }
+      g = hs_wave_sum_dpp(g);
+      if ( lane == 0 )
+         part[wave] = g;
+      __syncthreads();
+   }
+   if ( tid != 0 )
+      return;
+   if ( S.at == OV_EX )
+   {
+      ov_extreme(C, &S, X.out[HS_SYEVX_OUT_LAM]);
+      if ( S.at != OV_DONE )
+         ov_extreme(C, &S, X.out2[HS_SYEVX_OUT_LAM]);
+      S.at = OV_DONE;
+   }
+   else if ( S.at != OV_DONE )
+      ov_decide(C, &S, X.out[HS_SYEVX_OUT_LAM], wantvec ? ((part[0] + part[1]) + part[2]) + part[3] : 0.0);
+   if ( S.at == OV_DONE )
+   {
+      ov_store(J, &S);
+      P.act[job] = 0;
+   }
+   else
+      P.act[job] = HS_SXM_ACTIVE | (S.wantvec ? HS_SXM_VEC : 0);
+   *reinterpret_cast<ov_state*>(P.state + (long long) job * HS_OVL_STATE) = S;
+}
+
+/* one workgroup behind the decide launch: how many jobs go on (integers, summed by thread 0) */
+__global__ void __launch_bounds__(256) k_onevar_large_count(int count, const int* __restrict__ act, int* __restrict__ nactive)
+{
+   __shared__ int part[256];
+   int c = 0;
+   for (int k = threadIdx.x; k < count; k += 256)
+      c += act[k] != 0 ? 1 : 0;
+   part[threadIdx.x] = c;
+   __syncthreads();
+   if ( threadIdx.x == 0 )
+   {
+      int tot = 0;
+      for (int k = 0; k < 256; ++k)
+         tot += part[k];
+      *nactive = tot;
+   }
+}
+
 
 /* ---- 64 < n <= 128: ALL eigenpairs in one launch ---------------------------------------------------------------------------------
  * The phases of k_syevi_small<true> with two entries per lane, laid out for what 160 KB of LDS hold: the reduction needs the matrix
@@ -2169,6 +2341,32 @@ int hs_onevar_all(hipStream_t st, int cls, const hs_ova_par* P)
       HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_onevar_all_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
       hipLaunchKernelGGL(k_onevar_all_mid, dim3(P->grid), dim3(EM_NT), (size_t) P->nmax * (P->nmax | 1) * sizeof(double), st, *P);
    }
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* the two launches of a round of hipsdp_onevar_bounds_large that stand around the batched tridiagonal path (see k_onevar_large_form) */
+static int ovl_check(const hs_ovl_par* P)
+{
+   return P->count >= 1 && P->maxevals >= 1 && P->round >= 0 && P->blocks != NULL && P->tab != NULL && P->jobs != NULL && P->act != NULL
+      && P->nactive != NULL && P->state != NULL && P->res != NULL;
+}
+
+int hs_onevar_large_form(hipStream_t st, const hs_ovl_par* P)
+{
+   if ( !ovl_check(P) || P->grid < 1 )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_onevar_large_form, dim3(P->grid, P->count), dim3(256), 0, st, *P);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_onevar_large_decide(hipStream_t st, const hs_ovl_par* P)
+{
+   if ( !ovl_check(P) )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_onevar_large_decide, dim3(P->count), dim3(256), 0, st, *P);
+   hipLaunchKernelGGL(k_onevar_large_count, dim3(1), dim3(256), 0, st, P->count, P->act, P->nactive);
    HS_HIP( hipGetLastError() );
    return HS_OK;
 }

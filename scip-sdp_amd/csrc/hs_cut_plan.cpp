@@ -73,3 +73,42 @@ void hs_ova_layout_make(int m, int count, int tabw, int resw, long long z_len, i
    L->len.upload_len = L->res; L->len.pin_len = L->res + L->len.res_len;
    L->len.dev_len = L->slabs + 2LL * mid_grid * mid_nmax * mid_nmax;
 }
+
+void hs_ovl_layout_make(int m, int count, int tabw, int jobw, int resw, int statew, long long z_len, const long long* ws_len,
+   const long long* out_len, long long* ws, long long* out, hs_ovl_layout* L)
+{
+   L->u = 0;
+   L->tab = even(m);
+   L->jobs = even(L->tab + (long long) count * tabw);
+   L->act = even(L->jobs + (long long) count * jobw);
+   L->nactive = L->act + even(((long long) count + 1) / 2);
+   L->res = L->nactive + 2;
+   L->state = even(L->res + (long long) count * resw);
+   L->Z = even(L->state + (long long) count * statew);
+   L->slabs = L->Z + even(z_len);
+   long long at = L->slabs;
+   for (int k = 0; k < count; ++k)
+   {
+      ws[k] = at;
+      at += even(ws_len[k]);
+      out[k] = at;
+      at += even(out_len[k]);
+   }
+   L->len.res_off = L->res; L->len.res_len = (long long) count * resw;
+   L->len.upload_len = L->res; L->len.pin_len = L->res + L->len.res_len;
+   L->len.dev_len = at;
+}
+
+int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs)
+{
+   long long used = 0;
+   int k = start;
+   while ( k < count )
+   {
+      if ( k > start && (used + job_len[k] > budget || (maxjobs > 0 && k - start >= maxjobs)) )
+         break;
+      used += job_len[k];
+      ++k;
+   }
+   return k;
+}

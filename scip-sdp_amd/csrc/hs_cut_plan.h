@@ -72,6 +72,19 @@ void hs_scl_layout_make(int n, int m, int maxcuts, int smax, long long ws_len, l
 /* z_len: sum of hs_cut_mat_len(n) over the blocks with jobs; mid_grid = 0: no job of the 65-128 class */
 void hs_ova_layout_make(int m, int count, int tabw, int resw, long long z_len, int mid_grid, int mid_nmax, hs_ova_layout* L);
 
+/* hipsdp_onevar_bounds_large (csrc/onevar_large.hip), ONE CHUNK of `count` jobs:
+ *    u[m] | table [count][tabw] | job table [count][jobw] | act[count] (int) | nactive (int, one double) | result [count][resw]
+ *    | state [count][statew] | Z of the chunk's blocks | per job: workspace of the tridiagonal form, then its selection output
+ * every part starts at an even offset.  Uploaded: everything in front of the result; read back after every round: nactive alone, at the
+ * end the result; the pinned mirror ends behind the result.  ws[k] / out[k]: where job k's workspace and output start (the caller's
+ * arrays of `count` entries); ws_len[k], out_len[k]: hs_syevx_ws(n_k), HS_SXM_OUT(n_k), passed in as numbers */
+struct hs_ovl_layout { long long u, tab, jobs, act, nactive, res, state, Z, slabs; hs_cut_lens len; };
+void hs_ovl_layout_make(int m, int count, int tabw, int jobw, int resw, int statew, long long z_len, const long long* ws_len,
+   const long long* out_len, long long* ws, long long* out, hs_ovl_layout* L);
+/* the chunks of a call: jobs start .. (return value - 1) of a list ordered by descending n form the next chunk - as many as fit into
+ * `budget` doubles of job_len[] (workspace + output of a job), at least one, and at most maxjobs when maxjobs > 0 */
+int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs);
+
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
 {

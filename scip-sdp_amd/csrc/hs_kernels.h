@@ -392,6 +392,57 @@ struct hs_ova_par
    double* res;
 };
 int hs_onevar_all(hipStream_t st, int cls, const hs_ova_par* P);
+/* ... and of blocks of up to 512 rows as ROUNDS over all jobs (hipsdp_onevar_bounds_large; host side: onevar_large.hip): the eigenpairs
+ * come from the batched tridiagonal path of syevx.hip (hs_sxm_job, declared below), and the two launches here stand around it.
+ *   hs_onevar_large_form:   M = Z_b(u) + (mu - u_i) A_i (EXTREMES: A_i) of every active job into its hs_sxm_job.A, zeros into .R; the
+ *                           point mu is that of ov_begin in round 0, afterwards that of the job's state.
+ *   hs_onevar_large_decide: g = v^T A_i v from the block's storage form in a fixed order, the branch of the job (ov_decide /
+ *                           ov_extreme), its next point or its row of the result and act = 0; a second launch of one workgroup
+ *                           writes to *nactive how many jobs go on (TWO launches).
+ * tab: rows of HS_OVA_TAB; state: HS_OVL_STATE doubles per row; act: the flags of hs_sxm_job's launches (the host sets those of round 0:
+ * HS_SXM_ACTIVE, | HS_SXM_VEC for NEWTON, | HS_SXM_BOTH for EXTREMES); grid: workgroups per job of the form launch. */
+#define HS_OVL_STATE 10
+struct hs_sxm_job;
+struct hs_ovl_par
+{
+   int count, maxevals, round, grid;
+   double feastol, infinity;
+   const hs_ec_job* blocks;
+   const double* tab;            /* [count][HS_OVA_TAB] */
+   const hs_sxm_job* jobs;       /* [count] */
+   int* act;                     /* [count] */
+   int* nactive;
+   double* state;                /* [count][HS_OVL_STATE] */
+   double* res;
+};
+int hs_onevar_large_form(hipStream_t st, const hs_ovl_par* P);
+int hs_onevar_large_decide(hipStream_t st, const hs_ovl_par* P);
+/* onevar_large.hip: ONE CHUNK of the call, as hipsdp_onevar_bounds_large and the unit entry (units.hip) run it.  rows: the chunk's jobs
+ * by descending n, none of them declined (hs_onevar_large_declined: those never reach the device); entry: the index of the job's
+ * block in dblocks, a table in device memory whose first nz entries get their Z(u) formed here (nz = 0: every Z lies there already).
+ * hs_onevar_large_plan lays the chunk out (z_len: doubles of all Z of the chunk); the caller then provides dev / pin of L.len.dev_len /
+ * L.len.pin_len doubles and the table of blocks with their Z from dev + L.Z on; hs_onevar_large_chunk uploads, runs the rounds and
+ * leaves row k's result at pin + L.res + k HS_OV_RES.  cap <= 0: the default number of workgroups per job for this many jobs.
+ * launches / readbacks are added to; *rounds: the rounds the chunk took. */
+struct hs_ovl_row { int n, var, kind, entry; double lb, ub, shift; };
+struct hs_ovl_chunk
+{
+   int m, count, nz, nzmax, cap, maxevals;
+   double feastol, infinity;
+   const double* u;
+   const hs_ovl_row* rows;
+   const hs_ec_job* dblocks;
+   double* dev; double* pin;
+};
+static inline bool hs_onevar_large_declined(int kind, double lb, double ub, double infinity)
+{
+   return kind != HS_OV_KIND_EXTREMES && (lb <= -infinity || ub >= infinity);
+}
+long long hs_onevar_large_job_len(int n);
+void hs_onevar_large_plan(int m, int count, const hs_ovl_row* rows, long long z_len, hs_ovl_layout* L, std::vector<long long>* ws,
+   std::vector<long long>* out);
+int hs_onevar_large_chunk(hipStream_t st, const hs_ovl_chunk* c, const hs_ovl_layout& L, const std::vector<long long>& ws,
+   const std::vector<long long>& out, long long* launches, long long* readbacks, int* rounds);
 
 /* ---- sparsecuts.hip: sparse eigenvector cuts of all blocks (hipsdp_sparsecuts_all) -------------------------------------------- */
 #define HS_SC_MAXN 128
@@ -457,6 +508,9 @@ struct hs_solver_cut_ws
 int hs_solver_dims(const hipsdp_solver* s, int* m, int* nblocks);
 int hs_solver_block_n(const hipsdp_solver* s, int block);
 int hs_solver_cut_enter(hipsdp_solver* s, int only, std::vector<int>* ids);
+/* its sibling without the 128-row filter: every block with whole matrices on this device and at most maxn rows, in index order (none
+ * for a solver with a communicator or sharded matrices, which is not touched); hs_solver_cut_blocks serves any subset of them too */
+int hs_solver_cut_enter_large(hipsdp_solver* s, int maxn, std::vector<int>* ids);
 int hs_solver_cut_prepare(hipsdp_solver* s, const std::vector<int>& ids, const std::vector<long long>& vecoff, long long slabs,
    const hs_cut_lens& len, int* nmax, hs_solver_cut_ws* w);
 int hs_solver_cut_rounds(hipsdp_solver* s, const std::vector<hs_scr_job>& xjobs, const std::vector<hs_eig_job>& sjobs, hs_solver_cut_ws* w);
@@ -495,6 +549,21 @@ void hs_syevx_tridiag_view(int n, double* ws, double** d, double** e, double** R
 /* its stages 2 to 4 alone on the form hs_syevx_tridiag_dev left in ws: the arguments of hs_syevx_dev without the matrix, one launch
  * for the values and two more for the vectors.  Several requests may follow one tridiagonalisation, each with a dOut of its own. */
 int hs_syevx_select_dev(hipStream_t st, int n, int mode, int il, int iu, double bound, int maxk, double* dOut, double* ws);
+/* the same four stages for MANY matrices per launch (mixed n, 2 .. 512 each): a table of hs_sxm_job in device memory and one int per
+ * matrix, act[k] = 0: matrix k takes no part in the launches; else HS_SXM_ACTIVE | HS_SXM_VEC (the unit vector of eigenvalue 1 to
+ * out + HS_SYEVX_OUT_VEC) | HS_SXM_BOTH (eigenvalue n as well, to out2[HS_SYEVX_OUT_LAM]); eigenvalue 1 lies at out[HS_SYEVX_OUT_LAM].
+ * The caller's own kernel writes the symmetric matrix to A (n x n, no pitch) and zeros to R (n x n) before hs_syevx_many_cols.
+ * hs_syevx_many_job fills an entry from the matrix's workspace (hs_syevx_ws(n) doubles) and output (HS_SXM_OUT(n) doubles).
+ * hs_syevx_many_cols: nmax - 1 launches (nmax: the largest n of the table; cap: workgroups per matrix at most - the bits do not depend
+ * on it); hs_syevx_many_select: 3 launches (both != 0: some matrix may carry HS_SXM_BOTH).  No launch depends on act. */
+#define HS_SXM_ACTIVE 1
+#define HS_SXM_VEC    2
+#define HS_SXM_BOTH   4
+#define HS_SXM_OUT(n) (2 * HS_SYEVX_OUT_VEC + (((long long) (n) + 1) & ~1LL))
+struct hs_sxm_job { int n, pad; double* ws; double* A; double* R; double* out; double* out2; };
+int hs_syevx_many_job(int n, double* ws, double* out, hs_sxm_job* J);
+int hs_syevx_many_cols(hipStream_t st, int count, int nmax, int cap, const hs_sxm_job* djobs, const int* dact);
+int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs_sxm_job* djobs, const int* dact);
 
 /* ---- syevr.hip: ALL eigenpairs of a matrix of 2 .. 512 rows through the tridiagonal form (stage 1 is hs_syevx_tridiag_dev) --------
  * dA as for hs_syevx_dev.  dOut, HS_SYEVR_OUT(n) doubles: [k] k-th eigenvalue (ascending), [HS_SYEVR_OUT_VEC(n) + k n + i] component

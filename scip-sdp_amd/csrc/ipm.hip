@@ -5816,6 +5816,23 @@ int hs_solver_cut_enter(hipsdp_solver* s, int only, std::vector<int>* ids)
    return HS_OK;
 }
 
+/* the sibling of hs_solver_cut_enter for the calls whose launches hold blocks of up to maxn rows (hipsdp_onevar_bounds_large: 512): ids
+ * are ALL blocks with whole matrices on this device and at most maxn rows, in index order; hs_solver_cut_blocks then hands out the
+ * table of any subset of them.  A solver with a communicator or sharded matrices: none, and it is not touched. */
+int hs_solver_cut_enter_large(hipsdp_solver* s, int maxn, std::vector<int>* ids)
+{
+   ids->clear();
+   if ( s->comm != NULL || s->shardA )
+      return HS_OK;
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( stage_sync(s) );
+   HS_CALL( ensure_packed(s) );
+   for (size_t b = 0; b < s->blk.size(); ++b)
+      if ( s->blk[b].n <= maxn && ec_has_matrices(s->blk[b]) )
+         ids->push_back((int) b);
+   return HS_OK;
+}
+
 /* the storage form the kernels read the block's matrices in (J zeroed by the caller) */
 static void ec_job_form(const Block& B, hs_ec_job* J)
 {

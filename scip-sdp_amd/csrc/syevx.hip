@@ -25,7 +25,9 @@
  *      inside the clusters of eigenvalues closer than 1e-3 ||T|| }; only the RETURNED vectors are made orthonormal, so an index inside a
  *      cluster of hundreds of equal eigenvalues (low-rank matrices) costs what the k <= 32 wanted vectors cost.
  *   4. Back-transformation through the reflectors (k_syevx_back): one wavefront per vector, the reflectors read four ahead.
- * Every reduction runs in a fixed order (no floating-point atomics): the same input gives the same bits. */
+ * Every reduction runs in a fixed order (no floating-point atomics): the same input gives the same bits.
+ * Each stage is a __device__ body (d_syevx_col, d_syevx_values, d_syevx_tvec, d_syevx_back) with two kernels around it: the one of a
+ * single matrix and the one of MANY matrices per launch (k_syevx_*_many, hs_syevx_many_*: the rounds of hipsdp_onevar_bounds_large). */
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_tridiag.h"
@@ -69,6 +71,11 @@ size_t sx_ws_doubles(int n)
    return 2 * n2 + 5 * nl + 4 * (size_t) SX_K * nl;
 }
 
+/* Workgroups of the column launches: four rows per workgroup - each of its four wavefronts takes ONE row per launch (at 512 rows:
+ * eight loads per lane, one pass) -, at most 128: half the compute units, every workgroup resident at once, and the redundant O(n)
+ * part of a launch (w, the reflector) stays a small share of what the dispatcher starts. */
+__host__ __device__ inline int sx_groups(int n) { const int g = (n + 3) / 4; return g < 128 ? g : 128; }
+
 /* the symmetric matrix from the triangle the callers fill (memory positions [j n + i], i >= j), reflector array cleared */
 __global__ void __launch_bounds__(256) k_syevx_init(int n, const double* __restrict__ in, double* __restrict__ A, double* __restrict__ R)
 {
@@ -80,13 +87,14 @@ __global__ void __launch_bounds__(256) k_syevx_init(int n, const double* __restr
    }
 }
 
-/* column j of the reduction, 0 <= j <= n - 2 (see the head of the file); workgroup g owns the rows g, g + G, g + 2 G, ... */
-__global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __restrict__ A, double* __restrict__ R, double* __restrict__ P,
+/* column j of the reduction, 0 <= j <= n - 2 (see the head of the file); workgroup g of the G of the matrix owns the rows g, g + G,
+ * g + 2 G, ...  The body of k_syevx_col and of k_syevx_col_many (one matrix per blockIdx.y): the same arithmetic for both, and no sum
+ * crosses workgroups, so the bits do not depend on G */
+__device__ __forceinline__ void d_syevx_col(int n, int j, int G, int g, double* __restrict__ A, double* __restrict__ R, double* __restrict__ P,
    double* __restrict__ tau, double* __restrict__ d, double* __restrict__ e)
 {
    __shared__ double vp[SX_N], wp[SX_N], xs[SX_N], red[2][SX_CT / 64];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   const int G = gridDim.x, g = blockIdx.x;
    const double* __restrict__ pprev = P + (size_t) ((j + 1) & 1) * n;
    double* __restrict__ pcur = P + (size_t) (j & 1) * n;
    const double tprev = (j > 0) ? tau[j - 1] : 0.0;
@@ -195,9 +203,15 @@ __global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __res
    }
 }
 
+__global__ void __launch_bounds__(SX_CT) k_syevx_col(int n, int j, double* __restrict__ A, double* __restrict__ R, double* __restrict__ P,
+   double* __restrict__ tau, double* __restrict__ d, double* __restrict__ e)
+{
+   d_syevx_col(n, j, (int) gridDim.x, (int) blockIdx.x, A, R, P, tau, d, e);
+}
+
 /* ---- stage 2: the wanted eigenvalues.  out[0] = how many pairs are returned, out[1] = eigenvalues below the bound (-1 for an index
  * range), out[2] = Gershgorin span, out[3] = norm bound of T, out[HS_SYEVX_OUT_LAM + k] = k-th returned eigenvalue */
-__global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il, int iu, double bound, int maxk, const double* __restrict__ d,
+__device__ __forceinline__ void d_syevx_values(int n, int below, int il, int iu, double bound, int maxk, const double* __restrict__ d,
    const double* __restrict__ e, double* __restrict__ out)
 {
    __shared__ double ds[SX_N + 8], es[SX_N + 8], red[3][SX_VT / 64];
@@ -273,11 +287,17 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il
    }
 }
 
-/* ---- stage 3: eigenvectors of T for the returned eigenvalues, Zt[k][i].  Dynamic LDS: Z[SX_K][n | 1]. */
-__global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __restrict__ dg, const double* __restrict__ eg, const double* __restrict__ out,
-   double* __restrict__ Zt, double* __restrict__ G0, double* __restrict__ G1, double* __restrict__ G2)
+__global__ void __launch_bounds__(SX_VT) k_syevx_values(int n, int below, int il, int iu, double bound, int maxk, const double* __restrict__ d,
+   const double* __restrict__ e, double* __restrict__ out)
 {
-   extern __shared__ __attribute__((aligned(16))) double Z[];
+   d_syevx_values(n, below, il, iu, bound, maxk, d, e, out);
+}
+
+/* ---- stage 3: eigenvectors of T for the returned eigenvalues, Zt[k][i].  Dynamic LDS: Z[SX_K][n | 1] (the batched launch asks for one
+ * vector per matrix: Z[1][nmax | 1]). */
+__device__ __forceinline__ void d_syevx_tvec(int n, const double* __restrict__ dg, const double* __restrict__ eg, const double* __restrict__ out,
+   double* __restrict__ Zt, double* __restrict__ G0, double* __restrict__ G1, double* __restrict__ G2, double* Z)
+{
    __shared__ double d[SX_N], e[SX_N], th[SX_K], coef[SX_K], red[2][SX_VT / 64];
    __shared__ int cstart[SX_K];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -363,14 +383,21 @@ __global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __res
    }
 }
 
+__global__ void __launch_bounds__(SX_VT) k_syevx_tvec(int n, const double* __restrict__ dg, const double* __restrict__ eg, const double* __restrict__ out,
+   double* __restrict__ Zt, double* __restrict__ G0, double* __restrict__ G1, double* __restrict__ G2)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   d_syevx_tvec(n, dg, eg, out, Zt, G0, G1, G2, Z);
+}
+
 /* ---- stage 4: x = H_0 H_1 ... H_{n-3} z, one wavefront per vector: lane l holds the entries l + 64 m; a reflector is a dot product
  * and an axpy over the wavefront, and the reflectors are read four ahead of their use (they do not depend on z).
  * k 2 n^2 multiply-adds bound by the latency of the reduction: nothing for the matrix cores at k <= 32. */
-__global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zt,
+__device__ __forceinline__ void d_syevx_back(int n, int k, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zt,
    double* __restrict__ out)
 {
    __shared__ double ts[SX_N];
-   const int lane = threadIdx.x, k = blockIdx.x;
+   const int lane = threadIdx.x;
    if ( k >= (int) out[0] )
       return;
    for (int i = lane; i < n; i += 64)
@@ -416,14 +443,103 @@ __global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restri
    hs_td_store_unit(z, n, lane, out + HS_SYEVX_OUT_VEC + (size_t) k * n);
 }
 
+__global__ void __launch_bounds__(64) k_syevx_back(int n, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zt,
+   double* __restrict__ out)
+{
+   d_syevx_back(n, (int) blockIdx.x, R, tau, Zt, out);
+}
+
+/* ---- the same four stages for MANY matrices per launch (hs_syevx_many_*; caller: hipsdp_onevar_bounds_large, onevar_large.hip): matrix
+ * blockIdx.y of the table, its workspace and its n from its hs_sxm_job, act[job] == 0: the matrix takes no part in this round.  Both
+ * conditions at the top of a kernel are uniform per workgroup.  A matrix gets min(sx_groups(n), gridDim.x) workgroups of a column
+ * launch.  Selection: eigenvalue 1, with HS_SXM_BOTH also eigenvalue n (to out2), with HS_SXM_VEC the vector of eigenvalue 1. */
+__global__ void __launch_bounds__(SX_CT) k_syevx_col_many(int j, const hs_sxm_job* __restrict__ jobs, const int* __restrict__ act)
+{
+   const int job = blockIdx.y;
+   const int n = jobs[job].n;
+   if ( act[job] == 0 || j > n - 2 )
+      return;
+   const int G = min(sx_groups(n), (int) gridDim.x);
+   if ( (int) blockIdx.x >= G )
+      return;
+   const sx_ws w = sx_layout(n, jobs[job].ws);
+   d_syevx_col(n, j, G, (int) blockIdx.x, w.A, w.R, w.P, w.tau, w.d, w.e);
+}
+
+__global__ void __launch_bounds__(SX_VT) k_syevx_values_many(const hs_sxm_job* __restrict__ jobs, const int* __restrict__ act)
+{
+   const int job = blockIdx.x, which = blockIdx.y;
+   const int a = act[job];
+   if ( a == 0 || (which == 1 && !(a & HS_SXM_BOTH)) )
+      return;
+   const int n = jobs[job].n;
+   const sx_ws w = sx_layout(n, jobs[job].ws);
+   const int ith = which == 0 ? 1 : n;
+   d_syevx_values(n, 0, ith, ith, 0.0, 0, w.d, w.e, which == 0 ? jobs[job].out : jobs[job].out2);
+}
+
+__global__ void __launch_bounds__(SX_VT) k_syevx_tvec_many(const hs_sxm_job* __restrict__ jobs, const int* __restrict__ act)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   const int job = blockIdx.x;
+   if ( !(act[job] & HS_SXM_VEC) )
+      return;
+   const int n = jobs[job].n;
+   const sx_ws w = sx_layout(n, jobs[job].ws);
+   d_syevx_tvec(n, w.d, w.e, jobs[job].out, w.Zt, w.G0, w.G1, w.G2, Z);
+}
+
+__global__ void __launch_bounds__(64) k_syevx_back_many(const hs_sxm_job* __restrict__ jobs, const int* __restrict__ act)
+{
+   const int job = blockIdx.x;
+   if ( !(act[job] & HS_SXM_VEC) )
+      return;
+   const int n = jobs[job].n;
+   const sx_ws w = sx_layout(n, jobs[job].ws);
+   d_syevx_back(n, 0, w.R, w.tau, w.Zt, jobs[job].out);
+}
+
 }
 
 size_t hs_syevx_ws(int n) { return (n < 2 || n > SX_N) ? 0 : sx_ws_doubles(n); }
 
-/* Workgroups of the column launches: four rows per workgroup - each of its four wavefronts takes ONE row per launch (at 512 rows:
- * eight loads per lane, one pass) -, at most 128: half the compute units, every workgroup resident at once, and the redundant O(n)
- * part of a launch (w, the reflector) stays a small share of what the dispatcher starts. */
-static int sx_groups(int n) { const int g = (n + 3) / 4; return g < 128 ? g : 128; }
+/* ---- many matrices per launch.  hs_syevx_many_job: the table entry of a matrix of n rows with its workspace (hs_syevx_ws(n) doubles)
+ * and its selection output (HS_SXM_OUT(n) doubles); A and R are where the caller's own kernel writes the symmetric matrix (n x n, no
+ * pitch) and clears the reflector array before hs_syevx_many_cols - in place of k_syevx_init. */
+int hs_syevx_many_job(int n, double* ws, double* out, hs_sxm_job* J)
+{
+   if ( n < 2 || n > SX_N || ws == NULL || out == NULL || J == NULL )
+      return HS_ERR_ARG;
+   const sx_ws w = sx_layout(n, ws);
+   J->n = n; J->pad = 0; J->ws = ws; J->A = w.A; J->R = w.R;
+   J->out = out; J->out2 = out + HS_SYEVX_OUT_VEC + (((size_t) n + 1) & ~(size_t) 1);
+   return HS_OK;
+}
+
+/* nmax - 1 launches: column j of every matrix with act != 0 and n - 2 >= j; cap: workgroups per matrix at most (1 .. 128) */
+int hs_syevx_many_cols(hipStream_t st, int count, int nmax, int cap, const hs_sxm_job* djobs, const int* dact)
+{
+   if ( count < 1 || nmax < 2 || nmax > SX_N || cap < 1 || djobs == NULL || dact == NULL )
+      return HS_ERR_ARG;
+   const int G = sx_groups(nmax) < cap ? sx_groups(nmax) : cap;
+   for (int j = 0; j + 1 < nmax; ++j)
+      hipLaunchKernelGGL(k_syevx_col_many, dim3(G, count), dim3(SX_CT), 0, st, j, djobs, dact);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* three launches, whatever the flags say: the values (both: a second row of workgroups for eigenvalue n), the vector of T, its
+ * back-transformation */
+int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs_sxm_job* djobs, const int* dact)
+{
+   if ( count < 1 || nmax < 2 || nmax > SX_N || djobs == NULL || dact == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_syevx_values_many, dim3(count, both ? 2 : 1), dim3(SX_VT), 0, st, djobs, dact);
+   hipLaunchKernelGGL(k_syevx_tvec_many, dim3(count), dim3(SX_VT), (size_t) (nmax | 1) * sizeof(double), st, djobs, dact);
+   hipLaunchKernelGGL(k_syevx_back_many, dim3(count), dim3(64), 0, st, djobs, dact);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
 
 /* stage 1 alone: d, e, tau and the reflector array in the workspace (hs_syevx_tridiag_view) */
 int hs_syevx_tridiag_dev(hipStream_t st, int n, const double* dA, double* ws)

@@ -1644,6 +1644,119 @@ extern "C" int hipsdp_onevar_all_unit(int device, int count, const int* n, const
    return HIPSDP_OK;
 }
 
+/* the rounds of hipsdp_onevar_bounds_large alone (csrc/onevar_large.hip: hs_onevar_large_chunk, the function the product call runs per
+ * chunk) on host matrices per job: every job is a block of its own - dense rows, row 1 = A_j, variable index 0 - whose Z is uploaded
+ * where k_ec_form_z would have put it */
+extern "C" int hipsdp_onevar_large_unit(int device, int count, const int* n, const double* Z, const double* A, const double* shift,
+   const int* kind, const double* lb, const double* ub, double feastol, int maxevals, int wg_cap, int chunk,
+   int* status, double* optval, double* lmin, double* grad, int* evals, int* rounds)
+{
+   HS_CALL( pick_device(device) );
+   if ( count < 1 || n == NULL || Z == NULL || A == NULL || shift == NULL || lb == NULL || ub == NULL || !(feastol >= 0.0)
+      || status == NULL || optval == NULL )
+      return HIPSDP_ERR_ARG;
+   std::vector<long long> off((size_t) count + 1, 0);
+   std::vector<int> list;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( n[j] < 2 || n[j] > HS_SYEVX_MAXN )
+         return HIPSDP_ERR_ARG;
+      if ( kind != NULL && (kind[j] < 0 || kind[j] > HS_OV_KIND_EXTREMES) )
+         return HIPSDP_ERR_ARG;
+      off[j + 1] = off[j] + (long long) n[j] * n[j];
+   }
+   if ( rounds != NULL )
+      *rounds = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      const int kd = kind != NULL ? kind[j] : HIPSDP_ONEVAR_NEWTON;
+      if ( hs_onevar_large_declined(kd, lb[j], ub[j], 1e20) )
+      {
+         status[j] = HIPSDP_ONEVAR_DECLINED; optval[j] = 0.0;
+         if ( lmin != NULL ) lmin[j] = 0.0;
+         if ( grad != NULL ) grad[j] = 0.0;
+         if ( evals != NULL ) evals[j] = 0;
+      }
+      else
+         list.push_back(j);
+   }
+   std::stable_sort(list.begin(), list.end(), [&](int a, int c) { return n[a] > n[c]; });
+   const int total = (int) list.size();
+   std::vector<long long> job_len((size_t) total);
+   for (int k = 0; k < total; ++k)
+      job_len[k] = hs_onevar_large_job_len(n[list[k]]);
+   /* the dense rows of every job: row 0 (never read) and row 1 = A_j */
+   DevBuf da;
+   const long long tot = off[count];
+   HS_CALL( da.alloc(2 * tot) );
+   {
+      std::vector<double> ha((size_t) (2 * tot), 0.0);
+      for (int j = 0; j < count; ++j)
+         memcpy(ha.data() + 2 * off[j] + (long long) n[j] * n[j], A + off[j], (size_t) n[j] * n[j] * sizeof(double));
+      HS_CALL( da.up(ha.data(), 2 * tot) );
+   }
+   for (int start = 0; start < total; )
+   {
+      const int end = hs_ovl_chunk_end(job_len.data(), total, start, chunk > 0 ? job_len[start] * chunk : (1LL << 40), chunk > 0 ? chunk : 0);
+      const int cnt = end - start;
+      std::vector<hs_ovl_row> rows((size_t) cnt);
+      long long zlen = 0;
+      std::vector<long long> zoff((size_t) cnt);
+      for (int k = 0; k < cnt; ++k)
+      {
+         const int j = list[start + k];
+         hs_ovl_row& r = rows[k];
+         r.n = n[j]; r.var = 0; r.kind = kind != NULL ? kind[j] : HIPSDP_ONEVAR_NEWTON; r.entry = k;
+         r.lb = lb[j]; r.ub = ub[j]; r.shift = shift[j];
+         zoff[k] = zlen;
+         zlen += hs_cut_mat_len(n[j]);
+      }
+      hs_ovl_layout L;
+      std::vector<long long> wso, outo;
+      hs_onevar_large_plan(0, cnt, rows.data(), zlen, &L, &wso, &outo);
+      DevBuf dev, djobs;
+      HS_CALL( dev.alloc(L.len.dev_len) );
+      HS_CALL( djobs.alloc((long long) ((size_t) cnt * sizeof(hs_ec_job) + sizeof(double) - 1) / (long long) sizeof(double)) );
+      std::vector<double> pin((size_t) L.len.pin_len, 0.0);
+      std::vector<hs_ec_job> jobs((size_t) cnt);
+      for (int k = 0; k < cnt; ++k)
+      {
+         const int j = list[start + k];
+         const long long n2 = (long long) n[j] * n[j];
+         memset(&jobs[k], 0, sizeof(hs_ec_job));
+         jobs[k].n = n[j]; jobs[k].form = HS_EC_DENSE; jobs[k].blk = k; jobs[k].ld = n2;
+         jobs[k].A = da.p + 2 * off[j];
+         jobs[k].Z = dev.p + L.Z + zoff[k];
+         HS_HIP( hipMemcpy(jobs[k].Z, Z + off[j], (size_t) n2 * sizeof(double), hipMemcpyHostToDevice) );
+      }
+      HS_HIP( hipMemcpy(djobs.p, jobs.data(), (size_t) cnt * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+      hs_ovl_chunk c;
+      memset(&c, 0, sizeof(c));
+      c.m = 0; c.count = cnt; c.nz = 0; c.nzmax = 0; c.cap = wg_cap; c.maxevals = maxevals > 0 ? maxevals : 100;
+      c.feastol = feastol; c.infinity = 1e20;
+      c.u = NULL; c.rows = rows.data(); c.dblocks = reinterpret_cast<const hs_ec_job*>(djobs.p); c.dev = dev.p; c.pin = pin.data();
+      long long launches = 0, readbacks = 0;
+      int r = 0;
+      HS_CALL( hs_onevar_large_chunk(0, &c, L, wso, outo, &launches, &readbacks, &r) );
+      if ( rounds != NULL )
+         *rounds += r;
+      for (int k = 0; k < cnt; ++k)
+      {
+         const int j = list[start + k];
+         const double* q = pin.data() + L.res + (long long) k * HS_OV_RES;
+         if ( !(q[0] >= 0.0 && q[0] <= (double) HIPSDP_ONEVAR_DONE) )
+            return HIPSDP_ERR_NUMERIC;
+         status[j] = (int) q[0];
+         optval[j] = q[1];
+         if ( lmin != NULL ) lmin[j] = q[2];
+         if ( grad != NULL ) grad[j] = q[3];
+         if ( evals != NULL ) evals[j] = (int) q[4];
+      }
+      start = end;
+   }
+   return HIPSDP_OK;
+}
+
 /* k_sc_tpower_large alone (csrc/sparsecuts_large.hip) on one host matrix: lmin is given as -1 with tol = -infinity, so the matrix
  * takes part */
 extern "C" int hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, const double* v0, double maxeig, int size,

@@ -1,0 +1,199 @@
+"""CPU: hipsdp_onevar_bounds_large - the C ABI, the libraries and the binding carry the call and its unit entry; every argument error
+is refused before a device is looked at; the chunk layout and the chunk splitter (hs_ovl_layout_make, hs_ovl_chunk_end,
+csrc/hs_cut_plan.cpp) run clean in a stand-alone program under AddressSanitizer + UBSan; the family of
+tests/test_gpu_onevar_large.py (129 .. 512 rows) keeps the counts its tests rely on against the numpy restatement, and the restatement
+agrees with the oracle's solve_one_var_sdp at 129 rows.  What needs a shaped solver is checked in tests/test_gpu_onevar_large.py."""
+import ctypes as C
+import importlib.util
+import inspect
+import os
+import re
+import subprocess
+from conftest import ROOT
+import sdpi_driver
+import onevar_cases as K
+import onevar_all_cases as KA
+import onevar_large_cases as KL
+
+PKG = os.path.join(ROOT, "scip-sdp_amd")
+
+
+def _read(*parts):
+    with open(os.path.join(ROOT, *parts)) as f:
+        return f.read()
+
+
+def test_the_call_is_declared_and_bound():
+    hdr, units = _read("include", "hipsdp.h"), _read("include", "hipsdp_units.h")
+    assert re.search(r"HIPSDP_API\s+int\s+hipsdp_onevar_bounds_large\s*\(\s*hipsdp_solver\s*\*\s*solver\s*,\s*const\s+double\s*\*\s*u\s*,"
+                     r"\s*int\s+count\s*,\s*const\s+int\s*\*\s*blocks\s*,\s*const\s+int\s*\*\s*vars\s*,\s*const\s+int\s*\*\s*kind\s*,"
+                     r"\s*const\s+double\s*\*\s*lb\s*,\s*const\s+double\s*\*\s*ub\s*,\s*const\s+hipsdp_onevar_opts\s*\*\s*opts\s*,"
+                     r"\s*int\s*\*\s*status\s*,\s*double\s*\*\s*optval\s*,\s*double\s*\*\s*lmin\s*,\s*double\s*\*\s*grad\s*,"
+                     r"\s*int\s*\*\s*evals\s*\)", hdr)
+    assert re.search(r"HIPSDP_API\s+int\s+hipsdp_onevar_bounds_large_stats\s*\(\s*long\s+long\s*\*\s*calls\s*,\s*long\s+long\s*\*\s*launches\s*,"
+                     r"\s*long\s+long\s*\*\s*readbacks\s*\)", hdr)
+    assert re.search(r"#define\s+HIPSDP_ONEVAR_LARGE_MAXN\s+512\b", hdr) and re.search(r"#define\s+HIPSDP_SYEVX_MAXN\s+512\b", hdr)
+    assert re.search(r"HIPSDP_API\s+int\s+hipsdp_onevar_large_unit\s*\(\s*int\s+device\s*,\s*int\s+count\s*,\s*const\s+int\s*\*\s*n\s*,", units)
+    assert "hipsdp_onevar_large_unit" not in hdr and not re.search(r"HIPSDP_API\s+int\s+hipsdp_onevar_bounds_large", units)
+    spec = importlib.util.spec_from_file_location("hipsdp_binding_onevar_large", os.path.join(PKG, "binding.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    p = inspect.signature(mod.Solver.onevar_bounds_large).parameters
+    assert list(p) == ["self", "u", "lb", "ub", "feastol", "blocks", "vars", "kind", "infinity", "maxevals"]
+    assert [p[k].default for k in ("blocks", "vars", "kind", "infinity", "maxevals")] == [None, None, None, 1e20, 0]
+    assert callable(mod.onevar_bounds_large_stats) and callable(mod.Solver.onevar_bounds_large_stats) and callable(mod.onevar_large_unit)
+    q = inspect.signature(mod.onevar_large_unit).parameters
+    assert "wg_cap" in q and "chunk" in q
+
+
+def test_libraries_export_the_calls(hb):
+    lib, ulib = hb.lib(), hb.ulib()
+    assert hasattr(lib, "hipsdp_onevar_bounds_large") and hasattr(lib, "hipsdp_onevar_bounds_large_stats")
+    assert hasattr(ulib, "hipsdp_onevar_large_unit") and not hasattr(lib, "hipsdp_onevar_large_unit")
+
+
+def test_argument_errors_and_the_totals_without_a_device(hb):
+    """no device is looked at: every error of the list returns HIPSDP_ERR_ARG (3), status stays, the totals stay (without a device
+    `solver NULL` stands in front of every other error; with a solver each one is checked alone in tests/test_gpu_onevar_large.py)"""
+    lib = hb.lib()
+    f = lib.hipsdp_onevar_bounds_large
+    c, l, r = C.c_longlong(-1), C.c_longlong(-1), C.c_longlong(-1)
+    assert lib.hipsdp_onevar_bounds_large_stats(C.byref(c), C.byref(l), C.byref(r)) == 0
+    assert c.value >= 0 and l.value >= 0 and r.value >= 0
+    assert lib.hipsdp_onevar_bounds_large_stats(None, None, None) == 0
+    opts, neg = hb.OnevarOpts(1e-6, 1e20, 0), hb.OnevarOpts(-1.0, 1e20, 0)
+    o = C.byref(opts)
+    two = (C.c_double * 2)(0.0, 0.0)
+    st = (C.c_int * 2)(7, 7)
+    idx, bad, kbad = (C.c_int * 2)(0, 0), (C.c_int * 2)(0, -1), (C.c_int * 2)(0, 3)
+    calls = [
+        (None, None, 2, None, None, None, None, None, None, None, None),
+        (None, two, 2, idx, idx, idx, two, two, o, st, two),
+        (None, None, 2, idx, idx, idx, two, two, o, st, two),
+        (None, two, 2, idx, idx, idx, None, two, o, st, two),
+        (None, two, 2, idx, idx, idx, two, None, o, st, two),
+        (None, two, 2, idx, idx, idx, two, two, None, st, two),
+        (None, two, 2, idx, idx, idx, two, two, o, None, two),
+        (None, two, 2, idx, idx, idx, two, two, o, st, None),
+        (None, two, -1, idx, idx, idx, two, two, o, st, two),
+        (None, two, 2, bad, idx, idx, two, two, o, st, two),
+        (None, two, 2, idx, bad, idx, two, two, o, st, two),
+        (None, two, 2, idx, idx, kbad, two, two, o, st, two),
+        (None, two, 2, idx, idx, idx, two, two, C.byref(neg), st, two),
+        (None, two, 2, idx, None, idx, two, two, o, st, two),
+        (None, two, 2, None, idx, idx, two, two, o, st, two),
+        (None, two, 2, None, None, None, two, two, o, st, two),
+        (None, two, 0, idx, idx, idx, two, two, o, st, two),
+    ]
+    for a in calls:
+        assert f(*a, None, None, None) == 3, a
+    assert list(st) == [7, 7]
+    c2, l2, r2 = C.c_longlong(-1), C.c_longlong(-1), C.c_longlong(-1)
+    assert lib.hipsdp_onevar_bounds_large_stats(C.byref(c2), C.byref(l2), C.byref(r2)) == 0
+    assert (c2.value, l2.value, r2.value) == (c.value, l.value, r.value)
+    # the order in the source: the argument checks stand in front of the first look at the device
+    src = _read("scip-sdp_amd", "csrc", "onevar_large.hip")
+    body = src[src.index('extern "C" int hipsdp_onevar_bounds_large('):]
+    assert body.index("return HIPSDP_ERR_ARG") < body.index("hs_solver_cut_enter_large(") < body.index("hs_onevar_large_chunk(")
+    assert body.count("return HIPSDP_ERR_ARG") == 3 and body.index("if ( count == 0 )") < body.index("hs_solver_cut_enter_large(")
+
+
+def test_layout_and_chunks_run_clean_under_the_sanitizers(tmp_path):
+    """the stand-alone program tests/harness/onevar_large_plan_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
+    -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
+    preloaded)"""
+    exe = str(tmp_path / "onevar_large_plan_check")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
+           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "onevar_large_plan_check.cpp"),
+           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "onevar large plan check: ok" in r.stdout, r.stdout[-4000:]
+    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+
+
+def test_the_sources_are_where_the_build_expects_them_and_share_their_bodies():
+    assert "csrc/onevar_large.hip" in _read("scip-sdp_amd", "Makefile")
+    host = _read("scip-sdp_amd", "csrc", "onevar_large.hip")
+    assert "__global__" not in host and "hs_ovl_chunk_end(" in host and "hs_solver_cut_blocks(" in host
+    assert '"HIPSDP_ONEVAR_LARGE_CHUNK"' in host
+    hdr = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h")
+    assert "hs_ovl_layout_make" in hdr and "hs_ovl_chunk_end" in hdr and "hip_runtime" not in hdr
+    sx = _read("scip-sdp_amd", "csrc", "syevx.hip")
+    # one body per stage, called by the kernel of one matrix and by the batched one
+    for name in ("d_syevx_col", "d_syevx_values", "d_syevx_tvec", "d_syevx_back"):
+        assert len(re.findall(r"__device__\s+__forceinline__\s+void\s+%s\s*\(" % name, sx)) == 1, name
+        assert len(re.findall(r"\b%s\s*\(" % name, sx)) == 3, name
+    for name in ("k_syevx_col_many", "k_syevx_values_many", "k_syevx_tvec_many", "k_syevx_back_many"):
+        assert name in sx, name
+    # the hazard rule: the kernel boundary is the only synchronisation between workgroups
+    for text in (sx, host):
+        assert "cooperative" not in text.lower() and "grid.sync" not in text and not re.search(r"atomic\w*\s*\(", text)
+    ei = _read("scip-sdp_amd", "csrc", "eigi.hip")
+    assert "k_onevar_large_form" in ei and "k_onevar_large_decide" in ei and "ov_decide(C, &S," in ei
+    assert len(re.findall(r"__device__\s+__forceinline__\s+void\s+ov_decide\s*\(", ei)) == 1
+
+
+def test_family_counts():
+    """576 jobs: the status mix per size, at most 7 evaluations per job, the undecidable jobs per size, and the cap of 5 % over the
+    WHOLE family (the 512-row size alone has 4 of 72)"""
+    assert KL.SIZES == [(129, 6, 10), (130, 6, 10), (192, 6, 12), (257, 6, 12), (511, 4, 16), (512, 4, 16)]
+    total = und = evals = 0
+    for size in KL.SIZES:
+        mix = {K.INNER: 0, K.INFEASIBLE: 0, K.LB: 0}
+        bad = 0
+        for fl, sd, A, lb, ub, refs in KL.instances(size):
+            assert A.shape == (size[1] + 1, size[0], size[0])
+            for r in refs:
+                total += 1
+                mix[r[0]] += 1
+                bad += 0 if K.decidable(K.NEWTON, r[5]) else 1
+                evals += r[4]
+                assert r[4] <= 7
+        assert (mix[K.INNER], mix[K.INFEASIBLE], mix[K.LB]) == KL.STATUS_MIX[size[0]], (size, mix)
+        assert bad == KL.UNDECIDABLE[size[0]], (size, bad)
+        und += bad
+    assert total == KL.JOBS == 576 and und == 6
+    assert und <= K.UNDECIDABLE_CAP * total
+    assert 3.0 <= evals / total <= 3.2
+    print("%d of %d jobs undecidable, %.2f evaluations per job" % (und, total, evals / total))
+
+
+def _entries(M):
+    n = M.shape[0]
+    return [(r, c, float(M[r, c])) for r in range(n) for c in range(r + 1) if M[r, c] != 0.0]
+
+
+def test_restatement_agrees_with_the_oracle_at_129_rows():
+    """as tests/test_onevar_cpu.py at its sizes: the device formulation Z(u) + (mu - u_i) A_i against the reference's mu A_i - C_i"""
+    size = KL.SIZES[0]
+    worst = 0.0
+    for fl, sd, A, lb, ub, refs in KL.instances(size):
+        Z = K.z_of(A, ub)
+        for i, r in enumerate(refs):
+            Cm = A[0].copy()
+            for k in range(len(ub)):
+                if k != i and ub[k] != 0.0:
+                    Cm -= A[k + 1] * ub[k]
+            calls = [0]
+
+            def lmin(M):
+                calls[0] += 1
+                return sdpi_driver.lmin_numpy(M)
+            objval, ov, cert = sdpi_driver.solve_one_var_sdp(1.0, lb[i], ub[i], size[0], _entries(Cm), _entries(A[i + 1]), K.FEASTOL, lmin=lmin)
+            assert objval is not None
+            st = K.INFEASIBLE if objval >= sdpi_driver.INF else (K.LB if ov == lb[i] and cert == 0.0 else K.INNER)
+            if not K.decidable(K.NEWTON, r[5]):
+                continue
+            assert (st, calls[0]) == (r[0], r[4]), (fl, sd, i)
+            if st == K.LB or (st != K.INNER and len(r[5]) <= 2):
+                assert ov == r[1], (fl, sd, i)
+            else:
+                bound, g = K.inner_bound(Z, A[i + 1], ub[i], ov, r[1], K.FEASTOL)
+                assert abs(ov - r[1]) <= bound, (fl, sd, i)
+                if st == K.INNER:
+                    worst = max(worst, abs(ov - r[1]) * g / K.FEASTOL)
+    print("n = 129: worst |optval - oracle| g / feastol = %.3g" % worst)
+    assert KA.EXTREMES == 2
