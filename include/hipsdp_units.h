@@ -191,6 +191,53 @@ HIPSDP_API int  hipsdp_onevar_large_unit(int device, int count, const int* n, co
 HIPSDP_API int  hipsdp_objs_fanout_unit(int device, int count, int m, int q, int nblk, const int* ns, const double* B, const double* b_own,
    int have_start, const double* y, const double* x, const double* z, const double* XZ, int gap, double guard, long long* lane_len,
    long long* offs, double* lanes, int* launches);
+/* The small-problem passes and their recorded forms inside the single-workgroup batch kernel (csrc/kernels.hip: the RB_* records of
+ * k_red_batch).  recorded = 0: the engine function with no batch open, so the kernel gets its own launch; 1: the same call between
+ * hs_red_batch_hold and hs_red_batch_release.  *pending: the records waiting just before the release: 0 when the call declined (too much
+ * work for one workgroup) or recorded = 0.  Outputs that an operation does not write come back as NaN.
+ * dir_block: out = s1 Zinv - X - sym((c X R + E) Zinv), n x n each, E may be NULL; n > 48 gives the engine's HIPSDP_ERR_ARG.
+ * lp_rows: t_r = Dext[r, :] . v (Dext q x m1); mode 0: out1 = t - z; mode 1: out1 = t + eta rd, out2 = sigmu / z - x - (x out1 + elp) / z
+ *    (elp may be NULL); out1[q], out2[q].
+ * apply_A: out[i] = sum_k <A_k[i], V_k> + sum_r Dext[r][i] vlp[r], i < m1: nblk in 1 .. 8 blocks of n2[k] entries, one behind the other
+ *    in A (block k as m1 x n2[k]) and in V; q >= 0 LP rows (Dext q x m1); epi 1: vout[i - 1] = out[i] - scal vin[i - 1], epi 2:
+ *    vout[i - 1] = vin[i - 1] scal - out[i] for i >= 1; out[m1], vin[m1 - 1], vout[m1 - 1].
+ * elementwise: in[6][n] = x, z, r, elp, a, b; par = sigmu, eta, alpha, s0, s1.  hs_lp_dir: o_lp = sigmu / z - x - (eta x r + elp) / z
+ *    (use_elp = 0: no elp); hs_vec_mul: o_mul = a .* b; hs_make_ext: o_ext[n + 1] = [s0; s1 a]; hs_axpy3: ys += alpha xs on three vectors
+ *    of nn[0], nn[1], nn[2] >= 0 entries, one behind the other in xs and ys.
+ * gemv_t: out[e] = sum_i coef[i] A[i lda + e] + sa add[e], R rows of lda >= E doubles; add_mode 0: no additive term, 1: add[E] an array
+ *    of its own, 2: the output itself, which starts as add[E]. */
+HIPSDP_API int  hipsdp_small_dir_block_unit(int device, int n, double c, double s1, const double* X, const double* R, const double* E,
+   const double* Zinv, int recorded, double* out, int* pending);
+HIPSDP_API int  hipsdp_small_lp_rows_unit(int device, int q, int m1, const double* Dext, const double* v, int mode, double eta, double sigmu,
+   const double* x, const double* z, const double* rd, const double* elp, int recorded, double* out1, double* out2, int* pending);
+HIPSDP_API int  hipsdp_small_apply_A_unit(int device, int m1, int nblk, const int* n2, const double* A, const double* V, int q,
+   const double* Dext, const double* vlp, int epi, double scal, const double* vin, int recorded, double* out, double* vout, int* pending);
+HIPSDP_API int  hipsdp_small_elementwise_unit(int device, int n, const int* nn, const double* par, int use_elp, const double* in,
+   const double* xs, int recorded, double* o_lp, double* o_mul, double* o_ext, double* ys, int* pending);
+HIPSDP_API int  hipsdp_small_gemv_t_unit(int device, int R, long long E, long long lda, const double* A, const double* coef, double sa,
+   int add_mode, const double* add, int recorded, double* out, int* pending);
+/* `count` <= 8 reductions of one kind (0 hs_dot <a, b>, 1 hs_absmax max |a|, 2 hs_ratio_min min over b < 0 of -a / b, 3 hs_lp_s0
+ * sum (a / b) c^2), reduction j over len[j] entries (operands one behind the other in a, b, c) into out[slot[j]], slot[j] < nslots <= 32,
+ * accumulate[j] = 1: combined with what the slot holds.  Every slot is first set to preset[.] by hs_fill_scalar.  recorded = 1: fills and
+ * reductions inside one hs_red_batch_begin / hs_red_batch_end (the fills are records too: *pending counts them, and more records than a
+ * batch holds are launched on the way); 0: every call a launch of its own */
+HIPSDP_API int  hipsdp_reductions_unit(int device, int kind, int count, const int* len, const int* slot, const int* accumulate,
+   const double* a, const double* b, const double* c, int nslots, const double* preset, int recorded, double* out, int* pending);
+/* the two small solves with the factor of M (m <= 64, M symmetric positive definite, factored on the device as the engine does it;
+ * *fail its flag).  form 0: hs_red_batch_solve inside a batch, nrhs <= 8 right-hand sides ld >= m apart, rhs[nrhs x ld] in place.
+ * form 1: k_solve2_small: rhs[2 m] comes in as [g ; b] and goes out as the two solutions, u2[m], wt[m + 1].  The environment switch
+ * HIPSDP_SMALL_SOLVE=subst is read by the call */
+HIPSDP_API int  hipsdp_small_solve_unit(int device, int m, const double* M, int form, int nrhs, long long ld, double* rhs, double* u2,
+   double* wt, int* pending, int* fail);
+/* out[v][e] = sum_i c[v][i] A[i lda + e], v < 3 (c[3][R], out[3][E]): fused = 1 hs_gemv_t3 (and, when it does not take the shape, the
+ * three hs_gemv_t calls the engine then makes), 0: three hs_gemv_t calls; *took = 1 when the fused kernel ran */
+HIPSDP_API int  hipsdp_gemv_t3_unit(int device, int R, long long E, long long lda, const double* A, const double* c, int fused, double* out,
+   int* took);
+/* hs_gemv_n: out[v][i] = sum_e A[i lda + e] V[v][e], nv <= 4 (V[nv][E], out[nv][R]); the device copies of the vectors start voff doubles
+ * behind a 16-byte aligned address; wsdoubles: the workspace given for the split form.  info[0] = slices a row is cut into, info[1] = 1
+ * when the two-at-a-time kernel is taken (the launcher's rule recomputed from the same inputs) */
+HIPSDP_API int  hipsdp_pass_a_unit(int device, int R, long long E, long long lda, const double* A, int nv, const double* V, int voff,
+   long long wsdoubles, double* out, int* info);
 
 #ifdef __cplusplus
 }

@@ -1176,6 +1176,136 @@ def tail_dots_unit(a, v, fused, device=0):
     return out
 
 
+def _opt(a):
+    return None if a is None else _dp(a)
+
+
+def small_dir_block_unit(c, s1, X, R, E, Zinv, recorded, device=0):
+    """hs_dir_block_small launched (recorded=False) or as a record of the batch kernel -> (out[n, n], records pending)"""
+    X, R, Zinv = _f64(X), _f64(R), _f64(Zinv)
+    E = None if E is None else _f64(E)
+    n = X.shape[0]
+    assert X.shape == R.shape == Zinv.shape == (n, n) and (E is None or E.shape == (n, n))
+    out, pend = np.zeros((n, n)), C.c_int(-1)
+    _chk(ulib().hipsdp_small_dir_block_unit(device, n, C.c_double(c), C.c_double(s1), _dp(X), _dp(R), _opt(E), _dp(Zinv), int(recorded),
+                                            _dp(out), C.byref(pend)), "hipsdp_small_dir_block_unit")
+    return out, pend.value
+
+
+def small_lp_rows_unit(Dext, v, mode, eta, sigmu, x, z, rd, elp, recorded, device=0):
+    """hs_lp_rows_small -> (out1[q], out2[q], records pending)"""
+    Dext, v, x, z, rd = _f64(Dext), _f64(v), _f64(x), _f64(z), _f64(rd)
+    elp = None if elp is None else _f64(elp)
+    q, m1 = Dext.shape
+    assert v.size == m1 and x.size == z.size == rd.size == q and (elp is None or elp.size == q)
+    o1, o2, pend = np.zeros(q), np.zeros(q), C.c_int(-1)
+    _chk(ulib().hipsdp_small_lp_rows_unit(device, q, m1, _dp(Dext), _dp(v), int(mode), C.c_double(eta), C.c_double(sigmu), _dp(x), _dp(z),
+                                          _dp(rd), _opt(elp), int(recorded), _dp(o1), _dp(o2), C.byref(pend)), "hipsdp_small_lp_rows_unit")
+    return o1, o2, pend.value
+
+
+def small_apply_A_unit(As, Vs, Dext, vlp, epi, scal, vin, recorded, device=0):
+    """hs_apply_A_small over the blocks As[k] (m1 x n2_k) with Vs[k] (n2_k) and the LP rows Dext (q x m1, q may be 0) with vlp
+    -> (out[m1], vout[m1 - 1], records pending)"""
+    As = [_f64(a) for a in As]
+    Vs = [_f64(v).ravel() for v in Vs]
+    m1 = As[0].shape[0]
+    n2 = np.array([a.shape[1] for a in As], dtype=np.int32)
+    assert all(a.shape[0] == m1 for a in As) and all(v.size == k for v, k in zip(Vs, n2))
+    A = np.concatenate([a.ravel() for a in As])
+    V = np.concatenate(Vs)
+    Dext, vlp, vin = _f64(Dext).reshape(-1, m1), _f64(vlp), _f64(vin)
+    q = Dext.shape[0]
+    assert vlp.size == q and vin.size == m1 - 1
+    out, vout, pend = np.zeros(m1), np.zeros(m1 - 1), C.c_int(-1)
+    _chk(ulib().hipsdp_small_apply_A_unit(device, m1, len(As), _ip(n2), _dp(A), _dp(V), q, _dp(Dext), _dp(vlp), int(epi), C.c_double(scal),
+                                          _dp(vin), int(recorded), _dp(out), _dp(vout), C.byref(pend)), "hipsdp_small_apply_A_unit")
+    return out, vout, pend.value
+
+
+def small_elementwise_unit(vecs, par, xs, ys, nn, use_elp, recorded, device=0):
+    """hs_lp_dir, hs_vec_mul, hs_make_ext and hs_axpy3 in one call: vecs[6, n] = x, z, r, elp, a, b; par = sigmu, eta, alpha, s0, s1;
+    xs, ys: the three vectors of hs_axpy3 (nn[0], nn[1], nn[2] entries) one behind the other
+    -> (o_lp[n], o_mul[n], o_ext[n + 1], ys after the update, records pending)"""
+    vecs, par, xs, ys = _f64(vecs), _f64(par), _f64(xs), _f64(ys).copy()
+    nn = np.ascontiguousarray(nn, dtype=np.int32)
+    n = vecs.shape[1]
+    assert vecs.shape == (6, n) and par.size == 5 and nn.size == 3 and xs.size == ys.size == int(nn.sum())
+    o_lp, o_mul, o_ext, pend = np.zeros(n), np.zeros(n), np.zeros(n + 1), C.c_int(-1)
+    _chk(ulib().hipsdp_small_elementwise_unit(device, n, _ip(nn), _dp(par), int(use_elp), _dp(vecs), _dp(xs), int(recorded), _dp(o_lp),
+                                              _dp(o_mul), _dp(o_ext), _dp(ys), C.byref(pend)), "hipsdp_small_elementwise_unit")
+    return o_lp, o_mul, o_ext, ys, pend.value
+
+
+def small_gemv_t_unit(A, E, coef, sa, add, add_mode, recorded, device=0):
+    """hs_gemv_t on the first E entries of the rows of A[R, lda]; add_mode 0: no additive term, 1: add an array of its own, 2: add is
+    what the output holds before the call -> (out[E], records pending)"""
+    A, coef = _f64(A), _f64(coef)
+    R, lda = A.shape
+    add = None if add is None else _f64(add)
+    assert coef.size == R and 1 <= E <= lda and (add_mode == 0 or add.size == E)
+    out, pend = np.zeros(E), C.c_int(-1)
+    _chk(ulib().hipsdp_small_gemv_t_unit(device, R, C.c_longlong(E), C.c_longlong(lda), _dp(A), _dp(coef), C.c_double(sa), int(add_mode),
+                                         _opt(add), int(recorded), _dp(out), C.byref(pend)), "hipsdp_small_gemv_t_unit")
+    return out, pend.value
+
+
+def reductions_unit(kind, lens, slots, accumulate, a, b, c, preset, recorded, device=0):
+    """reductions of one kind (0 dot, 1 absmax, 2 ratio_min, 3 lp_s0), reduction j over lens[j] entries of a, b, c (one behind the
+    other) into slot slots[j] of preset.size slots, every slot first set to preset -> (out[nslots], records pending)"""
+    lens, slots, accumulate = (np.ascontiguousarray(v, dtype=np.int32) for v in (lens, slots, accumulate))
+    a, b, c, preset = _f64(a), _f64(b), _f64(c), _f64(preset)
+    assert lens.size == slots.size == accumulate.size and a.size == b.size == c.size == int(lens.sum())
+    out, pend = np.zeros(preset.size), C.c_int(-1)
+    _chk(ulib().hipsdp_reductions_unit(device, int(kind), lens.size, _ip(lens), _ip(slots), _ip(accumulate), _dp(a), _dp(b), _dp(c),
+                                       preset.size, _dp(preset), int(recorded), _dp(out), C.byref(pend)), "hipsdp_reductions_unit")
+    return out, pend.value
+
+
+def small_solve_unit(M, rhs, form, ld=None, device=0):
+    """the small solves with the factor of M (m <= 64).  form 0: hs_red_batch_solve on rhs[nrhs, ld] in place -> (rhs, records pending,
+    factorization flag); form 1: k_solve2_small on rhs = [g ; b] -> (rhs2[2 m], u2[m], wt[m + 1], factorization flag)"""
+    M = _f64(M)
+    m = M.shape[0]
+    rhs = _f64(rhs).copy()
+    pend, fail = C.c_int(-1), C.c_int(-1)
+    if form == 0:
+        nrhs, ld = rhs.shape
+        _chk(ulib().hipsdp_small_solve_unit(device, m, _dp(M), 0, nrhs, C.c_longlong(ld), _dp(rhs), None, None, C.byref(pend),
+                                            C.byref(fail)), "hipsdp_small_solve_unit")
+        return rhs, pend.value, fail.value
+    assert rhs.size == 2 * m
+    u2, wt = np.zeros(m), np.zeros(m + 1)
+    _chk(ulib().hipsdp_small_solve_unit(device, m, _dp(M), 1, 0, C.c_longlong(0), _dp(rhs), _dp(u2), _dp(wt), C.byref(pend),
+                                        C.byref(fail)), "hipsdp_small_solve_unit")
+    return rhs, u2, wt, fail.value
+
+
+def gemv_t3_unit(A, E, c, fused, device=0):
+    """three linear combinations c[3, R] of the first E entries of the rows of A[R, lda] -> (out[3, E], fused kernel took the shape)"""
+    A, c = _f64(A), _f64(c)
+    R, lda = A.shape
+    assert c.shape == (3, R) and 1 <= E <= lda
+    out, took = np.zeros((3, E)), C.c_int(-1)
+    _chk(ulib().hipsdp_gemv_t3_unit(device, R, C.c_longlong(E), C.c_longlong(lda), _dp(A), _dp(c), int(fused), _dp(out), C.byref(took)),
+         "hipsdp_gemv_t3_unit")
+    return out, took.value
+
+
+def pass_a_unit(A, E, V, voff=0, wsdoubles=0, device=0):
+    """hs_gemv_n on the first E entries of the rows of A[R, lda] with the vectors V[nv, E] (device copies voff doubles behind an aligned
+    address) and a workspace of wsdoubles -> (out[nv, R], slices a row was cut into, two-at-a-time kernel taken)"""
+    A, V = _f64(A), _f64(V)
+    R, lda = A.shape
+    nv = V.shape[0]
+    assert V.shape == (nv, E) and 1 <= E <= lda
+    out = np.zeros((nv, R))
+    info = np.zeros(2, dtype=np.int32)
+    _chk(ulib().hipsdp_pass_a_unit(device, R, C.c_longlong(E), C.c_longlong(lda), _dp(A), nv, _dp(V), int(voff), C.c_longlong(wsdoubles),
+                                   _dp(out), _ip(info)), "hipsdp_pass_a_unit")
+    return out, int(info[0]), bool(info[1])
+
+
 def trtri(A, device=0):
     A = _f64(A)
     Li = np.zeros_like(A)

@@ -59,6 +59,7 @@ int hs_copy_scalar(hipStream_t s, double* dst, const double* src);
 void hs_red_batch_hold(hipStream_t s);
 int hs_red_batch_release(void);
 int hs_red_batch_flush(void);
+int hs_red_batch_pending(void);            /* records waiting for the launch */
 int hs_red_batch_end_all(void);
 int hs_make_ext(hipStream_t s, int m, double s0, double s1, const double* v, double* ext);
 int hs_lp_rows_small(hipStream_t s, int q, int m1, const double* Dext, const double* v, int mode, double eta, double sigmu, const double* x,
@@ -888,6 +889,10 @@ struct hs_solve1_args
 #define S1_BIND_P
 #endif
 int hs_small_solve_by_substitution(void);
+/* k_solve2_small (ipm.hip), m <= 64: rhs2 = [g ; b] with g = Mx[0, 1:], both solved with the single-block factor (dinv = inv(L) as 64 x 64,
+ * L as m x m), then u2 = rhs2[m:] - rhs2[:m] and wt = [1, -rhs2[:m]]; subst: hs_small_solve_by_substitution() */
+int hs_solve2_small(hipStream_t st, int m, const double* Mx, const double* b, const double* dinv, const double* L, double* rhs2, double* u2,
+   double* wt, int subst);
 int hs_solve1_fits(int m, int q, int nblk, const int* n);
 long long hs_solve1_ws_doubles(int m, int q, int nblk, const int* n);
 int hs_solve1_launch(hipStream_t st, const hs_solve1_args* a);

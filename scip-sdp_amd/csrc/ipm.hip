@@ -1961,6 +1961,14 @@ __global__ void __launch_bounds__(128) k_solve2_small(int m, const double* __res
    }
 }
 
+int hs_solve2_small(hipStream_t st, int m, const double* Mx, const double* b, const double* dinv, const double* L, double* rhs2, double* u2,
+   double* wt, int subst)
+{
+   hipLaunchKernelGGL(k_solve2_small, dim3(1), dim3(128), 0, st, m, Mx, b, dinv, L, rhs2, u2, wt, subst);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
 /* h = AH[1:] - eta * rp */
 __global__ void k_h(int m, double eta, const double* __restrict__ AH, const double* __restrict__ rp, double* __restrict__ h)
 {
@@ -4282,8 +4290,7 @@ struct GeneralSolve
          HS_CALL( hs_potrf_psd(st, m, s->Lm, s->dinvm, s->flags + 2, s->dya, s->regmask, setf) );
          if ( m <= 64 )
          {
-            hipLaunchKernelGGL(k_solve2_small, dim3(1), dim3(128), 0, st, m, s->Mx, s->b, s->dinvm, s->Lm, s->rhs2, s->u2, s->wt, hs_small_solve_by_substitution());
-            HS_LAUNCH_CHECK();
+            HS_CALL( hs_solve2_small(st, m, s->Mx, s->b, s->dinvm, s->Lm, s->rhs2, s->u2, s->wt, hs_small_solve_by_substitution()) );
          }
          else
          {

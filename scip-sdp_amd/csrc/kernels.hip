@@ -811,6 +811,7 @@ __device__ __forceinline__ double block_reduce_256(double v, double* sh)
 #define RED_ABSMAX   1
 #define RED_RATIOMIN 2
 #define RED_LPS0     3
+#define RED_STAGE_N  2048   /* entries per workgroup of the first stage; up to that many, one workgroup writes the result itself */
 
 template<int KIND> struct RedTraits;
 template<> struct RedTraits<RED_DOT>      { typedef OpSum OP; };
@@ -911,18 +912,64 @@ struct rb_args { int cnt; rb_desc d[RB_MAX]; rb_finish fin; int pub_n; const dou
 static_assert(sizeof(rb_args) <= 4096, "the records travel as kernel arguments");
 static thread_local struct { bool open; hipStream_t s; int hold; size_t smem; rb_args args; } g_rb = {false, NULL, 0, 0, {0, {}}};
 
+/* a launched reduction of more than RED_STAGE_N entries takes two stages (reduce_launch): k_reduce_stage1 on g = ceil(n / RED_STAGE_N)
+ * workgroups, thread t of workgroup k over the entries 256 k + t, 256 (g + k) + t, ..., then k_reduce_stage2 over the g partial results.
+ * Its record re-enacts both: the one workgroup keeps the g partial results of a thread position in registers (each over the same
+ * entries in the same order; one pass, so the loads of the g virtual workgroups are in flight together), reduces each as its
+ * workgroup would, and combines them as the second stage does - the same bits as the launch (tests/test_gpu_small_path.py,
+ * red_workgroup_form at 2049 and 16 384 entries: before, the record summed in the one-workgroup order at every length). */
+#define RB_STAGES (RB_MAXN / RED_STAGE_N)
+static_assert(RB_STAGES * RED_STAGE_N == RB_MAXN && RB_STAGES <= 256, "rb_run keeps one partial result per first-stage workgroup");
+
 template<int KIND>
-__device__ __forceinline__ double rb_run(const rb_desc& D, double* sh)
+__device__ __forceinline__ double rb_run(const rb_desc& D, double* sh, double* part)
 {
    typedef typename RedTraits<KIND>::OP OP;
-   double v = OP::id();
    const double* a = (const double*) D.p[0];
    const double* b = (const double*) D.p[1];
    const double* c = (const double*) D.p[2];
    double* out = (double*) D.p[3];
-   for (long long i = threadIdx.x; i < D.i[0]; i += 256)
-      v = OP::f(v, red_elem<KIND>(i, a, b, c));
-   v = block_reduce_256<OP>(v, sh);
+   const int n = D.i[0];
+   const int g = (n + RED_STAGE_N - 1) / RED_STAGE_N;
+   double v = OP::id();
+   if ( g <= 1 )
+   {
+      for (long long i = threadIdx.x; i < n; i += 256)
+         v = OP::f(v, red_elem<KIND>(i, a, b, c));
+      v = block_reduce_256<OP>(v, sh);
+   }
+   else
+   {
+      double w[RB_STAGES];
+#pragma unroll
+      for (int k = 0; k < RB_STAGES; ++k)
+         w[k] = OP::id();
+      for (int base = threadIdx.x; base < n; base += 256 * g)
+      {
+#pragma unroll
+         for (int k = 0; k < RB_STAGES; ++k)
+         {
+            const int i = base + 256 * k;
+            if ( k < g && i < n )
+               w[k] = OP::f(w[k], red_elem<KIND>(i, a, b, c));
+         }
+      }
+#pragma unroll
+      for (int k = 0; k < RB_STAGES; ++k)
+      {
+         if ( k < g )
+         {
+            const double r = block_reduce_256<OP>(w[k], sh);
+            if ( threadIdx.x == 0 )
+               part[k] = r;
+         }
+      }
+      __syncthreads();
+      /* k_reduce_stage2 with nparts = g <= 256: one term per thread */
+      if ( (int) threadIdx.x < g )
+         v = OP::f(v, part[threadIdx.x]);
+      v = block_reduce_256<OP>(v, sh);
+   }
    if ( threadIdx.x == 0 )
       *out = D.accumulate ? OP::f(*out, v) : v;
    return v;
@@ -977,6 +1024,7 @@ __global__ void __launch_bounds__(256) k_red_batch(rb_args A)
 {
    extern __shared__ double rb_dyn[];
    __shared__ double sh[4];
+   __shared__ double sh_part[RB_STAGES];
    for (int t = 0; t < A.cnt; ++t)
    {
       {
@@ -1024,10 +1072,10 @@ __global__ void __launch_bounds__(256) k_red_batch(rb_args A)
       const unsigned long long c_begin = (A.dbg != NULL) ? clock64() : 0ULL;
       switch ( D.kind )
       {
-      case RED_DOT:      rb_run<RED_DOT>(D, sh); break;
-      case RED_ABSMAX:   rb_run<RED_ABSMAX>(D, sh); break;
-      case RED_RATIOMIN: rb_run<RED_RATIOMIN>(D, sh); break;
-      case RED_LPS0:     rb_run<RED_LPS0>(D, sh); break;
+      case RED_DOT:      rb_run<RED_DOT>(D, sh, sh_part); break;
+      case RED_ABSMAX:   rb_run<RED_ABSMAX>(D, sh, sh_part); break;
+      case RED_RATIOMIN: rb_run<RED_RATIOMIN>(D, sh, sh_part); break;
+      case RED_LPS0:     rb_run<RED_LPS0>(D, sh, sh_part); break;
       case RB_FILL:      if ( threadIdx.x == 0 ) *(double*) D.p[3] = D.d[0]; break;
       case RB_COPY1:     if ( threadIdx.x == 0 ) *(double*) D.p[3] = *(const double*) D.p[0]; break;
       case RB_STAGE2:
@@ -1230,7 +1278,7 @@ __global__ void __launch_bounds__(256) k_red_batch(rb_args A)
                   {
                      const int i = base + min(ii + u, nm - 1);
                      xa[u] = ap[(long long) i * n2a];
-                     xd[u] = dp[i];
+                     xd[u] = hl ? dp[i] : 0.0;         /* (q = 0: Dext has no row to read in place of a thread's own - tests/small_path_cases.py, applya_straight with q = 0) */
                   }
 #pragma unroll
                   for (int u = 0; u < 8; ++u)
@@ -1568,6 +1616,12 @@ int hs_red_batch_release(void)
 int hs_red_batch_flush(void)
 {
    return (g_rb.open && g_rb.hold > 0) ? rb_flush() : HS_OK;
+}
+
+/* records waiting for the batch's launch (the unit entries: whether a call was recorded or declined) */
+int hs_red_batch_pending(void)
+{
+   return g_rb.args.cnt;
 }
 
 /* drops whatever is recorded (an earlier call may have left a batch open on an error path) */
@@ -1937,7 +1991,7 @@ static int reduce_launch(hipStream_t s, long long n, const double* a, const doub
       }
       return HS_OK;
    }
-   const int g = grid_for(n, 2048, 256);
+   const int g = grid_for(n, RED_STAGE_N, 256);
    (void) hs_red_batch_flush();
    if ( g == 1 )
    {

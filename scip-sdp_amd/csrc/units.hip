@@ -1942,3 +1942,345 @@ extern "C" int hipsdp_objs_fanout_unit(int device, int count, int m, int q, int 
    HS_HIP( hipDeviceSynchronize() );
    return dL.down(lanes, nl * len);
 }
+
+/* ---- test entries of the small-problem passes and of their recorded forms inside the single-workgroup batch kernel (kernels.hip: the
+ * RB_* records of k_red_batch).  recorded = 0: the engine function with no batch open, the kernel gets its own launch; 1: the same call
+ * between hs_red_batch_hold(0) and hs_red_batch_release().  *pending: records waiting just before the release - 0 when the call declined
+ * (or recorded = 0).  Outputs start as NaN on the device, so that what an operation does not write shows. */
+namespace {
+struct RecScope
+{
+   int recorded;
+   explicit RecScope(int r) : recorded(r) { hs_red_batch_reset(); if ( recorded ) hs_red_batch_hold(0); }
+   int close(int rc, int* pending)
+   {
+      if ( pending != NULL ) *pending = hs_red_batch_pending();
+      if ( recorded && rc == HS_OK ) rc = hs_red_batch_release();
+      if ( hipDeviceSynchronize() != hipSuccess && rc == HS_OK ) rc = HS_ERR_HIP;
+      hs_red_batch_reset();
+      return rc;
+   }
+};
+bool flag01(int v) { return v == 0 || v == 1; }
+}
+
+/* hs_dir_block_small: out = s1 Zinv - X - sym((c X R + E) Zinv), n x n each, E may be NULL.  n > HS_SMALL_N: the engine's HS_ERR_ARG */
+extern "C" int hipsdp_small_dir_block_unit(int device, int n, double c, double s1, const double* X, const double* R, const double* E,
+   const double* Zinv, int recorded, double* out, int* pending)
+{
+   if ( n < 1 || n > 4096 || !flag01(recorded) || X == NULL || R == NULL || Zinv == NULL || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n2 = (long long) n * n;
+   DevBuf dX, dR, dE, dZ, dO;
+   HS_CALL( dX.alloc(n2) ); HS_CALL( dR.alloc(n2) ); HS_CALL( dE.alloc(n2) ); HS_CALL( dZ.alloc(n2) ); HS_CALL( dO.alloc(n2) );
+   HS_CALL( nan_fill(dO, n2) );
+   HS_CALL( dX.up(X, n2) ); HS_CALL( dR.up(R, n2) ); HS_CALL( dZ.up(Zinv, n2) );
+   if ( E != NULL ) HS_CALL( dE.up(E, n2) );
+   RecScope sc(recorded);
+   int rc = hs_dir_block_small(0, n, c, dX.p, dR.p, E != NULL ? dE.p : NULL, dZ.p, s1, dO.p);
+   HS_CALL( sc.close(rc, pending) );
+   return dO.down(out, n2);
+}
+
+/* hs_lp_rows_small: t_r = Dext[r, :] . v (Dext q x m1); mode 0: out1 = t - z; mode 1: out1 = t + eta rd, out2 = sigmu / z - x -
+ * (x out1 + elp) / z (elp may be NULL); out1[q], out2[q] (mode 0 leaves out2 alone) */
+extern "C" int hipsdp_small_lp_rows_unit(int device, int q, int m1, const double* Dext, const double* v, int mode, double eta, double sigmu,
+   const double* x, const double* z, const double* rd, const double* elp, int recorded, double* out1, double* out2, int* pending)
+{
+   if ( q < 1 || m1 < 1 || !flag01(mode) || !flag01(recorded) || Dext == NULL || v == NULL || x == NULL || z == NULL || rd == NULL
+         || out1 == NULL || out2 == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long qm = (long long) q * m1;
+   DevBuf dD, dv, dx, dz, dr, de, d1, d2;
+   HS_CALL( dD.alloc(qm) ); HS_CALL( dv.alloc(m1) ); HS_CALL( dx.alloc(q) ); HS_CALL( dz.alloc(q) ); HS_CALL( dr.alloc(q) );
+   HS_CALL( de.alloc(q) ); HS_CALL( d1.alloc(q) ); HS_CALL( d2.alloc(q) );
+   HS_CALL( nan_fill(d1, q) ); HS_CALL( nan_fill(d2, q) );
+   HS_CALL( dD.up(Dext, qm) ); HS_CALL( dv.up(v, m1) ); HS_CALL( dx.up(x, q) ); HS_CALL( dz.up(z, q) ); HS_CALL( dr.up(rd, q) );
+   if ( elp != NULL ) HS_CALL( de.up(elp, q) );
+   RecScope sc(recorded);
+   int rc = hs_lp_rows_small(0, q, m1, dD.p, dv.p, mode, eta, sigmu, dx.p, dz.p, dr.p, elp != NULL ? de.p : NULL, d1.p, d2.p);
+   HS_CALL( sc.close(rc, pending) );
+   HS_CALL( d1.down(out1, q) );
+   return d2.down(out2, q);
+}
+
+/* hs_apply_A_small: out[i] = sum_k <A_k[i], V_k> + sum_r Dext[r][i] vlp[r], i < m1, over nblk blocks of n2[k] entries (A: the blocks one
+ * behind the other, block k as m1 x n2[k]; V likewise) and q LP rows (Dext q x m1; q = 0: not read); epi 1: vout[i - 1] = out[i] - scal
+ * vin[i - 1], epi 2: vout[i - 1] = vin[i - 1] scal - out[i], i >= 1 (epi 0 leaves vout alone); out[m1], vin, vout[m1 - 1] */
+extern "C" int hipsdp_small_apply_A_unit(int device, int m1, int nblk, const int* n2, const double* A, const double* V, int q,
+   const double* Dext, const double* vlp, int epi, double scal, const double* vin, int recorded, double* out, double* vout, int* pending)
+{
+   if ( m1 < 1 || nblk < 1 || nblk > HS_AS_MAXBLK || n2 == NULL || A == NULL || V == NULL || q < 0 || (q > 0 && (Dext == NULL || vlp == NULL))
+         || epi < 0 || epi > 2 || (m1 > 1 && (vin == NULL || vout == NULL)) || !flag01(recorded) || out == NULL )
+      return HIPSDP_ERR_ARG;
+   long long tot = 0;
+   for (int k = 0; k < nblk; ++k)
+   {
+      if ( n2[k] < 1 )
+         return HIPSDP_ERR_ARG;
+      tot += n2[k];
+   }
+   HS_CALL( pick_device(device) );
+   DevBuf dA, dV, dD, dl, dO, di, dvo;
+   HS_CALL( dA.alloc(tot * m1) ); HS_CALL( dV.alloc(tot) ); HS_CALL( dD.alloc((long long) q * m1) ); HS_CALL( dl.alloc(q) );
+   HS_CALL( dO.alloc(m1) ); HS_CALL( di.alloc(m1 - 1) ); HS_CALL( dvo.alloc(m1 - 1) );
+   HS_CALL( nan_fill(dO, m1) ); HS_CALL( nan_fill(dvo, m1 - 1) );
+   HS_CALL( dA.up(A, tot * m1) ); HS_CALL( dV.up(V, tot) ); HS_CALL( dD.up(Dext, (long long) q * m1) ); HS_CALL( dl.up(vlp, q) );
+   HS_CALL( di.up(vin, m1 - 1) );
+   hs_as_args B;
+   memset(&B, 0, sizeof(B));
+   B.nblk = nblk;
+   long long off = 0;
+   for (int k = 0; k < nblk; ++k)
+   {
+      B.n2[k] = n2[k]; B.A[k] = dA.p + off * m1; B.V[k] = dV.p + off;
+      off += n2[k];
+   }
+   RecScope sc(recorded);
+   int rc = hs_apply_A_small(0, m1, &B, q, dD.p, dl.p, dO.p, epi, scal, di.p, dvo.p);
+   HS_CALL( sc.close(rc, pending) );
+   HS_CALL( dO.down(out, m1) );
+   return dvo.down(vout, m1 - 1);
+}
+
+/* the element-wise kernels of the small path in one call, each one line of arithmetic: in[6][n] = x, z, r, elp, a, b; par = sigmu, eta,
+ * alpha, s0, s1.  hs_lp_dir: o_lp = sigmu / z - x - (eta x r + elp) / z (use_elp = 0: without elp); hs_vec_mul: o_mul = a .* b;
+ * hs_make_ext: o_ext[n + 1] = [s0; s1 a]; hs_axpy3: ys += alpha xs on three vectors of nn[0], nn[1], nn[2] entries (>= 0), one behind
+ * the other in xs and ys (ys read and written) */
+extern "C" int hipsdp_small_elementwise_unit(int device, int n, const int* nn, const double* par, int use_elp, const double* in,
+   const double* xs, int recorded, double* o_lp, double* o_mul, double* o_ext, double* ys, int* pending)
+{
+   if ( n < 1 || nn == NULL || nn[0] < 0 || nn[1] < 0 || nn[2] < 0 || par == NULL || !flag01(use_elp) || in == NULL || xs == NULL
+         || !flag01(recorded) || o_lp == NULL || o_mul == NULL || o_ext == NULL || ys == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long n3 = (long long) nn[0] + nn[1] + nn[2];
+   DevBuf dI, dX, dY, dL, dM, dE;
+   HS_CALL( dI.alloc(6LL * n) ); HS_CALL( dX.alloc(n3) ); HS_CALL( dY.alloc(n3) ); HS_CALL( dL.alloc(n) ); HS_CALL( dM.alloc(n) );
+   HS_CALL( dE.alloc(n + 1) );
+   HS_CALL( nan_fill(dL, n) ); HS_CALL( nan_fill(dM, n) ); HS_CALL( nan_fill(dE, n + 1) );
+   HS_CALL( dI.up(in, 6LL * n) ); HS_CALL( dX.up(xs, n3) ); HS_CALL( dY.up(ys, n3) );
+   const double* x = dI.p; const double* z = dI.p + n; const double* r = dI.p + 2LL * n; const double* elp = dI.p + 3LL * n;
+   const double* a = dI.p + 4LL * n; const double* b = dI.p + 5LL * n;
+   RecScope sc(recorded);
+   int rc = hs_lp_dir(0, n, par[0], par[1], x, z, r, use_elp ? elp : NULL, dL.p);
+   if ( rc == HS_OK ) rc = hs_vec_mul(0, n, a, b, dM.p);
+   if ( rc == HS_OK ) rc = hs_make_ext(0, n, par[3], par[4], a, dE.p);
+   if ( rc == HS_OK ) rc = hs_axpy3(0, par[2], nn[0], dX.p, dY.p, nn[1], dX.p + nn[0], dY.p + nn[0], nn[2], dX.p + nn[0] + nn[1],
+         dY.p + nn[0] + nn[1]);
+   HS_CALL( sc.close(rc, pending) );
+   HS_CALL( dL.down(o_lp, n) ); HS_CALL( dM.down(o_mul, n) ); HS_CALL( dE.down(o_ext, n + 1) );
+   return dY.down(ys, n3);
+}
+
+/* hs_gemv_t with a free row pitch: out[e] = sum_i coef[i] A[i lda + e] + sa add[e], A: R rows of lda >= E doubles (the last one E).
+ * add_mode 0: no additive term; 1: add[E], an array of its own; 2: the output itself, which starts as add[E] (as ipm.hip calls it:
+ * hs_gemv_t(..., 1.0, out, out)) */
+extern "C" int hipsdp_small_gemv_t_unit(int device, int R, long long E, long long lda, const double* A, const double* coef, double sa,
+   int add_mode, const double* add, int recorded, double* out, int* pending)
+{
+   if ( R < 1 || E < 1 || lda < E || A == NULL || coef == NULL || add_mode < 0 || add_mode > 2 || (add_mode > 0 && add == NULL)
+         || !flag01(recorded) || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long na = span(R, (int) E, lda);
+   DevBuf dA, dc, dadd, dO;
+   HS_CALL( dA.alloc(na) ); HS_CALL( dc.alloc(R) ); HS_CALL( dadd.alloc(E) ); HS_CALL( dO.alloc(E) );
+   HS_CALL( nan_fill(dO, E) );
+   HS_CALL( dA.up(A, na) ); HS_CALL( dc.up(coef, R) );
+   if ( add_mode == 1 ) HS_CALL( dadd.up(add, E) );
+   if ( add_mode == 2 ) HS_CALL( dO.up(add, E) );
+   RecScope sc(recorded);
+   int rc = hs_gemv_t(0, R, E, dA.p, lda, dc.p, sa, add_mode == 0 ? NULL : (add_mode == 1 ? dadd.p : dO.p), dO.p);
+   HS_CALL( sc.close(rc, pending) );
+   return dO.down(out, E);
+}
+
+/* `count` <= 8 reductions of one kind (0 hs_dot <a, b>, 1 hs_absmax max |a|, 2 hs_ratio_min min over b < 0 of -a / b, 3 hs_lp_s0
+ * sum (a / b) c^2), reduction j over len[j] >= 1 entries - the operands of the reductions one behind the other in a, b, c - into
+ * out[slot[j]] (slot[j] < nslots <= 32), accumulate[j] = 1: combined with what the slot holds.  Every slot is first set to preset[.] by
+ * hs_fill_scalar.  recorded = 1: fills and reductions inside ONE hs_red_batch_begin / hs_red_batch_end (the fills are records too:
+ * *pending counts them, and more than the batch holds are launched on the way); 0: no batch, every call a launch of its own */
+extern "C" int hipsdp_reductions_unit(int device, int kind, int count, const int* len, const int* slot, const int* accumulate,
+   const double* a, const double* b, const double* c, int nslots, const double* preset, int recorded, double* out, int* pending)
+{
+   if ( kind < 0 || kind > 3 || count < 1 || count > 8 || len == NULL || slot == NULL || accumulate == NULL || a == NULL || b == NULL
+         || c == NULL || nslots < 1 || nslots > 32 || preset == NULL || !flag01(recorded) || out == NULL )
+      return HIPSDP_ERR_ARG;
+   long long tot = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( len[j] < 1 || slot[j] < 0 || slot[j] >= nslots || !flag01(accumulate[j]) )
+         return HIPSDP_ERR_ARG;
+      tot += len[j];
+   }
+   HS_CALL( pick_device(device) );
+   DevBuf dA, dB, dC, dO, dW;
+   HS_CALL( dA.alloc(tot) ); HS_CALL( dB.alloc(tot) ); HS_CALL( dC.alloc(tot) ); HS_CALL( dO.alloc(nslots) );
+   HS_CALL( dW.alloc(HS_RED_WS_DOUBLES) );
+   HS_CALL( nan_fill(dO, nslots) ); HS_CALL( nan_fill(dW, HS_RED_WS_DOUBLES) );
+   HS_CALL( dA.up(a, tot) ); HS_CALL( dB.up(b, tot) ); HS_CALL( dC.up(c, tot) );
+   hs_red_batch_reset();
+   if ( recorded )
+      hs_red_batch_begin(0);
+   int rc = HS_OK;
+   for (int k = 0; k < nslots && rc == HS_OK; ++k)
+      rc = hs_fill_scalar(0, dO.p + k, preset[k]);
+   long long off = 0;
+   for (int j = 0; j < count && rc == HS_OK; ++j)
+   {
+      double* o = dO.p + slot[j];
+      switch ( kind )
+      {
+      case 0:  rc = hs_dot(0, len[j], dA.p + off, dB.p + off, o, accumulate[j], dW.p); break;
+      case 1:  rc = hs_absmax(0, len[j], dA.p + off, o, accumulate[j], dW.p); break;
+      case 2:  rc = hs_ratio_min(0, len[j], dA.p + off, dB.p + off, o, accumulate[j], dW.p); break;
+      default: rc = hs_lp_s0(0, len[j], dA.p + off, dB.p + off, dC.p + off, o, accumulate[j], dW.p); break;
+      }
+      off += len[j];
+   }
+   if ( pending != NULL ) *pending = hs_red_batch_pending();
+   if ( recorded && rc == HS_OK ) rc = hs_red_batch_end();
+   if ( hipDeviceSynchronize() != hipSuccess && rc == HS_OK ) rc = HS_ERR_HIP;
+   hs_red_batch_reset();
+   HS_CALL( rc );
+   return dO.down(out, nslots);
+}
+
+/* the two small solves with the factor of M, m <= 64.  M (m x m, symmetric positive definite) is factored on the device as the engine
+ * does it (hs_potrf_psd with diag0 = diag(M) and a mask: L and inv(L) as 64 x 64); *fail: the factorization flag.
+ * form 0: hs_red_batch_solve inside a batch on nrhs right-hand sides, ld >= m apart: rhs[nrhs x ld] in place (entries m .. ld - 1 of a
+ *         row are not touched); *pending: records before the batch's end.  u2, wt are not used.
+ * form 1: k_solve2_small through hs_solve2_small: rhs[2 m] comes in as [g ; b] (g travels as row 0 of an Mx: Mx[0][1 + i] = g[i]) and
+ *         goes out as the two solutions; u2[m], wt[m + 1].  nrhs, ld are not used, *pending = 0.
+ * The switch HIPSDP_SMALL_SOLVE is read by the call, as the engine reads it */
+extern "C" int hipsdp_small_solve_unit(int device, int m, const double* M, int form, int nrhs, long long ld, double* rhs, double* u2,
+   double* wt, int* pending, int* fail)
+{
+   if ( m < 1 || m > 64 || M == NULL || !flag01(form) || rhs == NULL || (form == 0 && (nrhs < 1 || nrhs > 8 || ld < m))
+         || (form == 1 && (u2 == NULL || wt == NULL)) )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long m2 = (long long) m * m;
+   const long long nr = form == 0 ? nrhs * ld : 2LL * m;
+   DevBuf dL, dD, dG, dR, dMx, db, dU, dW;
+   int* dint = NULL;
+   HS_CALL( dL.alloc(m2) ); HS_CALL( dD.alloc(hs_potrf_dinv_len(m)) ); HS_CALL( dG.alloc(m) ); HS_CALL( dR.alloc(nr) );
+   HS_CALL( dMx.alloc(m + 1) ); HS_CALL( db.alloc(m) ); HS_CALL( dU.alloc(m) ); HS_CALL( dW.alloc(m + 1) );
+   HS_CALL( nan_fill(dU, m) ); HS_CALL( nan_fill(dW, m + 1) );
+   std::vector<double> dg(m), mx0(m + 1, 0.0);
+   for (int i = 0; i < m; ++i) dg[i] = M[(long long) i * m + i];
+   HS_CALL( dL.up(M, m2) ); HS_CALL( dG.up(dg.data(), m) );
+   if ( form == 0 )
+      HS_CALL( dR.up(rhs, nr) );
+   else
+   {
+      for (int i = 0; i < m; ++i) mx0[1 + i] = rhs[i];
+      HS_CALL( dMx.up(mx0.data(), m + 1) ); HS_CALL( db.up(rhs + m, m) ); HS_CALL( nan_fill(dR, nr) );
+   }
+   HS_HIP( hipMemset(dD.p, 0, (size_t) hs_potrf_dinv_len(m) * sizeof(double)) );
+   HS_HIP( hipMalloc((void**) &dint, (size_t) (m + 1) * sizeof(int)) );
+   int rc = hipMemset(dint, 0, (size_t) (m + 1) * sizeof(int)) == hipSuccess ? HS_OK : HS_ERR_HIP;
+   int pend = 0;
+   hs_red_batch_reset();
+   if ( rc == HS_OK ) rc = hs_potrf_psd(0, m, dL.p, dD.p, dint, dG.p, dint + 1, 0);
+   if ( rc == HS_OK && form == 0 )
+   {
+      hs_red_batch_begin(0);
+      if ( hs_red_batch_solve(0, m, dD.p, dL.p, nrhs, dR.p, ld) != 1 ) rc = HS_ERR_ARG;
+      pend = hs_red_batch_pending();
+      if ( rc == HS_OK ) rc = hs_red_batch_end();
+   }
+   else if ( rc == HS_OK )
+      rc = hs_solve2_small(0, m, dMx.p, db.p, dD.p, dL.p, dR.p, dU.p, dW.p, hs_small_solve_by_substitution());
+   if ( hipDeviceSynchronize() != hipSuccess && rc == HS_OK ) rc = HS_ERR_HIP;
+   hs_red_batch_reset();
+   int hflag = 0;
+   if ( rc == HS_OK && hipMemcpy(&hflag, dint, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ) rc = HS_ERR_HIP;
+   (void) hipFree(dint);
+   HS_CALL( rc );
+   if ( pending != NULL ) *pending = pend;
+   if ( fail != NULL ) *fail = hflag;
+   HS_CALL( dR.down(rhs, nr) );
+   if ( form == 1 )
+   {
+      HS_CALL( dU.down(u2, m) ); HS_CALL( dW.down(wt, m + 1) );
+   }
+   return HIPSDP_OK;
+}
+
+/* three linear combinations of the rows of A (R rows of lda >= E doubles): out[v][e] = sum_i c[v][i] A[i lda + e], c[3][R], out[3][E].
+ * fused = 1: hs_gemv_t3, and when it does not take the shape (odd E or lda) the three hs_gemv_t calls the engine then makes;
+ * fused = 0: three hs_gemv_t calls.  *took = 1 when the fused kernel ran */
+extern "C" int hipsdp_gemv_t3_unit(int device, int R, long long E, long long lda, const double* A, const double* c, int fused, double* out,
+   int* took)
+{
+   if ( R < 1 || E < 1 || lda < E || A == NULL || c == NULL || !flag01(fused) || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long na = span(R, (int) E, lda), Ep = E + (E & 1);
+   DevBuf dA, dc, dO;
+   HS_CALL( dA.alloc(na) ); HS_CALL( dc.alloc(3LL * R) ); HS_CALL( dO.alloc(3 * Ep) );
+   HS_CALL( nan_fill(dO, 3 * Ep) );
+   HS_CALL( dA.up(A, na) ); HS_CALL( dc.up(c, 3LL * R) );
+   hs_red_batch_reset();
+   int t = 0, rc = HS_OK;
+   if ( fused )
+   {
+      t = hs_gemv_t3(0, R, E, dA.p, lda, dc.p, dc.p + R, dc.p + 2LL * R, dO.p, dO.p + Ep, dO.p + 2 * Ep);
+      if ( t < 0 ) { rc = -t; t = 0; }
+   }
+   if ( t == 0 )
+      for (int v = 0; v < 3 && rc == HS_OK; ++v)
+         rc = hs_gemv_t(0, R, E, dA.p, lda, dc.p + (long long) v * R, 0.0, NULL, dO.p + v * Ep);
+   if ( hipDeviceSynchronize() != hipSuccess && rc == HS_OK ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   if ( took != NULL ) *took = t;
+   for (int v = 0; v < 3; ++v)
+      HS_HIP( hipMemcpy(out + v * E, dO.p + v * Ep, (size_t) E * sizeof(double), hipMemcpyDeviceToHost) );
+   return HIPSDP_OK;
+}
+
+/* hs_gemv_n (the pass A): out[v][i] = sum_e A[i lda + e] V[v][e], i < R, v < nv <= 4; A: R rows of lda >= E doubles, V[nv][E].  The
+ * device copies of the vectors start voff >= 0 doubles behind a 16-byte aligned address (an odd voff takes the two-at-a-time loads
+ * away); wsdoubles >= 0: the workspace the call is given for the split form.  info[0] = slices a row is cut into (the launcher's rule,
+ * recomputed here from the same inputs; 1: one workgroup per row), info[1] = 1 when the launcher takes the two-at-a-time kernel */
+extern "C" int hipsdp_pass_a_unit(int device, int R, long long E, long long lda, const double* A, int nv, const double* V, int voff,
+   long long wsdoubles, double* out, int* info)
+{
+   if ( R < 1 || E < 1 || lda < E || A == NULL || nv < 1 || nv > 4 || V == NULL || voff < 0 || voff > 64 || wsdoubles < 0 || out == NULL )
+      return HIPSDP_ERR_ARG;
+   HS_CALL( pick_device(device) );
+   const long long na = span(R, (int) E, lda), Ep = E + (E & 1);
+   DevBuf dA, dV, dO, dW;
+   HS_CALL( dA.alloc(na) ); HS_CALL( dV.alloc(nv * Ep + voff) ); HS_CALL( dO.alloc((long long) nv * R) ); HS_CALL( dW.alloc(wsdoubles) );
+   HS_CALL( nan_fill(dO, (long long) nv * R) ); HS_CALL( nan_fill(dW, wsdoubles) );
+   HS_CALL( dA.up(A, na) );
+   const double* vp[4];
+   for (int v = 0; v < nv; ++v)
+   {
+      HS_HIP( hipMemcpy(dV.p + voff + v * Ep, V + v * E, (size_t) E * sizeof(double), hipMemcpyHostToDevice) );
+      vp[v] = dV.p + voff + v * Ep;
+   }
+   if ( info != NULL )
+   {
+      /* gemv_n_launch of kernels.hip */
+      const bool vec = (lda & 1) == 0 && (voff & 1) == 0;
+      long long nsplit = 1;
+      if ( R < 512 && E >= 16384 )
+      {
+         nsplit = (1024 + R - 1) / R;
+         if ( nsplit > E / 8192 ) nsplit = E / 8192;
+         if ( nsplit < 1 ) nsplit = 1;
+         if ( nsplit * nv * R > wsdoubles ) nsplit = 1;
+      }
+      info[0] = (int) nsplit; info[1] = vec ? 1 : 0;
+   }
+   hs_red_batch_reset();
+   int rc = hs_gemv_n(0, R, E, dA.p, lda, nv, vp, dO.p, R, dW.p, wsdoubles);
+   if ( hipDeviceSynchronize() != hipSuccess && rc == HS_OK ) rc = HS_ERR_HIP;
+   HS_CALL( rc );
+   return dO.down(out, (long long) nv * R);
+}

@@ -38,10 +38,11 @@ print("RESULT " + json.dumps(out))
 COUNT = 60
 
 
-def run(batch):
+def run(batch, count=COUNT, extra=None):
     env = dict(os.environ)
     env["HIPSDP_BATCH"] = batch
-    r = subprocess.run([sys.executable, "-c", WORKER, ROOT, str(COUNT)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    env.update(extra or {})
+    r = subprocess.run([sys.executable, "-c", WORKER, ROOT, str(count)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
     return json.loads(line[len("RESULT "):])
@@ -51,6 +52,19 @@ def run(batch):
 def test_recorded_regions_do_not_change_a_single_bit(gpu):
     off = run("0")
     on = run("1")
+    assert len(off) == len(on) == COUNT
+    assert sum(1 for a in off if a["status"] == 0) >= COUNT // 3          # the family is not all failures
+    for k, (a, b) in enumerate(zip(off, on)):
+        assert a == b, "seed %d differs: %s / %s" % (k, {x: a[x] for x in ("status", "iterations", "dobj")},
+                                                     {x: b[x] for x in ("status", "iterations", "dobj")})
+
+
+@pytest.mark.gpu
+def test_recorded_regions_do_not_change_a_single_bit_without_the_one_launch_kernel(gpu):
+    """HIPSDP_SOLVE1=0 in both processes: the one-launch kernel takes no problem, so every small problem of the family goes through the
+    recorded regions, the m <= 64 solves (RB_SOLVE, k_solve2_small) included"""
+    off = run("0", extra={"HIPSDP_SOLVE1": "0"})
+    on = run("1", extra={"HIPSDP_SOLVE1": "0"})
     assert len(off) == len(on) == COUNT
     assert sum(1 for a in off if a["status"] == 0) >= COUNT // 3          # the family is not all failures
     for k, (a, b) in enumerate(zip(off, on)):
