@@ -31,6 +31,14 @@ HIPSDP_API int  hipsdp_gram_selfcheck(int device, int M, long long K, int reps, 
  * TWO runs of the default dispatch (must be 0) */
 HIPSDP_API int  hipsdp_dgemm_selfcheck3(int device, int M, int N, int K, int layB, int batch, int splitk, int flags, double alpha, double beta,
    int reps, int* used, long long* ndiff, double* maxdiff, long long* nrepro, double* ms_tile, double* ms_fast);
+/* one product with a triangular operand (flags: HS_GEMM_A_LOWTRI / HS_GEMM_B_LOWTRI) from the caller's operands with the instance of
+ * the paired-band kernel forced (mode 0: 128 x 128, 1: 256 in the streamed dimension, -1: default dispatch).  A [M][K], B [batch][K][N]
+ * (layB = 1) or [batch][N][K] (0), C [batch][crows][ldc] in and out (crows >= M, ldc >= N); used[2]: products taken by the paired-band
+ * kernel, of these by its wide instance */
+HIPSDP_API int  hipsdp_tri_product_unit(int device, int mode, int M, int N, int K, int layB, int batch, int flags, const double* A,
+   const double* B, double* Cio, int crows, int ldc, int* used);
+/* the same choice for products reached through other entries (hipsdp_schur_form_unit); returns the wide instance's products so far */
+HIPSDP_API int  hipsdp_tri_instance_force(int mode);
 /* first assembly of a cold solve: Mx += <A_i, A_j> on the lower tiles, from the packed lower triangles (full_storage = 0) or from the
  * full rows (1); *flops: FP64 matrix-core flops executed by the call */
 HIPSDP_API int  hipsdp_schur_identity_unit(int device, int m1, int n, const double* A, double ws_gbytes, int full_storage, double* Mx,

@@ -993,6 +993,28 @@ def dgemm_selfcheck3(M, N, K, layB=1, batch=1, splitk=1, flags=0, alpha=1.0, bet
     return used.value, nd.value, md.value, nr.value, t0.value, t1.value
 
 
+def tri_product_unit(A, B, flags, mode, layB=1, sentinel=None, pad_rows=0, pad_cols=0, device=0):
+    """one product with a triangular operand from the caller's operands, the paired-band kernel's instance forced (mode 0: 128 x 128,
+    1: wide, -1: default dispatch): A (M x K), B (batch x K x N for layB = 1, batch x N x K for 0) -> (C as (batch, M + pad_rows,
+    N + pad_cols) that started as `sentinel` everywhere, (products of the paired-band kernel, of these the wide instance's))"""
+    A = _f64(A); B = _f64(B)
+    M, K = A.shape
+    batch = B.shape[0]
+    N = B.shape[2] if layB == 1 else B.shape[1]
+    assert B.shape == ((batch, K, N) if layB == 1 else (batch, N, K))
+    Cio = np.full((batch, M + pad_rows, N + pad_cols), np.nan if sentinel is None else sentinel)
+    used = (C.c_int * 2)(0, 0)
+    _chk(ulib().hipsdp_tri_product_unit(device, mode, M, N, K, layB, batch, flags, _dp(A), _dp(B), _dp(Cio), M + pad_rows, N + pad_cols, used),
+         "hipsdp_tri_product_unit")
+    return Cio, tuple(used)
+
+
+def tri_instance_force(mode):
+    """forces the paired-band kernel's instance for products reached through other entries of the units library (0: 128 x 128, 1: wide,
+    -1: chosen per shape again) -> products the wide instance has taken so far"""
+    return ulib().hipsdp_tri_instance_force(mode)
+
+
 def gram_selfcheck(M, K, reps=0, device=0):
     """W W^T on the lower triangle through the K-sliced tile kernels and through the Gram kernel (csrc/gram.hip)
     -> (Gram kernel took it, max |difference| over the lower triangle, elements not reproduced by a second run, ms tile path, ms Gram kernel)"""

@@ -481,6 +481,18 @@ double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kch
       }
       return f;
    };
+   if ( persistent && BT == 128 && kstage == 8 && hs_dgemm2_tri5_wide(a) )
+   {
+      /* the wide instance of the paired-band kernel: whole tiles of 256 in the streamed dimension (rows for a triangular B, columns
+       * for a triangular A), each issued the matrix instructions of two 128 x 128 tiles over the K range of its 128-wide panel of
+       * the triangular operand */
+      const long long wl = triB ? (a->M + 2 * BT - 1) / (2 * BT) : (a->N + 2 * BT - 1) / (2 * BT);
+      const long long np = triB ? tn : tm;
+      double f = 0.0;
+      for (long long t = 0; t < np; ++t)
+         f += 2.0 * tile_flops(triB ? 0 : (int) t * BT, triB ? (int) t * BT : 0);
+      return f * (double) wl * (double) a->batch;
+   }
    double per_entry = 0.0;
    if ( a->flags & HS_GEMM_LOWER )
       per_entry = (double) (tm * (tm + 1) / 2) * tile_flops(0, 0);
@@ -559,6 +571,19 @@ int hs_dgemm(hipStream_t stream, const hs_gemm_args* a)
       return HS_ERR_ARG;
    if ( (a->flags & HS_GEMM_REMAP) && (a->flags & HS_GEMM_LOWER) && a->M != a->N )
       return HS_ERR_ARG;
+
+   /* a test forces an instance of the paired-band kernel (hs_dgemm2_wide_force): it then takes every product it can, whatever the size */
+   if ( hs_dgemm2_tri5_forced() && hs_dgemm2_tri5_eligible(a) && !(a->flags & HS_GEMM_TILE64) )
+   {
+      const int r5 = hs_dgemm2_try(stream, a, a->K);
+      if ( r5 < 0 )
+         return -r5;
+      if ( r5 == 1 )
+      {
+         hs_mfma_flops_add(hs_gemm_executed_flops(a, 128, 8, a->K, 1));
+         return HS_OK;
+      }
+   }
 
    /* few tiles, no split-K: the latency-oriented 32 x 32 kernel (dgemm3.hip) */
    if ( a->splitk <= 1 )

@@ -568,11 +568,17 @@ __global__ void __launch_bounds__(256, G2_WGPC) hs_dgemm2_kernel(hs_gemm_args p,
 #ifndef G5_DESC
 #define G5_DESC 1
 #endif
+#ifndef G5_WIDE_TRI
+#define G5_WIDE_TRI 3                       /* which product may take the wide instance: bit 0 A_stack R, bit 1 G T_j */
+#endif
+#ifndef G5_WIDE_MIN_ITEMS
+#define G5_WIDE_MIN_ITEMS 16                /* the wide instance from this many 256-wide items per workgroup (measured from 30 up) */
+#endif
 #ifndef G5_ABL
 #define G5_ABL 0                            /* developer ablations (wrong results): 1 no C stores, 2 no DMA, 4 no matrix instructions */
 #endif
 
-/* developer instrumentation (make EXTRA=-DG5_PROF, tests/devtools/tri5_prof.py): per wavefront the cycles spent waiting for the DMA
+/* developer instrumentation (make EXTRA=-DG5_PROF, tests/devtools/tri5_prof.py, tri5_prof_wide.py): per wavefront the cycles spent waiting for the DMA
  * counter, at the stage barriers, in the epilogues (drain + barrier + stores) and in total; s_memtime around the waits */
 #ifdef G5_PROF
 __device__ unsigned long long g5_prof[512 * 4 * 8];
@@ -597,7 +603,7 @@ struct g5_frag
  * 30 per workgroup).  Returns false past the end of the list. */
 template<int TRI>
 __device__ __forceinline__ bool g5_decode(const hs_gemm_args& p, long long idx, long long base, long long Tx, int tm, int tn,
-   long long ntile, int tailwant, int* om0, int* on0, int* obz)
+   long long ntile, int tailwant, int bm, int bn, int* om0, int* on0, int* obz)
 {
    const bool ok = idx < Tx;
    if ( !ok )
@@ -630,8 +636,8 @@ __device__ __forceinline__ bool g5_decode(const hs_gemm_args& p, long long idx, 
    const long long bz = pos / ntile;
    const int t = (int) (pos - bz * ntile);
    const int ti = t / tn, tj = t - ti * tn;
-   *om0 = ok ? ti * G2_BT : 0;
-   *on0 = ok ? tj * G2_BT : 0;
+   *om0 = ok ? ti * bm : 0;
+   *on0 = ok ? tj * bn : 0;
    *obz = ok ? (int) bz : 0;
    return ok;
 }
@@ -645,7 +651,7 @@ __device__ __forceinline__ bool g5_decode(const hs_gemm_args& p, long long idx, 
  * entries, taken by four workgroups within a few microseconds.  The last entries of the list by decreasing K length as above. */
 template<int TRI>
 __device__ __forceinline__ bool g5_decode_sets(long long idx, long long base, long long Tx, int tm, int tn, long long ntile, int tailwant,
-   int* om0, int* on0, int* obz)
+   int bm, int bn, int* om0, int* on0, int* obz)
 {
    const bool ok = idx < Tx;
    if ( !ok )
@@ -692,22 +698,36 @@ __device__ __forceinline__ bool g5_decode_sets(long long idx, long long base, lo
    const long long bz = pos / ntile;
    const int t = (int) (pos - bz * ntile);
    const int ti = t / tn, tj = t - ti * tn;
-   *om0 = ok ? ti * G2_BT : 0;
-   *on0 = ok ? tj * G2_BT : 0;
+   *om0 = ok ? ti * bm : 0;
+   *on0 = ok ? tj * bn : 0;
    *obz = ok ? (int) bz : 0;
    return ok;
 }
 
 #define G5_UNI(x) __builtin_amdgcn_readfirstlane(x)        /* wave-uniform by construction: keep it in a scalar register */
 
-template<int LB, int TRI>
-__global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long long ntile, long long total, unsigned int* __restrict__ ctr)
+/* WIDE = 1: the tile is twice as long in the dimension of the streamed operand (TRI = 1: 256 rows of A x 128 columns of R, TRI = 2:
+ * 128 rows of G x 256 columns of T_j) and belongs to one workgroup of EIGHT wavefronts: wavefronts 0 - 3 own the first 128 of the
+ * long dimension exactly as the four wavefronts of the 128 x 128 instance own their tile, wavefronts 4 - 7 the second 128.  A stage
+ * is (256 + 128) x 8 doubles, 24 KB (two 128 x 128 tiles: 32 KB for the same matrix instructions) in THREE requests per wavefront -
+ * two pieces of the long operand, one of the short - and the ring of four slots takes 96 KB: one workgroup per CU, two wavefronts
+ * per SIMD as before.  The stage image: [A: 16 pieces][B: 8 K rows] (TRI = 1), [A: 8 pieces][B first 128 columns][B second 128
+ * columns] (TRI = 2; B K-contiguous: 16 pieces), every 128-wide part laid out as in the 128 x 128 instance.  K range, stage order
+ * and band pairs depend on the 128-wide panel of the triangular operand alone, which is the same in both instances: every output
+ * element sees the same K positions in the same order, the two instances give the same bits. */
+template<int LB, int TRI, int WIDE>
+__global__ void __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) hs_dgemm5_kernel(hs_gemm_args p, long long ntile, long long total, unsigned int* __restrict__ ctr)
 {
    extern __shared__ __attribute__((aligned(1024))) double g2_smem[];
    __shared__ unsigned int g5_q[4];        /* list entries the workgroup has taken: entry of item g in slot g & 3 */
+   constexpr int BM = (WIDE && TRI == 1) ? 2 * G2_BT : G2_BT, BN = (WIDE && TRI == 2) ? 2 * G2_BT : G2_BT;
+   constexpr int BOFF = (WIDE && TRI == 1) ? 2 * G2_OPSZ : G2_OPSZ;       /* where B starts in a stage image */
+   constexpr int SLOT = WIDE ? 3 * G2_OPSZ : G2_SLOT;
+   constexpr int GPS = WIDE ? 3 : G2_GPS;                                  /* LDS-DMA requests per wavefront and stage */
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-   const int tm = (p.M + G2_BT - 1) / G2_BT, tn = (p.N + G2_BT - 1) / G2_BT;
+   const int half = WIDE ? wave >> 2 : 0, hw = WIDE ? wave & 3 : wave;     /* which 128 of the long dimension, and the wavefront's place in it */
+   const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
    constexpr int NI = TRI == 1 ? 2 : 8, NJ = TRI == 1 ? 8 : 2;
 
    const int xcd = blockIdx.x & 7;
@@ -739,11 +759,39 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
       int dm0 = 0, dn0 = 0, dbz = 0;
       /* (past the end of the list: item (0, 0, 0) with an empty K range - every request then reads the zero constant - and a stage
        * count that is never reached; no early return: the compiler then keeps the state behind it in scratch memory) */
-      nvalid = sets ? g5_decode_sets<TRI>(idx, base, Tx, tm, tn, ntile, tailwant, &dm0, &dn0, &dbz)
-         : g5_decode<TRI>(p, idx, base, Tx, tm, tn, ntile, tailwant, &dm0, &dn0, &dbz);
+      nvalid = sets ? g5_decode_sets<TRI>(idx, base, Tx, tm, tn, ntile, tailwant, BM, BN, &dm0, &dn0, &dbz)
+         : g5_decode<TRI>(p, idx, base, Tx, tm, tn, ntile, tailwant, BM, BN, &dm0, &dn0, &dbz);
       nm0 = G5_UNI(dm0); nn0 = G5_UNI(dn0); nbz = G5_UNI(dbz);
       const double* A = p.A + (long long) nbz * p.strideA;
       const double* B = p.B + (long long) nbz * p.strideB;
+      if ( WIDE )
+      {
+         /* three pieces per wavefront: two of the long operand (na / nb [0], [1]), one of the short ([0]) */
+#pragma unroll
+         for (int i = 0; i < 2; ++i)
+         {
+            if ( TRI == 1 || i == 0 )
+            {
+               int row = nm0 + (TRI == 1 ? wave * 2 + i : wave) * 16 + ar;
+               if ( row > p.M - 1 ) row = p.M - 1;
+               na[i] = A + (long long) row * p.lda + 2 * ac;
+            }
+            if ( TRI == 2 && LB == HS_KC )
+            {
+               int rowb = nn0 + (wave * 2 + i) * 16 + ar;
+               if ( rowb > p.N - 1 ) rowb = p.N - 1;
+               nb[i] = B + (long long) rowb * p.ldb + 2 * ac;
+            }
+            else if ( TRI == 2 || i == 0 )
+            {
+               /* K row `wave` of the stage; TRI = 2: its first and its second 128 columns */
+               int col = nn0 + G2_BT * i + 2 * (lane ^ ((wave & 1) << 3));
+               if ( col > p.N - 2 ) col = p.N - 2;
+               nb[i] = B + (long long) wave * p.ldb + col;
+            }
+         }
+      }
+      if ( !WIDE )
 #pragma unroll
       for (int i = 0; i < 2; ++i)
       {
@@ -791,7 +839,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
    int rq_K0 = 0;
    auto stage_begin = [&](int slotidx) __attribute__((always_inline))
    {
-      rq_slot = g2_smem + slotidx * G2_SLOT;
+      rq_slot = g2_smem + slotidx * SLOT;
       /* both kinds: the full stages first, then the band.  TRI = 1 walks its full stages from the END of the K range down to the
        * band: the column tiles of a row panel, taken by four workgroups of the XCD within a few microseconds of each other, then
        * read the same columns of A at the same time (G5_DESC=0: ascending from the band's end) */
@@ -804,6 +852,33 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
    };
    auto stage_piece = [&](int k) __attribute__((always_inline))
    {
+      if ( WIDE )
+      {
+         /* request k = 0 .. 2 of the wavefront: A first (TRI = 1: pieces 2 wave, 2 wave + 1; TRI = 2: piece wave), then B (TRI = 1: K row
+          * wave; TRI = 2: K row wave of both column halves, or the pieces 2 wave, 2 wave + 1 of a K-contiguous B) */
+         const bool isA = k < (TRI == 1 ? 2 : 1);
+         const int i = TRI == 1 ? (k & 1) : (k == 0 ? 0 : k - 1);
+         const double* src;
+         int dst;
+         if ( isA )
+         {
+            src = (rq_K0 + 2 * ac < pkend) ? pa[i] + rq_K0 : hs_g2_zero;
+            dst = (TRI == 1 ? wave * 2 + i : wave) * 128;
+         }
+         else if ( LB == HS_KC )
+         {
+            src = (rq_K0 + 2 * ac < pkend) ? pb[i] + rq_K0 : hs_g2_zero;
+            dst = BOFF + (wave * 2 + i) * 128;
+         }
+         else
+         {
+            src = (rq_K0 + wave + vzero < pkend) ? pb[i] + (long long) rq_K0 * p.ldb : hs_g2_zero;
+            dst = BOFF + i * G2_OPSZ + wave * 128;
+         }
+         if ( !(G5_ABL & 2) )
+            __builtin_amdgcn_global_load_lds((hs_gbl_ptr) src, (hs_lds_ptr) (rq_slot + dst), 16, 0, 0);
+         return;
+      }
       const int i = k & 1;
       const int piece = wave * 2 + i;
       const double* src;
@@ -837,7 +912,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
    {
       stage_begin(slotidx);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
+      for (int k = 0; k < GPS; ++k)
          stage_piece(k);
       stage_end();
    };
@@ -876,7 +951,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
 #pragma unroll
          for (int c = 0; c < 8; ++c)
             if ( c >= t0 && c <= t1 )
-               f.t[c] = g2_frag<LB>(slot + G2_OPSZ, 0, c, ks, lane);
+               f.t[c] = g2_frag<LB>(slot + BOFF, 0, c, ks, lane);
       }
       else
       {
@@ -886,7 +961,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
                f.t[r] = g2_frag<HS_KC>(slot, 0, r, ks, lane);
 #pragma unroll
          for (int j = 0; j < 2; ++j)
-            f.o[j] = g2_frag<LB>(slot + G2_OPSZ, 0, 2 * wave + j, ks, lane);
+            f.o[j] = g2_frag<LB>(slot + BOFF + half * G2_OPSZ, 0, 2 * hw + j, ks, lane);
       }
    };
    /* tell the compiler the fragments have landed (see landed_frags of the kernel above) */
@@ -945,7 +1020,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
        * as many operations outstanding as loads were issued behind L" still proves that L has landed; stores that are still on
        * their way only make such a wait longer. */
       if ( gc + 1 >= landed )
-         g2_wait_vm<2 * G2_GPS>();
+         g2_wait_vm<2 * GPS>();
       landed = gc + 2 > landed ? gc + 2 : landed;
       __builtin_amdgcn_s_barrier();
       double* C = p.C + (long long) cbz * p.strideC;
@@ -956,7 +1031,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
       if ( (G5_ABL & 1) && acc[0][0][0] != 1.2345e301 )
       {
       }
-      else if ( cm0 + G2_BT <= p.M && cn0 + G2_BT <= p.N && beta == 0.0 )
+      else if ( cm0 + BM <= p.M && cn0 + BN <= p.N && beta == 0.0 )
       {
          /* interior tile, nothing to add to: one address per row of four-row groups, the columns as immediate offsets */
          double* c0 = C + (long long) row0 * ldc + col0;
@@ -1040,13 +1115,13 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
       if ( nf <= 0 )
          return;
       g5_frag f0, f1;
-      read_frags(f0, g2_smem + (gc & 3) * G2_SLOT, 0, 0, 7);
+      read_frags(f0, g2_smem + (gc & 3) * SLOT, 0, 0, 7);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       frags_landed(f0, 0, 7);
       for (int s = 0; s < nf; ++s)
       {
-         const double* sa = g2_smem + (gc & 3) * G2_SLOT;
-         const double* sn = g2_smem + ((gc + 1) & 3) * G2_SLOT;
+         const double* sa = g2_smem + (gc & 3) * SLOT;
+         const double* sn = g2_smem + ((gc + 1) & 3) * SLOT;
          /* first half: K step 0, the fragments of K step 1 between its matrix instructions */
          __builtin_amdgcn_sched_barrier(0);
          read_frags(f1, sa, 1, 0, 7);
@@ -1067,10 +1142,10 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
          if ( s + 1 < nf )
          {
             if ( gc + 1 >= landed )
-               g2_wait_vm<2 * G2_GPS>();
+               g2_wait_vm<2 * GPS>();
          }
          else if ( gc + 2 >= landed )
-            g2_wait_vm<1 * G2_GPS>();
+            g2_wait_vm<1 * GPS>();
          G5_T(tb);
          __builtin_amdgcn_s_barrier();
          G5_T(tc);
@@ -1084,7 +1159,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
          mfma_one(f1, 0, 7, false, 0);
          mfma_one(f1, 0, 7, false, 1);
 #pragma unroll
-         for (int k = 0; k < 4; ++k)
+         for (int k = 0; k < GPS; ++k)
          {
             __builtin_amdgcn_sched_barrier(0);
             stage_piece(k);
@@ -1094,7 +1169,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
          stage_end();
          read_frags(f0, sn, 0, 0, 7);
 #pragma unroll
-         for (int k = 6; k < 16; ++k)
+         for (int k = 2 + GPS; k < 16; ++k)
             mfma_one(f1, 0, 7, false, k);
 #pragma unroll
          for (int q = 0; q < 10; ++q)
@@ -1102,6 +1177,8 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
          }
+         if ( WIDE )
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
          __builtin_amdgcn_sched_barrier(0);
          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
          frags_landed(f0, 0, 7);
@@ -1117,8 +1194,8 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
       g5_frag l0, h0, l1, h1;
       unsigned int taken = 0;
       {
-         const double* slo = g2_smem + (gc & 3) * G2_SLOT;
-         const double* shi = g2_smem + ((gc + 1) & 3) * G2_SLOT;
+         const double* slo = g2_smem + (gc & 3) * SLOT;
+         const double* shi = g2_smem + ((gc + 1) & 3) * SLOT;
          read_frags(l0, slo, 0, 0, TRI == 1 ? 0 : 7);
          read_frags(h0, shi, 0, TRI == 1 ? 0 : 7, 7);
          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1133,10 +1210,10 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
          const int ht0 = TRI == 1 ? 0 : 7 - q, ht1 = TRI == 1 ? 7 - q : 7;         /* slabs of stage 15 - d */
          const int nlt0 = TRI == 1 ? 0 : qn, nlt1 = TRI == 1 ? qn : 7;
          const int nht0 = TRI == 1 ? 0 : 7 - qn, nht1 = TRI == 1 ? 7 - qn : 7;
-         const double* slo = g2_smem + (gc & 3) * G2_SLOT;
-         const double* shi = g2_smem + ((gc + 1) & 3) * G2_SLOT;
-         const double* nlo = g2_smem + ((gc + 2) & 3) * G2_SLOT;
-         const double* nhi = g2_smem + ((gc + 3) & 3) * G2_SLOT;
+         const double* slo = g2_smem + (gc & 3) * SLOT;
+         const double* shi = g2_smem + ((gc + 1) & 3) * SLOT;
+         const double* nlo = g2_smem + ((gc + 2) & 3) * SLOT;
+         const double* nhi = g2_smem + ((gc + 3) & 3) * SLOT;
          /* first half: K step 0 of both stages (18 matrix instructions), the 13 fragments of K step 1 between them */
          __builtin_amdgcn_sched_barrier(0);
          read_frags(l1, slo, 1, lt0, lt1);
@@ -1173,7 +1250,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
                g2_wait_vm<0>();
          }
          else if ( gc + 2 >= landed )
-            g2_wait_vm<1 * G2_GPS>();
+            g2_wait_vm<1 * GPS>();
          G5_T(tb);
          __builtin_amdgcn_s_barrier();
          G5_T(tc);
@@ -1194,7 +1271,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
             bm(0);
             bm(1);
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < GPS; ++k)
             {
                __builtin_amdgcn_sched_barrier(0);
                stage_piece(k);
@@ -1204,11 +1281,11 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
             stage_end();
             stage_begin((gc + 1) & 3);
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < GPS; ++k)
             {
                __builtin_amdgcn_sched_barrier(0);
                stage_piece(k);
-               bm(6 + k);
+               bm(2 + GPS + k);
             }
             __builtin_amdgcn_sched_barrier(0);
             stage_end();
@@ -1228,7 +1305,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
                read_frags(h0, nhi, 0, nht0, nht1);
             }
 #pragma unroll
-            for (int k = 10; k < 18; ++k)
+            for (int k = 2 + 2 * GPS; k < 18; ++k)
                bm(k);
             if ( d < 7 )
             {
@@ -1238,7 +1315,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
                   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                   __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                }
-               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+               __builtin_amdgcn_sched_group_barrier(0x008, WIDE ? 3 : 1, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
          }
@@ -1290,7 +1367,7 @@ __global__ void __launch_bounds__(256, 2) hs_dgemm5_kernel(hs_gemm_args p, long 
 #ifdef G5_PROF
    if ( lane == 0 )
    {
-      unsigned long long* o = g5_prof + ((long long) blockIdx.x * 4 + wave) * 8;
+      unsigned long long* o = g5_prof + ((long long) blockIdx.x * (WIDE ? 8 : 4) + wave) * 8;
       for (int i = 0; i < 7; ++i)
          o[i] = prof_acc[i];
       o[7] = __builtin_readcyclecounter() - prof_t0;
@@ -1309,6 +1386,8 @@ extern "C" __attribute__((visibility("default"))) int hs_dgemm5_prof_read(unsign
 static int g2_disabled = 0;
 static int g2_taken = 0;
 static int g5_taken = 0;
+static int g5_wide_mode = -1;
+static int g5_wide_taken = 0;
 
 /* test hook: on = 0 forces dgemm.hip for every product, on = 1 restores the default; returns how many products the
  * persistent kernel has taken so far */
@@ -1322,6 +1401,22 @@ int hs_dgemm2_enable(int on)
 int hs_dgemm2_paired_taken(void)
 {
    return __atomic_load_n(&g5_taken, __ATOMIC_RELAXED);
+}
+
+/* test hook: which instance of the paired-band kernel takes the products it is eligible for.  mode -1: chosen per shape
+ * (hs_dgemm2_tri5_wide), 0: the 128 x 128 instance, 1: the wide instance (256 in the streamed dimension, eight wavefronts); forced
+ * (0, 1), the kernel also takes products below the size from which the persistent kernels are used.  Any other mode changes
+ * nothing.  Returns how many products the wide instance has taken so far. */
+int hs_dgemm2_wide_force(int mode)
+{
+   if ( mode >= -1 && mode <= 1 )
+      g5_wide_mode = mode;
+   return __atomic_load_n(&g5_wide_taken, __ATOMIC_RELAXED);
+}
+
+int hs_dgemm2_tri5_forced(void)
+{
+   return g5_wide_mode >= 0;
 }
 
 /* 16 counters per (device, stream): launches on one stream are ordered, so they can share them (cleared before each launch);
@@ -1353,6 +1448,27 @@ int hs_dgemm2_tri5_eligible(const hs_gemm_args* a)
       && !(triB && a->layB != HS_MC);
 }
 
+/* of those, the ones the wide instance takes (unless a test forces either instance).  Measured per product, both instances in turn
+ * on one device (profiles/r16_wide_products.txt): at n = 500 and 1000 (4 and 8 panels of the triangular operand) the wide instance
+ * is 0 - 3 % faster, at n = 250 (A_stack R: + 8 %) and n = 300 (G T_j: + 30 %, its 300 columns are padded to 512 instead of 384) it
+ * is slower.  So: at least four panels, no more padded columns than the 128-wide tiles have, and a list long enough that one
+ * workgroup per CU with items of twice the work still ends evenly. */
+int hs_dgemm2_tri5_wide(const hs_gemm_args* a)
+{
+   if ( !hs_dgemm2_tri5_eligible(a) )
+      return 0;
+   if ( g5_wide_mode >= 0 )
+      return g5_wide_mode;
+   const bool triB = (a->flags & HS_GEMM_B_LOWTRI) != 0;
+   if ( !((G5_WIDE_TRI >> (triB ? 0 : 1)) & 1) )
+      return 0;
+   const long long panels = triB ? (a->N + G2_BT - 1) / G2_BT : (a->M + G2_BT - 1) / G2_BT;
+   const long long wtiles = triB ? (a->M + 2 * G2_BT - 1) / (2 * G2_BT) : (long long) ((a->N + 2 * G2_BT - 1) / (2 * G2_BT)) * a->batch;
+   if ( !triB && 2 * ((a->N + 2 * G2_BT - 1) / (2 * G2_BT)) != (a->N + G2_BT - 1) / G2_BT )
+      return 0;
+   return panels >= 4 && panels * wtiles >= 256LL * G5_WIDE_MIN_ITEMS;
+}
+
 int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
 {
    if ( g2_disabled )
@@ -1373,7 +1489,7 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
    const long long ntile = (a->flags & HS_GEMM_LOWER) ? tm * (tm + 1) / 2 : tm * tn;
    const long long nz = a->splitk > 1 ? a->splitk : a->batch;
    const long long total = ntile * nz;
-   if ( total < 384 )
+   if ( total < 384 && !(g5_wide_mode >= 0 && hs_dgemm2_tri5_eligible(a)) )
       return 0;
    int grid = 256 * G2_WGPC;           /* G2_WGPC workgroups per CU, 32 G2_WGPC per XCD */
    const int Wx = grid / 8;
@@ -1392,16 +1508,21 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
    const bool triA = (a->flags & HS_GEMM_A_LOWTRI) != 0, triB = (a->flags & HS_GEMM_B_LOWTRI) != 0;
    if ( hs_dgemm2_tri5_eligible(a) )
    {
-      /* the paired-band kernel: one triangular operand, whole K range per item */
-      static hs_attr_mask attr5[3];
-      const int inst5 = triB ? 0 : (a->layB == HS_MC ? 1 : 2);
-      const size_t smem5 = (size_t) G5_NS * G2_SLOT * sizeof(double);
+      /* the paired-band kernel: one triangular operand, whole K range per item; its wide instance (256 in the streamed dimension,
+       * 512 threads, one workgroup per CU) where hs_dgemm2_tri5_wide says so */
+      static hs_attr_mask attr5[6];
+      const int wide = hs_dgemm2_tri5_wide(a);
+      const int inst5 = (triB ? 0 : (a->layB == HS_MC ? 1 : 2)) + 3 * wide;
+      const size_t smem5 = (size_t) G5_NS * (wide ? 3 * G2_OPSZ : G2_SLOT) * sizeof(double);
       const void* fn5 = NULL;
       switch ( inst5 )
       {
-      case 0: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 1>); break;
-      case 1: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 2>); break;
-      default: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_KC, 2>); break;
+      case 0: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 1, 0>); break;
+      case 1: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 2, 0>); break;
+      case 2: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_KC, 2, 0>); break;
+      case 3: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 1, 1>); break;
+      case 4: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_MC, 2, 1>); break;
+      default: fn5 = reinterpret_cast<const void*>(&hs_dgemm5_kernel<HS_KC, 2, 1>); break;
       }
       if ( hs_func_max_lds(fn5, (int) smem5, &attr5[inst5]) != HS_OK )
          return -HS_ERR_HIP;
@@ -1413,16 +1534,26 @@ int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* a, int kchunk)
        * non-temporally (kernel arguments rather than template constants: folded in, they cost the kernel up to 16 VGPRs) */
       hs_gemm_args a5 = *a;
       a5.flags |= G5_F_NT | G5_F_SETS | G5_F_PAIRS;
+      /* the lists are made of this instance's tiles */
+      const long long tm5 = triB && wide ? (a->M + 2 * G2_BT - 1) / (2 * G2_BT) : tm;
+      const long long tn5 = !triB && wide ? (a->N + 2 * G2_BT - 1) / (2 * G2_BT) : tn;
+      const long long ntile5 = tm5 * tn5, total5 = ntile5 * nz;
+      const int grid5 = wide ? 256 : grid;
       switch ( inst5 )
       {
-      case 0: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 1>), dim3(grid), dim3(256), smem5, stream, a5, ntile, total, ctr); break;
-      case 1: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 2>), dim3(grid), dim3(256), smem5, stream, a5, ntile, total, ctr); break;
-      default: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_KC, 2>), dim3(grid), dim3(256), smem5, stream, a5, ntile, total, ctr); break;
+      case 0: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 1, 0>), dim3(grid5), dim3(256), smem5, stream, a5, ntile5, total5, ctr); break;
+      case 1: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 2, 0>), dim3(grid5), dim3(256), smem5, stream, a5, ntile5, total5, ctr); break;
+      case 2: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_KC, 2, 0>), dim3(grid5), dim3(256), smem5, stream, a5, ntile5, total5, ctr); break;
+      case 3: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 1, 1>), dim3(grid5), dim3(512), smem5, stream, a5, ntile5, total5, ctr); break;
+      case 4: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_MC, 2, 1>), dim3(grid5), dim3(512), smem5, stream, a5, ntile5, total5, ctr); break;
+      default: hipLaunchKernelGGL((hs_dgemm5_kernel<HS_KC, 2, 1>), dim3(grid5), dim3(512), smem5, stream, a5, ntile5, total5, ctr); break;
       }
       if ( hipGetLastError() != hipSuccess )
          return -HS_ERR_HIP;
       (void) __atomic_add_fetch(&g2_taken, 1, __ATOMIC_RELAXED);
       (void) __atomic_add_fetch(&g5_taken, 1, __ATOMIC_RELAXED);
+      if ( wide )
+         (void) __atomic_add_fetch(&g5_wide_taken, 1, __ATOMIC_RELAXED);
       return 1;
    }
    const int il = triA != triB ? (triB ? 1 : 2) : 0;

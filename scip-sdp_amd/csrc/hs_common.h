@@ -107,6 +107,10 @@ int hs_dgemm(hipStream_t stream, const hs_gemm_args* args);
 int hs_dgemm2_try(hipStream_t stream, const hs_gemm_args* args, int kchunk);
 int hs_dgemm2_enable(int on);
 int hs_dgemm2_paired_taken(void);
+/* test hook: -1 the paired-band kernel's instance is chosen per shape, 0 / 1 forces its 128 x 128 / its wide instance; returns how many
+ * products the wide instance has taken */
+int hs_dgemm2_wide_force(int mode);
+int hs_dgemm2_tri5_forced(void);                    /* 1 while a test forces either instance */
 int hs_gram_taken(void);
 
 /* the Gram product of the Schur assembly (gram.hip): C (M x M, lower triangle) = alpha W W^T + beta C with W [M][K] K contiguous,
@@ -127,6 +131,7 @@ int hs_dgemm3_try(hipStream_t stream, const hs_gemm_args* args);
 double hs_mfma_flops_total(void);
 void   hs_mfma_flops_add(double flops);
 int hs_dgemm2_tri5_eligible(const hs_gemm_args* a);
+int hs_dgemm2_tri5_wide(const hs_gemm_args* a);     /* ... and its wide instance (256 in the streamed dimension) takes it */
 double hs_gemm_executed_flops(const hs_gemm_args* a, int BT, int kstage, int kchunk, int persistent);
 
 /* choose a split-K factor for a [M x N x K] product so that at least ~2 waves of workgroups exist */

@@ -251,6 +251,42 @@ extern "C" int hipsdp_dgemm_selfcheck3(int device, int M, int N, int K, int layB
    return dgemm_selfcheck_impl(device, M, N, K, layB, batch, splitk, flags, alpha, beta, reps, used, ndiff, ms_tile, ms_fast, maxdiff, nrepro);
 }
 
+/* One product with a triangular operand from the caller's operands through hs_dgemm, with the instance of the paired-band kernel
+ * (csrc/dgemm2.hip) forced: mode 0 its 128 x 128 instance, 1 its wide instance, -1 the default dispatch.  A [M][K] K contiguous
+ * (shared by the batch), B [batch][K][N] (layB = HS_MC) or [batch][N][K] (HS_KC), C [batch][crows][ldc] with crows >= M and ldc >= N:
+ * passed in and returned whole, so the caller sees what lies outside the M x N results.  alpha = 1, beta = 0.
+ * used[2]: products of the call the paired-band kernel took, and of these its wide instance. */
+extern "C" int hipsdp_tri_product_unit(int device, int mode, int M, int N, int K, int layB, int batch, int flags, const double* A,
+   const double* B, double* Cio, int crows, int ldc, int* used)
+{
+   HS_CALL( pick_device(device) );
+   if ( mode < -1 || mode > 1 || M < 1 || N < 1 || K < 1 || batch < 1 || (layB != HS_MC && layB != HS_KC) || A == NULL || B == NULL || Cio == NULL
+      || crows < M || ldc < N || used == NULL )
+      return HIPSDP_ERR_ARG;
+   const long long na = (long long) M * K, nb = (long long) N * K, nc = (long long) crows * ldc;
+   DevBuf dA, dB, dC;
+   HS_CALL( dA.alloc(na) ); HS_CALL( dB.alloc(nb * batch) ); HS_CALL( dC.alloc(nc * batch) );
+   HS_CALL( dA.up(A, na) ); HS_CALL( dB.up(B, nb * batch) ); HS_CALL( dC.up(Cio, nc * batch) );
+   hs_gemm_args g = {M, N, K, HS_KC, layB, dA.p, K, 0, dB.p, layB == HS_KC ? (long long) K : (long long) N, nb, dC.p, ldc, nc, 1.0, 0.0,
+      batch, flags, 1, NULL};
+   const int t5 = hs_dgemm2_paired_taken();
+   const int tw = hs_dgemm2_wide_force(mode);
+   int rc = hs_dgemm(0, &g);
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   used[1] = hs_dgemm2_wide_force(-1) - tw;
+   used[0] = hs_dgemm2_paired_taken() - t5;
+   HS_CALL( rc );
+   HS_CALL( dC.down(Cio, nc * batch) );
+   return HIPSDP_OK;
+}
+
+/* test hook of the same choice for the calls that reach these products through the assembly (hipsdp_schur_form_unit): mode as above;
+ * returns how many products the wide instance has taken so far */
+extern "C" int hipsdp_tri_instance_force(int mode)
+{
+   return hs_dgemm2_wide_force(mode);
+}
+
 /* lower triangle: max |a - b| over r >= c, and the number of elements there whose bits differ */
 __global__ void k_unit_lowdiff(int M, const double* __restrict__ a, const double* __restrict__ b, unsigned long long* __restrict__ out)
 {
