@@ -123,7 +123,10 @@ HIPSDP_API int  hipsdp_mem_info(int device, double* free_bytes, double* total_by
 /* objective b[m] (host) */
 HIPSDP_API int  hipsdp_set_obj(hipsdp_solver* solver, const double* b);
 /* Scatter lower-triangular COO entries (row >= col) into block k: entry e belongs to matrix var[e] (0 = constant matrix,
- * i = variable i, 1-based) at (row[e], col[e]); both triangles of the dense storage are written.  Host arrays. */
+ * i = variable i, 1-based) at (row[e], col[e]); both triangles of the dense storage are written.  Host arrays.  An entry with
+ * row < col stands for its mirror position.  A position named more than once in one call keeps its LAST entry, in a block kept as
+ * nonzeros and - for calls of at most 16384 entries, which are checked on the host - in dense storage alike; a larger call into
+ * dense storage is scattered by the device in no order and must name every position once. */
 HIPSDP_API int  hipsdp_add_entries(hipsdp_solver* solver, int block, long long nnz, const int* var, const int* row, const int* col,
    const double* val);
 /* Master copy (optional, for callers that solve many nodes of one problem): the matrices of the variables in ORIGINAL block

@@ -70,10 +70,22 @@ HIPSDP_API int  hipsdp_schur_shard_time(int device, int m1, int n, int nranks, i
 /* the same for one rank of the variable-sharded assembly (hipsdp_shard_matrices): only that rank's rows of A are allocated, the
  * column slices are cw wide, the all-to-all keeps the rank's own piece; *a2a_bytes = bytes the rank would send per assembly */
 HIPSDP_API int  hipsdp_schur_var_share_time(int device, int m1, int n, int nranks, int rank, int cw, int reps, double* ms, double* a2a_bytes);
-/* sparse block mode: Schur entries of matrices given as triplets (var 1 .. m, row >= col) exactly as the engine assembles them
- * (csrc/sparse.hip); Mx (m + 1) x (m + 1), lower triangle of rows / columns 1 .. m */
+/* sparse block mode: Schur entries of matrices given as triplets (var 1 .. m; either triangle, the last of several entries with the
+ * same (var, row, col) counts) exactly as the engine assembles them (csrc/sparse.hip); Mx (m + 1) x (m + 1), lower triangle of
+ * rows / columns 1 .. m */
 HIPSDP_API int  hipsdp_schur_sparse_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
    const double* val, const double* X, const double* Zinv, double* Mx);
+/* the same with the kernel chosen by the caller: kernel = -1 the engine's rule (fewer than 24 full entries per matrix on average: one
+ * thread per pair), 0 forces k_sp_schur_t (one thread per pair), 1 forces k_sp_schur (one wavefront per pair); *took (may be NULL):
+ * the kernel that ran, 0 or 1 */
+HIPSDP_API int  hipsdp_schur_sparse_unit2(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* X, const double* Zinv, double* Mx, int kernel, int* took);
+/* the two passes over a block kept as nonzeros, on the structure built from the caller's triplets: outA[m] = <A_v, V>, v = 1 .. m
+ * (hs_sp_apply_A; V[n][n] need not be symmetric, both V[r][c] and V[c][r] are read); outAT[n][n] = base + sum_{v >= 1} coef[v] A_v
+ * (hs_sp_apply_AT on a copy of base[n][n]; coef[m + 1], coef[0] is not used).  V / outA or coef / base / outAT may be NULL: that
+ * half is skipped */
+HIPSDP_API int  hipsdp_sparse_ops_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* V, const double* coef, const double* base, double* outA, double* outAT);
 /* measured FP64 matrix peak of the device: a chip-filling launch of register-only v_mfma_f64_16x16x4_f64 for about ms milliseconds;
  * *tflops by HIP events, *ghz = shader clocks per wall tick inside the kernel (bench.py prices its roofline against this as well) */
 HIPSDP_API int  hipsdp_mfma_peak(int device, double ms, double* tflops, double* ghz);

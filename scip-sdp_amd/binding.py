@@ -905,6 +905,47 @@ def schur_sparse_unit(n, m, coo, X, Zinv, device=0):
     return Mx
 
 
+def _coo_i32(coo):
+    var, row, col, val = coo
+    return (np.ascontiguousarray(var, dtype=np.int32), np.ascontiguousarray(row, dtype=np.int32),
+            np.ascontiguousarray(col, dtype=np.int32), _f64(val))
+
+
+def schur_sparse_unit2(n, m, coo, X, Zinv, kernel=-1, device=0):
+    """schur_sparse_unit with the kernel in the caller's hand (hipsdp_schur_sparse_unit2: kernel -1 the engine's rule, 0 one thread
+    per pair, 1 one wavefront per pair): (Mx, took) with took = the kernel that ran"""
+    var, row, col, val = _coo_i32(coo)
+    X = _f64(X); Zinv = _f64(Zinv)
+    Mx = np.zeros((m + 1, m + 1))
+    took = C.c_int(-7)
+    _chk(ulib().hipsdp_schur_sparse_unit2(device, n, m, C.c_longlong(len(val)), _ip(var), _ip(row), _ip(col), _dp(val), _dp(X), _dp(Zinv),
+                                          _dp(Mx), int(kernel), C.byref(took)), "hipsdp_schur_sparse_unit2")
+    return Mx, took.value
+
+
+def sparse_ops_unit(n, m, coo, V=None, coef=None, base=None, device=0):
+    """the two passes of csrc/sparse.hip on the caller's triplets (hipsdp_sparse_ops_unit): (outA[m] = <A_v, V> or None when V is None,
+    outAT[n, n] = base + sum_v coef[v] A_v or None when coef is None; coef has m + 1 entries, base defaults to zeros)"""
+    var, row, col, val = _coo_i32(coo)
+    outA = outAT = None
+    pV = pc = pb = pA = pAT = None
+    if V is not None:
+        V = _f64(V)
+        assert V.shape == (n, n)
+        outA = np.full(m, np.nan)
+        pV, pA = _dp(V), _dp(outA)
+    if coef is not None:
+        coef = _f64(coef)
+        assert coef.shape == (m + 1,)
+        base = np.zeros((n, n)) if base is None else _f64(base)
+        assert base.shape == (n, n)
+        outAT = np.full((n, n), np.nan)
+        pc, pb, pAT = _dp(coef), _dp(base), _dp(outAT)
+    _chk(ulib().hipsdp_sparse_ops_unit(device, n, m, C.c_longlong(len(val)), _ip(var), _ip(row), _ip(col), _dp(val), pV, pc, pb, pA, pAT),
+         "hipsdp_sparse_ops_unit")
+    return outA, outAT
+
+
 def schur_w(A, X, Z, device=0):
     A = _f64(A)
     m1, n = A.shape[0], A.shape[1]

@@ -224,6 +224,9 @@ long long hs_sp_nnz(const hs_sparse* sp);
 int  hs_sp_apply_A(hipStream_t s, const hs_sparse* sp, const double* V, double* out_var1);       /* out[v - 1] = <A_v, V>, v = 1 .. m */
 int  hs_sp_apply_AT(hipStream_t s, const hs_sparse* sp, const double* coef, double* out);        /* out += sum_{v >= 1} coef[v] A_v */
 int  hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx);   /* lower triangle, i, j >= 1 */
+/* hs_sp_schur with the choice of kernel in the caller's hand (kernel: -1 the engine's rule, 0 one thread per pair, 1 one wavefront
+ * per pair) and the kernel that ran in *took (may be NULL) - the unit entries */
+int  hs_sp_schur_ex(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx, int kernel, int* took);
 int  hs_sp_expand(hipStream_t s, const hs_sparse* sp, double* A);
 
 /* ---- sp_master.hip: master copy of a block kept as triplets in ORIGINAL indices, and the gather of a node from it ------- */

@@ -1073,6 +1073,32 @@ __global__ void k_scatter_coo(long long nnz, int n, const int* __restrict__ var,
    }
 }
 
+/* k_scatter_coo writes its entries in no order, and an entry writes both triangles: a position named twice in one call (as (r, c)
+ * and again as (r, c) or (c, r)) would keep either value, or one value per triangle.  A block kept as nonzeros keeps the LAST entry
+ * of a position (hs_sp_build), so the dense scatter is handed only that one: false when no position repeats (nothing to do), else
+ * keep = the entries to scatter, in the caller's order.  Indices are in range (checked by the caller). */
+static bool scatter_last_of_each_position(long long nnz, int n, const int* var, const int* row, const int* col, std::vector<long long>* keep)
+{
+   std::vector<std::pair<unsigned long long, long long> > key((size_t) nnz);
+   for (long long e = 0; e < nnz; ++e)
+   {
+      const unsigned long long r = (unsigned long long) (row[e] >= col[e] ? row[e] : col[e]), c = (unsigned long long) (row[e] >= col[e] ? col[e] : row[e]);
+      key[(size_t) e] = std::make_pair(((unsigned long long) var[e] * (unsigned long long) n + r) * (unsigned long long) n + c, e);
+   }
+   std::sort(key.begin(), key.end());
+   bool repeats = false;
+   for (size_t k = 0; k + 1 < key.size() && !repeats; ++k)
+      repeats = key[k].first == key[k + 1].first;
+   if ( !repeats )
+      return false;
+   keep->clear();
+   for (size_t k = 0; k < key.size(); ++k)
+      if ( k + 1 == key.size() || key[k].first != key[k + 1].first )
+         keep->push_back(key[k].second);
+   std::sort(keep->begin(), keep->end());
+   return true;
+}
+
 extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, const int* var, const int* row, const int* col,
    const double* val)
 {
@@ -1115,6 +1141,17 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
       s->solved = false;
       if ( cv.empty() )
          return HIPSDP_OK;
+      {
+         std::vector<long long> keep;
+         if ( scatter_last_of_each_position((long long) cv.size(), B.n, cv.data(), cr.data(), cc.data(), &keep) )
+         {
+            for (size_t k = 0; k < keep.size(); ++k)         /* (keep ascends: in place) */
+            {
+               cr[k] = cr[(size_t) keep[k]]; cc[k] = cc[(size_t) keep[k]]; cx[k] = cx[(size_t) keep[k]];
+            }
+            cv.resize(keep.size()); cr.resize(keep.size()); cc.resize(keep.size()); cx.resize(keep.size());
+         }
+      }
       nnz = (long long) cv.size();
       int *dv, *dr, *dc; double* dval;
       HS_CALL( flush_cmds(s) );
@@ -1131,6 +1168,7 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
       dfree(dv); dfree(dr); dfree(dc); dfree(dval);
       return HIPSDP_OK;
    }
+   std::vector<int> kv, kr, kc; std::vector<double> kx;       /* (the call's entries without the overwritten ones, when there are any) */
    if ( nnz <= 16384 )
    {
       /* a few triplets (the constant matrix of a node): indices checked here, the triplets through the arena, no wait */
@@ -1142,6 +1180,16 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
       {
          set_err("hipsdp_add_entries: index out of range");
          return HIPSDP_ERR_ARG;
+      }
+      std::vector<long long> keep;
+      if ( scatter_last_of_each_position(nnz, B.n, var, row, col, &keep) )
+      {
+         for (long long e : keep)
+         {
+            kv.push_back(var[e]); kr.push_back(row[e]); kc.push_back(col[e]); kx.push_back(val[e]);
+         }
+         nnz = (long long) keep.size();
+         var = kv.data(); row = kr.data(); col = kc.data(); val = kx.data();
       }
       void* dvp = NULL;
       char* h = (char*) stage_take(s, (size_t) nnz * (3 * sizeof(int) + sizeof(double)) + 64, &dvp);

@@ -345,8 +345,12 @@ __global__ void __launch_bounds__(256) k_sp_schur_t(int m, int n, const int* __r
    }
 }
 
-int hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx)
+/* kernel: -1 the rule below (one thread per pair when a matrix has fewer than 24 full entries on average), 0 k_sp_schur_t, 1 k_sp_schur
+ * whatever the average is (the unit entries, to see either kernel on any input); *took (may be NULL): the kernel that ran, -1 none */
+int hs_sp_schur_ex(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx, int kernel, int* took)
 {
+   if ( took != NULL )
+      *took = -1;
    if ( sp->m <= 0 )
       return HS_OK;
    const long long npairs = (long long) sp->m * (sp->m + 1) / 2;
@@ -359,13 +363,15 @@ int hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const doubl
    }
    {
       const double avg = (double) sp->nfull / (double) sp->m;
-      if ( avg < 24.0 )
+      if ( kernel < 0 ? avg < 24.0 : kernel == 0 )
       {
          long long blocks = (npairs + 255) / 256;
          if ( blocks > 65536 ) blocks = 65536;
          hipLaunchKernelGGL(k_sp_schur_t, dim3((unsigned) blocks), dim3(256), 0, s, sp->m, sp->n, sp->foff, sp->frow, sp->fcol, sp->fval,
             sp->soff, sp->srow, sp->Tc, X, Mx, npairs);
          HS_HIP( hipGetLastError() );
+         if ( took != NULL )
+            *took = 0;
          return HS_OK;
       }
    }
@@ -374,7 +380,14 @@ int hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const doubl
    hipLaunchKernelGGL(k_sp_schur, dim3((unsigned) blocks), dim3(256), 0, s, sp->m, sp->n, sp->foff, sp->frow, sp->fcol, sp->fval,
       sp->soff, sp->srow, sp->Tc, X, Mx, npairs);
    HS_HIP( hipGetLastError() );
+   if ( took != NULL )
+      *took = 1;
    return HS_OK;
+}
+
+int hs_sp_schur(hipStream_t s, const hs_sparse* sp, const double* X, const double* Zinv, double* Mx)
+{
+   return hs_sp_schur_ex(s, sp, X, Zinv, Mx, -1, NULL);
 }
 
 __global__ void k_sp_expand(long long nnz, int n, const int* __restrict__ pvar_by_var, const int* __restrict__ voff, int m,

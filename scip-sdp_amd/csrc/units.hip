@@ -1274,10 +1274,11 @@ extern "C" int hipsdp_pass_at_unit(int device, int R, long long E, const double*
 }
 
 /* unit entry of the sparse block mode (csrc/sparse.hip): the Schur entries tr(A_i X A_j Zinv), i, j = 1 .. m, of matrices given as
- * triplets (var 1 .. m, row >= col), assembled by hs_sp_schur exactly as the engine calls it; Mx: (m + 1) x (m + 1), only the lower
+ * triplets (var 1 .. m; an entry may name either triangle, and of several with the same (var, row, col) the last one counts - what
+ * hs_sp_build makes of them), assembled by hs_sp_schur exactly as the engine calls it; Mx: (m + 1) x (m + 1), only the lower
  * triangle of the rows / columns 1 .. m is written (the rest is returned zero) */
-extern "C" int hipsdp_schur_sparse_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
-   const double* val, const double* X, const double* Zinv, double* Mx)
+static int schur_sparse_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* X, const double* Zinv, double* Mx, bool ex, int kernel, int* took)
 {
    HS_CALL( pick_device(device) );
    if ( n <= 0 || m <= 0 || nnz < 0 || X == NULL || Zinv == NULL || Mx == NULL )
@@ -1292,9 +1293,64 @@ extern "C" int hipsdp_schur_sparse_unit(int device, int n, int m, long long nnz,
    if ( rc == HS_OK ) rc = dX.up(X, n2);
    if ( rc == HS_OK ) rc = dZ.up(Zinv, n2);
    if ( rc == HS_OK && hipMemset(dM.p, 0, (size_t) mm * sizeof(double)) != hipSuccess ) rc = HS_ERR_HIP;
-   if ( rc == HS_OK ) rc = hs_sp_schur(0, sp, dX.p, dZ.p, dM.p);
+   if ( rc == HS_OK ) rc = ex ? hs_sp_schur_ex(0, sp, dX.p, dZ.p, dM.p, kernel, took) : hs_sp_schur(0, sp, dX.p, dZ.p, dM.p);
    if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
    if ( rc == HS_OK ) rc = dM.down(Mx, mm);
+   hs_sp_free(sp);
+   return rc;
+}
+
+extern "C" int hipsdp_schur_sparse_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* X, const double* Zinv, double* Mx)
+{
+   return schur_sparse_unit(device, n, m, nnz, var, row, col, val, X, Zinv, Mx, false, -1, NULL);
+}
+
+/* the same with the kernel in the caller's hand: kernel = -1 the engine's rule, 0 k_sp_schur_t (one thread per pair), 1 k_sp_schur (one
+ * wavefront per pair) on whatever input; *took (may be NULL): the kernel that ran */
+extern "C" int hipsdp_schur_sparse_unit2(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* X, const double* Zinv, double* Mx, int kernel, int* took)
+{
+   if ( kernel < -1 || kernel > 1 )
+      return HIPSDP_ERR_ARG;
+   return schur_sparse_unit(device, n, m, nnz, var, row, col, val, X, Zinv, Mx, true, kernel, took);
+}
+
+/* the two passes over a block kept as nonzeros (csrc/sparse.hip) on a structure hs_sp_build makes of the caller's triplets:
+ * outA[m] = <A_v, V>, v = 1 .. m, by hs_sp_apply_A (V[n][n] need not be symmetric: an off-diagonal entry reads V[r][c] and V[c][r]);
+ * outAT[n][n] = base + sum_{v >= 1} coef[v] A_v by hs_sp_apply_AT on a copy of base (coef[m + 1]; coef[0] belongs to the constant
+ * matrix and is not used).  Either pair (V, outA) / (coef, base, outAT) may be NULL: that half is skipped. */
+extern "C" int hipsdp_sparse_ops_unit(int device, int n, int m, long long nnz, const int* var, const int* row, const int* col,
+   const double* val, const double* V, const double* coef, const double* base, double* outA, double* outAT)
+{
+   HS_CALL( pick_device(device) );
+   const bool doA = V != NULL && outA != NULL, doAT = coef != NULL && base != NULL && outAT != NULL;
+   if ( n <= 0 || m <= 0 || nnz < 0 || (!doA && !doAT) )
+      return HIPSDP_ERR_ARG;
+   hs_sparse* sp = NULL;
+   HS_CALL( hs_sp_build(&sp, n, m, nnz, var, row, col, val) );
+   const long long n2 = (long long) n * n;
+   DevBuf dV, dA, dc, dO;
+   int rc = HS_OK;
+   if ( doA )
+   {
+      rc = dV.alloc(n2);
+      if ( rc == HS_OK ) rc = dA.alloc(m);
+      if ( rc == HS_OK ) rc = dV.up(V, n2);
+      if ( rc == HS_OK && hipMemset(dA.p, 0, (size_t) m * sizeof(double)) != hipSuccess ) rc = HS_ERR_HIP;
+      if ( rc == HS_OK ) rc = hs_sp_apply_A(0, sp, dV.p, dA.p);
+   }
+   if ( rc == HS_OK && doAT )
+   {
+      rc = dc.alloc(m + 1);
+      if ( rc == HS_OK ) rc = dO.alloc(n2);
+      if ( rc == HS_OK ) rc = dc.up(coef, m + 1);
+      if ( rc == HS_OK ) rc = dO.up(base, n2);
+      if ( rc == HS_OK ) rc = hs_sp_apply_AT(0, sp, dc.p, dO.p);
+   }
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   if ( rc == HS_OK && doA ) rc = dA.down(outA, m);
+   if ( rc == HS_OK && doAT ) rc = dO.down(outAT, n2);
    hs_sp_free(sp);
    return rc;
 }
