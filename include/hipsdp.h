@@ -371,9 +371,8 @@ HIPSDP_API int hipsdp_sparsecuts_stats(long long* calls, long long* launches, lo
  * variant == 0: the call IS hipsdp_sparsecuts_all / hipsdp_sparsecuts - the same launches, the same bits, booked under their stats;
  * the totals of hipsdp_sparsecuts_ex_stats do not move.  A bit above HIPSDP_SC_EXACTTRANS set: HIPSDP_ERR_ARG, nothing launched.
  * variant != 0 serves blocks of AT MOST 128 ROWS of a solver without communicator and without sharded matrices, in all three storage
- * forms of a block.  A block of more than 128 rows gets ncuts = -1 and nothing else written, from BOTH calls: for 129 .. 512 rows
- * this is a limit of the present implementation (every cut would need a tridiagonalisation of its own) - keep the host loop for such a
- * block, or call with variant 0.
+ * forms of a block.  A block of more than 128 rows gets ncuts = -1 and nothing else written, from BOTH calls: the blocks of
+ * 129 .. 512 rows are served by hipsdp_sparsecuts_all_large (below) - call it for the blocks that came back with -1.
  * The loop runs as maxcuts + 1 rounds on the device (csrc/sparsecuts_rounds.hip): the state of a block stays in the workspace, the
  * decompositions stand between the TPower launches, and nothing is read back in between.  With s = 1 for
  * HIPSDP_SC_RECOMPUTE_SPARSEEV (else 0) and d = 1 for HIPSDP_SC_RECOMPUTE_INITIAL or HIPSDP_SC_EXACTTRANS (else 0) a call issues
@@ -389,6 +388,38 @@ HIPSDP_API int hipsdp_sparsecuts_ex(hipsdp_solver* solver, int block, const doub
    unsigned variant, int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
 /* process totals of the two calls with variant != 0: calls, kernel launches they issued, device->host synchronisations they waited on */
 HIPSDP_API int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks);
+
+/* The partner of hipsdp_sparsecuts_all_ex for the blocks it turns away: the sparse cuts of ALL blocks of 129 .. HIPSDP_SPARSECUTS_MAXN
+ * rows of a solver in one call, with every combination of the three switches (variant 0 .. 7, zero included).  Call
+ * hipsdp_sparsecuts_all_ex first, then this for the blocks that came back with ncuts = -1.  Arguments, output layout (slot (b, c), the
+ * vectors of block b at vecs + maxcuts (n_0 + ... + n_{b-1})), NULL rules, the meaning of ncuts = 0, of flags bits 0 - 2 and of
+ * eigvals[c], "slots c >= ncuts[b] are not written" and the argument errors (HIPSDP_ERR_ARG before the device is looked at; a variant
+ * bit above HIPSDP_SC_EXACTTRANS is one) are those of hipsdp_sparsecuts_all_ex.
+ * Served: blocks of 129 .. 512 rows of a solver without communicator and without sharded matrices, in all three storage forms.
+ * ncuts[b] = -1 and nothing else written: a block of at most 128 rows, a block of more than 512 rows, and - LIMIT - a block whose
+ * sizes[b] exceeds 128 while HIPSDP_SC_RECOMPUTE_SPARSEEV is set (its Z_S goes through the one-launch decompositions, which end at 128
+ * rows).  The other blocks are still served.  A solver with a communicator or sharded matrices: every ncuts = -1, nothing launched; a
+ * call with no served block launches nothing.
+ * The device side (csrc/sparsecuts_large_rounds.hip): Z_b(y) of the served blocks in one launch; (lmin, v0) and maxeig of every block
+ * from the batched tridiagonal path of hipsdp_onevar_bounds_large (one staging launch, nmax - 1 column launches that hold the matrices
+ * of all blocks, 3 selection launches; nmax: rows of the largest served block); then with variant == 0 ONE launch with a workgroup per
+ * block that runs the block's whole loop (the loop of hipsdp_sparsecuts), and with variant != 0 maxcuts + 1 rounds as in
+ * hipsdp_sparsecuts_all_ex - a TPower launch over all blocks, with HIPSDP_SC_RECOMPUTE_SPARSEEV (s = 1, else 0) three decomposition
+ * launches and the cut, with HIPSDP_SC_RECOMPUTE_INITIAL or HIPSDP_SC_EXACTTRANS (d = 1, else 0) the nmax + 3 launches of the
+ * tridiagonal path on the deflated matrices of the blocks that go on; the coefficients in one launch.  Kernel launches of a call:
+ *     1 + (nmax + 3) + r (1 + 4 s + d (nmax + 3)) + 1 + [maxcuts > 0],    r = maxcuts with variant != 0, r = 0 with variant == 0
+ * - a function of (variant, maxcuts, nmax) alone, whatever the number of blocks, cuts and iterations -, one upload and ONE read-back.
+ * A block takes about 4.3 n^2 doubles of the solver's cut workspace (9 MB at 512 rows): the blocks are ordered by descending n and run
+ * in chunks of at most 512 MiB (HIPSDP_SPARSECUTS_LARGE_CHUNK in the environment, read at every call: blocks per chunk instead), and
+ * every chunk is a call of its own in launches and read-backs (nmax: the chunk's largest block).
+ * The bits of a block depend on the block, y, its size, the options and the mask alone - not on the other blocks, their order or the
+ * chunks; same input, same bits.  With variant == 0 counts, supports and flags are those of hipsdp_sparsecuts.  lmin and maxeig have
+ * the accuracy of hipsdp_syevx.  Two host threads may call it at the same time on different solvers. */
+HIPSDP_API int hipsdp_sparsecuts_all_large(hipsdp_solver* solver, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags);
+/* process totals of hipsdp_sparsecuts_all_large alone: calls that served a block, kernel launches they issued, device->host
+ * synchronisations they waited on (one per chunk); the totals of the other three sparse-cut stats calls do not move, and the reverse */
+HIPSDP_API int hipsdp_sparsecuts_all_large_stats(long long* calls, long long* launches, long long* readbacks);
 
 /* All one-variable SDPs of a block in one call: the bound-tightening loops of cons_sdp.c - tightenBounds (:1968-2201) and
  * tightenMatrices (:1856-1961) solve one SDP PER VARIABLE of a block, each the semismooth Newton method of

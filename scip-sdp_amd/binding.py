@@ -514,6 +514,39 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's sparsecuts_ex_stats()"""
         return sparsecuts_ex_stats()
 
+    def sparsecuts_all_large(self, y, sizes, tol, feastol, maxcuts, variant, convtol=0, maxit=0):
+        """the partner of sparsecuts_all_ex for the blocks it turns away (hipsdp_sparsecuts_all_large): the sparse cuts of all blocks
+        of 129 .. 512 rows in one call, variant 0 .. 7; the same list of tuples - ncuts = -1 for a block of at most 128 or more than
+        512 rows, and for a block whose sizes[b] exceeds 128 while SC_RECOMPUTE_SPARSEEV is set"""
+        y = _f64(y)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        m, nb, mc = len(y), len(self.ns), max(1, maxcuts)
+        assert len(sizes) == nb
+        opts = SparsecutOpts(tol, feastol, convtol, maxcuts, maxit)
+        k = np.zeros(max(1, nb), dtype=np.int32)
+        it = np.zeros(max(1, nb), dtype=np.int32)
+        fl = np.zeros(max(1, nb), dtype=np.int32)
+        lmin = np.full(max(1, nb), np.nan)
+        ev = np.zeros(max(1, nb) * mc)
+        co = np.zeros(max(1, nb) * mc * max(1, m))
+        lh = np.zeros(max(1, nb) * mc)
+        ve = np.zeros(max(1, maxcuts * sum(self.ns)))
+        _chk(self._l().hipsdp_sparsecuts_all_large(self.h, _dp(y), _ip(sizes), C.byref(opts), C.c_uint(variant), _ip(k), _dp(lmin), _dp(ev),
+                                                   _dp(co), _dp(lh), _dp(ve), _ip(it), _ip(fl)), "hipsdp_sparsecuts_all_large")
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            kb = max(0, int(k[b]))
+            s0 = b * maxcuts
+            out.append((int(k[b]), float(lmin[b]), ev[s0:s0 + kb].copy(), co[s0 * m:(s0 + kb) * m].reshape(kb, m).copy(),
+                        lh[s0:s0 + kb].copy(), ve[off:off + kb * n].reshape(kb, n).copy(), int(it[b]), int(fl[b])))
+            off += maxcuts * n
+        return out
+
+    @staticmethod
+    def sparsecuts_all_large_stats():
+        """process totals (calls, launches, read-backs): the module's sparsecuts_all_large_stats()"""
+        return sparsecuts_all_large_stats()
+
     def onevar_bounds(self, block, u, lb, ub, feastol, vars=None, kind=None, infinity=1e20, maxevals=0):
         """all one-variable SDPs of a block in one call (hipsdp_onevar_bounds): job j works on Z_block(u) + (mu - u_i) A_i with
         i = vars[j] (None: all variables in index order), kind[j] ONEVAR_NEWTON (None: all) or ONEVAR_TWOPOINT, bounds lb[j], ub[j].
@@ -721,6 +754,14 @@ def sparsecuts_ex_stats():
     device->host synchronisations)"""
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_sparsecuts_ex_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_ex_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def sparsecuts_all_large_stats():
+    """process totals of hipsdp_sparsecuts_all_large: (calls that served a block, kernel launches issued, device->host
+    synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_sparsecuts_all_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_all_large_stats")
     return calls.value, launches.value, readbacks.value
 
 

@@ -1,6 +1,7 @@
 /* cut_calls.hip - the host side of the cut calls that serve many blocks, or one large block, in a fixed number of launches:
  * hipsdp_eigencuts_all (kernels: eigcuts.hip, many-forms of the decompositions: eigi.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts
- * (sparsecuts.hip, sparsecuts_large.hip) and their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip).
+ * (sparsecuts.hip, sparsecuts_large.hip), their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip), and
+ * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip).
  *
  * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
  * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
@@ -11,13 +12,16 @@
 #include "hs_cut_plan.h"
 #include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
-#include <vector>
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <vector>
 
 namespace {
 
-/* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, and the two _ex calls with a switch set */
-CutStats g_ec, g_sc, g_sc1, g_scx;
+/* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, the two _ex calls with a switch set, hipsdp_sparsecuts_all_large */
+CutStats g_ec, g_sc, g_sc1, g_scx, g_scl;
 
 /* the caller's arrays of a call, or of one block of it (all but ncuts may be NULL) */
 struct CutDst
@@ -367,6 +371,218 @@ int sparsecuts_large(hipsdp_solver* s, int m, int block, const double* y, int si
    return cut_block_out(h, 0, h.ncuts[0], maxcuts, 0, m, n, d);
 }
 
+/* ---- hipsdp_sparsecuts_all_large: all blocks of 129 .. 512 rows per launch, switches included (kernels: sparsecuts_large_rounds.hip) ---- */
+static_assert(sizeof(hs_sxm_job) == 6 * sizeof(double), "hs_sclr_layout: jobw");
+static_assert(sizeof(hs_sclr_job) == 7 * sizeof(double), "hs_sclr_layout: xjobw");
+static_assert(sizeof(hs_eig_job) == 3 * sizeof(double), "hs_sclr_layout: sjobw");
+#define SCLR_JOBW 6
+#define SCLR_XJOBW 7
+#define SCLR_SJOBW 3
+#define SCLR_BUDGET (512LL * 1024 * 1024 / (long long) sizeof(double))    /* doubles of block workspace per chunk */
+
+/* what a served block of n rows takes of the chunk's workspace (ns: rows of its Z_S, 0 without recomputesparseev) */
+hs_sclr_block sclr_block(int n, int ns)
+{
+   return hs_sclr_block_make(n, ns, ns > 0 ? hs_syev_small_scratch(ns) : 0, (long long) hs_syevx_ws(n), HS_SXM_OUT(n));
+}
+
+/* workgroups per matrix of the column launches: about four workgroups per compute unit over all blocks, at least 8, at most the 128 of
+ * a matrix alone (the rule of hipsdp_onevar_bounds_large; the bits do not depend on it) */
+int sclr_cap(int count)
+{
+   const int cus = hs_device_cus();
+   const int g = (4 * (cus > 0 ? cus : 256)) / count;
+   return g < 8 ? 8 : (g > 128 ? 128 : g);
+}
+
+/* ONE CHUNK: the served blocks `ids` (descending n) of a solver with nb blocks - a call of its own in everything but the entry: its
+ * layout of the workspace (hs_sclr_layout), ONE upload of  y | sizes | the three tables | act,  the launches - hs_sclr_launches(variant,
+ * maxcuts, nmax) of them, whatever the blocks do -, ONE read-back, the copy-out.  gvecoff: where a block's vectors start in the caller's
+ * array. */
+int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, const CutDst& d, const std::vector<long long>& gvecoff)
+{
+   const int cnt = (int) ids.size(), maxcuts = opts->maxcuts;
+   const bool sparseev = (variant & HS_SCR_SPARSEEV) != 0, deflated = (variant & (HS_SCR_INITIAL | HS_SCR_EXACTTRANS)) != 0;
+   /* the chunk's result: indexed by the block's number, vectors of the chunk's blocks alone */
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   {
+      std::vector<char> in((size_t) nb, 0);
+      for (int b : ids)
+         in[b] = 1;
+      for (int b = 0; b < nb; ++b)
+         vecoff[b + 1] = vecoff[b] + (in[b] ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
+   }
+   int smax = 1, nmax = 0;
+   long long blocks_len = 0;
+   std::vector<hs_sclr_block> B((size_t) cnt);
+   std::vector<long long> start((size_t) cnt), zoff((size_t) cnt);
+   std::vector<int> ns((size_t) cnt);
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int n = hs_solver_block_n(s, ids[j]), size = sizes[ids[j]];
+      if ( size <= n && size > smax )
+         smax = size;
+      nmax = n > nmax ? n : nmax;
+      ns[j] = sparseev ? size : 0;
+      B[j] = sclr_block(n, ns[j]);
+      start[j] = blocks_len;
+      blocks_len += B[j].len;
+   }
+   hs_sclr_layout L;
+   hs_sclr_layout_make(nb, m, maxcuts, smax, vecoff[nb], cnt, SCLR_JOBW, SCLR_XJOBW, SCLR_SJOBW, blocks_len, &L);
+   for (int j = 0; j < cnt; ++j)
+      zoff[j] = L.blocks + start[j] + B[j].Z;
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_blocks(s, ids, zoff, L.len.dev_len, L.len.pin_len, &w) );
+   hipStream_t st = w.stream;
+   /* y | sizes | tables | act  in the pinned mirror */
+   if ( m > 0 )
+      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+   memcpy(w.pin + L.sizes, sizes, (size_t) nb * sizeof(int));
+   hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
+   hs_sclr_job* hx = reinterpret_cast<hs_sclr_job*>(w.pin + L.xjobs);
+   int* hact = reinterpret_cast<int*>(w.pin + L.act);
+   std::vector<hs_eig_job> sj;               /* the Z_S jobs by decomposition class: the host copy hs_syev_small_many wants */
+   for (int j = 0; j < cnt; ++j)
+   {
+      double* base = w.dev + L.blocks + start[j];
+      HS_CALL( hs_syevx_many_job(hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, &hsx[j]) );
+      hs_sclr_job& X = hx[j];
+      memset(&X, 0, sizeof(X));
+      X.st = reinterpret_cast<hs_scr_state*>(base + B[j].st);
+      X.v0 = base + B[j].v0;
+      X.MT = base + B[j].MT;
+      if ( ns[j] > 0 )
+      {
+         X.ZS = base + B[j].ZS;
+         X.wsS = base + B[j].wsS;
+         X.vposS = hs_syev_many_vecpos(ns[j]);
+      }
+      X.vecoff = vecoff[ids[j]];
+      hact[j] = HS_SXM_ACTIVE | HS_SXM_VEC | HS_SXM_BOTH;
+   }
+   for (int cls = 0; cls < 3 && sparseev; ++cls)
+      for (int j = 0; j < cnt; ++j)
+         if ( hs_syev_many_class(ns[j]) == cls )
+         {
+            hs_eig_job E;
+            memset(&E, 0, sizeof(E));
+            E.n = ns[j]; E.in = hx[j].ZS; E.ws = hx[j].wsS;
+            sj.push_back(E);
+         }
+   if ( !sj.empty() )
+      memcpy(w.pin + L.sjobs, sj.data(), sj.size() * sizeof(hs_eig_job));
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+
+   const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
+   const hs_sclr_job* dx = reinterpret_cast<const hs_sclr_job*>(w.dev + L.xjobs);
+   const hs_eig_job* dsj = reinterpret_cast<const hs_eig_job*>(w.dev + L.sjobs);
+   int* dact = reinterpret_cast<int*>(w.dev + L.act);
+   const int* dsizes = reinterpret_cast<const int*>(w.dev + L.sizes);
+   const hs_sc_out out = hs_cut_view(L.r, w.dev);
+   hs_sc_par par;
+   sc_par_from_opts(opts, &par);
+   const int cap = sclr_cap(cnt);
+   int launches = 0;
+   HS_CALL( hs_ec_form_z(st, cnt, nmax, m, w.djobs, w.dev + L.y) );
+   ++launches;
+   /* (lmin, v0) and maxeig of Z(y) of every block: stage, nmax - 1 column launches, 3 selection launches */
+   HS_CALL( hs_sclr_stage(st, cnt, w.djobs, dsx, dx, dsizes, dact, sparseev ? 1 : 0) );
+   HS_CALL( hs_syevx_many_cols(st, cnt, nmax, cap, dsx, dact) );
+   HS_CALL( hs_syevx_many_select(st, cnt, nmax, 1, dsx, dact) );
+   launches += nmax + 3;
+   if ( variant == 0 )
+   {
+      HS_CALL( hs_sclr_tpower_all(st, cnt, m, w.djobs, dsx, dx, dsizes, &par, &out) );
+      ++launches;
+   }
+   else
+   {
+      /* what the tridiagonalisations of the deflated Z have to give a block that goes on */
+      const int act_on = HS_SXM_ACTIVE | ((variant & HS_SCR_INITIAL) ? HS_SXM_VEC : 0) | ((variant & HS_SCR_EXACTTRANS) ? HS_SXM_BOTH : 0);
+      for (int round = 0; round <= maxcuts; ++round)
+      {
+         HS_CALL( hs_sclr_tpower(st, cnt, m, w.djobs, dsx, dx, dsizes, &par, variant, round, act_on, dact, &out) );
+         ++launches;
+         if ( round == maxcuts )             /* (a block that is still running has maxcuts cuts: this run cannot produce one) */
+            break;
+         if ( sparseev )
+         {
+            HS_CALL( scx_syev(st, cnt, sj.data(), dsj, &launches) );
+            HS_CALL( hs_sclr_cut(st, cnt, m, w.djobs, dx, dsizes, &par, dact, &out) );
+            ++launches;
+         }
+         if ( deflated )
+         {
+            HS_CALL( hs_sclr_stage(st, cnt, w.djobs, dsx, dx, dsizes, dact, 0) );
+            HS_CALL( hs_syevx_many_cols(st, cnt, nmax, cap, dsx, dact) );
+            HS_CALL( hs_syevx_many_select(st, cnt, nmax, (variant & HS_SCR_EXACTTRANS) ? 1 : 0, dsx, dact) );
+            launches += nmax + 3;
+         }
+      }
+   }
+   if ( maxcuts > 0 )
+   {
+      HS_CALL( hs_sclr_coefs(st, cnt, m, maxcuts, w.djobs, dx, dsizes, &out) );
+      ++launches;
+   }
+   HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_scl.launches += launches;
+   g_scl.readbacks += 1;
+   const hs_sc_out h = hs_cut_view(L.r, w.pin);
+   for (int b : ids)
+      HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, gvecoff[b])) );
+   return HIPSDP_OK;
+}
+
+int sparsecuts_all_large_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
+   const CutDst& d)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || sizes == NULL || opts == NULL || d.ncuts == NULL || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   const int maxcuts = opts->maxcuts;
+   if ( maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      if ( sizes[b] < 1 )
+         return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      d.ncuts[b] = -1;
+   /* the blocks this call serves: whole matrices on this device (none for a solver with a communicator or sharded matrices), 129 .. 512
+    * rows, and with recomputesparseev a target size the decomposition of Z_S takes */
+   std::vector<int> all, ids;
+   HS_CALL( hs_solver_cut_enter_large(s, HIPSDP_SPARSECUTS_MAXN, &all) );
+   const bool sparseev = (variant & HS_SCR_SPARSEEV) != 0;
+   for (int b : all)
+      if ( hs_solver_block_n(s, b) > HS_SC_MAXN && !(sparseev && sizes[b] > HS_SC_MAXN) )
+         ids.push_back(b);
+   if ( ids.empty() )
+      return HIPSDP_OK;
+   std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
+   const int total = (int) ids.size();
+   std::vector<long long> job_len((size_t) total);
+   for (int k = 0; k < total; ++k)
+      job_len[k] = sclr_block(hs_solver_block_n(s, ids[k]), sparseev ? sizes[ids[k]] : 0).len;
+   int maxjobs = 0;
+   const char* env = getenv("HIPSDP_SPARSECUTS_LARGE_CHUNK");          /* (read at every call, like HIPSDP_ONEVAR_LARGE_CHUNK) */
+   if ( env != NULL && atoi(env) > 0 )
+      maxjobs = atoi(env);
+   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts, -1);
+   for (int start = 0; start < total; )
+   {
+      /* (a block count stands alone: blocks of equal n differ in their Z_S, so no budget in doubles expresses it) */
+      const int end = hs_ovl_chunk_end(job_len.data(), total, start, maxjobs > 0 ? std::numeric_limits<long long>::max() / 2 : SCLR_BUDGET, maxjobs);
+      const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
+      HS_CALL( sclr_chunk(s, m, nb, chunk, y, sizes, opts, variant, d, gvecoff) );
+      start = end;
+   }
+   ++g_scl.calls;
+   return HIPSDP_OK;
+}
+
 /* hipsdp_sparsecuts (variant = 0, booked under g_sc1) and hipsdp_sparsecuts_ex with a switch set: blocks of at most 128 rows */
 int sparsecuts_impl(hipsdp_solver* s, int block, const double* y, int size, const hipsdp_sparsecut_opts* opts, unsigned variant, const CutDst& d)
 {
@@ -411,6 +627,11 @@ extern "C" int hipsdp_sparsecuts_stats(long long* calls, long long* launches, lo
 extern "C" int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches, long long* readbacks)
 {
    return g_scx.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_sparsecuts_all_large_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_scl.get(calls, launches, readbacks);
 }
 
 extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
@@ -506,4 +727,12 @@ extern "C" int hipsdp_sparsecuts_ex(hipsdp_solver* s, int block, const double* y
    if ( !variant_ok(variant) )
       return HIPSDP_ERR_ARG;
    return sparsecuts_impl(s, block, y, size, opts, variant, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}
+
+extern "C" int hipsdp_sparsecuts_all_large(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts,
+   unsigned variant, int* ncuts, double* lmin, double* eigvals, double* coefs, double* lhs, double* vecs, int* iters, int* flags)
+{
+   if ( !variant_ok(variant) )
+      return HIPSDP_ERR_ARG;
+   return sparsecuts_all_large_impl(s, y, sizes, opts, variant, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
 }

@@ -99,6 +99,39 @@ void hs_ovl_layout_make(int m, int count, int tabw, int jobw, int resw, int stat
    L->len.dev_len = at;
 }
 
+hs_sclr_block hs_sclr_block_make(int n, int ns, long long scratch, long long ws_len, long long out_len)
+{
+   hs_sclr_block B;
+   B.st = 0;
+   B.v0 = HS_SCR_STATE_LEN;
+   B.Z = B.v0 + even(n);
+   B.MT = B.Z + hs_cut_mat_len(n);
+   B.ZS = B.MT + hs_cut_mat_len(n);
+   B.wsS = B.ZS + (ns > 0 ? hs_cut_mat_len(ns) : 0);
+   B.ws = B.wsS + (ns > 0 ? even(scratch) : 0);
+   B.out = B.ws + even(ws_len);
+   B.len = B.out + even(out_len);
+   return B;
+}
+
+void hs_sclr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, int count, int jobw, int xjobw, int sjobw,
+   long long blocks_len, hs_sclr_layout* L)
+{
+   L->y = 0;
+   L->sizes = even(m);
+   L->jobs = L->sizes + even(((long long) nb + 1) / 2);
+   L->xjobs = L->jobs + even((long long) count * jobw);
+   L->sjobs = L->xjobs + even((long long) count * xjobw);
+   L->act = L->sjobs + even((long long) count * sjobw);
+   L->len.res_off = L->act + even(((long long) count + 1) / 2);
+   L->r.ints = res_arrays(L->len.res_off, nb, m, maxcuts, vec_len, &L->r);
+   L->r.smax = smax;
+   L->r.sup = L->r.ints + (3LL * nb + 1) / 2;
+   L->blocks = even(L->r.sup + ((long long) nb * maxcuts * smax + 1) / 2);
+   L->len.res_len = L->r.sup - L->len.res_off;
+   L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->blocks + blocks_len;
+}
+
 int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs)
 {
    long long used = 0;

@@ -85,6 +85,32 @@ void hs_ovl_layout_make(int m, int count, int tabw, int jobw, int resw, int stat
  * `budget` doubles of job_len[] (workspace + output of a job), at least one, and at most maxjobs when maxjobs > 0 */
 int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs);
 
+/* hipsdp_sparsecuts_all_large (csrc/sparsecuts_large_rounds.hip), ONE CHUNK of `count` served blocks of a solver with nb blocks:
+ *    y[m] | sizes[nb] (int) | tridiagonal jobs [count][jobw] | block table [count][xjobw] | Z_S jobs [count][sjobw] | act[count] (int)
+ *    | res (the arrays of hs_cut_res over nb blocks) | sup | per served block (hs_sclr_block): hs_scr_state | v0[n] | Z | MT | Z_S | the
+ *    slab of its decomposition | workspace of the tridiagonal form | its selection output
+ * every part starts at an even offset.  The tables stand IN FRONT of the result, so that ONE upload (everything before res) carries y,
+ * sizes and the tables, and the pinned mirror ends behind the result's ints (sup and everything behind it is never mirrored). */
+struct hs_sclr_layout { long long y, sizes, jobs, xjobs, sjobs, act; hs_cut_res r; long long blocks; hs_cut_lens len; };
+/* a served block of n rows, as offsets from the block's start: ns: rows of its Z_S (0: none, the call runs without recomputesparseev),
+ * scratch = hs_syev_small_scratch(ns), ws_len = hs_syevx_ws(n), out_len = HS_SXM_OUT(n), passed in as numbers; len: where the next
+ * block starts */
+struct hs_sclr_block { long long st, v0, Z, MT, ZS, wsS, ws, out, len; };
+hs_sclr_block hs_sclr_block_make(int n, int ns, long long scratch, long long ws_len, long long out_len);
+/* jobw, xjobw, sjobw: doubles of a row of the three tables; blocks_len: sum of hs_sclr_block_make(..).len over the chunk's blocks */
+void hs_sclr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len, int count, int jobw, int xjobw, int sjobw,
+   long long blocks_len, hs_sclr_layout* L);
+/* kernel launches of one chunk of hipsdp_sparsecuts_all_large: a function of (variant, maxcuts, nmax) alone, nmax the chunk's largest
+ * block - Z(y); stage, nmax - 1 columns and 3 selection launches; with a switch set maxcuts rounds of a TPower launch, with
+ * recomputesparseev (s) 3 decomposition launches and the cut, with recomputeinitial or exacttrans (d) the nmax + 3 again; the last
+ * TPower launch; the coefficients */
+static inline long long hs_sclr_launches(unsigned variant, int maxcuts, int nmax)
+{
+   const int s = (variant & 1u) ? 1 : 0, d = (variant & 6u) ? 1 : 0;
+   const long long rounds = variant != 0 ? maxcuts : 0;       /* (variant 0: the whole loop is the one TPower launch) */
+   return 1 + ((long long) nmax + 3) + rounds * (1 + 4 * s + (long long) d * (nmax + 3)) + 1 + (maxcuts > 0 ? 1 : 0);
+}
+
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
 {

@@ -484,6 +484,36 @@ int hs_scl_tpower(hipStream_t st, int n, int size, const double* Z, const double
 /* grid (m + 1): x_c^T A_i x_c of every cut of job[0] (its blk and vecoff are 0) in any of the three storage forms */
 int hs_scl_coefs(hipStream_t st, int m, int maxcuts, int size, const hs_ec_job* job, const hs_sc_out* out);
 
+/* ---- sparsecuts_large_rounds.hip: the same for ALL blocks of 129 .. 512 rows per launch, switches included (hipsdp_sparsecuts_all_large) --
+ * Entry j of the three tables belongs to served block j: jobs[j] its hs_ec_job (Z(y), later the deflated Z, at .Z; .blk its index in the
+ * result), sx[j] its job of the batched tridiagonal path (hs_sxm_job: lmin at out[HS_SYEVX_OUT_LAM], the first vector at out +
+ * HS_SYEVX_OUT_VEC, maxeig at out2[HS_SYEVX_OUT_LAM]), xjobs[j] what it has besides; act[j]: the flags of hs_syevx_many_* for block j. */
+struct hs_sxm_job;
+struct hs_sclr_job
+{
+   hs_scr_state* st; double* v0; double* MT;         /* state between the launches, the start vector of round 0, n^2 doubles for M^T */
+   double* ZS; double* wsS; long long vposS;         /* with HS_SCR_SPARSEEV: Z_S, the slab of its decomposition, its eigenvectors in it */
+   long long vecoff;                                 /* where the block's vectors start in the result */
+};
+/* Z of every block with act != 0 into its sx.A in the form the column launches consume (they destroy it), zeros into sx.R; init_zs: the
+ * Z_S of every block becomes the identity (in front of round 0 with HS_SCR_SPARSEEV) */
+int hs_sclr_stage(hipStream_t st, int count, const hs_ec_job* jobs, const hs_sxm_job* sx, const hs_sclr_job* xjobs, const int* sizes,
+   const int* act, int init_zs);
+/* variant 0: the whole loop over cuts and iterations of every block in ONE launch, a workgroup of 512 threads per block (the loop of
+ * k_sc_tpower_large) */
+int hs_sclr_tpower_all(hipStream_t st, int count, int m, const hs_ec_job* jobs, const hs_sxm_job* sx, const hs_sclr_job* xjobs, const int* sizes,
+   const hs_sc_par* par, const hs_sc_out* out);
+/* variant != 0, round `round` of every block: M^T from the current Z, ONE TPower run, its decision; without HS_SCR_SPARSEEV the cut, with
+ * it the support and Z_S for hs_sclr_cut behind the decomposition of the Z_S.  act_on: what act[j] of a block that goes on becomes (a
+ * finished block gets 0) */
+int hs_sclr_tpower(hipStream_t st, int count, int m, const hs_ec_job* jobs, const hs_sxm_job* sx, const hs_sclr_job* xjobs, const int* sizes,
+   const hs_sc_par* par, unsigned variant, int round, int act_on, int* act, const hs_sc_out* out);
+int hs_sclr_cut(hipStream_t st, int count, int m, const hs_ec_job* jobs, const hs_sclr_job* xjobs, const int* sizes, const hs_sc_par* par,
+   int* act, const hs_sc_out* out);
+/* grid (m + 1, count): the coefficients of every cut of every block */
+int hs_sclr_coefs(hipStream_t st, int count, int m, int maxcuts, const hs_ec_job* jobs, const hs_sclr_job* xjobs, const int* sizes,
+   const hs_sc_out* out);
+
 /* ---- ipm.hip: what the cut calls (cut_calls.hip) and hipsdp_onevar_bounds (onevar.hip) need of a solver, whose definition they do not see --
  * hs_solver_dims: 0 when s is NULL or has no shape, else 1 with the number of variables and blocks; hs_solver_block_n: rows of a block.
  * hs_solver_cut_enter: the device is set, staged entries are flushed, the packed triangles and the device form of blocks kept as

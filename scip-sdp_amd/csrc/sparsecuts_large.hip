@@ -8,6 +8,8 @@
  *    k_sc_coefs_large    grid (m + 1), 256 threads      workgroup i: x_c^T A_i x_c of every cut c over the pairs of its support (a
  *                                                       block kept as nonzeros: over the variable's nonzeros)
  *
+ * The bodies of both kernels are device functions of hs_scl_tpower.h (scl_tpower_loop, scl_coefs_block), which the kernels of
+ * sparsecuts_large_rounds.hip - all such blocks of a solver per launch - instantiate as well.
  * An iteration is a chain of dependent steps (|w| -> ranks -> norm -> product -> Rayleigh quotient), not a throughput problem, and
  * the only synchronisation between the rows is the workgroup barrier.  HAZARD RULE: one workgroup, so there is no grid barrier, no
  * flag, no waiting on another workgroup and no atomic operation; MT is read and written by this workgroup alone, and a workgroup
@@ -23,318 +25,23 @@
  * the wavefronts before it.  All sums: hs_wave_sum_dpp per wavefront, then the eight wavefronts in index order.  Every loop
  * condition is false for a NaN, and every loop is bounded by maxit or maxcuts. */
 #include "hs_kernels.h"
-#include "hs_wave.h"
-
 #define SCL_NT 512         /* k_sc_tpower_large: one thread per row, HS_SCL_MAXN rows at most */
-#define SCL_NW (SCL_NT / 64)
-#define SCL_CT 256         /* k_sc_coefs_large */
-
-/* Sum over the workgroup, the same bits in every thread.  ONE barrier, behind the stores to red - red must not be written again
- * before the next barrier of the caller. */
-__device__ __forceinline__ double scl_block_sum(double v, double* red)
-{
-   v = hs_wave_sum_dpp(v);
-   if ( (threadIdx.x & 63) == 0 )
-      red[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double s = red[0];
-#pragma unroll
-   for (int w = 1; w < SCL_NW; ++w)
-      s += red[w];
-   return s;
-}
-
-/* (M x)_i = sum_p M[i][s_p] x_p in the order of p, mcol = MT + i: M[i][c] lies at mcol[c n].  LIST: s_p = sup[p] (x on its ascending
- * support), otherwise s_p = p (a dense x).  The loads of eight summands are in flight together - one round trip to the L2 per eight
- * instead of one per summand -, the additions keep their order. */
-template<bool LIST>
-__device__ __forceinline__ double scl_row_product(const double* mcol, int n, const double* xv, const int* sup, int cnt)
-{
-   double acc = 0.0;
-   int p = 0;
-   for (; p + 8 <= cnt; p += 8)
-   {
-      double mv[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-         mv[k] = mcol[(size_t) (LIST ? sup[p + k] : p + k) * n];
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-         acc += mv[k] * xv[p + k];
-   }
-   for (; p < cnt; ++p)
-      acc += mcol[(size_t) (LIST ? sup[p] : p) * n] * xv[p];
-   return acc;
-}
-
-/* the global stores of this wavefront to MT have left it: with the barrier that follows, the workgroup's later loads see them */
-#define SCL_STORES_DONE() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#include "hs_scl_tpower.h"
 
 __global__ void __launch_bounds__(SCL_NT) k_sc_tpower_large(int n, int size, const double* __restrict__ Z, const double* __restrict__ plmin,
    const double* __restrict__ pmaxeig, const double* __restrict__ v0, double* MT, hs_sc_par par, hs_sc_out out)
 {
-   __shared__ __attribute__((aligned(16))) long long keys[SCL_NT];            /* |w| as ordered integers; rows n .. 511 hold -1 */
-   __shared__ __attribute__((aligned(16))) long long ckey[SCL_NT + 2];        /* the keys of the candidates, in index order */
-   __shared__ double zd[SCL_NT];             /* the diagonal of Z: M's is formed from it again after every cut */
-   __shared__ double xc[SCL_NT];             /* x on its support: xc[p] = x[sup[p]] */
-   __shared__ double v0s[SCL_NT];
-   __shared__ double red[SCL_NW];
-   __shared__ int sup[SCL_NT];
-   __shared__ int wkept[SCL_NW], wcand[SCL_NW];
-   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   const double lmin = plmin[0];
-   if ( n < 1 || n > SCL_NT || !(lmin < -par.tol) || size > n || size < 1 || par.maxcuts <= 0 )
-   {
-      if ( tid == 0 )
-      {
-         out.ncuts[0] = 0; out.iters[0] = 0; out.flags[0] = 0;
-         out.lmin[0] = lmin;
-      }
-      return;
-   }
-   const bool row = tid < n;
-   const bool prune = size < 64;             /* (with 64 and more every row is a candidate) */
-   double maxeig = pmaxeig[0];
-   /* MT[c n + r] = M[r][c]: Z is read in memory order, as k_sc_tpower reads it */
-   for (int e0 = tid; e0 < n * n; e0 += 8 * SCL_NT)
-   {
-      double zv[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k)             /* (eight loads in flight, as in scl_row_product) */
-         zv[k] = e0 + k * SCL_NT < n * n ? Z[e0 + k * SCL_NT] : 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-      {
-         const int e = e0 + k * SCL_NT;
-         if ( e < n * n )
-         {
-            const int r = e / n, c = e - r * n;
-            MT[(size_t) c * n + r] = r == c ? maxeig - zv[k] : -zv[k];
-            if ( r == c )
-               zd[r] = zv[k];
-         }
-      }
-   }
-   v0s[tid] = row ? v0[tid] : 0.0;
-   keys[tid] = -1;
-   sup[tid] = 0;
-   const double* mcol = MT + (row ? tid : 0);          /* M[tid][c] at mcol[c n] */
-   int nc = 0, iters = 0, flags = 0;
-   for (;;)
-   {
-      /* ---- one TPower run from v0 on M (as in the reference, one more follows the last cut) ---- */
-      SCL_STORES_DONE();
-      __syncthreads();           /* MT (first run: filled, later: after the cut) and the last reads of x and the support */
-      double x = 0.0, u = 0.0;
-      if ( row )
-      {
-         x = v0s[tid];
-         u = scl_row_product<false>(mcol, n, v0s, sup, n);
-      }
-      double newv = -1.0, oldv = -2.0;
-      int it = 0;
-      bool dead = false;
-      while ( newv - oldv > par.convtol && it < par.maxit )
-      {
-         oldv = newv;
-         const double w = u;
-         /* The truncation: entry i stays when fewer than `size` entries lie ABOVE it - j above i: |w_j| > |w_i|, or |w_j| == |w_i|
-          * and j < i.  Non-negative doubles order as their bit patterns read as signed integers (+0 is 0; a NaN lies above every
-          * number, so the order stays total, exactly `size` entries stay and the lists stay inside their arrays).  Ranking every
-          * entry among all n is n^2 comparisons on one compute unit; instead
-          *   1. every entry is ranked inside its own wavefront of 64 rows; with `size` entries above it there it cannot stay.  The
-          *      others are the CANDIDATES, at most `size` per wavefront, listed in index order (ballot and the counts of the
-          *      wavefronts before, as for the support);
-          *   2. a candidate is ranked among the candidates alone.  That decides exactly as the full ranking: the `size` entries
-          *      that stay have fewer than `size` entries above them in their wavefront too, so all of them are candidates, and
-          *      they lie above every entry that does not stay; an entry that stays has fewer than `size` entries above it at all.
-          * In the list the order of the positions is the order of the indices: the tie rule reads the positions. */
-         const long long key = __double_as_longlong(fabs(w));
-         if ( row )
-            keys[tid] = key;
-         __syncthreads();
-         bool cand = row;
-         if ( prune )
-         {
-            const long long* kw = keys + (wave << 6);
-            int loc = 0;
-#pragma unroll 4
-            for (int j = 0; j < 64; j += 2)
-            {
-               const longlong2 a = *reinterpret_cast<const longlong2*>(kw + j);
-               loc += (int) (a.x > key) | ((int) (a.x == key) & (int) (j < lane));
-               loc += (int) (a.y > key) | ((int) (a.y == key) & (int) (j + 1 < lane));
-            }
-            cand = row && loc < size;
-         }
-         const unsigned long long cmask = __ballot(cand);
-         if ( lane == 0 )
-            wcand[wave] = __popcll(cmask);
-         __syncthreads();
-         int cpos = __popcll(cmask & ((1ull << lane) - 1ull)), ncand = 0;
-#pragma unroll
-         for (int v = 0; v < SCL_NW; ++v)
-         {
-            cpos += v < wave ? wcand[v] : 0;
-            ncand += wcand[v];
-         }
-         if ( cand )
-            ckey[cpos] = key;
-         if ( tid == 0 )
-            ckey[ncand] = -1;              /* (the list is read in pairs) */
-         __syncthreads();
-         int above = 0;
-         if ( cand )
-         {
-#pragma unroll 4
-            for (int j = 0; j < ncand; j += 2)
-            {
-               const longlong2 a = *reinterpret_cast<const longlong2*>(ckey + j);
-               above += (int) (a.x > key) | ((int) (a.x == key) & (int) (j < cpos));
-               above += (int) (a.y > key) | ((int) (a.y == key) & (int) (j + 1 < cpos));
-            }
-         }
-         const bool kept = cand && above < size;
-         const unsigned long long mask = __ballot(kept);
-         const int before = __popcll(mask & ((1ull << lane) - 1ull));
-         if ( lane == 0 )
-            wkept[wave] = __popcll(mask);
-         const double nrm = sqrt(scl_block_sum(kept ? w * w : 0.0, red));
-         if ( nrm == 0.0 )
-         {
-            dead = true;
-            break;
-         }
-         int pos = before;
-         for (int v = 0; v < wave; ++v)
-            pos += wkept[v];
-         x = kept ? w / nrm : 0.0;
-         if ( kept )
-         {
-            sup[pos] = tid;
-            xc[pos] = x;
-         }
-         __syncthreads();
-         u = row ? scl_row_product<true>(mcol, n, xc, sup, size) : 0.0;
-         newv = scl_block_sum(x * u, red);
-         ++it;
-      }
-      iters += it;
-      if ( dead )
-      {
-         flags |= 2;
-         break;
-      }
-      if ( it == 0 )             /* (convtol >= 1: no iterate, no support) */
-         break;
-      if ( it >= par.maxit && newv - oldv > par.convtol )
-         flags |= 1;
-      const double scalar = maxeig - newv;
-      if ( !(scalar < -par.feastol) || nc >= par.maxcuts )
-         break;
-      /* ---- cut nc: its value, the dense vector, the ascending support; then Z -= scalar x x^T (its support only) and
-       *      maxeig -= scalar: M's entries off the diagonal gain scalar x_r x_c, its diagonal is formed again ---- */
-      if ( tid == 0 )
-         out.eig[nc] = scalar;
-      if ( row )
-         out.vec[(long long) nc * n + tid] = x;
-      if ( tid < size )
-         out.sup[(long long) nc * out.smax + tid] = sup[tid];
-      for (int e = tid; e < size * size; e += SCL_NT)
-      {
-         const int p = e / size, q = e - p * size;
-         const double t = scalar * xc[p] * xc[q];
-         if ( p == q )
-            zd[sup[p]] -= t;
-         else
-            MT[(size_t) sup[q] * n + sup[p]] += t;
-      }
-      maxeig -= scalar;
-      SCL_STORES_DONE();
-      __syncthreads();
-      if ( row )
-         MT[(size_t) tid * n + tid] = maxeig - zd[tid];
-      ++nc;
-   }
-   if ( tid == 0 )
-   {
-      out.ncuts[0] = nc; out.iters[0] = iters; out.flags[0] = flags;
-      out.lmin[0] = lmin;
-   }
+   SCL_LDS_DECL(L);
+   scl_tpower_loop(n, size, Z, plmin[0], pmaxeig[0], v0, MT, par, out, L);
 }
 
-/* k_sc_coefs with room for 512 rows: the support and the values of a cut (a block kept as nonzeros: the dense vector) in LDS */
+/* k_sc_coefs with room for 512 rows: scl_coefs_block for matrix blockIdx.x of the one block */
 __global__ void __launch_bounds__(SCL_CT) k_sc_coefs_large(int m, int maxcuts, int size, const hs_ec_job* __restrict__ jobs, hs_sc_out out)
 {
    __shared__ double xs[HS_SCL_MAXN];
    __shared__ int sup[HS_SCL_MAXN];
    __shared__ double part[SCL_CT / 64];
-   const hs_ec_job job = jobs[0];
-   const int n = job.n, i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   const int nc = out.ncuts[0];
-   if ( nc <= 0 || nc > maxcuts || size > n || size < 1 || n > HS_SCL_MAXN )
-      return;
-   const bool walk = job.form == HS_EC_SPARSE && i > 0;       /* (the constant matrix of a sparse block is its dense row 0) */
-   const double* __restrict__ a = job.A + (walk ? 0LL : (long long) i * job.ld);
-   const int np = size * (size + 1) / 2;
-   for (int c = 0; c < nc; ++c)
-   {
-      const double* __restrict__ v = out.vec + (long long) c * n;
-      if ( walk )
-      {
-         for (int t = tid; t < n; t += SCL_CT)
-            xs[t] = v[t];
-      }
-      else
-      {
-         for (int t = tid; t < size; t += SCL_CT)
-         {
-            const int s = out.sup[(long long) c * out.smax + t];
-            sup[t] = s;
-            xs[t] = v[s];
-         }
-      }
-      __syncthreads();
-      double acc = 0.0;
-      if ( walk )
-      {
-         for (int e = job.sp.voff[i - 1] + tid; e < job.sp.voff[i]; e += SCL_CT)
-         {
-            const int r = job.sp.vrow[e], q = job.sp.vcol[e];
-            acc += (r == q ? 1.0 : 2.0) * job.sp.vval[e] * xs[r] * xs[q];
-         }
-      }
-      else
-      {
-         for (int t = tid; t < np; t += SCL_CT)
-         {
-            int p = (int) ((sqrt(8.0 * (double) t + 1.0) - 1.0) * 0.5);
-            while ( p * (p + 1) / 2 > t ) --p;
-            while ( (p + 1) * (p + 2) / 2 <= t ) ++p;
-            const int q = t - p * (p + 1) / 2;
-            const int r = sup[p], s = sup[q];                    /* s <= r: the list ascends */
-            const long long at = job.form == HS_EC_PACKED ? (long long) r * (r + 1) / 2 + s : (long long) r * n + s;
-            acc += (p == q ? 1.0 : 2.0) * a[at] * xs[p] * xs[q];
-         }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1)
-         acc += __shfl_xor(acc, off, 64);
-      if ( lane == 0 )
-         part[wave] = acc;
-      __syncthreads();
-      if ( tid == 0 )
-      {
-         double t = 0.0;
-         for (int w = 0; w < SCL_CT / 64; ++w)
-            t += part[w];
-         if ( i == 0 )
-            out.lhs[c] = t;
-         else
-            out.coef[(long long) c * m + (i - 1)] = t;
-      }
-      __syncthreads();
-   }
+   scl_coefs_block(m, maxcuts, size, (int) blockIdx.x, jobs[0], out, xs, sup, part);
 }
 
 int hs_scl_tpower(hipStream_t st, int n, int size, const double* Z, const double* lmin, const double* maxeig, const double* v0, double* MT,
