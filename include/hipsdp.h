@@ -290,7 +290,8 @@ HIPSDP_API int  hipsdp_eigencuts(hipsdp_solver* solver, int block, const double*
  * Blocks of at most 128 rows of a solver without communicator and without sharded matrices are BATCHED: whatever their number
  * and the number of cuts, the call issues one upload of y, one launch that forms all Z_b(y), at most three launches for the
  * decompositions, one for the selection and all coefficients, and one read-back (csrc/eigcuts.hip).  Every other block is served
- * inside the same call the way hipsdp_eigencuts serves it.  Two host threads may call it at the same time on different solvers. */
+ * inside the same call the way hipsdp_eigencuts serves it (hipsdp_eigencuts_all_large, below, batches the blocks of 129 .. 512 rows of
+ * a solver that is asked for them there).  Two host threads may call it at the same time on different solvers. */
 HIPSDP_API int hipsdp_eigencuts_all(hipsdp_solver* solver, const double* y, double tol, int maxcuts, int* ncuts, double* lmin,
                                     double* eigvals, double* coefs, double* lhs, double* vecs);
 /* process totals: calls, kernel launches those calls issued for batched blocks, device->host synchronisations they waited on */
@@ -420,6 +421,40 @@ HIPSDP_API int hipsdp_sparsecuts_all_large(hipsdp_solver* solver, const double* 
 /* process totals of hipsdp_sparsecuts_all_large alone: calls that served a block, kernel launches they issued, device->host
  * synchronisations they waited on (one per chunk); the totals of the other three sparse-cut stats calls do not move, and the reverse */
 HIPSDP_API int hipsdp_sparsecuts_all_large_stats(long long* calls, long long* launches, long long* readbacks);
+
+/* The partner of hipsdp_eigencuts_all for the blocks of 129 .. 512 rows, which that call serves one after the other with a full
+ * decomposition each: the DENSE eigenvector cuts (the default separation mode of cons_sdp.c) and the feasibility eigenvalue of ALL such
+ * blocks of a solver per launch, from the wanted eigenpairs alone.  Arguments, output layout, the NULL rules (lmin and vecs may be NULL;
+ * with maxcuts == 0 also eigvals, coefs, lhs), "slots c >= ncuts[b] are not written" and maxcuts == 0 as a pure feasibility check
+ * (ncuts = 0 and lmin of every served block) are those of hipsdp_eigencuts_all; the selection is the rule of hipsdp_eigencuts:
+ * eigenvalue <= -tol, most negative first, at most maxcuts.
+ * Served: blocks of 129 .. 512 rows of a solver without communicator and without sharded matrices, in all three storage forms.
+ * ncuts[b] = -1 and nothing else written, lmin[b] included: a block of at most 128 rows (hipsdp_eigencuts_all batches it) and a block of
+ * more than 512 rows.  The other blocks are still served.  A solver with a communicator or sharded matrices: every ncuts = -1, nothing
+ * launched; a call with no served block launches nothing and leaves the totals unchanged.
+ * HIPSDP_ERR_ARG, before the device is looked at: solver NULL or without a shape, y or ncuts NULL, maxcuts < 0 or maxcuts >
+ * HIPSDP_EIGENCUTS_LARGE_MAXCUTS, maxcuts > 0 with eigvals, coefs or lhs NULL.
+ * lmin[b] is eigenvalue 1 of Z_b(y) with the accuracy of hipsdp_syevx; when ncuts[b] > 0 it is eigvals slot (b, 0) bit for bit.
+ * The device side (csrc/eigcuts_large.hip, csrc/syevx.hip): Z_b(y) of the served blocks formed straight into the matrices of the
+ * batched tridiagonalisation and their reflector arrays cleared (2 launches), nmax - 1 column launches that hold the matrices of all
+ * blocks (nmax: rows of the largest served block), one launch for eigenvalue 1 and the eigenvalues <= -tol of every block, with
+ * maxcuts > 0 one for their eigenvectors of the tridiagonal matrices and one for the back-transformation, and one launch that stores
+ * counts and lmin and sweeps every A_i once for all cuts of its block.  Kernel launches of a call:
+ *     2 + (nmax - 1) + 1 + 2 [maxcuts > 0] + 1   =   nmax + 3 + 2 [maxcuts > 0]
+ * - a function of nmax and of maxcuts > 0 alone, whatever the number of blocks and cuts -, one upload and ONE read-back.
+ * A block takes about 2 n^2 + 165 n doubles of the solver's cut workspace (4.9 MB at 512 rows): the blocks are ordered by descending n
+ * and run in chunks of at most 512 MiB (HIPSDP_EIGENCUTS_LARGE_CHUNK in the environment, read at every call: blocks per chunk instead),
+ * and every chunk is a call of its own in launches and read-backs (nmax: the chunk's largest block).
+ * The bits of a block depend on the block, y, tol and maxcuts alone - not on the other blocks, their order or the chunks; same input,
+ * same bits.  Two host threads may call it at the same time on different solvers. */
+#define HIPSDP_EIGENCUTS_LARGE_MAXN    512     /* = HIPSDP_SPARSECUTS_MAXN */
+#define HIPSDP_EIGENCUTS_LARGE_MAXCUTS 32      /* = the most pairs hipsdp_syevx returns */
+HIPSDP_API int hipsdp_eigencuts_all_large(hipsdp_solver* solver, const double* y, double tol, int maxcuts, int* ncuts, double* lmin,
+                                          double* eigvals, double* coefs, double* lhs, double* vecs);
+/* process totals of hipsdp_eigencuts_all_large alone: calls that served a block, kernel launches they issued, device->host
+ * synchronisations they waited on (one per chunk); the totals of hipsdp_eigencuts_all and of the sparse-cut calls do not move, and the
+ * reverse */
+HIPSDP_API int hipsdp_eigencuts_all_large_stats(long long* calls, long long* launches, long long* readbacks);
 
 /* All one-variable SDPs of a block in one call: the bound-tightening loops of cons_sdp.c - tightenBounds (:1968-2201) and
  * tightenMatrices (:1856-1961) solve one SDP PER VARIABLE of a block, each the semismooth Newton method of

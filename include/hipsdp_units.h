@@ -168,6 +168,14 @@ HIPSDP_API int  hipsdp_sparsecuts_unit(int device, int count, const int* ns, con
  * vecs[maxcuts x n], *iters, *flags as hipsdp_sparsecuts returns them; slots c >= *ncuts are not written. */
 HIPSDP_API int  hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, const double* v0, double maxeig, int size,
    const hipsdp_sparsecut_opts* opts, int* ncuts, double* eigvals, double* vecs, int* iters, int* flags);
+/* the batched selection of SEVERAL eigenpairs behind hipsdp_eigencuts_all_large (hs_syevx_many_below, csrc/syevx.hip) on `count` host
+ * matrices of mixed sizes, one behind the other in A (matrix j: n[j] x n[j], 2 <= n[j] <= 512, read as hipsdp_syevx_below reads it):
+ * through the staging of that call, the column launches with at most cap (1 .. 128) workgroups per matrix and the selection of the
+ * eigenvalues <= bound, at most maxk <= 32.  cnt[j]: pairs returned, lam + j maxk: their eigenvalues (ascending), V + maxk (n[0] + ... +
+ * n[j - 1]): their unit vectors, row k of n[j] values (V may be NULL) - for every matrix the bits of hipsdp_syevx_below on it alone,
+ * whatever cap is.  Entries behind cnt[j] are not written. */
+HIPSDP_API int  hipsdp_syevx_many_below_unit(int device, int count, const int* n, const double* A, double bound, int maxk, int cap, int* cnt,
+   double* lam, double* V);
 /* the first stage of hipsdp_syevx alone, 2 <= n <= 512: the tridiagonal matrix Q^T A Q (d[n], e[n - 1] in e[0 .. n - 2], e[n - 1] = 0)
  * and Q = H_0 H_1 ... H_{n-2}, H_j = I - tau[j] v_j v_j^T, row j of Vrefl (n x n) = v_j (zeros up to entry j, entry j + 1 one) */
 HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau);

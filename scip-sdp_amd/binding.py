@@ -408,6 +408,37 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's eigencuts_all_stats()"""
         return eigencuts_all_stats()
 
+    def eigencuts_all_large(self, y, tol, maxcuts):
+        """the partner of eigencuts_all for the blocks of 129 .. 512 rows (hipsdp_eigencuts_all_large): their dense eigenvector cuts
+        and feasibility eigenvalues in one call; per block a tuple (lmin, eigvals[k], coefs[k, m], lhs[k], vecs[k, n]) as
+        eigencuts_all returns it, or None for a block that came back with -1 (at most 128 or more than 512 rows)"""
+        y = _f64(y)
+        m, nb, mc = len(y), len(self.ns), max(1, maxcuts)
+        k = np.zeros(max(1, nb), dtype=np.int32)
+        lmin = np.full(max(1, nb), np.nan)
+        ev = np.zeros(max(1, nb) * mc)
+        co = np.zeros(max(1, nb) * mc * max(1, m))
+        lh = np.zeros(max(1, nb) * mc)
+        ve = np.zeros(max(1, maxcuts * sum(self.ns)))
+        _chk(self._l().hipsdp_eigencuts_all_large(self.h, _dp(y), C.c_double(tol), int(maxcuts), _ip(k), _dp(lmin), _dp(ev), _dp(co), _dp(lh),
+                                                  _dp(ve)), "hipsdp_eigencuts_all_large")
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            kb = int(k[b])
+            if kb < 0:
+                out.append(None)
+            else:
+                s0 = b * maxcuts
+                out.append((float(lmin[b]), ev[s0:s0 + kb].copy(), co[s0 * m:(s0 + kb) * m].reshape(kb, m).copy(), lh[s0:s0 + kb].copy(),
+                            ve[off:off + kb * n].reshape(kb, n).copy()))
+            off += maxcuts * n
+        return out
+
+    @staticmethod
+    def eigencuts_all_large_stats():
+        """process totals (calls, launches, read-backs): the module's eigencuts_all_large_stats()"""
+        return eigencuts_all_large_stats()
+
     def sparsecuts_all(self, y, sizes, tol, feastol, maxcuts, convtol=0, maxit=0):
         """sparse eigenvector cuts of all blocks in one call (hipsdp_sparsecuts_all; sizes[b]: target sparsity of block b): per block
         a tuple (ncuts, lmin, eigvals[k], coefs[k, m], lhs[k], vecs[k, n], iters, flags); ncuts = -1: the block is not served (then
@@ -815,6 +846,38 @@ def eigencuts_all_stats():
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_eigencuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_stats")
     return calls.value, launches.value, readbacks.value
+
+
+def eigencuts_all_large_stats():
+    """process totals of hipsdp_eigencuts_all_large: (calls that served a block, kernel launches issued, device->host
+    synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_eigencuts_all_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_large_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def syevx_many_below_unit(mats, bound, maxk, cap, device=0):
+    """the batched selection behind hipsdp_eigencuts_all_large on host matrices of mixed sizes (hipsdp_syevx_many_below_unit of the
+    units library): the eigenvalues <= bound of every matrix, at most maxk, through column launches of at most cap workgroups per
+    matrix; per matrix (count, lam[count], V[count, n])"""
+    mats = [np.asarray(a, dtype=np.float64) for a in mats]
+    ns = np.ascontiguousarray([a.shape[0] for a in mats], dtype=np.int32)
+    assert all(a.shape == (n, n) for a, n in zip(mats, ns))
+    cat = _f64(np.concatenate([a.reshape(-1) for a in mats]))
+    cnt = np.full(len(mats), -1, dtype=np.int32)
+    mk = max(1, int(maxk))
+    lam = np.zeros(len(mats) * mk)
+    V = np.zeros(mk * int(sum(ns)))
+    rc = ulib().hipsdp_syevx_many_below_unit(device, len(mats), _ip(ns), _dp(cat), C.c_double(bound), int(maxk), int(cap), _ip(cnt), _dp(lam),
+                                             _dp(V))
+    if rc != 0:
+        raise RuntimeError("hipsdp_syevx_many_below_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    out, off = [], 0
+    for j, n in enumerate(ns):
+        kj = int(cnt[j])
+        out.append((kj, lam[j * maxk:j * maxk + kj].copy(), V[off:off + kj * n].reshape(kj, n).copy()))
+        off += maxk * int(n)
+    return out
 
 
 # ---- unit-level host-buffer kernels ---------------------------------------------------------------------------------

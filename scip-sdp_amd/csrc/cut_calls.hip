@@ -1,7 +1,8 @@
 /* cut_calls.hip - the host side of the cut calls that serve many blocks, or one large block, in a fixed number of launches:
  * hipsdp_eigencuts_all (kernels: eigcuts.hip, many-forms of the decompositions: eigi.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts
  * (sparsecuts.hip, sparsecuts_large.hip), their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip), and
- * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip).
+ * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip),
+ * and hipsdp_eigencuts_all_large, the partner of hipsdp_eigencuts_all for those blocks (eigcuts_large.hip).
  *
  * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
  * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
@@ -20,8 +21,9 @@
 
 namespace {
 
-/* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, the two _ex calls with a switch set, hipsdp_sparsecuts_all_large */
-CutStats g_ec, g_sc, g_sc1, g_scx, g_scl;
+/* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, the two _ex calls with a switch set, hipsdp_sparsecuts_all_large,
+ * hipsdp_eigencuts_all_large */
+CutStats g_ec, g_sc, g_sc1, g_scx, g_scl, g_ecl;
 
 /* the caller's arrays of a call, or of one block of it (all but ncuts may be NULL) */
 struct CutDst
@@ -607,6 +609,128 @@ int sparsecuts_impl(hipsdp_solver* s, int block, const double* y, int size, cons
    return HIPSDP_OK;
 }
 
+/* ---- hipsdp_eigencuts_all_large: the dense cuts of all blocks of 129 .. 512 rows per launch (kernels: eigcuts_large.hip, syevx.hip) ---- */
+hs_ecl_block ecl_block(int n)
+{
+   return hs_ecl_block_make((long long) hs_syevx_ws(n), HS_SXB_OUT(n));
+}
+
+/* ONE CHUNK: the served blocks `ids` (descending n) of a solver with nb blocks - its layout of the workspace (hs_ecl_layout), ONE upload
+ * of  y | the table | vecoff | act,  hs_ecl_launches(maxcuts, nmax) launches whatever the blocks and their counts are, ONE read-back, the
+ * copy-out.  gvecoff: where a block's vectors start in the caller's array. */
+int ecl_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const double* y, double tol, int maxcuts, const CutDst& d,
+   const std::vector<long long>& gvecoff)
+{
+   const int cnt = (int) ids.size();
+   /* the chunk's result: indexed by the block's number, vectors of the chunk's blocks alone */
+   std::vector<long long> vecoff((size_t) nb + 1, 0);
+   {
+      std::vector<char> in((size_t) nb, 0);
+      for (int b : ids)
+         in[b] = 1;
+      for (int b = 0; b < nb; ++b)
+         vecoff[b + 1] = vecoff[b] + (in[b] ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
+   }
+   int nmax = 0;
+   long long blocks_len = 0;
+   std::vector<hs_ecl_block> B((size_t) cnt);
+   std::vector<long long> start((size_t) cnt), zoff((size_t) cnt);
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int n = hs_solver_block_n(s, ids[j]);
+      nmax = n > nmax ? n : nmax;
+      B[j] = ecl_block(n);
+      start[j] = blocks_len;
+      blocks_len += B[j].len;
+   }
+   hs_ecl_layout L;
+   hs_ecl_layout_make(nb, m, maxcuts, vecoff[nb], cnt, SCLR_JOBW, blocks_len, &L);
+   /* Z(y) of a block goes where the column launches read their matrix: the head of the block's workspace (hs_sxm_job.A) */
+   for (int j = 0; j < cnt; ++j)
+      zoff[j] = L.blocks + start[j] + B[j].ws;
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_blocks(s, ids, zoff, L.len.dev_len, L.len.pin_len, &w) );
+   hipStream_t st = w.stream;
+   if ( m > 0 )
+      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+   hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
+   long long* hvo = reinterpret_cast<long long*>(w.pin + L.vecoff);
+   int* hact = reinterpret_cast<int*>(w.pin + L.act);
+   for (int j = 0; j < cnt; ++j)
+   {
+      double* base = w.dev + L.blocks + start[j];
+      HS_CALL( hs_syevx_many_below_job(hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, &hsx[j]) );
+      if ( hsx[j].A != w.dev + zoff[j] )
+         return HIPSDP_ERR_NUMERIC;
+      hvo[j] = vecoff[ids[j]];
+      hact[j] = HS_SXM_ACTIVE;
+   }
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+
+   const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
+   const long long* dvo = reinterpret_cast<const long long*>(w.dev + L.vecoff);
+   const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
+   const hs_sc_out out = hs_cut_view(L.r, w.dev);
+   int launches = 0;
+   HS_CALL( hs_ec_form_z(st, cnt, nmax, m, w.djobs, w.dev + L.y) );
+   HS_CALL( hs_ecl_clear(st, cnt, dsx) );
+   launches += 2;
+   HS_CALL( hs_syevx_many_cols(st, cnt, nmax, sclr_cap(cnt), dsx, dact) );
+   launches += nmax - 1;
+   /* eigenvalue <= -tol, most negative first, at most maxcuts: the count of the selection is the number of cuts */
+   HS_CALL( hs_syevx_many_below(st, cnt, nmax, -tol, maxcuts, dsx, dact) );
+   launches += maxcuts > 0 ? 3 : 1;
+   HS_CALL( hs_ecl_cuts(st, cnt, nmax, m, maxcuts, w.djobs, dsx, dvo, &out) );
+   ++launches;
+   HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   g_ecl.launches += launches;
+   g_ecl.readbacks += 1;
+   const hs_sc_out h = hs_cut_view(L.r, w.pin);
+   for (int b : ids)
+      HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, gvecoff[b])) );
+   return HIPSDP_OK;
+}
+
+int eigencuts_all_large_impl(hipsdp_solver* s, const double* y, double tol, int maxcuts, const CutDst& d)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || d.ncuts == NULL || maxcuts < 0 || maxcuts > HIPSDP_EIGENCUTS_LARGE_MAXCUTS )
+      return HIPSDP_ERR_ARG;
+   if ( maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      d.ncuts[b] = -1;
+   /* the blocks this call serves: whole matrices on this device (none for a solver with a communicator or sharded matrices), 129 .. 512
+    * rows */
+   std::vector<int> all, ids;
+   HS_CALL( hs_solver_cut_enter_large(s, HIPSDP_EIGENCUTS_LARGE_MAXN, &all) );
+   for (int b : all)
+      if ( hs_solver_block_n(s, b) > HS_SC_MAXN )
+         ids.push_back(b);
+   if ( ids.empty() )
+      return HIPSDP_OK;
+   std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
+   const int total = (int) ids.size();
+   std::vector<long long> job_len((size_t) total);
+   for (int k = 0; k < total; ++k)
+      job_len[k] = ecl_block(hs_solver_block_n(s, ids[k])).len;
+   int maxjobs = 0;
+   const char* env = getenv("HIPSDP_EIGENCUTS_LARGE_CHUNK");           /* (read at every call, like HIPSDP_SPARSECUTS_LARGE_CHUNK) */
+   if ( env != NULL && atoi(env) > 0 )
+      maxjobs = atoi(env);
+   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts, -1);
+   for (int start = 0; start < total; )
+   {
+      const int end = hs_ovl_chunk_end(job_len.data(), total, start, maxjobs > 0 ? std::numeric_limits<long long>::max() / 2 : SCLR_BUDGET, maxjobs);
+      const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
+      HS_CALL( ecl_chunk(s, m, nb, chunk, y, tol, maxcuts, d, gvecoff) );
+      start = end;
+   }
+   ++g_ecl.calls;
+   return HIPSDP_OK;
+}
+
 }
 
 extern "C" int hipsdp_eigencuts_all_stats(long long* calls, long long* launches, long long* readbacks)
@@ -632,6 +756,11 @@ extern "C" int hipsdp_sparsecuts_ex_stats(long long* calls, long long* launches,
 extern "C" int hipsdp_sparsecuts_all_large_stats(long long* calls, long long* launches, long long* readbacks)
 {
    return g_scl.get(calls, launches, readbacks);
+}
+
+extern "C" int hipsdp_eigencuts_all_large_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_ecl.get(calls, launches, readbacks);
 }
 
 extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
@@ -735,4 +864,10 @@ extern "C" int hipsdp_sparsecuts_all_large(hipsdp_solver* s, const double* y, co
    if ( !variant_ok(variant) )
       return HIPSDP_ERR_ARG;
    return sparsecuts_all_large_impl(s, y, sizes, opts, variant, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, iters, flags});
+}
+
+extern "C" int hipsdp_eigencuts_all_large(hipsdp_solver* s, const double* y, double tol, int maxcuts, int* ncuts, double* lmin, double* eigvals,
+   double* coefs, double* lhs, double* vecs)
+{
+   return eigencuts_all_large_impl(s, y, tol, maxcuts, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, NULL, NULL});
 }

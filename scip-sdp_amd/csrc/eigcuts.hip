@@ -18,9 +18,7 @@
  * bits.  The three storage forms of a block (dense rows, packed lower triangles, nonzeros) are the three branches below; the
  * packed and the sparse form count an off-diagonal entry twice, as hs_pack_weighted and cons_sdp.c:826-865 do. */
 #include "hs_kernels.h"
-
-#define EC_NT 256
-#define EC_CH 8            /* cuts swept together (accumulators in registers); more cuts of a block: further sweeps out of L2 */
+#include "hs_ec_sweep.h"         /* EC_NT, EC_CH, ec_sweep, ec_sweep_store: shared with eigcuts_large.hip */
 
 /* index of the position (r, c), c <= r, in the list sorted by (row, column), or -1 */
 __device__ __forceinline__ long long ec_find_pos(const hs_sp_view& sp, int r, int c)
@@ -69,63 +67,13 @@ __global__ void __launch_bounds__(EC_NT) k_ec_form_z(int m, const hs_ec_job* __r
    job.Z[e] = acc;
 }
 
-/* partial sums of one sweep: v_c^T A v_c for the cuts c0 .. c0 + EC_CH - 1 (those below k) over the entries this thread visits */
-template<int FORM>
-__device__ __forceinline__ void ec_sweep(const hs_ec_job& job, int i, int n, int k, int c0, const double* vs, double* acc)
-{
-   const int tid = threadIdx.x;
-   if ( FORM == HS_EC_DENSE )
-   {
-      const double* __restrict__ a = job.A + (long long) i * job.ld;
-      for (int e = tid; e < n * n; e += EC_NT)
-      {
-         const int r = e / n, c = e - r * n;
-         const double av = a[e];
-#pragma unroll
-         for (int u = 0; u < EC_CH; ++u)
-            if ( c0 + u < k )
-               acc[u] += av * vs[(c0 + u) * n + r] * vs[(c0 + u) * n + c];
-      }
-   }
-   else if ( FORM == HS_EC_PACKED )
-   {
-      const double* __restrict__ a = job.A + (long long) i * job.ld;
-      const int np = n * (n + 1) / 2;
-      for (int p = tid; p < np; p += EC_NT)
-      {
-         int r = (int) ((sqrt(8.0 * (double) p + 1.0) - 1.0) * 0.5);
-         while ( r * (r + 1) / 2 > p ) --r;
-         while ( (r + 1) * (r + 2) / 2 <= p ) ++r;
-         const int c = p - r * (r + 1) / 2;
-         const double av = (r == c ? 1.0 : 2.0) * a[p];
-#pragma unroll
-         for (int u = 0; u < EC_CH; ++u)
-            if ( c0 + u < k )
-               acc[u] += av * vs[(c0 + u) * n + r] * vs[(c0 + u) * n + c];
-      }
-   }
-   else
-   {
-      /* variable i >= 1: its lower-triangular nonzeros */
-      for (int e = job.sp.voff[i - 1] + tid; e < job.sp.voff[i]; e += EC_NT)
-      {
-         const int r = job.sp.vrow[e], c = job.sp.vcol[e];
-         const double av = (r == c ? 1.0 : 2.0) * job.sp.vval[e];
-#pragma unroll
-         for (int u = 0; u < EC_CH; ++u)
-            if ( c0 + u < k )
-               acc[u] += av * vs[(c0 + u) * n + r] * vs[(c0 + u) * n + c];
-      }
-   }
-}
-
 __global__ void __launch_bounds__(EC_NT) k_ec_cuts(int m, int nb, int maxcuts, double tol, const hs_ec_job* __restrict__ jobs,
    double* __restrict__ res)
 {
    extern __shared__ __attribute__((aligned(16))) double ec_vs[];
    __shared__ double part[EC_NT / 64][EC_CH];
    const hs_ec_job job = jobs[blockIdx.y];
-   const int n = job.n, i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int n = job.n, i = blockIdx.x, tid = threadIdx.x;
    const double* __restrict__ lam = job.ws;
    const double* __restrict__ V = job.ws + job.vpos;
    /* the selection rule of hipsdp_eigencuts: eigenvalue <= -tol, most negative first, at most maxcuts (every thread, same answer) */
@@ -156,41 +104,7 @@ __global__ void __launch_bounds__(EC_NT) k_ec_cuts(int m, int nb, int maxcuts, d
    for (int e = tid; e < k * n; e += EC_NT)
       ec_vs[e] = V[e];
    __syncthreads();
-   for (int c0 = 0; c0 < k; c0 += EC_CH)
-   {
-      double acc[EC_CH];
-#pragma unroll
-      for (int u = 0; u < EC_CH; ++u)
-         acc[u] = 0.0;
-      if ( job.form == HS_EC_PACKED )
-         ec_sweep<HS_EC_PACKED>(job, i, n, k, c0, ec_vs, acc);
-      else if ( job.form == HS_EC_SPARSE && i > 0 )
-         ec_sweep<HS_EC_SPARSE>(job, i, n, k, c0, ec_vs, acc);
-      else
-         ec_sweep<HS_EC_DENSE>(job, i, n, k, c0, ec_vs, acc);      /* (the constant matrix of a sparse block is its dense row 0) */
-#pragma unroll
-      for (int u = 0; u < EC_CH; ++u)
-      {
-         double a = acc[u];
-#pragma unroll
-         for (int off = 32; off > 0; off >>= 1)
-            a += __shfl_xor(a, off, 64);
-         if ( lane == 0 )
-            part[wave][u] = a;
-      }
-      __syncthreads();
-      if ( tid < EC_CH && c0 + tid < k )
-      {
-         double t = 0.0;
-         for (int w = 0; w < EC_NT / 64; ++w)
-            t += part[w][tid];
-         if ( i == 0 )
-            r_lhs[slot0 + c0 + tid] = t;
-         else
-            r_coef[(slot0 + c0 + tid) * m + (i - 1)] = t;
-      }
-      __syncthreads();
-   }
+   ec_sweep_store(job, i, n, k, m, slot0, ec_vs, part, r_lhs, r_coef);
 }
 
 int hs_ec_form_z(hipStream_t st, int count, int nmax, int m, const hs_ec_job* jobs, const double* y)

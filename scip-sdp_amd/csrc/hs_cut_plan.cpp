@@ -132,6 +132,29 @@ void hs_sclr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len
    L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->blocks + blocks_len;
 }
 
+hs_ecl_block hs_ecl_block_make(long long ws_len, long long out_len)
+{
+   hs_ecl_block B;
+   B.ws = 0;
+   B.out = even(ws_len);
+   B.len = B.out + even(out_len);
+   return B;
+}
+
+void hs_ecl_layout_make(int nb, int m, int maxcuts, long long vec_len, int count, int jobw, long long blocks_len, hs_ecl_layout* L)
+{
+   L->y = 0;
+   L->jobs = even(m);
+   L->vecoff = L->jobs + even((long long) count * jobw);
+   L->act = L->vecoff + even(count);
+   L->len.res_off = L->act + even(((long long) count + 1) / 2);
+   L->r.ints = even(res_arrays(L->len.res_off, nb, m, maxcuts, vec_len, &L->r));
+   L->r.sup = L->r.ints + even((3LL * nb + 1) / 2);            /* (no supports: where the result ends) */
+   L->blocks = L->r.sup;
+   L->len.res_len = L->r.sup - L->len.res_off;
+   L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->blocks + blocks_len;
+}
+
 int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs)
 {
    long long used = 0;

@@ -111,6 +111,28 @@ static inline long long hs_sclr_launches(unsigned variant, int maxcuts, int nmax
    return 1 + ((long long) nmax + 3) + rounds * (1 + 4 * s + (long long) d * (nmax + 3)) + 1 + (maxcuts > 0 ? 1 : 0);
 }
 
+/* hipsdp_eigencuts_all_large (csrc/eigcuts_large.hip), ONE CHUNK of `count` served blocks of a solver with nb blocks:
+ *    y[m] | tridiagonal jobs [count][jobw] | vecoff[count] (long long) | act[count] (int)
+ *    | res (the arrays of hs_cut_res over nb blocks: lmin, eig, lhs, coef, vec, then the ints ncuts, iters, flags)
+ *    | per served block (hs_ecl_block): workspace of the tridiagonal form (its head is the matrix Z(y) is formed into) | its selection
+ *    output
+ * every part starts at an even offset.  The tables stand in front of the result: ONE upload (everything before res) carries y and the
+ * tables, ONE read-back takes res, and the pinned mirror ends behind the result's ints. */
+struct hs_ecl_layout { long long y, jobs, vecoff, act; hs_cut_res r; long long blocks; hs_cut_lens len; };
+/* a served block, as offsets from the block's start: ws_len = hs_syevx_ws(n), out_len = HS_SXB_OUT(n), passed in as numbers; len: where
+ * the next block starts */
+struct hs_ecl_block { long long ws, out, len; };
+hs_ecl_block hs_ecl_block_make(long long ws_len, long long out_len);
+/* jobw: doubles of a row of the job table; vec_len: maxcuts * rows of the chunk's blocks; blocks_len: sum of hs_ecl_block_make(..).len */
+void hs_ecl_layout_make(int nb, int m, int maxcuts, long long vec_len, int count, int jobw, long long blocks_len, hs_ecl_layout* L);
+/* kernel launches of one chunk of hipsdp_eigencuts_all_large: a function of (maxcuts > 0, nmax) alone, nmax the chunk's largest block -
+ * Z(y) and the clearing of the reflector arrays; nmax - 1 columns; the values; with maxcuts > 0 the vectors of the tridiagonal
+ * matrices and their back-transformation; the launch that stores counts, lmin and, with maxcuts > 0, the coefficients */
+static inline long long hs_ecl_launches(int maxcuts, int nmax)
+{
+   return 2 + ((long long) nmax - 1) + 1 + (maxcuts > 0 ? 2 : 0) + 1;
+}
+
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
 {

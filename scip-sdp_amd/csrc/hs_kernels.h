@@ -598,6 +598,24 @@ struct hs_sxm_job { int n, pad; double* ws; double* A; double* R; double* out; d
 int hs_syevx_many_job(int n, double* ws, double* out, hs_sxm_job* J);
 int hs_syevx_many_cols(hipStream_t st, int count, int nmax, int cap, const hs_sxm_job* djobs, const int* dact);
 int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs_sxm_job* djobs, const int* dact);
+/* SEVERAL pairs per matrix on the forms hs_syevx_many_cols leaves: the eigenvalues <= bound of every matrix with act != 0, at most maxk
+ * <= HS_SYEVX_MAXK of them, ascending, with their unit vectors - to out in the layout of hs_syevx_dev (HS_SYEVX_OUT(n): pairs returned
+ * at [0], values from HS_SYEVX_OUT_LAM, vectors from HS_SYEVX_OUT_VEC) - and eigenvalue 1 by index to out2[HS_SYEVX_OUT_LAM].  The bits
+ * of a matrix are those of hs_syevx_dev(HS_SYEVX_BELOW) on it alone.  hs_syevx_many_below_job: the entry of hs_syevx_many_job with out
+ * of HS_SXB_OUT(n) doubles, out2 behind the selection.  1 launch with maxk == 0 (eigenvalue 1 alone), 3 with maxk > 0. */
+#define HS_SXB_OUT(n) (HS_SYEVX_OUT(n) + HS_SYEVX_OUT_VEC)
+int hs_syevx_many_below_job(int n, double* ws, double* out, hs_sxm_job* J);
+int hs_syevx_many_below(hipStream_t st, int count, int nmax, double bound, int maxk, const hs_sxm_job* djobs, const int* dact);
+
+/* ---- eigcuts_large.hip: the dense eigenvector cuts of ALL blocks of 129 .. 512 rows per launch (hipsdp_eigencuts_all_large) ----------------
+ * Entry j of the tables belongs to served block j: jobs[j] its hs_ec_job (.Z is sx[j].A: hs_ec_form_z writes Z(y) where the column
+ * launches consume it; .blk its index in the result), sx[j] its job of hs_syevx_many_below, vecoff[j] where its vectors start in the
+ * result.  hs_ecl_clear: zeros into the reflector array sx[j].R of every block.  hs_ecl_cuts, grid (m + 1, count) - (1, count) with
+ * maxcuts == 0 -: workgroup (i, j) takes the count and the vectors of block j from the selection, sweeps A_i once for all cuts
+ * (hs_ec_sweep.h); workgroup (0, j) also stores ncuts, lmin (eigenvalue slot 0 when there is a cut, else out2), eigenvalues, vectors. */
+int hs_ecl_clear(hipStream_t st, int count, const hs_sxm_job* sx);
+int hs_ecl_cuts(hipStream_t st, int count, int nmax, int m, int maxcuts, const hs_ec_job* jobs, const hs_sxm_job* sx, const long long* vecoff,
+   const hs_sc_out* out);
 
 /* ---- syevr.hip: ALL eigenpairs of a matrix of 2 .. 512 rows through the tridiagonal form (stage 1 is hs_syevx_tridiag_dev) --------
  * dA as for hs_syevx_dev.  dOut, HS_SYEVR_OUT(n) doubles: [k] k-th eigenvalue (ascending), [HS_SYEVR_OUT_VEC(n) + k n + i] component

@@ -27,7 +27,8 @@
  *   4. Back-transformation through the reflectors (k_syevx_back): one wavefront per vector, the reflectors read four ahead.
  * Every reduction runs in a fixed order (no floating-point atomics): the same input gives the same bits.
  * Each stage is a __device__ body (d_syevx_col, d_syevx_values, d_syevx_tvec, d_syevx_back) with two kernels around it: the one of a
- * single matrix and the one of MANY matrices per launch (k_syevx_*_many, hs_syevx_many_*: the rounds of hipsdp_onevar_bounds_large). */
+ * single matrix and the one of MANY matrices per launch (k_syevx_*_many, hs_syevx_many_*: the rounds of hipsdp_onevar_bounds_large;
+ * k_syevx_*_below_many, hs_syevx_many_below: several pairs per matrix, hipsdp_eigencuts_all_large). */
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_tridiag.h"
@@ -499,6 +500,10 @@ __global__ void __launch_bounds__(64) k_syevx_back_many(const hs_sxm_job* __rest
    d_syevx_back(n, 0, w.R, w.tau, w.Zt, jobs[job].out);
 }
 
+/* ---- the BELOW selection for many matrices per launch (k_syevx_*_below_many; host side: hs_syevx_many_below further down): wrappers of
+ * the same kind around the bodies of stages 2 to 4, kept in a file of their own */
+#include "hs_syevx_below_many.h"
+
 }
 
 size_t hs_syevx_ws(int n) { return (n < 2 || n > SX_N) ? 0 : sx_ws_doubles(n); }
@@ -537,6 +542,33 @@ int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs
    hipLaunchKernelGGL(k_syevx_values_many, dim3(count, both ? 2 : 1), dim3(SX_VT), 0, st, djobs, dact);
    hipLaunchKernelGGL(k_syevx_tvec_many, dim3(count), dim3(SX_VT), (size_t) (nmax | 1) * sizeof(double), st, djobs, dact);
    hipLaunchKernelGGL(k_syevx_back_many, dim3(count), dim3(64), 0, st, djobs, dact);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* the entry of a matrix for hs_syevx_many_below: as hs_syevx_many_job, with out = HS_SXB_OUT(n) doubles - the selection in the layout
+ * HS_SYEVX_OUT(n), and behind it the HS_SYEVX_OUT_VEC doubles of eigenvalue 1 (out2) */
+int hs_syevx_many_below_job(int n, double* ws, double* out, hs_sxm_job* J)
+{
+   HS_CALL( hs_syevx_many_job(n, ws, out, J) );
+   J->out2 = out + HS_SYEVX_OUT(n);
+   return HS_OK;
+}
+
+/* one launch for the values (a second row of workgroups for the eigenvalues below the bound when maxk > 0) and, with maxk > 0, two more:
+ * the vectors of T and their back-transformation - whatever the counts turn out to be */
+int hs_syevx_many_below(hipStream_t st, int count, int nmax, double bound, int maxk, const hs_sxm_job* djobs, const int* dact)
+{
+   if ( count < 1 || nmax < 2 || nmax > SX_N || maxk < 0 || maxk > SX_K || djobs == NULL || dact == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_syevx_values_below_many, dim3(count, maxk > 0 ? 2 : 1), dim3(SX_VT), 0, st, djobs, dact, bound, maxk);
+   if ( maxk > 0 )
+   {
+      static hs_attr_mask attr_done;
+      HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_syevx_tvec_below_many), SX_K * (SX_N + 1) * (int) sizeof(double), &attr_done) );
+      hipLaunchKernelGGL(k_syevx_tvec_below_many, dim3(count), dim3(SX_VT), (size_t) maxk * (nmax | 1) * sizeof(double), st, djobs, dact);
+      hipLaunchKernelGGL(k_syevx_back_below_many, dim3(count, maxk), dim3(64), 0, st, djobs, dact);
+   }
    HS_HIP( hipGetLastError() );
    return HS_OK;
 }

@@ -1893,6 +1893,74 @@ extern "C" int hipsdp_sparsecuts_large_unit(int device, int n, const double* Z, 
    return HIPSDP_OK;
 }
 
+/* the batched BELOW selection (hs_syevx_many_below, csrc/syevx.hip) on `count` host matrices of mixed sizes through the staging of
+ * hipsdp_eigencuts_all_large: the symmetric matrix into the head of its workspace, the reflector arrays cleared by hs_ecl_clear, the
+ * column launches with `cap` workgroups per matrix at most, the selection */
+extern "C" int hipsdp_syevx_many_below_unit(int device, int count, const int* n, const double* A, double bound, int maxk, int cap, int* cnt,
+   double* lam, double* V)
+{
+   HS_CALL( pick_device(device) );
+   if ( count < 1 || n == NULL || A == NULL || maxk < 0 || maxk > HS_SYEVX_MAXK || cap < 1 || cap > 128 || cnt == NULL || lam == NULL
+      || bound != bound )
+      return HIPSDP_ERR_ARG;
+   int nmax = 0;
+   std::vector<long long> off((size_t) count + 1, 0), wso((size_t) count), outo((size_t) count);
+   long long len = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      if ( n[j] < 2 || n[j] > HS_SYEVX_MAXN )
+         return HIPSDP_ERR_ARG;
+      nmax = n[j] > nmax ? n[j] : nmax;
+      off[j + 1] = off[j] + (long long) n[j] * n[j];
+      const hs_ecl_block B = hs_ecl_block_make((long long) hs_syevx_ws(n[j]), HS_SXB_OUT(n[j]));
+      wso[j] = len + B.ws; outo[j] = len + B.out;
+      len += B.len;
+   }
+   static_assert(sizeof(hs_sxm_job) == 6 * sizeof(double), "job table in doubles");
+   DevBuf dev, djobs, dact;
+   HS_CALL( dev.alloc(len) ); HS_CALL( djobs.alloc(6LL * count) ); HS_CALL( dact.alloc(((long long) count + 1) / 2) );
+   std::vector<hs_sxm_job> jobs((size_t) count);
+   std::vector<int> act((size_t) count, HS_SXM_ACTIVE);
+   std::vector<double> sym;
+   for (int j = 0; j < count; ++j)
+   {
+      HS_CALL( hs_syevx_many_below_job(n[j], dev.p + wso[j], dev.p + outo[j], &jobs[j]) );
+      /* the matrix the single-matrix path builds from the triangle at [c n + i], i >= c */
+      const int nn = n[j];
+      const double* in = A + off[j];
+      sym.resize((size_t) nn * nn);
+      for (int i = 0; i < nn; ++i)
+         for (int c = 0; c < nn; ++c)
+            sym[(size_t) i * nn + c] = (c <= i) ? in[(size_t) c * nn + i] : in[(size_t) i * nn + c];
+      HS_HIP( hipMemcpy(jobs[j].A, sym.data(), (size_t) nn * nn * sizeof(double), hipMemcpyHostToDevice) );
+   }
+   HS_HIP( hipMemcpy(djobs.p, jobs.data(), (size_t) count * sizeof(hs_sxm_job), hipMemcpyHostToDevice) );
+   HS_HIP( hipMemcpy(dact.p, act.data(), (size_t) count * sizeof(int), hipMemcpyHostToDevice) );
+   const hs_sxm_job* dj = reinterpret_cast<const hs_sxm_job*>(djobs.p);
+   const int* da = reinterpret_cast<const int*>(dact.p);
+   HS_CALL( hs_ecl_clear(0, count, dj) );
+   HS_CALL( hs_syevx_many_cols(0, count, nmax, cap, dj, da) );
+   HS_CALL( hs_syevx_many_below(0, count, nmax, bound, maxk, dj, da) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> h;
+   long long voff = 0;
+   for (int j = 0; j < count; ++j)
+   {
+      const long long ol = HS_SYEVX_OUT(n[j]);
+      h.resize((size_t) ol);
+      HS_HIP( hipMemcpy(h.data(), dev.p + outo[j], (size_t) (maxk > 0 ? ol : HS_SYEVX_OUT_VEC) * sizeof(double), hipMemcpyDeviceToHost) );
+      const int k = maxk > 0 ? (int) h[0] : 0;
+      if ( k < 0 || k > maxk )
+         return HIPSDP_ERR_NUMERIC;
+      cnt[j] = k;
+      memcpy(lam + (size_t) j * maxk, h.data() + HS_SYEVX_OUT_LAM, (size_t) k * sizeof(double));
+      if ( V != NULL )
+         memcpy(V + voff, h.data() + HS_SYEVX_OUT_VEC, (size_t) k * n[j] * sizeof(double));
+      voff += (long long) maxk * n[j];
+   }
+   return HIPSDP_OK;
+}
+
 extern "C" int hipsdp_tridiag_unit(int device, int n, const double* A, double* d, double* e, double* Vrefl, double* tau)
 {
    HS_CALL( pick_device(device) );
