@@ -720,6 +720,32 @@ HIPSDP_API int hipsdp_psd_project_many(int device, int count, hipsdp_psd_job* jo
 /* process totals: calls with count > 0 that passed the argument checks, kernel launches they issued for batched jobs, device->host
  * synchronisations they waited on (one for all batched jobs of a call, one more per job above 128 rows); any pointer may be NULL */
 HIPSDP_API int hipsdp_psd_project_many_stats(long long* calls, long long* launches, long long* readbacks);
+/* The partner of hipsdp_psd_project_many for jobs of HIPSDP_PSD_LARGE_MINN .. HIPSDP_PSD_LARGE_MAXN rows: all of them go through the
+ * same launches instead of the single-call chain one after the other (csrc/psd_large.hip).  Job structure, modes, epsilon rule, output
+ * order, cap rule, HIPSDP_PSD_MANY_MAXJOBS and the argument-error list are those of hipsdp_psd_project_many: a kept entry has
+ * row <= col and |value| > epsilon, row-major order; an eigenvalue lam is raised when lam - minev < -epsilon; a job that does not fit
+ * its cap gets the needed length in nnz_out and nothing written, the others are written and the call returns HIPSDP_ERR_ARG.
+ * A job with n < HIPSDP_PSD_LARGE_MINN or n > HIPSDP_PSD_LARGE_MAXN is NOT SERVED: nnz_out = -1, nothing written, the call still
+ * returns HIPSDP_OK and serves the others (the convention of hipsdp_eigencuts_all_large); hand such jobs to hipsdp_psd_project_many.
+ * DECOMPOSITION: through the tridiagonal form - eigenvalues and eigenvectors of a served job are, bit for bit, what hipsdp_syevr
+ * returns for its expanded matrix alone (NOT the block Jacobi of hipsdp_psd_project / hipsdp_syev).
+ * mode 0 depends on the basis and the signs of the eigenvectors: its result is the literal chain of hipsdp_psd_project evaluated on
+ * hipsdp_syevr's vectors, so it agrees with hipsdp_psd_project(mode 0) only as far as the two bases agree.  mode 1 does not depend on
+ * the basis and agrees with hipsdp_psd_project(mode 1) to rounding.
+ * LAUNCHES: the served jobs are taken in chunks of at most 512 MiB of device workspace (HIPSDP_PSD_LARGE_CHUNK = MiB overrides the
+ * limit; a chunk holds at least one job).  A chunk whose largest job has nmax rows issues one upload, then
+ *      nmax + 8 + 6 ceil(nmax / 32)
+ * kernel launches whatever the number of its jobs (1 expand, nmax - 1 columns of the tridiagonalisation, 2 for the eigenvalues,
+ * 3 + 6 ceil(nmax / 32) for the eigenvectors of the tridiagonal matrices, 1 back-transformation, 1 recombination, 1 write), one
+ * device->host copy and one synchronisation.  The bits of a job do not depend on count, on the other jobs, on the job's position,
+ * on the chunking or on the calling thread.  Two host threads may call it at the same time (contexts are thread-local).
+ * HIPSDP_ERR_ARG is checked on the host before the device is looked at; count == 0: HIPSDP_OK, nothing launched. */
+#define HIPSDP_PSD_LARGE_MINN 129
+#define HIPSDP_PSD_LARGE_MAXN 512
+HIPSDP_API int hipsdp_psd_project_many_large(int device, int count, hipsdp_psd_job* jobs, double epsilon, int mode);
+/* process totals: calls with count > 0 that passed the argument checks, kernel launches they issued, device->host synchronisations
+ * they waited on (one per chunk); any pointer may be NULL */
+HIPSDP_API int hipsdp_psd_project_many_large_stats(long long* calls, long long* launches, long long* readbacks);
 HIPSDP_API int  hipsdp_gemv_n(int device, int R, long long E, const double* A, int nv, const double* V, double* out);
 HIPSDP_API int  hipsdp_gemv_t(int device, int R, long long E, const double* A, const double* coef, double* out);
 

@@ -182,6 +182,12 @@ HIPSDP_API int  hipsdp_tridiag_unit(int device, int n, const double* A, double* 
 /* stages 2 and 3 of the full decomposition above 128 rows (csrc/syevr.hip) alone on a caller's symmetric tridiagonal matrix, 2 <= n <= 512,
  * diagonal d[n], off-diagonal e[n - 1]: all eigenvalues (ascending) and the unit eigenvectors of T as the rows of Z (n x n) */
 HIPSDP_API int  hipsdp_tvec_unit(int device, int n, const double* d, const double* e, double* lam, double* Z);
+/* the batched full decomposition of the large PSD projections (csrc/psd_large.hip: hs_syevx_many_cols, hs_syevr_many_tvec, hs_syevr_many_back) on
+ * `count` dense host matrices of mixed sizes, one behind the other in A (matrix j: n[j] x n[j], 129 <= n[j] <= 512, read as hipsdp_syevr
+ * reads it): the column launches with at most cap (1 .. 128) workgroups per matrix, then all eigenpairs of every matrix.  lam: the
+ * eigenvalues of matrix j (ascending) at n[0] + ... + n[j - 1]; V: its unit eigenvectors, row k of n[j] values, at n[0]^2 + ... +
+ * n[j - 1]^2 - for every matrix the bits of hipsdp_syevr on it alone, whatever the table holds beside it and whatever cap is. */
+HIPSDP_API int  hipsdp_syevr_many_unit(int device, int count, const int* n, const double* A, int cap, double* lam, double* V);
 /* the device structure of engine block `block` of a solver CREATED FROM THIS LIBRARY (it contains the engine), a block kept as
  * nonzeros - built first if triplets are waiting: counts[6] = n, m, nnz, npos, nfull, nslots, then every array that is not NULL:
  * voff[m + 1], vrow / vcol / vval[nnz]; poff[npos + 1], prow / pcol[npos], pvar / pval[nnz]; foff[m + 1], frow / fcol / fval[nfull];

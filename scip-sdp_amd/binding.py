@@ -1624,3 +1624,55 @@ def psd_project_many_stats():
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_psd_project_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_psd_project_many_stats")
     return calls.value, launches.value, readbacks.value
+
+
+def psd_project_many_large(jobs, epsilon=1e-9, mode=0, device=0):
+    """hipsdp_psd_project_many_large: jobs as for psd_project_many; per job the (row, col, val) of its projection, or None for a job
+    the call does not serve (fewer than 129 or more than 512 rows)"""
+    count = len(jobs)
+    tab = (PsdJob * max(count, 1))()
+    keep = []
+    for j, (n, row, col, val, minev) in enumerate(jobs):
+        row = np.ascontiguousarray(row, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = _f64(val)
+        cap = n * (n + 1) // 2
+        ro = np.zeros(cap, dtype=np.int32)
+        co = np.zeros(cap, dtype=np.int32)
+        vo = np.zeros(cap)
+        keep.append((row, col, val, ro, co, vo))
+        tab[j].n, tab[j].nnz, tab[j].minev, tab[j].cap = n, len(val), minev, cap
+        tab[j].row, tab[j].col, tab[j].val = _ip(row), _ip(col), _dp(val)
+        tab[j].rowout, tab[j].colout, tab[j].valout = _ip(ro), _ip(co), _dp(vo)
+    _chk(lib().hipsdp_psd_project_many_large(device, count, tab, C.c_double(epsilon), mode), "hipsdp_psd_project_many_large")
+    return [None if tab[j].nnz_out < 0 else (k[3][:tab[j].nnz_out], k[4][:tab[j].nnz_out], k[5][:tab[j].nnz_out])
+            for j, k in enumerate(keep)]
+
+
+def psd_project_many_large_stats():
+    """process totals of hipsdp_psd_project_many_large: (calls, kernel launches, device->host synchronisations - one per chunk)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(lib().hipsdp_psd_project_many_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)),
+         "hipsdp_psd_project_many_large_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def syevr_many_unit(mats, cap, device=0):
+    """the batched decomposition behind hipsdp_psd_project_many_large on dense host matrices of mixed sizes, 129 .. 512 rows each
+    (hipsdp_syevr_many_unit of the units library), column launches of at most cap workgroups per matrix: per matrix (lam, V)"""
+    mats = [np.asarray(a, dtype=np.float64) for a in mats]
+    ns = np.ascontiguousarray([a.shape[0] for a in mats], dtype=np.int32)
+    assert all(a.shape == (n, n) for a, n in zip(mats, ns))
+    cat = _f64(np.concatenate([a.reshape(-1) for a in mats]))
+    lam = np.zeros(int(ns.sum()))
+    V = np.zeros(int((ns.astype(np.int64) ** 2).sum()))
+    rc = ulib().hipsdp_syevr_many_unit(device, len(mats), _ip(ns), _dp(cat), int(cap), _dp(lam), _dp(V))
+    if rc != 0:
+        raise RuntimeError("hipsdp_syevr_many_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    out, lo, vo = [], 0, 0
+    for n in ns:
+        n = int(n)
+        out.append((lam[lo:lo + n].copy(), V[vo:vo + n * n].reshape(n, n).copy()))
+        lo += n
+        vo += n * n
+    return out

@@ -629,6 +629,18 @@ size_t hs_syevr_ws(int n);
  * dOut[0 .. n - 1], the eigenvectors of the tridiagonal matrix as the rows of the n x n array hs_syevr_tvec_view returns */
 int hs_syevr_tvec_dev(hipStream_t st, int n, int vectors, double* dOut, double* ws);
 double* hs_syevr_tvec_view(int n, double* ws);
+/* its stages 2 to 4 for MANY matrices per launch (mixed n, 2 .. 512 each) on the forms hs_syevx_many_cols leaves: a table of hs_srm_job
+ * in device memory, entry k filled by hs_syevr_many_job from the matrix's workspace (hs_syevr_ws(n) doubles; its head is the workspace
+ * of the matrix's hs_sxm_job) and its output (HS_SYEVR_OUT(n) doubles, the layout of hs_syevr_dev).  hs_syevr_many_tvec:
+ * 5 + 6 ceil(nmax / 32) launches (nmax: the largest n of the table); hs_syevr_many_back: one.  The bits of a matrix are those of
+ * hs_syevr_dev on it alone, whatever the table holds beside it. */
+struct hs_srm_job { int n, pad; double* d; double* e; double* R; double* tau; double* sr; double* out; };
+int hs_syevr_many_job(int n, double* ws, double* out, hs_srm_job* J);
+int hs_syevr_many_tvec(hipStream_t st, int count, int nmax, const hs_srm_job* djobs);
+int hs_syevr_many_back(hipStream_t st, int count, int nmax, const hs_srm_job* djobs);
+/* psd_large.hip, for the unit entry: the three calls above (with hs_syevx_many_cols, `cap` workgroups per matrix) on `count` dense host
+ * matrices of 129 .. 512 rows through the calling thread's context of hipsdp_psd_project_many_large; lam and V one matrix behind the other */
+int hs_ppl_syevr_many_host(int device, int count, const int* n, const double* A, int cap, double* lam, double* V);
 
 /* ---- solve1.hip: a whole node solve of a B&B-sized problem in one launch of one workgroup ------------------------------- */
 #define HS_S1_MAXBLK 8

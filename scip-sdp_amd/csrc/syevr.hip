@@ -27,7 +27,9 @@
  *      which reads every reflector once into LDS for its eight vectors; a reflector that lies below the support of z is skipped.
  * HAZARD RULE: inside one launch no workgroup reads what another workgroup writes; the kernel boundary is the only
  * synchronisation between workgroups.  Every reduction runs in a fixed order, no floating-point atomics: same input, same bits.
- * Launches: n for stage 1, 2 for stage 2, 3 + 6 ceil(n / 32) for stage 3, 1 for stage 4. */
+ * Launches: n for stage 1, 2 for stage 2, 3 + 6 ceil(n / 32) for stage 3, 1 for stage 4.
+ * Each of stages 2 to 4 is a __device__ body (d_syevr_values, _order, _step, _ortho_prev, _ortho_panel, _back) with two kernels around
+ * it: the one of a single matrix and the one of MANY matrices per launch (k_syevr_*_many, hs_syevr_many_*: hipsdp_psd_project_many_large). */
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_tridiag.h"
@@ -50,7 +52,7 @@ struct sr_ws
 __host__ __device__ inline size_t sr_even(size_t v) { return (v + 1) & ~(size_t) 1; }
 __host__ __device__ inline size_t sr_npad(int n) { return (size_t) SR_P * ((n + SR_P - 1) / SR_P); }
 
-inline sr_ws sr_layout(int n, double* base)
+__host__ __device__ inline sr_ws sr_layout(int n, double* base)
 {
    const size_t nl = sr_even((size_t) n), n2 = sr_even((size_t) n * n), ng = sr_even((size_t) n * sr_npad(n));
    sr_ws w;
@@ -69,7 +71,7 @@ size_t sr_ws_doubles(int n)
 }
 
 /* ---- stage 2a: split table and the eigenvalues of 32 slots per workgroup.  meta[0] = Gershgorin span, meta[1] = norm bound of T */
-__global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __restrict__ d, const double* __restrict__ e, double* __restrict__ lamU,
+__device__ __forceinline__ void d_syevr_values(int n, int blk, const double* __restrict__ d, const double* __restrict__ e, double* __restrict__ lamU,
    int* __restrict__ bsU, int* __restrict__ beU, double* __restrict__ meta)
 {
    __shared__ double ds[SR_N + 8], es[SR_N + 8], red[3][SR_T / 64];
@@ -106,7 +108,7 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
    /* thread = (slot kk of this workgroup, one of 16 shifts) */
    const int S = SR_T / SR_P;
    const int kk = tid / S, sh = tid % S;
-   const int slot = blockIdx.x * SR_P + kk;
+   const int slot = blk * SR_P + kk;
    int bs = 0, be = 1;
    if ( slot < n )
    {
@@ -128,16 +130,22 @@ __global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __re
       bsU[slot] = bs;
       beU[slot] = be;
    }
-   if ( blockIdx.x == 0 && tid == 0 )
+   if ( blk == 0 && tid == 0 )
    {
       meta[0] = span0;
       meta[1] = tnorm;
    }
 }
 
+__global__ void __launch_bounds__(SR_T) k_syevr_values(int n, const double* __restrict__ d, const double* __restrict__ e, double* __restrict__ lamU,
+   int* __restrict__ bsU, int* __restrict__ beU, double* __restrict__ meta)
+{
+   d_syevr_values(n, (int) blockIdx.x, d, e, lamU, bsU, beU, meta);
+}
+
 /* ---- stage 2b: ascending order and the cluster table.  For the eigenvalue of ascending index k: lam[k] (also to out), vlo / vhi =
  * its block of rows, cid = ascending index of the first member of its cluster (cid[k] <= k; == k: first member). */
-__global__ void __launch_bounds__(SR_T) k_syevr_order(int n, const double* __restrict__ lamU, const int* __restrict__ bsU, const int* __restrict__ beU,
+__device__ __forceinline__ void d_syevr_order(int n, const double* __restrict__ lamU, const int* __restrict__ bsU, const int* __restrict__ beU,
    const double* __restrict__ meta, double* __restrict__ lam, int* __restrict__ vlo, int* __restrict__ vhi, int* __restrict__ cid, double* __restrict__ out)
 {
    __shared__ double lu[SR_N];
@@ -179,23 +187,28 @@ __global__ void __launch_bounds__(SR_T) k_syevr_order(int n, const double* __res
    }
 }
 
+__global__ void __launch_bounds__(SR_T) k_syevr_order(int n, const double* __restrict__ lamU, const int* __restrict__ bsU, const int* __restrict__ beU,
+   const double* __restrict__ meta, double* __restrict__ lam, int* __restrict__ vlo, int* __restrict__ vhi, int* __restrict__ cid, double* __restrict__ out)
+{
+   d_syevr_order(n, lamU, bsU, beU, meta, lam, vlo, vhi, cid, out);
+}
+
 /* ---- stage 3, the step: vector k = 32 blockIdx + t on the rows [vlo[k], vhi[k]) of T.  Dynamic LDS: Z[32][n | 1].  iter == 0: start
  * vectors hashed per vector and row; later: the vectors of the previous round from Zg.  G0 .. G2: this workgroup's slab, [row][t]. */
-__global__ void __launch_bounds__(SR_T) k_syevr_step(int n, int iter, const double* __restrict__ dg, const double* __restrict__ eg, const double* __restrict__ lam,
-   const int* __restrict__ vlo, const int* __restrict__ vhi, const double* __restrict__ meta, double* __restrict__ Zg, double* __restrict__ G0g,
-   double* __restrict__ G1g, double* __restrict__ G2g)
+__device__ __forceinline__ void d_syevr_step(int n, int iter, int blk, const double* __restrict__ dg, const double* __restrict__ eg,
+   const double* __restrict__ lam, const int* __restrict__ vlo, const int* __restrict__ vhi, const double* __restrict__ meta, double* __restrict__ Zg,
+   double* __restrict__ G0g, double* __restrict__ G1g, double* __restrict__ G2g, double* __restrict__ Z)
 {
-   extern __shared__ __attribute__((aligned(16))) double Z[];
    __shared__ double d[SR_N], e[SR_N], th[SR_P];
    __shared__ int blo[SR_P], bhi[SR_P];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    const int ld = n | 1;
-   const int k0 = blockIdx.x * SR_P;
+   const int k0 = blk * SR_P;
    const int cnt = min(SR_P, n - k0);
    const double span0 = meta[0];
-   double* __restrict__ G0 = G0g + (size_t) blockIdx.x * SR_P * n;
-   double* __restrict__ G1 = G1g + (size_t) blockIdx.x * SR_P * n;
-   double* __restrict__ G2 = G2g + (size_t) blockIdx.x * SR_P * n;
+   double* __restrict__ G0 = G0g + (size_t) blk * SR_P * n;
+   double* __restrict__ G1 = G1g + (size_t) blk * SR_P * n;
+   double* __restrict__ G2 = G2g + (size_t) blk * SR_P * n;
    if ( tid < n )
    {
       d[tid] = dg[tid];
@@ -237,16 +250,24 @@ __global__ void __launch_bounds__(SR_T) k_syevr_step(int n, int iter, const doub
    }
 }
 
+__global__ void __launch_bounds__(SR_T) k_syevr_step(int n, int iter, const double* __restrict__ dg, const double* __restrict__ eg, const double* __restrict__ lam,
+   const int* __restrict__ vlo, const int* __restrict__ vhi, const double* __restrict__ meta, double* __restrict__ Zg, double* __restrict__ G0g,
+   double* __restrict__ G1g, double* __restrict__ G2g)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   d_syevr_step(n, iter, (int) blockIdx.x, dg, eg, lam, vlo, vhi, meta, Zg, G0g, G1g, G2g, Z);
+}
+
 /* ---- stage 3, A(p): vector k = 32 p + blockIdx against the members of its cluster in the panels before p, twice.  The
  * coefficients one wavefront per earlier vector, the correction one thread per row with the earlier vectors in ascending order. */
-__global__ void __launch_bounds__(SR_T) k_syevr_ortho_prev(int n, int p, const int* __restrict__ vlo, const int* __restrict__ vhi, const int* __restrict__ cid,
+__device__ __forceinline__ void d_syevr_ortho_prev(int n, int p, int t, const int* __restrict__ vlo, const int* __restrict__ vhi, const int* __restrict__ cid,
    double* __restrict__ Zg)
 {
    __shared__ double zs[SR_N], coef[SR_N];
    __shared__ int mate[SR_N];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    const int kend = SR_P * p;
-   const int k = kend + blockIdx.x;
+   const int k = kend + t;
    if ( k >= n )
       return;
    const int c = cid[k];
@@ -300,11 +321,16 @@ __global__ void __launch_bounds__(SR_T) k_syevr_ortho_prev(int n, int p, const i
       Zg[(size_t) k * n + r0 + tid] = zs[tid];
 }
 
+__global__ void __launch_bounds__(SR_T) k_syevr_ortho_prev(int n, int p, const int* __restrict__ vlo, const int* __restrict__ vhi, const int* __restrict__ cid,
+   double* __restrict__ Zg)
+{
+   d_syevr_ortho_prev(n, p, (int) blockIdx.x, vlo, vhi, cid, Zg);
+}
+
 /* ---- stage 3, B(p): the panel finished - Gram-Schmidt, twice, among the members of a cluster inside the panel, then the norm of
  * every vector that has earlier members at all.  Dynamic LDS: Z[32][n | 1]. */
-__global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel(int n, int p, const int* __restrict__ cid, double* __restrict__ Zg)
+__device__ __forceinline__ void d_syevr_ortho_panel(int n, int p, const int* __restrict__ cid, double* __restrict__ Zg, double* __restrict__ Z)
 {
-   extern __shared__ __attribute__((aligned(16))) double Z[];
    __shared__ double coef[SR_P], red[2][SR_T / 64];
    __shared__ int cs[SR_P];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -369,16 +395,22 @@ __global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel(int n, int p, const 
    }
 }
 
+__global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel(int n, int p, const int* __restrict__ cid, double* __restrict__ Zg)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   d_syevr_ortho_panel(n, p, cid, Zg, Z);
+}
+
 /* ---- stage 4: x = H_0 H_1 ... H_{n-3} z for all n vectors.  Wavefront w of workgroup g owns vector 8 g + w, lane l holds the entries
  * l + 64 m.  The reflectors come through LDS eight at a time, read once from L2 per workgroup (wavefront w fetches reflector w of
  * the next eight into registers while the current eight are applied).  H_j acts on the rows j + 1 .. n - 1: a vector whose support ends at or before
  * row j + 1 is not changed by it and skips it, as it skips tau_j = 0. */
-__global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zg,
+__device__ __forceinline__ void d_syevr_back(int n, int blk, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zg,
    const int* __restrict__ vhi, double* __restrict__ out)
 {
    __shared__ double vs[SR_BC][SR_N], ts[SR_N];
    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-   const int k = blockIdx.x * SR_BW + wave;
+   const int k = blk * SR_BW + wave;
    const bool have = k < n;
    for (int i = tid; i < n; i += SR_BW * 64)
       ts[i] = tau[i];
@@ -429,6 +461,72 @@ __global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* 
    if ( !have )
       return;
    hs_td_store_unit(z, n, lane, out + (size_t) k * n);
+}
+
+__global__ void __launch_bounds__(SR_BW * 64) k_syevr_back(int n, const double* __restrict__ R, const double* __restrict__ tau, const double* __restrict__ Zg,
+   const int* __restrict__ vhi, double* __restrict__ out)
+{
+   d_syevr_back(n, (int) blockIdx.x, R, tau, Zg, vhi, out);
+}
+
+/* ---- the same stages for MANY matrices per launch (hs_syevr_many_*; caller: hipsdp_psd_project_many_large, psd_large.hip): matrix
+ * blockIdx.y of the table, its n and its arrays from its hs_srm_job; the bodies are those of the single matrix, so the bits of a
+ * matrix are those of hs_syevr_dev on it alone.  The grids are sized by the largest matrix of the table: a workgroup whose slots,
+ * panel or vectors lie beyond its matrix's n leaves at once (uniform per workgroup). */
+__global__ void __launch_bounds__(SR_T) k_syevr_values_many(const hs_srm_job* __restrict__ jobs)
+{
+   const hs_srm_job J = jobs[blockIdx.y];
+   if ( (int) blockIdx.x * SR_P >= J.n )
+      return;
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_values(J.n, (int) blockIdx.x, J.d, J.e, w.lamU, w.bsU, w.beU, w.meta);
+}
+
+__global__ void __launch_bounds__(SR_T) k_syevr_order_many(const hs_srm_job* __restrict__ jobs)
+{
+   const hs_srm_job J = jobs[blockIdx.y];
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_order(J.n, w.lamU, w.bsU, w.beU, w.meta, w.lam, w.vlo, w.vhi, w.cid, J.out);
+}
+
+/* dynamic LDS: 32 x (nmax | 1) doubles */
+__global__ void __launch_bounds__(SR_T) k_syevr_step_many(int iter, const hs_srm_job* __restrict__ jobs)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   const hs_srm_job J = jobs[blockIdx.y];
+   if ( (int) blockIdx.x * SR_P >= J.n )
+      return;
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_step(J.n, iter, (int) blockIdx.x, J.d, J.e, w.lam, w.vlo, w.vhi, w.meta, w.Z, w.G0, w.G1, w.G2, Z);
+}
+
+__global__ void __launch_bounds__(SR_T) k_syevr_ortho_prev_many(int p, const hs_srm_job* __restrict__ jobs)
+{
+   const hs_srm_job J = jobs[blockIdx.y];
+   if ( SR_P * p + (int) blockIdx.x >= J.n )
+      return;
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_ortho_prev(J.n, p, (int) blockIdx.x, w.vlo, w.vhi, w.cid, w.Z);
+}
+
+/* dynamic LDS: 32 x (nmax | 1) doubles */
+__global__ void __launch_bounds__(SR_T) k_syevr_ortho_panel_many(int p, const hs_srm_job* __restrict__ jobs)
+{
+   extern __shared__ __attribute__((aligned(16))) double Z[];
+   const hs_srm_job J = jobs[blockIdx.y];
+   if ( SR_P * p >= J.n )
+      return;
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_ortho_panel(J.n, p, w.cid, w.Z, Z);
+}
+
+__global__ void __launch_bounds__(SR_BW * 64) k_syevr_back_many(const hs_srm_job* __restrict__ jobs)
+{
+   const hs_srm_job J = jobs[blockIdx.y];
+   if ( (int) blockIdx.x * SR_BW >= J.n )
+      return;
+   const sr_ws w = sr_layout(J.n, J.sr);
+   d_syevr_back(J.n, (int) blockIdx.x, J.R, J.tau, w.Z, w.vhi, J.out + HS_SYEVR_OUT_VEC(J.n));
 }
 
 }
@@ -484,5 +582,54 @@ int hs_syevr_dev(hipStream_t st, int n, const double* dA, int vectors, double* d
       hipLaunchKernelGGL(k_syevr_back, dim3((n + SR_BW - 1) / SR_BW), dim3(SR_BW * 64), 0, st, n, R, tau, w.Z, w.vhi, dOut + HS_SYEVR_OUT_VEC(n));
       HS_HIP( hipGetLastError() );
    }
+   return HS_OK;
+}
+
+/* ---- many matrices per launch.  hs_syevr_many_job: the table entry of a matrix of n rows with its workspace (hs_syevr_ws(n) doubles,
+ * its head the workspace hs_syevx_many_job takes) and its output (HS_SYEVR_OUT(n) doubles, the layout of hs_syevr_dev). */
+int hs_syevr_many_job(int n, double* ws, double* out, hs_srm_job* J)
+{
+   if ( n < 2 || n > SR_N || ws == NULL || out == NULL || J == NULL )
+      return HS_ERR_ARG;
+   J->n = n; J->pad = 0;
+   hs_syevx_tridiag_view(n, ws, &J->d, &J->e, &J->R, &J->tau);
+   J->sr = ws + hs_syevx_ws(n);
+   J->out = out;
+   return HS_OK;
+}
+
+/* stages 2 and 3 of every matrix on the forms hs_syevx_many_cols leaves: 5 + 6 ceil(nmax / 32) launches, whatever the matrices are */
+int hs_syevr_many_tvec(hipStream_t st, int count, int nmax, const hs_srm_job* djobs)
+{
+   if ( count < 1 || nmax < 2 || nmax > SR_N || djobs == NULL )
+      return HS_ERR_ARG;
+   const int np = (nmax + SR_P - 1) / SR_P;
+   static hs_attr_mask step_done, panel_done;
+   const int ldsmax = SR_P * (SR_N + 1) * (int) sizeof(double);
+   const size_t lds = (size_t) SR_P * (nmax | 1) * sizeof(double);
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_syevr_step_many), ldsmax, &step_done) );
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_syevr_ortho_panel_many), ldsmax, &panel_done) );
+   hipLaunchKernelGGL(k_syevr_values_many, dim3(np, count), dim3(SR_T), 0, st, djobs);
+   hipLaunchKernelGGL(k_syevr_order_many, dim3(1, count), dim3(SR_T), 0, st, djobs);
+   for (int iter = 0; iter < 3; ++iter)
+   {
+      hipLaunchKernelGGL(k_syevr_step_many, dim3(np, count), dim3(SR_T), lds, st, iter, djobs);
+      for (int p = 0; p < np; ++p)
+      {
+         hipLaunchKernelGGL(k_syevr_ortho_prev_many, dim3(SR_P, count), dim3(SR_T), 0, st, p, djobs);
+         hipLaunchKernelGGL(k_syevr_ortho_panel_many, dim3(1, count), dim3(SR_T), lds, st, p, djobs);
+      }
+   }
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* stage 4 of every matrix: all vectors of all matrices in one launch */
+int hs_syevr_many_back(hipStream_t st, int count, int nmax, const hs_srm_job* djobs)
+{
+   if ( count < 1 || nmax < 2 || nmax > SR_N || djobs == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_syevr_back_many, dim3((nmax + SR_BW - 1) / SR_BW, count), dim3(SR_BW * 64), 0, st, djobs);
+   HS_HIP( hipGetLastError() );
    return HS_OK;
 }

@@ -2000,6 +2000,13 @@ extern "C" int hipsdp_tvec_unit(int device, int n, const double* d, const double
    return HIPSDP_OK;
 }
 
+/* the batched full decomposition of hipsdp_psd_project_many_large on dense host matrices (hs_ppl_syevr_many_host, csrc/psd_large.hip) */
+extern "C" int hipsdp_syevr_many_unit(int device, int count, const int* n, const double* A, int cap, double* lam, double* V)
+{
+   HS_CALL( pick_device(device) );
+   return hs_ppl_syevr_many_host(device, count, n, A, cap, lam, V);
+}
+
 /* the device structure of a block kept as nonzeros, copied to the host as it stands (tests/test_gpu_sparse_master.py compares the
  * structure hipsdp_master_gather builds on the device with the one hs_sp_build makes from the node's triplets) */
 extern "C" int hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long long* counts, int* voff, int* vrow, int* vcol, double* vval,
