@@ -11,12 +11,11 @@
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_cut_plan.h"
+#include "hs_chunks.h"
 #include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 namespace {
@@ -43,12 +42,17 @@ bool variant_ok(unsigned variant)
    return variant <= (HS_SCR_SPARSEEV | HS_SCR_INITIAL | HS_SCR_EXACTTRANS);
 }
 
-/* where the vectors of block b start in the result, [nb]: their total length - maxcuts vectors per block, or of block `only` alone */
-std::vector<long long> cut_vecoff(const hipsdp_solver* s, int nb, int maxcuts, int only)
+/* where the vectors of block b start in the result, [nb]: their total length - maxcuts vectors per block, or per block of `members`
+ * alone when that is given */
+std::vector<long long> cut_vecoff(const hipsdp_solver* s, int nb, int maxcuts, const std::vector<int>* members = NULL)
 {
+   std::vector<char> in((size_t) nb, members == NULL ? 1 : 0);
+   if ( members != NULL )
+      for (int b : *members)
+         in[b] = 1;
    std::vector<long long> vecoff((size_t) nb + 1, 0);
    for (int b = 0; b < nb; ++b)
-      vecoff[b + 1] = vecoff[b] + (only < 0 || b == only ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
+      vecoff[b + 1] = vecoff[b] + (in[b] ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
    return vecoff;
 }
 
@@ -86,6 +90,17 @@ int cut_block_out(const hs_sc_out& h, int b, int k, int maxcuts, long long voff,
    if ( d.flags != NULL ) *d.flags = h.flags[b];
    cut_copy_out(h, (size_t) b * maxcuts, voff, k, m, n, d.eigvals, d.lhs, d.coefs, d.vecs);
    return HIPSDP_OK;
+}
+
+/* the tail of every call and chunk: ONE read-back of the result range, the launches and the read-back booked; h: its pinned view */
+int cut_readback(const hs_solver_cut_ws& w, const hs_cut_res& r, const hs_cut_lens& len, int launches, CutStats* stats, hs_sc_out* h)
+{
+   HS_HIP( hipMemcpyAsync(w.pin + len.res_off, w.dev + len.res_off, (size_t) len.res_len * sizeof(double), hipMemcpyDeviceToHost, w.stream) );
+   HS_HIP( hipStreamSynchronize(w.stream) );
+   stats->launches += launches;
+   stats->readbacks += 1;
+   *h = hs_cut_view(r, w.pin);
+   return HS_OK;
 }
 
 void sc_par_from_opts(const hipsdp_sparsecut_opts* opts, hs_sc_par* par)
@@ -207,13 +222,7 @@ int sc_finish(ScRun& R, CutStats* stats, hs_sc_out* h)
       HS_CALL( hs_sc_coefs(w.stream, R.nj, R.m, R.maxcuts, w.djobs, R.dsizes, &R.out) );
       ++R.launches;
    }
-   HS_HIP( hipMemcpyAsync(w.pin + R.len.res_off, w.dev + R.len.res_off, (size_t) R.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
-         w.stream) );
-   HS_HIP( hipStreamSynchronize(w.stream) );
-   stats->launches += R.launches;
-   stats->readbacks += 1;
-   *h = hs_cut_view(R.r, w.pin);
-   return HS_OK;
+   return cut_readback(w, R.r, R.len, R.launches, stats, h);
 }
 
 /* The launches of a round with a switch set (variant: HS_SCR_* bits, != 0) between sc_begin and sc_finish: the decompositions of Z(y),
@@ -265,24 +274,31 @@ int sc_round(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const
    return sc_finish(R, variant == 0 ? stats0 : &g_scx, h);
 }
 
+/* the argument checks of the sparse-cut calls over all blocks: nothing is written, no device is looked at */
+int sc_all_args(const hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, const CutDst& d, int* m, int* nb)
+{
+   if ( !hs_solver_dims(s, m, nb) || y == NULL || sizes == NULL || opts == NULL || d.ncuts == NULL || opts->maxcuts < 0 )
+      return HIPSDP_ERR_ARG;
+   if ( opts->maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < *nb; ++b)
+      if ( sizes[b] < 1 )
+         return HIPSDP_ERR_ARG;
+   return HIPSDP_OK;
+}
+
 /* hipsdp_sparsecuts_all (variant = 0) and hipsdp_sparsecuts_all_ex with a switch set */
 int sparsecuts_all_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
    const CutDst& d)
 {
    int m = 0, nb = 0;
-   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || sizes == NULL || opts == NULL || d.ncuts == NULL || opts->maxcuts < 0 )
-      return HIPSDP_ERR_ARG;
+   HS_CALL( sc_all_args(s, y, sizes, opts, d, &m, &nb) );
    const int maxcuts = opts->maxcuts;
-   if ( maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
-      return HIPSDP_ERR_ARG;
-   for (int b = 0; b < nb; ++b)
-      if ( sizes[b] < 1 )
-         return HIPSDP_ERR_ARG;
    for (int b = 0; b < nb; ++b)
       d.ncuts[b] = -1;
    std::vector<int> ids;
    HS_CALL( hs_solver_cut_enter(s, -1, &ids) );
-   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, -1);
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts);
    if ( !ids.empty() )
    {
       hs_sc_out h;
@@ -304,7 +320,7 @@ int sparsecuts_small(hipsdp_solver* s, int m, int nb, int block, const double* y
    if ( !*served )
       return HIPSDP_OK;
    const int maxcuts = opts->maxcuts;
-   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, block);      /* only this block has vectors */
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, &ids);       /* only this block has vectors */
    std::vector<int> sizes((size_t) nb, 1);
    sizes[block] = size;
    hs_sc_out h;
@@ -339,37 +355,29 @@ int sparsecuts_large(hipsdp_solver* s, int m, int block, const double* y, int si
    ++launches;
    HS_CALL( hs_syevx_tridiag_dev(st, n, dZ, dws) );
    launches += n;
-   /* the one read-back: the result block, or with maxcuts = 0 the head of the first request's output (its eigenvalue) */
-   double* hres = w.pin + L.len.res_off;
-   const double* dres = w.dev + L.len.res_off;
-   long long reslen = L.len.res_len;
    if ( maxcuts == 0 )
    {
+      /* no result block: the one read-back is the head of the request's output (its eigenvalue), to where the result would lie */
+      double* hres = w.pin + L.len.res_off;
       HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, o1, dws) );
       ++launches;
-      dres = o1; reslen = HS_SYEVX_OUT_VEC;
-   }
-   else
-   {
-      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
-      HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
-      HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, w.dev + L.MT, &par, &out) );
-      HS_CALL( hs_scl_coefs(st, m, maxcuts, size, w.djobs, &out) );
-      launches += 3 + 1 + 1 + 1;
-   }
-   HS_HIP( hipMemcpyAsync(hres, dres, (size_t) reslen * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_sc1.launches += launches;
-   g_sc1.readbacks += 1;
-   if ( maxcuts == 0 )
-   {
+      HS_HIP( hipMemcpyAsync(hres, o1, (size_t) HS_SYEVX_OUT_VEC * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+      g_sc1.launches += launches;
+      g_sc1.readbacks += 1;
       *d.ncuts = 0;
       if ( d.lmin != NULL ) *d.lmin = hres[HS_SYEVX_OUT_LAM];
       if ( d.iters != NULL ) *d.iters = 0;
       if ( d.flags != NULL ) *d.flags = 0;
       return HIPSDP_OK;
    }
-   const hs_sc_out h = hs_cut_view(L.r, w.pin);
+   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX, 1, 1, 0.0, 0, o1, dws) );
+   HS_CALL( hs_syevx_select_dev(st, n, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, n, n, 0.0, 0, o2, dws) );
+   HS_CALL( hs_scl_tpower(st, n, size, dZ, o1 + HS_SYEVX_OUT_LAM, o2 + HS_SYEVX_OUT_LAM, o1 + HS_SYEVX_OUT_VEC, w.dev + L.MT, &par, &out) );
+   HS_CALL( hs_scl_coefs(st, m, maxcuts, size, w.djobs, &out) );
+   launches += 3 + 1 + 1 + 1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, L.r, L.len, launches, &g_sc1, &h) );
    return cut_block_out(h, 0, h.ncuts[0], maxcuts, 0, m, n, d);
 }
 
@@ -388,13 +396,77 @@ hs_sclr_block sclr_block(int n, int ns)
    return hs_sclr_block_make(n, ns, ns > 0 ? hs_syev_small_scratch(ns) : 0, (long long) hs_syevx_ws(n), HS_SXM_OUT(n));
 }
 
-/* workgroups per matrix of the column launches: about four workgroups per compute unit over all blocks, at least 8, at most the 128 of
- * a matrix alone (the rule of hipsdp_onevar_bounds_large; the bits do not depend on it) */
-int sclr_cap(int count)
+/* the blocks a _large cut call serves: whole matrices on this device (none for a solver with a communicator or sharded matrices) of
+ * HS_SC_MAXN + 1 .. maxn rows that pass `keep`, by descending n, the caller's order among equal sizes */
+template <class Keep>
+int large_served(hipsdp_solver* s, int maxn, Keep keep, std::vector<int>* ids)
 {
-   const int cus = hs_device_cus();
-   const int g = (4 * (cus > 0 ? cus : 256)) / count;
-   return g < 8 ? 8 : (g > 128 ? 128 : g);
+   std::vector<int> all;
+   HS_CALL( hs_solver_cut_enter_large(s, maxn, &all) );
+   ids->clear();
+   for (int b : all)
+      if ( hs_solver_block_n(s, b) > HS_SC_MAXN && keep(b) )
+         ids->push_back(b);
+   std::stable_sort(ids->begin(), ids->end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
+   return HS_OK;
+}
+
+/* a chunk of a _large cut call between its two ends, as ScRun is a round's: the workspace, the chunk's own result (indexed by the
+ * block's number, vectors of the chunk's blocks alone), where every block's part of the workspace starts, the launches so far */
+struct LargeRun
+{
+   hs_solver_cut_ws w;
+   hs_cut_res r;
+   hs_cut_lens len;
+   std::vector<long long> vecoff;      /* [nb + 1] */
+   std::vector<long long> start;       /* [cnt]: doubles from the device workspace's start */
+   int nmax, launches;
+};
+
+/* The head of the chunk over the served blocks `ids` (descending n) of a solver with nb blocks.  len_of(j): what block j takes of the
+ * workspace; make(vec_len, blocks_len, L): the call's layout (hs_sclr_layout, hs_ecl_layout: y, r, blocks and len are read from it);
+ * z_of(j): where Z(y) of block j goes inside its part.  Leaves the workspace with the solver's table of the blocks (w.djobs) and y in
+ * the pinned mirror; the call's tables and the ONE upload of [0, upload_len) are the caller's. */
+template <class Layout, class LenOf, class Make, class ZOf>
+int large_begin(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, const double* y, int maxcuts, LenOf len_of, Make make, ZOf z_of,
+   Layout* L, LargeRun* R)
+{
+   const int cnt = (int) ids.size();
+   R->nmax = 0; R->launches = 0;
+   R->vecoff = cut_vecoff(s, nb, maxcuts, &ids);
+   R->start.resize((size_t) cnt);
+   long long blocks_len = 0;
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int n = hs_solver_block_n(s, ids[j]);
+      R->nmax = n > R->nmax ? n : R->nmax;
+      R->start[j] = blocks_len;
+      blocks_len += len_of(j);
+   }
+   make(R->vecoff[nb], blocks_len, L);
+   std::vector<long long> zoff((size_t) cnt);
+   for (int j = 0; j < cnt; ++j)
+   {
+      R->start[j] += L->blocks;
+      zoff[j] = R->start[j] + z_of(j);
+   }
+   HS_CALL( hs_solver_cut_blocks(s, ids, zoff, L->len.dev_len, L->len.pin_len, &R->w) );
+   R->r = L->r; R->len = L->len;
+   if ( m > 0 )
+      memcpy(R->w.pin + L->y, y, (size_t) m * sizeof(double));
+   return HS_OK;
+}
+
+/* The tail of the chunk: ONE read-back, its launches booked under `stats`, every block of the chunk to the caller's arrays.  gvecoff:
+ * where a block's vectors start in the caller's array. */
+int large_end(const hipsdp_solver* s, const LargeRun& R, int m, const std::vector<int>& ids, int maxcuts, CutStats* stats, const CutDst& d,
+   const std::vector<long long>& gvecoff)
+{
+   hs_sc_out h;
+   HS_CALL( cut_readback(R.w, R.r, R.len, R.launches, stats, &h) );
+   for (int b : ids)
+      HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, R.vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, gvecoff[b])) );
+   return HIPSDP_OK;
 }
 
 /* ONE CHUNK: the served blocks `ids` (descending n) of a solver with nb blocks - a call of its own in everything but the entry: its
@@ -406,41 +478,28 @@ int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, con
 {
    const int cnt = (int) ids.size(), maxcuts = opts->maxcuts;
    const bool sparseev = (variant & HS_SCR_SPARSEEV) != 0, deflated = (variant & (HS_SCR_INITIAL | HS_SCR_EXACTTRANS)) != 0;
-   /* the chunk's result: indexed by the block's number, vectors of the chunk's blocks alone */
-   std::vector<long long> vecoff((size_t) nb + 1, 0);
-   {
-      std::vector<char> in((size_t) nb, 0);
-      for (int b : ids)
-         in[b] = 1;
-      for (int b = 0; b < nb; ++b)
-         vecoff[b + 1] = vecoff[b] + (in[b] ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
-   }
-   int smax = 1, nmax = 0;
-   long long blocks_len = 0;
+   int smax = 1;
    std::vector<hs_sclr_block> B((size_t) cnt);
-   std::vector<long long> start((size_t) cnt), zoff((size_t) cnt);
    std::vector<int> ns((size_t) cnt);
    for (int j = 0; j < cnt; ++j)
    {
       const int n = hs_solver_block_n(s, ids[j]), size = sizes[ids[j]];
       if ( size <= n && size > smax )
          smax = size;
-      nmax = n > nmax ? n : nmax;
       ns[j] = sparseev ? size : 0;
       B[j] = sclr_block(n, ns[j]);
-      start[j] = blocks_len;
-      blocks_len += B[j].len;
    }
    hs_sclr_layout L;
-   hs_sclr_layout_make(nb, m, maxcuts, smax, vecoff[nb], cnt, SCLR_JOBW, SCLR_XJOBW, SCLR_SJOBW, blocks_len, &L);
-   for (int j = 0; j < cnt; ++j)
-      zoff[j] = L.blocks + start[j] + B[j].Z;
-   hs_solver_cut_ws w;
-   HS_CALL( hs_solver_cut_blocks(s, ids, zoff, L.len.dev_len, L.len.pin_len, &w) );
+   LargeRun R;
+   HS_CALL( large_begin(s, m, nb, ids, y, maxcuts, [&](int j) { return B[j].len; },
+         [&](long long vec_len, long long blocks_len, hs_sclr_layout* l)
+         { hs_sclr_layout_make(nb, m, maxcuts, smax, vec_len, cnt, SCLR_JOBW, SCLR_XJOBW, SCLR_SJOBW, blocks_len, l); },
+         [&](int j) { return B[j].Z; }, &L, &R) );
+   const hs_solver_cut_ws& w = R.w;
    hipStream_t st = w.stream;
-   /* y | sizes | tables | act  in the pinned mirror */
-   if ( m > 0 )
-      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+   const int nmax = R.nmax;
+   int& launches = R.launches;
+   /* sizes | tables | act  behind y in the pinned mirror */
    memcpy(w.pin + L.sizes, sizes, (size_t) nb * sizeof(int));
    hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
    hs_sclr_job* hx = reinterpret_cast<hs_sclr_job*>(w.pin + L.xjobs);
@@ -448,7 +507,7 @@ int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, con
    std::vector<hs_eig_job> sj;               /* the Z_S jobs by decomposition class: the host copy hs_syev_small_many wants */
    for (int j = 0; j < cnt; ++j)
    {
-      double* base = w.dev + L.blocks + start[j];
+      double* base = w.dev + R.start[j];
       HS_CALL( hs_syevx_many_job(hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, &hsx[j]) );
       hs_sclr_job& X = hx[j];
       memset(&X, 0, sizeof(X));
@@ -461,7 +520,7 @@ int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, con
          X.wsS = base + B[j].wsS;
          X.vposS = hs_syev_many_vecpos(ns[j]);
       }
-      X.vecoff = vecoff[ids[j]];
+      X.vecoff = R.vecoff[ids[j]];
       hact[j] = HS_SXM_ACTIVE | HS_SXM_VEC | HS_SXM_BOTH;
    }
    for (int cls = 0; cls < 3 && sparseev; ++cls)
@@ -485,8 +544,7 @@ int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, con
    const hs_sc_out out = hs_cut_view(L.r, w.dev);
    hs_sc_par par;
    sc_par_from_opts(opts, &par);
-   const int cap = sclr_cap(cnt);
-   int launches = 0;
+   const int cap = hs_syevx_many_cap(cnt);
    HS_CALL( hs_ec_form_z(st, cnt, nmax, m, w.djobs, w.dev + L.y) );
    ++launches;
    /* (lmin, v0) and maxeig of Z(y) of every block: stage, nmax - 1 column launches, 3 selection launches */
@@ -529,58 +587,33 @@ int sclr_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, con
       HS_CALL( hs_sclr_coefs(st, cnt, m, maxcuts, w.djobs, dx, dsizes, &out) );
       ++launches;
    }
-   HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_scl.launches += launches;
-   g_scl.readbacks += 1;
-   const hs_sc_out h = hs_cut_view(L.r, w.pin);
-   for (int b : ids)
-      HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, gvecoff[b])) );
-   return HIPSDP_OK;
+   return large_end(s, R, m, ids, maxcuts, &g_scl, d, gvecoff);
 }
 
 int sparsecuts_all_large_impl(hipsdp_solver* s, const double* y, const int* sizes, const hipsdp_sparsecut_opts* opts, unsigned variant,
    const CutDst& d)
 {
    int m = 0, nb = 0;
-   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || sizes == NULL || opts == NULL || d.ncuts == NULL || opts->maxcuts < 0 )
-      return HIPSDP_ERR_ARG;
+   HS_CALL( sc_all_args(s, y, sizes, opts, d, &m, &nb) );
    const int maxcuts = opts->maxcuts;
-   if ( maxcuts > 0 && (d.eigvals == NULL || d.coefs == NULL || d.lhs == NULL) )
-      return HIPSDP_ERR_ARG;
-   for (int b = 0; b < nb; ++b)
-      if ( sizes[b] < 1 )
-         return HIPSDP_ERR_ARG;
    for (int b = 0; b < nb; ++b)
       d.ncuts[b] = -1;
-   /* the blocks this call serves: whole matrices on this device (none for a solver with a communicator or sharded matrices), 129 .. 512
-    * rows, and with recomputesparseev a target size the decomposition of Z_S takes */
-   std::vector<int> all, ids;
-   HS_CALL( hs_solver_cut_enter_large(s, HIPSDP_SPARSECUTS_MAXN, &all) );
+   /* the blocks this call serves: 129 .. 512 rows, and with recomputesparseev a target size the decomposition of Z_S takes */
    const bool sparseev = (variant & HS_SCR_SPARSEEV) != 0;
-   for (int b : all)
-      if ( hs_solver_block_n(s, b) > HS_SC_MAXN && !(sparseev && sizes[b] > HS_SC_MAXN) )
-         ids.push_back(b);
+   std::vector<int> ids;
+   HS_CALL( large_served(s, HIPSDP_SPARSECUTS_MAXN, [&](int b) { return !(sparseev && sizes[b] > HS_SC_MAXN); }, &ids) );
    if ( ids.empty() )
       return HIPSDP_OK;
-   std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
    const int total = (int) ids.size();
    std::vector<long long> job_len((size_t) total);
    for (int k = 0; k < total; ++k)
       job_len[k] = sclr_block(hs_solver_block_n(s, ids[k]), sparseev ? sizes[ids[k]] : 0).len;
-   int maxjobs = 0;
-   const char* env = getenv("HIPSDP_SPARSECUTS_LARGE_CHUNK");          /* (read at every call, like HIPSDP_ONEVAR_LARGE_CHUNK) */
-   if ( env != NULL && atoi(env) > 0 )
-      maxjobs = atoi(env);
-   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts, -1);
-   for (int start = 0; start < total; )
-   {
-      /* (a block count stands alone: blocks of equal n differ in their Z_S, so no budget in doubles expresses it) */
-      const int end = hs_ovl_chunk_end(job_len.data(), total, start, maxjobs > 0 ? std::numeric_limits<long long>::max() / 2 : SCLR_BUDGET, maxjobs);
-      const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
-      HS_CALL( sclr_chunk(s, m, nb, chunk, y, sizes, opts, variant, d, gvecoff) );
-      start = end;
-   }
+   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts);
+   HS_CALL( hs_chunks_run(job_len.data(), total, SCLR_BUDGET, hs_chunk_env("HIPSDP_SPARSECUTS_LARGE_CHUNK"), [&](int start, int end)
+      {
+         const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
+         return sclr_chunk(s, m, nb, chunk, y, sizes, opts, variant, d, gvecoff);
+      }) );
    ++g_scl.calls;
    return HIPSDP_OK;
 }
@@ -622,47 +655,29 @@ int ecl_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, cons
    const std::vector<long long>& gvecoff)
 {
    const int cnt = (int) ids.size();
-   /* the chunk's result: indexed by the block's number, vectors of the chunk's blocks alone */
-   std::vector<long long> vecoff((size_t) nb + 1, 0);
-   {
-      std::vector<char> in((size_t) nb, 0);
-      for (int b : ids)
-         in[b] = 1;
-      for (int b = 0; b < nb; ++b)
-         vecoff[b + 1] = vecoff[b] + (in[b] ? (long long) maxcuts * hs_solver_block_n(s, b) : 0);
-   }
-   int nmax = 0;
-   long long blocks_len = 0;
    std::vector<hs_ecl_block> B((size_t) cnt);
-   std::vector<long long> start((size_t) cnt), zoff((size_t) cnt);
    for (int j = 0; j < cnt; ++j)
-   {
-      const int n = hs_solver_block_n(s, ids[j]);
-      nmax = n > nmax ? n : nmax;
-      B[j] = ecl_block(n);
-      start[j] = blocks_len;
-      blocks_len += B[j].len;
-   }
-   hs_ecl_layout L;
-   hs_ecl_layout_make(nb, m, maxcuts, vecoff[nb], cnt, SCLR_JOBW, blocks_len, &L);
+      B[j] = ecl_block(hs_solver_block_n(s, ids[j]));
    /* Z(y) of a block goes where the column launches read their matrix: the head of the block's workspace (hs_sxm_job.A) */
-   for (int j = 0; j < cnt; ++j)
-      zoff[j] = L.blocks + start[j] + B[j].ws;
-   hs_solver_cut_ws w;
-   HS_CALL( hs_solver_cut_blocks(s, ids, zoff, L.len.dev_len, L.len.pin_len, &w) );
+   hs_ecl_layout L;
+   LargeRun R;
+   HS_CALL( large_begin(s, m, nb, ids, y, maxcuts, [&](int j) { return B[j].len; },
+         [&](long long vec_len, long long blocks_len, hs_ecl_layout* l) { hs_ecl_layout_make(nb, m, maxcuts, vec_len, cnt, SCLR_JOBW, blocks_len, l); },
+         [&](int j) { return B[j].ws; }, &L, &R) );
+   const hs_solver_cut_ws& w = R.w;
+   const int nmax = R.nmax;
+   int& launches = R.launches;
    hipStream_t st = w.stream;
-   if ( m > 0 )
-      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
    hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
    long long* hvo = reinterpret_cast<long long*>(w.pin + L.vecoff);
    int* hact = reinterpret_cast<int*>(w.pin + L.act);
    for (int j = 0; j < cnt; ++j)
    {
-      double* base = w.dev + L.blocks + start[j];
+      double* base = w.dev + R.start[j];
       HS_CALL( hs_syevx_many_below_job(hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, &hsx[j]) );
-      if ( hsx[j].A != w.dev + zoff[j] )
+      if ( hsx[j].A != base + B[j].ws )
          return HIPSDP_ERR_NUMERIC;
-      hvo[j] = vecoff[ids[j]];
+      hvo[j] = R.vecoff[ids[j]];
       hact[j] = HS_SXM_ACTIVE;
    }
    HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
@@ -671,25 +686,17 @@ int ecl_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, cons
    const long long* dvo = reinterpret_cast<const long long*>(w.dev + L.vecoff);
    const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
    const hs_sc_out out = hs_cut_view(L.r, w.dev);
-   int launches = 0;
    HS_CALL( hs_ec_form_z(st, cnt, nmax, m, w.djobs, w.dev + L.y) );
    HS_CALL( hs_ecl_clear(st, cnt, dsx) );
    launches += 2;
-   HS_CALL( hs_syevx_many_cols(st, cnt, nmax, sclr_cap(cnt), dsx, dact) );
+   HS_CALL( hs_syevx_many_cols(st, cnt, nmax, hs_syevx_many_cap(cnt), dsx, dact) );
    launches += nmax - 1;
    /* eigenvalue <= -tol, most negative first, at most maxcuts: the count of the selection is the number of cuts */
    HS_CALL( hs_syevx_many_below(st, cnt, nmax, -tol, maxcuts, dsx, dact) );
    launches += maxcuts > 0 ? 3 : 1;
    HS_CALL( hs_ecl_cuts(st, cnt, nmax, m, maxcuts, w.djobs, dsx, dvo, &out) );
    ++launches;
-   HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost, st) );
-   HS_HIP( hipStreamSynchronize(st) );
-   g_ecl.launches += launches;
-   g_ecl.readbacks += 1;
-   const hs_sc_out h = hs_cut_view(L.r, w.pin);
-   for (int b : ids)
-      HS_CALL( cut_block_out(h, b, h.ncuts[b], maxcuts, vecoff[b], m, hs_solver_block_n(s, b), d.block(b, maxcuts, m, gvecoff[b])) );
-   return HIPSDP_OK;
+   return large_end(s, R, m, ids, maxcuts, &g_ecl, d, gvecoff);
 }
 
 int eigencuts_all_large_impl(hipsdp_solver* s, const double* y, double tol, int maxcuts, const CutDst& d)
@@ -701,32 +708,21 @@ int eigencuts_all_large_impl(hipsdp_solver* s, const double* y, double tol, int 
       return HIPSDP_ERR_ARG;
    for (int b = 0; b < nb; ++b)
       d.ncuts[b] = -1;
-   /* the blocks this call serves: whole matrices on this device (none for a solver with a communicator or sharded matrices), 129 .. 512
-    * rows */
-   std::vector<int> all, ids;
-   HS_CALL( hs_solver_cut_enter_large(s, HIPSDP_EIGENCUTS_LARGE_MAXN, &all) );
-   for (int b : all)
-      if ( hs_solver_block_n(s, b) > HS_SC_MAXN )
-         ids.push_back(b);
+   /* the blocks this call serves: 129 .. 512 rows */
+   std::vector<int> ids;
+   HS_CALL( large_served(s, HIPSDP_EIGENCUTS_LARGE_MAXN, [](int) { return true; }, &ids) );
    if ( ids.empty() )
       return HIPSDP_OK;
-   std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
    const int total = (int) ids.size();
    std::vector<long long> job_len((size_t) total);
    for (int k = 0; k < total; ++k)
       job_len[k] = ecl_block(hs_solver_block_n(s, ids[k])).len;
-   int maxjobs = 0;
-   const char* env = getenv("HIPSDP_EIGENCUTS_LARGE_CHUNK");           /* (read at every call, like HIPSDP_SPARSECUTS_LARGE_CHUNK) */
-   if ( env != NULL && atoi(env) > 0 )
-      maxjobs = atoi(env);
-   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts, -1);
-   for (int start = 0; start < total; )
-   {
-      const int end = hs_ovl_chunk_end(job_len.data(), total, start, maxjobs > 0 ? std::numeric_limits<long long>::max() / 2 : SCLR_BUDGET, maxjobs);
-      const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
-      HS_CALL( ecl_chunk(s, m, nb, chunk, y, tol, maxcuts, d, gvecoff) );
-      start = end;
-   }
+   const std::vector<long long> gvecoff = cut_vecoff(s, nb, maxcuts);
+   HS_CALL( hs_chunks_run(job_len.data(), total, SCLR_BUDGET, hs_chunk_env("HIPSDP_EIGENCUTS_LARGE_CHUNK"), [&](int start, int end)
+      {
+         const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
+         return ecl_chunk(s, m, nb, chunk, y, tol, maxcuts, d, gvecoff);
+      }) );
    ++g_ecl.calls;
    return HIPSDP_OK;
 }
@@ -776,7 +772,7 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
    std::vector<int> ids;
    HS_CALL( hs_solver_cut_enter(s, -1, &ids) );
    const CutDst dst = {ncuts, lmin, eigvals, coefs, lhs, vecs, NULL, NULL};
-   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts, -1);
+   const std::vector<long long> vecoff = cut_vecoff(s, nb, maxcuts);
    const int nj = (int) ids.size();
    std::vector<char> served((size_t) nb, 0);
    if ( nj > 0 )
@@ -799,12 +795,8 @@ extern "C" int hipsdp_eigencuts_all(hipsdp_solver* s, const double* y, double to
       HS_CALL( hs_syev_small_many(st, nj, w.ejobs, w.dejobs, &launches) );
       HS_CALL( hs_ec_cuts(st, nj, nmax, m, nb, maxcuts, tol, w.djobs, w.dev + L.len.res_off) );
       ++launches;
-      HS_HIP( hipMemcpyAsync(w.pin + L.len.res_off, w.dev + L.len.res_off, (size_t) L.len.res_len * sizeof(double), hipMemcpyDeviceToHost,
-            st) );
-      HS_HIP( hipStreamSynchronize(st) );
-      g_ec.launches += launches;
-      g_ec.readbacks += 1;
-      const hs_sc_out h = hs_cut_view(L.r, w.pin);
+      hs_sc_out h;
+      HS_CALL( cut_readback(w, L.r, L.len, launches, &g_ec, &h) );
       for (int b : ids)
       {
          const int k = (int) w.pin[L.ncuts + b], n = hs_solver_block_n(s, b);

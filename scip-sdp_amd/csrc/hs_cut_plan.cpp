@@ -154,17 +154,3 @@ void hs_ecl_layout_make(int nb, int m, int maxcuts, long long vec_len, int count
    L->len.res_len = L->r.sup - L->len.res_off;
    L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->blocks + blocks_len;
 }
-
-int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs)
-{
-   long long used = 0;
-   int k = start;
-   while ( k < count )
-   {
-      if ( k > start && (used + job_len[k] > budget || (maxjobs > 0 && k - start >= maxjobs)) )
-         break;
-      used += job_len[k];
-      ++k;
-   }
-   return k;
-}

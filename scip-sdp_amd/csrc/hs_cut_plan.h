@@ -81,9 +81,6 @@ void hs_ova_layout_make(int m, int count, int tabw, int resw, long long z_len, i
 struct hs_ovl_layout { long long u, tab, jobs, act, nactive, res, state, Z, slabs; hs_cut_lens len; };
 void hs_ovl_layout_make(int m, int count, int tabw, int jobw, int resw, int statew, long long z_len, const long long* ws_len,
    const long long* out_len, long long* ws, long long* out, hs_ovl_layout* L);
-/* the chunks of a call: jobs start .. (return value - 1) of a list ordered by descending n form the next chunk - as many as fit into
- * `budget` doubles of job_len[] (workspace + output of a job), at least one, and at most maxjobs when maxjobs > 0 */
-int hs_ovl_chunk_end(const long long* job_len, int count, int start, long long budget, int maxjobs);
 
 /* hipsdp_sparsecuts_all_large (csrc/sparsecuts_large_rounds.hip), ONE CHUNK of `count` served blocks of a solver with nb blocks:
  *    y[m] | sizes[nb] (int) | tridiagonal jobs [count][jobw] | block table [count][xjobw] | Z_S jobs [count][sjobw] | act[count] (int)

@@ -589,7 +589,8 @@ int hs_syevx_select_dev(hipStream_t st, int n, int mode, int il, int iu, double 
  * The caller's own kernel writes the symmetric matrix to A (n x n, no pitch) and zeros to R (n x n) before hs_syevx_many_cols.
  * hs_syevx_many_job fills an entry from the matrix's workspace (hs_syevx_ws(n) doubles) and output (HS_SXM_OUT(n) doubles).
  * hs_syevx_many_cols: nmax - 1 launches (nmax: the largest n of the table; cap: workgroups per matrix at most - the bits do not depend
- * on it); hs_syevx_many_select: 3 launches (both != 0: some matrix may carry HS_SXM_BOTH).  No launch depends on act. */
+ * on it; hs_syevx_many_cap(count): the cap the calls use that name none, 4 x compute units / count within 8 .. 128);
+ * hs_syevx_many_select: 3 launches (both != 0: some matrix may carry HS_SXM_BOTH).  No launch depends on act. */
 #define HS_SXM_ACTIVE 1
 #define HS_SXM_VEC    2
 #define HS_SXM_BOTH   4
@@ -597,6 +598,7 @@ int hs_syevx_select_dev(hipStream_t st, int n, int mode, int il, int iu, double 
 struct hs_sxm_job { int n, pad; double* ws; double* A; double* R; double* out; double* out2; };
 int hs_syevx_many_job(int n, double* ws, double* out, hs_sxm_job* J);
 int hs_syevx_many_cols(hipStream_t st, int count, int nmax, int cap, const hs_sxm_job* djobs, const int* dact);
+int hs_syevx_many_cap(int count);
 int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs_sxm_job* djobs, const int* dact);
 /* SEVERAL pairs per matrix on the forms hs_syevx_many_cols leaves: the eigenvalues <= bound of every matrix with act != 0, at most maxk
  * <= HS_SYEVX_MAXK of them, ascending, with their unit vectors - to out in the layout of hs_syevx_dev (HS_SYEVX_OUT(n): pairs returned

@@ -1,5 +1,6 @@
 /* hs_psd_large_plan.cpp - see hs_psd_large_plan.h */
 #include "hs_psd_large_plan.h"
+#include "hs_chunks.h"
 #include <stddef.h>
 #include <algorithm>
 
@@ -56,16 +57,10 @@ int hs_ppl_chunk_make(std::vector<hs_ppl_item>* items, int start, long long budg
       || start >= (int) items->size() )
       return HIPSDP_ERR_ARG;
    const int total = (int) items->size();
-   long long used = 0;
-   int k = start;
-   while ( k < total )
-   {
-      const long long len = (*items)[(size_t) k].len;
-      if ( k > start && used + len > budget )
-         break;
-      used += len;
-      ++k;
-   }
+   std::vector<long long> len((size_t) total);
+   for (int i = 0; i < total; ++i)
+      len[(size_t) i] = (*items)[(size_t) i].len;
+   const int k = hs_chunk_end(len.data(), total, start, budget, 0);
    chunk->first = start; chunk->end = k;
    chunk->nmax = 0;
    chunk->trips = chunk->ws_len = chunk->out_len = chunk->cnt_len = chunk->res_len = 0;

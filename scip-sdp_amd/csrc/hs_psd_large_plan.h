@@ -42,9 +42,8 @@ int hs_ppl_check(int count, const hipsdp_psd_job* jobs, int mode);
 /* the served jobs (HIPSDP_PSD_LARGE_MINN <= n <= HIPSDP_PSD_LARGE_MAXN), largest first, caller's order among equal sizes, with
  * job, n, nnz, cap, ntc and len filled in; jobs must have passed hs_ppl_check */
 int hs_ppl_items(int count, const hipsdp_psd_job* jobs, const hs_ppl_rules* rules, std::vector<hs_ppl_item>* items);
-/* the chunk that starts at item `start`: as many items as fit `budget` bytes of workspace, at least one (the rule of hs_ovl_chunk_end,
- * hs_cut_plan.h, restated here so that this file and its check program link without the cut planning); fills the offsets of its items
- * and returns its description */
+/* the chunk that starts at item `start`: as many items as fit `budget` bytes of workspace, at least one (hs_chunk_end of hs_chunks.h
+ * over the items' len); fills the offsets of its items and returns its description */
 int hs_ppl_chunk_make(std::vector<hs_ppl_item>* items, int start, long long budget, const hs_ppl_rules* rules, hs_ppl_chunk* chunk);
 /* kernel launches of a chunk whose largest job has nmax rows: nmax + 8 + 6 ceil(nmax / 32)
  *    1 expand, nmax - 1 columns of the tridiagonalisation, 2 for the eigenvalues and their order, 3 + 6 ceil(nmax / 32) for the

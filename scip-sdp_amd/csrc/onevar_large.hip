@@ -13,7 +13,7 @@
  *
  * A job needs hs_syevx_ws(n) + HS_SXM_OUT(n) doubles (4.7 MB at 512 rows) in the solver's grow-only cut workspace, so the jobs are
  * ordered by descending n and run in CHUNKS of at most 512 MiB of such workspace (HIPSDP_ONEVAR_LARGE_CHUNK in the environment: a job
- * count instead), one chunk after the other on the solver's stream; the layout of a chunk: hs_ovl_layout, hs_cut_plan.h.  A chunk is a
+ * count instead; hs_chunks.h), one chunk after the other on the solver's stream; the layout of a chunk: hs_ovl_layout, hs_cut_plan.h.  A chunk is a
  * call of its own in everything but the entry: its blocks, their Z(u), its rounds, its read-backs.  The bits of a job depend on
  * nothing but the job: every entry of M has one writer, no sum crosses workgroups, and the number of workgroups per job (fewer when
  * there are many jobs) only decides who owns which rows.
@@ -22,10 +22,10 @@
  * The solver is seen through hs_solver_dims, hs_solver_block_n, hs_solver_cut_enter_large and hs_solver_cut_blocks (hs_kernels.h). */
 #include "hs_common.h"
 #include "hs_kernels.h"
+#include "hs_chunks.h"
 #include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -57,15 +57,6 @@ void hs_onevar_large_plan(int m, int count, const hs_ovl_row* rows, long long z_
    ws->assign((size_t) count, 0);
    out->assign((size_t) count, 0);
    hs_ovl_layout_make(m, count, HS_OVA_TAB, OVL_JOBW, HS_OV_RES, HS_OVL_STATE, z_len, wl.data(), ol.data(), ws->data(), out->data(), L);
-}
-
-/* workgroups per job of the column launches when the caller names none: about four workgroups per compute unit over all jobs, at least
- * 8 (a job of 512 rows then has 16 rows per wavefront and launch), at most the 128 of a matrix alone */
-static int ovl_default_cap(int count)
-{
-   const int cus = hs_device_cus();
-   const int g = (4 * (cus > 0 ? cus : 256)) / count;
-   return g < 8 ? 8 : (g > 128 ? 128 : g);
 }
 
 int hs_onevar_large_chunk(hipStream_t st, const hs_ovl_chunk* c, const hs_ovl_layout& L, const std::vector<long long>& ws,
@@ -101,7 +92,7 @@ int hs_onevar_large_chunk(hipStream_t st, const hs_ovl_chunk* c, const hs_ovl_la
       HS_CALL( hs_ec_form_z(st, c->nz, c->nzmax, c->m, c->dblocks, dev + L.u) );
       *launches += 1;
    }
-   const int cap = c->cap > 0 ? (c->cap < 128 ? c->cap : 128) : ovl_default_cap(count);
+   const int cap = c->cap > 0 ? (c->cap < 128 ? c->cap : 128) : hs_syevx_many_cap(count);
    hs_ovl_par P;
    memset(&P, 0, sizeof(P));
    P.count = count; P.maxevals = c->maxevals; P.grid = cap < 64 ? cap : 64;
@@ -200,16 +191,11 @@ extern "C" int hipsdp_onevar_bounds_large(hipsdp_solver* s, const double* u, int
    std::vector<long long> job_len((size_t) total);
    for (int k = 0; k < total; ++k)
       job_len[k] = hs_onevar_large_job_len(hs_solver_block_n(s, block_of(list[k])));
-   int maxjobs = 0;
-   const char* env = getenv("HIPSDP_ONEVAR_LARGE_CHUNK");           /* (read at every call, like HIPSDP_OBJECTIVES_CHUNK) */
-   if ( env != NULL && atoi(env) > 0 )
-      maxjobs = atoi(env);
    const int maxevals = opts->maxevals > 0 ? opts->maxevals : 100;
 
-   long long launches = 0, readbacks = 0;
-   for (int start = 0; start < total; )
+   /* one chunk: jobs start .. end - 1 of the list */
+   auto chunk = [&](int start, int end) -> int
    {
-      const int end = hs_ovl_chunk_end(job_len.data(), total, start, maxjobs > 0 ? job_len[start] * maxjobs : OVL_BUDGET, maxjobs);
       const int cnt = end - start;
       /* the chunk's blocks, those with a NEWTON or TWOPOINT job first: k_ec_form_z runs over that head alone */
       std::vector<int> use((size_t) nb, -1), entry((size_t) nb, -1), tids;
@@ -253,9 +239,9 @@ extern "C" int hipsdp_onevar_bounds_large(hipsdp_solver* s, const double* u, int
       c.feastol = opts->feastol; c.infinity = opts->infinity;
       c.u = u; c.rows = rows.data(); c.dblocks = w.djobs; c.dev = w.dev; c.pin = w.pin;
       int rounds = 0;
+      long long launches = 0, readbacks = 0;
       const int rc = hs_onevar_large_chunk(w.stream, &c, L, wso, outo, &launches, &readbacks, &rounds);
       g_ovl.launches += launches; g_ovl.readbacks += readbacks;
-      launches = readbacks = 0;
       HS_CALL( rc );
       for (int k = 0; k < cnt; ++k)
       {
@@ -269,8 +255,9 @@ extern "C" int hipsdp_onevar_bounds_large(hipsdp_solver* s, const double* u, int
          if ( grad != NULL ) grad[j] = r[3];
          if ( evals != NULL ) evals[j] = (int) r[4];
       }
-      start = end;
-   }
+      return HIPSDP_OK;
+   };
+   HS_CALL( hs_chunks_run(job_len.data(), total, OVL_BUDGET, hs_chunk_env("HIPSDP_ONEVAR_LARGE_CHUNK"), chunk) );
    ++g_ovl.calls;
    return HIPSDP_OK;
 }

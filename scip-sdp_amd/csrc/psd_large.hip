@@ -26,9 +26,9 @@
  * whatever the batch, the chunking, the position and the calling thread. */
 #include "hs_kernels.h"
 #include "hs_psd_large_plan.h"
+#include "hs_chunks.h"
+#include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
-#include <atomic>
-#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -315,18 +315,10 @@ int ppl_grow(ppl_ctx* c, size_t up, size_t work, size_t out)
 size_t ppl_up16(size_t b) { return (b + 15) & ~(size_t) 15; }
 size_t ppl_up256(size_t b) { return (b + 255) & ~(size_t) 255; }
 
-std::atomic<long long> g_calls(0), g_launches(0), g_readbacks(0);
+CutStats g_stats;
 
 long long ppl_ws_len(int n) { return (long long) hs_syevr_ws(n); }
 long long ppl_out_len(int n) { return HS_SYEVR_OUT(n); }
-
-/* workgroups per matrix of a column launch (as the cut calls): four waves of workgroups over the device, 8 .. 128 */
-int ppl_cap(int count)
-{
-   const int cus = hs_device_cus();
-   const int g = (4 * (cus > 0 ? cus : 256)) / count;
-   return g < 8 ? 8 : (g > 128 ? 128 : g);
-}
 
 /* one chunk of served jobs; *overflow: some job did not fit its cap */
 int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_item>& items, const hs_ppl_chunk& C, double epsilon, int mode,
@@ -391,7 +383,7 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
       hipLaunchKernelGGL(k_ppl_expand, dim3(PL_EG, (unsigned) nb), dim3(PL_NT), 0, st, dtab, reinterpret_cast<const int*>(c->dwork + u_row),
          reinterpret_cast<const int*>(c->dwork + u_col), reinterpret_cast<const double*>(c->dwork + u_val));
       ++launches;
-      if ( (rc = hs_syevx_many_cols(st, (int) nb, C.nmax, ppl_cap((int) nb), dsx, dact)) != HS_OK )
+      if ( (rc = hs_syevx_many_cols(st, (int) nb, C.nmax, hs_syevx_many_cap((int) nb), dsx, dact)) != HS_OK )
          break;
       launches += C.nmax - 1;
       if ( (rc = hs_syevr_many_tvec(st, (int) nb, C.nmax, dsr)) != HS_OK )
@@ -411,9 +403,9 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
       e = hipMemcpyAsync(c->hout, dres, res_bytes, hipMemcpyDeviceToHost, st);
       if ( e != hipSuccess ) { hs_record_hip_error(e, "hipMemcpyAsync(psd_project_many_large, result)", __FILE__, __LINE__); rc = HS_ERR_HIP; }
    } while ( false );
-   g_launches += launches;
+   g_stats.launches += launches;
    const hipError_t es = hipStreamSynchronize(st);
-   ++g_readbacks;
+   ++g_stats.readbacks;
    if ( rc == HS_OK && es != hipSuccess )
    {
       hs_record_hip_error(es, "hipStreamSynchronize(psd_project_many_large)", __FILE__, __LINE__);
@@ -543,17 +535,15 @@ extern "C" int hipsdp_psd_project_many_large(int device, int count, hipsdp_psd_j
    if ( device >= nd )
       return HIPSDP_ERR_ARG;
    HS_HIP( hipSetDevice(device) );
-   ++g_calls;
+   ++g_stats.calls;
    std::vector<hs_ppl_item> items;
    HS_CALL( hs_ppl_items(count, jobs, &rules, &items) );
    /* a job this call does not serve: nnz_out = -1, nothing written (the convention of hipsdp_eigencuts_all_large) */
    for (int j = 0; j < count; ++j)
       if ( jobs[j].n < HIPSDP_PSD_LARGE_MINN || jobs[j].n > HIPSDP_PSD_LARGE_MAXN )
          jobs[j].nnz_out = -1;
-   long long budget = 512LL * 1024 * 1024;
-   const char* env = getenv("HIPSDP_PSD_LARGE_CHUNK");                 /* MiB of workspace per chunk (read at every call) */
-   if ( env != NULL && atoi(env) > 0 )
-      budget = (long long) atoi(env) * 1024 * 1024;
+   const int mib = hs_chunk_env("HIPSDP_PSD_LARGE_CHUNK");             /* MiB of workspace per chunk (read at every call) */
+   const long long budget = (mib > 0 ? mib : 512LL) * 1024 * 1024;
    bool overflow = false;
    for (int start = 0; start < (int) items.size(); )
    {
@@ -567,8 +557,5 @@ extern "C" int hipsdp_psd_project_many_large(int device, int count, hipsdp_psd_j
 
 extern "C" int hipsdp_psd_project_many_large_stats(long long* calls, long long* launches, long long* readbacks)
 {
-   if ( calls != NULL ) *calls = g_calls.load();
-   if ( launches != NULL ) *launches = g_launches.load();
-   if ( readbacks != NULL ) *readbacks = g_readbacks.load();
-   return HIPSDP_OK;
+   return g_stats.get(calls, launches, readbacks);
 }

@@ -533,6 +533,15 @@ int hs_syevx_many_cols(hipStream_t st, int count, int nmax, int cap, const hs_sx
    return HS_OK;
 }
 
+/* the `cap` of a call that names none: about four workgroups per compute unit over all `count` matrices, at least 8 (a matrix of 512
+ * rows then has 16 rows per wavefront and launch), at most the 128 of a matrix alone */
+int hs_syevx_many_cap(int count)
+{
+   const int cus = hs_device_cus();
+   const int g = (4 * (cus > 0 ? cus : 256)) / count;
+   return g < 8 ? 8 : (g > 128 ? 128 : g);
+}
+
 /* three launches, whatever the flags say: the values (both: a second row of workgroups for eigenvalue n), the vector of T, its
  * back-transformation */
 int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs_sxm_job* djobs, const int* dact)

@@ -3,6 +3,7 @@
  * per-call allocations - fine for tests, not for the product: what lapack_interface_hip.c calls (hipsdp_dgemm, hipsdp_gemv_*,
  * hipsdp_syev) lives in host_entries.hip.  Nothing here has a CPU code path. */
 #include "hs_kernels.h"
+#include "hs_chunks.h"
 #include "hs_gram_cache.h"
 #include "../../include/hipsdp.h"
 #include "../../include/hipsdp_units.h"
@@ -1787,9 +1788,9 @@ extern "C" int hipsdp_onevar_large_unit(int device, int count, const int* n, con
          memcpy(ha.data() + 2 * off[j] + (long long) n[j] * n[j], A + off[j], (size_t) n[j] * n[j] * sizeof(double));
       HS_CALL( da.up(ha.data(), 2 * tot) );
    }
-   for (int start = 0; start < total; )
+   /* one chunk: jobs start .. end - 1 of the list (chunk <= 0: no budget, all jobs at once) */
+   auto run = [&](int start, int end) -> int
    {
-      const int end = hs_ovl_chunk_end(job_len.data(), total, start, chunk > 0 ? job_len[start] * chunk : (1LL << 40), chunk > 0 ? chunk : 0);
       const int cnt = end - start;
       std::vector<hs_ovl_row> rows((size_t) cnt);
       long long zlen = 0;
@@ -1844,9 +1845,9 @@ extern "C" int hipsdp_onevar_large_unit(int device, int count, const int* n, con
          if ( grad != NULL ) grad[j] = q[3];
          if ( evals != NULL ) evals[j] = (int) q[4];
       }
-      start = end;
-   }
-   return HIPSDP_OK;
+      return HIPSDP_OK;
+   };
+   return hs_chunks_run(job_len.data(), total, 1LL << 40, chunk > 0 ? chunk : 0, run);
 }
 
 /* k_sc_tpower_large alone (csrc/sparsecuts_large.hip) on one host matrix: lmin is given as -1 with tol = -infinity, so the matrix

@@ -1,5 +1,5 @@
 /* cut_plan_ecl_check.cpp - stand-alone check of the chunk layout of hipsdp_eigencuts_all_large (hs_ecl_layout_make, hs_ecl_block_make,
- * hs_ecl_launches: scip-sdp_amd/csrc/hs_cut_plan.h/.cpp) and of its chunks (hs_ovl_chunk_end), meant to be compiled with the host
+ * hs_ecl_launches: scip-sdp_amd/csrc/hs_cut_plan.h/.cpp) and of its chunks (hs_chunk_end), meant to be compiled with the host
  * compiler and -fsanitize=address,undefined (tests/test_eigencuts_all_large_cpu.py does that).
  *     y[m] | tridiagonal jobs | vecoff (long long) | act (int) | res (lmin, eig, lhs, coef, vec, ints) | per block: workspace of the
  *     tridiagonal form | selection output
@@ -11,6 +11,7 @@
  * compared with literal numbers.
  * Prints "cut plan ecl check: ok" and returns 0, or says what failed and returns 1. */
 #include "hs_cut_plan.h"
+#include "hs_chunks.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -115,7 +116,7 @@ static int chunks(void)
    int start = 0, n = 0;
    while ( start < 200 )
    {
-      const int end = hs_ovl_chunk_end(len.data(), 200, start, budget, 0);
+      const int end = hs_chunk_end(len.data(), 200, start, budget, 0);
       long long used = 0;
       for (int k = start; k < end; ++k) used += len[k];
       CHECK( end > start && end <= 200 && (used <= budget || end == start + 1) );
@@ -126,10 +127,10 @@ static int chunks(void)
    CHECK( n == 2 );
    /* the environment override, a block count instead: one per chunk, three per chunk */
    const long long nolimit = 1LL << 60;                        /* (what the call passes with a block count) */
-   for (int k = 0; k < 200; ++k) CHECK( hs_ovl_chunk_end(len.data(), 200, k, nolimit, 1) == k + 1 );
-   CHECK( hs_ovl_chunk_end(len.data(), 200, 0, nolimit, 3) == 3 && hs_ovl_chunk_end(len.data(), 200, 199, nolimit, 3) == 200 );
-   CHECK( hs_ovl_chunk_end(len.data(), 200, 149, nolimit, 3) == 152 );
-   CHECK( hs_ovl_chunk_end(len.data(), 200, 5, 1, 0) == 6 && hs_ovl_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
+   for (int k = 0; k < 200; ++k) CHECK( hs_chunk_end(len.data(), 200, k, nolimit, 1) == k + 1 );
+   CHECK( hs_chunk_end(len.data(), 200, 0, nolimit, 3) == 3 && hs_chunk_end(len.data(), 200, 199, nolimit, 3) == 200 );
+   CHECK( hs_chunk_end(len.data(), 200, 149, nolimit, 3) == 152 );
+   CHECK( hs_chunk_end(len.data(), 200, 5, 1, 0) == 6 && hs_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
    return 0;
 }
 

@@ -1,5 +1,5 @@
 /* cut_plan_large_check.cpp - stand-alone check of the chunk layout of hipsdp_sparsecuts_all_large (hs_sclr_layout_make,
- * hs_sclr_block_make, hs_sclr_launches: scip-sdp_amd/csrc/hs_cut_plan.h/.cpp) and of its chunks (hs_ovl_chunk_end), meant to be compiled
+ * hs_sclr_block_make, hs_sclr_launches: scip-sdp_amd/csrc/hs_cut_plan.h/.cpp) and of its chunks (hs_chunk_end), meant to be compiled
  * with the host compiler and -fsanitize=address,undefined (tests/test_sparsecuts_all_large_cpu.py does that).
  *     y[m] | sizes[nb] (int) | tridiagonal jobs | block table | Z_S jobs | act (int) | res | sup | per block: state | v0 | Z | MT | Z_S |
  *     its slab | workspace of the tridiagonal form | selection output
@@ -10,6 +10,7 @@
  * budget unless a chunk is one block, and respect the block cap.  The launch formula is compared with literal numbers.
  * Prints "cut plan large check: ok" and returns 0, or says what failed and returns 1. */
 #include "hs_cut_plan.h"
+#include "hs_chunks.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -137,7 +138,7 @@ static int chunks(void)
    int start = 0, n = 0;
    while ( start < 100 )
    {
-      const int end = hs_ovl_chunk_end(len.data(), 100, start, budget, 0);
+      const int end = hs_chunk_end(len.data(), 100, start, budget, 0);
       long long used = 0;
       for (int k = start; k < end; ++k) used += len[k];
       CHECK( end > start && end <= 100 && (used <= budget || end == start + 1) );
@@ -148,10 +149,10 @@ static int chunks(void)
    CHECK( n == 2 );
    /* a block count instead: one per chunk, three per chunk */
    const long long nolimit = 1LL << 60;                        /* (what the call passes with a block count) */
-   for (int k = 0; k < 100; ++k) CHECK( hs_ovl_chunk_end(len.data(), 100, k, nolimit, 1) == k + 1 );
-   CHECK( hs_ovl_chunk_end(len.data(), 100, 0, nolimit, 3) == 3 && hs_ovl_chunk_end(len.data(), 100, 99, nolimit, 3) == 100 );
-   CHECK( hs_ovl_chunk_end(len.data(), 100, 69, nolimit, 3) == 72 );
-   CHECK( hs_ovl_chunk_end(len.data(), 100, 5, 1, 0) == 6 && hs_ovl_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
+   for (int k = 0; k < 100; ++k) CHECK( hs_chunk_end(len.data(), 100, k, nolimit, 1) == k + 1 );
+   CHECK( hs_chunk_end(len.data(), 100, 0, nolimit, 3) == 3 && hs_chunk_end(len.data(), 100, 99, nolimit, 3) == 100 );
+   CHECK( hs_chunk_end(len.data(), 100, 69, nolimit, 3) == 72 );
+   CHECK( hs_chunk_end(len.data(), 100, 5, 1, 0) == 6 && hs_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
    return 0;
 }
 

@@ -3,6 +3,8 @@ restatement oracle/eigcuts_ref.cuts_dense, shared by the CPU test of their margi
 eigencuts_all_large_rate.py.  The families are those of sparsecuts_all_large_cases.py:
 
   "f3"   : blocks of 16, 150, 48, 200, 10 rows, m = 25; the call serves blocks 1 and 3;
+  "f4"   : blocks of 130, 12, 129, 131 rows, m = 25 (CHUNKED): the call serves blocks 0, 2 and 3; compared with nothing but itself, the
+           same call in one, two and three chunks, so it has no ROWS;
   "n129", "n257", "n512": one block each at the point y of that file - 129 rows is the first size of the path (two wavefronts and one
            row), 257 is one past a power of two, 512 is the cap.
 
@@ -22,6 +24,7 @@ ROWS = [("f3", 1, 150), ("f3", 3, 200), ("n129", 0, 129), ("n257", 0, 257), ("n5
 # the margins every compared row has to keep (measured: smallest relative gap 1.4e-3, nearest eigenvalue to -tol 3.2e-3)
 MIN_GAP, MIN_TOL_DIST = 1e-3, 1e-3
 
+CHUNKED = S.CHUNKED
 family = S.family
 large_blocks = S.large_blocks
 _ref, _spec = {}, {}

@@ -1,5 +1,5 @@
 /* onevar_large_plan_check.cpp - stand-alone check of the chunk layout and the chunk splitter of hipsdp_onevar_bounds_large
- * (hs_ovl_layout_make, hs_ovl_chunk_end: scip-sdp_amd/csrc/hs_cut_plan.cpp), meant to be compiled with the host compiler and
+ * (hs_ovl_layout_make: scip-sdp_amd/csrc/hs_cut_plan.cpp; hs_chunk_end, hs_chunks_run: csrc/hs_chunks.h), meant to be compiled with the host compiler and
  * -fsanitize=address,undefined (tests/test_onevar_large_cpu.py does that).
  *     u[m] | table | job table | act (int) | nactive | result | state | Z of the chunk's blocks | per job: workspace, output
  * Over m = 0, 1, 6, 7, count = 1 .. 9 jobs of mixed rows the parts must come in that order, pairwise disjoint, each at an even offset,
@@ -8,6 +8,7 @@
  * unless it is one job, and respect the job cap.  A few shapes are compared with literal numbers.
  * Prints "onevar large plan check: ok" and returns 0, or says what failed and returns 1. */
 #include "hs_cut_plan.h"
+#include "hs_chunks.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -94,26 +95,60 @@ static int chunks(void)
    /* 64 jobs of 512 rows with the default budget of 512 MiB: 4.7 MB each, so one chunk holds 113 of them - all 64 */
    std::vector<long long> len(64, ws_len(512) + out_len(512));
    const long long budget = 512LL * 1024 * 1024 / 8;
-   CHECK( hs_ovl_chunk_end(len.data(), 64, 0, budget, 0) == 64 );
+   CHECK( hs_chunk_end(len.data(), 64, 0, budget, 0) == 64 );
    len.assign(300, ws_len(512) + out_len(512));
    const int per = (int) (budget / len[0]);
    CHECK( per == 113 );
    int start = 0, n = 0;
    while ( start < 300 )
    {
-      const int end = hs_ovl_chunk_end(len.data(), 300, start, budget, 0);
+      const int end = hs_chunk_end(len.data(), 300, start, budget, 0);
       CHECK( end > start && end - start <= per && (end == 300 || end - start == per) );
       start = end;
       ++n;
    }
    CHECK( n == 3 );
    /* a job count: chunks of exactly two, the last one of what is left; a budget below one job still makes progress */
-   CHECK( hs_ovl_chunk_end(len.data(), 7, 0, len[0] * 2, 2) == 2 && hs_ovl_chunk_end(len.data(), 7, 6, len[0] * 2, 2) == 7 );
-   CHECK( hs_ovl_chunk_end(len.data(), 7, 3, 1, 0) == 4 );
-   CHECK( hs_ovl_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
+   CHECK( hs_chunk_end(len.data(), 7, 0, len[0] * 2, 2) == 2 && hs_chunk_end(len.data(), 7, 6, len[0] * 2, 2) == 7 );
+   CHECK( hs_chunk_end(len.data(), 7, 3, 1, 0) == 4 );
+   CHECK( hs_chunk_end(len.data(), 0, 0, budget, 0) == 0 );
    /* descending lengths: the budget counts the doubles of the jobs, not their number */
    long long mixed[5] = { 100, 60, 40, 30, 5 };
-   CHECK( hs_ovl_chunk_end(mixed, 5, 0, 160, 0) == 2 && hs_ovl_chunk_end(mixed, 5, 2, 160, 0) == 5 );
+   CHECK( hs_chunk_end(mixed, 5, 0, 160, 0) == 2 && hs_chunk_end(mixed, 5, 2, 160, 0) == 5 );
+   return 0;
+}
+
+/* what a job of n rows counts for in a chunk (hs_onevar_large_job_len, csrc/onevar_large.hip, from the stand-ins above) */
+static long long job_len(int n) { return ((ws_len(n) + 1) & ~1LL) + out_len(n); }
+
+/* the driver: a forced job count stands alone.  The call used to pass  job_len[start] * count  as the budget of such a chunk, which is
+ * no bound only because the lengths do not increase along a list ordered by descending n - asserted here for every n the call serves -
+ * so on such a list the driver's chunks are those of that budget */
+static int driver(void)
+{
+   for (int n = 3; n <= 512; ++n)
+      CHECK( job_len(n) >= job_len(n - 1) );
+   static const int ROWS[] = {512, 512, 511, 257, 257, 257, 200, 130, 129, 129, 129};
+   std::vector<long long> len;
+   for (int k = 0; k < 11; ++k)
+      len.push_back(job_len(ROWS[k]));
+   for (int forced = 1; forced <= 12; ++forced)
+   {
+      int next = 0, bad = 0;
+      CHECK( hs_chunks_run(len.data(), 11, 1, forced, [&](int start, int end)
+         {
+            bad += (start != next || end != (start + forced < 11 ? start + forced : 11)) ? 1 : 0;
+            bad += end != hs_chunk_end(len.data(), 11, start, len[start] * forced, forced) ? 1 : 0;
+            next = end;
+            return 0;
+         }) == 0 );
+      CHECK( bad == 0 && next == 11 );
+   }
+   /* no forced count: the budget binds; the first status that is not 0 ends the walk and is returned */
+   int calls = 0;
+   CHECK( hs_chunks_run(len.data(), 11, len[0] * 2, 0, [&](int start, int end) { ++calls; return end - start == 2 && start == 0 ? 0 : 7; }) == 7 );
+   CHECK( calls == 2 );
+   CHECK( hs_chunks_run(len.data(), 0, 1, 0, [&](int, int) { ++calls; return 7; }) == 0 && calls == 2 );
    return 0;
 }
 
@@ -144,7 +179,7 @@ int main(void)
       if ( check(MS[im], rows, zlen) != 0 ) return 1;
       ++shapes;
    }
-   if ( chunks() != 0 || literals() != 0 ) return 1;
+   if ( chunks() != 0 || driver() != 0 || literals() != 0 ) return 1;
    printf("onevar large plan check: ok (%lld shapes)\n", shapes);
    return 0;
 }

@@ -3,6 +3,7 @@
  * (tests/test_psd_project_many_large_cpu.py does that).  Every array a job points to is a heap block of exactly the stated length, so
  * a read past a triplet list is reported.  Prints "psd large plan check: ok" and returns 0, or says what failed and returns 1. */
 #include "hs_psd_large_plan.h"
+#include "hs_chunks.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -59,11 +60,16 @@ static int check_plan(const JobSet& S, std::vector<hs_ppl_item>& items, long lon
          CHECK( items[k - 1].n > it.n || (items[k - 1].n == it.n && items[k - 1].job < it.job) );
    }
    *nchunks = 0;
+   std::vector<long long> lens;
+   for (size_t k = 0; k < items.size(); ++k)
+      lens.push_back(items[k].len);
    for (int start = 0; start < (int) items.size(); )
    {
       hs_ppl_chunk C;
       CHECK( hs_ppl_chunk_make(&items, start, budget, &rules, &C) == HIPSDP_OK );
       CHECK( C.first == start && C.end > start && C.end <= (int) items.size() );
+      /* the chunk ends where the one chunk rule says (hs_chunks.h) */
+      CHECK( C.end == hs_chunk_end(lens.data(), (int) lens.size(), start, budget, 0) );
       long long used = 0, trips = 0, res = 0;
       for (int i = C.first; i < C.end; ++i)
       {

@@ -3,6 +3,10 @@ restatement (sparsecuts_variants_ref.py), shared by the CPU test of their stabil
 sparsecuts_all_large_rate.py.
 
   "f3"   : family "f3" of sparsecuts_variants_cases.py - blocks of 16, 150, 48, 200, 10 rows, m = 25; the call serves blocks 1 and 3;
+  "f4"   : its family "f4" - blocks of 130, 12, 129, 131 rows, m = 25; the call serves blocks 0, 2 and 3, by descending rows 3, 0, 2.  It
+           is compared with nothing but itself: the same call in one, two and three chunks (CHUNKED).  What that needs: every large block
+           cuts at size 4 under masks 0 and 7, and has at least 5 eigenvalues <= -tol.  Seeds 3 and 4 leave a block without a cut at
+           size 4; seed 5 holds;
   "n129", "n257", "n512": one block each, at the edges of the 512-thread workgroup of the TPower kernel - 129 rows are two wavefronts
            and one row, 257 four and one, 512 all eight full: instances.planted_dense(n, 25, seed) with the constant matrix rebuilt as
            sym(sum_i ys_i A_i - Zs), y = ys + 0.7 default_rng(seed).standard_normal(25).
@@ -27,14 +31,16 @@ CASES = [(f, k, sz, v) for f, k, sz in ROWS for v in SWITCHED] + [("n129", 0, 4,
 CASES0 = [(f, k, sz, 0) for f, k, sz in ROWS if f != "f3"]
 # the 200-row block of f3 at size 4: no cut under any mask, the loop ends at once
 QUIET = ("f3", 3, 4)
+# the family, target size and masks of the chunk tests: three large blocks, so that a chunk of two is neither one block nor the call
+CHUNKED, CHUNKED_SIZE, CHUNKED_MASKS = "f4", 4, (0, 7)
 
 _fam, _ref, _mg = {}, {}, {}
 
 
 def family(name):
     """(blocks [A_k (m + 1, n_k, n_k)], ys, y, b)"""
-    if name == "f3":
-        return K.family("f3")
+    if name in ("f3", "f4"):
+        return K.family(name)
     if name not in _fam:
         n, seed = SINGLES[name]
         b, A, ys, Xs, Zs = instances.planted_dense(n, M, seed)

@@ -9,7 +9,9 @@ is ys + 0.7 N(0, 1)):
   "b12" : eight blocks of 12 rows, m = 15 (the first eight of its family 1);
   "b40" : four blocks of 40 rows, m = 15 (its family 2);
   "r12" : the 32 blocks of 12 rows of its family 1 (the rate tool only);
-  "f3"  : its family 3 - blocks of 16, 150, 48, 200, 10 rows, m = 25: two blocks above the 128 rows a call with a switch serves.
+  "f3"  : its family 3 - blocks of 16, 150, 48, 200, 10 rows, m = 25: two blocks above the 128 rows a call with a switch serves;
+  "f4"  : blocks of 130, 12, 129, 131 rows, m = 25, none quiet: three blocks above 128 rows whose index order is not their size order
+          (the chunk tests of the _large calls: a chunk of several blocks that is not the whole call).
 CASES: (family, target size, variant) - variants 1, 2, 4 and 7 everywhere, 3, 5 and 6 on the 12-row family, so that every combination
 of the three switches runs."""
 import numpy as np
@@ -22,7 +24,8 @@ FAMILIES = {"f0": ([3, 9, 10, 17, 33, 64, 65, 100, 128], 20, (2, 5), 0),
             "b12": ([12] * 8, 15, (), 1),
             "b40": ([40] * 4, 15, (), 1),
             "r12": ([12] * 32, 15, (), 1),
-            "f3": ([16, 150, 48, 200, 10], 25, (2,), 2)}
+            "f3": ([16, 150, 48, 200, 10], 25, (2,), 2),
+            "f4": ([130, 12, 129, 131], 25, (), 5)}
 SIZES = [("f0", 2), ("f0", 4), ("f0", 10), ("b12", 4), ("b40", 4), ("b40", 10)]
 CASES = [(f, sz, v) for f, sz in SIZES for v in (1, 2, 4, 7)] + [("b12", 4, v) for v in (3, 5, 6)]
 

@@ -3,10 +3,8 @@ run clean in a stand-alone program under AddressSanitizer + UBSan - segments in 
 window around the result arrays alone, the views written through on heap blocks of exactly the stated lengths, and literal offsets
 for a few shapes per call form - and the file is host-only and part of the build."""
 import os
-import subprocess
 from conftest import ROOT
-
-PKG = os.path.join(ROOT, "scip-sdp_amd")
+import host_check
 
 
 def _read(*parts):
@@ -17,16 +15,7 @@ def _read(*parts):
 def test_layouts_run_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/cut_plan_check.cpp + csrc/hs_cut_plan.cpp, host compiler, -fsanitize=address,undefined:
     a program of its own with the runtimes linked in (nothing is loaded into python, nothing is preloaded)"""
-    exe = str(tmp_path / "cut_plan_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "cut_plan_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "cut plan check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "cut_plan_check.cpp", ["hs_cut_plan.cpp"], "cut plan check: ok")
 
 
 def test_the_layouts_are_host_only_and_built_into_the_library():

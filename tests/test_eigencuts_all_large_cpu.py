@@ -1,7 +1,7 @@
 """CPU: hipsdp_eigencuts_all_large - the C ABI, the library and the binding carry the call, its stats and (units library only) the unit
 entry of the batched selection; every argument error is refused before a device is looked at; the cases of tests/harness/
 eigencuts_all_large_cases.py keep the margins that make counts and vectors comparable; the launch formula of the header is the host
-function hs_ecl_launches; the chunk layout (hs_ecl_layout_make, hs_ecl_block_make) and the chunks of hs_ovl_chunk_end run clean in a
+function hs_ecl_launches; the chunk layout (hs_ecl_layout_make, hs_ecl_block_make) and the chunks of hs_chunk_end run clean in a
 stand-alone program under AddressSanitizer + UBSan.  What needs a shaped solver is checked in tests/test_gpu_eigencuts_all_large.py."""
 import ctypes as C
 import importlib.util
@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 from conftest import ROOT
+import host_check
 import eigencuts_all_large_cases as E
 
 PKG = os.path.join(ROOT, "scip-sdp_amd")
@@ -85,7 +86,10 @@ def test_argument_errors_and_the_totals_without_a_device(hb):
     src = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
     body = src[src.index("int eigencuts_all_large_impl("):src.index('extern "C" int hipsdp_eigencuts_all_stats(')]
     assert body.count("return HIPSDP_ERR_ARG") == 2 and "HIPSDP_EIGENCUTS_LARGE_MAXCUTS" in body
-    assert body.rindex("return HIPSDP_ERR_ARG") < body.index("d.ncuts[b] = -1") < body.index("hs_solver_cut_enter_large(") < body.index("ecl_chunk(")
+    # large_served is the first function that touches the device (hs_solver_cut_enter_large)
+    served = src[src.index("int large_served("):src.index("struct LargeRun")]
+    assert "hs_solver_cut_enter_large(" in served and body.count("hs_solver_cut_") == 0
+    assert body.rindex("return HIPSDP_ERR_ARG") < body.index("d.ncuts[b] = -1") < body.index("large_served(") < body.index("ecl_chunk(")
 
 
 @pytest.mark.parametrize("name,k,rows", E.ROWS)
@@ -115,6 +119,18 @@ def test_no_block_is_left_out_and_the_multiple_case_is_multiple():
     assert np.sum(np.abs(ev + 0.01) <= 1e-12) == 129 - 12 and ev[117] > 0.0
 
 
+def test_the_family_of_the_chunk_tests_has_three_large_blocks_with_five_cuts_each():
+    """f4: rows 130, 12, 129, 131; every large block has at least maxcuts = 5 eigenvalues <= -tol (the oracle returns 5 cuts), so every
+    chunk of the chunk test copies out full lists"""
+    blocks, ys, y, b = E.family(E.CHUNKED)
+    assert [A.shape[1] for A in blocks] == [130, 12, 129, 131] and E.large_blocks(E.CHUNKED) == [0, 2, 3]
+    for k in E.large_blocks(E.CHUNKED):
+        below = int(np.sum(E.spectrum(E.CHUNKED, k) <= -E.TOL))
+        lmin, ev, co, lh, ve = E.reference(E.CHUNKED, k, E.MAXCUTS)
+        print("f4 block %d: %d eigenvalues <= -tol, %d cuts" % (k, below, len(ev)))
+        assert below >= E.MAXCUTS == 5 and len(ev) == E.MAXCUTS and np.all(ev <= -E.TOL)
+
+
 def test_the_launch_formula_of_the_header_is_the_host_function(tmp_path):
     hdr = _read("include", "hipsdp.h")
     assert re.search(r"2 \+ \(nmax - 1\) \+ 1 \+ 2 \[maxcuts > 0\] \+ 1\s+=\s+nmax \+ 3 \+ 2 \[maxcuts > 0\]", hdr)
@@ -142,16 +158,7 @@ def test_layout_and_chunks_run_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/cut_plan_ecl_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    exe = str(tmp_path / "cut_plan_ecl_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "cut_plan_ecl_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "cut plan ecl check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "cut_plan_ecl_check.cpp", ["hs_cut_plan.cpp"], "cut plan ecl check: ok")
 
 
 def test_the_sources_are_where_the_build_expects_them_and_share_the_sweep():
@@ -180,6 +187,8 @@ def test_the_sources_are_where_the_build_expects_them_and_share_the_sweep():
     for name in ("d_syevx_values", "d_syevx_tvec", "d_syevx_back"):
         assert len(re.findall(r"__device__\s+__forceinline__\s+void\s+%s\s*\(" % name, sx)) == 1, name
     host = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
-    assert '"HIPSDP_EIGENCUTS_LARGE_CHUNK"' in host and "hs_ecl_layout_make(" in host and "hs_ovl_chunk_end(" in host
+    assert 'hs_chunk_env("HIPSDP_EIGENCUTS_LARGE_CHUNK")' in host and "hs_ecl_layout_make(" in host and "hs_chunks_run(" in host
+    chunks = _read("scip-sdp_amd", "csrc", "hs_chunks.h")
+    assert "int hs_chunk_end(" in chunks and "hs_chunk_end(" in chunks[chunks.index("hs_chunks_run("):]
     plan = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h")
     assert "hs_ecl_layout_make" in plan and "hs_ecl_block_make" in plan and "hs_ecl_launches" in plan

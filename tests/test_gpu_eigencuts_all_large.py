@@ -255,7 +255,7 @@ spec = importlib.util.spec_from_file_location("hb_child", %(binding)r)
 hb = importlib.util.module_from_spec(spec); spec.loader.exec_module(hb)
 import eigencuts_all_large_cases as E
 import test_gpu_eigencuts_all as T
-blocks, ys, y, b = E.family("f3")
+blocks, ys, y, b = E.family(%(family)r)
 s = T.load_dense(hb, blocks, b)
 c0 = hb.eigencuts_all_large_stats()
 res = s.eigencuts_all_large(y, E.TOL, E.MAXCUTS)
@@ -266,12 +266,12 @@ print(json.dumps({"bits": [None if r is None else [np.asarray(a).tobytes().hex()
 """
 
 
-def _child(chunk):
+def _child(chunk, family="f3"):
     env = dict(os.environ)
     env.pop("HIPSDP_EIGENCUTS_LARGE_CHUNK", None)
     if chunk:
         env["HIPSDP_EIGENCUTS_LARGE_CHUNK"] = str(chunk)
-    code = _CHILD % {"tests": os.path.join(ROOT, "tests"), "harness": os.path.join(ROOT, "tests", "harness"),
+    code = _CHILD % {"family": family, "tests": os.path.join(ROOT, "tests"), "harness": os.path.join(ROOT, "tests", "harness"),
                      "oracle": os.path.join(ROOT, "oracle"), "binding": os.path.join(ROOT, "scip-sdp_amd", "binding.py")}
     r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -288,6 +288,21 @@ def test_bits_do_not_depend_on_the_chunking(gpu):
     assert one["bits"] == here
     assert one["stats"] == [1, formula(MAXCUTS, 200), 1]
     assert two["stats"] == [1, formula(MAXCUTS, 200) + formula(MAXCUTS, 150), 2]
+
+
+def test_a_chunk_of_several_blocks_that_is_not_the_whole_call(gpu):
+    """family f4 - blocks of 130, 12, 129, 131 rows, served by descending rows as 3, 0, 2 - with the chunk variable unset (one chunk
+    of three), 2 (blocks 3 and 0, then block 2: a chunk whose own vector offsets differ from the caller's) and 1, each in a fresh
+    child process: the same bits, the 12-row block turned away, one read-back per chunk, the launches of a chunk those of its own
+    largest block"""
+    whole, pair, single = (_child(c, E.CHUNKED) for c in (0, 2, 1))
+    print("stats %s / %s / %s" % (whole["stats"], pair["stats"], single["stats"]))
+    assert whole["bits"] == pair["bits"] == single["bits"]
+    assert whole["bits"][1] is None and all(whole["bits"][k] is not None for k in (0, 2, 3))      # (None: ncuts = -1)
+    f = lambda n: formula(MAXCUTS, n)
+    assert whole["stats"] == [1, f(131), 1]
+    assert pair["stats"] == [1, f(131) + f(129), 2]
+    assert single["stats"] == [1, f(131) + f(130) + f(129), 3]
 
 
 def test_two_host_threads_reproduce_the_single_thread_bits(gpu):

@@ -248,12 +248,12 @@ spec = importlib.util.spec_from_file_location("hb_child", %(binding)r)
 hb = importlib.util.module_from_spec(spec); spec.loader.exec_module(hb)
 import sparsecuts_all_large_cases as L
 import test_gpu_sparsecuts_all as T
-blocks, ys, y, b = L.family("f3")
+blocks, ys, y, b = L.family(%(family)r)
 s = T.load_dense(hb, blocks, b)
 out = {}
 for variant in (0, 7):
     c0 = hb.sparsecuts_all_large_stats()
-    res = s.sparsecuts_all_large(y, [10] * len(blocks), L.TOL, L.FEASTOL, L.MAXCUTS, variant)
+    res = s.sparsecuts_all_large(y, [%(size)d] * len(blocks), L.TOL, L.FEASTOL, L.MAXCUTS, variant)
     c1 = hb.sparsecuts_all_large_stats()
     out[str(variant)] = {"bits": [[r[0], r[6], r[7]] + [np.asarray(a).tobytes().hex() for a in r[1:6]] for r in res],
                          "stats": [c1[k] - c0[k] for k in range(3)]}
@@ -262,12 +262,12 @@ print(json.dumps(out))
 """
 
 
-def _child(chunk):
+def _child(chunk, family="f3", size=10):
     env = dict(os.environ)
     env.pop("HIPSDP_SPARSECUTS_LARGE_CHUNK", None)
     if chunk:
         env["HIPSDP_SPARSECUTS_LARGE_CHUNK"] = str(chunk)
-    code = _CHILD % {"tests": os.path.join(ROOT, "tests"), "harness": os.path.join(ROOT, "tests", "harness"),
+    code = _CHILD % {"family": family, "size": size, "tests": os.path.join(ROOT, "tests"), "harness": os.path.join(ROOT, "tests", "harness"),
                      "oracle": os.path.join(ROOT, "oracle"), "binding": os.path.join(ROOT, "scip-sdp_amd", "binding.py")}
     r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -282,6 +282,24 @@ def test_bits_do_not_depend_on_the_chunking(gpu):
         assert one[v]["bits"] == two[v]["bits"], v
         assert one[v]["stats"] == [1, formula(int(v), MAXCUTS, 200), 1], v
         assert two[v]["stats"] == [1, formula(int(v), MAXCUTS, 200) + formula(int(v), MAXCUTS, 150), 2], v
+
+
+def test_a_chunk_of_several_blocks_that_is_not_the_whole_call(gpu):
+    """family f4 - blocks of 130, 12, 129, 131 rows, served by descending rows as 3, 0, 2 - at size 4 with the chunk variable unset
+    (one chunk of three), 2 (blocks 3 and 0, then block 2: a chunk whose own vector offsets differ from the caller's) and 1, each in
+    a fresh child process: the same bits, the 12-row block turned away, one read-back per chunk, the launches of a chunk those of
+    its own largest block"""
+    assert L.CHUNKED_MASKS == (0, 7)
+    runs = [_child(c, L.CHUNKED, L.CHUNKED_SIZE) for c in (0, 2, 1)]
+    for v in ("0", "7"):
+        f = lambda n: formula(int(v), MAXCUTS, n)
+        whole, pair, single = (r[v] for r in runs)
+        print("variant %s: stats %s / %s / %s, ncuts %s" % (v, whole["stats"], pair["stats"], single["stats"], [r[0] for r in whole["bits"]]))
+        assert whole["bits"] == pair["bits"] == single["bits"], v
+        assert whole["bits"][1][0] == -1 and all(whole["bits"][k][0] >= 1 for k in (0, 2, 3)), v
+        assert whole["stats"] == [1, f(131), 1], v
+        assert pair["stats"] == [1, f(131) + f(129), 2], v
+        assert single["stats"] == [1, f(131) + f(130) + f(129), 3], v
 
 
 def test_two_host_threads_reproduce_the_single_thread_bits(gpu):

@@ -8,9 +8,9 @@ import importlib.util
 import inspect
 import os
 import re
-import subprocess
 import numpy as np
 from conftest import ROOT
+import host_check
 import onevar_cases as K
 import onevar_all_cases as KA
 
@@ -101,16 +101,7 @@ def test_layout_runs_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/onevar_plan_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    exe = str(tmp_path / "onevar_plan_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "onevar_plan_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "onevar plan check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "onevar_plan_check.cpp", ["hs_cut_plan.cpp"], "onevar plan check: ok")
 
 
 def test_the_layout_stays_host_only_and_the_kernels_share_their_bodies():

@@ -1,6 +1,6 @@
 """CPU: hipsdp_onevar_bounds_large - the C ABI, the libraries and the binding carry the call and its unit entry; every argument error
-is refused before a device is looked at; the chunk layout and the chunk splitter (hs_ovl_layout_make, hs_ovl_chunk_end,
-csrc/hs_cut_plan.cpp) run clean in a stand-alone program under AddressSanitizer + UBSan; the family of
+is refused before a device is looked at; the chunk layout (hs_ovl_layout_make, csrc/hs_cut_plan.cpp), the chunk rule and its driver
+(hs_chunk_end, hs_chunks_run, csrc/hs_chunks.h) run clean in a stand-alone program under AddressSanitizer + UBSan; the family of
 tests/test_gpu_onevar_large.py (129 .. 512 rows) keeps the counts its tests rely on against the numpy restatement, and the restatement
 agrees with the oracle's solve_one_var_sdp at 129 rows.  What needs a shaped solver is checked in tests/test_gpu_onevar_large.py."""
 import ctypes as C
@@ -8,8 +8,8 @@ import importlib.util
 import inspect
 import os
 import re
-import subprocess
 from conftest import ROOT
+import host_check
 import sdpi_driver
 import onevar_cases as K
 import onevar_all_cases as KA
@@ -102,26 +102,25 @@ def test_layout_and_chunks_run_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/onevar_large_plan_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    exe = str(tmp_path / "onevar_large_plan_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "onevar_large_plan_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "onevar large plan check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "onevar_large_plan_check.cpp", ["hs_cut_plan.cpp"], "onevar large plan check: ok")
 
 
 def test_the_sources_are_where_the_build_expects_them_and_share_their_bodies():
     assert "csrc/onevar_large.hip" in _read("scip-sdp_amd", "Makefile")
     host = _read("scip-sdp_amd", "csrc", "onevar_large.hip")
-    assert "__global__" not in host and "hs_ovl_chunk_end(" in host and "hs_solver_cut_blocks(" in host
-    assert '"HIPSDP_ONEVAR_LARGE_CHUNK"' in host
-    hdr = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h")
-    assert "hs_ovl_layout_make" in hdr and "hs_ovl_chunk_end" in hdr and "hip_runtime" not in hdr
+    assert "__global__" not in host and "hs_chunks_run(" in host and "hs_solver_cut_blocks(" in host
+    assert 'hs_chunk_env("HIPSDP_ONEVAR_LARGE_CHUNK")' in host and "getenv" not in host
+    hdr, chunks = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h"), _read("scip-sdp_amd", "csrc", "hs_chunks.h")
+    assert "hs_ovl_layout_make" in hdr and "hip_runtime" not in hdr
+    # one definition of the chunk rule, host-only, and the driver walks it
+    assert "int hs_chunk_end(" in chunks and "hs_chunk_end(" in chunks[chunks.index("hs_chunks_run("):] and "#include <hip" not in chunks and "hip_runtime" not in chunks
+    assert "chunk_end" not in hdr and "chunk_end" not in _read("scip-sdp_amd", "csrc", "hs_cut_plan.cpp")
     sx = _read("scip-sdp_amd", "csrc", "syevx.hip")
+    # one rule for the workgroups per matrix of a column launch: hs_syevx_many_cap, beside hs_syevx_many_cols
+    rule = re.compile(r"4 \* \(cus > 0 \? cus : 256\)\) / count")
+    assert len(rule.findall(sx)) == 1 and "int hs_syevx_many_cap(int count)" in sx and "hs_syevx_many_cap(count)" in host
+    for other in ("cut_calls.hip", "psd_large.hip", "onevar_large.hip", "units.hip"):
+        assert not rule.search(_read("scip-sdp_amd", "csrc", other)), other
     # one body per stage, called by the kernel of one matrix and by the batched one
     for name in ("d_syevx_col", "d_syevx_values", "d_syevx_tvec", "d_syevx_back"):
         assert len(re.findall(r"__device__\s+__forceinline__\s+void\s+%s\s*\(" % name, sx)) == 1, name

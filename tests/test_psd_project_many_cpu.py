@@ -8,6 +8,7 @@ import re
 import subprocess
 import importlib.util
 from conftest import ROOT
+import host_check
 
 PKG = os.path.join(ROOT, "scip-sdp_amd")
 FIELDS = ["n", "nnz", "row", "col", "val", "minev", "cap", "nnz_out", "rowout", "colout", "valout"]
@@ -61,16 +62,7 @@ def test_binding_structure_has_the_layout_the_compiler_gives_the_header(tmp_path
 def test_host_planning_runs_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/psd_plan_check.cpp + csrc/hs_psd_plan.cpp, host compiler, -fsanitize=address,undefined:
     a program of its own with the runtimes linked in (nothing is loaded into python, nothing is preloaded)"""
-    exe = str(tmp_path / "psd_plan_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "psd_plan_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_psd_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "psd plan check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "psd_plan_check.cpp", ["hs_psd_plan.cpp"], "psd plan check: ok")
 
 
 def test_library_exports_the_new_symbols_and_checks_arguments_without_a_device(hb):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import host_check
 import psd_project_ref as ref
 import psd_large_cases as cases
 
@@ -159,16 +160,7 @@ def test_host_planning_runs_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/psd_large_plan_check.cpp + csrc/hs_psd_large_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    exe = str(tmp_path / "psd_large_plan_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "psd_large_plan_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_psd_large_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "psd large plan check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "psd_large_plan_check.cpp", ["hs_psd_large_plan.cpp"], "psd large plan check: ok")
 
 
 def test_sources_keep_their_shape():
@@ -189,3 +181,7 @@ def test_sources_keep_their_shape():
     assert not re.search(r"atomic\w*\s*\(", pl) and "cooperative" not in pl and "grid.sync" not in pl
     assert "hs_syevx_many_cols" in pl and "hs_syevr_many_tvec" in pl and "hs_syevr_many_back" in pl
     assert "__builtin_amdgcn_mfma_f64_16x16x4f64" in pl and "hs_ppl_launches" in _read("scip-sdp_amd", "csrc", "hs_psd_large_plan.h")
+    # the chunk rule, the chunk variable and the totals are the shared ones (hs_chunks.h, hs_cut_stats.h)
+    assert 'hs_chunk_env("HIPSDP_PSD_LARGE_CHUNK")' in pl and "getenv" not in pl and "CutStats" in pl and "hs_syevx_many_cap(" in pl
+    plan = _read("scip-sdp_amd", "csrc", "hs_psd_large_plan.cpp")
+    assert '#include "hs_chunks.h"' in plan and "hs_chunk_end(" in plan and "hs_cut_plan" not in plan

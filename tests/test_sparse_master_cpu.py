@@ -4,9 +4,9 @@ triplet master (one-time sort into the three orders, index maps of a node: csrc/
 in a stand-alone program under AddressSanitizer + UBSan."""
 import os
 import re
-import subprocess
 import importlib.util
 from conftest import ROOT
+import host_check
 
 PKG = os.path.join(ROOT, "scip-sdp_amd")
 
@@ -55,16 +55,7 @@ def test_library_exports_the_new_symbols(hb):
 def test_host_side_of_the_triplet_master_runs_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/sp_master_check.cpp + csrc/hs_sp_master.cpp, host compiler, -fsanitize=address,undefined:
     a program of its own with the runtimes linked in (nothing is loaded into python, nothing is preloaded)"""
-    exe = str(tmp_path / "sp_master_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "sp_master_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_sp_master.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "sp master check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "sp_master_check.cpp", ["hs_sp_master.cpp"], "sp master check: ok")
 
 
 def test_the_gather_is_built_from_its_own_sources():

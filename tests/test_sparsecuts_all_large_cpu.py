@@ -1,7 +1,7 @@
 """CPU: hipsdp_sparsecuts_all_large - the C ABI, the library and the binding carry the call and its stats; every argument error is
 refused before a device is looked at; the cases of tests/harness/sparsecuts_all_large_cases.py are stable in the numpy restatement
 (so that the GPU tests may compare counts, supports and iteration numbers); the launch formula of the header is the host function
-hs_sclr_launches; the chunk layout (hs_sclr_layout_make, hs_sclr_block_make) and the chunks of hs_ovl_chunk_end run clean in a
+hs_sclr_launches; the chunk layout (hs_sclr_layout_make, hs_sclr_block_make) and the chunks of hs_chunk_end run clean in a
 stand-alone program under AddressSanitizer + UBSan.  What needs a shaped solver is checked in tests/test_gpu_sparsecuts_all_large.py."""
 import ctypes as C
 import importlib.util
@@ -11,6 +11,7 @@ import re
 import subprocess
 import pytest
 from conftest import ROOT
+import host_check
 import sparsecuts_all_large_cases as L
 
 PKG = os.path.join(ROOT, "scip-sdp_amd")
@@ -87,8 +88,17 @@ def test_argument_errors_and_the_totals_without_a_device(hb):
     entry = src[src.index('extern "C" int hipsdp_sparsecuts_all_large('):]
     assert entry.index("variant_ok(variant)") < entry.index("sparsecuts_all_large_impl(")
     body = src[src.index("int sparsecuts_all_large_impl("):src.index("/* hipsdp_sparsecuts (variant = 0, booked under g_sc1)")]
-    assert body.count("return HIPSDP_ERR_ARG") == 3
-    assert body.rindex("return HIPSDP_ERR_ARG") < body.index("d.ncuts[b] = -1") < body.index("hs_solver_cut_enter_large(") < body.index("sclr_chunk(")
+    # the three argument errors are those of sc_all_args, which writes nothing and looks at no device ...
+    args = src[src.index("int sc_all_args("):src.index("/* hipsdp_sparsecuts_all (variant = 0)")]
+    assert args.count("return HIPSDP_ERR_ARG") == 3 and "ncuts[" not in args and "hs_solver_cut_" not in args and "HS_HIP" not in args
+    # ... large_served is the first function that touches the device (hs_solver_cut_enter_large), and behind it nothing is an argument error
+    served = src[src.index("int large_served("):src.index("struct LargeRun")]
+    assert "hs_solver_cut_enter_large(" in served and body.count("hs_solver_cut_") == 0
+    assert body.index("sc_all_args(") < body.index("d.ncuts[b] = -1") < body.index("large_served(") < body.index("sclr_chunk(")
+    assert "return HIPSDP_ERR_ARG" not in body
+    # the partner for the blocks of at most 128 rows checks its arguments through the same function, in the same place
+    small = src[src.index("int sparsecuts_all_impl("):src.index("/* a block of at most 128 rows")]
+    assert small.index("sc_all_args(") < small.index("d.ncuts[b] = -1") < small.index("hs_solver_cut_enter(") and "return HIPSDP_ERR_ARG" not in small
 
 
 @pytest.mark.parametrize("name,k,size,variant", L.CASES + L.CASES0)
@@ -121,6 +131,19 @@ def test_no_block_is_left_out_and_the_quiet_block_is_quiet():
         assert L.reference(*c)[0] >= 1, c
 
 
+def test_the_family_of_the_chunk_tests_has_three_large_blocks_that_all_cut():
+    """f4: rows 130, 12, 129, 131, so the served order 3, 0, 2 is not the index order; every large block gives at least one cut at the
+    size and the masks of the chunk test (the restatement), so that no chunk copies out empty lists alone"""
+    blocks, ys, y, b = L.family(L.CHUNKED)
+    assert [A.shape[1] for A in blocks] == [130, 12, 129, 131] and len(y) == L.M and L.large_blocks(L.CHUNKED) == [0, 2, 3]
+    assert (L.CHUNKED_SIZE, L.CHUNKED_MASKS) == (4, (0, 7))
+    for k in L.large_blocks(L.CHUNKED):
+        for v in L.CHUNKED_MASKS:
+            r = L.reference(L.CHUNKED, k, L.CHUNKED_SIZE, v)
+            print("f4 block %d variant %d: %d cuts, %d iterations" % (k, v, r[0], r[7]))
+            assert r[0] >= 1, (k, v)
+
+
 def test_the_launch_formula_of_the_header_is_the_host_function(tmp_path):
     hdr = _read("include", "hipsdp.h")
     assert re.search(r"1 \+ \(nmax \+ 3\) \+ r \(1 \+ 4 s \+ d \(nmax \+ 3\)\) \+ 1 \+ \[maxcuts > 0\],\s+r = maxcuts with variant != 0, r = 0 with variant == 0", hdr)
@@ -150,16 +173,7 @@ def test_layout_and_chunks_run_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/cut_plan_large_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    exe = str(tmp_path / "cut_plan_large_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "harness", "cut_plan_large_check.cpp"),
-           os.path.join(PKG, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "cut plan large check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "cut_plan_large_check.cpp", ["hs_cut_plan.cpp"], "cut plan large check: ok")
 
 
 def test_the_sources_are_where_the_build_expects_them_and_share_their_bodies():
@@ -178,6 +192,13 @@ def test_the_sources_are_where_the_build_expects_them_and_share_their_bodies():
     for text in (body, many):
         assert "cooperative" not in text.lower() and "grid.sync" not in text and not re.search(r"atomic\w*\s*\(", text)
     host = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
-    assert '"HIPSDP_SPARSECUTS_LARGE_CHUNK"' in host and "hs_sclr_layout_make(" in host and "hs_ovl_chunk_end(" in host
+    assert 'hs_chunk_env("HIPSDP_SPARSECUTS_LARGE_CHUNK")' in host and "hs_sclr_layout_make(" in host and "hs_chunks_run(" in host
+    chunks = _read("scip-sdp_amd", "csrc", "hs_chunks.h")
+    assert "int hs_chunk_end(" in chunks and "hs_chunk_end(" in chunks[chunks.index("hs_chunks_run("):] and "#include <hip" not in chunks and "hip_runtime" not in chunks
+    # one tail: neither chunk function reads back on its own
+    for name, end in (("int sclr_chunk(", "int sparsecuts_all_large_impl("), ("int ecl_chunk(", "int eigencuts_all_large_impl(")):
+        fn = host[host.index(name):host.index(end)]
+        assert "DeviceToHost" not in fn and "large_begin(" in fn and "large_end(" in fn, name
+    assert "getenv" not in host
     plan = _read("scip-sdp_amd", "csrc", "hs_cut_plan.h")
     assert "hs_sclr_layout_make" in plan and "hs_sclr_block_make" in plan and "hs_sclr_launches" in plan

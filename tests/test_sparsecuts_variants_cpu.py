@@ -6,11 +6,11 @@ eigenpair it takes by 1e-9 relative - the residual bound of the eigen contract -
 import ctypes as C
 import os
 import re
-import subprocess
 import importlib.util
 import numpy as np
 import pytest
 from conftest import ROOT
+import host_check
 import sparsecuts_ref as R
 import sparsecuts_variants_ref as V
 import sparsecuts_variants_cases as K
@@ -104,17 +104,7 @@ def test_the_layout_of_the_rounds_runs_clean_under_the_sanitizers(tmp_path):
     """the stand-alone program tests/harness/cut_plan_rounds_check.cpp + csrc/hs_cut_plan.cpp, host compiler,
     -fsanitize=address,undefined: a program of its own with the runtimes linked in (nothing is loaded into python, nothing is
     preloaded)"""
-    pkg = os.path.join(ROOT, "scip-sdp_amd")
-    exe = str(tmp_path / "cut_plan_rounds_check")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(pkg, "csrc"), os.path.join(ROOT, "tests", "harness", "cut_plan_rounds_check.cpp"),
-           os.path.join(pkg, "csrc", "hs_cut_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "cut plan rounds check: ok" in r.stdout, r.stdout[-4000:]
-    assert "AddressSanitizer" not in r.stdout and "runtime error:" not in r.stdout, r.stdout[-4000:]
+    host_check.run_clean(tmp_path, "cut_plan_rounds_check.cpp", ["hs_cut_plan.cpp"], "cut plan rounds check: ok")
     assert "hs_scr_layout_make" in _read("scip-sdp_amd", "csrc", "cut_calls.hip") and "hs_scr_block_make" in _read("scip-sdp_amd", "csrc", "cut_calls.hip")
 
 
