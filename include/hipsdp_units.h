@@ -39,6 +39,17 @@ HIPSDP_API int  hipsdp_tri_product_unit(int device, int mode, int M, int N, int 
    const double* B, double* Cio, int crows, int ldc, int* used);
 /* the same choice for products reached through other entries (hipsdp_schur_form_unit); returns the wide instance's products so far */
 HIPSDP_API int  hipsdp_tri_instance_force(int mode);
+/* one Gram product from the caller's operands with the instance of the Gram kernel (csrc/gram.hip) forced (mode 0: 128 x 128 tiles, 1:
+ * 256 x 256 on eight wavefronts, -1: chosen per shape): W [M][ldw], ldw >= K; Cio [M][M] in and out, lower triangle = alpha W W^T +
+ * beta Cio; nslab (1 .. 64) slabs of M x M doubles granted; used[2]: the Gram kernel took the product, and its wide instance did */
+HIPSDP_API int  hipsdp_gram_product_unit(int device, int mode, int M, long long K, const double* W, long long ldw, double alpha, double beta,
+   double* Cio, int nslab, int* used);
+/* the same choice for products reached through other entries (hipsdp_schur_form_unit, hipsdp_schur_identity_unit,
+ * hipsdp_gram_selfcheck); returns the wide instance's products so far */
+HIPSDP_API int  hipsdp_gram_instance_force(int mode);
+/* host only: the plan of one instance for a shape.  info[4] = items, lists (512 / 256), partial tiles per off-diagonal / diagonal tile;
+ * off[lists + 1]; the first cap items as six ints each (ti, tj, k0, k1, slab, column half).  HIPSDP_ERR_ARG when the instance has no plan */
+HIPSDP_API int  hipsdp_gram_plan_unit(int inst, int forced, int M, long long K, int nslab, int cap, int* items, int* off, int* info);
 /* first assembly of a cold solve: Mx += <A_i, A_j> on the lower tiles, from the packed lower triangles (full_storage = 0) or from the
  * full rows (1); *flops: FP64 matrix-core flops executed by the call */
 HIPSDP_API int  hipsdp_schur_identity_unit(int device, int m1, int n, const double* A, double ws_gbytes, int full_storage, double* Mx,

@@ -1160,6 +1160,38 @@ def tri_instance_force(mode):
     return ulib().hipsdp_tri_instance_force(mode)
 
 
+def gram_product_unit(W, K, mode, alpha=1.0, beta=0.0, Cin=None, nslab=64, device=0):
+    """one Gram product from the caller's operands, the Gram kernel's instance forced (mode 0: 128 x 128, 1: wide, -1: chosen per
+    shape): W (M x ldw, the first K of every row are the operand) -> (C (M x M) that started as Cin with its lower triangle
+    = alpha W W^T + beta Cin, (the Gram kernel took it, its wide instance did))"""
+    W = _f64(W)
+    M, ldw = W.shape
+    Cio = np.zeros((M, M)) if Cin is None else _f64(Cin).copy()
+    assert Cio.shape == (M, M)
+    used = (C.c_int * 2)(0, 0)
+    _chk(ulib().hipsdp_gram_product_unit(device, mode, M, C.c_longlong(K), _dp(W), C.c_longlong(ldw), C.c_double(alpha), C.c_double(beta),
+                                         _dp(Cio), nslab, used), "hipsdp_gram_product_unit")
+    return Cio, tuple(used)
+
+
+def gram_instance_force(mode):
+    """forces the Gram kernel's instance for products reached through other entries of the units library (0: 128 x 128, 1: wide,
+    -1: chosen per shape again) -> products the wide instance has taken so far"""
+    return ulib().hipsdp_gram_instance_force(mode)
+
+
+def gram_plan_unit(inst, M, K, nslab=64, forced=False):
+    """host only: the plan of one instance of the Gram kernel -> None, or (items as an (n, 5) array of ti, tj, k0, k1, slab; list
+    offsets; partial tiles per off-diagonal tile; per diagonal tile)"""
+    info = (C.c_int * 4)()
+    off = np.zeros(513, dtype=np.int32)
+    items = np.zeros((4096, 6), dtype=np.int32)
+    if ulib().hipsdp_gram_plan_unit(inst, int(forced), M, C.c_longlong(K), nslab, items.shape[0], _ip(items), _ip(off), info) != 0:
+        return None
+    assert info[0] <= items.shape[0]
+    return items[:info[0], :5].copy(), off[:info[1] + 1].copy(), info[2], info[3]
+
+
 def gram_selfcheck(M, K, reps=0, device=0):
     """W W^T on the lower triangle through the K-sliced tile kernels and through the Gram kernel (csrc/gram.hip)
     -> (Gram kernel took it, max |difference| over the lower triangle, elements not reproduced by a second run, ms tile path, ms Gram kernel)"""

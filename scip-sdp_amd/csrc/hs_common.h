@@ -111,14 +111,21 @@ int hs_dgemm2_paired_taken(void);
  * products the wide instance has taken */
 int hs_dgemm2_wide_force(int mode);
 int hs_dgemm2_tri5_forced(void);                    /* 1 while a test forces either instance */
-int hs_gram_taken(void);
+int hs_gram_taken(void);                            /* products the Gram kernel has taken, either instance */
+/* test hook: -1 the Gram kernel's instance is chosen per shape, 0 / 1 forces its 128 x 128 / its wide instance (then for every shape it
+ * can serve, whatever the size); returns how many products the wide instance has taken */
+int hs_gram_instance_force(int mode);
 
 /* the Gram product of the Schur assembly (gram.hip): C (M x M, lower triangle) = alpha W W^T + beta C with W [M][K] K contiguous,
- * through nslab >= 8 slabs of M x M doubles at ws; diagonal tiles at 9 / 16 of the matrix instructions, a static list of items per
- * workgroup built on the host (no atomics).  1: done, 0: not eligible (the caller takes hs_dgemm with HS_GEMM_LOWER), < 0: error code negated */
+ * through nslab >= 2 slabs of M x M doubles at ws; diagonal tiles at 9 / 16 (wide instance: 17 / 32) of the matrix instructions, a static
+ * list of items per workgroup built on the host (no atomics).  1: done, 0: not eligible (the caller takes hs_dgemm with HS_GEMM_LOWER),
+ * < 0: error code negated */
 int hs_gram_try(hipStream_t stream, int M, long long K, const double* W, long long ldw, double* C, long long ldc, double alpha, double beta,
    double* ws, int nslab, double* executed);
 int hs_gram_plan_info(int M, long long K, int nslab, int* no, int* nd, int* nitems, double* span);
+/* host only: the plan of one instance (0 / 1) as the launcher would build it; info[4] = items, lists, no, nd; off[lists + 1]; the first
+ * cap items as (ti, tj, k0, k1, slab, column half).  1: there is a plan, 0: none */
+int hs_gram_plan_host(int inst, int forced, int M, long long K, int nslab, int cap, int* items, int* off, int* info);
 
 /* latency-oriented 32 x 32 kernel with the K split inside the workgroup (dgemm3.hip) for products of few tiles: 1 launched,
  * 0 not eligible, < 0 error (negated code); hs_dgemm tries it first for products without split-K */

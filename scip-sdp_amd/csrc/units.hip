@@ -404,6 +404,51 @@ extern "C" int hipsdp_gram_plan_info(int device, int M, long long K, int nslab, 
    return hs_gram_plan_info(M, K, nslab, no, nd, nitems, span) ? HIPSDP_OK : HIPSDP_ERR_ARG;
 }
 
+/* One Gram product from the caller's operands through hs_gram_try with the instance of the Gram kernel (csrc/gram.hip) forced: mode 0
+ * its 128 x 128 instance, 1 its wide instance, -1 chosen per shape.  W [M][ldw] (ldw >= K, the K first of every row are read),
+ * Cio [M][M] in and out: lower triangle = alpha W W^T + beta Cio, the rest comes back as it went in.  nslab: slabs of M x M doubles
+ * granted.  used[2]: 1 when the Gram kernel took the product (0: it declined, Cio is unchanged), and 1 when that was its wide instance */
+extern "C" int hipsdp_gram_product_unit(int device, int mode, int M, long long K, const double* W, long long ldw, double alpha, double beta,
+   double* Cio, int nslab, int* used)
+{
+   HS_CALL( pick_device(device) );
+   if ( mode < -1 || mode > 1 || M < 1 || K < 1 || ldw < K || W == NULL || Cio == NULL || nslab < 1 || nslab > 64 || used == NULL )
+      return HIPSDP_ERR_ARG;
+   const long long MM = (long long) M * M;
+   DevBuf dW, dC, dS;
+   HS_CALL( dW.alloc((long long) M * ldw) ); HS_CALL( dC.alloc(MM) ); HS_CALL( dS.alloc((long long) nslab * MM) );
+   HS_CALL( dW.up(W, (long long) M * ldw) ); HS_CALL( dC.up(Cio, MM) );
+   hipLaunchKernelGGL(k_unit_fill, dim3(1024), dim3(256), 0, 0, (long long) nslab * MM, 52ULL, dS.p);
+   const int tg = hs_gram_taken();
+   const int tw = hs_gram_instance_force(mode);
+   const int r = hs_gram_try(0, M, K, dW.p, ldw, dC.p, M, alpha, beta, dS.p, nslab, NULL);
+   int rc = r < 0 ? -r : HS_OK;
+   if ( rc == HS_OK && hipDeviceSynchronize() != hipSuccess ) rc = HS_ERR_HIP;
+   used[1] = hs_gram_instance_force(-1) - tw;
+   used[0] = hs_gram_taken() - tg;
+   HS_CALL( rc );
+   HS_CALL( dC.down(Cio, MM) );
+   return HIPSDP_OK;
+}
+
+/* test hook of the same choice for the calls that reach the Gram product through the assembly (hipsdp_schur_form_unit,
+ * hipsdp_schur_identity_unit) or through hipsdp_gram_selfcheck: mode as above; returns how many products the wide instance has taken
+ * so far */
+extern "C" int hipsdp_gram_instance_force(int mode)
+{
+   return hs_gram_instance_force(mode);
+}
+
+/* host only: the plan csrc/gram.hip builds for instance inst (0: 128 x 128 tiles on 512 lists, 1: 256 x 256 on 256) of a shape with
+ * nslab slabs granted; forced = 1 as a forced instance gets it.  info[4] = items, lists, partial tiles per off-diagonal / diagonal
+ * tile; off[lists + 1] (513 ints are enough); the first cap items as six ints (ti, tj, k0, k1, slab, column half).  HIPSDP_ERR_ARG: no plan */
+extern "C" int hipsdp_gram_plan_unit(int inst, int forced, int M, long long K, int nslab, int cap, int* items, int* off, int* info)
+{
+   if ( items == NULL || off == NULL || info == NULL || cap < 0 )
+      return HIPSDP_ERR_ARG;
+   return hs_gram_plan_host(inst, forced, M, K, nslab, cap, items, off, info) ? HIPSDP_OK : HIPSDP_ERR_ARG;
+}
+
 /* The cold start's first assembly on its own: Mx (m1 x m1, as the caller filled it) += the Gram matrix <A_i, A_j> of the host matrices
  * A[m1][n][n] on the lower tiles.  full_storage = 0: hs_pack_rows + hs_schur_W_identity_packed (2 P P^T - D D^T over the packed lower
  * triangles), 1: hs_schur_W_identity over the full rows.  ws_gbytes > 0: the Schur workspace under that budget (chunked when the
