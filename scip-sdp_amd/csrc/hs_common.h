@@ -60,6 +60,29 @@ int hs_pool_alloc(void** p, size_t bytes);
 void hs_pool_free(void* p);
 void hs_pool_trim(void);
 
+/* a pooled block for the length of a scope: the temporaries of the blocking calls.  The pool hands a freed block out again without
+ * a device synchronisation, so a block goes back only when the work that uses it has completed: the buffer knows the stream it
+ * serves and drains it before it frees.  Behind the wait that ends a normal path the stream is idle and the drain costs nothing;
+ * on an early return it is what keeps the pool's rule.  A buffer that outlives the function that fills it is the caller's, handed
+ * in empty. */
+template<class T> struct PoolBuf
+{
+   T* p;
+   hipStream_t stream;
+   explicit PoolBuf(hipStream_t st) : p(NULL), stream(st) {}
+   ~PoolBuf()
+   {
+      if ( p == NULL )
+         return;
+      (void) hipStreamSynchronize(stream);
+      hs_pool_free(p);
+   }
+   int alloc(long long count) { return hs_pool_alloc((void**) &p, (size_t) (count > 0 ? count : 1) * sizeof(T)); }
+private:
+   PoolBuf(const PoolBuf&);
+   PoolBuf& operator=(const PoolBuf&);
+};
+
 /* operand storage of a GEMM operand as seen from the product C[M x N] = A[M x K] * B[K x N]:
  *  HS_KC: the K index is contiguous in memory (A stored row-major [M][K], or B stored as [N][K])
  *  HS_MC: the M (resp. N) index is contiguous   (A stored as [K][M],      or B stored row-major [K][N]) */

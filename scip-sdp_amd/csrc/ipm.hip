@@ -1099,6 +1099,37 @@ static bool scatter_last_of_each_position(long long nnz, int n, const int* var, 
    return true;
 }
 
+/* the one launch of k_scatter_coo; every operand is on the device (or in the arena).  No wait */
+static int scatter_launch(hipStream_t st, long long nnz, int n, const int* var, const int* row, const int* col, const double* val,
+   double* A, int r0, int r1, double* A0, int vmax, int* err)
+{
+   long long g = (nnz + 255) / 256; if ( g > 4096 ) g = 4096;
+   hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g), dim3(256), 0, st, nnz, n, var, row, col, val, A, r0, r1, A0, vmax, err);
+   HS_LAUNCH_CHECK();
+   return HS_OK;
+}
+
+/* the blocking route: the caller's triplets to pooled buffers, the flag cleared, the scatter, the flag back (herr == NULL: nobody
+ * reads it, the indices were checked on the host) and ONE wait.  Entries in range are written even when one is not. */
+static int scatter_host_triplets(hipsdp_solver* s, int n, long long nnz, const int* var, const int* row, const int* col, const double* val,
+   double* A, int r0, int r1, double* A0, int vmax, int* dflag, int* herr)
+{
+   hipStream_t st = s->stream;
+   PoolBuf<int> dv(st), dr(st), dc(st);
+   PoolBuf<double> dval(st);
+   HS_CALL( dv.alloc(nnz) ); HS_CALL( dr.alloc(nnz) ); HS_CALL( dc.alloc(nnz) ); HS_CALL( dval.alloc(nnz) );
+   HS_HIP( hipMemcpyAsync(dv.p, var, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, st) );
+   HS_HIP( hipMemcpyAsync(dr.p, row, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, st) );
+   HS_HIP( hipMemcpyAsync(dc.p, col, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, st) );
+   HS_HIP( hipMemcpyAsync(dval.p, val, (size_t) nnz * sizeof(double), hipMemcpyHostToDevice, st) );
+   HS_HIP( hipMemsetAsync(dflag, 0, sizeof(int), st) );
+   HS_CALL( scatter_launch(st, nnz, n, dv.p, dr.p, dc.p, dval.p, A, r0, r1, A0, vmax, dflag) );
+   if ( herr != NULL )
+      HS_HIP( hipMemcpyAsync(herr, dflag, sizeof(int), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   return HS_OK;
+}
+
 extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, const int* var, const int* row, const int* col,
    const double* val)
 {
@@ -1153,20 +1184,8 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
          }
       }
       nnz = (long long) cv.size();
-      int *dv, *dr, *dc; double* dval;
       HS_CALL( flush_cmds(s) );
-      HS_CALL( dalloc(&dv, nnz) ); HS_CALL( dalloc(&dr, nnz) ); HS_CALL( dalloc(&dc, nnz) ); HS_CALL( dalloc(&dval, nnz) );
-      HS_HIP( hipMemcpy(dv, cv.data(), (size_t) nnz * sizeof(int), hipMemcpyHostToDevice) );
-      HS_HIP( hipMemcpy(dr, cr.data(), (size_t) nnz * sizeof(int), hipMemcpyHostToDevice) );
-      HS_HIP( hipMemcpy(dc, cc.data(), (size_t) nnz * sizeof(int), hipMemcpyHostToDevice) );
-      HS_HIP( hipMemcpy(dval, cx.data(), (size_t) nnz * sizeof(double), hipMemcpyHostToDevice) );
-      long long g0 = (nnz + 255) / 256; if ( g0 > 4096 ) g0 = 4096;
-      HS_HIP( hipMemsetAsync(s->flags + 6, 0, sizeof(int), s->stream) );
-      hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g0), dim3(256), 0, s->stream, nnz, B.n, dv, dr, dc, dval, B.A0, 0, 1, B.A0, 0, s->flags + 6);
-      HS_LAUNCH_CHECK();
-      HS_HIP( hipStreamSynchronize(s->stream) );
-      dfree(dv); dfree(dr); dfree(dc); dfree(dval);
-      return HIPSDP_OK;
+      return scatter_host_triplets(s, B.n, nnz, cv.data(), cr.data(), cc.data(), cx.data(), B.A0, 0, 1, B.A0, 0, s->flags + 6, NULL);
    }
    std::vector<int> kv, kr, kc; std::vector<double> kx;       /* (the call's entries without the overwritten ones, when there are any) */
    if ( nnz <= 16384 )
@@ -1211,34 +1230,18 @@ extern "C" int hipsdp_add_entries(hipsdp_solver* s, int block, long long nnz, co
          }
          else
          {
-            long long g = (nnz + 255) / 256; if ( g > 4096 ) g = 4096;
             HS_CALL( flush_cmds(s) );
-            hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g), dim3(256), 0, s->stream, nnz, B.n, di, di + nnz, di + 2 * nnz, dval, B.A,
-               s->a_r0, s->a_r1, B.A0, s->m, s->flags + 6);
-            HS_LAUNCH_CHECK();
+            HS_CALL( scatter_launch(s->stream, nnz, B.n, di, di + nnz, di + 2 * nnz, dval, B.A, s->a_r0, s->a_r1, B.A0, s->m, s->flags + 6) );
             s->stage_pending = true;
          }
          s->solved = false;
          return HIPSDP_OK;
       }
    }
-   int *dv, *dr, *dc; double* dval;
    a_written(s, B);         /* (before the first call that can fail: entries in range are written even when one is not) */
    HS_CALL( flush_cmds(s) );
-   HS_CALL( dalloc(&dv, nnz) ); HS_CALL( dalloc(&dr, nnz) ); HS_CALL( dalloc(&dc, nnz) ); HS_CALL( dalloc(&dval, nnz) );
-   HS_HIP( hipMemcpyAsync(dv, var, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dr, row, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dc, col, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dval, val, (size_t) nnz * sizeof(double), hipMemcpyHostToDevice, s->stream) );
-   long long g = (nnz + 255) / 256; if ( g > 4096 ) g = 4096;
    int herr = 0;
-   HS_HIP( hipMemsetAsync(s->flags + 6, 0, sizeof(int), s->stream) );
-   hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g), dim3(256), 0, s->stream, nnz, B.n, dv, dr, dc, dval, B.A, s->a_r0, s->a_r1, B.A0,
-      s->m, s->flags + 6);
-   HS_LAUNCH_CHECK();
-   HS_HIP( hipMemcpyAsync(&herr, s->flags + 6, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
-   HS_HIP( hipStreamSynchronize(s->stream) );
-   dfree(dv); dfree(dr); dfree(dc); dfree(dval);
+   HS_CALL( scatter_host_triplets(s, B.n, nnz, var, row, col, val, B.A, s->a_r0, s->a_r1, B.A0, s->m, s->flags + 6, &herr) );
    s->solved = false;
    if ( herr != 0 )
    {
@@ -1341,24 +1344,12 @@ extern "C" int hipsdp_master_add_entries(hipsdp_solver* s, int block, long long 
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
    const int n = s->master_sizes[block];
-   int *dv, *dr, *dc; double* dval;
-   int* derr = NULL;
-   HS_CALL( dalloc(&derr, 1) );
-   HS_CALL( dalloc(&dv, nnz) ); HS_CALL( dalloc(&dr, nnz) ); HS_CALL( dalloc(&dc, nnz) ); HS_CALL( dalloc(&dval, nnz) );
-   HS_HIP( hipMemcpyAsync(dv, var, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dr, row, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dc, col, (size_t) nnz * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-   HS_HIP( hipMemcpyAsync(dval, val, (size_t) nnz * sizeof(double), hipMemcpyHostToDevice, s->stream) );
-   long long g = (nnz + 255) / 256; if ( g > 4096 ) g = 4096;
+   PoolBuf<int> derr(s->stream);         /* (a master copy is defined before any shape: no s->flags yet) */
+   HS_CALL( derr.alloc(1) );
    /* slot 0 of the master copy is a variable like the others: A0 = A, nothing is skipped by the row range */
    int herr = 0;
-   HS_HIP( hipMemsetAsync(derr, 0, sizeof(int), s->stream) );
-   hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g), dim3(256), 0, s->stream, nnz, n, dv, dr, dc, dval, s->master_A[block], 0, 2147483647,
-      s->master_A[block], s->master_slots[block] - 1, derr);
-   HS_LAUNCH_CHECK();
-   HS_HIP( hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
-   HS_HIP( hipStreamSynchronize(s->stream) );
-   dfree(dv); dfree(dr); dfree(dc); dfree(dval); dfree(derr);
+   HS_CALL( scatter_host_triplets(s, n, nnz, var, row, col, val, s->master_A[block], 0, 2147483647, s->master_A[block],
+         s->master_slots[block] - 1, derr.p, &herr) );
    if ( herr != 0 )
    {
       set_err("hipsdp_master_add_entries: index out of range");
@@ -1428,9 +1419,9 @@ extern "C" int hipsdp_master_add_vars(hipsdp_solver* s, int block, int nslots, c
    HS_CALL( stage_ensure(s, total) );
    const long long cap = s->stage_cap;
    const int n = s->master_sizes[block];
-   int* derr = NULL;
-   HS_CALL( dalloc(&derr, 1) );
-   HS_HIP( hipMemsetAsync(derr, 0, sizeof(int), s->stream) );
+   PoolBuf<int> derr(s->stream);
+   HS_CALL( derr.alloc(1) );
+   HS_HIP( hipMemsetAsync(derr.p, 0, sizeof(int), s->stream) );
    int k = 0;
    long long off = 0;                  /* entries of slot k already shipped */
    int set = 0;
@@ -1476,18 +1467,15 @@ extern "C" int hipsdp_master_add_vars(hipsdp_solver* s, int block, int nslots, c
       HS_HIP( hipMemcpyAsync(drow, hrow, (size_t) fill * sizeof(int), hipMemcpyHostToDevice, s->stream) );
       HS_HIP( hipMemcpyAsync(dcol, hcol, (size_t) fill * sizeof(int), hipMemcpyHostToDevice, s->stream) );
       HS_HIP( hipMemcpyAsync(dval, hval, (size_t) fill * sizeof(double), hipMemcpyHostToDevice, s->stream) );
-      long long g = (fill + 255) / 256; if ( g > 4096 ) g = 4096;
-      hipLaunchKernelGGL(k_scatter_coo, dim3((unsigned) g), dim3(256), 0, s->stream, fill, n, dvar, drow, dcol, dval, s->master_A[block], 0,
-         2147483647, s->master_A[block], s->master_slots[block] - 1, derr);
-      HS_LAUNCH_CHECK();
+      HS_CALL( scatter_launch(s->stream, fill, n, dvar, drow, dcol, dval, s->master_A[block], 0, 2147483647, s->master_A[block],
+            s->master_slots[block] - 1, derr.p) );
       HS_HIP( hipEventRecord(s->stage_ev[set], s->stream) );
       used[set] = true;
       set ^= 1;
    }
    int herr = 0;
-   HS_HIP( hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
+   HS_HIP( hipMemcpyAsync(&herr, derr.p, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
    HS_HIP( hipStreamSynchronize(s->stream) );
-   dfree(derr);
    if ( herr != 0 )
    {
       set_err("hipsdp_master_add_vars: index out of range");
@@ -1510,6 +1498,35 @@ __global__ void k_master_gather(int nactive, int nk, int N, const int* __restric
       A[(a + 1) * nk2 + rc] = act[a] >= 0 ? master[((long long) act[a] * N + kept[r]) * N + kept[c]] : 0.0;
    }
 }
+
+/* The two index lists of a gather where a kernel can read them.  Through the arena when it has room: the kernel reads them there, nothing
+ * is copied and nothing waits (wait = false; b follows a).  Else asynchronous copies into two pooled buffers, and the caller's launch is
+ * followed by one hipStreamSynchronize (wait = true). */
+struct IndexLists
+{
+   PoolBuf<int> da, db;
+   const int *a, *b;
+   bool wait;
+   explicit IndexLists(hipStream_t st) : da(st), db(st), a(NULL), b(NULL), wait(false) {}
+   int stage(hipsdp_solver* s, const int* ha, int na, const int* hb, int nb)
+   {
+      void* dv = NULL;
+      int* hidx = (int*) stage_take(s, (size_t) (na + nb) * sizeof(int), &dv);
+      wait = hidx == NULL;
+      if ( !wait )
+      {
+         memcpy(hidx, ha, (size_t) na * sizeof(int));
+         memcpy(hidx + na, hb, (size_t) nb * sizeof(int));
+         a = (const int*) dv; b = a + na;
+         return HS_OK;
+      }
+      HS_CALL( da.alloc(na) ); HS_CALL( db.alloc(nb) );
+      HS_HIP( hipMemcpyAsync(da.p, ha, (size_t) na * sizeof(int), hipMemcpyHostToDevice, s->stream) );
+      HS_HIP( hipMemcpyAsync(db.p, hb, (size_t) nb * sizeof(int), hipMemcpyHostToDevice, s->stream) );
+      a = da.p; b = db.p;
+      return HS_OK;
+   }
+};
 
 /* from a master block kept as triplets (csrc/sp_master.hip): into a block kept as nonzeros the node's whole structure is built on the
  * device, in the master block's workspace; into a dense block the rows of the active variables are cleared and scattered */
@@ -1564,27 +1581,16 @@ static int master_gather_triplets(hipsdp_solver* s, int engine_block, int master
       return HIPSDP_OK;
    a_written(s, B);
    HS_CALL( flush_cmds(s) );                 /* (the clears of set_shape come first) */
-   void* dv = NULL;
-   int* hidx = (int*) stage_take(s, (size_t) (nactive + N) * sizeof(int), &dv);
-   if ( hidx != NULL )
+   IndexLists idx(s->stream);
+   HS_CALL( idx.stage(s, activevars, nactive, inv.data(), N) );
+   HS_CALL( hs_spm_gather_dense(s->stream, M, nkept, nactive, idx.a, idx.b, B.A, &s->mg_launches) );
+   if ( idx.wait )
    {
-      memcpy(hidx, activevars, (size_t) nactive * sizeof(int));
-      memcpy(hidx + nactive, inv.data(), (size_t) N * sizeof(int));
-      const int* didx = (const int*) dv;
-      HS_CALL( hs_spm_gather_dense(s->stream, M, nkept, nactive, didx, didx + nactive, B.A, &s->mg_launches) );
-      s->stage_pending = true;
-   }
-   else
-   {
-      int *dact, *dinv;
-      HS_CALL( dalloc(&dact, nactive) ); HS_CALL( dalloc(&dinv, N) );
-      HS_HIP( hipMemcpyAsync(dact, activevars, (size_t) nactive * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-      HS_HIP( hipMemcpyAsync(dinv, inv.data(), (size_t) N * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-      HS_CALL( hs_spm_gather_dense(s->stream, M, nkept, nactive, dact, dinv, B.A, &s->mg_launches) );
       HS_HIP( hipStreamSynchronize(s->stream) );
       ++s->mg_readbacks;
-      dfree(dact); dfree(dinv);
    }
+   else
+      s->stage_pending = true;
    s->solved = false;
    return HIPSDP_OK;
 }
@@ -1614,43 +1620,25 @@ extern "C" int hipsdp_master_gather(hipsdp_solver* s, int engine_block, int mast
          return HIPSDP_ERR_ARG;
    Block& B = s->blk[engine_block];
    a_written(s, B);
-   long long g = ((long long) nactive * nkept * nkept + 255) / 256; if ( g > 65536 ) g = 65536;
+   const long long total = (long long) nactive * nkept * nkept;
+   IndexLists idx(s->stream);
+   HS_CALL( idx.stage(s, activevars, nactive, kept, nkept) );
+   NodeCmd* q = (!idx.wait && total <= NC_LIMIT) ? cmd_new(s) : NULL;
+   if ( q != NULL )
    {
-      /* the two index lists through the arena: the kernel reads them there, nothing is copied and nothing waited for */
-      void* dv = NULL;
-      int* hidx = (int*) stage_take(s, (size_t) (nactive + nkept) * sizeof(int), &dv);
-      if ( hidx != NULL )
-      {
-         memcpy(hidx, activevars, (size_t) nactive * sizeof(int));
-         memcpy(hidx + nactive, kept, (size_t) nkept * sizeof(int));
-         const int* didx = (const int*) dv;
-         NodeCmd* q = ((long long) nactive * nkept * nkept <= NC_LIMIT) ? cmd_new(s) : NULL;
-         if ( q != NULL )
-         {
-            q->op = NC_GATHER; q->i0 = nactive; q->i1 = nkept; q->i2 = N; q->idx = didx; q->src = s->master_A[master_block]; q->dst = B.A;
-         }
-         else
-         {
-            HS_CALL( flush_cmds(s) );
-            hipLaunchKernelGGL(k_master_gather, dim3((unsigned) g), dim3(256), 0, s->stream, nactive, nkept, N, didx, didx + nactive,
-               s->master_A[master_block], B.A);
-            HS_LAUNCH_CHECK();
-            s->stage_pending = true;
-         }
-      }
-      else
-      {
-         int *dact, *dkept;
-         HS_CALL( flush_cmds(s) );
-         HS_CALL( dalloc(&dact, nactive) ); HS_CALL( dalloc(&dkept, nkept) );
-         HS_HIP( hipMemcpyAsync(dact, activevars, (size_t) nactive * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-         HS_HIP( hipMemcpyAsync(dkept, kept, (size_t) nkept * sizeof(int), hipMemcpyHostToDevice, s->stream) );
-         hipLaunchKernelGGL(k_master_gather, dim3((unsigned) g), dim3(256), 0, s->stream, nactive, nkept, N, dact, dkept,
-            s->master_A[master_block], B.A);
-         HS_LAUNCH_CHECK();
+      q->op = NC_GATHER; q->i0 = nactive; q->i1 = nkept; q->i2 = N; q->idx = idx.a; q->src = s->master_A[master_block]; q->dst = B.A;
+   }
+   else
+   {
+      long long g = (total + 255) / 256; if ( g > 65536 ) g = 65536;
+      HS_CALL( flush_cmds(s) );
+      hipLaunchKernelGGL(k_master_gather, dim3((unsigned) g), dim3(256), 0, s->stream, nactive, nkept, N, idx.a, idx.b,
+         s->master_A[master_block], B.A);
+      HS_LAUNCH_CHECK();
+      if ( idx.wait )
          HS_HIP( hipStreamSynchronize(s->stream) );
-         dfree(dact); dfree(dkept);
-      }
+      else
+         s->stage_pending = true;
    }
    s->solved = false;
    return HIPSDP_OK;
@@ -2952,6 +2940,19 @@ struct CommOff        /* the communicator is out of sight while a replicated (sm
 static int solve_begin(hipsdp_solver* s, const hipsdp_params* params, hipsdp_info* info);
 static int solve_run(hipsdp_solver* s, hipsdp_info* info, bool try1);
 
+/* the buffers of the preoptimal iterate that do not exist yet (they stay until the problem is freed) */
+static int ensure_preoptimal(hipsdp_solver* s)
+{
+   if ( s->pre_y == NULL )
+      HS_CALL( dalloc(&s->pre_y, s->m_alloc > s->m ? s->m_alloc : s->m) );
+   if ( s->pre_x == NULL )
+      HS_CALL( dalloc(&s->pre_x, s->q_alloc > s->q ? s->q_alloc : s->q) );
+   for (auto& B : s->blk)
+      if ( B.Xpre == NULL )
+         HS_CALL( dalloc(&B.Xpre, (long long) B.n * B.n) );
+   return HS_OK;
+}
+
 static int sync_outcome(hipsdp_solver* s, int rc, hipsdp_info* info)
 {
    struct Pack { int rc, solved, last_status, pre_valid; double sol_scale, tau, kappa, pre_scale; hipsdp_info info; } pk;
@@ -2959,16 +2960,15 @@ static int sync_outcome(hipsdp_solver* s, int rc, hipsdp_info* info)
    pk.rc = rc; pk.solved = s->solved ? 1 : 0; pk.last_status = s->last_status; pk.pre_valid = s->pre_valid ? 1 : 0;
    pk.sol_scale = s->sol_scale; pk.tau = s->tau; pk.kappa = s->kappa; pk.pre_scale = s->pre_scale; pk.info = *info;
    const long long nint = (long long) ((sizeof(Pack) + sizeof(int) - 1) / sizeof(int));
-   int* d = NULL;
    hipStream_t st = s->stream;
-   HS_CALL( dalloc(&d, nint) );
-   int r = HS_OK;
-   if ( hipMemcpyAsync(d, &pk, sizeof(pk), hipMemcpyHostToDevice, st) != hipSuccess ) r = HS_ERR_HIP;
-   if ( r == HS_OK ) r = hs_bcast_ints(s->comm, d, nint, st);
-   if ( r == HS_OK && (hipMemcpyAsync(&pk, d, sizeof(pk), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) )
-      r = HS_ERR_HIP;
-   dfree(d);
-   HS_CALL( r );
+   {
+      PoolBuf<int> d(st);
+      HS_CALL( d.alloc(nint) );
+      HS_HIP( hipMemcpyAsync(d.p, &pk, sizeof(pk), hipMemcpyHostToDevice, st) );
+      HS_CALL( hs_bcast_ints(s->comm, d.p, nint, st) );
+      HS_HIP( hipMemcpyAsync(&pk, d.p, sizeof(pk), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
+   }
    s->solved = pk.solved != 0; s->last_status = pk.last_status; s->sol_scale = pk.sol_scale; s->tau = pk.tau; s->kappa = pk.kappa;
    s->pre_scale = pk.pre_scale;
    *info = pk.info;
@@ -2989,19 +2989,11 @@ static int sync_outcome(hipsdp_solver* s, int rc, hipsdp_info* info)
    }
    if ( pk.pre_valid )
    {
-      if ( s->pre_y == NULL )
-      {
-         HS_CALL( dalloc(&s->pre_y, s->m_alloc > m ? s->m_alloc : m) );
-         HS_CALL( dalloc(&s->pre_x, s->q_alloc > q ? s->q_alloc : q) );
-      }
+      HS_CALL( ensure_preoptimal(s) );
       if ( m > 0 ) HS_CALL( hs_bcast_doubles(s->comm, s->pre_y, m, st) );
       if ( q > 0 ) HS_CALL( hs_bcast_doubles(s->comm, s->pre_x, q, st) );
       for (auto& B : s->blk)
-      {
-         if ( B.Xpre == NULL )
-            HS_CALL( dalloc(&B.Xpre, (long long) B.n * B.n) );
          HS_CALL( hs_bcast_doubles(s->comm, B.Xpre, (long long) B.n * B.n, st) );
-      }
    }
    s->pre_valid = pk.pre_valid != 0;
    HS_HIP( hipStreamSynchronize(st) );
@@ -3249,16 +3241,7 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered, const S1L
       memset(s->s1_host, 0, (size_t) (HS_S1_OUT_DOUBLES + 8) * sizeof(double));
    }
    if ( par.preoptgap > 0.0 )
-   {
-      if ( s->pre_y == NULL )
-      {
-         HS_CALL( dalloc(&s->pre_y, s->m_alloc > s->m ? s->m_alloc : s->m) );
-         HS_CALL( dalloc(&s->pre_x, s->q_alloc > s->q ? s->q_alloc : s->q) );
-      }
-      for (auto& B : s->blk)
-         if ( B.Xpre == NULL )
-            HS_CALL( dalloc(&B.Xpre, (long long) B.n * B.n) );
-   }
+      HS_CALL( ensure_preoptimal(s) );
    pp->t_begin = std::chrono::steady_clock::now();
    hs_solve1_args& a = pp->a;
    memset(&a, 0, sizeof(a));
@@ -3300,34 +3283,70 @@ static int solve1_prepare(hipsdp_solver* s, S1Prep* pp, bool* offered, const S1L
    return HS_OK;
 }
 
-/* spin on the sequence word of the launch on st (host: the pinned part of its lane) */
+/* The results of the one-launch kernels come through pinned memory: the last thing a problem's workgroup stores is its sequence word.
+ * A word to wait for: the pinned part of the problem's lane, the number its launch publishes, and which of the caller's queues the
+ * launch went to (< 0: never launched - not waited for, not published). */
+struct SeqWord { const double* host; unsigned long long seq; int queue; };
+
+/* Spins on all the words together; pub[i] = 1 once word i holds its number.  A launch that failed would never publish: after every
+ * 0x4000 words read, each queue that still has a word missing is asked.  Not ready: keep spinning.  Finished: its missing words are
+ * read once more, and what is still missing is reported.  Any other answer is recorded, and the queue's missing words count as not
+ * published (pub[i] = 0); `what` names the query in that record.  No allocation: this is the wait of every B&B node solve. */
+static void wait_published(const SeqWord* w, int n, const hipStream_t* queues, int nqueues, const char* what, char* pub)
+{
+   auto holds = [&](int i) -> bool {
+      return *reinterpret_cast<const volatile unsigned long long*>(w[i].host + HS_S1_OUT_DOUBLES) == w[i].seq;
+   };
+   int left = 0;
+   for (int i = 0; i < n; ++i)
+   {
+      pub[i] = 0;
+      if ( w[i].queue >= 0 ) ++left;
+   }
+   const char GIVEN_UP = 2;
+   long long reads = 0;
+   while ( left > 0 )
+   {
+      reads += left;
+      for (int i = 0; i < n; ++i)
+         if ( w[i].queue >= 0 && pub[i] == 0 && holds(i) ) { pub[i] = 1; --left; }
+      if ( left == 0 || reads < 0x4000 )
+         continue;
+      reads = 0;
+      for (int c = 0; c < nqueues; ++c)
+      {
+         bool any = false;
+         for (int i = 0; i < n && !any; ++i) any = w[i].queue == c && pub[i] == 0;
+         if ( !any )
+            continue;
+         const hipError_t e = hipStreamQuery(queues[c]);
+         if ( e == hipErrorNotReady )
+            continue;
+         if ( e != hipSuccess )
+            hs_record_hip_error(e, what, __FILE__, __LINE__);
+         for (int i = 0; i < n; ++i)
+            if ( w[i].queue == c && pub[i] == 0 )
+            {
+               --left;
+               if ( e == hipSuccess && holds(i) ) { pub[i] = 1; continue; }
+               if ( e == hipSuccess )
+                  set_err("the one-launch solve finished without publishing its results");
+               pub[i] = GIVEN_UP;
+            }
+      }
+   }
+   for (int i = 0; i < n; ++i)
+      pub[i] = pub[i] == 1;
+   __atomic_thread_fence(__ATOMIC_ACQUIRE);
+}
+
+/* one word: the launch on st (host: the pinned part of its lane) */
 static int solve1_wait(const double* host, unsigned long long seq, hipStream_t st)
 {
-   {
-      const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(host + HS_S1_OUT_DOUBLES);
-      long long spins = 0;
-      while ( *flag != seq )
-      {
-         if ( (++spins & 0x3FFF) == 0 )
-         {
-            const hipError_t e = hipStreamQuery(st);
-            if ( e == hipSuccess )
-            {
-               if ( *flag == seq )
-                  break;
-               set_err("the one-launch solve finished without publishing its results");
-               return HS_ERR_HIP;
-            }
-            if ( e != hipErrorNotReady )
-            {
-               hs_record_hip_error(e, "hipStreamQuery(one-launch solve)", __FILE__, __LINE__);
-               return HS_ERR_HIP;
-            }
-         }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-   }
-   return HS_OK;
+   const SeqWord w = {host, seq, 0};
+   char pub = 0;
+   wait_published(&w, 1, &st, 1, "hipStreamQuery(one-launch solve)", &pub);
+   return pub ? HS_OK : HS_ERR_HIP;
 }
 
 /* *done = true: the solve ran there; false: the kernel declined (too much work for one compute unit) or gave up numerically, and the
@@ -3914,19 +3933,11 @@ struct GeneralSolve
       if ( par.preoptgap > 0.0 && !s->pre_valid && pinf <= par.feastol && dabs <= par.feastol
          && gap / (1.0 + 0.5 * fabs(pobj / tau) + 0.5 * fabs(dobj / tau)) < par.preoptgap )
       {
-         if ( s->pre_y == NULL )
-         {
-            HS_CALL( dalloc(&s->pre_y, s->m_alloc > m ? s->m_alloc : m) );
-            HS_CALL( dalloc(&s->pre_x, s->q_alloc > q ? s->q_alloc : q) );
-         }
+         HS_CALL( ensure_preoptimal(s) );
          if ( m > 0 ) HS_CALL( hs_copy(st, s->pre_y, s->y, m) );
          if ( q > 0 ) HS_CALL( hs_copy(st, s->pre_x, s->x, q) );
          for (auto& B : s->blk)
-         {
-            if ( B.Xpre == NULL )
-               HS_CALL( dalloc(&B.Xpre, (long long) B.n * B.n) );
             HS_CALL( hs_copy(st, B.Xpre, B.X, (long long) B.n * B.n) );
-         }
          s->pre_scale = 1.0 / tau;
          s->pre_valid = true;
       }
@@ -4953,49 +4964,14 @@ extern "C" int hipsdp_solve_many(int count, hipsdp_solver* const* solvers, const
    /* 3. the sequence words of all launched problems, polled together; a launch queue that has finished while a member's word is
     * missing: that launch failed (asked at the cadence of hipsdp_solve's wait, counted in words read) */
    {
-      std::vector<char> pend((size_t) count, 0);
-      int left = 0;
+      std::vector<SeqWord> words((size_t) count);
+      std::vector<char> pub((size_t) count, 0);
       for (int i = 0; i < count; ++i)
-         if ( it[i].launched ) { pend[i] = 1; ++left; }
-      auto published = [&](int i) -> bool {
-         const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(it[i].pp.host + HS_S1_OUT_DOUBLES);
-         return *flag == it[i].pp.a.seq;
-      };
-      long long spins = 0;
-      while ( left > 0 )
-      {
-         for (int i = 0; i < count; ++i)
-            if ( pend[i] && published(i) ) { pend[i] = 0; --left; }
-         spins += left + 1;
-         if ( left == 0 || spins < 0x4000 )
-            continue;
-         spins = 0;
-         for (int c = 0; c < 4; ++c)
-         {
-            if ( lst[c] == NULL )
-               continue;
-            bool any = false;
-            for (int i : members[c]) any = any || pend[i];
-            if ( !any )
-               continue;
-            const hipError_t e = hipStreamQuery(lst[c]);
-            if ( e == hipErrorNotReady )
-               continue;
-            if ( e != hipSuccess )
-               hs_record_hip_error(e, "hipStreamQuery(one-launch solve of many)", __FILE__, __LINE__);
-            for (int i : members[c])
-               if ( pend[i] )
-               {
-                  pend[i] = 0; --left;
-                  if ( e == hipSuccess && published(i) )
-                     continue;
-                  if ( e == hipSuccess )
-                     set_err("the one-launch solve finished without publishing its results");
-                  it[i].rc = HIPSDP_ERR_HIP;
-               }
-         }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+         words[i] = SeqWord{it[i].pp.host, it[i].pp.a.seq, it[i].launched ? it[i].cls : -1};
+      wait_published(words.data(), count, lst, 4, "hipStreamQuery(one-launch solve of many)", pub.data());
+      for (int i = 0; i < count; ++i)
+         if ( it[i].launched && !pub[i] )
+            it[i].rc = HIPSDP_ERR_HIP;
    }
 
    /* 4. the results, then the general path for the problems the kernel declined or gave up on (from the same start) and the ones
@@ -5243,6 +5219,8 @@ extern "C" int hipsdp_solve_objectives(hipsdp_solver* s, int count, const double
          return leave(solve_end(s, r));
       ManyStage& g = g_many;
       std::vector<S1Prep> pp((size_t) chunk);
+      std::vector<SeqWord> words((size_t) chunk);
+      std::vector<char> pub((size_t) chunk, 0);
       int cls = 0;
       bool all_published = true;
       for (int c0 = 0; c0 < count; c0 += chunk)
@@ -5344,46 +5322,16 @@ extern "C" int hipsdp_solve_objectives(hipsdp_solver* s, int count, const double
             all_published = false;
             break;
          }
-         /* 6. the sequence words of the chunk, polled together (hipsdp_solve_many's loop on one queue) */
-         std::vector<char> pend((size_t) n, 1);
-         {
-            int left = n;
-            auto published = [&](int j) -> bool {
-               const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(pp[j].host + HS_S1_OUT_DOUBLES);
-               return *flag == pp[j].a.seq;
-            };
-            long long spins = 0;
-            while ( left > 0 )
-            {
-               for (int j = 0; j < n; ++j)
-                  if ( pend[j] && published(j) ) { pend[j] = 0; --left; }
-               spins += left + 1;
-               if ( left == 0 || spins < 0x4000 )
-                  continue;
-               spins = 0;
-               const hipError_t e = hipStreamQuery(st);
-               if ( e == hipErrorNotReady )
-                  continue;
-               if ( e != hipSuccess )
-                  hs_record_hip_error(e, "hipStreamQuery(one-launch solve of many objectives)", __FILE__, __LINE__);
-               for (int j = 0; j < n; ++j)
-                  if ( pend[j] )
-                  {
-                     --left;
-                     if ( e == hipSuccess && published(j) ) { pend[j] = 0; continue; }
-                     if ( e == hipSuccess )
-                        set_err("the one-launch solve finished without publishing its results");
-                     rc[c0 + j] = HIPSDP_ERR_HIP;
-                  }
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-         }
+         /* 6. the sequence words of the chunk, polled together */
+         for (int j = 0; j < n; ++j)
+            words[j] = SeqWord{pp[j].host, pp[j].a.seq, 0};
+         wait_published(words.data(), n, &st, 1, "hipStreamQuery(one-launch solve of many objectives)", pub.data());
          /* 7. every job's results out of its lane's pinned part: no copy from the device */
          bool chunk_ok = true;
          for (int j = 0; j < n; ++j)
          {
             const int J = c0 + j;
-            if ( pend[j] ) { chunk_ok = false; continue; }
+            if ( !pub[j] ) { rc[J] = HIPSDP_ERR_HIP; chunk_ok = false; continue; }
             S1Sol sol;
             bool done = false;
             rc[J] = solve1_result(s, &pp[j], &infos[J], &sol, &done);
@@ -5581,17 +5529,14 @@ extern "C" int hipsdp_sync_flag(hipsdp_solver* s, int* flag)
       return HIPSDP_OK;
    HS_HIP( hipSetDevice(s->device) );
    HS_CALL( stage_sync(s) );
-   int* d = NULL;
-   HS_CALL( dalloc(&d, 1) );
-   int rc = HS_OK;
-   if ( hipMemcpyAsync(d, flag, sizeof(int), hipMemcpyHostToDevice, s->stream) != hipSuccess ) rc = HS_ERR_HIP;
+   PoolBuf<int> d(s->stream);
+   HS_CALL( d.alloc(1) );
    hs_comm_phase(2);
-   if ( rc == HS_OK ) rc = hs_bcast_ints(s->comm, d, 1, s->stream);
-   if ( rc == HS_OK && (hipMemcpyAsync(flag, d, sizeof(int), hipMemcpyDeviceToHost, s->stream) != hipSuccess
-         || hipStreamSynchronize(s->stream) != hipSuccess) )
-      rc = HS_ERR_HIP;
-   dfree(d);
-   return rc;
+   HS_HIP( hipMemcpyAsync(d.p, flag, sizeof(int), hipMemcpyHostToDevice, s->stream) );
+   HS_CALL( hs_bcast_ints(s->comm, d.p, 1, s->stream) );
+   HS_HIP( hipMemcpyAsync(flag, d.p, sizeof(int), hipMemcpyDeviceToHost, s->stream) );
+   HS_HIP( hipStreamSynchronize(s->stream) );
+   return HS_OK;
 }
 
 /* a point y of the host for the passes over A: y in s->ys, (-1, y) in s->dyt, the packed triangles and the device form of the blocks
@@ -5607,26 +5552,20 @@ static int point_to_device(hipsdp_solver* s, const double* y)
 }
 
 /* The full decomposition of B.W (up to 128 rows: tridiagonal reduction, multisection, inverse iteration in one launch, eigi.hip; block
- * Jacobi above): its first nlam eigenvalues (ascending) to hlam, one read-back.  Vout (may be NULL): the eigenvectors, rows of an
- * n x n device array that the caller releases with dfree. */
-static int decompose_W(hipsdp_solver* s, Block& B, int nlam, double* hlam, double** Vout)
+ * Jacobi above): its first nlam eigenvalues (ascending) to hlam, one read-back.  Vout (may be NULL): the caller's empty
+ * buffer, which gets the eigenvectors as the rows of an n x n array. */
+static int decompose_W(hipsdp_solver* s, Block& B, int nlam, double* hlam, PoolBuf<double>* Vout)
 {
    const int n = B.n;
    hipStream_t st = s->stream;
-   double *lam = NULL, *V = NULL, *ws = NULL;
-   int rc = dalloc(&lam, n);
-   if ( rc == HS_OK ) rc = dalloc(&V, (long long) n * n);
-   if ( rc == HS_OK ) rc = dalloc(&ws, n <= 128 ? hs_syev_small_scratch(n) : hs_syev_ws(n));
-   if ( rc == HS_OK ) rc = n <= 128 ? hs_syev_small_dev(st, n, B.W, lam, V, ws) : hs_syev_jacobi(st, n, B.W, lam, V, NULL, ws);
-   if ( rc == HS_OK && (hipMemcpyAsync(hlam, lam, (size_t) nlam * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
-         || hipStreamSynchronize(st) != hipSuccess) )
-      rc = HS_ERR_HIP;
-   dfree(lam); dfree(ws);
-   if ( rc == HS_OK && Vout != NULL )
-      *Vout = V;
-   else
-      dfree(V);
-   return rc;
+   PoolBuf<double> lam(st), Vown(st), ws(st);
+   PoolBuf<double>& V = Vout != NULL ? *Vout : Vown;
+   HS_CALL( lam.alloc(n) ); HS_CALL( V.alloc((long long) n * n) );
+   HS_CALL( ws.alloc(n <= 128 ? hs_syev_small_scratch(n) : hs_syev_ws(n)) );
+   HS_CALL( n <= 128 ? hs_syev_small_dev(st, n, B.W, lam.p, V.p, ws.p) : hs_syev_jacobi(st, n, B.W, lam.p, V.p, NULL, ws.p) );
+   HS_HIP( hipMemcpyAsync(hlam, lam.p, (size_t) nlam * sizeof(double), hipMemcpyDeviceToHost, st) );
+   HS_HIP( hipStreamSynchronize(st) );
+   return HS_OK;
 }
 
 static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* lmin, double* lpviol);
@@ -5703,16 +5642,12 @@ static int check_y_impl(hipsdp_solver* s, const double* y, double tol, double* l
       {
          /* tridiagonalisation and Sturm multisection for the first eigenvalue alone (syevx.hip): accurate to rounding relative to
           * the norm of Z(y) at every scale, and cheaper than the factorization */
-         double *out = NULL, *ws = NULL;
+         PoolBuf<double> out(st), ws(st);
          double l0 = 0.0;
-         int rc = dalloc(&out, HS_SYEVX_OUT_VEC);
-         if ( rc == HS_OK ) rc = dalloc(&ws, (long long) hs_syevx_ws(n));
-         if ( rc == HS_OK ) rc = hs_syevx_dev(st, n, B.W, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, out, ws);
-         if ( rc == HS_OK && (hipMemcpyAsync(&l0, out + HS_SYEVX_OUT_LAM, sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
-               || hipStreamSynchronize(st) != hipSuccess) )
-            rc = HS_ERR_HIP;
-         dfree(out); dfree(ws);
-         HS_CALL( rc );
+         HS_CALL( out.alloc(HS_SYEVX_OUT_VEC) ); HS_CALL( ws.alloc((long long) hs_syevx_ws(n)) );
+         HS_CALL( hs_syevx_dev(st, n, B.W, HS_SYEVX_INDEX | HS_SYEVX_NOVEC, 1, 1, 0.0, 0, out.p, ws.p) );
+         HS_HIP( hipMemcpyAsync(&l0, out.p + HS_SYEVX_OUT_LAM, sizeof(double), hipMemcpyDeviceToHost, st) );
+         HS_HIP( hipStreamSynchronize(st) );
          lmin[b] = l0;
          continue;
       }
@@ -5768,36 +5703,27 @@ static int eigencuts_one(hipsdp_solver* s, int block, const double* y, double to
    hipStream_t st = s->stream;
    HS_CALL( point_to_device(s, y) );
    HS_CALL( pass_AT(s, B, s->dyt, 0.0, NULL, B.W) );
-   double *V = NULL, *out = NULL;
-   std::vector<double> hlam(n), hout;
-   int rc = dalloc(&out, m1);
-   if ( rc == HS_OK ) rc = decompose_W(s, B, n, hlam.data(), &V);
+   PoolBuf<double> V(st), out(st);
+   std::vector<double> hlam(n), hout(m1);
+   HS_CALL( out.alloc(m1) );
+   HS_CALL( decompose_W(s, B, n, hlam.data(), &V) );
    int k = 0;
-   if ( rc == HS_OK )
+   while ( k < n && k < maxcuts && hlam[k] <= -tol )
+      ++k;
+   for (int c = 0; c < k; ++c)
    {
-      while ( k < n && k < maxcuts && hlam[k] <= -tol )
-         ++k;
-      hout.resize(m1);
-   }
-   for (int c = 0; c < k && rc == HS_OK; ++c)
-   {
-      hipLaunchKernelGGL(k_outer_row, g1d(n2), dim3(256), 0, st, n, V, c, B.W2);
-      if ( hipGetLastError() != hipSuccess ) { rc = HS_ERR_HIP; break; }
-      rc = pass_A(s, B, B.W2, out);
-      if ( rc == HS_OK && (hipMemcpyAsync(hout.data(), out, (size_t) m1 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess
-            || hipStreamSynchronize(st) != hipSuccess) )
-         rc = HS_ERR_HIP;
-      if ( rc != HS_OK )
-         break;
+      hipLaunchKernelGGL(k_outer_row, g1d(n2), dim3(256), 0, st, n, V.p, c, B.W2);
+      HS_LAUNCH_CHECK();
+      HS_CALL( pass_A(s, B, B.W2, out.p) );
+      HS_HIP( hipMemcpyAsync(hout.data(), out.p, (size_t) m1 * sizeof(double), hipMemcpyDeviceToHost, st) );
+      HS_HIP( hipStreamSynchronize(st) );
       eigvals[c] = hlam[c];
       lhs[c] = hout[0];
       for (int i = 0; i < m; ++i)
          coefs[(size_t) c * m + i] = hout[1 + i];
-      if ( vecs != NULL && hipMemcpy(vecs + (size_t) c * n, V + (size_t) c * n, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess )
-         rc = HS_ERR_HIP;
+      if ( vecs != NULL )
+         HS_HIP( hipMemcpy(vecs + (size_t) c * n, V.p + (size_t) c * n, (size_t) n * sizeof(double), hipMemcpyDeviceToHost) );
    }
-   dfree(V); dfree(out);
-   HS_CALL( rc );
    *ncuts = k;
    if ( lam0 != NULL )
       *lam0 = hlam[0];

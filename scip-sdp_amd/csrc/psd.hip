@@ -195,14 +195,6 @@ static int d2h_through_staging(int device, hipStream_t st, void* dst, const void
    return rc;
 }
 
-template<class T> struct PoolBuf
-{
-   T* p;
-   PoolBuf() : p(NULL) {}
-   ~PoolBuf() { if ( p != NULL ) hs_pool_free(p); }
-   int alloc(long long count) { return hs_pool_alloc((void**) &p, (size_t) (count > 0 ? count : 1) * sizeof(T)); }
-};
-
 }
 
 /* one projection, the body of hipsdp_psd_project; hipsdp_psd_project_many (psd_many.hip) sends its jobs above 128 rows here */
@@ -221,8 +213,8 @@ int hs_psd_project_one(int device, int n, int nnz, const int* row, const int* co
    HS_HIP( hipSetDevice(device) );
    hipStream_t st = 0;
    const long long n2 = (long long) n * n;
-   PoolBuf<double> A, lam, V, S, ws, dval, oval;
-   PoolBuf<int> drow, dcol, cnt, off, orow, ocol;
+   PoolBuf<double> A(st), lam(st), V(st), S(st), ws(st), dval(st), oval(st);
+   PoolBuf<int> drow(st), dcol(st), cnt(st), off(st), orow(st), ocol(st);
    HS_CALL( A.alloc(n2) ); HS_CALL( lam.alloc(n) ); HS_CALL( V.alloc(n2) ); HS_CALL( S.alloc(n2) ); HS_CALL( ws.alloc(hs_syev_ws(n)) );
    HS_CALL( drow.alloc(nnz) ); HS_CALL( dcol.alloc(nnz) ); HS_CALL( dval.alloc(nnz) );
    HS_CALL( cnt.alloc(n) ); HS_CALL( off.alloc(n + 1) );
@@ -271,7 +263,7 @@ int hs_psd_project_one(int device, int n, int nnz, const int* row, const int* co
    }
    /* the decomposition SCIPlapackComputeEigenvectorDecomposition returns for this size (the literal chain of mode 0 depends on the
     * basis: both paths must use the same eigenvectors) */
-   PoolBuf<double> scr;                              /* (lives to the end of the call: no wait in the middle of the chain) */
+   PoolBuf<double> scr(st);                            /* (lives to the end of the call: no wait in the middle of the chain) */
    if ( n <= 128 )
    {
       HS_CALL( scr.alloc(hs_syev_small_scratch(n)) );

@@ -28,6 +28,17 @@ def marshal(slots, N, node):
     return cat(var, np.int32), cat(row, np.int32), cat(col, np.int32), cat(val, np.float64)
 
 
+def once_per_position(slots):
+    """the same matrices with every position named once, in the lower triangle (the later entry of a repeated position stays)"""
+    out = []
+    for r, c, v in slots:
+        ent = {}
+        for ri, ci, vi in zip(r, c, v):
+            ent[(max(int(ri), int(ci)), min(int(ri), int(ci)))] = float(vi)
+        out.append(([k[0] for k in ent], [k[1] for k in ent], list(ent.values())))
+    return out
+
+
 def shape_a():
     """N = 12, 6 slots: slot 1 dense (78 lower entries: the ballot compaction crosses a wavefront), slot 2 sits entirely on rows 0,
     5 and 11, slot 3 on the diagonal, slot 4 is given partly in the upper triangle with repeated positions, all share (7, 3)"""

@@ -200,25 +200,14 @@ def test_workspace_of_the_master_block_carries_nothing_over(gpu):
 
 # ---- 4. dense target, read-back of the matrices ------------------------------------------------------------------------------
 
-def once_per_position(slots):
-    """the same matrices with every position named once, in the lower triangle (the later entry of a repeated position stays)"""
-    out = []
-    for r, c, v in slots:
-        ent = {}
-        for ri, ci, vi in zip(r, c, v):
-            ent[(max(int(ri), int(ci)), min(int(ri), int(ci)))] = float(vi)
-        out.append(([k[0] for k in ent], [k[1] for k in ent], list(ent.values())))
-    return out
-
-
 def test_dense_engine_block_and_get_block_dense(gpu):
     """a triplet master block gathered into a DENSE engine block against the dense master's gather, and hipsdp_get_block_dense of a
     gathered block kept as nonzeros against the direct load's.  The dense master scatters its entries in no order - which of two
     entries at one position stays is not defined there - so both masters of the first comparison get every position once; the
     blocks kept as nonzeros, where the later entry counts by rule, get the repeated positions of shape A as they are."""
     N, slots, nodes = cases.shape_a()
-    st = gpu.Solver(0); st.sparse_policy(0); define_master(st, N, once_per_position(slots), triplets=True)
-    sd = gpu.Solver(0); sd.sparse_policy(0); define_master(sd, N, once_per_position(slots), triplets=False)
+    st = gpu.Solver(0); st.sparse_policy(0); define_master(st, N, cases.once_per_position(slots), triplets=True)
+    sd = gpu.Solver(0); sd.sparse_policy(0); define_master(sd, N, cases.once_per_position(slots), triplets=False)
     sg = gpu.Solver(0); sg.sparse_policy(2); define_master(sg, N, slots, triplets=True)
     sh = gpu.Solver(0); sh.sparse_policy(2)
     for node in nodes:
