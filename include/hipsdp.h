@@ -456,6 +456,44 @@ HIPSDP_API int hipsdp_eigencuts_all_large(hipsdp_solver* solver, const double* y
  * reverse */
 HIPSDP_API int hipsdp_eigencuts_all_large_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* The feasibility check of MANY candidate points in one call: what SCIPsdpSolcheckerCheck / CONSCHECK (sdpsolchecker.c:201-257) computes
+ * for every solution a heuristic proposes - per block the smallest eigenvalue of Z_b(y) = sum_i A_i^b y_i - A_0^b, and the LP rows - for
+ * count points at once (the roundings of heur_sdprand.c:353-420, the fully fixed nodes of a branch and bound).  Y: count x m, row-major,
+ * host values (engine variables).
+ *     lmin[j nblocks + b] = eigenvalue 1 of Z_b(Y[j]), a COMPUTED eigenvalue at every served size (not the Lanczos lower estimate
+ *                           hipsdp_check_y returns up to 200 rows), with the accuracy of the SCALE RANGE paragraph below: within 1e-12 of
+ *                           the largest eigenvalue in absolute value;
+ *     lpviol[j]           = max(0, max_r (c_r - (D Y[j])_r)), the convention of hipsdp_check_y; 0 without LP rows; lpviol may be NULL;
+ *     served[b]           = 0: block b is served; -1: it is not, and column b of lmin is not written.  served may be NULL.
+ * Served: blocks of 1 .. 512 rows of a solver without communicator and without sharded matrices, in all three storage forms (dense rows,
+ * packed lower triangles, nonzeros).  Not served: a block of more than 512 rows or without matrices on this device; the other blocks
+ * are still served.  A solver with a communicator or sharded matrices: every served = -1, nothing launched, lmin and lpviol not written,
+ * HIPSDP_OK.  hipsdp_check_y remains the call for one point, with its own semantics.
+ * HIPSDP_ERR_ARG, before the device is looked at and with nothing launched: solver NULL or without a shape, count < 0, Y or lmin NULL
+ * with count > 0.  count == 0: HIPSDP_OK, nothing launched, nothing written (served included), the totals unchanged.
+ * The device side (csrc/check_many.hip, csrc/eigi.hip, csrc/syevx.hip): ONE launch forms Z_b(Y[j]) of all served blocks and candidates,
+ * a group of 8 candidates per pass over a block's storage - the pass a loop over hipsdp_check_y or hipsdp_eigencuts_all makes once per
+ * candidate; eigenvalue 1 alone, no vector, by the tridiagonalisation and Sturm multisection of hipsdp_syevi_small up to 128 rows (a
+ * matrix per workgroup up to 64 rows, one launch; at most a workgroup per compute unit that runs its matrices one after the other for
+ * 65 .. 128 rows, one launch) and by the batched tridiagonal path of hipsdp_syevx for 129 .. 512 rows (the reflector arrays cleared,
+ * nmax - 1 column launches that hold the matrices of all candidates and blocks, 3 selection launches; nmax: rows of the largest served
+ * block above 128 rows); ONE launch stores lmin and evaluates the LP rows.  Kernel launches of a call, with [..] = 1 when a served block
+ * of that class exists:
+ *     [any block] + [1 .. 64 rows] + [65 .. 128 rows] + [129 .. 512 rows] (nmax + 3) + 1
+ * - a function of the classes present and of nmax alone, never of count or of the number of blocks -, one upload and ONE read-back.
+ * A candidate takes n_b^2 doubles of the solver's grow-only cut workspace per block up to 128 rows and about 2 n_b^2 + 165 n_b above: the
+ * candidates run in chunks of at most 512 MiB (HIPSDP_CHECK_MANY_CHUNK in the environment, read at every call: candidates per chunk
+ * instead), and every chunk is a call of its own in launches and read-backs.
+ * The bits of (j, b) depend on the block and on row j of Y alone - not on count, the other candidates, j's position, the other blocks or
+ * the chunks; same input, same bits; no floating-point atomics.  Two host threads may call it at the same time on different solvers. */
+HIPSDP_API int hipsdp_check_y_many(hipsdp_solver* solver, int count, const double* Y /* count x m, row-major, host */,
+                                   double* lmin   /* count x nblocks */,
+                                   double* lpviol /* count; may be NULL */,
+                                   int* served    /* nblocks; may be NULL */);
+/* process totals of hipsdp_check_y_many alone: calls that launched something, kernel launches they issued, device->host synchronisations
+ * they waited on (one per chunk); any pointer may be NULL.  The totals of the other calls do not move, and the reverse */
+HIPSDP_API int hipsdp_check_y_many_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* All one-variable SDPs of a block in one call: the bound-tightening loops of cons_sdp.c - tightenBounds (:1968-2201) and
  * tightenMatrices (:1856-1961) solve one SDP PER VARIABLE of a block, each the semismooth Newton method of
  * SCIPsolveOneVarSDPDense (solveonevarsdp.c:370-533) on  mu A_i - C_i,  C_i = A_0 - sum_{k != i} ub_k A_k.  With

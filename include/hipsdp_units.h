@@ -205,6 +205,14 @@ HIPSDP_API int  hipsdp_syevr_many_unit(int device, int count, const int* n, cons
  * soff[m + 1], srow[nslots], sent[nslots + 1].  A first call with the arrays NULL gives the counts to size them by. */
 HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long long* counts, int* voff, int* vrow, int* vcol, double* vval,
    int* poff, int* prow, int* pcol, int* pvar, double* pval, int* foff, int* frow, int* fcol, double* fval, int* soff, int* srow, int* sent);
+/* the first launch of hipsdp_check_y_many (csrc/check_many.hip: k_cm_form_z) alone on a loaded solver CREATED FROM THIS LIBRARY: Z_b(Y[j])
+ * of every candidate j < count (Y: count x m, row-major, host) and every block b of at most 512 rows the call serves, as plain n_b x n_b
+ * arrays: Z + j (n_0^2 + ... + n_{nb-1}^2) + (n_0^2 + ... + n_{b-1}^2).  served[b] (may be NULL) = 0, or -1 for a block that is not
+ * served, whose parts of Z are not written.  *launches: the kernel launches issued (one, whatever count and the blocks are).
+ * HIPSDP_ERR_ARG: solver NULL or without a shape, count < 1, Y, Z or launches NULL. */
+HIPSDP_API int  hipsdp_form_z_many_unit(hipsdp_solver* solver, int count, const double* Y, double* Z, int* served, int* launches);
+/* the candidates k_cm_form_z serves per pass over a block's storage (HS_CM_G, a compile-time constant of csrc/hs_kernels.h) */
+HIPSDP_API int  hipsdp_check_many_group(void);
 /* the Newton kernel of hipsdp_onevar_bounds (csrc/eigi.hip: k_onevar_small for n <= 64, k_onevar_mid for n <= 128) alone on host
  * matrices: Z (n x n) and, for job j < count, the dense A + j n^2 (n x n), the shift shift[j] (= u_i), kind[j] (NULL: all NEWTON),
  * lb[j], ub[j]: M_j(mu) = Z + (mu - shift[j]) A_j.  infinity is 1e20, maxevals <= 0 means 100.  status, optval, lmin, grad, evals as

@@ -439,6 +439,41 @@ class Solver:
         """process totals (calls, launches, read-backs): the module's eigencuts_all_large_stats()"""
         return eigencuts_all_large_stats()
 
+    def check_y_many(self, Y, lmin_fill=np.nan):
+        """the feasibility check of many candidate points in one call (hipsdp_check_y_many): Y is count x m; returns
+        (lmin[count, nblocks], lpviol[count], served[nblocks]) - served[b] = -1: block b is not served and column b of lmin keeps
+        lmin_fill"""
+        Y = _f64(Y).reshape(-1, self.m) if self.m > 0 else np.zeros((len(Y), 0))
+        count, nb = Y.shape[0], len(self.ns)
+        lmin = np.full((max(1, count), max(1, nb)), lmin_fill, dtype=np.float64)
+        viol = np.zeros(max(1, count))
+        served = np.full(max(1, nb), -1, dtype=np.int32)
+        _chk(self._l().hipsdp_check_y_many(self.h, count, _dp(Y), _dp(lmin), _dp(viol), _ip(served)), "hipsdp_check_y_many")
+        return lmin[:count, :nb], viol[:count], served[:nb]
+
+    def check_y_many_stats(self):
+        """process totals (calls, launches, read-backs) of hipsdp_check_y_many in the library this solver lives in"""
+        return check_y_many_stats(self._l)
+
+    def form_z_many_unit(self, Y):
+        """k_cm_form_z alone (hipsdp_form_z_many_unit; the solver must have been created with units=True): Y is count x m; returns
+        ([per block b: Z[count, n_b, n_b] or None for a block that is not served], launches)"""
+        assert self._l is ulib
+        Y = _f64(Y).reshape(-1, self.m) if self.m > 0 else np.zeros((len(Y), 0))
+        count, nb = Y.shape[0], len(self.ns)
+        per = sum(n * n for n in self.ns)
+        Z = np.full((count, max(1, per)), np.nan)
+        served = np.full(max(1, nb), -1, dtype=np.int32)
+        launches = C.c_int(-1)
+        rc = ulib().hipsdp_form_z_many_unit(self.h, count, _dp(Y), _dp(Z), _ip(served), C.byref(launches))
+        if rc != 0:
+            raise RuntimeError("hipsdp_form_z_many_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+        out, off = [], 0
+        for b, n in enumerate(self.ns):
+            out.append(Z[:, off:off + n * n].reshape(count, n, n).copy() if served[b] == 0 else None)
+            off += n * n
+        return out, launches.value
+
     def sparsecuts_all(self, y, sizes, tol, feastol, maxcuts, convtol=0, maxit=0):
         """sparse eigenvector cuts of all blocks in one call (hipsdp_sparsecuts_all; sizes[b]: target sparsity of block b): per block
         a tuple (ncuts, lmin, eigvals[k], coefs[k, m], lhs[k], vecs[k, n], iters, flags); ncuts = -1: the block is not served (then
@@ -854,6 +889,19 @@ def eigencuts_all_large_stats():
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk(lib().hipsdp_eigencuts_all_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_large_stats")
     return calls.value, launches.value, readbacks.value
+
+
+def check_y_many_stats(which=None):
+    """process totals of hipsdp_check_y_many: (calls that launched something, kernel launches issued, device->host synchronisations);
+    which: the library loader whose copy of the engine is asked (lib, the default, or ulib)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk((which or lib)().hipsdp_check_y_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_check_y_many_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def check_many_group():
+    """the candidates k_cm_form_z serves per pass over a block's storage (hipsdp_check_many_group of the units library)"""
+    return int(ulib().hipsdp_check_many_group())
 
 
 def syevx_many_below_unit(mats, bound, maxk, cap, device=0):

@@ -2,7 +2,8 @@
  * hipsdp_eigencuts_all (kernels: eigcuts.hip, many-forms of the decompositions: eigi.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts
  * (sparsecuts.hip, sparsecuts_large.hip), their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip), and
  * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip),
- * and hipsdp_eigencuts_all_large, the partner of hipsdp_eigencuts_all for those blocks (eigcuts_large.hip).
+ * and hipsdp_eigencuts_all_large, the partner of hipsdp_eigencuts_all for those blocks (eigcuts_large.hip).  At the end of the file:
+ * hipsdp_check_y_many, the feasibility check of many candidate points per call (check_many.hip).
  *
  * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
  * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
@@ -21,8 +22,8 @@
 namespace {
 
 /* hipsdp_eigencuts_all, hipsdp_sparsecuts_all, hipsdp_sparsecuts, the two _ex calls with a switch set, hipsdp_sparsecuts_all_large,
- * hipsdp_eigencuts_all_large */
-CutStats g_ec, g_sc, g_sc1, g_scx, g_scl, g_ecl;
+ * hipsdp_eigencuts_all_large, hipsdp_check_y_many */
+CutStats g_ec, g_sc, g_sc1, g_scx, g_scl, g_ecl, g_cm;
 
 /* the caller's arrays of a call, or of one block of it (all but ncuts may be NULL) */
 struct CutDst
@@ -862,4 +863,262 @@ extern "C" int hipsdp_eigencuts_all_large(hipsdp_solver* s, const double* y, dou
    double* coefs, double* lhs, double* vecs)
 {
    return eigencuts_all_large_impl(s, y, tol, maxcuts, CutDst{ncuts, lmin, eigvals, coefs, lhs, vecs, NULL, NULL});
+}
+
+namespace {
+
+/* ---- hipsdp_check_y_many: the feasibility check of many candidate points (kernels: check_many.hip, eigi.hip, syevx.hip) ---------------- */
+static_assert(sizeof(hs_cm_blk) == 4 * sizeof(double), "hs_cm_layout: blkw");
+#define CM_BLKW 4
+
+/* the blocks the call serves, in the order of its tables: at most 64 rows, 65 .. 128 rows, 129 .. 512 rows by descending n, the caller's
+ * order inside a class and among equal sizes; nmax_*: the largest block of a class (0: none), nmax: of all */
+struct CmBlocks
+{
+   std::vector<int> ids;
+   int nsmall, nmid, nlarge, nmax_small, nmax_mid, nmax_large, nmax;
+};
+
+int cm_class(int n) { return n <= 64 ? 0 : (n <= HS_SC_MAXN ? 1 : 2); }
+
+int cm_served(hipsdp_solver* s, CmBlocks* P)
+{
+   std::vector<int> all;
+   HS_CALL( hs_solver_cut_enter_large(s, HS_SYEVX_MAXN, &all) );
+   P->ids.clear();
+   P->nsmall = P->nmid = P->nlarge = P->nmax_small = P->nmax_mid = P->nmax_large = 0;
+   for (int cls = 0; cls < 3; ++cls)
+      for (int b : all)
+      {
+         const int n = hs_solver_block_n(s, b);
+         if ( cm_class(n) != cls )
+            continue;
+         P->ids.push_back(b);
+         int& cnt = cls == 0 ? P->nsmall : (cls == 1 ? P->nmid : P->nlarge);
+         int& top = cls == 0 ? P->nmax_small : (cls == 1 ? P->nmax_mid : P->nmax_large);
+         ++cnt;
+         top = n > top ? n : top;
+      }
+   std::stable_sort(P->ids.begin() + P->nsmall + P->nmid, P->ids.end(),
+      [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
+   P->nmax = std::max(P->nmax_small, std::max(P->nmax_mid, P->nmax_large));
+   return HS_OK;
+}
+
+/* what a matrix of n rows takes of a chunk's workspace: Z alone up to 128 rows, above that the workspace of the tridiagonal form (Z is
+ * formed into its head) and the selection output */
+hs_ecl_block cm_large_block(int n) { return hs_ecl_block_make((long long) hs_syevx_ws(n), HS_SXM_OUT(n)); }
+long long cm_mat_len(int n) { return n <= HS_SC_MAXN ? hs_cut_mat_len(n) : cm_large_block(n).len; }
+
+/* a chunk between its layout and its launches: the workspace with the solver's table of the served blocks (w.djobs), the layout, where
+ * the matrices of every served block start */
+struct CmRun
+{
+   hs_solver_cut_ws w;
+   hs_cm_layout L;
+   std::vector<long long> start;       /* [nsv]: doubles from the device workspace's start */
+   int launches;
+};
+
+/* The head of the chunk over the candidates Y[0 .. cc) (rows of m): the layout - with_eig = false: every block's matrices are plain
+ * n x n arrays and nothing of the eigenvalue path is laid out (the unit entry) -, the workspace, Yg, the block table and, for the
+ * blocks of 129 .. 512 rows, the jobs of the batched tridiagonal path in the pinned mirror, the ONE upload, Z of every (candidate, block). */
+int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y, bool with_eig, CmRun* R)
+{
+   const int nsv = (int) P.ids.size(), nlarge = with_eig ? P.nlarge : 0, nsm = nsv - nlarge;
+   R->start.resize((size_t) nsv);
+   R->launches = 0;
+   long long blocks_len = 0;
+   for (int k = 0; k < nsv; ++k)
+   {
+      const int n = hs_solver_block_n(s, P.ids[k]);
+      R->start[k] = blocks_len;
+      blocks_len += (long long) cc * (k < nsm ? hs_cut_mat_len(n) : cm_large_block(n).len);
+   }
+   hs_cm_layout& L = R->L;
+   hs_cm_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, blocks_len, &L);
+   HS_CALL( hs_solver_cut_blocks(s, P.ids, std::vector<long long>((size_t) nsv, 0), L.len.dev_len, L.len.pin_len, &R->w) );
+   const hs_solver_cut_ws& w = R->w;
+   /* Yg[g][i][k] = Y[g HS_CM_G + k][i], zeros behind the last candidate */
+   double* yg = w.pin + L.Yg;
+   memset(yg, 0, (size_t) (L.blks - L.Yg) * sizeof(double));
+   for (int c = 0; c < cc; ++c)
+   {
+      double* dst = yg + (long long) (c / HS_CM_G) * m * HS_CM_G + c % HS_CM_G;
+      const double* src = Y + (size_t) c * m;
+      for (int i = 0; i < m; ++i)
+         dst[(long long) i * HS_CM_G] = src[i];
+   }
+   hs_cm_blk* hb = reinterpret_cast<hs_cm_blk*>(w.pin + L.blks);
+   hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
+   int* hact = reinterpret_cast<int*>(w.pin + L.act);
+   for (int k = 0; k < nsv; ++k)
+   {
+      const int n = hs_solver_block_n(s, P.ids[k]);
+      double* base = w.dev + L.blocks + R->start[k];
+      hs_cm_blk& B = hb[k];
+      if ( k < nsm )
+      {
+         B.Z = base; B.zstride = hs_cut_mat_len(n);
+         B.lam = w.dev + L.lam + 2LL * cc * k; B.lstride = 2;
+         continue;
+      }
+      /* job (block k, candidate c) of the tridiagonal path: Z goes where the column launches read their matrix, the head of its workspace */
+      const hs_ecl_block E = cm_large_block(n);
+      for (int c = 0; c < cc; ++c)
+      {
+         const size_t j = (size_t) (k - nsm) * cc + c;
+         double* jb = base + (long long) c * E.len;
+         HS_CALL( hs_syevx_many_job(n, jb + E.ws, jb + E.out, &hsx[j]) );
+         if ( hsx[j].A != jb + E.ws )
+            return HIPSDP_ERR_NUMERIC;
+         hact[j] = HS_SXM_ACTIVE;
+      }
+      B.Z = base + E.ws; B.zstride = E.len;
+      B.lam = base + E.out + HS_SYEVX_OUT_LAM; B.lstride = E.len;
+   }
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, w.stream) );
+   if ( nsv > 0 )
+   {
+      HS_CALL( hs_cm_form_z(w.stream, nsv, P.nmax, m, cc, w.djobs, reinterpret_cast<const hs_cm_blk*>(w.dev + L.blks), w.dev + L.Yg) );
+      ++R->launches;
+   }
+   return HS_OK;
+}
+
+/* ONE CHUNK: the candidates Y[0 .. cc) - a call of its own in everything but the entry: ONE upload, hs_cm_launches(..) launches whatever
+ * cc and the number of blocks are, ONE read-back, the copy-out to lmin (rows of nb) and lpviol (may be NULL) of these candidates */
+int cm_chunk(hipsdp_solver* s, int m, int nb, const CmBlocks& P, int q, const double* Dext, int cc, const double* Y, double* lmin, double* lpviol)
+{
+   CmRun R;
+   HS_CALL( cm_begin(s, m, P, cc, Y, true, &R) );
+   const hs_solver_cut_ws& w = R.w;
+   const hs_cm_layout& L = R.L;
+   hipStream_t st = w.stream;
+   const int nsv = (int) P.ids.size();
+   const hs_cm_blk* db = reinterpret_cast<const hs_cm_blk*>(w.dev + L.blks);
+   if ( P.nsmall > 0 )
+   {
+      HS_CALL( hs_lmin_many_small(st, P.nsmall, cc, P.nmax_small, w.djobs, db) );
+      ++R.launches;
+   }
+   if ( P.nmid > 0 )
+   {
+      const int cus = hs_device_cus();
+      HS_CALL( hs_lmin_many_mid(st, P.nmid, cc, P.nmax_mid, cus > 0 ? cus : 256, w.djobs + P.nsmall, db + P.nsmall) );
+      ++R.launches;
+   }
+   if ( P.nlarge > 0 )
+   {
+      const int jobs = P.nlarge * cc;
+      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
+      const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
+      HS_CALL( hs_ecl_clear(st, jobs, dsx) );
+      HS_CALL( hs_syevx_many_cols(st, jobs, P.nmax_large, hs_syevx_many_cap(jobs), dsx, dact) );
+      HS_CALL( hs_syevx_many_select(st, jobs, P.nmax_large, 0, dsx, dact) );
+      R.launches += 1 + (P.nmax_large - 1) + 3;
+   }
+   HS_CALL( hs_cm_result(st, nsv, cc, m, q, Dext, db, w.dev + L.Yg, w.dev + L.res) );
+   ++R.launches;
+   if ( R.launches != hs_cm_launches(nsv > 0, P.nsmall > 0, P.nmid > 0, P.nmax_large) )
+      return HIPSDP_ERR_NUMERIC;
+   hs_cut_res none;
+   memset(&none, 0, sizeof(none));
+   none.ints = none.sup = -1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, none, L.len, R.launches, &g_cm, &h) );
+   const double* res = w.pin + L.res;
+   for (int c = 0; c < cc; ++c)
+   {
+      for (int k = 0; k < nsv; ++k)
+         lmin[(size_t) c * nb + P.ids[k]] = res[(size_t) c * nsv + k];
+      if ( lpviol != NULL )
+         lpviol[c] = res[(size_t) cc * nsv + c];
+   }
+   return HIPSDP_OK;
+}
+
+int check_y_many_impl(hipsdp_solver* s, int count, const double* Y, double* lmin, double* lpviol, int* served)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || count < 0 || (count > 0 && (Y == NULL || lmin == NULL)) )
+      return HIPSDP_ERR_ARG;
+   if ( count == 0 )
+      return HIPSDP_OK;
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = -1;
+   int q = 0;
+   const double* Dext = NULL;
+   if ( !hs_solver_lp_rows(s, &q, &Dext) )
+      return HIPSDP_OK;
+   CmBlocks P;
+   HS_CALL( cm_served(s, &P) );
+   if ( served != NULL )
+      for (int b : P.ids)
+         served[b] = 0;
+   if ( P.ids.empty() && q == 0 )
+   {
+      if ( lpviol != NULL )
+         for (int j = 0; j < count; ++j)
+            lpviol[j] = 0.0;
+      return HIPSDP_OK;
+   }
+   /* what a candidate takes of the workspace: its matrices, its eigenvalues, its point, its jobs and its row of the result */
+   long long per = (long long) m + (long long) P.nlarge * (SCLR_JOBW + 1) + 3LL * P.ids.size() + 1;
+   for (int b : P.ids)
+      per += cm_mat_len(hs_solver_block_n(s, b));
+   const std::vector<long long> job_len((size_t) count, per);
+   HS_CALL( hs_chunks_run(job_len.data(), count, SCLR_BUDGET, hs_chunk_env("HIPSDP_CHECK_MANY_CHUNK"), [&](int start, int end)
+      {
+         return cm_chunk(s, m, nb, P, q, Dext, end - start, Y + (size_t) start * m, lmin + (size_t) start * nb,
+            lpviol != NULL ? lpviol + start : NULL);
+      }) );
+   ++g_cm.calls;
+   return HIPSDP_OK;
+}
+
+}
+
+int hs_check_many_form_z(hipsdp_solver* s, int count, const double* Y, double* Zout, int* served, int* launches)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || count < 1 || Y == NULL || Zout == NULL || launches == NULL )
+      return HIPSDP_ERR_ARG;
+   *launches = 0;
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = -1;
+   CmBlocks P;
+   HS_CALL( cm_served(s, &P) );
+   if ( P.ids.empty() )
+      return HIPSDP_OK;
+   CmRun R;
+   HS_CALL( cm_begin(s, m, P, count, Y, false, &R) );
+   std::vector<long long> off((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+      off[b + 1] = off[b] + (long long) hs_solver_block_n(s, b) * hs_solver_block_n(s, b);
+   for (size_t k = 0; k < P.ids.size(); ++k)
+   {
+      const int b = P.ids[k], n = hs_solver_block_n(s, b);
+      const double* Z = R.w.dev + R.L.blocks + R.start[k];
+      for (int c = 0; c < count; ++c)
+         HS_HIP( hipMemcpyAsync(Zout + (size_t) c * off[nb] + off[b], Z + (long long) c * hs_cut_mat_len(n), (size_t) n * n * sizeof(double),
+               hipMemcpyDeviceToHost, R.w.stream) );
+      if ( served != NULL )
+         served[b] = 0;
+   }
+   HS_HIP( hipStreamSynchronize(R.w.stream) );
+   *launches = R.launches;
+   return HIPSDP_OK;
+}
+
+extern "C" int hipsdp_check_y_many(hipsdp_solver* s, int count, const double* Y, double* lmin, double* lpviol, int* served)
+{
+   return check_y_many_impl(s, count, Y, lmin, lpviol, served);
+}
+
+extern "C" int hipsdp_check_y_many_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_cm.get(calls, launches, readbacks);
 }

@@ -1987,6 +1987,30 @@ __global__ void __launch_bounds__(256) k_syevi_small_many(const hs_eig_job* __re
       reinterpret_cast<unsigned long long*>(job.ws + EI_N + (long long) EI_N * EI_N + 4));
 }
 
+/* many-forms of the two i-th eigenvalue bodies with i = 1 and no vector (hipsdp_check_y_many): matrix (block b, candidate c) of the
+ * tables of check_many.hip lies at blks[b].Z + c zstride, its eigenvalue goes to blks[b].lam + c lstride (two doubles: the value and the
+ * half width of its interval).  Up to 64 rows a matrix per workgroup; above, the bounded grid of k_onevar_all_mid: workgroup w runs the
+ * matrices w, w + grid, ... one after the other, the barrier behind a matrix between wavefront 0's last read of the LDS and the next
+ * reduction's first write.  The bits of a matrix are those of the body on it alone. */
+__global__ void __launch_bounds__(256) k_lmin_many_small(const hs_ec_job* __restrict__ jobs, const hs_cm_blk* __restrict__ blks)
+{
+   const hs_cm_blk B = blks[blockIdx.y];
+   const long long c = blockIdx.x;
+   d_syevi_small<false>(jobs[blockIdx.y].n, 1, 0, B.Z + c * B.zstride, B.lam + c * B.lstride, 0ULL, NULL);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_lmin_many_mid(int cc, int total, const hs_ec_job* __restrict__ jobs, const hs_cm_blk* __restrict__ blks)
+{
+   for (int job = blockIdx.x; job < total; job += (int) gridDim.x)
+   {
+      const int b = job / cc;
+      const long long c = job - b * cc;
+      const hs_cm_blk B = blks[b];
+      d_syevi_mid(jobs[b].n, 1, 0, B.Z + c * B.zstride, B.lam + c * B.lstride, 0ULL, NULL);
+      __syncthreads();
+   }
+}
+
 /* dynamic LDS of k_syev_mid: the matrix / the eigenvectors of T, and up to 64 rows the two factor arrays of the inverse iteration */
 static size_t em_all_lds(int n)
 {
@@ -2367,6 +2391,31 @@ int hs_onevar_large_decide(hipStream_t st, const hs_ovl_par* P)
       return HS_ERR_ARG;
    hipLaunchKernelGGL(k_onevar_large_decide, dim3(P->count), dim3(256), 0, st, *P);
    hipLaunchKernelGGL(k_onevar_large_count, dim3(1), dim3(256), 0, st, P->count, P->act, P->nactive);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* eigenvalue 1 of cc matrices of each of nblk blocks (hipsdp_check_y_many): jobs / blks are the entries of the first block of the class
+ * in the two device tables.  hs_lmin_many_small: every block has at most 64 rows, grid (cc, nblk).  hs_lmin_many_mid: 65 to 128 rows,
+ * nmax the largest of them, `grid` workgroups that stride over the cc nblk matrices.  One launch each. */
+int hs_lmin_many_small(hipStream_t st, int nblk, int cc, int nmax, const hs_ec_job* jobs, const hs_cm_blk* blks)
+{
+   if ( nblk < 1 || cc < 1 || nmax < 1 || nmax > EI_N || jobs == NULL || blks == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_lmin_many_small, dim3(cc, nblk), dim3(256), 0, st, jobs, blks);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_lmin_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const hs_ec_job* jobs, const hs_cm_blk* blks)
+{
+   if ( nblk < 1 || cc < 1 || nmax <= EI_N || nmax > EM_N || grid < 1 || (long long) nblk * cc > 0x7fffffffLL || jobs == NULL || blks == NULL )
+      return HS_ERR_ARG;
+   const int total = nblk * cc;
+   static hs_attr_mask attr_mid;
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_lmin_many_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
+   hipLaunchKernelGGL(k_lmin_many_mid, dim3(grid < total ? grid : total), dim3(EM_NT), (size_t) nmax * (nmax | 1) * sizeof(double), st, cc, total,
+      jobs, blks);
    HS_HIP( hipGetLastError() );
    return HS_OK;
 }

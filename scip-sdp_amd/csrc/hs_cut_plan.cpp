@@ -132,6 +132,20 @@ void hs_sclr_layout_make(int nb, int m, int maxcuts, int smax, long long vec_len
    L->len.upload_len = L->len.res_off; L->len.pin_len = L->r.sup; L->len.dev_len = L->blocks + blocks_len;
 }
 
+void hs_cm_layout_make(int m, int cc, int group, int nsv, int nlarge, int blkw, int jobw, long long blocks_len, hs_cm_layout* L)
+{
+   const long long groups = ((long long) cc + group - 1) / group, jobs = (long long) cc * nlarge;
+   L->Yg = 0;
+   L->blks = even(groups * m * group);
+   L->jobs = L->blks + even((long long) nsv * blkw);
+   L->act = L->jobs + even(jobs * jobw);
+   L->res = L->act + even((jobs + 1) / 2);
+   L->lam = L->res + even((long long) cc * nsv + cc);
+   L->blocks = L->lam + 2LL * cc * (nsv - nlarge);
+   L->len.res_off = L->res; L->len.res_len = L->lam - L->res;
+   L->len.upload_len = L->res; L->len.pin_len = L->lam; L->len.dev_len = L->blocks + blocks_len;
+}
+
 hs_ecl_block hs_ecl_block_make(long long ws_len, long long out_len)
 {
    hs_ecl_block B;

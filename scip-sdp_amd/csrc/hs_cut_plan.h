@@ -130,6 +130,25 @@ static inline long long hs_ecl_launches(int maxcuts, int nmax)
    return 2 + ((long long) nmax - 1) + 1 + (maxcuts > 0 ? 2 : 0) + 1;
 }
 
+/* hipsdp_check_y_many (csrc/check_many.hip), ONE CHUNK of cc candidates over nsv served blocks, nlarge of them of 129 .. 512 rows:
+ *    Yg [groups][m][group] (groups = ceil(cc / group): the candidates' points, a group's values of one variable side by side)
+ *    | block table [nsv][blkw] | tridiagonal jobs [cc nlarge][jobw] | act[cc nlarge] (int)
+ *    | res: lmin [cc][nsv], then lpviol [cc]
+ *    | lam [cc][nsv - nlarge][2] (eigenvalue and half width of every matrix of at most 128 rows)
+ *    | blocks: per served block its cc matrices one behind the other (blocks_len doubles in all: the caller lays them out)
+ * every part starts at an even offset.  ONE upload carries everything in front of res, ONE read-back takes res, and the pinned mirror ends
+ * behind it. */
+struct hs_cm_layout { long long Yg, blks, jobs, act, res, lam, blocks; hs_cut_lens len; };
+void hs_cm_layout_make(int m, int cc, int group, int nsv, int nlarge, int blkw, int jobw, long long blocks_len, hs_cm_layout* L);
+/* kernel launches of one chunk of hipsdp_check_y_many: a function of the size classes present (blocks of at most 64 rows, of 65 .. 128,
+ * of 129 .. 512) and of nmax, the chunk's largest block above 128 rows, alone - Z of all blocks and candidates (with a served block);
+ * one launch per class of at most 128 rows; for the third class the clearing of the reflector arrays, nmax - 1 columns and the 3 launches
+ * of the selection; the launch that stores lmin and lpviol */
+static inline long long hs_cm_launches(int any, int small, int mid, int nmax_large)
+{
+   return (any ? 1 : 0) + (small ? 1 : 0) + (mid ? 1 : 0) + (nmax_large > 0 ? (long long) nmax_large + 3 : 0) + 1;
+}
+
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
 {

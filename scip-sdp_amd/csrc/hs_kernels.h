@@ -619,6 +619,30 @@ int hs_ecl_clear(hipStream_t st, int count, const hs_sxm_job* sx);
 int hs_ecl_cuts(hipStream_t st, int count, int nmax, int m, int maxcuts, const hs_ec_job* jobs, const hs_sxm_job* sx, const long long* vecoff,
    const hs_sc_out* out);
 
+/* ---- check_many.hip: feasibility of MANY candidate points per call (hipsdp_check_y_many; host side: cut_calls.hip) ------------------------
+ * A chunk of cc candidates runs in groups of HS_CM_G: Yg[g][i][k] = y_i of candidate g HS_CM_G + k of the chunk (zeros behind the last
+ * candidate), so that a group's values of one variable lie side by side.  Entry b of the two device tables belongs to served block b:
+ * jobs[b] its hs_ec_job (n and the storage form; .Z and .ws are not used), blks[b] where its matrices and eigenvalues go - Z of candidate
+ * c at Z + c zstride (n x n, no pitch), its eigenvalue 1 at lam[c lstride].
+ *   hs_cm_form_z: grid (entry tiles, blocks, groups), ONE launch: Z_b(Y[c]) of every block and candidate, one pass over the block's
+ *                 storage per group; candidate c's Z has the bits hs_ec_form_z gives for Y[c] alone.
+ *   hs_cm_result: grid (cc), ONE launch, the last of a chunk: res[c nblk + b] = eigenvalue 1 of (c, b), and behind those cc nblk values
+ *                 res[cc nblk + c] = max(0, max_r (c_r - (D Y[c])_r)) over the q rows of Dext (q x (m + 1), column 0 = c), 0 with q = 0.
+ * (eigi.hip) hs_lmin_many_small / hs_lmin_many_mid: eigenvalue 1 of the matrices of the blocks of at most 64 / of 65 .. 128 rows. */
+#define HS_CM_G 8
+struct hs_cm_blk { double* Z; long long zstride; double* lam; long long lstride; };
+int hs_cm_form_z(hipStream_t st, int nblk, int nmax, int m, int cc, const hs_ec_job* jobs, const hs_cm_blk* blks, const double* Yg);
+int hs_cm_result(hipStream_t st, int nblk, int cc, int m, int q, const double* Dext, const hs_cm_blk* blks, const double* Yg, double* res);
+int hs_lmin_many_small(hipStream_t st, int nblk, int cc, int nmax, const hs_ec_job* jobs, const hs_cm_blk* blks);
+int hs_lmin_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const hs_ec_job* jobs, const hs_cm_blk* blks);
+/* cut_calls.hip, for the unit entry: hs_cm_form_z alone on a loaded solver - Z of candidate j and block b to Zout + j (n_0^2 + ... +
+ * n_{nb-1}^2) + (n_0^2 + ... + n_{b-1}^2) for every block of at most 512 rows the call serves (served[b] = 0, else -1 and its part is not
+ * written), *launches: the kernel launches issued */
+int hs_check_many_form_z(hipsdp_solver* s, int count, const double* Y, double* Zout, int* served, int* launches);
+/* ipm.hip: the LP rows of a solver - 0 (nothing set) for a solver with a communicator or sharded matrices, else 1, the number of rows and
+ * the device array q x (m + 1) whose column 0 is c */
+int hs_solver_lp_rows(const hipsdp_solver* s, int* q, const double** Dext);
+
 /* ---- syevr.hip: ALL eigenpairs of a matrix of 2 .. 512 rows through the tridiagonal form (stage 1 is hs_syevx_tridiag_dev) --------
  * dA as for hs_syevx_dev.  dOut, HS_SYEVR_OUT(n) doubles: [k] k-th eigenvalue (ascending), [HS_SYEVR_OUT_VEC(n) + k n + i] component
  * i of its unit vector (vectors != 0; otherwise no vector kernel is launched).  ws: hs_syevr_ws(n) doubles, its head is the

@@ -5759,6 +5759,15 @@ int hs_solver_block_n(const hipsdp_solver* s, int block)
    return s->blk[block].n;
 }
 
+int hs_solver_lp_rows(const hipsdp_solver* s, int* q, const double** Dext)
+{
+   if ( s->comm != NULL || s->shardA )
+      return 0;
+   *q = s->q;
+   *Dext = s->Dext;
+   return 1;
+}
+
 /* the whole matrices of the block are on this device */
 static bool ec_has_matrices(const Block& B)
 {

@@ -2078,6 +2078,18 @@ extern "C" int hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long lo
    return HIPSDP_OK;
 }
 
+/* k_cm_form_z alone on a loaded solver (hs_check_many_form_z, csrc/cut_calls.hip: the head of a chunk of hipsdp_check_y_many with every
+ * matrix laid out as a plain n x n array), and the size of its groups */
+extern "C" int hipsdp_form_z_many_unit(hipsdp_solver* solver, int count, const double* Y, double* Z, int* served, int* launches)
+{
+   return hs_check_many_form_z(solver, count, Y, Z, served, launches);
+}
+
+extern "C" int hipsdp_check_many_group(void)
+{
+   return HS_CM_G;
+}
+
 /* the fan-out of hipsdp_solve_objectives alone (hs_objs_fanout, csrc/kernels.hip): the sources in device memory as the engine holds them
  * (the objectives in rows of m rounded up to even), the lanes filled with the guard word, one launch, the lanes back */
 extern "C" int hipsdp_objs_fanout_unit(int device, int count, int m, int q, int nblk, const int* ns, const double* B, const double* b_own,
