@@ -784,6 +784,67 @@ HIPSDP_API int hipsdp_psd_project_many_large(int device, int count, hipsdp_psd_j
 /* process totals: calls with count > 0 that passed the argument checks, kernel launches they issued, device->host synchronisations
  * they waited on (one per chunk); any pointer may be NULL */
 HIPSDP_API int hipsdp_psd_project_many_large_stats(long long* calls, long long* launches, long long* readbacks);
+/* The device work of the PRIMAL ROUNDING PROBLEM of a warm-started node (relax/warmstartproject = 4: solvePrimalRoundingProblem,
+ * relax_sdp.c:1551-2640) in two calls.  The reference decomposes the start matrix X* of every block (:1875-1877), computes for EVERY
+ * eigenvector v_j of a block - all n_b of them - the coefficients of the rounding LP, obj[j] = v_j^T A_0 v_j (:1906-1923) and
+ * val[j][i] = v_j^T A_i v_j (:1926-1947), and recombines V^T diag(lambda) V once for X from the primal rounding LP (:2164-2207) and once
+ * for Z from the dual one (:2550-2591), both on the same eigenvectors.  off_b = n_0 + .. + n_{b-1}, N = sum n_b.
+ * STAGE 1, hipsdp_rounding_frame: X_b as the triplets of expandSparseMatrix (relax_sdp.c:243-277; the convention of hipsdp_psd_project:
+ * both triangles are filled, a position named twice is outside the contract, xnnz[b] = 0 is the zero matrix).  For a served block:
+ *     eigvals[off_b + j]            the eigenvalues of X_b, ascending;
+ *     obj[off_b + j]              = v_j^T A_0^b v_j;
+ *     coefs[(off_b + j) m + i]    = v_j^T A_{i+1}^b v_j - the reference's val[evind * nvars + varind], dense: dropping the SCIPisZero
+ *                                   entries stays with the caller; variables are the engine's, as in hipsdp_eigencuts;
+ *     vecs[sum_{k<b} n_k^2 + j n_b + r] = component r of v_j (vecs may be NULL): the caller builds the -V_iv V_jv rows of the dual
+ *                                   rounding LP (:2353-2375) from it on the host;
+ *     served[b]                   = 0: block b is served; -1: it is not, and none of its slots is written.  served may be NULL.
+ * The eigenvectors stay on the device: the solver's ROUNDING FRAME, a grow-only allocation of N + sum n_b^2 doubles.
+ * Served: blocks of 1 .. 512 rows of a solver without communicator and without sharded matrices, in all three storage forms, all size
+ * classes in one call.  Not served: a block of more than 512 rows or without matrices on this device; the others are still served.  A
+ * solver with a communicator or sharded matrices: every served = -1, nothing launched, HIPSDP_OK.
+ * HIPSDP_ERR_ARG, before the device is looked at and with nothing launched: solver NULL or without a shape; xnnz, eigvals, obj or coefs
+ * NULL; xnnz[b] < 0; a NULL triplet array with xnnz[b] > 0; an index outside the block.
+ * EIGENPAIRS of a served block are, bit for bit, those of hipsdp_syev_small (up to 128 rows) or hipsdp_syevr (129 .. 512 rows) on the
+ * expanded matrix alone; the SCALE RANGE paragraph above applies.  A block of one row is a scalar.
+ * COEFFICIENTS: blocks of more than 64 rows held as packed triangles or dense rows go through a GEMM over the storage index p on
+ * v_mfma_f64_16x16x4_f64 - C[j][i] = sum_p P[j][p] A_i[p], P[j][p] = w_p V[j][r_p] V[j][c_p], w = 1 on the diagonal of a packed triangle
+ * and 2 off it, formed from V while it is staged; tiles of 64 vectors x 64 matrices, p ascending, and for a block with few tiles p in
+ * slices whose number depends on (n_b, m) alone and whose partial tables are added in slice order.  Blocks of at most 64 rows and blocks
+ * kept as nonzeros: one thread per (vector, matrix) sums over the stored entries in storage order (csrc/rounding.hip).
+ * STAGE 2, hipsdp_rounding_recombine, any number of times per frame: R_b = the recombination of the frame's vectors of block b with
+ * lambda[off_b .. off_b + n_b), used as given (nothing is clamped):
+ *     mode 0  R[i][j] = sum_c V[i][c] lambda_c V[j][c], the reference's literal chain (scaleTransposedMatrix +
+ *             SCIPlapackMatrixMatrixMult(V, TRUE, S, FALSE), :2172-2183), mode 0 of hipsdp_psd_project;
+ *     mode 1  R = sum_k lambda_k v_k v_k^T.
+ * Output per block as hipsdp_psd_project_many writes it: the entries with row <= col and |value| > epsilon in row-major order, their
+ * number in nnz_out; a block over its cap gets the needed length in nnz_out and nothing written, the others are written and the call
+ * returns HIPSDP_ERR_ARG; a block the frame does not hold gets nnz_out = -1.  The launches are those of hipsdp_psd_project_many (up to
+ * 128 rows) and hipsdp_psd_project_many_large (above), on jobs that point at the frame.
+ * It needs a frame: HIPSDP_ERR_ARG without one, and for solver, lambda or out NULL, a mode other than 0 / 1, cap < 0, a NULL output
+ * array with cap > 0.  The frame lives from a hipsdp_rounding_frame that returned HIPSDP_OK until the next hipsdp_rounding_frame,
+ * hipsdp_set_shape* or hipsdp_free; it does not depend on the constraint matrices, so writing them does not invalidate it.
+ * LAUNCHES.  The served blocks are taken by descending size in chunks of at most 512 MiB of the solver's cut workspace
+ * (HIPSDP_ROUNDING_CHUNK in the environment, read at every call: blocks per chunk instead); the frame itself is not chunked.  Every chunk
+ * issues one upload and ONE read-back, and with [..] = 1 when the chunk has a block of that class and nmax the rows of its largest block
+ * above 128 rows:
+ *     stage 1:  [1 .. 128 rows] 4 + [129 .. 512 rows] (nmax + 6 + 6 ceil(nmax / 32)) + 4
+ *     stage 2:  [1 .. 128 rows] 2 + [129 .. 512 rows] 2
+ * (stage 1: per class the expand launch and the decomposition - 3 launches up to 128 rows, nmax - 1 columns, 5 + 6 ceil(nmax / 32) for
+ * the values and vectors of the tridiagonal matrices and the back-transformation above; then the move into the frame, the two
+ * coefficient launches and the store) - a function of the classes present and of nmax alone, never of the number of blocks.
+ * The bits of a block depend on its X and its matrices (stage 1), or on its V and lambda (stage 2), alone - not on the other blocks,
+ * their order or the chunks; same input, same bits; no floating-point atomics.  Two host threads may call either function at the same
+ * time on different solvers. */
+HIPSDP_API int hipsdp_rounding_frame(hipsdp_solver* solver,
+   const int* xnnz, const int* const* xrow, const int* const* xcol, const double* const* xval,   /* per block: triplets of X_b */
+   double* eigvals /* N */, double* obj /* N */, double* coefs /* N x m */, double* vecs /* sum n_b^2, may be NULL */,
+   int* served /* nblocks, may be NULL */);
+typedef struct hipsdp_rounding_out { int cap; int nnz_out; int *rowout, *colout; double* valout; } hipsdp_rounding_out;
+HIPSDP_API int hipsdp_rounding_recombine(hipsdp_solver* solver, const double* lambda /* N */, double epsilon, int mode,
+   hipsdp_rounding_out* out /* nblocks */);
+/* process totals of both stages: calls that launched something, kernel launches they issued, device->host synchronisations they
+ * waited on (one per chunk); any pointer may be NULL.  The totals of the other calls do not move, and the reverse */
+HIPSDP_API int hipsdp_rounding_stats(long long* calls, long long* launches, long long* readbacks);
 HIPSDP_API int  hipsdp_gemv_n(int device, int R, long long E, const double* A, int nv, const double* V, double* out);
 HIPSDP_API int  hipsdp_gemv_t(int device, int R, long long E, const double* A, const double* coef, double* out);
 

@@ -213,6 +213,15 @@ HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long l
 HIPSDP_API int  hipsdp_form_z_many_unit(hipsdp_solver* solver, int count, const double* Y, double* Z, int* served, int* launches);
 /* the candidates k_cm_form_z serves per pass over a block's storage (HS_CM_G, a compile-time constant of csrc/hs_kernels.h) */
 HIPSDP_API int  hipsdp_check_many_group(void);
+/* the coefficient launches of hipsdp_rounding_frame (csrc/rounding.hip: k_rf_gather, k_rf_coefs_scalar, k_rf_coefs_mc, k_rf_store) alone
+ * on host data of ONE block, through the routing rule of the call: V (n x n, row j = v_j) and the block's matrices in the form `form` -
+ * 0: dense rows, A = (m + 1) x n^2; 1: packed lower triangles, A = (m + 1) x n (n + 1) / 2, entry (r, c), c <= r, at r (r + 1) / 2 + c;
+ * 2: nonzeros, A = the dense constant matrix (n x n) and the variables' lower-triangular nonzeros as nnz triplets (var 1 .. m, row >= col,
+ * val) sorted by var.  out[j (m + 1) + i] = v_j^T A_i v_j, i = 0: the constant matrix.  *route (may be NULL) = 1: the matrix-core kernel
+ * served the block (more than 64 rows, forms 0 and 1), 0: the scalar one; *slices (may be NULL): the slices of the storage index.
+ * HIPSDP_ERR_ARG: n outside 1 .. 512, m < 0, another form, V, A or out NULL, a triplet outside the lower triangle or out of order. */
+HIPSDP_API int  hipsdp_rounding_coefs_unit(int device, int n, int m, int form, const double* V, const double* A, long long nnz, const int* var,
+   const int* row, const int* col, const double* val, double* out, int* route, int* slices);
 /* the Newton kernel of hipsdp_onevar_bounds (csrc/eigi.hip: k_onevar_small for n <= 64, k_onevar_mid for n <= 128) alone on host
  * matrices: Z (n x n) and, for job j < count, the dense A + j n^2 (n x n), the shift shift[j] (= u_i), kind[j] (NULL: all NEWTON),
  * lb[j], ub[j]: M_j(mu) = Z + (mu - shift[j]) A_j.  infinity is 1e20, maxevals <= 0 means 100.  status, optval, lmin, grad, evals as

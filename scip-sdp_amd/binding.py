@@ -455,6 +455,70 @@ class Solver:
         """process totals (calls, launches, read-backs) of hipsdp_check_y_many in the library this solver lives in"""
         return check_y_many_stats(self._l)
 
+    def rounding_frame(self, X, want_vecs=True, fill=np.nan, raw=False):
+        """stage 1 of the primal rounding problem (hipsdp_rounding_frame): X is a list with one entry per block - a dense symmetric
+        n_b x n_b array (its nonzeros of both triangles become the triplets), a tuple (row, col, val) of triplets, or None (the zero
+        matrix).  Returns (eigvals[N], obj[N], coefs[N, m], vecs[sum n_b^2] or None, served[nblocks]); the slots of a block that is not
+        served keep `fill`.  raw: the status is returned in front instead of raised"""
+        nb, N = len(self.ns), int(sum(self.ns))
+        assert len(X) == nb
+        keep, cnt = [], np.zeros(max(1, nb), dtype=np.int32)
+        rows, cols, vals = (C.POINTER(C.c_int) * max(1, nb))(), (C.POINTER(C.c_int) * max(1, nb))(), (C.POINTER(C.c_double) * max(1, nb))()
+        for b, Xb in enumerate(X):
+            if Xb is None:
+                continue
+            if isinstance(Xb, tuple):
+                r, c, v = Xb
+            else:
+                Xb = np.asarray(Xb, dtype=np.float64)
+                r, c = np.nonzero(Xb)
+                v = Xb[r, c]
+            r, c, v = np.ascontiguousarray(r, dtype=np.int32), np.ascontiguousarray(c, dtype=np.int32), _f64(v)
+            keep.append((r, c, v))
+            cnt[b] = len(v)
+            if len(v):
+                rows[b], cols[b], vals[b] = _ip(r), _ip(c), _dp(v)
+        eig, obj = np.full(max(1, N), fill), np.full(max(1, N), fill)
+        coefs = np.full((max(1, N), max(1, self.m)), fill)
+        vecs = np.full(max(1, sum(n * n for n in self.ns)), fill) if want_vecs else None
+        served = np.full(max(1, nb), -1, dtype=np.int32)
+        rc = self._l().hipsdp_rounding_frame(self.h, _ip(cnt), rows, cols, vals, _dp(eig), _dp(obj), _dp(coefs),
+                                             _dp(vecs) if want_vecs else None, _ip(served))
+        res = (eig[:N], obj[:N], coefs[:N, :self.m], vecs, served[:nb])
+        if raw:
+            return (rc,) + res
+        _chk(rc, "hipsdp_rounding_frame")
+        return res
+
+    def rounding_recombine(self, lam, epsilon=1e-9, mode=0, caps=None, raw=False):
+        """stage 2 (hipsdp_rounding_recombine) on the frame of the last rounding_frame: lam[N]; per block (row, col, val) of the kept
+        upper-triangle entries, None for a block the frame does not hold, or the int needed length for a block over its cap
+        (caps[b]; default n (n + 1) / 2).  raw: (status, list) instead of raising on a status other than 0"""
+        nb = len(self.ns)
+        lam = _f64(lam)
+        assert lam.shape == (int(sum(self.ns)),)
+        tab = (RoundingOut * max(1, nb))()
+        keep = []
+        for b, n in enumerate(self.ns):
+            cap = n * (n + 1) // 2 if caps is None else int(caps[b])
+            ro, co, vo = np.zeros(max(1, cap), dtype=np.int32), np.zeros(max(1, cap), dtype=np.int32), np.zeros(max(1, cap))
+            keep.append((ro, co, vo))
+            tab[b].cap, tab[b].nnz_out = cap, -7
+            tab[b].rowout, tab[b].colout, tab[b].valout = _ip(ro), _ip(co), _dp(vo)
+        rc = self._l().hipsdp_rounding_recombine(self.h, _dp(lam), C.c_double(epsilon), int(mode), tab)
+        out = []
+        for b in range(nb):
+            k = tab[b].nnz_out
+            out.append(None if k < 0 else (k if k > tab[b].cap else (keep[b][0][:k].copy(), keep[b][1][:k].copy(), keep[b][2][:k].copy())))
+        if raw:
+            return rc, out
+        _chk(rc, "hipsdp_rounding_recombine")
+        return out
+
+    def rounding_stats(self):
+        """process totals (calls, launches, read-backs) of both rounding stages in the library this solver lives in"""
+        return rounding_stats(self._l)
+
     def form_z_many_unit(self, Y):
         """k_cm_form_z alone (hipsdp_form_z_many_unit; the solver must have been created with units=True): Y is count x m; returns
         ([per block b: Z[count, n_b, n_b] or None for a block that is not served], launches)"""
@@ -897,6 +961,51 @@ def check_y_many_stats(which=None):
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk((which or lib)().hipsdp_check_y_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_check_y_many_stats")
     return calls.value, launches.value, readbacks.value
+
+
+class RoundingOut(C.Structure):
+    """hipsdp_rounding_out of include/hipsdp.h, field for field"""
+    _fields_ = [("cap", C.c_int), ("nnz_out", C.c_int), ("rowout", C.POINTER(C.c_int)), ("colout", C.POINTER(C.c_int)),
+                ("valout", C.POINTER(C.c_double))]
+
+
+def rounding_stats(which=None):
+    """process totals of hipsdp_rounding_frame and hipsdp_rounding_recombine together: (calls that launched something, kernel launches
+    issued, device->host synchronisations); which: lib (default) or ulib"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk((which or lib)().hipsdp_rounding_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_rounding_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def rounding_coefs_unit(V, A, form, nonzeros=None, device=0):
+    """the coefficient launches of hipsdp_rounding_frame alone (hipsdp_rounding_coefs_unit of the units library) on one block: V (n x n,
+    row j = v_j); form 0: A = [m + 1, n, n] dense; form 1: the same dense input, packed here into lower triangles; form 2: A = the
+    dense constant matrix [n, n] and nonzeros = (m, var 1 .. m, row, col <= row, val).
+    Returns (table[n, m + 1], route, slices)"""
+    V = _f64(V)
+    n = V.shape[0]
+    A = np.asarray(A, dtype=np.float64)
+    var = row = col = val = None
+    nnz = 0
+    if form == 2:
+        m, mats = nonzeros[0], _f64(A.reshape(n, n))
+        var, row, col, val = [np.asarray(x) for x in nonzeros[1:]]
+        order = np.argsort(var, kind="stable")
+        var, row, col = [np.ascontiguousarray(x[order], dtype=np.int32) for x in (var, row, col)]
+        val = _f64(val[order])
+        nnz = len(val)
+    else:
+        m = A.shape[0] - 1
+        il = np.tril_indices(n)
+        mats = _f64(A.reshape(m + 1, n * n) if form == 0 else np.stack([A[i][il] for i in range(m + 1)]))
+    out = np.full((n, m + 1), np.nan)
+    route, slices = C.c_int(-1), C.c_int(-1)
+    rc = ulib().hipsdp_rounding_coefs_unit(device, n, int(m), int(form), _dp(V), _dp(mats), C.c_longlong(nnz),
+                                           _ip(var) if nnz else None, _ip(row) if nnz else None, _ip(col) if nnz else None,
+                                           _dp(val) if nnz else None, _dp(out), C.byref(route), C.byref(slices))
+    if rc != 0:
+        raise RuntimeError("hipsdp_rounding_coefs_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    return out, route.value, slices.value
 
 
 def check_many_group():

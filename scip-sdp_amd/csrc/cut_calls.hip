@@ -3,7 +3,8 @@
  * (sparsecuts.hip, sparsecuts_large.hip), their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip), and
  * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip),
  * and hipsdp_eigencuts_all_large, the partner of hipsdp_eigencuts_all for those blocks (eigcuts_large.hip).  At the end of the file:
- * hipsdp_check_y_many, the feasibility check of many candidate points per call (check_many.hip).
+ * hipsdp_check_y_many, the feasibility check of many candidate points per call (check_many.hip), and hipsdp_rounding_frame /
+ * hipsdp_rounding_recombine, the two device stages of the primal rounding problem (rounding.hip; planning: hs_round_plan.h).
  *
  * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
  * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
@@ -12,6 +13,7 @@
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_cut_plan.h"
+#include "hs_round_plan.h"
 #include "hs_chunks.h"
 #include "hs_cut_stats.h"
 #include "../../include/hipsdp.h"
@@ -1121,4 +1123,414 @@ extern "C" int hipsdp_check_y_many(hipsdp_solver* s, int count, const double* Y,
 extern "C" int hipsdp_check_y_many_stats(long long* calls, long long* launches, long long* readbacks)
 {
    return g_cm.get(calls, launches, readbacks);
+}
+
+namespace {
+
+/* ---- hipsdp_rounding_frame / hipsdp_rounding_recombine: the two device stages of the primal rounding problem (kernels: rounding.hip, the
+ * expand, recombine and write launches of psd_many.hip / psd_large.hip, the batched decompositions of eigi.hip, syevx.hip, syevr.hip;
+ * planning: hs_round_plan.h) ------------------------------------------------------------------------------------------------------------ */
+CutStats g_rf;
+
+static_assert(sizeof(hs_rf_job) % 8 == 0 && sizeof(hs_pp_job) % 8 == 0 && sizeof(hs_eig_job) % 8 == 0 && sizeof(hs_ppl_job) % 8 == 0
+   && sizeof(hs_sxm_job) % 8 == 0 && sizeof(hs_srm_job) % 8 == 0, "hs_rf_layout: rows of the tables are whole doubles");
+const hs_rf_widths RF_W = {(int) (sizeof(hs_rf_job) / 8), (int) (sizeof(hs_pp_job) / 8), (int) (sizeof(hs_eig_job) / 8),
+   (int) (sizeof(hs_ppl_job) / 8), (int) (sizeof(hs_sxm_job) / 8), (int) (sizeof(hs_srm_job) / 8)};
+
+long long rf_small_scratch(int n) { return hs_syev_small_scratch(n); }
+long long rf_large_ws(int n) { return (long long) hs_syevr_ws(n); }
+long long rf_large_out(int n) { return HS_SYEVR_OUT(n); }
+const hs_rf_rules RF_RULES = {rf_small_scratch, rf_large_ws, rf_large_out};
+
+/* off[b] = n_0 + .. + n_{b-1}, voff[b] = n_0^2 + .. + n_{b-1}^2 ([nb]: the totals) */
+void rf_offsets(const hipsdp_solver* s, int nb, std::vector<long long>* off, std::vector<long long>* voff)
+{
+   off->assign((size_t) nb + 1, 0);
+   voff->assign((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+   {
+      const long long n = hs_solver_block_n(s, b);
+      (*off)[b + 1] = (*off)[b] + n;
+      (*voff)[b + 1] = (*voff)[b] + n * n;
+   }
+}
+
+/* the caller's arrays of hipsdp_rounding_frame */
+struct RfArgs
+{
+   const int* xnnz; const int* const* xrow; const int* const* xcol; const double* const* xval;
+   double *eigvals, *obj, *coefs, *vecs;
+};
+
+/* ONE CHUNK of stage 1: the served blocks items[start .. end), largest first - ONE upload (tables and triplets), hs_rf_launches(..)
+ * launches whatever the number of blocks, ONE read-back, the copy-out */
+int rf_chunk(hipsdp_solver* s, int m, const std::vector<hs_rf_item>& items, int start, int end, const RfArgs& a, const hs_round_frame& F,
+   const std::vector<long long>& off, const std::vector<long long>& voff)
+{
+   const int cnt = end - start, nb = (int) off.size() - 1;
+   int nlarge = 0;
+   while ( nlarge < cnt && items[(size_t) start + nlarge].n > HS_RF_SMALLN )
+      ++nlarge;
+   const int nsmall = cnt - nlarge;
+   std::vector<int> ids((size_t) cnt);
+   std::vector<hs_rf_block> blk((size_t) cnt);
+   std::vector<long long> at((size_t) cnt), row0((size_t) cnt), vec0((size_t) cnt), trip0((size_t) cnt);
+   long long blocks_len = 0, rows = 0, vec_len = 0, trips = 0, tiles = 1;
+   int nmax = 0;
+   for (int k = 0; k < cnt; ++k)
+   {
+      const hs_rf_item& it = items[(size_t) start + k];
+      ids[k] = it.blk;
+      blk[k] = hs_rf_block_make(it.n, m, it.route, it.slices, &RF_RULES);
+      at[k] = blocks_len; row0[k] = rows; vec0[k] = vec_len; trip0[k] = trips;
+      blocks_len += blk[k].len;
+      rows += it.n;
+      vec_len += a.vecs != NULL ? (long long) it.n * it.n : 0;
+      trips += it.nnz;
+      nmax = it.n > nmax ? it.n : nmax;
+      if ( it.route )
+         tiles = std::max(tiles, hs_rf_tiles(it.n, m, it.slices));
+   }
+   hs_rf_layout L;
+   hs_rf_layout_make(m, cnt, nsmall, nlarge, trips, rows, vec_len, &RF_W, blocks_len, &L);
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_blocks(s, ids, std::vector<long long>((size_t) cnt, 0), L.len.dev_len, L.len.pin_len, &w) );
+   hs_rf_job* hrf = reinterpret_cast<hs_rf_job*>(w.pin + L.rf);
+   hs_pp_job* hpp = reinterpret_cast<hs_pp_job*>(w.pin + L.pp);
+   hs_eig_job* heig = reinterpret_cast<hs_eig_job*>(w.pin + L.eig);
+   hs_ppl_job* hppl = reinterpret_cast<hs_ppl_job*>(w.pin + L.ppl);
+   hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.sx);
+   hs_srm_job* hsr = reinterpret_cast<hs_srm_job*>(w.pin + L.sr);
+   int* hact = reinterpret_cast<int*>(w.pin + L.act);
+   double* hval = w.pin + L.val;
+   int* hrow = reinterpret_cast<int*>(w.pin + L.row);
+   int* hcol = reinterpret_cast<int*>(w.pin + L.col);
+   const long long N = off[nb];
+   for (int k = 0; k < cnt; ++k)
+   {
+      const hs_rf_item& it = items[(size_t) start + k];
+      const int n = it.n, b = it.blk;
+      double* base = w.dev + L.blocks + at[k];
+      hs_rf_job& J = hrf[k];
+      memset(&J, 0, sizeof(J));
+      J.n = n; J.route = it.route; J.slices = it.slices; J.pps = it.pps; J.klen = it.klen;
+      J.lam = F.dev + off[b]; J.V = F.dev + N + voff[b];
+      J.VT = it.route == 0 ? base + blk[k].VT : NULL;
+      J.part = base + blk[k].part;
+      J.row0 = row0[k]; J.vec0 = vec0[k];
+      if ( k < nlarge )
+      {
+         HS_CALL( hs_syevx_many_job(n, base + blk[k].ws, base + blk[k].out, &hsx[k]) );      /* (its selection output is not used) */
+         HS_CALL( hs_syevr_many_job(n, base + blk[k].ws, base + blk[k].out, &hsr[k]) );
+         if ( hsx[k].A != base + blk[k].ws )
+            return HIPSDP_ERR_NUMERIC;
+         hact[k] = HS_SXM_ACTIVE;
+         hs_ppl_job& T = hppl[k];
+         memset(&T, 0, sizeof(T));
+         T.n = n; T.nnz = (int) it.nnz; T.ntc = (n + HS_RF_TILE - 1) / HS_RF_TILE; T.trip = trip0[k];
+         T.A = hsx[k].A; T.R = hsx[k].R;
+         J.lam_src = base + blk[k].out; J.V_src = base + blk[k].out + HS_SYEVR_OUT_VEC(n);
+      }
+      else
+      {
+         /* the decompositions want their table ordered by class: the small blocks of the chunk, which descend in n, backwards */
+         const int t = cnt - 1 - k;
+         hs_pp_job& T = hpp[t];
+         memset(&T, 0, sizeof(T));
+         T.n = n; T.nnz = (int) it.nnz; T.trip = trip0[k]; T.A = base + blk[k].mat;
+         memset(&heig[t], 0, sizeof(hs_eig_job));
+         heig[t].n = n; heig[t].in = base + blk[k].mat; heig[t].ws = base + blk[k].ws;
+         J.lam_src = base + blk[k].ws; J.V_src = base + blk[k].ws + hs_syev_many_vecpos(n);
+      }
+      if ( it.nnz > 0 )
+      {
+         memcpy(hval + trip0[k], a.xval[b], (size_t) it.nnz * sizeof(double));
+         memcpy(hrow + trip0[k], a.xrow[b], (size_t) it.nnz * sizeof(int));
+         memcpy(hcol + trip0[k], a.xcol[b], (size_t) it.nnz * sizeof(int));
+      }
+   }
+   hipStream_t st = w.stream;
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   const hs_rf_job* drf = reinterpret_cast<const hs_rf_job*>(w.dev + L.rf);
+   const int* drow = reinterpret_cast<const int*>(w.dev + L.row);
+   const int* dcol = reinterpret_cast<const int*>(w.dev + L.col);
+   int launches = 0;
+   if ( nsmall > 0 )
+   {
+      HS_CALL( hs_pp_expand(st, nsmall, reinterpret_cast<const hs_pp_job*>(w.dev + L.pp), drow, dcol, w.dev + L.val) );
+      ++launches;
+      HS_CALL( scx_syev(st, nsmall, heig, reinterpret_cast<const hs_eig_job*>(w.dev + L.eig), &launches) );
+   }
+   if ( nlarge > 0 )
+   {
+      const int nml = items[(size_t) start].n;
+      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.sx);
+      const hs_srm_job* dsr = reinterpret_cast<const hs_srm_job*>(w.dev + L.sr);
+      HS_CALL( hs_ppl_expand(st, nlarge, reinterpret_cast<const hs_ppl_job*>(w.dev + L.ppl), drow, dcol, w.dev + L.val) );
+      HS_CALL( hs_syevx_many_cols(st, nlarge, nml, hs_syevx_many_cap(nlarge), dsx, reinterpret_cast<const int*>(w.dev + L.act)) );
+      HS_CALL( hs_syevr_many_tvec(st, nlarge, nml, dsr) );
+      HS_CALL( hs_syevr_many_back(st, nlarge, nml, dsr) );
+      launches += 1 + (nml - 1) + 5 + 6 * ((nml + 31) / 32) + 1;
+   }
+   HS_CALL( hs_rf_gather(st, cnt, drf) );
+   HS_CALL( hs_rf_coefs_scalar(st, cnt, nmax, m, w.djobs, drf) );
+   HS_CALL( hs_rf_coefs_mc(st, cnt, tiles, m, w.djobs, drf) );
+   HS_CALL( hs_rf_store(st, cnt, m, drf, w.dev + L.r_eig, w.dev + L.r_obj, w.dev + L.r_coef, a.vecs != NULL ? w.dev + L.r_vec : NULL) );
+   launches += 4;
+   if ( launches != hs_rf_launches(nsmall > 0, nlarge > 0 ? items[(size_t) start].n : 0) )
+      return HIPSDP_ERR_NUMERIC;
+   hs_cut_res none;
+   memset(&none, 0, sizeof(none));
+   none.ints = none.sup = -1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, none, L.len, launches, &g_rf, &h) );
+   for (int k = 0; k < cnt; ++k)
+   {
+      const hs_rf_item& it = items[(size_t) start + k];
+      const size_t n = (size_t) it.n, o = (size_t) off[it.blk];
+      memcpy(a.eigvals + o, w.pin + L.r_eig + row0[k], n * sizeof(double));
+      memcpy(a.obj + o, w.pin + L.r_obj + row0[k], n * sizeof(double));
+      if ( m > 0 )
+         memcpy(a.coefs + o * m, w.pin + L.r_coef + row0[k] * m, n * m * sizeof(double));
+      if ( a.vecs != NULL )
+         memcpy(a.vecs + voff[it.blk], w.pin + L.r_vec + vec0[k], n * n * sizeof(double));
+   }
+   return HIPSDP_OK;
+}
+
+int rounding_frame_impl(hipsdp_solver* s, const RfArgs& a, int* served)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || a.xnnz == NULL || a.eigvals == NULL || a.obj == NULL || a.coefs == NULL )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+   {
+      const int n = hs_solver_block_n(s, b);
+      if ( a.xnnz[b] < 0 )
+         return HIPSDP_ERR_ARG;
+      if ( a.xnnz[b] == 0 )
+         continue;
+      if ( a.xrow == NULL || a.xcol == NULL || a.xval == NULL || a.xrow[b] == NULL || a.xcol[b] == NULL || a.xval[b] == NULL )
+         return HIPSDP_ERR_ARG;
+      for (int e = 0; e < a.xnnz[b]; ++e)
+         if ( a.xrow[b][e] < 0 || a.xrow[b][e] >= n || a.xcol[b][e] < 0 || a.xcol[b][e] >= n )
+            return HIPSDP_ERR_ARG;
+   }
+   hs_round_frame* F = NULL;
+   HS_CALL( hs_solver_round_frame(s, 0, &F) );
+   F->valid = 0;
+   F->served.assign((size_t) nb, -1);
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = -1;
+   std::vector<int> all;
+   HS_CALL( hs_solver_cut_enter_large(s, HS_RF_MAXN, &all) );
+   std::vector<int> ns((size_t) nb), ok((size_t) nb, 0), form((size_t) nb, 0);
+   for (int b = 0; b < nb; ++b)
+      ns[b] = hs_solver_block_n(s, b);
+   for (int b : all)
+   {
+      ok[b] = 1;
+      form[b] = hs_solver_block_form(s, b);
+   }
+   std::vector<hs_rf_item> items;
+   hs_rf_items(nb, m, ns.data(), ok.data(), form.data(), a.xnnz, a.vecs != NULL, &RF_RULES, &items);
+   if ( items.empty() )
+   {
+      F->valid = 1;                    /* (a frame that holds no block: stage 2 serves none) */
+      return HIPSDP_OK;
+   }
+   std::vector<long long> off, voff;
+   rf_offsets(s, nb, &off, &voff);
+   HS_CALL( hs_solver_round_frame(s, off[nb] + voff[nb], &F) );
+   std::vector<long long> len(items.size());
+   for (size_t k = 0; k < items.size(); ++k)
+      len[k] = items[k].len;
+   HS_CALL( hs_chunks_run(len.data(), (int) items.size(), SCLR_BUDGET, hs_chunk_env("HIPSDP_ROUNDING_CHUNK"), [&](int start, int end)
+      { return rf_chunk(s, m, items, start, end, a, *F, off, voff); }) );
+   for (const hs_rf_item& it : items)
+   {
+      F->served[it.blk] = 0;
+      if ( served != NULL )
+         served[it.blk] = 0;
+   }
+   F->valid = 1;
+   ++g_rf.calls;
+   return HIPSDP_OK;
+}
+
+/* a served block of stage 2 in the order of its chunks */
+struct Rf2Item { int blk, n, cap; };
+
+/* ONE CHUNK of stage 2: ONE upload (lambda and the two job tables), hs_rf2_launches(..) launches, ONE read-back, the copy-out */
+int rf2_chunk(hipsdp_solver* s, const std::vector<Rf2Item>& items, int start, int end, const double* lambda, double epsilon, int mode,
+   hipsdp_rounding_out* out, const hs_round_frame& F, const std::vector<long long>& off, const std::vector<long long>& voff, bool* overflow)
+{
+   const int cnt = end - start, nb = (int) off.size() - 1;
+   int nlarge = 0;
+   while ( nlarge < cnt && items[(size_t) start + nlarge].n > HS_RF_SMALLN )
+      ++nlarge;
+   const int nsmall = cnt - nlarge;
+   std::vector<long long> row0((size_t) cnt), int0((size_t) cnt), mat0((size_t) cnt);
+   long long rows = 0, cap_small = 0, cap_large = 0, ints_len = 0, mats_len = 0;
+   int nmax_small = 0;
+   for (int k = 0; k < cnt; ++k)
+   {
+      const Rf2Item& it = items[(size_t) start + k];
+      const long long full = (long long) it.n * (it.n + 1) / 2, res = it.cap < full ? it.cap : full;
+      const long long tc = (it.n + HS_RF_TILE - 1) / HS_RF_TILE;
+      row0[k] = rows; int0[k] = ints_len; mat0[k] = mats_len;
+      rows += it.n;
+      mats_len += hs_cut_mat_len(it.n);
+      if ( k < nlarge )
+      {
+         cap_large += res;
+         ints_len += (it.n * tc + tc * tc + 1) & ~1LL;
+      }
+      else
+      {
+         cap_small += res;
+         ints_len += ((long long) it.n + 2) & ~1LL;
+         nmax_small = it.n > nmax_small ? it.n : nmax_small;
+      }
+   }
+   hs_rf2_layout L;
+   hs_rf2_layout_make(nsmall, nlarge, rows, cap_small, cap_large, &RF_W, ints_len, mats_len, &L);
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_plain(s, L.len.dev_len, L.len.pin_len, &w) );
+   hs_pp_job* hpp = reinterpret_cast<hs_pp_job*>(w.pin + L.pp);
+   hs_ppl_job* hppl = reinterpret_cast<hs_ppl_job*>(w.pin + L.ppl);
+   int* dints = reinterpret_cast<int*>(w.dev + L.ints);
+   const long long N = off[nb];
+   for (int k = 0; k < cnt; ++k)
+   {
+      const Rf2Item& it = items[(size_t) start + k];
+      memcpy(w.pin + L.lam + row0[k], lambda + off[it.blk], (size_t) it.n * sizeof(double));
+      if ( k < nlarge )
+      {
+         hs_ppl_job& T = hppl[k];
+         memset(&T, 0, sizeof(T));
+         T.n = it.n; T.cap = it.cap; T.ntc = (it.n + HS_RF_TILE - 1) / HS_RF_TILE;
+         T.A = w.dev + L.mats + mat0[k]; T.lam = w.dev + L.lam + row0[k]; T.V = F.dev + N + voff[it.blk];
+         T.minev = -HUGE_VAL; T.cnt = dints + int0[k];
+      }
+      else
+      {
+         hs_pp_job& T = hpp[k - nlarge];
+         memset(&T, 0, sizeof(T));
+         T.n = it.n; T.cap = it.cap;
+         T.A = w.dev + L.mats + mat0[k]; T.lam = w.dev + L.lam + row0[k]; T.V = F.dev + N + voff[it.blk];
+         T.minev = -HUGE_VAL; T.rowoff = dints + int0[k];
+      }
+   }
+   hipStream_t st = w.stream;
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   int launches = 0;
+   if ( nsmall > 0 )
+   {
+      const hs_pp_job* dpp = reinterpret_cast<const hs_pp_job*>(w.dev + L.pp);
+      int* dtot = reinterpret_cast<int*>(w.dev + L.tot);
+      HS_CALL( hs_pp_recombine(st, nsmall, nmax_small, dpp, epsilon, mode, dtot) );
+      HS_CALL( hs_pp_write(st, nsmall, nmax_small, dpp, dtot, epsilon, cap_small, reinterpret_cast<int*>(w.dev + L.t_small),
+            reinterpret_cast<int*>(w.dev + L.r_small), reinterpret_cast<int*>(w.dev + L.c_small), w.dev + L.v_small) );
+      launches += 2;
+   }
+   if ( nlarge > 0 )
+   {
+      const hs_ppl_job* dppl = reinterpret_cast<const hs_ppl_job*>(w.dev + L.ppl);
+      const int nml = items[(size_t) start].n;
+      HS_CALL( hs_ppl_recombine(st, nlarge, nml, dppl, epsilon, mode) );
+      HS_CALL( hs_ppl_write(st, nlarge, nml, dppl, epsilon, cap_large, reinterpret_cast<int*>(w.dev + L.t_large),
+            reinterpret_cast<int*>(w.dev + L.r_large), reinterpret_cast<int*>(w.dev + L.c_large), w.dev + L.v_large) );
+      launches += 2;
+   }
+   if ( launches != hs_rf2_launches(nsmall > 0, nlarge > 0) )
+      return HIPSDP_ERR_NUMERIC;
+   hs_cut_res none;
+   memset(&none, 0, sizeof(none));
+   none.ints = none.sup = -1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, none, L.len, launches, &g_rf, &h) );
+   for (int cls = 0; cls < 2; ++cls)
+   {
+      const int k0 = cls == 0 ? 0 : nlarge, k1 = cls == 0 ? nlarge : cnt;
+      const int* tot = reinterpret_cast<const int*>(w.pin + (cls == 0 ? L.t_large : L.t_small));
+      const double* val = w.pin + (cls == 0 ? L.v_large : L.v_small);
+      const int* row = reinterpret_cast<const int*>(w.pin + (cls == 0 ? L.r_large : L.r_small));
+      const int* col = reinterpret_cast<const int*>(w.pin + (cls == 0 ? L.c_large : L.c_small));
+      const long long room = cls == 0 ? cap_large : cap_small;
+      long long pos = 0;
+      for (int k = k0; k < k1; ++k)
+      {
+         hipsdp_rounding_out& O = out[items[(size_t) start + k].blk];
+         const int t = tot[k - k0];
+         O.nnz_out = t;
+         if ( t > O.cap )
+         {
+            *overflow = true;
+            continue;
+         }
+         if ( t < 0 || pos + t > room )
+            return HIPSDP_ERR_NUMERIC;
+         if ( t > 0 )
+         {
+            memcpy(O.valout, val + pos, (size_t) t * sizeof(double));
+            memcpy(O.rowout, row + pos, (size_t) t * sizeof(int));
+            memcpy(O.colout, col + pos, (size_t) t * sizeof(int));
+         }
+         pos += t;
+      }
+   }
+   return HIPSDP_OK;
+}
+
+int rounding_recombine_impl(hipsdp_solver* s, const double* lambda, double epsilon, int mode, hipsdp_rounding_out* out)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || lambda == NULL || out == NULL || mode < 0 || mode > 1 )
+      return HIPSDP_ERR_ARG;
+   for (int b = 0; b < nb; ++b)
+      if ( out[b].cap < 0 || (out[b].cap > 0 && (out[b].rowout == NULL || out[b].colout == NULL || out[b].valout == NULL)) )
+         return HIPSDP_ERR_ARG;
+   hs_round_frame* F = NULL;
+   HS_CALL( hs_solver_round_frame(s, 0, &F) );
+   if ( !F->valid || (int) F->served.size() != nb )
+      return HIPSDP_ERR_ARG;
+   std::vector<Rf2Item> items;
+   for (int b = 0; b < nb; ++b)
+   {
+      out[b].nnz_out = -1;
+      if ( F->served[b] == 0 )
+         items.push_back(Rf2Item{b, hs_solver_block_n(s, b), out[b].cap});
+   }
+   if ( items.empty() )
+      return HIPSDP_OK;
+   std::stable_sort(items.begin(), items.end(), [](const Rf2Item& x, const Rf2Item& y) { return x.n > y.n; });
+   std::vector<long long> off, voff, len(items.size());
+   rf_offsets(s, nb, &off, &voff);
+   for (size_t k = 0; k < items.size(); ++k)
+      len[k] = hs_rf2_item_len(items[k].n, items[k].cap);
+   bool overflow = false;
+   HS_CALL( hs_chunks_run(len.data(), (int) items.size(), SCLR_BUDGET, hs_chunk_env("HIPSDP_ROUNDING_CHUNK"), [&](int start, int end)
+      { return rf2_chunk(s, items, start, end, lambda, epsilon, mode, out, *F, off, voff, &overflow); }) );
+   ++g_rf.calls;
+   return overflow ? HIPSDP_ERR_ARG : HIPSDP_OK;
+}
+
+}
+
+extern "C" int hipsdp_rounding_frame(hipsdp_solver* s, const int* xnnz, const int* const* xrow, const int* const* xcol,
+   const double* const* xval, double* eigvals, double* obj, double* coefs, double* vecs, int* served)
+{
+   return rounding_frame_impl(s, RfArgs{xnnz, xrow, xcol, xval, eigvals, obj, coefs, vecs}, served);
+}
+
+extern "C" int hipsdp_rounding_recombine(hipsdp_solver* s, const double* lambda, double epsilon, int mode, hipsdp_rounding_out* out)
+{
+   return rounding_recombine_impl(s, lambda, epsilon, mode, out);
+}
+
+extern "C" int hipsdp_rounding_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_rf.get(calls, launches, readbacks);
 }

@@ -7,6 +7,7 @@
 #define HS_EC_SWEEP_H
 
 #include "hs_kernels.h"
+#include "hs_round_plan.h"     /* hs_rf_weight: the weight of a stored entry, shared with rounding.hip */
 
 #define EC_NT 256
 #define EC_CH 8            /* cuts swept together (accumulators in registers); more cuts of a block: further sweeps out of L2 */
@@ -39,7 +40,7 @@ __device__ __forceinline__ void ec_sweep(const hs_ec_job& job, int i, int n, int
          while ( r * (r + 1) / 2 > p ) --r;
          while ( (r + 1) * (r + 2) / 2 <= p ) ++r;
          const int c = p - r * (r + 1) / 2;
-         const double av = (r == c ? 1.0 : 2.0) * a[p];
+         const double av = hs_rf_weight(r, c) * a[p];
 #pragma unroll
          for (int u = 0; u < EC_CH; ++u)
             if ( c0 + u < k )
@@ -52,7 +53,7 @@ __device__ __forceinline__ void ec_sweep(const hs_ec_job& job, int i, int n, int
       for (int e = job.sp.voff[i - 1] + tid; e < job.sp.voff[i]; e += EC_NT)
       {
          const int r = job.sp.vrow[e], c = job.sp.vcol[e];
-         const double av = (r == c ? 1.0 : 2.0) * job.sp.vval[e];
+         const double av = hs_rf_weight(r, c) * job.sp.vval[e];
 #pragma unroll
          for (int u = 0; u < EC_CH; ++u)
             if ( c0 + u < k )

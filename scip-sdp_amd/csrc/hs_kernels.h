@@ -668,6 +668,87 @@ int hs_syevr_many_back(hipStream_t st, int count, int nmax, const hs_srm_job* dj
  * matrices of 129 .. 512 rows through the calling thread's context of hipsdp_psd_project_many_large; lam and V one matrix behind the other */
 int hs_ppl_syevr_many_host(int device, int count, const int* n, const double* A, int cap, double* lam, double* V);
 
+/* ---- psd_many.hip / psd_large.hip: the expand, recombine and packed-write launches of hipsdp_psd_project_many[_large] over a job table in
+ * device memory - shared with hipsdp_rounding_frame (the expand launches) and hipsdp_rounding_recombine (the other two, on jobs that
+ * point at a solver's rounding frame and at the caller's lambda; minev = -infinity raises no eigenvalue).  nmax: the largest n of the
+ * table.  hs_pp_*: jobs of at most 128 rows, one workgroup per job; hs_ppl_*: jobs of 129 .. 512 rows. */
+struct hs_pp_job
+{
+   int n, nnz, cap, pad;
+   long long trip;             /* first triplet of the job in the packed arrays */
+   double* A;                  /* n x n slab: the matrix, later the upper triangle of the result */
+   const double* lam;          /* the decomposition: eigenvalues ascending, row k of V = k-th eigenvector */
+   const double* V;
+   double minev;
+   int* rowoff;                /* n + 1: where the rows start inside the job's result */
+};
+int hs_pp_expand(hipStream_t st, int count, const hs_pp_job* djobs, const int* row, const int* col, const double* val);
+int hs_pp_recombine(hipStream_t st, int count, int nmax, const hs_pp_job* djobs, double eps, int mode, int* dtot);
+int hs_pp_write(hipStream_t st, int count, int nmax, const hs_pp_job* djobs, const int* dtot, double eps, long long outlen, int* htot,
+   int* orow, int* ocol, double* oval);
+struct hs_ppl_job
+{
+   int n, nnz, cap, ntc;
+   long long trip;             /* first triplet of the job in the packed arrays */
+   double* A;                  /* n x n, no pitch: the matrix (head of the decomposition's workspace), later the upper triangle of the result */
+   double* R;                  /* n x n: the reflector array of the tridiagonalisation */
+   const double* lam;          /* the decomposition: eigenvalues ascending, row k of V = k-th eigenvector */
+   const double* V;
+   double minev;
+   int* cnt;                   /* [i ntc + q]: kept entries of row i inside tile column q >= i / 64; from n ntc on [ti ntc + tj]: tile totals */
+};
+int hs_ppl_expand(hipStream_t st, int count, const hs_ppl_job* djobs, const int* row, const int* col, const double* val);
+int hs_ppl_recombine(hipStream_t st, int count, int nmax, const hs_ppl_job* djobs, double eps, int mode);
+int hs_ppl_write(hipStream_t st, int count, int nmax, const hs_ppl_job* djobs, double eps, long long outlen, int* tot, int* orow, int* ocol,
+   double* oval);
+
+/* ---- rounding.hip: the coefficient table of ALL eigenvectors of every served block (hipsdp_rounding_frame; host side: cut_calls.hip) --------
+ * Entry k of the two device tables belongs to served block k of a chunk: ejobs[k] its hs_ec_job (n, storage form, matrices; .Z and .ws
+ * are not used), jobs[k] where its pairs come from and go to:
+ *   hs_rf_gather        grid (32, count), ONE launch: eigenvalues and vectors from where the decomposition left them into the solver's
+ *                       frame (lam, V: row j = v_j), and for a block of the scalar route the transposed copy VT[r n + j] = v_j[r]
+ *   hs_rf_coefs_scalar  ONE launch: blocks with route 0 (at most 64 rows, or kept as nonzeros) - thread j owns v_j for matrix i and sums
+ *                       over the entries of A_i in storage order, weights hs_rf_weight; no reduction across threads
+ *   hs_rf_coefs_mc      ONE launch: blocks with route 1 on v_mfma_f64_16x16x4_f64 - tiles of 64 vectors x 64 matrices over the storage
+ *                       index in ascending order, `slices` slices of pps panels each (hs_round_plan.h)
+ *                       both write part[(s n + j) (m + 1) + i], i = 0: the constant matrix
+ *   hs_rf_store         grid (32, count), ONE launch: eig, obj, coef (the slices added in slice order) and, with vec != NULL, the vectors
+ *                       into the chunk's result arrays, rows row0 .. row0 + n - 1 of the block, its vectors from vec0 on
+ * nmax, the largest block of the table, and tiles, the most workgroups a block of the matrix-core route has (hs_rf_tiles of
+ * hs_round_plan.h; 1 without such a block), size the grids; a block of the other route leaves at once. */
+struct hs_rf_job
+{
+   int n, route, slices, pad;
+   long long pps, klen;                /* panels per slice; entries of a stored matrix (matrix-core route) */
+   const double* lam_src; const double* V_src;
+   double* lam; double* V;             /* the frame */
+   double* VT;                         /* scalar route: n x n */
+   double* part;                       /* slices x n x (m + 1) */
+   long long row0, vec0;
+};
+int hs_rf_gather(hipStream_t st, int count, const hs_rf_job* jobs);
+int hs_rf_coefs_scalar(hipStream_t st, int count, int nmax, int m, const hs_ec_job* ejobs, const hs_rf_job* jobs);
+int hs_rf_coefs_mc(hipStream_t st, int count, long long tiles, int m, const hs_ec_job* ejobs, const hs_rf_job* jobs);
+int hs_rf_store(hipStream_t st, int count, int m, const hs_rf_job* jobs, double* eig, double* obj, double* coef, double* vec);
+/* the three coefficient launches alone (gather, scalar, matrix cores) and a copy of the summed table, for the unit entry
+ * hipsdp_rounding_coefs_unit (units.hip): host V (n x n, row j = v_j) and host matrices of ONE block in the form `form` (HS_EC_DENSE:
+ * (m + 1) x n^2; HS_EC_PACKED: (m + 1) x n (n + 1) / 2; HS_EC_SPARSE: A = the dense constant matrix, the variables' lower-triangular
+ * nonzeros as nnz triplets (var 1 .. m, row >= col, val) sorted by variable), through the routing rule of the call; out: n x (m + 1),
+ * out[j (m + 1) + i] = v_j^T A_i v_j; *route, *slices: what the rule chose */
+int hs_rf_coefs_host(int device, int n, int m, int form, const double* V, const double* A, long long nnz, const int* var, const int* row,
+   const int* col, const double* val, double* out, int* route, int* slices);
+
+/* ipm.hip: the rounding frame of a solver - a grow-only device allocation of N + sum n_b^2 doubles (eigenvalues of block b at off[b],
+ * its vectors at N + voff[b]), valid from a hipsdp_rounding_frame that returned HIPSDP_OK until the next one, hipsdp_set_shape* or
+ * hipsdp_free; served[b] = 0: the frame holds block b.  hs_solver_round_frame: the solver's frame, grown to `need` doubles when
+ * need > 0 (the device is set by the caller: hs_solver_cut_enter_large / hs_solver_cut_plain).  hs_solver_cut_plain: the device is set
+ * and the cut workspace holds dev_len / pin_len doubles - no table, no matrix is looked at. */
+struct hs_round_frame { double* dev = NULL; long long len = 0; int valid = 0; std::vector<int> served; };
+int hs_solver_round_frame(hipsdp_solver* s, long long need, hs_round_frame** frame);
+int hs_solver_cut_plain(hipsdp_solver* s, long long dev_len, long long pin_len, hs_solver_cut_ws* w);
+/* the storage form (HS_EC_*) the job tables of hs_solver_cut_blocks name for the block, behind hs_solver_cut_enter[_large] */
+int hs_solver_block_form(const hipsdp_solver* s, int block);
+
 /* ---- solve1.hip: a whole node solve of a B&B-sized problem in one launch of one workgroup ------------------------------- */
 #define HS_S1_MAXBLK 8
 /* termination status written to out[0]: the HIPSDP_STATUS_* values of include/hipsdp.h, or -2: declined (too much work for one

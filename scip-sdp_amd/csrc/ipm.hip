@@ -289,6 +289,7 @@ struct hipsdp_solver
    /* pinned / device staging chunks of hipsdp_master_add_vars (kept until hipsdp_free) */
    void* stage_h[2]; void* stage_d[2]; hipEvent_t stage_ev[2]; long long stage_cap;
    CutWs cw;               /* the calls of csrc/cut_calls.hip and csrc/onevar.hip, through hs_solver_cut_* below */
+   hs_round_frame rframe;  /* hipsdp_rounding_frame / hipsdp_rounding_recombine (csrc/cut_calls.hip), through hs_solver_round_frame below */
    /* the first assembly of a cold solve, kept across solves of the same matrices (hs_gram_cache.h; GeneralSolve::assemble_forms):
     * gc_M holds (m1 + 32) m1 doubles as the identity assemblies left them in Mx, gc_key says of what.  Allocated at the first cold
     * solve that qualifies (gc_nomem: that failed for this shape, not tried again), freed with the problem. */
@@ -615,6 +616,8 @@ static void free_problem(hipsdp_solver* s)
    s->beta = s->elp = s->dxa = s->dza = s->dx = s->dz = s->xs = s->zs = s->ys = s->u1 = s->rhs2 = s->cvec = s->u2 = s->dy = s->dya = NULL;
    s->Mx = s->Lm = s->dinvm = s->Slp = s->sc = s->red_ws = s->gemv_ws = s->lan_ws = s->lan_ws2 = NULL;
    s->flags = NULL;
+   s->rframe.valid = 0;          /* (the frame belongs to a shape) */
+   s->rframe.served.clear();
    s->shaped = false;
    s->solved = false;
 }
@@ -737,6 +740,8 @@ extern "C" void hipsdp_free(hipsdp_solver** ps)
    if ( s->s1_ws != NULL ) (void) hipFree(s->s1_ws);
    s->s1_ws = NULL;
    s->cw.release();
+   if ( s->rframe.dev != NULL ) (void) hipFree(s->rframe.dev);
+   s->rframe.dev = NULL; s->rframe.len = 0;
    if ( s->clk_buf != NULL ) (void) hipFree(s->clk_buf);
    s->clk_buf = NULL;
    if ( s->clk_stream != NULL ) (void) hipStreamDestroy(s->clk_stream);
@@ -830,6 +835,8 @@ extern "C" int hipsdp_set_shape2(hipsdp_solver* s, int m, int nblocks, const int
       HS_HIP( hipStreamSynchronize(s->stream2) );
    s->stage_pending = false; s->stage_off = 0; s->ncmd = 0; s->cmd_inflight = false;
    s->zero_b = false; s->zero_D = false; s->s1_sol_host = false;
+   s->rframe.valid = 0;          /* (a rounding frame belongs to the shape it was made for, the same shape set again included) */
+   s->rframe.served.clear();
    /* The same shape again (the next node of a tree with the same fixings pattern, a re-load of the same problem): every
     * allocation is kept - the constraint matrices (GBs at the bench sizes), their packed copy and the Schur workspace cost tens
     * of milliseconds to free and allocate again - and only the contents are reset to what a fresh shape has. */
@@ -5924,6 +5931,36 @@ int hs_solver_cut_blocks(hipsdp_solver* s, const std::vector<int>& ids, const st
    }
    HS_CALL( cw.upload(jobs, std::vector<hs_eig_job>()) );
    cw.view(s->stream, w);
+   return HS_OK;
+}
+
+int hs_solver_block_form(const hipsdp_solver* s, int block)
+{
+   hs_ec_job J;
+   memset(&J, 0, sizeof(J));
+   ec_job_form(s->blk[block], &J);
+   return J.form;
+}
+
+int hs_solver_cut_plain(hipsdp_solver* s, long long dev_len, long long pin_len, hs_solver_cut_ws* w)
+{
+   HS_HIP( hipSetDevice(s->device) );
+   HS_CALL( s->cw.grow(dev_len, pin_len, 0) );
+   s->cw.view(s->stream, w);
+   return HS_OK;
+}
+
+int hs_solver_round_frame(hipsdp_solver* s, long long need, hs_round_frame** frame)
+{
+   hs_round_frame& F = s->rframe;
+   if ( need > F.len )
+   {
+      if ( F.dev != NULL ) HS_HIP( hipFree(F.dev) );
+      F.dev = NULL; F.len = 0;
+      HS_HIP( hipMalloc((void**) &F.dev, (size_t) need * sizeof(double)) );
+      F.len = need;
+   }
+   *frame = &F;
    return HS_OK;
 }
 

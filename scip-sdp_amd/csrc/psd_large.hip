@@ -41,22 +41,10 @@ namespace {
 
 typedef double pl_v4 __attribute__((ext_vector_type(4)));
 
-struct ppl_job
-{
-   int n, nnz, cap, ntc;
-   long long trip;             /* first triplet of the job in the packed arrays */
-   double* A;                  /* n x n, no pitch: the matrix (head of the decomposition's workspace), later the upper triangle of the result */
-   double* R;                  /* n x n: the reflector array of the tridiagonalisation */
-   const double* lam;          /* the decomposition: eigenvalues ascending, row k of V = k-th eigenvector */
-   const double* V;
-   double minev;
-   int* cnt;                   /* [i ntc + q]: kept entries of row i inside tile column q >= i / 64; from n ntc on [ti ntc + tj]: tile totals */
-};
-
-__global__ void __launch_bounds__(PL_NT) k_ppl_expand(const ppl_job* __restrict__ jobs, const int* __restrict__ row, const int* __restrict__ col,
+__global__ void __launch_bounds__(PL_NT) k_ppl_expand(const hs_ppl_job* __restrict__ jobs, const int* __restrict__ row, const int* __restrict__ col,
    const double* __restrict__ val)
 {
-   const ppl_job J = jobs[blockIdx.y];
+   const hs_ppl_job J = jobs[blockIdx.y];
    const int n = J.n, g = blockIdx.x, G = gridDim.x;
    for (int i = g; i < n; i += G)
       for (int c = threadIdx.x; c < n; c += PL_NT)
@@ -79,7 +67,7 @@ __global__ void __launch_bounds__(PL_NT) k_ppl_expand(const ppl_job* __restrict_
 /* s[kk][xx] = operand entry (x0 + xx, k0 + kk), zero beyond n.  mode 1: entry (x, k) = V[k n + x], consecutive threads walk x;
  * mode 0: V[x n + k], consecutive threads walk k - either way a wavefront reads whole lines.  SCALE: times the clamped eigenvalue k. */
 template <bool SCALE>
-__device__ __forceinline__ void ppl_panel(double (*s)[PL_LD], const ppl_job& J, int x0, int k0, int mode, double eps)
+__device__ __forceinline__ void ppl_panel(double (*s)[PL_LD], const hs_ppl_job& J, int x0, int k0, int mode, double eps)
 {
    const int n = J.n;
    for (int idx = threadIdx.x; idx < PL_K * PL_T; idx += PL_NT)
@@ -103,11 +91,11 @@ __device__ __forceinline__ void ppl_panel(double (*s)[PL_LD], const ppl_job& J, 
 
 /* Tile (ti, tj), ti <= tj, of job blockIdx.y.  Wavefront w owns the rows 16 w .. 16 w + 15 of the tile and its 64 columns: four
  * accumulators of v_mfma_f64_16x16x4_f64 (lane l holds A[l & 15][l >> 4], B[l >> 4][l & 15] and D[(l >> 4) + 4 r][l & 15], r = 0 .. 3). */
-__global__ void __launch_bounds__(PL_NT) k_ppl_recombine(const ppl_job* __restrict__ jobs, double eps, int mode)
+__global__ void __launch_bounds__(PL_NT) k_ppl_recombine(const hs_ppl_job* __restrict__ jobs, double eps, int mode)
 {
    __shared__ double sA[PL_K][PL_LD], sB[PL_K][PL_LD];
    __shared__ int swt[PL_NT / 64];
-   const ppl_job J = jobs[blockIdx.y];
+   const hs_ppl_job J = jobs[blockIdx.y];
    const int n = J.n, ntc = J.ntc;
    int ti = 0, rem = blockIdx.x;
    if ( rem >= ntc * (ntc + 1) / 2 )
@@ -167,7 +155,7 @@ __global__ void __launch_bounds__(PL_NT) k_ppl_recombine(const ppl_job* __restri
 }
 
 /* entries the projection of a job keeps: the totals of its upper-triangle tiles, in a fixed order */
-__device__ __forceinline__ int ppl_total(const ppl_job& J)
+__device__ __forceinline__ int ppl_total(const hs_ppl_job& J)
 {
    const int* __restrict__ t = J.cnt + J.n * J.ntc;
    int s = 0;
@@ -179,12 +167,12 @@ __device__ __forceinline__ int ppl_total(const ppl_job& J)
 
 /* workgroup (job, y) writes the rows 16 y .. 16 y + 15 of the job: wavefront w the rows 16 y + w + 4 k.  The job's offset in the
  * packed result = sum of the totals of the jobs before it (a job that does not fit its cap takes no room and writes nothing). */
-__global__ void __launch_bounds__(PL_NT) k_ppl_write(const ppl_job* __restrict__ jobs, double eps, long long outlen, int* __restrict__ tot,
+__global__ void __launch_bounds__(PL_NT) k_ppl_write(const hs_ppl_job* __restrict__ jobs, double eps, long long outlen, int* __restrict__ tot,
    int* __restrict__ orow, int* __restrict__ ocol, double* __restrict__ oval)
 {
    __shared__ long long sh[PL_NT / 64];
    __shared__ int srow[HIPSDP_PSD_LARGE_MAXN];
-   const ppl_job J = jobs[blockIdx.x];
+   const hs_ppl_job J = jobs[blockIdx.x];
    const int n = J.n, ntc = J.ntc, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    if ( (int) blockIdx.y * 16 >= n )
       return;
@@ -327,8 +315,8 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
    const size_t nb = (size_t) (C.end - C.first);
    ppl_ctx* c = NULL;
    HS_CALL( ppl_context(device, &c) );
-   /* upload: [ppl_job table | hs_sxm_job table | hs_srm_job table | act | values | rows | columns] */
-   const size_t u_tab = 0, u_sx = ppl_up16(u_tab + nb * sizeof(ppl_job)), u_sr = ppl_up16(u_sx + nb * sizeof(hs_sxm_job));
+   /* upload: [hs_ppl_job table | hs_sxm_job table | hs_srm_job table | act | values | rows | columns] */
+   const size_t u_tab = 0, u_sx = ppl_up16(u_tab + nb * sizeof(hs_ppl_job)), u_sr = ppl_up16(u_sx + nb * sizeof(hs_sxm_job));
    const size_t u_act = ppl_up16(u_sr + nb * sizeof(hs_srm_job)), u_val = ppl_up16(u_act + nb * sizeof(int));
    const size_t u_row = ppl_up16(u_val + (size_t) C.trips * sizeof(double)), u_col = ppl_up16(u_row + (size_t) C.trips * sizeof(int));
    const size_t up_bytes = ppl_up16(u_col + (size_t) C.trips * sizeof(int));
@@ -338,7 +326,7 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
    const size_t o_val = ppl_up16(nb * sizeof(int)), o_row = o_val + (size_t) C.res_len * sizeof(double);
    const size_t o_col = ppl_up16(o_row + (size_t) C.res_len * sizeof(int)), res_bytes = ppl_up16(o_col + (size_t) C.res_len * sizeof(int));
    HS_CALL( ppl_grow(c, up_bytes, w_res + res_bytes, res_bytes) );
-   ppl_job* tab = reinterpret_cast<ppl_job*>(c->hup + u_tab);
+   hs_ppl_job* tab = reinterpret_cast<hs_ppl_job*>(c->hup + u_tab);
    hs_sxm_job* sx = reinterpret_cast<hs_sxm_job*>(c->hup + u_sx);
    hs_srm_job* sr = reinterpret_cast<hs_srm_job*>(c->hup + u_sr);
    int* act = reinterpret_cast<int*>(c->hup + u_act);
@@ -356,7 +344,7 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
       HS_CALL( hs_syevx_many_job(it.n, dws + it.ws_off, dout + it.out_off, &sx[k]) );       /* (its selection output is not used) */
       HS_CALL( hs_syevr_many_job(it.n, dws + it.ws_off, dout + it.out_off, &sr[k]) );
       act[k] = HS_SXM_ACTIVE;
-      ppl_job& T = tab[k];
+      hs_ppl_job& T = tab[k];
       memset(&T, 0, sizeof(T));
       T.n = it.n; T.nnz = it.nnz; T.cap = it.cap; T.ntc = it.ntc; T.trip = it.trip;
       T.A = sx[k].A; T.R = sx[k].R; T.lam = dout + it.out_off; T.V = dout + it.out_off + HS_SYEVR_OUT_VEC(it.n);
@@ -369,19 +357,19 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
       }
    }
    hipStream_t st = c->stream;
-   const ppl_job* dtab = reinterpret_cast<const ppl_job*>(c->dwork + u_tab);
+   const hs_ppl_job* dtab = reinterpret_cast<const hs_ppl_job*>(c->dwork + u_tab);
    const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(c->dwork + u_sx);
    const hs_srm_job* dsr = reinterpret_cast<const hs_srm_job*>(c->dwork + u_sr);
    const int* dact = reinterpret_cast<const int*>(c->dwork + u_act);
-   const int ntc = (C.nmax + PL_T - 1) / PL_T;
    int launches = 0;
    int rc = HS_OK;
    do
    {
       hipError_t e = hipMemcpyAsync(c->dwork, c->hup, up_bytes, hipMemcpyHostToDevice, st);
       if ( e != hipSuccess ) { hs_record_hip_error(e, "hipMemcpyAsync(psd_project_many_large)", __FILE__, __LINE__); rc = HS_ERR_HIP; break; }
-      hipLaunchKernelGGL(k_ppl_expand, dim3(PL_EG, (unsigned) nb), dim3(PL_NT), 0, st, dtab, reinterpret_cast<const int*>(c->dwork + u_row),
-         reinterpret_cast<const int*>(c->dwork + u_col), reinterpret_cast<const double*>(c->dwork + u_val));
+      if ( (rc = hs_ppl_expand(st, (int) nb, dtab, reinterpret_cast<const int*>(c->dwork + u_row),
+               reinterpret_cast<const int*>(c->dwork + u_col), reinterpret_cast<const double*>(c->dwork + u_val))) != HS_OK )
+         break;
       ++launches;
       if ( (rc = hs_syevx_many_cols(st, (int) nb, C.nmax, hs_syevx_many_cap((int) nb), dsx, dact)) != HS_OK )
          break;
@@ -392,11 +380,12 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
       if ( (rc = hs_syevr_many_back(st, (int) nb, C.nmax, dsr)) != HS_OK )
          break;
       ++launches;
-      hipLaunchKernelGGL(k_ppl_recombine, dim3((unsigned) (ntc * (ntc + 1) / 2), (unsigned) nb), dim3(PL_NT), 0, st, dtab, epsilon, mode);
+      if ( (rc = hs_ppl_recombine(st, (int) nb, C.nmax, dtab, epsilon, mode)) != HS_OK )
+         break;
       ++launches;
-      hipLaunchKernelGGL(k_ppl_write, dim3((unsigned) nb, (unsigned) ((C.nmax + 15) / 16)), dim3(PL_NT), 0, st, dtab, epsilon, C.res_len,
-         reinterpret_cast<int*>(dres), reinterpret_cast<int*>(dres + o_row), reinterpret_cast<int*>(dres + o_col),
-         reinterpret_cast<double*>(dres + o_val));
+      if ( (rc = hs_ppl_write(st, (int) nb, C.nmax, dtab, epsilon, C.res_len, reinterpret_cast<int*>(dres), reinterpret_cast<int*>(dres + o_row),
+               reinterpret_cast<int*>(dres + o_col), reinterpret_cast<double*>(dres + o_val))) != HS_OK )
+         break;
       ++launches;
       e = hipGetLastError();
       if ( e != hipSuccess ) { hs_record_hip_error(e, "kernel launch (psd_project_many_large)", __FILE__, __LINE__); rc = HS_ERR_HIP; break; }
@@ -441,6 +430,35 @@ int ppl_run_chunk(int device, hipsdp_psd_job* jobs, const std::vector<hs_ppl_ite
    return HS_OK;
 }
 
+}
+
+/* the three launches over a job table in device memory, for this file and for hipsdp_rounding_frame / hipsdp_rounding_recombine
+ * (cut_calls.hip): the expand launch writes X where the column launches read it, the recombination and the write run on jobs that point
+ * at a solver's rounding frame (minev = -infinity: no eigenvalue is raised); nmax: the largest n of the table */
+int hs_ppl_expand(hipStream_t st, int count, const hs_ppl_job* djobs, const int* row, const int* col, const double* val)
+{
+   hipLaunchKernelGGL(k_ppl_expand, dim3(PL_EG, (unsigned) count), dim3(PL_NT), 0, st, djobs, row, col, val);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_ppl_recombine(hipStream_t st, int count, int nmax, const hs_ppl_job* djobs, double eps, int mode)
+{
+   if ( nmax < 1 || nmax > HIPSDP_PSD_LARGE_MAXN )
+      return HS_ERR_ARG;
+   const int ntc = (nmax + PL_T - 1) / PL_T;
+   hipLaunchKernelGGL(k_ppl_recombine, dim3((unsigned) (ntc * (ntc + 1) / 2), (unsigned) count), dim3(PL_NT), 0, st, djobs, eps, mode);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_ppl_write(hipStream_t st, int count, int nmax, const hs_ppl_job* djobs, double eps, long long outlen, int* tot, int* orow, int* ocol,
+   double* oval)
+{
+   hipLaunchKernelGGL(k_ppl_write, dim3((unsigned) count, (unsigned) ((nmax + 15) / 16)), dim3(PL_NT), 0, st, djobs, eps, outlen, tot, orow,
+      ocol, oval);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
 }
 
 /* the batched decomposition alone on `count` dense host matrices of mixed sizes (129 .. 512 rows each), for the unit entry

@@ -28,21 +28,10 @@ namespace {
 
 #define PP_NT 256
 
-struct pp_job
-{
-   int n, nnz, cap, pad;
-   long long trip;             /* first triplet of the job in the packed arrays */
-   double* A;                  /* n x n slab: the matrix, later the upper triangle of the result */
-   const double* ws;           /* slab of the decomposition: eigenvalues at [0 .. n), row k of the vectors at vpos + k n */
-   long long vpos;
-   double minev;
-   int* rowoff;                /* n + 1: where the rows start inside the job's result */
-};
-
-__global__ void __launch_bounds__(PP_NT) k_pp_expand(const pp_job* __restrict__ jobs, const int* __restrict__ row, const int* __restrict__ col,
+__global__ void __launch_bounds__(PP_NT) k_pp_expand(const hs_pp_job* __restrict__ jobs, const int* __restrict__ row, const int* __restrict__ col,
    const double* __restrict__ val)
 {
-   const pp_job J = jobs[blockIdx.x];
+   const hs_pp_job J = jobs[blockIdx.x];
    const int n2 = J.n * J.n;
    for (int e = threadIdx.x; e < n2; e += PP_NT)
       J.A[e] = 0.0;
@@ -64,10 +53,10 @@ static size_t pp_lds(int n)
 
 /* Lane = column j, a wavefront item = 4 rows x 64 columns.  mode 0 reads V[j][c] (lane stride = the odd pitch: conflict-free) and
  * V[i][c] (one address: broadcast); mode 1 reads V[k][j] (consecutive lanes, consecutive words) and V[k][i] (broadcast). */
-__global__ void __launch_bounds__(PP_NT) k_pp_recombine(const pp_job* __restrict__ jobs, double eps, int mode, int* __restrict__ tot)
+__global__ void __launch_bounds__(PP_NT) k_pp_recombine(const hs_pp_job* __restrict__ jobs, double eps, int mode, int* __restrict__ tot)
 {
    extern __shared__ __attribute__((aligned(16))) char pp_smem[];
-   const pp_job J = jobs[blockIdx.x];
+   const hs_pp_job J = jobs[blockIdx.x];
    const int n = J.n, ld = n | 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    double* sV = reinterpret_cast<double*>(pp_smem);
    double* sl = sV + n * ld;
@@ -75,11 +64,11 @@ __global__ void __launch_bounds__(PP_NT) k_pp_recombine(const pp_job* __restrict
    for (int e = tid; e < n * n; e += PP_NT)
    {
       const int k = e / n;
-      sV[k * ld + (e - k * n)] = J.ws[J.vpos + e];
+      sV[k * ld + (e - k * n)] = J.V[e];
    }
    for (int k = tid; k < n; k += PP_NT)
    {
-      const double l = J.ws[k];
+      const double l = J.lam[k];
       sl[k] = (l - J.minev < -eps) ? J.minev : l;
       scnt[2 * k] = 0; scnt[2 * k + 1] = 0;
    }
@@ -151,11 +140,11 @@ __global__ void __launch_bounds__(PP_NT) k_pp_recombine(const pp_job* __restrict
 
 /* workgroup (job, y) writes the rows 16 y .. 16 y + 15 of the job: wavefront w the rows 16 y + w + 4 k.  The job's offset in the
  * packed result = sum of the totals of the jobs before it (a job that does not fit its cap takes no room and writes nothing). */
-__global__ void __launch_bounds__(PP_NT) k_pp_write(const pp_job* __restrict__ jobs, const int* __restrict__ tot, double eps, long long outlen,
+__global__ void __launch_bounds__(PP_NT) k_pp_write(const hs_pp_job* __restrict__ jobs, const int* __restrict__ tot, double eps, long long outlen,
    int* __restrict__ htot, int* __restrict__ orow, int* __restrict__ ocol, double* __restrict__ oval)
 {
    __shared__ long long sh[PP_NT / 64];
-   const pp_job J = jobs[blockIdx.x];
+   const hs_pp_job J = jobs[blockIdx.x];
    const int n = J.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
    if ( (int) blockIdx.y * 16 >= n )
       return;
@@ -282,8 +271,8 @@ int pp_run_batched(int device, hipsdp_psd_job* jobs, const hs_pp_plan& P, double
    const size_t nb = P.items.size();
    pp_ctx* c = NULL;
    HS_CALL( pp_context(device, &c) );
-   /* upload: [pp_job table | hs_eig_job table | values | rows | columns] */
-   const size_t u_tab = 0, u_eig = pp_up16(u_tab + nb * sizeof(pp_job)), u_val = pp_up16(u_eig + nb * sizeof(hs_eig_job));
+   /* upload: [hs_pp_job table | hs_eig_job table | values | rows | columns] */
+   const size_t u_tab = 0, u_eig = pp_up16(u_tab + nb * sizeof(hs_pp_job)), u_val = pp_up16(u_eig + nb * sizeof(hs_eig_job));
    const size_t u_row = pp_up16(u_val + (size_t) P.trips * sizeof(double)), u_col = pp_up16(u_row + (size_t) P.trips * sizeof(int));
    const size_t up_bytes = pp_up16(u_col + (size_t) P.trips * sizeof(int));
    /* device block: [upload mirror | matrix slabs | decomposition slabs | row offsets | totals] */
@@ -294,7 +283,7 @@ int pp_run_batched(int device, hipsdp_psd_job* jobs, const hs_pp_plan& P, double
    const size_t o_row = (size_t) P.out_len * sizeof(double), o_col = pp_up16(o_row + (size_t) P.out_len * sizeof(int));
    const size_t o_tot = pp_up16(o_col + (size_t) P.out_len * sizeof(int)), out_bytes = o_tot + nb * sizeof(int);
    HS_CALL( pp_grow(c, up_bytes, work_bytes, out_bytes) );
-   pp_job* tab = reinterpret_cast<pp_job*>(c->hup + u_tab);
+   hs_pp_job* tab = reinterpret_cast<hs_pp_job*>(c->hup + u_tab);
    hs_eig_job* eig = reinterpret_cast<hs_eig_job*>(c->hup + u_eig);
    double* uval = reinterpret_cast<double*>(c->hup + u_val);
    int* urow = reinterpret_cast<int*>(c->hup + u_row);
@@ -307,10 +296,11 @@ int pp_run_batched(int device, hipsdp_psd_job* jobs, const hs_pp_plan& P, double
    {
       const hs_pp_item& it = P.items[k];
       const hipsdp_psd_job& J = jobs[it.job];
-      pp_job& T = tab[k];
+      hs_pp_job& T = tab[k];
       memset(&T, 0, sizeof(T));
       T.n = it.n; T.nnz = it.nnz; T.cap = it.cap; T.trip = it.trip;
-      T.A = dA + it.a_off; T.ws = dws + it.ws_off; T.vpos = hs_syev_many_vecpos(it.n); T.minev = J.minev; T.rowoff = doff + it.row_off;
+      T.A = dA + it.a_off; T.lam = dws + it.ws_off; T.V = dws + it.ws_off + hs_syev_many_vecpos(it.n); T.minev = J.minev;
+      T.rowoff = doff + it.row_off;
       memset(&eig[k], 0, sizeof(hs_eig_job));
       eig[k].n = it.n; eig[k].in = dA + it.a_off; eig[k].ws = dws + it.ws_off;
       if ( it.nnz > 0 )
@@ -321,26 +311,25 @@ int pp_run_batched(int device, hipsdp_psd_job* jobs, const hs_pp_plan& P, double
       }
    }
    hipStream_t st = c->stream;
-   const pp_job* dtab = reinterpret_cast<const pp_job*>(c->dwork + u_tab);
+   const hs_pp_job* dtab = reinterpret_cast<const hs_pp_job*>(c->dwork + u_tab);
    int launches = 0;
    int rc = HS_OK;
    do
    {
       hipError_t e = hipMemcpyAsync(c->dwork, c->hup, up_bytes, hipMemcpyHostToDevice, st);
       if ( e != hipSuccess ) { hs_record_hip_error(e, "hipMemcpyAsync(psd_project_many)", __FILE__, __LINE__); rc = HS_ERR_HIP; break; }
-      hipLaunchKernelGGL(k_pp_expand, dim3((unsigned) nb), dim3(PP_NT), 0, st, dtab, reinterpret_cast<const int*>(c->dwork + u_row),
-         reinterpret_cast<const int*>(c->dwork + u_col), reinterpret_cast<const double*>(c->dwork + u_val));
+      if ( (rc = hs_pp_expand(st, (int) nb, dtab, reinterpret_cast<const int*>(c->dwork + u_row),
+               reinterpret_cast<const int*>(c->dwork + u_col), reinterpret_cast<const double*>(c->dwork + u_val))) != HS_OK )
+         break;
       ++launches;
       if ( (rc = hs_syev_small_many(st, (int) nb, eig, reinterpret_cast<const hs_eig_job*>(c->dwork + u_eig), &launches)) != HS_OK )
          break;
-      static hs_attr_mask attr_done;
-      if ( (rc = hs_func_max_lds(reinterpret_cast<const void*>(&k_pp_recombine), (int) pp_lds(HS_PP_MAXN), &attr_done)) != HS_OK )
+      if ( (rc = hs_pp_recombine(st, (int) nb, P.nmax, dtab, epsilon, mode, dtot)) != HS_OK )
          break;
-      hipLaunchKernelGGL(k_pp_recombine, dim3((unsigned) nb), dim3(PP_NT), pp_lds(P.nmax), st, dtab, epsilon, mode, dtot);
       ++launches;
-      hipLaunchKernelGGL(k_pp_write, dim3((unsigned) nb, (unsigned) ((P.nmax + 15) / 16)), dim3(PP_NT), 0, st, dtab, dtot, epsilon,
-         P.out_len, reinterpret_cast<int*>(c->dout + o_tot), reinterpret_cast<int*>(c->dout + o_row), reinterpret_cast<int*>(c->dout + o_col),
-         reinterpret_cast<double*>(c->dout));
+      if ( (rc = hs_pp_write(st, (int) nb, P.nmax, dtab, dtot, epsilon, P.out_len, reinterpret_cast<int*>(c->dout + o_tot),
+               reinterpret_cast<int*>(c->dout + o_row), reinterpret_cast<int*>(c->dout + o_col), reinterpret_cast<double*>(c->dout))) != HS_OK )
+         break;
       ++launches;
       e = hipGetLastError();
       if ( e != hipSuccess ) { hs_record_hip_error(e, "kernel launch (psd_project_many)", __FILE__, __LINE__); rc = HS_ERR_HIP; }
@@ -384,6 +373,35 @@ int pp_run_batched(int device, hipsdp_psd_job* jobs, const hs_pp_plan& P, double
 int pp_class(int n) { return hs_syev_many_class(n); }
 long long pp_scratch(int n) { return hs_syev_small_scratch(n); }
 
+}
+
+/* the three launches over a job table in device memory, for this file and for the recombinations of hipsdp_rounding_recombine
+ * (cut_calls.hip), whose jobs point at a solver's rounding frame; nmax: the largest n of the table */
+int hs_pp_expand(hipStream_t st, int count, const hs_pp_job* djobs, const int* row, const int* col, const double* val)
+{
+   hipLaunchKernelGGL(k_pp_expand, dim3((unsigned) count), dim3(PP_NT), 0, st, djobs, row, col, val);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_pp_recombine(hipStream_t st, int count, int nmax, const hs_pp_job* djobs, double eps, int mode, int* dtot)
+{
+   if ( nmax < 1 || nmax > HS_PP_MAXN )
+      return HS_ERR_ARG;
+   static hs_attr_mask attr_done;
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_pp_recombine), (int) pp_lds(HS_PP_MAXN), &attr_done) );
+   hipLaunchKernelGGL(k_pp_recombine, dim3((unsigned) count), dim3(PP_NT), pp_lds(nmax), st, djobs, eps, mode, dtot);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_pp_write(hipStream_t st, int count, int nmax, const hs_pp_job* djobs, const int* dtot, double eps, long long outlen, int* htot,
+   int* orow, int* ocol, double* oval)
+{
+   hipLaunchKernelGGL(k_pp_write, dim3((unsigned) count, (unsigned) ((nmax + 15) / 16)), dim3(PP_NT), 0, st, djobs, dtot, eps, outlen, htot,
+      orow, ocol, oval);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
 }
 
 extern "C" int hipsdp_psd_project_many(int device, int count, hipsdp_psd_job* jobs, double epsilon, int mode)

@@ -2090,6 +2090,14 @@ extern "C" int hipsdp_check_many_group(void)
    return HS_CM_G;
 }
 
+/* the coefficient launches of hipsdp_rounding_frame alone on host data of one block (hs_rf_coefs_host, csrc/rounding.hip): the kernels and
+ * the routing rule of the call */
+extern "C" int hipsdp_rounding_coefs_unit(int device, int n, int m, int form, const double* V, const double* A, long long nnz, const int* var,
+   const int* row, const int* col, const double* val, double* out, int* route, int* slices)
+{
+   return hs_rf_coefs_host(device, n, m, form, V, A, nnz, var, row, col, val, out, route, slices);
+}
+
 /* the fan-out of hipsdp_solve_objectives alone (hs_objs_fanout, csrc/kernels.hip): the sources in device memory as the engine holds them
  * (the objectives in rows of m rounded up to even), the lanes filled with the guard word, one launch, the lanes back */
 extern "C" int hipsdp_objs_fanout_unit(int device, int count, int m, int q, int nblk, const int* ns, const double* B, const double* b_own,
