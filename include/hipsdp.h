@@ -252,7 +252,9 @@ HIPSDP_API int  hipsdp_get_preoptimal_X(hipsdp_solver* solver, int block, double
 
 /* smallest eigenvalue of  sum_i A_i^k y_i - A_0^k  for every block, on the device (backs the feasibility check of
  * sdpsolchecker.c:201-257 inside the backend); y: m host values; lmin: nblocks host values.  Per block: up to 200 rows the
- * Lanczos value minus its residual norm, a lower estimate and no decomposition; 201 .. HIPSDP_SYEVX_MAXN (512) rows the first eigenvalue
+ * Lanczos value minus its residual norm of a run of n steps (up to 16 rows: the exact kernel), no decomposition - a run that stopped
+ * before n steps (the start vector lies in an invariant subspace: repeated eigenvalues) has not seen the whole space, and the block
+ * is served like the next class; 201 .. HIPSDP_SYEVX_MAXN (512) rows the first eigenvalue
  * as hipsdp_syevx computes it, relative to the norm of Z(y) in the scale range stated there; above that a lower bound
  * estimate - 1e-9 (1 + |estimate|) certified by a Cholesky factorization, whose margin is absolute, or the computed eigenvalue
  * where the factorization fails */

@@ -150,6 +150,11 @@ HIPSDP_API int  hipsdp_tail_dir_unit(int device, int m, int n, int fused, const 
 HIPSDP_API int  hipsdp_tail_dots_unit(int device, int m, int n, int fused, const double* a, const double* v, double* out);
 HIPSDP_API int  hipsdp_trtri(int device, int n, const double* A, double* Linv);              /* A spd -> inverse of its Cholesky factor */
 HIPSDP_API int  hipsdp_lambda_min(int device, int n, const double* W, int steps, double* theta, double* resid);
+/* the Lanczos entry of the engine without a solver's exchange vectors, one or two matrices per launch (W1 may be NULL): exact up to 16
+ * rows, the fused launch per step up to 8192, a launch per step and matrix above; steps <= 0: min(n, 250).  theta[2], resid[2],
+ * steps_done[2]: {theta, residual bound, size of the tridiagonal matrix} per matrix (NaN, NaN, -1 for a matrix that is not given) */
+HIPSDP_API int  hipsdp_lambda_min2_unit(int device, int n, const double* W0, const double* W1, int steps, double* theta, double* resid,
+   int* steps_done);
 /* lambda_min(L D L^T), n <= 64, L lower triangular, D symmetric: the small-block step-length kernels; theta[2], resid[2] */
 HIPSDP_API int  hipsdp_lambda_min_scaled(int device, int n, const double* L, const double* D, int steps, double* theta, double* resid);
 /* host only: whether the one-launch kernel admits a shape (m variables, q LP rows, nblk blocks of ns[k] rows: its LDS layout fits),

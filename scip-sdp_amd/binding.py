@@ -1677,6 +1677,22 @@ def lambda_min(W, steps=0, device=0):
     return th.value, rs.value
 
 
+def lambda_min2_unit(W0, W1=None, steps=0, device=0):
+    """hs_lanczos_lmin2 without a solver's exchange vectors on one or two host matrices (hipsdp_lambda_min2_unit of the units library):
+    exact up to 16 rows, the fused launch per step up to 8192 rows, a launch per step and matrix above; steps 0: min(n, 250).
+    Returns (theta[2], resid[2], steps_done[2]); without W1 slot 1 keeps (nan, nan, -1)"""
+    W0 = _f64(W0)
+    n = W0.shape[0]
+    if W1 is not None:
+        W1 = _f64(W1)
+        assert W1.shape == W0.shape
+    th, rs = np.zeros(2), np.zeros(2)
+    sd = np.zeros(2, dtype=np.int32)
+    _chk(ulib().hipsdp_lambda_min2_unit(device, n, _dp(W0), _dp(W1) if W1 is not None else None, int(steps), _dp(th), _dp(rs), _ip(sd)),
+         "hipsdp_lambda_min2_unit")
+    return th, rs, sd
+
+
 def syev(A, device=0):
     A = _f64(A)
     n = A.shape[0]

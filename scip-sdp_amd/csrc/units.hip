@@ -1258,6 +1258,41 @@ extern "C" int hipsdp_lambda_min(int device, int n, const double* W, int steps, 
    return HIPSDP_OK;
 }
 
+/* hs_lanczos_lmin2 as the engine calls it where no solver's exchange vectors exist (rot = dsync = NULL): one or two matrices per
+ * launch (W1 may be NULL) - k_lmin_tiny up to 16 rows, k_lanczos_fused up to 8192, a launch per step and matrix above; steps <= 0:
+ * min(n, 250).  theta[2], resid[2], steps_done[2] = res[0 .. 2] of both matrices; the slot of a matrix that is not given keeps
+ * NaN, NaN, -1. */
+extern "C" int hipsdp_lambda_min2_unit(int device, int n, const double* W0, const double* W1, int steps, double* theta, double* resid,
+   int* steps_done)
+{
+   HS_CALL( pick_device(device) );
+   if ( n <= 0 || W0 == NULL || theta == NULL || resid == NULL || steps_done == NULL ) return HIPSDP_ERR_ARG;
+   if ( steps <= 0 ) steps = n < 250 ? n : 250;
+   if ( steps > 250 ) steps = 250;
+   const long long n2 = (long long) n * n;
+   DevBuf dW0, dW1, dR, dS0, dS1;
+   double h[16];
+   for (int i = 0; i < 16; ++i)
+      h[i] = (i & 7) == 2 ? -1.0 : NAN;
+   HS_CALL( dW0.alloc(n2) ); HS_CALL( dR.alloc(16) ); HS_CALL( dS0.alloc(hs_lanczos_ws(n, steps)) );
+   HS_CALL( dW0.up(W0, n2) ); HS_CALL( dR.up(h, 16) );
+   if ( W1 != NULL )
+   {
+      HS_CALL( dW1.alloc(n2) ); HS_CALL( dS1.alloc(hs_lanczos_ws(n, steps)) );
+      HS_CALL( dW1.up(W1, n2) );
+   }
+   HS_CALL( hs_lanczos_lmin2(0, n, dW0.p, W1 != NULL ? dW1.p : NULL, steps, dR.p, dR.p + 8, dS0.p, dS1.p, NULL, NULL, 0) );
+   HS_HIP( hipDeviceSynchronize() );
+   HS_CALL( dR.down(h, 16) );
+   for (int j = 0; j < 2; ++j)
+   {
+      theta[j] = h[8 * j];
+      resid[j] = h[8 * j + 1];
+      steps_done[j] = (int) h[8 * j + 2];
+   }
+   return HIPSDP_OK;
+}
+
 /* lambda_min(L D L^T) as the step-length code computes it for small blocks: theta and the residual bound, for the X-side and the
  * Z-side slot at once (same operands) */
 extern "C" int hipsdp_lambda_min_scaled(int device, int n, const double* L, const double* D, int steps, double* theta, double* resid)
