@@ -496,6 +496,90 @@ HIPSDP_API int hipsdp_check_y_many(hipsdp_solver* solver, int count, const doubl
  * they waited on (one per chunk); any pointer may be NULL.  The totals of the other calls do not move, and the reverse */
 HIPSDP_API int hipsdp_check_y_many_stats(long long* calls, long long* launches, long long* readbacks);
 
+/* The rank-1 constraints of MANY candidate points in one call: what the rank-1 part of CONSCHECK (consCheckSdp, cons_sdp.c:7735-7865)
+ * computes per solution and rank-1 constraint - isMatrixRankOne (:733-823): eigenvalue n - 1 of Z_b(y) = sum_i A_i^b y_i - A_0^b and, when
+ * that is not zero, the scan of all n (n - 1) / 2 principal 2 x 2 minors for the largest smaller eigenvalue; with quadconsrank1
+ * checkRank1QuadConss (:3712-3785): the scan of the minors' determinants against feastol - for count points at once, the points
+ * hipsdp_check_y_many checks for eigenvalue 1.  Y: count x m, row-major, host values (engine variables).  With Z = Z_b(Y[j]), o = j nblocks + b:
+ *     lam[3 o ..]         = COMPUTED eigenvalues 1, n - 1 and n of Z, each with the accuracy of the SCALE RANGE paragraph below: within
+ *                           1e-12 of the largest eigenvalue in absolute value.  n = 2: slot 1 is eigenvalue 1.  n = 1: slots 0 and 2 are the
+ *                           scalar, slot 1 is 0.0.  Slot 0 is what hipsdp_check_y_many returns for the same row, bit for bit.
+ *     minorev[o],         = the scan of :788-806: over the pairs (i, k), k < i, i ascending and then k ascending, the smaller eigenvalue
+ *     minorind[2 o ..]      of [[Z_ii, Z_ik], [Z_ik, Z_kk]]; the largest value that is > 0 and its pair (i, k); of equal values the FIRST
+ *                           pair in that order (the reference's strict >).  No minor with a positive smaller eigenvalue, or n = 1: 0.0
+ *                           and (-1, -1) - the reference asserts that case away (it scans only when eigenvalue n - 1 is not zero).  The
+ *                           value is the closed form  h - sqrt(g g + b b),  h = (a + c) / 2, g = (a - c) / 2, a = Z_ii, b = Z_ik,
+ *                           c = Z_kk, in plain FP64, every operation rounded on its own: absolute error a few ulp of |a| + |b| + |c|.
+ *     minordet[o],        = the scan of :3756-3780: minor = Z_ii Z_kk - Z_ik^2, both products rounded and then subtracted, no
+ *     detind[2 o ..]        contraction; minordet = the largest |minor| (0.0 for n = 1), detind = the FIRST pair in the same order with
+ *                           minor < -feastol || minor > feastol (the reference's early exit), else (-1, -1).
+ *     served[b]           = 0: block b is served; -1: it is not, and nothing of column b is written.  served may be NULL.
+ * Of the four output groups only lam is required: a NULL pair (minorev with minorind, minordet with detind) skips nothing on the device
+ * but is not copied out.
+ * Served: as hipsdp_check_y_many - blocks of 1 .. 512 rows of a solver without communicator and without sharded matrices, in all three
+ * storage forms; a block of more than 512 rows or without matrices on this device is not served and the other blocks still are; a solver
+ * with a communicator or sharded matrices: every served = -1, nothing launched, nothing written, HIPSDP_OK.
+ * HIPSDP_ERR_ARG, before the device is looked at and with nothing launched: solver NULL or without a shape, count < 0, feastol negative or
+ * not a number, Y or lam NULL with count > 0, one pointer of a pair NULL and the other not.  count == 0: HIPSDP_OK, nothing launched,
+ * nothing written (served included), the totals unchanged.
+ * The device side (csrc/rank1.hip, csrc/check_many.hip, csrc/eigi.hip, csrc/syevx.hip): the ONE launch of hipsdp_check_y_many forms
+ * Z_b(Y[j]) of all served blocks and candidates; ONE launch (k_r1_minors) runs both scans over the lower triangle of every Z, a workgroup
+ * per matrix, a fixed reduction order - while Z is still intact: the column launches below consume it; the eigenvalues {1, n - 1, n} come
+ * from ONE reduction per matrix, values only - up to 128 rows the tridiagonalisation of hipsdp_syevi_small once and its Sturm
+ * multisection once per index (one launch per class: 1 .. 64 rows, 65 .. 128 rows), for 129 .. 512 rows the batched tridiagonal path of
+ * hipsdp_syevx (the reflector arrays cleared, nmax - 1 column launches, ONE values launch for the ranges [1, 1] and [n - 1, n]; no vector
+ * launches; nmax: rows of the largest served block above 128 rows); ONE launch stores the eigenvalues.  Kernel launches of a call, with
+ * [..] = 1 when a served block of that class exists:
+ *     3 [any block] + [1 .. 64 rows] + [65 .. 128 rows] + [129 .. 512 rows] (nmax + 1)
+ * - a function of the classes present and of nmax alone, never of count or of the number of blocks -, one upload and ONE read-back.
+ * The workspace and the chunks are those of hipsdp_check_y_many (at most 512 MiB per chunk; HIPSDP_RANK1_CHUNK in the environment, read at
+ * every call: candidates per chunk instead), and every chunk is a call of its own in launches and read-backs.
+ * The bits of (j, b) depend on the block and on row j of Y alone - not on count, the other candidates, j's position, the other blocks or
+ * the chunks; same input, same bits; no atomics.  Two host threads may call it at the same time on different solvers. */
+HIPSDP_API int hipsdp_rank1_check_many(hipsdp_solver* solver, int count, const double* Y /* count x m, row-major, host */,
+                                       double feastol,
+                                       double* lam      /* count x nblocks x 3: eigenvalues 1, n-1, n of Z_b(Y[j]) */,
+                                       double* minorev  /* count x nblocks */, int* minorind /* count x nblocks x 2 */,
+                                       double* minordet /* count x nblocks */, int* detind   /* count x nblocks x 2 */,
+                                       int* served      /* nblocks; may be NULL */);
+/* process totals of hipsdp_rank1_check_many alone: calls that launched something, kernel launches they issued, device->host
+ * synchronisations they waited on (one per chunk); any pointer may be NULL.  The totals of the other calls do not move, and the reverse */
+HIPSDP_API int hipsdp_rank1_check_many_stats(long long* calls, long long* launches, long long* readbacks);
+
+/* The device part of the best rank-1 approximation heuristic (constraints/SDP/rank1approxheur, cons_sdp.c:7869-8185): per violated rank-1
+ * constraint the reference decomposes Z_b(y) FULLY, forms lambda_max v v^T by a matrix product and from it the right-hand side
+ * A_0 + lambda_max v v^T of a least-squares system - ONE eigenpair is used.  Here, for every asked-for block b (want[b] != 0; want NULL:
+ * all), with off_b = n_0 + ... + n_{b-1} and pos_b = sum_{b' < b} n_b' (n_b' + 1) / 2 over ALL blocks:
+ *     lmax[b]                           = eigenvalue n of Z_b(y), used as it is (the reference only asserts that the others are >= 0);
+ *     vec[off_b + i]                    = component i of its unit vector v;
+ *                                         the eigen entries' bounds: |lmax - ev| <= 1e-12 scale, | ||v|| - 1 | <= 1e-12, residual
+ *                                         |Z v - lmax v| <= 1e-9 scale (SCALE RANGE paragraph below);
+ *     rhs[pos_b + i (i + 1) / 2 + k]    = A_0[i][k] + (lmax v_i) v_k for k <= i - rhsmatrix of :8058-8092 in the reference's row order,
+ *                                         every operation rounded on its own, no contraction;
+ *     served[b]                         = 0: served; 1: not asked for; -1: asked for and not served.  served may be NULL.
+ * The slices of a block that is not served or not asked for are not written.  The coefficient matrix of the least-squares system is the
+ * caller's own constant data, and SCIPlapackLinearSolve (DGELSD) stays on the host ("Rank-1 constraints").
+ * Served: blocks of 1 .. 512 rows of a solver without communicator and without sharded matrices, in all three storage forms; such a solver
+ * otherwise: nothing launched, every asked-for block -1, HIPSDP_OK.
+ * HIPSDP_ERR_ARG, before the device is looked at: solver NULL or without a shape, y, lmax, vec or rhs NULL.
+ * The device side (csrc/rank1.hip, csrc/eigcuts.hip, csrc/eigi.hip, csrc/syevx.hip): ONE launch writes Z_b(y) of the asked-for blocks; up to
+ * 128 rows the batched full decomposition of hipsdp_eigencuts_all (3 launches) gives pair n; for 129 .. 512 rows ONE launch negates Z in the
+ * matrices of the batched tridiagonal path and clears the reflector arrays, nmax - 1 column launches and the 3 selection launches give
+ * eigenvalue 1 of -Z with its vector, which is pair n of Z (nmax: rows of the largest asked-for block above 128 rows); ONE launch stores
+ * lmax (the sign put back), vec and rhs, A_0 read from the block's storage form.  Kernel launches, with [..] = 1 when an asked-for served
+ * block of that class exists:
+ *     2 + 3 [1 .. 128 rows] + [129 .. 512 rows] (nmax + 3)
+ * one upload and ONE read-back.  The blocks are taken by descending size in chunks of at most 512 MiB of the cut workspace
+ * (HIPSDP_RANK1_APPROX_CHUNK in the environment, read at every call: blocks per chunk instead); every chunk is a call of its own in
+ * launches and read-backs.  The bits of a block do not depend on the other blocks, on want or on the chunks. */
+HIPSDP_API int hipsdp_rank1_approx(hipsdp_solver* solver, const double* y /* m */, const int* want /* nblocks, or NULL: all */,
+                                   double* lmax /* nblocks */, double* vec /* sum n_b, block b at off_b */,
+                                   double* rhs  /* sum n_b (n_b + 1) / 2 */,
+                                   int* served  /* nblocks; may be NULL: 0 served, 1 not asked for, -1 not served */);
+/* process totals of hipsdp_rank1_approx alone (calls that launched something, kernel launches, read-backs: one per chunk); any pointer may
+ * be NULL */
+HIPSDP_API int hipsdp_rank1_approx_stats(long long* calls, long long* launches, long long* readbacks);
+
 /* All one-variable SDPs of a block in one call: the bound-tightening loops of cons_sdp.c - tightenBounds (:1968-2201) and
  * tightenMatrices (:1856-1961) solve one SDP PER VARIABLE of a block, each the semismooth Newton method of
  * SCIPsolveOneVarSDPDense (solveonevarsdp.c:370-533) on  mu A_i - C_i,  C_i = A_0 - sum_{k != i} ub_k A_k.  With

@@ -218,6 +218,16 @@ HIPSDP_API int  hipsdp_sparse_dump_unit(hipsdp_solver* solver, int block, long l
 HIPSDP_API int  hipsdp_form_z_many_unit(hipsdp_solver* solver, int count, const double* Y, double* Z, int* served, int* launches);
 /* the candidates k_cm_form_z serves per pass over a block's storage (HS_CM_G, a compile-time constant of csrc/hs_kernels.h) */
 HIPSDP_API int  hipsdp_check_many_group(void);
+/* the minors launch of hipsdp_rank1_check_many (csrc/rank1.hip: k_r1_minors's scans) alone on `count` host matrices, matrix k of n[k]
+ * rows (1 .. 512), one behind the other in Z (the lower triangle at [i n + k], k <= i, is read): minorev[k], minorind[2 k ..],
+ * minordet[k], detind[2 k ..] as the call returns them for one (candidate, block).  HIPSDP_ERR_ARG: count < 1, a size outside 1 .. 512,
+ * feastol negative or not a number, a NULL pointer. */
+HIPSDP_API int  hipsdp_rank1_minors_unit(int device, int count, const int* n, const double* Z, double feastol, double* minorev, int* minorind,
+   double* minordet, int* detind);
+/* the three-index values kernels of hipsdp_rank1_check_many on `count` (at most 65535) host matrices laid out as above, every matrix by
+ * the kernels of its size class (1 .. 64 rows, 65 .. 128 rows, 129 .. 512 rows: the column launches and the one values launch) and the
+ * launch that stores the eigenvalues: lam[3 k ..] = eigenvalues 1, n - 1, n of matrix k (n = 1, 2: the call's conventions) */
+HIPSDP_API int  hipsdp_lsel_many_unit(int device, int count, const int* n, const double* Z, double* lam);
 /* the coefficient launches of hipsdp_rounding_frame (csrc/rounding.hip: k_rf_gather, k_rf_coefs_scalar, k_rf_coefs_mc, k_rf_store) alone
  * on host data of ONE block, through the routing rule of the call: V (n x n, row j = v_j) and the block's matrices in the form `form` -
  * 0: dense rows, A = (m + 1) x n^2; 1: packed lower triangles, A = (m + 1) x n (n + 1) / 2, entry (r, c), c <= r, at r (r + 1) / 2 + c;

@@ -455,6 +455,55 @@ class Solver:
         """process totals (calls, launches, read-backs) of hipsdp_check_y_many in the library this solver lives in"""
         return check_y_many_stats(self._l)
 
+    def rank1_check_many(self, Y, feastol, fill=np.nan, minors=True, dets=True):
+        """the rank-1 constraints of many candidate points in one call (hipsdp_rank1_check_many): Y is count x m; returns
+        (lam[count, nblocks, 3], minorev[count, nblocks], minorind[count, nblocks, 2], minordet[count, nblocks],
+        detind[count, nblocks, 2], served[nblocks]) - served[b] = -1: block b is not served and its columns keep `fill` (the index
+        arrays -7); minors / dets = False: that pair is passed as NULL and returned as None"""
+        Y = _f64(Y).reshape(-1, self.m) if self.m > 0 else np.zeros((len(Y), 0))
+        count, nb = Y.shape[0], len(self.ns)
+        c1, b1 = max(1, count), max(1, nb)
+        lam = np.full((c1, b1, 3), fill, dtype=np.float64)
+        mev, mdet = np.full((c1, b1), fill, dtype=np.float64), np.full((c1, b1), fill, dtype=np.float64)
+        mind, dind = np.full((c1, b1, 2), -7, dtype=np.int32), np.full((c1, b1, 2), -7, dtype=np.int32)
+        served = np.full(b1, -1, dtype=np.int32)
+        _chk(self._l().hipsdp_rank1_check_many(self.h, count, _dp(Y), C.c_double(feastol), _dp(lam), _dp(mev) if minors else None,
+                                               _ip(mind) if minors else None, _dp(mdet) if dets else None, _ip(dind) if dets else None,
+                                               _ip(served)), "hipsdp_rank1_check_many")
+        return (lam[:count, :nb], mev[:count, :nb] if minors else None, mind[:count, :nb] if minors else None,
+                mdet[:count, :nb] if dets else None, dind[:count, :nb] if dets else None, served[:nb])
+
+    def rank1_approx(self, y, want=None, fill=np.nan, raw=False):
+        """the device part of the rank-1 approximation heuristic (hipsdp_rank1_approx): per block (lmax, v[n], rhs[n (n + 1) / 2]) or None
+        for a block that is not asked for or not served; returns (list, served[nblocks]); raw: the call's own arrays (lmax[nblocks], vec,
+        rhs, served) instead, the slices it did not write still holding `fill`"""
+        y = _f64(y)
+        nb = len(self.ns)
+        lmax = np.full(max(1, nb), fill)
+        vec = np.full(max(1, int(sum(self.ns))), fill)
+        rhs = np.full(max(1, sum(n * (n + 1) // 2 for n in self.ns)), fill)
+        served = np.full(max(1, nb), -7, dtype=np.int32)
+        w = None if want is None else np.ascontiguousarray(want, dtype=np.int32)
+        _chk(self._l().hipsdp_rank1_approx(self.h, _dp(y), None if w is None else _ip(w), _dp(lmax), _dp(vec), _dp(rhs), _ip(served)),
+             "hipsdp_rank1_approx")
+        if raw:
+            return lmax[:nb], vec, rhs, served[:nb]
+        out, vo, ro = [], 0, 0
+        for b, n in enumerate(self.ns):
+            t = n * (n + 1) // 2
+            out.append((float(lmax[b]), vec[vo:vo + n].copy(), rhs[ro:ro + t].copy()) if served[b] == 0 else None)
+            vo += n
+            ro += t
+        return out, served[:nb]
+
+    def rank1_approx_stats(self):
+        """process totals (calls, launches, read-backs) of hipsdp_rank1_approx in the library this solver lives in"""
+        return rank1_approx_stats(self._l)
+
+    def rank1_check_many_stats(self):
+        """process totals (calls, launches, read-backs) of hipsdp_rank1_check_many in the library this solver lives in"""
+        return rank1_check_many_stats(self._l)
+
     def rounding_frame(self, X, want_vecs=True, fill=np.nan, raw=False):
         """stage 1 of the primal rounding problem (hipsdp_rounding_frame): X is a list with one entry per block - a dense symmetric
         n_b x n_b array (its nonzeros of both triangles become the triplets), a tuple (row, col, val) of triplets, or None (the zero
@@ -961,6 +1010,53 @@ def check_y_many_stats(which=None):
     calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     _chk((which or lib)().hipsdp_check_y_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_check_y_many_stats")
     return calls.value, launches.value, readbacks.value
+
+
+def rank1_check_many_stats(which=None):
+    """process totals of hipsdp_rank1_check_many: (calls that launched something, kernel launches issued, device->host
+    synchronisations); which: the library loader whose copy of the engine is asked (lib, the default, or ulib)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk((which or lib)().hipsdp_rank1_check_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)),
+         "hipsdp_rank1_check_many_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def rank1_approx_stats(which=None):
+    """process totals of hipsdp_rank1_approx: (calls that launched something, kernel launches issued, device->host synchronisations)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk((which or lib)().hipsdp_rank1_approx_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_rank1_approx_stats")
+    return calls.value, launches.value, readbacks.value
+
+
+def _mats_cat(mats):
+    mats = [np.asarray(a, dtype=np.float64) for a in mats]
+    ns = np.ascontiguousarray([a.shape[0] for a in mats], dtype=np.int32)
+    assert all(a.shape == (n, n) for a, n in zip(mats, ns))
+    return ns, _f64(np.concatenate([a.reshape(-1) for a in mats]))
+
+
+def rank1_minors_unit(mats, feastol, device=0):
+    """the two scans over the principal 2 x 2 minors on host matrices of mixed sizes (hipsdp_rank1_minors_unit of the units library):
+    (minorev[count], minorind[count, 2], minordet[count], detind[count, 2])"""
+    ns, cat = _mats_cat(mats)
+    k = len(ns)
+    mev, mdet = np.full(k, np.nan), np.full(k, np.nan)
+    mind, dind = np.full((k, 2), -7, dtype=np.int32), np.full((k, 2), -7, dtype=np.int32)
+    rc = ulib().hipsdp_rank1_minors_unit(device, k, _ip(ns), _dp(cat), C.c_double(feastol), _dp(mev), _ip(mind), _dp(mdet), _ip(dind))
+    if rc != 0:
+        raise RuntimeError("hipsdp_rank1_minors_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    return mev, mind, mdet, dind
+
+
+def lsel_many_unit(mats, device=0):
+    """eigenvalues 1, n - 1 and n of host matrices of mixed sizes by the three-index values kernels of hipsdp_rank1_check_many
+    (hipsdp_lsel_many_unit of the units library): lam[count, 3]"""
+    ns, cat = _mats_cat(mats)
+    lam = np.full((len(ns), 3), np.nan)
+    rc = ulib().hipsdp_lsel_many_unit(device, len(ns), _ip(ns), _dp(cat), _dp(lam))
+    if rc != 0:
+        raise RuntimeError("hipsdp_lsel_many_unit: %d (%s)" % (rc, ulib().hipsdp_last_error()))
+    return lam
 
 
 class RoundingOut(C.Structure):

@@ -913,7 +913,8 @@ hs_ecl_block cm_large_block(int n) { return hs_ecl_block_make((long long) hs_sye
 long long cm_mat_len(int n) { return n <= HS_SC_MAXN ? hs_cut_mat_len(n) : cm_large_block(n).len; }
 
 /* a chunk between its layout and its launches: the workspace with the solver's table of the served blocks (w.djobs), the layout, where
- * the matrices of every served block start */
+ * the matrices of every served block start.  lamw: doubles per matrix of at most 128 rows in L.lam - 2: hipsdp_check_y_many's layout, 4:
+ * that of hipsdp_rank1_check_many (hs_r1_layout_make) */
 struct CmRun
 {
    hs_solver_cut_ws w;
@@ -925,7 +926,7 @@ struct CmRun
 /* The head of the chunk over the candidates Y[0 .. cc) (rows of m): the layout - with_eig = false: every block's matrices are plain
  * n x n arrays and nothing of the eigenvalue path is laid out (the unit entry) -, the workspace, Yg, the block table and, for the
  * blocks of 129 .. 512 rows, the jobs of the batched tridiagonal path in the pinned mirror, the ONE upload, Z of every (candidate, block). */
-int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y, bool with_eig, CmRun* R)
+int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y, bool with_eig, CmRun* R, int lamw = 2)
 {
    const int nsv = (int) P.ids.size(), nlarge = with_eig ? P.nlarge : 0, nsm = nsv - nlarge;
    R->start.resize((size_t) nsv);
@@ -938,7 +939,10 @@ int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y
       blocks_len += (long long) cc * (k < nsm ? hs_cut_mat_len(n) : cm_large_block(n).len);
    }
    hs_cm_layout& L = R->L;
-   hs_cm_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, blocks_len, &L);
+   if ( lamw == 2 )
+      hs_cm_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, blocks_len, &L);
+   else
+      hs_r1_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, HS_R1_RESW, blocks_len, &L);
    HS_CALL( hs_solver_cut_blocks(s, P.ids, std::vector<long long>((size_t) nsv, 0), L.len.dev_len, L.len.pin_len, &R->w) );
    const hs_solver_cut_ws& w = R->w;
    /* Yg[g][i][k] = Y[g HS_CM_G + k][i], zeros behind the last candidate */
@@ -962,7 +966,7 @@ int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y
       if ( k < nsm )
       {
          B.Z = base; B.zstride = hs_cut_mat_len(n);
-         B.lam = w.dev + L.lam + 2LL * cc * k; B.lstride = 2;
+         B.lam = w.dev + L.lam + (long long) lamw * cc * k; B.lstride = lamw;
          continue;
       }
       /* job (block k, candidate c) of the tridiagonal path: Z goes where the column launches read their matrix, the head of its workspace */
@@ -1533,4 +1537,300 @@ extern "C" int hipsdp_rounding_recombine(hipsdp_solver* s, const double* lambda,
 extern "C" int hipsdp_rounding_stats(long long* calls, long long* launches, long long* readbacks)
 {
    return g_rf.get(calls, launches, readbacks);
+}
+
+namespace {
+
+/* ---- hipsdp_rank1_check_many: eigenvalues 1, n - 1, n and the two scans over the 2 x 2 principal minors of every Z_b(Y[j]) (kernels:
+ * rank1.hip, check_many.hip, eigi.hip, syevx.hip).  The served blocks, the chunks, the workspace and Z are those of hipsdp_check_y_many
+ * (cm_served, cm_begin); what follows Z differs. ---------------------------------------------------------------------------------------- */
+CutStats g_r1;
+
+/* where the four optional output groups of a chunk's candidates go (rows of nb blocks); a NULL pair is not copied out */
+struct R1Dst { double* lam; double* minorev; int* minorind; double* minordet; int* detind; };
+
+/* ONE CHUNK: the candidates Y[0 .. cc): ONE upload, hs_r1_launches(..) launches whatever cc and the number of blocks are, ONE read-back.
+ * The minors launch stands right behind Z(y): the column launches of the 129 .. 512 class consume their matrix. */
+int r1_chunk(hipsdp_solver* s, int m, int nb, const CmBlocks& P, int cc, const double* Y, double feastol, const R1Dst& d)
+{
+   CmRun R;
+   HS_CALL( cm_begin(s, m, P, cc, Y, true, &R, 4) );
+   const hs_solver_cut_ws& w = R.w;
+   const hs_cm_layout& L = R.L;
+   hipStream_t st = w.stream;
+   const int nsv = (int) P.ids.size();
+   const hs_cm_blk* db = reinterpret_cast<const hs_cm_blk*>(w.dev + L.blks);
+   double* dres = w.dev + L.res;
+   HS_CALL( hs_r1_minors(st, nsv, cc, P.nmax, feastol, w.djobs, db, dres) );
+   ++R.launches;
+   if ( P.nsmall > 0 )
+   {
+      HS_CALL( hs_lsel_many_small(st, P.nsmall, cc, P.nmax_small, w.djobs, db) );
+      ++R.launches;
+   }
+   if ( P.nmid > 0 )
+   {
+      const int cus = hs_device_cus();
+      HS_CALL( hs_lsel_many_mid(st, P.nmid, cc, P.nmax_mid, cus > 0 ? cus : 256, w.djobs + P.nsmall, db + P.nsmall) );
+      ++R.launches;
+   }
+   if ( P.nlarge > 0 )
+   {
+      const int jobs = P.nlarge * cc;
+      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
+      const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
+      HS_CALL( hs_ecl_clear(st, jobs, dsx) );
+      HS_CALL( hs_syevx_many_cols(st, jobs, P.nmax_large, hs_syevx_many_cap(jobs), dsx, dact) );
+      HS_CALL( hs_syevx_many_index(st, jobs, P.nmax_large, dsx, dact) );
+      R.launches += 1 + (P.nmax_large - 1) + 1;
+   }
+   HS_CALL( hs_r1_result(st, nsv, cc, w.djobs, db, dres) );
+   ++R.launches;
+   if ( R.launches != hs_r1_launches(nsv > 0, P.nsmall > 0, P.nmid > 0, P.nmax_large) )
+      return HIPSDP_ERR_NUMERIC;
+   hs_cut_res none;
+   memset(&none, 0, sizeof(none));
+   none.ints = none.sup = -1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, none, L.len, R.launches, &g_r1, &h) );
+   const double* res = w.pin + L.res;
+   for (int c = 0; c < cc; ++c)
+      for (int k = 0; k < nsv; ++k)
+      {
+         const double* row = res + ((size_t) c * nsv + k) * HS_R1_RESW;
+         const size_t o = (size_t) c * nb + P.ids[k];
+         int ind[4];
+         memcpy(ind, row + 5, sizeof(ind));
+         d.lam[3 * o] = row[0]; d.lam[3 * o + 1] = row[1]; d.lam[3 * o + 2] = row[2];
+         if ( d.minorev != NULL )
+         {
+            d.minorev[o] = row[3];
+            d.minorind[2 * o] = ind[0]; d.minorind[2 * o + 1] = ind[1];
+         }
+         if ( d.minordet != NULL )
+         {
+            d.minordet[o] = row[4];
+            d.detind[2 * o] = ind[2]; d.detind[2 * o + 1] = ind[3];
+         }
+      }
+   return HIPSDP_OK;
+}
+
+int rank1_check_many_impl(hipsdp_solver* s, int count, const double* Y, double feastol, const R1Dst& d, int* served)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || count < 0 || !(feastol >= 0.0) || (count > 0 && (Y == NULL || d.lam == NULL))
+      || (d.minorev == NULL) != (d.minorind == NULL) || (d.minordet == NULL) != (d.detind == NULL) )
+      return HIPSDP_ERR_ARG;
+   if ( count == 0 )
+      return HIPSDP_OK;
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = -1;
+   int q = 0;
+   const double* Dext = NULL;
+   if ( !hs_solver_lp_rows(s, &q, &Dext) )                  /* a communicator or sharded matrices: nothing is served */
+      return HIPSDP_OK;
+   CmBlocks P;
+   HS_CALL( cm_served(s, &P) );
+   if ( served != NULL )
+      for (int b : P.ids)
+         served[b] = 0;
+   if ( P.ids.empty() )
+      return HIPSDP_OK;
+   /* what a candidate takes of the workspace: its matrices, its eigenvalues, its point, its jobs and its rows of the result */
+   long long per = (long long) m + (long long) P.nlarge * (SCLR_JOBW + 1) + (4LL + HS_R1_RESW) * P.ids.size();
+   for (int b : P.ids)
+      per += cm_mat_len(hs_solver_block_n(s, b));
+   const std::vector<long long> job_len((size_t) count, per);
+   HS_CALL( hs_chunks_run(job_len.data(), count, SCLR_BUDGET, hs_chunk_env("HIPSDP_RANK1_CHUNK"), [&](int start, int end)
+      {
+         const size_t o = (size_t) start * nb;
+         const R1Dst c = { d.lam + 3 * o, d.minorev != NULL ? d.minorev + o : NULL, d.minorind != NULL ? d.minorind + 2 * o : NULL,
+            d.minordet != NULL ? d.minordet + o : NULL, d.detind != NULL ? d.detind + 2 * o : NULL };
+         return r1_chunk(s, m, nb, P, end - start, Y + (size_t) start * m, feastol, c);
+      }) );
+   ++g_r1.calls;
+   return HIPSDP_OK;
+}
+
+}
+
+extern "C" int hipsdp_rank1_check_many(hipsdp_solver* s, int count, const double* Y, double feastol, double* lam, double* minorev, int* minorind,
+   double* minordet, int* detind, int* served)
+{
+   const R1Dst d = { lam, minorev, minorind, minordet, detind };
+   return rank1_check_many_impl(s, count, Y, feastol, d, served);
+}
+
+extern "C" int hipsdp_rank1_check_many_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_r1.get(calls, launches, readbacks);
+}
+
+namespace {
+
+/* ---- hipsdp_rank1_approx: eigenpair n of Z_b(y) and the right-hand side A_0 + lambda v v^T of the rank-1 approximation heuristic for the
+ * asked-for blocks (kernels: eigcuts.hip for Z(y), the batched full decomposition of eigi.hip up to 128 rows, the batched tridiagonal path
+ * of syevx.hip on -Z above, rank1.hip for the rest) --------------------------------------------------------------------------------------- */
+static_assert(sizeof(hs_r1a_job) == 5 * sizeof(double), "hs_r1a_layout: tabw");
+#define R1A_TABW 5
+CutStats g_r1a;
+
+/* what a block of n rows takes of a chunk's workspace: Z and the slab of its decomposition, or the workspace of the tridiagonal form (Z is
+ * formed into its head) and the selection output */
+long long r1a_block_len(int n)
+{
+   return n <= HS_SC_MAXN ? hs_cut_mat_len(n) + ((hs_syev_small_scratch(n) + 1) & ~1LL) : cm_large_block(n).len;
+}
+
+/* ONE CHUNK: the asked-for served blocks `ids` (descending n): ONE upload, hs_r1a_launches(..) launches, ONE read-back, the copy-out.
+ * voff / roff: where a block's vector and right-hand side start in the caller's arrays. */
+int r1a_chunk(hipsdp_solver* s, int m, const std::vector<int>& ids, const double* y, const std::vector<long long>& voff,
+   const std::vector<long long>& roff, double* lmax, double* vec, double* rhs)
+{
+   const int cnt = (int) ids.size();
+   /* the tables want the blocks of at most 128 rows ordered by decomposition class; the larger ones come first in ids */
+   int nlg = 0, nmax = 0, nmax_large = 0;
+   for (int b : ids)
+      nlg += hs_solver_block_n(s, b) > HS_SC_MAXN ? 1 : 0;
+   const int nsm = cnt - nlg;
+   std::vector<int> order(ids.begin(), ids.begin() + nlg);
+   for (int cls = 0; cls < 3; ++cls)
+      for (int j = nlg; j < cnt; ++j)
+         if ( hs_syev_many_class(hs_solver_block_n(s, ids[j])) == cls )
+            order.push_back(ids[j]);
+   std::vector<long long> start((size_t) cnt), cvoff((size_t) cnt), croff((size_t) cnt), zoff((size_t) cnt);
+   long long blocks_len = 0, vec_len = 0, rhs_len = 0;
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int n = hs_solver_block_n(s, order[j]);
+      nmax = std::max(nmax, n);
+      if ( j < nlg )
+         nmax_large = std::max(nmax_large, n);
+      start[j] = blocks_len; cvoff[j] = vec_len; croff[j] = rhs_len;
+      blocks_len += r1a_block_len(n);
+      vec_len += n;
+      rhs_len += (long long) n * (n + 1) / 2;
+   }
+   hs_r1a_layout L;
+   hs_r1a_layout_make(m, cnt, nsm, R1A_TABW, SCLR_SJOBW, SCLR_JOBW, vec_len, rhs_len, blocks_len, &L);
+   for (int j = 0; j < cnt; ++j)
+      zoff[j] = L.blocks + start[j] + (j < nlg ? cm_large_block(hs_solver_block_n(s, order[j])).ws : 0);
+   hs_solver_cut_ws w;
+   HS_CALL( hs_solver_cut_blocks(s, order, zoff, L.len.dev_len, L.len.pin_len, &w) );
+   hipStream_t st = w.stream;
+   if ( m > 0 )
+      memcpy(w.pin + L.y, y, (size_t) m * sizeof(double));
+   hs_r1a_job* htab = reinterpret_cast<hs_r1a_job*>(w.pin + L.tab);
+   hs_eig_job* hej = reinterpret_cast<hs_eig_job*>(w.pin + L.ejobs);
+   hs_sxm_job* hsx = reinterpret_cast<hs_sxm_job*>(w.pin + L.jobs);
+   int* hact = reinterpret_cast<int*>(w.pin + L.act);
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int n = hs_solver_block_n(s, order[j]);
+      double* base = w.dev + L.blocks + start[j];
+      hs_r1a_job& T = htab[j];
+      T.voff = cvoff[j]; T.roff = croff[j];
+      if ( j < nlg )
+      {
+         const hs_ecl_block E = cm_large_block(n);
+         HS_CALL( hs_syevx_many_job(n, base + E.ws, base + E.out, &hsx[j]) );
+         if ( hsx[j].A != base + E.ws )
+            return HIPSDP_ERR_NUMERIC;
+         hact[j] = HS_SXM_ACTIVE | HS_SXM_VEC;
+         T.lam = base + E.out + HS_SYEVX_OUT_LAM; T.vec = base + E.out + HS_SYEVX_OUT_VEC; T.sign = -1.0;
+         continue;
+      }
+      hs_eig_job& E = hej[j - nlg];
+      memset(&E, 0, sizeof(E));
+      E.n = n; E.in = base; E.ws = base + hs_cut_mat_len(n);
+      T.lam = E.ws + (n - 1); T.vec = E.ws + hs_syev_many_vecpos(n) + (long long) (n - 1) * n; T.sign = 1.0;
+   }
+   HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
+   int launches = 0;
+   HS_CALL( hs_ec_form_z(st, cnt, nmax, m, w.djobs, w.dev + L.y) );
+   ++launches;
+   if ( nsm > 0 )
+      HS_CALL( scx_syev(st, nsm, hej, reinterpret_cast<const hs_eig_job*>(w.dev + L.ejobs), &launches) );
+   if ( nlg > 0 )
+   {
+      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
+      const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
+      HS_CALL( hs_r1_negate(st, nlg, nmax_large, dsx) );
+      HS_CALL( hs_syevx_many_cols(st, nlg, nmax_large, hs_syevx_many_cap(nlg), dsx, dact) );
+      HS_CALL( hs_syevx_many_select(st, nlg, nmax_large, 0, dsx, dact) );
+      launches += 1 + (nmax_large - 1) + 3;
+   }
+   HS_CALL( hs_r1_rhs(st, cnt, nmax, w.djobs, reinterpret_cast<const hs_r1a_job*>(w.dev + L.tab), w.dev + L.lmax, w.dev + L.vec, w.dev + L.rhs) );
+   ++launches;
+   if ( launches != hs_r1a_launches(nsm > 0, nmax_large) )
+      return HIPSDP_ERR_NUMERIC;
+   hs_cut_res none;
+   memset(&none, 0, sizeof(none));
+   none.ints = none.sup = -1;
+   hs_sc_out h;
+   HS_CALL( cut_readback(w, none, L.len, launches, &g_r1a, &h) );
+   for (int j = 0; j < cnt; ++j)
+   {
+      const int b = order[j], n = hs_solver_block_n(s, b);
+      lmax[b] = w.pin[L.lmax + j];
+      memcpy(vec + voff[b], w.pin + L.vec + cvoff[j], (size_t) n * sizeof(double));
+      memcpy(rhs + roff[b], w.pin + L.rhs + croff[j], (size_t) n * (n + 1) / 2 * sizeof(double));
+   }
+   return HIPSDP_OK;
+}
+
+int rank1_approx_impl(hipsdp_solver* s, const double* y, const int* want, double* lmax, double* vec, double* rhs, int* served)
+{
+   int m = 0, nb = 0;
+   if ( !hs_solver_dims(s, &m, &nb) || y == NULL || lmax == NULL || vec == NULL || rhs == NULL )
+      return HIPSDP_ERR_ARG;
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = (want == NULL || want[b] != 0) ? -1 : 1;
+   std::vector<int> all, ids;
+   HS_CALL( hs_solver_cut_enter_large(s, HS_SYEVX_MAXN, &all) );
+   for (int b : all)
+      if ( want == NULL || want[b] != 0 )
+         ids.push_back(b);
+   if ( ids.empty() )
+      return HIPSDP_OK;
+   std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
+   std::vector<long long> voff((size_t) nb + 1, 0), roff((size_t) nb + 1, 0);
+   for (int b = 0; b < nb; ++b)
+   {
+      const long long n = hs_solver_block_n(s, b);
+      voff[b + 1] = voff[b] + n;
+      roff[b + 1] = roff[b] + n * (n + 1) / 2;
+   }
+   const int total = (int) ids.size();
+   std::vector<long long> job_len((size_t) total);
+   for (int k = 0; k < total; ++k)
+   {
+      const long long n = hs_solver_block_n(s, ids[k]);
+      job_len[k] = r1a_block_len((int) n) + n + n * (n + 1) / 2 + R1A_TABW + SCLR_JOBW + 2;
+   }
+   HS_CALL( hs_chunks_run(job_len.data(), total, SCLR_BUDGET, hs_chunk_env("HIPSDP_RANK1_APPROX_CHUNK"), [&](int start, int end)
+      {
+         const std::vector<int> chunk(ids.begin() + start, ids.begin() + end);
+         return r1a_chunk(s, m, chunk, y, voff, roff, lmax, vec, rhs);
+      }) );
+   if ( served != NULL )
+      for (int b : ids)
+         served[b] = 0;
+   ++g_r1a.calls;
+   return HIPSDP_OK;
+}
+
+}
+
+extern "C" int hipsdp_rank1_approx(hipsdp_solver* s, const double* y, const int* want, double* lmax, double* vec, double* rhs, int* served)
+{
+   return rank1_approx_impl(s, y, want, lmax, vec, rhs, served);
+}
+
+extern "C" int hipsdp_rank1_approx_stats(long long* calls, long long* launches, long long* readbacks)
+{
+   return g_r1a.get(calls, launches, readbacks);
 }

@@ -41,12 +41,35 @@ namespace {
  * reciprocals and the first superdiagonal of U; its second superdiagonal is e[i + 1] in the rows that were swapped and 0 elsewhere:
  * one bit per row in a register). */
 
+/* One more index on a tridiagonal form wavefront 0 has searched already (the several-indices values form: k_lsel_many_small /
+ * k_lsel_many_mid): the multisection of the two bodies below, written down as they have it - ds, es: the matrix scaled to norm 1 and
+ * padded, [lo, hi]: its scaled Gershgorin bracket; 64 shifts per round, one per lane.  Returns the eigenvalue of the unscaled matrix. */
+__device__ __forceinline__ double ei_sel_value(const double* ds, const double* es, int nb, double lo, double hi, int ith, int lane, double rtol,
+   double rfloor, double tnorm)
+{
+   for (int round = 0; round < 16; ++round)
+   {
+      const double x = lo + (hi - lo) * (double) (lane + 1) / 65.0;
+      const int cnt = ei_sturm_count(ds, es, nb, x);   /* eigenvalues below x */
+      const unsigned long long msk = __ballot(cnt >= ith);
+      const int first = msk ? __ffsll((long long) msk) - 1 : 64;
+      const double w = (hi - lo) / 65.0;
+      const double nlo = lo + w * (double) first;
+      const double nhi = (first < 64) ? lo + w * (double) (first + 1) : hi;
+      lo = nlo; hi = nhi;
+      if ( hi - lo <= rtol * fmax(fmax(fabs(lo), fabs(hi)), rfloor) )
+         break;
+   }
+   lo *= tnorm; hi *= tnorm;
+   return 0.5 * (lo + hi);
+}
+
 #define EI_ALL_LDS ((EI_N * EI_N + 2 * EI_N * EI_N) * (int) sizeof(double))
 /* the body (flag == NULL: no sequence number, no system-scope fence - the caller is another kernel of the engine, see
  * k_lmin_exact_multi below; in may then point into LDS) */
 template<bool ALL>
 __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const double* in, double* out,
-   unsigned long long seq, unsigned long long* flag, double mtol = 2e-16)
+   unsigned long long seq, unsigned long long* flag, double mtol = 2e-16, int ith2 = 0, int ith3 = 0)
 {
    extern __shared__ __attribute__((aligned(16))) double ei_dyn[];
    __shared__ double a[EI_N][EI_LD];
@@ -410,6 +433,7 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
    lo *= sinv; hi *= sinv;
+   const double lo0 = lo, hi0 = hi;
    const int nb = (n - 1 + 3) >> 2;
    /* the search ends at two ulps of the eigenvalue (an interval cannot get shorter than one: the test "2e-16 relative" never fired
     * and all 16 rounds ran) or at the caller's relative width; without a caller's width not below half an ulp of the norm */
@@ -435,6 +459,17 @@ __device__ __forceinline__ void d_syevi_small(int n, int ith, int wantvec, const
       out[0] = theta;
       if ( flag == NULL && !wantvec )
          out[1] = 0.5 * (hi - lo);                     /* the eigenvalue lies within this of theta (engine callers: a rigorous bound) */
+   }
+   /* several indices of one reduction (ith2, ith3 > 0; no caller with a flag or a vector sets them): out[2], out[3] */
+   if ( ith2 > 0 )
+   {
+      const double t2 = ei_sel_value(ds, es, nb, lo0, hi0, ith2, lane, rtol, rfloor, tnorm);
+      const double t3 = ei_sel_value(ds, es, nb, lo0, hi0, ith3, lane, rtol, rfloor, tnorm);
+      if ( lane == 0 )
+      {
+         out[2] = t2;
+         out[3] = t3;
+      }
    }
 
    if ( wantvec )
@@ -738,7 +773,7 @@ __device__ __forceinline__ void em_tridiag(int n, const double* __restrict__ in,
 /* the body (flag == NULL: no sequence number, no system-scope fence - the caller is another kernel of the engine, k_onevar_mid below;
  * the wavefronts other than 0 come back right after the reduction, the caller's barrier waits for wavefront 0) */
 __device__ __forceinline__ void d_syevi_mid(int n, int ith, int wantvec, const double* __restrict__ in, double* __restrict__ out,
-   unsigned long long seq, unsigned long long* __restrict__ flag)
+   unsigned long long seq, unsigned long long* __restrict__ flag, int ith2 = 0, int ith3 = 0)
 {
    extern __shared__ __attribute__((aligned(16))) double em_a[];
    __shared__ double vv[EM_N + 8], pp[EM_N], ww[EM_N + 8], tau[EM_N], d[EM_N], e[EM_N], zz[EM_N];
@@ -768,6 +803,7 @@ __device__ __forceinline__ void d_syevi_mid(int n, int ith, int wantvec, const d
    __builtin_amdgcn_s_waitcnt(0xc07f);
    __builtin_amdgcn_wave_barrier();
    lo *= sinv; hi *= sinv;
+   const double lo0 = lo, hi0 = hi;
    const int nb = (n - 1 + 3) >> 2;
    for (int round = 0; round < 16; ++round)
    {
@@ -786,6 +822,18 @@ __device__ __forceinline__ void d_syevi_mid(int n, int ith, int wantvec, const d
    const double theta = 0.5 * (lo + hi);
    if ( lane == 0 )
       out[0] = theta;
+   /* several indices of one reduction (ith2, ith3 > 0; no caller with a flag or a vector sets them): out[2], out[3], by the stopping
+    * rule of hs_td_converged */
+   if ( ith2 > 0 )
+   {
+      const double t2 = ei_sel_value(ds, es, nb, lo0, hi0, ith2, lane, 4.5e-16, 0.25, tnorm);
+      const double t3 = ei_sel_value(ds, es, nb, lo0, hi0, ith3, lane, 4.5e-16, 0.25, tnorm);
+      if ( lane == 0 )
+      {
+         out[2] = t2;
+         out[3] = t3;
+      }
+   }
 
    if ( wantvec )
    {
@@ -2011,6 +2059,30 @@ __global__ void __launch_bounds__(EM_NT) k_lmin_many_mid(int cc, int total, cons
    }
 }
 
+/* the several-indices values form (hipsdp_rank1_check_many): eigenvalues 1, n - 1 and n of every matrix from ONE reduction - the grids
+ * and tables of the two kernels above, blks[b].lam + c lstride takes four doubles: eigenvalue 1 with the bits of k_lmin_many_*, the half
+ * width of its interval (up to 64 rows), eigenvalue max(n - 1, 1), eigenvalue n. */
+__global__ void __launch_bounds__(256) k_lsel_many_small(const hs_ec_job* __restrict__ jobs, const hs_cm_blk* __restrict__ blks)
+{
+   const hs_cm_blk B = blks[blockIdx.y];
+   const long long c = blockIdx.x;
+   const int n = jobs[blockIdx.y].n;
+   d_syevi_small<false>(n, 1, 0, B.Z + c * B.zstride, B.lam + c * B.lstride, 0ULL, NULL, 2e-16, n > 1 ? n - 1 : 1, n);
+}
+
+__global__ void __launch_bounds__(EM_NT) k_lsel_many_mid(int cc, int total, const hs_ec_job* __restrict__ jobs, const hs_cm_blk* __restrict__ blks)
+{
+   for (int job = blockIdx.x; job < total; job += (int) gridDim.x)
+   {
+      const int b = job / cc;
+      const long long c = job - b * cc;
+      const hs_cm_blk B = blks[b];
+      const int n = jobs[b].n;
+      d_syevi_mid(n, 1, 0, B.Z + c * B.zstride, B.lam + c * B.lstride, 0ULL, NULL, n - 1, n);
+      __syncthreads();
+   }
+}
+
 /* dynamic LDS of k_syev_mid: the matrix / the eigenvectors of T, and up to 64 rows the two factor arrays of the inverse iteration */
 static size_t em_all_lds(int n)
 {
@@ -2415,6 +2487,30 @@ int hs_lmin_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const
    static hs_attr_mask attr_mid;
    HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_lmin_many_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
    hipLaunchKernelGGL(k_lmin_many_mid, dim3(grid < total ? grid : total), dim3(EM_NT), (size_t) nmax * (nmax | 1) * sizeof(double), st, cc, total,
+      jobs, blks);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* eigenvalues 1, n - 1 and n (hipsdp_rank1_check_many): the arguments and grids of the two calls above, four doubles per matrix at
+ * blks[b].lam + c lstride.  One launch each. */
+int hs_lsel_many_small(hipStream_t st, int nblk, int cc, int nmax, const hs_ec_job* jobs, const hs_cm_blk* blks)
+{
+   if ( nblk < 1 || cc < 1 || nmax < 1 || nmax > EI_N || jobs == NULL || blks == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_lsel_many_small, dim3(cc, nblk), dim3(256), 0, st, jobs, blks);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+int hs_lsel_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const hs_ec_job* jobs, const hs_cm_blk* blks)
+{
+   if ( nblk < 1 || cc < 1 || nmax <= EI_N || nmax > EM_N || grid < 1 || (long long) nblk * cc > 0x7fffffffLL || jobs == NULL || blks == NULL )
+      return HS_ERR_ARG;
+   const int total = nblk * cc;
+   static hs_attr_mask attr_mid;
+   HS_CALL( hs_func_max_lds(reinterpret_cast<const void*>(&k_lsel_many_mid), EM_N * (EM_N + 1) * (int) sizeof(double), &attr_mid) );
+   hipLaunchKernelGGL(k_lsel_many_mid, dim3(grid < total ? grid : total), dim3(EM_NT), (size_t) nmax * (nmax | 1) * sizeof(double), st, cc, total,
       jobs, blks);
    HS_HIP( hipGetLastError() );
    return HS_OK;

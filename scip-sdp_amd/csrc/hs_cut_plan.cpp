@@ -146,6 +146,15 @@ void hs_cm_layout_make(int m, int cc, int group, int nsv, int nlarge, int blkw, 
    L->len.upload_len = L->res; L->len.pin_len = L->lam; L->len.dev_len = L->blocks + blocks_len;
 }
 
+void hs_r1_layout_make(int m, int cc, int group, int nsv, int nlarge, int blkw, int jobw, int resw, long long blocks_len, hs_cm_layout* L)
+{
+   hs_cm_layout_make(m, cc, group, nsv, nlarge, blkw, jobw, blocks_len, L);
+   L->lam = L->res + even((long long) cc * nsv * resw);
+   L->blocks = L->lam + 4LL * cc * (nsv - nlarge);
+   L->len.res_len = L->lam - L->res;
+   L->len.pin_len = L->lam; L->len.dev_len = L->blocks + blocks_len;
+}
+
 hs_ecl_block hs_ecl_block_make(long long ws_len, long long out_len)
 {
    hs_ecl_block B;

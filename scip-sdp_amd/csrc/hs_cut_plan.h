@@ -149,6 +149,52 @@ static inline long long hs_cm_launches(int any, int small, int mid, int nmax_lar
    return (any ? 1 : 0) + (small ? 1 : 0) + (mid ? 1 : 0) + (nmax_large > 0 ? (long long) nmax_large + 3 : 0) + 1;
 }
 
+/* hipsdp_rank1_check_many (csrc/rank1.hip), ONE CHUNK: the parts and the order of hs_cm_layout, with
+ *    res: [cc][nsv][resw] (resw = 7: eigenvalues 1, n - 1, n | minorev | minordet | minorind, detind as four ints)
+ *    lam: [cc][nsv - nlarge][4] (eigenvalue 1, its half width, eigenvalues n - 1 and n of every matrix of at most 128 rows)
+ * ONE upload carries everything in front of res, ONE read-back takes res. */
+void hs_r1_layout_make(int m, int cc, int group, int nsv, int nlarge, int blkw, int jobw, int resw, long long blocks_len, hs_cm_layout* L);
+/* kernel launches of one chunk of hipsdp_rank1_check_many: a function of the size classes present and of nmax, the chunk's largest block
+ * above 128 rows, alone - Z of all blocks and candidates and the minors launch (with a served block); one values launch per class of at
+ * most 128 rows; for the third class the clearing of the reflector arrays, nmax - 1 columns and ONE values launch (no vector launches:
+ * hs_cm_launches's nmax + 3 becomes nmax + 1); the launch that stores the eigenvalues */
+static inline long long hs_r1_launches(int any, int small, int mid, int nmax_large)
+{
+   return (any ? 3 : 0) + (small ? 1 : 0) + (mid ? 1 : 0) + (nmax_large > 0 ? (long long) nmax_large + 1 : 0);
+}
+
+/* hipsdp_rank1_approx (csrc/rank1.hip), ONE CHUNK of cnt asked-for blocks, nsm of them of at most 128 rows, with vec_len = sum n and
+ * rhs_len = sum n (n + 1) / 2 over the chunk:
+ *    y[m] | result table [cnt][tabw] | decomposition jobs [nsm][ejobw] | tridiagonal jobs [cnt - nsm][jobw] | act[cnt - nsm] (int)
+ *    | res: lmax[cnt] | vec[vec_len] | rhs[rhs_len]
+ *    | blocks (blocks_len doubles: per block Z and its decomposition slab, or the workspace of the tridiagonal form and its output)
+ * every part starts at an even offset.  ONE upload carries everything in front of res, ONE read-back takes res. */
+struct hs_r1a_layout { long long y, tab, ejobs, jobs, act, lmax, vec, rhs, blocks; hs_cut_lens len; };
+static inline void hs_r1a_layout_make(int m, int cnt, int nsm, int tabw, int ejobw, int jobw, long long vec_len, long long rhs_len,
+   long long blocks_len, hs_r1a_layout* L)
+{
+   const long long nlg = cnt - nsm;
+   L->y = 0;
+   L->tab = ((long long) m + 1) & ~1LL;
+   L->ejobs = L->tab + (((long long) cnt * tabw + 1) & ~1LL);
+   L->jobs = L->ejobs + (((long long) nsm * ejobw + 1) & ~1LL);
+   L->act = L->jobs + ((nlg * jobw + 1) & ~1LL);
+   L->lmax = L->act + ((((nlg + 1) / 2) + 1) & ~1LL);
+   L->vec = L->lmax + (((long long) cnt + 1) & ~1LL);
+   L->rhs = L->vec + ((vec_len + 1) & ~1LL);
+   L->blocks = L->rhs + ((rhs_len + 1) & ~1LL);
+   L->len.res_off = L->lmax; L->len.res_len = L->blocks - L->lmax;
+   L->len.upload_len = L->lmax; L->len.pin_len = L->blocks; L->len.dev_len = L->blocks + blocks_len;
+}
+/* kernel launches of one chunk of hipsdp_rank1_approx: a function of the classes present (blocks of at most 128 rows; of 129 .. 512) and
+ * of nmax, the chunk's largest block above 128 rows, alone - Z(y); the three launches of the batched full decomposition; for the second
+ * class the launch that negates Z and clears the reflector arrays, nmax - 1 columns and the 3 selection launches; the launch that stores
+ * lmax, vec and rhs */
+static inline long long hs_r1a_launches(int small, int nmax_large)
+{
+   return 1 + (small ? 3 : 0) + (nmax_large > 0 ? (long long) nmax_large + 3 : 0) + 1;
+}
+
 /* the result arrays as pointers into the buffer that starts at base: the device workspace or its pinned mirror */
 static inline hs_sc_out hs_cut_view(const hs_cut_res& r, double* base)
 {

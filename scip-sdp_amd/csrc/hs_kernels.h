@@ -639,6 +639,32 @@ int hs_lmin_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const
  * n_{nb-1}^2) + (n_0^2 + ... + n_{b-1}^2) for every block of at most 512 rows the call serves (served[b] = 0, else -1 and its part is not
  * written), *launches: the kernel launches issued */
 int hs_check_many_form_z(hipsdp_solver* s, int count, const double* Y, double* Zout, int* served, int* launches);
+/* ---- rank1.hip: the rank-1 constraints for MANY candidate points per call (hipsdp_rank1_check_many; host side: cut_calls.hip) ------------
+ * The tables of check_many.hip, with blks[b].lam + c lstride the FOUR doubles of hs_lsel_many_small / hs_lsel_many_mid (eigi.hip:
+ * eigenvalue 1 with the bits of hs_lmin_many_*, the half width of its interval, eigenvalue max(n - 1, 1), eigenvalue n) for a block of at
+ * most 128 rows, and for a larger one out[HS_SYEVX_OUT_LAM] of its hs_sxm_job, which hs_syevx_many_index (syevx.hip) fills.  The result
+ * block: HS_R1_RESW doubles per (candidate c, block b) at res + (c nblk + b) HS_R1_RESW - eigenvalues 1, n - 1, n | minorev | minordet |
+ * minorind, detind (four ints).
+ *   hs_r1_minors: grid (cc, nblk), ONE launch: both scans over the 2 x 2 principal minors of every Z - which must still be intact, so in
+ *                 front of hs_syevx_many_cols; writes [3 .. 6] of a row.
+ *   hs_r1_result: grid (cc), ONE launch, the last of a chunk: [0 .. 2] of every row (n = 1: value, 0.0, value; n = 2: eigenvalue 1 twice).
+ *   hs_r1_minors_unit: the scans on `count` matrices, matrix k of n[k] rows at Z + off[k] (device arrays), o[2 k]: minorev, minordet,
+ *                 ind[4 k]: minorind, detind. */
+#define HS_R1_RESW 7
+int hs_lsel_many_small(hipStream_t st, int nblk, int cc, int nmax, const hs_ec_job* jobs, const hs_cm_blk* blks);
+int hs_lsel_many_mid(hipStream_t st, int nblk, int cc, int nmax, int grid, const hs_ec_job* jobs, const hs_cm_blk* blks);
+int hs_syevx_many_index(hipStream_t st, int count, int nmax, const hs_sxm_job* djobs, const int* dact);
+int hs_r1_minors(hipStream_t st, int nblk, int cc, int nmax, double feastol, const hs_ec_job* jobs, const hs_cm_blk* blks, double* res);
+int hs_r1_result(hipStream_t st, int nblk, int cc, const hs_ec_job* jobs, const hs_cm_blk* blks, double* res);
+int hs_r1_minors_unit(hipStream_t st, int count, int nmax, const int* n, const long long* off, const double* Z, double feastol, double* o, int* ind);
+/* hipsdp_rank1_approx: row j of the table belongs to jobs[j] (hs_ec_job: n, the storage form, A_0) - lam[0]: the eigenvalue, taken times
+ * sign (-1: it is eigenvalue 1 of -Z); vec: its unit vector; lmax, vec and rhs of the block go to res_lmax[j], res_vec + voff, res_rhs + roff.
+ *   hs_r1_negate: grid (tiles, count), ONE launch: A = -A and R = 0 of every job of the batched tridiagonal path (Z was formed into A).
+ *   hs_r1_rhs:    grid (tiles, count), ONE launch: rhs[i (i + 1) / 2 + k] = A_0[i][k] + (lam v_i) v_k, k <= i, every operation rounded on
+ *                 its own; A_0 from row 0 of dense rows or packed triangles, or the dense constant matrix of a block kept as nonzeros. */
+struct hs_r1a_job { const double* lam; const double* vec; double sign; long long voff, roff; };
+int hs_r1_negate(hipStream_t st, int count, int nmax, const hs_sxm_job* sx);
+int hs_r1_rhs(hipStream_t st, int count, int nmax, const hs_ec_job* jobs, const hs_r1a_job* tab, double* res_lmax, double* res_vec, double* res_rhs);
 /* ipm.hip: the LP rows of a solver - 0 (nothing set) for a solver with a communicator or sharded matrices, else 1, the number of rows and
  * the device array q x (m + 1) whose column 0 is c */
 int hs_solver_lp_rows(const hipsdp_solver* s, int* q, const double** Dext);

@@ -503,6 +503,9 @@ __global__ void __launch_bounds__(64) k_syevx_back_many(const hs_sxm_job* __rest
 /* ---- the BELOW selection for many matrices per launch (k_syevx_*_below_many; host side: hs_syevx_many_below further down): wrappers of
  * the same kind around the bodies of stages 2 to 4, kept in a file of their own */
 #include "hs_syevx_below_many.h"
+/* ---- the several-indices values launch for many matrices (k_syevx_values_index_many; host side: hs_syevx_many_index further down): a
+ * wrapper of the same kind around the body of stage 2 */
+#include "hs_syevx_index_many.h"
 
 }
 
@@ -551,6 +554,17 @@ int hs_syevx_many_select(hipStream_t st, int count, int nmax, int both, const hs
    hipLaunchKernelGGL(k_syevx_values_many, dim3(count, both ? 2 : 1), dim3(SX_VT), 0, st, djobs, dact);
    hipLaunchKernelGGL(k_syevx_tvec_many, dim3(count), dim3(SX_VT), (size_t) (nmax | 1) * sizeof(double), st, djobs, dact);
    hipLaunchKernelGGL(k_syevx_back_many, dim3(count), dim3(64), 0, st, djobs, dact);
+   HS_HIP( hipGetLastError() );
+   return HS_OK;
+}
+
+/* ONE launch, values only: eigenvalue 1 of every matrix with act != 0 to out[HS_SYEVX_OUT_LAM], eigenvalues n - 1 and n to
+ * out2[HS_SYEVX_OUT_LAM], out2[HS_SYEVX_OUT_LAM + 1] */
+int hs_syevx_many_index(hipStream_t st, int count, int nmax, const hs_sxm_job* djobs, const int* dact)
+{
+   if ( count < 1 || nmax < 2 || nmax > SX_N || djobs == NULL || dact == NULL )
+      return HS_ERR_ARG;
+   hipLaunchKernelGGL(k_syevx_values_index_many, dim3(count, 2), dim3(SX_VT), 0, st, djobs, dact);
    HS_HIP( hipGetLastError() );
    return HS_OK;
 }

@@ -2552,3 +2552,131 @@ extern "C" int hipsdp_pass_a_unit(int device, int R, long long E, long long lda,
    HS_CALL( rc );
    return dO.down(out, (long long) nv * R);
 }
+
+/* k_r1_minors's scans (hs_r1_minors_unit, csrc/rank1.hip) on `count` host matrices, matrix k of n[k] rows (1 .. 512), one behind the
+ * other in Z: minorev[k], minorind[2 k], minordet[k], detind[2 k] as hipsdp_rank1_check_many returns them for one (candidate, block) */
+extern "C" int hipsdp_rank1_minors_unit(int device, int count, const int* n, const double* Z, double feastol, double* minorev, int* minorind,
+   double* minordet, int* detind)
+{
+   if ( count < 1 || n == NULL || Z == NULL || !(feastol >= 0.0) || minorev == NULL || minorind == NULL || minordet == NULL || detind == NULL )
+      return HIPSDP_ERR_ARG;
+   std::vector<long long> off((size_t) count + 1, 0);
+   int nmax = 0;
+   for (int k = 0; k < count; ++k)
+   {
+      if ( n[k] < 1 || n[k] > HS_SYEVX_MAXN )
+         return HIPSDP_ERR_ARG;
+      off[k + 1] = off[k] + (long long) n[k] * n[k];
+      nmax = std::max(nmax, n[k]);
+   }
+   HS_CALL( pick_device(device) );
+   DevBuf dZ, dn, doff, dout, dind;
+   HS_CALL( dZ.alloc(off[count]) ); HS_CALL( dn.alloc(((long long) count + 1) / 2) ); HS_CALL( doff.alloc(count) );
+   HS_CALL( dout.alloc(2LL * count) ); HS_CALL( dind.alloc(2LL * count) );
+   HS_CALL( dZ.up(Z, off[count]) );
+   HS_HIP( hipMemcpy(dn.p, n, (size_t) count * sizeof(int), hipMemcpyHostToDevice) );
+   HS_HIP( hipMemcpy(doff.p, off.data(), (size_t) count * sizeof(long long), hipMemcpyHostToDevice) );
+   HS_CALL( hs_r1_minors_unit(0, count, nmax, reinterpret_cast<const int*>(dn.p), reinterpret_cast<const long long*>(doff.p), dZ.p, feastol, dout.p,
+         reinterpret_cast<int*>(dind.p)) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> o(2 * (size_t) count);
+   std::vector<int> ind(4 * (size_t) count);
+   HS_CALL( dout.down(o.data(), 2LL * count) );
+   HS_HIP( hipMemcpy(ind.data(), dind.p, ind.size() * sizeof(int), hipMemcpyDeviceToHost) );
+   for (int k = 0; k < count; ++k)
+   {
+      minorev[k] = o[2 * (size_t) k]; minordet[k] = o[2 * (size_t) k + 1];
+      minorind[2 * k] = ind[4 * (size_t) k]; minorind[2 * k + 1] = ind[4 * (size_t) k + 1];
+      detind[2 * k] = ind[4 * (size_t) k + 2]; detind[2 * k + 1] = ind[4 * (size_t) k + 3];
+   }
+   return HIPSDP_OK;
+}
+
+/* the three-index values kernels of hipsdp_rank1_check_many on `count` host matrices (n[k] rows, 1 .. 512, one behind the other in Z):
+ * hs_lsel_many_small up to 64 rows, hs_lsel_many_mid up to 128, above that hs_ecl_clear, hs_syevx_many_cols and hs_syevx_many_index; then
+ * hs_r1_result.  Every matrix is a block of its own with one candidate.  lam[3 k ..]: eigenvalues 1, n - 1, n of matrix k. */
+extern "C" int hipsdp_lsel_many_unit(int device, int count, const int* n, const double* Z, double* lam)
+{
+   if ( count < 1 || count > 65535 || n == NULL || Z == NULL || lam == NULL )
+      return HIPSDP_ERR_ARG;
+   std::vector<long long> off((size_t) count + 1, 0);
+   long long ws_len = 0;
+   for (int k = 0; k < count; ++k)
+   {
+      if ( n[k] < 1 || n[k] > HS_SYEVX_MAXN )
+         return HIPSDP_ERR_ARG;
+      off[k + 1] = off[k] + (long long) n[k] * n[k];
+   }
+   /* the tables in the order of the classes */
+   std::vector<int> order;
+   int cnt[3] = {0, 0, 0}, top[3] = {0, 0, 0};
+   for (int cls = 0; cls < 3; ++cls)
+      for (int k = 0; k < count; ++k)
+         if ( (n[k] <= 64 ? 0 : (n[k] <= HS_SC_MAXN ? 1 : 2)) == cls )
+         {
+            order.push_back(k);
+            ++cnt[cls];
+            top[cls] = std::max(top[cls], n[k]);
+            if ( cls == 2 )
+               ws_len += (((long long) hs_syevx_ws(n[k]) + 1) & ~1LL) + HS_SXM_OUT(n[k]);
+         }
+   HS_CALL( pick_device(device) );
+   const long long jobw = (long long) (sizeof(hs_ec_job) / sizeof(double)), blkw = (long long) (sizeof(hs_cm_blk) / sizeof(double)),
+      sxw = (long long) (sizeof(hs_sxm_job) / sizeof(double));
+   DevBuf dZ, dws, dlam, djobs, dblks, dsx, dact, dres;
+   HS_CALL( dZ.alloc(off[count]) ); HS_CALL( dws.alloc(ws_len) ); HS_CALL( dlam.alloc(4LL * count) );
+   HS_CALL( djobs.alloc(jobw * count) ); HS_CALL( dblks.alloc(blkw * count) ); HS_CALL( dsx.alloc(sxw * cnt[2]) );
+   HS_CALL( dact.alloc(((long long) cnt[2] + 1) / 2) ); HS_CALL( dres.alloc((long long) HS_R1_RESW * count) );
+   HS_CALL( dZ.up(Z, off[count]) );
+   std::vector<hs_ec_job> jobs((size_t) count);
+   std::vector<hs_cm_blk> blks((size_t) count);
+   std::vector<hs_sxm_job> sx((size_t) cnt[2]);
+   std::vector<int> act((size_t) cnt[2], HS_SXM_ACTIVE);
+   memset(jobs.data(), 0, jobs.size() * sizeof(hs_ec_job));
+   long long wpos = 0;
+   for (int t = 0; t < count; ++t)
+   {
+      const int k = order[t], nk = n[k];
+      jobs[t].n = nk; jobs[t].blk = t;
+      blks[t].Z = dZ.p + off[k]; blks[t].zstride = 0;
+      blks[t].lam = dlam.p + 4LL * t; blks[t].lstride = 0;
+      if ( nk <= HS_SC_MAXN )
+         continue;
+      const int j = t - cnt[0] - cnt[1];
+      double* ws = dws.p + wpos;
+      double* out = ws + (((long long) hs_syevx_ws(nk) + 1) & ~1LL);
+      wpos += (((long long) hs_syevx_ws(nk) + 1) & ~1LL) + HS_SXM_OUT(nk);
+      HS_CALL( hs_syevx_many_job(nk, ws, out, &sx[j]) );
+      HS_HIP( hipMemcpy(sx[j].A, dZ.p + off[k], (size_t) nk * nk * sizeof(double), hipMemcpyDeviceToDevice) );
+      blks[t].lam = out + HS_SYEVX_OUT_LAM;
+   }
+   HS_HIP( hipMemcpy(djobs.p, jobs.data(), jobs.size() * sizeof(hs_ec_job), hipMemcpyHostToDevice) );
+   HS_HIP( hipMemcpy(dblks.p, blks.data(), blks.size() * sizeof(hs_cm_blk), hipMemcpyHostToDevice) );
+   const hs_ec_job* dj = reinterpret_cast<const hs_ec_job*>(djobs.p);
+   const hs_cm_blk* db = reinterpret_cast<const hs_cm_blk*>(dblks.p);
+   if ( cnt[0] > 0 )
+      HS_CALL( hs_lsel_many_small(0, cnt[0], 1, top[0], dj, db) );
+   if ( cnt[1] > 0 )
+   {
+      const int cus = hs_device_cus();
+      HS_CALL( hs_lsel_many_mid(0, cnt[1], 1, top[1], cus > 0 ? cus : 256, dj + cnt[0], db + cnt[0]) );
+   }
+   if ( cnt[2] > 0 )
+   {
+      HS_HIP( hipMemcpy(dsx.p, sx.data(), sx.size() * sizeof(hs_sxm_job), hipMemcpyHostToDevice) );
+      HS_HIP( hipMemcpy(dact.p, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice) );
+      const hs_sxm_job* ds = reinterpret_cast<const hs_sxm_job*>(dsx.p);
+      const int* da = reinterpret_cast<const int*>(dact.p);
+      HS_CALL( hs_ecl_clear(0, cnt[2], ds) );
+      HS_CALL( hs_syevx_many_cols(0, cnt[2], top[2], hs_syevx_many_cap(cnt[2]), ds, da) );
+      HS_CALL( hs_syevx_many_index(0, cnt[2], top[2], ds, da) );
+   }
+   HS_CALL( hs_r1_result(0, count, 1, dj, db, dres.p) );
+   HS_HIP( hipDeviceSynchronize() );
+   std::vector<double> res((size_t) HS_R1_RESW * count);
+   HS_CALL( dres.down(res.data(), (long long) res.size()) );
+   for (int t = 0; t < count; ++t)
+      for (int i = 0; i < 3; ++i)
+         lam[3 * (size_t) order[t] + i] = res[(size_t) HS_R1_RESW * t + i];
+   return HIPSDP_OK;
+}
