@@ -66,6 +66,13 @@ def _chk(rc, what):
         raise RuntimeError("%s failed: rc=%d (%s)" % (what, rc, lib().hipsdp_last_error().decode()))
 
 
+def _stats3(name, which=None):
+    """the process totals (calls, launches, read-backs) of the C getter `name`; which: the library loader that is asked (None: lib)"""
+    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _chk(getattr((which or lib)(), name)(C.byref(calls), C.byref(launches), C.byref(readbacks)), name)
+    return calls.value, launches.value, readbacks.value
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -814,16 +821,12 @@ ONEVAR_EXTREMES, ONEVAR_DONE = 2, 6                                             
 
 def onevar_bounds_stats():
     """process totals of hipsdp_onevar_bounds: (calls that served their block, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_onevar_bounds_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_onevar_bounds_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_onevar_bounds_stats")
 
 
 def onevar_bounds_all_stats():
     """process totals of hipsdp_onevar_bounds_all: (calls that served a job, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_onevar_bounds_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_onevar_bounds_all_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_onevar_bounds_all_stats")
 
 
 def onevar_all_unit(Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, mid_cap=256, device=0):
@@ -853,9 +856,7 @@ def onevar_all_unit(Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, mid_cap
 
 def onevar_bounds_large_stats():
     """process totals of hipsdp_onevar_bounds_large: (calls that served a job, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_onevar_bounds_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_onevar_bounds_large_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_onevar_bounds_large_stats")
 
 
 def onevar_large_unit(Z, A, shift, lb, ub, feastol, kind=None, maxevals=0, wg_cap=0, chunk=0, device=0, with_rounds=False):
@@ -913,16 +914,12 @@ class SparsecutOpts(C.Structure):
 
 def sparsecuts_all_stats():
     """process totals of hipsdp_sparsecuts_all: (calls, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_sparsecuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_all_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_sparsecuts_all_stats")
 
 
 def sparsecuts_stats():
     """process totals of hipsdp_sparsecuts: (calls, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_sparsecuts_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_sparsecuts_stats")
 
 
 SC_RECOMPUTE_SPARSEEV, SC_RECOMPUTE_INITIAL, SC_EXACTTRANS = 1, 2, 4      # HIPSDP_SC_*
@@ -931,17 +928,13 @@ SC_RECOMPUTE_SPARSEEV, SC_RECOMPUTE_INITIAL, SC_EXACTTRANS = 1, 2, 4      # HIPS
 def sparsecuts_ex_stats():
     """process totals of hipsdp_sparsecuts_all_ex / hipsdp_sparsecuts_ex with a switch set: (calls, kernel launches issued,
     device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_sparsecuts_ex_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_ex_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_sparsecuts_ex_stats")
 
 
 def sparsecuts_all_large_stats():
     """process totals of hipsdp_sparsecuts_all_large: (calls that served a block, kernel launches issued, device->host
     synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_sparsecuts_all_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_sparsecuts_all_large_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_sparsecuts_all_large_stats")
 
 
 def sparsecuts_large_unit(n, Z, v0, maxeig, size, feastol, maxcuts, convtol=0, maxit=0, device=0):
@@ -991,41 +984,30 @@ def sparsecuts_unit(ns, Zs, v0s, maxeig, sizes, feastol, maxcuts, convtol=0, max
 
 def eigencuts_all_stats():
     """process totals of hipsdp_eigencuts_all: (calls, kernel launches issued for batched blocks, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_eigencuts_all_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_eigencuts_all_stats")
 
 
 def eigencuts_all_large_stats():
     """process totals of hipsdp_eigencuts_all_large: (calls that served a block, kernel launches issued, device->host
     synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_eigencuts_all_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_eigencuts_all_large_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_eigencuts_all_large_stats")
 
 
 def check_y_many_stats(which=None):
     """process totals of hipsdp_check_y_many: (calls that launched something, kernel launches issued, device->host synchronisations);
     which: the library loader whose copy of the engine is asked (lib, the default, or ulib)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk((which or lib)().hipsdp_check_y_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_check_y_many_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_check_y_many_stats", which)
 
 
 def rank1_check_many_stats(which=None):
     """process totals of hipsdp_rank1_check_many: (calls that launched something, kernel launches issued, device->host
     synchronisations); which: the library loader whose copy of the engine is asked (lib, the default, or ulib)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk((which or lib)().hipsdp_rank1_check_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)),
-         "hipsdp_rank1_check_many_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_rank1_check_many_stats", which)
 
 
 def rank1_approx_stats(which=None):
     """process totals of hipsdp_rank1_approx: (calls that launched something, kernel launches issued, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk((which or lib)().hipsdp_rank1_approx_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_rank1_approx_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_rank1_approx_stats", which)
 
 
 def _mats_cat(mats):
@@ -1068,9 +1050,7 @@ class RoundingOut(C.Structure):
 def rounding_stats(which=None):
     """process totals of hipsdp_rounding_frame and hipsdp_rounding_recombine together: (calls that launched something, kernel launches
     issued, device->host synchronisations); which: lib (default) or ulib"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk((which or lib)().hipsdp_rounding_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_rounding_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_rounding_stats", which)
 
 
 def rounding_coefs_unit(V, A, form, nonzeros=None, device=0):
@@ -1922,9 +1902,7 @@ def psd_project_many(jobs, epsilon=1e-9, mode=0, device=0):
 
 def psd_project_many_stats():
     """process totals of hipsdp_psd_project_many: (calls, kernel launches issued for batched jobs, device->host synchronisations)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_psd_project_many_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)), "hipsdp_psd_project_many_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_psd_project_many_stats")
 
 
 def psd_project_many_large(jobs, epsilon=1e-9, mode=0, device=0):
@@ -1952,10 +1930,7 @@ def psd_project_many_large(jobs, epsilon=1e-9, mode=0, device=0):
 
 def psd_project_many_large_stats():
     """process totals of hipsdp_psd_project_many_large: (calls, kernel launches, device->host synchronisations - one per chunk)"""
-    calls, launches, readbacks = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    _chk(lib().hipsdp_psd_project_many_large_stats(C.byref(calls), C.byref(launches), C.byref(readbacks)),
-         "hipsdp_psd_project_many_large_stats")
-    return calls.value, launches.value, readbacks.value
+    return _stats3("hipsdp_psd_project_many_large_stats")
 
 
 def syevr_many_unit(mats, cap, device=0):

@@ -1,15 +1,25 @@
-/* cut_calls.hip - the host side of the cut calls that serve many blocks, or one large block, in a fixed number of launches:
- * hipsdp_eigencuts_all (kernels: eigcuts.hip, many-forms of the decompositions: eigi.hip), hipsdp_sparsecuts_all and hipsdp_sparsecuts
- * (sparsecuts.hip, sparsecuts_large.hip), their _ex forms with the reference's refinement switches (sparsecuts_rounds.hip), and
- * hipsdp_sparsecuts_all_large, the partner of hipsdp_sparsecuts_all_ex for the blocks of 129 .. 512 rows (sparsecuts_large_rounds.hip),
- * and hipsdp_eigencuts_all_large, the partner of hipsdp_eigencuts_all for those blocks (eigcuts_large.hip).  At the end of the file:
- * hipsdp_check_y_many, the feasibility check of many candidate points per call (check_many.hip), and hipsdp_rounding_frame /
- * hipsdp_rounding_recombine, the two device stages of the primal rounding problem (rounding.hip; planning: hs_round_plan.h).
- *
+/* cut_calls.hip - the host side of the calls that serve many blocks, many candidate points or one large block of a loaded solver in a
+ * fixed number of launches.  Section by section:
+ *   1. what all calls share: CutDst and the copy-out of a block's cuts, block_sums (prefix sums of f(n) over blocks), the tail
+ *      chunk_readback (cut_readback: with the view of a cut layout), sxm_job (a matrix of 129 .. 512 rows on the tridiagonal path);
+ *   2. the sparse cuts of blocks of at most 128 rows, hipsdp_sparsecuts_all and hipsdp_sparsecuts with their _ex forms (the reference's
+ *      refinement switches): sc_begin / scx_rounds / sc_finish (sparsecuts.hip, sparsecuts_rounds.hip), and hipsdp_sparsecuts of one
+ *      block of 129 .. 512 rows (sparsecuts_large.hip);
+ *   3. the cuts of all blocks of 129 .. 512 rows, hipsdp_sparsecuts_all_large (sparsecuts_large_rounds.hip) and
+ *      hipsdp_eigencuts_all_large (eigcuts_large.hip): large_served, the chunk frame large_begin / large_end, sclr_chunk, ecl_chunk;
+ *   4. hipsdp_eigencuts_all (eigcuts.hip, the many-forms of the decompositions: eigi.hip) and the extern "C" entries of 2. and 3.;
+ *   5. the calls over candidate points, hipsdp_check_y_many (check_many.hip) and, behind 6., hipsdp_rank1_check_many (rank1.hip): the
+ *      entry cm_enter, cm_candidate_len, the head of a chunk cm_begin (the caller names the layout), the eigenvalue stage
+ *      cm_eigenvalues, the chunks cm_chunk and r1_chunk, the unit entry hs_check_many_form_z;
+ *   6. hipsdp_rounding_frame / hipsdp_rounding_recombine, the two device stages of the primal rounding problem: rf_chunk, rf2_chunk
+ *      (rounding.hip, psd_many.hip, psd_large.hip; planning: hs_round_plan.h);
+ *   7. hipsdp_rank1_approx: r1a_chunk (rank1.hip).
  * Every call is the same choreography: argument checks (before the device is looked at), a layout of the solver's cut workspace
- * (hs_cut_plan.h), ONE upload of  y | sizes  through its pinned mirror, the launches, ONE read-back of the result arrays, and the
- * copy-out of every block to the caller's arrays.  The solver itself is seen through the hs_solver_* functions of hs_kernels.h alone:
- * they enter a call, grow the workspace and keep its job tables on the device (ipm.hip). */
+ * (hs_cut_plan.h), ONE upload through its pinned mirror, the launches, ONE read-back of the result range, the copy-out to the caller's
+ * arrays; a call that may outgrow the budget does this once per chunk (hs_chunks_run, hs_chunks.h).  A new call uses the shared pieces
+ * instead of copying a neighbour: large_begin / large_end for cuts of blocks of 129 .. 512 rows; cm_enter, cm_begin and cm_eigenvalues
+ * for candidate points; sxm_job, block_sums and chunk_readback everywhere.  The solver itself is seen through the hs_solver_* functions
+ * of hs_kernels.h alone: they enter a call, grow the workspace and keep its job tables on the device (ipm.hip). */
 #include "hs_common.h"
 #include "hs_kernels.h"
 #include "hs_cut_plan.h"
@@ -59,6 +69,19 @@ std::vector<long long> cut_vecoff(const hipsdp_solver* s, int nb, int maxcuts, c
    return vecoff;
 }
 
+/* sum[j] = f(n_0) + .. + f(n_{j-1}), [count]: the total - n_j: the rows of block ids[j] of the solver, of block j with ids == NULL */
+template <class F>
+std::vector<long long> block_sums(const hipsdp_solver* s, int count, const int* ids, F f)
+{
+   std::vector<long long> sum((size_t) count + 1, 0);
+   for (int j = 0; j < count; ++j)
+      sum[j + 1] = sum[j] + f(hs_solver_block_n(s, ids != NULL ? ids[j] : j));
+   return sum;
+}
+long long n_rows(int n) { return n; }
+long long n_full(int n) { return (long long) n * n; }
+long long n_tri(int n) { return (long long) n * (n + 1) / 2; }
+
 /* Z and the decomposition workspace of every block of a round */
 long long ec_slab_len(const hipsdp_solver* s, const std::vector<int>& ids)
 {
@@ -95,14 +118,33 @@ int cut_block_out(const hs_sc_out& h, int b, int k, int maxcuts, long long voff,
    return HIPSDP_OK;
 }
 
-/* the tail of every call and chunk: ONE read-back of the result range, the launches and the read-back booked; h: its pinned view */
-int cut_readback(const hs_solver_cut_ws& w, const hs_cut_res& r, const hs_cut_lens& len, int launches, CutStats* stats, hs_sc_out* h)
+/* the tail of every call and chunk: ONE read-back of the result range to the pinned mirror, the launches and the read-back booked */
+int chunk_readback(const hs_solver_cut_ws& w, const hs_cut_lens& len, int launches, CutStats* stats)
 {
    HS_HIP( hipMemcpyAsync(w.pin + len.res_off, w.dev + len.res_off, (size_t) len.res_len * sizeof(double), hipMemcpyDeviceToHost, w.stream) );
    HS_HIP( hipStreamSynchronize(w.stream) );
    stats->launches += launches;
    stats->readbacks += 1;
+   return HS_OK;
+}
+
+/* the same where the result range holds the arrays of a cut layout; h: their pinned view */
+int cut_readback(const hs_solver_cut_ws& w, const hs_cut_res& r, const hs_cut_lens& len, int launches, CutStats* stats, hs_sc_out* h)
+{
+   HS_CALL( chunk_readback(w, len, launches, stats) );
    *h = hs_cut_view(r, w.pin);
+   return HS_OK;
+}
+
+/* The job of a matrix of n rows (129 .. 512) on the batched tridiagonal path and its act word: `make` (hs_syevx_many_job,
+ * hs_syevx_many_below_job) fills J from the matrix's workspace and selection output.  The caller has Z formed into the head of the
+ * workspace, so that is where the column launches must read their matrix (hs_sxm_job.A). */
+int sxm_job(int (*make)(int, double*, double*, hs_sxm_job*), int n, double* ws, double* out, int act, hs_sxm_job* J, int* hact)
+{
+   HS_CALL( make(n, ws, out, J) );
+   if ( J->A != ws )
+      return HIPSDP_ERR_NUMERIC;
+   *hact = act;
    return HS_OK;
 }
 
@@ -677,11 +719,8 @@ int ecl_chunk(hipsdp_solver* s, int m, int nb, const std::vector<int>& ids, cons
    for (int j = 0; j < cnt; ++j)
    {
       double* base = w.dev + R.start[j];
-      HS_CALL( hs_syevx_many_below_job(hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, &hsx[j]) );
-      if ( hsx[j].A != base + B[j].ws )
-         return HIPSDP_ERR_NUMERIC;
+      HS_CALL( sxm_job(hs_syevx_many_below_job, hs_solver_block_n(s, ids[j]), base + B[j].ws, base + B[j].out, HS_SXM_ACTIVE, &hsx[j], &hact[j]) );
       hvo[j] = R.vecoff[ids[j]];
-      hact[j] = HS_SXM_ACTIVE;
    }
    HS_HIP( hipMemcpyAsync(w.dev, w.pin, (size_t) L.len.upload_len * sizeof(double), hipMemcpyHostToDevice, st) );
 
@@ -912,9 +951,35 @@ int cm_served(hipsdp_solver* s, CmBlocks* P)
 hs_ecl_block cm_large_block(int n) { return hs_ecl_block_make((long long) hs_syevx_ws(n), HS_SXM_OUT(n)); }
 long long cm_mat_len(int n) { return n <= HS_SC_MAXN ? hs_cut_mat_len(n) : cm_large_block(n).len; }
 
+/* The entry of a call over candidate points, behind its argument checks: served[nb] (may be NULL) = -1, then 0 for the blocks P that
+ * the call serves; q, Dext: the solver's LP rows.  *go = false: a communicator or sharded matrices - nothing is served, nothing to do. */
+int cm_enter(hipsdp_solver* s, int nb, int* served, CmBlocks* P, int* q, const double** Dext, bool* go)
+{
+   if ( served != NULL )
+      for (int b = 0; b < nb; ++b)
+         served[b] = -1;
+   *go = hs_solver_lp_rows(s, q, Dext) != 0;
+   if ( !*go )
+      return HIPSDP_OK;
+   HS_CALL( cm_served(s, P) );
+   if ( served != NULL )
+      for (int b : P->ids)
+         served[b] = 0;
+   return HIPSDP_OK;
+}
+
+/* what a candidate takes of the workspace: its point, its matrices, its jobs, and per served block lamw doubles of eigenvalues and resw
+ * doubles of the result */
+long long cm_candidate_len(const hipsdp_solver* s, int m, const CmBlocks& P, int lamw, int resw)
+{
+   long long per = (long long) m + (long long) P.nlarge * (SCLR_JOBW + 1) + (long long) (lamw + resw) * P.ids.size();
+   for (int b : P.ids)
+      per += cm_mat_len(hs_solver_block_n(s, b));
+   return per;
+}
+
 /* a chunk between its layout and its launches: the workspace with the solver's table of the served blocks (w.djobs), the layout, where
- * the matrices of every served block start.  lamw: doubles per matrix of at most 128 rows in L.lam - 2: hipsdp_check_y_many's layout, 4:
- * that of hipsdp_rank1_check_many (hs_r1_layout_make) */
+ * the matrices of every served block start */
 struct CmRun
 {
    hs_solver_cut_ws w;
@@ -923,10 +988,16 @@ struct CmRun
    int launches;
 };
 
-/* The head of the chunk over the candidates Y[0 .. cc) (rows of m): the layout - with_eig = false: every block's matrices are plain
+/* the layout of hipsdp_check_y_many, as cm_begin takes it */
+void cm_layout(int m, int cc, int nsv, int nlarge, long long blocks_len, hs_cm_layout* L)
+{ hs_cm_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, blocks_len, L); }
+
+/* The head of the chunk over the candidates Y[0 .. cc) (rows of m): the layout - make(m, cc, nsv, nlarge, blocks_len, L): the call's
+ * (cm_layout, r1_layout), with lamw doubles per matrix of at most 128 rows in L.lam; with_eig = false: every block's matrices are plain
  * n x n arrays and nothing of the eigenvalue path is laid out (the unit entry) -, the workspace, Yg, the block table and, for the
  * blocks of 129 .. 512 rows, the jobs of the batched tridiagonal path in the pinned mirror, the ONE upload, Z of every (candidate, block). */
-int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y, bool with_eig, CmRun* R, int lamw = 2)
+int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y, bool with_eig, int lamw,
+   void (*make)(int, int, int, int, long long, hs_cm_layout*), CmRun* R)
 {
    const int nsv = (int) P.ids.size(), nlarge = with_eig ? P.nlarge : 0, nsm = nsv - nlarge;
    R->start.resize((size_t) nsv);
@@ -939,10 +1010,7 @@ int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y
       blocks_len += (long long) cc * (k < nsm ? hs_cut_mat_len(n) : cm_large_block(n).len);
    }
    hs_cm_layout& L = R->L;
-   if ( lamw == 2 )
-      hs_cm_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, blocks_len, &L);
-   else
-      hs_r1_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, HS_R1_RESW, blocks_len, &L);
+   make(m, cc, nsv, nlarge, blocks_len, &L);
    HS_CALL( hs_solver_cut_blocks(s, P.ids, std::vector<long long>((size_t) nsv, 0), L.len.dev_len, L.len.pin_len, &R->w) );
    const hs_solver_cut_ws& w = R->w;
    /* Yg[g][i][k] = Y[g HS_CM_G + k][i], zeros behind the last candidate */
@@ -975,10 +1043,7 @@ int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y
       {
          const size_t j = (size_t) (k - nsm) * cc + c;
          double* jb = base + (long long) c * E.len;
-         HS_CALL( hs_syevx_many_job(n, jb + E.ws, jb + E.out, &hsx[j]) );
-         if ( hsx[j].A != jb + E.ws )
-            return HIPSDP_ERR_NUMERIC;
-         hact[j] = HS_SXM_ACTIVE;
+         HS_CALL( sxm_job(hs_syevx_many_job, n, jb + E.ws, jb + E.out, HS_SXM_ACTIVE, &hsx[j], &hact[j]) );
       }
       B.Z = base + E.ws; B.zstride = E.len;
       B.lam = base + E.out + HS_SYEVX_OUT_LAM; B.lstride = E.len;
@@ -992,47 +1057,57 @@ int cm_begin(hipsdp_solver* s, int m, const CmBlocks& P, int cc, const double* Y
    return HS_OK;
 }
 
+/* The eigenvalue stage of a chunk of cc candidates, class by class: `small` and `mid` (hs_lmin_many_*, hs_lsel_many_*), one launch
+ * each, for the blocks of at most 64 and of 65 .. 128 rows; for those of 129 .. 512 rows the clearing of the reflector arrays, the
+ * nmax_large - 1 column launches and close(st, jobs, nmax_large, dsx, dact), which takes close_launches launches. */
+template <class Close>
+int cm_eigenvalues(const CmBlocks& P, int cc, int (*small)(hipStream_t, int, int, int, const hs_ec_job*, const hs_cm_blk*),
+   int (*mid)(hipStream_t, int, int, int, int, const hs_ec_job*, const hs_cm_blk*), Close close, int close_launches, CmRun* R)
+{
+   const hs_solver_cut_ws& w = R->w;
+   hipStream_t st = w.stream;
+   const hs_cm_blk* db = reinterpret_cast<const hs_cm_blk*>(w.dev + R->L.blks);
+   if ( P.nsmall > 0 )
+   {
+      HS_CALL( small(st, P.nsmall, cc, P.nmax_small, w.djobs, db) );
+      ++R->launches;
+   }
+   if ( P.nmid > 0 )
+   {
+      const int cus = hs_device_cus();
+      HS_CALL( mid(st, P.nmid, cc, P.nmax_mid, cus > 0 ? cus : 256, w.djobs + P.nsmall, db + P.nsmall) );
+      ++R->launches;
+   }
+   if ( P.nlarge > 0 )
+   {
+      const int jobs = P.nlarge * cc;
+      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + R->L.jobs);
+      const int* dact = reinterpret_cast<const int*>(w.dev + R->L.act);
+      HS_CALL( hs_ecl_clear(st, jobs, dsx) );
+      HS_CALL( hs_syevx_many_cols(st, jobs, P.nmax_large, hs_syevx_many_cap(jobs), dsx, dact) );
+      HS_CALL( close(st, jobs, P.nmax_large, dsx, dact) );
+      R->launches += 1 + (P.nmax_large - 1) + close_launches;
+   }
+   return HS_OK;
+}
+
 /* ONE CHUNK: the candidates Y[0 .. cc) - a call of its own in everything but the entry: ONE upload, hs_cm_launches(..) launches whatever
  * cc and the number of blocks are, ONE read-back, the copy-out to lmin (rows of nb) and lpviol (may be NULL) of these candidates */
 int cm_chunk(hipsdp_solver* s, int m, int nb, const CmBlocks& P, int q, const double* Dext, int cc, const double* Y, double* lmin, double* lpviol)
 {
    CmRun R;
-   HS_CALL( cm_begin(s, m, P, cc, Y, true, &R) );
+   HS_CALL( cm_begin(s, m, P, cc, Y, true, 2, cm_layout, &R) );
    const hs_solver_cut_ws& w = R.w;
    const hs_cm_layout& L = R.L;
-   hipStream_t st = w.stream;
    const int nsv = (int) P.ids.size();
-   const hs_cm_blk* db = reinterpret_cast<const hs_cm_blk*>(w.dev + L.blks);
-   if ( P.nsmall > 0 )
-   {
-      HS_CALL( hs_lmin_many_small(st, P.nsmall, cc, P.nmax_small, w.djobs, db) );
-      ++R.launches;
-   }
-   if ( P.nmid > 0 )
-   {
-      const int cus = hs_device_cus();
-      HS_CALL( hs_lmin_many_mid(st, P.nmid, cc, P.nmax_mid, cus > 0 ? cus : 256, w.djobs + P.nsmall, db + P.nsmall) );
-      ++R.launches;
-   }
-   if ( P.nlarge > 0 )
-   {
-      const int jobs = P.nlarge * cc;
-      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
-      const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
-      HS_CALL( hs_ecl_clear(st, jobs, dsx) );
-      HS_CALL( hs_syevx_many_cols(st, jobs, P.nmax_large, hs_syevx_many_cap(jobs), dsx, dact) );
-      HS_CALL( hs_syevx_many_select(st, jobs, P.nmax_large, 0, dsx, dact) );
-      R.launches += 1 + (P.nmax_large - 1) + 3;
-   }
-   HS_CALL( hs_cm_result(st, nsv, cc, m, q, Dext, db, w.dev + L.Yg, w.dev + L.res) );
+   /* the third class closes with the selection of eigenvalue 1: 3 launches */
+   HS_CALL( cm_eigenvalues(P, cc, hs_lmin_many_small, hs_lmin_many_mid, [](hipStream_t st, int jobs, int nmax, const hs_sxm_job* dsx, const int* dact)
+      { return hs_syevx_many_select(st, jobs, nmax, 0, dsx, dact); }, 3, &R) );
+   HS_CALL( hs_cm_result(w.stream, nsv, cc, m, q, Dext, reinterpret_cast<const hs_cm_blk*>(w.dev + L.blks), w.dev + L.Yg, w.dev + L.res) );
    ++R.launches;
    if ( R.launches != hs_cm_launches(nsv > 0, P.nsmall > 0, P.nmid > 0, P.nmax_large) )
       return HIPSDP_ERR_NUMERIC;
-   hs_cut_res none;
-   memset(&none, 0, sizeof(none));
-   none.ints = none.sup = -1;
-   hs_sc_out h;
-   HS_CALL( cut_readback(w, none, L.len, R.launches, &g_cm, &h) );
+   HS_CALL( chunk_readback(w, L.len, R.launches, &g_cm) );
    const double* res = w.pin + L.res;
    for (int c = 0; c < cc; ++c)
    {
@@ -1051,18 +1126,13 @@ int check_y_many_impl(hipsdp_solver* s, int count, const double* Y, double* lmin
       return HIPSDP_ERR_ARG;
    if ( count == 0 )
       return HIPSDP_OK;
-   if ( served != NULL )
-      for (int b = 0; b < nb; ++b)
-         served[b] = -1;
    int q = 0;
    const double* Dext = NULL;
-   if ( !hs_solver_lp_rows(s, &q, &Dext) )
-      return HIPSDP_OK;
    CmBlocks P;
-   HS_CALL( cm_served(s, &P) );
-   if ( served != NULL )
-      for (int b : P.ids)
-         served[b] = 0;
+   bool go = false;
+   HS_CALL( cm_enter(s, nb, served, &P, &q, &Dext, &go) );
+   if ( !go )
+      return HIPSDP_OK;
    if ( P.ids.empty() && q == 0 )
    {
       if ( lpviol != NULL )
@@ -1070,11 +1140,8 @@ int check_y_many_impl(hipsdp_solver* s, int count, const double* Y, double* lmin
             lpviol[j] = 0.0;
       return HIPSDP_OK;
    }
-   /* what a candidate takes of the workspace: its matrices, its eigenvalues, its point, its jobs and its row of the result */
-   long long per = (long long) m + (long long) P.nlarge * (SCLR_JOBW + 1) + 3LL * P.ids.size() + 1;
-   for (int b : P.ids)
-      per += cm_mat_len(hs_solver_block_n(s, b));
-   const std::vector<long long> job_len((size_t) count, per);
+   /* per served block two doubles of eigenvalues and lmin in the candidate's row of the result, which ends with lpviol */
+   const std::vector<long long> job_len((size_t) count, cm_candidate_len(s, m, P, 2, 1) + 1);
    HS_CALL( hs_chunks_run(job_len.data(), count, SCLR_BUDGET, hs_chunk_env("HIPSDP_CHECK_MANY_CHUNK"), [&](int start, int end)
       {
          return cm_chunk(s, m, nb, P, q, Dext, end - start, Y + (size_t) start * m, lmin + (size_t) start * nb,
@@ -1100,10 +1167,8 @@ int hs_check_many_form_z(hipsdp_solver* s, int count, const double* Y, double* Z
    if ( P.ids.empty() )
       return HIPSDP_OK;
    CmRun R;
-   HS_CALL( cm_begin(s, m, P, count, Y, false, &R) );
-   std::vector<long long> off((size_t) nb + 1, 0);
-   for (int b = 0; b < nb; ++b)
-      off[b + 1] = off[b] + (long long) hs_solver_block_n(s, b) * hs_solver_block_n(s, b);
+   HS_CALL( cm_begin(s, m, P, count, Y, false, 2, cm_layout, &R) );
+   const std::vector<long long> off = block_sums(s, nb, NULL, n_full);
    for (size_t k = 0; k < P.ids.size(); ++k)
    {
       const int b = P.ids[k], n = hs_solver_block_n(s, b);
@@ -1146,17 +1211,14 @@ long long rf_large_ws(int n) { return (long long) hs_syevr_ws(n); }
 long long rf_large_out(int n) { return HS_SYEVR_OUT(n); }
 const hs_rf_rules RF_RULES = {rf_small_scratch, rf_large_ws, rf_large_out};
 
-/* off[b] = n_0 + .. + n_{b-1}, voff[b] = n_0^2 + .. + n_{b-1}^2 ([nb]: the totals) */
-void rf_offsets(const hipsdp_solver* s, int nb, std::vector<long long>* off, std::vector<long long>* voff)
+/* how many of the items [start, end) of a chunk, which descend in n, are above HS_RF_SMALLN rows: the leading ones */
+template <class Item>
+int rf_count_large(const std::vector<Item>& items, int start, int end)
 {
-   off->assign((size_t) nb + 1, 0);
-   voff->assign((size_t) nb + 1, 0);
-   for (int b = 0; b < nb; ++b)
-   {
-      const long long n = hs_solver_block_n(s, b);
-      (*off)[b + 1] = (*off)[b] + n;
-      (*voff)[b + 1] = (*voff)[b] + n * n;
-   }
+   int nlarge = 0;
+   while ( start + nlarge < end && items[(size_t) start + nlarge].n > HS_RF_SMALLN )
+      ++nlarge;
+   return nlarge;
 }
 
 /* the caller's arrays of hipsdp_rounding_frame */
@@ -1171,11 +1233,7 @@ struct RfArgs
 int rf_chunk(hipsdp_solver* s, int m, const std::vector<hs_rf_item>& items, int start, int end, const RfArgs& a, const hs_round_frame& F,
    const std::vector<long long>& off, const std::vector<long long>& voff)
 {
-   const int cnt = end - start, nb = (int) off.size() - 1;
-   int nlarge = 0;
-   while ( nlarge < cnt && items[(size_t) start + nlarge].n > HS_RF_SMALLN )
-      ++nlarge;
-   const int nsmall = cnt - nlarge;
+   const int cnt = end - start, nb = (int) off.size() - 1, nlarge = rf_count_large(items, start, end), nsmall = cnt - nlarge;
    std::vector<int> ids((size_t) cnt);
    std::vector<hs_rf_block> blk((size_t) cnt);
    std::vector<long long> at((size_t) cnt), row0((size_t) cnt), vec0((size_t) cnt), trip0((size_t) cnt);
@@ -1224,11 +1282,9 @@ int rf_chunk(hipsdp_solver* s, int m, const std::vector<hs_rf_item>& items, int 
       J.row0 = row0[k]; J.vec0 = vec0[k];
       if ( k < nlarge )
       {
-         HS_CALL( hs_syevx_many_job(n, base + blk[k].ws, base + blk[k].out, &hsx[k]) );      /* (its selection output is not used) */
+         /* (the selection output of the first is not used) */
+         HS_CALL( sxm_job(hs_syevx_many_job, n, base + blk[k].ws, base + blk[k].out, HS_SXM_ACTIVE, &hsx[k], &hact[k]) );
          HS_CALL( hs_syevr_many_job(n, base + blk[k].ws, base + blk[k].out, &hsr[k]) );
-         if ( hsx[k].A != base + blk[k].ws )
-            return HIPSDP_ERR_NUMERIC;
-         hact[k] = HS_SXM_ACTIVE;
          hs_ppl_job& T = hppl[k];
          memset(&T, 0, sizeof(T));
          T.n = n; T.nnz = (int) it.nnz; T.ntc = (n + HS_RF_TILE - 1) / HS_RF_TILE; T.trip = trip0[k];
@@ -1283,11 +1339,7 @@ int rf_chunk(hipsdp_solver* s, int m, const std::vector<hs_rf_item>& items, int 
    launches += 4;
    if ( launches != hs_rf_launches(nsmall > 0, nlarge > 0 ? items[(size_t) start].n : 0) )
       return HIPSDP_ERR_NUMERIC;
-   hs_cut_res none;
-   memset(&none, 0, sizeof(none));
-   none.ints = none.sup = -1;
-   hs_sc_out h;
-   HS_CALL( cut_readback(w, none, L.len, launches, &g_rf, &h) );
+   HS_CALL( chunk_readback(w, L.len, launches, &g_rf) );
    for (int k = 0; k < cnt; ++k)
    {
       const hs_rf_item& it = items[(size_t) start + k];
@@ -1344,8 +1396,8 @@ int rounding_frame_impl(hipsdp_solver* s, const RfArgs& a, int* served)
       F->valid = 1;                    /* (a frame that holds no block: stage 2 serves none) */
       return HIPSDP_OK;
    }
-   std::vector<long long> off, voff;
-   rf_offsets(s, nb, &off, &voff);
+   /* where a block's eigenvalues and its vectors start in the frame and in the caller's arrays */
+   const std::vector<long long> off = block_sums(s, nb, NULL, n_rows), voff = block_sums(s, nb, NULL, n_full);
    HS_CALL( hs_solver_round_frame(s, off[nb] + voff[nb], &F) );
    std::vector<long long> len(items.size());
    for (size_t k = 0; k < items.size(); ++k)
@@ -1370,11 +1422,7 @@ struct Rf2Item { int blk, n, cap; };
 int rf2_chunk(hipsdp_solver* s, const std::vector<Rf2Item>& items, int start, int end, const double* lambda, double epsilon, int mode,
    hipsdp_rounding_out* out, const hs_round_frame& F, const std::vector<long long>& off, const std::vector<long long>& voff, bool* overflow)
 {
-   const int cnt = end - start, nb = (int) off.size() - 1;
-   int nlarge = 0;
-   while ( nlarge < cnt && items[(size_t) start + nlarge].n > HS_RF_SMALLN )
-      ++nlarge;
-   const int nsmall = cnt - nlarge;
+   const int cnt = end - start, nb = (int) off.size() - 1, nlarge = rf_count_large(items, start, end), nsmall = cnt - nlarge;
    std::vector<long long> row0((size_t) cnt), int0((size_t) cnt), mat0((size_t) cnt);
    long long rows = 0, cap_small = 0, cap_large = 0, ints_len = 0, mats_len = 0;
    int nmax_small = 0;
@@ -1450,11 +1498,7 @@ int rf2_chunk(hipsdp_solver* s, const std::vector<Rf2Item>& items, int start, in
    }
    if ( launches != hs_rf2_launches(nsmall > 0, nlarge > 0) )
       return HIPSDP_ERR_NUMERIC;
-   hs_cut_res none;
-   memset(&none, 0, sizeof(none));
-   none.ints = none.sup = -1;
-   hs_sc_out h;
-   HS_CALL( cut_readback(w, none, L.len, launches, &g_rf, &h) );
+   HS_CALL( chunk_readback(w, L.len, launches, &g_rf) );
    for (int cls = 0; cls < 2; ++cls)
    {
       const int k0 = cls == 0 ? 0 : nlarge, k1 = cls == 0 ? nlarge : cnt;
@@ -1488,7 +1532,9 @@ int rf2_chunk(hipsdp_solver* s, const std::vector<Rf2Item>& items, int start, in
    return HIPSDP_OK;
 }
 
-int rounding_recombine_impl(hipsdp_solver* s, const double* lambda, double epsilon, int mode, hipsdp_rounding_out* out)
+}
+
+extern "C" int hipsdp_rounding_recombine(hipsdp_solver* s, const double* lambda, double epsilon, int mode, hipsdp_rounding_out* out)
 {
    int m = 0, nb = 0;
    if ( !hs_solver_dims(s, &m, &nb) || lambda == NULL || out == NULL || mode < 0 || mode > 1 )
@@ -1510,8 +1556,8 @@ int rounding_recombine_impl(hipsdp_solver* s, const double* lambda, double epsil
    if ( items.empty() )
       return HIPSDP_OK;
    std::stable_sort(items.begin(), items.end(), [](const Rf2Item& x, const Rf2Item& y) { return x.n > y.n; });
-   std::vector<long long> off, voff, len(items.size());
-   rf_offsets(s, nb, &off, &voff);
+   const std::vector<long long> off = block_sums(s, nb, NULL, n_rows), voff = block_sums(s, nb, NULL, n_full);
+   std::vector<long long> len(items.size());
    for (size_t k = 0; k < items.size(); ++k)
       len[k] = hs_rf2_item_len(items[k].n, items[k].cap);
    bool overflow = false;
@@ -1521,17 +1567,10 @@ int rounding_recombine_impl(hipsdp_solver* s, const double* lambda, double epsil
    return overflow ? HIPSDP_ERR_ARG : HIPSDP_OK;
 }
 
-}
-
 extern "C" int hipsdp_rounding_frame(hipsdp_solver* s, const int* xnnz, const int* const* xrow, const int* const* xcol,
    const double* const* xval, double* eigvals, double* obj, double* coefs, double* vecs, int* served)
 {
    return rounding_frame_impl(s, RfArgs{xnnz, xrow, xcol, xval, eigvals, obj, coefs, vecs}, served);
-}
-
-extern "C" int hipsdp_rounding_recombine(hipsdp_solver* s, const double* lambda, double epsilon, int mode, hipsdp_rounding_out* out)
-{
-   return rounding_recombine_impl(s, lambda, epsilon, mode, out);
 }
 
 extern "C" int hipsdp_rounding_stats(long long* calls, long long* launches, long long* readbacks)
@@ -1542,19 +1581,23 @@ extern "C" int hipsdp_rounding_stats(long long* calls, long long* launches, long
 namespace {
 
 /* ---- hipsdp_rank1_check_many: eigenvalues 1, n - 1, n and the two scans over the 2 x 2 principal minors of every Z_b(Y[j]) (kernels:
- * rank1.hip, check_many.hip, eigi.hip, syevx.hip).  The served blocks, the chunks, the workspace and Z are those of hipsdp_check_y_many
- * (cm_served, cm_begin); what follows Z differs. ---------------------------------------------------------------------------------------- */
+ * rank1.hip, check_many.hip, eigi.hip, syevx.hip).  The served blocks, the chunks, the workspace, Z and the eigenvalue stage are those of
+ * hipsdp_check_y_many (cm_enter, cm_begin, cm_eigenvalues); the layout, the minors and the result differ. ------------------------------- */
 CutStats g_r1;
 
 /* where the four optional output groups of a chunk's candidates go (rows of nb blocks); a NULL pair is not copied out */
 struct R1Dst { double* lam; double* minorev; int* minorind; double* minordet; int* detind; };
+
+/* the layout of hipsdp_rank1_check_many, as cm_begin takes it: four doubles per matrix of at most 128 rows in L.lam */
+void r1_layout(int m, int cc, int nsv, int nlarge, long long blocks_len, hs_cm_layout* L)
+{ hs_r1_layout_make(m, cc, HS_CM_G, nsv, nlarge, CM_BLKW, SCLR_JOBW, HS_R1_RESW, blocks_len, L); }
 
 /* ONE CHUNK: the candidates Y[0 .. cc): ONE upload, hs_r1_launches(..) launches whatever cc and the number of blocks are, ONE read-back.
  * The minors launch stands right behind Z(y): the column launches of the 129 .. 512 class consume their matrix. */
 int r1_chunk(hipsdp_solver* s, int m, int nb, const CmBlocks& P, int cc, const double* Y, double feastol, const R1Dst& d)
 {
    CmRun R;
-   HS_CALL( cm_begin(s, m, P, cc, Y, true, &R, 4) );
+   HS_CALL( cm_begin(s, m, P, cc, Y, true, 4, r1_layout, &R) );
    const hs_solver_cut_ws& w = R.w;
    const hs_cm_layout& L = R.L;
    hipStream_t st = w.stream;
@@ -1563,36 +1606,13 @@ int r1_chunk(hipsdp_solver* s, int m, int nb, const CmBlocks& P, int cc, const d
    double* dres = w.dev + L.res;
    HS_CALL( hs_r1_minors(st, nsv, cc, P.nmax, feastol, w.djobs, db, dres) );
    ++R.launches;
-   if ( P.nsmall > 0 )
-   {
-      HS_CALL( hs_lsel_many_small(st, P.nsmall, cc, P.nmax_small, w.djobs, db) );
-      ++R.launches;
-   }
-   if ( P.nmid > 0 )
-   {
-      const int cus = hs_device_cus();
-      HS_CALL( hs_lsel_many_mid(st, P.nmid, cc, P.nmax_mid, cus > 0 ? cus : 256, w.djobs + P.nsmall, db + P.nsmall) );
-      ++R.launches;
-   }
-   if ( P.nlarge > 0 )
-   {
-      const int jobs = P.nlarge * cc;
-      const hs_sxm_job* dsx = reinterpret_cast<const hs_sxm_job*>(w.dev + L.jobs);
-      const int* dact = reinterpret_cast<const int*>(w.dev + L.act);
-      HS_CALL( hs_ecl_clear(st, jobs, dsx) );
-      HS_CALL( hs_syevx_many_cols(st, jobs, P.nmax_large, hs_syevx_many_cap(jobs), dsx, dact) );
-      HS_CALL( hs_syevx_many_index(st, jobs, P.nmax_large, dsx, dact) );
-      R.launches += 1 + (P.nmax_large - 1) + 1;
-   }
+   /* the third class closes with the three indexed eigenvalues alone: 1 launch */
+   HS_CALL( cm_eigenvalues(P, cc, hs_lsel_many_small, hs_lsel_many_mid, hs_syevx_many_index, 1, &R) );
    HS_CALL( hs_r1_result(st, nsv, cc, w.djobs, db, dres) );
    ++R.launches;
    if ( R.launches != hs_r1_launches(nsv > 0, P.nsmall > 0, P.nmid > 0, P.nmax_large) )
       return HIPSDP_ERR_NUMERIC;
-   hs_cut_res none;
-   memset(&none, 0, sizeof(none));
-   none.ints = none.sup = -1;
-   hs_sc_out h;
-   HS_CALL( cut_readback(w, none, L.len, R.launches, &g_r1, &h) );
+   HS_CALL( chunk_readback(w, L.len, R.launches, &g_r1) );
    const double* res = w.pin + L.res;
    for (int c = 0; c < cc; ++c)
       for (int k = 0; k < nsv; ++k)
@@ -1624,25 +1644,14 @@ int rank1_check_many_impl(hipsdp_solver* s, int count, const double* Y, double f
       return HIPSDP_ERR_ARG;
    if ( count == 0 )
       return HIPSDP_OK;
-   if ( served != NULL )
-      for (int b = 0; b < nb; ++b)
-         served[b] = -1;
-   int q = 0;
+   int q = 0;                                              /* (the LP rows are not looked at) */
    const double* Dext = NULL;
-   if ( !hs_solver_lp_rows(s, &q, &Dext) )                  /* a communicator or sharded matrices: nothing is served */
-      return HIPSDP_OK;
    CmBlocks P;
-   HS_CALL( cm_served(s, &P) );
-   if ( served != NULL )
-      for (int b : P.ids)
-         served[b] = 0;
-   if ( P.ids.empty() )
+   bool go = false;
+   HS_CALL( cm_enter(s, nb, served, &P, &q, &Dext, &go) );
+   if ( !go || P.ids.empty() )
       return HIPSDP_OK;
-   /* what a candidate takes of the workspace: its matrices, its eigenvalues, its point, its jobs and its rows of the result */
-   long long per = (long long) m + (long long) P.nlarge * (SCLR_JOBW + 1) + (4LL + HS_R1_RESW) * P.ids.size();
-   for (int b : P.ids)
-      per += cm_mat_len(hs_solver_block_n(s, b));
-   const std::vector<long long> job_len((size_t) count, per);
+   const std::vector<long long> job_len((size_t) count, cm_candidate_len(s, m, P, 4, HS_R1_RESW));
    HS_CALL( hs_chunks_run(job_len.data(), count, SCLR_BUDGET, hs_chunk_env("HIPSDP_RANK1_CHUNK"), [&](int start, int end)
       {
          const size_t o = (size_t) start * nb;
@@ -1700,21 +1709,18 @@ int r1a_chunk(hipsdp_solver* s, int m, const std::vector<int>& ids, const double
       for (int j = nlg; j < cnt; ++j)
          if ( hs_syev_many_class(hs_solver_block_n(s, ids[j])) == cls )
             order.push_back(ids[j]);
-   std::vector<long long> start((size_t) cnt), cvoff((size_t) cnt), croff((size_t) cnt), zoff((size_t) cnt);
-   long long blocks_len = 0, vec_len = 0, rhs_len = 0;
    for (int j = 0; j < cnt; ++j)
    {
-      const int n = hs_solver_block_n(s, order[j]);
-      nmax = std::max(nmax, n);
+      nmax = std::max(nmax, hs_solver_block_n(s, order[j]));
       if ( j < nlg )
-         nmax_large = std::max(nmax_large, n);
-      start[j] = blocks_len; cvoff[j] = vec_len; croff[j] = rhs_len;
-      blocks_len += r1a_block_len(n);
-      vec_len += n;
-      rhs_len += (long long) n * (n + 1) / 2;
+         nmax_large = std::max(nmax_large, hs_solver_block_n(s, order[j]));
    }
+   /* where a block's part of the workspace, its vector and its right-hand side start in the chunk */
+   const std::vector<long long> start = block_sums(s, cnt, order.data(), r1a_block_len), cvoff = block_sums(s, cnt, order.data(), n_rows),
+      croff = block_sums(s, cnt, order.data(), n_tri);
+   std::vector<long long> zoff((size_t) cnt);
    hs_r1a_layout L;
-   hs_r1a_layout_make(m, cnt, nsm, R1A_TABW, SCLR_SJOBW, SCLR_JOBW, vec_len, rhs_len, blocks_len, &L);
+   hs_r1a_layout_make(m, cnt, nsm, R1A_TABW, SCLR_SJOBW, SCLR_JOBW, cvoff[cnt], croff[cnt], start[cnt], &L);
    for (int j = 0; j < cnt; ++j)
       zoff[j] = L.blocks + start[j] + (j < nlg ? cm_large_block(hs_solver_block_n(s, order[j])).ws : 0);
    hs_solver_cut_ws w;
@@ -1735,10 +1741,7 @@ int r1a_chunk(hipsdp_solver* s, int m, const std::vector<int>& ids, const double
       if ( j < nlg )
       {
          const hs_ecl_block E = cm_large_block(n);
-         HS_CALL( hs_syevx_many_job(n, base + E.ws, base + E.out, &hsx[j]) );
-         if ( hsx[j].A != base + E.ws )
-            return HIPSDP_ERR_NUMERIC;
-         hact[j] = HS_SXM_ACTIVE | HS_SXM_VEC;
+         HS_CALL( sxm_job(hs_syevx_many_job, n, base + E.ws, base + E.out, HS_SXM_ACTIVE | HS_SXM_VEC, &hsx[j], &hact[j]) );
          T.lam = base + E.out + HS_SYEVX_OUT_LAM; T.vec = base + E.out + HS_SYEVX_OUT_VEC; T.sign = -1.0;
          continue;
       }
@@ -1766,11 +1769,7 @@ int r1a_chunk(hipsdp_solver* s, int m, const std::vector<int>& ids, const double
    ++launches;
    if ( launches != hs_r1a_launches(nsm > 0, nmax_large) )
       return HIPSDP_ERR_NUMERIC;
-   hs_cut_res none;
-   memset(&none, 0, sizeof(none));
-   none.ints = none.sup = -1;
-   hs_sc_out h;
-   HS_CALL( cut_readback(w, none, L.len, launches, &g_r1a, &h) );
+   HS_CALL( chunk_readback(w, L.len, launches, &g_r1a) );
    for (int j = 0; j < cnt; ++j)
    {
       const int b = order[j], n = hs_solver_block_n(s, b);
@@ -1797,13 +1796,7 @@ int rank1_approx_impl(hipsdp_solver* s, const double* y, const int* want, double
    if ( ids.empty() )
       return HIPSDP_OK;
    std::stable_sort(ids.begin(), ids.end(), [&](int a, int c) { return hs_solver_block_n(s, a) > hs_solver_block_n(s, c); });
-   std::vector<long long> voff((size_t) nb + 1, 0), roff((size_t) nb + 1, 0);
-   for (int b = 0; b < nb; ++b)
-   {
-      const long long n = hs_solver_block_n(s, b);
-      voff[b + 1] = voff[b] + n;
-      roff[b + 1] = roff[b] + n * (n + 1) / 2;
-   }
+   const std::vector<long long> voff = block_sums(s, nb, NULL, n_rows), roff = block_sums(s, nb, NULL, n_tri);
    const int total = (int) ids.size();
    std::vector<long long> job_len((size_t) total);
    for (int k = 0; k < total; ++k)

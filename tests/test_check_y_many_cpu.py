@@ -82,7 +82,11 @@ def test_argument_errors_and_the_totals_without_a_device(hb):
     src = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
     body = src[src.index("int check_y_many_impl("):src.index("int hs_check_many_form_z(")]
     assert body.count("return HIPSDP_ERR_ARG") == 1
-    assert body.index("return HIPSDP_ERR_ARG") < body.index("hs_solver_lp_rows(") < body.index("cm_served(") < body.index("cm_chunk(")
+    assert body.index("return HIPSDP_ERR_ARG") < body.index("cm_enter(") < body.index("cm_chunk(")
+    # ... and the shared entry of the calls over candidate points looks at the device, in this order, and refuses nothing
+    entry = src[src.index("int cm_enter("):src.index("long long cm_candidate_len(")]
+    assert entry.index("hs_solver_lp_rows(") < entry.index("cm_served(")
+    assert "return HIPSDP_ERR_ARG" not in entry and "getenv" not in entry
     assert 'hs_chunk_env("HIPSDP_CHECK_MANY_CHUNK")' in body and "hs_chunks_run(" in body
 
 

@@ -26,3 +26,19 @@ def test_the_layouts_are_host_only_and_built_into_the_library():
     src = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
     for name in ("hs_ec_layout_make", "hs_sc_layout_make", "hs_scl_layout_make", "hs_cut_view"):
         assert name in src, name
+
+
+def test_the_tail_of_a_chunk_stands_once():
+    """one tail for every call and chunk, chunk_readback: the copy of the result range, the synchronise and the two counters stand once
+    in the file, cut_readback adds the view of a cut layout to it, and a chunk without a cut layout passes no dummy layout to get it"""
+    src = _read("scip-sdp_amd", "csrc", "cut_calls.hip")
+    assert src.count("stats->readbacks += 1") == 1 and src.count("stats->launches += launches") == 1
+    tail = src[src.index("int chunk_readback("):src.index("int cut_readback(")]
+    assert tail.index("hipMemcpyDeviceToHost") < tail.index("hipStreamSynchronize(") < tail.index("stats->launches += launches") \
+        < tail.index("stats->readbacks += 1")
+    assert tail.count("hipMemcpyAsync(") == 1 and tail.count("hipStreamSynchronize(") == 1 and "len.res_off" in tail and "len.res_len" in tail
+    view = src[src.index("int cut_readback("):src.index("int sxm_job(")]
+    assert view.index("chunk_readback(") < view.index("hs_cut_view(") and "hipStreamSynchronize" not in view
+    # the dummy layout (a zeroed hs_cut_res with ints = sup = -1) that five chunks once built for the tail's sake is gone
+    assert src.count("none.ints = none.sup") == 0 and "hs_cut_res none" not in src
+    assert src.count("chunk_readback(") >= 7
